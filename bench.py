@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — walker-lnprob evaluations/sec of the HIP hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR]
 
 With N > 1 and no WORLD_SIZE in the environment bench.py launches its own N rank processes (one per GPU, before the
 parent makes any GPU call), waits for them and exits with the first non-zero child code; rank 0 prints the line.  Under
@@ -50,6 +50,9 @@ Prints one JSON line on rank 0 (contract in the task description) with extra obj
                    before that rank touches the GPU; the other ranks wait for it in the rendezvous).
 `value` (the contract's K timed steps) is the authoritative figure; `sustained` is its >= 2 s cross-check and
 `ensemble_sampler` the same metric through the dependent half-steps of ONE ensemble (SURVEY.md 8(d) names both).
+
+--dump-outputs DIR writes what the last of the K timed steps computed (dump_outputs) as float64 .npy files.  The proposals
+come from --seed alone, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -80,6 +83,7 @@ FP64_VALU_PEAK_TFLOPS = 78.6   # MI355X fp64 vector peak (spec)
 BYTES_PER_EVAL_A = 48 + 8 + 4  # mode A: 6 fp64 parameters in, lnprob + status out
 BYTES_LTOT = 10001 * 8         # mode B adds the model light curve
 EVENT_EVERY = 4                # kernel duration is sampled with HIP events on every 4th launch of a timed region
+DUMP_CURVE_ROWS = 512          # --dump-outputs writes at most this many model light curves (512 x 10 001 fp64 = 41 MB)
 # |lnprob - reference| contract of SURVEY.md 8(c); points where the reference's default-tolerance LSODA run itself is off
 # by more than this are enumerated in the golden files (*_lsoda_noise_idx) and checked against the tight run instead
 REF_ATOL, REF_RTOL = 1.0e-5, 2.0e-6
@@ -592,8 +596,29 @@ def run_passes(c, config, scaling, steps, warmup, curve=False, nwalk=None, grb=N
         "check": {"lnprob0": float(full[0].item()), "n_not_ok": int((status[:n_local] != 0).sum().item()), "checksum": checksum},
     }
     c.last = {"lp": lp, "props": props, "launch": launch, "stream": stream, "truth": truth, "gen": gen, "x": x, "y": y,
-              "yerr": yerr, "grb": grb, "n_global": n_global, "n_local": n_local, "lo": lo, "hi": hi, "status": status}
+              "yerr": yerr, "grb": grb, "n_global": n_global, "n_local": n_local, "lo": lo, "hi": hi, "status": status,
+              "lnprob": results[total - 1, :n_global], "ltot": ltot}
     return res
+
+
+def dump_outputs(path, L, seed):
+    """--dump-outputs: what the last timed pass handed back, as float64 .npy files under `path`.  lnprob of every walker;
+    status (0 ok, otherwise the flag) of this rank's walkers; in mode B the model light curves of at most DUMP_CURVE_ROWS
+    of this rank's walkers, a seeded sample, with their walker indices in ltot_rows.  Must run before any later leg
+    launches into the same status buffer."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = L["n_local"]
+    out = {"lnprob": L["lnprob"], "status": L["status"][:n]}
+    if L["ltot"] is not None:
+        rows = np.arange(n)
+        if n > DUMP_CURVE_ROWS:
+            rows = np.sort(np.random.default_rng(seed).choice(n, DUMP_CURVE_ROWS, replace=False))
+        out["ltot"] = L["ltot"][torch.from_numpy(rows).to(L["ltot"].device)]
+        out["ltot_rows"] = L["lo"] + rows
+    for name, v in out.items():
+        v = v.cpu().numpy() if torch.is_tensor(v) else v
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def brief(r):
@@ -643,7 +668,12 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check: every rank joins the process group over gloo, all-reduces a one and rank 0 prints "
                          "{\"dry_run\": true, \"ranks_seen\": N}; no GPU work (runs on a box without a GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): lnprob, status, "
+                         "and with --curve ltot + ltot_rows (a seeded sample of at most %d walkers); rank 0 only" % DUMP_CURVE_ROWS)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a.gpus, sys.argv[1:]))            # before anything here has touched the GPU
@@ -730,6 +760,8 @@ def main():
     # ---- the headline leg (the contract's timed region)
     main_leg = run_passes(c, a.config, scaling, a.steps, a.warmup, curve=a.curve, nwalk=a.nwalk, grb=a.grb, spin_up=a.spin_up)
     L = c.last
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, L, a.seed)
     lp, launch, stream, truth, gen = L["lp"], L["launch"], L["stream"], L["truth"], L["gen"]
     x, y, yerr, n_global = L["x"], L["y"], L["yerr"], L["n_global"]
 

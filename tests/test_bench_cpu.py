@@ -55,6 +55,12 @@ def test_single_process_needs_no_group():
     assert r.returncode == 0 and json.loads(r.stdout.strip())["ranks_seen"] == 1
 
 
+def test_steps_must_time_at_least_one_step():
+    """--steps K is the number of timed steps: K = 0 (nothing to time) is refused before any GPU work."""
+    r = _run(["--steps", "0", "--dump-outputs", "unused"])
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr and not r.stdout.strip()
+
+
 def test_self_launch_eight_ranks():
     """The driver's largest form (N = 8; BASELINE configs[3]) through bench.py's own launcher: eight rank processes
     rendezvous over 127.0.0.1, rank 0 prints the one line.  (On the GPU boxes of this pool at most six processes may share the

@@ -448,3 +448,45 @@ def test_bench_self_launch_two_ranks():
     assert d["configs"]["4_strong"]["n_walk_total"] == 8192 and d["configs"]["4_strong"]["n_walk_per_gpu"] == 4096
     assert d["configs"]["5_strong"]["n_walk_total"] == 4096 and d["configs"]["5_strong"]["n_not_ok"] == 0
     assert "gloo" in d["config"]["parallelism"]
+
+
+def test_bench_dump_outputs(tmp_path, gsynth):
+    """`bench.py --dump-outputs DIR`: the last timed step's lnprob and status as float64 .npy files, identical in two runs
+    with the same arguments, and equal to a fresh evaluation of that step's proposals; with --curve also a seeded sample
+    of 512 of the 1 024 model light curves and their walker indices."""
+    import json
+    import subprocess
+    import sys
+
+    import torch
+
+    from magprop_amd import LogProb
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--spin-up", "0",
+            "--no-cpu-baseline", "--no-extra", "--no-mcmc"]
+    runs = {}
+    for tag, extra in (("a", []), ("b", []), ("curve", ["--curve"])):
+        r = subprocess.run(args + extra + ["--dump-outputs", str(tmp_path / tag)], env=env, capture_output=True, text=True,
+                           timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        runs[tag] = json.loads(lines[0]), {f[:-4]: np.load(tmp_path / tag / f) for f in os.listdir(tmp_path / tag)}
+    d, o = runs["a"]
+    assert d["steps"] == 3 and sorted(o) == ["lnprob", "status"]
+    assert all(v.dtype == np.float64 and v.shape == (1024,) for v in o.values())
+    assert o["lnprob"][0] == d["check"]["lnprob0"] and np.sum(o["status"] != 0) == d["check"]["n_not_ok"] == 0
+    assert all(np.array_equal(o[k], runs["b"][1][k]) for k in o)
+    # the last of the warmup + steps = 4 passes, drawn as bench.py draws them
+    gen = torch.Generator(device="cuda:0").manual_seed(20261003)
+    truth = torch.tensor(TRUTHS["Humped"], dtype=torch.float64, device="cuda:0")
+    props = truth + 1.0e-4 * torch.randn(4, 1024, 6, dtype=torch.float64, device="cuda:0", generator=gen)
+    lp = LogProb(gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"], device=0)
+    np.testing.assert_allclose(o["lnprob"], lp(props[3].cpu().numpy()), rtol=1e-12, atol=0.0)
+    d, o = runs["curve"]
+    assert sorted(o) == ["lnprob", "ltot", "ltot_rows", "status"] and o["lnprob"][0] == d["check"]["lnprob0"]
+    assert o["ltot"].shape == (512, 10001) and o["ltot"].dtype == np.float64 and o["ltot_rows"].shape == (512,)
+    rows = o["ltot_rows"].astype(int)
+    assert np.array_equal(rows, o["ltot_rows"]) and np.all(np.diff(rows) > 0) and 0 <= rows[0] and rows[-1] < 1024
+    assert np.all(np.isfinite(o["ltot"])) and np.all(o["ltot"] >= 0.0)
+    assert sum(os.path.getsize(tmp_path / "curve" / (k + ".npy")) for k in o) <= 64 * 2 ** 20
