@@ -227,6 +227,31 @@ int mp_rhs_batch(mp_handle *h, const double *pars, int ndim, const double *t, co
                  double *lam);
 
 /*
+ * Posterior-predictive band of the model light curves (ABI 5, additive): per grid point the quantiles q[nq] of the curves
+ * of n parameter rows, computed on the device.  The reference's post-processing takes percentiles of the PARAMETERS and
+ * draws one curve at their medians (code/synthetic_datasets/plot_synth.py:143-206); this is the band over the samples.
+ *   pars[n][ndim]  host rows; physical = 0: sampler coordinates, prior and log_mask of mp_set_prior applied exactly as in
+ *                  mp_lnprob_batch (ndim = 0 there: no prior); physical = 1: physical parameters taken as given (mp_model_lc)
+ *   q[nq]          each finite and in [0, 1], any order; 1 <= nq <= MP_BAND_MAX_Q
+ *   components     non-empty mask of MP_BAND_LTOT | MP_BAND_LPROP | MP_BAND_LDIP
+ *   band_out       [k][nq][n_grid]: k over the set component bits in ascending order, j over q in the caller's order
+ *   status_out[n]  (optional) what mp_lnprob_batch reports for these rows; *n_used (optional) the rows with MP_STATUS_OK
+ * Per grid point the result is np.nanquantile(curves, q, axis=0) (method "linear") bit for bit, where rows that did not
+ * finish are NaN; no row finished: all NaN and MP_OK.  The curves come from ONE launch of the curve kernels (the build
+ * kernel_spl_curves(n) names, as mp_lnprob_batch(..., ltot_out) runs for the same n rows), without a dataset.  Host
+ * buffers; returns when the results are in them.  A multi-device handle runs the call on its first device.
+ * Workspace: up to n * n_grid * (components + 1) doubles on the device (5.2 GB at the cap with all three components),
+ * owned by the handle, grow-only, freed by mp_destroy.
+ */
+#define MP_BAND_MAX_SAMPLES 16384
+#define MP_BAND_MAX_Q 16
+#define MP_BAND_LTOT 1u
+#define MP_BAND_LPROP 2u
+#define MP_BAND_LDIP 4u
+int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physical, const double *q, int nq, uint32_t components,
+                  double *band_out, int32_t *status_out, int32_t *n_used);
+
+/*
  * Ensemble sampler: emcee's affine-invariant stretch move (Goodman & Weare 2010) with a random red/blue
  * split per step, as driven by code/synthetic_datasets/synth_mcmc.py:175-185
  * (em.EnsembleSampler(Nwalk, Npars, lnprob, ...).run_mcmc(pos, Nstep)).  Positions, log-posteriors,

@@ -18,6 +18,9 @@ MP_OK, MP_EINVAL, MP_EHIP, MP_ERANGE, MP_ENODEV, MP_ESTATE = 0, -1, -2, -3, -4, 
 STATUS_OK, STATUS_FLAG, STATUS_NONFINITE, STATUS_PRIOR, STATUS_BADDATASET = 0, 1, 2, 3, 4
 MAX_NDIM = 9
 MAX_DATASETS = 64
+BAND_MAX_SAMPLES, BAND_MAX_Q = 16384, 16                      # include/magprop_amd.h MP_BAND_*
+BAND_LTOT, BAND_LPROP, BAND_LDIP = 1, 2, 4
+BAND_COMPONENTS = {"Ltot": BAND_LTOT, "Lprop": BAND_LPROP, "Ldip": BAND_LDIP}
 
 EXPORTS = (
     "mp_abi_version", "mp_last_error", "mp_cfg_synth", "mp_cfg_lib", "mp_create", "mp_destroy",
@@ -27,7 +30,7 @@ EXPORTS = (
     "mp_sampler_get_bad", "mp_sampler_n_slots", "mp_sampler_row_doubles", "mp_sampler_halfstep_shard",
     "mp_sampler_halfstep_apply", "mp_sampler_step_blocks", "mp_sampler_step_row_doubles", "mp_sampler_step_shard",
     "mp_sampler_step_apply", "mp_sampler_state_ptrs", "mp_sweep_tol", "mp_n_simd", "mp_last_sweeps", "mp_last_tiles", "mp_tile_log", "mp_last_tile_log",
-    "mp_get_policy", "mp_create_multi", "mp_n_devices",
+    "mp_get_policy", "mp_create_multi", "mp_n_devices", "mp_model_band",
 )
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -131,6 +134,7 @@ def lib():
     L.mp_lnprob_batch_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.mp_model_lc.argtypes = [vp, dp, C.c_int, dp, dp, ip]
     L.mp_rhs_batch.argtypes = [vp, dp, C.c_int, dp, dp, C.c_int, dp, dp]
+    L.mp_model_band.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_uint32, dp, ip, ip]
     L.mp_synchronize.argtypes = [vp]
     L.mp_device.argtypes = [vp]
     L.mp_stream.argtypes = [vp]
@@ -172,7 +176,7 @@ def lib():
     L.mp_sampler_step_shard.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.mp_sampler_step_apply.argtypes = [vp, vp, vp, vp, vp]
     for name in ("mp_destroy", "mp_set_dataset", "mp_set_prior", "mp_lnprob_batch", "mp_lnprob_batch_dev",
-                 "mp_model_lc", "mp_rhs_batch", "mp_synchronize", "mp_device", "mp_n_grid", "mp_sampler_destroy",
+                 "mp_model_lc", "mp_model_band", "mp_rhs_batch", "mp_synchronize", "mp_device", "mp_n_grid", "mp_sampler_destroy",
                  "mp_sampler_set_positions", "mp_sampler_run", "mp_sampler_set_whole_step", "mp_sampler_get_state", "mp_sampler_get_bad",
                  "mp_sampler_n_slots", "mp_sampler_row_doubles", "mp_sampler_halfstep_shard",
                  "mp_sampler_halfstep_apply", "mp_sampler_step_blocks", "mp_sampler_step_row_doubles",
@@ -240,6 +244,32 @@ def whole_step_fits(whole_step_blocks, n_simd):
     rule of magprop_amd/csrc/mp_device.h stretch_whole_step_fits, restated for labels (tests/test_capi_cpu.py holds the two
     together)."""
     return 8 * int(whole_step_blocks) <= 19 * int(n_simd)
+
+
+def band_args(q, components):
+    """Validated (q as float64, component mask, component names in output order) of a band request (mp_model_band's limits)."""
+    qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+    if qa.ndim != 1 or not 1 <= qa.size <= BAND_MAX_Q:
+        raise ValueError(f"q must hold 1 to {BAND_MAX_Q} (MP_BAND_MAX_Q) quantiles, got shape {np.shape(q)}")
+    if not np.all((qa >= 0.0) & (qa <= 1.0)):
+        raise ValueError("every quantile in q must be finite and in [0, 1]")
+    names = (components,) if isinstance(components, str) else tuple(components)
+    if not names or any(c not in BAND_COMPONENTS for c in names) or len(set(names)) != len(names):
+        raise ValueError(f"components must be a non-empty selection of {tuple(BAND_COMPONENTS)} without repeats, got {components!r}")
+    mask = 0
+    for c in names:
+        mask |= BAND_COMPONENTS[c]
+    return qa, mask, tuple(c for c in BAND_COMPONENTS if mask & BAND_COMPONENTS[c])
+
+
+def band_rows(pars, ndim=None):
+    """pars as contiguous float64 rows (n, ndim), 1 <= n <= BAND_MAX_SAMPLES (mp_model_band's limit)."""
+    p = np.ascontiguousarray(pars, dtype=np.float64)
+    if p.ndim != 2 or (ndim is not None and p.shape[1] != ndim):
+        raise ValueError(f"pars must be 2-D (n, {ndim if ndim is not None else 'ndim'}), got shape {p.shape}")
+    if not 1 <= p.shape[0] <= BAND_MAX_SAMPLES:
+        raise ValueError(f"a band takes 1 to {BAND_MAX_SAMPLES} (MP_BAND_MAX_SAMPLES) rows, got {p.shape[0]}: thin the chain")
+    return p
 
 
 def _dptr(a):
@@ -347,6 +377,20 @@ class Handle:
         check(self._L.mp_model_lc(self._h, _dptr(p), int(p.size), _dptr(out), _dptr(traj), C.byref(st)),
               "mp_model_lc")
         return (st.value, out, traj) if want_traj else (st.value, out)
+
+    def model_band(self, pars, q, components=("Ltot",), physical=False):
+        """Quantiles q of the model light curves of the rows of pars over the handle's grid (mp_model_band): returns
+        (band[ncomp, nq, n_grid], status[n], n_used); components in the order Ltot, Lprop, Ldip whatever order they are
+        named in.  physical=False: sampler coordinates under the handle's prior, as lnprob_batch takes them."""
+        qa, mask, names = band_args(q, components)
+        p = band_rows(pars)
+        n, nd = p.shape
+        band = np.empty((len(names), qa.size, self.tgrid.size), dtype=np.float64)
+        st = np.empty(n, dtype=np.int32)
+        used = C.c_int32(0)
+        check(self._L.mp_model_band(self._h, _dptr(p), n, nd, int(bool(physical)), _dptr(qa), int(qa.size), C.c_uint32(mask),
+                                    _dptr(band), _iptr(st), C.byref(used)), "mp_model_band")
+        return band, st, int(used.value)
 
     def rhs_batch(self, pars, t, y, want_lam=False):
         """(dMdisc/dt, domega/dt) at n states: pars (n, ndim) physical, t (n,), y (n, 2) = (Mdisc, omega)."""

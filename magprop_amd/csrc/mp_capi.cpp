@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "mp_band.h"
 #include "mp_device.h"
 
 namespace {
@@ -123,6 +124,7 @@ struct mp_handle {
     std::vector<mp::DsDesc> desc;   // host mirror of d_ds
     // workspace of the host-buffer entry points
     DevBuf<double> w_pars, w_lnprob, w_curves;
+    DevBuf<double> w_band, w_band_out;   // mp_model_band: [components][n][n_grid] curves | [n_grid][n] transposed; [components][nq][n_grid]
     DevBuf<int32_t> w_dsid, w_status, w_sweeps;
     double last_mean_tiles = 0.0;
     bool tile_log_on = false;
@@ -522,6 +524,7 @@ int mp_destroy(mp_handle *h) {
     h->d_tgrid.release(); h->d_obs_dx.release(); h->d_obs_idt.release(); h->d_obs_y.release();
     h->d_obs_yerr.release(); h->d_obs_g.release(); h->d_tile_ptr.release(); h->d_ds.release();
     h->w_pars.release(); h->w_lnprob.release(); h->w_curves.release();
+    h->w_band.release(); h->w_band_out.release();
     h->w_dsid.release(); h->w_status.release(); h->w_sweeps.release(); h->w_tile_log.release();
     h->h_io.release();
     for (int i = 0; i < mp_handle::kOrderRing; ++i) {
@@ -776,6 +779,62 @@ int mp_model_lc(mp_handle *h, const double *pars, int ndim, double *out, double 
     HIP_TRY(hipMemcpyAsync(&stt, h->w_status.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (status) *status = stt;
+    return MP_OK;
+}
+
+int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physical, const double *q, int nq, uint32_t components,
+                  double *band_out, int32_t *status_out, int32_t *n_used) {
+    if (!h || !pars || !q || !band_out) return fail(MP_EINVAL, "mp_model_band: NULL argument");
+    if (n < 1 || n > MP_BAND_MAX_SAMPLES) return fail(MP_EINVAL, "mp_model_band: n must be 1..%d (MP_BAND_MAX_SAMPLES), got %d", MP_BAND_MAX_SAMPLES, n);
+    if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "mp_model_band: ndim must be 6..9, got %d", ndim);
+    if (nq < 1 || nq > MP_BAND_MAX_Q) return fail(MP_EINVAL, "mp_model_band: nq must be 1..%d (MP_BAND_MAX_Q), got %d", MP_BAND_MAX_Q, nq);
+    for (int j = 0; j < nq; ++j)
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(MP_EINVAL, "mp_model_band: q[%d] = %g is not in [0, 1]", j, q[j]);
+    const uint32_t all = MP_BAND_LTOT | MP_BAND_LPROP | MP_BAND_LDIP;
+    if (components == 0 || (components & ~all)) return fail(MP_EINVAL, "mp_model_band: components 0x%x is not a non-empty mask of MP_BAND_*", components);
+    if (!h->sub.empty()) return mp_model_band(h->sub[0], pars, n, ndim, physical, q, nq, components, band_out, status_out, n_used);
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    const size_t ng = h->tgrid.size(), rows = (size_t)n * ng;
+    const int ncomp = __builtin_popcount(components);
+    int rc;
+    if ((rc = h->w_pars.ensure((size_t)n * ndim)) || (rc = h->w_lnprob.ensure((size_t)n)) || (rc = h->w_status.ensure((size_t)n)) ||
+        (rc = h->w_band.ensure(rows * (size_t)(ncomp + 1))) || (rc = h->w_band_out.ensure((size_t)ncomp * nq * ng)))
+        return rc;
+    hipStream_t st = h->stream;
+    HIP_TRY(hipMemcpyAsync(h->w_pars.p, pars, sizeof(double) * (size_t)n * ndim, hipMemcpyHostToDevice, st));
+    mp::LaunchArgs a{};
+    a.pars = h->w_pars.p;
+    a.n = n;
+    a.ndim = ndim;
+    a.physical = physical ? 1 : 0;
+    a.want_chi2 = 0;                          // curves only: no dataset needed
+    a.lnprob = h->w_lnprob.p;
+    a.status = h->w_status.p;
+    double *curve[3] = {nullptr, nullptr, nullptr};
+    for (int c = 0, k = 0; c < 3; ++c)
+        if (components & (1u << c)) curve[c] = h->w_band.p + (size_t)k++ * rows;
+    a.ltot = curve[0];                        // rows of walkers that did not finish are NaN-filled by the kernel
+    a.lprop = curve[1];
+    a.ldip = curve[2];
+    if ((rc = launch_lnprob_ordered(h, a, st))) return rc;
+    mp::BandQ bq{};
+    for (int j = 0; j < nq; ++j) bq.q[j] = q[j];
+    bq.nq = nq;
+    double *cols = h->w_band.p + (size_t)ncomp * rows;
+    for (int c = 0, k = 0; c < 3; ++c) {
+        if (!curve[c]) continue;
+        int e = mp::launch_band_transpose(curve[c], cols, n, (int)ng, (void *)st);
+        if (!e) e = mp::launch_band_select(cols, n, (int)ng, bq, h->w_band_out.p + (size_t)k * nq * ng, (void *)st);
+        if (e) return fail(MP_EHIP, "band kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        ++k;
+    }
+    std::vector<int32_t> stt((size_t)n);
+    HIP_TRY(hipMemcpyAsync(band_out, h->w_band_out.p, sizeof(double) * (size_t)ncomp * nq * ng, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(stt.data(), h->w_status.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * (size_t)n);
+    if (n_used) *n_used = (int32_t)std::count(stt.begin(), stt.end(), (int32_t)MP_STATUS_OK);
     return MP_OK;
 }
 

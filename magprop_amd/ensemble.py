@@ -222,8 +222,43 @@ class EnsembleSampler:
     def acceptance_fraction(self):
         return self.get_last_sample()[2] / max(self.iteration, 1)
 
+    def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), discard=0, thin=1, ensemble=0):
+        """Posterior-predictive band over the stored chain: the quantiles q of the model light curves of the rows
+        chain[discard::thin, ensemble's walkers], evaluated on this sampler's handle (its prior, grid and configuration).
+        Returns {"t": grid, "Ltot": (nq, n_grid), ..., "n_used": rows that entered}."""
+        if self._target != 0:
+            raise ValueError("get_model_band needs the posterior target: a target='gaussian' sampler has no light curve")
+        qa, _, names = _capi.band_args(q, components)
+        rows = band_selection(self._chain, self.nwalkers, self.nensembles, discard, thin, ensemble)
+        band, _, used = self.handle.model_band(rows, qa, names)
+        out = {"t": self.handle.tgrid.copy()}
+        out.update({c: band[k] for k, c in enumerate(names)})
+        out["n_used"] = used
+        return out
+
     def get_autocorr_time(self, c=5.0, tol=50, quiet=False):
         """emcee's default (quiet=False) raises when the chain is shorter than tol autocorrelation times; the
         reference calls it bare (code/synthetic_datasets/synth_mcmc.py:220)."""
         from .mcmc_io import integrated_time
         return integrated_time(self._chain, c=c, tol=tol, quiet=quiet)
+
+
+def band_selection(chain, nwalkers, nensembles=1, discard=0, thin=1, ensemble=0):
+    """Rows chain[discard::thin, ensemble * nwalkers:(ensemble + 1) * nwalkers] of a stored chain (nsteps, nwalkers *
+    nensembles, ndim), flattened to (rows, ndim): what EnsembleSampler.get_model_band evaluates.  Raises ValueError for an
+    empty chain, a bad selection and one of more than _capi.BAND_MAX_SAMPLES rows."""
+    if chain is None or len(chain) == 0:
+        raise ValueError("the chain is empty: run_mcmc(..., store=True) first")
+    discard, thin, ensemble = int(discard), int(thin), int(ensemble)
+    if discard < 0 or thin < 1:
+        raise ValueError(f"discard must be >= 0 and thin >= 1, got discard={discard}, thin={thin}")
+    if not 0 <= ensemble < nensembles:
+        raise ValueError(f"ensemble must be in 0..{nensembles - 1}, got {ensemble}")
+    sel = chain[discard::thin, ensemble * nwalkers:(ensemble + 1) * nwalkers]
+    rows = sel.reshape(-1, chain.shape[-1])
+    if rows.shape[0] == 0:
+        raise ValueError(f"discard={discard} leaves no step of the {len(chain)} stored")
+    if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
+        raise ValueError(f"the selection holds {rows.shape[0]} rows, more than {_capi.BAND_MAX_SAMPLES} (MP_BAND_MAX_SAMPLES): "
+                         "raise thin or discard")
+    return rows

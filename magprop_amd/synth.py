@@ -69,3 +69,24 @@ def lnprob(pars, x, y, yerr, fbad=None, device=-1):
                 for r in rows:
                     f.write(", ".join(f"{v}" for v in r) + "\n")
     return out
+
+
+def model_band(samples, q=(0.025, 0.5, 0.975), components=("Ltot",), device=-1):
+    """Posterior-predictive band of the synthetic model: per point of the grid logspace(0, 6, 10001), the quantiles q of the
+    light curves of `samples` (rows in sampler coordinates, as a chain stores them; rows outside the prior or whose model
+    failed are left out, as np.nanquantile leaves out NaN).  The reference's plot_synth.py:143-206 takes percentiles of the
+    parameters and draws one curve at their medians instead.  Returns {"t": tarr, "Ltot": (nq, n_grid), ..., "n_used": rows
+    that entered}; a grid point no row reached is NaN."""
+    qa, _, names = _capi.band_args(q, components)
+    p = _capi.band_rows(samples, 6)
+    eng = engine.acquire(_cfg(), None, device)
+    try:
+        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
+        band, _, used = eng.handle.model_band(p, qa, names)
+        tarr = eng.handle.tgrid.copy()
+    finally:
+        engine.release(eng)
+    out = {"t": tarr}
+    out.update({c: band[k] for k, c in enumerate(names)})
+    out["n_used"] = used
+    return out
