@@ -282,6 +282,24 @@ int mp_sampler_set_whole_step(mp_sampler *s, int enable);
 /* any of the outputs may be NULL */
 int mp_sampler_get_state(mp_sampler *s, double *pos, double *lnprob, int64_t *n_accepted, int64_t *steps_done);
 /*
+ * Parallel tempering (ABI 5, additive; Earl & Deem 2005, Vousden, Farr & Mandel 2016).  The n_ensembles ensembles form
+ * n_ensembles / n_temps groups of n_temps: ensemble e is group e / n_temps at inverse temperature betas[e % n_temps], and all
+ * ensembles of a group must be on the same dataset.  The ladder: betas[0] == 1, strictly decreasing, every entry finite and
+ * > 0 (beta = 0 is refused: failed models have lnprob = -inf), n_temps >= 2.  Call before the first mp_sampler_set_positions
+ * (else MP_ESTATE); a bad ladder, n_ensembles % n_temps != 0 or mixed datasets in a group give MP_EINVAL.
+ * The move decides against prior x L^beta: (ndim - 1) ln z + beta lnprob(proposal) - beta lnprob(walker) > ln u (unfused;
+ * beta = 1 is the untempered test bit for bit).  After every step of mp_sampler_run each group runs one swap sweep, hottest
+ * pair first (t = n_temps - 1 .. 1): slot i of temperature t - 1 (walker perm[i] of that step's split) against slot i of
+ * temperature t, accepted if ln u < (beta_{t-1} - beta_t)(lnprob_hot - lnprob_cold), u from Philox keyed
+ * (seed; step, 2, cold walker, 0).  An accepted swap exchanges the two walkers' positions and lnprob (acceptance counters stay
+ * with the walkers); chain row s is the state after step s's swaps.  Stored and reported lnprob stay untempered.
+ * The walker-sharded entry points (mp_sampler_halfstep_*, mp_sampler_step_*) return MP_ESTATE on a tempered sampler.
+ */
+int mp_sampler_set_temperatures(mp_sampler *s, int n_temps, const double *betas);
+/* accepted swaps since the ladder was set, n_swaps_accepted[n_ensembles / n_temps][n_temps - 1] (pair t - 1, t at index t - 1);
+ * each pair is proposed n_walkers times per step.  MP_ESTATE on an untempered sampler. */
+int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted);
+/*
  * Proposals inside the prior whose model evaluation failed ('flag' / non-finite): what the reference's lnprob appends
  * to its `fbad` file (code/synthetic_datasets/mcmc_eqns.py:72-79).  The kernels collect them in a device-side window of
  * MP_BAD_WINDOW rows which the library drains into a host-side log (after every chunk of mp_sampler_run and in this

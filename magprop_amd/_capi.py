@@ -30,7 +30,7 @@ EXPORTS = (
     "mp_sampler_get_bad", "mp_sampler_n_slots", "mp_sampler_row_doubles", "mp_sampler_halfstep_shard",
     "mp_sampler_halfstep_apply", "mp_sampler_step_blocks", "mp_sampler_step_row_doubles", "mp_sampler_step_shard",
     "mp_sampler_step_apply", "mp_sampler_state_ptrs", "mp_sweep_tol", "mp_n_simd", "mp_last_sweeps", "mp_last_tiles", "mp_tile_log", "mp_last_tile_log",
-    "mp_get_policy", "mp_create_multi", "mp_n_devices", "mp_model_band",
+    "mp_get_policy", "mp_create_multi", "mp_n_devices", "mp_model_band", "mp_sampler_set_temperatures", "mp_sampler_get_swaps",
 )
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -148,6 +148,8 @@ def lib():
     L.mp_sampler_run.argtypes = [vp, C.c_int, dp, dp]
     L.mp_sampler_set_whole_step.argtypes = [vp, C.c_int]
     L.mp_sampler_get_state.argtypes = [vp, dp, dp, i64p, i64p]
+    L.mp_sampler_set_temperatures.argtypes = [vp, C.c_int, dp]
+    L.mp_sampler_get_swaps.argtypes = [vp, i64p]
     L.mp_last_mean_sweeps.argtypes = [vp]
     L.mp_last_mean_sweeps.restype = C.c_double
     L.mp_last_mean_tiles.argtypes = [vp]
@@ -180,7 +182,8 @@ def lib():
                  "mp_sampler_set_positions", "mp_sampler_run", "mp_sampler_set_whole_step", "mp_sampler_get_state", "mp_sampler_get_bad",
                  "mp_sampler_n_slots", "mp_sampler_row_doubles", "mp_sampler_halfstep_shard",
                  "mp_sampler_halfstep_apply", "mp_sampler_step_blocks", "mp_sampler_step_row_doubles",
-                 "mp_sampler_step_shard", "mp_sampler_step_apply", "mp_sampler_state_ptrs", "mp_n_simd"):
+                 "mp_sampler_step_shard", "mp_sampler_step_apply", "mp_sampler_state_ptrs", "mp_n_simd",
+                 "mp_sampler_set_temperatures", "mp_sampler_get_swaps"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

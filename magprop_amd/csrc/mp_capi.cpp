@@ -921,6 +921,10 @@ struct mp_sampler {
     // failed proposals (the reference's fbad file): the device window d_bad is drained into this log
     std::vector<double> bad_log;    // [rows][ndim]
     int64_t n_bad = 0;              // exact count since creation (rows beyond the window between two drains are counted, not kept)
+    // parallel tempering (mp_sampler_set_temperatures): ensemble e runs at beta[e % n_temps]; 0 = untempered
+    int n_temps = 0;
+    DevBuf<double> d_beta;          // [n_ensembles]
+    DevBuf<int64_t> d_swaps;        // [n_ensembles / n_temps][n_temps - 1] accepted swaps
 };
 
 // Move the device window of failed proposals into the host log and reset it.  The caller has made sure that no kernel
@@ -978,6 +982,7 @@ static mp::StretchArgs stretch_args(const mp_sampler *s, const int32_t *d_perm, 
     g.n_total = s->n_total; g.ndim = s->ndim; g.half = half; g.target = s->target;
     g.step = (uint32_t)step; g.seed = s->seed; g.a = s->a;
     g.bad_log = s->d_bad.p; g.bad_count = s->d_bad_count.p; g.bad_cap = (uint32_t)(s->d_bad.cap / (size_t)std::max(s->ndim, 1));
+    g.beta = s->n_temps ? s->d_beta.p : nullptr;
     // Ensembles on light curves of different lengths (BASELINE config 5: 50 / 410 / 8 / 1 944 points): the half-step launch
     // starts the ensemble with the longest light curve first, so that its waves do not begin last and finish alone.  The order
     // is a function of the datasets only, so every rank of a walker-sharded run derives the same one.
@@ -1048,12 +1053,49 @@ int mp_sampler_destroy(mp_sampler *s) {
     (void)hipDeviceSynchronize();
     s->d_pos.release(); s->d_lnprob.release(); s->d_chain.release(); s->d_chain_lnp.release();
     s->d_acc.release(); s->d_perm.release(); s->d_dsid.release(); s->d_status.release(); s->h_perm.release();
-    s->d_bad.release(); s->d_bad_count.release();
+    s->d_bad.release(); s->d_bad_count.release(); s->d_beta.release(); s->d_swaps.release();
     for (int b = 0; b < 2; ++b) {
         s->d_win[b].release(); s->h_win[b].release();
         if (s->win_copied[b]) (void)hipEventDestroy(s->win_copied[b]);
     }
     delete s;
+    return MP_OK;
+}
+
+int mp_sampler_set_temperatures(mp_sampler *s, int n_temps, const double *betas) {
+    if (!s || !betas) return fail(MP_EINVAL, "mp_sampler_set_temperatures: NULL argument");
+    Lock lock(s->h->mu);
+    if (s->have_state) return fail(MP_ESTATE, "mp_sampler_set_temperatures: call it before the first mp_sampler_set_positions");
+    if (n_temps < 2) return fail(MP_EINVAL, "mp_sampler_set_temperatures: a ladder needs at least 2 temperatures, got %d", n_temps);
+    if (s->n_ensembles % n_temps) return fail(MP_EINVAL, "mp_sampler_set_temperatures: %d ensembles are not groups of %d temperatures", s->n_ensembles, n_temps);
+    if (betas[0] != 1.0) return fail(MP_EINVAL, "mp_sampler_set_temperatures: betas[0] must be 1, got %g", betas[0]);
+    for (int t = 1; t < n_temps; ++t)
+        // (beta = 0 is refused: failed models have lnprob = -inf, and 0 x -inf is NaN)
+        if (!std::isfinite(betas[t]) || !(betas[t] > 0.0) || !(betas[t] < betas[t - 1]))
+            return fail(MP_EINVAL, "mp_sampler_set_temperatures: betas must be finite, > 0 and strictly decreasing (betas[%d] = %g)", t, betas[t]);
+    for (int e = 0; e < s->n_ensembles; ++e)
+        if (s->ens_ds[(size_t)e] != s->ens_ds[(size_t)(e - e % n_temps)])
+            return fail(MP_EINVAL, "mp_sampler_set_temperatures: ensembles %d and %d of one group have different datasets", e - e % n_temps, e);
+    DeviceScope scope(s->h->device);
+    std::vector<double> b((size_t)s->n_ensembles);
+    for (int e = 0; e < s->n_ensembles; ++e) b[(size_t)e] = betas[e % n_temps];
+    const size_t n_pairs = (size_t)(s->n_ensembles / n_temps) * (size_t)(n_temps - 1);
+    int rc;
+    if ((rc = s->d_beta.ensure(b.size())) || (rc = s->d_swaps.ensure(n_pairs))) return rc;
+    HIP_TRY(hipMemcpy(s->d_beta.p, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(s->d_swaps.p, 0, n_pairs * sizeof(int64_t)));
+    s->n_temps = n_temps;
+    return MP_OK;
+}
+
+int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted) {
+    if (!s || !n_swaps_accepted) return fail(MP_EINVAL, "mp_sampler_get_swaps: NULL argument");
+    Lock lock(s->h->mu);
+    if (!s->n_temps) return fail(MP_ESTATE, "mp_sampler_get_swaps: the sampler is not tempered (mp_sampler_set_temperatures)");
+    DeviceScope scope(s->h->device);
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t n_pairs = (size_t)(s->n_ensembles / s->n_temps) * (size_t)(s->n_temps - 1);
+    HIP_TRY(hipMemcpy(n_swaps_accepted, s->d_swaps.p, n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost));
     return MP_OK;
 }
 
@@ -1133,6 +1175,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
                     g.spec = s->d_spec.p;
                     int e = mp::launch_stretch_step(h->sh, g, 3 * n_slots, h->stream);
                     if (!e) e = mp::launch_stretch_step_commit(g, h->stream);
+                    if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
                     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
                     continue;
                 }
@@ -1141,7 +1184,8 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
                     g.chain = chain ? s->d_chain.p : nullptr;
                     g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
                     g.chain_row = st;
-                    const int e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
+                    int e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
+                    if (!e && half == 1 && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
                     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
                 }
             }
@@ -1194,6 +1238,7 @@ int mp_sampler_n_slots(const mp_sampler *s) { return s ? (s->n_walkers / 2) * s-
 int mp_sampler_halfstep_shard(mp_sampler *s, int half, int slot_lo, int slot_hi, double *d_rows, void *stream) {
     if (!s || (half != 0 && half != 1)) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: bad argument");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_halfstep_shard: call mp_sampler_set_positions first");
+    if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_halfstep_shard: a tempered sampler runs on one device only (mp_sampler_run)");
     const int n_slots = (s->n_walkers / 2) * s->n_ensembles;
     if (slot_lo < 0 || slot_hi > n_slots || slot_lo > slot_hi) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: slots [%d, %d) outside [0, %d)", slot_lo, slot_hi, n_slots);
     if (slot_hi > slot_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: NULL row buffer");
@@ -1219,6 +1264,7 @@ int mp_sampler_halfstep_apply(mp_sampler *s, int half, const double *d_rows, dou
     if (!s || !d_rows || (half != 0 && half != 1)) return fail(MP_EINVAL, "mp_sampler_halfstep_apply: bad argument");
     if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_halfstep_apply: chain row and lnprob row go together");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_halfstep_apply: call mp_sampler_set_positions first");
+    if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_halfstep_apply: a tempered sampler runs on one device only (mp_sampler_run)");
     mp_handle *h = s->h;
     Lock lock(h->mu);
     DeviceScope scope(h->device);
@@ -1245,6 +1291,7 @@ int mp_sampler_step_row_doubles(const mp_sampler *s) { return s ? s->ndim + mp::
 int mp_sampler_step_shard(mp_sampler *s, int block_lo, int block_hi, double *d_rows, void *stream) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL sampler");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_step_shard: call mp_sampler_set_positions first");
+    if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_step_shard: a tempered sampler runs on one device only (mp_sampler_run)");
     const int n_blocks = 3 * (s->n_walkers / 2) * s->n_ensembles;
     if (block_lo < 0 || block_hi > n_blocks || block_lo > block_hi) return fail(MP_EINVAL, "mp_sampler_step_shard: blocks [%d, %d) outside [0, %d)", block_lo, block_hi, n_blocks);
     if (block_hi > block_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL row buffer");
@@ -1269,6 +1316,7 @@ int mp_sampler_step_apply(mp_sampler *s, const double *d_rows, double *d_chain_r
     if (!s || !d_rows) return fail(MP_EINVAL, "mp_sampler_step_apply: bad argument");
     if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_step_apply: chain row and lnprob row go together");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_step_apply: call mp_sampler_set_positions first");
+    if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_step_apply: a tempered sampler runs on one device only (mp_sampler_run)");
     mp_handle *h = s->h;
     Lock lock(h->mu);
     DeviceScope scope(h->device);

@@ -153,6 +153,8 @@ struct StretchArgs {
     uint64_t seed;
     double a;               // stretch scale (emcee default 2)
     uint64_t ens_order;     // half-step launches: ensemble at position p of the launch = (ens_order >> 4p) & 15; 0 = identity
+    const double *beta;     // [n_ensembles] inverse temperature of every ensemble (parallel tempering), or nullptr: 1 for all.
+                            // Only the decisions use it; stored log-probabilities stay untempered
 };
 
 // ---------------------------------------------------------------- compile-time constants of the stride policy
@@ -257,6 +259,8 @@ int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void
 int launch_stretch_apply(const StretchArgs &g, void *stream);
 int launch_stretch_step(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream);   // blocks [g.slot_lo, + n_blocks) of 3 * n_half * n_ensembles
 int launch_stretch_step_commit(const StretchArgs &g, void *stream);
+// the swap sweep of a tempered step (stretch_swap_kernel): one workgroup per group of n_temps ensembles; n_swaps[group][n_temps - 1]
+int launch_stretch_swap(const StretchArgs &g, int n_temps, int64_t *n_swaps, void *stream);
 // columns behind the proposal in an outcome row of a whole-step launch
 constexpr int kSpecExtra = 6;   // lnprob, status, (ndim - 1) ln z, ln u, lnprob of the walker before the move, partner's slot
 

@@ -28,7 +28,8 @@
 //
 // Kernels: lnprob_kernel<CURVES, SPL, LONG> (one wavefront per walker), stretch_kernel<SPL, LONG> (emcee's stretch
 // move fused around it) and stretch_apply_kernel (the state update of a half-step whose proposals were evaluated
-// on several GPUs); LONG = built with the path for light curves of more than 64 points.
+// on several GPUs); LONG = built with the path for light curves of more than 64 points.  Tempered samplers (parallel
+// tempering) take their decisions against beta x lnprob and run stretch_swap_kernel after every step.
 // No MFMA (no dense contraction anywhere on this path), fp64 throughout; bound by the VALU issue rate of one wave per
 // SIMD (profiles/, tools/ubench).  The arithmetic is algebraically simplified with respect to the reference formulas
 // (e.g. fastness w = (Rm/Rc)^1.5 = omega*Rm^1.5/sqrt(GM), eta1-eta2 = -tanh); oracle/mp_oracle.c keeps the literal
@@ -207,7 +208,10 @@ struct TeamLds<G, false> {
 // W, OCC: small ensembles evaluate every proposal on a team of W = 4 wavefronts (lnprob_team_kernel; OCC = wavefronts resident
 // per SIMD the build is made for), chosen by the size of a WHOLE step of the sampler (stretch_waves, mp_device.h) so that one
 // launch per step and one per half-step run the same arithmetic: the chains stay equal bit for bit.
-template <int SPL, bool LONG, int W = 1, int OCC = 0>
+// TEMPERED: the builds of tempered samplers (g.beta set), which decide against beta x lnprob.  Separate builds, because even a
+// read of beta behind the evaluation moves the register allocation of walker_eval (scratch and SGPR spills of the untempered
+// builds would change with it); the untempered builds are the code they were.
+template <int SPL, bool LONG, int W = 1, int OCC = 0, bool TEMPERED = false>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
 void stretch_kernel(const DevShared sh, const StretchArgs g) {
     __shared__ TileImage<SPL * W> im;
@@ -267,7 +271,15 @@ void stretch_kernel(const DevShared sh, const StretchArgs g) {
     }
     if (lane0) {   // lane 0 of the evaluating wavefront (team: of its first one)
         const double lnp_old = park[MP_MAX_NDIM + 2];
-        const double lnpdiff = sub_rn(add_rn(park[MP_MAX_NDIM], lnp), lnp_old);
+        double lnpdiff;
+        if constexpr (TEMPERED) {
+            // target prior x L^beta: with a box prior the test is beta (lnprob(proposal) - lnprob(walker)); beta = 1 gives the
+            // untempered test bit for bit (mul_rn(1, x) == x).  beta is read here, behind the evaluation, from the walker's ensemble
+            const double beta = g.beta[k / g.n_walkers];
+            lnpdiff = sub_rn(add_rn(park[MP_MAX_NDIM], mul_rn(beta, lnp)), mul_rn(beta, lnp_old));
+        } else {
+            lnpdiff = sub_rn(add_rn(park[MP_MAX_NDIM], lnp), lnp_old);
+        }
         const bool accept = lnpdiff > park[MP_MAX_NDIM + 1];      // false for NaN / -inf proposals
         if (g.upd) {
             double *u = g.upd + (size_t)blockIdx.x * (g.ndim + 3);
@@ -435,7 +447,9 @@ void stretch_step_kernel(const DevShared sh, const StretchArgs g) {
     }
 }
 
-// The decisions of a whole step from the outcome rows of stretch_step_kernel: one thread per walker.
+// The decisions of a whole step from the outcome rows of stretch_step_kernel: one thread per walker.  TEMPERED: as in
+// stretch_kernel (the untempered build stays the code it was).
+template <bool TEMPERED>
 __global__ __launch_bounds__(256) void stretch_step_commit_kernel(const StretchArgs g) {
     const int n_slots = g.n_half * g.n_ensembles, R = g.ndim + kSpecExtra;
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -444,6 +458,10 @@ __global__ __launch_bounds__(256) void stretch_step_commit_kernel(const StretchA
     const int w_ens = gs / g.n_half, slot = gs - w_ens * g.n_half;
     const int k = w_ens * g.n_walkers + g.perm[(size_t)w_ens * g.n_walkers + half * g.n_half + slot];
     auto accepted = [&](const double *u) {   // emcee: lnpdiff = (ndim - 1) ln z + lnprob(proposal) - lnprob(walker) > ln u
+        if constexpr (TEMPERED) {            // (ndim - 1) ln z + beta lnprob(proposal) - beta lnprob(walker), beta of the ensemble
+            const double beta = g.beta[w_ens];
+            return sub_rn(add_rn(u[g.ndim + 2], mul_rn(beta, u[g.ndim])), mul_rn(beta, u[g.ndim + 4])) > u[g.ndim + 3];
+        }
         return sub_rn(add_rn(u[g.ndim + 2], u[g.ndim]), u[g.ndim + 4]) > u[g.ndim + 3];
     };
     const double *u = g.spec + (size_t)gs * R;
@@ -470,6 +488,56 @@ __global__ __launch_bounds__(256) void stretch_step_commit_kernel(const StretchA
         const unsigned slot_b = atomicAdd(g.bad_count, 1u);
         if (slot_b < g.bad_cap)
             for (int i = 0; i < g.ndim; ++i) g.bad_log[(size_t)slot_b * g.ndim + i] = u[i];
+    }
+}
+
+// ---------------------------------------------------------------- parallel tempering: the swap sweep of a step
+// A tempered sampler holds n_groups x n_temps ensembles; ensemble e is group e / n_temps at temperature t = e % n_temps.  After
+// the decisions of a step every group runs one sweep over its neighbouring pairs, hottest first (t = n_temps - 1 .. 1), each
+// pair seeing the outcome of the one before.  Slot i of temperature t - 1 pairs with slot i of temperature t, slot i of an
+// ensemble being walker perm_e[i] of the step's split: the pairing is fixed before the state is looked at, so the swap, like
+// the move, leaves the joint target invariant given the permutation.  Accept if ln u < (beta_{t-1} - beta_t)(L_hot - L_cold)
+// (unfused; NaN and -inf reject), u from Philox keyed (seed; step, 2, cold walker, 0): half index 2 is never drawn by the move.
+// An accepted swap exchanges positions and lnprob of the two walkers and rewrites their entries of the step's chain row;
+// the acceptance counters stay with the walkers.
+// One workgroup per group, thread i owns slot i of EVERY temperature of the group, so the chain of pairs t, t - 1 that a slot
+// runs through is one thread's sequence of reads and writes: the sweep needs no barrier between the pairs.
+__global__ __launch_bounds__(256) void stretch_swap_kernel(const StretchArgs g, int n_temps, unsigned long long *n_swaps) {
+    const int e0 = blockIdx.x * n_temps;   // first (coldest) ensemble of this group
+    for (int t = n_temps - 1; t >= 1; --t) {
+        const int ec = e0 + t - 1, eh = e0 + t;
+        const double dbeta = sub_rn(g.beta[ec], g.beta[eh]);
+        for (int i = (int)threadIdx.x; i < g.n_walkers; i += (int)blockDim.x) {
+            const int kc = ec * g.n_walkers + g.perm[(size_t)ec * g.n_walkers + i];
+            const int kh = eh * g.n_walkers + g.perm[(size_t)eh * g.n_walkers + i];
+            uint32_t r[4];
+            philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, 2u, (uint32_t)kc, 0u, r);
+            const double lc = g.lnprob[kc], lh = g.lnprob[kh];
+            const bool accept = log(u01(r[0], r[1])) < mul_rn(dbeta, sub_rn(lh, lc));
+            if (accept) {
+                for (int d = 0; d < g.ndim; ++d) {
+                    const double xc = g.pos[(size_t)kc * g.ndim + d];
+                    g.pos[(size_t)kc * g.ndim + d] = g.pos[(size_t)kh * g.ndim + d];
+                    g.pos[(size_t)kh * g.ndim + d] = xc;
+                }
+                g.lnprob[kc] = lh;
+                g.lnprob[kh] = lc;
+                if (g.chain) {
+                    double *cc = g.chain + ((size_t)g.chain_row * g.n_total + kc) * g.ndim;
+                    double *ch = g.chain + ((size_t)g.chain_row * g.n_total + kh) * g.ndim;
+                    for (int d = 0; d < g.ndim; ++d) {
+                        cc[d] = g.pos[(size_t)kc * g.ndim + d];
+                        ch[d] = g.pos[(size_t)kh * g.ndim + d];
+                    }
+                    g.chain_lnp[(size_t)g.chain_row * g.n_total + kc] = lh;
+                    g.chain_lnp[(size_t)g.chain_row * g.n_total + kh] = lc;
+                }
+            }
+            // one atomic per wavefront: lane 0 holds the smallest i of its wavefront, so it is active whenever any lane is
+            const unsigned long long acc_mask = __ballot(accept);
+            if ((threadIdx.x & 63) == 0 && acc_mask)
+                atomicAdd(n_swaps + (size_t)blockIdx.x * (n_temps - 1) + (t - 1), (unsigned long long)__popcll(acc_mask));
+        }
     }
 }
 
@@ -578,29 +646,33 @@ int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
 }
 
 // n_blocks slots of the active half starting at g.slot_lo
-int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
-    if (n_blocks <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
+template <bool TEMPERED>
+static int launch_stretch_t(const DevShared &sh, const StretchArgs &g, int n_blocks, hipStream_t st) {
     dim3 grid((unsigned)n_blocks);
     const bool lng = sh.has_long != 0;
     if (stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4) {   // small ensembles: a team of four wavefronts per proposal
         if (4 * n_blocks <= sh.n_simd) {
-            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 1>), grid, dim3(256), 0, st, sh, g);
-            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 1>), grid, dim3(256), 0, st, sh, g);
+            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 1, TEMPERED>), grid, dim3(256), 0, st, sh, g);
+            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 1, TEMPERED>), grid, dim3(256), 0, st, sh, g);
         } else {
-            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 2>), grid, dim3(256), 0, st, sh, g);
-            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 2>), grid, dim3(256), 0, st, sh, g);
+            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 2, TEMPERED>), grid, dim3(256), 0, st, sh, g);
+            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 2, TEMPERED>), grid, dim3(256), 0, st, sh, g);
         }
         return (int)hipGetLastError();
     }
     if ((sh.force_spl ? sh.force_spl : kernel_spl(sh, n_blocks)) == 4) {
-        if (lng) hipLaunchKernelGGL((stretch_kernel<4, true>), grid, dim3(64), 0, st, sh, g);
-        else hipLaunchKernelGGL((stretch_kernel<4, false>), grid, dim3(64), 0, st, sh, g);
+        if (lng) hipLaunchKernelGGL((stretch_kernel<4, true, 1, 0, TEMPERED>), grid, dim3(64), 0, st, sh, g);
+        else hipLaunchKernelGGL((stretch_kernel<4, false, 1, 0, TEMPERED>), grid, dim3(64), 0, st, sh, g);
     } else {
-        if (lng) hipLaunchKernelGGL((stretch_kernel<2, true>), grid, dim3(64), 0, st, sh, g);
-        else hipLaunchKernelGGL((stretch_kernel<2, false>), grid, dim3(64), 0, st, sh, g);
+        if (lng) hipLaunchKernelGGL((stretch_kernel<2, true, 1, 0, TEMPERED>), grid, dim3(64), 0, st, sh, g);
+        else hipLaunchKernelGGL((stretch_kernel<2, false, 1, 0, TEMPERED>), grid, dim3(64), 0, st, sh, g);
     }
     return (int)hipGetLastError();
+}
+
+int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
+    if (n_blocks <= 0) return 0;
+    return g.beta ? launch_stretch_t<true>(sh, g, n_blocks, (hipStream_t)stream) : launch_stretch_t<false>(sh, g, n_blocks, (hipStream_t)stream);
 }
 
 int launch_stretch_step(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
@@ -631,7 +703,15 @@ int launch_stretch_step(const DevShared &sh, const StretchArgs &g, int n_blocks,
 int launch_stretch_step_commit(const StretchArgs &g, void *stream) {
     const int n = 2 * g.n_half * g.n_ensembles;
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(stretch_step_commit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+    if (g.beta) hipLaunchKernelGGL(stretch_step_commit_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL(stretch_step_commit_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+    return (int)hipGetLastError();
+}
+
+int launch_stretch_swap(const StretchArgs &g, int n_temps, int64_t *n_swaps, void *stream) {
+    if (n_temps < 2 || g.n_ensembles % n_temps || !g.beta) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(stretch_swap_kernel, dim3((unsigned)(g.n_ensembles / n_temps)), dim3(256), 0, (hipStream_t)stream, g, n_temps,
+                       (unsigned long long *)n_swaps);
     return (int)hipGetLastError();
 }
 

@@ -190,7 +190,10 @@ class DistributedEnsembleSampler:
     def __init__(self, engine, group=None, via_host=False, always_gather=False, whole_step=None):
         """whole_step: None = a whole step per launch and ONE all-gather per step when the engine offers it and a rank's
         share of the 3/2 x walkers evaluations fits its device (engine.whole_step_ok); False = one launch and one gather
-        per half-step (larger ensembles get that anyway).  Same chain either way."""
+        per half-step (larger ensembles get that anyway).  Same chain either way.
+        A tempered sampler (EnsembleSampler(..., betas=...)) is refused: sharded tempering is not supported."""
+        if getattr(getattr(engine, "s", None), "betas", None) is not None:
+            raise ValueError("DistributedEnsembleSampler: a tempered sampler runs on one device (EnsembleSampler.run_mcmc)")
         self.engine = engine
         self.group = group
         self.via_host = via_host       # gather through host memory: gloo rehearsal with GPU engines

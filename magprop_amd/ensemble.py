@@ -9,24 +9,30 @@
 `EnsembleSampler` here keeps positions, log-posteriors, acceptance counters and the chain in HBM and runs every
 stretch-move half-step as one fused kernel (propose -> lnprob -> accept -> store), so there is no host round
 trip per half-step.  Several independent ensembles (e.g. one per GRB dataset) can be advanced together.
+With a ladder of inverse temperatures (betas=...) every dataset gets one ensemble per temperature and the sampler runs
+parallel tempering: tempered decisions in the same fused kernels plus one swap kernel per step (magprop_amd.tempering,
+EnsembleSampler.log_evidence).
 """
 import ctypes as C
 import sys
 
 import numpy as np
 
-from . import _capi, engine, synth
+from . import _capi, engine, synth, tempering
 
 
 class EnsembleSampler:
     def __init__(self, nwalkers, ndim=6, x=None, y=None, yerr=None, variant="synth", GRBtype=None, seed=0, a=2.0,
                  datasets=None, lower="default", upper="default", log_mask=None, device=-1, target="posterior",
-                 fbad=None, sweep_tol=None, max_stride=None, whole_step=True):
+                 fbad=None, sweep_tol=None, max_stride=None, whole_step=True, betas=None):
         """One ensemble on dataset (x, y, yerr), or one ensemble per entry of `datasets` = [(x, y, yerr), ...].
         whole_step: small ensembles run a whole step per launch (include/magprop_amd.h mp_sampler_set_whole_step; same
         chain bit for bit as one launch per half-step, which False selects).
         fbad: file that receives the proposals whose model failed, like the reference's lnprob(…, fbad)
-        (code/synthetic_datasets/mcmc_eqns.py:72-79); written after every run_mcmc call."""
+        (code/synthetic_datasets/mcmc_eqns.py:72-79); written after every run_mcmc call.
+        betas: None (untempered, as emcee), or a ladder 1 = beta_0 > beta_1 > ... > 0 (magprop_amd.tempering.check_ladder):
+        parallel tempering with one ensemble per (dataset, temperature), nensembles = len(datasets) x T (T for
+        target="gaussian"), positions in ensemble order (group g, temperature t: walkers [(g T + t) nwalkers, + nwalkers))."""
         if nwalkers % 2 or nwalkers < 2:
             raise ValueError("nwalkers must be even")            # emcee requires an even number too
         self.nwalkers, self.ndim = int(nwalkers), int(ndim)
@@ -49,6 +55,7 @@ class EnsembleSampler:
             mask = log_mask
         self.handle = _capi.Handle(cfg, engine.grid(GRBtype), device)
         self.handle.set_prior(lo, hi, mask)
+        self._prior = (lo, hi)
         self._target = {"posterior": 0, "gaussian": 1}[target]
         if datasets is None:
             datasets = [(x, y, yerr)] if x is not None else []
@@ -56,13 +63,19 @@ class EnsembleSampler:
             raise ValueError("a dataset is required")
         for k, (dx, dy, de) in enumerate(datasets):
             self.handle.set_dataset(k, dx, dy, de)
-        self.nensembles = max(1, len(datasets))
-        ids = np.arange(self.nensembles, dtype=np.int32)
+        self.betas = None if betas is None else tempering.check_ladder(betas)
+        self.ntemps = 1 if self.betas is None else int(self.betas.size)
+        self.ngroups = max(1, len(datasets))
+        self.nensembles = self.ngroups * self.ntemps
+        ids = np.repeat(np.arange(self.ngroups, dtype=np.int32), self.ntemps)   # the temperatures of a group share its dataset
         self._s = self._L.mp_sampler_create(self.handle._h, self.nwalkers, self.nensembles, self.ndim,
                                             ids.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint64(int(seed)),
                                             C.c_double(a), self._target)
         if not self._s:
             raise _capi.MagpropAmdError("mp_sampler_create failed: " + _capi.last_error())
+        if self.betas is not None:
+            _capi.check(self._L.mp_sampler_set_temperatures(self._s, self.ntemps, self.betas.ctypes.data_as(C.POINTER(C.c_double))),
+                        "mp_sampler_set_temperatures")
         _capi.check(self._L.mp_sampler_set_whole_step(self._s, int(bool(whole_step))), "mp_sampler_set_whole_step")
         self.seed = int(seed)
         self._chain = None
@@ -203,12 +216,67 @@ class EnsembleSampler:
         return pos, lnp, acc
 
     # ---- emcee-shaped views (synth_mcmc.py:188-226 indexes chain[i, j, k], lnprobability[i, j])
-    def get_chain(self):
-        """(nsteps, nwalkers_total, ndim)"""
-        return self._chain
+    def get_chain(self, temp=None):
+        """(nsteps, nwalkers_total, ndim); temp=t: the walkers at beta_t of every group, in group order
+        (nsteps, ngroups x nwalkers, ndim)."""
+        return self._at_temp(self._chain, temp)
 
-    def get_log_prob(self):
-        return self._lnp
+    def get_log_prob(self, temp=None):
+        """(nsteps, nwalkers_total), untempered lnprob; temp=t: as in get_chain."""
+        return self._at_temp(self._lnp, temp)
+
+    def _at_temp(self, a, temp):
+        if temp is None:
+            return a
+        t = int(temp)
+        if not 0 <= t < self.ntemps:
+            raise ValueError(f"temp must be in 0..{self.ntemps - 1}, got {temp}")
+        if a is None:
+            return None
+        v = a.reshape((a.shape[0], self.ngroups, self.ntemps, self.nwalkers) + a.shape[2:])[:, :, t]
+        return v.reshape((a.shape[0], self.ngroups * self.nwalkers) + a.shape[2:])
+
+    @property
+    def swap_acceptance_fraction(self):
+        """(ngroups, T - 1): accepted / proposed swaps of every neighbouring pair (t - 1, t); each pair is proposed nwalkers
+        times per step."""
+        if self.betas is None:
+            raise ValueError("swap_acceptance_fraction needs a tempered sampler (betas=...)")
+        acc = np.zeros((self.ngroups, self.ntemps - 1), dtype=np.int64)
+        _capi.check(self._L.mp_sampler_get_swaps(self._s, acc.ctypes.data_as(C.POINTER(C.c_int64))), "mp_sampler_get_swaps")
+        done = C.c_int64(0)
+        _capi.check(self._L.mp_sampler_get_state(self._s, None, None, None, C.byref(done)), "mp_sampler_get_state")
+        return acc / max(done.value * self.nwalkers, 1)
+
+    def log_evidence(self, discard=0, group=0, prior_draws=2 ** 20):
+        """(lnZ, dlnZ) of group `group`'s dataset, the prior normalised over its box, from the stored chain of a tempered run:
+        thermodynamic integration of the per-temperature mean lnL over steps[discard:] (magprop_amd.tempering) plus
+        ln f_valid, the fraction of `prior_draws` uniform box draws (numpy generator seeded by the sampler seed, evaluated on
+        this sampler's handle) whose lnprob is finite.  dlnZ = |TI - TI over every other temperature| in quadrature with the
+        binomial error of ln f_valid.  target="gaussian" has no prior box: lnZ is the integral alone."""
+        if self.betas is None:
+            raise ValueError("log_evidence needs a tempered sampler (betas=...)")
+        if self._lnp is None or len(self._lnp) == 0:
+            raise ValueError("the chain is empty: run_mcmc(..., store=True) first")
+        discard, group = int(discard), int(group)
+        if not 0 <= discard < len(self._lnp):
+            raise ValueError(f"discard={discard} leaves no step of the {len(self._lnp)} stored")
+        if not 0 <= group < self.ngroups:
+            raise ValueError(f"group must be in 0..{self.ngroups - 1}, got {group}")
+        lnl = self._lnp[discard:].reshape(-1, self.ngroups, self.ntemps, self.nwalkers)[:, group]
+        means = lnl.transpose(1, 0, 2).reshape(self.ntemps, -1).mean(axis=1)
+        ti, dti = tempering.ti_log_evidence(self.betas, means)
+        if self._target != 0:
+            return ti, dti
+        lo, hi = np.asarray(self._prior[0], dtype=np.float64), np.asarray(self._prior[1], dtype=np.float64)
+        rng = np.random.default_rng(self.seed)
+        n_draws, n_finite, chunk = int(prior_draws), 0, 1 << 16
+        for first in range(0, n_draws, chunk):
+            m = min(chunk, n_draws - first)
+            lp = self.handle.lnprob_batch(lo + (hi - lo) * rng.random((m, lo.size)), ds_id=group)
+            n_finite += int(np.count_nonzero(np.isfinite(lp)))
+        lnf, dlnf = tempering.validity_term(n_finite, n_draws)
+        return ti + lnf, float(np.hypot(dti, dlnf))
 
     @property
     def chain(self):
@@ -229,7 +297,9 @@ class EnsembleSampler:
         if self._target != 0:
             raise ValueError("get_model_band needs the posterior target: a target='gaussian' sampler has no light curve")
         qa, _, names = _capi.band_args(q, components)
-        rows = band_selection(self._chain, self.nwalkers, self.nensembles, discard, thin, ensemble)
+        # (tempered: the beta = 1 walkers of group `ensemble`)
+        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
+                              discard, thin, ensemble)
         band, _, used = self.handle.model_band(rows, qa, names)
         out = {"t": self.handle.tgrid.copy()}
         out.update({c: band[k] for k, c in enumerate(names)})
@@ -240,7 +310,7 @@ class EnsembleSampler:
         """emcee's default (quiet=False) raises when the chain is shorter than tol autocorrelation times; the
         reference calls it bare (code/synthetic_datasets/synth_mcmc.py:220)."""
         from .mcmc_io import integrated_time
-        return integrated_time(self._chain, c=c, tol=tol, quiet=quiet)
+        return integrated_time(self.get_chain(temp=0 if self.betas is not None else None), c=c, tol=tol, quiet=quiet)
 
 
 def band_selection(chain, nwalkers, nensembles=1, discard=0, thin=1, ensemble=0):
