@@ -300,6 +300,39 @@ int mp_sampler_set_temperatures(mp_sampler *s, int n_temps, const double *betas)
  * each pair is proposed n_walkers times per step.  MP_ESTATE on an untempered sampler. */
 int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted);
 /*
+ * Proposal moves (ABI 5, additive; emcee 3's moves=).  Every move is a red-blue move over the step's two-way split: walker k
+ * of the active half draws its partners from the n_comp = n_walkers - n_half slots of the other half.  Random numbers are
+ * Philox4x32-10 keyed (seed; step, half, k, c3): the stretch move uses c3 = 0, 1, DE and snooker c3 = 2 (r) and 3 (r2).
+ * pick(u, m) = min(floor(u m), m - 1); a second index distinct from a first is pick(u', m - 1), plus 1 if >= the first; a third
+ * is drawn over m - 2 and steps over the first two in increasing order.  u01(a, b) = 53-bit uniform of the pair.  All proposal
+ * arithmetic is unfused (separately rounded products and sums, IEEE division), so a numpy restatement reproduces the chain.
+ *   MP_MOVE_STRETCH  params[0] = a (> 1): the stretch move of mp_sampler_create.
+ *   MP_MOVE_DE       (ter Braak 2006) params[0] = g0 (0: 2.38 / sqrt(2 ndim)), params[1] = sigma in [0, 1/sqrt(3)).
+ *                    Partners c1 = pick(u01(r0, r1), n_comp), c2 distinct from c1 by u01(r2, r3); gamma = g0 (1 + s (2 u01(r2_0,
+ *                    r2_1) - 1)), s = sigma sqrt(3): gamma is uniform with standard deviation sigma g0 (emcee draws it normal).
+ *                    q = x_k + gamma (x_c1 - x_c2), Hastings term 0.
+ *   MP_MOVE_SNOOKER  (ter Braak & Vrugt 2008) params[0] = gamma_s (> 0; emcee's default 1.7).  Partners z, z1, z2 from (r0, r1),
+ *                    (r2, r3), (r2_0, r2_1), all three distinct.  d = x_k - z, dd = sum d_i^2, p = sum d_i (z1_i - z2_i) (index
+ *                    order), q = x_k + (gamma_s (p / dd)) d, Hastings term h = (ndim - 1)/2 (ln sum (q - z)_i^2 - ln dd) (dd = 0:
+ *                    NaN, rejected).  emcee splits the walkers four ways for this move; here the split is two-way.
+ * ln u = ln u01(r2_2, r2_3) for DE and snooker.  Decision (every move): h + beta lnprob(q) - beta lnprob(x_k) > ln u, beta of the
+ * walker's ensemble (1 untempered); the stretch move's h is (ndim - 1) ln z.
+ * Mixtures: one move per step for the whole sampler.  With n_moves > 1, step s draws r = Philox(seed; s, 3, 0, 0x30FE) and takes
+ * the first move m with u01(r0, r1) C_last < C_m, C the cumulative weights (summed in order, double): the move of a step depends
+ * on (seed, s, table) only, so split runs give the chain of one run.  DE and snooker steps run two half-step launches (plus the
+ * swap sweep when tempered); stretch steps run as mp_sampler_set_whole_step decides.
+ * n_moves == 0 restores the default (the stretch move with the a of mp_sampler_create); may be called between runs.
+ * MP_EINVAL: NULL sampler or arrays, n_moves outside [0, MP_MAX_MOVES], an unknown kind, a weight that is not finite and > 0,
+ * bad params, DE with n_half < 2, snooker with n_half < 3.  With a table set (n_moves > 0), the walker-sharded entry points
+ * (mp_sampler_halfstep_*, mp_sampler_step_*) return MP_ESTATE.
+ */
+#define MP_MOVE_STRETCH 0   /* params: a (> 1)                                              */
+#define MP_MOVE_DE      1   /* params: g0 (0: 2.38/sqrt(2 ndim)), sigma in [0, 1/sqrt(3))    */
+#define MP_MOVE_SNOOKER 2   /* params: gamma_s (> 0)                                         */
+#define MP_MAX_MOVES    8
+int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const double *weights,
+                         const double *params /* [n_moves][2] */);
+/*
  * Proposals inside the prior whose model evaluation failed ('flag' / non-finite): what the reference's lnprob appends
  * to its `fbad` file (code/synthetic_datasets/mcmc_eqns.py:72-79).  The kernels collect them in a device-side window of
  * MP_BAD_WINDOW rows which the library drains into a host-side log (after every chunk of mp_sampler_run and in this

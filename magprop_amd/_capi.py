@@ -31,6 +31,7 @@ EXPORTS = (
     "mp_sampler_halfstep_apply", "mp_sampler_step_blocks", "mp_sampler_step_row_doubles", "mp_sampler_step_shard",
     "mp_sampler_step_apply", "mp_sampler_state_ptrs", "mp_sweep_tol", "mp_n_simd", "mp_last_sweeps", "mp_last_tiles", "mp_tile_log", "mp_last_tile_log",
     "mp_get_policy", "mp_create_multi", "mp_n_devices", "mp_model_band", "mp_sampler_set_temperatures", "mp_sampler_get_swaps",
+    "mp_sampler_set_moves",
 )
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -150,6 +151,7 @@ def lib():
     L.mp_sampler_get_state.argtypes = [vp, dp, dp, i64p, i64p]
     L.mp_sampler_set_temperatures.argtypes = [vp, C.c_int, dp]
     L.mp_sampler_get_swaps.argtypes = [vp, i64p]
+    L.mp_sampler_set_moves.argtypes = [vp, C.c_int, ip, dp, dp]
     L.mp_last_mean_sweeps.argtypes = [vp]
     L.mp_last_mean_sweeps.restype = C.c_double
     L.mp_last_mean_tiles.argtypes = [vp]

@@ -925,6 +925,13 @@ struct mp_sampler {
     int n_temps = 0;
     DevBuf<double> d_beta;          // [n_ensembles]
     DevBuf<int64_t> d_swaps;        // [n_ensembles / n_temps][n_temps - 1] accepted swaps
+    // proposal moves (mp_sampler_set_moves); empty: the stretch move with scale a
+    struct Move {
+        int32_t kind;
+        double p0, p1;              // stretch: a; DE: g0 (resolved), s = sigma sqrt(3); snooker: gamma_s
+    };
+    std::vector<Move> moves;
+    std::vector<double> move_cum;   // cumulative weights, summed in order
 };
 
 // Move the device window of failed proposals into the host log and reset it.  The caller has made sure that no kernel
@@ -971,6 +978,19 @@ static void draw_splits(const mp_sampler *s, uint64_t step0, int count, int32_t 
     for (int k = 1; k < n_thr; ++k) pool.emplace_back(work, k, n_thr);
     work(0, n_thr);
     for (auto &th : pool) th.join();
+}
+
+// the move of step `step` (an index into s->moves): r = Philox(seed; step, 3, 0, 0x30FE), the first m with u01(r0, r1) C_last < C_m
+static int draw_move(const mp_sampler *s, uint64_t step64) {
+    const int n = (int)s->moves.size();
+    if (n <= 1) return 0;
+    uint32_t r[4];
+    philox4x32_10((uint32_t)s->seed, (uint32_t)(s->seed >> 32), (uint32_t)step64, 3u, 0u, 0x30FEu, r);
+    const double u = (double)((((uint64_t)r[0] << 32) | r[1]) >> 11) * (1.0 / 9007199254740992.0);
+    const double x = u * s->move_cum[(size_t)n - 1];
+    for (int m = 0; m < n - 1; ++m)
+        if (x < s->move_cum[(size_t)m]) return m;
+    return n - 1;
 }
 
 static mp::StretchArgs stretch_args(const mp_sampler *s, const int32_t *d_perm, uint64_t step, int half) {
@@ -1088,6 +1108,48 @@ int mp_sampler_set_temperatures(mp_sampler *s, int n_temps, const double *betas)
     return MP_OK;
 }
 
+int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const double *weights, const double *params) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_set_moves: NULL sampler");
+    if (n_moves < 0 || n_moves > MP_MAX_MOVES) return fail(MP_EINVAL, "mp_sampler_set_moves: n_moves must be in [0, %d], got %d", MP_MAX_MOVES, n_moves);
+    if (n_moves > 0 && (!kinds || !weights || !params)) return fail(MP_EINVAL, "mp_sampler_set_moves: NULL argument");
+    const int n_half = s->n_walkers / 2;
+    std::vector<mp_sampler::Move> mv;
+    std::vector<double> cum;
+    double c = 0.0;
+    for (int m = 0; m < n_moves; ++m) {
+        const double w = weights[m], p0 = params[2 * m], p1 = params[2 * m + 1];
+        if (!std::isfinite(w) || !(w > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: weight %d must be finite and > 0, got %g", m, w);
+        mp_sampler::Move x{kinds[m], 0.0, 0.0};
+        switch (kinds[m]) {
+        case MP_MOVE_STRETCH:
+            if (!std::isfinite(p0) || !(p0 > 1.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: stretch scale a must be finite and > 1, got %g", p0);
+            x.p0 = p0;
+            break;
+        case MP_MOVE_DE:
+            if (!std::isfinite(p0) || p0 < 0.0) return fail(MP_EINVAL, "mp_sampler_set_moves: DE g0 must be finite and >= 0 (0: 2.38/sqrt(2 ndim)), got %g", p0);
+            if (!(p1 >= 0.0) || !(p1 * std::sqrt(3.0) < 1.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: DE sigma must be in [0, 1/sqrt(3)), got %g", p1);
+            if (n_half < 2) return fail(MP_EINVAL, "mp_sampler_set_moves: the DE move needs n_walkers >= 4 (two partners in the other half)");
+            x.p0 = p0 > 0.0 ? p0 : 2.38 / std::sqrt(2.0 * s->ndim);
+            x.p1 = p1 * std::sqrt(3.0);
+            break;
+        case MP_MOVE_SNOOKER:
+            if (!std::isfinite(p0) || !(p0 > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: snooker gamma_s must be finite and > 0, got %g", p0);
+            if (n_half < 3) return fail(MP_EINVAL, "mp_sampler_set_moves: the snooker move needs n_walkers >= 6 (three partners in the other half)");
+            x.p0 = p0;
+            break;
+        default:
+            return fail(MP_EINVAL, "mp_sampler_set_moves: unknown move kind %d", (int)kinds[m]);
+        }
+        mv.push_back(x);
+        c += w;
+        cum.push_back(c);
+    }
+    Lock lock(s->h->mu);
+    s->moves = std::move(mv);
+    s->move_cum = std::move(cum);
+    return MP_OK;
+}
+
 int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted) {
     if (!s || !n_swaps_accepted) return fail(MP_EINVAL, "mp_sampler_get_swaps: NULL argument");
     Lock lock(s->h->mu);
@@ -1164,11 +1226,31 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
         for (int sub = 0; sub < chunk; sub += kSub) {
             const int sub_end = std::min(chunk, sub + kSub);
             draw_splits(s, s->steps_done + (uint64_t)sub, sub_end - sub, perm + (size_t)sub * nt);
+            int step_move[kSub];   // with a move table: the move of every step of the batch, drawn next to its splits
+            for (int st = sub; st < sub_end; ++st) step_move[st - sub] = draw_move(s, s->steps_done + (uint64_t)st);
             HIP_TRY(hipMemcpyAsync(s->d_perm.p + (size_t)sub * nt, perm + (size_t)sub * nt,
                                    (size_t)(sub_end - sub) * nt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
             for (int st = sub; st < sub_end; ++st) {
+                const mp_sampler::Move *mv = s->moves.empty() ? nullptr : &s->moves[(size_t)step_move[st - sub]];
+                if (mv && mv->kind != MP_MOVE_STRETCH) {
+                    // DE / snooker: two half-step launches (the DIFF builds of stretch_kernel), then the swap sweep when tempered
+                    for (int half = 0; half < 2; ++half) {
+                        mp::StretchArgs g = stretch_args(s, s->d_perm.p + (size_t)st * nt, s->steps_done + (uint64_t)st, half);
+                        g.chain = chain ? s->d_chain.p : nullptr;
+                        g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
+                        g.chain_row = st;
+                        g.move = mv->kind;
+                        if (mv->kind == MP_MOVE_DE) { g.de_g0 = mv->p0; g.de_s = mv->p1; }
+                        else g.gamma_s = mv->p0;
+                        int e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
+                        if (!e && half == 1 && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
+                        if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+                    }
+                    continue;
+                }
                 if (whole) {
                     mp::StretchArgs g = stretch_args(s, s->d_perm.p + (size_t)st * nt, s->steps_done + (uint64_t)st, 0);
+                    if (mv) g.a = mv->p0;
                     g.chain = chain ? s->d_chain.p : nullptr;
                     g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
                     g.chain_row = st;
@@ -1181,6 +1263,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
                 }
                 for (int half = 0; half < 2; ++half) {
                     mp::StretchArgs g = stretch_args(s, s->d_perm.p + (size_t)st * nt, s->steps_done + (uint64_t)st, half);
+                    if (mv) g.a = mv->p0;
                     g.chain = chain ? s->d_chain.p : nullptr;
                     g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
                     g.chain_row = st;
@@ -1239,6 +1322,7 @@ int mp_sampler_halfstep_shard(mp_sampler *s, int half, int slot_lo, int slot_hi,
     if (!s || (half != 0 && half != 1)) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: bad argument");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_halfstep_shard: call mp_sampler_set_positions first");
     if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_halfstep_shard: a tempered sampler runs on one device only (mp_sampler_run)");
+    if (!s->moves.empty()) return fail(MP_ESTATE, "mp_sampler_halfstep_shard: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)");
     const int n_slots = (s->n_walkers / 2) * s->n_ensembles;
     if (slot_lo < 0 || slot_hi > n_slots || slot_lo > slot_hi) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: slots [%d, %d) outside [0, %d)", slot_lo, slot_hi, n_slots);
     if (slot_hi > slot_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: NULL row buffer");
@@ -1265,6 +1349,7 @@ int mp_sampler_halfstep_apply(mp_sampler *s, int half, const double *d_rows, dou
     if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_halfstep_apply: chain row and lnprob row go together");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_halfstep_apply: call mp_sampler_set_positions first");
     if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_halfstep_apply: a tempered sampler runs on one device only (mp_sampler_run)");
+    if (!s->moves.empty()) return fail(MP_ESTATE, "mp_sampler_halfstep_apply: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)");
     mp_handle *h = s->h;
     Lock lock(h->mu);
     DeviceScope scope(h->device);
@@ -1292,6 +1377,7 @@ int mp_sampler_step_shard(mp_sampler *s, int block_lo, int block_hi, double *d_r
     if (!s) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL sampler");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_step_shard: call mp_sampler_set_positions first");
     if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_step_shard: a tempered sampler runs on one device only (mp_sampler_run)");
+    if (!s->moves.empty()) return fail(MP_ESTATE, "mp_sampler_step_shard: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)");
     const int n_blocks = 3 * (s->n_walkers / 2) * s->n_ensembles;
     if (block_lo < 0 || block_hi > n_blocks || block_lo > block_hi) return fail(MP_EINVAL, "mp_sampler_step_shard: blocks [%d, %d) outside [0, %d)", block_lo, block_hi, n_blocks);
     if (block_hi > block_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL row buffer");
@@ -1317,6 +1403,7 @@ int mp_sampler_step_apply(mp_sampler *s, const double *d_rows, double *d_chain_r
     if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_step_apply: chain row and lnprob row go together");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_step_apply: call mp_sampler_set_positions first");
     if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_step_apply: a tempered sampler runs on one device only (mp_sampler_run)");
+    if (!s->moves.empty()) return fail(MP_ESTATE, "mp_sampler_step_apply: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)");
     mp_handle *h = s->h;
     Lock lock(h->mu);
     DeviceScope scope(h->device);

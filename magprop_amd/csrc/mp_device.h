@@ -155,6 +155,12 @@ struct StretchArgs {
     uint64_t ens_order;     // half-step launches: ensemble at position p of the launch = (ens_order >> 4p) & 15; 0 = identity
     const double *beta;     // [n_ensembles] inverse temperature of every ensemble (parallel tempering), or nullptr: 1 for all.
                             // Only the decisions use it; stored log-probabilities stay untempered
+    // the proposal of a half-step launch (mp_sampler_set_moves; appended so that the stretch builds read what they read before)
+    int32_t move;           // MP_MOVE_STRETCH (a above), MP_MOVE_DE or MP_MOVE_SNOOKER (the DIFF builds of stretch_kernel)
+    uint32_t pad2;
+    double de_g0;           // DE: gamma = de_g0 (1 + de_s (2u - 1)), de_s = sigma sqrt(3)
+    double de_s;
+    double gamma_s;         // snooker scale
 };
 
 // ---------------------------------------------------------------- compile-time constants of the stride policy

@@ -29,7 +29,8 @@
 // Kernels: lnprob_kernel<CURVES, SPL, LONG> (one wavefront per walker), stretch_kernel<SPL, LONG> (emcee's stretch
 // move fused around it) and stretch_apply_kernel (the state update of a half-step whose proposals were evaluated
 // on several GPUs); LONG = built with the path for light curves of more than 64 points.  Tempered samplers (parallel
-// tempering) take their decisions against beta x lnprob and run stretch_swap_kernel after every step.
+// tempering) take their decisions against beta x lnprob and run stretch_swap_kernel after every step.  The DIFF builds of
+// stretch_kernel propose emcee's differential-evolution and snooker moves instead (mp_sampler_set_moves).
 // No MFMA (no dense contraction anywhere on this path), fp64 throughout; bound by the VALU issue rate of one wave per
 // SIMD (profiles/, tools/ubench).  The arithmetic is algebraically simplified with respect to the reference formulas
 // (e.g. fastness w = (Rm/Rc)^1.5 = omega*Rm^1.5/sqrt(GM), eta1-eta2 = -tanh); oracle/mp_oracle.c keeps the literal
@@ -205,13 +206,74 @@ struct TeamLds<G, false> {
     __device__ TeamX<G> *ptr() { return nullptr; }
 };
 
+// ---- differential-evolution and snooker proposals (the DIFF builds of stretch_kernel; include/magprop_amd.h MP_MOVE_*)
+// Index draws over the m slots of the complementary half: pick(u, m) = min(floor(u m), m - 1); a second index distinct from a
+// first is drawn over m - 1 and steps over it, a third over m - 2 and steps over the first two in increasing order.
+MP_DEV int pick(double u, int m) { return min((int)(u * m), m - 1); }
+MP_DEV int pick_skip(double u, int m, int c) {
+    const int t = pick(u, m - 1);
+    return t >= c ? t + 1 : t;
+}
+MP_DEV int pick_skip2(double u, int m, int c0, int c1) {
+    int t = pick(u, m - 2);
+    t = t >= min(c0, c1) ? t + 1 : t;
+    return t >= max(c0, c1) ? t + 1 : t;
+}
+// The proposal par[] of walker k and, for the snooker move, the sums behind its Hastings term (qq = sum (q - z)^2, dd =
+// sum (x_k - z)^2, in index order).  r = Philox(...; c3 = 2), r2 = Philox(...; c3 = 3).  Unfused, like the stretch move.
+//   DE (ter Braak 2006):        partners j1, j2;  gamma = g0 (1 + s (2 u - 1));  q = x_k + gamma (x_j1 - x_j2)
+//   snooker (ter Braak & Vrugt 2008): partners z, z1, z2;  d = x_k - z;  q = x_k + (gamma_s (d.(z1 - z2)) / (d.d)) d
+MP_DEV void diff_proposal(const StretchArgs &g, int k, int base, const int32_t *perm, int n_comp, const uint32_t (&r)[4],
+                          const uint32_t (&r2)[4], double (&par)[MP_MAX_NDIM], double &qq, double &dd) {
+    const int32_t *comp = perm + (1 - g.half) * g.n_half;
+    const double *xk = g.pos + (size_t)k * g.ndim;
+    if (g.move == MP_MOVE_DE) {
+        const int c1 = pick(u01(r[0], r[1]), n_comp);
+        const int c2 = pick_skip(u01(r[2], r[3]), n_comp, c1);
+        const double *x1 = g.pos + (size_t)(base + comp[c1]) * g.ndim, *x2 = g.pos + (size_t)(base + comp[c2]) * g.ndim;
+        const double gamma = mul_rn(g.de_g0, add_rn(1.0, mul_rn(g.de_s, sub_rn(mul_rn(2.0, u01(r2[0], r2[1])), 1.0))));
+#pragma unroll
+        for (int i = 0; i < MP_MAX_NDIM; ++i) par[i] = i < g.ndim ? add_rn(xk[i], mul_rn(gamma, sub_rn(x1[i], x2[i]))) : 0.0;
+        qq = dd = 1.0;
+        return;
+    }
+    const int cz = pick(u01(r[0], r[1]), n_comp);
+    const int c1 = pick_skip(u01(r[2], r[3]), n_comp, cz);
+    const int c2 = pick_skip2(u01(r2[0], r2[1]), n_comp, cz, c1);
+    const double *z = g.pos + (size_t)(base + comp[cz]) * g.ndim;
+    const double *z1 = g.pos + (size_t)(base + comp[c1]) * g.ndim, *z2 = g.pos + (size_t)(base + comp[c2]) * g.ndim;
+    double d[MP_MAX_NDIM], p = 0.0;
+    dd = 0.0;
+#pragma unroll
+    for (int i = 0; i < MP_MAX_NDIM; ++i) {
+        d[i] = i < g.ndim ? sub_rn(xk[i], z[i]) : 0.0;
+        if (i < g.ndim) {
+            dd = add_rn(dd, mul_rn(d[i], d[i]));
+            p = add_rn(p, mul_rn(d[i], sub_rn(z1[i], z2[i])));
+        }
+    }
+    const double f = mul_rn(g.gamma_s, p / dd);   // dd = 0: NaN, and the Hastings term rejects the proposal
+    qq = 0.0;
+#pragma unroll
+    for (int i = 0; i < MP_MAX_NDIM; ++i) {
+        par[i] = i < g.ndim ? add_rn(xk[i], mul_rn(f, d[i])) : 0.0;
+        if (i < g.ndim) {
+            const double e = sub_rn(par[i], z[i]);
+            qq = add_rn(qq, mul_rn(e, e));
+        }
+    }
+}
+
 // W, OCC: small ensembles evaluate every proposal on a team of W = 4 wavefronts (lnprob_team_kernel; OCC = wavefronts resident
 // per SIMD the build is made for), chosen by the size of a WHOLE step of the sampler (stretch_waves, mp_device.h) so that one
 // launch per step and one per half-step run the same arithmetic: the chains stay equal bit for bit.
 // TEMPERED: the builds of tempered samplers (g.beta set), which decide against beta x lnprob.  Separate builds, because even a
 // read of beta behind the evaluation moves the register allocation of walker_eval (scratch and SGPR spills of the untempered
 // builds would change with it); the untempered builds are the code they were.
-template <int SPL, bool LONG, int W = 1, int OCC = 0, bool TEMPERED = false>
+// DIFF: the builds of the differential-evolution and snooker moves (g.move, decided at run time): only the proposal stage
+// differs -- partners, proposal, Hastings term and ln u, from the counters c3 = 2, 3 -- and the stretch builds are the code
+// they were.  Evaluation, decision, commit, chain row and failure log are shared.
+template <int SPL, bool LONG, int W = 1, int OCC = 0, bool TEMPERED = false, bool DIFF = false>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
 void stretch_kernel(const DevShared sh, const StretchArgs g) {
     __shared__ TileImage<SPL * W> im;
@@ -228,8 +290,8 @@ void stretch_kernel(const DevShared sh, const StretchArgs g) {
     const int base = w_ens * g.n_walkers;
     const int k = base + perm[g.half * g.n_half + slot];           // active walker (global index)
     uint32_t r[4], r2[4];
-    philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, 0u, r);
-    philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, 1u, r2);
+    philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, DIFF ? 2u : 0u, r);
+    philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, DIFF ? 3u : 1u, r2);
     const int n_comp = g.n_walkers - g.n_half;
     const int jc = (int)(u01(r[0], r[1]) * n_comp);                // partner from the complementary half
     const int j = base + perm[(1 - g.half) * g.n_half + min(jc, n_comp - 1)];
@@ -237,15 +299,23 @@ void stretch_kernel(const DevShared sh, const StretchArgs g) {
     const double zr = add_rn(mul_rn(g.a - 1.0, u01(r[2], r[3])), 1.0);
     const double zz = mul_rn(zr, zr) / g.a;                      // g(z) ~ 1/sqrt(z) on [1/a, a]
     double par[MP_MAX_NDIM];
+    double qq = 1.0, dd = 1.0;   // (DIFF: the snooker move's sums)
+    if constexpr (DIFF) {
+        // (the stretch draw above is dead code here; it stays first because moving it into the else branch changed the SGPR
+        // spills of four stretch builds)
+        diff_proposal(g, k, base, perm, n_comp, r, r2, par, qq, dd);
+    } else {
 #pragma unroll
-    for (int i = 0; i < MP_MAX_NDIM; ++i) {
-        const double xk = i < g.ndim ? g.pos[(size_t)k * g.ndim + i] : 0.0;
-        const double xj = i < g.ndim ? g.pos[(size_t)j * g.ndim + i] : 0.0;
-        par[i] = sub_rn(xj, mul_rn(sub_rn(xj, xk), zz));
+        for (int i = 0; i < MP_MAX_NDIM; ++i) {
+            const double xk = i < g.ndim ? g.pos[(size_t)k * g.ndim + i] : 0.0;
+            const double xj = i < g.ndim ? g.pos[(size_t)j * g.ndim + i] : 0.0;
+            par[i] = sub_rn(xj, mul_rn(sub_rn(xj, xk), zz));
+        }
     }
     // Nothing of the draw stays live across walker_eval (which needs every register): lane 0 parks the proposal, the
     // acceptance threshold and the walker's current value in LDS and reads them back behind the evaluation.
-    //   park[0 .. ndim-1] proposal, [ndim] (ndim - 1) ln z, [ndim + 1] ln u, [ndim + 2] lnprob of the walker now
+    //   park[0 .. ndim-1] proposal, [ndim] Hastings term ((ndim - 1) ln z; DE 0; snooker (ndim - 1)/2 ln(qq / dd)),
+    //   [ndim + 1] ln u, [ndim + 2] lnprob of the walker now
     const bool lane0 = W > 1 ? threadIdx.x == 0 : (threadIdx.x & 63) == 0;   // (of the team's first wavefront)
     double lnp = 0.0;
     if (g.target == 1) {   // isotropic unit Gaussian: exercises the move itself (tests)
@@ -255,8 +325,13 @@ void stretch_kernel(const DevShared sh, const StretchArgs g) {
     if (lane0) {
 #pragma unroll
         for (int i = 0; i < MP_MAX_NDIM; ++i) park[i] = par[i];
-        park[MP_MAX_NDIM] = mul_rn(g.ndim - 1.0, log(zz));
-        park[MP_MAX_NDIM + 1] = log(u01(r2[0], r2[1]));
+        if constexpr (!DIFF) {
+            park[MP_MAX_NDIM] = mul_rn(g.ndim - 1.0, log(zz));
+            park[MP_MAX_NDIM + 1] = log(u01(r2[0], r2[1]));
+        } else {
+            park[MP_MAX_NDIM] = g.move == MP_MOVE_DE ? 0.0 : mul_rn(mul_rn(0.5, g.ndim - 1.0), sub_rn(log(qq), log(dd)));
+            park[MP_MAX_NDIM + 1] = log(u01(r2[2], r2[3]));
+        }
         park[MP_MAX_NDIM + 2] = g.lnprob[k];
     }
     int status = MP_STATUS_OK, sweeps, tiles;
@@ -645,34 +720,36 @@ int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
     return (int)hipGetLastError();
 }
 
-// n_blocks slots of the active half starting at g.slot_lo
-template <bool TEMPERED>
+// n_blocks slots of the active half starting at g.slot_lo; DIFF: the DE / snooker builds, chosen by the same rule
+template <bool TEMPERED, bool DIFF = false>
 static int launch_stretch_t(const DevShared &sh, const StretchArgs &g, int n_blocks, hipStream_t st) {
     dim3 grid((unsigned)n_blocks);
     const bool lng = sh.has_long != 0;
     if (stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4) {   // small ensembles: a team of four wavefronts per proposal
         if (4 * n_blocks <= sh.n_simd) {
-            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 1, TEMPERED>), grid, dim3(256), 0, st, sh, g);
-            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 1, TEMPERED>), grid, dim3(256), 0, st, sh, g);
+            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 1, TEMPERED, DIFF>), grid, dim3(256), 0, st, sh, g);
+            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 1, TEMPERED, DIFF>), grid, dim3(256), 0, st, sh, g);
         } else {
-            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 2, TEMPERED>), grid, dim3(256), 0, st, sh, g);
-            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 2, TEMPERED>), grid, dim3(256), 0, st, sh, g);
+            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 2, TEMPERED, DIFF>), grid, dim3(256), 0, st, sh, g);
+            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 2, TEMPERED, DIFF>), grid, dim3(256), 0, st, sh, g);
         }
         return (int)hipGetLastError();
     }
     if ((sh.force_spl ? sh.force_spl : kernel_spl(sh, n_blocks)) == 4) {
-        if (lng) hipLaunchKernelGGL((stretch_kernel<4, true, 1, 0, TEMPERED>), grid, dim3(64), 0, st, sh, g);
-        else hipLaunchKernelGGL((stretch_kernel<4, false, 1, 0, TEMPERED>), grid, dim3(64), 0, st, sh, g);
+        if (lng) hipLaunchKernelGGL((stretch_kernel<4, true, 1, 0, TEMPERED, DIFF>), grid, dim3(64), 0, st, sh, g);
+        else hipLaunchKernelGGL((stretch_kernel<4, false, 1, 0, TEMPERED, DIFF>), grid, dim3(64), 0, st, sh, g);
     } else {
-        if (lng) hipLaunchKernelGGL((stretch_kernel<2, true, 1, 0, TEMPERED>), grid, dim3(64), 0, st, sh, g);
-        else hipLaunchKernelGGL((stretch_kernel<2, false, 1, 0, TEMPERED>), grid, dim3(64), 0, st, sh, g);
+        if (lng) hipLaunchKernelGGL((stretch_kernel<2, true, 1, 0, TEMPERED, DIFF>), grid, dim3(64), 0, st, sh, g);
+        else hipLaunchKernelGGL((stretch_kernel<2, false, 1, 0, TEMPERED, DIFF>), grid, dim3(64), 0, st, sh, g);
     }
     return (int)hipGetLastError();
 }
 
 int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
     if (n_blocks <= 0) return 0;
-    return g.beta ? launch_stretch_t<true>(sh, g, n_blocks, (hipStream_t)stream) : launch_stretch_t<false>(sh, g, n_blocks, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (g.move != MP_MOVE_STRETCH) return g.beta ? launch_stretch_t<true, true>(sh, g, n_blocks, st) : launch_stretch_t<false, true>(sh, g, n_blocks, st);
+    return g.beta ? launch_stretch_t<true>(sh, g, n_blocks, st) : launch_stretch_t<false>(sh, g, n_blocks, st);
 }
 
 int launch_stretch_step(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {

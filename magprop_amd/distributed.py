@@ -191,9 +191,13 @@ class DistributedEnsembleSampler:
         """whole_step: None = a whole step per launch and ONE all-gather per step when the engine offers it and a rank's
         share of the 3/2 x walkers evaluations fits its device (engine.whole_step_ok); False = one launch and one gather
         per half-step (larger ensembles get that anyway).  Same chain either way.
-        A tempered sampler (EnsembleSampler(..., betas=...)) is refused: sharded tempering is not supported."""
+        A tempered sampler (EnsembleSampler(..., betas=...)) is refused: sharded tempering is not supported.  So is a sampler
+        with moves=...: sharded runs use the default stretch move."""
         if getattr(getattr(engine, "s", None), "betas", None) is not None:
             raise ValueError("DistributedEnsembleSampler: a tempered sampler runs on one device (EnsembleSampler.run_mcmc)")
+        if getattr(getattr(engine, "s", None), "moves", None) is not None:
+            raise ValueError("DistributedEnsembleSampler: a sampler with moves= runs on one device (EnsembleSampler.run_mcmc); "
+                             "sharded runs use the default stretch move")
         self.engine = engine
         self.group = group
         self.via_host = via_host       # gather through host memory: gloo rehearsal with GPU engines

@@ -11,7 +11,8 @@ stretch-move half-step as one fused kernel (propose -> lnprob -> accept -> store
 trip per half-step.  Several independent ensembles (e.g. one per GRB dataset) can be advanced together.
 With a ladder of inverse temperatures (betas=...) every dataset gets one ensemble per temperature and the sampler runs
 parallel tempering: tempered decisions in the same fused kernels plus one swap kernel per step (magprop_amd.tempering,
-EnsembleSampler.log_evidence).
+EnsembleSampler.log_evidence).  moves=... selects emcee's differential-evolution and snooker moves, or a weighted mixture
+(magprop_amd.moves), proposed inside the same fused half-step kernels.
 """
 import ctypes as C
 import sys
@@ -19,12 +20,13 @@ import sys
 import numpy as np
 
 from . import _capi, engine, synth, tempering
+from . import moves as _moves
 
 
 class EnsembleSampler:
     def __init__(self, nwalkers, ndim=6, x=None, y=None, yerr=None, variant="synth", GRBtype=None, seed=0, a=2.0,
                  datasets=None, lower="default", upper="default", log_mask=None, device=-1, target="posterior",
-                 fbad=None, sweep_tol=None, max_stride=None, whole_step=True, betas=None):
+                 fbad=None, sweep_tol=None, max_stride=None, whole_step=True, betas=None, moves=None):
         """One ensemble on dataset (x, y, yerr), or one ensemble per entry of `datasets` = [(x, y, yerr), ...].
         whole_step: small ensembles run a whole step per launch (include/magprop_amd.h mp_sampler_set_whole_step; same
         chain bit for bit as one launch per half-step, which False selects).
@@ -32,9 +34,18 @@ class EnsembleSampler:
         (code/synthetic_datasets/mcmc_eqns.py:72-79); written after every run_mcmc call.
         betas: None (untempered, as emcee), or a ladder 1 = beta_0 > beta_1 > ... > 0 (magprop_amd.tempering.check_ladder):
         parallel tempering with one ensemble per (dataset, temperature), nensembles = len(datasets) x T (T for
-        target="gaussian"), positions in ensemble order (group g, temperature t: walkers [(g T + t) nwalkers, + nwalkers))."""
+        target="gaussian"), positions in ensemble order (group g, temperature t: walkers [(g T + t) nwalkers, + nwalkers)).
+        moves: None (the stretch move with scale a, as emcee), or emcee's moves= forms over magprop_amd.moves (StretchMove,
+        DEMove, DESnookerMove): a move, a list of moves, or a list of (move, weight); one move is drawn per step
+        (include/magprop_amd.h mp_sampler_set_moves).  Give the stretch scale as StretchMove(a) then: moves together with a
+        non-default a is refused."""
         if nwalkers % 2 or nwalkers < 2:
             raise ValueError("nwalkers must be even")            # emcee requires an even number too
+        move_tab = None
+        if moves is not None:
+            if float(a) != 2.0:
+                raise ValueError("give the stretch scale as moves=StretchMove(a=...) when moves= is set, not as a=")
+            move_tab = _moves.move_table(moves, int(ndim))
         self.nwalkers, self.ndim = int(nwalkers), int(ndim)
         self._L = _capi.lib()
         tol_kw = {} if sweep_tol is None else {"sweep_tol": float(sweep_tol)}   # None: _capi.DEFAULT_SWEEP_TOL
@@ -77,6 +88,14 @@ class EnsembleSampler:
             _capi.check(self._L.mp_sampler_set_temperatures(self._s, self.ntemps, self.betas.ctypes.data_as(C.POINTER(C.c_double))),
                         "mp_sampler_set_temperatures")
         _capi.check(self._L.mp_sampler_set_whole_step(self._s, int(bool(whole_step))), "mp_sampler_set_whole_step")
+        self.moves = None if moves is None else _moves.parse_moves(moves)
+        if move_tab is not None:
+            kinds = np.asarray(move_tab[0], dtype=np.int32)
+            weights = np.asarray(move_tab[1], dtype=np.float64)
+            params = np.ascontiguousarray(move_tab[2], dtype=np.float64)
+            _capi.check(self._L.mp_sampler_set_moves(self._s, int(kinds.size), kinds.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     weights.ctypes.data_as(C.POINTER(C.c_double)),
+                                                     params.ctypes.data_as(C.POINTER(C.c_double))), "mp_sampler_set_moves")
         self.seed = int(seed)
         self._chain = None
         self._lnp = None

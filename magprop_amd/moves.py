@@ -1,0 +1,141 @@
+"""Proposal moves of the ensemble sampler, with emcee 3's names and defaults (include/magprop_amd.h MP_MOVE_*).
+
+    EnsembleSampler(..., moves=DEMove())
+    EnsembleSampler(..., moves=[(DEMove(), 0.8), (DESnookerMove(), 0.2)])
+
+Every move runs inside the fused half-step kernels; these classes only carry the parameters.  One move is drawn per step for
+the whole sampler, with probability proportional to its weight, as in emcee.  Two deviations from emcee 3.1:
+the jitter of DEMove's gamma is uniform with standard deviation sigma, not normal, and the snooker move draws its three
+partners from the other half of a two-way split, not from a four-way split.
+"""
+import math
+
+MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER = 0, 1, 2      # include/magprop_amd.h MP_MOVE_*
+MAX_MOVES = 8                                       # MP_MAX_MOVES
+
+
+class Move:
+    kind = None
+
+    def params(self, ndim):
+        """The two doubles mp_sampler_set_moves takes for this move."""
+        raise NotImplementedError
+
+    def __eq__(self, other):
+        return type(self) is type(other) and self.params(0) == other.params(0)
+
+    def __hash__(self):
+        return hash((type(self).__name__, self.params(0)))
+
+
+class StretchMove(Move):
+    """The affine-invariant stretch move (Goodman & Weare 2010), scale a > 1; emcee's default move."""
+    kind = MOVE_STRETCH
+
+    def __init__(self, a=2.0):
+        a = float(a)
+        if not (math.isfinite(a) and a > 1.0):
+            raise ValueError(f"StretchMove: a must be finite and > 1, got {a}")
+        self.a = a
+
+    def params(self, ndim):
+        return (self.a, 0.0)
+
+    def __repr__(self):
+        return f"StretchMove(a={self.a})"
+
+
+class DEMove(Move):
+    """Differential evolution (ter Braak 2006): q = x + gamma (x_j1 - x_j2), two distinct partners from the other half.
+    gamma0=None: 2.38 / sqrt(2 ndim).  gamma = gamma0 (1 + jitter), the jitter uniform with standard deviation sigma
+    (sigma < 1/sqrt(3), so gamma keeps its sign)."""
+    kind = MOVE_DE
+
+    def __init__(self, sigma=1.0e-5, gamma0=None):
+        sigma = float(sigma)
+        if not (0.0 <= sigma and sigma * math.sqrt(3.0) < 1.0):
+            raise ValueError(f"DEMove: sigma must be in [0, 1/sqrt(3)), got {sigma}")
+        if gamma0 is not None:
+            gamma0 = float(gamma0)
+            if not (math.isfinite(gamma0) and gamma0 > 0.0):
+                raise ValueError(f"DEMove: gamma0 must be finite and > 0 (or None), got {gamma0}")
+        self.sigma, self.gamma0 = sigma, gamma0
+
+    def params(self, ndim):
+        return (0.0 if self.gamma0 is None else self.gamma0, self.sigma)   # 0: the library's 2.38 / sqrt(2 ndim)
+
+    def __repr__(self):
+        return f"DEMove(sigma={self.sigma}, gamma0={self.gamma0})"
+
+
+class DESnookerMove(Move):
+    """The snooker move (ter Braak & Vrugt 2008): along the line through x and a partner z, by gammas times the projection of
+    the difference of two further partners, with its Hastings term (ndim - 1) ln(|q - z| / |x - z|)."""
+    kind = MOVE_SNOOKER
+
+    def __init__(self, gammas=1.7):
+        gammas = float(gammas)
+        if not (math.isfinite(gammas) and gammas > 0.0):
+            raise ValueError(f"DESnookerMove: gammas must be finite and > 0, got {gammas}")
+        self.gammas = gammas
+
+    def params(self, ndim):
+        return (self.gammas, 0.0)
+
+    def __repr__(self):
+        return f"DESnookerMove(gammas={self.gammas})"
+
+
+def parse_moves(moves):
+    """emcee's forms of moves=: a move, a list of moves (equal weights) or a list of (move, weight).  Returns a list of
+    (move, weight).  Weights are kept as given (emcee normalises them; the draw is the same up to rounding)."""
+    if isinstance(moves, Move):
+        return [(moves, 1.0)]
+    try:
+        items = list(moves)
+    except TypeError:
+        raise ValueError(f"moves must be a move, a list of moves or a list of (move, weight), got {moves!r}") from None
+    if not items:
+        raise ValueError("moves is empty")
+    if len(items) > MAX_MOVES:
+        raise ValueError(f"at most {MAX_MOVES} moves, got {len(items)}")
+    out = []
+    for it in items:
+        if isinstance(it, Move):
+            out.append((it, 1.0))
+            continue
+        try:
+            mv, w = it
+        except (TypeError, ValueError):
+            raise ValueError(f"moves entries must be moves or (move, weight) pairs, got {it!r}") from None
+        if not isinstance(mv, Move):
+            raise ValueError(f"not a move: {mv!r} (StretchMove, DEMove, DESnookerMove)")
+        w = float(w)
+        if not (math.isfinite(w) and w > 0.0):
+            raise ValueError(f"move weights must be finite and > 0, got {w}")
+        out.append((mv, w))
+    if any(isinstance(it, Move) for it in items) and not all(isinstance(it, Move) for it in items):
+        raise ValueError("moves mixes bare moves and (move, weight) pairs")
+    return out
+
+
+def move_table(moves, ndim):
+    """(kinds, weights, params[n][2]) of a parsed list, as mp_sampler_set_moves takes them."""
+    table = parse_moves(moves)
+    kinds = [m.kind for m, _ in table]
+    weights = [w for _, w in table]
+    params = [m.params(ndim) for m, _ in table]
+    return kinds, weights, params
+
+
+def parse_spec(spec):
+    """'de:0.8,snooker:0.2' (the command-line form of tools/run_synth_mcmc.py) -> [(DEMove(), 0.8), (DESnookerMove(), 0.2)].
+    Names: stretch, de, snooker; a missing weight is 1."""
+    names = {"stretch": StretchMove, "de": DEMove, "snooker": DESnookerMove}
+    out = []
+    for part in str(spec).split(","):
+        name, _, w = part.strip().partition(":")
+        if name not in names:
+            raise ValueError(f"unknown move {name!r} in {spec!r} (stretch, de, snooker)")
+        out.append((names[name](), float(w) if w else 1.0))
+    return out

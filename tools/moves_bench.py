@@ -1,0 +1,132 @@
+"""Throughput and mixing of the sampler's proposal moves (EnsembleSampler(..., moves=...)) on Humped, one GPU.
+
+    python tools/moves_bench.py rate [--sizes 64,512,1024,4096]   walker-steps/s and acceptance of every configuration
+    python tools/moves_bench.py tau                               integrated autocorrelation time per move, 512 walkers x 6 000 steps
+    python tools/moves_bench.py profile --walkers 1024            a short DE run to profile (rocprofv3 --kernel-trace --stats -- ...)
+
+Configurations: stretch with its default launch (a whole step per launch where it fits), stretch with whole_step=False (the
+launches DE and snooker run: two half-step launches per step), DE, snooker, and the mixture 0.8 DE + 0.2 snooker.
+Rate: every sampler starts at the Humped truth (1e-4 ball), runs --warm steps unstored, then --steps timed steps unstored
+(mp_sampler_run returns when its steps are done).  Tau: --tau-steps stored steps, the first quarter discarded; effective samples
+per second = walker-steps/s of the rate run at the same size / mean tau over the six parameters.
+Prints one JSON line; --out also writes it to a file.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from magprop_amd import DEMove, DESnookerMove, EnsembleSampler  # noqa: E402
+
+TRUTH = [1.0, 5.0, -3.0, 2.0, -1.0, 0.0]     # Humped, sampler coordinates
+CONFIGS = {
+    "stretch": dict(),
+    "stretch_half_steps": dict(whole_step=False),
+    "de": dict(moves=DEMove()),
+    "snooker": dict(moves=DESnookerMove()),
+    "de0.8_snooker0.2": dict(moves=[(DEMove(), 0.8), (DESnookerMove(), 0.2)]),
+}
+
+
+def data():
+    g = np.load(os.path.join(ROOT, "tests", "golden", "golden_synth.npz"))
+    return g["Humped_x"], g["Humped_y"], g["Humped_yerr"]
+
+
+def _start(nwalk, seed):
+    return np.array(TRUTH) + 1.0e-4 * np.random.default_rng(seed).standard_normal((nwalk, 6))
+
+
+def rate_at(nwalk, warm, steps):
+    x, y, yerr = data()
+    rows = {}
+    for name, kw in CONFIGS.items():
+        s = EnsembleSampler(nwalk, 6, x, y, yerr, seed=1, **kw)
+        s.run_mcmc(_start(nwalk, 0), warm, store=False)
+        a0 = s.get_last_sample()[2].copy()
+        t0 = time.perf_counter()
+        s.run_mcmc(None, steps, store=False)
+        dt = time.perf_counter() - t0
+        acc = (s.get_last_sample()[2] - a0) / steps
+        nbad, _ = s.get_bad()
+        rows[name] = {"ms_per_step": dt / steps * 1e3, "walker_steps_per_s": nwalk * steps / dt,
+                      "acceptance": float(acc.mean()), "failed_proposal_fraction": nbad / (nwalk * (warm + steps))}
+        s.close()
+    base, half = rows["stretch"]["walker_steps_per_s"], rows["stretch_half_steps"]["walker_steps_per_s"]
+    for r in rows.values():
+        r["over_stretch_default"] = r["walker_steps_per_s"] / base
+        r["over_stretch_half_steps"] = r["walker_steps_per_s"] / half
+    return rows
+
+
+def rate(args):
+    out = {"what": "proposal moves, walker-steps/s on Humped near the truths", "warm": args.warm, "steps": args.steps, "sizes": {}}
+    for n in [int(v) for v in args.sizes.split(",")]:
+        out["sizes"][str(n)] = rate_at(n, args.warm, args.steps)
+    # gate: DE and snooker at >= 0.85 x the stretch move on the same launches (whole_step=False)
+    out["gate_min_over_half_steps"] = min(r[k]["over_stretch_half_steps"] for r in out["sizes"].values()
+                                          for k in ("de", "snooker", "de0.8_snooker0.2"))
+    return out
+
+
+def tau(args):
+    x, y, yerr = data()
+    nwalk, n_steps = args.walkers, args.tau_steps
+    rates = rate_at(nwalk, args.warm, args.steps)
+    out = {"what": f"integrated autocorrelation time on Humped, {nwalk} walkers x {n_steps} steps from the truths, first quarter "
+                   "discarded; effective samples/s = walker-steps/s / mean tau", "walkers": nwalk, "steps": n_steps, "moves": {}}
+    for name, kw in CONFIGS.items():
+        if name == "stretch_half_steps":
+            continue                                   # the chain of "stretch", bit for bit
+        s = EnsembleSampler(nwalk, 6, x, y, yerr, seed=2, **kw)
+        s.run_mcmc(_start(nwalk, 1), n_steps)
+        chain = s.get_chain()[n_steps // 4:]
+        from magprop_amd.mcmc_io import integrated_time
+        t = integrated_time(chain, c=5.0, tol=50, quiet=True)
+        r = rates[name]
+        out["moves"][name] = {"tau": [float(v) for v in t], "tau_mean": float(np.mean(t)),
+                              "acceptance": float(s.acceptance_fraction.mean()), "walker_steps_per_s": r["walker_steps_per_s"],
+                              "effective_samples_per_s": r["walker_steps_per_s"] / float(np.mean(t)),
+                              "median": [float(v) for v in np.median(chain.reshape(-1, 6), axis=0)],
+                              "std": [float(v) for v in chain.reshape(-1, 6).std(axis=0)]}
+        s.close()
+    ref = out["moves"]["stretch"]["effective_samples_per_s"]
+    for r in out["moves"].values():
+        r["ess_rate_over_stretch"] = r["effective_samples_per_s"] / ref
+    return out
+
+
+def profile(args):
+    x, y, yerr = data()
+    s = EnsembleSampler(args.walkers, 6, x, y, yerr, seed=1, moves=DEMove())
+    s.run_mcmc(_start(args.walkers, 0), args.steps, store=False)
+    s.close()
+    return {"what": "profiling run (DE)", "walkers": args.walkers, "steps": args.steps}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("mode", choices=("rate", "tau", "profile"))
+    ap.add_argument("--sizes", default="64,512,1024,4096")
+    ap.add_argument("--walkers", type=int, default=512)
+    ap.add_argument("--warm", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--tau-steps", type=int, default=6000)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    res = {"rate": rate, "tau": tau, "profile": profile}[args.mode](args)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -17,7 +17,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from magprop_amd import EnsembleSampler, mcmc_io  # noqa: E402
+from magprop_amd import EnsembleSampler, mcmc_io, moves  # noqa: E402
 
 TRUTHS = {"Humped": [1.0, 5.0, -3.0, 2.0, -1.0, 0.0], "Classic": [1.0, 5.0, -3.0, 3.0, -1.0, 0.0],
           "Sloped": [1.0, 1.0, -3.0, 2.0, 1.0, 1.0], "Stuttering": [1.0, 5.0, -5.0, 2.0, -1.0, 2.0]}
@@ -32,6 +32,7 @@ def main(argv=None):
     ap.add_argument("--data", default=None, help="x,y,yerr CSV (default: the seeded golden dataset)")
     ap.add_argument("--out", default="synth_out")
     ap.add_argument("-r", "--re-run", action="store_true", help="repeat the run recorded in <out>/<grb>_info.json")
+    ap.add_argument("--moves", default=None, help="proposal moves, e.g. de:0.8,snooker:0.2 (default: the stretch move)")
     a = ap.parse_args(argv)
     if a.re_run:
         rec = mcmc_io.read_info(os.path.join(a.out, a.grb + "_info.json"))
@@ -48,7 +49,7 @@ def main(argv=None):
     base = os.path.join(a.out, a.grb)
     rng = np.random.default_rng(a.seed)
     pos = np.array(TRUTHS[a.grb]) + 1.0e-4 * rng.standard_normal((a.n_walk, 6))      # synth_mcmc.py:175-176
-    s = EnsembleSampler(a.n_walk, 6, x, y, yerr, seed=a.seed)
+    s = EnsembleSampler(a.n_walk, 6, x, y, yerr, seed=a.seed, moves=None if a.moves is None else moves.parse_spec(a.moves))
     t0 = time.perf_counter()
     s.run_mcmc(pos, a.n_step)
     dt = time.perf_counter() - t0
