@@ -885,18 +885,6 @@ int mp_synchronize(mp_handle *h) {
 }
 
 // ---------------------------------------------------------------- ensemble sampler (stretch move)
-// Philox4x32-10 (same function as in mp_kernels.hip); the host uses it for the random red/blue split.
-static void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out[4]) {
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 struct mp_sampler {
     mp_handle *h = nullptr;
     int n_walkers = 0, n_ensembles = 0, n_total = 0, ndim = 0, target = 0;
@@ -957,7 +945,7 @@ static void draw_split(const mp_sampler *s, uint64_t step64, int32_t *perm) {
         std::iota(p, p + s->n_walkers, 0);
         for (int i = s->n_walkers - 1; i > 0; --i) {
             uint32_t r[4];
-            philox4x32_10((uint32_t)s->seed, (uint32_t)(s->seed >> 32), step, (uint32_t)e, (uint32_t)i, 0x5117u, r);
+            mp::philox4x32_10((uint32_t)s->seed, (uint32_t)(s->seed >> 32), step, (uint32_t)e, (uint32_t)i, 0x5117u, r);
             const uint64_t r64 = ((uint64_t)r[0] << 32) | r[1];
             std::swap(p[i], p[(size_t)(r64 % (uint64_t)(i + 1))]);
         }
@@ -985,9 +973,8 @@ static int draw_move(const mp_sampler *s, uint64_t step64) {
     const int n = (int)s->moves.size();
     if (n <= 1) return 0;
     uint32_t r[4];
-    philox4x32_10((uint32_t)s->seed, (uint32_t)(s->seed >> 32), (uint32_t)step64, 3u, 0u, 0x30FEu, r);
-    const double u = (double)((((uint64_t)r[0] << 32) | r[1]) >> 11) * (1.0 / 9007199254740992.0);
-    const double x = u * s->move_cum[(size_t)n - 1];
+    mp::philox4x32_10((uint32_t)s->seed, (uint32_t)(s->seed >> 32), (uint32_t)step64, 3u, 0u, 0x30FEu, r);
+    const double x = mp::u01(r[0], r[1]) * s->move_cum[(size_t)n - 1];
     for (int m = 0; m < n - 1; ++m)
         if (x < s->move_cum[(size_t)m]) return m;
     return n - 1;
@@ -1190,6 +1177,36 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
     return MP_OK;
 }
 
+// Enqueue step steps_done + row of mp_sampler_run on the handle's stream: split d_perm, chain row `row` of the device slab when
+// chain is set, move mv (nullptr: the stretch move of mp_sampler_create).  A whole step per launch (stretch_step_kernel and the
+// commit kernel) where `whole` and the move is the stretch move, else two half-step launches; then the swap sweep when tempered.
+static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_sampler::Move *mv, bool chain, bool whole) {
+    mp_handle *h = s->h;
+    mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done + (uint64_t)row, 0);
+    g.chain = chain ? s->d_chain.p : nullptr;
+    g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
+    g.chain_row = row;
+    if (mv) {
+        g.move = mv->kind;
+        if (mv->kind == MP_MOVE_STRETCH) g.a = mv->p0;
+        else if (mv->kind == MP_MOVE_DE) { g.de_g0 = mv->p0; g.de_s = mv->p1; }
+        else g.gamma_s = mv->p0;
+    }
+    int e;
+    if (whole && g.move == MP_MOVE_STRETCH) {
+        g.spec = s->d_spec.p;
+        e = mp::launch_stretch_step(h->sh, g, 3 * g.n_half * g.n_ensembles, h->stream);
+        if (!e) e = mp::launch_stretch_step_commit(g, h->stream);
+    } else {
+        e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
+        g.half = 1;
+        if (!e) e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
+    }
+    if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    return MP_OK;
+}
+
 int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnprob) {
     if (!s || n_steps < 0) return fail(MP_EINVAL, "mp_sampler_run: bad argument");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_run: call mp_sampler_set_positions first");
@@ -1232,45 +1249,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
                                    (size_t)(sub_end - sub) * nt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
             for (int st = sub; st < sub_end; ++st) {
                 const mp_sampler::Move *mv = s->moves.empty() ? nullptr : &s->moves[(size_t)step_move[st - sub]];
-                if (mv && mv->kind != MP_MOVE_STRETCH) {
-                    // DE / snooker: two half-step launches (the DIFF builds of stretch_kernel), then the swap sweep when tempered
-                    for (int half = 0; half < 2; ++half) {
-                        mp::StretchArgs g = stretch_args(s, s->d_perm.p + (size_t)st * nt, s->steps_done + (uint64_t)st, half);
-                        g.chain = chain ? s->d_chain.p : nullptr;
-                        g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
-                        g.chain_row = st;
-                        g.move = mv->kind;
-                        if (mv->kind == MP_MOVE_DE) { g.de_g0 = mv->p0; g.de_s = mv->p1; }
-                        else g.gamma_s = mv->p0;
-                        int e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
-                        if (!e && half == 1 && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
-                        if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-                    }
-                    continue;
-                }
-                if (whole) {
-                    mp::StretchArgs g = stretch_args(s, s->d_perm.p + (size_t)st * nt, s->steps_done + (uint64_t)st, 0);
-                    if (mv) g.a = mv->p0;
-                    g.chain = chain ? s->d_chain.p : nullptr;
-                    g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
-                    g.chain_row = st;
-                    g.spec = s->d_spec.p;
-                    int e = mp::launch_stretch_step(h->sh, g, 3 * n_slots, h->stream);
-                    if (!e) e = mp::launch_stretch_step_commit(g, h->stream);
-                    if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
-                    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-                    continue;
-                }
-                for (int half = 0; half < 2; ++half) {
-                    mp::StretchArgs g = stretch_args(s, s->d_perm.p + (size_t)st * nt, s->steps_done + (uint64_t)st, half);
-                    if (mv) g.a = mv->p0;
-                    g.chain = chain ? s->d_chain.p : nullptr;
-                    g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
-                    g.chain_row = st;
-                    int e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
-                    if (!e && half == 1 && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
-                    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-                }
+                if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, chain != nullptr, whole))) return rc;
             }
         }
         if (chain) {
@@ -1318,27 +1297,35 @@ static int current_split(mp_sampler *s, hipStream_t st, const int32_t **d_perm) 
 int mp_sampler_row_doubles(const mp_sampler *s) { return s ? s->ndim + 3 : 0; }
 int mp_sampler_n_slots(const mp_sampler *s) { return s ? (s->n_walkers / 2) * s->n_ensembles : 0; }
 
+// The prologue of the four sharded entry points (fn: the entry point, which every message starts with): a sampler without state,
+// a tempered one and one with a move table are refused (those run through mp_sampler_run only); otherwise the handle's lock and
+// device are held for the call, d_perm is the split of the current step and the sampler notes work on a caller's stream.
+struct ShardCall {
+    Lock lock;
+    DeviceScope scope;
+    const int32_t *d_perm = nullptr;
+    int rc = MP_OK;
+    ShardCall(mp_sampler *s, const char *fn, void *stream) : lock(s->h->mu), scope(s->h->device) {
+        if (!s->have_state) rc = fail(MP_ESTATE, "%s: call mp_sampler_set_positions first", fn);
+        else if (s->n_temps) rc = fail(MP_ESTATE, "%s: a tempered sampler runs on one device only (mp_sampler_run)", fn);
+        else if (!s->moves.empty())
+            rc = fail(MP_ESTATE, "%s: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)", fn);
+        else if (!(rc = current_split(s, (hipStream_t)stream, &d_perm))) s->ext_stream_work = true;
+    }
+};
+
 int mp_sampler_halfstep_shard(mp_sampler *s, int half, int slot_lo, int slot_hi, double *d_rows, void *stream) {
     if (!s || (half != 0 && half != 1)) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: bad argument");
-    if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_halfstep_shard: call mp_sampler_set_positions first");
-    if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_halfstep_shard: a tempered sampler runs on one device only (mp_sampler_run)");
-    if (!s->moves.empty()) return fail(MP_ESTATE, "mp_sampler_halfstep_shard: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)");
+    ShardCall c(s, "mp_sampler_halfstep_shard", stream);
+    if (c.rc) return c.rc;
     const int n_slots = (s->n_walkers / 2) * s->n_ensembles;
     if (slot_lo < 0 || slot_hi > n_slots || slot_lo > slot_hi) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: slots [%d, %d) outside [0, %d)", slot_lo, slot_hi, n_slots);
     if (slot_hi > slot_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: NULL row buffer");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const int32_t *d_perm = nullptr;
-    int rc;
-    if ((rc = current_split(s, st, &d_perm))) return rc;
-    s->ext_stream_work = true;
     if (slot_hi == slot_lo) return MP_OK;
-    mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done, half);
+    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, half);
     g.upd = d_rows;
     g.slot_lo = slot_lo;
-    const int e = mp::launch_stretch(h->sh, g, slot_hi - slot_lo, stream);
+    const int e = mp::launch_stretch(s->h->sh, g, slot_hi - slot_lo, stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return MP_OK;
 }
@@ -1347,17 +1334,9 @@ int mp_sampler_halfstep_apply(mp_sampler *s, int half, const double *d_rows, dou
                               void *stream) {
     if (!s || !d_rows || (half != 0 && half != 1)) return fail(MP_EINVAL, "mp_sampler_halfstep_apply: bad argument");
     if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_halfstep_apply: chain row and lnprob row go together");
-    if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_halfstep_apply: call mp_sampler_set_positions first");
-    if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_halfstep_apply: a tempered sampler runs on one device only (mp_sampler_run)");
-    if (!s->moves.empty()) return fail(MP_ESTATE, "mp_sampler_halfstep_apply: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const int32_t *d_perm = nullptr;
-    int rc;
-    if ((rc = current_split(s, (hipStream_t)stream, &d_perm))) return rc;
-    s->ext_stream_work = true;
-    mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done, half);
+    ShardCall c(s, "mp_sampler_halfstep_apply", stream);
+    if (c.rc) return c.rc;
+    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, half);
     g.upd = const_cast<double *>(d_rows);
     g.chain = d_chain_row;
     g.chain_lnp = d_chain_lnp_row;
@@ -1375,25 +1354,16 @@ int mp_sampler_step_row_doubles(const mp_sampler *s) { return s ? s->ndim + mp::
 
 int mp_sampler_step_shard(mp_sampler *s, int block_lo, int block_hi, double *d_rows, void *stream) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL sampler");
-    if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_step_shard: call mp_sampler_set_positions first");
-    if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_step_shard: a tempered sampler runs on one device only (mp_sampler_run)");
-    if (!s->moves.empty()) return fail(MP_ESTATE, "mp_sampler_step_shard: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)");
+    ShardCall c(s, "mp_sampler_step_shard", stream);
+    if (c.rc) return c.rc;
     const int n_blocks = 3 * (s->n_walkers / 2) * s->n_ensembles;
     if (block_lo < 0 || block_hi > n_blocks || block_lo > block_hi) return fail(MP_EINVAL, "mp_sampler_step_shard: blocks [%d, %d) outside [0, %d)", block_lo, block_hi, n_blocks);
     if (block_hi > block_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL row buffer");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const int32_t *d_perm = nullptr;
-    int rc;
-    if ((rc = current_split(s, st, &d_perm))) return rc;
-    s->ext_stream_work = true;
     if (block_hi == block_lo) return MP_OK;
-    mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done, 0);
+    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, 0);
     g.spec = d_rows;
     g.slot_lo = block_lo;
-    const int e = mp::launch_stretch_step(h->sh, g, block_hi - block_lo, stream);
+    const int e = mp::launch_stretch_step(s->h->sh, g, block_hi - block_lo, stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return MP_OK;
 }
@@ -1401,17 +1371,9 @@ int mp_sampler_step_shard(mp_sampler *s, int block_lo, int block_hi, double *d_r
 int mp_sampler_step_apply(mp_sampler *s, const double *d_rows, double *d_chain_row, double *d_chain_lnp_row, void *stream) {
     if (!s || !d_rows) return fail(MP_EINVAL, "mp_sampler_step_apply: bad argument");
     if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_step_apply: chain row and lnprob row go together");
-    if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_step_apply: call mp_sampler_set_positions first");
-    if (s->n_temps) return fail(MP_ESTATE, "mp_sampler_step_apply: a tempered sampler runs on one device only (mp_sampler_run)");
-    if (!s->moves.empty()) return fail(MP_ESTATE, "mp_sampler_step_apply: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const int32_t *d_perm = nullptr;
-    int rc;
-    if ((rc = current_split(s, (hipStream_t)stream, &d_perm))) return rc;
-    s->ext_stream_work = true;
-    mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done, 0);
+    ShardCall c(s, "mp_sampler_step_apply", stream);
+    if (c.rc) return c.rc;
+    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, 0);
     g.spec = const_cast<double *>(d_rows);
     g.chain = d_chain_row;
     g.chain_lnp = d_chain_lnp_row;

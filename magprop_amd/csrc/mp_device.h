@@ -4,7 +4,31 @@
 
 #include "../../include/magprop_amd.h"
 
+#if defined(__HIP__) || defined(__HIPCC__)
+#define MP_HD __host__ __device__
+#else
+#define MP_HD
+#endif
+
 namespace mp {
+
+// Counter-based RNG (Philox4x32-10, Salmon et al. 2011): one independent stream per key and counter.  The kernels draw the
+// moves and swaps with it, the host the random splits and the move of every step, so the chains depend on this one definition.
+MP_HD inline void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+MP_HD inline double u01(uint32_t hi, uint32_t lo) {   // 53-bit uniform in [0, 1)
+    return (double)((((uint64_t)hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
+}
 
 constexpr int kTile = 64;    // observation bucket size in grid intervals (the kernels' tiles are 64*SPL steps)
 constexpr int kTile64 = 64;  // the same, for code inside the kernels where kTile names their own tile length

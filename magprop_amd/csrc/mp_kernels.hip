@@ -147,19 +147,6 @@ int launch_order(const DevShared &sh, const int32_t *ds_id, int n, int32_t *orde
 }
 
 // ---------------------------------------------------------------- fused stretch-move half-step kernel
-// Counter-based RNG (Philox4x32-10, Salmon et al. 2011): one independent stream per (seed, step, walker).
-MP_DEV void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 // Unfused double arithmetic (hipcc contracts a*b+c into an FMA by default, also through __dmul_rn/__dadd_rn):
 // the proposal and the test target are computed with separately rounded operations so that a numpy
 // restatement of the move reproduces the chain bit for bit.
@@ -176,10 +163,6 @@ MP_DEV double sub_rn(double a, double b) {
     return a - b;
 }
 
-MP_DEV double u01(uint32_t hi, uint32_t lo) {   // 53-bit uniform in [0, 1)
-    return (double)((((uint64_t)hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-}
-
 // One wavefront = one walker of the active half: draw the partner and the stretch factor, form the
 // proposal (emcee's StretchMove.get_proposal), evaluate its log-posterior with walker_eval, accept or
 // reject against the walker's current value, update position / lnprob / counters in place and write the
@@ -187,8 +170,8 @@ MP_DEV double u01(uint32_t hi, uint32_t lo) {   // 53-bit uniform in [0, 1)
 // A launch covers the slots [slot_lo, slot_lo + gridDim.x) of the active half (all ensembles flattened).  With g.upd set
 // (walker-sharded ensembles, one process per GPU) nothing is updated in place: the outcome of slot s goes to row
 // s - slot_lo of g.upd as (proposal[ndim], its lnprob, accepted 0/1) and stretch_apply_kernel commits the rows of all
-// ranks after the all-gather.  The random numbers are keyed by (seed; step, half, walker), so every rank draws what the
-// single-GPU launch would have drawn for the same walker.
+// ranks after the all-gather.  The random numbers (Philox, mp_device.h) are keyed by (seed; step, half, walker), so every rank
+// draws what the single-GPU launch would have drawn for the same walker.
 // Half-step launches run the ensembles in the order of StretchArgs::ens_order (mp_capi.cpp: longest light curve first, four
 // bits per position; 0 = the ensembles as they are numbered): the waves that take longest start first, as in order_kernel.
 __device__ __forceinline__ int ens_of_slot(const StretchArgs &g, int e_pos) {
@@ -363,6 +346,7 @@ void stretch_kernel(const DevShared sh, const StretchArgs g) {
             u[g.ndim + 1] = accept ? 1.0 : 0.0;
             u[g.ndim + 2] = (double)status;
         } else {
+            // (commit_outcome's sequence, written out: routing this kernel through the helper changes its register allocation)
             if (accept) {
                 for (int i = 0; i < g.ndim; ++i) g.pos[(size_t)k * g.ndim + i] = park[i];
                 g.lnprob[k] = lnp;
@@ -386,6 +370,27 @@ void stretch_kernel(const DevShared sh, const StretchArgs g) {
     }
 }
 
+// The commit of a decision on walker k (see stretch_kernel, which commits the same way from LDS): an accepted proposal u[0 ..
+// ndim - 1] of log-posterior lnp becomes the walker's state, the step's chain row is written from the state after the update, and
+// a proposal whose model failed goes to the fbad log.  lnp_old: the walker's log-posterior before the decision.
+MP_DEV void commit_outcome(const StretchArgs &g, int k, bool accept, const double *u, double lnp, double lnp_old, int status) {
+    if (accept) {
+        for (int i = 0; i < g.ndim; ++i) g.pos[(size_t)k * g.ndim + i] = u[i];
+        g.lnprob[k] = lnp;
+        g.n_accepted[k] += 1;
+    }
+    if (g.chain) {
+        double *c = g.chain + ((size_t)g.chain_row * g.n_total + k) * g.ndim;
+        for (int i = 0; i < g.ndim; ++i) c[i] = g.pos[(size_t)k * g.ndim + i];
+        g.chain_lnp[(size_t)g.chain_row * g.n_total + k] = accept ? lnp : lnp_old;
+    }
+    if (g.bad_log && (status == MP_STATUS_FLAG || status == MP_STATUS_NONFINITE)) {
+        const unsigned slot_b = atomicAdd(g.bad_count, 1u);
+        if (slot_b < g.bad_cap)
+            for (int i = 0; i < g.ndim; ++i) g.bad_log[(size_t)slot_b * g.ndim + i] = u[i];
+    }
+}
+
 // Commit one half-step from the gathered outcome rows (see stretch_kernel): one thread per slot of the active half.
 __global__ __launch_bounds__(256) void stretch_apply_kernel(const StretchArgs g) {
     const int gs = blockIdx.x * 256 + threadIdx.x;
@@ -393,24 +398,7 @@ __global__ __launch_bounds__(256) void stretch_apply_kernel(const StretchArgs g)
     const int w_ens = ens_of_slot(g, gs / g.n_half), slot = gs % g.n_half;
     const int k = w_ens * g.n_walkers + g.perm[(size_t)w_ens * g.n_walkers + g.half * g.n_half + slot];
     const double *u = g.upd + (size_t)gs * (g.ndim + 3);
-    const bool accept = u[g.ndim + 1] != 0.0;
-    const double lnp_old = g.lnprob[k];
-    if (accept) {
-        for (int i = 0; i < g.ndim; ++i) g.pos[(size_t)k * g.ndim + i] = u[i];
-        g.lnprob[k] = u[g.ndim];
-        g.n_accepted[k] += 1;
-    }
-    if (g.chain) {
-        double *c = g.chain + ((size_t)g.chain_row * g.n_total + k) * g.ndim;
-        for (int i = 0; i < g.ndim; ++i) c[i] = accept ? u[i] : g.pos[(size_t)k * g.ndim + i];
-        g.chain_lnp[(size_t)g.chain_row * g.n_total + k] = accept ? u[g.ndim] : lnp_old;
-    }
-    const int status = (int)u[g.ndim + 2];
-    if (g.bad_log && (status == MP_STATUS_FLAG || status == MP_STATUS_NONFINITE)) {
-        const unsigned slot_b = atomicAdd(g.bad_count, 1u);
-        if (slot_b < g.bad_cap)
-            for (int i = 0; i < g.ndim; ++i) g.bad_log[(size_t)slot_b * g.ndim + i] = u[i];
-    }
+    commit_outcome(g, k, u[g.ndim + 1] != 0.0, u, u[g.ndim], g.lnprob[k], (int)u[g.ndim + 2]);
 }
 
 // ---------------------------------------------------------------- a whole stretch-move step in one launch
@@ -546,24 +534,7 @@ __global__ __launch_bounds__(256) void stretch_step_commit_kernel(const StretchA
         const bool moved = accepted(g.spec + (size_t)gs_j * R);
         u = moved ? g.spec + (size_t)(2 * n_slots + gs) * R : u1;
     }
-    const bool accept = accepted(u);
-    const double lnp_old = u[g.ndim + 4];
-    if (accept) {
-        for (int i = 0; i < g.ndim; ++i) g.pos[(size_t)k * g.ndim + i] = u[i];
-        g.lnprob[k] = u[g.ndim];
-        g.n_accepted[k] += 1;
-    }
-    if (g.chain) {
-        double *c = g.chain + ((size_t)g.chain_row * g.n_total + k) * g.ndim;
-        for (int i = 0; i < g.ndim; ++i) c[i] = accept ? u[i] : g.pos[(size_t)k * g.ndim + i];
-        g.chain_lnp[(size_t)g.chain_row * g.n_total + k] = accept ? u[g.ndim] : lnp_old;
-    }
-    const int status = (int)u[g.ndim + 1];
-    if (g.bad_log && (status == MP_STATUS_FLAG || status == MP_STATUS_NONFINITE)) {
-        const unsigned slot_b = atomicAdd(g.bad_count, 1u);
-        if (slot_b < g.bad_cap)
-            for (int i = 0; i < g.ndim; ++i) g.bad_log[(size_t)slot_b * g.ndim + i] = u[i];
-    }
+    commit_outcome(g, k, accepted(u), u, u[g.ndim], u[g.ndim + 4], (int)u[g.ndim + 1]);
 }
 
 // ---------------------------------------------------------------- parallel tempering: the swap sweep of a step
@@ -651,6 +622,18 @@ int launch_rhs(const DevShared &sh, const RhsArgs &r, void *stream) {
     return (int)hipGetLastError();
 }
 
+// Run-time flags to compile-time ones: dispatch(f, b0, b1, ...) calls f(std::integral_constant<bool, b0>(), ...), so that a
+// launcher states its choice of kernel build once, as one template expression.  Every combination of the flags is instantiated.
+template <class F>
+static void dispatch(F &&f) {
+    f();
+}
+template <class F, class... B>
+static void dispatch(F &&f, bool b, B... rest) {
+    if (b) dispatch([&](auto... c) { f(std::true_type(), c...); }, rest...);
+    else dispatch([&](auto... c) { f(std::false_type(), c...); }, rest...);
+}
+
 int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
     if (a.n <= 0) return 0;
     // (the alternative dipole torque, cfg.dipole_torque = 1, lives in the curve kernels only: such a handle runs them for
@@ -663,8 +646,9 @@ int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
     //  - beyond: two steps per lane, which keeps two waves resident per SIMD (they fill each other's issue gaps);
     //  - a handle that holds a light curve of more than 64 points runs the LONG builds of the same kernels.
     //  - curve outputs (mode B): by rounds of resident workgroups, kernel_spl_curves (mp_device.h);
+    //  - diagnostics requested (a.tile_log): the LOG builds, which record the tile words.
     const bool wide = (sh.force_spl ? sh.force_spl : (curves ? kernel_spl_curves(sh, a.n) : kernel_spl(sh, a.n))) == 4;
-    const bool lng = sh.has_long != 0;
+    const bool lng = sh.has_long != 0, log = a.tile_log != nullptr || kAlwaysLog;
     hipStream_t st = (hipStream_t)stream;
     //  - launches that would leave SIMDs idle (n <= n_simd / 2): a team of four wavefronts per walker, one step per lane each
     //    (the same 256-step tiles and policy; mode A; LONG builds for handles with longer light curves).  Up to n_simd / 4 walkers every
@@ -672,116 +656,71 @@ int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
     //    (profiles/r05_team_*.log): 256 walkers 0.0755 -> 0.0577 ms, 512 walkers 0.0767 -> 0.0699 ms near the truth
     //    (0.197 -> 0.165 ms prior-wide); a team of two (2 steps per lane) at 512 walkers 0.0701 / 0.197 ms.
     const int team = (curves || !a.want_chi2 || a.physical) ? 1 : kernel_waves(sh, a.n);
-    if (team > 1) {
-        const bool log = a.tile_log != nullptr || kAlwaysLog;
-        if (team == 4 && 4 * a.n <= sh.n_simd) {
-            if (lng) {
-                if (log) hipLaunchKernelGGL((lnprob_team_kernel<1, 4, 1, true, true>), grid, dim3(256), 0, st, sh, a);
-                else hipLaunchKernelGGL((lnprob_team_kernel<1, 4, 1, false, true>), grid, dim3(256), 0, st, sh, a);
-            } else if (log) hipLaunchKernelGGL((lnprob_team_kernel<1, 4, 1, true>), grid, dim3(256), 0, st, sh, a);
-            else hipLaunchKernelGGL((lnprob_team_kernel<1, 4, 1, false>), grid, dim3(256), 0, st, sh, a);
-        } else if (team == 4) {
-            if (lng) {
-                if (log) hipLaunchKernelGGL((lnprob_team_kernel<1, 4, 2, true, true>), grid, dim3(256), 0, st, sh, a);
-                else hipLaunchKernelGGL((lnprob_team_kernel<1, 4, 2, false, true>), grid, dim3(256), 0, st, sh, a);
-            } else if (log) hipLaunchKernelGGL((lnprob_team_kernel<1, 4, 2, true>), grid, dim3(256), 0, st, sh, a);
-            else hipLaunchKernelGGL((lnprob_team_kernel<1, 4, 2, false>), grid, dim3(256), 0, st, sh, a);
-        } else {
+    if (team == 4) {
+        dispatch([&](auto occ1, auto log_, auto lng_) {
+            hipLaunchKernelGGL((lnprob_team_kernel<1, 4, occ1 ? 1 : 2, log_, lng_>), grid, dim3(256), 0, st, sh, a);
+        }, 4 * a.n <= sh.n_simd, log, lng);
+    } else if (team > 1) {
 #ifdef MP_EXPERIMENTS
-            if (2 * a.n <= sh.n_simd) {
-                if (log) hipLaunchKernelGGL((lnprob_team_kernel<2, 2, 1, true>), grid, dim3(128), 0, st, sh, a);
-                else hipLaunchKernelGGL((lnprob_team_kernel<2, 2, 1, false>), grid, dim3(128), 0, st, sh, a);
-            } else {
-                if (log) hipLaunchKernelGGL((lnprob_team_kernel<2, 2, 2, true>), grid, dim3(128), 0, st, sh, a);
-                else hipLaunchKernelGGL((lnprob_team_kernel<2, 2, 2, false>), grid, dim3(128), 0, st, sh, a);
-            }
+        dispatch([&](auto occ1, auto log_) {
+            hipLaunchKernelGGL((lnprob_team_kernel<2, 2, occ1 ? 1 : 2, log_>), grid, dim3(128), 0, st, sh, a);
+        }, 2 * a.n <= sh.n_simd, log);
 #endif
-        }
-        return (int)hipGetLastError();
-    }
-    if (curves) {
-        if (wide) hipLaunchKernelGGL((lnprob_kernel<true, 4, false>), grid, block, 0, st, sh, a);
-        else hipLaunchKernelGGL((lnprob_kernel<true, 2, false>), grid, block, 0, st, sh, a);
-    } else if (a.tile_log != nullptr || kAlwaysLog) {   // diagnostics requested: the builds that record the tile words
-        if (wide) {
-            if (lng) hipLaunchKernelGGL((lnprob_kernel<false, 4, true, true>), grid, block, 0, st, sh, a);
-            else hipLaunchKernelGGL((lnprob_kernel<false, 4, false, true>), grid, block, 0, st, sh, a);
-        } else {
-            if (lng) hipLaunchKernelGGL((lnprob_kernel<false, 2, true, true>), grid, block, 0, st, sh, a);
-            else hipLaunchKernelGGL((lnprob_kernel<false, 2, false, true>), grid, block, 0, st, sh, a);
-        }
-    } else if (wide) {
-        if (lng) hipLaunchKernelGGL((lnprob_kernel<false, 4, true>), grid, block, 0, st, sh, a);
-        else hipLaunchKernelGGL((lnprob_kernel<false, 4, false>), grid, block, 0, st, sh, a);
+    } else if (curves) {
+        dispatch([&](auto wide_) { hipLaunchKernelGGL((lnprob_kernel<true, wide_ ? 4 : 2, false>), grid, block, 0, st, sh, a); }, wide);
     } else {
-        if (lng) hipLaunchKernelGGL((lnprob_kernel<false, 2, true>), grid, block, 0, st, sh, a);
-        else hipLaunchKernelGGL((lnprob_kernel<false, 2, false>), grid, block, 0, st, sh, a);
+        dispatch([&](auto wide_, auto lng_, auto log_) {
+            hipLaunchKernelGGL((lnprob_kernel<false, wide_ ? 4 : 2, lng_, log_>), grid, block, 0, st, sh, a);
+        }, wide, lng, log);
     }
     return (int)hipGetLastError();
 }
 
-// n_blocks slots of the active half starting at g.slot_lo; DIFF: the DE / snooker builds, chosen by the same rule
-template <bool TEMPERED, bool DIFF = false>
-static int launch_stretch_t(const DevShared &sh, const StretchArgs &g, int n_blocks, hipStream_t st) {
-    dim3 grid((unsigned)n_blocks);
-    const bool lng = sh.has_long != 0;
-    if (stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4) {   // small ensembles: a team of four wavefronts per proposal
-        if (4 * n_blocks <= sh.n_simd) {
-            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 1, TEMPERED, DIFF>), grid, dim3(256), 0, st, sh, g);
-            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 1, TEMPERED, DIFF>), grid, dim3(256), 0, st, sh, g);
-        } else {
-            if (lng) hipLaunchKernelGGL((stretch_kernel<1, true, 4, 2, TEMPERED, DIFF>), grid, dim3(256), 0, st, sh, g);
-            else hipLaunchKernelGGL((stretch_kernel<1, false, 4, 2, TEMPERED, DIFF>), grid, dim3(256), 0, st, sh, g);
-        }
-        return (int)hipGetLastError();
-    }
-    if ((sh.force_spl ? sh.force_spl : kernel_spl(sh, n_blocks)) == 4) {
-        if (lng) hipLaunchKernelGGL((stretch_kernel<4, true, 1, 0, TEMPERED, DIFF>), grid, dim3(64), 0, st, sh, g);
-        else hipLaunchKernelGGL((stretch_kernel<4, false, 1, 0, TEMPERED, DIFF>), grid, dim3(64), 0, st, sh, g);
-    } else {
-        if (lng) hipLaunchKernelGGL((stretch_kernel<2, true, 1, 0, TEMPERED, DIFF>), grid, dim3(64), 0, st, sh, g);
-        else hipLaunchKernelGGL((stretch_kernel<2, false, 1, 0, TEMPERED, DIFF>), grid, dim3(64), 0, st, sh, g);
-    }
-    return (int)hipGetLastError();
+// The build of a stretch launch of n_blocks blocks, one rule for stretch_kernel and stretch_step_kernel.  Small samplers, by the
+// size of a WHOLE step (stretch_waves), evaluate every proposal on a team of W = 4 wavefronts, OCC = 1 wavefront per SIMD while
+// every wavefront of the launch has a SIMD of its own, else 2.  Larger ones run one wavefront per proposal (W = 1, OCC = 0) with
+// SPL = 4 steps per lane up to one wavefront per SIMD, else 2 (kernel_spl, or force_spl).  roomy: OCC = 1 for a team, else SPL = 4.
+struct StretchVariant {
+    bool team, roomy;
+};
+static StretchVariant stretch_variant(const DevShared &sh, const StretchArgs &g, int n_blocks) {
+    if (stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4) return {true, 4 * n_blocks <= sh.n_simd};
+    return {false, (sh.force_spl ? sh.force_spl : kernel_spl(sh, n_blocks)) == 4};
 }
+template <bool TEAM, bool ROOMY>   // the variant as template arguments
+struct StretchBuild {
+    static constexpr int SPL = TEAM ? 1 : (ROOMY ? 4 : 2), W = TEAM ? 4 : 1, OCC = TEAM ? (ROOMY ? 1 : 2) : 0;
+};
 
+// n_blocks slots of the active half starting at g.slot_lo; the DIFF builds (DE / snooker) are chosen by the same rule
 int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
     if (n_blocks <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (g.move != MP_MOVE_STRETCH) return g.beta ? launch_stretch_t<true, true>(sh, g, n_blocks, st) : launch_stretch_t<false, true>(sh, g, n_blocks, st);
-    return g.beta ? launch_stretch_t<true>(sh, g, n_blocks, st) : launch_stretch_t<false>(sh, g, n_blocks, st);
+    const StretchVariant v = stretch_variant(sh, g, n_blocks);
+    dispatch([&](auto team, auto roomy, auto lng, auto tempered, auto diff) {
+        using B = StretchBuild<team, roomy>;
+        hipLaunchKernelGGL((stretch_kernel<B::SPL, lng, B::W, B::OCC, tempered, diff>), dim3((unsigned)n_blocks), dim3(64 * B::W), 0,
+                           (hipStream_t)stream, sh, g);
+    }, v.team, v.roomy, sh.has_long != 0, g.beta != nullptr, g.move != MP_MOVE_STRETCH);
+    return (int)hipGetLastError();
 }
 
 int launch_stretch_step(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
     if (n_blocks <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)n_blocks);
-    const bool lng = sh.has_long != 0;
-    if (stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4) {
-        if (4 * n_blocks <= sh.n_simd) {
-            if (lng) hipLaunchKernelGGL((stretch_step_kernel<1, true, 4, 1>), grid, dim3(256), 0, st, sh, g);
-            else hipLaunchKernelGGL((stretch_step_kernel<1, false, 4, 1>), grid, dim3(256), 0, st, sh, g);
-        } else {
-            if (lng) hipLaunchKernelGGL((stretch_step_kernel<1, true, 4, 2>), grid, dim3(256), 0, st, sh, g);
-            else hipLaunchKernelGGL((stretch_step_kernel<1, false, 4, 2>), grid, dim3(256), 0, st, sh, g);
-        }
-        return (int)hipGetLastError();
-    }
-    if ((sh.force_spl ? sh.force_spl : kernel_spl(sh, n_blocks)) == 4) {
-        if (lng) hipLaunchKernelGGL((stretch_step_kernel<4, true>), grid, dim3(64), 0, st, sh, g);
-        else hipLaunchKernelGGL((stretch_step_kernel<4, false>), grid, dim3(64), 0, st, sh, g);
-    } else {
-        if (lng) hipLaunchKernelGGL((stretch_step_kernel<2, true>), grid, dim3(64), 0, st, sh, g);
-        else hipLaunchKernelGGL((stretch_step_kernel<2, false>), grid, dim3(64), 0, st, sh, g);
-    }
+    const StretchVariant v = stretch_variant(sh, g, n_blocks);
+    dispatch([&](auto team, auto roomy, auto lng) {
+        using B = StretchBuild<team, roomy>;
+        hipLaunchKernelGGL((stretch_step_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n_blocks), dim3(64 * B::W), 0,
+                           (hipStream_t)stream, sh, g);
+    }, v.team, v.roomy, sh.has_long != 0);
     return (int)hipGetLastError();
 }
 
 int launch_stretch_step_commit(const StretchArgs &g, void *stream) {
     const int n = 2 * g.n_half * g.n_ensembles;
     if (n <= 0) return 0;
-    if (g.beta) hipLaunchKernelGGL(stretch_step_commit_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL(stretch_step_commit_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+    dispatch([&](auto tempered) {
+        hipLaunchKernelGGL(stretch_step_commit_kernel<tempered>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
+    }, g.beta != nullptr);
     return (int)hipGetLastError();
 }
 
