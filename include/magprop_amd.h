@@ -384,6 +384,49 @@ int mp_sampler_step_apply(mp_sampler *s, const double *d_rows, double *d_chain_r
 /* device pointers of the resident state: pos[n_total][ndim], lnprob[n_total] (read-only for the caller) */
 int mp_sampler_state_ptrs(mp_sampler *s, double **d_pos, double **d_lnprob);
 
+/*
+ * Differential-evolution optimizer (ABI 5, additive): scipy.optimize.differential_evolution with deferred updating, without
+ * the polish step, every generation one launch that builds, evaluates and judges every trial (plus one small reduction).
+ * n_pops populations of popsize members each (5 <= popsize <= 1024, 1 <= n_pops <= MP_MAX_DATASETS); population p runs on
+ * dataset pop_ds_id[p] (NULL: dataset 0 for all; several populations may share a dataset: multiple starts).  Member k =
+ * p * popsize + i.  The bounds box lower[ndim] < upper[ndim] (finite) is in sampler coordinates.  target: 0 the log-posterior
+ * of the handle, 1 the isotropic unit Gaussian (tests).  Maximises lnprob, i.e. minimises the energy E = -lnprob.
+ * Generation g >= 1 of population p, member i (all from the population of generation g - 1):
+ *   u_j = j-th uniform of Philox4x32-10 keyed (seed; g, p, i, 0xDE00 + j / 2): u01(r0, r1) for even j, u01(r2, r3) for odd j;
+ *   F = f_lo + (f_hi - f_lo) u01(r0, r1) of Philox (seed; g, 0xFFFF, 0, 0xDEFF), once per generation (scipy's dither);
+ *   a0 = pick(u_0, m), a1 = distinct from a0 by u_1, a2 = distinct from both by u_2, m = popsize - 1 (the pick rule of
+ *   mp_sampler_set_moves), slot r_j = a_j + (a_j >= i): three distinct members other than i;
+ *   mutant  MP_DE_BEST1BIN: x_b + F (x_r0 - x_r1), b = best member of generation g - 1;  MP_DE_RAND1BIN: x_r0 + F (x_r1 - x_r2);
+ *   binomial crossover: coordinate d takes the mutant if d == pick(u_3, ndim) (scipy's fill point) or u_{4+d} < cr, else x_i;
+ *   a trial coordinate outside [lower_d, upper_d] (or NaN) becomes lower_d + u_{4+ndim+d} (upper_d - lower_d).
+ * All of it unfused (separately rounded products and sums).  Greedy decision: the trial replaces member i iff
+ * lnprob(trial) >= lnprob(member) (scipy's energy test <=; a NaN lnprob counts as -inf, and is stored as such).
+ * After each generation the best member is the largest lnprob, lowest index on ties; the population has converged when
+ * std(E) <= atol + tol |mean(E)| (population std, sums in member order: mean = (sum E) / popsize, var = (sum (E - mean)^2) /
+ * popsize; a -inf lnprob means not converged).  A converged population is frozen: its members, lnprob, status, nit and nfev
+ * stay as they are, and its later generations evaluate nothing.
+ * Kernel build: the rule of mp_lnprob_batch for a batch of n_pops * popsize walkers, so that (shipped build) a member's lnprob is
+ * bit for bit what mp_lnprob_batch returns for the same row in a batch of that size.
+ * mp_optimizer_create: MP_EINVAL on bad sizes, strategy, f_lo > f_hi (or outside [0, 2)), cr outside [0, 1], tol / atol not
+ * finite and >= 0, an empty or non-finite box, unset datasets; MP_ESTATE on multi-device handles and (target 0) handles with
+ * cfg.dipole_torque = 1.  mp_optimizer_set_population(pop[n_pops * popsize][ndim]) evaluates it (generation 0: nit = 0, nfev =
+ * popsize) and clears the converged flags.  mp_optimizer_run runs up to max_generations more generations of every population
+ * that has not converged, in chunks of launches with one read-back of the flags per chunk; *n_running (optional) = populations
+ * still running.  mp_optimizer_get_state: any output may be NULL; pop[n_total][ndim], lnprob[n_total], status[n_total],
+ * best[n_pops] (index inside the population), nit[n_pops], converged[n_pops], nfev[n_pops].
+ */
+#define MP_DE_BEST1BIN 0
+#define MP_DE_RAND1BIN 1
+typedef struct mp_optimizer mp_optimizer;
+mp_optimizer *mp_optimizer_create(mp_handle *h, int popsize, int n_pops, int ndim, const int32_t *pop_ds_id, uint64_t seed,
+                                  int strategy, double f_lo, double f_hi, double cr, double tol, double atol,
+                                  const double *lower, const double *upper, int target);
+int mp_optimizer_set_population(mp_optimizer *o, const double *pop);
+int mp_optimizer_run(mp_optimizer *o, int max_generations, int *n_running);
+int mp_optimizer_get_state(mp_optimizer *o, double *pop, double *lnprob, int32_t *status, int32_t *best, int32_t *nit,
+                           int32_t *converged, int64_t *nfev);
+int mp_optimizer_destroy(mp_optimizer *o);
+
 /* wait for everything enqueued on the handle's own stream */
 int mp_synchronize(mp_handle *h);
 

@@ -1421,6 +1421,170 @@ int mp_sampler_get_state(mp_sampler *s, double *pos, double *lnprob, int64_t *n_
     return MP_OK;
 }
 
+// ---------------------------------------------------------------- differential-evolution optimizer (mp_opt.hip)
+struct mp_optimizer {
+    mp_handle *h = nullptr;
+    mp::OptArgs a{};                // pointers: cur / next as of the next launch
+    int n_total = 0;
+    uint32_t gen = 0;               // generations launched so far (0: only the initial evaluation)
+    bool have_state = false;
+    DevBuf<double> d_pop[2], d_lnp[2];
+    DevBuf<int32_t> d_st[2], d_dsid, d_best, d_conv, d_nit;
+    DevBuf<int64_t> d_nfev;
+};
+
+static void opt_swap(mp_optimizer *o) {
+    std::swap(o->a.pop_cur, o->a.pop_next);
+    std::swap(o->a.lnp_cur, o->a.lnp_next);
+    std::swap(o->a.st_cur, o->a.st_next);
+}
+
+// one generation (trial = 1) or the initial evaluation (trial = 0) on the handle's stream, then the buffers change roles
+static int opt_enqueue(mp_optimizer *o, int trial) {
+    o->a.trial = trial;
+    o->a.gen = o->gen;
+    int e = mp::launch_opt_trial(o->h->sh, o->a, o->h->stream);
+    if (!e) e = mp::launch_opt_reduce(o->a, o->h->stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    opt_swap(o);
+    return MP_OK;
+}
+
+mp_optimizer *mp_optimizer_create(mp_handle *h, int popsize, int n_pops, int ndim, const int32_t *pop_ds_id, uint64_t seed,
+                                  int strategy, double f_lo, double f_hi, double cr, double tol, double atol,
+                                  const double *lower, const double *upper, int target) {
+    if (!h || !lower || !upper) { fail(MP_EINVAL, "mp_optimizer_create: NULL argument"); return nullptr; }
+    if (!h->sub.empty()) { fail(MP_ESTATE, "mp_optimizer_create: the optimizer lives on ONE device (a multi-device handle serves host-buffer batches only)"); return nullptr; }
+    if (popsize < 5 || popsize > 1024) { fail(MP_EINVAL, "mp_optimizer_create: popsize must be 5 .. 1024, got %d", popsize); return nullptr; }
+    if (n_pops < 1 || n_pops > MP_MAX_DATASETS) { fail(MP_EINVAL, "mp_optimizer_create: n_pops must be 1 .. %d", MP_MAX_DATASETS); return nullptr; }
+    if (target != 0 && target != 1) { fail(MP_EINVAL, "mp_optimizer_create: target must be 0 (posterior) or 1 (unit Gaussian)"); return nullptr; }
+    if (ndim < 1 || ndim > MP_MAX_NDIM || (target == 0 && ndim < 6)) { fail(MP_EINVAL, "mp_optimizer_create: bad ndim %d", ndim); return nullptr; }
+    if (strategy != MP_DE_BEST1BIN && strategy != MP_DE_RAND1BIN) { fail(MP_EINVAL, "mp_optimizer_create: unknown strategy %d", strategy); return nullptr; }
+    if (!(f_lo >= 0.0 && f_lo <= f_hi && f_hi < 2.0)) { fail(MP_EINVAL, "mp_optimizer_create: need 0 <= f_lo <= f_hi < 2"); return nullptr; }
+    if (!(cr >= 0.0 && cr <= 1.0)) { fail(MP_EINVAL, "mp_optimizer_create: cr must lie in [0, 1]"); return nullptr; }
+    if (!(std::isfinite(tol) && tol >= 0.0 && std::isfinite(atol) && atol >= 0.0)) { fail(MP_EINVAL, "mp_optimizer_create: tol and atol must be finite and >= 0"); return nullptr; }
+    for (int d = 0; d < ndim; ++d)
+        if (!(std::isfinite(lower[d]) && std::isfinite(upper[d]) && lower[d] < upper[d])) {
+            fail(MP_EINVAL, "mp_optimizer_create: bounds of coordinate %d are empty or not finite", d);
+            return nullptr;
+        }
+    if (target == 0 && h->sh.cfg.dipole_torque != 0) { fail(MP_ESTATE, "mp_optimizer_create: the alternative dipole torque (cfg.dipole_torque = 1) is served by the curve kernels only"); return nullptr; }
+    Lock lock(h->mu);
+    if (target == 0)
+        for (int p = 0; p < n_pops; ++p) {
+            const int d = pop_ds_id ? pop_ds_id[p] : 0;
+            if (d < 0 || d >= MP_MAX_DATASETS || !h->ds[d].set) {
+                fail(MP_ESTATE, "mp_optimizer_create: population %d refers to unset dataset %d", p, d);
+                return nullptr;
+            }
+        }
+    mp_optimizer *o = new mp_optimizer();
+    o->h = h;
+    o->n_total = popsize * n_pops;
+    mp::OptArgs &a = o->a;
+    a.popsize = popsize; a.n_pops = n_pops; a.ndim = ndim; a.strategy = strategy; a.target = target; a.seed = seed;
+    a.f_lo = f_lo; a.f_hi = f_hi; a.cr = cr; a.tol = tol; a.atol = atol;
+    for (int d = 0; d < ndim; ++d) { a.lower[d] = lower[d]; a.upper[d] = upper[d]; }
+    DeviceScope scope(h->device);
+    const size_t nt = (size_t)o->n_total;
+    std::vector<int32_t> ds(nt);
+    for (int p = 0; p < n_pops; ++p) std::fill(ds.begin() + (size_t)p * popsize, ds.begin() + (size_t)(p + 1) * popsize, pop_ds_id ? pop_ds_id[p] : 0);
+    if (o->d_pop[0].ensure(nt * ndim) || o->d_pop[1].ensure(nt * ndim) || o->d_lnp[0].ensure(nt) || o->d_lnp[1].ensure(nt) ||
+        o->d_st[0].ensure(nt) || o->d_st[1].ensure(nt) || o->d_dsid.ensure(nt) || o->d_best.ensure(n_pops) ||
+        o->d_conv.ensure(n_pops) || o->d_nit.ensure(n_pops) || o->d_nfev.ensure(n_pops) ||
+        hipMemcpy(o->d_dsid.p, ds.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        fail(MP_EHIP, "mp_optimizer_create: device allocation failed");
+        mp_optimizer_destroy(o);
+        return nullptr;
+    }
+    a.pop_cur = o->d_pop[0].p; a.pop_next = o->d_pop[1].p;
+    a.lnp_cur = o->d_lnp[0].p; a.lnp_next = o->d_lnp[1].p;
+    a.st_cur = o->d_st[0].p; a.st_next = o->d_st[1].p;
+    a.ds_id = o->d_dsid.p; a.best = o->d_best.p; a.converged = o->d_conv.p; a.nit = o->d_nit.p; a.nfev = o->d_nfev.p;
+    return o;
+}
+
+int mp_optimizer_destroy(mp_optimizer *o) {
+    if (!o) return MP_OK;
+    Lock lock(o->h->mu);
+    DeviceScope scope(o->h->device);
+    (void)hipStreamSynchronize(o->h->stream);
+    for (int b = 0; b < 2; ++b) { o->d_pop[b].release(); o->d_lnp[b].release(); o->d_st[b].release(); }
+    o->d_dsid.release(); o->d_best.release(); o->d_conv.release(); o->d_nit.release(); o->d_nfev.release();
+    delete o;
+    return MP_OK;
+}
+
+int mp_optimizer_set_population(mp_optimizer *o, const double *pop) {
+    if (!o || !pop) return fail(MP_EINVAL, "mp_optimizer_set_population: NULL argument");
+    mp_handle *h = o->h;
+    const size_t nt = (size_t)o->n_total, n_pops = (size_t)o->a.n_pops;
+    for (size_t i = 0; i < nt * o->a.ndim; ++i)
+        if (!std::isfinite(pop[i])) return fail(MP_EINVAL, "mp_optimizer_set_population: non-finite coordinate");
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    HIP_TRY(hipMemcpyAsync(o->a.pop_cur, pop, nt * o->a.ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(o->a.converged, 0, n_pops * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(o->a.nit, 0, n_pops * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(o->a.nfev, 0, n_pops * sizeof(int64_t), h->stream));
+    o->gen = 0;
+    int rc = opt_enqueue(o, 0);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    o->have_state = true;
+    return MP_OK;
+}
+
+int mp_optimizer_run(mp_optimizer *o, int max_generations, int *n_running) {
+    if (!o || max_generations < 0) return fail(MP_EINVAL, "mp_optimizer_run: bad argument");
+    if (!o->have_state) return fail(MP_ESTATE, "mp_optimizer_run: call mp_optimizer_set_population first");
+    mp_handle *h = o->h;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    // Chunks of generations enqueued back to back (no allocation, no wait inside a chunk); the flags are read back behind each
+    // chunk, and the run ends early once every population has converged.  A frozen population costs an empty workgroup per
+    // member and launch.
+    constexpr int kChunk = 16;
+    const int n_pops = o->a.n_pops;
+    std::vector<int32_t> conv((size_t)n_pops);
+    int running = n_pops;
+    HIP_TRY(hipMemcpy(conv.data(), o->a.converged, (size_t)n_pops * sizeof(int32_t), hipMemcpyDeviceToHost));
+    running = n_pops - (int)std::count(conv.begin(), conv.end(), 1);
+    for (int done = 0; done < max_generations && running > 0;) {
+        const int chunk = std::min(kChunk, max_generations - done);
+        for (int g = 0; g < chunk; ++g) {
+            ++o->gen;
+            const int rc = opt_enqueue(o, 1);
+            if (rc) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(conv.data(), o->a.converged, (size_t)n_pops * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        running = n_pops - (int)std::count(conv.begin(), conv.end(), 1);
+        done += chunk;
+    }
+    if (n_running) *n_running = running;
+    return MP_OK;
+}
+
+int mp_optimizer_get_state(mp_optimizer *o, double *pop, double *lnprob, int32_t *status, int32_t *best, int32_t *nit,
+                           int32_t *converged, int64_t *nfev) {
+    if (!o) return fail(MP_EINVAL, "mp_optimizer_get_state: NULL optimizer");
+    if (!o->have_state) return fail(MP_ESTATE, "mp_optimizer_get_state: call mp_optimizer_set_population first");
+    mp_handle *h = o->h;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    const size_t nt = (size_t)o->n_total, np = (size_t)o->a.n_pops;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (pop) HIP_TRY(hipMemcpy(pop, o->a.pop_cur, nt * o->a.ndim * sizeof(double), hipMemcpyDeviceToHost));
+    if (lnprob) HIP_TRY(hipMemcpy(lnprob, o->a.lnp_cur, nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIP_TRY(hipMemcpy(status, o->a.st_cur, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (best) HIP_TRY(hipMemcpy(best, o->a.best, np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (nit) HIP_TRY(hipMemcpy(nit, o->a.nit, np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (converged) HIP_TRY(hipMemcpy(converged, o->a.converged, np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (nfev) HIP_TRY(hipMemcpy(nfev, o->a.nfev, np * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return MP_OK;
+}
+
 int mp_device(const mp_handle *h) { return h ? h->device : -1; }
 void *mp_stream(const mp_handle *h) { return h ? (void *)h->stream : nullptr; }   // (a multi-device handle has none: NULL)
 int mp_n_grid(const mp_handle *h) { return h ? (int)h->tgrid.size() : 0; }

@@ -294,4 +294,33 @@ int launch_stretch_swap(const StretchArgs &g, int n_temps, int64_t *n_swaps, voi
 // columns behind the proposal in an outcome row of a whole-step launch
 constexpr int kSpecExtra = 6;   // lnprob, status, (ndim - 1) ln z, ln u, lnprob of the walker before the move, partner's slot
 
+// Arguments of one generation of the differential-evolution optimizer (mp_opt.hip; include/magprop_amd.h mp_optimizer_*).
+// Member k = p * popsize + i is member i of population p; the population is double-buffered (cur -> next): a trial launch reads
+// only the cur buffers and writes only the next ones, so no workgroup reads what another one writes.  (The reduction writes the
+// cur buffers of a population that has just converged: both buffers then hold its final state.)
+struct OptArgs {
+    double *pop_cur;         // [n_total][ndim]
+    double *pop_next;
+    double *lnp_cur;         // [n_total]
+    double *lnp_next;
+    int32_t *st_cur;         // [n_total] status of every member (MP_STATUS_*)
+    int32_t *st_next;
+    const int32_t *ds_id;    // [n_total] dataset of every member
+    int32_t *best;           // [n_pops] best member of the last generation (index inside the population)
+    int32_t *converged;      // [n_pops] 1: frozen
+    int32_t *nit;            // [n_pops] generations run (scipy's nit)
+    int64_t *nfev;           // [n_pops] evaluations
+    double lower[MP_MAX_NDIM], upper[MP_MAX_NDIM];   // the bounds box (sampler coordinates)
+    int32_t popsize, n_pops, ndim, strategy;         // strategy: MP_DE_BEST1BIN or MP_DE_RAND1BIN
+    int32_t target;          // 0: posterior, 1: isotropic unit Gaussian
+    int32_t trial;           // 0: evaluate pop_cur as it is (generation 0), 1: a generation of trials
+    uint32_t gen;            // generation number (the Philox counter); 0 = the initial evaluation
+    uint32_t pad;
+    uint64_t seed;
+    double f_lo, f_hi, cr, tol, atol;
+};
+// one workgroup per member (trial = 0 or 1), then one per population (best member, stop rule, counters); include/magprop_amd.h
+int launch_opt_trial(const DevShared &sh, const OptArgs &o, void *stream);
+int launch_opt_reduce(const OptArgs &o, void *stream);
+
 }  // namespace mp

@@ -372,6 +372,16 @@ struct TeamX {
     double D4[G][64];    // smoothness indicators of the steps
     unsigned flags[4][64];
 };
+// (the team's exchange area in LDS, or nothing for the one-wavefront builds)
+template <int G, bool ON>
+struct TeamLds {
+    TeamX<G> x;
+    __device__ TeamX<G> *ptr() { return &x; }
+};
+template <int G>
+struct TeamLds<G, false> {
+    __device__ TeamX<G> *ptr() { return nullptr; }
+};
 // entry v SPL + s of a group array: the value of this wavefront's own step s (v is wave-uniform)
 template <int SPL, int W>
 MP_DEV double own_of(const double (&g)[SPL * W], int wave, int s) {

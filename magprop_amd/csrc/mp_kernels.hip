@@ -147,21 +147,7 @@ int launch_order(const DevShared &sh, const int32_t *ds_id, int n, int32_t *orde
 }
 
 // ---------------------------------------------------------------- fused stretch-move half-step kernel
-// Unfused double arithmetic (hipcc contracts a*b+c into an FMA by default, also through __dmul_rn/__dadd_rn):
-// the proposal and the test target are computed with separately rounded operations so that a numpy
-// restatement of the move reproduces the chain bit for bit.
-MP_DEV double mul_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-MP_DEV double add_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-MP_DEV double sub_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
+// (unfused arithmetic: mul_rn / add_rn / sub_rn, mp_math.hpp)
 
 // One wavefront = one walker of the active half: draw the partner and the stretch factor, form the
 // proposal (emcee's StretchMove.get_proposal), evaluate its log-posterior with walker_eval, accept or
@@ -178,30 +164,8 @@ __device__ __forceinline__ int ens_of_slot(const StretchArgs &g, int e_pos) {
     return g.ens_order ? (int)((g.ens_order >> (4 * e_pos)) & 15u) : e_pos;
 }
 
-// (the team's exchange area in LDS, or nothing for the one-wavefront builds)
-template <int G, bool ON>
-struct TeamLds {
-    TeamX<G> x;
-    __device__ TeamX<G> *ptr() { return &x; }
-};
-template <int G>
-struct TeamLds<G, false> {
-    __device__ TeamX<G> *ptr() { return nullptr; }
-};
-
 // ---- differential-evolution and snooker proposals (the DIFF builds of stretch_kernel; include/magprop_amd.h MP_MOVE_*)
-// Index draws over the m slots of the complementary half: pick(u, m) = min(floor(u m), m - 1); a second index distinct from a
-// first is drawn over m - 1 and steps over it, a third over m - 2 and steps over the first two in increasing order.
-MP_DEV int pick(double u, int m) { return min((int)(u * m), m - 1); }
-MP_DEV int pick_skip(double u, int m, int c) {
-    const int t = pick(u, m - 1);
-    return t >= c ? t + 1 : t;
-}
-MP_DEV int pick_skip2(double u, int m, int c0, int c1) {
-    int t = pick(u, m - 2);
-    t = t >= min(c0, c1) ? t + 1 : t;
-    return t >= max(c0, c1) ? t + 1 : t;
-}
+// (index draws over the m slots of the complementary half: pick / pick_skip / pick_skip2, mp_math.hpp)
 // The proposal par[] of walker k and, for the snooker move, the sums behind its Hastings term (qq = sum (q - z)^2, dd =
 // sum (x_k - z)^2, in index order).  r = Philox(...; c3 = 2), r2 = Philox(...; c3 = 3).  Unfused, like the stretch move.
 //   DE (ter Braak 2006):        partners j1, j2;  gamma = g0 (1 + s (2 u - 1));  q = x_k + gamma (x_j1 - x_j2)

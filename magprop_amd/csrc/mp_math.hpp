@@ -1,6 +1,6 @@
 // mp_math.hpp — device-side building blocks of the gfx950 kernels: DPP wavefront primitives (affine-map scan,
 // neighbour fetch, broadcast), the per-lane N-vector type, hand-rolled fp64 elementary functions and the
-// exponential-integrator phi functions.  Included by mp_kernels.hip only.
+// exponential-integrator phi functions, the unfused arithmetic of the random moves.  Included by mp_kernels.hip and mp_opt.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -564,6 +564,37 @@ MP_DEV Vd<N> eam5_increment_nodes(const EamW5<N> &w, const Vd<N> &h, const Vd<N>
     FORN acc[i] = fma(w.c0[i], v0[i], acc[i]);
     FORN acc[i] = h[i] * acc[i];
     return acc;
+}
+
+// ---------------------------------------------------------------- unfused arithmetic and index draws
+// (shared by the sampler's moves, mp_kernels.hip, and the optimizer, mp_opt.hip)
+// Unfused double arithmetic (hipcc contracts a*b+c into an FMA by default, also through __dmul_rn/__dadd_rn):
+// proposals, trial vectors and test targets are computed with separately rounded operations so that a numpy
+// restatement reproduces the chains bit for bit.
+MP_DEV double mul_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+MP_DEV double add_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+MP_DEV double sub_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+// Index draws over m slots: pick(u, m) = min(floor(u m), m - 1); a second index distinct from a first is drawn over m - 1 and
+// steps over it, a third over m - 2 and steps over the first two in increasing order.
+MP_DEV int pick(double u, int m) { return min((int)(u * m), m - 1); }
+MP_DEV int pick_skip(double u, int m, int c) {
+    const int t = pick(u, m - 1);
+    return t >= c ? t + 1 : t;
+}
+MP_DEV int pick_skip2(double u, int m, int c0, int c1) {
+    int t = pick(u, m - 2);
+    t = t >= min(c0, c1) ? t + 1 : t;
+    return t >= max(c0, c1) ? t + 1 : t;
 }
 
 }  // namespace mp

@@ -1,0 +1,223 @@
+"""GPU tests of the differential-evolution optimizer (include/magprop_amd.h mp_optimizer_*, magprop_amd.optimize): the device
+state against the numpy restatement (tests/de_restated.py) bit for bit, best fits on the synthetic sets and on long Swift light
+curves, frozen populations and refused handles."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import de_restated as de
+from conftest import GOLDEN, TRUTHS, TYPES
+
+pytestmark = pytest.mark.gpu
+
+dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+
+
+class RawOptimizer:
+    """mp_optimizer_* through ctypes on handle h."""
+
+    def __init__(self, h, popsize, n_pops, ndim, lower, upper, seed, strategy, target, ds=None, f=(0.5, 1.0), cr=0.7, tol=0.01,
+                 atol=0.0):
+        from magprop_amd import _capi
+        self.L, self.popsize, self.n_pops, self.ndim = _capi.lib(), popsize, n_pops, ndim
+        self.lo, self.hi = np.ascontiguousarray(lower, dtype=np.float64), np.ascontiguousarray(upper, dtype=np.float64)
+        ids = None if ds is None else np.ascontiguousarray(ds, dtype=np.int32)
+        self.o = self.L.mp_optimizer_create(h._h, popsize, n_pops, ndim, None if ids is None else ids.ctypes.data_as(ip),
+                                            C.c_uint64(seed), strategy, f[0], f[1], cr, tol, atol, self.lo.ctypes.data_as(dp),
+                                            self.hi.ctypes.data_as(dp), target)
+        assert self.o, _capi.last_error()
+
+    def set_population(self, pop):
+        p = np.ascontiguousarray(pop, dtype=np.float64)
+        assert self.L.mp_optimizer_set_population(self.o, p.ctypes.data_as(dp)) == 0
+
+    def run(self, n):
+        running = C.c_int32(-1)
+        assert self.L.mp_optimizer_run(self.o, n, C.byref(running)) == 0
+        return running.value
+
+    def state(self):
+        from magprop_amd import optimize
+        return optimize.get_state(self.L, self.o, self.n_pops, self.popsize, self.ndim)
+
+    def close(self):
+        self.L.mp_optimizer_destroy(self.o)
+
+
+def _assert_equal(st, s):
+    assert np.array_equal(st["pop"], s.pop)
+    assert np.array_equal(st["lnprob"], s.lnp)
+    assert np.array_equal(st["status"], s.status)
+    assert np.array_equal(st["best"], s.best)
+    assert np.array_equal(st["nit"], s.nit)
+    assert np.array_equal(st["converged"], s.converged)
+    assert np.array_equal(st["nfev"], s.nfev)
+
+
+@pytest.mark.parametrize("strategy", [de.BEST1BIN, de.RAND1BIN])
+@pytest.mark.parametrize("n_pops", [1, 3])
+def test_gaussian_state_matches_the_restatement_bit_for_bit(strategy, n_pops):
+    """Unit Gaussian in a box whose corner (0.05, 0.1, -0.2) lies next to the optimum: 300 generations run as 120 + 180, every
+    population, lnprob, status, best index, nit and nfev equal to the restatement."""
+    from magprop_amd import _capi, engine
+    ndim, popsize, seed = 3, 12, 20261015 + strategy
+    lo, hi = np.array([0.05, 0.1, -3.0]), np.array([3.0, 2.5, -0.2])
+    pop0 = lo + (hi - lo) * np.random.default_rng(7 + n_pops).random((n_pops, popsize, ndim))
+    kw = dict(strategy=strategy, f_lo=0.5, f_hi=1.0, cr=0.7, tol=1e-12, atol=0.0, lower=lo, upper=hi)
+    ref = de.run(pop0, 300, de.gaussian, seed, **kw)
+    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    opt = RawOptimizer(h, popsize, n_pops, ndim, lo, hi, seed, strategy, 1, tol=1e-12)
+    try:
+        opt.set_population(pop0.reshape(-1, ndim))
+        opt.run(120)
+        opt.run(180)
+        st = opt.state()
+    finally:
+        opt.close()
+        h.close()
+    _assert_equal(st, ref)
+    assert ref.lnp.max() > -0.5 * (0.05 ** 2 + 0.1 ** 2 + 0.2 ** 2) - 1e-3
+
+
+def test_humped_posterior_matches_the_restatement_with_lnprob_batch():
+    """20 generations of two populations on Humped with the posterior: the restatement's evaluations are mp_lnprob_batch calls on
+    batches of the launch's size (60 rows: the same kernel build), and the device state equals it bit for bit."""
+    from magprop_amd import _capi, engine, optimize, synth
+    g = np.load(GOLDEN + "/golden_synth.npz")
+    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h.set_prior(synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK)
+    h.set_dataset(0, g["Humped_x"], g["Humped_y"], g["Humped_yerr"])
+    lo, hi = synth.PRIOR_LOWER, synth.PRIOR_UPPER
+    rng = np.random.default_rng(5)
+    pop0 = np.stack([optimize.latin_hypercube(rng, 30, lo, hi) for _ in range(2)])
+
+    def evaluate(rows):
+        assert rows.shape == (60, 6)
+        return h.lnprob_batch(rows, ds_id=0, want_status=True)
+
+    ref = de.run(pop0, 20, evaluate, 99, de.BEST1BIN, 0.5, 1.0, 0.7, 0.01, 0.0, lo, hi)
+    opt = RawOptimizer(h, 30, 2, 6, lo, hi, 99, de.BEST1BIN, 0, ds=[0, 0])
+    try:
+        opt.set_population(pop0.reshape(-1, 6))
+        opt.run(20)
+        st = opt.state()
+    finally:
+        opt.close()
+        h.close()
+    _assert_equal(st, ref)
+    assert np.all(np.isfinite(ref.lnp.max(axis=1)))
+
+
+@pytest.fixture(scope="module")
+def synth_fit():
+    """Four populations per synthetic dataset from Latin hypercubes over the prior box, all in one call."""
+    from magprop_amd import optimize
+    g = np.load(GOLDEN + "/golden_synth.npz")
+    ds = [(g[f"{t}_x"], g[f"{t}_y"], g[f"{t}_yerr"]) for t in TYPES]
+    res = optimize.differential_evolution(datasets=ds, n_starts=4, seed=3, maxiter=1000)
+    return ds, res
+
+
+def test_best_fits_on_the_four_synthetic_sets_reach_the_truth(synth_fit):
+    from magprop_amd import LogProb
+    ds, res = synth_fit
+    assert len(res) == 16
+    for k, t in enumerate(TYPES):
+        lp_truth = LogProb(*ds[k])(np.array(TRUTHS[t], dtype=float))
+        best = max(r.lnprob for r in res[4 * k:4 * k + 4])
+        assert best >= lp_truth - 1.0, (t, best, lp_truth)
+        for r in res[4 * k:4 * k + 4]:
+            assert r.fun == -r.lnprob and r.nfev == r.population.shape[0] * (r.nit + 1)
+            assert r.success == (r.nit < 1000)
+
+
+def test_population_lnprob_equals_logprob_in_a_batch_of_the_same_size(synth_fit):
+    from magprop_amd import LogProb
+    ds, res = synth_fit
+    lp = LogProb(*ds[0])
+    for d in ds[1:]:
+        lp.add_dataset(*d)
+    P = np.concatenate([r.population for r in res])
+    ids = np.repeat(np.arange(4, dtype=np.int32), 4 * res[0].population.shape[0])
+    out, st = lp.handle.lnprob_batch(P, ds_id=ids, want_status=True)
+    assert P.shape[0] == 16 * 90
+    assert np.array_equal(out, np.concatenate([r.population_lnprob for r in res]))
+    assert np.array_equal(st, np.concatenate([r.population_status for r in res]))
+
+
+def test_converged_populations_stay_frozen():
+    """Population 0 starts collapsed (converges at once), population 1 spread over the box: after the first converges, its
+    members, lnprob, nit and nfev no longer change while the other goes on; the whole run equals the restatement."""
+    from magprop_amd import _capi, engine
+    ndim, popsize, seed = 2, 10, 4
+    lo, hi = np.array([-5.0, -5.0]), np.array([5.0, 5.0])
+    rng = np.random.default_rng(0)
+    pop0 = np.stack([1.0 + 1e-9 * rng.random((popsize, ndim)), lo + (hi - lo) * rng.random((popsize, ndim))])
+    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    opt = RawOptimizer(h, popsize, 2, ndim, lo, hi, seed, de.BEST1BIN, 1, tol=1e-3, atol=1e-9)
+    try:
+        opt.set_population(pop0.reshape(-1, ndim))
+        assert opt.run(3) == 1
+        a = opt.state()
+        assert a["converged"].tolist() == [1, 0]
+        assert opt.run(40) in (0, 1)
+        b = opt.state()
+    finally:
+        opt.close()
+        h.close()
+    assert np.array_equal(a["pop"][0], b["pop"][0]) and np.array_equal(a["lnprob"][0], b["lnprob"][0])
+    assert a["nit"][0] == b["nit"][0] and a["nfev"][0] == b["nfev"][0] == popsize * (a["nit"][0] + 1)
+    assert b["nit"][1] > a["nit"][1] and b["nfev"][1] == popsize * (b["nit"][1] + 1)
+    _assert_equal(b, de.run(pop0, 43, de.gaussian, seed, de.BEST1BIN, 0.5, 1.0, 0.7, 1e-3, 1e-9, lo, hi))
+
+
+def test_long_swift_light_curve_synth_reaches_the_truth(gswift):
+    """LONG builds: the synth variant on the 1 921 points of GRB 060614 (swift_060614_pars[0] is its truth)."""
+    from magprop_amd import LogProb, optimize
+    x, y, yerr = gswift["swift_060614_ds"]
+    truth = gswift["swift_060614_pars"][0]
+    res = optimize.differential_evolution(x, y, yerr, seed=1, maxiter=1000)
+    lp_truth = LogProb(x, y, yerr)(truth)
+    assert res.lnprob >= lp_truth - 1.0, (res.lnprob, lp_truth)
+
+
+def test_long_swift_light_curve_lib(gswift):
+    """The lib variant on GRB 051016B (79 points, GRBtype "S"): 6 dimensions reach the best finite lnlike of the fixture's
+    parameter sets; 9 dimensions finish with a finite best inside the box."""
+    from magprop_amd import mcmc_eqns, optimize
+    x, y, yerr = gswift["swift_051016B_libS_ds"]
+    ref = gswift["swift_051016B_libS_lnlike"]
+    res = optimize.differential_evolution(x, y, yerr, variant="lib", GRBtype="S", seed=2, maxiter=1000)
+    assert res.lnprob >= np.max(ref[np.isfinite(ref)]), (res.lnprob, ref)
+    lo, hi = mcmc_eqns._bounds(9)
+    res9 = optimize.differential_evolution(x, y, yerr, variant="lib", GRBtype="S", bounds=np.stack([lo, hi], axis=1), popsize=10,
+                                           seed=2, maxiter=300)
+    assert np.isfinite(res9.lnprob) and np.all((res9.x >= lo) & (res9.x <= hi))
+
+
+def test_multi_device_and_alternative_torque_handles_are_refused():
+    from magprop_amd import _capi, engine
+    L = _capi.lib()
+    lo, hi = np.zeros(6), np.ones(6)
+    x = np.logspace(0.5, 3.0, 20)
+    hm = _capi.Handle(_capi.cfg_synth(), engine.grid(None), device=[0])
+    ha = _capi.Handle(_capi.cfg_synth(dipole_torque=1), engine.grid(None))
+    try:
+        for h, what in ((hm, "ONE device"), (ha, "dipole torque")):
+            h.set_dataset(0, x, np.ones_like(x), np.ones_like(x))
+            o = L.mp_optimizer_create(h._h, 10, 1, 6, None, C.c_uint64(0), 0, 0.5, 1.0, 0.7, 0.01, 0.0, lo.ctypes.data_as(dp),
+                                      hi.ctypes.data_as(dp), 0)
+            assert not o and what in _capi.last_error()
+        # argument codes on a plain handle
+        h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+        for bad in (dict(popsize=4), dict(cr=1.5), dict(f=(1.0, 0.5)), dict(upper=np.zeros(6))):
+            kw = dict(popsize=10, cr=0.7, f=(0.5, 1.0), upper=hi)
+            kw.update(bad)
+            o = L.mp_optimizer_create(h._h, kw["popsize"], 1, 6, None, C.c_uint64(0), 0, kw["f"][0], kw["f"][1], kw["cr"], 0.01,
+                                      0.0, lo.ctypes.data_as(dp), np.ascontiguousarray(kw["upper"]).ctypes.data_as(dp), 1)
+            assert not o, bad
+        h.close()
+    finally:
+        hm.close()
+        ha.close()
