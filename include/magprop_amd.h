@@ -427,6 +427,57 @@ int mp_optimizer_get_state(mp_optimizer *o, double *pop, double *lnprob, int32_t
                            int32_t *converged, int64_t *nfev);
 int mp_optimizer_destroy(mp_optimizer *o);
 
+/*
+ * Nested sampler (ABI 5, additive): Skilling's nested sampling (2006) with batch removal (dynesty's), the dead points replaced by
+ * constrained DE random walks; one select and one walk launch per iteration.  n_runs independent runs (1 <= n_runs <=
+ * MP_MAX_DATASETS) of nlive live points each (MP_NEST_MIN_LIVE <= N <= MP_NEST_MAX_LIVE); run r runs on dataset run_ds_id[r]
+ * (NULL: dataset 0 for all; several runs may share a dataset).  Live slot j of run r is row r * N + j.  The prior is uniform
+ * over the box lower[ndim] < upper[ndim] (finite; sampler coordinates).  target: 0 the log-posterior of the handle (lnL), 1 the
+ * isotropic unit Gaussian -0.5 sum x^2 (tests).  A NaN lnL counts (and is stored) as -inf.
+ * Iteration t of run r (t = the run's own iteration count, from 0), K = nbatch (1 <= K <= N / 2), M = N - K:
+ *   order the live points by (lnL, slot); the first K die, in that order (dead k = 0 .. K-1), L* = lnL of dead K - 1;
+ *   survivors s_0 < s_1 < ... < s_{M-1}: the other slots in slot order;
+ *   the walk into dead slot j draws from Philox4x32-10 keyed (seed; t, r, j, 0x4E000000 + c):
+ *     c = 0:          start x = live point s_{pick(u01(r0, r1), M)} (its lnL and status come with it);
+ *     c = 2 s + 1:    step s's partners c1 = pick(u01(r0, r1), M), c2 = distinct from c1 by u01(r2, r3) (mp_sampler_set_moves' rule);
+ *     c = 2 s + 2:    gamma = g0 (1 + s3 (2 u01(r0, r1) - 1)), s3 = sigma sqrt(3), g0 = 2.38 / sqrt(2 ndim) when given as <= 0;
+ *   step s = 0 .. walks-1:  q_d = x_d + gamma (x_{s_c1, d} - x_{s_c2, d}) (unfused); accepted iff lower_d <= q_d <= upper_d for
+ *   every d (a proposal outside is not evaluated) and lnL(q) > L*; then x = q.  The difference set (the survivors) is fixed
+ *   during the walk: the proposal is symmetric, and this is Metropolis for the prior restricted to lnL > L*.
+ *   The walk's end point, its lnL, status and accepted-step count replace dead slot j.
+ * Volume bookkeeping, one thread per run, dead k = 0 .. K-1 with n_k = N - k live points:
+ *   lnw_k = (lnL_k + ln X) + log(-expm1(-1 / n_k));  ln X = ln X - 1 / n_k;  ln Z = logaddexp(ln Z, lnw_k)
+ *   (logaddexp(x, y) = m + log1p(exp(-|x - y|)), m = max(x, y); -inf when both are), from ln X = 0, ln Z = -inf.
+ * Stop rule, on the live set as it stands before an iteration (and behind every chunk of mp_nested_run): the run stops (is frozen:
+ * it evaluates nothing more and keeps its full live set) when log1p(exp((lnL_max + ln X) - ln Z)) < dlogz, lnL_max the largest
+ * live lnL.  The state does not depend on how mp_nested_run is split into calls.
+ * Every iteration writes the dead rows (pars, lnL, n_k) of every running run; mp_nested_run reads them back behind every chunk
+ * of iterations (one wait per chunk) and keeps them per run in order.  The final estimate (adding the live points, the
+ * information H, the error, resampling) is the caller's (magprop_amd.nested).
+ * Kernel build: the rule of mp_lnprob_batch for a batch of n_runs * nbatch walkers (the live-set evaluation: n_runs * nlive).
+ * mp_nested_create: MP_EINVAL on bad sizes (ndim < 6 for target 0, walks outside 1 .. MP_NEST_MAX_WALKS), g0 > 0 not finite,
+ * sigma outside [0, 1/sqrt(3)), dlogz not finite and > 0, an empty or non-finite box, unset datasets; MP_ESTATE on
+ * multi-device handles and (target 0) handles with cfg.dipole_torque = 1.  mp_nested_set_live(live[n_runs * nlive][ndim], inside
+ * the box) evaluates the live set and resets every run (no dead rows, ln X = 0, ln Z = -inf, counters 0).  mp_nested_run runs up
+ * to max_iterations more iterations of every run not yet stopped; *n_running (optional) = runs still running.
+ * mp_nested_get_dead(run): *n_rows = the run's dead rows so far; the first min(max_rows, *n_rows) are copied into pars[][ndim],
+ * lnl[], n_live[] (each may be NULL).  mp_nested_get_state: any output may be NULL; live[n_runs * nlive][ndim], lnl, status,
+ * acc (accepted steps of the walk that put the point there; 0 for the caller's points) [n_runs * nlive]; per run: nit, stopped,
+ * lnx, lnz, ncall (evaluations inside walks), nacc (accepted steps), nzero (walks that accepted nothing).
+ */
+#define MP_NEST_MIN_LIVE 16
+#define MP_NEST_MAX_LIVE 4096
+#define MP_NEST_MAX_WALKS 4096
+typedef struct mp_nested mp_nested;
+mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int ndim, const int32_t *run_ds_id, uint64_t seed,
+                            int walks, double g0, double sigma, double dlogz, const double *lower, const double *upper, int target);
+int mp_nested_set_live(mp_nested *ns, const double *live);
+int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running);
+int mp_nested_get_dead(mp_nested *ns, int run, int64_t max_rows, double *pars, double *lnl, int32_t *n_live, int64_t *n_rows);
+int mp_nested_get_state(mp_nested *ns, double *live, double *lnl, int32_t *status, int32_t *acc, int32_t *nit, int32_t *stopped,
+                        double *lnx, double *lnz, int64_t *ncall, int64_t *nacc, int64_t *nzero);
+int mp_nested_destroy(mp_nested *ns);
+
 /* wait for everything enqueued on the handle's own stream */
 int mp_synchronize(mp_handle *h);
 

@@ -1585,6 +1585,217 @@ int mp_optimizer_get_state(mp_optimizer *o, double *pop, double *lnprob, int32_t
     return MP_OK;
 }
 
+// ---------------------------------------------------------------- nested sampler (mp_nest.hip)
+struct mp_nested {
+    mp_handle *h = nullptr;
+    mp::NestArgs a{};
+    int n_total = 0;                // n_runs * nlive
+    int chunk = 0;                  // iterations per chunk (slots of the dead buffers)
+    uint32_t iter = 0;              // iterations launched since mp_nested_set_live
+    bool have_state = false;
+    DevBuf<double> d_live, d_lnl, d_lstar, d_dpars, d_dlnl, d_lnx, d_lnz;
+    DevBuf<int32_t> d_st, d_acc, d_dsid, d_dslot, d_surv, d_dn, d_stop, d_nit;
+    DevBuf<int64_t> d_ncall, d_nacc, d_nzero;
+    std::vector<std::vector<double>> dead_pars, dead_lnl;   // per run, in order
+    std::vector<std::vector<int32_t>> dead_n;
+};
+
+mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int ndim, const int32_t *run_ds_id, uint64_t seed,
+                            int walks, double g0, double sigma, double dlogz, const double *lower, const double *upper, int target) {
+    if (!h || !lower || !upper) { fail(MP_EINVAL, "mp_nested_create: NULL argument"); return nullptr; }
+    if (!h->sub.empty()) { fail(MP_ESTATE, "mp_nested_create: the nested sampler lives on ONE device (a multi-device handle serves host-buffer batches only)"); return nullptr; }
+    if (nlive < MP_NEST_MIN_LIVE || nlive > MP_NEST_MAX_LIVE) { fail(MP_EINVAL, "mp_nested_create: nlive must be %d .. %d, got %d", MP_NEST_MIN_LIVE, MP_NEST_MAX_LIVE, nlive); return nullptr; }
+    if (nbatch < 1 || nbatch > nlive / 2) { fail(MP_EINVAL, "mp_nested_create: nbatch must be 1 .. nlive / 2, got %d", nbatch); return nullptr; }
+    if (n_runs < 1 || n_runs > MP_MAX_DATASETS) { fail(MP_EINVAL, "mp_nested_create: n_runs must be 1 .. %d", MP_MAX_DATASETS); return nullptr; }
+    if (target != 0 && target != 1) { fail(MP_EINVAL, "mp_nested_create: target must be 0 (posterior) or 1 (unit Gaussian)"); return nullptr; }
+    if (ndim < 1 || ndim > MP_MAX_NDIM || (target == 0 && ndim < 6)) { fail(MP_EINVAL, "mp_nested_create: bad ndim %d", ndim); return nullptr; }
+    if (walks < 1 || walks > MP_NEST_MAX_WALKS) { fail(MP_EINVAL, "mp_nested_create: walks must be 1 .. %d", MP_NEST_MAX_WALKS); return nullptr; }
+    if (!std::isfinite(g0)) { fail(MP_EINVAL, "mp_nested_create: g0 must be finite (<= 0: the default)"); return nullptr; }
+    if (!(sigma >= 0.0 && sigma < 1.0 / std::sqrt(3.0))) { fail(MP_EINVAL, "mp_nested_create: sigma must lie in [0, 1/sqrt(3))"); return nullptr; }
+    if (!(std::isfinite(dlogz) && dlogz > 0.0)) { fail(MP_EINVAL, "mp_nested_create: dlogz must be finite and > 0"); return nullptr; }
+    for (int d = 0; d < ndim; ++d)
+        if (!(std::isfinite(lower[d]) && std::isfinite(upper[d]) && lower[d] < upper[d])) {
+            fail(MP_EINVAL, "mp_nested_create: bounds of coordinate %d are empty or not finite", d);
+            return nullptr;
+        }
+    if (target == 0 && h->sh.cfg.dipole_torque != 0) { fail(MP_ESTATE, "mp_nested_create: the alternative dipole torque (cfg.dipole_torque = 1) is served by the curve kernels only"); return nullptr; }
+    Lock lock(h->mu);
+    if (target == 0)
+        for (int r = 0; r < n_runs; ++r) {
+            const int d = run_ds_id ? run_ds_id[r] : 0;
+            if (d < 0 || d >= MP_MAX_DATASETS || !h->ds[d].set) {
+                fail(MP_ESTATE, "mp_nested_create: run %d refers to unset dataset %d", r, d);
+                return nullptr;
+            }
+        }
+    mp_nested *ns = new mp_nested();
+    ns->h = h;
+    ns->n_total = nlive * n_runs;
+    // dead buffers of about 16 MB at most, up to 32 iterations per chunk
+    const size_t row = (size_t)n_runs * nbatch * (ndim + 2) * sizeof(double);
+    ns->chunk = (int)std::max<size_t>(1, std::min<size_t>(32, (16u << 20) / row));
+    mp::NestArgs &a = ns->a;
+    a.nlive = nlive; a.nbatch = nbatch; a.n_runs = n_runs; a.ndim = ndim; a.walks = walks; a.target = target; a.seed = seed;
+    a.g0 = g0 > 0.0 ? g0 : 2.38 / std::sqrt(2.0 * ndim);
+    a.sig3 = sigma * std::sqrt(3.0);
+    a.dlogz = dlogz;
+    for (int d = 0; d < ndim; ++d) { a.lower[d] = lower[d]; a.upper[d] = upper[d]; }
+    ns->dead_pars.resize(n_runs); ns->dead_lnl.resize(n_runs); ns->dead_n.resize(n_runs);
+    DeviceScope scope(h->device);
+    const size_t nt = (size_t)ns->n_total, nr = (size_t)n_runs, nk = nr * nbatch, nc = (size_t)ns->chunk * nk;
+    std::vector<int32_t> ds(nr);
+    for (int r = 0; r < n_runs; ++r) ds[r] = run_ds_id ? run_ds_id[r] : 0;
+    if (ns->d_live.ensure(nt * ndim) || ns->d_lnl.ensure(nt) || ns->d_st.ensure(nt) || ns->d_acc.ensure(nt) || ns->d_dsid.ensure(nr) ||
+        ns->d_dslot.ensure(nk) || ns->d_surv.ensure(nr * (nlive - nbatch)) || ns->d_lstar.ensure(nr) || ns->d_dpars.ensure(nc * ndim) ||
+        ns->d_dlnl.ensure(nc) || ns->d_dn.ensure(nc) || ns->d_lnx.ensure(nr) || ns->d_lnz.ensure(nr) || ns->d_stop.ensure(nr) ||
+        ns->d_nit.ensure(nr) || ns->d_ncall.ensure(nr) || ns->d_nacc.ensure(nr) || ns->d_nzero.ensure(nr) ||
+        hipMemcpy(ns->d_dsid.p, ds.data(), nr * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        fail(MP_EHIP, "mp_nested_create: device allocation failed");
+        mp_nested_destroy(ns);
+        return nullptr;
+    }
+    a.live = ns->d_live.p; a.lnl = ns->d_lnl.p; a.st = ns->d_st.p; a.acc = ns->d_acc.p; a.ds_id = ns->d_dsid.p;
+    a.dead_slot = ns->d_dslot.p; a.surv = ns->d_surv.p; a.lstar = ns->d_lstar.p; a.dead_pars = ns->d_dpars.p;
+    a.dead_lnl = ns->d_dlnl.p; a.dead_n = ns->d_dn.p; a.lnx = ns->d_lnx.p; a.lnz = ns->d_lnz.p; a.stopped = ns->d_stop.p;
+    a.nit = ns->d_nit.p; a.ncall = ns->d_ncall.p; a.nacc = ns->d_nacc.p; a.nzero = ns->d_nzero.p;
+    return ns;
+}
+
+int mp_nested_destroy(mp_nested *ns) {
+    if (!ns) return MP_OK;
+    Lock lock(ns->h->mu);
+    DeviceScope scope(ns->h->device);
+    (void)hipStreamSynchronize(ns->h->stream);
+    ns->d_live.release(); ns->d_lnl.release(); ns->d_lstar.release(); ns->d_dpars.release(); ns->d_dlnl.release();
+    ns->d_lnx.release(); ns->d_lnz.release(); ns->d_st.release(); ns->d_acc.release(); ns->d_dsid.release(); ns->d_dslot.release();
+    ns->d_surv.release(); ns->d_dn.release(); ns->d_stop.release(); ns->d_nit.release(); ns->d_ncall.release(); ns->d_nacc.release();
+    ns->d_nzero.release();
+    delete ns;
+    return MP_OK;
+}
+
+int mp_nested_set_live(mp_nested *ns, const double *live) {
+    if (!ns || !live) return fail(MP_EINVAL, "mp_nested_set_live: NULL argument");
+    mp_handle *h = ns->h;
+    mp::NestArgs &a = ns->a;
+    const size_t nt = (size_t)ns->n_total, nr = (size_t)a.n_runs;
+    for (size_t i = 0; i < nt; ++i)
+        for (int d = 0; d < a.ndim; ++d) {
+            const double v = live[i * a.ndim + d];
+            if (!(v >= a.lower[d] && v <= a.upper[d])) return fail(MP_EINVAL, "mp_nested_set_live: live point %zu lies outside the box", i);
+        }
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    const std::vector<double> zero(nr, 0.0), ninf(nr, -INFINITY);
+    HIP_TRY(hipMemcpyAsync(a.live, live, nt * a.ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a.lnx, zero.data(), nr * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(a.lnz, ninf.data(), nr * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(a.stopped, 0, nr * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(a.nit, 0, nr * sizeof(int32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(a.ncall, 0, nr * sizeof(int64_t), h->stream));
+    HIP_TRY(hipMemsetAsync(a.nacc, 0, nr * sizeof(int64_t), h->stream));
+    HIP_TRY(hipMemsetAsync(a.nzero, 0, nr * sizeof(int64_t), h->stream));
+    a.mode = 1;
+    a.iter = 0;
+    const int e = mp::launch_nest_walk(h->sh, a, h->stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    ns->iter = 0;
+    for (size_t r = 0; r < nr; ++r) { ns->dead_pars[r].clear(); ns->dead_lnl[r].clear(); ns->dead_n[r].clear(); }
+    ns->have_state = true;
+    return MP_OK;
+}
+
+int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running) {
+    if (!ns || max_iterations < 0) return fail(MP_EINVAL, "mp_nested_run: bad argument");
+    if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_run: call mp_nested_set_live first");
+    mp_handle *h = ns->h;
+    mp::NestArgs &a = ns->a;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    // Chunks of iterations enqueued back to back (select, walk, select, walk, ...; no wait inside a chunk), then a stop check on
+    // the live set as it stands and one read-back of the counters and the dead rows; the run ends early once every run stopped.
+    const int nr = a.n_runs, K = a.nbatch, nd = a.ndim;
+    const size_t per = (size_t)nr * K;
+    std::vector<int32_t> stop((size_t)nr), nit0((size_t)nr), nit1((size_t)nr);
+    std::vector<double> hp, hl;
+    std::vector<int32_t> hn;
+    HIP_TRY(hipMemcpy(stop.data(), a.stopped, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int running = nr - (int)std::count(stop.begin(), stop.end(), 1);
+    for (int done = 0; done < max_iterations && running > 0;) {
+        const int chunk = std::min(ns->chunk, max_iterations - done);
+        HIP_TRY(hipMemcpyAsync(nit0.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        for (int c = 0; c < chunk; ++c) {
+            a.slot = c;
+            a.iter = ns->iter++;
+            a.mode = 0;
+            int e = mp::launch_nest_select(a, h->stream);
+            if (!e) e = mp::launch_nest_walk(h->sh, a, h->stream);
+            if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        }
+        a.mode = 1;
+        int e = mp::launch_nest_select(a, h->stream);
+        if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        hp.resize((size_t)chunk * per * nd);
+        hl.resize((size_t)chunk * per);
+        hn.resize((size_t)chunk * per);
+        HIP_TRY(hipMemcpyAsync(hp.data(), a.dead_pars, hp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(hl.data(), a.dead_lnl, hl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(hn.data(), a.dead_n, hn.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(nit1.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(stop.data(), a.stopped, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        // run r ran the first nit1 - nit0 iterations of the chunk (a stopped run stays stopped)
+        for (int r = 0; r < nr; ++r)
+            for (int c = 0; c < nit1[r] - nit0[r]; ++c) {
+                const size_t o = ((size_t)c * nr + r) * K;
+                ns->dead_pars[r].insert(ns->dead_pars[r].end(), hp.begin() + o * nd, hp.begin() + (o + K) * nd);
+                ns->dead_lnl[r].insert(ns->dead_lnl[r].end(), hl.begin() + o, hl.begin() + o + K);
+                ns->dead_n[r].insert(ns->dead_n[r].end(), hn.begin() + o, hn.begin() + o + K);
+            }
+        running = nr - (int)std::count(stop.begin(), stop.end(), 1);
+        done += chunk;
+    }
+    if (n_running) *n_running = running;
+    return MP_OK;
+}
+
+int mp_nested_get_dead(mp_nested *ns, int run, int64_t max_rows, double *pars, double *lnl, int32_t *n_live, int64_t *n_rows) {
+    if (!ns || run < 0 || run >= ns->a.n_runs || max_rows < 0) return fail(MP_EINVAL, "mp_nested_get_dead: bad argument");
+    if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_get_dead: call mp_nested_set_live first");
+    Lock lock(ns->h->mu);
+    const int64_t have = (int64_t)ns->dead_lnl[run].size(), n = std::min(have, max_rows);
+    if (pars) std::copy(ns->dead_pars[run].begin(), ns->dead_pars[run].begin() + n * ns->a.ndim, pars);
+    if (lnl) std::copy(ns->dead_lnl[run].begin(), ns->dead_lnl[run].begin() + n, lnl);
+    if (n_live) std::copy(ns->dead_n[run].begin(), ns->dead_n[run].begin() + n, n_live);
+    if (n_rows) *n_rows = have;
+    return MP_OK;
+}
+
+int mp_nested_get_state(mp_nested *ns, double *live, double *lnl, int32_t *status, int32_t *acc, int32_t *nit, int32_t *stopped,
+                        double *lnx, double *lnz, int64_t *ncall, int64_t *nacc, int64_t *nzero) {
+    if (!ns) return fail(MP_EINVAL, "mp_nested_get_state: NULL sampler");
+    if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_get_state: call mp_nested_set_live first");
+    mp_handle *h = ns->h;
+    const mp::NestArgs &a = ns->a;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    const size_t nt = (size_t)ns->n_total, nr = (size_t)a.n_runs;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (live) HIP_TRY(hipMemcpy(live, a.live, nt * a.ndim * sizeof(double), hipMemcpyDeviceToHost));
+    if (lnl) HIP_TRY(hipMemcpy(lnl, a.lnl, nt * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIP_TRY(hipMemcpy(status, a.st, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (acc) HIP_TRY(hipMemcpy(acc, a.acc, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (nit) HIP_TRY(hipMemcpy(nit, a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (stopped) HIP_TRY(hipMemcpy(stopped, a.stopped, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (lnx) HIP_TRY(hipMemcpy(lnx, a.lnx, nr * sizeof(double), hipMemcpyDeviceToHost));
+    if (lnz) HIP_TRY(hipMemcpy(lnz, a.lnz, nr * sizeof(double), hipMemcpyDeviceToHost));
+    if (ncall) HIP_TRY(hipMemcpy(ncall, a.ncall, nr * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (nacc) HIP_TRY(hipMemcpy(nacc, a.nacc, nr * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (nzero) HIP_TRY(hipMemcpy(nzero, a.nzero, nr * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return MP_OK;
+}
+
 int mp_device(const mp_handle *h) { return h ? h->device : -1; }
 void *mp_stream(const mp_handle *h) { return h ? (void *)h->stream : nullptr; }   // (a multi-device handle has none: NULL)
 int mp_n_grid(const mp_handle *h) { return h ? (int)h->tgrid.size() : 0; }

@@ -323,4 +323,42 @@ struct OptArgs {
 int launch_opt_trial(const DevShared &sh, const OptArgs &o, void *stream);
 int launch_opt_reduce(const OptArgs &o, void *stream);
 
+// Arguments of one iteration of the nested sampler (mp_nest.hip; include/magprop_amd.h mp_nested_*).  Live slot j of run r is
+// row r * nlive + j.  The select launch ranks the live set and writes this iteration's dead list, survivor list and L*; the walk
+// launch reads only survivors (and those lists) and writes only dead slots, so no workgroup reads what another one writes.
+struct NestArgs {
+    double *live;            // [n_runs * nlive][ndim]
+    double *lnl;             // [n_runs * nlive] (NaN stored as -inf)
+    int32_t *st;             // [n_runs * nlive] status of every live point (MP_STATUS_*)
+    int32_t *acc;            // [n_runs * nlive] accepted steps of the walk that put the point there (0: set by the caller)
+    const int32_t *ds_id;    // [n_runs] dataset of every run
+    int32_t *dead_slot;      // [n_runs][nbatch] this iteration's dead slots, ascending lnL
+    int32_t *surv;           // [n_runs][nlive - nbatch] this iteration's survivors in slot order
+    double *lstar;           // [n_runs] this iteration's L* (largest dead lnL)
+    double *dead_pars;       // [chunk][n_runs][nbatch][ndim] the dead rows of the chunk's iterations
+    double *dead_lnl;        // [chunk][n_runs][nbatch]
+    int32_t *dead_n;         // [chunk][n_runs][nbatch] live count n_i of every dead point
+    double *lnx;             // [n_runs] ln X after the run's last iteration
+    double *lnz;             // [n_runs] running ln Z
+    int32_t *stopped;        // [n_runs] 1: frozen
+    int32_t *nit;            // [n_runs] iterations run
+    int64_t *ncall;          // [n_runs] evaluations inside walks
+    int64_t *nacc;           // [n_runs] accepted walk steps
+    int64_t *nzero;          // [n_runs] walks that accepted nothing
+    double lower[MP_MAX_NDIM], upper[MP_MAX_NDIM];   // the prior box (sampler coordinates)
+    int32_t nlive, nbatch, n_runs, ndim;
+    int32_t walks;           // steps per walk
+    int32_t target;          // 0: posterior, 1: isotropic unit Gaussian
+    int32_t mode;            // select: 0 iteration, 1 stop check only; walk: 0 iteration, 1 evaluate the live set as it is
+    int32_t slot;            // chunk slot of this iteration's dead rows
+    uint32_t iter;           // iteration number (the Philox counter)
+    uint32_t pad;
+    uint64_t seed;
+    double g0, sig3, dlogz;  // sig3 = sigma sqrt(3)
+};
+// one workgroup per run (rank, dead rows, L*, survivors, ln X, ln Z, stop rule), then one per dead slot (the constrained walk;
+// mode 1: one per live point, evaluated as it is); include/magprop_amd.h
+int launch_nest_select(const NestArgs &a, void *stream);
+int launch_nest_walk(const DevShared &sh, const NestArgs &a, void *stream);
+
 }  // namespace mp

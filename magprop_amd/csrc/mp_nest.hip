@@ -1,0 +1,238 @@
+// mp_nest.hip — gfx950 kernels of the nested sampler (include/magprop_amd.h mp_nested_*): Skilling's nested sampling with batch
+// removal, constrained DE random walks, one select and one walk launch per iteration.
+//
+// nest_select_kernel: one workgroup per run.  It ranks the live lnL (by lnL, then slot; N <= 4096 keys in LDS), applies the stop
+// rule to the live set as it stands, and otherwise writes the iteration's dead list (ascending lnL), the survivors in slot order,
+// L*, the dead rows of the chunk and the new ln X and ln Z (one thread, in the order of the header).
+// nest_walk_kernel: one workgroup per dead slot (the builds of lnprob_kernel / lnprob_team_kernel).  Lane 0 picks a survivor as
+// the start and builds every DE step in LDS, the workgroup evaluates the step with walker_eval, lane 0 decides (inside the box and
+// lnL > L*).  Survivors are only read and dead slots only written, so the workgroups need no hand-off among themselves.  Mode 1
+// evaluates the live set as the caller set it.
+#include <hip/hip_runtime.h>
+
+#include "mp_eval.hpp"
+
+namespace mp {
+
+namespace {
+
+constexpr uint32_t kNestCtr = 0x4E000000u;   // third counter word: 0x4E000000 + j, j = 0 start, 2 s + 1 and 2 s + 2 step s
+
+MP_DEV void nest_draw(const NestArgs &a, int r, int slot, uint32_t j, uint32_t (&out)[4]) {
+    philox4x32_10((uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.iter, (uint32_t)r, (uint32_t)slot, kNestCtr + j, out);
+}
+
+// log(exp(x) + exp(y)), -inf when both are
+MP_DEV double logaddexp(double x, double y) {
+    const double m = fmax(x, y);
+    if (m == -INFINITY) return m;
+    return add_rn(m, log1p(exp(-fabs(sub_rn(x, y)))));
+}
+
+// W, OCC, SPL, LONG: the builds of launch_lnprob (W = 4: lnprob_team_kernel<1, 4, OCC>; W = 1: lnprob_kernel<false, SPL>), chosen
+// by the same rule for the launch's workgroup count (launch_nest_walk).
+template <int SPL, bool LONG, int W = 1, int OCC = 0>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
+void nest_walk_kernel(const DevShared sh, const NestArgs a) {
+    const int b = (int)blockIdx.x, per = a.mode ? a.nlive : a.nbatch, r = b / per, k = b - r * per;
+    if (a.mode == 0 && a.stopped[r]) return;   // frozen run (uniform for the workgroup): nothing to do
+    __shared__ TileImage<SPL * W> im;
+    __shared__ TimeTable<SPL * W> tt;
+    __shared__ double lds[1];
+    __shared__ double cur[MP_MAX_NDIM];      // the walk's current point
+    __shared__ double prop[MP_MAX_NDIM];     // the step's proposal across walker_eval
+    __shared__ int go;                       // 1: the proposal lies in the box (evaluate it)
+    __shared__ TeamLds<SPL * W, (W > 1)> tl;
+    TeamX<SPL * W> *const tx = tl.ptr();
+    tables_init<SPL * W, 64 * W>(sh, tt);
+    const int nd = a.ndim, m = a.nlive - a.nbatch, base = r * a.nlive;
+    const int slot = a.mode ? k : a.dead_slot[r * a.nbatch + k];
+    const int steps = a.mode ? 1 : a.walks;
+    double lnl_cur = -INFINITY, lstar = 0.0;
+    int st_cur = MP_STATUS_OK, n_acc = 0, n_eval = 0;
+    if (threadIdx.x == 0) {
+        int from = base + slot;
+        if (!a.mode) {
+            uint32_t u[4];
+            nest_draw(a, r, slot, 0u, u);
+            from = base + a.surv[r * m + pick(u01(u[0], u[1]), m)];
+            lnl_cur = a.lnl[from];
+            st_cur = a.st[from];
+            lstar = a.lstar[r];
+        }
+        for (int d = 0; d < nd; ++d) cur[d] = a.live[(size_t)from * nd + d];
+    }
+    for (int s = 0; s < steps; ++s) {
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (a.mode) {
+                for (int d = 0; d < nd; ++d) prop[d] = cur[d];
+                go = 1;
+            } else {
+                uint32_t u[4], v[4];
+                nest_draw(a, r, slot, 2u * (uint32_t)s + 1u, u);
+                nest_draw(a, r, slot, 2u * (uint32_t)s + 2u, v);
+                const int c1 = pick(u01(u[0], u[1]), m), c2 = pick_skip(u01(u[2], u[3]), m, c1);
+                const double *x1 = a.live + (size_t)(base + a.surv[r * m + c1]) * nd;
+                const double *x2 = a.live + (size_t)(base + a.surv[r * m + c2]) * nd;
+                const double gamma = mul_rn(a.g0, add_rn(1.0, mul_rn(a.sig3, sub_rn(mul_rn(2.0, u01(v[0], v[1])), 1.0))));
+                int in = 1;
+                for (int d = 0; d < nd; ++d) {
+                    const double q = add_rn(cur[d], mul_rn(gamma, sub_rn(x1[d], x2[d])));
+                    in &= (q >= a.lower[d] && q <= a.upper[d]) ? 1 : 0;
+                    prop[d] = q;
+                }
+                go = in;
+            }
+        }
+        __syncthreads();
+        if (!go) continue;                     // (uniform: LDS behind the barrier)
+        double par[MP_MAX_NDIM];
+#pragma unroll
+        for (int d = 0; d < MP_MAX_NDIM; ++d) par[d] = d < nd ? prop[d] : 0.0;
+        double lnp = 0.0;
+        int status = MP_STATUS_OK, sweeps, tiles;
+        if (a.target == 1) {   // isotropic unit Gaussian: exercises the algorithm itself (tests)
+#pragma unroll
+            for (int d = 0; d < MP_MAX_NDIM; ++d) lnp = d < nd ? sub_rn(lnp, mul_rn(mul_rn(0.5, par[d]), par[d])) : lnp;
+        } else {
+            LaunchArgs la{};
+            la.ds_id = a.ds_id;
+            la.ndim = nd;
+            la.physical = 0;
+            la.want_chi2 = 1;
+            if constexpr (W > 1) walker_eval<false, SPL, LONG, false, W, OCC >= 2>(sh, la, r, par, im, tt, lds, lnp, status, sweeps, tiles, tx);
+            else walker_eval<false, SPL, LONG>(sh, la, r, par, im, tt, lds, lnp, status, sweeps, tiles);
+        }
+        if (threadIdx.x == 0) {
+            if (lnp != lnp) lnp = -INFINITY;   // NaN counts (and is kept) as -inf
+            ++n_eval;
+            if (a.mode || lnp > lstar) {
+                for (int d = 0; d < nd; ++d) cur[d] = prop[d];
+                lnl_cur = lnp;
+                st_cur = status;
+                n_acc += a.mode ? 0 : 1;
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        const size_t row = (size_t)(base + slot);
+        for (int d = 0; d < nd; ++d) a.live[row * nd + d] = cur[d];
+        a.lnl[row] = lnl_cur;
+        a.st[row] = st_cur;
+        a.acc[row] = n_acc;
+        if (!a.mode) {
+            atomicAdd((unsigned long long *)&a.ncall[r], (unsigned long long)n_eval);
+            atomicAdd((unsigned long long *)&a.nacc[r], (unsigned long long)n_acc);
+            if (n_acc == 0) atomicAdd((unsigned long long *)&a.nzero[r], 1ull);
+        }
+    }
+}
+
+template <bool TEAM, bool ROOMY, bool LONG>   // ROOMY: OCC = 1 for a team, else SPL = 4 (as in launch_lnprob)
+void nest_walk_launch(const DevShared &sh, const NestArgs &a, int n, hipStream_t st) {
+    constexpr int SPL = TEAM ? 1 : (ROOMY ? 4 : 2), W = TEAM ? 4 : 1, OCC = TEAM ? (ROOMY ? 1 : 2) : 0;
+    hipLaunchKernelGGL((nest_walk_kernel<SPL, LONG, W, OCC>), dim3((unsigned)n), dim3(64 * W), 0, st, sh, a);
+}
+
+constexpr int kSelThreads = 1024;
+
+// Ranks, the stop rule and the bookkeeping of one iteration of run blockIdx.x (include/magprop_amd.h states the arithmetic).
+__global__ __launch_bounds__(kSelThreads) void nest_select_kernel(const NestArgs a) {
+    const int r = (int)blockIdx.x, n = a.nlive, K = a.nbatch, m = n - K, base = r * n, tid = (int)threadIdx.x;
+    if (a.stopped[r]) return;
+    __shared__ double key[MP_NEST_MAX_LIVE];
+    __shared__ int rank[MP_NEST_MAX_LIVE];
+    __shared__ int dslot[MP_NEST_MAX_LIVE / 2];
+    __shared__ double shell[MP_NEST_MAX_LIVE / 2];   // log(-expm1(-1 / n_k)) of dead k
+    __shared__ double lmax;
+    __shared__ int stop;
+    for (int j = tid; j < n; j += kSelThreads) {
+        const double v = a.lnl[base + j];
+        key[j] = v != v ? -INFINITY : v;
+    }
+    __syncthreads();
+    // rank of slot j: the live points before it in the order (lnL, slot)
+    for (int j = tid; j < n; j += kSelThreads) {
+        const double kj = key[j];
+        int c = 0;
+        for (int i = 0; i < n; ++i) {
+            const double ki = key[i];
+            c += (ki < kj || (ki == kj && i < j)) ? 1 : 0;
+        }
+        rank[j] = c;
+        if (c == n - 1) lmax = kj;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        stop = log1p(exp(sub_rn(add_rn(lmax, a.lnx[r]), a.lnz[r]))) < a.dlogz;
+        if (stop) a.stopped[r] = 1;
+    }
+    __syncthreads();
+    if (stop || a.mode) return;
+    for (int j = tid; j < n; j += kSelThreads) {
+        const int c = rank[j];
+        if (c < K) {
+            dslot[c] = j;
+            a.dead_slot[r * K + c] = j;
+        } else {
+            int before = 0;   // dead slots in front of j
+            for (int i = 0; i < j; ++i) before += rank[i] < K ? 1 : 0;
+            a.surv[r * m + j - before] = j;
+        }
+    }
+    __syncthreads();
+    const size_t drow = ((size_t)a.slot * a.n_runs + r) * K;
+    for (int e = tid; e < K * a.ndim; e += kSelThreads) {
+        const int k = e / a.ndim, d = e - k * a.ndim;
+        a.dead_pars[(drow + k) * a.ndim + d] = a.live[(size_t)(base + dslot[k]) * a.ndim + d];
+    }
+    for (int k = tid; k < K; k += kSelThreads) {
+        a.dead_lnl[drow + k] = key[dslot[k]];
+        a.dead_n[drow + k] = n - k;
+        shell[k] = log(-expm1(-(1.0 / (double)(n - k))));
+    }
+    __syncthreads();
+    if (tid == 0) {   // (the chain of ln X and ln Z in order; the shell terms came from every thread)
+        double lnx = a.lnx[r], lnz = a.lnz[r];
+        for (int k = 0; k < K; ++k) {
+            const double inv = 1.0 / (double)(n - k);
+            const double lnw = add_rn(add_rn(key[dslot[k]], lnx), shell[k]);
+            lnx = sub_rn(lnx, inv);
+            lnz = logaddexp(lnz, lnw);
+        }
+        a.lstar[r] = key[dslot[K - 1]];
+        a.lnx[r] = lnx;
+        a.lnz[r] = lnz;
+        a.nit[r] += 1;
+    }
+}
+
+}  // namespace
+
+// The build of launch_lnprob for a batch of n = n_runs * nbatch walkers (mode 1: n_runs * nlive): a team of four wavefronts per
+// walk where kernel_waves says so (OCC 1 while 4 n <= n_simd, else 2), else one wavefront with kernel_spl's steps per lane;
+// LONG builds for handles with light curves of more than 64 points.
+int launch_nest_walk(const DevShared &sh, const NestArgs &a, void *stream) {
+    const int n = a.n_runs * (a.mode ? a.nlive : a.nbatch);
+    if (n <= 0) return 0;
+    const bool team = kernel_waves(sh, n) == 4, lng = sh.has_long != 0;
+    const bool roomy = team ? 4 * n <= sh.n_simd : (sh.force_spl ? sh.force_spl : kernel_spl(sh, n)) == 4;
+    const hipStream_t st = (hipStream_t)stream;
+    if (team) {
+        if (roomy) lng ? nest_walk_launch<true, true, true>(sh, a, n, st) : nest_walk_launch<true, true, false>(sh, a, n, st);
+        else lng ? nest_walk_launch<true, false, true>(sh, a, n, st) : nest_walk_launch<true, false, false>(sh, a, n, st);
+    } else {
+        if (roomy) lng ? nest_walk_launch<false, true, true>(sh, a, n, st) : nest_walk_launch<false, true, false>(sh, a, n, st);
+        else lng ? nest_walk_launch<false, false, true>(sh, a, n, st) : nest_walk_launch<false, false, false>(sh, a, n, st);
+    }
+    return (int)hipGetLastError();
+}
+
+int launch_nest_select(const NestArgs &a, void *stream) {
+    if (a.n_runs <= 0) return 0;
+    hipLaunchKernelGGL(nest_select_kernel, dim3((unsigned)a.n_runs), dim3(kSelThreads), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace mp

@@ -1,0 +1,307 @@
+"""Evidence and posterior samples on the GPU: nested sampling (Skilling 2006) with batch removal, device-resident.
+
+Every iteration of every run is one select launch (the K lowest live points die; ln X and ln Z advance) and one walk launch
+(each dead slot is refilled by a constrained DE random walk from a survivor); the host reads the dead points back once per chunk
+of iterations (include/magprop_amd.h mp_nested_*).  The final estimate is host-side and pure: ``add_live``, ``estimate`` and
+``resample_equal`` need no device, after dynesty's ``add_live`` and ``resample_equal``.
+
+The prior is uniform over a box in sampler coordinates, as for ``EnsembleSampler.log_evidence``.  The live set starts from
+uniform box draws with a finite lnprob, so the run integrates over the region where the model succeeds and
+ln Z = ln Z_ns + ln f_valid (``tempering.validity_term``).
+"""
+import ctypes as C
+import math
+import warnings
+
+import numpy as np
+
+from . import _capi, engine, tempering
+from .optimize import OptimizeResult, _variant_box
+
+TARGETS = {"posterior": 0, "gaussian": 1}
+MAX_DRAW_ROUNDS = 4096
+
+
+class Results(OptimizeResult):
+    """dynesty's result names as a dict whose keys are also attributes (one run)."""
+
+
+def add_live(lnx_final, live_lnl):
+    """dynesty's add_live: the N live points in ascending lnL with volumes X_final (1 - j / (N + 1)), j = 1 .. N; returns
+    (order, ln X of every one, ln w of every one), ln w_j = lnL_j + ln(X_{j-1} - X_j) = lnL_j + ln X_final - ln(N + 1)."""
+    lnl = np.asarray(live_lnl, dtype=np.float64)
+    n = lnl.size
+    order = np.lexsort((np.arange(n), lnl))
+    j = np.arange(1, n + 1)
+    lnx = float(lnx_final) + np.log1p(-j / (n + 1.0))
+    lnw = lnl[order] + float(lnx_final) - math.log(n + 1.0)
+    return order, lnx, lnw
+
+
+def dead_weights(dead_lnl, dead_n):
+    """(ln X after each dead point, ln w of each) of the dead sequence: ln X_i = ln X_{i-1} - 1 / n_i,
+    ln w_i = lnL_i + ln X_{i-1} + ln(-expm1(-1 / n_i)), from ln X_0 = 0."""
+    lnl = np.asarray(dead_lnl, dtype=np.float64)
+    inv = 1.0 / np.asarray(dead_n, dtype=np.float64)
+    lnx = -np.cumsum(inv)
+    prev = np.concatenate([[0.0], lnx[:-1]])
+    return lnx, lnl + prev + np.log(-np.expm1(-inv))
+
+
+def _logsumexp(a):
+    a = np.asarray(a, dtype=np.float64)
+    m = np.max(a) if a.size else -np.inf
+    if not np.isfinite(m):
+        return float(m)
+    return float(m + np.log(np.sum(np.exp(a - m))))
+
+
+def estimate(dead_lnl, dead_n, live_lnl, nlive, ln_f_valid=0.0, dln_f_valid=0.0):
+    """ln Z, its error, the information H and the weighted sequence of one run.  Dead points then the live points (add_live);
+    p_i = w_i / Z, H = sum p_i ln(L_i / Z), dlnZ = sqrt(H / nlive) combined in quadrature with the error of ln f_valid.
+    Returns a dict: logz, logzerr, information, logl, logwt, logvol, order (indices into the live set of the appended rows)."""
+    lnx, lnw_d = dead_weights(dead_lnl, dead_n)
+    lnx_final = float(lnx[-1]) if lnx.size else 0.0
+    order, lnx_l, lnw_l = add_live(lnx_final, live_lnl)
+    logl = np.concatenate([np.asarray(dead_lnl, dtype=np.float64), np.asarray(live_lnl, dtype=np.float64)[order]])
+    logwt = np.concatenate([lnw_d, lnw_l])
+    logz = _logsumexp(logwt)
+    if not np.isfinite(logz):
+        raise ValueError("every weight is zero: no live or dead point has a finite lnL")
+    p = np.exp(logwt - logz)
+    keep = p > 0.0
+    h = float(max(np.sum(p[keep] * (logl[keep] - logz)), 0.0))
+    err = math.sqrt(h / int(nlive) + float(dln_f_valid) ** 2)
+    return {"logz": logz + float(ln_f_valid), "logzerr": err, "information": h, "logl": logl, "logwt": logwt,
+            "logvol": np.concatenate([lnx, lnx_l]), "order": order}
+
+
+def resample_equal(samples, logwt, rng=None):
+    """Systematic resampling to equal weights (dynesty's resample_equal): n = len(samples) positions (u + i) / n, i = 0 .. n-1,
+    one uniform u, against the cumulative normalised weights; the picked rows in random order."""
+    samples = np.asarray(samples)
+    w = np.exp(np.asarray(logwt, dtype=np.float64) - _logsumexp(logwt))
+    if samples.shape[0] != w.size or w.size == 0:
+        raise ValueError("one log-weight per sample expected")
+    rng = np.random.default_rng(rng)
+    n = w.size
+    cum = np.cumsum(w)
+    cum /= cum[-1]
+    idx = np.minimum(np.searchsorted(cum, (rng.random() + np.arange(n)) / n, side="right"), n - 1)
+    return samples[rng.permutation(idx)]
+
+
+def _check_args(x, datasets, nlive, nbatch, walks, variant, ndim, bounds, n_runs, g0, sigma, target):
+    """(box lower, box upper, prior lower, prior upper, log mask, nbatch, number of datasets): every check, no device touched."""
+    if target not in TARGETS:
+        raise ValueError(f"target must be one of {tuple(TARGETS)}, got {target!r}")
+    if int(nlive) != nlive or not _capi.NEST_MIN_LIVE <= nlive <= _capi.NEST_MAX_LIVE:
+        raise ValueError(f"nlive must be an integer in {_capi.NEST_MIN_LIVE} .. {_capi.NEST_MAX_LIVE}")
+    nbatch = max(1, int(nlive) // 4) if nbatch is None else nbatch
+    if int(nbatch) != nbatch or not 1 <= nbatch <= nlive // 2:
+        raise ValueError("nbatch must be an integer in 1 .. nlive // 2")
+    if int(walks) != walks or not 1 <= walks <= _capi.NEST_MAX_WALKS:
+        raise ValueError(f"walks must be an integer in 1 .. {_capi.NEST_MAX_WALKS}")
+    if not np.isfinite(g0):
+        raise ValueError("g0 must be finite (<= 0: 2.38 / sqrt(2 ndim))")
+    if not 0.0 <= sigma < 1.0 / math.sqrt(3.0):
+        raise ValueError("sigma must lie in [0, 1/sqrt(3))")
+    if int(n_runs) != n_runs or n_runs < 1:
+        raise ValueError("n_runs must be a positive integer")
+    if target == "gaussian":
+        if bounds is None:
+            raise ValueError("the gaussian target needs bounds")
+        b = np.asarray(bounds, dtype=np.float64)
+        if b.ndim != 2 or b.shape[1] != 2 or not 1 <= b.shape[0] <= 9:
+            raise ValueError("bounds must be 1 to 9 (lower, upper) pairs")
+        plo = phi = mask = None
+        n_ds = 1
+    else:
+        plo, phi, mask = _variant_box(variant, ndim)
+        if bounds is None:
+            b = np.stack([plo, phi], axis=1)
+        else:
+            b = np.asarray(bounds, dtype=np.float64)
+            if b.shape != (ndim, 2):
+                raise ValueError(f"bounds must be {ndim} (lower, upper) pairs")
+        n_ds = len(datasets) if datasets is not None else (1 if x is not None else 0)
+        if n_ds == 0:
+            raise ValueError("a dataset is required: (x, y, yerr) or datasets=[...]")
+    lo, hi = b[:, 0].copy(), b[:, 1].copy()
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("every bound must be finite with lower < upper")
+    if n_ds * int(n_runs) > _capi.MAX_DATASETS:
+        raise ValueError(f"len(datasets) x n_runs runs must be at most {_capi.MAX_DATASETS}")
+    return lo, hi, plo, phi, mask, int(nbatch), n_ds
+
+
+class NestedSampler:
+    """Nested sampling of the log-posterior of light curve (x, y, yerr), or of every light curve of datasets=[(x, y, yerr), ...],
+    under a uniform prior over a box, on the GPU.
+
+    nlive live points per run (16 .. 4096); nbatch of them die per iteration (1 .. nlive // 2; default nlive // 4) and are
+    replaced by constrained random walks of `walks` DE steps (gamma = g0 (1 + sigma sqrt(3) (2u - 1)), g0 <= 0: 2.38 / sqrt(2
+    ndim)) whose difference vectors come from the surviving live points.  variant / ndim / GRBtype / bounds follow
+    optimize.differential_evolution (default box: the variant's prior box).  n_runs: independent runs per dataset, all in one
+    launch per iteration (run index = dataset index x n_runs + run).  seed keys both the live-set draws (numpy) and the device's
+    walks (Philox).  target="gaussian" samples the isotropic unit Gaussian -0.5 sum x^2 in `bounds` (tests, measurements)."""
+
+    def __init__(self, x=None, y=None, yerr=None, nlive=500, nbatch=None, walks=25, variant="synth", ndim=6, GRBtype=None,
+                 datasets=None, n_runs=1, seed=0, bounds=None, log_mask=None, g0=0.0, sigma=0.1, target="posterior", device=-1):
+        lo, hi, plo, phi, mask, nbatch, n_ds = _check_args(x, datasets, nlive, nbatch, walks, variant, ndim, bounds, n_runs, g0,
+                                                            sigma, target)
+        self.lower, self.upper = lo, hi
+        self.ndim = lo.size
+        self.nlive, self.nbatch, self.walks = int(nlive), nbatch, int(walks)
+        self.variant, self.GRBtype, self.target = variant, GRBtype, target
+        self.datasets = [] if target == "gaussian" else (list(datasets) if datasets is not None else [(x, y, yerr)])
+        self.n_runs = n_ds * int(n_runs)
+        self.run_ds = np.repeat(np.arange(n_ds, dtype=np.int32), int(n_runs))
+        self.seed, self.g0, self.sigma, self.device = int(seed), float(g0), float(sigma), device
+        self._prior = (plo, phi, mask if log_mask is None else log_mask)
+        self.handle = None
+        self.results = None
+
+    def _open(self):
+        if self.handle is not None:
+            return
+        cfg = _capi.cfg_lib() if self.variant == "lib" else _capi.cfg_synth()
+        self.handle = _capi.Handle(cfg, engine.grid(self.GRBtype), self.device)
+        if self.target == "posterior":
+            self.handle.set_prior(*self._prior)
+            for k, (dx, dy, de) in enumerate(self.datasets):
+                self.handle.set_dataset(k, dx, dy, de)
+
+    def close(self):
+        if self.handle is not None:
+            self.handle.close()
+            self.handle = None
+
+    def initial_live(self):
+        """(live[n_runs, nlive, ndim], prior draws per run): uniform box draws from np.random.default_rng(seed), run after run;
+        the first nlive with a finite lnprob are kept, and the draws up to the last one kept are counted."""
+        rng = np.random.default_rng(self.seed)
+        n, lo, hi = self.nlive, self.lower, self.upper
+        live = np.empty((self.n_runs, n, self.ndim))
+        draws = np.zeros(self.n_runs, dtype=np.int64)
+        for r in range(self.n_runs):
+            if self.target == "gaussian":
+                live[r] = lo + (hi - lo) * rng.random((n, self.ndim))
+                draws[r] = n
+                continue
+            got = 0
+            for _ in range(MAX_DRAW_ROUNDS):
+                P = lo + (hi - lo) * rng.random((2 * n, self.ndim))
+                ok = np.isfinite(self.handle.lnprob_batch(P, ds_id=int(self.run_ds[r])))
+                idx = np.nonzero(ok)[0][:n - got]
+                live[r, got:got + idx.size] = P[idx]
+                got += idx.size
+                draws[r] += (idx[-1] + 1) if got == n else P.shape[0]
+                if got == n:
+                    break
+            else:
+                raise RuntimeError(f"run {r}: fewer than {n} finite draws in {MAX_DRAW_ROUNDS * 2 * n} uniform box draws")
+        return live, draws
+
+    def run_nested(self, dlogz=0.01, maxiter=None):
+        """Run every run until log1p(exp(lnL_max + ln X - ln Z)) < dlogz, or for maxiter iterations; fills .results (a Results
+        for one run, else a list in run order): logz, logzerr, information, samples, logl, logwt, logvol, niter (iterations of
+        nbatch dead points), ncall (prior draws of the live set plus evaluations inside walks), eff (100 x dead points / ncall),
+        nzero (walks that accepted nothing), ln_f_valid, samples_n (live count of every row), stopped."""
+        if not (np.isfinite(dlogz) and dlogz > 0.0):
+            raise ValueError("dlogz must be finite and > 0")
+        if maxiter is not None and (int(maxiter) != maxiter or maxiter < 0):
+            raise ValueError("maxiter must be an integer >= 0")
+        self._open()
+        live0, draws = self.initial_live()
+        L = _capi.lib()
+        dp = C.POINTER(C.c_double)
+        ns = L.mp_nested_create(self.handle._h, self.nlive, self.nbatch, self.n_runs, self.ndim,
+                                self.run_ds.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint64(self.seed), self.walks, self.g0,
+                                self.sigma, float(dlogz), self.lower.ctypes.data_as(dp), self.upper.ctypes.data_as(dp),
+                                TARGETS[self.target])
+        if not ns:
+            raise _capi.MagpropAmdError("mp_nested_create failed: " + _capi.last_error())
+        try:
+            _capi.check(L.mp_nested_set_live(ns, np.ascontiguousarray(live0).ctypes.data_as(dp)), "mp_nested_set_live")
+            _capi.check(L.mp_nested_run(ns, 2 ** 31 - 1 if maxiter is None else int(maxiter), None), "mp_nested_run")
+            st = get_state(L, ns, self.n_runs, self.nlive, self.ndim)
+            dead = [get_dead(L, ns, r, self.ndim) for r in range(self.n_runs)]
+        finally:
+            L.mp_nested_destroy(ns)
+        out = []
+        for r in range(self.n_runs):
+            lnf, dlnf = tempering.validity_term(self.nlive, draws[r]) if self.target == "posterior" else (0.0, 0.0)
+            pars, lnl, nl = dead[r]
+            est = estimate(lnl, nl, st["lnl"][r], self.nlive, lnf, dlnf)
+            samples = np.concatenate([pars, st["live"][r][est["order"]]])
+            n_dead = lnl.size
+            ncall = int(draws[r]) + int(st["ncall"][r])
+            walks_run = int(st["nit"][r]) * self.nbatch
+            nzero = int(st["nzero"][r])
+            if walks_run and nzero > 0.01 * walks_run:
+                warnings.warn(f"run {r}: {nzero} of {walks_run} walks accepted no step: the live set may be poorly mixed "
+                              "(more walks, or a smaller g0)", RuntimeWarning, stacklevel=2)
+            out.append(Results(
+                logz=est["logz"], logzerr=est["logzerr"], information=est["information"], samples=samples, logl=est["logl"],
+                logwt=est["logwt"], logvol=est["logvol"], niter=int(st["nit"][r]), ncall=ncall,
+                eff=100.0 * n_dead / max(ncall, 1), nzero=nzero, nacc=int(st["nacc"][r]), ln_f_valid=lnf,
+                samples_n=np.concatenate([nl, np.arange(self.nlive, 0, -1)]), stopped=bool(st["stopped"][r]),
+                device_logz=float(st["lnz"][r])))
+        self.results = out[0] if self.n_runs == 1 else out
+        return self.results
+
+    def _run(self, run):
+        res = self.results if isinstance(self.results, list) else [self.results]
+        if self.results is None:
+            raise ValueError("run_nested first")
+        if int(run) != run or not 0 <= run < len(res):
+            raise ValueError(f"run must be 0 .. {len(res) - 1}")
+        return res[int(run)]
+
+    def resample_equal(self, run=0, seed=None):
+        """Equal-weight posterior samples of run `run` (systematic resampling of its weighted sequence)."""
+        r = self._run(run)
+        return resample_equal(r.samples, r.logwt, self.seed if seed is None else seed)
+
+    def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), run=0):
+        """Posterior-predictive band of run `run`: the quantiles q of the model light curves of its equal-weight samples (at most
+        _capi.BAND_MAX_SAMPLES, evenly thinned), on this sampler's handle (mp_model_band).  Returns {"t": grid, "Ltot": (nq,
+        n_grid), ..., "n_used": rows that entered}."""
+        if self.target != "posterior":
+            raise ValueError("get_model_band needs the posterior target: the gaussian target has no light curve")
+        qa, _, names = _capi.band_args(q, components)
+        rows = self.resample_equal(run)
+        if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
+            rows = rows[np.linspace(0, rows.shape[0] - 1, _capi.BAND_MAX_SAMPLES).astype(int)]
+        band, _, used = self.handle.model_band(rows, qa, names)
+        out = {"t": self.handle.tgrid.copy()}
+        out.update({c: band[k] for k, c in enumerate(names)})
+        out["n_used"] = used
+        return out
+
+
+def get_state(L, ns, n_runs, nlive, ndim):
+    """mp_nested_get_state as arrays: live (n_runs, nlive, ndim), lnl / status / acc (n_runs, nlive), per run nit, stopped, lnx,
+    lnz, ncall, nacc, nzero."""
+    st = {"live": np.empty((n_runs, nlive, ndim)), "lnl": np.empty((n_runs, nlive)), "status": np.empty((n_runs, nlive), dtype=np.int32),
+          "acc": np.empty((n_runs, nlive), dtype=np.int32), "nit": np.empty(n_runs, dtype=np.int32),
+          "stopped": np.empty(n_runs, dtype=np.int32), "lnx": np.empty(n_runs), "lnz": np.empty(n_runs),
+          "ncall": np.empty(n_runs, dtype=np.int64), "nacc": np.empty(n_runs, dtype=np.int64), "nzero": np.empty(n_runs, dtype=np.int64)}
+    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    _capi.check(L.mp_nested_get_state(ns, st["live"].ctypes.data_as(dp), st["lnl"].ctypes.data_as(dp), st["status"].ctypes.data_as(ip),
+                                      st["acc"].ctypes.data_as(ip), st["nit"].ctypes.data_as(ip), st["stopped"].ctypes.data_as(ip),
+                                      st["lnx"].ctypes.data_as(dp), st["lnz"].ctypes.data_as(dp), st["ncall"].ctypes.data_as(lp),
+                                      st["nacc"].ctypes.data_as(lp), st["nzero"].ctypes.data_as(lp)), "mp_nested_get_state")
+    return st
+
+
+def get_dead(L, ns, run, ndim):
+    """mp_nested_get_dead of one run: (pars[n, ndim], lnl[n], live count[n])."""
+    n = C.c_int64(0)
+    _capi.check(L.mp_nested_get_dead(ns, int(run), 0, None, None, None, C.byref(n)), "mp_nested_get_dead")
+    pars, lnl, nl = np.empty((n.value, ndim)), np.empty(n.value), np.empty(n.value, dtype=np.int32)
+    _capi.check(L.mp_nested_get_dead(ns, int(run), n.value, pars.ctypes.data_as(C.POINTER(C.c_double)),
+                                     lnl.ctypes.data_as(C.POINTER(C.c_double)), nl.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)),
+                "mp_nested_get_dead")
+    return pars, lnl, nl

@@ -1,0 +1,167 @@
+"""numpy restatement of the nested sampler (include/magprop_amd.h mp_nested_*): the ranking, the Philox draw layout, the
+constrained DE walks with the unfused arithmetic of the kernels (magprop_amd/csrc/mp_nest.hip), the volume bookkeeping and the
+stop rule.  Test infrastructure: the GPU tests compare the device state with it bit for bit (ln X and ln Z to rounding: the
+device's log1p / exp / expm1 are not numpy's), the CPU tests check with it that the scheme samples the constrained prior.
+Every product and sum is a separately rounded float64 operation in the kernel's order (Python floats)."""
+import math
+
+import numpy as np
+
+from moves_restated import pick, pick_skip
+from oracle.stretch_oracle import philox4x32_10, u01
+
+M32 = 0xFFFFFFFF
+CTR = 0x4E000000
+
+
+def draw(seed, t, r, slot, j):
+    """Philox (seed; t, r, slot, 0x4E000000 + j)."""
+    seed = int(seed)
+    return philox4x32_10(seed & M32, seed >> 32, int(t) & M32, int(r), int(slot), CTR + int(j))
+
+
+def logaddexp(x, y):
+    m = max(x, y)
+    if m == -math.inf:
+        return m
+    return m + math.log1p(math.exp(-abs(x - y)))
+
+
+def stops(lmax, lnx, lnz, dlogz):
+    """log1p(exp((lnL_max + ln X) - ln Z)) < dlogz (NaN: no)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.log1p(np.exp((np.float64(lmax) + np.float64(lnx)) - np.float64(lnz)))
+    return bool(v < dlogz)
+
+
+def resolve(g0, sigma, ndim):
+    """(g0, s3) as the library keeps them."""
+    return (g0 if g0 > 0.0 else 2.38 / math.sqrt(2.0 * ndim)), sigma * math.sqrt(3.0)
+
+
+class State:
+    """live[n_runs, N, ndim], lnl, status, acc [n_runs, N]; per run nit, stopped, lnx, lnz, ncall, nacc, nzero; dead rows per run."""
+
+    def __init__(self, live, lnl, status):
+        n_runs, n = lnl.shape
+        self.live, self.lnl, self.status = live, lnl, status
+        self.acc = np.zeros((n_runs, n), dtype=np.int32)
+        self.nit = np.zeros(n_runs, dtype=np.int32)
+        self.stopped = np.zeros(n_runs, dtype=np.int32)
+        self.lnx = np.zeros(n_runs)
+        self.lnz = np.full(n_runs, -np.inf)
+        self.ncall = np.zeros(n_runs, dtype=np.int64)
+        self.nacc = np.zeros(n_runs, dtype=np.int64)
+        self.nzero = np.zeros(n_runs, dtype=np.int64)
+        self.dead_pars = [[] for _ in range(n_runs)]
+        self.dead_lnl = [[] for _ in range(n_runs)]
+        self.dead_n = [[] for _ in range(n_runs)]
+
+
+def _clean(v):
+    return -math.inf if v != v else float(v)
+
+
+def start(live0, evaluate):
+    """The live set live0 (n_runs, N, ndim) evaluated: evaluate(rows[n, ndim]) -> (lnL, status)."""
+    live = np.array(live0, dtype=np.float64)
+    n_runs, n, ndim = live.shape
+    lnl, st = evaluate(live.reshape(-1, ndim))
+    lnl = np.array([_clean(v) for v in lnl]).reshape(n_runs, n)
+    return State(live, lnl, np.asarray(st, dtype=np.int32).reshape(n_runs, n))
+
+
+def order(lnl):
+    """Slots in ascending (lnL, slot)."""
+    return sorted(range(len(lnl)), key=lambda j: (lnl[j], j))
+
+
+def walk(s, r, slot, t, surv, lstar, seed, walks, g0, s3, lower, upper, evaluate_one):
+    """The constrained walk into dead slot `slot` of run r, iteration t: (end point, lnL, status, accepted steps, evaluations)."""
+    m = len(surv)
+    u = draw(seed, t, r, slot, 0)
+    fr = surv[pick(u01(u[0], u[1]), m)]
+    x = [float(v) for v in s.live[r, fr]]
+    lnl, st = float(s.lnl[r, fr]), int(s.status[r, fr])
+    n_acc = n_eval = 0
+    for k in range(walks):
+        u = draw(seed, t, r, slot, 2 * k + 1)
+        v = draw(seed, t, r, slot, 2 * k + 2)
+        c1 = pick(u01(u[0], u[1]), m)
+        c2 = pick_skip(u01(u[2], u[3]), m, c1)
+        a, b = s.live[r, surv[c1]], s.live[r, surv[c2]]
+        gamma = g0 * (1.0 + s3 * (2.0 * u01(v[0], v[1]) - 1.0))
+        q = [x[d] + gamma * (float(a[d]) - float(b[d])) for d in range(len(x))]
+        if not all(lower[d] <= q[d] <= upper[d] for d in range(len(x))):
+            continue
+        lq, sq = evaluate_one(np.array(q))
+        lq = _clean(lq)
+        n_eval += 1
+        if lq > lstar:
+            x, lnl, st = q, lq, int(sq)
+            n_acc += 1
+    return x, lnl, st, n_acc, n_eval
+
+
+def iteration(s, nbatch, seed, walks, g0, sigma, dlogz, lower, upper, evaluate_one):
+    """One iteration of every run not stopped (the stop rule first, on the live set as it stands)."""
+    n_runs, n, ndim = s.live.shape
+    g0, s3 = resolve(g0, sigma, ndim)
+    for r in range(n_runs):
+        if s.stopped[r]:
+            continue
+        o = order(s.lnl[r])
+        if stops(s.lnl[r, o[-1]], s.lnx[r], s.lnz[r], dlogz):
+            s.stopped[r] = 1
+            continue
+        dead, surv = o[:nbatch], sorted(o[nbatch:])
+        lnx, lnz = float(s.lnx[r]), float(s.lnz[r])
+        for k, j in enumerate(dead):
+            s.dead_pars[r].append(s.live[r, j].copy())
+            s.dead_lnl[r].append(float(s.lnl[r, j]))
+            s.dead_n[r].append(n - k)
+            inv = 1.0 / float(n - k)
+            lnw = (float(s.lnl[r, j]) + lnx) + math.log(-math.expm1(-inv))
+            lnx = lnx - inv
+            lnz = logaddexp(lnz, lnw)
+        s.lnx[r], s.lnz[r] = lnx, lnz
+        lstar = float(s.lnl[r, dead[-1]])
+        t = int(s.nit[r])
+        out = [walk(s, r, j, t, surv, lstar, seed, walks, g0, s3, lower, upper, evaluate_one) for j in dead]
+        for j, (x, lq, sq, na, ne) in zip(dead, out):
+            s.live[r, j], s.lnl[r, j], s.status[r, j], s.acc[r, j] = x, lq, sq, na
+            s.ncall[r] += ne
+            s.nacc[r] += na
+            s.nzero[r] += na == 0
+        s.nit[r] += 1
+
+
+def check_stops(s, dlogz):
+    for r in range(len(s.nit)):
+        if not s.stopped[r] and stops(np.max(s.lnl[r]), s.lnx[r], s.lnz[r], dlogz):
+            s.stopped[r] = 1
+
+
+def run(s, iterations, nbatch, seed, walks=25, g0=0.0, sigma=0.1, dlogz=0.01, lower=None, upper=None, evaluate_one=None):
+    """Up to `iterations` iterations and the stop check behind them (mp_nested_run); s is advanced in place."""
+    if iterations <= 0 or np.all(s.stopped):
+        return s
+    for _ in range(iterations):
+        if np.all(s.stopped):
+            break
+        iteration(s, nbatch, seed, walks, g0, sigma, dlogz, lower, upper, evaluate_one)
+    check_stops(s, dlogz)
+    return s
+
+
+def gaussian_one(q):
+    """The unit-Gaussian target of the kernels (lnL = lnL - (0.5 x_d) x_d in index order), status 0."""
+    lp = 0.0
+    for v in q:
+        lp = lp - (0.5 * float(v)) * float(v)
+    return lp, 0
+
+
+def gaussian(P):
+    out = np.array([gaussian_one(p)[0] for p in P])
+    return out, np.zeros(len(P), dtype=np.int32)

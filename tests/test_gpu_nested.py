@@ -1,0 +1,255 @@
+"""GPU tests of the nested sampler (include/magprop_amd.h mp_nested_*, magprop_amd.nested): the device state against the numpy
+restatement (tests/nest_restated.py) bit for bit, chunk independence, evidence against closed forms and brute force, posterior
+samples against a long ensemble chain, a long Swift light curve, and refused handles."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+from scipy.special import erf
+
+import nest_restated as nr
+from conftest import TRUTHS
+
+pytestmark = pytest.mark.gpu
+
+dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+EVIDENCE_INFLATION = 10.0       # tests/test_gpu_tempering.py: Humped with yerr x 10
+
+
+class RawNested:
+    """mp_nested_* through ctypes on handle h."""
+
+    def __init__(self, h, nlive, nbatch, n_runs, ndim, lower, upper, seed, walks, target, ds=None, g0=0.0, sigma=0.1, dlogz=0.01):
+        from magprop_amd import _capi
+        self.L, self.nlive, self.n_runs, self.ndim = _capi.lib(), nlive, n_runs, ndim
+        self.lo, self.hi = np.ascontiguousarray(lower, dtype=np.float64), np.ascontiguousarray(upper, dtype=np.float64)
+        ids = None if ds is None else np.ascontiguousarray(ds, dtype=np.int32)
+        self.ns = self.L.mp_nested_create(h._h, nlive, nbatch, n_runs, ndim, None if ids is None else ids.ctypes.data_as(ip),
+                                          C.c_uint64(seed), walks, g0, sigma, dlogz, self.lo.ctypes.data_as(dp),
+                                          self.hi.ctypes.data_as(dp), target)
+        assert self.ns, _capi.last_error()
+
+    def set_live(self, live):
+        p = np.ascontiguousarray(live, dtype=np.float64)
+        assert self.L.mp_nested_set_live(self.ns, p.ctypes.data_as(dp)) == 0
+
+    def run(self, n):
+        running = C.c_int32(-1)
+        assert self.L.mp_nested_run(self.ns, n, C.byref(running)) == 0
+        return running.value
+
+    def state(self):
+        from magprop_amd import nested
+        st = nested.get_state(self.L, self.ns, self.n_runs, self.nlive, self.ndim)
+        st["dead"] = [nested.get_dead(self.L, self.ns, r, self.ndim) for r in range(self.n_runs)]
+        return st
+
+    def close(self):
+        self.L.mp_nested_destroy(self.ns)
+
+
+def _assert_equal(st, s):
+    assert np.array_equal(st["live"], s.live)
+    assert np.array_equal(st["lnl"], s.lnl)
+    assert np.array_equal(st["status"], s.status)
+    assert np.array_equal(st["acc"], s.acc)
+    assert np.array_equal(st["nit"], s.nit)
+    assert np.array_equal(st["stopped"], s.stopped)
+    assert np.array_equal(st["ncall"], s.ncall)
+    assert np.array_equal(st["nacc"], s.nacc)
+    assert np.array_equal(st["nzero"], s.nzero)
+    for r, (pars, lnl, n) in enumerate(st["dead"]):
+        assert np.array_equal(pars, np.array(s.dead_pars[r]).reshape(-1, s.live.shape[2]))
+        assert np.array_equal(lnl, np.array(s.dead_lnl[r]))
+        assert np.array_equal(n, np.array(s.dead_n[r], dtype=np.int32))
+    assert np.allclose(st["lnx"], s.lnx, rtol=1e-14, atol=0.0)
+    assert np.allclose(st["lnz"], s.lnz, rtol=1e-14, atol=0.0)
+
+
+def _gaussian_lnz(lo, hi):
+    """ln Z of exp(-0.5 |x|^2) under the uniform prior on the box: a product of erf differences over the box volume."""
+    return sum(math.log(math.sqrt(math.pi / 2.0) * (erf(h / math.sqrt(2.0)) - erf(l / math.sqrt(2.0))) / (h - l))
+               for l, h in zip(lo, hi))
+
+
+@pytest.mark.parametrize("n_runs", [1, 3])
+def test_gaussian_state_matches_the_restatement_bit_for_bit(n_runs):
+    """Unit Gaussian in an asymmetric 3-d box, N = 32, K = 8, 10 steps per walk, dlogz = 0.05: 6 iterations, then on to the stop
+    rule; live set, lnL, status, accepted counts, the dead sequence, the stop iteration and the counters equal the restatement,
+    ln X and ln Z to 1e-14 relative."""
+    from magprop_amd import _capi, engine
+    ndim, nlive, nbatch, walks, seed = 3, 32, 8, 10, 20261015 + n_runs
+    lo, hi = np.array([-2.0, -1.0, -4.0]), np.array([3.0, 2.5, 1.5])
+    live0 = lo + (hi - lo) * np.random.default_rng(7 + n_runs).random((n_runs, nlive, ndim))
+    kw = dict(walks=walks, g0=0.0, sigma=0.1, dlogz=0.05, lower=lo, upper=hi, evaluate_one=nr.gaussian_one)
+    s = nr.start(live0, nr.gaussian)
+    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    ns = RawNested(h, nlive, nbatch, n_runs, ndim, lo, hi, seed, walks, 1, dlogz=0.05)
+    try:
+        ns.set_live(live0.reshape(-1, ndim))
+        ns.run(6)
+        nr.run(s, 6, nbatch, seed, **kw)
+        _assert_equal(ns.state(), s)
+        assert ns.run(1000) == 0
+        nr.run(s, 1000, nbatch, seed, **kw)
+        st = ns.state()
+    finally:
+        ns.close()
+        h.close()
+    _assert_equal(st, s)
+    assert np.all(st["stopped"] == 1) and np.all(st["nit"] > 6)
+    print(f"stop iterations {st['nit'].tolist()}, ln Z {st['lnz'].tolist()}")
+
+
+def test_chunks_of_one_iteration_equal_one_unsplit_run():
+    """Two runs of N = 64 (K = 8, 25 steps) on the unit Gaussian: mp_nested_run(1) called until both stopped equals one
+    mp_nested_run(10 000), whose chunks are the library's own."""
+    from magprop_amd import _capi, engine
+    ndim, nlive, nbatch = 4, 64, 8
+    lo, hi = np.full(ndim, -3.0), np.array([2.0, 3.0, 4.0, 5.0])
+    live0 = lo + (hi - lo) * np.random.default_rng(3).random((2 * nlive, ndim))
+    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    states = []
+    try:
+        for split in (True, False):
+            ns = RawNested(h, nlive, nbatch, 2, ndim, lo, hi, 11, 25, 1)
+            try:
+                ns.set_live(live0)
+                if split:
+                    for _ in range(10000):
+                        if ns.run(1) == 0:
+                            break
+                else:
+                    assert ns.run(10000) == 0
+                states.append(ns.state())
+            finally:
+                ns.close()
+    finally:
+        h.close()
+    a, b = states
+    for k in ("live", "lnl", "status", "acc", "nit", "stopped", "lnx", "lnz", "ncall", "nacc", "nzero"):
+        assert np.array_equal(a[k], b[k]), k
+    for (pa, la, na), (pb, lb, nb) in zip(a["dead"], b["dead"]):
+        assert np.array_equal(pa, pb) and np.array_equal(la, lb) and np.array_equal(na, nb)
+    assert np.all(a["nit"] > 33)                # (more than one of the library's chunks of 32)
+
+
+def test_gaussian_evidence_in_an_asymmetric_6d_box():
+    """Four runs in one launch, N = 512, K = 128: ln Z of each within 3 logzerr of the closed form."""
+    from magprop_amd import NestedSampler
+    lo = np.array([-2.0, -1.0, -4.0, -0.5, -3.0, -1.5])
+    hi = np.array([3.0, 2.5, 1.5, 4.0, 0.5, 1.0])
+    truth = _gaussian_lnz(lo, hi)
+    s = NestedSampler(nlive=512, nbatch=128, target="gaussian", bounds=np.stack([lo, hi], axis=1), n_runs=4, seed=5)
+    res = s.run_nested()
+    s.close()
+    for r in res:
+        print(f"6-d Gaussian: ln Z {r.logz:.4f} +- {r.logzerr:.4f} (truth {truth:.4f}), {r.niter} iterations, ncall {r.ncall}, "
+              f"eff {r.eff:.2f} %, walks without a step {r.nzero}")
+        assert r.stopped and abs(r.logz - truth) < 3.0 * r.logzerr, (r.logz, r.logzerr, truth)
+        assert abs(r.device_logz - r.logz) < 0.05
+
+
+def test_humped_evidence_against_brute_force(gsynth):
+    """Humped with yerr x 10 (the brute-force case of tests/test_gpu_tempering.py, -5.5046 measured there): the brute-force
+    evidence over 4 x 2^20 uniform box draws against a nested run of N = 1024, K = 256; within max(3 logzerr, 0.05)."""
+    from magprop_amd import LogProb, NestedSampler, synth
+    x, y, yerr = gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"] * EVIDENCE_INFLATION
+    lo, hi = synth.PRIOR_LOWER, synth.PRIOR_UPPER
+    lp = LogProb(x, y, yerr)
+    rng = np.random.default_rng(2026)
+    n_bf, chunk = 4 << 20, 1 << 18
+    vals = np.concatenate([lp(lo + (hi - lo) * rng.random((chunk, 6))) for _ in range(n_bf // chunk)])
+    w = np.exp(vals - vals.max())
+    lnz_bf = vals.max() + np.log(w.sum()) - np.log(n_bf)
+    s = NestedSampler(x, y, yerr, nlive=1024, nbatch=256, seed=9)
+    r = s.run_nested()
+    s.close()
+    print(f"Humped yerr x 10: brute force {lnz_bf:.4f}, nested {r.logz:.4f} +- {r.logzerr:.4f} (H {r.information:.2f}, "
+          f"ln f_valid {r.ln_f_valid:.4f}), {r.niter} iterations, ncall {r.ncall}, walks without a step {r.nzero}")
+    assert r.stopped
+    assert abs(r.logz - lnz_bf) < max(3.0 * r.logzerr, 0.05), (r.logz, r.logzerr, lnz_bf)
+
+
+def test_humped_posterior_samples(gsynth):
+    """Humped as it is, N = 1024, K = 256: every truth inside the central 95 % of the equal-weight samples; posterior means and
+    standard deviations against a stretch chain of 512 walkers x 3 000 steps from the truths (first 1 000 discarded): means within
+    0.3 chain sigma, standard deviations within a factor 1.35.  A band of the equal-weight samples brackets its median.
+    Calibrated once on an MI355X: mean shifts 0.005 .. 0.025 sigma, standard-deviation ratios 0.98 .. 1.21 (log10 M_disc: 1.21);
+    ln Z = -46.20 +- 0.12 in 77 iterations."""
+    from magprop_amd import EnsembleSampler, NestedSampler
+    x, y, yerr = gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"]
+    s = NestedSampler(x, y, yerr, nlive=1024, nbatch=256, seed=4)
+    r = s.run_nested()
+    eq = s.resample_equal()
+    band = s.get_model_band(q=(0.025, 0.5, 0.975))
+    s.close()
+    truth = np.array(TRUTHS["Humped"])
+    q025, q975 = np.quantile(eq, [0.025, 0.975], axis=0)
+    rng = np.random.default_rng(30)
+    e = EnsembleSampler(512, 6, x, y, yerr, seed=31)
+    e.run_mcmc(truth + 1.0e-4 * rng.standard_normal((512, 6)), 3000)
+    ref = e.get_chain()[1000:].reshape(-1, 6)
+    e.close()
+    dmean = np.abs(eq.mean(axis=0) - ref.mean(axis=0)) / ref.std(axis=0)
+    sratio = eq.std(axis=0) / ref.std(axis=0)
+    print(f"Humped: ln Z {r.logz:.3f} +- {r.logzerr:.3f}, {r.niter} iterations, ncall {r.ncall}, {eq.shape[0]} samples; mean "
+          f"shift / sigma {np.round(dmean, 3)}, sd ratio {np.round(sratio, 3)}, walks without a step {r.nzero}")
+    assert np.all((truth >= q025) & (truth <= q975)), (q025, q975)
+    assert np.all(dmean < 0.3), dmean
+    assert np.all((sratio > 1 / 1.35) & (sratio < 1.35)), sratio
+    lo_, mid, hi_ = band["Ltot"]
+    ok = np.isfinite(mid)
+    assert band["n_used"] > 0 and np.all(lo_[ok] <= mid[ok]) and np.all(mid[ok] <= hi_[ok])
+
+
+def test_long_swift_light_curve_lib_reaches_the_best_fit(gswift):
+    """LONG builds, lib variant: GRB 051016B (79 points, GRBtype "S") runs to the stop rule; its best dead lnL lies within 1 of
+    the DE optimizer's best fit."""
+    from magprop_amd import NestedSampler, optimize
+    x, y, yerr = gswift["swift_051016B_libS_ds"]
+    best = optimize.differential_evolution(x, y, yerr, variant="lib", GRBtype="S", seed=2, maxiter=1000)
+    s = NestedSampler(x, y, yerr, nlive=256, nbatch=64, variant="lib", GRBtype="S", seed=6)
+    r = s.run_nested()
+    s.close()
+    print(f"GRB 051016B: ln Z {r.logz:.3f} +- {r.logzerr:.3f}, best dead lnL {np.max(r.logl):.3f} (DE {best.lnprob:.3f}), "
+          f"{r.niter} iterations, ncall {r.ncall}")
+    assert r.stopped
+    assert np.max(r.logl) >= best.lnprob - 1.0, (np.max(r.logl), best.lnprob)
+
+
+def test_multi_device_and_alternative_torque_handles_are_refused():
+    from magprop_amd import _capi, engine
+    L = _capi.lib()
+    lo, hi = np.zeros(6), np.ones(6)
+    x = np.logspace(0.5, 3.0, 20)
+    hm = _capi.Handle(_capi.cfg_synth(), engine.grid(None), device=[0])
+    ha = _capi.Handle(_capi.cfg_synth(dipole_torque=1), engine.grid(None))
+    try:
+        for h, what in ((hm, "ONE device"), (ha, "dipole torque")):
+            h.set_dataset(0, x, np.ones_like(x), np.ones_like(x))
+            ns = L.mp_nested_create(h._h, 64, 16, 1, 6, None, C.c_uint64(0), 25, 0.0, 0.1, 0.01, lo.ctypes.data_as(dp),
+                                    hi.ctypes.data_as(dp), 0)
+            assert not ns and what in _capi.last_error()
+        # argument codes on a plain handle
+        h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+        for bad in (dict(nlive=8), dict(nbatch=33), dict(nbatch=0), dict(walks=0), dict(sigma=0.6), dict(dlogz=0.0),
+                    dict(upper=np.zeros(6)), dict(n_runs=65)):
+            kw = dict(nlive=64, nbatch=16, walks=25, sigma=0.1, dlogz=0.01, upper=hi, n_runs=1)
+            kw.update(bad)
+            ns = L.mp_nested_create(h._h, kw["nlive"], kw["nbatch"], kw["n_runs"], 6, None, C.c_uint64(0), kw["walks"], 0.0,
+                                    kw["sigma"], kw["dlogz"], lo.ctypes.data_as(dp),
+                                    np.ascontiguousarray(kw["upper"]).ctypes.data_as(dp), 1)
+            assert not ns, bad
+        ns = L.mp_nested_create(h._h, 64, 16, 1, 6, None, C.c_uint64(0), 25, 0.0, 0.1, 0.01, lo.ctypes.data_as(dp),
+                                hi.ctypes.data_as(dp), 1)
+        assert ns
+        assert L.mp_nested_run(ns, 1, None) == _capi.MP_ESTATE                   # before set_live
+        out = np.full((64, 6), 2.0)
+        assert L.mp_nested_set_live(ns, out.ctypes.data_as(dp)) == _capi.MP_EINVAL   # outside the box
+        L.mp_nested_destroy(ns)
+        h.close()
+    finally:
+        hm.close()
+        ha.close()
