@@ -59,10 +59,16 @@ struct HostDataset {
     std::vector<double> dx, idt, y, yerr;
 };
 
+// Device memory owned by its holder: freed on destruction (on the device current then: the destroy functions delete their object
+// inside a DeviceScope of its device), never copied.
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
     int ensure(size_t n) {
         if (n <= cap) return MP_OK;
         if (p) (void)hipFree(p);
@@ -73,10 +79,15 @@ struct DevBuf {
         cap = want;
         return MP_OK;
     }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+};
+
+// Allocates a driver's buffers (ensure) and points the fields of its launch arguments at them: bind(buffer, size, field).  The
+// first failure sticks in rc, and the allocations behind it are skipped.
+struct Binder {
+    int rc = MP_OK;
+    template <typename T, typename P>
+    void operator()(DevBuf<T> &b, size_t n, P *&field) {
+        if (!rc && !(rc = b.ensure(n))) field = b.p;
     }
 };
 
@@ -86,6 +97,10 @@ struct PinnedBuf {
     unsigned char *p = nullptr;
     unsigned char *dev = nullptr;   // the same memory as the device sees it (mapped, coherent): kernels may read and write it in place
     size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
     int ensure(size_t n) {
         if (n <= cap) return MP_OK;
         if (p) (void)hipHostFree(p);
@@ -97,12 +112,25 @@ struct PinnedBuf {
         cap = want;
         return MP_OK;
     }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = dev = nullptr;
-        cap = 0;
-    }
 };
+
+// An event owned by its holder (created by it when first needed, destroyed with it)
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+};
+
+// Device-to-host copies of the state of a driver: read_back(dst, src, n, dst2, src2, n2, ...) copies n elements of src to dst
+// for every triple whose dst is not NULL.
+int read_back() { return MP_OK; }
+template <typename T, typename... Rest>
+int read_back(T *dst, const T *src, size_t n, Rest... rest) {
+    if (dst) HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+    return read_back(rest...);
+}
 
 }  // namespace
 
@@ -139,7 +167,7 @@ struct mp_handle {
     // launch to have finished -- launches fewer than kOrderRing apart share nothing.
     static constexpr int kOrderRing = 8;
     DevBuf<int32_t> order[kOrderRing];
-    hipEvent_t order_done[kOrderRing] = {};
+    Event order_done[kOrderRing];
     unsigned order_next = 0;
     // Threading / stream contract (include/magprop_amd.h): every entry point that takes a handle or a sampler holds
     // `mu` for its duration.  Launches share nothing writable but their own outputs (round 4: no per-walker scratch rows),
@@ -170,15 +198,15 @@ int launch_lnprob_ordered(mp_handle *h, const mp::LaunchArgs &a_in, hipStream_t 
             const int rc = h->order[slot].ensure((size_t)a.n);
             if (rc) return rc;
         }
-        if (!h->order_done[slot]) HIP_TRY(hipEventCreateWithFlags(&h->order_done[slot], hipEventDisableTiming));
-        else HIP_TRY(hipStreamWaitEvent(st, h->order_done[slot], 0));
+        if (!h->order_done[slot].e) HIP_TRY(hipEventCreateWithFlags(&h->order_done[slot].e, hipEventDisableTiming));
+        else HIP_TRY(hipStreamWaitEvent(st, h->order_done[slot].e, 0));
         const int eo = mp::launch_order(h->sh, a.ds_id, a.n, h->order[slot].p, (void *)st);
         if (eo) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)eo));
         a.order = h->order[slot].p;
     }
     const int e = mp::launch_lnprob(h->sh, a, (void *)st);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (slot >= 0) HIP_TRY(hipEventRecord(h->order_done[slot], st));
+    if (slot >= 0) HIP_TRY(hipEventRecord(h->order_done[slot].e, st));
     return MP_OK;
 }
 }  // namespace
@@ -248,6 +276,55 @@ static int upload_dataset(mp_handle *h, int d, bool replaced) {
     const int rc = append_dataset(h, d);
     if (rc) return rc;
     publish_datasets(h);
+    return MP_OK;
+}
+
+// ---------------------------------------------------------------- what the resident drivers share
+// (the ensemble sampler, the differential-evolution optimizer and the nested sampler: mp_sampler_*, mp_optimizer_*, mp_nested_*)
+
+// The checks of their create functions (fn), in the order they fail: a multi-device handle (`multi`: what the message says about
+// it), ndim (the posterior, target 0, needs 6 or more), the driver's own arguments (args(): MP_OK or the code of a failure), the
+// alternative dipole torque, and the dataset of every one of n_groups groups (`group` g: ds_id[g], dataset 0 without ds_id).
+// The caller holds the handle's lock.
+template <class Args>
+static int check_create(mp_handle *h, const char *fn, const char *multi, int ndim, int target, const char *group, int n_groups,
+                        const int32_t *ds_id, Args &&args) {
+    if (!h->sub.empty()) return fail(MP_ESTATE, "%s: %s", fn, multi);
+    if (ndim < 1 || ndim > MP_MAX_NDIM || (target == 0 && ndim < 6)) return fail(MP_EINVAL, "%s: bad ndim %d", fn, ndim);
+    const int rc = args();
+    if (rc) return rc;
+    if (target != 0) return MP_OK;
+    if (h->sh.cfg.dipole_torque != 0)
+        return fail(MP_ESTATE, "%s: the alternative dipole torque (cfg.dipole_torque = 1) is served by the curve kernels only", fn);
+    for (int g = 0; g < n_groups; ++g) {
+        const int d = ds_id ? ds_id[g] : 0;
+        if (d < 0 || d >= MP_MAX_DATASETS || !h->ds[d].set) return fail(MP_ESTATE, "%s: %s %d refers to unset dataset %d", fn, group, g, d);
+    }
+    return MP_OK;
+}
+
+// the bounds box of the optimizer and the nested sampler: finite, lower < upper in every coordinate
+static int check_box(const char *fn, int ndim, const double *lower, const double *upper) {
+    for (int d = 0; d < ndim; ++d)
+        if (!(std::isfinite(lower[d]) && std::isfinite(upper[d]) && lower[d] < upper[d]))
+            return fail(MP_EINVAL, "%s: bounds of coordinate %d are empty or not finite", fn, d);
+    return MP_OK;
+}
+
+// the dataset of every row, ds_id[g] (dataset 0 without ds_id) for the `rows` consecutive rows of group g, uploaded to dst
+static int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int rows) {
+    std::vector<int32_t> ds((size_t)n_groups * rows);
+    for (int g = 0; g < n_groups; ++g) std::fill_n(ds.begin() + (size_t)g * rows, rows, ds_id ? ds_id[g] : 0);
+    HIP_TRY(hipMemcpy(dst, ds.data(), ds.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    return MP_OK;
+}
+
+// *running = the groups whose flag (d_flags[n], read back behind the work on the handle's stream) is not 1 (converged, stopped)
+static int groups_running(mp_handle *h, const int32_t *d_flags, int n, int *running) {
+    std::vector<int32_t> f((size_t)n);
+    HIP_TRY(hipMemcpyAsync(f.data(), d_flags, f.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *running = n - (int)std::count(f.begin(), f.end(), 1);
     return MP_OK;
 }
 
@@ -520,19 +597,8 @@ int mp_destroy(mp_handle *h) {
     }
     DeviceScope scope(h->device);
     (void)hipDeviceSynchronize();
-    h->d_wtab.release();
-    h->d_tgrid.release(); h->d_obs_dx.release(); h->d_obs_idt.release(); h->d_obs_y.release();
-    h->d_obs_yerr.release(); h->d_obs_g.release(); h->d_tile_ptr.release(); h->d_ds.release();
-    h->w_pars.release(); h->w_lnprob.release(); h->w_curves.release();
-    h->w_band.release(); h->w_band_out.release();
-    h->w_dsid.release(); h->w_status.release(); h->w_sweeps.release(); h->w_tile_log.release();
-    h->h_io.release();
-    for (int i = 0; i < mp_handle::kOrderRing; ++i) {
-        h->order[i].release();
-        if (h->order_done[i]) (void)hipEventDestroy(h->order_done[i]);
-    }
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // (frees the buffers and events, on the handle's device)
     return MP_OK;
 }
 
@@ -903,7 +969,7 @@ struct mp_sampler {
     static constexpr int kWin = 32;
     DevBuf<int32_t> d_win[2];
     PinnedBuf h_win[2];
-    hipEvent_t win_copied[2] = {nullptr, nullptr};
+    Event win_copied[2];
     int64_t win_id[2] = {-1, -1};
     bool ext_stream_work = false;   // half-steps were enqueued on a caller's stream since the last device-wide wait
     // failed proposals (the reference's fbad file): the device window d_bad is drained into this log
@@ -1010,42 +1076,29 @@ static mp::StretchArgs stretch_args(const mp_sampler *s, const int32_t *d_perm, 
 mp_sampler *mp_sampler_create(mp_handle *h, int n_walkers, int n_ensembles, int ndim, const int32_t *ens_ds_id,
                               uint64_t seed, double a, int target) {
     if (!h) { fail(MP_EINVAL, "mp_sampler_create: NULL handle"); return nullptr; }
-    if (!h->sub.empty()) { fail(MP_ESTATE, "mp_sampler_create: the device-resident sampler lives on ONE device (walker sharding across devices: magprop_amd/distributed.py)"); return nullptr; }
-    if (n_walkers < 2 || (n_walkers & 1)) { fail(MP_EINVAL, "mp_sampler_create: n_walkers must be even and >= 2"); return nullptr; }
-    if (n_ensembles < 1 || ndim < 1 || ndim > MP_MAX_NDIM || (target == 0 && ndim < 6)) {
-        fail(MP_EINVAL, "mp_sampler_create: bad n_ensembles / ndim");
-        return nullptr;
-    }
-    if (!(a > 1.0)) { fail(MP_EINVAL, "mp_sampler_create: stretch scale a must exceed 1"); return nullptr; }
-    if (target == 0 && h->sh.cfg.dipole_torque != 0) { fail(MP_ESTATE, "mp_sampler_create: the alternative dipole torque (cfg.dipole_torque = 1) is served by the curve kernels only"); return nullptr; }
     Lock lock(h->mu);
-    if (target == 0) {
-        for (int e = 0; e < n_ensembles; ++e) {
-            const int d = ens_ds_id ? ens_ds_id[e] : 0;
-            if (d < 0 || d >= MP_MAX_DATASETS || !h->ds[d].set) {
-                fail(MP_ESTATE, "mp_sampler_create: ensemble %d refers to unset dataset %d", e, d);
-                return nullptr;
-            }
-        }
-    }
+    const int rc = check_create(h, "mp_sampler_create", "the device-resident sampler lives on ONE device (walker sharding across devices: magprop_amd/distributed.py)",
+                                ndim, target, "ensemble", n_ensembles, ens_ds_id, [&] {
+        if (n_walkers < 2 || (n_walkers & 1)) return fail(MP_EINVAL, "mp_sampler_create: n_walkers must be even and >= 2");
+        if (n_ensembles < 1) return fail(MP_EINVAL, "mp_sampler_create: bad n_ensembles");
+        if (!(a > 1.0)) return fail(MP_EINVAL, "mp_sampler_create: stretch scale a must exceed 1");
+        return MP_OK;
+    });
+    if (rc) return nullptr;
     mp_sampler *s = new mp_sampler();
     s->h = h; s->n_walkers = n_walkers; s->n_ensembles = n_ensembles; s->n_total = n_walkers * n_ensembles;
     s->ndim = ndim; s->target = target; s->seed = seed; s->a = a;
     DeviceScope scope(h->device);
     const size_t nt = (size_t)s->n_total;
-    std::vector<int32_t> ds(nt, 0);
-    s->ens_ds.resize((size_t)n_ensembles);
-    for (int e = 0; e < n_ensembles; ++e) s->ens_ds[(size_t)e] = ens_ds_id ? ens_ds_id[e] : 0;
-    for (int e = 0; e < n_ensembles; ++e)
-        for (int k = 0; k < n_walkers; ++k) ds[(size_t)e * n_walkers + k] = ens_ds_id ? ens_ds_id[e] : 0;
+    for (int e = 0; e < n_ensembles; ++e) s->ens_ds.push_back(ens_ds_id ? ens_ds_id[e] : 0);
     constexpr size_t kBadRows = MP_BAD_WINDOW;   // device window of failed proposals between two drains (drain_bad)
     if (s->d_pos.ensure(nt * ndim) || s->d_lnprob.ensure(nt) || s->d_acc.ensure(nt) || s->d_dsid.ensure(nt) ||
         s->d_status.ensure(nt) || s->d_bad.ensure(kBadRows * ndim) || s->d_bad_count.ensure(1) ||
-        hipMemcpy(s->d_dsid.p, ds.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        upload_ds_rows(s->d_dsid.p, ens_ds_id, n_ensembles, n_walkers) ||
         hipMemset(s->d_acc.p, 0, nt * sizeof(int64_t)) != hipSuccess ||
         hipMemset(s->d_bad_count.p, 0, sizeof(uint32_t)) != hipSuccess ||
-        hipEventCreateWithFlags(&s->win_copied[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->win_copied[1], hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&s->win_copied[0].e, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&s->win_copied[1].e, hipEventDisableTiming) != hipSuccess) {
         fail(MP_EHIP, "mp_sampler_create: device allocation failed");
         mp_sampler_destroy(s);
         return nullptr;
@@ -1058,13 +1111,6 @@ int mp_sampler_destroy(mp_sampler *s) {
     Lock lock(s->h->mu);
     DeviceScope scope(s->h->device);
     (void)hipDeviceSynchronize();
-    s->d_pos.release(); s->d_lnprob.release(); s->d_chain.release(); s->d_chain_lnp.release();
-    s->d_acc.release(); s->d_perm.release(); s->d_dsid.release(); s->d_status.release(); s->h_perm.release();
-    s->d_bad.release(); s->d_bad_count.release(); s->d_beta.release(); s->d_swaps.release();
-    for (int b = 0; b < 2; ++b) {
-        s->d_win[b].release(); s->h_win[b].release();
-        if (s->win_copied[b]) (void)hipEventDestroy(s->win_copied[b]);
-    }
     delete s;
     return MP_OK;
 }
@@ -1282,12 +1328,12 @@ static int current_split(mp_sampler *s, hipStream_t st, const int32_t **d_perm) 
         int rc;
         const size_t bytes = (size_t)mp_sampler::kWin * nt * sizeof(int32_t);
         if ((rc = s->h_win[b].ensure(bytes)) || (rc = s->d_win[b].ensure((size_t)mp_sampler::kWin * nt))) return rc;
-        if (s->win_id[b] >= 0) HIP_TRY(hipEventSynchronize(s->win_copied[b]));   // staged two windows ago: long done
+        if (s->win_id[b] >= 0) HIP_TRY(hipEventSynchronize(s->win_copied[b].e));   // staged two windows ago: long done
         int32_t *perm = (int32_t *)s->h_win[b].p;
         draw_splits(s, (uint64_t)win * mp_sampler::kWin, mp_sampler::kWin, perm);
         // stream order puts the copy behind every kernel that still reads this buffer's previous contents
         HIP_TRY(hipMemcpyAsync(s->d_win[b].p, perm, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(s->win_copied[b], st));
+        HIP_TRY(hipEventRecord(s->win_copied[b].e, st));
         s->win_id[b] = win;
     }
     *d_perm = s->d_win[b].p + (size_t)(s->steps_done % mp_sampler::kWin) * nt;
@@ -1414,9 +1460,8 @@ int mp_sampler_get_state(mp_sampler *s, double *pos, double *lnprob, int64_t *n_
     DeviceScope scope(h->device);
     const size_t nt = (size_t)s->n_total;
     HIP_TRY(hipDeviceSynchronize());
-    if (pos) HIP_TRY(hipMemcpy(pos, s->d_pos.p, nt * s->ndim * sizeof(double), hipMemcpyDeviceToHost));
-    if (lnprob) HIP_TRY(hipMemcpy(lnprob, s->d_lnprob.p, nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (n_accepted) HIP_TRY(hipMemcpy(n_accepted, s->d_acc.p, nt * sizeof(int64_t), hipMemcpyDeviceToHost));
+    const int rc = read_back(pos, s->d_pos.p, nt * s->ndim, lnprob, s->d_lnprob.p, nt, n_accepted, s->d_acc.p, nt);
+    if (rc) return rc;
     if (steps_done) *steps_done = (int64_t)s->steps_done;
     return MP_OK;
 }
@@ -1454,30 +1499,19 @@ mp_optimizer *mp_optimizer_create(mp_handle *h, int popsize, int n_pops, int ndi
                                   int strategy, double f_lo, double f_hi, double cr, double tol, double atol,
                                   const double *lower, const double *upper, int target) {
     if (!h || !lower || !upper) { fail(MP_EINVAL, "mp_optimizer_create: NULL argument"); return nullptr; }
-    if (!h->sub.empty()) { fail(MP_ESTATE, "mp_optimizer_create: the optimizer lives on ONE device (a multi-device handle serves host-buffer batches only)"); return nullptr; }
-    if (popsize < 5 || popsize > 1024) { fail(MP_EINVAL, "mp_optimizer_create: popsize must be 5 .. 1024, got %d", popsize); return nullptr; }
-    if (n_pops < 1 || n_pops > MP_MAX_DATASETS) { fail(MP_EINVAL, "mp_optimizer_create: n_pops must be 1 .. %d", MP_MAX_DATASETS); return nullptr; }
-    if (target != 0 && target != 1) { fail(MP_EINVAL, "mp_optimizer_create: target must be 0 (posterior) or 1 (unit Gaussian)"); return nullptr; }
-    if (ndim < 1 || ndim > MP_MAX_NDIM || (target == 0 && ndim < 6)) { fail(MP_EINVAL, "mp_optimizer_create: bad ndim %d", ndim); return nullptr; }
-    if (strategy != MP_DE_BEST1BIN && strategy != MP_DE_RAND1BIN) { fail(MP_EINVAL, "mp_optimizer_create: unknown strategy %d", strategy); return nullptr; }
-    if (!(f_lo >= 0.0 && f_lo <= f_hi && f_hi < 2.0)) { fail(MP_EINVAL, "mp_optimizer_create: need 0 <= f_lo <= f_hi < 2"); return nullptr; }
-    if (!(cr >= 0.0 && cr <= 1.0)) { fail(MP_EINVAL, "mp_optimizer_create: cr must lie in [0, 1]"); return nullptr; }
-    if (!(std::isfinite(tol) && tol >= 0.0 && std::isfinite(atol) && atol >= 0.0)) { fail(MP_EINVAL, "mp_optimizer_create: tol and atol must be finite and >= 0"); return nullptr; }
-    for (int d = 0; d < ndim; ++d)
-        if (!(std::isfinite(lower[d]) && std::isfinite(upper[d]) && lower[d] < upper[d])) {
-            fail(MP_EINVAL, "mp_optimizer_create: bounds of coordinate %d are empty or not finite", d);
-            return nullptr;
-        }
-    if (target == 0 && h->sh.cfg.dipole_torque != 0) { fail(MP_ESTATE, "mp_optimizer_create: the alternative dipole torque (cfg.dipole_torque = 1) is served by the curve kernels only"); return nullptr; }
     Lock lock(h->mu);
-    if (target == 0)
-        for (int p = 0; p < n_pops; ++p) {
-            const int d = pop_ds_id ? pop_ds_id[p] : 0;
-            if (d < 0 || d >= MP_MAX_DATASETS || !h->ds[d].set) {
-                fail(MP_ESTATE, "mp_optimizer_create: population %d refers to unset dataset %d", p, d);
-                return nullptr;
-            }
-        }
+    const int rc = check_create(h, "mp_optimizer_create", "the optimizer lives on ONE device (a multi-device handle serves host-buffer batches only)",
+                                ndim, target, "population", n_pops, pop_ds_id, [&] {
+        if (popsize < 5 || popsize > 1024) return fail(MP_EINVAL, "mp_optimizer_create: popsize must be 5 .. 1024, got %d", popsize);
+        if (n_pops < 1 || n_pops > MP_MAX_DATASETS) return fail(MP_EINVAL, "mp_optimizer_create: n_pops must be 1 .. %d", MP_MAX_DATASETS);
+        if (target != 0 && target != 1) return fail(MP_EINVAL, "mp_optimizer_create: target must be 0 (posterior) or 1 (unit Gaussian)");
+        if (strategy != MP_DE_BEST1BIN && strategy != MP_DE_RAND1BIN) return fail(MP_EINVAL, "mp_optimizer_create: unknown strategy %d", strategy);
+        if (!(f_lo >= 0.0 && f_lo <= f_hi && f_hi < 2.0)) return fail(MP_EINVAL, "mp_optimizer_create: need 0 <= f_lo <= f_hi < 2");
+        if (!(cr >= 0.0 && cr <= 1.0)) return fail(MP_EINVAL, "mp_optimizer_create: cr must lie in [0, 1]");
+        if (!(std::isfinite(tol) && tol >= 0.0 && std::isfinite(atol) && atol >= 0.0)) return fail(MP_EINVAL, "mp_optimizer_create: tol and atol must be finite and >= 0");
+        return check_box("mp_optimizer_create", ndim, lower, upper);
+    });
+    if (rc) return nullptr;
     mp_optimizer *o = new mp_optimizer();
     o->h = h;
     o->n_total = popsize * n_pops;
@@ -1487,20 +1521,17 @@ mp_optimizer *mp_optimizer_create(mp_handle *h, int popsize, int n_pops, int ndi
     for (int d = 0; d < ndim; ++d) { a.lower[d] = lower[d]; a.upper[d] = upper[d]; }
     DeviceScope scope(h->device);
     const size_t nt = (size_t)o->n_total;
-    std::vector<int32_t> ds(nt);
-    for (int p = 0; p < n_pops; ++p) std::fill(ds.begin() + (size_t)p * popsize, ds.begin() + (size_t)(p + 1) * popsize, pop_ds_id ? pop_ds_id[p] : 0);
-    if (o->d_pop[0].ensure(nt * ndim) || o->d_pop[1].ensure(nt * ndim) || o->d_lnp[0].ensure(nt) || o->d_lnp[1].ensure(nt) ||
-        o->d_st[0].ensure(nt) || o->d_st[1].ensure(nt) || o->d_dsid.ensure(nt) || o->d_best.ensure(n_pops) ||
-        o->d_conv.ensure(n_pops) || o->d_nit.ensure(n_pops) || o->d_nfev.ensure(n_pops) ||
-        hipMemcpy(o->d_dsid.p, ds.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    Binder bind;
+    bind(o->d_pop[0], nt * ndim, a.pop_cur); bind(o->d_pop[1], nt * ndim, a.pop_next);
+    bind(o->d_lnp[0], nt, a.lnp_cur); bind(o->d_lnp[1], nt, a.lnp_next);
+    bind(o->d_st[0], nt, a.st_cur); bind(o->d_st[1], nt, a.st_next);
+    bind(o->d_dsid, nt, a.ds_id);
+    bind(o->d_best, n_pops, a.best); bind(o->d_conv, n_pops, a.converged); bind(o->d_nit, n_pops, a.nit); bind(o->d_nfev, n_pops, a.nfev);
+    if (bind.rc || upload_ds_rows(o->d_dsid.p, pop_ds_id, n_pops, popsize)) {
         fail(MP_EHIP, "mp_optimizer_create: device allocation failed");
         mp_optimizer_destroy(o);
         return nullptr;
     }
-    a.pop_cur = o->d_pop[0].p; a.pop_next = o->d_pop[1].p;
-    a.lnp_cur = o->d_lnp[0].p; a.lnp_next = o->d_lnp[1].p;
-    a.st_cur = o->d_st[0].p; a.st_next = o->d_st[1].p;
-    a.ds_id = o->d_dsid.p; a.best = o->d_best.p; a.converged = o->d_conv.p; a.nit = o->d_nit.p; a.nfev = o->d_nfev.p;
     return o;
 }
 
@@ -1509,8 +1540,6 @@ int mp_optimizer_destroy(mp_optimizer *o) {
     Lock lock(o->h->mu);
     DeviceScope scope(o->h->device);
     (void)hipStreamSynchronize(o->h->stream);
-    for (int b = 0; b < 2; ++b) { o->d_pop[b].release(); o->d_lnp[b].release(); o->d_st[b].release(); }
-    o->d_dsid.release(); o->d_best.release(); o->d_conv.release(); o->d_nit.release(); o->d_nfev.release();
     delete o;
     return MP_OK;
 }
@@ -1545,21 +1574,15 @@ int mp_optimizer_run(mp_optimizer *o, int max_generations, int *n_running) {
     // chunk, and the run ends early once every population has converged.  A frozen population costs an empty workgroup per
     // member and launch.
     constexpr int kChunk = 16;
-    const int n_pops = o->a.n_pops;
-    std::vector<int32_t> conv((size_t)n_pops);
-    int running = n_pops;
-    HIP_TRY(hipMemcpy(conv.data(), o->a.converged, (size_t)n_pops * sizeof(int32_t), hipMemcpyDeviceToHost));
-    running = n_pops - (int)std::count(conv.begin(), conv.end(), 1);
+    int running, rc;
+    if ((rc = groups_running(h, o->a.converged, o->a.n_pops, &running))) return rc;
     for (int done = 0; done < max_generations && running > 0;) {
         const int chunk = std::min(kChunk, max_generations - done);
         for (int g = 0; g < chunk; ++g) {
             ++o->gen;
-            const int rc = opt_enqueue(o, 1);
-            if (rc) return rc;
+            if ((rc = opt_enqueue(o, 1))) return rc;
         }
-        HIP_TRY(hipMemcpyAsync(conv.data(), o->a.converged, (size_t)n_pops * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        running = n_pops - (int)std::count(conv.begin(), conv.end(), 1);
+        if ((rc = groups_running(h, o->a.converged, o->a.n_pops, &running))) return rc;
         done += chunk;
     }
     if (n_running) *n_running = running;
@@ -1575,14 +1598,9 @@ int mp_optimizer_get_state(mp_optimizer *o, double *pop, double *lnprob, int32_t
     DeviceScope scope(h->device);
     const size_t nt = (size_t)o->n_total, np = (size_t)o->a.n_pops;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (pop) HIP_TRY(hipMemcpy(pop, o->a.pop_cur, nt * o->a.ndim * sizeof(double), hipMemcpyDeviceToHost));
-    if (lnprob) HIP_TRY(hipMemcpy(lnprob, o->a.lnp_cur, nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (status) HIP_TRY(hipMemcpy(status, o->a.st_cur, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (best) HIP_TRY(hipMemcpy(best, o->a.best, np * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (nit) HIP_TRY(hipMemcpy(nit, o->a.nit, np * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (converged) HIP_TRY(hipMemcpy(converged, o->a.converged, np * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (nfev) HIP_TRY(hipMemcpy(nfev, o->a.nfev, np * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return MP_OK;
+    const mp::OptArgs &a = o->a;
+    return read_back(pop, a.pop_cur, nt * a.ndim, lnprob, a.lnp_cur, nt, status, a.st_cur, nt,
+                     best, a.best, np, nit, a.nit, np, converged, a.converged, np, nfev, a.nfev, np);
 }
 
 // ---------------------------------------------------------------- nested sampler (mp_nest.hip)
@@ -1603,31 +1621,20 @@ struct mp_nested {
 mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int ndim, const int32_t *run_ds_id, uint64_t seed,
                             int walks, double g0, double sigma, double dlogz, const double *lower, const double *upper, int target) {
     if (!h || !lower || !upper) { fail(MP_EINVAL, "mp_nested_create: NULL argument"); return nullptr; }
-    if (!h->sub.empty()) { fail(MP_ESTATE, "mp_nested_create: the nested sampler lives on ONE device (a multi-device handle serves host-buffer batches only)"); return nullptr; }
-    if (nlive < MP_NEST_MIN_LIVE || nlive > MP_NEST_MAX_LIVE) { fail(MP_EINVAL, "mp_nested_create: nlive must be %d .. %d, got %d", MP_NEST_MIN_LIVE, MP_NEST_MAX_LIVE, nlive); return nullptr; }
-    if (nbatch < 1 || nbatch > nlive / 2) { fail(MP_EINVAL, "mp_nested_create: nbatch must be 1 .. nlive / 2, got %d", nbatch); return nullptr; }
-    if (n_runs < 1 || n_runs > MP_MAX_DATASETS) { fail(MP_EINVAL, "mp_nested_create: n_runs must be 1 .. %d", MP_MAX_DATASETS); return nullptr; }
-    if (target != 0 && target != 1) { fail(MP_EINVAL, "mp_nested_create: target must be 0 (posterior) or 1 (unit Gaussian)"); return nullptr; }
-    if (ndim < 1 || ndim > MP_MAX_NDIM || (target == 0 && ndim < 6)) { fail(MP_EINVAL, "mp_nested_create: bad ndim %d", ndim); return nullptr; }
-    if (walks < 1 || walks > MP_NEST_MAX_WALKS) { fail(MP_EINVAL, "mp_nested_create: walks must be 1 .. %d", MP_NEST_MAX_WALKS); return nullptr; }
-    if (!std::isfinite(g0)) { fail(MP_EINVAL, "mp_nested_create: g0 must be finite (<= 0: the default)"); return nullptr; }
-    if (!(sigma >= 0.0 && sigma < 1.0 / std::sqrt(3.0))) { fail(MP_EINVAL, "mp_nested_create: sigma must lie in [0, 1/sqrt(3))"); return nullptr; }
-    if (!(std::isfinite(dlogz) && dlogz > 0.0)) { fail(MP_EINVAL, "mp_nested_create: dlogz must be finite and > 0"); return nullptr; }
-    for (int d = 0; d < ndim; ++d)
-        if (!(std::isfinite(lower[d]) && std::isfinite(upper[d]) && lower[d] < upper[d])) {
-            fail(MP_EINVAL, "mp_nested_create: bounds of coordinate %d are empty or not finite", d);
-            return nullptr;
-        }
-    if (target == 0 && h->sh.cfg.dipole_torque != 0) { fail(MP_ESTATE, "mp_nested_create: the alternative dipole torque (cfg.dipole_torque = 1) is served by the curve kernels only"); return nullptr; }
     Lock lock(h->mu);
-    if (target == 0)
-        for (int r = 0; r < n_runs; ++r) {
-            const int d = run_ds_id ? run_ds_id[r] : 0;
-            if (d < 0 || d >= MP_MAX_DATASETS || !h->ds[d].set) {
-                fail(MP_ESTATE, "mp_nested_create: run %d refers to unset dataset %d", r, d);
-                return nullptr;
-            }
-        }
+    const int rc = check_create(h, "mp_nested_create", "the nested sampler lives on ONE device (a multi-device handle serves host-buffer batches only)",
+                                ndim, target, "run", n_runs, run_ds_id, [&] {
+        if (nlive < MP_NEST_MIN_LIVE || nlive > MP_NEST_MAX_LIVE) return fail(MP_EINVAL, "mp_nested_create: nlive must be %d .. %d, got %d", MP_NEST_MIN_LIVE, MP_NEST_MAX_LIVE, nlive);
+        if (nbatch < 1 || nbatch > nlive / 2) return fail(MP_EINVAL, "mp_nested_create: nbatch must be 1 .. nlive / 2, got %d", nbatch);
+        if (n_runs < 1 || n_runs > MP_MAX_DATASETS) return fail(MP_EINVAL, "mp_nested_create: n_runs must be 1 .. %d", MP_MAX_DATASETS);
+        if (target != 0 && target != 1) return fail(MP_EINVAL, "mp_nested_create: target must be 0 (posterior) or 1 (unit Gaussian)");
+        if (walks < 1 || walks > MP_NEST_MAX_WALKS) return fail(MP_EINVAL, "mp_nested_create: walks must be 1 .. %d", MP_NEST_MAX_WALKS);
+        if (!std::isfinite(g0)) return fail(MP_EINVAL, "mp_nested_create: g0 must be finite (<= 0: the default)");
+        if (!(sigma >= 0.0 && sigma < 1.0 / std::sqrt(3.0))) return fail(MP_EINVAL, "mp_nested_create: sigma must lie in [0, 1/sqrt(3))");
+        if (!(std::isfinite(dlogz) && dlogz > 0.0)) return fail(MP_EINVAL, "mp_nested_create: dlogz must be finite and > 0");
+        return check_box("mp_nested_create", ndim, lower, upper);
+    });
+    if (rc) return nullptr;
     mp_nested *ns = new mp_nested();
     ns->h = h;
     ns->n_total = nlive * n_runs;
@@ -1643,21 +1650,17 @@ mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int
     ns->dead_pars.resize(n_runs); ns->dead_lnl.resize(n_runs); ns->dead_n.resize(n_runs);
     DeviceScope scope(h->device);
     const size_t nt = (size_t)ns->n_total, nr = (size_t)n_runs, nk = nr * nbatch, nc = (size_t)ns->chunk * nk;
-    std::vector<int32_t> ds(nr);
-    for (int r = 0; r < n_runs; ++r) ds[r] = run_ds_id ? run_ds_id[r] : 0;
-    if (ns->d_live.ensure(nt * ndim) || ns->d_lnl.ensure(nt) || ns->d_st.ensure(nt) || ns->d_acc.ensure(nt) || ns->d_dsid.ensure(nr) ||
-        ns->d_dslot.ensure(nk) || ns->d_surv.ensure(nr * (nlive - nbatch)) || ns->d_lstar.ensure(nr) || ns->d_dpars.ensure(nc * ndim) ||
-        ns->d_dlnl.ensure(nc) || ns->d_dn.ensure(nc) || ns->d_lnx.ensure(nr) || ns->d_lnz.ensure(nr) || ns->d_stop.ensure(nr) ||
-        ns->d_nit.ensure(nr) || ns->d_ncall.ensure(nr) || ns->d_nacc.ensure(nr) || ns->d_nzero.ensure(nr) ||
-        hipMemcpy(ns->d_dsid.p, ds.data(), nr * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    Binder bind;
+    bind(ns->d_live, nt * ndim, a.live); bind(ns->d_lnl, nt, a.lnl); bind(ns->d_st, nt, a.st); bind(ns->d_acc, nt, a.acc);
+    bind(ns->d_dsid, nr, a.ds_id); bind(ns->d_dslot, nk, a.dead_slot); bind(ns->d_surv, nr * (nlive - nbatch), a.surv);
+    bind(ns->d_lstar, nr, a.lstar); bind(ns->d_dpars, nc * ndim, a.dead_pars); bind(ns->d_dlnl, nc, a.dead_lnl); bind(ns->d_dn, nc, a.dead_n);
+    bind(ns->d_lnx, nr, a.lnx); bind(ns->d_lnz, nr, a.lnz); bind(ns->d_stop, nr, a.stopped); bind(ns->d_nit, nr, a.nit);
+    bind(ns->d_ncall, nr, a.ncall); bind(ns->d_nacc, nr, a.nacc); bind(ns->d_nzero, nr, a.nzero);
+    if (bind.rc || upload_ds_rows(ns->d_dsid.p, run_ds_id, n_runs, 1)) {
         fail(MP_EHIP, "mp_nested_create: device allocation failed");
         mp_nested_destroy(ns);
         return nullptr;
     }
-    a.live = ns->d_live.p; a.lnl = ns->d_lnl.p; a.st = ns->d_st.p; a.acc = ns->d_acc.p; a.ds_id = ns->d_dsid.p;
-    a.dead_slot = ns->d_dslot.p; a.surv = ns->d_surv.p; a.lstar = ns->d_lstar.p; a.dead_pars = ns->d_dpars.p;
-    a.dead_lnl = ns->d_dlnl.p; a.dead_n = ns->d_dn.p; a.lnx = ns->d_lnx.p; a.lnz = ns->d_lnz.p; a.stopped = ns->d_stop.p;
-    a.nit = ns->d_nit.p; a.ncall = ns->d_ncall.p; a.nacc = ns->d_nacc.p; a.nzero = ns->d_nzero.p;
     return ns;
 }
 
@@ -1666,10 +1669,6 @@ int mp_nested_destroy(mp_nested *ns) {
     Lock lock(ns->h->mu);
     DeviceScope scope(ns->h->device);
     (void)hipStreamSynchronize(ns->h->stream);
-    ns->d_live.release(); ns->d_lnl.release(); ns->d_lstar.release(); ns->d_dpars.release(); ns->d_dlnl.release();
-    ns->d_lnx.release(); ns->d_lnz.release(); ns->d_st.release(); ns->d_acc.release(); ns->d_dsid.release(); ns->d_dslot.release();
-    ns->d_surv.release(); ns->d_dn.release(); ns->d_stop.release(); ns->d_nit.release(); ns->d_ncall.release(); ns->d_nacc.release();
-    ns->d_nzero.release();
     delete ns;
     return MP_OK;
 }
@@ -1717,11 +1716,11 @@ int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running) {
     // the live set as it stands and one read-back of the counters and the dead rows; the run ends early once every run stopped.
     const int nr = a.n_runs, K = a.nbatch, nd = a.ndim;
     const size_t per = (size_t)nr * K;
-    std::vector<int32_t> stop((size_t)nr), nit0((size_t)nr), nit1((size_t)nr);
+    std::vector<int32_t> nit0((size_t)nr), nit1((size_t)nr);
     std::vector<double> hp, hl;
     std::vector<int32_t> hn;
-    HIP_TRY(hipMemcpy(stop.data(), a.stopped, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
-    int running = nr - (int)std::count(stop.begin(), stop.end(), 1);
+    int running, rc;
+    if ((rc = groups_running(h, a.stopped, nr, &running))) return rc;
     for (int done = 0; done < max_iterations && running > 0;) {
         const int chunk = std::min(ns->chunk, max_iterations - done);
         HIP_TRY(hipMemcpyAsync(nit0.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -1743,8 +1742,7 @@ int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running) {
         HIP_TRY(hipMemcpyAsync(hl.data(), a.dead_lnl, hl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(hn.data(), a.dead_n, hn.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(nit1.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(stop.data(), a.stopped, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        if ((rc = groups_running(h, a.stopped, nr, &running))) return rc;   // (behind the copies above: they have landed)
         // run r ran the first nit1 - nit0 iterations of the chunk (a stopped run stays stopped)
         for (int r = 0; r < nr; ++r)
             for (int c = 0; c < nit1[r] - nit0[r]; ++c) {
@@ -1753,7 +1751,6 @@ int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running) {
                 ns->dead_lnl[r].insert(ns->dead_lnl[r].end(), hl.begin() + o, hl.begin() + o + K);
                 ns->dead_n[r].insert(ns->dead_n[r].end(), hn.begin() + o, hn.begin() + o + K);
             }
-        running = nr - (int)std::count(stop.begin(), stop.end(), 1);
         done += chunk;
     }
     if (n_running) *n_running = running;
@@ -1782,18 +1779,8 @@ int mp_nested_get_state(mp_nested *ns, double *live, double *lnl, int32_t *statu
     DeviceScope scope(h->device);
     const size_t nt = (size_t)ns->n_total, nr = (size_t)a.n_runs;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (live) HIP_TRY(hipMemcpy(live, a.live, nt * a.ndim * sizeof(double), hipMemcpyDeviceToHost));
-    if (lnl) HIP_TRY(hipMemcpy(lnl, a.lnl, nt * sizeof(double), hipMemcpyDeviceToHost));
-    if (status) HIP_TRY(hipMemcpy(status, a.st, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (acc) HIP_TRY(hipMemcpy(acc, a.acc, nt * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (nit) HIP_TRY(hipMemcpy(nit, a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (stopped) HIP_TRY(hipMemcpy(stopped, a.stopped, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (lnx) HIP_TRY(hipMemcpy(lnx, a.lnx, nr * sizeof(double), hipMemcpyDeviceToHost));
-    if (lnz) HIP_TRY(hipMemcpy(lnz, a.lnz, nr * sizeof(double), hipMemcpyDeviceToHost));
-    if (ncall) HIP_TRY(hipMemcpy(ncall, a.ncall, nr * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (nacc) HIP_TRY(hipMemcpy(nacc, a.nacc, nr * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (nzero) HIP_TRY(hipMemcpy(nzero, a.nzero, nr * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return MP_OK;
+    return read_back(live, a.live, nt * a.ndim, lnl, a.lnl, nt, status, a.st, nt, acc, a.acc, nt, nit, a.nit, nr,
+                     stopped, a.stopped, nr, lnx, a.lnx, nr, lnz, a.lnz, nr, ncall, a.ncall, nr, nacc, a.nacc, nr, nzero, a.nzero, nr);
 }
 
 int mp_device(const mp_handle *h) { return h ? h->device : -1; }

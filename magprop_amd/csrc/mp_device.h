@@ -2,6 +2,8 @@
 #pragma once
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/magprop_amd.h"
 
 #if defined(__HIP__) || defined(__HIPCC__)
@@ -269,6 +271,36 @@ inline int stretch_waves(const DevShared &sh, int whole_step_blocks) {
 // step / two half-steps: 1 364 walkers 0.140 / 0.191, 1 536 walkers 0.173 / 0.193, 1 700 walkers 0.201 / 0.193, 2 048 walkers
 // 0.216 / 0.195; until round 5 the limit was 2 x n_simd).
 inline bool stretch_whole_step_fits(const DevShared &sh, long long whole_step_blocks) { return 8 * whole_step_blocks <= 19 * (long long)sh.n_simd; }
+
+// The build of a mode-A launch of n walker workgroups (launch_lnprob, the optimizer's trials, the nested sampler's walks, the
+// stretch launches), given whether it is a team launch (kernel_waves(sh, n) == 4; stretch launches: stretch_waves of the whole
+// step).  A team of 4 wavefronts per walker runs OCC = 1 wavefront per SIMD while every wavefront of the launch has a SIMD of its
+// own, else 2; one wavefront per walker runs SPL = 4 steps per lane up to one wavefront per SIMD, else 2 (kernel_spl, or
+// force_spl).  roomy: OCC = 1 for a team, else SPL = 4.
+struct Variant {
+    bool team, roomy;
+};
+inline Variant walker_variant(const DevShared &sh, int n, bool team) {
+    if (team) return {true, 4 * n <= sh.n_simd};
+    return {false, (sh.force_spl ? sh.force_spl : kernel_spl(sh, n)) == 4};
+}
+// the variant as the kernels' template arguments: SPL steps per lane, W wavefronts per walker, OCC wavefronts per SIMD of a team
+template <bool TEAM, bool ROOMY>
+struct Build {
+    static constexpr int SPL = TEAM ? 1 : (ROOMY ? 4 : 2), W = TEAM ? 4 : 1, OCC = TEAM ? (ROOMY ? 1 : 2) : 0;
+};
+
+// Run-time flags to compile-time ones: dispatch(f, b0, b1, ...) calls f(std::integral_constant<bool, b0>(), ...), so that a
+// launcher states its choice of kernel build once, as one template expression.  Every combination of the flags is instantiated.
+template <class F>
+void dispatch(F &&f) {
+    f();
+}
+template <class F, class... B>
+void dispatch(F &&f, bool b, B... rest) {
+    if (b) dispatch([&](auto... c) { f(std::true_type(), c...); }, rest...);
+    else dispatch([&](auto... c) { f(std::false_type(), c...); }, rest...);
+}
 
 // Arguments of the batched right-hand-side evaluation (mp_kernels.hip: rhs_kernel), device pointers.
 struct RhsArgs {

@@ -1,7 +1,7 @@
 // mp_eval.hpp — evaluation of ONE walker's log-posterior on a wavefront (walker_eval): physics of the reference's RHS /
 // luminosity stage in simplified algebra and the time-parallel exponential Adams-Moulton solver with tile-level stride
-// adaptivity (serial restatement: oracle/mp_oracle.c mpo_trajectory_mode).  Included by
-// mp_kernels.hip only.
+// adaptivity (serial restatement: oracle/mp_oracle.c mpo_trajectory_mode).  Included by the kernel
+// files (mp_kernels.hip, mp_opt.hip, mp_nest.hip).
 #pragma once
 #include "mp_math.hpp"
 

@@ -37,8 +37,6 @@
 // formulas and the tests compare the two.
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "mp_eval.hpp"
 
 namespace mp {
@@ -586,18 +584,6 @@ int launch_rhs(const DevShared &sh, const RhsArgs &r, void *stream) {
     return (int)hipGetLastError();
 }
 
-// Run-time flags to compile-time ones: dispatch(f, b0, b1, ...) calls f(std::integral_constant<bool, b0>(), ...), so that a
-// launcher states its choice of kernel build once, as one template expression.  Every combination of the flags is instantiated.
-template <class F>
-static void dispatch(F &&f) {
-    f();
-}
-template <class F, class... B>
-static void dispatch(F &&f, bool b, B... rest) {
-    if (b) dispatch([&](auto... c) { f(std::true_type(), c...); }, rest...);
-    else dispatch([&](auto... c) { f(std::false_type(), c...); }, rest...);
-}
-
 int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
     if (a.n <= 0) return 0;
     // (the alternative dipole torque, cfg.dipole_torque = 1, lives in the curve kernels only: such a handle runs them for
@@ -611,7 +597,6 @@ int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
     //  - a handle that holds a light curve of more than 64 points runs the LONG builds of the same kernels.
     //  - curve outputs (mode B): by rounds of resident workgroups, kernel_spl_curves (mp_device.h);
     //  - diagnostics requested (a.tile_log): the LOG builds, which record the tile words.
-    const bool wide = (sh.force_spl ? sh.force_spl : (curves ? kernel_spl_curves(sh, a.n) : kernel_spl(sh, a.n))) == 4;
     const bool lng = sh.has_long != 0, log = a.tile_log != nullptr || kAlwaysLog;
     hipStream_t st = (hipStream_t)stream;
     //  - launches that would leave SIMDs idle (n <= n_simd / 2): a team of four wavefronts per walker, one step per lane each
@@ -619,49 +604,35 @@ int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
     //    wavefront has a SIMD of its own; up to n_simd / 2 two share one and fill each other's stalls.  Measured on one box
     //    (profiles/r05_team_*.log): 256 walkers 0.0755 -> 0.0577 ms, 512 walkers 0.0767 -> 0.0699 ms near the truth
     //    (0.197 -> 0.165 ms prior-wide); a team of two (2 steps per lane) at 512 walkers 0.0701 / 0.197 ms.
-    const int team = (curves || !a.want_chi2 || a.physical) ? 1 : kernel_waves(sh, a.n);
-    if (team == 4) {
-        dispatch([&](auto occ1, auto log_, auto lng_) {
-            hipLaunchKernelGGL((lnprob_team_kernel<1, 4, occ1 ? 1 : 2, log_, lng_>), grid, dim3(256), 0, st, sh, a);
-        }, 4 * a.n <= sh.n_simd, log, lng);
-    } else if (team > 1) {
+    const int waves = (curves || !a.want_chi2 || a.physical) ? 1 : kernel_waves(sh, a.n);
+    if (curves) {
+        const bool wide = (sh.force_spl ? sh.force_spl : kernel_spl_curves(sh, a.n)) == 4;
+        dispatch([&](auto wide_) { hipLaunchKernelGGL((lnprob_kernel<true, wide_ ? 4 : 2, false>), grid, block, 0, st, sh, a); }, wide);
 #ifdef MP_EXPERIMENTS
+    } else if (waves == 2) {   // (force_waves = 2: the two-wavefront team)
         dispatch([&](auto occ1, auto log_) {
             hipLaunchKernelGGL((lnprob_team_kernel<2, 2, occ1 ? 1 : 2, log_>), grid, dim3(128), 0, st, sh, a);
         }, 2 * a.n <= sh.n_simd, log);
 #endif
-    } else if (curves) {
-        dispatch([&](auto wide_) { hipLaunchKernelGGL((lnprob_kernel<true, wide_ ? 4 : 2, false>), grid, block, 0, st, sh, a); }, wide);
-    } else {
-        dispatch([&](auto wide_, auto lng_, auto log_) {
-            hipLaunchKernelGGL((lnprob_kernel<false, wide_ ? 4 : 2, lng_, log_>), grid, block, 0, st, sh, a);
-        }, wide, lng, log);
+    } else {   // mode A: the rule of every walker launch (walker_variant, mp_device.h)
+        const Variant v = walker_variant(sh, a.n, waves == 4);
+        dispatch([&](auto team, auto roomy, auto log_, auto lng_) {
+            using B = Build<team, roomy>;
+            if constexpr (team) hipLaunchKernelGGL((lnprob_team_kernel<B::SPL, B::W, B::OCC, log_, lng_>), grid, dim3(64 * B::W), 0, st, sh, a);
+            else hipLaunchKernelGGL((lnprob_kernel<false, B::SPL, lng_, log_>), grid, block, 0, st, sh, a);
+        }, v.team, v.roomy, log, lng);
     }
     return (int)hipGetLastError();
 }
 
-// The build of a stretch launch of n_blocks blocks, one rule for stretch_kernel and stretch_step_kernel.  Small samplers, by the
-// size of a WHOLE step (stretch_waves), evaluate every proposal on a team of W = 4 wavefronts, OCC = 1 wavefront per SIMD while
-// every wavefront of the launch has a SIMD of its own, else 2.  Larger ones run one wavefront per proposal (W = 1, OCC = 0) with
-// SPL = 4 steps per lane up to one wavefront per SIMD, else 2 (kernel_spl, or force_spl).  roomy: OCC = 1 for a team, else SPL = 4.
-struct StretchVariant {
-    bool team, roomy;
-};
-static StretchVariant stretch_variant(const DevShared &sh, const StretchArgs &g, int n_blocks) {
-    if (stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4) return {true, 4 * n_blocks <= sh.n_simd};
-    return {false, (sh.force_spl ? sh.force_spl : kernel_spl(sh, n_blocks)) == 4};
-}
-template <bool TEAM, bool ROOMY>   // the variant as template arguments
-struct StretchBuild {
-    static constexpr int SPL = TEAM ? 1 : (ROOMY ? 4 : 2), W = TEAM ? 4 : 1, OCC = TEAM ? (ROOMY ? 1 : 2) : 0;
-};
-
+// The build of a stretch launch of n_blocks blocks, one rule for stretch_kernel and stretch_step_kernel (walker_variant): small
+// samplers, by the size of a WHOLE step (stretch_waves), evaluate every proposal on a team of four wavefronts.
 // n_blocks slots of the active half starting at g.slot_lo; the DIFF builds (DE / snooker) are chosen by the same rule
 int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
     if (n_blocks <= 0) return 0;
-    const StretchVariant v = stretch_variant(sh, g, n_blocks);
+    const Variant v = walker_variant(sh, n_blocks, stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4);
     dispatch([&](auto team, auto roomy, auto lng, auto tempered, auto diff) {
-        using B = StretchBuild<team, roomy>;
+        using B = Build<team, roomy>;
         hipLaunchKernelGGL((stretch_kernel<B::SPL, lng, B::W, B::OCC, tempered, diff>), dim3((unsigned)n_blocks), dim3(64 * B::W), 0,
                            (hipStream_t)stream, sh, g);
     }, v.team, v.roomy, sh.has_long != 0, g.beta != nullptr, g.move != MP_MOVE_STRETCH);
@@ -670,9 +641,9 @@ int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void
 
 int launch_stretch_step(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
     if (n_blocks <= 0) return 0;
-    const StretchVariant v = stretch_variant(sh, g, n_blocks);
+    const Variant v = walker_variant(sh, n_blocks, stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4);
     dispatch([&](auto team, auto roomy, auto lng) {
-        using B = StretchBuild<team, roomy>;
+        using B = Build<team, roomy>;
         hipLaunchKernelGGL((stretch_step_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n_blocks), dim3(64 * B::W), 0,
                            (hipStream_t)stream, sh, g);
     }, v.team, v.roomy, sh.has_long != 0);

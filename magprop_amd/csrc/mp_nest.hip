@@ -129,12 +129,6 @@ void nest_walk_kernel(const DevShared sh, const NestArgs a) {
     }
 }
 
-template <bool TEAM, bool ROOMY, bool LONG>   // ROOMY: OCC = 1 for a team, else SPL = 4 (as in launch_lnprob)
-void nest_walk_launch(const DevShared &sh, const NestArgs &a, int n, hipStream_t st) {
-    constexpr int SPL = TEAM ? 1 : (ROOMY ? 4 : 2), W = TEAM ? 4 : 1, OCC = TEAM ? (ROOMY ? 1 : 2) : 0;
-    hipLaunchKernelGGL((nest_walk_kernel<SPL, LONG, W, OCC>), dim3((unsigned)n), dim3(64 * W), 0, st, sh, a);
-}
-
 constexpr int kSelThreads = 1024;
 
 // Ranks, the stop rule and the bookkeeping of one iteration of run blockIdx.x (include/magprop_amd.h states the arithmetic).
@@ -210,22 +204,16 @@ __global__ __launch_bounds__(kSelThreads) void nest_select_kernel(const NestArgs
 
 }  // namespace
 
-// The build of launch_lnprob for a batch of n = n_runs * nbatch walkers (mode 1: n_runs * nlive): a team of four wavefronts per
-// walk where kernel_waves says so (OCC 1 while 4 n <= n_simd, else 2), else one wavefront with kernel_spl's steps per lane;
-// LONG builds for handles with light curves of more than 64 points.
+// The build of launch_lnprob for a batch of n = n_runs * nbatch walkers (mode 1: n_runs * nlive): walker_variant with a team where
+// kernel_waves says so; LONG builds for handles with light curves of more than 64 points.
 int launch_nest_walk(const DevShared &sh, const NestArgs &a, void *stream) {
     const int n = a.n_runs * (a.mode ? a.nlive : a.nbatch);
     if (n <= 0) return 0;
-    const bool team = kernel_waves(sh, n) == 4, lng = sh.has_long != 0;
-    const bool roomy = team ? 4 * n <= sh.n_simd : (sh.force_spl ? sh.force_spl : kernel_spl(sh, n)) == 4;
-    const hipStream_t st = (hipStream_t)stream;
-    if (team) {
-        if (roomy) lng ? nest_walk_launch<true, true, true>(sh, a, n, st) : nest_walk_launch<true, true, false>(sh, a, n, st);
-        else lng ? nest_walk_launch<true, false, true>(sh, a, n, st) : nest_walk_launch<true, false, false>(sh, a, n, st);
-    } else {
-        if (roomy) lng ? nest_walk_launch<false, true, true>(sh, a, n, st) : nest_walk_launch<false, true, false>(sh, a, n, st);
-        else lng ? nest_walk_launch<false, false, true>(sh, a, n, st) : nest_walk_launch<false, false, false>(sh, a, n, st);
-    }
+    const Variant v = walker_variant(sh, n, kernel_waves(sh, n) == 4);
+    dispatch([&](auto team, auto roomy, auto lng) {
+        using B = Build<team, roomy>;
+        hipLaunchKernelGGL((nest_walk_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n), dim3(64 * B::W), 0, (hipStream_t)stream, sh, a);
+    }, v.team, v.roomy, sh.has_long != 0);
     return (int)hipGetLastError();
 }
 

@@ -136,31 +136,19 @@ __global__ __launch_bounds__(64) void opt_reduce_kernel(const OptArgs o) {
     }
 }
 
-template <bool TEAM, bool ROOMY, bool LONG>   // ROOMY: OCC = 1 for a team, else SPL = 4 (as in launch_lnprob)
-void opt_trial_launch(const DevShared &sh, const OptArgs &o, int n, hipStream_t st) {
-    constexpr int SPL = TEAM ? 1 : (ROOMY ? 4 : 2), W = TEAM ? 4 : 1, OCC = TEAM ? (ROOMY ? 1 : 2) : 0;
-    hipLaunchKernelGGL((opt_trial_kernel<SPL, LONG, W, OCC>), dim3((unsigned)n), dim3(64 * W), 0, st, sh, o);
-}
-
 }  // namespace
 
 // The build of launch_lnprob for a batch of n = n_pops * popsize walkers (fixed for the whole run, converged populations or not):
-// a team of four wavefronts per member where kernel_waves says so (OCC 1 while 4 n <= n_simd, else 2), else one wavefront with
-// kernel_spl's steps per lane; LONG builds for handles with light curves of more than 64 points.  (The experiments build's
-// two-wavefront team, force_waves = 2, has no optimizer build: one wavefront there.)
+// walker_variant with a team where kernel_waves says so; LONG builds for handles with light curves of more than 64 points.  (The
+// experiments build's two-wavefront team, force_waves = 2, has no optimizer build: one wavefront there.)
 int launch_opt_trial(const DevShared &sh, const OptArgs &o, void *stream) {
     const int n = o.popsize * o.n_pops;
     if (n <= 0) return 0;
-    const bool team = kernel_waves(sh, n) == 4, lng = sh.has_long != 0;
-    const bool roomy = team ? 4 * n <= sh.n_simd : (sh.force_spl ? sh.force_spl : kernel_spl(sh, n)) == 4;
-    const hipStream_t st = (hipStream_t)stream;
-    if (team) {
-        if (roomy) lng ? opt_trial_launch<true, true, true>(sh, o, n, st) : opt_trial_launch<true, true, false>(sh, o, n, st);
-        else lng ? opt_trial_launch<true, false, true>(sh, o, n, st) : opt_trial_launch<true, false, false>(sh, o, n, st);
-    } else {
-        if (roomy) lng ? opt_trial_launch<false, true, true>(sh, o, n, st) : opt_trial_launch<false, true, false>(sh, o, n, st);
-        else lng ? opt_trial_launch<false, false, true>(sh, o, n, st) : opt_trial_launch<false, false, false>(sh, o, n, st);
-    }
+    const Variant v = walker_variant(sh, n, kernel_waves(sh, n) == 4);
+    dispatch([&](auto team, auto roomy, auto lng) {
+        using B = Build<team, roomy>;
+        hipLaunchKernelGGL((opt_trial_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n), dim3(64 * B::W), 0, (hipStream_t)stream, sh, o);
+    }, v.team, v.roomy, sh.has_long != 0);
     return (int)hipGetLastError();
 }
 
