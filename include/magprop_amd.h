@@ -315,20 +315,34 @@ int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted);
  *                    (r2, r3), (r2_0, r2_1), all three distinct.  d = x_k - z, dd = sum d_i^2, p = sum d_i (z1_i - z2_i) (index
  *                    order), q = x_k + (gamma_s (p / dd)) d, Hastings term h = (ndim - 1)/2 (ln sum (q - z)_i^2 - ln dd) (dd = 0:
  *                    NaN, rejected).  emcee splits the walkers four ways for this move; here the split is two-way.
+ *   MP_MOVE_KDE      (emcee's KDEMove) params[0] = bandwidth: 0 Scott, f = n_comp^(-1/(ndim+4)); -1 Silverman, f = (n_comp
+ *                    (ndim + 2)/4)^(-1/(ndim+4)); > 0 (finite) the factor f itself; params[1] = 0.  Over the slots C of the other
+ *                    half: mu = their mean, S = their sample covariance (ddof 1), Sigma = f^2 S = L L^T (Cholesky).  Partner c =
+ *                    pick(u01(r0, r1), n_comp) from r = Philox(...; c3 = 0x4B00); n_i standard normals by Box-Muller, pair p from
+ *                    Philox(...; c3 = 0x4B01 + p): n_2p, n_2p+1 = sqrt(-2 ln(1 - u01(s0, s1))) cos, sin (2 pi u01(s2, s3)).
+ *                    q = x_c + L n.  Hastings term h = lse_j(-|L^-1 (x_k - x_j)|^2 / 2) - lse_j(-|L^-1 (q - x_j)|^2 / 2), j over
+ *                    C, lse = log-sum-exp with the maximum subtracted first (the kernel's normalising constants cancel).  ln u =
+ *                    ln u01(r2, r3).  Where S is not positive definite (a pivot of the factorisation not finite and > 0), every
+ *                    proposal of that ensemble in that half-step is NaN, is rejected and is never stored.  Sums and the
+ *                    log-sum-exp run in a fixed order of their own (workgroup reductions), so a restatement agrees to rounding
+ *                    and to the accuracy of log, exp, sqrt, cos, sin; n_comp >= ndim + 1 is required.
  * ln u = ln u01(r2_2, r2_3) for DE and snooker.  Decision (every move): h + beta lnprob(q) - beta lnprob(x_k) > ln u, beta of the
  * walker's ensemble (1 untempered); the stretch move's h is (ndim - 1) ln z.
+ * Philox counters c3 in use: 0, 1 (stretch), 2, 3 (DE, snooker), 0x4B00 .. 0x4B05 (KDE), 0x5117 (splits), 0x30FE (move of a
+ * step), 0 with half = 2 (swaps); the optimizer 0xDE00 .. and 0xDEFF, the nested sampler 0x4E000000 + j.
  * Mixtures: one move per step for the whole sampler.  With n_moves > 1, step s draws r = Philox(seed; s, 3, 0, 0x30FE) and takes
  * the first move m with u01(r0, r1) C_last < C_m, C the cumulative weights (summed in order, double): the move of a step depends
- * on (seed, s, table) only, so split runs give the chain of one run.  DE and snooker steps run two half-step launches (plus the
+ * on (seed, s, table) only, so split runs give the chain of one run.  DE, snooker and KDE steps run two half-step launches (plus the
  * swap sweep when tempered); stretch steps run as mp_sampler_set_whole_step decides.
  * n_moves == 0 restores the default (the stretch move with the a of mp_sampler_create); may be called between runs.
  * MP_EINVAL: NULL sampler or arrays, n_moves outside [0, MP_MAX_MOVES], an unknown kind, a weight that is not finite and > 0,
- * bad params, DE with n_half < 2, snooker with n_half < 3.  With a table set (n_moves > 0), the walker-sharded entry points
- * (mp_sampler_halfstep_*, mp_sampler_step_*) return MP_ESTATE.
+ * bad params (NaN and inf included), DE with n_half < 2, snooker with n_half < 3, KDE with n_comp < ndim + 1.  With a table
+ * set (n_moves > 0), the walker-sharded entry points (mp_sampler_halfstep_*, mp_sampler_step_*) return MP_ESTATE.
  */
 #define MP_MOVE_STRETCH 0   /* params: a (> 1)                                              */
 #define MP_MOVE_DE      1   /* params: g0 (0: 2.38/sqrt(2 ndim)), sigma in [0, 1/sqrt(3))    */
 #define MP_MOVE_SNOOKER 2   /* params: gamma_s (> 0)                                         */
+#define MP_MOVE_KDE     3   /* params: bandwidth (0 Scott, -1 Silverman, > 0 factor), 0      */
 #define MP_MAX_MOVES    8
 int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const double *weights,
                          const double *params /* [n_moves][2] */);

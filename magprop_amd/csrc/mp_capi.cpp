@@ -982,7 +982,7 @@ struct mp_sampler {
     // proposal moves (mp_sampler_set_moves); empty: the stretch move with scale a
     struct Move {
         int32_t kind;
-        double p0, p1;              // stretch: a; DE: g0 (resolved), s = sigma sqrt(3); snooker: gamma_s
+        double p0, p1;              // stretch: a; DE: g0 (resolved), s = sigma sqrt(3); snooker: gamma_s; KDE: f (resolved)
     };
     std::vector<Move> moves;
     std::vector<double> move_cum;   // cumulative weights, summed in order
@@ -1170,6 +1170,17 @@ int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const
             if (n_half < 3) return fail(MP_EINVAL, "mp_sampler_set_moves: the snooker move needs n_walkers >= 6 (three partners in the other half)");
             x.p0 = p0;
             break;
+        case MP_MOVE_KDE: {
+            const int n_comp = s->n_walkers - n_half, d = s->ndim;
+            if (!(p0 == 0.0 || p0 == -1.0 || (std::isfinite(p0) && p0 > 0.0)))
+                return fail(MP_EINVAL, "mp_sampler_set_moves: KDE bandwidth must be 0 (Scott), -1 (Silverman) or a finite factor > 0, got %g", p0);
+            if (p1 != 0.0) return fail(MP_EINVAL, "mp_sampler_set_moves: KDE params[1] must be 0, got %g", p1);
+            if (n_comp < d + 1)
+                return fail(MP_EINVAL, "mp_sampler_set_moves: the KDE move needs n_walkers - n_walkers / 2 >= ndim + 1 (a full-rank covariance of the other half), got %d", n_comp);
+            // scipy.stats.gaussian_kde's scotts_factor / silverman_factor with neff = n_comp
+            x.p0 = p0 > 0.0 ? p0 : std::pow(p0 == 0.0 ? (double)n_comp : n_comp * (d + 2.0) / 4.0, -1.0 / (d + 4));
+            break;
+        }
         default:
             return fail(MP_EINVAL, "mp_sampler_set_moves: unknown move kind %d", (int)kinds[m]);
         }
@@ -1236,7 +1247,8 @@ static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_
         g.move = mv->kind;
         if (mv->kind == MP_MOVE_STRETCH) g.a = mv->p0;
         else if (mv->kind == MP_MOVE_DE) { g.de_g0 = mv->p0; g.de_s = mv->p1; }
-        else g.gamma_s = mv->p0;
+        else if (mv->kind == MP_MOVE_SNOOKER) g.gamma_s = mv->p0;
+        else g.kde_f = mv->p0;
     }
     int e;
     if (whole && g.move == MP_MOVE_STRETCH) {

@@ -182,11 +182,13 @@ struct StretchArgs {
     const double *beta;     // [n_ensembles] inverse temperature of every ensemble (parallel tempering), or nullptr: 1 for all.
                             // Only the decisions use it; stored log-probabilities stay untempered
     // the proposal of a half-step launch (mp_sampler_set_moves; appended so that the stretch builds read what they read before)
-    int32_t move;           // MP_MOVE_STRETCH (a above), MP_MOVE_DE or MP_MOVE_SNOOKER (the DIFF builds of stretch_kernel)
+    int32_t move;           // MP_MOVE_STRETCH (a above), MP_MOVE_DE or MP_MOVE_SNOOKER (the DIFF builds of stretch_kernel),
+                            // MP_MOVE_KDE (the KDE builds)
     uint32_t pad2;
     double de_g0;           // DE: gamma = de_g0 (1 + de_s (2u - 1)), de_s = sigma sqrt(3)
     double de_s;
     double gamma_s;         // snooker scale
+    double kde_f;           // KDE: bandwidth factor f (resolved by mp_sampler_set_moves), kernel covariance f^2 S
 };
 
 // ---------------------------------------------------------------- compile-time constants of the stride policy

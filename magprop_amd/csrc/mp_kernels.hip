@@ -30,7 +30,8 @@
 // move fused around it) and stretch_apply_kernel (the state update of a half-step whose proposals were evaluated
 // on several GPUs); LONG = built with the path for light curves of more than 64 points.  Tempered samplers (parallel
 // tempering) take their decisions against beta x lnprob and run stretch_swap_kernel after every step.  The DIFF builds of
-// stretch_kernel propose emcee's differential-evolution and snooker moves instead (mp_sampler_set_moves).
+// stretch_kernel propose emcee's differential-evolution and snooker moves instead, the KDE builds emcee's KDE move
+// (mp_sampler_set_moves).
 // No MFMA (no dense contraction anywhere on this path), fp64 throughout; bound by the VALU issue rate of one wave per
 // SIMD (profiles/, tools/ubench).  The arithmetic is algebraically simplified with respect to the reference formulas
 // (e.g. fastness w = (Rm/Rc)^1.5 = omega*Rm^1.5/sqrt(GM), eta1-eta2 = -tanh); oracle/mp_oracle.c keeps the literal
@@ -209,6 +210,207 @@ MP_DEV void diff_proposal(const StretchArgs &g, int k, int base, const int32_t *
     }
 }
 
+// ---- the KDE proposal (the KDE builds of stretch_kernel; include/magprop_amd.h MP_MOVE_KDE)
+// Emcee's KDEMove over the two-way split: a Gaussian kernel density estimate of the other half C (kernel covariance f^2 S, S
+// the sample covariance of C) is both the proposal density, q = x_c + L n, and, through the ratio of its values at x_k and
+// q, the Hastings term.  Every workgroup computes the covariance of its ensemble's complement itself: n_comp d^2 operations
+// spread over the workgroup's lanes against an evaluation of ~190 k cycles.  Its LDS scratch aliases the tile image, which
+// is unused before walker_eval.
+constexpr int kKdeTri = MP_MAX_NDIM * (MP_MAX_NDIM + 1) / 2;   // lower triangle, by rows: entry (a, b <= a) at a (a + 1) / 2 + b
+constexpr uint32_t kKdeCtr = 0x4B00u;                          // Philox c3: 0x4B00 partner and ln u, 0x4B01 + p normals 2p, 2p + 1
+template <int W>
+struct KdeScratch {
+    double mean[W][MP_MAX_NDIM];   // per wavefront: its sums of the slots
+    double cov[W][kKdeTri];        // per wavefront: its sums of the centred products
+    double L[kKdeTri];             // Cholesky factor of f^2 S
+    double inv_diag[MP_MAX_NDIM];  // 1 / L_aa
+    double xk[MP_MAX_NDIM], q[MP_MAX_NDIM];
+    double lse[W][4];              // per wavefront: the running log-sum-exp pairs (m, s) at x_k and at q
+    int ok;                        // S positive definite
+};
+
+// Every thread of the workgroup (W wavefronts) calls this.  Leaves the proposal in park[0 .. MP_MAX_NDIM - 1] (zero beyond
+// ndim; NaN where S is not positive definite), the Hastings term in park[MP_MAX_NDIM] and ln u in park[MP_MAX_NDIM + 1],
+// behind a workgroup barrier; nothing else outlives it.  Sums over C: thread t takes slots t, t + 64 W, ... in order, then a
+// butterfly over the wavefront (wave_sum, wave_lse), then the W wavefronts' partials in order.  Unfused, like the other moves.
+template <int W>
+MP_DEV void kde_proposal(const StretchArgs &g, int k, int base, const int32_t *perm, int n_comp, const uint32_t (&r)[4],
+                         KdeScratch<W> &ks, double *park) {
+    constexpr int NT = 64 * W;
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6, d = g.ndim;
+    const int32_t *comp = perm + (1 - g.half) * g.n_half;
+    const double *pos = g.pos + (size_t)base * d;
+    // 1. the mean of C
+    {
+        double acc[MP_MAX_NDIM];
+#pragma unroll
+        for (int a = 0; a < MP_MAX_NDIM; ++a) acc[a] = 0.0;
+        for (int c = t; c < n_comp; c += NT) {
+            const double *x = pos + (size_t)comp[c] * d;
+#pragma unroll
+            for (int a = 0; a < MP_MAX_NDIM; ++a)
+                if (a < d) acc[a] = add_rn(acc[a], x[a]);
+        }
+#pragma unroll
+        for (int a = 0; a < MP_MAX_NDIM; ++a)
+            if (a < d) {
+                const double v = wave_sum(acc[a]);
+                if (lane == 0) ks.mean[wave][a] = v;
+            }
+    }
+    __syncthreads();
+    // 2. the centred products, summed over C
+    {
+        double mu[MP_MAX_NDIM], acc[kKdeTri];
+#pragma unroll
+        for (int a = 0; a < MP_MAX_NDIM; ++a) {
+            double m = 0.0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) m = a < d ? add_rn(m, ks.mean[w][a]) : 0.0;
+            mu[a] = m / n_comp;
+        }
+#pragma unroll
+        for (int p = 0; p < kKdeTri; ++p) acc[p] = 0.0;
+        for (int c = t; c < n_comp; c += NT) {
+            const double *x = pos + (size_t)comp[c] * d;
+            double e[MP_MAX_NDIM];
+#pragma unroll
+            for (int a = 0; a < MP_MAX_NDIM; ++a) e[a] = a < d ? sub_rn(x[a], mu[a]) : 0.0;
+#pragma unroll
+            for (int a = 0; a < MP_MAX_NDIM; ++a)
+                if (a < d) {
+#pragma unroll
+                    for (int b = 0; b <= a; ++b) acc[a * (a + 1) / 2 + b] = add_rn(acc[a * (a + 1) / 2 + b], mul_rn(e[a], e[b]));
+                }
+        }
+#pragma unroll
+        for (int a = 0; a < MP_MAX_NDIM; ++a)
+            if (a < d) {
+#pragma unroll
+                for (int b = 0; b <= a; ++b) {
+                    const double v = wave_sum(acc[a * (a + 1) / 2 + b]);
+                    if (lane == 0) ks.cov[wave][a * (a + 1) / 2 + b] = v;
+                }
+            }
+    }
+    __syncthreads();
+    // 3. one thread: Sigma = f^2 S (S = sums / (n_comp - 1)), its Cholesky factor by rows, the partner, the normals, q
+    if (t == 0) {
+        const double f2 = mul_rn(g.kde_f, g.kde_f), nm1 = n_comp - 1.0;
+        double L[kKdeTri];
+        bool ok = true;
+#pragma unroll
+        for (int a = 0; a < MP_MAX_NDIM; ++a)
+            if (a < d) {
+#pragma unroll
+                for (int b = 0; b <= a; ++b) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int w = 0; w < W; ++w) s = add_rn(s, ks.cov[w][a * (a + 1) / 2 + b]);
+                    s = mul_rn(f2, s / nm1);
+#pragma unroll
+                    for (int c = 0; c < b; ++c) s = sub_rn(s, mul_rn(L[a * (a + 1) / 2 + c], L[b * (b + 1) / 2 + c]));
+                    if (b == a) {
+                        ok = ok && s > 0.0 && s < INFINITY;   // a zero, negative or non-finite pivot
+                        L[a * (a + 1) / 2 + a] = sqrt(s);
+                    } else {
+                        L[a * (a + 1) / 2 + b] = s / L[b * (b + 1) / 2 + b];
+                    }
+                }
+            }
+        double nrm[MP_MAX_NDIM + 1];
+#pragma unroll
+        for (int p = 0; p < (MP_MAX_NDIM + 1) / 2; ++p)
+            if (2 * p < d) {   // Box-Muller: sqrt(-2 ln(1 - u_a)) cos, sin (2 pi u_b)
+                uint32_t s4[4];
+                philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, kKdeCtr + 1u + p, s4);
+                const double rad = sqrt(mul_rn(-2.0, log(sub_rn(1.0, u01(s4[0], s4[1])))));
+                const double ang = mul_rn(6.283185307179586, u01(s4[2], s4[3]));
+                nrm[2 * p] = mul_rn(rad, cos(ang));
+                nrm[2 * p + 1] = mul_rn(rad, sin(ang));
+            }
+        const double *xc = pos + (size_t)comp[pick(u01(r[0], r[1]), n_comp)] * d;
+        const double *xk = g.pos + (size_t)k * d;
+#pragma unroll
+        for (int a = 0; a < MP_MAX_NDIM; ++a) {
+            double qa = 0.0;
+            if (a < d) {
+                double s = 0.0;
+#pragma unroll
+                for (int b = 0; b <= a; ++b) s = add_rn(s, mul_rn(L[a * (a + 1) / 2 + b], nrm[b]));
+                qa = ok ? add_rn(xc[a], s) : NAN;
+                ks.xk[a] = xk[a];
+                ks.q[a] = qa;
+                ks.inv_diag[a] = 1.0 / L[a * (a + 1) / 2 + a];
+#pragma unroll
+                for (int b = 0; b <= a; ++b) ks.L[a * (a + 1) / 2 + b] = L[a * (a + 1) / 2 + b];
+            }
+            park[a] = qa;
+        }
+        ks.ok = ok ? 1 : 0;
+        park[MP_MAX_NDIM + 1] = log(u01(r[2], r[3]));
+    }
+    __syncthreads();
+    // 4. the two log-sum-exps over C of -|L^-1 (x - x_j)|^2 / 2, x = x_k and x = q (forward substitution)
+    const bool ok = ks.ok != 0;
+    if (ok) {
+        double Lr[kKdeTri], ivd[MP_MAX_NDIM], xk[MP_MAX_NDIM], q[MP_MAX_NDIM];
+#pragma unroll
+        for (int a = 0; a < MP_MAX_NDIM; ++a)
+            if (a < d) {
+                ivd[a] = ks.inv_diag[a];
+                xk[a] = ks.xk[a];
+                q[a] = ks.q[a];
+#pragma unroll
+                for (int b = 0; b < a; ++b) Lr[a * (a + 1) / 2 + b] = ks.L[a * (a + 1) / 2 + b];
+            }
+        double m0 = -INFINITY, s0 = 0.0, m1 = -INFINITY, s1 = 0.0;
+        for (int c = t; c < n_comp; c += NT) {
+            const double *x = pos + (size_t)comp[c] * d;
+            double y0[MP_MAX_NDIM], y1[MP_MAX_NDIM], v0 = 0.0, v1 = 0.0;
+#pragma unroll
+            for (int a = 0; a < MP_MAX_NDIM; ++a)
+                if (a < d) {
+                    double u0 = sub_rn(xk[a], x[a]), u1 = sub_rn(q[a], x[a]);
+#pragma unroll
+                    for (int b = 0; b < a; ++b) {
+                        u0 = sub_rn(u0, mul_rn(Lr[a * (a + 1) / 2 + b], y0[b]));
+                        u1 = sub_rn(u1, mul_rn(Lr[a * (a + 1) / 2 + b], y1[b]));
+                    }
+                    y0[a] = mul_rn(u0, ivd[a]);
+                    y1[a] = mul_rn(u1, ivd[a]);
+                    v0 = add_rn(v0, mul_rn(y0[a], y0[a]));
+                    v1 = add_rn(v1, mul_rn(y1[a], y1[a]));
+                }
+            lse_add(m0, s0, mul_rn(-0.5, v0));
+            lse_add(m1, s1, mul_rn(-0.5, v1));
+        }
+        wave_lse(m0, s0);
+        wave_lse(m1, s1);
+        if (lane == 0) {
+            ks.lse[wave][0] = m0;
+            ks.lse[wave][1] = s0;
+            ks.lse[wave][2] = m1;
+            ks.lse[wave][3] = s1;
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        double h = NAN;
+        if (ok) {
+            double m0 = ks.lse[0][0], s0 = ks.lse[0][1], m1 = ks.lse[0][2], s1 = ks.lse[0][3];
+#pragma unroll
+            for (int w = 1; w < W; ++w) {
+                lse_merge(m0, s0, ks.lse[w][0], ks.lse[w][1]);
+                lse_merge(m1, s1, ks.lse[w][2], ks.lse[w][3]);
+            }
+            h = sub_rn(add_rn(m0, log(s0)), add_rn(m1, log(s1)));
+        }
+        park[MP_MAX_NDIM] = h;
+    }
+    __syncthreads();   // (the tile image is free for walker_eval again; park is read behind it)
+}
+
 // W, OCC: small ensembles evaluate every proposal on a team of W = 4 wavefronts (lnprob_team_kernel; OCC = wavefronts resident
 // per SIMD the build is made for), chosen by the size of a WHOLE step of the sampler (stretch_waves, mp_device.h) so that one
 // launch per step and one per half-step run the same arithmetic: the chains stay equal bit for bit.
@@ -218,7 +420,9 @@ MP_DEV void diff_proposal(const StretchArgs &g, int k, int base, const int32_t *
 // DIFF: the builds of the differential-evolution and snooker moves (g.move, decided at run time): only the proposal stage
 // differs -- partners, proposal, Hastings term and ln u, from the counters c3 = 2, 3 -- and the stretch builds are the code
 // they were.  Evaluation, decision, commit, chain row and failure log are shared.
-template <int SPL, bool LONG, int W = 1, int OCC = 0, bool TEMPERED = false, bool DIFF = false>
+// KDE: the builds of the KDE move (kde_proposal, DIFF false): the workgroup's proposal stage over the other half, counters
+// c3 = 0x4B00 + j; a NaN proposal (S not positive definite) is not evaluated and is rejected.
+template <int SPL, bool LONG, int W = 1, int OCC = 0, bool TEMPERED = false, bool DIFF = false, bool KDE = false>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
 void stretch_kernel(const DevShared sh, const StretchArgs g) {
     __shared__ TileImage<SPL * W> im;
@@ -235,7 +439,7 @@ void stretch_kernel(const DevShared sh, const StretchArgs g) {
     const int base = w_ens * g.n_walkers;
     const int k = base + perm[g.half * g.n_half + slot];           // active walker (global index)
     uint32_t r[4], r2[4];
-    philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, DIFF ? 2u : 0u, r);
+    philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, KDE ? kKdeCtr : (DIFF ? 2u : 0u), r);
     philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, DIFF ? 3u : 1u, r2);
     const int n_comp = g.n_walkers - g.n_half;
     const int jc = (int)(u01(r[0], r[1]) * n_comp);                // partner from the complementary half
@@ -245,7 +449,12 @@ void stretch_kernel(const DevShared sh, const StretchArgs g) {
     const double zz = mul_rn(zr, zr) / g.a;                      // g(z) ~ 1/sqrt(z) on [1/a, a]
     double par[MP_MAX_NDIM];
     double qq = 1.0, dd = 1.0;   // (DIFF: the snooker move's sums)
-    if constexpr (DIFF) {
+    if constexpr (KDE) {
+        static_assert(sizeof(KdeScratch<W>) <= sizeof(TileImage<SPL * W>), "the KDE scratch must fit the tile image");
+        kde_proposal<W>(g, k, base, perm, n_comp, r, *reinterpret_cast<KdeScratch<W> *>(&im), park);
+#pragma unroll
+        for (int i = 0; i < MP_MAX_NDIM; ++i) par[i] = park[i];
+    } else if constexpr (DIFF) {
         // (the stretch draw above is dead code here; it stays first because moving it into the else branch changed the SGPR
         // spills of four stretch builds)
         diff_proposal(g, k, base, perm, n_comp, r, r2, par, qq, dd);
@@ -268,19 +477,21 @@ void stretch_kernel(const DevShared sh, const StretchArgs g) {
         for (int i = 0; i < MP_MAX_NDIM; ++i) lnp = i < g.ndim ? sub_rn(lnp, mul_rn(mul_rn(0.5, par[i]), par[i])) : lnp;
     }
     if (lane0) {
+        if constexpr (!KDE) {   // (the KDE stage has parked its proposal, Hastings term and ln u)
 #pragma unroll
-        for (int i = 0; i < MP_MAX_NDIM; ++i) park[i] = par[i];
-        if constexpr (!DIFF) {
-            park[MP_MAX_NDIM] = mul_rn(g.ndim - 1.0, log(zz));
-            park[MP_MAX_NDIM + 1] = log(u01(r2[0], r2[1]));
-        } else {
-            park[MP_MAX_NDIM] = g.move == MP_MOVE_DE ? 0.0 : mul_rn(mul_rn(0.5, g.ndim - 1.0), sub_rn(log(qq), log(dd)));
-            park[MP_MAX_NDIM + 1] = log(u01(r2[2], r2[3]));
+            for (int i = 0; i < MP_MAX_NDIM; ++i) park[i] = par[i];
+            if constexpr (!DIFF) {
+                park[MP_MAX_NDIM] = mul_rn(g.ndim - 1.0, log(zz));
+                park[MP_MAX_NDIM + 1] = log(u01(r2[0], r2[1]));
+            } else {
+                park[MP_MAX_NDIM] = g.move == MP_MOVE_DE ? 0.0 : mul_rn(mul_rn(0.5, g.ndim - 1.0), sub_rn(log(qq), log(dd)));
+                park[MP_MAX_NDIM + 1] = log(u01(r2[2], r2[3]));
+            }
         }
         park[MP_MAX_NDIM + 2] = g.lnprob[k];
     }
     int status = MP_STATUS_OK, sweeps, tiles;
-    if (g.target != 1) {
+    if (g.target != 1 && !(KDE && par[0] != par[0])) {   // (KDE: a NaN proposal keeps lnp = 0, its Hastings term NaN rejects it)
         LaunchArgs a{};
         a.ds_id = g.ds_id;
         a.ndim = g.ndim;
@@ -627,10 +838,19 @@ int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
 
 // The build of a stretch launch of n_blocks blocks, one rule for stretch_kernel and stretch_step_kernel (walker_variant): small
 // samplers, by the size of a WHOLE step (stretch_waves), evaluate every proposal on a team of four wavefronts.
-// n_blocks slots of the active half starting at g.slot_lo; the DIFF builds (DE / snooker) are chosen by the same rule
+// n_blocks slots of the active half starting at g.slot_lo; the DIFF builds (DE / snooker) and the KDE builds are chosen by the
+// same rule
 int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
     if (n_blocks <= 0) return 0;
     const Variant v = walker_variant(sh, n_blocks, stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4);
+    if (g.move == MP_MOVE_KDE) {
+        dispatch([&](auto team, auto roomy, auto lng, auto tempered) {
+            using B = Build<team, roomy>;
+            hipLaunchKernelGGL((stretch_kernel<B::SPL, lng, B::W, B::OCC, tempered, false, true>), dim3((unsigned)n_blocks), dim3(64 * B::W),
+                               0, (hipStream_t)stream, sh, g);
+        }, v.team, v.roomy, sh.has_long != 0, g.beta != nullptr);
+        return (int)hipGetLastError();
+    }
     dispatch([&](auto team, auto roomy, auto lng, auto tempered, auto diff) {
         using B = Build<team, roomy>;
         hipLaunchKernelGGL((stretch_kernel<B::SPL, lng, B::W, B::OCC, tempered, diff>), dim3((unsigned)n_blocks), dim3(64 * B::W), 0,

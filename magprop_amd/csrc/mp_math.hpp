@@ -597,4 +597,32 @@ MP_DEV int pick_skip2(double u, int m, int c0, int c1) {
     return t >= max(c0, c1) ? t + 1 : t;
 }
 
+// ---------------------------------------------------------------- log-sum-exp (the KDE move's Hastings term, mp_kernels.hip)
+// A running log-sum-exp is a pair (m, s): the sum is e^m s, m the largest term so far; (-inf, 0) is the empty sum.
+// lse_add takes one more term v, lse_merge another pair.  Unfused and symmetric in its two operands (no contraction into
+// an FMA, which would round one product and not the other), so that every lane of a butterfly ends with the same pair.
+MP_DEV void lse_add(double &m, double &s, double v) {
+    if (v > m) {
+        s = add_rn(mul_rn(s, exp(m - v)), 1.0);
+        m = v;
+    } else if (v > -INFINITY) {
+        s = add_rn(s, exp(sub_rn(v, m)));
+    }
+}
+MP_DEV void lse_merge(double &m, double &s, double mo, double so) {
+    const double mx = fmax(m, mo);
+    const double a = s != 0.0 ? mul_rn(s, exp(sub_rn(m, mx))) : 0.0;
+    const double b = so != 0.0 ? mul_rn(so, exp(sub_rn(mo, mx))) : 0.0;
+    s = add_rn(a, b);
+    m = s != 0.0 ? mx : -INFINITY;
+}
+// the pair over the 64 lanes of the wavefront (butterfly, every lane ends with the same pair)
+MP_DEV void wave_lse(double &m, double &s) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double mo = __shfl_xor(m, d, 64), so = __shfl_xor(s, d, 64);
+        lse_merge(m, s, mo, so);
+    }
+}
+
 }  // namespace mp

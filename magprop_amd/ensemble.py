@@ -36,7 +36,7 @@ class EnsembleSampler:
         parallel tempering with one ensemble per (dataset, temperature), nensembles = len(datasets) x T (T for
         target="gaussian"), positions in ensemble order (group g, temperature t: walkers [(g T + t) nwalkers, + nwalkers)).
         moves: None (the stretch move with scale a, as emcee), or emcee's moves= forms over magprop_amd.moves (StretchMove,
-        DEMove, DESnookerMove): a move, a list of moves, or a list of (move, weight); one move is drawn per step
+        DEMove, DESnookerMove, KDEMove): a move, a list of moves, or a list of (move, weight); one move is drawn per step
         (include/magprop_amd.h mp_sampler_set_moves).  Give the stretch scale as StretchMove(a) then: moves together with a
         non-default a is refused."""
         if nwalkers % 2 or nwalkers < 2:

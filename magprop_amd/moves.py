@@ -2,6 +2,7 @@
 
     EnsembleSampler(..., moves=DEMove())
     EnsembleSampler(..., moves=[(DEMove(), 0.8), (DESnookerMove(), 0.2)])
+    EnsembleSampler(..., moves=KDEMove())
 
 Every move runs inside the fused half-step kernels; these classes only carry the parameters.  One move is drawn per step for
 the whole sampler, with probability proportional to its weight, as in emcee.  Two deviations from emcee 3.1:
@@ -10,7 +11,7 @@ partners from the other half of a two-way split, not from a four-way split.
 """
 import math
 
-MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER = 0, 1, 2      # include/magprop_amd.h MP_MOVE_*
+MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_KDE = 0, 1, 2, 3   # include/magprop_amd.h MP_MOVE_*
 MAX_MOVES = 8                                       # MP_MAX_MOVES
 
 
@@ -86,6 +87,35 @@ class DESnookerMove(Move):
         return f"DESnookerMove(gammas={self.gammas})"
 
 
+class KDEMove(Move):
+    """emcee's KDEMove: q drawn from a Gaussian kernel density estimate of the other half of the ensemble (kernel covariance
+    f^2 S, S the half's sample covariance), with the Hastings term ln KDE(x) - ln KDE(q).  bw_method as scipy.stats.gaussian_kde
+    takes it: None or "scott" (f = n^(-1/(ndim+4))), "silverman" (f = (n (ndim+2)/4)^(-1/(ndim+4))) or a positive factor f,
+    n = the walkers of the other half.  Needs n >= ndim + 1."""
+    kind = MOVE_KDE
+
+    def __init__(self, bw_method=None):
+        if bw_method is None or (isinstance(bw_method, str) and bw_method in ("scott", "silverman")):
+            self.bw_method = "scott" if bw_method is None else bw_method
+            return
+        if isinstance(bw_method, (str, bool)):
+            raise ValueError(f"KDEMove: bw_method must be None, 'scott', 'silverman' or a positive number, got {bw_method!r}")
+        try:
+            f = float(bw_method)
+        except (TypeError, ValueError):
+            raise ValueError(f"KDEMove: bw_method must be None, 'scott', 'silverman' or a positive number, got {bw_method!r}") from None
+        if not (math.isfinite(f) and f > 0.0):
+            raise ValueError(f"KDEMove: a bandwidth factor must be finite and > 0, got {bw_method!r}")
+        self.bw_method = f
+
+    def params(self, ndim):
+        codes = {"scott": 0.0, "silverman": -1.0}   # the library's codes; a factor goes as it is
+        return (codes[self.bw_method] if isinstance(self.bw_method, str) else self.bw_method, 0.0)
+
+    def __repr__(self):
+        return f"KDEMove(bw_method={self.bw_method!r})"
+
+
 def parse_moves(moves):
     """emcee's forms of moves=: a move, a list of moves (equal weights) or a list of (move, weight).  Returns a list of
     (move, weight).  Weights are kept as given (emcee normalises them; the draw is the same up to rounding)."""
@@ -109,7 +139,7 @@ def parse_moves(moves):
         except (TypeError, ValueError):
             raise ValueError(f"moves entries must be moves or (move, weight) pairs, got {it!r}") from None
         if not isinstance(mv, Move):
-            raise ValueError(f"not a move: {mv!r} (StretchMove, DEMove, DESnookerMove)")
+            raise ValueError(f"not a move: {mv!r} (StretchMove, DEMove, DESnookerMove, KDEMove)")
         w = float(w)
         if not (math.isfinite(w) and w > 0.0):
             raise ValueError(f"move weights must be finite and > 0, got {w}")
@@ -130,12 +160,12 @@ def move_table(moves, ndim):
 
 def parse_spec(spec):
     """'de:0.8,snooker:0.2' (the command-line form of tools/run_synth_mcmc.py) -> [(DEMove(), 0.8), (DESnookerMove(), 0.2)].
-    Names: stretch, de, snooker; a missing weight is 1."""
-    names = {"stretch": StretchMove, "de": DEMove, "snooker": DESnookerMove}
+    Names: stretch, de, snooker, kde; a missing weight is 1."""
+    names = {"stretch": StretchMove, "de": DEMove, "snooker": DESnookerMove, "kde": KDEMove}
     out = []
     for part in str(spec).split(","):
         name, _, w = part.strip().partition(":")
         if name not in names:
-            raise ValueError(f"unknown move {name!r} in {spec!r} (stretch, de, snooker)")
+            raise ValueError(f"unknown move {name!r} in {spec!r} (stretch, de, snooker, kde)")
         out.append((names[name](), float(w) if w else 1.0))
     return out

@@ -2,10 +2,11 @@
 
     python tools/moves_bench.py rate [--sizes 64,512,1024,4096]   walker-steps/s and acceptance of every configuration
     python tools/moves_bench.py tau                               integrated autocorrelation time per move, 512 walkers x 6 000 steps
-    python tools/moves_bench.py profile --walkers 1024            a short DE run to profile (rocprofv3 --kernel-trace --stats -- ...)
+    python tools/moves_bench.py profile --walkers 1024 [--move kde]  a short DE (KDE) run to profile (rocprofv3 --kernel-trace --stats -- ...)
 
 Configurations: stretch with its default launch (a whole step per launch where it fits), stretch with whole_step=False (the
-launches DE and snooker run: two half-step launches per step), DE, snooker, and the mixture 0.8 DE + 0.2 snooker.
+launches DE and snooker run: two half-step launches per step), DE, snooker, the mixture 0.8 DE + 0.2 snooker, KDE and the
+mixture 0.8 KDE + 0.2 DE.
 Rate: every sampler starts at the Humped truth (1e-4 ball), runs --warm steps unstored, then --steps timed steps unstored
 (mp_sampler_run returns when its steps are done).  Tau: --tau-steps stored steps, the first quarter discarded; effective samples
 per second = walker-steps/s of the rate run at the same size / mean tau over the six parameters.
@@ -22,7 +23,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from magprop_amd import DEMove, DESnookerMove, EnsembleSampler  # noqa: E402
+from magprop_amd import DEMove, DESnookerMove, EnsembleSampler, KDEMove  # noqa: E402
 
 TRUTH = [1.0, 5.0, -3.0, 2.0, -1.0, 0.0]     # Humped, sampler coordinates
 CONFIGS = {
@@ -31,6 +32,8 @@ CONFIGS = {
     "de": dict(moves=DEMove()),
     "snooker": dict(moves=DESnookerMove()),
     "de0.8_snooker0.2": dict(moves=[(DEMove(), 0.8), (DESnookerMove(), 0.2)]),
+    "kde": dict(moves=KDEMove()),
+    "kde0.8_de0.2": dict(moves=[(KDEMove(), 0.8), (DEMove(), 0.2)]),
 }
 
 
@@ -72,6 +75,10 @@ def rate(args):
     # gate: DE and snooker at >= 0.85 x the stretch move on the same launches (whole_step=False)
     out["gate_min_over_half_steps"] = min(r[k]["over_stretch_half_steps"] for r in out["sizes"].values()
                                           for k in ("de", "snooker", "de0.8_snooker0.2"))
+    # gate: KDE half-steps at >= 0.85 x the DE move's
+    for r in out["sizes"].values():
+        r["kde"]["over_de"] = r["kde"]["walker_steps_per_s"] / r["de"]["walker_steps_per_s"]
+    out["gate_kde_min_over_de"] = min(r["kde"]["over_de"] for r in out["sizes"].values())
     return out
 
 
@@ -104,10 +111,10 @@ def tau(args):
 
 def profile(args):
     x, y, yerr = data()
-    s = EnsembleSampler(args.walkers, 6, x, y, yerr, seed=1, moves=DEMove())
+    s = EnsembleSampler(args.walkers, 6, x, y, yerr, seed=1, moves=KDEMove() if args.move == "kde" else DEMove())
     s.run_mcmc(_start(args.walkers, 0), args.steps, store=False)
     s.close()
-    return {"what": "profiling run (DE)", "walkers": args.walkers, "steps": args.steps}
+    return {"what": f"profiling run ({args.move})", "walkers": args.walkers, "steps": args.steps}
 
 
 def main():
@@ -118,6 +125,7 @@ def main():
     ap.add_argument("--warm", type=int, default=200)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--tau-steps", type=int, default=6000)
+    ap.add_argument("--move", choices=("de", "kde"), default="de", help="profile: the move of the run")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     res = {"rate": rate, "tau": tau, "profile": profile}[args.mode](args)
