@@ -329,7 +329,8 @@ int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted);
  * ln u = ln u01(r2_2, r2_3) for DE and snooker.  Decision (every move): h + beta lnprob(q) - beta lnprob(x_k) > ln u, beta of the
  * walker's ensemble (1 untempered); the stretch move's h is (ndim - 1) ln z.
  * Philox counters c3 in use: 0, 1 (stretch), 2, 3 (DE, snooker), 0x4B00 .. 0x4B05 (KDE), 0x5117 (splits), 0x30FE (move of a
- * step), 0 with half = 2 (swaps); the optimizer 0xDE00 .. and 0xDEFF, the nested sampler 0x4E000000 + j.
+ * step), 0 with half = 2 (swaps); the optimizer 0xDE00 .. and 0xDEFF, the nested sampler 0x4E000000 + j (random walk) and
+ * 0x4E400000 + 0x100 s + c (slice mode).
  * Mixtures: one move per step for the whole sampler.  With n_moves > 1, step s draws r = Philox(seed; s, 3, 0, 0x30FE) and takes
  * the first move m with u01(r0, r1) C_last < C_m, C the cumulative weights (summed in order, double): the move of a step depends
  * on (seed, s, table) only, so split runs give the chain of one run.  DE, snooker and KDE steps run two half-step launches (plus the
@@ -443,9 +444,9 @@ int mp_optimizer_destroy(mp_optimizer *o);
 
 /*
  * Nested sampler (ABI 5, additive): Skilling's nested sampling (2006) with batch removal (dynesty's), the dead points replaced by
- * constrained DE random walks; one select and one walk launch per iteration.  n_runs independent runs (1 <= n_runs <=
- * MP_MAX_DATASETS) of nlive live points each (MP_NEST_MIN_LIVE <= N <= MP_NEST_MAX_LIVE); run r runs on dataset run_ds_id[r]
- * (NULL: dataset 0 for all; several runs may share a dataset).  Live slot j of run r is row r * N + j.  The prior is uniform
+ * constrained DE random walks or (slice mode) slice updates; one select and one walk launch per iteration.  n_runs independent
+ * runs (1 <= n_runs <= MP_MAX_DATASETS) of nlive live points each (MP_NEST_MIN_LIVE <= N <= MP_NEST_MAX_LIVE); run r runs on
+ * dataset run_ds_id[r] (NULL: dataset 0 for all; several runs may share a dataset).  Live slot j of run r is row r * N + j.  The prior is uniform
  * over the box lower[ndim] < upper[ndim] (finite; sampler coordinates).  target: 0 the log-posterior of the handle (lnL), 1 the
  * isotropic unit Gaussian -0.5 sum x^2 (tests).  A NaN lnL counts (and is stored) as -inf.
  * Iteration t of run r (t = the run's own iteration count, from 0), K = nbatch (1 <= K <= N / 2), M = N - K:
@@ -459,6 +460,23 @@ int mp_optimizer_destroy(mp_optimizer *o);
  *   every d (a proposal outside is not evaluated) and lnL(q) > L*; then x = q.  The difference set (the survivors) is fixed
  *   during the walk: the proposal is symmetric, and this is Metropolis for the prior restricted to lnL > L*.
  *   The walk's end point, its lnL, status and accepted-step count replace dead slot j.
+ * Slice mode (mp_nested_set_slice with slices > 0, from the next iteration on): the walk into dead slot j is `slices` slice
+ * updates along survivor differences (ensemble slice sampling's differential direction, Karamanis & Beutler 2021, on the
+ * constrained prior; Neal 2003's stepping out and shrinkage).  Start: the random walk's, c = 0 above.  Slice s = 0 .. slices-1
+ * draws from Philox4x32-10 keyed (seed; t, r, j, 0x4E400000 + 0x100 s + c):
+ *     c = 0:          partners c1 = pick(u01(r0, r1), M), c2 = distinct from c1 by u01(r2, r3); d = x_{s_c1} - x_{s_c2};
+ *                     points on the line q(t)_d = x_d + t d_d (unfused);
+ *     c = 1:          L = -(mu u01(r0, r1)), R = L + mu; of the stepping-out budget m = max_steps_out, J = floor(m u01(r2, r3))
+ *                     steps go left and K = m - 1 - J right;
+ *     c = 2 + i:      shrink point i = 0 .. max_shrink-1: t = L + u01(r0, r1) (R - L).
+ *   Inside means lower_d <= q_d <= upper_d for every d (a point outside the box is outside and is not evaluated) and lnL(q) >
+ *   L*.  Stepping out: while J > 0 and q(L) is inside, L = L - mu, J = J - 1; then while K > 0 and q(R) is inside, R = R + mu,
+ *   K = K - 1.  Shrinkage: if q(t) is inside, x = q(t) (with its lnL and status) and the slice ends; otherwise L = t if t < 0,
+ *   else R = t.  After max_shrink rejected points, or at once when d = 0 (coinciding survivors), the slice ends where it
+ *   started and counts as failed.  A start whose lnL equals L* (a tie with dead K - 1) is not inside: its slices run as any
+ *   other, a shrink point inside moves it, and a slice that finds none fails with x unchanged, as a random walk that accepts
+ *   nothing.  In slice mode acc counts the walk's slices that moved, nacc the slices that moved, nzero the walks in which no
+ *   slice moved; nexpand counts stepping-out steps taken, ncontract rejected shrink points, nfail failed slices.
  * Volume bookkeeping, one thread per run, dead k = 0 .. K-1 with n_k = N - k live points:
  *   lnw_k = (lnL_k + ln X) + log(-expm1(-1 / n_k));  ln X = ln X - 1 / n_k;  ln Z = logaddexp(ln Z, lnw_k)
  *   (logaddexp(x, y) = m + log1p(exp(-|x - y|)), m = max(x, y); -inf when both are), from ln X = 0, ln Z = -inf.
@@ -478,10 +496,18 @@ int mp_optimizer_destroy(mp_optimizer *o);
  * lnl[], n_live[] (each may be NULL).  mp_nested_get_state: any output may be NULL; live[n_runs * nlive][ndim], lnl, status,
  * acc (accepted steps of the walk that put the point there; 0 for the caller's points) [n_runs * nlive]; per run: nit, stopped,
  * lnx, lnz, ncall (evaluations inside walks), nacc (accepted steps), nzero (walks that accepted nothing).
+ * mp_nested_set_slice(slices, mu, max_steps_out, max_shrink): slices = 0 restores the random walk; may be called between runs
+ * (the state depends on the iteration it was called before, not on how mp_nested_run is split).  MP_EINVAL: NULL sampler, slices
+ * outside 0 .. MP_NEST_MAX_SLICES, mu not finite and > 0, max_steps_out outside 1 .. MP_NEST_MAX_STEPS_OUT, max_shrink outside 1 ..
+ * MP_NEST_MAX_SHRINK (the counters c = 2 + i stay below 0x100).  mp_nested_get_slice_stats: per run since mp_nested_set_live,
+ * nexpand, ncontract, nfail [n_runs] (each may be NULL; 0 while only random walks ran); MP_ESTATE before mp_nested_set_live.
  */
 #define MP_NEST_MIN_LIVE 16
 #define MP_NEST_MAX_LIVE 4096
 #define MP_NEST_MAX_WALKS 4096
+#define MP_NEST_MAX_SLICES 4096
+#define MP_NEST_MAX_STEPS_OUT 4096
+#define MP_NEST_MAX_SHRINK 254
 typedef struct mp_nested mp_nested;
 mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int ndim, const int32_t *run_ds_id, uint64_t seed,
                             int walks, double g0, double sigma, double dlogz, const double *lower, const double *upper, int target);
@@ -490,6 +516,8 @@ int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running);
 int mp_nested_get_dead(mp_nested *ns, int run, int64_t max_rows, double *pars, double *lnl, int32_t *n_live, int64_t *n_rows);
 int mp_nested_get_state(mp_nested *ns, double *live, double *lnl, int32_t *status, int32_t *acc, int32_t *nit, int32_t *stopped,
                         double *lnx, double *lnz, int64_t *ncall, int64_t *nacc, int64_t *nzero);
+int mp_nested_set_slice(mp_nested *ns, int slices, double mu, int max_steps_out, int max_shrink);
+int mp_nested_get_slice_stats(mp_nested *ns, int64_t *nexpand, int64_t *ncontract, int64_t *nfail);
 int mp_nested_destroy(mp_nested *ns);
 
 /* wait for everything enqueued on the handle's own stream */

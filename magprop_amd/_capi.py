@@ -23,6 +23,7 @@ BAND_LTOT, BAND_LPROP, BAND_LDIP = 1, 2, 4
 BAND_COMPONENTS = {"Ltot": BAND_LTOT, "Lprop": BAND_LPROP, "Ldip": BAND_LDIP}
 DE_BEST1BIN, DE_RAND1BIN = 0, 1                               # include/magprop_amd.h MP_DE_*
 NEST_MIN_LIVE, NEST_MAX_LIVE, NEST_MAX_WALKS = 16, 4096, 4096  # include/magprop_amd.h MP_NEST_*
+NEST_MAX_SLICES, NEST_MAX_STEPS_OUT, NEST_MAX_SHRINK = 4096, 4096, 254
 
 EXPORTS = (
     "mp_abi_version", "mp_last_error", "mp_cfg_synth", "mp_cfg_lib", "mp_create", "mp_destroy",
@@ -35,7 +36,7 @@ EXPORTS = (
     "mp_get_policy", "mp_create_multi", "mp_n_devices", "mp_model_band", "mp_sampler_set_temperatures", "mp_sampler_get_swaps",
     "mp_sampler_set_moves", "mp_optimizer_create", "mp_optimizer_set_population", "mp_optimizer_run", "mp_optimizer_get_state",
     "mp_optimizer_destroy", "mp_nested_create", "mp_nested_set_live", "mp_nested_run", "mp_nested_get_dead", "mp_nested_get_state",
-    "mp_nested_destroy",
+    "mp_nested_destroy", "mp_nested_set_slice", "mp_nested_get_slice_stats",
 )
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -171,6 +172,8 @@ def lib():
     L.mp_nested_get_dead.argtypes = [vp, C.c_int, C.c_int64, dp, dp, ip, i64p]
     L.mp_nested_get_state.argtypes = [vp, dp, dp, ip, ip, ip, ip, dp, dp, i64p, i64p, i64p]
     L.mp_nested_destroy.argtypes = [vp]
+    L.mp_nested_set_slice.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int]
+    L.mp_nested_get_slice_stats.argtypes = [vp, i64p, i64p, i64p]
     L.mp_last_mean_sweeps.argtypes = [vp]
     L.mp_last_mean_sweeps.restype = C.c_double
     L.mp_last_mean_tiles.argtypes = [vp]
@@ -206,7 +209,7 @@ def lib():
                  "mp_sampler_step_shard", "mp_sampler_step_apply", "mp_sampler_state_ptrs", "mp_n_simd",
                  "mp_sampler_set_temperatures", "mp_sampler_get_swaps", "mp_optimizer_set_population", "mp_optimizer_run",
                  "mp_optimizer_get_state", "mp_optimizer_destroy", "mp_nested_set_live", "mp_nested_run", "mp_nested_get_dead",
-                 "mp_nested_get_state", "mp_nested_destroy"):
+                 "mp_nested_get_state", "mp_nested_destroy", "mp_nested_set_slice", "mp_nested_get_slice_stats"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

@@ -1625,7 +1625,8 @@ struct mp_nested {
     bool have_state = false;
     DevBuf<double> d_live, d_lnl, d_lstar, d_dpars, d_dlnl, d_lnx, d_lnz;
     DevBuf<int32_t> d_st, d_acc, d_dsid, d_dslot, d_surv, d_dn, d_stop, d_nit;
-    DevBuf<int64_t> d_ncall, d_nacc, d_nzero;
+    DevBuf<int64_t> d_ncall, d_nacc, d_nzero, d_nexp, d_ncon, d_nfail;
+    mp::NestSlice sl{};             // slice mode (sl.slices > 0) from the next iteration on
     std::vector<std::vector<double>> dead_pars, dead_lnl;   // per run, in order
     std::vector<std::vector<int32_t>> dead_n;
 };
@@ -1668,6 +1669,7 @@ mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int
     bind(ns->d_lstar, nr, a.lstar); bind(ns->d_dpars, nc * ndim, a.dead_pars); bind(ns->d_dlnl, nc, a.dead_lnl); bind(ns->d_dn, nc, a.dead_n);
     bind(ns->d_lnx, nr, a.lnx); bind(ns->d_lnz, nr, a.lnz); bind(ns->d_stop, nr, a.stopped); bind(ns->d_nit, nr, a.nit);
     bind(ns->d_ncall, nr, a.ncall); bind(ns->d_nacc, nr, a.nacc); bind(ns->d_nzero, nr, a.nzero);
+    bind(ns->d_nexp, nr, ns->sl.nexpand); bind(ns->d_ncon, nr, ns->sl.ncontract); bind(ns->d_nfail, nr, ns->sl.nfail);
     if (bind.rc || upload_ds_rows(ns->d_dsid.p, run_ds_id, n_runs, 1)) {
         fail(MP_EHIP, "mp_nested_create: device allocation failed");
         mp_nested_destroy(ns);
@@ -1706,6 +1708,9 @@ int mp_nested_set_live(mp_nested *ns, const double *live) {
     HIP_TRY(hipMemsetAsync(a.ncall, 0, nr * sizeof(int64_t), h->stream));
     HIP_TRY(hipMemsetAsync(a.nacc, 0, nr * sizeof(int64_t), h->stream));
     HIP_TRY(hipMemsetAsync(a.nzero, 0, nr * sizeof(int64_t), h->stream));
+    HIP_TRY(hipMemsetAsync(ns->sl.nexpand, 0, nr * sizeof(int64_t), h->stream));
+    HIP_TRY(hipMemsetAsync(ns->sl.ncontract, 0, nr * sizeof(int64_t), h->stream));
+    HIP_TRY(hipMemsetAsync(ns->sl.nfail, 0, nr * sizeof(int64_t), h->stream));
     a.mode = 1;
     a.iter = 0;
     const int e = mp::launch_nest_walk(h->sh, a, h->stream);
@@ -1741,7 +1746,7 @@ int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running) {
             a.iter = ns->iter++;
             a.mode = 0;
             int e = mp::launch_nest_select(a, h->stream);
-            if (!e) e = mp::launch_nest_walk(h->sh, a, h->stream);
+            if (!e) e = ns->sl.slices ? mp::launch_nest_slice(h->sh, a, ns->sl, h->stream) : mp::launch_nest_walk(h->sh, a, h->stream);
             if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
         }
         a.mode = 1;
@@ -1793,6 +1798,33 @@ int mp_nested_get_state(mp_nested *ns, double *live, double *lnl, int32_t *statu
     HIP_TRY(hipStreamSynchronize(h->stream));
     return read_back(live, a.live, nt * a.ndim, lnl, a.lnl, nt, status, a.st, nt, acc, a.acc, nt, nit, a.nit, nr,
                      stopped, a.stopped, nr, lnx, a.lnx, nr, lnz, a.lnz, nr, ncall, a.ncall, nr, nacc, a.nacc, nr, nzero, a.nzero, nr);
+}
+
+int mp_nested_set_slice(mp_nested *ns, int slices, double mu, int max_steps_out, int max_shrink) {
+    if (!ns) return fail(MP_EINVAL, "mp_nested_set_slice: NULL sampler");
+    if (slices < 0 || slices > MP_NEST_MAX_SLICES) return fail(MP_EINVAL, "mp_nested_set_slice: slices must be 0 .. %d, got %d", MP_NEST_MAX_SLICES, slices);
+    if (!(std::isfinite(mu) && mu > 0.0)) return fail(MP_EINVAL, "mp_nested_set_slice: mu must be finite and > 0");
+    if (max_steps_out < 1 || max_steps_out > MP_NEST_MAX_STEPS_OUT)
+        return fail(MP_EINVAL, "mp_nested_set_slice: max_steps_out must be 1 .. %d, got %d", MP_NEST_MAX_STEPS_OUT, max_steps_out);
+    if (max_shrink < 1 || max_shrink > MP_NEST_MAX_SHRINK)
+        return fail(MP_EINVAL, "mp_nested_set_slice: max_shrink must be 1 .. %d, got %d", MP_NEST_MAX_SHRINK, max_shrink);
+    Lock lock(ns->h->mu);   // (read by the next mp_nested_run)
+    ns->sl.slices = slices;
+    ns->sl.mu = mu;
+    ns->sl.max_steps_out = max_steps_out;
+    ns->sl.max_shrink = max_shrink;
+    return MP_OK;
+}
+
+int mp_nested_get_slice_stats(mp_nested *ns, int64_t *nexpand, int64_t *ncontract, int64_t *nfail) {
+    if (!ns) return fail(MP_EINVAL, "mp_nested_get_slice_stats: NULL sampler");
+    if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_get_slice_stats: call mp_nested_set_live first");
+    mp_handle *h = ns->h;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    const size_t nr = (size_t)ns->a.n_runs;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return read_back(nexpand, ns->sl.nexpand, nr, ncontract, ns->sl.ncontract, nr, nfail, ns->sl.nfail, nr);
 }
 
 int mp_device(const mp_handle *h) { return h ? h->device : -1; }

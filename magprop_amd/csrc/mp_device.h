@@ -394,5 +394,19 @@ struct NestArgs {
 // mode 1: one per live point, evaluated as it is); include/magprop_amd.h
 int launch_nest_select(const NestArgs &a, void *stream);
 int launch_nest_walk(const DevShared &sh, const NestArgs &a, void *stream);
+// Slice mode of the nested sampler (mp_nested_set_slice): the walk into a dead slot is `slices` slice updates along survivor
+// differences (include/magprop_amd.h states the scheme).  Passed beside NestArgs, which the random walk's kernels keep as it is.
+struct NestSlice {
+    int64_t *nexpand;        // [n_runs] stepping-out steps that widened an interval
+    int64_t *ncontract;      // [n_runs] shrink points that were rejected
+    int64_t *nfail;          // [n_runs] slices that ended where they started (shrink cap, or a zero direction)
+    double mu;               // initial interval width, in units of the direction
+    int32_t slices;          // slice updates per walk (0: the random walk)
+    int32_t max_steps_out;   // Neal's stepping-out budget m
+    int32_t max_shrink;      // shrink points per slice before it counts as failed
+    int32_t pad;
+};
+// one workgroup per dead slot (mode 0 only), the builds of launch_nest_walk
+int launch_nest_slice(const DevShared &sh, const NestArgs &a, const NestSlice &sl, void *stream);
 
 }  // namespace mp

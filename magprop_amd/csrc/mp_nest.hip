@@ -8,6 +8,9 @@
 // the start and builds every DE step in LDS, the workgroup evaluates the step with walker_eval, lane 0 decides (inside the box and
 // lnL > L*).  Survivors are only read and dead slots only written, so the workgroups need no hand-off among themselves.  Mode 1
 // evaluates the live set as the caller set it.
+// nest_slice_kernel: the walk of slice mode (mp_nested_set_slice), the same workgroups and builds.  Lane 0 runs the slice updates
+// as a state machine in LDS (start a slice, step out left, step out right, shrink) that names one point per round or ends the
+// walk; the workgroup evaluates the named point through the one walker_eval call site of the kernel.
 #include <hip/hip_runtime.h>
 
 #include "mp_eval.hpp"
@@ -129,6 +132,178 @@ void nest_walk_kernel(const DevShared sh, const NestArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- slice mode
+constexpr uint32_t kSliceCtr = 0x4E400000u;   // third counter word: 0x4E400000 + 0x100 s + c, c = 0 .. 1 + max_shrink, slice s
+
+// The walk's state between rounds, in LDS (only lane 0 reads or writes it).  phase: kStart begins slice s (ends the walk after
+// the last), kLeft / kRight step out (budgets left / right), kShrink draws shrink point i of [lo, hi].
+enum { kStart = 0, kLeft = 1, kRight = 2, kShrink = 3 };
+struct SliceState {
+    double lnl, lo, hi, t;    // the current point's lnL; the interval along dir; the parameter of the named point
+    int st, s, phase, left, right, i, moved, n_eval, n_exp, n_con, n_fail;
+};
+
+// Lane 0, once per round: takes the outcome of the point named last round (have: one was evaluated, lnL lnp, status), then
+// advances until it names the next point in the box (prop = cur + t dir, unfused; returns 1) or the walk ends (returns 0).
+// Inside = in the box and lnL > L*; a point outside the box is outside without an evaluation.
+MP_DEV int slice_round(const NestArgs &a, const NestSlice &sl, int r, int slot, SliceState &z, double *cur, double *dir,
+                       double *prop, bool have, double lnp, int status) {
+    const int nd = a.ndim, m = a.nlive - a.nbatch, base = r * a.nlive;
+    const double lstar = a.lstar[r];
+    bool in = have && lnp > lstar;
+    for (;;) {
+        if (have) {   // the named point's outcome (evaluated, or outside the box)
+            have = false;
+            if (z.phase == kLeft) {
+                if (in) { z.lo = sub_rn(z.lo, sl.mu); --z.left; ++z.n_exp; } else z.phase = kRight;
+            } else if (z.phase == kRight) {
+                if (in) { z.hi = add_rn(z.hi, sl.mu); --z.right; ++z.n_exp; } else z.phase = kShrink;
+            } else if (in) {
+                for (int d = 0; d < nd; ++d) cur[d] = prop[d];
+                z.lnl = lnp;
+                z.st = status;
+                ++z.moved;
+                ++z.s;
+                z.phase = kStart;
+            } else {
+                ++z.n_con;
+                if (z.t < 0.0) z.lo = z.t;
+                else z.hi = z.t;
+            }
+        }
+        double t;
+        if (z.phase == kStart) {
+            if (z.s == sl.slices) return 0;
+            uint32_t u[4];
+            philox4x32_10((uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.iter, (uint32_t)r, (uint32_t)slot, kSliceCtr + 0x100u * (uint32_t)z.s, u);
+            const int c1 = pick(u01(u[0], u[1]), m), c2 = pick_skip(u01(u[2], u[3]), m, c1);
+            const double *x1 = a.live + (size_t)(base + a.surv[r * m + c1]) * nd;
+            const double *x2 = a.live + (size_t)(base + a.surv[r * m + c2]) * nd;
+            int nz = 0;
+            for (int d = 0; d < nd; ++d) {
+                dir[d] = sub_rn(x1[d], x2[d]);
+                nz |= dir[d] != 0.0 ? 1 : 0;
+            }
+            if (!nz) {   // coinciding partners: the slice fails where it starts
+                ++z.n_fail;
+                ++z.s;
+                continue;
+            }
+            philox4x32_10((uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.iter, (uint32_t)r, (uint32_t)slot, kSliceCtr + 0x100u * (uint32_t)z.s + 1u, u);
+            z.lo = -mul_rn(sl.mu, u01(u[0], u[1]));
+            z.hi = add_rn(z.lo, sl.mu);
+            z.left = (int)(u01(u[2], u[3]) * (double)sl.max_steps_out);
+            z.right = sl.max_steps_out - 1 - z.left;
+            z.i = 0;
+            z.phase = kLeft;
+            continue;
+        }
+        if (z.phase == kLeft) {
+            if (z.left == 0) { z.phase = kRight; continue; }
+            t = z.lo;
+        } else if (z.phase == kRight) {
+            if (z.right == 0) { z.phase = kShrink; continue; }
+            t = z.hi;
+        } else {
+            if (z.i == sl.max_shrink) {   // the cap: the slice fails where it starts
+                ++z.n_fail;
+                ++z.s;
+                z.phase = kStart;
+                continue;
+            }
+            uint32_t u[4];
+            philox4x32_10((uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.iter, (uint32_t)r, (uint32_t)slot,
+                          kSliceCtr + 0x100u * (uint32_t)z.s + 2u + (uint32_t)z.i, u);
+            ++z.i;
+            t = add_rn(z.lo, mul_rn(u01(u[0], u[1]), sub_rn(z.hi, z.lo)));
+        }
+        z.t = t;
+        int box = 1;
+        for (int d = 0; d < nd; ++d) {
+            const double q = add_rn(cur[d], mul_rn(t, dir[d]));
+            box &= (q >= a.lower[d] && q <= a.upper[d]) ? 1 : 0;
+            prop[d] = q;
+        }
+        if (box) return 1;
+        have = true;   // outside the box: outside, not evaluated
+        in = false;
+    }
+}
+
+// One workgroup per dead slot of a running run; builds and template arguments as nest_walk_kernel.
+template <int SPL, bool LONG, int W = 1, int OCC = 0>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
+void nest_slice_kernel(const DevShared sh, const NestArgs a, const NestSlice sl) {
+    const int b = (int)blockIdx.x, r = b / a.nbatch, k = b - r * a.nbatch;
+    if (a.stopped[r]) return;   // frozen run (uniform for the workgroup): nothing to do
+    __shared__ TileImage<SPL * W> im;
+    __shared__ TimeTable<SPL * W> tt;
+    __shared__ double lds[1];
+    __shared__ double cur[MP_MAX_NDIM];      // the walk's current point
+    __shared__ double dir[MP_MAX_NDIM];      // the slice's direction
+    __shared__ double prop[MP_MAX_NDIM];     // the named point across walker_eval
+    __shared__ SliceState z;
+    __shared__ int go;                       // 1: evaluate prop; 0: the walk has ended
+    __shared__ TeamLds<SPL * W, (W > 1)> tl;
+    TeamX<SPL * W> *const tx = tl.ptr();
+    tables_init<SPL * W, 64 * W>(sh, tt);
+    const int nd = a.ndim, m = a.nlive - a.nbatch, base = r * a.nlive;
+    const int slot = a.dead_slot[r * a.nbatch + k];
+    if (threadIdx.x == 0) {
+        uint32_t u[4];
+        nest_draw(a, r, slot, 0u, u);
+        const int from = base + a.surv[r * m + pick(u01(u[0], u[1]), m)];
+        for (int d = 0; d < nd; ++d) cur[d] = a.live[(size_t)from * nd + d];
+        z = SliceState{};
+        z.lnl = a.lnl[from];
+        z.st = a.st[from];
+        z.phase = kStart;
+    }
+    double lnp = 0.0;
+    int status = MP_STATUS_OK;
+    for (bool have = false;; have = true) {
+        __syncthreads();
+        if (threadIdx.x == 0) go = slice_round(a, sl, r, slot, z, cur, dir, prop, have, lnp, status);
+        __syncthreads();
+        if (!go) break;                        // (uniform: LDS behind the barrier)
+        double par[MP_MAX_NDIM];
+#pragma unroll
+        for (int d = 0; d < MP_MAX_NDIM; ++d) par[d] = d < nd ? prop[d] : 0.0;
+        lnp = 0.0;
+        status = MP_STATUS_OK;
+        int sweeps, tiles;
+        if (a.target == 1) {   // isotropic unit Gaussian: exercises the algorithm itself (tests)
+#pragma unroll
+            for (int d = 0; d < MP_MAX_NDIM; ++d) lnp = d < nd ? sub_rn(lnp, mul_rn(mul_rn(0.5, par[d]), par[d])) : lnp;
+        } else {
+            LaunchArgs la{};
+            la.ds_id = a.ds_id;
+            la.ndim = nd;
+            la.physical = 0;
+            la.want_chi2 = 1;
+            if constexpr (W > 1) walker_eval<false, SPL, LONG, false, W, OCC >= 2>(sh, la, r, par, im, tt, lds, lnp, status, sweeps, tiles, tx);
+            else walker_eval<false, SPL, LONG>(sh, la, r, par, im, tt, lds, lnp, status, sweeps, tiles);
+        }
+        if (threadIdx.x == 0) {
+            if (lnp != lnp) lnp = -INFINITY;   // NaN counts (and is kept) as -inf
+            ++z.n_eval;
+        }
+    }
+    if (threadIdx.x == 0) {
+        const size_t row = (size_t)(base + slot);
+        for (int d = 0; d < nd; ++d) a.live[row * nd + d] = cur[d];
+        a.lnl[row] = z.lnl;
+        a.st[row] = z.st;
+        a.acc[row] = z.moved;
+        atomicAdd((unsigned long long *)&a.ncall[r], (unsigned long long)z.n_eval);
+        atomicAdd((unsigned long long *)&a.nacc[r], (unsigned long long)z.moved);
+        if (z.moved == 0) atomicAdd((unsigned long long *)&a.nzero[r], 1ull);
+        atomicAdd((unsigned long long *)&sl.nexpand[r], (unsigned long long)z.n_exp);
+        atomicAdd((unsigned long long *)&sl.ncontract[r], (unsigned long long)z.n_con);
+        atomicAdd((unsigned long long *)&sl.nfail[r], (unsigned long long)z.n_fail);
+    }
+}
+
 constexpr int kSelThreads = 1024;
 
 // Ranks, the stop rule and the bookkeeping of one iteration of run blockIdx.x (include/magprop_amd.h states the arithmetic).
@@ -213,6 +388,18 @@ int launch_nest_walk(const DevShared &sh, const NestArgs &a, void *stream) {
     dispatch([&](auto team, auto roomy, auto lng) {
         using B = Build<team, roomy>;
         hipLaunchKernelGGL((nest_walk_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n), dim3(64 * B::W), 0, (hipStream_t)stream, sh, a);
+    }, v.team, v.roomy, sh.has_long != 0);
+    return (int)hipGetLastError();
+}
+
+// slice mode: the builds of launch_nest_walk for its n_runs * nbatch workgroups
+int launch_nest_slice(const DevShared &sh, const NestArgs &a, const NestSlice &sl, void *stream) {
+    const int n = a.n_runs * a.nbatch;
+    if (n <= 0 || a.mode) return 0;
+    const Variant v = walker_variant(sh, n, kernel_waves(sh, n) == 4);
+    dispatch([&](auto team, auto roomy, auto lng) {
+        using B = Build<team, roomy>;
+        hipLaunchKernelGGL((nest_slice_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n), dim3(64 * B::W), 0, (hipStream_t)stream, sh, a, sl);
     }, v.team, v.roomy, sh.has_long != 0);
     return (int)hipGetLastError();
 }

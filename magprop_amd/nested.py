@@ -1,8 +1,8 @@
 """Evidence and posterior samples on the GPU: nested sampling (Skilling 2006) with batch removal, device-resident.
 
 Every iteration of every run is one select launch (the K lowest live points die; ln X and ln Z advance) and one walk launch
-(each dead slot is refilled by a constrained DE random walk from a survivor); the host reads the dead points back once per chunk
-of iterations (include/magprop_amd.h mp_nested_*).  The final estimate is host-side and pure: ``add_live``, ``estimate`` and
+(each dead slot is refilled from a survivor by a constrained DE random walk, or with sample="slice" by slice updates along
+survivor differences); the host reads the dead points back once per chunk of iterations (include/magprop_amd.h mp_nested_*).  The final estimate is host-side and pure: ``add_live``, ``estimate`` and
 ``resample_equal`` need no device, after dynesty's ``add_live`` and ``resample_equal``.
 
 The prior is uniform over a box in sampler coordinates, as for ``EnsembleSampler.log_evidence``.  The live set starts from
@@ -19,6 +19,7 @@ from . import _capi, engine, tempering
 from .optimize import OptimizeResult, _variant_box
 
 TARGETS = {"posterior": 0, "gaussian": 1}
+SAMPLES = ("rwalk", "slice")
 MAX_DRAW_ROUNDS = 4096
 
 
@@ -135,6 +136,26 @@ def _check_args(x, datasets, nlive, nbatch, walks, variant, ndim, bounds, n_runs
     return lo, hi, plo, phi, mask, int(nbatch), n_ds
 
 
+def _check_slice(sample, slices, slice_mu, max_steps_out, max_shrink, ndim):
+    """Slice updates per walk (0 for the random walk): every check of the walk method, no device touched."""
+    if sample not in SAMPLES:
+        raise ValueError(f"sample must be one of {SAMPLES}, got {sample!r}")
+    if not (isinstance(slice_mu, (int, float, np.floating, np.integer)) and np.isfinite(slice_mu) and slice_mu > 0.0):
+        raise ValueError("slice_mu must be finite and > 0")
+    if int(max_steps_out) != max_steps_out or not 1 <= max_steps_out <= _capi.NEST_MAX_STEPS_OUT:
+        raise ValueError(f"max_steps_out must be an integer in 1 .. {_capi.NEST_MAX_STEPS_OUT}")
+    if int(max_shrink) != max_shrink or not 1 <= max_shrink <= _capi.NEST_MAX_SHRINK:
+        raise ValueError(f"max_shrink must be an integer in 1 .. {_capi.NEST_MAX_SHRINK}")
+    if sample == "rwalk":
+        if slices is not None:
+            raise ValueError("slices applies to sample='slice' only")
+        return 0
+    slices = ndim if slices is None else slices
+    if int(slices) != slices or not 1 <= slices <= _capi.NEST_MAX_SLICES:
+        raise ValueError(f"slices must be an integer in 1 .. {_capi.NEST_MAX_SLICES}")
+    return int(slices)
+
+
 class NestedSampler:
     """Nested sampling of the log-posterior of light curve (x, y, yerr), or of every light curve of datasets=[(x, y, yerr), ...],
     under a uniform prior over a box, on the GPU.
@@ -144,12 +165,22 @@ class NestedSampler:
     ndim)) whose difference vectors come from the surviving live points.  variant / ndim / GRBtype / bounds follow
     optimize.differential_evolution (default box: the variant's prior box).  n_runs: independent runs per dataset, all in one
     launch per iteration (run index = dataset index x n_runs + run).  seed keys both the live-set draws (numpy) and the device's
-    walks (Philox).  target="gaussian" samples the isotropic unit Gaussian -0.5 sum x^2 in `bounds` (tests, measurements)."""
+    walks (Philox).  target="gaussian" samples the isotropic unit Gaussian -0.5 sum x^2 in `bounds` (tests, measurements).
+
+    sample="slice" replaces the random walk by `slices` slice updates per walk (default ndim; dynesty's sample="slice" with the
+    directions of ensemble slice sampling): each slice runs along the difference of two survivors, starts from an interval of
+    slice_mu differences at a random offset, steps out with Neal's budget max_steps_out and shrinks at most max_shrink times (a
+    slice that reaches the cap, or draws two coinciding survivors, stays where it started and counts as failed).  It needs no
+    step size and moves on every slice that does not fail; walks, g0 and sigma are then unused."""
 
     def __init__(self, x=None, y=None, yerr=None, nlive=500, nbatch=None, walks=25, variant="synth", ndim=6, GRBtype=None,
-                 datasets=None, n_runs=1, seed=0, bounds=None, log_mask=None, g0=0.0, sigma=0.1, target="posterior", device=-1):
+                 datasets=None, n_runs=1, seed=0, bounds=None, log_mask=None, g0=0.0, sigma=0.1, target="posterior", device=-1,
+                 sample="rwalk", slices=None, slice_mu=1.0, max_steps_out=8, max_shrink=64):
         lo, hi, plo, phi, mask, nbatch, n_ds = _check_args(x, datasets, nlive, nbatch, walks, variant, ndim, bounds, n_runs, g0,
                                                             sigma, target)
+        self.slices = _check_slice(sample, slices, slice_mu, max_steps_out, max_shrink, lo.size)
+        self.sample, self.slice_mu = sample, float(slice_mu)
+        self.max_steps_out, self.max_shrink = int(max_steps_out), int(max_shrink)
         self.lower, self.upper = lo, hi
         self.ndim = lo.size
         self.nlive, self.nbatch, self.walks = int(nlive), nbatch, int(walks)
@@ -207,7 +238,10 @@ class NestedSampler:
         """Run every run until log1p(exp(lnL_max + ln X - ln Z)) < dlogz, or for maxiter iterations; fills .results (a Results
         for one run, else a list in run order): logz, logzerr, information, samples, logl, logwt, logvol, niter (iterations of
         nbatch dead points), ncall (prior draws of the live set plus evaluations inside walks), eff (100 x dead points / ncall),
-        nzero (walks that accepted nothing), ln_f_valid, samples_n (live count of every row), stopped."""
+        nzero (walks that accepted nothing; slice mode: walks in which no slice moved), nacc (accepted steps; slice mode: slices
+        that moved), nexpand / ncontract / nfail (slice mode: stepping-out steps, rejected shrink points, failed slices; 0 for
+        the random walk), ln_f_valid, samples_n (live count of every row), stopped.  Warns (RuntimeWarning) when more than 1 %
+        of the walks accepted nothing (random walk) or more than 1 % of the slices failed (slice mode)."""
         if not (np.isfinite(dlogz) and dlogz > 0.0):
             raise ValueError("dlogz must be finite and > 0")
         if maxiter is not None and (int(maxiter) != maxiter or maxiter < 0):
@@ -223,9 +257,13 @@ class NestedSampler:
         if not ns:
             raise _capi.MagpropAmdError("mp_nested_create failed: " + _capi.last_error())
         try:
+            if self.slices:
+                _capi.check(L.mp_nested_set_slice(ns, self.slices, self.slice_mu, self.max_steps_out, self.max_shrink),
+                            "mp_nested_set_slice")
             _capi.check(L.mp_nested_set_live(ns, np.ascontiguousarray(live0).ctypes.data_as(dp)), "mp_nested_set_live")
             _capi.check(L.mp_nested_run(ns, 2 ** 31 - 1 if maxiter is None else int(maxiter), None), "mp_nested_run")
             st = get_state(L, ns, self.n_runs, self.nlive, self.ndim)
+            st.update(get_slice_stats(L, ns, self.n_runs))
             dead = [get_dead(L, ns, r, self.ndim) for r in range(self.n_runs)]
         finally:
             L.mp_nested_destroy(ns)
@@ -238,14 +276,21 @@ class NestedSampler:
             n_dead = lnl.size
             ncall = int(draws[r]) + int(st["ncall"][r])
             walks_run = int(st["nit"][r]) * self.nbatch
-            nzero = int(st["nzero"][r])
-            if walks_run and nzero > 0.01 * walks_run:
+            nzero, nfail = int(st["nzero"][r]), int(st["nfail"][r])
+            if self.slices:
+                slices_run = walks_run * self.slices
+                if slices_run and nfail > 0.01 * slices_run:
+                    warnings.warn(f"run {r}: {nfail} of {slices_run} slices failed (shrink cap or coinciding survivors): the "
+                                  "live set may be poorly mixed (a larger max_shrink, or a smaller slice_mu)", RuntimeWarning,
+                                  stacklevel=2)
+            elif walks_run and nzero > 0.01 * walks_run:
                 warnings.warn(f"run {r}: {nzero} of {walks_run} walks accepted no step: the live set may be poorly mixed "
                               "(more walks, or a smaller g0)", RuntimeWarning, stacklevel=2)
             out.append(Results(
                 logz=est["logz"], logzerr=est["logzerr"], information=est["information"], samples=samples, logl=est["logl"],
                 logwt=est["logwt"], logvol=est["logvol"], niter=int(st["nit"][r]), ncall=ncall,
-                eff=100.0 * n_dead / max(ncall, 1), nzero=nzero, nacc=int(st["nacc"][r]), ln_f_valid=lnf,
+                eff=100.0 * n_dead / max(ncall, 1), nzero=nzero, nacc=int(st["nacc"][r]), nexpand=int(st["nexpand"][r]),
+                ncontract=int(st["ncontract"][r]), nfail=nfail, ln_f_valid=lnf,
                 samples_n=np.concatenate([nl, np.arange(self.nlive, 0, -1)]), stopped=bool(st["stopped"][r]),
                 device_logz=float(st["lnz"][r])))
         self.results = out[0] if self.n_runs == 1 else out
@@ -293,6 +338,15 @@ def get_state(L, ns, n_runs, nlive, ndim):
                                       st["acc"].ctypes.data_as(ip), st["nit"].ctypes.data_as(ip), st["stopped"].ctypes.data_as(ip),
                                       st["lnx"].ctypes.data_as(dp), st["lnz"].ctypes.data_as(dp), st["ncall"].ctypes.data_as(lp),
                                       st["nacc"].ctypes.data_as(lp), st["nzero"].ctypes.data_as(lp)), "mp_nested_get_state")
+    return st
+
+
+def get_slice_stats(L, ns, n_runs):
+    """mp_nested_get_slice_stats as arrays: per run nexpand, ncontract, nfail."""
+    st = {k: np.empty(n_runs, dtype=np.int64) for k in ("nexpand", "ncontract", "nfail")}
+    lp = C.POINTER(C.c_int64)
+    _capi.check(L.mp_nested_get_slice_stats(ns, st["nexpand"].ctypes.data_as(lp), st["ncontract"].ctypes.data_as(lp),
+                                            st["nfail"].ctypes.data_as(lp)), "mp_nested_get_slice_stats")
     return st
 
 
