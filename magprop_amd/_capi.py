@@ -25,19 +25,6 @@ DE_BEST1BIN, DE_RAND1BIN = 0, 1                               # include/magprop_
 NEST_MIN_LIVE, NEST_MAX_LIVE, NEST_MAX_WALKS = 16, 4096, 4096  # include/magprop_amd.h MP_NEST_*
 NEST_MAX_SLICES, NEST_MAX_STEPS_OUT, NEST_MAX_SHRINK = 4096, 4096, 254
 
-EXPORTS = (
-    "mp_abi_version", "mp_last_error", "mp_cfg_synth", "mp_cfg_lib", "mp_create", "mp_destroy",
-    "mp_set_dataset", "mp_set_prior", "mp_lnprob_batch", "mp_lnprob_batch_dev", "mp_model_lc", "mp_rhs_batch",
-    "mp_synchronize", "mp_device", "mp_stream", "mp_n_grid", "mp_last_mean_sweeps", "mp_last_mean_tiles",
-    "mp_sampler_create", "mp_sampler_destroy", "mp_sampler_set_positions", "mp_sampler_run", "mp_sampler_set_whole_step", "mp_sampler_get_state",
-    "mp_sampler_get_bad", "mp_sampler_n_slots", "mp_sampler_row_doubles", "mp_sampler_halfstep_shard",
-    "mp_sampler_halfstep_apply", "mp_sampler_step_blocks", "mp_sampler_step_row_doubles", "mp_sampler_step_shard",
-    "mp_sampler_step_apply", "mp_sampler_state_ptrs", "mp_sweep_tol", "mp_n_simd", "mp_last_sweeps", "mp_last_tiles", "mp_tile_log", "mp_last_tile_log",
-    "mp_get_policy", "mp_create_multi", "mp_n_devices", "mp_model_band", "mp_sampler_set_temperatures", "mp_sampler_get_swaps",
-    "mp_sampler_set_moves", "mp_optimizer_create", "mp_optimizer_set_population", "mp_optimizer_run", "mp_optimizer_get_state",
-    "mp_optimizer_destroy", "mp_nested_create", "mp_nested_set_live", "mp_nested_run", "mp_nested_get_dead", "mp_nested_get_state",
-    "mp_nested_destroy", "mp_nested_set_slice", "mp_nested_get_slice_stats",
-)
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
 POLICY_FIELDS = ("max_stride", "stride_tol", "sweep_tol", "early_hold_seconds", "k4_tol_factor", "coarse_tol_factor",
@@ -56,6 +43,76 @@ class ModelCfg(C.Structure):
         "dipeff", "propeff", "f_beam", "nacc_lum_threshold")] + [
         ("lprop_gm_term", C.c_int32), ("max_stride", C.c_int32), ("sweep_tol", C.c_double), ("stride_tol", C.c_double),
         ("dipole_torque", C.c_int32), ("reserved", C.c_int32)]
+
+
+_i, _u32, _i64, _u64, _d = C.c_int, C.c_uint32, C.c_int64, C.c_uint64, C.c_double
+_vp, _dp, _ip, _i64p, _cfgp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(ModelCfg)
+# name -> (restype, argtypes) of every function of include/magprop_amd.h, in header order (tests/test_capi_cpu.py holds the two
+# together).  Handles, samplers, optimizers, nested samplers and streams are c_void_p; so are the host pointers of
+# mp_lnprob_batch, passed as integers (the hot entry), and the device pointers.
+SIGNATURES = {
+    "mp_abi_version": (_i, []),
+    "mp_last_error": (C.c_char_p, []),
+    "mp_cfg_synth": (None, [_cfgp]),
+    "mp_cfg_lib": (None, [_cfgp]),
+    "mp_create": (_vp, [_cfgp, _dp, _i, _i]),
+    "mp_destroy": (_i, [_vp]),
+    "mp_create_multi": (_vp, [_cfgp, _dp, _i, _ip, _i]),
+    "mp_n_devices": (_i, [_vp]),
+    "mp_set_dataset": (_i, [_vp, _i, _dp, _dp, _dp, _i]),
+    "mp_set_prior": (_i, [_vp, _dp, _dp, _i, _u32]),
+    "mp_lnprob_batch": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "mp_lnprob_batch_dev": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "mp_model_lc": (_i, [_vp, _dp, _i, _dp, _dp, _ip]),
+    "mp_rhs_batch": (_i, [_vp, _dp, _i, _dp, _dp, _i, _dp, _dp]),
+    "mp_model_band": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _u32, _dp, _ip, _ip]),
+    "mp_sampler_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _d, _i]),
+    "mp_sampler_destroy": (_i, [_vp]),
+    "mp_sampler_set_positions": (_i, [_vp, _dp]),
+    "mp_sampler_run": (_i, [_vp, _i, _dp, _dp]),
+    "mp_sampler_set_whole_step": (_i, [_vp, _i]),
+    "mp_sampler_get_state": (_i, [_vp, _dp, _dp, _i64p, _i64p]),
+    "mp_sampler_set_temperatures": (_i, [_vp, _i, _dp]),
+    "mp_sampler_get_swaps": (_i, [_vp, _i64p]),
+    "mp_sampler_set_moves": (_i, [_vp, _i, _ip, _dp, _dp]),
+    "mp_sampler_get_bad": (_i, [_vp, _i64, _dp, _i, _i64p, _i64p]),
+    "mp_sampler_n_slots": (_i, [_vp]),
+    "mp_sampler_row_doubles": (_i, [_vp]),
+    "mp_sampler_halfstep_shard": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "mp_sampler_halfstep_apply": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "mp_sampler_step_blocks": (_i, [_vp]),
+    "mp_sampler_step_row_doubles": (_i, [_vp]),
+    "mp_sampler_step_shard": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mp_sampler_step_apply": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "mp_sampler_state_ptrs": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "mp_optimizer_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _i, _d, _d, _d, _d, _d, _dp, _dp, _i]),
+    "mp_optimizer_set_population": (_i, [_vp, _dp]),
+    "mp_optimizer_run": (_i, [_vp, _i, _ip]),
+    "mp_optimizer_get_state": (_i, [_vp, _dp, _dp, _ip, _ip, _ip, _ip, _i64p]),
+    "mp_optimizer_destroy": (_i, [_vp]),
+    "mp_nested_create": (_vp, [_vp, _i, _i, _i, _i, _ip, _u64, _i, _d, _d, _d, _dp, _dp, _i]),
+    "mp_nested_set_live": (_i, [_vp, _dp]),
+    "mp_nested_run": (_i, [_vp, _i, _ip]),
+    "mp_nested_get_dead": (_i, [_vp, _i, _i64, _dp, _dp, _ip, _i64p]),
+    "mp_nested_get_state": (_i, [_vp, _dp, _dp, _ip, _ip, _ip, _ip, _dp, _dp, _i64p, _i64p, _i64p]),
+    "mp_nested_set_slice": (_i, [_vp, _i, _d, _i, _i]),
+    "mp_nested_get_slice_stats": (_i, [_vp, _i64p, _i64p, _i64p]),
+    "mp_nested_destroy": (_i, [_vp]),
+    "mp_synchronize": (_i, [_vp]),
+    "mp_device": (_i, [_vp]),
+    "mp_stream": (_vp, [_vp]),
+    "mp_n_grid": (_i, [_vp]),
+    "mp_last_mean_sweeps": (_d, [_vp]),
+    "mp_last_mean_tiles": (_d, [_vp]),
+    "mp_last_sweeps": (_i, [_vp, _ip, _i]),
+    "mp_tile_log": (_i, [_vp, _i]),
+    "mp_last_tile_log": (_i, [_vp, _i, _ip, _i]),
+    "mp_last_tiles": (_i, [_vp, _ip, _i]),
+    "mp_sweep_tol": (_d, [_vp]),
+    "mp_get_policy": (_i, [_vp, _dp, _i]),
+    "mp_n_simd": (_i, [_vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def build(force=False, verbose=False):
@@ -111,106 +168,18 @@ def lib():
         L = C.CDLL(LIB_PATH)
     except OSError as exc:
         raise MagpropAmdError(f"cannot load {LIB_PATH}: {exc}") from exc
-    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
     # the ABI check comes before any other symbol is touched: a stale build must fail with the rebuild hint, not with an
     # AttributeError on a symbol it does not have yet
     try:
-        L.mp_abi_version.restype = C.c_int
-        abi = L.mp_abi_version()
+        abi = L.mp_abi_version()            # (ctypes' default restype: int)
     except AttributeError:
         abi = None
     if abi != ABI_VERSION:
         raise MagpropAmdError(f"{LIB_PATH} has ABI version {abi}, this binding expects {ABI_VERSION}: "
                               "rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
-    L.mp_last_error.restype = C.c_char_p
-    L.mp_cfg_synth.argtypes = [C.POINTER(ModelCfg)]
-    L.mp_cfg_synth.restype = None
-    L.mp_cfg_lib.argtypes = [C.POINTER(ModelCfg)]
-    L.mp_cfg_lib.restype = None
-    L.mp_create.restype = vp
-    L.mp_create.argtypes = [C.POINTER(ModelCfg), dp, C.c_int, C.c_int]
-    L.mp_create_multi.restype = vp
-    L.mp_create_multi.argtypes = [C.POINTER(ModelCfg), dp, C.c_int, ip, C.c_int]
-    L.mp_n_devices.argtypes = [vp]
-    L.mp_n_devices.restype = C.c_int
-    L.mp_destroy.argtypes = [vp]
-    L.mp_set_dataset.argtypes = [vp, C.c_int, dp, dp, dp, C.c_int]
-    L.mp_set_prior.argtypes = [vp, dp, dp, C.c_int, C.c_uint32]
-    L.mp_lnprob_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]   # (host pointers as integers: the hot entry)
-    L.mp_lnprob_batch_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.mp_model_lc.argtypes = [vp, dp, C.c_int, dp, dp, ip]
-    L.mp_rhs_batch.argtypes = [vp, dp, C.c_int, dp, dp, C.c_int, dp, dp]
-    L.mp_model_band.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_uint32, dp, ip, ip]
-    L.mp_synchronize.argtypes = [vp]
-    L.mp_device.argtypes = [vp]
-    L.mp_stream.argtypes = [vp]
-    L.mp_stream.restype = vp
-    L.mp_n_grid.argtypes = [vp]
-    i64p = C.POINTER(C.c_int64)
-    L.mp_sampler_create.restype = vp
-    L.mp_sampler_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_uint64, C.c_double, C.c_int]
-    L.mp_sampler_destroy.argtypes = [vp]
-    L.mp_sampler_set_positions.argtypes = [vp, dp]
-    L.mp_sampler_run.argtypes = [vp, C.c_int, dp, dp]
-    L.mp_sampler_set_whole_step.argtypes = [vp, C.c_int]
-    L.mp_sampler_get_state.argtypes = [vp, dp, dp, i64p, i64p]
-    L.mp_sampler_set_temperatures.argtypes = [vp, C.c_int, dp]
-    L.mp_sampler_get_swaps.argtypes = [vp, i64p]
-    L.mp_sampler_set_moves.argtypes = [vp, C.c_int, ip, dp, dp]
-    L.mp_optimizer_create.restype = vp
-    L.mp_optimizer_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_uint64, C.c_int, C.c_double, C.c_double, C.c_double,
-                                      C.c_double, C.c_double, dp, dp, C.c_int]
-    L.mp_optimizer_set_population.argtypes = [vp, dp]
-    L.mp_optimizer_run.argtypes = [vp, C.c_int, ip]
-    L.mp_optimizer_get_state.argtypes = [vp, dp, dp, ip, ip, ip, ip, i64p]
-    L.mp_optimizer_destroy.argtypes = [vp]
-    L.mp_nested_create.restype = vp
-    L.mp_nested_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_uint64, C.c_int, C.c_double, C.c_double, C.c_double,
-                                   dp, dp, C.c_int]
-    L.mp_nested_set_live.argtypes = [vp, dp]
-    L.mp_nested_run.argtypes = [vp, C.c_int, ip]
-    L.mp_nested_get_dead.argtypes = [vp, C.c_int, C.c_int64, dp, dp, ip, i64p]
-    L.mp_nested_get_state.argtypes = [vp, dp, dp, ip, ip, ip, ip, dp, dp, i64p, i64p, i64p]
-    L.mp_nested_destroy.argtypes = [vp]
-    L.mp_nested_set_slice.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int]
-    L.mp_nested_get_slice_stats.argtypes = [vp, i64p, i64p, i64p]
-    L.mp_last_mean_sweeps.argtypes = [vp]
-    L.mp_last_mean_sweeps.restype = C.c_double
-    L.mp_last_mean_tiles.argtypes = [vp]
-    L.mp_last_mean_tiles.restype = C.c_double
-    L.mp_sweep_tol.argtypes = [vp]
-    L.mp_sweep_tol.restype = C.c_double
-    L.mp_n_simd.argtypes = [vp]
-    L.mp_get_policy.argtypes = [vp, dp, C.c_int]
-    L.mp_get_policy.restype = C.c_int
-    L.mp_last_sweeps.argtypes = [vp, ip, C.c_int]
-    L.mp_last_sweeps.restype = C.c_int
-    L.mp_last_tiles.argtypes = [vp, ip, C.c_int]
-    L.mp_last_tiles.restype = C.c_int
-    L.mp_tile_log.argtypes = [vp, C.c_int]
-    L.mp_tile_log.restype = C.c_int
-    L.mp_last_tile_log.argtypes = [vp, C.c_int, ip, C.c_int]
-    L.mp_last_tile_log.restype = C.c_int
-    L.mp_sampler_get_bad.argtypes = [vp, C.c_int64, dp, C.c_int, i64p, i64p]
-    L.mp_sampler_n_slots.argtypes = [vp]
-    L.mp_sampler_row_doubles.argtypes = [vp]
-    L.mp_sampler_halfstep_shard.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
-    L.mp_sampler_halfstep_apply.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-    L.mp_sampler_state_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-    L.mp_sampler_step_blocks.argtypes = [vp]
-    L.mp_sampler_step_row_doubles.argtypes = [vp]
-    L.mp_sampler_step_shard.argtypes = [vp, C.c_int, C.c_int, vp, vp]
-    L.mp_sampler_step_apply.argtypes = [vp, vp, vp, vp, vp]
-    for name in ("mp_destroy", "mp_set_dataset", "mp_set_prior", "mp_lnprob_batch", "mp_lnprob_batch_dev",
-                 "mp_model_lc", "mp_model_band", "mp_rhs_batch", "mp_synchronize", "mp_device", "mp_n_grid", "mp_sampler_destroy",
-                 "mp_sampler_set_positions", "mp_sampler_run", "mp_sampler_set_whole_step", "mp_sampler_get_state", "mp_sampler_get_bad",
-                 "mp_sampler_n_slots", "mp_sampler_row_doubles", "mp_sampler_halfstep_shard",
-                 "mp_sampler_halfstep_apply", "mp_sampler_step_blocks", "mp_sampler_step_row_doubles",
-                 "mp_sampler_step_shard", "mp_sampler_step_apply", "mp_sampler_state_ptrs", "mp_n_simd",
-                 "mp_sampler_set_temperatures", "mp_sampler_get_swaps", "mp_optimizer_set_population", "mp_optimizer_run",
-                 "mp_optimizer_get_state", "mp_optimizer_destroy", "mp_nested_set_live", "mp_nested_run", "mp_nested_get_dead",
-                 "mp_nested_get_state", "mp_nested_destroy", "mp_nested_set_slice", "mp_nested_get_slice_stats"):
-        getattr(L, name).restype = C.c_int
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = res, args
     _lib = L
     return L
 
@@ -301,6 +270,11 @@ def band_rows(pars, ndim=None):
     return p
 
 
+def ptr(a):
+    """Typed pointer to the buffer of ndarray a (double *, int32_t *, int64_t * ... by its dtype)."""
+    return a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+
+
 def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
@@ -309,7 +283,64 @@ def _iptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
-class Handle:
+def read_back(fn, obj, spec, *lead):
+    """fn(obj, *lead, out...) of an ABI getter, checked: one output per (key, shape, dtype) of spec in argument order, a new
+    array of that shape and dtype (shape (): a scalar), or NULL where shape is None.  Returns {key: array} of the non-NULL ones."""
+    out = {k: np.empty(shape, dtype) for k, shape, dtype in spec if shape is not None}
+    check(fn(obj, *lead, *(ptr(out[k]) if k in out else None for k, _, _ in spec)), fn.__name__)
+    return out
+
+
+def band_result(handle, rows, q, names):
+    """{"t": grid, name: (nq, n_grid) per component, "n_used": rows that entered} of handle.model_band(rows, q, names)."""
+    band, _, used = handle.model_band(rows, q, names)
+    out = {"t": handle.tgrid.copy()}
+    out.update({c: band[k] for k, c in enumerate(names)})
+    out["n_used"] = used
+    return out
+
+
+class _Owner:
+    """close() on `with`-exit and when garbage-collected."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        if sys is None or sys.is_finalizing():      # interpreter shutdown: the HIP runtime may already be gone; the OS reclaims the rest
+            return
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class Driver(_Owner):
+    """Owns one device-resident driver object (mp_sampler, mp_optimizer, mp_nested) of `handle`: `name`_create(handle,
+    *args), freed once by `name`_destroy.  Passed to the ABI as its pointer (NULL once closed); holds the handle, so the
+    handle outlives it."""
+
+    def __init__(self, name, handle, *args):
+        L = lib()
+        self.handle, self._destroy = handle, getattr(L, name + "_destroy")
+        self.ptr = getattr(L, name + "_create")(handle._h, *args)
+        if not self.ptr:
+            raise MagpropAmdError(f"{name}_create failed: " + last_error())
+
+    @property
+    def _as_parameter_(self):
+        return self.ptr
+
+    def close(self):
+        if getattr(self, "ptr", None):
+            self._destroy(self.ptr)
+            self.ptr = None
+
+
+class Handle(_Owner):
     """Owns one mp_handle: a model configuration + time grid bound to one GPU."""
 
     def __init__(self, cfg, tgrid, device=-1):
@@ -334,14 +365,6 @@ class Handle:
         if getattr(self, "_h", None):
             self._L.mp_destroy(self._h)
             self._h = None
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():      # interpreter shutdown: the HIP runtime may already be gone; the OS reclaims the rest
-            return
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     @property
     def device(self):

@@ -1,4 +1,5 @@
-"""Handle / dataset caches shared by the reference-shaped front ends (funcs, mcmc_eqns, synth, LogProb)."""
+"""Handle / dataset caches shared by the reference-shaped front ends (funcs, mcmc_eqns, synth), and the model setup of the
+front ends that own a handle (LogProb, EnsembleSampler, differential_evolution, NestedSampler)."""
 import contextlib
 import hashlib
 import threading
@@ -20,6 +21,41 @@ def grid(GRBtype=None):
     if GRBtype is None or GRBtype == "L":
         return np.logspace(0.0, 6.0, num=10001, base=10.0)
     raise ValueError("Please provide a valid value for GRBtype.\nOptions are: L, S, or None.")
+
+
+def prior_box(variant, ndim, strict=False):
+    """(prior lower, prior upper, log mask) in sampler coordinates of model variant "synth" (its 6-parameter box) or "lib"
+    (mcmc_eqns' default limits for ndim parameters); strict: refuse an ndim the variant does not have.  Touches no device."""
+    if variant == "synth":
+        from . import synth
+        if strict and ndim != 6:
+            raise ValueError("the synth variant has 6 parameters")
+        return synth.PRIOR_LOWER.copy(), synth.PRIOR_UPPER.copy(), synth.LOG_MASK
+    if variant == "lib":
+        from . import mcmc_eqns
+        if strict and not 6 <= ndim <= 9:
+            raise ValueError("the lib variant has 6 to 9 parameters")
+        return (*mcmc_eqns._bounds(ndim), mcmc_eqns.LIB_LOG_MASK)
+    raise ValueError("variant must be 'synth' or 'lib'")
+
+
+def open_handle(variant, GRBtype, device, prior, datasets, sweep_tol=None, max_stride=None):
+    """A private Handle on the grid of GRBtype with the model configuration of `variant` (cfg_lib for "lib", else cfg_synth;
+    sweep_tol / max_stride None: _capi.DEFAULT_SWEEP_TOL / DEFAULT_MAX_STRIDE), the prior (lower, upper, log mask) set unless
+    it is None, and datasets [(x, y, yerr), ...] registered as ds_id 0, 1, ...  Closed again if any of that fails."""
+    kw = {} if sweep_tol is None else {"sweep_tol": float(sweep_tol)}
+    if max_stride is not None:
+        kw["max_stride"] = int(max_stride)
+    h = _capi.Handle((_capi.cfg_lib if variant == "lib" else _capi.cfg_synth)(**kw), grid(GRBtype), device)
+    try:
+        if prior is not None:
+            h.set_prior(*prior)
+        for k, (x, y, yerr) in enumerate(datasets):
+            h.set_dataset(k, x, y, yerr)
+    except BaseException:
+        h.close()
+        raise
+    return h
 
 
 def _as_f64(a):

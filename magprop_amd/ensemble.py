@@ -15,11 +15,10 @@ EnsembleSampler.log_evidence).  moves=... selects emcee's differential-evolution
 (magprop_amd.moves), proposed inside the same fused half-step kernels.
 """
 import ctypes as C
-import sys
 
 import numpy as np
 
-from . import _capi, engine, synth, tempering
+from . import _capi, engine, tempering
 from . import moves as _moves
 
 
@@ -48,24 +47,12 @@ class EnsembleSampler:
             move_tab = _moves.move_table(moves, int(ndim))
         self.nwalkers, self.ndim = int(nwalkers), int(ndim)
         self._L = _capi.lib()
-        tol_kw = {} if sweep_tol is None else {"sweep_tol": float(sweep_tol)}   # None: _capi.DEFAULT_SWEEP_TOL
-        if max_stride is not None:                                              # None: _capi.DEFAULT_MAX_STRIDE
-            tol_kw["max_stride"] = int(max_stride)
-        if variant == "synth":
-            cfg, lo, hi, mask = _capi.cfg_synth(**tol_kw), synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK
-        elif variant == "lib":
-            from . import mcmc_eqns
-            cfg = _capi.cfg_lib(**tol_kw)
-            lo, hi = mcmc_eqns._bounds(ndim)
-            mask = mcmc_eqns.LIB_LOG_MASK
-        else:
-            raise ValueError("variant must be 'synth' or 'lib'")
+        lo, hi, mask = engine.prior_box(variant, ndim)   # (no range check of ndim: target="gaussian" takes any)
         if not isinstance(lower, str):
             lo, hi = lower, upper
         if log_mask is not None:
             mask = log_mask
-        self.handle = _capi.Handle(cfg, engine.grid(GRBtype), device)
-        self.handle.set_prior(lo, hi, mask)
+        self.handle = engine.open_handle(variant, GRBtype, device, (lo, hi, mask), (), sweep_tol, max_stride)
         self._prior = (lo, hi)
         self._target = {"posterior": 0, "gaussian": 1}[target]
         if datasets is None:
@@ -79,23 +66,18 @@ class EnsembleSampler:
         self.ngroups = max(1, len(datasets))
         self.nensembles = self.ngroups * self.ntemps
         ids = np.repeat(np.arange(self.ngroups, dtype=np.int32), self.ntemps)   # the temperatures of a group share its dataset
-        self._s = self._L.mp_sampler_create(self.handle._h, self.nwalkers, self.nensembles, self.ndim,
-                                            ids.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint64(int(seed)),
-                                            C.c_double(a), self._target)
-        if not self._s:
-            raise _capi.MagpropAmdError("mp_sampler_create failed: " + _capi.last_error())
+        self._s = _capi.Driver("mp_sampler", self.handle, self.nwalkers, self.nensembles, self.ndim, _capi.ptr(ids), int(seed),
+                               float(a), self._target)
         if self.betas is not None:
-            _capi.check(self._L.mp_sampler_set_temperatures(self._s, self.ntemps, self.betas.ctypes.data_as(C.POINTER(C.c_double))),
-                        "mp_sampler_set_temperatures")
+            _capi.check(self._L.mp_sampler_set_temperatures(self._s, self.ntemps, _capi.ptr(self.betas)), "mp_sampler_set_temperatures")
         _capi.check(self._L.mp_sampler_set_whole_step(self._s, int(bool(whole_step))), "mp_sampler_set_whole_step")
         self.moves = None if moves is None else _moves.parse_moves(moves)
         if move_tab is not None:
             kinds = np.asarray(move_tab[0], dtype=np.int32)
             weights = np.asarray(move_tab[1], dtype=np.float64)
             params = np.ascontiguousarray(move_tab[2], dtype=np.float64)
-            _capi.check(self._L.mp_sampler_set_moves(self._s, int(kinds.size), kinds.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                     weights.ctypes.data_as(C.POINTER(C.c_double)),
-                                                     params.ctypes.data_as(C.POINTER(C.c_double))), "mp_sampler_set_moves")
+            _capi.check(self._L.mp_sampler_set_moves(self._s, int(kinds.size), _capi.ptr(kinds), _capi.ptr(weights), _capi.ptr(params)),
+                        "mp_sampler_set_moves")
         self.seed = int(seed)
         self._chain = None
         self._lnp = None
@@ -105,19 +87,11 @@ class EnsembleSampler:
         self._warned_bad = False
 
     def close(self):
+        """Free the sampler, then its handle (garbage collection does the same: the sampler holds the handle)."""
         if getattr(self, "_s", None):
-            self._L.mp_sampler_destroy(self._s)
-            self._s = None
+            self._s.close()
         if getattr(self, "handle", None):
             self.handle.close()
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
     @property
     def ntotal(self):
@@ -132,7 +106,7 @@ class EnsembleSampler:
         if store and nsteps > 0:
             chain = np.empty((nsteps, self.ntotal, self.ndim))
             lnp = np.empty((nsteps, self.ntotal))
-            cp, lp = chain.ctypes.data_as(C.POINTER(C.c_double)), lnp.ctypes.data_as(C.POINTER(C.c_double))
+            cp, lp = _capi.ptr(chain), _capi.ptr(lnp)
         _capi.check(self._L.mp_sampler_run(self._s, int(nsteps), cp, lp), "mp_sampler_run")
         if store and nsteps > 0:
             self._chain = chain if self._chain is None else np.concatenate([self._chain, chain])
@@ -155,8 +129,7 @@ class EnsembleSampler:
             want = min(want, int(max_rows))
         buf = np.empty((want, self.ndim))
         if want:
-            rows = self._L.mp_sampler_get_bad(self._s, int(first_row), buf.ctypes.data_as(C.POINTER(C.c_double)), want,
-                                              None, None)
+            rows = self._L.mp_sampler_get_bad(self._s, int(first_row), _capi.ptr(buf), want, None, None)
             if rows < 0:
                 _capi.check(rows, "mp_sampler_get_bad")
             buf = buf[:rows]
@@ -190,8 +163,7 @@ class EnsembleSampler:
         p = np.ascontiguousarray(pos, dtype=np.float64)
         if p.shape != (self.ntotal, self.ndim):
             raise ValueError(f"pos must have shape {(self.ntotal, self.ndim)}")
-        _capi.check(self._L.mp_sampler_set_positions(self._s, p.ctypes.data_as(C.POINTER(C.c_double))),
-                    "mp_sampler_set_positions")
+        _capi.check(self._L.mp_sampler_set_positions(self._s, _capi.ptr(p)), "mp_sampler_set_positions")
 
     def halfstep_shard(self, half, lo, hi, d_rows, stream=0):
         _capi.check(self._L.mp_sampler_halfstep_shard(self._s, int(half), int(lo), int(hi), C.c_void_p(d_rows or None),
@@ -224,15 +196,10 @@ class EnsembleSampler:
         self.iteration += 1
 
     def get_last_sample(self):
-        pos = np.empty((self.ntotal, self.ndim))
-        lnp = np.empty(self.ntotal)
-        acc = np.empty(self.ntotal, dtype=np.int64)
-        done = C.c_int64(0)
-        _capi.check(self._L.mp_sampler_get_state(self._s, pos.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 lnp.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 acc.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(done)),
-                    "mp_sampler_get_state")
-        return pos, lnp, acc
+        st = _capi.read_back(self._L.mp_sampler_get_state, self._s, [
+            ("pos", (self.ntotal, self.ndim), np.float64), ("lnp", self.ntotal, np.float64), ("acc", self.ntotal, np.int64),
+            ("done", (), np.int64)])
+        return st["pos"], st["lnp"], st["acc"]
 
     # ---- emcee-shaped views (synth_mcmc.py:188-226 indexes chain[i, j, k], lnprobability[i, j])
     def get_chain(self, temp=None):
@@ -261,11 +228,10 @@ class EnsembleSampler:
         times per step."""
         if self.betas is None:
             raise ValueError("swap_acceptance_fraction needs a tempered sampler (betas=...)")
-        acc = np.zeros((self.ngroups, self.ntemps - 1), dtype=np.int64)
-        _capi.check(self._L.mp_sampler_get_swaps(self._s, acc.ctypes.data_as(C.POINTER(C.c_int64))), "mp_sampler_get_swaps")
-        done = C.c_int64(0)
-        _capi.check(self._L.mp_sampler_get_state(self._s, None, None, None, C.byref(done)), "mp_sampler_get_state")
-        return acc / max(done.value * self.nwalkers, 1)
+        acc = _capi.read_back(self._L.mp_sampler_get_swaps, self._s, [("acc", (self.ngroups, self.ntemps - 1), np.int64)])["acc"]
+        done = _capi.read_back(self._L.mp_sampler_get_state, self._s, [("pos", None, None), ("lnp", None, None),
+                                                                       ("acc", None, None), ("done", (), np.int64)])["done"]
+        return acc / max(int(done) * self.nwalkers, 1)
 
     def log_evidence(self, discard=0, group=0, prior_draws=2 ** 20):
         """(lnZ, dlnZ) of group `group`'s dataset, the prior normalised over its box, from the stored chain of a tempered run:
@@ -319,11 +285,7 @@ class EnsembleSampler:
         # (tempered: the beta = 1 walkers of group `ensemble`)
         rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
                               discard, thin, ensemble)
-        band, _, used = self.handle.model_band(rows, qa, names)
-        out = {"t": self.handle.tgrid.copy()}
-        out.update({c: band[k] for k, c in enumerate(names)})
-        out["n_used"] = used
-        return out
+        return _capi.band_result(self.handle, rows, qa, names)
 
     def get_autocorr_time(self, c=5.0, tol=50, quiet=False):
         """emcee's default (quiet=False) raises when the chain is shorter than tol autocorrelation times; the

@@ -8,7 +8,7 @@ import threading
 
 import numpy as np
 
-from . import _capi, engine, synth
+from . import _capi, engine
 
 
 class LogProb:
@@ -17,29 +17,15 @@ class LogProb:
         """sweep_tol: Newton-sweep tolerance of the time-parallel solver (0 = the library default,
         include/magprop_amd.h MP_SWEEP_TOL_DEFAULT).  max_stride: grid intervals one step of the solver may span (1, 2, 4, 8;
         0 = the library default 8, MP_MAX_STRIDE_DEFAULT; 1 = every grid interval is a step)."""
-        tol_kw = {} if sweep_tol is None else {"sweep_tol": float(sweep_tol)}   # None: _capi.DEFAULT_SWEEP_TOL
-        if max_stride is not None:                                              # None: _capi.DEFAULT_MAX_STRIDE
-            tol_kw["max_stride"] = int(max_stride)
-        if variant == "synth":
-            cfg = _capi.cfg_synth(**tol_kw)
-            lo, hi, mask = synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK
-        elif variant == "lib":
-            from . import mcmc_eqns
-            cfg = _capi.cfg_lib(**tol_kw)
-            lo, hi = mcmc_eqns._bounds(6)
-            mask = mcmc_eqns.LIB_LOG_MASK
-        else:
-            raise ValueError("variant must be 'synth' or 'lib'")
+        lo, hi, mask = engine.prior_box(variant, 6)
         if not isinstance(lower, str):
             lo, hi = lower, upper
         if log_mask is not None:
             mask = log_mask
         # a private handle: the prior and datasets of this object are never swapped out by other callers
-        self.handle = _capi.Handle(cfg, engine.grid(GRBtype), device)
-        self.handle.set_prior(lo, hi, mask)
-        self.n_datasets = 0
+        self.handle = engine.open_handle(variant, GRBtype, device, (lo, hi, mask), [(x, y, yerr)], sweep_tol, max_stride)
+        self.n_datasets = 1
         self._lock = threading.Lock()     # host-buffer calls from several Python threads (ctypes drops the GIL)
-        self.add_dataset(x, y, yerr)
         self.fbad = fbad
 
     def add_dataset(self, x, y, yerr):

@@ -9,14 +9,13 @@ The prior is uniform over a box in sampler coordinates, as for ``EnsembleSampler
 uniform box draws with a finite lnprob, so the run integrates over the region where the model succeeds and
 ln Z = ln Z_ns + ln f_valid (``tempering.validity_term``).
 """
-import ctypes as C
 import math
 import warnings
 
 import numpy as np
 
 from . import _capi, engine, tempering
-from .optimize import OptimizeResult, _variant_box
+from .optimize import OptimizeResult
 
 TARGETS = {"posterior": 0, "gaussian": 1}
 SAMPLES = ("rwalk", "slice")
@@ -118,7 +117,7 @@ def _check_args(x, datasets, nlive, nbatch, walks, variant, ndim, bounds, n_runs
         plo = phi = mask = None
         n_ds = 1
     else:
-        plo, phi, mask = _variant_box(variant, ndim)
+        plo, phi, mask = engine.prior_box(variant, ndim, strict=True)
         if bounds is None:
             b = np.stack([plo, phi], axis=1)
         else:
@@ -196,12 +195,8 @@ class NestedSampler:
     def _open(self):
         if self.handle is not None:
             return
-        cfg = _capi.cfg_lib() if self.variant == "lib" else _capi.cfg_synth()
-        self.handle = _capi.Handle(cfg, engine.grid(self.GRBtype), self.device)
-        if self.target == "posterior":
-            self.handle.set_prior(*self._prior)
-            for k, (dx, dy, de) in enumerate(self.datasets):
-                self.handle.set_dataset(k, dx, dy, de)
+        self.handle = engine.open_handle(self.variant, self.GRBtype, self.device,
+                                         self._prior if self.target == "posterior" else None, self.datasets)
 
     def close(self):
         if self.handle is not None:
@@ -249,24 +244,17 @@ class NestedSampler:
         self._open()
         live0, draws = self.initial_live()
         L = _capi.lib()
-        dp = C.POINTER(C.c_double)
-        ns = L.mp_nested_create(self.handle._h, self.nlive, self.nbatch, self.n_runs, self.ndim,
-                                self.run_ds.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint64(self.seed), self.walks, self.g0,
-                                self.sigma, float(dlogz), self.lower.ctypes.data_as(dp), self.upper.ctypes.data_as(dp),
-                                TARGETS[self.target])
-        if not ns:
-            raise _capi.MagpropAmdError("mp_nested_create failed: " + _capi.last_error())
-        try:
+        with _capi.Driver("mp_nested", self.handle, self.nlive, self.nbatch, self.n_runs, self.ndim, _capi.ptr(self.run_ds),
+                          self.seed, self.walks, self.g0, self.sigma, float(dlogz), _capi.ptr(self.lower), _capi.ptr(self.upper),
+                          TARGETS[self.target]) as ns:
             if self.slices:
                 _capi.check(L.mp_nested_set_slice(ns, self.slices, self.slice_mu, self.max_steps_out, self.max_shrink),
                             "mp_nested_set_slice")
-            _capi.check(L.mp_nested_set_live(ns, np.ascontiguousarray(live0).ctypes.data_as(dp)), "mp_nested_set_live")
+            _capi.check(L.mp_nested_set_live(ns, _capi.ptr(np.ascontiguousarray(live0))), "mp_nested_set_live")
             _capi.check(L.mp_nested_run(ns, 2 ** 31 - 1 if maxiter is None else int(maxiter), None), "mp_nested_run")
             st = get_state(L, ns, self.n_runs, self.nlive, self.ndim)
             st.update(get_slice_stats(L, ns, self.n_runs))
             dead = [get_dead(L, ns, r, self.ndim) for r in range(self.n_runs)]
-        finally:
-            L.mp_nested_destroy(ns)
         out = []
         for r in range(self.n_runs):
             lnf, dlnf = tempering.validity_term(self.nlive, draws[r]) if self.target == "posterior" else (0.0, 0.0)
@@ -319,43 +307,28 @@ class NestedSampler:
         rows = self.resample_equal(run)
         if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
             rows = rows[np.linspace(0, rows.shape[0] - 1, _capi.BAND_MAX_SAMPLES).astype(int)]
-        band, _, used = self.handle.model_band(rows, qa, names)
-        out = {"t": self.handle.tgrid.copy()}
-        out.update({c: band[k] for k, c in enumerate(names)})
-        out["n_used"] = used
-        return out
+        return _capi.band_result(self.handle, rows, qa, names)
 
 
 def get_state(L, ns, n_runs, nlive, ndim):
     """mp_nested_get_state as arrays: live (n_runs, nlive, ndim), lnl / status / acc (n_runs, nlive), per run nit, stopped, lnx,
     lnz, ncall, nacc, nzero."""
-    st = {"live": np.empty((n_runs, nlive, ndim)), "lnl": np.empty((n_runs, nlive)), "status": np.empty((n_runs, nlive), dtype=np.int32),
-          "acc": np.empty((n_runs, nlive), dtype=np.int32), "nit": np.empty(n_runs, dtype=np.int32),
-          "stopped": np.empty(n_runs, dtype=np.int32), "lnx": np.empty(n_runs), "lnz": np.empty(n_runs),
-          "ncall": np.empty(n_runs, dtype=np.int64), "nacc": np.empty(n_runs, dtype=np.int64), "nzero": np.empty(n_runs, dtype=np.int64)}
-    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-    _capi.check(L.mp_nested_get_state(ns, st["live"].ctypes.data_as(dp), st["lnl"].ctypes.data_as(dp), st["status"].ctypes.data_as(ip),
-                                      st["acc"].ctypes.data_as(ip), st["nit"].ctypes.data_as(ip), st["stopped"].ctypes.data_as(ip),
-                                      st["lnx"].ctypes.data_as(dp), st["lnz"].ctypes.data_as(dp), st["ncall"].ctypes.data_as(lp),
-                                      st["nacc"].ctypes.data_as(lp), st["nzero"].ctypes.data_as(lp)), "mp_nested_get_state")
-    return st
+    f8, i4, i8 = np.float64, np.int32, np.int64
+    return _capi.read_back(L.mp_nested_get_state, ns, [
+        ("live", (n_runs, nlive, ndim), f8), ("lnl", (n_runs, nlive), f8), ("status", (n_runs, nlive), i4),
+        ("acc", (n_runs, nlive), i4), ("nit", n_runs, i4), ("stopped", n_runs, i4), ("lnx", n_runs, f8), ("lnz", n_runs, f8),
+        ("ncall", n_runs, i8), ("nacc", n_runs, i8), ("nzero", n_runs, i8)])
 
 
 def get_slice_stats(L, ns, n_runs):
     """mp_nested_get_slice_stats as arrays: per run nexpand, ncontract, nfail."""
-    st = {k: np.empty(n_runs, dtype=np.int64) for k in ("nexpand", "ncontract", "nfail")}
-    lp = C.POINTER(C.c_int64)
-    _capi.check(L.mp_nested_get_slice_stats(ns, st["nexpand"].ctypes.data_as(lp), st["ncontract"].ctypes.data_as(lp),
-                                            st["nfail"].ctypes.data_as(lp)), "mp_nested_get_slice_stats")
-    return st
+    return _capi.read_back(L.mp_nested_get_slice_stats, ns, [(k, n_runs, np.int64) for k in ("nexpand", "ncontract", "nfail")])
 
 
 def get_dead(L, ns, run, ndim):
     """mp_nested_get_dead of one run: (pars[n, ndim], lnl[n], live count[n])."""
-    n = C.c_int64(0)
-    _capi.check(L.mp_nested_get_dead(ns, int(run), 0, None, None, None, C.byref(n)), "mp_nested_get_dead")
-    pars, lnl, nl = np.empty((n.value, ndim)), np.empty(n.value), np.empty(n.value, dtype=np.int32)
-    _capi.check(L.mp_nested_get_dead(ns, int(run), n.value, pars.ctypes.data_as(C.POINTER(C.c_double)),
-                                     lnl.ctypes.data_as(C.POINTER(C.c_double)), nl.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)),
-                "mp_nested_get_dead")
-    return pars, lnl, nl
+    n = int(_capi.read_back(L.mp_nested_get_dead, ns, [("pars", None, None), ("lnl", None, None), ("n_live", None, None),
+                                                        ("n", (), np.int64)], int(run), 0)["n"])
+    d = _capi.read_back(L.mp_nested_get_dead, ns, [("pars", (n, ndim), np.float64), ("lnl", n, np.float64), ("n_live", n, np.int32),
+                                                   ("n", (), np.int64)], int(run), n)
+    return d["pars"], d["lnl"], d["n_live"]

@@ -5,11 +5,9 @@ keeps the better of trial and member (include/magprop_amd.h mp_optimizer_*); the
 between chunks of generations.  ``initial_ball`` turns a result into the starting walkers of ``EnsembleSampler.run_mcmc``, the
 reference's ``p0 + 1e-4 randn`` (code/synthetic_datasets/synth_mcmc.py).
 """
-import ctypes as C
-
 import numpy as np
 
-from . import _capi, engine, synth
+from . import _capi, engine
 
 STRATEGIES = {"best1bin": _capi.DE_BEST1BIN, "rand1bin": _capi.DE_RAND1BIN}
 
@@ -24,20 +22,6 @@ class OptimizeResult(dict):
             raise AttributeError(name) from exc
 
     __setattr__ = dict.__setitem__
-
-
-def _variant_box(variant, ndim):
-    if variant == "synth":
-        if ndim != 6:
-            raise ValueError("the synth variant has 6 parameters")
-        return synth.PRIOR_LOWER.copy(), synth.PRIOR_UPPER.copy(), synth.LOG_MASK
-    if variant == "lib":
-        from . import mcmc_eqns
-        if not 6 <= ndim <= 9:
-            raise ValueError("the lib variant has 6 to 9 parameters")
-        lo, hi = mcmc_eqns._bounds(ndim)
-        return lo, hi, mcmc_eqns.LIB_LOG_MASK
-    raise ValueError("variant must be 'synth' or 'lib'")
 
 
 def latin_hypercube(rng, n, lower, upper):
@@ -63,7 +47,7 @@ def _check_args(variant, bounds, strategy, maxiter, popsize, tol, atol, mutation
         if b.ndim != 2 or b.shape[1] != 2:
             raise ValueError("bounds must be a sequence of (lower, upper) pairs")
         ndim = b.shape[0]
-    plo, phi, mask = _variant_box(variant, ndim)
+    plo, phi, mask = engine.prior_box(variant, ndim, strict=True)
     lo, hi = (plo.copy(), phi.copy()) if bounds is None else (b[:, 0].copy(), b[:, 1].copy())
     if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
         raise ValueError("every bound must be finite with lower < upper")
@@ -133,28 +117,14 @@ def differential_evolution(x=None, y=None, yerr=None, variant="synth", GRBtype=N
     pop0 = np.ascontiguousarray(pop0, dtype=np.float64)
     if log_mask is not None:
         mask = log_mask
-    cfg = _capi.cfg_synth() if variant == "synth" else _capi.cfg_lib()
-    handle = _capi.Handle(cfg, engine.grid(GRBtype), device)
+    handle = engine.open_handle(variant, GRBtype, device, (plo, phi, mask), datasets)
     L = _capi.lib()
-    o = None
-    try:
-        handle.set_prior(plo, phi, mask)
-        for k, (dx, dy, de) in enumerate(datasets):
-            handle.set_dataset(k, dx, dy, de)
-        ids = np.repeat(np.arange(len(datasets), dtype=np.int32), int(n_starts))
-        dp = C.POINTER(C.c_double)
-        o = L.mp_optimizer_create(handle._h, members, n_pops, ndim, ids.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint64(int(seed)),
-                                  STRATEGIES[strategy], f_lo, f_hi, float(recombination), float(tol), float(atol),
-                                  lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), 0)
-        if not o:
-            raise _capi.MagpropAmdError("mp_optimizer_create failed: " + _capi.last_error())
-        _capi.check(L.mp_optimizer_set_population(o, pop0.ctypes.data_as(dp)), "mp_optimizer_set_population")
+    ids = np.repeat(np.arange(len(datasets), dtype=np.int32), int(n_starts))
+    with handle, _capi.Driver("mp_optimizer", handle, members, n_pops, ndim, _capi.ptr(ids), int(seed), STRATEGIES[strategy], f_lo,
+                              f_hi, float(recombination), float(tol), float(atol), _capi.ptr(lo), _capi.ptr(hi), 0) as o:
+        _capi.check(L.mp_optimizer_set_population(o, _capi.ptr(pop0)), "mp_optimizer_set_population")
         _capi.check(L.mp_optimizer_run(o, int(maxiter), None), "mp_optimizer_run")
         st = get_state(L, o, n_pops, members, ndim)
-    finally:
-        if o:
-            L.mp_optimizer_destroy(o)
-        handle.close()
     out = []
     for p in range(n_pops):
         b = int(st["best"][p])
@@ -171,15 +141,10 @@ def differential_evolution(x=None, y=None, yerr=None, variant="synth", GRBtype=N
 def get_state(L, o, n_pops, members, ndim):
     """mp_optimizer_get_state as arrays: pop (n_pops, members, ndim), lnprob and status (n_pops, members), best, nit,
     converged, nfev (n_pops)."""
-    st = {"pop": np.empty((n_pops, members, ndim)), "lnprob": np.empty((n_pops, members)),
-          "status": np.empty((n_pops, members), dtype=np.int32), "best": np.empty(n_pops, dtype=np.int32),
-          "nit": np.empty(n_pops, dtype=np.int32), "converged": np.empty(n_pops, dtype=np.int32), "nfev": np.empty(n_pops, dtype=np.int64)}
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    _capi.check(L.mp_optimizer_get_state(o, st["pop"].ctypes.data_as(dp), st["lnprob"].ctypes.data_as(dp),
-                                         st["status"].ctypes.data_as(ip), st["best"].ctypes.data_as(ip), st["nit"].ctypes.data_as(ip),
-                                         st["converged"].ctypes.data_as(ip), st["nfev"].ctypes.data_as(C.POINTER(C.c_int64))),
-                "mp_optimizer_get_state")
-    return st
+    return _capi.read_back(L.mp_optimizer_get_state, o, [
+        ("pop", (n_pops, members, ndim), np.float64), ("lnprob", (n_pops, members), np.float64),
+        ("status", (n_pops, members), np.int32), ("best", n_pops, np.int32), ("nit", n_pops, np.int32),
+        ("converged", n_pops, np.int32), ("nfev", n_pops, np.int64)])
 
 
 def initial_ball(res, nwalkers, scale=1.0e-4, seed=0):

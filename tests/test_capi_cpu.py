@@ -26,6 +26,59 @@ def test_library_exports_every_declared_symbol():
     assert L.mp_abi_version() == _capi.ABI_VERSION == 5
 
 
+def _prototypes():
+    """(return type, name, [argument types]) of every function of include/magprop_amd.h; a type is (base, pointer depth)."""
+    hdr = open(os.path.join(ROOT, "include", "magprop_amd.h")).read()
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", "", hdr, flags=re.S)
+    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
+
+    def ctype(decl, named):
+        words = [w for w in re.findall(r"[A-Za-z_]\w*", decl) if w != "const"]
+        return " ".join(words[:-1] if named else words), decl.count("*")
+
+    out = []
+    for ret, name, args in re.findall(r"([\w\s*]+?)\b(mp_\w+)\s*\(([^()]*)\)\s*;", hdr):
+        args = [] if args.strip() == "void" else [ctype(a, True) for a in args.split(",")]
+        out.append((ctype(ret, False), name, args))
+    return out
+
+
+_SCALAR = {"int": (ctypes.c_int, ctypes.c_int32), "uint32_t": (ctypes.c_uint32,), "int64_t": (ctypes.c_int64,),
+           "uint64_t": (ctypes.c_uint64,), "int32_t": (ctypes.c_int32,), "double": (ctypes.c_double,)}
+_OPAQUE = ("mp_handle", "mp_sampler", "mp_optimizer", "mp_nested")
+
+
+def _accepted(base, depth):
+    """ctypes types that pass a C type (base, pointer depth) correctly."""
+    P = ctypes.POINTER
+    if base in _OPAQUE and depth == 1:
+        return {ctypes.c_void_p}
+    if base == "mp_model_cfg" and depth == 1:
+        return {P(_capi.ModelCfg)}
+    if base == "char" and depth == 1:
+        return {ctypes.c_char_p}
+    if base == "void":
+        return [{None}, {ctypes.c_void_p}, {P(ctypes.c_void_p)}][depth]
+    ts = _SCALAR[base]
+    return [set(ts), {ctypes.c_void_p} | {P(t) for t in ts}, {P(ctypes.c_void_p)} | {P(P(t)) for t in ts}][depth]
+
+
+def test_signature_table_matches_the_header_prototypes():
+    """Every entry of _capi.SIGNATURES against its prototype: arity, every argument and the return type.  ctypes converts a
+    mismatched argument (an int where the library reads a double or an int64_t) without complaint."""
+    protos = _prototypes()
+    assert [name for _, name, _ in protos] == list(_capi.SIGNATURES) and len(protos) == len(_declared_functions())
+    for ret, name, args in protos:
+        restype, argtypes = _capi.SIGNATURES[name]
+        assert restype in _accepted(*ret), (name, ret, restype)
+        assert len(argtypes) == len(args), (name, args, argtypes)
+        for k, (a, t) in enumerate(zip(args, argtypes)):
+            assert t in _accepted(*a), (name, k, a, t)
+    L = _capi.lib()
+    for name, (restype, argtypes) in _capi.SIGNATURES.items():
+        assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == argtypes, name
+
+
 def test_python_mirror_follows_the_header_constants():
     """The constants and the order of mp_get_policy()'s vector in magprop_amd/_capi.py are those of include/magprop_amd.h."""
     hdr = open(os.path.join(ROOT, "include", "magprop_amd.h")).read()
