@@ -1,28 +1,19 @@
-// mp_capi.cpp — host side of the C ABI declared in include/magprop_amd.h.
+// mp_capi.cpp — host side of the C ABI declared in include/magprop_amd.h: the evaluator handle.
 //
 // Plain HIP runtime only (no torch, no hipBLAS): device buffers, one stream per handle, the
 // host-side digestion of observed light curves into the tile-bucketed layout the kernel reads,
-// and thin launch wrappers.  There is NO CPU fallback: without a HIP device mp_create() fails.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
+// thin launch wrappers, and the helpers that the resident drivers share (mp_host.h; the drivers
+// themselves: mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp).  There is NO CPU fallback:
+// without a HIP device mp_create() fails.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <numeric>
 #include <string>
-#include <thread>
-#include <vector>
 
 #include "mp_band.h"
-#include "mp_device.h"
+#include "mp_host.h"
 
-namespace {
-
-thread_local std::string g_err;
+static thread_local std::string g_err;
 
 int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -33,157 +24,6 @@ int fail(int code, const char *fmt, ...) {
     g_err = buf;
     return code;
 }
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(MP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DeviceScope {  // make the handle's device current for the duration of a call
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-struct HostDataset {
-    bool set = false;
-    std::vector<int32_t> g, tile_ptr;
-    std::vector<double> dx, idt, y, yerr;
-};
-
-// Device memory owned by its holder: freed on destruction (on the device current then: the destroy functions delete their object
-// inside a DeviceScope of its device), never copied.
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int ensure(size_t n) {
-        if (n <= cap) return MP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max<size_t>(n, 16);
-        HIP_TRY(hipMalloc((void **)&p, want * sizeof(T)));
-        cap = want;
-        return MP_OK;
-    }
-};
-
-// Allocates a driver's buffers (ensure) and points the fields of its launch arguments at them: bind(buffer, size, field).  The
-// first failure sticks in rc, and the allocations behind it are skipped.
-struct Binder {
-    int rc = MP_OK;
-    template <typename T, typename P>
-    void operator()(DevBuf<T> &b, size_t n, P *&field) {
-        if (!rc && !(rc = b.ensure(n))) field = b.p;
-    }
-};
-
-// Page-locked host staging area of the host-buffer entry points: copies to and from it are true asynchronous DMA
-// (pageable user buffers would be staged by the runtime copy by copy).
-struct PinnedBuf {
-    unsigned char *p = nullptr;
-    unsigned char *dev = nullptr;   // the same memory as the device sees it (mapped, coherent): kernels may read and write it in place
-    size_t cap = 0;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete;
-    PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-    int ensure(size_t n) {
-        if (n <= cap) return MP_OK;
-        if (p) (void)hipHostFree(p);
-        p = dev = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(n, 4096);
-        HIP_TRY(hipHostMalloc((void **)&p, want, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, p, 0));
-        cap = want;
-        return MP_OK;
-    }
-};
-
-// An event owned by its holder (created by it when first needed, destroyed with it)
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() = default;
-    Event(const Event &) = delete;
-    Event &operator=(const Event &) = delete;
-    ~Event() { if (e) (void)hipEventDestroy(e); }
-};
-
-// Device-to-host copies of the state of a driver: read_back(dst, src, n, dst2, src2, n2, ...) copies n elements of src to dst
-// for every triple whose dst is not NULL.
-int read_back() { return MP_OK; }
-template <typename T, typename... Rest>
-int read_back(T *dst, const T *src, size_t n, Rest... rest) {
-    if (dst) HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
-    return read_back(rest...);
-}
-
-}  // namespace
-
-struct mp_handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::vector<double> tgrid;
-    int n_tiles = 0;
-    HostDataset ds[MP_MAX_DATASETS];
-    mp::DevShared sh{};
-    // device copies of the shared data
-    DevBuf<double> d_wtab;
-    DevBuf<double> d_tgrid, d_obs_dx, d_obs_idt, d_obs_y, d_obs_yerr;
-    DevBuf<int32_t> d_obs_g, d_tile_ptr;
-    DevBuf<mp::DsDesc> d_ds;
-    // The packed observation arrays are an append-only arena: a new light curve goes behind the last one (obs_used /
-    // tp_used entries are live or stale), a replaced one leaves its old entries behind as garbage until the next rebuild.
-    size_t obs_used = 0, tp_used = 0;
-    std::vector<mp::DsDesc> desc;   // host mirror of d_ds
-    // workspace of the host-buffer entry points
-    DevBuf<double> w_pars, w_lnprob, w_curves;
-    DevBuf<double> w_band, w_band_out;   // mp_model_band: [components][n][n_grid] curves | [n_grid][n] transposed; [components][nq][n_grid]
-    DevBuf<int32_t> w_dsid, w_status, w_sweeps;
-    double last_mean_tiles = 0.0;
-    bool tile_log_on = false;
-    DevBuf<int32_t> w_tile_log;
-    std::vector<int32_t> last_tile_log;
-    PinnedBuf h_io;               // mp_lnprob_batch: [pars | ds_id] in, [lnprob | status | sweeps | tiles] out, read and written in place by the kernel
-    double last_mean_sweeps = 0.0;
-    std::vector<int32_t> last_sweeps, last_tiles;   // per walker, most recent host-buffer batch (diagnostic)
-    // Launch order of mixed-length batches (mp_kernels.hip order_kernel): a ring of index buffers, one per launch in flight.
-    // A slot is written by the launch that takes it and read by that launch's workgroups as they start; the launch that
-    // takes it kOrderRing launches later waits (stream-level, on the event recorded behind the earlier launch) for that
-    // launch to have finished -- launches fewer than kOrderRing apart share nothing.
-    static constexpr int kOrderRing = 8;
-    DevBuf<int32_t> order[kOrderRing];
-    Event order_done[kOrderRing];
-    unsigned order_next = 0;
-    // Threading / stream contract (include/magprop_amd.h): every entry point that takes a handle or a sampler holds
-    // `mu` for its duration.  Launches share nothing writable but their own outputs (round 4: no per-walker scratch rows),
-    // so launches of one handle on different streams may overlap freely.
-    std::recursive_mutex mu;
-    // Multi-device handle (mp_create_multi): one evaluator per listed device; this object then holds no device state of
-    // its own -- datasets and prior are forwarded to every evaluator, a host-buffer batch is dealt out in contiguous blocks.
-    std::vector<mp_handle *> sub;
-    int pend_n = 0;               // rows of the host-buffer batch between batch_begin and batch_end
-    size_t pend_in_bytes = 0;
-    double last_tot_sweeps = 0.0, last_tot_tiles = 0.0;   // over the walkers of the last batch that finished (status ok) ...
-    int last_cnt_ok = 0;                                  // ... and how many those were
-};
-
-namespace {
-using Lock = std::lock_guard<std::recursive_mutex>;
 
 // Launch the log-posterior kernel over a batch.  A batch that refers to light curves of more than 64 points next to short
 // ones and needs more than one round of the device's wave slots (two per SIMD) is evaluated longest light curves first.
@@ -209,7 +49,6 @@ int launch_lnprob_ordered(mp_handle *h, const mp::LaunchArgs &a_in, hipStream_t 
     if (slot >= 0) HIP_TRY(hipEventRecord(h->order_done[slot].e, st));
     return MP_OK;
 }
-}  // namespace
 
 static void publish_datasets(mp_handle *h) {
     int n_ds = 0, extra = 0;
@@ -281,30 +120,10 @@ static int upload_dataset(mp_handle *h, int d, bool replaced) {
 
 // ---------------------------------------------------------------- what the resident drivers share
 // (the ensemble sampler, the differential-evolution optimizer and the nested sampler: mp_sampler_*, mp_optimizer_*, mp_nested_*)
-
-// The checks of their create functions (fn), in the order they fail: a multi-device handle (`multi`: what the message says about
-// it), ndim (the posterior, target 0, needs 6 or more), the driver's own arguments (args(): MP_OK or the code of a failure), the
-// alternative dipole torque, and the dataset of every one of n_groups groups (`group` g: ds_id[g], dataset 0 without ds_id).
-// The caller holds the handle's lock.
-template <class Args>
-static int check_create(mp_handle *h, const char *fn, const char *multi, int ndim, int target, const char *group, int n_groups,
-                        const int32_t *ds_id, Args &&args) {
-    if (!h->sub.empty()) return fail(MP_ESTATE, "%s: %s", fn, multi);
-    if (ndim < 1 || ndim > MP_MAX_NDIM || (target == 0 && ndim < 6)) return fail(MP_EINVAL, "%s: bad ndim %d", fn, ndim);
-    const int rc = args();
-    if (rc) return rc;
-    if (target != 0) return MP_OK;
-    if (h->sh.cfg.dipole_torque != 0)
-        return fail(MP_ESTATE, "%s: the alternative dipole torque (cfg.dipole_torque = 1) is served by the curve kernels only", fn);
-    for (int g = 0; g < n_groups; ++g) {
-        const int d = ds_id ? ds_id[g] : 0;
-        if (d < 0 || d >= MP_MAX_DATASETS || !h->ds[d].set) return fail(MP_ESTATE, "%s: %s %d refers to unset dataset %d", fn, group, g, d);
-    }
-    return MP_OK;
-}
+// (declared in mp_host.h, next to the template check_create)
 
 // the bounds box of the optimizer and the nested sampler: finite, lower < upper in every coordinate
-static int check_box(const char *fn, int ndim, const double *lower, const double *upper) {
+int check_box(const char *fn, int ndim, const double *lower, const double *upper) {
     for (int d = 0; d < ndim; ++d)
         if (!(std::isfinite(lower[d]) && std::isfinite(upper[d]) && lower[d] < upper[d]))
             return fail(MP_EINVAL, "%s: bounds of coordinate %d are empty or not finite", fn, d);
@@ -312,7 +131,7 @@ static int check_box(const char *fn, int ndim, const double *lower, const double
 }
 
 // the dataset of every row, ds_id[g] (dataset 0 without ds_id) for the `rows` consecutive rows of group g, uploaded to dst
-static int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int rows) {
+int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int rows) {
     std::vector<int32_t> ds((size_t)n_groups * rows);
     for (int g = 0; g < n_groups; ++g) std::fill_n(ds.begin() + (size_t)g * rows, rows, ds_id ? ds_id[g] : 0);
     HIP_TRY(hipMemcpy(dst, ds.data(), ds.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -320,7 +139,7 @@ static int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int 
 }
 
 // *running = the groups whose flag (d_flags[n], read back behind the work on the handle's stream) is not 1 (converged, stopped)
-static int groups_running(mp_handle *h, const int32_t *d_flags, int n, int *running) {
+int groups_running(mp_handle *h, const int32_t *d_flags, int n, int *running) {
     std::vector<int32_t> f((size_t)n);
     HIP_TRY(hipMemcpyAsync(f.data(), d_flags, f.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -948,883 +767,6 @@ int mp_synchronize(mp_handle *h) {
     DeviceScope scope(h->device);
     HIP_TRY(hipStreamSynchronize(h->stream));
     return MP_OK;
-}
-
-// ---------------------------------------------------------------- ensemble sampler (stretch move)
-struct mp_sampler {
-    mp_handle *h = nullptr;
-    int n_walkers = 0, n_ensembles = 0, n_total = 0, ndim = 0, target = 0;
-    uint64_t seed = 0;
-    double a = 2.0;
-    uint64_t steps_done = 0;
-    bool have_state = false;
-    DevBuf<double> d_pos, d_lnprob, d_chain, d_chain_lnp, d_bad, d_spec;
-    std::vector<int32_t> ens_ds;   // dataset of every ensemble
-    int whole_step = 1;   // mp_sampler_run: one launch per step where the ensemble is small enough (mp_sampler_set_whole_step)
-    DevBuf<int64_t> d_acc;
-    DevBuf<int32_t> d_perm, d_dsid, d_status;
-    DevBuf<uint32_t> d_bad_count;
-    PinnedBuf h_perm;   // page-locked staging of the random splits: their upload overlaps the running half-steps
-    // walker-sharded driving (mp_sampler_halfstep_shard / _apply): splits of kWin steps at a time, double-buffered
-    static constexpr int kWin = 32;
-    DevBuf<int32_t> d_win[2];
-    PinnedBuf h_win[2];
-    Event win_copied[2];
-    int64_t win_id[2] = {-1, -1};
-    bool ext_stream_work = false;   // half-steps were enqueued on a caller's stream since the last device-wide wait
-    // failed proposals (the reference's fbad file): the device window d_bad is drained into this log
-    std::vector<double> bad_log;    // [rows][ndim]
-    int64_t n_bad = 0;              // exact count since creation (rows beyond the window between two drains are counted, not kept)
-    // parallel tempering (mp_sampler_set_temperatures): ensemble e runs at beta[e % n_temps]; 0 = untempered
-    int n_temps = 0;
-    DevBuf<double> d_beta;          // [n_ensembles]
-    DevBuf<int64_t> d_swaps;        // [n_ensembles / n_temps][n_temps - 1] accepted swaps
-    // proposal moves (mp_sampler_set_moves); empty: the stretch move with scale a
-    struct Move {
-        int32_t kind;
-        double p0, p1;              // stretch: a; DE: g0 (resolved), s = sigma sqrt(3); snooker: gamma_s; KDE: f (resolved)
-    };
-    std::vector<Move> moves;
-    std::vector<double> move_cum;   // cumulative weights, summed in order
-};
-
-// Move the device window of failed proposals into the host log and reset it.  The caller has made sure that no kernel
-// of this sampler is in flight.
-static int drain_bad(mp_sampler *s) {
-    uint32_t cnt = 0;
-    HIP_TRY(hipMemcpy(&cnt, s->d_bad_count.p, sizeof cnt, hipMemcpyDeviceToHost));
-    if (cnt == 0) return MP_OK;
-    const size_t cap = s->d_bad.cap / (size_t)s->ndim, rows = std::min<size_t>(cnt, cap);
-    const size_t old = s->bad_log.size();
-    s->bad_log.resize(old + rows * (size_t)s->ndim);
-    HIP_TRY(hipMemcpy(s->bad_log.data() + old, s->d_bad.p, rows * s->ndim * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(s->d_bad_count.p, 0, sizeof(uint32_t)));
-    s->n_bad += (int64_t)cnt;
-    return MP_OK;
-}
-
-// random split of every ensemble for step `step` (emcee's randomize_split): Fisher-Yates, counter (step, ensemble, i, 'split')
-static void draw_split(const mp_sampler *s, uint64_t step64, int32_t *perm) {
-    const uint32_t step = (uint32_t)step64;
-    for (int e = 0; e < s->n_ensembles; ++e) {
-        int32_t *p = perm + (size_t)e * s->n_walkers;
-        std::iota(p, p + s->n_walkers, 0);
-        for (int i = s->n_walkers - 1; i > 0; --i) {
-            uint32_t r[4];
-            mp::philox4x32_10((uint32_t)s->seed, (uint32_t)(s->seed >> 32), step, (uint32_t)e, (uint32_t)i, 0x5117u, r);
-            const uint64_t r64 = ((uint64_t)r[0] << 32) | r[1];
-            std::swap(p[i], p[(size_t)(r64 % (uint64_t)(i + 1))]);
-        }
-    }
-}
-
-// splits of `count` consecutive steps into perm[count][n_total]; the steps are independent (counter-based generator), so
-// large ensembles are drawn by a few host threads (8 192 walkers: 0.4 ms per step on one core, more than a half-step of a
-// walker-sharded ensemble takes on the GPU)
-static void draw_splits(const mp_sampler *s, uint64_t step0, int count, int32_t *perm) {
-    const size_t nt = (size_t)s->n_total;
-    const int n_thr = (int)std::min<size_t>({(size_t)count, (size_t)4, (nt * (size_t)count) / 8192});
-    auto work = [&](int first, int stride) {
-        for (int i = first; i < count; i += stride) draw_split(s, step0 + (uint64_t)i, perm + (size_t)i * nt);
-    };
-    if (n_thr <= 1) { work(0, 1); return; }
-    std::vector<std::thread> pool;
-    for (int k = 1; k < n_thr; ++k) pool.emplace_back(work, k, n_thr);
-    work(0, n_thr);
-    for (auto &th : pool) th.join();
-}
-
-// the move of step `step` (an index into s->moves): r = Philox(seed; step, 3, 0, 0x30FE), the first m with u01(r0, r1) C_last < C_m
-static int draw_move(const mp_sampler *s, uint64_t step64) {
-    const int n = (int)s->moves.size();
-    if (n <= 1) return 0;
-    uint32_t r[4];
-    mp::philox4x32_10((uint32_t)s->seed, (uint32_t)(s->seed >> 32), (uint32_t)step64, 3u, 0u, 0x30FEu, r);
-    const double x = mp::u01(r[0], r[1]) * s->move_cum[(size_t)n - 1];
-    for (int m = 0; m < n - 1; ++m)
-        if (x < s->move_cum[(size_t)m]) return m;
-    return n - 1;
-}
-
-static mp::StretchArgs stretch_args(const mp_sampler *s, const int32_t *d_perm, uint64_t step, int half) {
-    mp::StretchArgs g{};
-    g.pos = s->d_pos.p; g.lnprob = s->d_lnprob.p; g.n_accepted = s->d_acc.p;
-    g.perm = d_perm;
-    g.ds_id = s->d_dsid.p;
-    g.n_walkers = s->n_walkers; g.n_half = s->n_walkers / 2; g.n_ensembles = s->n_ensembles;
-    g.n_total = s->n_total; g.ndim = s->ndim; g.half = half; g.target = s->target;
-    g.step = (uint32_t)step; g.seed = s->seed; g.a = s->a;
-    g.bad_log = s->d_bad.p; g.bad_count = s->d_bad_count.p; g.bad_cap = (uint32_t)(s->d_bad.cap / (size_t)std::max(s->ndim, 1));
-    g.beta = s->n_temps ? s->d_beta.p : nullptr;
-    // Ensembles on light curves of different lengths (BASELINE config 5: 50 / 410 / 8 / 1 944 points): the half-step launch
-    // starts the ensemble with the longest light curve first, so that its waves do not begin last and finish alone.  The order
-    // is a function of the datasets only, so every rank of a walker-sharded run derives the same one.
-    if (s->target == 0 && s->n_ensembles > 1 && s->n_ensembles <= 16) {
-        int idx[16];
-        std::iota(idx, idx + s->n_ensembles, 0);
-        std::stable_sort(idx, idx + s->n_ensembles, [&](int x, int y) {
-            return s->h->ds[s->ens_ds[(size_t)x]].g.size() > s->h->ds[s->ens_ds[(size_t)y]].g.size();
-        });
-        bool identity = true;
-        for (int e = 0; e < s->n_ensembles; ++e) identity = identity && idx[e] == e;
-        if (!identity)
-            for (int e = 0; e < s->n_ensembles; ++e) g.ens_order |= (uint64_t)idx[e] << (4 * e);
-    }
-    return g;
-}
-
-mp_sampler *mp_sampler_create(mp_handle *h, int n_walkers, int n_ensembles, int ndim, const int32_t *ens_ds_id,
-                              uint64_t seed, double a, int target) {
-    if (!h) { fail(MP_EINVAL, "mp_sampler_create: NULL handle"); return nullptr; }
-    Lock lock(h->mu);
-    const int rc = check_create(h, "mp_sampler_create", "the device-resident sampler lives on ONE device (walker sharding across devices: magprop_amd/distributed.py)",
-                                ndim, target, "ensemble", n_ensembles, ens_ds_id, [&] {
-        if (n_walkers < 2 || (n_walkers & 1)) return fail(MP_EINVAL, "mp_sampler_create: n_walkers must be even and >= 2");
-        if (n_ensembles < 1) return fail(MP_EINVAL, "mp_sampler_create: bad n_ensembles");
-        if (!(a > 1.0)) return fail(MP_EINVAL, "mp_sampler_create: stretch scale a must exceed 1");
-        return MP_OK;
-    });
-    if (rc) return nullptr;
-    mp_sampler *s = new mp_sampler();
-    s->h = h; s->n_walkers = n_walkers; s->n_ensembles = n_ensembles; s->n_total = n_walkers * n_ensembles;
-    s->ndim = ndim; s->target = target; s->seed = seed; s->a = a;
-    DeviceScope scope(h->device);
-    const size_t nt = (size_t)s->n_total;
-    for (int e = 0; e < n_ensembles; ++e) s->ens_ds.push_back(ens_ds_id ? ens_ds_id[e] : 0);
-    constexpr size_t kBadRows = MP_BAD_WINDOW;   // device window of failed proposals between two drains (drain_bad)
-    if (s->d_pos.ensure(nt * ndim) || s->d_lnprob.ensure(nt) || s->d_acc.ensure(nt) || s->d_dsid.ensure(nt) ||
-        s->d_status.ensure(nt) || s->d_bad.ensure(kBadRows * ndim) || s->d_bad_count.ensure(1) ||
-        upload_ds_rows(s->d_dsid.p, ens_ds_id, n_ensembles, n_walkers) ||
-        hipMemset(s->d_acc.p, 0, nt * sizeof(int64_t)) != hipSuccess ||
-        hipMemset(s->d_bad_count.p, 0, sizeof(uint32_t)) != hipSuccess ||
-        hipEventCreateWithFlags(&s->win_copied[0].e, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s->win_copied[1].e, hipEventDisableTiming) != hipSuccess) {
-        fail(MP_EHIP, "mp_sampler_create: device allocation failed");
-        mp_sampler_destroy(s);
-        return nullptr;
-    }
-    return s;
-}
-
-int mp_sampler_destroy(mp_sampler *s) {
-    if (!s) return MP_OK;
-    Lock lock(s->h->mu);
-    DeviceScope scope(s->h->device);
-    (void)hipDeviceSynchronize();
-    delete s;
-    return MP_OK;
-}
-
-int mp_sampler_set_temperatures(mp_sampler *s, int n_temps, const double *betas) {
-    if (!s || !betas) return fail(MP_EINVAL, "mp_sampler_set_temperatures: NULL argument");
-    Lock lock(s->h->mu);
-    if (s->have_state) return fail(MP_ESTATE, "mp_sampler_set_temperatures: call it before the first mp_sampler_set_positions");
-    if (n_temps < 2) return fail(MP_EINVAL, "mp_sampler_set_temperatures: a ladder needs at least 2 temperatures, got %d", n_temps);
-    if (s->n_ensembles % n_temps) return fail(MP_EINVAL, "mp_sampler_set_temperatures: %d ensembles are not groups of %d temperatures", s->n_ensembles, n_temps);
-    if (betas[0] != 1.0) return fail(MP_EINVAL, "mp_sampler_set_temperatures: betas[0] must be 1, got %g", betas[0]);
-    for (int t = 1; t < n_temps; ++t)
-        // (beta = 0 is refused: failed models have lnprob = -inf, and 0 x -inf is NaN)
-        if (!std::isfinite(betas[t]) || !(betas[t] > 0.0) || !(betas[t] < betas[t - 1]))
-            return fail(MP_EINVAL, "mp_sampler_set_temperatures: betas must be finite, > 0 and strictly decreasing (betas[%d] = %g)", t, betas[t]);
-    for (int e = 0; e < s->n_ensembles; ++e)
-        if (s->ens_ds[(size_t)e] != s->ens_ds[(size_t)(e - e % n_temps)])
-            return fail(MP_EINVAL, "mp_sampler_set_temperatures: ensembles %d and %d of one group have different datasets", e - e % n_temps, e);
-    DeviceScope scope(s->h->device);
-    std::vector<double> b((size_t)s->n_ensembles);
-    for (int e = 0; e < s->n_ensembles; ++e) b[(size_t)e] = betas[e % n_temps];
-    const size_t n_pairs = (size_t)(s->n_ensembles / n_temps) * (size_t)(n_temps - 1);
-    int rc;
-    if ((rc = s->d_beta.ensure(b.size())) || (rc = s->d_swaps.ensure(n_pairs))) return rc;
-    HIP_TRY(hipMemcpy(s->d_beta.p, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(s->d_swaps.p, 0, n_pairs * sizeof(int64_t)));
-    s->n_temps = n_temps;
-    return MP_OK;
-}
-
-int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const double *weights, const double *params) {
-    if (!s) return fail(MP_EINVAL, "mp_sampler_set_moves: NULL sampler");
-    if (n_moves < 0 || n_moves > MP_MAX_MOVES) return fail(MP_EINVAL, "mp_sampler_set_moves: n_moves must be in [0, %d], got %d", MP_MAX_MOVES, n_moves);
-    if (n_moves > 0 && (!kinds || !weights || !params)) return fail(MP_EINVAL, "mp_sampler_set_moves: NULL argument");
-    const int n_half = s->n_walkers / 2;
-    std::vector<mp_sampler::Move> mv;
-    std::vector<double> cum;
-    double c = 0.0;
-    for (int m = 0; m < n_moves; ++m) {
-        const double w = weights[m], p0 = params[2 * m], p1 = params[2 * m + 1];
-        if (!std::isfinite(w) || !(w > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: weight %d must be finite and > 0, got %g", m, w);
-        mp_sampler::Move x{kinds[m], 0.0, 0.0};
-        switch (kinds[m]) {
-        case MP_MOVE_STRETCH:
-            if (!std::isfinite(p0) || !(p0 > 1.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: stretch scale a must be finite and > 1, got %g", p0);
-            x.p0 = p0;
-            break;
-        case MP_MOVE_DE:
-            if (!std::isfinite(p0) || p0 < 0.0) return fail(MP_EINVAL, "mp_sampler_set_moves: DE g0 must be finite and >= 0 (0: 2.38/sqrt(2 ndim)), got %g", p0);
-            if (!(p1 >= 0.0) || !(p1 * std::sqrt(3.0) < 1.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: DE sigma must be in [0, 1/sqrt(3)), got %g", p1);
-            if (n_half < 2) return fail(MP_EINVAL, "mp_sampler_set_moves: the DE move needs n_walkers >= 4 (two partners in the other half)");
-            x.p0 = p0 > 0.0 ? p0 : 2.38 / std::sqrt(2.0 * s->ndim);
-            x.p1 = p1 * std::sqrt(3.0);
-            break;
-        case MP_MOVE_SNOOKER:
-            if (!std::isfinite(p0) || !(p0 > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: snooker gamma_s must be finite and > 0, got %g", p0);
-            if (n_half < 3) return fail(MP_EINVAL, "mp_sampler_set_moves: the snooker move needs n_walkers >= 6 (three partners in the other half)");
-            x.p0 = p0;
-            break;
-        case MP_MOVE_KDE: {
-            const int n_comp = s->n_walkers - n_half, d = s->ndim;
-            if (!(p0 == 0.0 || p0 == -1.0 || (std::isfinite(p0) && p0 > 0.0)))
-                return fail(MP_EINVAL, "mp_sampler_set_moves: KDE bandwidth must be 0 (Scott), -1 (Silverman) or a finite factor > 0, got %g", p0);
-            if (p1 != 0.0) return fail(MP_EINVAL, "mp_sampler_set_moves: KDE params[1] must be 0, got %g", p1);
-            if (n_comp < d + 1)
-                return fail(MP_EINVAL, "mp_sampler_set_moves: the KDE move needs n_walkers - n_walkers / 2 >= ndim + 1 (a full-rank covariance of the other half), got %d", n_comp);
-            // scipy.stats.gaussian_kde's scotts_factor / silverman_factor with neff = n_comp
-            x.p0 = p0 > 0.0 ? p0 : std::pow(p0 == 0.0 ? (double)n_comp : n_comp * (d + 2.0) / 4.0, -1.0 / (d + 4));
-            break;
-        }
-        default:
-            return fail(MP_EINVAL, "mp_sampler_set_moves: unknown move kind %d", (int)kinds[m]);
-        }
-        mv.push_back(x);
-        c += w;
-        cum.push_back(c);
-    }
-    Lock lock(s->h->mu);
-    s->moves = std::move(mv);
-    s->move_cum = std::move(cum);
-    return MP_OK;
-}
-
-int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted) {
-    if (!s || !n_swaps_accepted) return fail(MP_EINVAL, "mp_sampler_get_swaps: NULL argument");
-    Lock lock(s->h->mu);
-    if (!s->n_temps) return fail(MP_ESTATE, "mp_sampler_get_swaps: the sampler is not tempered (mp_sampler_set_temperatures)");
-    DeviceScope scope(s->h->device);
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t n_pairs = (size_t)(s->n_ensembles / s->n_temps) * (size_t)(s->n_temps - 1);
-    HIP_TRY(hipMemcpy(n_swaps_accepted, s->d_swaps.p, n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return MP_OK;
-}
-
-int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
-    if (!s || !pos) return fail(MP_EINVAL, "mp_sampler_set_positions: NULL argument");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const size_t nt = (size_t)s->n_total;
-    for (size_t i = 0; i < nt * s->ndim; ++i)
-        if (!std::isfinite(pos[i])) return fail(MP_EINVAL, "mp_sampler_set_positions: non-finite coordinate");
-    HIP_TRY(hipDeviceSynchronize());   // the sharded entry points may have work in flight on a caller's stream
-    s->ext_stream_work = false;
-    HIP_TRY(hipMemcpyAsync(s->d_pos.p, pos, nt * s->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (s->target == 1) {
-        std::vector<double> lp(nt, 0.0);
-        for (size_t k = 0; k < nt; ++k)
-            for (int i = 0; i < s->ndim; ++i) lp[k] -= 0.5 * pos[k * s->ndim + i] * pos[k * s->ndim + i];
-        HIP_TRY(hipMemcpyAsync(s->d_lnprob.p, lp.data(), nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    } else {
-        mp::LaunchArgs a{};
-        a.pars = s->d_pos.p; a.ds_id = s->d_dsid.p; a.n = s->n_total; a.ndim = s->ndim; a.want_chi2 = 1;
-        a.lnprob = s->d_lnprob.p; a.status = s->d_status.p;
-        const int rc = launch_lnprob_ordered(h, a, h->stream);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    s->have_state = true;
-    return MP_OK;
-}
-
-// Enqueue step steps_done + row of mp_sampler_run on the handle's stream: split d_perm, chain row `row` of the device slab when
-// chain is set, move mv (nullptr: the stretch move of mp_sampler_create).  A whole step per launch (stretch_step_kernel and the
-// commit kernel) where `whole` and the move is the stretch move, else two half-step launches; then the swap sweep when tempered.
-static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_sampler::Move *mv, bool chain, bool whole) {
-    mp_handle *h = s->h;
-    mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done + (uint64_t)row, 0);
-    g.chain = chain ? s->d_chain.p : nullptr;
-    g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
-    g.chain_row = row;
-    if (mv) {
-        g.move = mv->kind;
-        if (mv->kind == MP_MOVE_STRETCH) g.a = mv->p0;
-        else if (mv->kind == MP_MOVE_DE) { g.de_g0 = mv->p0; g.de_s = mv->p1; }
-        else if (mv->kind == MP_MOVE_SNOOKER) g.gamma_s = mv->p0;
-        else g.kde_f = mv->p0;
-    }
-    int e;
-    if (whole && g.move == MP_MOVE_STRETCH) {
-        g.spec = s->d_spec.p;
-        e = mp::launch_stretch_step(h->sh, g, 3 * g.n_half * g.n_ensembles, h->stream);
-        if (!e) e = mp::launch_stretch_step_commit(g, h->stream);
-    } else {
-        e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
-        g.half = 1;
-        if (!e) e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
-    }
-    if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    return MP_OK;
-}
-
-int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnprob) {
-    if (!s || n_steps < 0) return fail(MP_EINVAL, "mp_sampler_run: bad argument");
-    if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_run: call mp_sampler_set_positions first");
-    if ((chain == nullptr) != (chain_lnprob == nullptr)) return fail(MP_EINVAL, "mp_sampler_run: chain and chain_lnprob go together");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const size_t nt = (size_t)s->n_total, row = nt * s->ndim;
-    // chunks of steps so that the device-resident chain slab stays below ~256 MB, the splits below ~64 MB, and the
-    // window of failed proposals (drained after every chunk) overflows only if more than 1 in 32 proposals fails
-    const size_t perm_cap = std::max<size_t>(1, std::min<size_t>((size_t)16 << 20, (size_t)32 * MP_BAD_WINDOW) / nt);
-    const int chunk_max = (int)std::min<size_t>(
-        (size_t)std::max(n_steps, 1),
-        chain ? std::max<size_t>(1, std::min<size_t>(perm_cap, (256u << 20) / (row * sizeof(double)))) : perm_cap);
-    constexpr int kSub = 8;   // steps per batch of splits: the host draws the next batch while the GPU runs this one
-    int rc;
-    // A whole step per launch (mp_kernels.hip stretch_step_kernel: 3 n/2 evaluations, a third of them speculative) while
-    // that beats two half-step launches (mp_device.h stretch_whole_step_fits); larger ensembles fill the device with one half-step
-    // at a time.
-    const int n_slots = (s->n_walkers / 2) * s->n_ensembles;
-    const bool whole = s->whole_step && mp::stretch_whole_step_fits(h->sh, 3 * (long long)n_slots);
-    if (whole && (rc = s->d_spec.ensure((size_t)3 * n_slots * (size_t)(s->ndim + mp::kSpecExtra)))) return rc;
-    if (s->ext_stream_work) {   // sharded half-steps on a caller's stream may still be updating the state
-        HIP_TRY(hipDeviceSynchronize());
-        s->ext_stream_work = false;
-    }
-    for (int done = 0; done < n_steps;) {
-        const int chunk = std::min(chunk_max, n_steps - done);
-        if ((rc = s->h_perm.ensure((size_t)chunk * nt * sizeof(int32_t))) || (rc = s->d_perm.ensure((size_t)chunk * nt))) return rc;
-        int32_t *perm = (int32_t *)s->h_perm.p;
-        if (chain) {
-            if ((rc = s->d_chain.ensure((size_t)chunk * row)) || (rc = s->d_chain_lnp.ensure((size_t)chunk * nt))) return rc;
-        }
-        for (int sub = 0; sub < chunk; sub += kSub) {
-            const int sub_end = std::min(chunk, sub + kSub);
-            draw_splits(s, s->steps_done + (uint64_t)sub, sub_end - sub, perm + (size_t)sub * nt);
-            int step_move[kSub];   // with a move table: the move of every step of the batch, drawn next to its splits
-            for (int st = sub; st < sub_end; ++st) step_move[st - sub] = draw_move(s, s->steps_done + (uint64_t)st);
-            HIP_TRY(hipMemcpyAsync(s->d_perm.p + (size_t)sub * nt, perm + (size_t)sub * nt,
-                                   (size_t)(sub_end - sub) * nt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            for (int st = sub; st < sub_end; ++st) {
-                const mp_sampler::Move *mv = s->moves.empty() ? nullptr : &s->moves[(size_t)step_move[st - sub]];
-                if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, chain != nullptr, whole))) return rc;
-            }
-        }
-        if (chain) {
-            HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if ((rc = drain_bad(s))) return rc;
-        s->steps_done += (uint64_t)chunk;
-        done += chunk;
-    }
-    return MP_OK;
-}
-
-int mp_sampler_set_whole_step(mp_sampler *s, int enable) {
-    if (!s) return fail(MP_EINVAL, "mp_sampler_set_whole_step: NULL sampler");
-    Lock lock(s->h->mu);
-    s->whole_step = enable != 0;
-    return MP_OK;
-}
-
-// ---- walker-sharded driving: the caller (one process per GPU) runs, per half-step,
-//        mp_sampler_halfstep_shard(its block of slots) -> all-gather of the outcome rows -> mp_sampler_halfstep_apply.
-// Device pointer of the split of the current step; uploads the next window of kWin splits when the step enters it.
-static int current_split(mp_sampler *s, hipStream_t st, const int32_t **d_perm) {
-    const size_t nt = (size_t)s->n_total;
-    const int64_t win = (int64_t)(s->steps_done / mp_sampler::kWin);
-    const int b = (int)(win & 1);
-    if (s->win_id[b] != win) {
-        int rc;
-        const size_t bytes = (size_t)mp_sampler::kWin * nt * sizeof(int32_t);
-        if ((rc = s->h_win[b].ensure(bytes)) || (rc = s->d_win[b].ensure((size_t)mp_sampler::kWin * nt))) return rc;
-        if (s->win_id[b] >= 0) HIP_TRY(hipEventSynchronize(s->win_copied[b].e));   // staged two windows ago: long done
-        int32_t *perm = (int32_t *)s->h_win[b].p;
-        draw_splits(s, (uint64_t)win * mp_sampler::kWin, mp_sampler::kWin, perm);
-        // stream order puts the copy behind every kernel that still reads this buffer's previous contents
-        HIP_TRY(hipMemcpyAsync(s->d_win[b].p, perm, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(s->win_copied[b].e, st));
-        s->win_id[b] = win;
-    }
-    *d_perm = s->d_win[b].p + (size_t)(s->steps_done % mp_sampler::kWin) * nt;
-    return MP_OK;
-}
-
-int mp_sampler_row_doubles(const mp_sampler *s) { return s ? s->ndim + 3 : 0; }
-int mp_sampler_n_slots(const mp_sampler *s) { return s ? (s->n_walkers / 2) * s->n_ensembles : 0; }
-
-// The prologue of the four sharded entry points (fn: the entry point, which every message starts with): a sampler without state,
-// a tempered one and one with a move table are refused (those run through mp_sampler_run only); otherwise the handle's lock and
-// device are held for the call, d_perm is the split of the current step and the sampler notes work on a caller's stream.
-struct ShardCall {
-    Lock lock;
-    DeviceScope scope;
-    const int32_t *d_perm = nullptr;
-    int rc = MP_OK;
-    ShardCall(mp_sampler *s, const char *fn, void *stream) : lock(s->h->mu), scope(s->h->device) {
-        if (!s->have_state) rc = fail(MP_ESTATE, "%s: call mp_sampler_set_positions first", fn);
-        else if (s->n_temps) rc = fail(MP_ESTATE, "%s: a tempered sampler runs on one device only (mp_sampler_run)", fn);
-        else if (!s->moves.empty())
-            rc = fail(MP_ESTATE, "%s: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)", fn);
-        else if (!(rc = current_split(s, (hipStream_t)stream, &d_perm))) s->ext_stream_work = true;
-    }
-};
-
-int mp_sampler_halfstep_shard(mp_sampler *s, int half, int slot_lo, int slot_hi, double *d_rows, void *stream) {
-    if (!s || (half != 0 && half != 1)) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: bad argument");
-    ShardCall c(s, "mp_sampler_halfstep_shard", stream);
-    if (c.rc) return c.rc;
-    const int n_slots = (s->n_walkers / 2) * s->n_ensembles;
-    if (slot_lo < 0 || slot_hi > n_slots || slot_lo > slot_hi) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: slots [%d, %d) outside [0, %d)", slot_lo, slot_hi, n_slots);
-    if (slot_hi > slot_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: NULL row buffer");
-    if (slot_hi == slot_lo) return MP_OK;
-    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, half);
-    g.upd = d_rows;
-    g.slot_lo = slot_lo;
-    const int e = mp::launch_stretch(s->h->sh, g, slot_hi - slot_lo, stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    return MP_OK;
-}
-
-int mp_sampler_halfstep_apply(mp_sampler *s, int half, const double *d_rows, double *d_chain_row, double *d_chain_lnp_row,
-                              void *stream) {
-    if (!s || !d_rows || (half != 0 && half != 1)) return fail(MP_EINVAL, "mp_sampler_halfstep_apply: bad argument");
-    if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_halfstep_apply: chain row and lnprob row go together");
-    ShardCall c(s, "mp_sampler_halfstep_apply", stream);
-    if (c.rc) return c.rc;
-    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, half);
-    g.upd = const_cast<double *>(d_rows);
-    g.chain = d_chain_row;
-    g.chain_lnp = d_chain_lnp_row;
-    g.chain_row = 0;
-    const int e = mp::launch_stretch_apply(g, stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (half == 1) s->steps_done += 1;
-    return MP_OK;
-}
-
-// ---- the same for a whole step per launch (mp_kernels.hip stretch_step_kernel): the caller runs, per STEP,
-//        mp_sampler_step_shard(its share of the 3 * n_slots blocks) -> ONE all-gather of the rows -> mp_sampler_step_apply.
-int mp_sampler_step_blocks(const mp_sampler *s) { return s ? 3 * (s->n_walkers / 2) * s->n_ensembles : 0; }
-int mp_sampler_step_row_doubles(const mp_sampler *s) { return s ? s->ndim + mp::kSpecExtra : 0; }
-
-int mp_sampler_step_shard(mp_sampler *s, int block_lo, int block_hi, double *d_rows, void *stream) {
-    if (!s) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL sampler");
-    ShardCall c(s, "mp_sampler_step_shard", stream);
-    if (c.rc) return c.rc;
-    const int n_blocks = 3 * (s->n_walkers / 2) * s->n_ensembles;
-    if (block_lo < 0 || block_hi > n_blocks || block_lo > block_hi) return fail(MP_EINVAL, "mp_sampler_step_shard: blocks [%d, %d) outside [0, %d)", block_lo, block_hi, n_blocks);
-    if (block_hi > block_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL row buffer");
-    if (block_hi == block_lo) return MP_OK;
-    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, 0);
-    g.spec = d_rows;
-    g.slot_lo = block_lo;
-    const int e = mp::launch_stretch_step(s->h->sh, g, block_hi - block_lo, stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    return MP_OK;
-}
-
-int mp_sampler_step_apply(mp_sampler *s, const double *d_rows, double *d_chain_row, double *d_chain_lnp_row, void *stream) {
-    if (!s || !d_rows) return fail(MP_EINVAL, "mp_sampler_step_apply: bad argument");
-    if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_step_apply: chain row and lnprob row go together");
-    ShardCall c(s, "mp_sampler_step_apply", stream);
-    if (c.rc) return c.rc;
-    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, 0);
-    g.spec = const_cast<double *>(d_rows);
-    g.chain = d_chain_row;
-    g.chain_lnp = d_chain_lnp_row;
-    g.chain_row = 0;
-    const int e = mp::launch_stretch_step_commit(g, stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    s->steps_done += 1;
-    return MP_OK;
-}
-
-int mp_sampler_state_ptrs(mp_sampler *s, double **d_pos, double **d_lnprob) {
-    if (!s) return fail(MP_EINVAL, "mp_sampler_state_ptrs: NULL sampler");
-    if (d_pos) *d_pos = s->d_pos.p;
-    if (d_lnprob) *d_lnprob = s->d_lnprob.p;
-    return MP_OK;
-}
-
-int mp_sampler_get_bad(mp_sampler *s, int64_t first_row, double *pars, int max_rows, int64_t *n_bad, int64_t *n_logged) {
-    if (!s || max_rows < 0 || first_row < 0 || (max_rows > 0 && !pars)) return fail(MP_EINVAL, "mp_sampler_get_bad: bad argument");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    HIP_TRY(hipDeviceSynchronize());
-    const int rc = drain_bad(s);
-    if (rc) return rc;
-    const int64_t logged = (int64_t)(s->bad_log.size() / (size_t)s->ndim);
-    if (n_bad) *n_bad = s->n_bad;
-    if (n_logged) *n_logged = logged;
-    const int64_t rows = std::max<int64_t>(0, std::min<int64_t>(logged - first_row, (int64_t)max_rows));
-    if (rows) std::memcpy(pars, s->bad_log.data() + (size_t)first_row * s->ndim, (size_t)rows * s->ndim * sizeof(double));
-    return (int)rows;
-}
-
-int mp_sampler_get_state(mp_sampler *s, double *pos, double *lnprob, int64_t *n_accepted, int64_t *steps_done) {
-    if (!s) return fail(MP_EINVAL, "mp_sampler_get_state: NULL sampler");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const size_t nt = (size_t)s->n_total;
-    HIP_TRY(hipDeviceSynchronize());
-    const int rc = read_back(pos, s->d_pos.p, nt * s->ndim, lnprob, s->d_lnprob.p, nt, n_accepted, s->d_acc.p, nt);
-    if (rc) return rc;
-    if (steps_done) *steps_done = (int64_t)s->steps_done;
-    return MP_OK;
-}
-
-// ---------------------------------------------------------------- differential-evolution optimizer (mp_opt.hip)
-struct mp_optimizer {
-    mp_handle *h = nullptr;
-    mp::OptArgs a{};                // pointers: cur / next as of the next launch
-    int n_total = 0;
-    uint32_t gen = 0;               // generations launched so far (0: only the initial evaluation)
-    bool have_state = false;
-    DevBuf<double> d_pop[2], d_lnp[2];
-    DevBuf<int32_t> d_st[2], d_dsid, d_best, d_conv, d_nit;
-    DevBuf<int64_t> d_nfev;
-};
-
-static void opt_swap(mp_optimizer *o) {
-    std::swap(o->a.pop_cur, o->a.pop_next);
-    std::swap(o->a.lnp_cur, o->a.lnp_next);
-    std::swap(o->a.st_cur, o->a.st_next);
-}
-
-// one generation (trial = 1) or the initial evaluation (trial = 0) on the handle's stream, then the buffers change roles
-static int opt_enqueue(mp_optimizer *o, int trial) {
-    o->a.trial = trial;
-    o->a.gen = o->gen;
-    int e = mp::launch_opt_trial(o->h->sh, o->a, o->h->stream);
-    if (!e) e = mp::launch_opt_reduce(o->a, o->h->stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    opt_swap(o);
-    return MP_OK;
-}
-
-mp_optimizer *mp_optimizer_create(mp_handle *h, int popsize, int n_pops, int ndim, const int32_t *pop_ds_id, uint64_t seed,
-                                  int strategy, double f_lo, double f_hi, double cr, double tol, double atol,
-                                  const double *lower, const double *upper, int target) {
-    if (!h || !lower || !upper) { fail(MP_EINVAL, "mp_optimizer_create: NULL argument"); return nullptr; }
-    Lock lock(h->mu);
-    const int rc = check_create(h, "mp_optimizer_create", "the optimizer lives on ONE device (a multi-device handle serves host-buffer batches only)",
-                                ndim, target, "population", n_pops, pop_ds_id, [&] {
-        if (popsize < 5 || popsize > 1024) return fail(MP_EINVAL, "mp_optimizer_create: popsize must be 5 .. 1024, got %d", popsize);
-        if (n_pops < 1 || n_pops > MP_MAX_DATASETS) return fail(MP_EINVAL, "mp_optimizer_create: n_pops must be 1 .. %d", MP_MAX_DATASETS);
-        if (target != 0 && target != 1) return fail(MP_EINVAL, "mp_optimizer_create: target must be 0 (posterior) or 1 (unit Gaussian)");
-        if (strategy != MP_DE_BEST1BIN && strategy != MP_DE_RAND1BIN) return fail(MP_EINVAL, "mp_optimizer_create: unknown strategy %d", strategy);
-        if (!(f_lo >= 0.0 && f_lo <= f_hi && f_hi < 2.0)) return fail(MP_EINVAL, "mp_optimizer_create: need 0 <= f_lo <= f_hi < 2");
-        if (!(cr >= 0.0 && cr <= 1.0)) return fail(MP_EINVAL, "mp_optimizer_create: cr must lie in [0, 1]");
-        if (!(std::isfinite(tol) && tol >= 0.0 && std::isfinite(atol) && atol >= 0.0)) return fail(MP_EINVAL, "mp_optimizer_create: tol and atol must be finite and >= 0");
-        return check_box("mp_optimizer_create", ndim, lower, upper);
-    });
-    if (rc) return nullptr;
-    mp_optimizer *o = new mp_optimizer();
-    o->h = h;
-    o->n_total = popsize * n_pops;
-    mp::OptArgs &a = o->a;
-    a.popsize = popsize; a.n_pops = n_pops; a.ndim = ndim; a.strategy = strategy; a.target = target; a.seed = seed;
-    a.f_lo = f_lo; a.f_hi = f_hi; a.cr = cr; a.tol = tol; a.atol = atol;
-    for (int d = 0; d < ndim; ++d) { a.lower[d] = lower[d]; a.upper[d] = upper[d]; }
-    DeviceScope scope(h->device);
-    const size_t nt = (size_t)o->n_total;
-    Binder bind;
-    bind(o->d_pop[0], nt * ndim, a.pop_cur); bind(o->d_pop[1], nt * ndim, a.pop_next);
-    bind(o->d_lnp[0], nt, a.lnp_cur); bind(o->d_lnp[1], nt, a.lnp_next);
-    bind(o->d_st[0], nt, a.st_cur); bind(o->d_st[1], nt, a.st_next);
-    bind(o->d_dsid, nt, a.ds_id);
-    bind(o->d_best, n_pops, a.best); bind(o->d_conv, n_pops, a.converged); bind(o->d_nit, n_pops, a.nit); bind(o->d_nfev, n_pops, a.nfev);
-    if (bind.rc || upload_ds_rows(o->d_dsid.p, pop_ds_id, n_pops, popsize)) {
-        fail(MP_EHIP, "mp_optimizer_create: device allocation failed");
-        mp_optimizer_destroy(o);
-        return nullptr;
-    }
-    return o;
-}
-
-int mp_optimizer_destroy(mp_optimizer *o) {
-    if (!o) return MP_OK;
-    Lock lock(o->h->mu);
-    DeviceScope scope(o->h->device);
-    (void)hipStreamSynchronize(o->h->stream);
-    delete o;
-    return MP_OK;
-}
-
-int mp_optimizer_set_population(mp_optimizer *o, const double *pop) {
-    if (!o || !pop) return fail(MP_EINVAL, "mp_optimizer_set_population: NULL argument");
-    mp_handle *h = o->h;
-    const size_t nt = (size_t)o->n_total, n_pops = (size_t)o->a.n_pops;
-    for (size_t i = 0; i < nt * o->a.ndim; ++i)
-        if (!std::isfinite(pop[i])) return fail(MP_EINVAL, "mp_optimizer_set_population: non-finite coordinate");
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    HIP_TRY(hipMemcpyAsync(o->a.pop_cur, pop, nt * o->a.ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(o->a.converged, 0, n_pops * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(o->a.nit, 0, n_pops * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(o->a.nfev, 0, n_pops * sizeof(int64_t), h->stream));
-    o->gen = 0;
-    int rc = opt_enqueue(o, 0);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    o->have_state = true;
-    return MP_OK;
-}
-
-int mp_optimizer_run(mp_optimizer *o, int max_generations, int *n_running) {
-    if (!o || max_generations < 0) return fail(MP_EINVAL, "mp_optimizer_run: bad argument");
-    if (!o->have_state) return fail(MP_ESTATE, "mp_optimizer_run: call mp_optimizer_set_population first");
-    mp_handle *h = o->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    // Chunks of generations enqueued back to back (no allocation, no wait inside a chunk); the flags are read back behind each
-    // chunk, and the run ends early once every population has converged.  A frozen population costs an empty workgroup per
-    // member and launch.
-    constexpr int kChunk = 16;
-    int running, rc;
-    if ((rc = groups_running(h, o->a.converged, o->a.n_pops, &running))) return rc;
-    for (int done = 0; done < max_generations && running > 0;) {
-        const int chunk = std::min(kChunk, max_generations - done);
-        for (int g = 0; g < chunk; ++g) {
-            ++o->gen;
-            if ((rc = opt_enqueue(o, 1))) return rc;
-        }
-        if ((rc = groups_running(h, o->a.converged, o->a.n_pops, &running))) return rc;
-        done += chunk;
-    }
-    if (n_running) *n_running = running;
-    return MP_OK;
-}
-
-int mp_optimizer_get_state(mp_optimizer *o, double *pop, double *lnprob, int32_t *status, int32_t *best, int32_t *nit,
-                           int32_t *converged, int64_t *nfev) {
-    if (!o) return fail(MP_EINVAL, "mp_optimizer_get_state: NULL optimizer");
-    if (!o->have_state) return fail(MP_ESTATE, "mp_optimizer_get_state: call mp_optimizer_set_population first");
-    mp_handle *h = o->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const size_t nt = (size_t)o->n_total, np = (size_t)o->a.n_pops;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const mp::OptArgs &a = o->a;
-    return read_back(pop, a.pop_cur, nt * a.ndim, lnprob, a.lnp_cur, nt, status, a.st_cur, nt,
-                     best, a.best, np, nit, a.nit, np, converged, a.converged, np, nfev, a.nfev, np);
-}
-
-// ---------------------------------------------------------------- nested sampler (mp_nest.hip)
-struct mp_nested {
-    mp_handle *h = nullptr;
-    mp::NestArgs a{};
-    int n_total = 0;                // n_runs * nlive
-    int chunk = 0;                  // iterations per chunk (slots of the dead buffers)
-    uint32_t iter = 0;              // iterations launched since mp_nested_set_live
-    bool have_state = false;
-    DevBuf<double> d_live, d_lnl, d_lstar, d_dpars, d_dlnl, d_lnx, d_lnz;
-    DevBuf<int32_t> d_st, d_acc, d_dsid, d_dslot, d_surv, d_dn, d_stop, d_nit;
-    DevBuf<int64_t> d_ncall, d_nacc, d_nzero, d_nexp, d_ncon, d_nfail;
-    mp::NestSlice sl{};             // slice mode (sl.slices > 0) from the next iteration on
-    std::vector<std::vector<double>> dead_pars, dead_lnl;   // per run, in order
-    std::vector<std::vector<int32_t>> dead_n;
-};
-
-mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int ndim, const int32_t *run_ds_id, uint64_t seed,
-                            int walks, double g0, double sigma, double dlogz, const double *lower, const double *upper, int target) {
-    if (!h || !lower || !upper) { fail(MP_EINVAL, "mp_nested_create: NULL argument"); return nullptr; }
-    Lock lock(h->mu);
-    const int rc = check_create(h, "mp_nested_create", "the nested sampler lives on ONE device (a multi-device handle serves host-buffer batches only)",
-                                ndim, target, "run", n_runs, run_ds_id, [&] {
-        if (nlive < MP_NEST_MIN_LIVE || nlive > MP_NEST_MAX_LIVE) return fail(MP_EINVAL, "mp_nested_create: nlive must be %d .. %d, got %d", MP_NEST_MIN_LIVE, MP_NEST_MAX_LIVE, nlive);
-        if (nbatch < 1 || nbatch > nlive / 2) return fail(MP_EINVAL, "mp_nested_create: nbatch must be 1 .. nlive / 2, got %d", nbatch);
-        if (n_runs < 1 || n_runs > MP_MAX_DATASETS) return fail(MP_EINVAL, "mp_nested_create: n_runs must be 1 .. %d", MP_MAX_DATASETS);
-        if (target != 0 && target != 1) return fail(MP_EINVAL, "mp_nested_create: target must be 0 (posterior) or 1 (unit Gaussian)");
-        if (walks < 1 || walks > MP_NEST_MAX_WALKS) return fail(MP_EINVAL, "mp_nested_create: walks must be 1 .. %d", MP_NEST_MAX_WALKS);
-        if (!std::isfinite(g0)) return fail(MP_EINVAL, "mp_nested_create: g0 must be finite (<= 0: the default)");
-        if (!(sigma >= 0.0 && sigma < 1.0 / std::sqrt(3.0))) return fail(MP_EINVAL, "mp_nested_create: sigma must lie in [0, 1/sqrt(3))");
-        if (!(std::isfinite(dlogz) && dlogz > 0.0)) return fail(MP_EINVAL, "mp_nested_create: dlogz must be finite and > 0");
-        return check_box("mp_nested_create", ndim, lower, upper);
-    });
-    if (rc) return nullptr;
-    mp_nested *ns = new mp_nested();
-    ns->h = h;
-    ns->n_total = nlive * n_runs;
-    // dead buffers of about 16 MB at most, up to 32 iterations per chunk
-    const size_t row = (size_t)n_runs * nbatch * (ndim + 2) * sizeof(double);
-    ns->chunk = (int)std::max<size_t>(1, std::min<size_t>(32, (16u << 20) / row));
-    mp::NestArgs &a = ns->a;
-    a.nlive = nlive; a.nbatch = nbatch; a.n_runs = n_runs; a.ndim = ndim; a.walks = walks; a.target = target; a.seed = seed;
-    a.g0 = g0 > 0.0 ? g0 : 2.38 / std::sqrt(2.0 * ndim);
-    a.sig3 = sigma * std::sqrt(3.0);
-    a.dlogz = dlogz;
-    for (int d = 0; d < ndim; ++d) { a.lower[d] = lower[d]; a.upper[d] = upper[d]; }
-    ns->dead_pars.resize(n_runs); ns->dead_lnl.resize(n_runs); ns->dead_n.resize(n_runs);
-    DeviceScope scope(h->device);
-    const size_t nt = (size_t)ns->n_total, nr = (size_t)n_runs, nk = nr * nbatch, nc = (size_t)ns->chunk * nk;
-    Binder bind;
-    bind(ns->d_live, nt * ndim, a.live); bind(ns->d_lnl, nt, a.lnl); bind(ns->d_st, nt, a.st); bind(ns->d_acc, nt, a.acc);
-    bind(ns->d_dsid, nr, a.ds_id); bind(ns->d_dslot, nk, a.dead_slot); bind(ns->d_surv, nr * (nlive - nbatch), a.surv);
-    bind(ns->d_lstar, nr, a.lstar); bind(ns->d_dpars, nc * ndim, a.dead_pars); bind(ns->d_dlnl, nc, a.dead_lnl); bind(ns->d_dn, nc, a.dead_n);
-    bind(ns->d_lnx, nr, a.lnx); bind(ns->d_lnz, nr, a.lnz); bind(ns->d_stop, nr, a.stopped); bind(ns->d_nit, nr, a.nit);
-    bind(ns->d_ncall, nr, a.ncall); bind(ns->d_nacc, nr, a.nacc); bind(ns->d_nzero, nr, a.nzero);
-    bind(ns->d_nexp, nr, ns->sl.nexpand); bind(ns->d_ncon, nr, ns->sl.ncontract); bind(ns->d_nfail, nr, ns->sl.nfail);
-    if (bind.rc || upload_ds_rows(ns->d_dsid.p, run_ds_id, n_runs, 1)) {
-        fail(MP_EHIP, "mp_nested_create: device allocation failed");
-        mp_nested_destroy(ns);
-        return nullptr;
-    }
-    return ns;
-}
-
-int mp_nested_destroy(mp_nested *ns) {
-    if (!ns) return MP_OK;
-    Lock lock(ns->h->mu);
-    DeviceScope scope(ns->h->device);
-    (void)hipStreamSynchronize(ns->h->stream);
-    delete ns;
-    return MP_OK;
-}
-
-int mp_nested_set_live(mp_nested *ns, const double *live) {
-    if (!ns || !live) return fail(MP_EINVAL, "mp_nested_set_live: NULL argument");
-    mp_handle *h = ns->h;
-    mp::NestArgs &a = ns->a;
-    const size_t nt = (size_t)ns->n_total, nr = (size_t)a.n_runs;
-    for (size_t i = 0; i < nt; ++i)
-        for (int d = 0; d < a.ndim; ++d) {
-            const double v = live[i * a.ndim + d];
-            if (!(v >= a.lower[d] && v <= a.upper[d])) return fail(MP_EINVAL, "mp_nested_set_live: live point %zu lies outside the box", i);
-        }
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const std::vector<double> zero(nr, 0.0), ninf(nr, -INFINITY);
-    HIP_TRY(hipMemcpyAsync(a.live, live, nt * a.ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(a.lnx, zero.data(), nr * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(a.lnz, ninf.data(), nr * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(a.stopped, 0, nr * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(a.nit, 0, nr * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(a.ncall, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(a.nacc, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(a.nzero, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(ns->sl.nexpand, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(ns->sl.ncontract, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(ns->sl.nfail, 0, nr * sizeof(int64_t), h->stream));
-    a.mode = 1;
-    a.iter = 0;
-    const int e = mp::launch_nest_walk(h->sh, a, h->stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    ns->iter = 0;
-    for (size_t r = 0; r < nr; ++r) { ns->dead_pars[r].clear(); ns->dead_lnl[r].clear(); ns->dead_n[r].clear(); }
-    ns->have_state = true;
-    return MP_OK;
-}
-
-int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running) {
-    if (!ns || max_iterations < 0) return fail(MP_EINVAL, "mp_nested_run: bad argument");
-    if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_run: call mp_nested_set_live first");
-    mp_handle *h = ns->h;
-    mp::NestArgs &a = ns->a;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    // Chunks of iterations enqueued back to back (select, walk, select, walk, ...; no wait inside a chunk), then a stop check on
-    // the live set as it stands and one read-back of the counters and the dead rows; the run ends early once every run stopped.
-    const int nr = a.n_runs, K = a.nbatch, nd = a.ndim;
-    const size_t per = (size_t)nr * K;
-    std::vector<int32_t> nit0((size_t)nr), nit1((size_t)nr);
-    std::vector<double> hp, hl;
-    std::vector<int32_t> hn;
-    int running, rc;
-    if ((rc = groups_running(h, a.stopped, nr, &running))) return rc;
-    for (int done = 0; done < max_iterations && running > 0;) {
-        const int chunk = std::min(ns->chunk, max_iterations - done);
-        HIP_TRY(hipMemcpyAsync(nit0.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        for (int c = 0; c < chunk; ++c) {
-            a.slot = c;
-            a.iter = ns->iter++;
-            a.mode = 0;
-            int e = mp::launch_nest_select(a, h->stream);
-            if (!e) e = ns->sl.slices ? mp::launch_nest_slice(h->sh, a, ns->sl, h->stream) : mp::launch_nest_walk(h->sh, a, h->stream);
-            if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        }
-        a.mode = 1;
-        int e = mp::launch_nest_select(a, h->stream);
-        if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        hp.resize((size_t)chunk * per * nd);
-        hl.resize((size_t)chunk * per);
-        hn.resize((size_t)chunk * per);
-        HIP_TRY(hipMemcpyAsync(hp.data(), a.dead_pars, hp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(hl.data(), a.dead_lnl, hl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(hn.data(), a.dead_n, hn.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(nit1.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if ((rc = groups_running(h, a.stopped, nr, &running))) return rc;   // (behind the copies above: they have landed)
-        // run r ran the first nit1 - nit0 iterations of the chunk (a stopped run stays stopped)
-        for (int r = 0; r < nr; ++r)
-            for (int c = 0; c < nit1[r] - nit0[r]; ++c) {
-                const size_t o = ((size_t)c * nr + r) * K;
-                ns->dead_pars[r].insert(ns->dead_pars[r].end(), hp.begin() + o * nd, hp.begin() + (o + K) * nd);
-                ns->dead_lnl[r].insert(ns->dead_lnl[r].end(), hl.begin() + o, hl.begin() + o + K);
-                ns->dead_n[r].insert(ns->dead_n[r].end(), hn.begin() + o, hn.begin() + o + K);
-            }
-        done += chunk;
-    }
-    if (n_running) *n_running = running;
-    return MP_OK;
-}
-
-int mp_nested_get_dead(mp_nested *ns, int run, int64_t max_rows, double *pars, double *lnl, int32_t *n_live, int64_t *n_rows) {
-    if (!ns || run < 0 || run >= ns->a.n_runs || max_rows < 0) return fail(MP_EINVAL, "mp_nested_get_dead: bad argument");
-    if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_get_dead: call mp_nested_set_live first");
-    Lock lock(ns->h->mu);
-    const int64_t have = (int64_t)ns->dead_lnl[run].size(), n = std::min(have, max_rows);
-    if (pars) std::copy(ns->dead_pars[run].begin(), ns->dead_pars[run].begin() + n * ns->a.ndim, pars);
-    if (lnl) std::copy(ns->dead_lnl[run].begin(), ns->dead_lnl[run].begin() + n, lnl);
-    if (n_live) std::copy(ns->dead_n[run].begin(), ns->dead_n[run].begin() + n, n_live);
-    if (n_rows) *n_rows = have;
-    return MP_OK;
-}
-
-int mp_nested_get_state(mp_nested *ns, double *live, double *lnl, int32_t *status, int32_t *acc, int32_t *nit, int32_t *stopped,
-                        double *lnx, double *lnz, int64_t *ncall, int64_t *nacc, int64_t *nzero) {
-    if (!ns) return fail(MP_EINVAL, "mp_nested_get_state: NULL sampler");
-    if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_get_state: call mp_nested_set_live first");
-    mp_handle *h = ns->h;
-    const mp::NestArgs &a = ns->a;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const size_t nt = (size_t)ns->n_total, nr = (size_t)a.n_runs;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return read_back(live, a.live, nt * a.ndim, lnl, a.lnl, nt, status, a.st, nt, acc, a.acc, nt, nit, a.nit, nr,
-                     stopped, a.stopped, nr, lnx, a.lnx, nr, lnz, a.lnz, nr, ncall, a.ncall, nr, nacc, a.nacc, nr, nzero, a.nzero, nr);
-}
-
-int mp_nested_set_slice(mp_nested *ns, int slices, double mu, int max_steps_out, int max_shrink) {
-    if (!ns) return fail(MP_EINVAL, "mp_nested_set_slice: NULL sampler");
-    if (slices < 0 || slices > MP_NEST_MAX_SLICES) return fail(MP_EINVAL, "mp_nested_set_slice: slices must be 0 .. %d, got %d", MP_NEST_MAX_SLICES, slices);
-    if (!(std::isfinite(mu) && mu > 0.0)) return fail(MP_EINVAL, "mp_nested_set_slice: mu must be finite and > 0");
-    if (max_steps_out < 1 || max_steps_out > MP_NEST_MAX_STEPS_OUT)
-        return fail(MP_EINVAL, "mp_nested_set_slice: max_steps_out must be 1 .. %d, got %d", MP_NEST_MAX_STEPS_OUT, max_steps_out);
-    if (max_shrink < 1 || max_shrink > MP_NEST_MAX_SHRINK)
-        return fail(MP_EINVAL, "mp_nested_set_slice: max_shrink must be 1 .. %d, got %d", MP_NEST_MAX_SHRINK, max_shrink);
-    Lock lock(ns->h->mu);   // (read by the next mp_nested_run)
-    ns->sl.slices = slices;
-    ns->sl.mu = mu;
-    ns->sl.max_steps_out = max_steps_out;
-    ns->sl.max_shrink = max_shrink;
-    return MP_OK;
-}
-
-int mp_nested_get_slice_stats(mp_nested *ns, int64_t *nexpand, int64_t *ncontract, int64_t *nfail) {
-    if (!ns) return fail(MP_EINVAL, "mp_nested_get_slice_stats: NULL sampler");
-    if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_get_slice_stats: call mp_nested_set_live first");
-    mp_handle *h = ns->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const size_t nr = (size_t)ns->a.n_runs;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return read_back(nexpand, ns->sl.nexpand, nr, ncontract, ns->sl.ncontract, nr, nfail, ns->sl.nfail, nr);
 }
 
 int mp_device(const mp_handle *h) { return h ? h->device : -1; }

@@ -1,4 +1,4 @@
-// mp_device.h — structures shared by the host C-ABI (mp_capi.cpp) and the gfx950 kernels (mp_kernels.hip).
+// mp_device.h — structures shared by the host sources of the C ABI (mp_host.h) and the gfx950 kernels (mp_kernels.hip).
 #pragma once
 #include <stdint.h>
 

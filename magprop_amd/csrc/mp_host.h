@@ -1,0 +1,199 @@
+// mp_host.h — what the host sources of the C ABI share (mp_capi.cpp, mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp).
+//
+// Internal: not installed, never seen by a kernel source.  Error reporting, owners of device memory, pinned memory and events,
+// the evaluator handle, and the helpers of mp_capi.cpp that the resident drivers call.  Each driver's own struct stays in its
+// source file.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <numeric>
+#include <vector>
+
+#include "mp_device.h"
+
+// Nothing declared here is part of the ABI: hidden, so that the library exports the mp_* functions of include/magprop_amd.h only.
+#pragma GCC visibility push(hidden)
+
+// records the message behind mp_last_error() for the calling thread and returns code (defined in mp_capi.cpp)
+int fail(int code, const char *fmt, ...);
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return fail(MP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+struct DeviceScope {  // make the handle's device current for the duration of a call
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceScope(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceScope() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+struct HostDataset {
+    bool set = false;
+    std::vector<int32_t> g, tile_ptr;
+    std::vector<double> dx, idt, y, yerr;
+};
+
+// Device memory owned by its holder: freed on destruction (on the device current then: the destroy functions delete their object
+// inside a DeviceScope of its device), never copied.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int ensure(size_t n) {
+        if (n <= cap) return MP_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        size_t want = std::max<size_t>(n, 16);
+        HIP_TRY(hipMalloc((void **)&p, want * sizeof(T)));
+        cap = want;
+        return MP_OK;
+    }
+};
+
+// Allocates a driver's buffers (ensure) and points the fields of its launch arguments at them: bind(buffer, size, field).  The
+// first failure sticks in rc, and the allocations behind it are skipped.
+struct Binder {
+    int rc = MP_OK;
+    template <typename T, typename P>
+    void operator()(DevBuf<T> &b, size_t n, P *&field) {
+        if (!rc && !(rc = b.ensure(n))) field = b.p;
+    }
+};
+
+// Page-locked host staging area of the host-buffer entry points: copies to and from it are true asynchronous DMA
+// (pageable user buffers would be staged by the runtime copy by copy).
+struct PinnedBuf {
+    unsigned char *p = nullptr;
+    unsigned char *dev = nullptr;   // the same memory as the device sees it (mapped, coherent): kernels may read and write it in place
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    int ensure(size_t n) {
+        if (n <= cap) return MP_OK;
+        if (p) (void)hipHostFree(p);
+        p = dev = nullptr;
+        cap = 0;
+        const size_t want = std::max<size_t>(n, 4096);
+        HIP_TRY(hipHostMalloc((void **)&p, want, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, p, 0));
+        cap = want;
+        return MP_OK;
+    }
+};
+
+// An event owned by its holder (created by it when first needed, destroyed with it)
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+};
+
+// Device-to-host copies of the state of a driver: read_back(dst, src, n, dst2, src2, n2, ...) copies n elements of src to dst
+// for every triple whose dst is not NULL.
+inline int read_back() { return MP_OK; }
+template <typename T, typename... Rest>
+int read_back(T *dst, const T *src, size_t n, Rest... rest) {
+    if (dst) HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+    return read_back(rest...);
+}
+
+struct mp_handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::vector<double> tgrid;
+    int n_tiles = 0;
+    HostDataset ds[MP_MAX_DATASETS];
+    mp::DevShared sh{};
+    // device copies of the shared data
+    DevBuf<double> d_wtab;
+    DevBuf<double> d_tgrid, d_obs_dx, d_obs_idt, d_obs_y, d_obs_yerr;
+    DevBuf<int32_t> d_obs_g, d_tile_ptr;
+    DevBuf<mp::DsDesc> d_ds;
+    // The packed observation arrays are an append-only arena: a new light curve goes behind the last one (obs_used /
+    // tp_used entries are live or stale), a replaced one leaves its old entries behind as garbage until the next rebuild.
+    size_t obs_used = 0, tp_used = 0;
+    std::vector<mp::DsDesc> desc;   // host mirror of d_ds
+    // workspace of the host-buffer entry points
+    DevBuf<double> w_pars, w_lnprob, w_curves;
+    DevBuf<double> w_band, w_band_out;   // mp_model_band: [components][n][n_grid] curves | [n_grid][n] transposed; [components][nq][n_grid]
+    DevBuf<int32_t> w_dsid, w_status, w_sweeps;
+    double last_mean_tiles = 0.0;
+    bool tile_log_on = false;
+    DevBuf<int32_t> w_tile_log;
+    std::vector<int32_t> last_tile_log;
+    PinnedBuf h_io;               // mp_lnprob_batch: [pars | ds_id] in, [lnprob | status | sweeps | tiles] out, read and written in place by the kernel
+    double last_mean_sweeps = 0.0;
+    std::vector<int32_t> last_sweeps, last_tiles;   // per walker, most recent host-buffer batch (diagnostic)
+    // Launch order of mixed-length batches (mp_kernels.hip order_kernel): a ring of index buffers, one per launch in flight.
+    // A slot is written by the launch that takes it and read by that launch's workgroups as they start; the launch that
+    // takes it kOrderRing launches later waits (stream-level, on the event recorded behind the earlier launch) for that
+    // launch to have finished -- launches fewer than kOrderRing apart share nothing.
+    static constexpr int kOrderRing = 8;
+    DevBuf<int32_t> order[kOrderRing];
+    Event order_done[kOrderRing];
+    unsigned order_next = 0;
+    // Threading / stream contract (include/magprop_amd.h): every entry point that takes a handle or a sampler holds
+    // `mu` for its duration.  Launches share nothing writable but their own outputs (round 4: no per-walker scratch rows),
+    // so launches of one handle on different streams may overlap freely.
+    std::recursive_mutex mu;
+    // Multi-device handle (mp_create_multi): one evaluator per listed device; this object then holds no device state of
+    // its own -- datasets and prior are forwarded to every evaluator, a host-buffer batch is dealt out in contiguous blocks.
+    std::vector<mp_handle *> sub;
+    int pend_n = 0;               // rows of the host-buffer batch between batch_begin and batch_end
+    size_t pend_in_bytes = 0;
+    double last_tot_sweeps = 0.0, last_tot_tiles = 0.0;   // over the walkers of the last batch that finished (status ok) ...
+    int last_cnt_ok = 0;                                  // ... and how many those were
+};
+
+using Lock = std::lock_guard<std::recursive_mutex>;
+
+// ---------------------------------------------------------------- defined in mp_capi.cpp, used by the drivers
+int launch_lnprob_ordered(mp_handle *h, const mp::LaunchArgs &a_in, hipStream_t st);
+int check_box(const char *fn, int ndim, const double *lower, const double *upper);
+int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int rows);
+int groups_running(mp_handle *h, const int32_t *d_flags, int n, int *running);
+
+// The checks of the drivers' create functions (fn), in the order they fail: a multi-device handle (`multi`: what the message says about
+// it), ndim (the posterior, target 0, needs 6 or more), the driver's own arguments (args(): MP_OK or the code of a failure), the
+// alternative dipole torque, and the dataset of every one of n_groups groups (`group` g: ds_id[g], dataset 0 without ds_id).
+// The caller holds the handle's lock.
+template <class Args>
+int check_create(mp_handle *h, const char *fn, const char *multi, int ndim, int target, const char *group, int n_groups,
+                 const int32_t *ds_id, Args &&args) {
+    if (!h->sub.empty()) return fail(MP_ESTATE, "%s: %s", fn, multi);
+    if (ndim < 1 || ndim > MP_MAX_NDIM || (target == 0 && ndim < 6)) return fail(MP_EINVAL, "%s: bad ndim %d", fn, ndim);
+    const int rc = args();
+    if (rc) return rc;
+    if (target != 0) return MP_OK;
+    if (h->sh.cfg.dipole_torque != 0)
+        return fail(MP_ESTATE, "%s: the alternative dipole torque (cfg.dipole_torque = 1) is served by the curve kernels only", fn);
+    for (int g = 0; g < n_groups; ++g) {
+        const int d = ds_id ? ds_id[g] : 0;
+        if (d < 0 || d >= MP_MAX_DATASETS || !h->ds[d].set) return fail(MP_ESTATE, "%s: %s %d refers to unset dataset %d", fn, group, g, d);
+    }
+    return MP_OK;
+}
+
+#pragma GCC visibility pop

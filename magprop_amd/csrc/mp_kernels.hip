@@ -157,7 +157,7 @@ int launch_order(const DevShared &sh, const int32_t *ds_id, int n, int32_t *orde
 // s - slot_lo of g.upd as (proposal[ndim], its lnprob, accepted 0/1) and stretch_apply_kernel commits the rows of all
 // ranks after the all-gather.  The random numbers (Philox, mp_device.h) are keyed by (seed; step, half, walker), so every rank
 // draws what the single-GPU launch would have drawn for the same walker.
-// Half-step launches run the ensembles in the order of StretchArgs::ens_order (mp_capi.cpp: longest light curve first, four
+// Half-step launches run the ensembles in the order of StretchArgs::ens_order (mp_sampler.cpp: longest light curve first, four
 // bits per position; 0 = the ensembles as they are numbered): the waves that take longest start first, as in order_kernel.
 __device__ __forceinline__ int ens_of_slot(const StretchArgs &g, int e_pos) {
     return g.ens_order ? (int)((g.ens_order >> (4 * e_pos)) & 15u) : e_pos;

@@ -1,0 +1,536 @@
+// mp_sampler.cpp — the device-resident ensemble sampler (mp_sampler_*): stretch, DE, snooker and KDE moves, tempering, whole-step
+// and walker-sharded driving.  Kernels: mp_kernels.hip.
+#include <thread>
+
+#include "mp_host.h"
+
+struct mp_sampler {
+    mp_handle *h = nullptr;
+    int n_walkers = 0, n_ensembles = 0, n_total = 0, ndim = 0, target = 0;
+    uint64_t seed = 0;
+    double a = 2.0;
+    uint64_t steps_done = 0;
+    bool have_state = false;
+    DevBuf<double> d_pos, d_lnprob, d_chain, d_chain_lnp, d_bad, d_spec;
+    std::vector<int32_t> ens_ds;   // dataset of every ensemble
+    int whole_step = 1;   // mp_sampler_run: one launch per step where the ensemble is small enough (mp_sampler_set_whole_step)
+    DevBuf<int64_t> d_acc;
+    DevBuf<int32_t> d_perm, d_dsid, d_status;
+    DevBuf<uint32_t> d_bad_count;
+    PinnedBuf h_perm;   // page-locked staging of the random splits: their upload overlaps the running half-steps
+    // walker-sharded driving (mp_sampler_halfstep_shard / _apply): splits of kWin steps at a time, double-buffered
+    static constexpr int kWin = 32;
+    DevBuf<int32_t> d_win[2];
+    PinnedBuf h_win[2];
+    Event win_copied[2];
+    int64_t win_id[2] = {-1, -1};
+    bool ext_stream_work = false;   // half-steps were enqueued on a caller's stream since the last device-wide wait
+    // failed proposals (the reference's fbad file): the device window d_bad is drained into this log
+    std::vector<double> bad_log;    // [rows][ndim]
+    int64_t n_bad = 0;              // exact count since creation (rows beyond the window between two drains are counted, not kept)
+    // parallel tempering (mp_sampler_set_temperatures): ensemble e runs at beta[e % n_temps]; 0 = untempered
+    int n_temps = 0;
+    DevBuf<double> d_beta;          // [n_ensembles]
+    DevBuf<int64_t> d_swaps;        // [n_ensembles / n_temps][n_temps - 1] accepted swaps
+    // proposal moves (mp_sampler_set_moves); empty: the stretch move with scale a
+    struct Move {
+        int32_t kind;
+        double p0, p1;              // stretch: a; DE: g0 (resolved), s = sigma sqrt(3); snooker: gamma_s; KDE: f (resolved)
+    };
+    std::vector<Move> moves;
+    std::vector<double> move_cum;   // cumulative weights, summed in order
+};
+
+// Move the device window of failed proposals into the host log and reset it.  The caller has made sure that no kernel
+// of this sampler is in flight.
+static int drain_bad(mp_sampler *s) {
+    uint32_t cnt = 0;
+    HIP_TRY(hipMemcpy(&cnt, s->d_bad_count.p, sizeof cnt, hipMemcpyDeviceToHost));
+    if (cnt == 0) return MP_OK;
+    const size_t cap = s->d_bad.cap / (size_t)s->ndim, rows = std::min<size_t>(cnt, cap);
+    const size_t old = s->bad_log.size();
+    s->bad_log.resize(old + rows * (size_t)s->ndim);
+    HIP_TRY(hipMemcpy(s->bad_log.data() + old, s->d_bad.p, rows * s->ndim * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(s->d_bad_count.p, 0, sizeof(uint32_t)));
+    s->n_bad += (int64_t)cnt;
+    return MP_OK;
+}
+
+// random split of every ensemble for step `step` (emcee's randomize_split): Fisher-Yates, counter (step, ensemble, i, 'split')
+static void draw_split(const mp_sampler *s, uint64_t step64, int32_t *perm) {
+    const uint32_t step = (uint32_t)step64;
+    for (int e = 0; e < s->n_ensembles; ++e) {
+        int32_t *p = perm + (size_t)e * s->n_walkers;
+        std::iota(p, p + s->n_walkers, 0);
+        for (int i = s->n_walkers - 1; i > 0; --i) {
+            uint32_t r[4];
+            mp::philox4x32_10((uint32_t)s->seed, (uint32_t)(s->seed >> 32), step, (uint32_t)e, (uint32_t)i, 0x5117u, r);
+            const uint64_t r64 = ((uint64_t)r[0] << 32) | r[1];
+            std::swap(p[i], p[(size_t)(r64 % (uint64_t)(i + 1))]);
+        }
+    }
+}
+
+// splits of `count` consecutive steps into perm[count][n_total]; the steps are independent (counter-based generator), so
+// large ensembles are drawn by a few host threads (8 192 walkers: 0.4 ms per step on one core, more than a half-step of a
+// walker-sharded ensemble takes on the GPU)
+static void draw_splits(const mp_sampler *s, uint64_t step0, int count, int32_t *perm) {
+    const size_t nt = (size_t)s->n_total;
+    const int n_thr = (int)std::min<size_t>({(size_t)count, (size_t)4, (nt * (size_t)count) / 8192});
+    auto work = [&](int first, int stride) {
+        for (int i = first; i < count; i += stride) draw_split(s, step0 + (uint64_t)i, perm + (size_t)i * nt);
+    };
+    if (n_thr <= 1) { work(0, 1); return; }
+    std::vector<std::thread> pool;
+    for (int k = 1; k < n_thr; ++k) pool.emplace_back(work, k, n_thr);
+    work(0, n_thr);
+    for (auto &th : pool) th.join();
+}
+
+// the move of step `step` (an index into s->moves): r = Philox(seed; step, 3, 0, 0x30FE), the first m with u01(r0, r1) C_last < C_m
+static int draw_move(const mp_sampler *s, uint64_t step64) {
+    const int n = (int)s->moves.size();
+    if (n <= 1) return 0;
+    uint32_t r[4];
+    mp::philox4x32_10((uint32_t)s->seed, (uint32_t)(s->seed >> 32), (uint32_t)step64, 3u, 0u, 0x30FEu, r);
+    const double x = mp::u01(r[0], r[1]) * s->move_cum[(size_t)n - 1];
+    for (int m = 0; m < n - 1; ++m)
+        if (x < s->move_cum[(size_t)m]) return m;
+    return n - 1;
+}
+
+static mp::StretchArgs stretch_args(const mp_sampler *s, const int32_t *d_perm, uint64_t step, int half) {
+    mp::StretchArgs g{};
+    g.pos = s->d_pos.p; g.lnprob = s->d_lnprob.p; g.n_accepted = s->d_acc.p;
+    g.perm = d_perm;
+    g.ds_id = s->d_dsid.p;
+    g.n_walkers = s->n_walkers; g.n_half = s->n_walkers / 2; g.n_ensembles = s->n_ensembles;
+    g.n_total = s->n_total; g.ndim = s->ndim; g.half = half; g.target = s->target;
+    g.step = (uint32_t)step; g.seed = s->seed; g.a = s->a;
+    g.bad_log = s->d_bad.p; g.bad_count = s->d_bad_count.p; g.bad_cap = (uint32_t)(s->d_bad.cap / (size_t)std::max(s->ndim, 1));
+    g.beta = s->n_temps ? s->d_beta.p : nullptr;
+    // Ensembles on light curves of different lengths (BASELINE config 5: 50 / 410 / 8 / 1 944 points): the half-step launch
+    // starts the ensemble with the longest light curve first, so that its waves do not begin last and finish alone.  The order
+    // is a function of the datasets only, so every rank of a walker-sharded run derives the same one.
+    if (s->target == 0 && s->n_ensembles > 1 && s->n_ensembles <= 16) {
+        int idx[16];
+        std::iota(idx, idx + s->n_ensembles, 0);
+        std::stable_sort(idx, idx + s->n_ensembles, [&](int x, int y) {
+            return s->h->ds[s->ens_ds[(size_t)x]].g.size() > s->h->ds[s->ens_ds[(size_t)y]].g.size();
+        });
+        bool identity = true;
+        for (int e = 0; e < s->n_ensembles; ++e) identity = identity && idx[e] == e;
+        if (!identity)
+            for (int e = 0; e < s->n_ensembles; ++e) g.ens_order |= (uint64_t)idx[e] << (4 * e);
+    }
+    return g;
+}
+
+extern "C" {
+
+mp_sampler *mp_sampler_create(mp_handle *h, int n_walkers, int n_ensembles, int ndim, const int32_t *ens_ds_id,
+                              uint64_t seed, double a, int target) {
+    if (!h) { fail(MP_EINVAL, "mp_sampler_create: NULL handle"); return nullptr; }
+    Lock lock(h->mu);
+    const int rc = check_create(h, "mp_sampler_create", "the device-resident sampler lives on ONE device (walker sharding across devices: magprop_amd/distributed.py)",
+                                ndim, target, "ensemble", n_ensembles, ens_ds_id, [&] {
+        if (n_walkers < 2 || (n_walkers & 1)) return fail(MP_EINVAL, "mp_sampler_create: n_walkers must be even and >= 2");
+        if (n_ensembles < 1) return fail(MP_EINVAL, "mp_sampler_create: bad n_ensembles");
+        if (!(a > 1.0)) return fail(MP_EINVAL, "mp_sampler_create: stretch scale a must exceed 1");
+        return MP_OK;
+    });
+    if (rc) return nullptr;
+    mp_sampler *s = new mp_sampler();
+    s->h = h; s->n_walkers = n_walkers; s->n_ensembles = n_ensembles; s->n_total = n_walkers * n_ensembles;
+    s->ndim = ndim; s->target = target; s->seed = seed; s->a = a;
+    DeviceScope scope(h->device);
+    const size_t nt = (size_t)s->n_total;
+    for (int e = 0; e < n_ensembles; ++e) s->ens_ds.push_back(ens_ds_id ? ens_ds_id[e] : 0);
+    constexpr size_t kBadRows = MP_BAD_WINDOW;   // device window of failed proposals between two drains (drain_bad)
+    if (s->d_pos.ensure(nt * ndim) || s->d_lnprob.ensure(nt) || s->d_acc.ensure(nt) || s->d_dsid.ensure(nt) ||
+        s->d_status.ensure(nt) || s->d_bad.ensure(kBadRows * ndim) || s->d_bad_count.ensure(1) ||
+        upload_ds_rows(s->d_dsid.p, ens_ds_id, n_ensembles, n_walkers) ||
+        hipMemset(s->d_acc.p, 0, nt * sizeof(int64_t)) != hipSuccess ||
+        hipMemset(s->d_bad_count.p, 0, sizeof(uint32_t)) != hipSuccess ||
+        hipEventCreateWithFlags(&s->win_copied[0].e, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&s->win_copied[1].e, hipEventDisableTiming) != hipSuccess) {
+        fail(MP_EHIP, "mp_sampler_create: device allocation failed");
+        mp_sampler_destroy(s);
+        return nullptr;
+    }
+    return s;
+}
+
+int mp_sampler_destroy(mp_sampler *s) {
+    if (!s) return MP_OK;
+    Lock lock(s->h->mu);
+    DeviceScope scope(s->h->device);
+    (void)hipDeviceSynchronize();
+    delete s;
+    return MP_OK;
+}
+
+int mp_sampler_set_temperatures(mp_sampler *s, int n_temps, const double *betas) {
+    if (!s || !betas) return fail(MP_EINVAL, "mp_sampler_set_temperatures: NULL argument");
+    Lock lock(s->h->mu);
+    if (s->have_state) return fail(MP_ESTATE, "mp_sampler_set_temperatures: call it before the first mp_sampler_set_positions");
+    if (n_temps < 2) return fail(MP_EINVAL, "mp_sampler_set_temperatures: a ladder needs at least 2 temperatures, got %d", n_temps);
+    if (s->n_ensembles % n_temps) return fail(MP_EINVAL, "mp_sampler_set_temperatures: %d ensembles are not groups of %d temperatures", s->n_ensembles, n_temps);
+    if (betas[0] != 1.0) return fail(MP_EINVAL, "mp_sampler_set_temperatures: betas[0] must be 1, got %g", betas[0]);
+    for (int t = 1; t < n_temps; ++t)
+        // (beta = 0 is refused: failed models have lnprob = -inf, and 0 x -inf is NaN)
+        if (!std::isfinite(betas[t]) || !(betas[t] > 0.0) || !(betas[t] < betas[t - 1]))
+            return fail(MP_EINVAL, "mp_sampler_set_temperatures: betas must be finite, > 0 and strictly decreasing (betas[%d] = %g)", t, betas[t]);
+    for (int e = 0; e < s->n_ensembles; ++e)
+        if (s->ens_ds[(size_t)e] != s->ens_ds[(size_t)(e - e % n_temps)])
+            return fail(MP_EINVAL, "mp_sampler_set_temperatures: ensembles %d and %d of one group have different datasets", e - e % n_temps, e);
+    DeviceScope scope(s->h->device);
+    std::vector<double> b((size_t)s->n_ensembles);
+    for (int e = 0; e < s->n_ensembles; ++e) b[(size_t)e] = betas[e % n_temps];
+    const size_t n_pairs = (size_t)(s->n_ensembles / n_temps) * (size_t)(n_temps - 1);
+    int rc;
+    if ((rc = s->d_beta.ensure(b.size())) || (rc = s->d_swaps.ensure(n_pairs))) return rc;
+    HIP_TRY(hipMemcpy(s->d_beta.p, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(s->d_swaps.p, 0, n_pairs * sizeof(int64_t)));
+    s->n_temps = n_temps;
+    return MP_OK;
+}
+
+int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const double *weights, const double *params) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_set_moves: NULL sampler");
+    if (n_moves < 0 || n_moves > MP_MAX_MOVES) return fail(MP_EINVAL, "mp_sampler_set_moves: n_moves must be in [0, %d], got %d", MP_MAX_MOVES, n_moves);
+    if (n_moves > 0 && (!kinds || !weights || !params)) return fail(MP_EINVAL, "mp_sampler_set_moves: NULL argument");
+    const int n_half = s->n_walkers / 2;
+    std::vector<mp_sampler::Move> mv;
+    std::vector<double> cum;
+    double c = 0.0;
+    for (int m = 0; m < n_moves; ++m) {
+        const double w = weights[m], p0 = params[2 * m], p1 = params[2 * m + 1];
+        if (!std::isfinite(w) || !(w > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: weight %d must be finite and > 0, got %g", m, w);
+        mp_sampler::Move x{kinds[m], 0.0, 0.0};
+        switch (kinds[m]) {
+        case MP_MOVE_STRETCH:
+            if (!std::isfinite(p0) || !(p0 > 1.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: stretch scale a must be finite and > 1, got %g", p0);
+            x.p0 = p0;
+            break;
+        case MP_MOVE_DE:
+            if (!std::isfinite(p0) || p0 < 0.0) return fail(MP_EINVAL, "mp_sampler_set_moves: DE g0 must be finite and >= 0 (0: 2.38/sqrt(2 ndim)), got %g", p0);
+            if (!(p1 >= 0.0) || !(p1 * std::sqrt(3.0) < 1.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: DE sigma must be in [0, 1/sqrt(3)), got %g", p1);
+            if (n_half < 2) return fail(MP_EINVAL, "mp_sampler_set_moves: the DE move needs n_walkers >= 4 (two partners in the other half)");
+            x.p0 = p0 > 0.0 ? p0 : 2.38 / std::sqrt(2.0 * s->ndim);
+            x.p1 = p1 * std::sqrt(3.0);
+            break;
+        case MP_MOVE_SNOOKER:
+            if (!std::isfinite(p0) || !(p0 > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: snooker gamma_s must be finite and > 0, got %g", p0);
+            if (n_half < 3) return fail(MP_EINVAL, "mp_sampler_set_moves: the snooker move needs n_walkers >= 6 (three partners in the other half)");
+            x.p0 = p0;
+            break;
+        case MP_MOVE_KDE: {
+            const int n_comp = s->n_walkers - n_half, d = s->ndim;
+            if (!(p0 == 0.0 || p0 == -1.0 || (std::isfinite(p0) && p0 > 0.0)))
+                return fail(MP_EINVAL, "mp_sampler_set_moves: KDE bandwidth must be 0 (Scott), -1 (Silverman) or a finite factor > 0, got %g", p0);
+            if (p1 != 0.0) return fail(MP_EINVAL, "mp_sampler_set_moves: KDE params[1] must be 0, got %g", p1);
+            if (n_comp < d + 1)
+                return fail(MP_EINVAL, "mp_sampler_set_moves: the KDE move needs n_walkers - n_walkers / 2 >= ndim + 1 (a full-rank covariance of the other half), got %d", n_comp);
+            // scipy.stats.gaussian_kde's scotts_factor / silverman_factor with neff = n_comp
+            x.p0 = p0 > 0.0 ? p0 : std::pow(p0 == 0.0 ? (double)n_comp : n_comp * (d + 2.0) / 4.0, -1.0 / (d + 4));
+            break;
+        }
+        default:
+            return fail(MP_EINVAL, "mp_sampler_set_moves: unknown move kind %d", (int)kinds[m]);
+        }
+        mv.push_back(x);
+        c += w;
+        cum.push_back(c);
+    }
+    Lock lock(s->h->mu);
+    s->moves = std::move(mv);
+    s->move_cum = std::move(cum);
+    return MP_OK;
+}
+
+int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted) {
+    if (!s || !n_swaps_accepted) return fail(MP_EINVAL, "mp_sampler_get_swaps: NULL argument");
+    Lock lock(s->h->mu);
+    if (!s->n_temps) return fail(MP_ESTATE, "mp_sampler_get_swaps: the sampler is not tempered (mp_sampler_set_temperatures)");
+    DeviceScope scope(s->h->device);
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t n_pairs = (size_t)(s->n_ensembles / s->n_temps) * (size_t)(s->n_temps - 1);
+    HIP_TRY(hipMemcpy(n_swaps_accepted, s->d_swaps.p, n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return MP_OK;
+}
+
+int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
+    if (!s || !pos) return fail(MP_EINVAL, "mp_sampler_set_positions: NULL argument");
+    mp_handle *h = s->h;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    const size_t nt = (size_t)s->n_total;
+    for (size_t i = 0; i < nt * s->ndim; ++i)
+        if (!std::isfinite(pos[i])) return fail(MP_EINVAL, "mp_sampler_set_positions: non-finite coordinate");
+    HIP_TRY(hipDeviceSynchronize());   // the sharded entry points may have work in flight on a caller's stream
+    s->ext_stream_work = false;
+    HIP_TRY(hipMemcpyAsync(s->d_pos.p, pos, nt * s->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (s->target == 1) {
+        std::vector<double> lp(nt, 0.0);
+        for (size_t k = 0; k < nt; ++k)
+            for (int i = 0; i < s->ndim; ++i) lp[k] -= 0.5 * pos[k * s->ndim + i] * pos[k * s->ndim + i];
+        HIP_TRY(hipMemcpyAsync(s->d_lnprob.p, lp.data(), nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    } else {
+        mp::LaunchArgs a{};
+        a.pars = s->d_pos.p; a.ds_id = s->d_dsid.p; a.n = s->n_total; a.ndim = s->ndim; a.want_chi2 = 1;
+        a.lnprob = s->d_lnprob.p; a.status = s->d_status.p;
+        const int rc = launch_lnprob_ordered(h, a, h->stream);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    s->have_state = true;
+    return MP_OK;
+}
+
+// Enqueue step steps_done + row of mp_sampler_run on the handle's stream: split d_perm, chain row `row` of the device slab when
+// chain is set, move mv (nullptr: the stretch move of mp_sampler_create).  A whole step per launch (stretch_step_kernel and the
+// commit kernel) where `whole` and the move is the stretch move, else two half-step launches; then the swap sweep when tempered.
+static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_sampler::Move *mv, bool chain, bool whole) {
+    mp_handle *h = s->h;
+    mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done + (uint64_t)row, 0);
+    g.chain = chain ? s->d_chain.p : nullptr;
+    g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
+    g.chain_row = row;
+    if (mv) {
+        g.move = mv->kind;
+        if (mv->kind == MP_MOVE_STRETCH) g.a = mv->p0;
+        else if (mv->kind == MP_MOVE_DE) { g.de_g0 = mv->p0; g.de_s = mv->p1; }
+        else if (mv->kind == MP_MOVE_SNOOKER) g.gamma_s = mv->p0;
+        else g.kde_f = mv->p0;
+    }
+    int e;
+    if (whole && g.move == MP_MOVE_STRETCH) {
+        g.spec = s->d_spec.p;
+        e = mp::launch_stretch_step(h->sh, g, 3 * g.n_half * g.n_ensembles, h->stream);
+        if (!e) e = mp::launch_stretch_step_commit(g, h->stream);
+    } else {
+        e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
+        g.half = 1;
+        if (!e) e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
+    }
+    if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    return MP_OK;
+}
+
+int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnprob) {
+    if (!s || n_steps < 0) return fail(MP_EINVAL, "mp_sampler_run: bad argument");
+    if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_run: call mp_sampler_set_positions first");
+    if ((chain == nullptr) != (chain_lnprob == nullptr)) return fail(MP_EINVAL, "mp_sampler_run: chain and chain_lnprob go together");
+    mp_handle *h = s->h;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    const size_t nt = (size_t)s->n_total, row = nt * s->ndim;
+    // chunks of steps so that the device-resident chain slab stays below ~256 MB, the splits below ~64 MB, and the
+    // window of failed proposals (drained after every chunk) overflows only if more than 1 in 32 proposals fails
+    const size_t perm_cap = std::max<size_t>(1, std::min<size_t>((size_t)16 << 20, (size_t)32 * MP_BAD_WINDOW) / nt);
+    const int chunk_max = (int)std::min<size_t>(
+        (size_t)std::max(n_steps, 1),
+        chain ? std::max<size_t>(1, std::min<size_t>(perm_cap, (256u << 20) / (row * sizeof(double)))) : perm_cap);
+    constexpr int kSub = 8;   // steps per batch of splits: the host draws the next batch while the GPU runs this one
+    int rc;
+    // A whole step per launch (mp_kernels.hip stretch_step_kernel: 3 n/2 evaluations, a third of them speculative) while
+    // that beats two half-step launches (mp_device.h stretch_whole_step_fits); larger ensembles fill the device with one half-step
+    // at a time.
+    const int n_slots = (s->n_walkers / 2) * s->n_ensembles;
+    const bool whole = s->whole_step && mp::stretch_whole_step_fits(h->sh, 3 * (long long)n_slots);
+    if (whole && (rc = s->d_spec.ensure((size_t)3 * n_slots * (size_t)(s->ndim + mp::kSpecExtra)))) return rc;
+    if (s->ext_stream_work) {   // sharded half-steps on a caller's stream may still be updating the state
+        HIP_TRY(hipDeviceSynchronize());
+        s->ext_stream_work = false;
+    }
+    for (int done = 0; done < n_steps;) {
+        const int chunk = std::min(chunk_max, n_steps - done);
+        if ((rc = s->h_perm.ensure((size_t)chunk * nt * sizeof(int32_t))) || (rc = s->d_perm.ensure((size_t)chunk * nt))) return rc;
+        int32_t *perm = (int32_t *)s->h_perm.p;
+        if (chain) {
+            if ((rc = s->d_chain.ensure((size_t)chunk * row)) || (rc = s->d_chain_lnp.ensure((size_t)chunk * nt))) return rc;
+        }
+        for (int sub = 0; sub < chunk; sub += kSub) {
+            const int sub_end = std::min(chunk, sub + kSub);
+            draw_splits(s, s->steps_done + (uint64_t)sub, sub_end - sub, perm + (size_t)sub * nt);
+            int step_move[kSub];   // with a move table: the move of every step of the batch, drawn next to its splits
+            for (int st = sub; st < sub_end; ++st) step_move[st - sub] = draw_move(s, s->steps_done + (uint64_t)st);
+            HIP_TRY(hipMemcpyAsync(s->d_perm.p + (size_t)sub * nt, perm + (size_t)sub * nt,
+                                   (size_t)(sub_end - sub) * nt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            for (int st = sub; st < sub_end; ++st) {
+                const mp_sampler::Move *mv = s->moves.empty() ? nullptr : &s->moves[(size_t)step_move[st - sub]];
+                if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, chain != nullptr, whole))) return rc;
+            }
+        }
+        if (chain) {
+            HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if ((rc = drain_bad(s))) return rc;
+        s->steps_done += (uint64_t)chunk;
+        done += chunk;
+    }
+    return MP_OK;
+}
+
+int mp_sampler_set_whole_step(mp_sampler *s, int enable) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_set_whole_step: NULL sampler");
+    Lock lock(s->h->mu);
+    s->whole_step = enable != 0;
+    return MP_OK;
+}
+
+// ---- walker-sharded driving: the caller (one process per GPU) runs, per half-step,
+//        mp_sampler_halfstep_shard(its block of slots) -> all-gather of the outcome rows -> mp_sampler_halfstep_apply.
+// Device pointer of the split of the current step; uploads the next window of kWin splits when the step enters it.
+static int current_split(mp_sampler *s, hipStream_t st, const int32_t **d_perm) {
+    const size_t nt = (size_t)s->n_total;
+    const int64_t win = (int64_t)(s->steps_done / mp_sampler::kWin);
+    const int b = (int)(win & 1);
+    if (s->win_id[b] != win) {
+        int rc;
+        const size_t bytes = (size_t)mp_sampler::kWin * nt * sizeof(int32_t);
+        if ((rc = s->h_win[b].ensure(bytes)) || (rc = s->d_win[b].ensure((size_t)mp_sampler::kWin * nt))) return rc;
+        if (s->win_id[b] >= 0) HIP_TRY(hipEventSynchronize(s->win_copied[b].e));   // staged two windows ago: long done
+        int32_t *perm = (int32_t *)s->h_win[b].p;
+        draw_splits(s, (uint64_t)win * mp_sampler::kWin, mp_sampler::kWin, perm);
+        // stream order puts the copy behind every kernel that still reads this buffer's previous contents
+        HIP_TRY(hipMemcpyAsync(s->d_win[b].p, perm, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(s->win_copied[b].e, st));
+        s->win_id[b] = win;
+    }
+    *d_perm = s->d_win[b].p + (size_t)(s->steps_done % mp_sampler::kWin) * nt;
+    return MP_OK;
+}
+
+int mp_sampler_row_doubles(const mp_sampler *s) { return s ? s->ndim + 3 : 0; }
+int mp_sampler_n_slots(const mp_sampler *s) { return s ? (s->n_walkers / 2) * s->n_ensembles : 0; }
+
+// The prologue of the four sharded entry points (fn: the entry point, which every message starts with): a sampler without state,
+// a tempered one and one with a move table are refused (those run through mp_sampler_run only); otherwise the handle's lock and
+// device are held for the call, d_perm is the split of the current step and the sampler notes work on a caller's stream.
+struct ShardCall {
+    Lock lock;
+    DeviceScope scope;
+    const int32_t *d_perm = nullptr;
+    int rc = MP_OK;
+    ShardCall(mp_sampler *s, const char *fn, void *stream) : lock(s->h->mu), scope(s->h->device) {
+        if (!s->have_state) rc = fail(MP_ESTATE, "%s: call mp_sampler_set_positions first", fn);
+        else if (s->n_temps) rc = fail(MP_ESTATE, "%s: a tempered sampler runs on one device only (mp_sampler_run)", fn);
+        else if (!s->moves.empty())
+            rc = fail(MP_ESTATE, "%s: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)", fn);
+        else if (!(rc = current_split(s, (hipStream_t)stream, &d_perm))) s->ext_stream_work = true;
+    }
+};
+
+int mp_sampler_halfstep_shard(mp_sampler *s, int half, int slot_lo, int slot_hi, double *d_rows, void *stream) {
+    if (!s || (half != 0 && half != 1)) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: bad argument");
+    ShardCall c(s, "mp_sampler_halfstep_shard", stream);
+    if (c.rc) return c.rc;
+    const int n_slots = (s->n_walkers / 2) * s->n_ensembles;
+    if (slot_lo < 0 || slot_hi > n_slots || slot_lo > slot_hi) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: slots [%d, %d) outside [0, %d)", slot_lo, slot_hi, n_slots);
+    if (slot_hi > slot_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_halfstep_shard: NULL row buffer");
+    if (slot_hi == slot_lo) return MP_OK;
+    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, half);
+    g.upd = d_rows;
+    g.slot_lo = slot_lo;
+    const int e = mp::launch_stretch(s->h->sh, g, slot_hi - slot_lo, stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    return MP_OK;
+}
+
+int mp_sampler_halfstep_apply(mp_sampler *s, int half, const double *d_rows, double *d_chain_row, double *d_chain_lnp_row,
+                              void *stream) {
+    if (!s || !d_rows || (half != 0 && half != 1)) return fail(MP_EINVAL, "mp_sampler_halfstep_apply: bad argument");
+    if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_halfstep_apply: chain row and lnprob row go together");
+    ShardCall c(s, "mp_sampler_halfstep_apply", stream);
+    if (c.rc) return c.rc;
+    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, half);
+    g.upd = const_cast<double *>(d_rows);
+    g.chain = d_chain_row;
+    g.chain_lnp = d_chain_lnp_row;
+    g.chain_row = 0;
+    const int e = mp::launch_stretch_apply(g, stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (half == 1) s->steps_done += 1;
+    return MP_OK;
+}
+
+// ---- the same for a whole step per launch (mp_kernels.hip stretch_step_kernel): the caller runs, per STEP,
+//        mp_sampler_step_shard(its share of the 3 * n_slots blocks) -> ONE all-gather of the rows -> mp_sampler_step_apply.
+int mp_sampler_step_blocks(const mp_sampler *s) { return s ? 3 * (s->n_walkers / 2) * s->n_ensembles : 0; }
+int mp_sampler_step_row_doubles(const mp_sampler *s) { return s ? s->ndim + mp::kSpecExtra : 0; }
+
+int mp_sampler_step_shard(mp_sampler *s, int block_lo, int block_hi, double *d_rows, void *stream) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL sampler");
+    ShardCall c(s, "mp_sampler_step_shard", stream);
+    if (c.rc) return c.rc;
+    const int n_blocks = 3 * (s->n_walkers / 2) * s->n_ensembles;
+    if (block_lo < 0 || block_hi > n_blocks || block_lo > block_hi) return fail(MP_EINVAL, "mp_sampler_step_shard: blocks [%d, %d) outside [0, %d)", block_lo, block_hi, n_blocks);
+    if (block_hi > block_lo && !d_rows) return fail(MP_EINVAL, "mp_sampler_step_shard: NULL row buffer");
+    if (block_hi == block_lo) return MP_OK;
+    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, 0);
+    g.spec = d_rows;
+    g.slot_lo = block_lo;
+    const int e = mp::launch_stretch_step(s->h->sh, g, block_hi - block_lo, stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    return MP_OK;
+}
+
+int mp_sampler_step_apply(mp_sampler *s, const double *d_rows, double *d_chain_row, double *d_chain_lnp_row, void *stream) {
+    if (!s || !d_rows) return fail(MP_EINVAL, "mp_sampler_step_apply: bad argument");
+    if ((d_chain_row == nullptr) != (d_chain_lnp_row == nullptr)) return fail(MP_EINVAL, "mp_sampler_step_apply: chain row and lnprob row go together");
+    ShardCall c(s, "mp_sampler_step_apply", stream);
+    if (c.rc) return c.rc;
+    mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, 0);
+    g.spec = const_cast<double *>(d_rows);
+    g.chain = d_chain_row;
+    g.chain_lnp = d_chain_lnp_row;
+    g.chain_row = 0;
+    const int e = mp::launch_stretch_step_commit(g, stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    s->steps_done += 1;
+    return MP_OK;
+}
+
+int mp_sampler_state_ptrs(mp_sampler *s, double **d_pos, double **d_lnprob) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_state_ptrs: NULL sampler");
+    if (d_pos) *d_pos = s->d_pos.p;
+    if (d_lnprob) *d_lnprob = s->d_lnprob.p;
+    return MP_OK;
+}
+
+int mp_sampler_get_bad(mp_sampler *s, int64_t first_row, double *pars, int max_rows, int64_t *n_bad, int64_t *n_logged) {
+    if (!s || max_rows < 0 || first_row < 0 || (max_rows > 0 && !pars)) return fail(MP_EINVAL, "mp_sampler_get_bad: bad argument");
+    mp_handle *h = s->h;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    HIP_TRY(hipDeviceSynchronize());
+    const int rc = drain_bad(s);
+    if (rc) return rc;
+    const int64_t logged = (int64_t)(s->bad_log.size() / (size_t)s->ndim);
+    if (n_bad) *n_bad = s->n_bad;
+    if (n_logged) *n_logged = logged;
+    const int64_t rows = std::max<int64_t>(0, std::min<int64_t>(logged - first_row, (int64_t)max_rows));
+    if (rows) std::memcpy(pars, s->bad_log.data() + (size_t)first_row * s->ndim, (size_t)rows * s->ndim * sizeof(double));
+    return (int)rows;
+}
+
+int mp_sampler_get_state(mp_sampler *s, double *pos, double *lnprob, int64_t *n_accepted, int64_t *steps_done) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_state: NULL sampler");
+    mp_handle *h = s->h;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    const size_t nt = (size_t)s->n_total;
+    HIP_TRY(hipDeviceSynchronize());
+    const int rc = read_back(pos, s->d_pos.p, nt * s->ndim, lnprob, s->d_lnprob.p, nt, n_accepted, s->d_acc.p, nt);
+    if (rc) return rc;
+    if (steps_done) *steps_done = (int64_t)s->steps_done;
+    return MP_OK;
+}
+
+}  // extern "C"
