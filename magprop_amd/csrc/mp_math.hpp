@@ -230,7 +230,8 @@ MP_DEV void horner2(Vd<N> &p, const Vd<N> &x, int k) {
 
 // Hand-rolled for this kernel's argument ranges (positive, normal, far from overflow): hardware
 // seed (v_rcp_f64 / v_rsq_f64, ~2^-23) + ONE third-order correction step, without the scaling / fix-up code the
-// general-purpose library versions carry.  All are accurate to ~1-2 ulp.
+// general-purpose library versions carry.  Held to 2 ulp over the whole domain (tests/test_gpu_math.py); measured on an MI355X
+// against multiprecision values: rcp 0.50, rsqrt 0.90, rcbrt 0.66, pow_m1_7 0.62 ulp at worst.
 template <int N>
 MP_DEV Vd<N> rcp_fast(const Vd<N> &x) {
     // one third-order step from the hardware seed: e = 1 - x r,  r <- r (1 + e + e^2)
@@ -256,7 +257,9 @@ MP_DEV Vd<N> rsqrt_fast(const Vd<N> &x) {
     return y;
 }
 
-// e^x for x in [-750, 700]; underflows cleanly to 0 below
+// e^x for x in [-750, 700]; underflows cleanly to 0 below.  The degree-12 Taylor polynomial is good to 1.7e-16 on the reduced
+// argument; the result to 2.26 ulp at worst (next to odd multiples of ln2 / 2, where the result sits just below a power of two),
+// subnormal results to one unit of 2^-1074.  Every operation is an IEEE one: tests/math_restated.py reproduces it bit for bit.
 template <int N>
 MP_DEV Vd<N> exp_fast(const Vd<N> &x) {
     Vd<N> k, r, p;
@@ -297,21 +300,46 @@ MP_DEV Vd<N> exp_fast(const Vd<N> &x) {
     return p;
 }
 
-// 10^x (un-logging of the sampler coordinates, code/synthetic_datasets/mcmc_eqns.py:16-17) as e^(x ln 10) with the
-// product carried in two parts; ~2 ulp, a twentieth of the instructions of the general-purpose pow()
+// 10^x (un-logging of the sampler coordinates, code/synthetic_datasets/mcmc_eqns.py:16-17) as e^(x ln 10), the product and
+// the reduced argument carried in two parts.  Held to 2 ulp (tests/test_gpu_math.py); e^r is summed as 1 + (r + r^2 q(r)) with
+// the Taylor series to degree 14, so that only the last two additions round at the size of the result: 0.8 ulp at worst over
+// the prior boxes and over [-300, 300].  (exp_fast on the same argument reaches 2.5 ulp here: its degree-12 polynomial alone is
+// 1.5 ulp off at the ends of the reduced range.)  One scalar call per log-masked coordinate and walker: its cost does not show.
+// Every operation is an IEEE one and none is left to contraction: tests/math_restated.py reproduces it.
 MP_DEV double exp10_fast(double x) {
     const double hi = x * 2.302585092994046;
-    const double lo = fma(x, 2.302585092994046, -hi) + x * -2.1707562233822494e-16;
-    const Vd<1> a{{fmin(fmax(hi, -750.0), 709.0)}};
-    const double e = exp_fast(a)[0];
-    return fma(e, lo, e);
+    const double lo = fma(x, -2.1707562233822494e-16, fma(x, 2.302585092994046, -hi));
+    const double a = fmin(fmax(hi, -750.0), 709.0);
+    const double k = __builtin_rint(a * 1.4426950408889634074);
+    const double r0 = fma(k, -6.93147180369123816490e-01, a);
+    const double d = fma(k, -1.90821492927058770002e-10, lo);
+    const double r = r0 + d;
+    const double t = (r0 - r) + d;                   // what the sum above dropped
+    double q = 1.0 / 87178291200.0;                  // (e^r - 1 - r) / r^2 to r^12 / 14!
+    q = fma(q, r, 1.0 / 6227020800.0);
+    q = fma(q, r, 1.0 / 479001600.0);
+    q = fma(q, r, 1.0 / 39916800.0);
+    q = fma(q, r, 1.0 / 3628800.0);
+    q = fma(q, r, 1.0 / 362880.0);
+    q = fma(q, r, 1.0 / 40320.0);
+    q = fma(q, r, 1.0 / 5040.0);
+    q = fma(q, r, 1.0 / 720.0);
+    q = fma(q, r, 1.0 / 120.0);
+    q = fma(q, r, 1.0 / 24.0);
+    q = fma(q, r, 1.0 / 6.0);
+    q = fma(q, r, 0.5);
+    const double rr = r * r;
+    const double s = fma(rr, q, fma(t, r, t));       // r^2 q + t (1 + r)
+    const double u = r + s;
+    return ldexp(1.0 + u, (int)k);
 }
 
 // x^(-1/3) for positive normal x within float range: v_log_f32/v_exp_f32 seed (~1e-6) + one fourth-order step
 template <int N>
 MP_DEV Vd<N> rcbrt_fast(const Vd<N> &x) {
     // one fourth-order step: e = 1 - x y^3,  y <- y (1 - e)^(-1/3) = y (1 + e/3 + 2 e^2/9 + 14 e^3/81 + ...)
-    // (the f32 log/exp seed is good to ~4e-6 for arguments up to 1e30, so e <~ 1.2e-5 and the e^4 term is < 1e-19)
+    // (the f32 log/exp seed is good to ~4e-6 over the whole normal float range, 2^-126 .. 2^127, so e <~ 1.2e-5 and the e^4 term
+    // is < 1e-19)
     Vd<N> y, y3, e, p;
     FORN y[i] = (double)__builtin_amdgcn_exp2f(-0.33333333f * __builtin_amdgcn_logf((float)x[i]));
     FORN y3[i] = y[i] * y[i];
@@ -348,7 +376,10 @@ MP_DEV Vd<N> pow_m1_7_fast(const Vd<N> &x) {
 // order-5 exponential Adams-Moulton formula: h * int_0^1 e^{z(1-theta)} P(theta) dtheta for the quartic P through the node
 // values at t_{j+1}, t_j, ..., t_{j-3} (quadrature matrix W5 of the tile's kind, LDS table).
 // phi_1..phi_5 of z = h*lambda.  Taylor series of phi_5: 7 terms when every |z| of the wavefront is below 1/32 (< 1e-17
-// relative), 13 terms for |z| < 1/2, closed forms elsewhere.
+// relative), 13 terms for |z| < 1/2, closed forms elsewhere.  Measured against multiprecision values: both
+// series give e^z and phi_1 .. phi_5 to 1.4e-16.  The closed forms are a cancelling recurrence that loses about 1/|z| per stage:
+// phi_1 .. phi_5 to 2.9e-16, 8.7e-16, 5.5e-15, 4.3e-14, 4.2e-13 on [1/2, 1), to 3.0e-16 .. 3.6e-14 on [1, 4), to 6.8e-16 on
+// [4, 40) and to 5.7e-16 beyond.  The thresholds are part of every pinned result: do not move them.
 template <int N>
 struct Phi5 {
     Vd<N> e, p1, p2, p3, p4, p5;
@@ -364,7 +395,7 @@ template <int N>
 MP_DEV Phi5<N> phi12345(const Vd<N> &z) {
     Vd<N> s;
     const double zmax = lane_maxabs(z.v);          // the lane's largest |z|: one comparison per range instead of one per step
-    const bool all_tiny = zmax < 0.03125;
+    const bool all_tiny = !(zmax >= 0.03125);      // (a lane whose z are all NaN does not change the series the others take)
     double inv6 = 1.0 / 6.0, inv24 = 1.0 / 24.0;
 #if MP_PHI_ALL_BIG
     // Every step of the wave in the stiff range (|z| >= 1/2: the tiles over 8 grid intervals from t ~ 20 s on): the recurrence
@@ -379,6 +410,7 @@ MP_DEV Phi5<N> phi12345(const Vd<N> &z) {
         const Vd<N> rz = rcp_fast(z);
         FORN {
             r.p1[i] = (r.e[i] - 1.0) * rz[i];
+            r.e[i] = fma(rz[i], 0.0, r.e[i]);   // e^z + 0: fmax above made e^NaN = e^-750; 1/NaN makes it a NaN again (off the phi chain)
             r.p2[i] = (r.p1[i] - 1.0) * rz[i];
             r.p3[i] = (r.p2[i] - 0.5) * rz[i];
             r.p4[i] = (r.p3[i] - inv6) * rz[i];
@@ -463,7 +495,7 @@ MP_DEV Phi5<N> phi12345(const Vd<N> &z) {
             const double c3 = (c2 - 0.5) * rz[i];
             const double c4 = (c3 - inv6) * rz[i];
             const double c5 = (c4 - inv24) * rz[i];
-            r.e[i] = big[i] ? ce[i] : r.e[i];
+            r.e[i] = big[i] ? fma(rz[i], 0.0, ce[i]) : r.e[i];   // (+ 0 x 1/z: a NaN z gives a NaN e^z, as above)
             r.p1[i] = big[i] ? c1 : r.p1[i];
             r.p2[i] = big[i] ? c2 : r.p2[i];
             r.p3[i] = big[i] ? c3 : r.p3[i];
@@ -475,7 +507,8 @@ MP_DEV Phi5<N> phi12345(const Vd<N> &z) {
 }
 
 // phi_6(z) next to a Phi5 of the same z (the Mdisc step, once per tile): Taylor series below |z| = 1/2 (12 terms, < 1e-16
-// relative), the recurrence phi_6 = (phi_5 - 1/5!)/z elsewhere.
+// relative; measured 1.2e-16), the recurrence phi_6 = (phi_5 - 1/5!)/z elsewhere (5.0e-12 at |z| = 1/2, 2.1e-13 on [1, 4), 1.1e-15 on
+// [4, 40), 6.6e-16 beyond).
 template <int N>
 MP_DEV Vd<N> phi6(const Vd<N> &z, const Phi5<N> &p) {
     Vd<N> s;

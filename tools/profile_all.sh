@@ -13,5 +13,6 @@ fi
 if [ $PART = a ]; then echo done; exit 0; fi
 KERN=lnprob_kernel    bash tools/profile.sh ${R}_curve1024 --curve --no-mcmc > /dev/null || exit 4
 KERN=lnprob_kernel    bash tools/profile.sh ${R}_config5 --config 5 > /dev/null || exit 5
+KERN=lnprob_team_kernel bash tools/profile.sh ${R}_config5_n512 --config 5 --nwalk 512 --no-mcmc > /dev/null || exit 9
 KERN=stretch_step_kernel bash tools/profile.sh ${R}_stretch_step1536 --steps 2 --warmup 1 --mcmc-steps 60 > /dev/null || exit 7
 echo done
