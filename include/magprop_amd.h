@@ -400,6 +400,50 @@ int mp_sampler_step_apply(mp_sampler *s, const double *d_rows, double *d_chain_r
 int mp_sampler_state_ptrs(mp_sampler *s, double **d_pos, double **d_lnprob);
 
 /*
+ * Autocorrelation monitor (ABI 5, additive): the integrated autocorrelation time that emcee's get_autocorr_time() reports
+ * (Sokal's automatic window, Goodman & Weare 2010; code/synthetic_datasets/synth_mcmc.py:216), accumulated on the device while
+ * mp_sampler_run runs.  Off by default; while it is off nothing about the sampler changes.
+ * A series is one coordinate d of one walker w of one ensemble e: the positions the sampler writes to its chain row, in sampler
+ * coordinates.  Sample t = 0 is the first step `discard` steps after the monitor was (re)started, n the number of samples so far.
+ * With the pivot p = x_0, y_t = x_t - p and K = max_lag the monitor keeps, per series and for the lags k = 0 .. K - 1,
+ *     S_k = sum_{t >= k} y_t y_{t-k},   T = sum_t y_t,   the head sums H_k = sum_{t < k} y_t,   the last K values of y,
+ * whose sums give the tails L_k = sum_{t >= n - k} y_t.  Every sum runs in increasing t from 0.0, and every product, sum and
+ * difference is rounded on its own (no FMA), so the accumulators are a function of the sample sequence alone: they do not depend
+ * on how mp_sampler_run chunks its steps or on how a run was split into calls, and a numpy restatement reproduces them bit for bit.
+ * Finalisation is emcee's estimator in moment form:
+ *     m = T / n,   c_k = (S_k - m ((2 T - H_k) - L_k)) + (n - k) (m m),   rho_k = c_k / c_0 (0 where c_0 = 0),
+ *     f_k = (sum of rho_k over the ensemble's walkers in walker order) / n_walkers,
+ *     taus_M = 2 (f_0 + ... + f_M) - 1 (summed in lag order),   window = the smallest M for which M < c taus_M is false,
+ *     tau = taus_window.
+ * Lags below min(K, n) are known.  Where none of them is a window: with n <= K the window is the last lag n - 1 (what the host
+ * estimator magprop_amd.mcmc_io.integrated_time falls back to); with n > K tau is NaN and the window -1: max_lag was too small,
+ * and a truncated sum is never returned as a number.
+ *
+ * mp_sampler_set_autocorr(s, max_lag, discard): max_lag = 0 turns the monitor off and frees it; 1 .. MP_ACF_MAX_LAG (re)starts
+ * it empty, accumulation beginning `discard` (>= 0) steps from now.  MP_EINVAL: max_lag or discard out of range, or accumulators
+ * (the ring of kept values, S, H and the finalisation's work array: about 4 max_lag + the rows of 64 MB of chain, times 8 bytes,
+ * per series) beyond MP_ACF_MAX_BYTES; the monitor is then off.
+ * While the monitor is on: mp_sampler_run writes its chain rows to the device slab also when `chain` is NULL (nothing is copied
+ * to the host then) and feeds the monitor once per chunk, on the handle's stream, behind the chunk's last step;
+ * mp_sampler_set_positions restarts the monitor (the series is broken; `discard` applies again); the walker-sharded entry points
+ * (mp_sampler_halfstep_*, mp_sampler_step_*) do not feed it and return MP_ESTATE.
+ * mp_sampler_get_autocorr: tau[n_ensembles][ndim], window[n_ensembles][ndim] (either may be NULL) for the window constant c
+ * (emcee's default 5); *n_samples = n (optional).  MP_ESTATE without a monitor or with n < 2.
+ * mp_sampler_get_acf: the walker-mean f_k of one ensemble, acf[rows][ndim] with rows = min(max_rows, max_lag, n), which it returns
+ * (or a negative MP_E* code; MP_ESTATE as above).
+ * mp_sampler_get_autocorr_sums: the raw accumulators of one ensemble (tests): S[max_lag][n_walkers][ndim], T[n_walkers][ndim],
+ * H[max_lag][n_walkers][ndim] (H_k = T for k > n), tail[max_lag][n_walkers][ndim] (row i is y_{n - max_lag + i}; zeros before
+ * sample 0), pivot[n_walkers][ndim]; any may be NULL.  MP_ESTATE without a monitor.
+ */
+#define MP_ACF_MAX_LAG 4096
+#define MP_ACF_MAX_BYTES 8589934592   /* 8 GiB */
+int mp_sampler_set_autocorr(mp_sampler *s, int max_lag, int64_t discard);
+int mp_sampler_get_autocorr(mp_sampler *s, double c, double *tau, int32_t *window, int64_t *n_samples);
+int mp_sampler_get_acf(mp_sampler *s, int ensemble, int max_rows, double *acf);
+int mp_sampler_get_autocorr_sums(mp_sampler *s, int ensemble, double *S, double *T, double *H, double *tail, double *pivot,
+                                 int64_t *n_samples);
+
+/*
  * Differential-evolution optimizer (ABI 5, additive): scipy.optimize.differential_evolution with deferred updating, without
  * the polish step, every generation one launch that builds, evaluates and judges every trial (plus one small reduction).
  * n_pops populations of popsize members each (5 <= popsize <= 1024, 1 <= n_pops <= MP_MAX_DATASETS); population p runs on

@@ -24,6 +24,7 @@ BAND_COMPONENTS = {"Ltot": BAND_LTOT, "Lprop": BAND_LPROP, "Ldip": BAND_LDIP}
 DE_BEST1BIN, DE_RAND1BIN = 0, 1                               # include/magprop_amd.h MP_DE_*
 NEST_MIN_LIVE, NEST_MAX_LIVE, NEST_MAX_WALKS = 16, 4096, 4096  # include/magprop_amd.h MP_NEST_*
 NEST_MAX_SLICES, NEST_MAX_STEPS_OUT, NEST_MAX_SHRINK = 4096, 4096, 254
+ACF_MAX_LAG, ACF_MAX_BYTES = 4096, 8 << 30                    # include/magprop_amd.h MP_ACF_*
 
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -85,6 +86,10 @@ SIGNATURES = {
     "mp_sampler_step_shard": (_i, [_vp, _i, _i, _vp, _vp]),
     "mp_sampler_step_apply": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mp_sampler_state_ptrs": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "mp_sampler_set_autocorr": (_i, [_vp, _i, _i64]),
+    "mp_sampler_get_autocorr": (_i, [_vp, _d, _dp, _ip, _i64p]),
+    "mp_sampler_get_acf": (_i, [_vp, _i, _i, _dp]),
+    "mp_sampler_get_autocorr_sums": (_i, [_vp, _i, _dp, _dp, _dp, _dp, _dp, _i64p]),
     "mp_optimizer_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _i, _d, _d, _d, _d, _d, _dp, _dp, _i]),
     "mp_optimizer_set_population": (_i, [_vp, _dp]),
     "mp_optimizer_run": (_i, [_vp, _i, _ip]),

@@ -1,8 +1,22 @@
 // mp_sampler.cpp — the device-resident ensemble sampler (mp_sampler_*): stretch, DE, snooker and KDE moves, tempering, whole-step
 // and walker-sharded driving.  Kernels: mp_kernels.hip.
+#include <memory>
 #include <thread>
 
+#include "mp_acf.h"
 #include "mp_host.h"
+
+// The autocorrelation monitor (mp_sampler_set_autocorr): accumulators and the history ring of mp_acf.h, fed once per chunk of
+// mp_sampler_run from the device slab of chain rows.
+struct AcfMonitor {
+    int max_lag = 0, kp = 0;        // lags asked for; rounded up to the kernels' lag block
+    int chunk_cap = 0;              // most steps per chunk of mp_sampler_run while the monitor is on
+    int ring_rows = 0, head = 0;    // the ring: kp + chunk_cap rows; row of the next sample
+    int64_t n = 0;                  // samples accumulated
+    int64_t discard = 0, skip = 0;  // steps to pass over after a (re)start; how many of them are left
+    DevBuf<double> hist, S, T, H, pivot, rho, f, tau;
+    DevBuf<int32_t> window;
+};
 
 struct mp_sampler {
     mp_handle *h = nullptr;
@@ -39,7 +53,59 @@ struct mp_sampler {
     };
     std::vector<Move> moves;
     std::vector<double> move_cum;   // cumulative weights, summed in order
+    std::unique_ptr<AcfMonitor> acf;   // the autocorrelation monitor; null: off
 };
+
+// Steps per chunk of mp_sampler_run when chain rows go to the device slab: the slab stays below ~256 MB
+static size_t slab_chunk_cap(const mp_sampler *s, size_t perm_cap) {
+    const size_t row = (size_t)s->n_total * s->ndim;
+    return std::max<size_t>(1, std::min<size_t>(perm_cap, (256u << 20) / (row * sizeof(double))));
+}
+static size_t perm_chunk_cap(const mp_sampler *s) {
+    return std::max<size_t>(1, std::min<size_t>((size_t)16 << 20, (size_t)32 * MP_BAD_WINDOW) / (size_t)s->n_total);
+}
+
+static mp::AcfArgs acf_args(const mp_sampler *s) {
+    const AcfMonitor *m = s->acf.get();
+    mp::AcfArgs a{};
+    a.chain = s->d_chain.p; a.hist = m->hist.p; a.S = m->S.p; a.T = m->T.p; a.H = m->H.p; a.pivot = m->pivot.p;
+    a.rho = m->rho.p; a.f = m->f.p; a.tau = m->tau.p; a.window = m->window.p;
+    a.n_series = s->n_total * s->ndim; a.n_walkers = s->n_walkers; a.n_ensembles = s->n_ensembles; a.ndim = s->ndim;
+    a.kp = m->kp; a.max_lag = m->max_lag; a.ring_rows = m->ring_rows; a.head = m->head; a.n0 = m->n;
+    return a;
+}
+
+// Empty the monitor (stream-ordered on the handle's stream): the series starts again, `discard` steps from now.
+static int acf_restart(mp_sampler *s) {
+    AcfMonitor *m = s->acf.get();
+    const size_t ns = (size_t)s->n_total * s->ndim;
+    hipStream_t st = s->h->stream;
+    HIP_TRY(hipMemsetAsync(m->hist.p, 0, (size_t)m->ring_rows * ns * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(m->S.p, 0, (size_t)m->kp * ns * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(m->H.p, 0, (size_t)m->kp * ns * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(m->T.p, 0, ns * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(m->pivot.p, 0, ns * sizeof(double), st));
+    m->n = 0;
+    m->head = 0;
+    m->skip = m->discard;
+    return MP_OK;
+}
+
+// The chunk's `chunk` rows of the device slab into the monitor, behind the chunk's last step on the handle's stream.
+static int acf_feed(mp_sampler *s, int chunk) {
+    AcfMonitor *m = s->acf.get();
+    const int first = (int)std::min<int64_t>(m->skip, chunk);
+    m->skip -= first;
+    if (first == chunk) return MP_OK;
+    mp::AcfArgs a = acf_args(s);
+    a.first = first;
+    a.rows = chunk - first;
+    const int e = mp::launch_acf_accumulate(a, s->h->stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    m->head = (m->head + a.rows) % m->ring_rows;
+    m->n += a.rows;
+    return MP_OK;
+}
 
 // Move the device window of failed proposals into the host log and reset it.  The caller has made sure that no kernel
 // of this sampler is in flight.
@@ -286,6 +352,7 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     s->have_state = true;
+    if (s->acf) return acf_restart(s);   // the series is broken
     return MP_OK;
 }
 
@@ -330,10 +397,10 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
     const size_t nt = (size_t)s->n_total, row = nt * s->ndim;
     // chunks of steps so that the device-resident chain slab stays below ~256 MB, the splits below ~64 MB, and the
     // window of failed proposals (drained after every chunk) overflows only if more than 1 in 32 proposals fails
-    const size_t perm_cap = std::max<size_t>(1, std::min<size_t>((size_t)16 << 20, (size_t)32 * MP_BAD_WINDOW) / nt);
-    const int chunk_max = (int)std::min<size_t>(
-        (size_t)std::max(n_steps, 1),
-        chain ? std::max<size_t>(1, std::min<size_t>(perm_cap, (256u << 20) / (row * sizeof(double)))) : perm_cap);
+    const size_t perm_cap = perm_chunk_cap(s);
+    const bool monitor = s->acf != nullptr, slab = chain || monitor;   // the monitor reads the chain rows from the device slab
+    int chunk_max = (int)std::min<size_t>((size_t)std::max(n_steps, 1), slab ? slab_chunk_cap(s, perm_cap) : perm_cap);
+    if (monitor) chunk_max = std::min(chunk_max, s->acf->chunk_cap);
     constexpr int kSub = 8;   // steps per batch of splits: the host draws the next batch while the GPU runs this one
     int rc;
     // A whole step per launch (mp_kernels.hip stretch_step_kernel: 3 n/2 evaluations, a third of them speculative) while
@@ -350,7 +417,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
         const int chunk = std::min(chunk_max, n_steps - done);
         if ((rc = s->h_perm.ensure((size_t)chunk * nt * sizeof(int32_t))) || (rc = s->d_perm.ensure((size_t)chunk * nt))) return rc;
         int32_t *perm = (int32_t *)s->h_perm.p;
-        if (chain) {
+        if (slab) {
             if ((rc = s->d_chain.ensure((size_t)chunk * row)) || (rc = s->d_chain_lnp.ensure((size_t)chunk * nt))) return rc;
         }
         for (int sub = 0; sub < chunk; sub += kSub) {
@@ -362,9 +429,10 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
                                    (size_t)(sub_end - sub) * nt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
             for (int st = sub; st < sub_end; ++st) {
                 const mp_sampler::Move *mv = s->moves.empty() ? nullptr : &s->moves[(size_t)step_move[st - sub]];
-                if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, chain != nullptr, whole))) return rc;
+                if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, slab, whole))) return rc;
             }
         }
+        if (monitor && (rc = acf_feed(s, chunk))) return rc;
         if (chain) {
             HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -374,6 +442,115 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
         s->steps_done += (uint64_t)chunk;
         done += chunk;
     }
+    return MP_OK;
+}
+
+// ---- autocorrelation monitor
+int mp_sampler_set_autocorr(mp_sampler *s, int max_lag, int64_t discard) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_set_autocorr: NULL sampler");
+    if (max_lag < 0 || max_lag > MP_ACF_MAX_LAG) return fail(MP_EINVAL, "mp_sampler_set_autocorr: max_lag must be in [0, %d] (MP_ACF_MAX_LAG; 0 turns the monitor off), got %d", MP_ACF_MAX_LAG, max_lag);
+    if (discard < 0) return fail(MP_EINVAL, "mp_sampler_set_autocorr: discard must be >= 0, got %lld", (long long)discard);
+    mp_handle *h = s->h;
+    Lock lock(h->mu);
+    DeviceScope scope(h->device);
+    HIP_TRY(hipDeviceSynchronize());
+    s->acf.reset();
+    if (max_lag == 0) return MP_OK;
+    const size_t ns = (size_t)s->n_total * s->ndim;
+    const int kp = (max_lag + mp::kAcfLagBlock - 1) / mp::kAcfLagBlock * mp::kAcfLagBlock;
+    // chunks of at most 64 MB of chain rows while the monitor is on: the ring holds one chunk behind the kp rows it keeps
+    const size_t cap = std::max<size_t>(1, std::min<size_t>(slab_chunk_cap(s, perm_chunk_cap(s)), ((size_t)64 << 20) / (ns * sizeof(double))));
+    const size_t ring = (size_t)kp + cap;
+    const double bytes = ((double)ring + 3.0 * kp + 2.0) * (double)ns * sizeof(double);   // ring, S, H, rho, T, pivot
+    if (bytes > (double)MP_ACF_MAX_BYTES)
+        return fail(MP_EINVAL, "mp_sampler_set_autocorr: max_lag = %d over %zu series needs %.0f bytes of accumulators, more than MP_ACF_MAX_BYTES = %lld: lower max_lag",
+                    max_lag, ns, bytes, (long long)MP_ACF_MAX_BYTES);
+    std::unique_ptr<AcfMonitor> m(new AcfMonitor());
+    m->max_lag = max_lag; m->kp = kp; m->chunk_cap = (int)cap; m->ring_rows = (int)ring; m->discard = discard;
+    const size_t ned = (size_t)s->n_ensembles * s->ndim;
+    int rc;
+    if ((rc = m->hist.ensure(ring * ns)) || (rc = m->S.ensure((size_t)kp * ns)) || (rc = m->H.ensure((size_t)kp * ns)) ||
+        (rc = m->rho.ensure((size_t)kp * ns)) || (rc = m->T.ensure(ns)) || (rc = m->pivot.ensure(ns)) ||
+        (rc = m->f.ensure(ned * kp)) || (rc = m->tau.ensure(ned)) || (rc = m->window.ensure(ned)))
+        return rc;
+    s->acf = std::move(m);
+    if ((rc = acf_restart(s))) s->acf.reset();
+    return rc;
+}
+
+// rho, the walker means, windows and taus of the samples so far into the monitor's buffers; waits for them
+static int acf_finalise(mp_sampler *s, const char *fn, double c) {
+    if (!s->acf) return fail(MP_ESTATE, "%s: the autocorrelation monitor is off (mp_sampler_set_autocorr)", fn);
+    if (s->acf->n < 2) return fail(MP_ESTATE, "%s: the monitor holds %lld samples, an estimate needs 2 or more", fn, (long long)s->acf->n);
+    mp::AcfArgs a = acf_args(s);
+    a.c = c;
+    const int e = mp::launch_acf_finalise(a, s->h->stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipStreamSynchronize(s->h->stream));
+    return MP_OK;
+}
+
+int mp_sampler_get_autocorr(mp_sampler *s, double c, double *tau, int32_t *window, int64_t *n_samples) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_autocorr: NULL sampler");
+    if (!(c > 0.0) || !std::isfinite(c)) return fail(MP_EINVAL, "mp_sampler_get_autocorr: c must be finite and > 0, got %g", c);
+    Lock lock(s->h->mu);
+    DeviceScope scope(s->h->device);
+    if (n_samples) *n_samples = s->acf ? s->acf->n : 0;
+    int rc = acf_finalise(s, "mp_sampler_get_autocorr", c);
+    if (rc) return rc;
+    const size_t ned = (size_t)s->n_ensembles * s->ndim;
+    return read_back(tau, (const double *)s->acf->tau.p, ned, window, (const int32_t *)s->acf->window.p, ned);
+}
+
+int mp_sampler_get_acf(mp_sampler *s, int ensemble, int max_rows, double *acf) {
+    if (!s || !acf || max_rows < 0) return fail(MP_EINVAL, "mp_sampler_get_acf: bad argument");
+    if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "mp_sampler_get_acf: ensemble must be in [0, %d), got %d", s->n_ensembles, ensemble);
+    Lock lock(s->h->mu);
+    DeviceScope scope(s->h->device);
+    int rc = acf_finalise(s, "mp_sampler_get_acf", 5.0);
+    if (rc) return rc;
+    const AcfMonitor *m = s->acf.get();
+    const int rows = (int)std::min<int64_t>({(int64_t)max_rows, (int64_t)m->max_lag, m->n});
+    std::vector<double> f((size_t)s->ndim * m->kp);
+    HIP_TRY(hipMemcpy(f.data(), m->f.p + (size_t)ensemble * s->ndim * m->kp, f.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int k = 0; k < rows; ++k)
+        for (int d = 0; d < s->ndim; ++d) acf[(size_t)k * s->ndim + d] = f[(size_t)d * m->kp + k];
+    return rows;
+}
+
+int mp_sampler_get_autocorr_sums(mp_sampler *s, int ensemble, double *S, double *T, double *H, double *tail, double *pivot,
+                                 int64_t *n_samples) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_autocorr_sums: NULL sampler");
+    if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "mp_sampler_get_autocorr_sums: ensemble must be in [0, %d), got %d", s->n_ensembles, ensemble);
+    Lock lock(s->h->mu);
+    DeviceScope scope(s->h->device);
+    if (!s->acf) return fail(MP_ESTATE, "mp_sampler_get_autocorr_sums: the autocorrelation monitor is off (mp_sampler_set_autocorr)");
+    const AcfMonitor *m = s->acf.get();
+    HIP_TRY(hipStreamSynchronize(s->h->stream));
+    const size_t ns = (size_t)s->n_total * s->ndim, w = (size_t)s->n_walkers * s->ndim, off = (size_t)ensemble * w;
+    const size_t K = (size_t)m->max_lag;
+    // rows [r0, r0 + rows) of a [.][n_series] device array, the ensemble's columns -> dst[rows][n_walkers][ndim]
+    auto cols = [&](double *dst, const double *src, size_t r0, size_t rows) {
+        return rows == 0 ? hipSuccess
+                         : hipMemcpy2D(dst, w * sizeof(double), src + r0 * ns + off, ns * sizeof(double), w * sizeof(double), rows, hipMemcpyDeviceToHost);
+    };
+    if (S) HIP_TRY(cols(S, m->S.p, 0, K));
+    if (T) HIP_TRY(cols(T, m->T.p, 0, 1));
+    if (pivot) HIP_TRY(cols(pivot, m->pivot.p, 0, 1));
+    if (H) {
+        HIP_TRY(cols(H, m->H.p, 0, K));
+        std::vector<double> t(w);
+        HIP_TRY(cols(t.data(), m->T.p, 0, 1));
+        for (size_t k = (size_t)std::min<int64_t>(m->n, (int64_t)K - 1) + 1; k < K; ++k)   // H_k = T once k >= n
+            std::memcpy(H + k * w, t.data(), w * sizeof(double));
+    }
+    if (tail) {   // samples n - K .. n - 1: the K ring rows behind the head, zeros before sample 0
+        const size_t start = ((size_t)m->head + (size_t)m->ring_rows - K) % (size_t)m->ring_rows;
+        const size_t a_rows = std::min(K, (size_t)m->ring_rows - start);
+        HIP_TRY(cols(tail, m->hist.p, start, a_rows));
+        HIP_TRY(cols(tail + a_rows * w, m->hist.p, 0, K - a_rows));
+    }
+    if (n_samples) *n_samples = m->n;
     return MP_OK;
 }
 
@@ -423,6 +600,8 @@ struct ShardCall {
         else if (s->n_temps) rc = fail(MP_ESTATE, "%s: a tempered sampler runs on one device only (mp_sampler_run)", fn);
         else if (!s->moves.empty())
             rc = fail(MP_ESTATE, "%s: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)", fn);
+        else if (s->acf)
+            rc = fail(MP_ESTATE, "%s: the autocorrelation monitor (mp_sampler_set_autocorr) is fed by mp_sampler_run only; turn it off first", fn);
         else if (!(rc = current_split(s, (hipStream_t)stream, &d_perm))) s->ext_stream_work = true;
     }
 };

@@ -85,6 +85,9 @@ class EnsembleSampler:
         self.fbad = fbad
         self._bad_written = 0
         self._warned_bad = False
+        self._acf = None            # (max_lag, discard) of the device autocorrelation monitor; None: off
+        self.converged = False      # run_mcmc_until
+        self.tau_history = []
 
     def close(self):
         """Free the sampler, then its handle (garbage collection does the same: the sampler holds the handle)."""
@@ -287,11 +290,124 @@ class EnsembleSampler:
                               discard, thin, ensemble)
         return _capi.band_result(self.handle, rows, qa, names)
 
-    def get_autocorr_time(self, c=5.0, tol=50, quiet=False):
+    def get_autocorr_time(self, c=5.0, tol=50, quiet=False, device=False):
         """emcee's default (quiet=False) raises when the chain is shorter than tol autocorrelation times; the
-        reference calls it bare (code/synthetic_datasets/synth_mcmc.py:220)."""
+        reference calls it bare (code/synthetic_datasets/synth_mcmc.py:220).
+        device=True reads the device monitor (monitor_autocorr) instead of the stored chain: (ndim,) for one ensemble, else
+        (nensembles, ndim), every ensemble on its own; a tempered sampler reports its beta = 1 ensembles.  tol and quiet act as
+        on the host path, over the monitor's sample count; a NaN tau (max_lag too small for the window) raises with
+        quiet=False and warns with quiet=True."""
+        if device:
+            tau, _, n = self.get_autocorr_device(c)
+            if np.any(np.isnan(tau)):
+                msg = (f"no window below max_lag = {self._acf[0]} after {n} samples: raise max_lag (monitor_autocorr); tau: {tau}")
+                if not quiet:
+                    raise RuntimeError(msg)
+                import warnings
+                warnings.warn(msg, RuntimeWarning)
+            if not quiet and np.any(tol * tau > n):
+                raise RuntimeError(f"The chain is shorter than {tol} times the integrated autocorrelation time; tau: {tau}")
+            return tau
         from .mcmc_io import integrated_time
         return integrated_time(self.get_chain(temp=0 if self.betas is not None else None), c=c, tol=tol, quiet=quiet)
+
+    # ---- the device autocorrelation monitor (include/magprop_amd.h mp_sampler_set_autocorr states the definition)
+    def monitor_autocorr(self, max_lag=1024, discard=0):
+        """Turn the monitor on (empty, accumulating from `discard` steps from now on; lags 0 .. max_lag - 1), or off with
+        max_lag=0.  While it is on, set_positions (run_mcmc with pos) restarts it and the walker-sharded entry points refuse."""
+        _capi.check(self._L.mp_sampler_set_autocorr(self._s, int(max_lag), int(discard)), "mp_sampler_set_autocorr")
+        self._acf = (int(max_lag), int(discard)) if int(max_lag) else None
+
+    def _reported(self, a):
+        """Rows of a per-ensemble array that get_autocorr_time(device=True) reports: the beta = 1 ensembles; one row squeezed."""
+        a = a[::self.ntemps]
+        return a[0] if len(a) == 1 else a
+
+    def get_autocorr_device(self, c=5.0, wait=False):
+        """(tau, window, n) of the monitor: n samples so far, tau and window shaped as get_autocorr_time(device=True) returns tau.
+        wait=True answers (None, None, n) instead of raising while a monitor that is on holds fewer than the 2 samples an
+        estimate needs (still inside its discard); every other failure raises either way."""
+        n = C.c_int64(0)
+        tau = np.empty((self.nensembles, self.ndim))
+        win = np.empty((self.nensembles, self.ndim), dtype=np.int32)
+        rc = self._L.mp_sampler_get_autocorr(self._s, float(c), _capi.ptr(tau), _capi.ptr(win), C.byref(n))
+        if wait and rc == _capi.MP_ESTATE and self._acf is not None and n.value < 2:
+            return None, None, int(n.value)
+        _capi.check(rc, "mp_sampler_get_autocorr")
+        return self._reported(tau), self._reported(win), int(n.value)
+
+    def get_acf(self, ensemble=0, max_rows=None):
+        """The walker-mean autocorrelation function f_k of one ensemble from the monitor: (min(max_rows, max_lag, n), ndim)."""
+        if self._acf is None:
+            raise _capi.MagpropAmdError("the autocorrelation monitor is off (monitor_autocorr)")
+        rows = self._acf[0] if max_rows is None else int(max_rows)
+        buf = np.empty((rows, self.ndim))
+        got = self._L.mp_sampler_get_acf(self._s, int(ensemble), rows, _capi.ptr(buf))
+        if got < 0:
+            _capi.check(got, "mp_sampler_get_acf")
+        return buf[:got]
+
+    def get_autocorr_sums(self, ensemble=0):
+        """The monitor's raw accumulators of one ensemble (tests/acf_restated.py restates them): {"S", "H", "tail": (max_lag,
+        nwalkers, ndim), "T", "pivot": (nwalkers, ndim), "n": samples}."""
+        if self._acf is None:
+            raise _capi.MagpropAmdError("the autocorrelation monitor is off (monitor_autocorr)")
+        k, w = self._acf[0], (self.nwalkers, self.ndim)
+        out = _capi.read_back(self._L.mp_sampler_get_autocorr_sums, self._s, [
+            ("S", (k,) + w, np.float64), ("T", w, np.float64), ("H", (k,) + w, np.float64), ("tail", (k,) + w, np.float64),
+            ("pivot", w, np.float64), ("n", (), np.int64)], int(ensemble))
+        out["n"] = int(out["n"])
+        return out
+
+    def run_mcmc_until(self, pos, max_steps, check_every=100, tol=50, rtol=0.01, c=5.0, store=True):
+        """emcee's run-until-converged recipe on the device monitor: after every check_every steps read tau (the beta = 1
+        ensembles of a tempered sampler) and stop once autocorr_converged(tau, previous tau, n, tol, rtol) holds, n the
+        monitor's samples, or after max_steps.  Turns the monitor on (max_lag 1024, discard 0) if it is off.  Sets
+        self.converged and self.tau_history = [(n, tau), ...]; returns the final positions.  store=True appends the steps
+        to the stored chain (preallocated once for max_steps, trimmed); store=False: no chain reaches the host."""
+        max_steps, check_every = int(max_steps), int(check_every)
+        if check_every < 1 or max_steps < 0:
+            raise ValueError(f"check_every must be >= 1 and max_steps >= 0, got {check_every}, {max_steps}")
+        if self._acf is None:
+            self.monitor_autocorr()
+        if pos is not None:
+            self.set_positions(pos)
+        chain = np.empty((max_steps, self.ntotal, self.ndim)) if store else None
+        lnp = np.empty((max_steps, self.ntotal)) if store else None
+        done, prev = 0, None
+        self.converged, self.tau_history = False, []
+        while done < max_steps and not self.converged:
+            k = min(check_every, max_steps - done)
+            cp, lp = (_capi.ptr(chain[done:done + k]), _capi.ptr(lnp[done:done + k])) if store else (None, None)
+            _capi.check(self._L.mp_sampler_run(self._s, k, cp, lp), "mp_sampler_run")
+            done += k
+            self.iteration += k
+            self._flush_fbad()
+            if k < check_every:
+                break                                  # (the checks come at multiples of check_every)
+            tau, _, n = self.get_autocorr_device(c, wait=True)
+            if tau is None:                            # still inside the monitor's discard: fewer than 2 samples
+                continue
+            self.tau_history.append((n, tau))
+            self.converged = autocorr_converged(tau, prev, n, tol, rtol)
+            prev = tau
+        if store and done > 0:
+            if done < max_steps:                       # an early stop gives the unused rows back (refcheck: no other owner here)
+                chain.resize((done,) + chain.shape[1:], refcheck=False)
+                lnp.resize((done,) + lnp.shape[1:], refcheck=False)
+            self._chain = chain if self._chain is None else np.concatenate([self._chain, chain])
+            self._lnp = lnp if self._lnp is None else np.concatenate([self._lnp, lnp])
+        return self.get_last_sample()[0]
+
+
+def autocorr_converged(tau, tau_prev, n, tol=50, rtol=0.01):
+    """emcee's stopping rule: the chain is longer than tol autocorrelation times in every dimension, all(tol tau < n), and the
+    estimate has settled, all(|tau - tau_prev| / tau < rtol).  False without a previous estimate and for any NaN."""
+    if tau_prev is None:
+        return False
+    tau, tau_prev = np.asarray(tau, dtype=float), np.asarray(tau_prev, dtype=float)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return bool(np.all(tol * tau < n) and np.all(np.abs(tau - tau_prev) / tau < rtol))
 
 
 def band_selection(chain, nwalkers, nensembles=1, discard=0, thin=1, ensemble=0):
