@@ -1,15 +1,15 @@
-"""numpy restatement of the sampler's KDE move (include/magprop_amd.h MP_MOVE_KDE) over the step's two-way split, alone or in
-a mixture with the moves of tests/moves_restated.py, with the swap sweep of a tempered sampler.  Test infrastructure: the GPU
-tests compare the device chains with it on the unit-Gaussian target, the CPU tests check it against scipy.stats.gaussian_kde
-and that it samples a correlated Gaussian.  The proposal arithmetic is unfused float64 in the kernel's order; the kernel's
-sums over the other half run in an order of their own, and log / exp / sqrt / cos / sin are not numpy's, so the device
-agrees with this to rounding, not bit for bit."""
+"""numpy restatement of the sampler's KDE move (include/magprop_amd.h MP_MOVE_KDE): bandwidth, fit of the other half, density
+sums and the proposal.  Test infrastructure: the step loop of tests/sampler_restated.py proposes with it, alone or in a
+mixture with the moves of tests/moves_restated.py; the GPU tests compare the device chains with that loop on the
+unit-Gaussian target, the CPU tests check it against scipy.stats.gaussian_kde and that it samples a correlated Gaussian.
+The proposal arithmetic is unfused float64 in the kernel's order; the kernel's sums over the other half run in an order of
+their own, and log / exp / sqrt / cos / sin are not numpy's, so the device agrees with this to rounding, not bit for bit."""
 import math
 
 import numpy as np
 
-from moves_restated import draw_move, pick, propose, resolve
-from oracle.stretch_oracle import gaussian_lnprob, philox4x32_10, split, u01
+from moves_restated import pick
+from oracle.stretch_oracle import philox4x32_10, u01
 
 M32 = 0xFFFFFFFF
 KDE = 3                  # MP_MOVE_KDE
@@ -100,70 +100,6 @@ def propose_kde(pos, k, comp, seed, step, half, L, zero_hastings=False):
         return q, 0.0, logu
     pts = pos[comp]
     return q, log_kernel_sum(pos[k], pts, L) - log_kernel_sum(q, pts, L), logu
-
-
-def swap_sweep(pos, lnp, perms, seed, step, betas, n_temps, n):
-    """The swap sweep of a tempered step (mp_kernels.hip stretch_swap_kernel), in place."""
-    for e0 in range(0, len(perms), n_temps):
-        for t in range(n_temps - 1, 0, -1):
-            ec, eh = e0 + t - 1, e0 + t
-            dbeta = betas[ec] - betas[eh]
-            for i in range(n):
-                kc, kh = ec * n + perms[ec][i], eh * n + perms[eh][i]
-                r = philox4x32_10(seed & M32, seed >> 32, step, 2, kc, 0)
-                u = u01(r[0], r[1])
-                if (math.log(u) if u > 0.0 else -math.inf) < dbeta * (lnp[kh] - lnp[kc]):
-                    pos[[kc, kh]] = pos[[kh, kc]]
-                    lnp[kc], lnp[kh] = lnp[kh], lnp[kc]
-
-
-def run(pos, n_steps, seed, table, lnprob_fn=gaussian_lnprob, n_ensembles=1, step0=0, betas=None, n_temps=0,
-        zero_hastings=False):
-    """table = [(kind, weight, p0, p1)] over MP_MOVE_* (KDE: p0 as mp_sampler_set_moves takes it).  betas[e] per ensemble
-    and n_temps > 1: the decisions against beta and the swap sweep after every step.  pos is advanced in place.
-    Returns chain (n_steps, n_total, ndim), chain_lnp, n_accepted, moves drawn per step, accepted[n_steps, n_total]."""
-    n_total, ndim = pos.shape
-    n = n_total // n_ensembles
-    half_n = n // 2
-    n_comp = n - half_n
-    moves, cum = resolve(table, ndim)   # (KDE entries pass through as they are)
-    lnp = np.array([lnprob_fn(p) for p in pos])
-    acc = np.zeros(n_total, dtype=np.int64)
-    chain = np.empty((n_steps, n_total, ndim))
-    chain_lnp = np.empty((n_steps, n_total))
-    accepted = np.zeros((n_steps, n_total), dtype=bool)
-    drawn = np.empty(n_steps, dtype=np.int64)
-    for s in range(n_steps):
-        step = step0 + s
-        m = draw_move(seed, step, cum)
-        drawn[s] = m
-        kde = table[m][0] == KDE
-        perms = [split(seed, step, e, n) for e in range(n_ensembles)]
-        for half in range(2):
-            for e in range(n_ensembles):
-                base, perm = e * n, perms[e]
-                b = 1.0 if betas is None else float(betas[e])
-                comp = [base + perm[(1 - half) * half_n + c] for c in range(n_comp)]
-                L = fit(pos[comp], bandwidth(table[m][2], n_comp, ndim))[1] if kde else None
-                for slot in range(half_n):
-                    k = base + perm[half * half_n + slot]
-                    if kde:
-                        q, h, logu = propose_kde(pos, k, comp, seed, step, half, L, zero_hastings)
-                    else:
-                        q, h, logu = propose(moves[m], pos, k, comp, seed, step, half, zero_hastings)
-                    new = lnprob_fn(q)
-                    with np.errstate(invalid="ignore"):
-                        accept = (h + b * new) - b * lnp[k] > logu
-                    if accept:
-                        pos[k] = q
-                        lnp[k] = new
-                        acc[k] += 1
-                        accepted[s, k] = True
-        if betas is not None and n_temps > 1:
-            swap_sweep(pos, lnp, perms, seed, step, betas, n_temps, n)
-        chain[s] = pos
-        chain_lnp[s] = lnp
-    return chain, chain_lnp, acc, drawn, accepted
 
 
 def correlated_gaussian_nd(cov):

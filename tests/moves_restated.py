@@ -1,12 +1,13 @@
-"""numpy restatement of the sampler's proposal moves (include/magprop_amd.h mp_sampler_set_moves): stretch, differential
-evolution, snooker and weighted mixtures of them, over the step's two-way split.  Test infrastructure: the GPU tests compare
-the device chains with it bit for bit on the unit-Gaussian target, the CPU tests check with it that the moves sample a
-correlated Gaussian.  Every product and sum is a separately rounded float64 operation in the kernel's order."""
+"""numpy restatement of the sampler's proposal moves (include/magprop_amd.h mp_sampler_set_moves): the proposals of stretch,
+differential evolution and snooker, the index draws and the mixture rule.  Test infrastructure: the step loop of
+tests/sampler_restated.py proposes with it; the GPU tests compare the device chains with that loop bit for bit on the
+unit-Gaussian target, the CPU tests check with it that the moves sample a correlated Gaussian.  Every product and sum is a
+separately rounded float64 operation in the kernel's order."""
 import math
 
 import numpy as np
 
-from oracle.stretch_oracle import _draw, gaussian_lnprob, philox4x32_10, split, u01
+from oracle.stretch_oracle import _draw, philox4x32_10, u01
 
 M32 = 0xFFFFFFFF
 STRETCH, DE, SNOOKER = 0, 1, 2      # MP_MOVE_*
@@ -92,50 +93,6 @@ def propose(move, pos, k, comp, seed, step, half, zero_hastings=False):
             qq = qq + e[i] * e[i]
         h = (0.5 * (ndim - 1.0)) * (np.log(qq) - np.log(dd))
     return q, (0.0 if zero_hastings else h), logu
-
-
-def run(pos, n_steps, seed, table, lnprob_fn=gaussian_lnprob, n_ensembles=1, step0=0, lnp=None, acc=None, betas=None,
-        zero_hastings=False):
-    """Untempered (betas None) or tempered without swaps (betas[e] per ensemble: the decision h + b lnp(q) - b lnp(x) > ln u;
-    only for statistics).  table = [(kind, weight, p0, p1)].  pos is advanced in place.
-    Returns chain (n_steps, n_total, ndim), chain_lnp, n_accepted, moves drawn per step."""
-    n_total, ndim = pos.shape
-    n = n_total // n_ensembles
-    half_n = n // 2
-    moves, cum = resolve(table, ndim)
-    if lnp is None:
-        lnp = np.array([lnprob_fn(p) for p in pos])
-    if acc is None:
-        acc = np.zeros(n_total, dtype=np.int64)
-    chain = np.empty((n_steps, n_total, ndim))
-    chain_lnp = np.empty((n_steps, n_total))
-    drawn = np.empty(n_steps, dtype=np.int64)
-    for s in range(n_steps):
-        step = step0 + s
-        m = draw_move(seed, step, cum)
-        drawn[s] = m
-        perms = [split(seed, step, e, n) for e in range(n_ensembles)]
-        for half in range(2):
-            for e in range(n_ensembles):
-                base, perm = e * n, perms[e]
-                b = 1.0 if betas is None else float(betas[e])
-                comp = [base + perm[(1 - half) * half_n + c] for c in range(n - half_n)]
-                for slot in range(half_n):
-                    k = base + perm[half * half_n + slot]
-                    q, h, logu = propose(moves[m], pos, k, comp, seed, step, half, zero_hastings)
-                    new = lnprob_fn(q)
-                    with np.errstate(invalid="ignore"):
-                        if betas is None:
-                            accept = (h + new) - lnp[k] > logu
-                        else:
-                            accept = (h + b * new) - b * lnp[k] > logu
-                    if accept:
-                        pos[k] = q
-                        lnp[k] = new
-                        acc[k] += 1
-        chain[s] = pos
-        chain_lnp[s] = lnp
-    return chain, chain_lnp, acc, drawn
 
 
 def correlated_gaussian(rho):

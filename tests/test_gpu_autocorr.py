@@ -9,6 +9,7 @@ import pytest
 
 import acf_restated as ar
 from conftest import TRUTHS
+from raw_abi import RawSampler, dp, ip
 from test_autocorr_cpu import MEASURED_DISCREPANCY
 
 pytestmark = pytest.mark.gpu
@@ -18,53 +19,33 @@ RESTATED_RTOL = 1e-12
 # against the host's FFT estimator: 10 x the restatement-vs-FFT discrepancy measured in tests/test_autocorr_cpu.py (7.9e-12); the
 # margin covers the longer real chains
 HOST_RTOL = 10.0 * MEASURED_DISCREPANCY
-_dp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 
 
-class Raw:
-    """A unit-Gaussian sampler of n_ens ensembles through the C ABI."""
+class Raw(RawSampler):
+    """A unit-Gaussian sampler of n_ens ensembles through the C ABI, started at standard-normal positions drawn from its seed,
+    with the read-outs of the monitor."""
 
     def __init__(self, n_walkers, n_ens, ndim, seed, max_lag=0, discard=0):
-        from magprop_amd import _capi, engine
-        self.cap, self.L = _capi, _capi.lib()
-        self.h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
-        self.nw, self.ne, self.ndim, self.nt = n_walkers, n_ens, ndim, n_walkers * n_ens
-        self.sp = self.L.mp_sampler_create(self.h._h, n_walkers, n_ens, ndim, None, C.c_uint64(seed), C.c_double(2.0), 1)
-        assert self.sp, _capi.last_error()
+        super().__init__(n_walkers, n_ens, ndim, seed)
         self.K = max_lag
         if max_lag:
-            assert self.L.mp_sampler_set_autocorr(self.sp, max_lag, discard) == _capi.MP_OK, _capi.last_error()
-        pos = np.ascontiguousarray(np.random.default_rng(seed).standard_normal((self.nt, ndim)))
-        assert self.L.mp_sampler_set_positions(self.sp, pos.ctypes.data_as(_dp)) == _capi.MP_OK
-
-    def run(self, n, store=True):
-        if not store:
-            assert self.L.mp_sampler_run(self.sp, n, None, None) == self.cap.MP_OK, self.cap.last_error()
-            return None, None
-        ch, lp = np.empty((n, self.nt, self.ndim)), np.empty((n, self.nt))
-        assert self.L.mp_sampler_run(self.sp, n, ch.ctypes.data_as(_dp), lp.ctypes.data_as(_dp)) == self.cap.MP_OK, self.cap.last_error()
-        return ch, lp
+            self.set_autocorr(max_lag, discard)
+        self.set_positions(np.random.default_rng(seed).standard_normal((self.nt, ndim)))
 
     def sums(self, e):
         w = (self.nw, self.ndim)
         out = {k: np.empty((self.K,) + w) for k in ("S", "H", "tail")}
         out.update({k: np.empty(w) for k in ("T", "pivot")})
         n = C.c_int64(0)
-        rc = self.L.mp_sampler_get_autocorr_sums(self.sp, e, *(out[k].ctypes.data_as(_dp) for k in ("S", "T", "H", "tail", "pivot")), C.byref(n))
-        assert rc == self.cap.MP_OK, self.cap.last_error()
+        self._ok(self.L.mp_sampler_get_autocorr_sums(self.sp, e, *(dp(out[k]) for k in ("S", "T", "H", "tail", "pivot")), C.byref(n)))
         out["n"] = n.value
         return out
 
     def tau(self, c=5.0):
         tau, win = np.empty((self.ne, self.ndim)), np.empty((self.ne, self.ndim), dtype=np.int32)
         n = C.c_int64(0)
-        rc = self.L.mp_sampler_get_autocorr(self.sp, C.c_double(c), tau.ctypes.data_as(_dp), win.ctypes.data_as(_ip), C.byref(n))
-        assert rc == self.cap.MP_OK, self.cap.last_error()
+        self._ok(self.L.mp_sampler_get_autocorr(self.sp, C.c_double(c), dp(tau), ip(win), C.byref(n)))
         return tau, win, n.value
-
-    def close(self):
-        self.L.mp_sampler_destroy(self.sp)
-        self.h.close()
 
 
 def _same_sums(a, b):
@@ -99,7 +80,7 @@ def test_accumulators_bit_equal_to_the_restatement(n_ens, n_walkers):
         assert np.array_equal(tau[e], rt)
         assert np.array_equal(win[e], hw) and rel_host <= HOST_RTOL
         f = np.empty((K, ndim))
-        rows = r.L.mp_sampler_get_acf(r.sp, e, K, f.ctypes.data_as(_dp))
+        rows = r.L.mp_sampler_get_acf(r.sp, e, K, dp(f))
         assert rows == K and np.allclose(f, rf, rtol=0, atol=1e-13) and np.all(f[0] == 1.0)
     r.close()
 
@@ -244,9 +225,9 @@ def test_refusals_carry_a_message():
         assert L.mp_sampler_set_autocorr(sp, bad, 0) == _capi.MP_EINVAL and "max_lag" in _capi.last_error()
     assert L.mp_sampler_set_autocorr(sp, 16, -1) == _capi.MP_EINVAL and "discard" in _capi.last_error()
     tau, win = np.empty((1, 2)), np.empty((1, 2), dtype=np.int32)
-    get = lambda: L.mp_sampler_get_autocorr(sp, C.c_double(5.0), tau.ctypes.data_as(_dp), win.ctypes.data_as(_ip), None)   # noqa: E731
+    get = lambda: L.mp_sampler_get_autocorr(sp, C.c_double(5.0), dp(tau), ip(win), None)   # noqa: E731
     assert get() == _capi.MP_ESTATE and "monitor is off" in _capi.last_error()
-    assert L.mp_sampler_get_acf(sp, 0, 4, tau.ctypes.data_as(_dp)) == _capi.MP_ESTATE
+    assert L.mp_sampler_get_acf(sp, 0, 4, dp(tau)) == _capi.MP_ESTATE
     assert L.mp_sampler_get_autocorr_sums(sp, 0, None, None, None, None, None, None) == _capi.MP_ESTATE
     assert L.mp_sampler_set_autocorr(sp, 16, 0) == _capi.MP_OK
     assert get() == _capi.MP_ESTATE and "2 or more" in _capi.last_error()

@@ -1,12 +1,14 @@
 """GPU tests of the proposal moves of the device-resident sampler (include/magprop_amd.h mp_sampler_set_moves): DE, snooker and
-mixtures against the numpy restatement (tests/moves_restated.py) bit for bit, moments, a posterior run and argument codes."""
+mixtures against the numpy restatement (tests/sampler_restated.py) bit for bit, moments, a posterior run and argument codes."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from conftest import TRUTHS
-from moves_restated import DE, SNOOKER, STRETCH, run as restate
+from moves_restated import DE, SNOOKER, STRETCH
+from raw_abi import RawSampler, dp, gaussian_run, synth_handle, table_args
+from sampler_restated import run as restate
 
 pytestmark = pytest.mark.gpu
 
@@ -21,48 +23,6 @@ TABLES = {
 }
 
 
-def _table_args(table):
-    kinds = np.array([t[0] for t in table], dtype=np.int32)
-    weights = np.array([t[1] for t in table], dtype=np.float64)
-    params = np.ascontiguousarray([[t[2], t[3]] for t in table], dtype=np.float64)
-    return kinds, weights, params
-
-
-def _set_moves(L, sp, table):
-    kinds, weights, params = _table_args(table)
-    return L.mp_sampler_set_moves(sp, len(table), kinds.ctypes.data_as(C.POINTER(C.c_int32)),
-                                  weights.ctypes.data_as(C.POINTER(C.c_double)), params.ctypes.data_as(C.POINTER(C.c_double)))
-
-
-def _raw_gaussian_run(n_walkers, n_ens, ndim, seed, table, pos, runs, whole=True):
-    """The unit-Gaussian target through the C ABI (several ensembles): runs = steps of consecutive mp_sampler_run calls.
-    Returns chain, chain_lnp, n_accepted."""
-    from magprop_amd import _capi, engine
-    L = _capi.lib()
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
-    sp = L.mp_sampler_create(h._h, n_walkers, n_ens, ndim, None, C.c_uint64(seed), C.c_double(2.0), 1)
-    assert sp, _capi.last_error()
-    try:
-        assert L.mp_sampler_set_whole_step(sp, int(whole)) == _capi.MP_OK
-        assert _set_moves(L, sp, table) == _capi.MP_OK, _capi.last_error()
-        p = np.ascontiguousarray(pos, dtype=np.float64)
-        assert L.mp_sampler_set_positions(sp, p.ctypes.data_as(C.POINTER(C.c_double))) == _capi.MP_OK
-        nt = n_walkers * n_ens
-        chains, lnps = [], []
-        for n in runs:
-            ch = np.empty((n, nt, ndim))
-            lp = np.empty((n, nt))
-            assert L.mp_sampler_run(sp, n, ch.ctypes.data_as(C.POINTER(C.c_double)), lp.ctypes.data_as(C.POINTER(C.c_double))) == _capi.MP_OK
-            chains.append(ch)
-            lnps.append(lp)
-        acc = np.empty(nt, dtype=np.int64)
-        assert L.mp_sampler_get_state(sp, None, None, acc.ctypes.data_as(C.POINTER(C.c_int64)), None) == _capi.MP_OK
-        return np.concatenate(chains), np.concatenate(lnps), acc
-    finally:
-        L.mp_sampler_destroy(sp)
-        h.close()
-
-
 @pytest.mark.parametrize("name", list(TABLES))
 def test_gaussian_chain_matches_the_restatement_bit_for_bit(name):
     """32 walkers x 2 ensembles x 3 dims x 120 steps (the team builds; stretch steps of a mixture as one launch per step):
@@ -70,16 +30,16 @@ def test_gaussian_chain_matches_the_restatement_bit_for_bit(name):
     table = TABLES[name]
     seed = 20261016
     pos = np.random.default_rng(3).normal(size=(2 * 32, 3)) * 1.5
-    chain, lnp, acc, drawn = restate(pos.copy(), 120, seed, table, n_ensembles=2)
+    ref = restate(pos.copy(), 120, seed, table, n_ensembles=2)
     if len(table) > 1:
-        assert 0 < np.count_nonzero(drawn == 1) < 120        # both moves were drawn
-    assert 0 < acc.sum() < 120 * 64
+        assert 0 < np.count_nonzero(ref.drawn == 1) < 120    # both moves were drawn
+    assert 0 < ref.acc.sum() < 120 * 64
     for whole in (True, False):
-        got = _raw_gaussian_run(32, 2, 3, seed, table, pos, (120,), whole=whole)
-        for a, b in zip(got, (chain, lnp, acc)):
+        got = gaussian_run(32, 2, 3, seed, table, pos, (120,), whole=whole)
+        for a, b in zip(got, (ref.chain, ref.lnp, ref.acc)):
             assert np.array_equal(a, b), (name, whole)
-    got = _raw_gaussian_run(32, 2, 3, seed, table, pos, (50, 70))
-    for a, b in zip(got, (chain, lnp, acc)):
+    got = gaussian_run(32, 2, 3, seed, table, pos, (50, 70), whole=True)
+    for a, b in zip(got, (ref.chain, ref.lnp, ref.acc)):
         assert np.array_equal(a, b), name
 
 
@@ -89,9 +49,9 @@ def test_gaussian_chain_bit_for_bit_on_the_one_wave_builds(name):
     table = TABLES[name]
     seed = 77
     pos = np.random.default_rng(4).normal(size=(2048, 2))
-    chain, lnp, acc, _ = restate(pos.copy(), 20, seed, table)
-    got = _raw_gaussian_run(2048, 1, 2, seed, table, pos, (20,))
-    for a, b in zip(got, (chain, lnp, acc)):
+    ref = restate(pos.copy(), 20, seed, table)
+    got = gaussian_run(2048, 1, 2, seed, table, pos, (20,), whole=True)
+    for a, b in zip(got, (ref.chain, ref.lnp, ref.acc)):
         assert np.array_equal(a, b), name
 
 
@@ -183,33 +143,28 @@ def test_humped_posterior_with_the_de_snooker_mixture(gsynth):
 
 def test_set_moves_argument_codes(gsynth):
     from magprop_amd import EnsembleSampler, _capi
-    L = _capi.lib()
-    dp = C.POINTER(C.c_double)
     x, y, yerr = gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"]
-    h = _capi.Handle(_capi.cfg_synth(), __import__("magprop_amd").engine.grid(None))
+    h = synth_handle()
     h.set_prior(gsynth["prior_lower"], gsynth["prior_upper"], 0b111100)
     h.set_dataset(0, x, y, yerr)
-    sp = L.mp_sampler_create(h._h, 8, 1, 6, None, C.c_uint64(1), C.c_double(2.0), 0)
-    assert sp
+    r = RawSampler(8, 1, 6, 1, target=0, handle=h)
+    L, sp = r.L, r.sp
     for bad in ([(5, 1.0, 0.0, 0.0)], [(-1, 1.0, 0.0, 0.0)], [(DE, 0.0, 0.0, 1e-5)], [(DE, -1.0, 0.0, 1e-5)],
                 [(DE, np.nan, 0.0, 1e-5)], [(DE, np.inf, 0.0, 1e-5)], [(STRETCH, 1.0, 1.0, 0.0)], [(STRETCH, 1.0, np.nan, 0.0)],
                 [(DE, 1.0, -0.1, 1e-5)], [(DE, 1.0, 0.0, 0.6)], [(DE, 1.0, 0.0, -1e-3)], [(DE, 1.0, 0.0, np.nan)],
                 [(SNOOKER, 1.0, 0.0, 0.0)], [(SNOOKER, 1.0, -1.7, 0.0)], [(SNOOKER, 1.0, np.inf, 0.0)], [DE_DEFAULT] * 9):
-        assert _set_moves(L, sp, bad) == _capi.MP_EINVAL, bad
-    k, w, p = _table_args([DE_DEFAULT])
-    assert L.mp_sampler_set_moves(sp, 1, None, w.ctypes.data_as(dp), p.ctypes.data_as(dp)) == _capi.MP_EINVAL
+        assert r.set_moves(bad, check=False) == _capi.MP_EINVAL, bad
+    k, w, p = table_args([DE_DEFAULT])
+    assert L.mp_sampler_set_moves(sp, 1, None, dp(w), dp(p)) == _capi.MP_EINVAL
     assert L.mp_sampler_set_moves(sp, -1, None, None, None) == _capi.MP_EINVAL
     # n_half: DE needs 2 partners, snooker 3 (8 walkers: n_half = 4; 4 walkers: 2; 2 walkers: 1)
     for nw, de_ok, sn_ok in ((8, True, True), (4, True, False), (2, False, False)):
-        s2 = L.mp_sampler_create(h._h, nw, 1, 6, None, C.c_uint64(1), C.c_double(2.0), 0)
-        assert s2
-        assert (_set_moves(L, s2, [DE_DEFAULT]) == _capi.MP_OK) == de_ok, nw
-        assert (_set_moves(L, s2, [SNOOKER_DEFAULT]) == _capi.MP_OK) == sn_ok, nw
-        L.mp_sampler_destroy(s2)
-    pos = np.ascontiguousarray(np.array(TRUTHS["Humped"]) + 1.0e-3 * np.random.default_rng(0).standard_normal((8, 6)))
-    assert L.mp_sampler_set_positions(sp, pos.ctypes.data_as(dp)) == _capi.MP_OK
-    assert _set_moves(L, sp, TABLES["de_snooker"]) == _capi.MP_OK
-    assert L.mp_sampler_run(sp, 3, None, None) == _capi.MP_OK
+        with RawSampler(nw, 1, 6, 1, target=0, handle=h) as s2:
+            assert (s2.set_moves([DE_DEFAULT], check=False) == _capi.MP_OK) == de_ok, nw
+            assert (s2.set_moves([SNOOKER_DEFAULT], check=False) == _capi.MP_OK) == sn_ok, nw
+    r.set_positions(np.array(TRUTHS["Humped"]) + 1.0e-3 * np.random.default_rng(0).standard_normal((8, 6)))
+    r.set_moves(TABLES["de_snooker"])
+    r.run(3, store=False)
     # the walker-sharded entry points refuse a move table
     rows = C.c_void_p(1)
     assert L.mp_sampler_halfstep_shard(sp, 0, 0, 1, rows, None) == _capi.MP_ESTATE
@@ -220,7 +175,7 @@ def test_set_moves_argument_codes(gsynth):
     assert L.mp_sampler_set_moves(sp, 0, None, None, None) == _capi.MP_OK
     assert L.mp_sampler_run(sp, 2, None, None) == _capi.MP_OK
     assert L.mp_sampler_n_slots(sp) == 4
-    L.mp_sampler_destroy(sp)
+    r.close()
     h.close()
     from magprop_amd import DEMove
     from magprop_amd.distributed import DistributedEnsembleSampler, HipShardEngine

@@ -1,5 +1,5 @@
 """GPU tests of the KDE move of the device-resident sampler (include/magprop_amd.h MP_MOVE_KDE): device chains against the numpy
-restatement (tests/kde_restated.py) on the unit-Gaussian target -- team and one-wavefront builds, tempered, mixtures, split
+restatement (tests/sampler_restated.py) on the unit-Gaussian target -- team and one-wavefront builds, tempered, mixtures, split
 runs --, moments, a Humped posterior run, argument codes and a degenerate other half."""
 import ctypes as C
 
@@ -7,8 +7,10 @@ import numpy as np
 import pytest
 
 from conftest import TRUTHS
-from kde_restated import KDE, run as restate
+from kde_restated import KDE
 from moves_restated import DE, STRETCH
+from raw_abi import RawSampler, gaussian_run, synth_handle
+from sampler_restated import run as restate
 
 pytestmark = pytest.mark.gpu
 
@@ -24,45 +26,6 @@ TABLES = {
 }
 
 
-def _set_moves(L, sp, table):
-    kinds = np.array([t[0] for t in table], dtype=np.int32)
-    weights = np.array([t[1] for t in table], dtype=np.float64)
-    params = np.ascontiguousarray([[t[2], t[3]] for t in table], dtype=np.float64)
-    return L.mp_sampler_set_moves(sp, len(table), kinds.ctypes.data_as(C.POINTER(C.c_int32)),
-                                  weights.ctypes.data_as(C.POINTER(C.c_double)), params.ctypes.data_as(C.POINTER(C.c_double)))
-
-
-def _raw_gaussian_run(n_walkers, n_ens, ndim, seed, table, pos, runs, betas=None):
-    """The unit-Gaussian target through the C ABI: runs = steps of consecutive mp_sampler_run calls; betas (per temperature,
-    n_ens a multiple of their number): a tempered sampler.  Returns chain, chain_lnp, n_accepted."""
-    from magprop_amd import _capi, engine
-    L = _capi.lib()
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
-    sp = L.mp_sampler_create(h._h, n_walkers, n_ens, ndim, None, C.c_uint64(seed), C.c_double(2.0), 1)
-    assert sp, _capi.last_error()
-    try:
-        if betas is not None:
-            b = np.ascontiguousarray(betas, dtype=np.float64)
-            assert L.mp_sampler_set_temperatures(sp, len(b), b.ctypes.data_as(C.POINTER(C.c_double))) == _capi.MP_OK
-        assert _set_moves(L, sp, table) == _capi.MP_OK, _capi.last_error()
-        p = np.ascontiguousarray(pos, dtype=np.float64)
-        assert L.mp_sampler_set_positions(sp, p.ctypes.data_as(C.POINTER(C.c_double))) == _capi.MP_OK
-        nt = n_walkers * n_ens
-        chains, lnps = [], []
-        for n in runs:
-            ch = np.empty((n, nt, ndim))
-            lp = np.empty((n, nt))
-            assert L.mp_sampler_run(sp, n, ch.ctypes.data_as(C.POINTER(C.c_double)), lp.ctypes.data_as(C.POINTER(C.c_double))) == _capi.MP_OK
-            chains.append(ch)
-            lnps.append(lp)
-        acc = np.empty(nt, dtype=np.int64)
-        assert L.mp_sampler_get_state(sp, None, None, acc.ctypes.data_as(C.POINTER(C.c_int64)), None) == _capi.MP_OK
-        return np.concatenate(chains), np.concatenate(lnps), acc
-    finally:
-        L.mp_sampler_destroy(sp)
-        h.close()
-
-
 def _moved(chain, pos0):
     """accepted[s, k] of an untempered chain: the walker's row changed (a proposal equals the old position with probability 0)."""
     prev = np.concatenate([pos0[None], chain[:-1]])
@@ -71,13 +34,12 @@ def _moved(chain, pos0):
 
 def _assert_agrees(got, ref, pos0, tempered=False):
     chain, lnp, acc = got
-    rchain, rlnp, racc, _, raccepted = ref
-    assert np.array_equal(acc, racc)
+    assert np.array_equal(acc, ref.acc)
     if not tempered:
-        assert np.array_equal(_moved(chain, pos0), raccepted)
+        assert np.array_equal(_moved(chain, pos0), ref.accepted)
     assert np.all(np.isfinite(chain)) and np.all(np.isfinite(lnp))
-    assert np.allclose(chain, rchain, rtol=RTOL, atol=ATOL), np.abs(chain - rchain).max()
-    assert np.allclose(lnp, rlnp, rtol=RTOL, atol=ATOL), np.abs(lnp - rlnp).max()
+    assert np.allclose(chain, ref.chain, rtol=RTOL, atol=ATOL), np.abs(chain - ref.chain).max()
+    assert np.allclose(lnp, ref.lnp, rtol=RTOL, atol=ATOL), np.abs(lnp - ref.lnp).max()
 
 
 @pytest.mark.parametrize("name", list(TABLES))
@@ -88,10 +50,10 @@ def test_gaussian_chain_matches_the_restatement_on_the_team_builds(name):
     pos = np.random.default_rng(3).normal(size=(2 * 32, 3)) * 1.5
     ref = restate(pos.copy(), 60, seed, table, n_ensembles=2)
     if len(table) > 1:
-        assert 0 < np.count_nonzero(ref[3] == 0) < 60                # both moves were drawn
-    assert 0 < ref[2].sum() < 60 * 64
-    _assert_agrees(_raw_gaussian_run(32, 2, 3, seed, table, pos, (60,)), ref, pos)
-    _assert_agrees(_raw_gaussian_run(32, 2, 3, seed, table, pos, (25, 35)), ref, pos)
+        assert 0 < np.count_nonzero(ref.drawn == 0) < 60               # both moves were drawn
+    assert 0 < ref.acc.sum() < 60 * 64
+    _assert_agrees(gaussian_run(32, 2, 3, seed, table, pos, (60,)), ref, pos)
+    _assert_agrees(gaussian_run(32, 2, 3, seed, table, pos, (25, 35)), ref, pos)
 
 
 @pytest.mark.parametrize("name", ["kde", "kde_de"])
@@ -100,7 +62,7 @@ def test_gaussian_chain_matches_the_restatement_on_the_one_wave_builds(name):
     table, seed = TABLES[name], 77
     pos = np.random.default_rng(4).normal(size=(2048, 2))
     ref = restate(pos.copy(), 8, seed, table)
-    _assert_agrees(_raw_gaussian_run(2048, 1, 2, seed, table, pos, (8,)), ref, pos)
+    _assert_agrees(gaussian_run(2048, 1, 2, seed, table, pos, (8,)), ref, pos)
 
 
 def test_tempered_gaussian_chain_matches_the_restatement():
@@ -108,7 +70,7 @@ def test_tempered_gaussian_chain_matches_the_restatement():
     table, seed, betas = TABLES["kde_stretch"], 5, (1.0, 0.5, 0.25)
     pos = np.random.default_rng(6).normal(size=(3 * 24, 3))
     ref = restate(pos.copy(), 40, seed, table, n_ensembles=3, betas=betas, n_temps=3)
-    _assert_agrees(_raw_gaussian_run(24, 3, 3, seed, table, pos, (40,), betas=betas), ref, pos, tempered=True)
+    _assert_agrees(gaussian_run(24, 3, 3, seed, table, pos, (40,), betas=betas), ref, pos, tempered=True)
 
 
 def test_gaussian_target_statistics_with_the_kde_move():
@@ -145,32 +107,28 @@ def test_humped_posterior_with_the_kde_move(gsynth):
 
 def test_set_moves_kde_argument_codes(gsynth):
     from magprop_amd import EnsembleSampler, KDEMove, _capi
-    L = _capi.lib()
-    h = _capi.Handle(_capi.cfg_synth(), __import__("magprop_amd").engine.grid(None))
+    h = synth_handle()
     h.set_prior(gsynth["prior_lower"], gsynth["prior_upper"], 0b111100)
     h.set_dataset(0, gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"])
-    sp = L.mp_sampler_create(h._h, 16, 1, 6, None, C.c_uint64(1), C.c_double(2.0), 0)
-    assert sp
+    r = RawSampler(16, 1, 6, 1, target=0, handle=h)
+    L, sp = r.L, r.sp
     for bad in ([(KDE, 1.0, -0.5, 0.0)], [(KDE, 1.0, -2.0, 0.0)], [(KDE, 1.0, np.nan, 0.0)], [(KDE, 1.0, np.inf, 0.0)],
                 [(KDE, 1.0, -np.inf, 0.0)], [(KDE, 1.0, 0.0, 1.0)], [(KDE, 1.0, 0.0, np.nan)], [(KDE, 1.0, 0.5, -1.0)],
                 [(KDE, 0.0, 0.0, 0.0)], [(KDE, np.nan, 0.0, 0.0)], [(5, 1.0, 0.0, 0.0)], [(-1, 1.0, 0.0, 0.0)]):
-        assert _set_moves(L, sp, bad) == _capi.MP_EINVAL, bad
+        assert r.set_moves(bad, check=False) == _capi.MP_EINVAL, bad
     for good in ([KDE_SCOTT], [(KDE, 1.0, -1.0, 0.0)], [(KDE, 1.0, 0.7, 0.0)], TABLES["kde_de"]):
-        assert _set_moves(L, sp, good) == _capi.MP_OK, good
+        assert r.set_moves(good, check=False) == _capi.MP_OK, good
     # n_comp = n_walkers / 2: 12 walkers give n_comp = 6 = ndim (refused), 14 walkers n_comp = 7 = ndim + 1 (accepted)
     for nw, ok in ((12, False), (14, True)):
-        s2 = L.mp_sampler_create(h._h, nw, 1, 6, None, C.c_uint64(1), C.c_double(2.0), 0)
-        assert s2
-        assert (_set_moves(L, s2, [KDE_SCOTT]) == _capi.MP_OK) == ok, nw
-        L.mp_sampler_destroy(s2)
-    pos = np.ascontiguousarray(np.array(TRUTHS["Humped"]) + 1.0e-3 * np.random.default_rng(0).standard_normal((16, 6)))
-    assert L.mp_sampler_set_positions(sp, pos.ctypes.data_as(C.POINTER(C.c_double))) == _capi.MP_OK
-    assert _set_moves(L, sp, [KDE_SCOTT]) == _capi.MP_OK
-    assert L.mp_sampler_run(sp, 3, None, None) == _capi.MP_OK
+        with RawSampler(nw, 1, 6, 1, target=0, handle=h) as s2:
+            assert (s2.set_moves([KDE_SCOTT], check=False) == _capi.MP_OK) == ok, nw
+    r.set_positions(np.array(TRUTHS["Humped"]) + 1.0e-3 * np.random.default_rng(0).standard_normal((16, 6)))
+    r.set_moves([KDE_SCOTT])
+    r.run(3, store=False)
     rows = C.c_void_p(1)
     assert L.mp_sampler_halfstep_shard(sp, 0, 0, 1, rows, None) == _capi.MP_ESTATE
     assert L.mp_sampler_step_shard(sp, 0, 1, rows, None) == _capi.MP_ESTATE
-    L.mp_sampler_destroy(sp)
+    r.close()
     h.close()
     from magprop_amd.distributed import DistributedEnsembleSampler, HipShardEngine
     s = EnsembleSampler(16, 6, gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"], moves=KDEMove())
@@ -185,7 +143,7 @@ def test_degenerate_other_half_moves_no_walker(nw, n_ens, ndim):
     moves, and neither the chain nor lnprob holds a NaN."""
     pos = np.random.default_rng(9).normal(size=(nw * n_ens, ndim))
     pos[:, 1] = 0.5
-    chain, lnp, acc = _raw_gaussian_run(nw, n_ens, ndim, 13, [KDE_SCOTT], pos, (5,))
+    chain, lnp, acc = gaussian_run(nw, n_ens, ndim, 13, [KDE_SCOTT], pos, (5,))
     assert np.all(acc == 0)
     assert np.all(np.isfinite(chain)) and np.all(np.isfinite(lnp))
     assert np.array_equal(chain, np.broadcast_to(pos, chain.shape))

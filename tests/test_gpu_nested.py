@@ -10,10 +10,10 @@ from scipy.special import erf
 
 import nest_restated as nr
 from conftest import TRUTHS
+from raw_abi import dp, ip, synth_handle
 
 pytestmark = pytest.mark.gpu
 
-dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 EVIDENCE_INFLATION = 10.0       # tests/test_gpu_tempering.py: Humped with yerr x 10
 
 
@@ -25,14 +25,13 @@ class RawNested:
         self.L, self.nlive, self.n_runs, self.ndim = _capi.lib(), nlive, n_runs, ndim
         self.lo, self.hi = np.ascontiguousarray(lower, dtype=np.float64), np.ascontiguousarray(upper, dtype=np.float64)
         ids = None if ds is None else np.ascontiguousarray(ds, dtype=np.int32)
-        self.ns = self.L.mp_nested_create(h._h, nlive, nbatch, n_runs, ndim, None if ids is None else ids.ctypes.data_as(ip),
-                                          C.c_uint64(seed), walks, g0, sigma, dlogz, self.lo.ctypes.data_as(dp),
-                                          self.hi.ctypes.data_as(dp), target)
+        self.ns = self.L.mp_nested_create(h._h, nlive, nbatch, n_runs, ndim, ip(ids), C.c_uint64(seed), walks, g0, sigma, dlogz,
+                                          dp(self.lo), dp(self.hi), target)
         assert self.ns, _capi.last_error()
 
     def set_live(self, live):
         p = np.ascontiguousarray(live, dtype=np.float64)
-        assert self.L.mp_nested_set_live(self.ns, p.ctypes.data_as(dp)) == 0
+        assert self.L.mp_nested_set_live(self.ns, dp(p)) == 0
 
     def run(self, n):
         running = C.c_int32(-1)
@@ -78,13 +77,12 @@ def test_gaussian_state_matches_the_restatement_bit_for_bit(n_runs):
     """Unit Gaussian in an asymmetric 3-d box, N = 32, K = 8, 10 steps per walk, dlogz = 0.05: 6 iterations, then on to the stop
     rule; live set, lnL, status, accepted counts, the dead sequence, the stop iteration and the counters equal the restatement,
     ln X and ln Z to 1e-14 relative."""
-    from magprop_amd import _capi, engine
     ndim, nlive, nbatch, walks, seed = 3, 32, 8, 10, 20261015 + n_runs
     lo, hi = np.array([-2.0, -1.0, -4.0]), np.array([3.0, 2.5, 1.5])
     live0 = lo + (hi - lo) * np.random.default_rng(7 + n_runs).random((n_runs, nlive, ndim))
     kw = dict(walks=walks, g0=0.0, sigma=0.1, dlogz=0.05, lower=lo, upper=hi, evaluate_one=nr.gaussian_one)
     s = nr.start(live0, nr.gaussian)
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h = synth_handle()
     ns = RawNested(h, nlive, nbatch, n_runs, ndim, lo, hi, seed, walks, 1, dlogz=0.05)
     try:
         ns.set_live(live0.reshape(-1, ndim))
@@ -105,11 +103,10 @@ def test_gaussian_state_matches_the_restatement_bit_for_bit(n_runs):
 def test_chunks_of_one_iteration_equal_one_unsplit_run():
     """Two runs of N = 64 (K = 8, 25 steps) on the unit Gaussian: mp_nested_run(1) called until both stopped equals one
     mp_nested_run(10 000), whose chunks are the library's own."""
-    from magprop_amd import _capi, engine
     ndim, nlive, nbatch = 4, 64, 8
     lo, hi = np.full(ndim, -3.0), np.array([2.0, 3.0, 4.0, 5.0])
     live0 = lo + (hi - lo) * np.random.default_rng(3).random((2 * nlive, ndim))
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h = synth_handle()
     states = []
     try:
         for split in (True, False):
@@ -220,34 +217,31 @@ def test_long_swift_light_curve_lib_reaches_the_best_fit(gswift):
 
 
 def test_multi_device_and_alternative_torque_handles_are_refused():
-    from magprop_amd import _capi, engine
+    from magprop_amd import _capi
     L = _capi.lib()
     lo, hi = np.zeros(6), np.ones(6)
     x = np.logspace(0.5, 3.0, 20)
-    hm = _capi.Handle(_capi.cfg_synth(), engine.grid(None), device=[0])
-    ha = _capi.Handle(_capi.cfg_synth(dipole_torque=1), engine.grid(None))
+    hm = synth_handle(device=[0])
+    ha = synth_handle(dipole_torque=1)
     try:
         for h, what in ((hm, "ONE device"), (ha, "dipole torque")):
             h.set_dataset(0, x, np.ones_like(x), np.ones_like(x))
-            ns = L.mp_nested_create(h._h, 64, 16, 1, 6, None, C.c_uint64(0), 25, 0.0, 0.1, 0.01, lo.ctypes.data_as(dp),
-                                    hi.ctypes.data_as(dp), 0)
+            ns = L.mp_nested_create(h._h, 64, 16, 1, 6, None, C.c_uint64(0), 25, 0.0, 0.1, 0.01, dp(lo), dp(hi), 0)
             assert not ns and what in _capi.last_error()
         # argument codes on a plain handle
-        h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+        h = synth_handle()
         for bad in (dict(nlive=8), dict(nbatch=33), dict(nbatch=0), dict(walks=0), dict(sigma=0.6), dict(dlogz=0.0),
                     dict(upper=np.zeros(6)), dict(n_runs=65)):
             kw = dict(nlive=64, nbatch=16, walks=25, sigma=0.1, dlogz=0.01, upper=hi, n_runs=1)
             kw.update(bad)
             ns = L.mp_nested_create(h._h, kw["nlive"], kw["nbatch"], kw["n_runs"], 6, None, C.c_uint64(0), kw["walks"], 0.0,
-                                    kw["sigma"], kw["dlogz"], lo.ctypes.data_as(dp),
-                                    np.ascontiguousarray(kw["upper"]).ctypes.data_as(dp), 1)
+                                    kw["sigma"], kw["dlogz"], dp(lo), dp(np.ascontiguousarray(kw["upper"])), 1)
             assert not ns, bad
-        ns = L.mp_nested_create(h._h, 64, 16, 1, 6, None, C.c_uint64(0), 25, 0.0, 0.1, 0.01, lo.ctypes.data_as(dp),
-                                hi.ctypes.data_as(dp), 1)
+        ns = L.mp_nested_create(h._h, 64, 16, 1, 6, None, C.c_uint64(0), 25, 0.0, 0.1, 0.01, dp(lo), dp(hi), 1)
         assert ns
         assert L.mp_nested_run(ns, 1, None) == _capi.MP_ESTATE                   # before set_live
         out = np.full((64, 6), 2.0)
-        assert L.mp_nested_set_live(ns, out.ctypes.data_as(dp)) == _capi.MP_EINVAL   # outside the box
+        assert L.mp_nested_set_live(ns, dp(out)) == _capi.MP_EINVAL   # outside the box
         L.mp_nested_destroy(ns)
         h.close()
     finally:

@@ -12,11 +12,10 @@ import pytest
 import nest_restated as nr
 import nest_slice_restated as sr
 from conftest import TRUTHS
+from raw_abi import lp, synth_handle
 from test_gpu_nested import EVIDENCE_INFLATION, RawNested, _assert_equal, _gaussian_lnz
 
 pytestmark = pytest.mark.gpu
-
-lp64 = C.POINTER(C.c_int64)
 
 
 def _set_slice(ns, slices, mu=1.0, steps_out=8, shrink=64):
@@ -41,13 +40,12 @@ def test_slice_state_matches_the_restatement_bit_for_bit(n_runs):
     """Unit Gaussian in an asymmetric 3-d box, N = 32, K = 8, 3 slices per walk (m = 4, 32 shrink points at most), dlogz = 0.05:
     6 iterations, then on to the stop rule; live set, lnL, status, moved-slice counts, the dead sequence, the stop iteration
     and every counter equal the restatement, ln X and ln Z to 1e-14 relative."""
-    from magprop_amd import _capi, engine
     ndim, nlive, nbatch, slices, seed = 3, 32, 8, 3, 20261016 + n_runs
     lo, hi = np.array([-2.0, -1.0, -4.0]), np.array([3.0, 2.5, 1.5])
     live0 = lo + (hi - lo) * np.random.default_rng(17 + n_runs).random((n_runs, nlive, ndim))
     kw = dict(mu=1.0, max_steps_out=4, max_shrink=32, dlogz=0.05, lower=lo, upper=hi, evaluate_one=nr.gaussian_one)
     s = sr.start(live0, nr.gaussian)
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h = synth_handle()
     ns = RawNested(h, nlive, nbatch, n_runs, ndim, lo, hi, seed, 25, 1, dlogz=0.05)
     try:
         assert _set_slice(ns, slices, 1.0, 4, 32) == 0
@@ -69,11 +67,10 @@ def test_slice_state_matches_the_restatement_bit_for_bit(n_runs):
 def test_slice_chunks_of_one_iteration_equal_one_unsplit_run():
     """Two runs of N = 64 (K = 8, 4 slices) on the unit Gaussian: mp_nested_run(1) called until both stopped equals one
     mp_nested_run(10 000)."""
-    from magprop_amd import _capi, engine
     ndim, nlive, nbatch = 4, 64, 8
     lo, hi = np.full(ndim, -3.0), np.array([2.0, 3.0, 4.0, 5.0])
     live0 = lo + (hi - lo) * np.random.default_rng(3).random((2 * nlive, ndim))
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h = synth_handle()
     states = []
     try:
         for split in (True, False):
@@ -104,11 +101,10 @@ def test_slice_chunks_of_one_iteration_equal_one_unsplit_run():
 def test_zero_slices_is_the_random_walk():
     """A sampler switched to slice mode and back (slices = 0) before its run equals one never switched, bit for bit, and its
     slice counters stay 0."""
-    from magprop_amd import _capi, engine
     ndim, nlive, nbatch = 3, 64, 16
     lo, hi = np.array([-2.0, -1.0, -4.0]), np.array([3.0, 2.5, 1.5])
     live0 = lo + (hi - lo) * np.random.default_rng(8).random((2 * nlive, ndim))
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h = synth_handle()
     states = []
     try:
         for switch in (True, False):
@@ -232,9 +228,9 @@ def test_slice_long_swift_light_curve_lib_reaches_the_best_fit(gswift):
 
 
 def test_set_slice_refuses_bad_arguments():
-    from magprop_amd import _capi, engine
+    from magprop_amd import _capi
     lo, hi = np.zeros(3), np.ones(3)
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h = synth_handle()
     ns = RawNested(h, 32, 8, 1, 3, lo, hi, 0, 25, 1)
     try:
         for bad in ((-1, 1.0, 8, 64), (_capi.NEST_MAX_SLICES + 1, 1.0, 8, 64), (3, 0.0, 8, 64), (3, -1.0, 8, 64),
@@ -243,7 +239,7 @@ def test_set_slice_refuses_bad_arguments():
             assert _set_slice(ns, *bad) == _capi.MP_EINVAL, bad
         assert ns.L.mp_nested_set_slice(None, 3, 1.0, 8, 64) == _capi.MP_EINVAL
         out = np.zeros(1, dtype=np.int64)
-        assert ns.L.mp_nested_get_slice_stats(ns.ns, out.ctypes.data_as(lp64), None, None) == _capi.MP_ESTATE
+        assert ns.L.mp_nested_get_slice_stats(ns.ns, lp(out), None, None) == _capi.MP_ESTATE
         assert _set_slice(ns, _capi.NEST_MAX_SLICES, 0.5, _capi.NEST_MAX_STEPS_OUT, _capi.NEST_MAX_SHRINK) == 0
         assert _set_slice(ns, 0) == 0
         ns.set_live(lo + (hi - lo) * np.random.default_rng(0).random((32, 3)))

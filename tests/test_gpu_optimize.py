@@ -8,10 +8,9 @@ import pytest
 
 import de_restated as de
 from conftest import GOLDEN, TRUTHS, TYPES
+from raw_abi import dp, ip, synth_handle
 
 pytestmark = pytest.mark.gpu
-
-dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 
 
 class RawOptimizer:
@@ -23,14 +22,13 @@ class RawOptimizer:
         self.L, self.popsize, self.n_pops, self.ndim = _capi.lib(), popsize, n_pops, ndim
         self.lo, self.hi = np.ascontiguousarray(lower, dtype=np.float64), np.ascontiguousarray(upper, dtype=np.float64)
         ids = None if ds is None else np.ascontiguousarray(ds, dtype=np.int32)
-        self.o = self.L.mp_optimizer_create(h._h, popsize, n_pops, ndim, None if ids is None else ids.ctypes.data_as(ip),
-                                            C.c_uint64(seed), strategy, f[0], f[1], cr, tol, atol, self.lo.ctypes.data_as(dp),
-                                            self.hi.ctypes.data_as(dp), target)
+        self.o = self.L.mp_optimizer_create(h._h, popsize, n_pops, ndim, ip(ids), C.c_uint64(seed), strategy, f[0], f[1], cr, tol,
+                                            atol, dp(self.lo), dp(self.hi), target)
         assert self.o, _capi.last_error()
 
     def set_population(self, pop):
         p = np.ascontiguousarray(pop, dtype=np.float64)
-        assert self.L.mp_optimizer_set_population(self.o, p.ctypes.data_as(dp)) == 0
+        assert self.L.mp_optimizer_set_population(self.o, dp(p)) == 0
 
     def run(self, n):
         running = C.c_int32(-1)
@@ -60,13 +58,12 @@ def _assert_equal(st, s):
 def test_gaussian_state_matches_the_restatement_bit_for_bit(strategy, n_pops):
     """Unit Gaussian in a box whose corner (0.05, 0.1, -0.2) lies next to the optimum: 300 generations run as 120 + 180, every
     population, lnprob, status, best index, nit and nfev equal to the restatement."""
-    from magprop_amd import _capi, engine
     ndim, popsize, seed = 3, 12, 20261015 + strategy
     lo, hi = np.array([0.05, 0.1, -3.0]), np.array([3.0, 2.5, -0.2])
     pop0 = lo + (hi - lo) * np.random.default_rng(7 + n_pops).random((n_pops, popsize, ndim))
     kw = dict(strategy=strategy, f_lo=0.5, f_hi=1.0, cr=0.7, tol=1e-12, atol=0.0, lower=lo, upper=hi)
     ref = de.run(pop0, 300, de.gaussian, seed, **kw)
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h = synth_handle()
     opt = RawOptimizer(h, popsize, n_pops, ndim, lo, hi, seed, strategy, 1, tol=1e-12)
     try:
         opt.set_population(pop0.reshape(-1, ndim))
@@ -83,9 +80,9 @@ def test_gaussian_state_matches_the_restatement_bit_for_bit(strategy, n_pops):
 def test_humped_posterior_matches_the_restatement_with_lnprob_batch():
     """20 generations of two populations on Humped with the posterior: the restatement's evaluations are mp_lnprob_batch calls on
     batches of the launch's size (60 rows: the same kernel build), and the device state equals it bit for bit."""
-    from magprop_amd import _capi, engine, optimize, synth
+    from magprop_amd import optimize, synth
     g = np.load(GOLDEN + "/golden_synth.npz")
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h = synth_handle()
     h.set_prior(synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK)
     h.set_dataset(0, g["Humped_x"], g["Humped_y"], g["Humped_yerr"])
     lo, hi = synth.PRIOR_LOWER, synth.PRIOR_UPPER
@@ -149,12 +146,11 @@ def test_population_lnprob_equals_logprob_in_a_batch_of_the_same_size(synth_fit)
 def test_converged_populations_stay_frozen():
     """Population 0 starts collapsed (converges at once), population 1 spread over the box: after the first converges, its
     members, lnprob, nit and nfev no longer change while the other goes on; the whole run equals the restatement."""
-    from magprop_amd import _capi, engine
     ndim, popsize, seed = 2, 10, 4
     lo, hi = np.array([-5.0, -5.0]), np.array([5.0, 5.0])
     rng = np.random.default_rng(0)
     pop0 = np.stack([1.0 + 1e-9 * rng.random((popsize, ndim)), lo + (hi - lo) * rng.random((popsize, ndim))])
-    h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+    h = synth_handle()
     opt = RawOptimizer(h, popsize, 2, ndim, lo, hi, seed, de.BEST1BIN, 1, tol=1e-3, atol=1e-9)
     try:
         opt.set_population(pop0.reshape(-1, ndim))
@@ -197,25 +193,24 @@ def test_long_swift_light_curve_lib(gswift):
 
 
 def test_multi_device_and_alternative_torque_handles_are_refused():
-    from magprop_amd import _capi, engine
+    from magprop_amd import _capi
     L = _capi.lib()
     lo, hi = np.zeros(6), np.ones(6)
     x = np.logspace(0.5, 3.0, 20)
-    hm = _capi.Handle(_capi.cfg_synth(), engine.grid(None), device=[0])
-    ha = _capi.Handle(_capi.cfg_synth(dipole_torque=1), engine.grid(None))
+    hm = synth_handle(device=[0])
+    ha = synth_handle(dipole_torque=1)
     try:
         for h, what in ((hm, "ONE device"), (ha, "dipole torque")):
             h.set_dataset(0, x, np.ones_like(x), np.ones_like(x))
-            o = L.mp_optimizer_create(h._h, 10, 1, 6, None, C.c_uint64(0), 0, 0.5, 1.0, 0.7, 0.01, 0.0, lo.ctypes.data_as(dp),
-                                      hi.ctypes.data_as(dp), 0)
+            o = L.mp_optimizer_create(h._h, 10, 1, 6, None, C.c_uint64(0), 0, 0.5, 1.0, 0.7, 0.01, 0.0, dp(lo), dp(hi), 0)
             assert not o and what in _capi.last_error()
         # argument codes on a plain handle
-        h = _capi.Handle(_capi.cfg_synth(), engine.grid(None))
+        h = synth_handle()
         for bad in (dict(popsize=4), dict(cr=1.5), dict(f=(1.0, 0.5)), dict(upper=np.zeros(6))):
             kw = dict(popsize=10, cr=0.7, f=(0.5, 1.0), upper=hi)
             kw.update(bad)
             o = L.mp_optimizer_create(h._h, kw["popsize"], 1, 6, None, C.c_uint64(0), 0, kw["f"][0], kw["f"][1], kw["cr"], 0.01,
-                                      0.0, lo.ctypes.data_as(dp), np.ascontiguousarray(kw["upper"]).ctypes.data_as(dp), 1)
+                                      0.0, dp(lo), dp(np.ascontiguousarray(kw["upper"])), 1)
             assert not o, bad
         h.close()
     finally:

@@ -5,78 +5,15 @@ import numpy as np
 import pytest
 
 from conftest import TRUTHS
-from oracle.stretch_oracle import _draw, philox4x32_10, split, u01
+from moves_restated import STRETCH
+from raw_abi import dp, ip, lp, swap_counts, synth_handle
+from sampler_restated import run as restate
 
 pytestmark = pytest.mark.gpu
 
-M32 = 0xFFFFFFFF
-
-
-def _gauss(p):
-    lnp = 0.0
-    for v in p:
-        lnp = lnp - (0.5 * v) * v
-    return lnp
-
-
-def restate(pos, n_steps, seed, betas, n_walkers, a=2.0):
-    """numpy restatement of the tempered sampler on the unit-Gaussian target: per step the two half-steps (decision
-    ((ndim - 1) ln z + beta lnp_new) - beta lnp_old > ln u, unfused), then one swap sweep per group, hottest pair first,
-    slot i of temperature t - 1 against slot i of temperature t (slot = position in the step's split), accepted if
-    ln u < (beta_{t-1} - beta_t)(L_hot - L_cold), u keyed (seed; step, 2, cold walker, 0).
-    Returns chain, chain_lnp (rows after the swaps), n_accepted, accepted swaps [n_groups][T - 1]."""
-    pos = np.array(pos, dtype=np.float64)
-    n_total, ndim = pos.shape
-    T = len(betas)
-    n_ens = n_total // n_walkers
-    n_groups = n_ens // T
-    half_n = n_walkers // 2
-    n_comp = n_walkers - half_n
-    beta_e = [float(betas[e % T]) for e in range(n_ens)]
-    lnp = np.array([_gauss(p) for p in pos])
-    acc = np.zeros(n_total, dtype=np.int64)
-    swaps = np.zeros((n_groups, T - 1), dtype=np.int64)
-    chain = np.empty((n_steps, n_total, ndim))
-    chain_lnp = np.empty((n_steps, n_total))
-    for step in range(n_steps):
-        perms = [split(seed, step, e, n_walkers) for e in range(n_ens)]
-        for half in range(2):
-            for e in range(n_ens):
-                base, perm, b = e * n_walkers, perms[e], beta_e[e]
-                for slot in range(half_n):
-                    k = base + perm[half * half_n + slot]
-                    jc, zz, logu = _draw(seed, step, half, k, n_comp, a)
-                    j = base + perm[(1 - half) * half_n + jc]
-                    prop = pos[j] - (pos[j] - pos[k]) * zz
-                    new = _gauss(prop)
-                    lnpdiff = ((ndim - 1.0) * np.log(zz) + b * new) - b * lnp[k]
-                    if lnpdiff > logu:
-                        pos[k] = prop
-                        lnp[k] = new
-                        acc[k] += 1
-        for g in range(n_groups):
-            for t in range(T - 1, 0, -1):
-                ec, eh = g * T + t - 1, g * T + t
-                dbeta = float(betas[t - 1]) - float(betas[t])
-                for i in range(n_walkers):
-                    kc, kh = ec * n_walkers + perms[ec][i], eh * n_walkers + perms[eh][i]
-                    r = philox4x32_10(seed & M32, seed >> 32, step, 2, kc, 0)
-                    with np.errstate(divide="ignore"):
-                        lnu = np.log(u01(r[0], r[1]))
-                    if lnu < dbeta * (lnp[kh] - lnp[kc]):
-                        pos[[kc, kh]] = pos[[kh, kc]]
-                        lnp[kc], lnp[kh] = lnp[kh], lnp[kc]
-                        swaps[g, t - 1] += 1
-        chain[step] = pos
-        chain_lnp[step] = lnp
-    return chain, chain_lnp, acc, swaps
-
 
 def _swap_counts(s):
-    from magprop_amd import _capi
-    out = np.zeros((s.ngroups, s.ntemps - 1), dtype=np.int64)
-    assert s._L.mp_sampler_get_swaps(s._s, out.ctypes.data_as(C.POINTER(C.c_int64))) == _capi.MP_OK
-    return out
+    return swap_counts(s._L, s._s, s.ngroups, s.ntemps)
 
 
 def test_tempered_gaussian_chain_matches_the_restatement_bit_for_bit():
@@ -87,7 +24,9 @@ def test_tempered_gaussian_chain_matches_the_restatement_bit_for_bit():
     seed = 20261015
     rng = np.random.default_rng(12)
     pos = rng.normal(size=(4 * 16, 3)) * 1.5
-    chain, lnp, acc, swaps = restate(pos, 200, seed, betas, 16)
+    ref = restate(pos.copy(), 200, seed, [(STRETCH, 1.0, 2.0, 0.0)], n_ensembles=4, n_temps=4,
+                  betas=[betas[e % 4] for e in range(4)])           # (the restatement takes one beta per ensemble)
+    chain, lnp, acc, swaps = ref.chain, ref.lnp, ref.acc, ref.swaps
     assert 0 < swaps.sum() < 200 * 16 * 3                     # swaps both accepted and refused
     for whole in (True, False):
         s = EnsembleSampler(16, 3, target="gaussian", seed=seed, betas=betas, whole_step=whole)
@@ -219,19 +158,18 @@ def test_log_evidence_against_brute_force(gsynth):
 def test_tempering_argument_validation(gsynth):
     from magprop_amd import EnsembleSampler, _capi
     L = _capi.lib()
-    dp = C.POINTER(C.c_double)
     x, y, yerr = gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"]
-    h = _capi.Handle(_capi.cfg_synth(), __import__("magprop_amd").engine.grid(None))
+    h = synth_handle()
     h.set_prior(gsynth["prior_lower"], gsynth["prior_upper"], 0b111100)
     h.set_dataset(0, x, y, yerr)
     h.set_dataset(1, x, y, 2.0 * yerr)
 
     def ladder(*b):
         a = np.array(b, dtype=np.float64)
-        return a, a.ctypes.data_as(dp)
+        return a, dp(a)
 
     ids = np.array([0, 0, 1, 1], dtype=np.int32)
-    sp = L.mp_sampler_create(h._h, 8, 4, 6, ids.ctypes.data_as(C.POINTER(C.c_int32)), C.c_uint64(1), C.c_double(2.0), 0)
+    sp = L.mp_sampler_create(h._h, 8, 4, 6, ip(ids), C.c_uint64(1), C.c_double(2.0), 0)
     assert sp
     for bad in ((0.9, 0.5), (1.0, 1.0), (1.0, 0.0), (1.0, -0.5), (1.0, np.nan), (1.0, np.inf), (1.0, 0.25, 0.5, 0.1)):
         a, p = ladder(*bad)
@@ -243,11 +181,11 @@ def test_tempering_argument_validation(gsynth):
     a, p = ladder(1.0, 0.5, 0.25, 0.125)
     assert L.mp_sampler_set_temperatures(sp, 4, p) == _capi.MP_EINVAL                  # datasets 0 and 1 in one group
     swaps = np.zeros(2, dtype=np.int64)
-    assert L.mp_sampler_get_swaps(sp, swaps.ctypes.data_as(C.POINTER(C.c_int64))) == _capi.MP_ESTATE   # not tempered
+    assert L.mp_sampler_get_swaps(sp, lp(swaps)) == _capi.MP_ESTATE   # not tempered
     a, p = ladder(1.0, 0.5)
     assert L.mp_sampler_set_temperatures(sp, 2, p) == _capi.MP_OK
     pos = np.ascontiguousarray(np.array(TRUTHS["Humped"]) + 1.0e-3 * np.random.default_rng(0).standard_normal((32, 6)))
-    assert L.mp_sampler_set_positions(sp, pos.ctypes.data_as(dp)) == _capi.MP_OK
+    assert L.mp_sampler_set_positions(sp, dp(pos)) == _capi.MP_OK
     assert L.mp_sampler_set_temperatures(sp, 2, p) == _capi.MP_ESTATE                  # after set_positions
     # the walker-sharded entry points refuse a tempered sampler
     rows = C.c_void_p(1)
@@ -256,7 +194,7 @@ def test_tempering_argument_validation(gsynth):
     assert L.mp_sampler_step_shard(sp, 0, 1, rows, None) == _capi.MP_ESTATE
     assert L.mp_sampler_step_apply(sp, rows, None, None, None) == _capi.MP_ESTATE
     assert L.mp_sampler_run(sp, 3, None, None) == _capi.MP_OK
-    assert L.mp_sampler_get_swaps(sp, swaps.ctypes.data_as(C.POINTER(C.c_int64))) == _capi.MP_OK
+    assert L.mp_sampler_get_swaps(sp, lp(swaps)) == _capi.MP_OK
     assert np.all((swaps >= 0) & (swaps <= 3 * 8))
     L.mp_sampler_destroy(sp)
     h.close()

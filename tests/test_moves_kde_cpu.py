@@ -1,12 +1,13 @@
 """CPU checks of the KDE move (include/magprop_amd.h MP_MOVE_KDE): KDEMove's arguments and table codes, the restatement
-(tests/kde_restated.py) against scipy.stats.gaussian_kde, and that it samples a correlated 6-d Gaussian -- and fails to with
-its Hastings term zeroed."""
+(tests/kde_restated.py) against scipy.stats.gaussian_kde, and that it samples a correlated 6-d Gaussian in the restated step
+loop (tests/sampler_restated.py) -- and fails to with its Hastings term zeroed."""
 import math
 
 import numpy as np
 import pytest
 
-from kde_restated import KDE, bandwidth, correlated_gaussian_nd, fit, log_kernel_sum, run
+from kde_restated import KDE, bandwidth, correlated_gaussian_nd, fit, log_kernel_sum
+from sampler_restated import run
 
 # 6-d Gaussian, unit variances, correlation 0.4 between neighbours
 COV6 = np.eye(6) + 0.4 * (np.eye(6, k=1) + np.eye(6, k=-1))
@@ -68,10 +69,10 @@ def test_degenerate_points_have_no_factor():
 def _moments(table, zero_hastings=False):
     rng = np.random.default_rng(21)
     pos = rng.normal(size=(64, 6))
-    chain, _, acc, _, _ = run(pos, 800, 4242, table, lnprob_fn=correlated_gaussian_nd(COV6), zero_hastings=zero_hastings)
-    x = chain[200:].reshape(-1, 6)
+    r = run(pos, 800, 4242, table, lnprob_fn=correlated_gaussian_nd(COV6), zero_hastings=zero_hastings)
+    x = r.chain[200:].reshape(-1, 6)
     c = np.corrcoef(x.T)
-    return x.mean(axis=0), x.var(axis=0), np.array([c[i, i + 1] for i in range(5)]), acc.mean() / 800
+    return x.mean(axis=0), x.var(axis=0), np.array([c[i, i + 1] for i in range(5)]), r.acc.mean() / 800
 
 
 def _within(m, v, c):
