@@ -1,10 +1,12 @@
-// mp_capi.cpp — host side of the C ABI declared in include/magprop_amd.h: the evaluator handle.
+// mp_capi.cpp — host side of the C ABI declared in include/magprop_amd.h: the handle and its evaluators.
 //
-// Plain HIP runtime only (no torch, no hipBLAS): device buffers, one stream per handle, the
-// host-side digestion of observed light curves into the tile-bucketed layout the kernel reads,
-// thin launch wrappers, and the helpers that the resident drivers share (mp_host.h; the drivers
-// themselves: mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp).  There is NO CPU fallback:
-// without a HIP device mp_create() fails.
+// Plain HIP runtime only (no torch, no hipBLAS).  First the per-device evaluator (mp_host.h Evaluator): device buffers,
+// one stream, the dataset arena, thin launch wrappers, its constants and tables, evaluator_create / evaluator_destroy, and
+// the helpers that the resident drivers share (the drivers themselves: mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp).
+// Then the mp_* entry points on the handle, a dealer over one evaluator per device: each has ONE code path, which loops
+// over the evaluators, deals a batch out among them, or runs on the first; mp_create's handle is the case of one
+// evaluator.  The host-side digestion of observed light curves into the tile-bucketed layout the kernel reads happens
+// once per mp_set_dataset.  There is NO CPU fallback: without a HIP device mp_create() fails.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -27,94 +29,94 @@ int fail(int code, const char *fmt, ...) {
 
 // Launch the log-posterior kernel over a batch.  A batch that refers to light curves of more than 64 points next to short
 // ones and needs more than one round of the device's wave slots (two per SIMD) is evaluated longest light curves first.
-int launch_lnprob_ordered(mp_handle *h, const mp::LaunchArgs &a_in, hipStream_t st) {
+int launch_lnprob_ordered(Evaluator *ev, const mp::LaunchArgs &a_in, hipStream_t st) {
     mp::LaunchArgs a = a_in;
     int slot = -1;
     const bool curves = a.ltot || a.lprop || a.ldip || a.mdisc || a.omega;
-    if (h->sh.has_long && h->sh.n_ds > 1 && a.ds_id && a.want_chi2 && !curves && a.n > 2 * h->sh.n_simd) {
-        slot = (int)(h->order_next++ % mp_handle::kOrderRing);
-        if (h->order[slot].cap < (size_t)a.n) {
+    if (ev->sh.has_long && ev->sh.n_ds > 1 && a.ds_id && a.want_chi2 && !curves && a.n > 2 * ev->sh.n_simd) {
+        slot = (int)(ev->order_next++ % Evaluator::kOrderRing);
+        if (ev->order[slot].cap < (size_t)a.n) {
             // (growing frees the old buffer, which waits for the device: nothing in flight reads it any more)
-            const int rc = h->order[slot].ensure((size_t)a.n);
+            const int rc = ev->order[slot].ensure((size_t)a.n);
             if (rc) return rc;
         }
-        if (!h->order_done[slot].e) HIP_TRY(hipEventCreateWithFlags(&h->order_done[slot].e, hipEventDisableTiming));
-        else HIP_TRY(hipStreamWaitEvent(st, h->order_done[slot].e, 0));
-        const int eo = mp::launch_order(h->sh, a.ds_id, a.n, h->order[slot].p, (void *)st);
+        if (!ev->order_done[slot].e) HIP_TRY(hipEventCreateWithFlags(&ev->order_done[slot].e, hipEventDisableTiming));
+        else HIP_TRY(hipStreamWaitEvent(st, ev->order_done[slot].e, 0));
+        const int eo = mp::launch_order(ev->sh, a.ds_id, a.n, ev->order[slot].p, (void *)st);
         if (eo) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)eo));
-        a.order = h->order[slot].p;
+        a.order = ev->order[slot].p;
     }
-    const int e = mp::launch_lnprob(h->sh, a, (void *)st);
+    const int e = mp::launch_lnprob(ev->sh, a, (void *)st);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (slot >= 0) HIP_TRY(hipEventRecord(h->order_done[slot].e, st));
+    if (slot >= 0) HIP_TRY(hipEventRecord(ev->order_done[slot].e, st));
     return MP_OK;
 }
 
-static void publish_datasets(mp_handle *h) {
+static void publish_datasets(Evaluator *ev) {
     int n_ds = 0, extra = 0;
     for (int d = 0; d < MP_MAX_DATASETS; ++d)
-        if (h->ds[d].set) { n_ds = d + 1; extra = std::max(extra, (int)h->ds[d].g.size() - 64); }
-    h->sh.ds = h->d_ds.p;
-    h->sh.n_ds = n_ds;
-    h->sh.tile_ptr = h->d_tile_ptr.p;
-    h->sh.obs_g = h->d_obs_g.p;
-    h->sh.obs_dx = h->d_obs_dx.p;
-    h->sh.obs_idt = h->d_obs_idt.p;
-    h->sh.obs_y = h->d_obs_y.p;
-    h->sh.obs_yerr = h->d_obs_yerr.p;
-    h->sh.has_long = extra > 0 ? 1 : 0;
+        if (ev->ds[d].set) { n_ds = d + 1; extra = std::max(extra, (int)ev->ds[d].g.size() - 64); }
+    ev->sh.ds = ev->d_ds.p;
+    ev->sh.n_ds = n_ds;
+    ev->sh.tile_ptr = ev->d_tile_ptr.p;
+    ev->sh.obs_g = ev->d_obs_g.p;
+    ev->sh.obs_dx = ev->d_obs_dx.p;
+    ev->sh.obs_idt = ev->d_obs_idt.p;
+    ev->sh.obs_y = ev->d_obs_y.p;
+    ev->sh.obs_yerr = ev->d_obs_yerr.p;
+    ev->sh.has_long = extra > 0 ? 1 : 0;
 }
 
 // Copy light curve d behind the arena's last entry and publish its descriptor (slots never set keep n_obs = 0, which
 // the kernels answer with MP_STATUS_BADDATASET).  Nothing in flight reads the target regions: no synchronisation.
-static int append_dataset(mp_handle *h, int d) {
-    const HostDataset &s = h->ds[d];
-    const size_t n = s.g.size(), o = h->obs_used, t = h->tp_used;
-    HIP_TRY(hipMemcpy(h->d_obs_g.p + o, s.g.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_obs_dx.p + o, s.dx.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_obs_idt.p + o, s.idt.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_obs_y.p + o, s.y.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_obs_yerr.p + o, s.yerr.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_tile_ptr.p + t, s.tile_ptr.data(), s.tile_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+static int append_dataset(Evaluator *ev, int d) {
+    const HostDataset &s = ev->ds[d];
+    const size_t n = s.g.size(), o = ev->obs_used, t = ev->tp_used;
+    HIP_TRY(hipMemcpy(ev->d_obs_g.p + o, s.g.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ev->d_obs_dx.p + o, s.dx.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ev->d_obs_idt.p + o, s.idt.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ev->d_obs_y.p + o, s.y.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ev->d_obs_yerr.p + o, s.yerr.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ev->d_tile_ptr.p + t, s.tile_ptr.data(), s.tile_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     int32_t flags = mp::kDsOnKnots;
     for (size_t j = 0; j < n; ++j) if (s.dx[j] != 0.0) { flags = 0; break; }
-    h->desc[d] = mp::DsDesc{(int32_t)n, (int32_t)o, (int32_t)t, flags};
-    HIP_TRY(hipMemcpy(h->d_ds.p + d, &h->desc[d], sizeof(mp::DsDesc), hipMemcpyHostToDevice));
-    h->obs_used = o + n;
-    h->tp_used = t + s.tile_ptr.size();
+    ev->desc[d] = mp::DsDesc{(int32_t)n, (int32_t)o, (int32_t)t, flags};
+    HIP_TRY(hipMemcpy(ev->d_ds.p + d, &ev->desc[d], sizeof(mp::DsDesc), hipMemcpyHostToDevice));
+    ev->obs_used = o + n;
+    ev->tp_used = t + s.tile_ptr.size();
     return MP_OK;
 }
 
 // Rebuild the arena from the host copies (first use, growth, or a replaced slot): waits for the device, because
 // kernels in flight may still read the old buffers, and leaves room for the sets to come.
-static int rebuild_datasets(mp_handle *h) {
+static int rebuild_datasets(Evaluator *ev) {
     size_t n_obs = 0, n_tp = 0;
     for (int d = 0; d < MP_MAX_DATASETS; ++d)
-        if (h->ds[d].set) { n_obs += h->ds[d].g.size(); n_tp += h->ds[d].tile_ptr.size(); }
+        if (ev->ds[d].set) { n_obs += ev->ds[d].g.size(); n_tp += ev->ds[d].tile_ptr.size(); }
     HIP_TRY(hipDeviceSynchronize());
-    const size_t cap_obs = std::max<size_t>(2 * n_obs, 4096), cap_tp = std::max<size_t>(2 * n_tp, 8 * ((size_t)h->n_tiles + 1));
+    const size_t cap_obs = std::max<size_t>(2 * n_obs, 4096), cap_tp = std::max<size_t>(2 * n_tp, 8 * ((size_t)ev->n_tiles + 1));
     int rc;
-    if ((rc = h->d_obs_g.ensure(cap_obs)) || (rc = h->d_obs_dx.ensure(cap_obs)) || (rc = h->d_obs_idt.ensure(cap_obs)) ||
-        (rc = h->d_obs_y.ensure(cap_obs)) || (rc = h->d_obs_yerr.ensure(cap_obs)) || (rc = h->d_tile_ptr.ensure(cap_tp)) ||
-        (rc = h->d_ds.ensure(MP_MAX_DATASETS)))
+    if ((rc = ev->d_obs_g.ensure(cap_obs)) || (rc = ev->d_obs_dx.ensure(cap_obs)) || (rc = ev->d_obs_idt.ensure(cap_obs)) ||
+        (rc = ev->d_obs_y.ensure(cap_obs)) || (rc = ev->d_obs_yerr.ensure(cap_obs)) || (rc = ev->d_tile_ptr.ensure(cap_tp)) ||
+        (rc = ev->d_ds.ensure(MP_MAX_DATASETS)))
         return rc;
-    h->desc.assign(MP_MAX_DATASETS, mp::DsDesc{0, 0, 0, 0});
-    HIP_TRY(hipMemset(h->d_ds.p, 0, MP_MAX_DATASETS * sizeof(mp::DsDesc)));
-    h->obs_used = h->tp_used = 0;
+    ev->desc.assign(MP_MAX_DATASETS, mp::DsDesc{0, 0, 0, 0});
+    HIP_TRY(hipMemset(ev->d_ds.p, 0, MP_MAX_DATASETS * sizeof(mp::DsDesc)));
+    ev->obs_used = ev->tp_used = 0;
     for (int d = 0; d < MP_MAX_DATASETS; ++d)
-        if (h->ds[d].set && (rc = append_dataset(h, d))) return rc;
-    publish_datasets(h);
+        if (ev->ds[d].set && (rc = append_dataset(ev, d))) return rc;
+    publish_datasets(ev);
     return MP_OK;
 }
 
-// After h->ds[d] has been (re)set on the host.
-static int upload_dataset(mp_handle *h, int d, bool replaced) {
-    const HostDataset &s = h->ds[d];
-    const bool fits = h->d_ds.p && h->obs_used + s.g.size() <= h->d_obs_g.cap && h->tp_used + s.tile_ptr.size() <= h->d_tile_ptr.cap;
-    if (replaced || !fits) return rebuild_datasets(h);
-    const int rc = append_dataset(h, d);
+// After ev->ds[d] has been (re)set on the host.
+static int upload_dataset(Evaluator *ev, int d, bool replaced) {
+    const HostDataset &s = ev->ds[d];
+    const bool fits = ev->d_ds.p && ev->obs_used + s.g.size() <= ev->d_obs_g.cap && ev->tp_used + s.tile_ptr.size() <= ev->d_tile_ptr.cap;
+    if (replaced || !fits) return rebuild_datasets(ev);
+    const int rc = append_dataset(ev, d);
     if (rc) return rc;
-    publish_datasets(h);
+    publish_datasets(ev);
     return MP_OK;
 }
 
@@ -139,111 +141,50 @@ int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int rows) {
 }
 
 // *running = the groups whose flag (d_flags[n], read back behind the work on the handle's stream) is not 1 (converged, stopped)
-int groups_running(mp_handle *h, const int32_t *d_flags, int n, int *running) {
+int groups_running(Evaluator *ev, const int32_t *d_flags, int n, int *running) {
     std::vector<int32_t> f((size_t)n);
-    HIP_TRY(hipMemcpyAsync(f.data(), d_flags, f.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(f.data(), d_flags, f.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ev->stream));
+    HIP_TRY(hipStreamSynchronize(ev->stream));
     *running = n - (int)std::count(f.begin(), f.end(), 1);
     return MP_OK;
 }
 
-extern "C" {
-
-int mp_abi_version(void) { return MP_ABI_VERSION; }
-
-const char *mp_last_error(void) { return g_err.c_str(); }
-
-void mp_cfg_synth(mp_model_cfg *c) {
-    if (!c) return;
-    *c = mp_model_cfg{0.35, 3.0, 10.0, 10.0, 0.1, 1.0, 0.9, 1.0, 1.0, 1.0, 0.27, 1, 0, 0.0, 0.0, 0, 0};
-}
-
-void mp_cfg_lib(mp_model_cfg *c) {
-    if (!c) return;
-    *c = mp_model_cfg{0.8, 1.0, 1.0, 1.0, 0.1, 1.0, 0.9, 0.05, 0.4, 1.0, 0.0, 0, 0, 0.0, 0.0, 0, 0};
-}
-
-mp_handle *mp_create(const mp_model_cfg *cfg, const double *tgrid, int n_grid, int device) {
-    if (!cfg || !tgrid || n_grid < 2) {
-        fail(MP_EINVAL, "mp_create: cfg/tgrid NULL or n_grid < 2");
-        return nullptr;
-    }
+// ---------------------------------------------------------------- the pieces of evaluator_create
+// the model configuration and the time grid of mp_create / mp_create_multi
+static int check_model_args(const mp_model_cfg *cfg, const double *tgrid, int n_grid) {
+    if (!cfg || !tgrid || n_grid < 2)
+        return fail(MP_EINVAL, "mp_create: cfg/tgrid NULL or n_grid < 2");
     for (int i = 1; i < n_grid; ++i)
-        if (!(tgrid[i] > tgrid[i - 1]) || !std::isfinite(tgrid[i])) {
-            fail(MP_EINVAL, "mp_create: tgrid must be finite and strictly increasing (index %d)", i);
-            return nullptr;
-        }
+        if (!(tgrid[i] > tgrid[i - 1]) || !std::isfinite(tgrid[i]))
+            return fail(MP_EINVAL, "mp_create: tgrid must be finite and strictly increasing (index %d)", i);
     // The integrator is built on a geometric grid (np.logspace), the only kind the reference uses
     // (magnetar/funcs.py:132-137, code/synthetic_datasets/funcs.py:19).
-    if (!(tgrid[0] > 0.0)) {
-        fail(MP_EINVAL, "mp_create: tgrid must be positive");
-        return nullptr;
-    }
+    if (!(tgrid[0] > 0.0))
+        return fail(MP_EINVAL, "mp_create: tgrid must be positive");
     // the kernels generate the step end times themselves, t_i = t_0 q^i: the grid has to be geometric to rounding
     const double lnq_check = std::log(tgrid[n_grid - 1] / tgrid[0]) / (double)(n_grid - 1);
     for (int i = 1; i < n_grid; ++i)
-        if (std::fabs(tgrid[i] / (tgrid[0] * std::exp((double)i * lnq_check)) - 1.0) > 1.0e-12) {
-            fail(MP_EINVAL, "mp_create: tgrid must be log-spaced (np.logspace); it leaves t0*q^i at index %d", i);
-            return nullptr;
-        }
+        if (std::fabs(tgrid[i] / (tgrid[0] * std::exp((double)i * lnq_check)) - 1.0) > 1.0e-12)
+            return fail(MP_EINVAL, "mp_create: tgrid must be log-spaced (np.logspace); it leaves t0*q^i at index %d", i);
     if (!(cfg->inertia_factor > 0) || !(cfg->alpha > 0) || !(cfg->cs7 > 0) || !(cfg->k > 0) ||
-        !(cfg->rm_massflow_factor > 0)) {
-        fail(MP_EINVAL, "mp_create: non-positive model constant in cfg");
-        return nullptr;
-    }
-    if (!(cfg->sweep_tol >= 0.0) || cfg->sweep_tol > 1.0e-3) {
-        fail(MP_EINVAL, "mp_create: cfg.sweep_tol must be 0 (library default) or in (0, 1e-3]");
-        return nullptr;
-    }
+        !(cfg->rm_massflow_factor > 0))
+        return fail(MP_EINVAL, "mp_create: non-positive model constant in cfg");
+    if (!(cfg->sweep_tol >= 0.0) || cfg->sweep_tol > 1.0e-3)
+        return fail(MP_EINVAL, "mp_create: cfg.sweep_tol must be 0 (library default) or in (0, 1e-3]");
     if (!(cfg->stride_tol >= 0.0) || cfg->stride_tol > 1.0e-3 ||
         !(cfg->max_stride == 0 || cfg->max_stride == 1 || cfg->max_stride == 2 || cfg->max_stride == 4 ||
-          cfg->max_stride == 8)) {
-        fail(MP_EINVAL, "mp_create: cfg.max_stride must be 0, 1, 2, 4 or 8 and cfg.stride_tol 0 or in (0, 1e-3]");
-        return nullptr;
-    }
-    if (cfg->dipole_torque != 0 && cfg->dipole_torque != 1) {
-        fail(MP_EINVAL, "mp_create: cfg.dipole_torque must be 0 (the packages' dipole torque) or 1 (code/figure_3.py's Bucciantini law)");
-        return nullptr;
-    }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        fail(MP_ENODEV, "mp_create: no HIP device visible (this library has no CPU fallback)");
-        return nullptr;
-    }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    if (device >= count) {
-        fail(MP_ENODEV, "mp_create: device %d out of range (%d visible)", device, count);
-        return nullptr;
-    }
-    mp_handle *h = new mp_handle();
-    h->device = device;
-    DeviceScope scope(device);
-    hipDeviceProp_t prop;
-    if (!scope.ok || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipGetDeviceProperties(&prop, device) != hipSuccess) {
-        fail(MP_EHIP, "mp_create: cannot select device %d / create stream", device);
-        mp_destroy(h);
-        return nullptr;
-    }
-    h->tgrid.assign(tgrid, tgrid + n_grid);
-    h->n_tiles = (n_grid - 1 + mp::kTile - 1) / mp::kTile;
-    if (h->d_tgrid.ensure((size_t)n_grid) != MP_OK ||
-        hipMemcpy(h->d_tgrid.p, tgrid, sizeof(double) * (size_t)n_grid, hipMemcpyHostToDevice) != hipSuccess) {
-        fail(MP_EHIP, "mp_create: cannot upload the time grid");
-        mp_destroy(h);
-        return nullptr;
-    }
-    mp::DevShared &s = h->sh;
-    s.tgrid = h->d_tgrid.p;
-    s.n_grid = n_grid;
-    s.n_tiles = h->n_tiles;
-    s.cfg = *cfg;
-    s.n_prior = 0;
-    s.log_mask = 0;
+          cfg->max_stride == 8))
+        return fail(MP_EINVAL, "mp_create: cfg.max_stride must be 0, 1, 2, 4 or 8 and cfg.stride_tol 0 or in (0, 1e-3]");
+    if (cfg->dipole_torque != 0 && cfg->dipole_torque != 1)
+        return fail(MP_EINVAL, "mp_create: cfg.dipole_torque must be 0 (the packages' dipole torque) or 1 (code/figure_3.py's Bucciantini law)");
+    return MP_OK;
+}
+
+static void star_constants(mp::DevShared &s, const mp_model_cfg &cfg) {
     // star constants, magnetar/funcs.py:7-13,75-76
     const double M = 1.4 * mp::kMsol;
     s.GM = mp::kG * M;
-    s.inertia = cfg->inertia_factor * M * mp::kR * mp::kR;
+    s.inertia = cfg.inertia_factor * M * mp::kR * mp::kR;
     s.inv_inertia = 1.0 / s.inertia;
     const double beta = s.GM / (mp::kR * mp::kC * mp::kC);
     const double modW = 0.6 * M * mp::kC * mp::kC * (beta / (1.0 - 0.5 * beta));
@@ -252,18 +193,16 @@ mp_handle *mp_create(const mp_model_cfg *cfg, const double *tgrid, int n_grid, i
     s.inv_sqrtGM = 1.0 / s.sqrtGM;
     s.sqrtR = std::sqrt(mp::kR);
     s.crm_unit = std::pow(1.0e15 * mp::kR * mp::kR * mp::kR, 4.0 / 7.0) * std::pow(s.GM, -1.0 / 7.0) *
-                 std::pow(cfg->rm_massflow_factor, -2.0 / 7.0);
-    s.t0 = tgrid[0];
-    const double lnq = std::log(tgrid[n_grid - 1] / tgrid[0]) / (double)(n_grid - 1);
-    s.lnq8 = lnq / 8.0;
-    s.pre_fine = std::min(32, n_grid - 1);                         // oracle/mp_oracle.c MPO_PRE_FINE
-    s.sweep_tol = cfg->sweep_tol > 0.0 ? cfg->sweep_tol : MP_SWEEP_TOL_DEFAULT;
-    s.stride_tol = cfg->stride_tol > 0.0 ? cfg->stride_tol : MP_STRIDE_TOL_DEFAULT;
+                 std::pow(cfg.rm_massflow_factor, -2.0 / 7.0);
+}
+
+static void policy_constants(mp::DevShared &s, const mp_model_cfg &cfg) {
+    s.sweep_tol = cfg.sweep_tol > 0.0 ? cfg.sweep_tol : MP_SWEEP_TOL_DEFAULT;
+    s.stride_tol = cfg.stride_tol > 0.0 ? cfg.stride_tol : MP_STRIDE_TOL_DEFAULT;
     {
-        const int ms = cfg->max_stride > 0 ? cfg->max_stride : MP_MAX_STRIDE_DEFAULT;
+        const int ms = cfg.max_stride > 0 ? cfg.max_stride : MP_MAX_STRIDE_DEFAULT;
         s.max_kind = ms == 1 ? 1 : (ms == 2 ? 2 : (ms == 4 ? 3 : 4));
     }
-    s.n_simd = std::max(1, prop.multiProcessorCount) * 4;         // 4 SIMDs per CU (1 024 on MI355X)
     s.force_spl = 0;
     s.force_waves = 0;
     // The constants of the stride policy (oracle/mp_oracle.c carries the same ones).  They are not
@@ -305,6 +244,9 @@ mp_handle *mp_create(const mp_model_cfg *cfg, const double *tgrid, int n_grid, i
         env_d("MAGPROP_AMD_STOP_FACTOR", 0.0, 1.0, s.stop_factor);        // (0: every tile runs its verification sweep)
     }
 #endif
+}
+
+static void build_tables(double lnq, mp::DevShared &s, std::vector<double> &wtab, size_t &ttab_off) {
     // Constants of the tile kinds: steps over 1/8, 1, 2, 4, 8 grid intervals (mp_device.h StrideK).
     // Quadrature matrices of the exponential Adams-Moulton formulas on nodes t_{j+1}, t_j, t_{j-1}, ... of a geometric
     // grid of ratio Q (in units of the step, origin t_j: 1, 0, -1/Q, -(1/Q + 1/Q^2), ...):
@@ -328,7 +270,7 @@ mp_handle *mp_create(const mp_model_cfg *cfg, const double *tgrid, int n_grid, i
             for (int m = 0; m < K; ++m) { if (m > 1) fact *= (double)m; W[k * K + m] = fact * co[m] / denom; }
         }
     };
-    std::vector<double> wtab((size_t)mp::kWtabSize, 0.0);
+    wtab.assign((size_t)mp::kWtabSize, 0.0);
     for (int kind = 0; kind < mp::kKinds; ++kind) {
         mp::StrideK &K = s.sk[kind];
         const double lnQ = kind == 0 ? lnq / 8.0 : lnq * (double)(1 << (kind - 1));
@@ -365,23 +307,117 @@ mp_handle *mp_create(const mp_model_cfg *cfg, const double *tgrid, int n_grid, i
         }
     }
     // behind it: Q^k of the kinds 1 .. 4 (mp_device.h DevShared::ttab)
-    const size_t ttab_off = wtab.size();
+    ttab_off = wtab.size();
     wtab.resize(ttab_off + (size_t)(mp::kKinds - 1) * mp::kTtabN);
     for (int kind = 1; kind < mp::kKinds; ++kind)
         for (int k = 0; k < mp::kTtabN; ++k) wtab[ttab_off + (size_t)(kind - 1) * mp::kTtabN + k] = std::exp((double)k * s.sk[kind].lnQ);
-    if (h->d_wtab.ensure(wtab.size()) != MP_OK ||
-        hipMemcpy(h->d_wtab.p, wtab.data(), wtab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        fail(MP_EHIP, "mp_create: cannot upload the quadrature tables");
-        mp_destroy(h);
+}
+
+// what mp_destroy does for every evaluator of a handle: the delete runs while its device is current (DevBuf, mp_host.h)
+static void evaluator_destroy(Evaluator *ev) {
+    DeviceScope scope(ev->device);
+    (void)hipDeviceSynchronize();
+    if (ev->stream) (void)hipStreamDestroy(ev->stream);
+    delete ev;   // (frees the buffers and events, on the evaluator's device)
+}
+
+// One evaluator on `device` (negative: the current one).  NULL with the message set on failure; the messages say mp_create,
+// the entry point that a caller of mp_create_multi reads them through as well.
+static Evaluator *evaluator_create(const mp_model_cfg *cfg, const double *tgrid, int n_grid, int device) {
+    if (check_model_args(cfg, tgrid, n_grid)) return nullptr;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+        fail(MP_ENODEV, "mp_create: no HIP device visible (this library has no CPU fallback)");
         return nullptr;
     }
-    s.wtab = h->d_wtab.p;
-    s.ttab = h->d_wtab.p + ttab_off;
-    if (rebuild_datasets(h) != MP_OK) {
-        mp_destroy(h);
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
+    if (device >= count) {
+        fail(MP_ENODEV, "mp_create: device %d out of range (%d visible)", device, count);
         return nullptr;
+    }
+    Evaluator *ev = new Evaluator();
+    ev->device = device;
+    DeviceScope scope(device);
+    hipDeviceProp_t prop;
+    if (!scope.ok || hipStreamCreateWithFlags(&ev->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipGetDeviceProperties(&prop, device) != hipSuccess) {
+        fail(MP_EHIP, "mp_create: cannot select device %d / create stream", device);
+        evaluator_destroy(ev);
+        return nullptr;
+    }
+    ev->tgrid.assign(tgrid, tgrid + n_grid);
+    ev->n_tiles = (n_grid - 1 + mp::kTile - 1) / mp::kTile;
+    if (ev->d_tgrid.ensure((size_t)n_grid) != MP_OK ||
+        hipMemcpy(ev->d_tgrid.p, tgrid, sizeof(double) * (size_t)n_grid, hipMemcpyHostToDevice) != hipSuccess) {
+        fail(MP_EHIP, "mp_create: cannot upload the time grid");
+        evaluator_destroy(ev);
+        return nullptr;
+    }
+    mp::DevShared &s = ev->sh;
+    s.tgrid = ev->d_tgrid.p;
+    s.n_grid = n_grid;
+    s.n_tiles = ev->n_tiles;
+    s.cfg = *cfg;
+    s.n_prior = 0;
+    s.log_mask = 0;
+    star_constants(s, *cfg);
+    s.t0 = tgrid[0];
+    const double lnq = std::log(tgrid[n_grid - 1] / tgrid[0]) / (double)(n_grid - 1);
+    s.lnq8 = lnq / 8.0;
+    s.pre_fine = std::min(32, n_grid - 1);                         // oracle/mp_oracle.c MPO_PRE_FINE
+    s.n_simd = std::max(1, prop.multiProcessorCount) * 4;         // 4 SIMDs per CU (1 024 on MI355X)
+    policy_constants(s, *cfg);
+    std::vector<double> wtab;
+    size_t ttab_off = 0;
+    build_tables(lnq, s, wtab, ttab_off);
+    if (ev->d_wtab.ensure(wtab.size()) != MP_OK ||
+        hipMemcpy(ev->d_wtab.p, wtab.data(), wtab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        fail(MP_EHIP, "mp_create: cannot upload the quadrature tables");
+        evaluator_destroy(ev);
+        return nullptr;
+    }
+    s.wtab = ev->d_wtab.p;
+    s.ttab = ev->d_wtab.p + ttab_off;
+    if (rebuild_datasets(ev) != MP_OK) {
+        evaluator_destroy(ev);
+        return nullptr;
+    }
+    return ev;
+}
+
+extern "C" {
+
+int mp_abi_version(void) { return MP_ABI_VERSION; }
+
+const char *mp_last_error(void) { return g_err.c_str(); }
+
+void mp_cfg_synth(mp_model_cfg *c) {
+    if (!c) return;
+    *c = mp_model_cfg{0.35, 3.0, 10.0, 10.0, 0.1, 1.0, 0.9, 1.0, 1.0, 1.0, 0.27, 1, 0, 0.0, 0.0, 0, 0};
+}
+
+void mp_cfg_lib(mp_model_cfg *c) {
+    if (!c) return;
+    *c = mp_model_cfg{0.8, 1.0, 1.0, 1.0, 0.1, 1.0, 0.9, 0.05, 0.4, 1.0, 0.0, 0, 0, 0.0, 0.0, 0, 0};
+}
+
+// the handle over one evaluator per listed device
+static mp_handle *handle_create(const mp_model_cfg *cfg, const double *tgrid, int n_grid, const int *devices, int n_devices, bool multi) {
+    mp_handle *h = new mp_handle();
+    h->multi = multi;
+    for (int g = 0; g < n_devices; ++g) {
+        Evaluator *ev = evaluator_create(cfg, tgrid, n_grid, devices[g]);
+        if (!ev) {
+            mp_destroy(h);
+            return nullptr;
+        }
+        h->ev.push_back(ev);
     }
     return h;
+}
+
+mp_handle *mp_create(const mp_model_cfg *cfg, const double *tgrid, int n_grid, int device) {
+    return handle_create(cfg, tgrid, n_grid, &device, 1, false);
 }
 
 mp_handle *mp_create_multi(const mp_model_cfg *cfg, const double *tgrid, int n_grid, const int *devices, int n_devices) {
@@ -389,35 +425,15 @@ mp_handle *mp_create_multi(const mp_model_cfg *cfg, const double *tgrid, int n_g
         fail(MP_EINVAL, "mp_create_multi: devices NULL or n_devices outside 1..64");
         return nullptr;
     }
-    mp_handle *h = new mp_handle();
-    for (int g = 0; g < n_devices; ++g) {
-        mp_handle *s = mp_create(cfg, tgrid, n_grid, devices[g]);     // (validates cfg / tgrid; its message stays in mp_last_error)
-        if (!s) {
-            mp_destroy(h);
-            return nullptr;
-        }
-        h->sub.push_back(s);
-    }
-    h->device = h->sub[0]->device;
-    h->tgrid = h->sub[0]->tgrid;
-    h->n_tiles = h->sub[0]->n_tiles;
-    h->sh = h->sub[0]->sh;          // the scalar settings (policy, tolerances, n_simd of the first device); no device pointer of it is used
-    return h;
+    return handle_create(cfg, tgrid, n_grid, devices, n_devices, true);
 }
 
-int mp_n_devices(const mp_handle *h) { return h ? (h->sub.empty() ? 1 : (int)h->sub.size()) : 0; }
+int mp_n_devices(const mp_handle *h) { return h ? (int)h->ev.size() : 0; }
 
 int mp_destroy(mp_handle *h) {
     if (!h) return MP_OK;
-    if (!h->sub.empty()) {
-        for (mp_handle *s : h->sub) (void)mp_destroy(s);
-        delete h;
-        return MP_OK;
-    }
-    DeviceScope scope(h->device);
-    (void)hipDeviceSynchronize();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;   // (frees the buffers and events, on the handle's device)
+    for (Evaluator *ev : h->ev) evaluator_destroy(ev);
+    delete h;
     return MP_OK;
 }
 
@@ -426,12 +442,7 @@ int mp_set_dataset(mp_handle *h, int ds_id, const double *x, const double *y, co
     if (ds_id < 0 || ds_id >= MP_MAX_DATASETS) return fail(MP_EINVAL, "mp_set_dataset: ds_id %d out of range", ds_id);
     if (n_obs <= 0) return fail(MP_EINVAL, "mp_set_dataset: n_obs must be positive");
     Lock lock(h->mu);
-    if (!h->sub.empty()) {
-        for (mp_handle *s : h->sub) { const int rc = mp_set_dataset(s, ds_id, x, y, yerr, n_obs); if (rc) return rc; }
-        h->sh.n_ds = h->sub[0]->sh.n_ds;
-        return MP_OK;
-    }
-    const std::vector<double> &t = h->tgrid;
+    const std::vector<double> &t = h->first()->tgrid;   // (every evaluator has the same grid: the light curve is digested once)
     const int n = (int)t.size();
     for (int j = 0; j < n_obs; ++j) {
         if (!(x[j] >= t.front()) || !(x[j] <= t.back()))  // interp1d(bounds_error=True), magnetar/funcs.py:214-215
@@ -443,7 +454,7 @@ int mp_set_dataset(mp_handle *h, int ds_id, const double *x, const double *y, co
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return x[a] < x[b]; });
     HostDataset d;
     d.set = true;
-    d.tile_ptr.assign((size_t)h->n_tiles + 1, 0);
+    d.tile_ptr.assign((size_t)h->first()->n_tiles + 1, 0);
     for (int k = 0; k < n_obs; ++k) {
         const int j = order[k];
         int g = (int)(std::upper_bound(t.begin(), t.end(), x[j]) - t.begin()) - 1;  // t[g] <= x < t[g+1]
@@ -456,10 +467,14 @@ int mp_set_dataset(mp_handle *h, int ds_id, const double *x, const double *y, co
         d.tile_ptr[(size_t)(g / mp::kTile) + 1] += 1;
     }
     for (size_t k = 1; k < d.tile_ptr.size(); ++k) d.tile_ptr[k] += d.tile_ptr[k - 1];
-    const bool replaced = h->ds[ds_id].set;
-    h->ds[ds_id] = std::move(d);
-    DeviceScope scope(h->device);
-    return upload_dataset(h, ds_id, replaced);
+    for (Evaluator *ev : h->ev) {
+        const bool replaced = ev->ds[ds_id].set;
+        ev->ds[ds_id] = d;
+        DeviceScope scope(ev->device);
+        const int rc = upload_dataset(ev, ds_id, replaced);
+        if (rc) return rc;
+    }
+    return MP_OK;
 }
 
 int mp_set_prior(mp_handle *h, const double *lower, const double *upper, int ndim, uint32_t log_mask) {
@@ -467,13 +482,14 @@ int mp_set_prior(mp_handle *h, const double *lower, const double *upper, int ndi
     if (ndim < 0 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "mp_set_prior: ndim %d out of range", ndim);
     if (ndim > 0 && (!lower || !upper)) return fail(MP_EINVAL, "mp_set_prior: NULL bounds");
     Lock lock(h->mu);
-    for (mp_handle *s : h->sub) { const int rc = mp_set_prior(s, lower, upper, ndim, log_mask); if (rc) return rc; }
-    for (int i = 0; i < MP_MAX_NDIM; ++i) {
-        h->sh.lower[i] = i < ndim ? lower[i] : -INFINITY;
-        h->sh.upper[i] = i < ndim ? upper[i] : INFINITY;
+    for (Evaluator *ev : h->ev) {
+        for (int i = 0; i < MP_MAX_NDIM; ++i) {
+            ev->sh.lower[i] = i < ndim ? lower[i] : -INFINITY;
+            ev->sh.upper[i] = i < ndim ? upper[i] : INFINITY;
+        }
+        ev->sh.n_prior = ndim;
+        ev->sh.log_mask = log_mask;
     }
-    h->sh.n_prior = ndim;
-    h->sh.log_mask = log_mask;
     return MP_OK;
 }
 
@@ -481,7 +497,7 @@ static int check_batch_args(const mp_handle *h, const void *pars, int n, int ndi
     if (!h || !pars || !lnprob) return fail(MP_EINVAL, "lnprob batch: NULL argument");
     if (n < 0) return fail(MP_EINVAL, "lnprob batch: negative n");
     if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "lnprob batch: ndim must be 6..9, got %d", ndim);
-    if (h->sh.n_ds <= 0) return fail(MP_ESTATE, "lnprob batch: no dataset registered (mp_set_dataset)");
+    if (h->first()->sh.n_ds <= 0) return fail(MP_ESTATE, "lnprob batch: no dataset registered (mp_set_dataset)");
     return MP_OK;
 }
 
@@ -489,10 +505,11 @@ int mp_lnprob_batch_dev(mp_handle *h, const double *d_pars, const int32_t *d_ds_
                         double *d_lnprob, int32_t *d_status, double *d_ltot, void *stream) {
     int rc = check_batch_args(h, d_pars, n, ndim, d_lnprob);
     if (rc) return rc;
-    if (!h->sub.empty()) return fail(MP_ESTATE, "mp_lnprob_batch_dev: device pointers belong to ONE device; a multi-device handle serves the host-buffer entries");
+    if (h->multi) return fail(MP_ESTATE, "mp_lnprob_batch_dev: device pointers belong to ONE device; a multi-device handle serves the host-buffer entries");
+    Evaluator *ev = h->first();
     Lock lock(h->mu);
-    if (!d_ds_id && !h->ds[0].set) return fail(MP_ESTATE, "lnprob batch: ds_id is NULL but dataset 0 is not set");
-    DeviceScope scope(h->device);
+    if (!d_ds_id && !ev->ds[0].set) return fail(MP_ESTATE, "lnprob batch: ds_id is NULL but dataset 0 is not set");
+    DeviceScope scope(ev->device);
     mp::LaunchArgs a{};
     a.pars = d_pars;
     a.ds_id = d_ds_id;
@@ -503,32 +520,32 @@ int mp_lnprob_batch_dev(mp_handle *h, const double *d_pars, const int32_t *d_ds_
     a.lnprob = d_lnprob;
     a.status = d_status;
     a.ltot = d_ltot;
-    return launch_lnprob_ordered(h, a, (hipStream_t)stream);
+    return launch_lnprob_ordered(ev, a, (hipStream_t)stream);
 }
 
-// The host-buffer batch in two halves, so that a multi-device handle can have every device's launch in flight before it
-// waits for the first: batch_begin stages the rows and enqueues the kernel on the handle's stream, batch_end waits and
-// hands the results over.  (Caller holds h->mu and has validated the arguments.)
-static int batch_begin(mp_handle *h, const double *pars, const int32_t *ds_id, int n, int ndim, double *ltot_out) {
+// An evaluator's block of a host-buffer batch in two halves, so that a handle can have every device's launch in flight before
+// it waits for the first: batch_begin stages the rows and enqueues the kernel on the evaluator's stream, batch_end waits and
+// hands the results over.  (Caller holds the handle's lock and has validated the arguments.)
+static int batch_begin(Evaluator *ev, const double *pars, const int32_t *ds_id, int n, int ndim, double *ltot_out, bool tile_log) {
     int rc;
-    DeviceScope scope(h->device);
-    const size_t ng = h->tgrid.size();
-    // One page-locked staging block owned by the handle, mapped into the device's address space: [pars n*ndim f64 | ds_id n i32]
+    DeviceScope scope(ev->device);
+    const size_t ng = ev->tgrid.size();
+    // One page-locked staging block owned by the evaluator, mapped into the device's address space: [pars n*ndim f64 | ds_id n i32]
     // in, [lnprob n f64 | status n i32 | sweeps n i32 | tiles n i32] out.  The kernel reads a walker's 48 - 72 bytes and writes
     // its 20 bytes IN PLACE over PCIe (round 5): no copy command either way -- one launch and one wait per call where the
     // two asynchronous copies around the kernel cost as much as the kernel itself.
     const size_t in_pars = sizeof(double) * (size_t)n * ndim, in_ids = ds_id ? sizeof(int32_t) * (size_t)n : 0;
     const size_t in_bytes = (in_pars + in_ids + 7) & ~(size_t)7;
     const size_t out_bytes = (sizeof(double) + 4 * sizeof(int32_t)) * (size_t)n;   // lnprob | status | sweeps | tiles (+ pad)
-    if ((rc = h->h_io.ensure(in_bytes + out_bytes)) || (ltot_out && (rc = h->w_curves.ensure((size_t)n * ng))))
+    if ((rc = ev->h_io.ensure(in_bytes + out_bytes)) || (ltot_out && (rc = ev->w_curves.ensure((size_t)n * ng))))
         return rc;
-    hipStream_t st = h->stream;
-    std::memcpy(h->h_io.p, pars, in_pars);
-    if (ds_id) std::memcpy(h->h_io.p + in_pars, ds_id, in_ids);
-    unsigned char *d_out = h->h_io.dev + in_bytes;
+    hipStream_t st = ev->stream;
+    std::memcpy(ev->h_io.p, pars, in_pars);
+    if (ds_id) std::memcpy(ev->h_io.p + in_pars, ds_id, in_ids);
+    unsigned char *d_out = ev->h_io.dev + in_bytes;
     mp::LaunchArgs a{};
-    a.pars = (const double *)h->h_io.dev;
-    a.ds_id = ds_id ? (const int32_t *)(h->h_io.dev + in_pars) : nullptr;
+    a.pars = (const double *)ev->h_io.dev;
+    a.ds_id = ds_id ? (const int32_t *)(ev->h_io.dev + in_pars) : nullptr;
     a.n = n;
     a.ndim = ndim;
     a.physical = 0;
@@ -537,41 +554,39 @@ static int batch_begin(mp_handle *h, const double *pars, const int32_t *ds_id, i
     a.status = (int32_t *)(d_out + sizeof(double) * (size_t)n);
     a.sweeps = a.status + n;
     a.tiles = a.sweeps + n;
-    a.ltot = ltot_out ? h->w_curves.p : nullptr;   // rows of walkers that fail are NaN-filled by the kernel
-    if (h->tile_log_on) {
-        if ((rc = h->w_tile_log.ensure((size_t)n * MP_TILE_LOG))) return rc;
-        HIP_TRY(hipMemsetAsync(h->w_tile_log.p, 0xFF, (size_t)n * MP_TILE_LOG * sizeof(int32_t), st));
-        a.tile_log = h->w_tile_log.p;
+    a.ltot = ltot_out ? ev->w_curves.p : nullptr;   // rows of walkers that fail are NaN-filled by the kernel
+    if (tile_log) {
+        if ((rc = ev->w_tile_log.ensure((size_t)n * MP_TILE_LOG))) return rc;
+        HIP_TRY(hipMemsetAsync(ev->w_tile_log.p, 0xFF, (size_t)n * MP_TILE_LOG * sizeof(int32_t), st));
+        a.tile_log = ev->w_tile_log.p;
     }
-    if ((rc = launch_lnprob_ordered(h, a, st))) return rc;
-    if (h->tile_log_on) {
-        h->last_tile_log.resize((size_t)n * MP_TILE_LOG);
-        HIP_TRY(hipMemcpyAsync(h->last_tile_log.data(), h->w_tile_log.p, (size_t)n * MP_TILE_LOG * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    } else h->last_tile_log.clear();
+    if ((rc = launch_lnprob_ordered(ev, a, st))) return rc;
+    if (tile_log) {
+        ev->last_tile_log.resize((size_t)n * MP_TILE_LOG);
+        HIP_TRY(hipMemcpyAsync(ev->last_tile_log.data(), ev->w_tile_log.p, (size_t)n * MP_TILE_LOG * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    } else ev->last_tile_log.clear();
     if (ltot_out)
-        HIP_TRY(hipMemcpyAsync(ltot_out, h->w_curves.p, sizeof(double) * (size_t)n * ng, hipMemcpyDeviceToHost, st));
-    h->pend_n = n;
-    h->pend_in_bytes = in_bytes;
+        HIP_TRY(hipMemcpyAsync(ltot_out, ev->w_curves.p, sizeof(double) * (size_t)n * ng, hipMemcpyDeviceToHost, st));
+    ev->pend_n = n;
+    ev->pend_in_bytes = in_bytes;
     return MP_OK;
 }
 
-static int batch_end(mp_handle *h, double *lnprob_out, int32_t *status_out) {
-    DeviceScope scope(h->device);
-    const int n = h->pend_n;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const unsigned char *h_out = h->h_io.p + h->pend_in_bytes;
+// (the block's sweeps and tiles per walker go behind those of the blocks before it)
+static int batch_end(Evaluator *ev, double *lnprob_out, int32_t *status_out, std::vector<int32_t> &sweeps_out, std::vector<int32_t> &tiles_out) {
+    DeviceScope scope(ev->device);
+    const int n = ev->pend_n;
+    HIP_TRY(hipStreamSynchronize(ev->stream));
+    const unsigned char *h_out = ev->h_io.p + ev->pend_in_bytes;
     std::memcpy(lnprob_out, h_out, sizeof(double) * (size_t)n);
     const int32_t *status = (const int32_t *)(h_out + sizeof(double) * (size_t)n), *sweeps = status + n, *tiles = sweeps + n;
     if (status_out) std::memcpy(status_out, status, sizeof(int32_t) * (size_t)n);
-    double tot = 0.0, tot_tiles = 0.0;
-    int cnt = 0;
-    h->last_sweeps.assign(sweeps, sweeps + n);
-    h->last_tiles.assign(tiles, tiles + n);
+    sweeps_out.insert(sweeps_out.end(), sweeps, sweeps + n);
+    tiles_out.insert(tiles_out.end(), tiles, tiles + n);
+    ev->last_tot_sweeps = ev->last_tot_tiles = 0.0;
+    ev->last_cnt_ok = 0;
     for (int i = 0; i < n; ++i)
-        if (status[i] == MP_STATUS_OK) { tot += sweeps[i]; tot_tiles += tiles[i]; ++cnt; }
-    h->last_tot_sweeps = tot; h->last_tot_tiles = tot_tiles; h->last_cnt_ok = cnt;
-    h->last_mean_sweeps = tot_tiles > 0.0 ? tot / tot_tiles : 0.0;
-    h->last_mean_tiles = cnt ? tot_tiles / (double)cnt : 0.0;
+        if (status[i] == MP_STATUS_OK) { ev->last_tot_sweeps += sweeps[i]; ev->last_tot_tiles += tiles[i]; ++ev->last_cnt_ok; }
     return MP_OK;
 }
 
@@ -581,7 +596,7 @@ int mp_lnprob_batch(mp_handle *h, const double *pars, const int32_t *ds_id, int 
     if (rc) return rc;
     if (n == 0) return MP_OK;
     Lock lock(h->mu);
-    const mp_handle *hd = h->sub.empty() ? h : h->sub[0];     // (the datasets of a multi-device handle live in its evaluators)
+    const Evaluator *hd = h->first();     // (every evaluator holds the same datasets)
     if (ds_id) {
         for (int i = 0; i < n; ++i)
             if (ds_id[i] < 0 || ds_id[i] >= MP_MAX_DATASETS || !hd->ds[ds_id[i]].set)
@@ -589,22 +604,18 @@ int mp_lnprob_batch(mp_handle *h, const double *pars, const int32_t *ds_id, int 
     } else if (!hd->ds[0].set) {
         return fail(MP_ESTATE, "lnprob batch: ds_id is NULL but dataset 0 is not set");
     }
-    if (h->sub.empty()) {
-        if ((rc = batch_begin(h, pars, ds_id, n, ndim, ltot_out))) return rc;
-        return batch_end(h, lnprob_out, status_out);
-    }
-    // Multi-device: contiguous blocks of ceil(n / G) rows (SURVEY.md 8(e)'s partitioning), every device's kernel enqueued before
-    // the first is waited for; one host thread drives them all (a launch returns in microseconds, the kernels run side by side).
-    const int G = (int)h->sub.size(), per = (n + G - 1) / G;
-    const size_t ng = h->tgrid.size();
+    // Contiguous blocks of ceil(n / G) rows (SURVEY.md 8(e)'s partitioning; one device: the batch is the block), every device's
+    // kernel enqueued before the first is waited for; one host thread drives them all (a launch returns in microseconds, the
+    // kernels run side by side).
+    const int G = (int)h->ev.size(), per = (n + G - 1) / G;
+    const size_t ng = hd->tgrid.size();
     int used = 0;
     for (int g = 0; g < G; ++g) {
         const int lo = std::min(g * per, n), cnt = std::min(lo + per, n) - lo;
         if (cnt <= 0) break;
-        mp_handle *s = h->sub[(size_t)g];
-        Lock sl(s->mu);
-        if ((rc = batch_begin(s, pars + (size_t)lo * ndim, ds_id ? ds_id + lo : nullptr, cnt, ndim, ltot_out ? ltot_out + (size_t)lo * ng : nullptr))) {
-            for (int k = 0; k < used; ++k) (void)hipStreamSynchronize(h->sub[(size_t)k]->stream);   // nothing may still write the caller's buffers
+        if ((rc = batch_begin(h->ev[(size_t)g], pars + (size_t)lo * ndim, ds_id ? ds_id + lo : nullptr, cnt, ndim,
+                              ltot_out ? ltot_out + (size_t)lo * ng : nullptr, h->tile_log_on))) {
+            for (int k = 0; k < used; ++k) (void)hipStreamSynchronize(h->ev[(size_t)k]->stream);   // nothing may still write the caller's buffers
             return rc;
         }
         ++used;
@@ -615,14 +626,11 @@ int mp_lnprob_batch(mp_handle *h, const double *pars, const int32_t *ds_id, int 
     double tot = 0.0, tot_tiles = 0.0;
     int cnt_ok = 0;
     for (int g = 0; g < used; ++g) {
-        mp_handle *s = h->sub[(size_t)g];
+        Evaluator *ev = h->ev[(size_t)g];
         const int lo = g * per;
-        Lock sl(s->mu);
-        rc = batch_end(s, lnprob_out + lo, status_out ? status_out + lo : nullptr);
+        rc = batch_end(ev, lnprob_out + lo, status_out ? status_out + lo : nullptr, h->last_sweeps, h->last_tiles);
         if (rc && !first_rc) first_rc = rc;
-        h->last_sweeps.insert(h->last_sweeps.end(), s->last_sweeps.begin(), s->last_sweeps.end());
-        h->last_tiles.insert(h->last_tiles.end(), s->last_tiles.begin(), s->last_tiles.end());
-        tot += s->last_tot_sweeps; tot_tiles += s->last_tot_tiles; cnt_ok += s->last_cnt_ok;
+        tot += ev->last_tot_sweeps; tot_tiles += ev->last_tot_tiles; cnt_ok += ev->last_cnt_ok;
     }
     if (first_rc) return first_rc;
     h->last_mean_sweeps = tot_tiles > 0.0 ? tot / tot_tiles : 0.0;
@@ -633,35 +641,34 @@ int mp_lnprob_batch(mp_handle *h, const double *pars, const int32_t *ds_id, int 
 int mp_model_lc(mp_handle *h, const double *pars, int ndim, double *out, double *traj, int32_t *status) {
     if (!h || !pars || !out) return fail(MP_EINVAL, "mp_model_lc: NULL argument");
     if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "mp_model_lc: ndim must be 6..9, got %d", ndim);
-    if (!h->sub.empty()) return mp_model_lc(h->sub[0], pars, ndim, out, traj, status);   // one walker: the first device
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const size_t ng = h->tgrid.size();
+    Evaluator *ev = h->first();   // one walker, one device: the first
+    Held held(h, ev);
+    const size_t ng = ev->tgrid.size();
     int rc;
-    if ((rc = h->w_pars.ensure(MP_MAX_NDIM)) || (rc = h->w_lnprob.ensure(1)) || (rc = h->w_status.ensure(1)) ||
-        (rc = h->w_curves.ensure(5 * ng)))
+    if ((rc = ev->w_pars.ensure(MP_MAX_NDIM)) || (rc = ev->w_lnprob.ensure(1)) || (rc = ev->w_status.ensure(1)) ||
+        (rc = ev->w_curves.ensure(5 * ng)))
         return rc;
-    hipStream_t st = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->w_pars.p, pars, sizeof(double) * (size_t)ndim, hipMemcpyHostToDevice, st));
+    hipStream_t st = ev->stream;
+    HIP_TRY(hipMemcpyAsync(ev->w_pars.p, pars, sizeof(double) * (size_t)ndim, hipMemcpyHostToDevice, st));
     mp::LaunchArgs a{};
-    a.pars = h->w_pars.p;
+    a.pars = ev->w_pars.p;
     a.n = 1;
     a.ndim = ndim;
     a.physical = 1;
     a.want_chi2 = 0;
-    a.lnprob = h->w_lnprob.p;
-    a.status = h->w_status.p;
-    a.ltot = h->w_curves.p;
-    a.lprop = h->w_curves.p + ng;
-    a.ldip = h->w_curves.p + 2 * ng;
-    a.mdisc = h->w_curves.p + 3 * ng;
-    a.omega = h->w_curves.p + 4 * ng;
-    if ((rc = launch_lnprob_ordered(h, a, st))) return rc;
+    a.lnprob = ev->w_lnprob.p;
+    a.status = ev->w_status.p;
+    a.ltot = ev->w_curves.p;
+    a.lprop = ev->w_curves.p + ng;
+    a.ldip = ev->w_curves.p + 2 * ng;
+    a.mdisc = ev->w_curves.p + 3 * ng;
+    a.omega = ev->w_curves.p + 4 * ng;
+    if ((rc = launch_lnprob_ordered(ev, a, st))) return rc;
     int32_t stt = 0;
-    std::memcpy(out, h->tgrid.data(), sizeof(double) * ng);
-    HIP_TRY(hipMemcpyAsync(out + ng, h->w_curves.p, sizeof(double) * 3 * ng, hipMemcpyDeviceToHost, st));
-    if (traj) HIP_TRY(hipMemcpyAsync(traj, h->w_curves.p + 3 * ng, sizeof(double) * 2 * ng, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&stt, h->w_status.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    std::memcpy(out, ev->tgrid.data(), sizeof(double) * ng);
+    HIP_TRY(hipMemcpyAsync(out + ng, ev->w_curves.p, sizeof(double) * 3 * ng, hipMemcpyDeviceToHost, st));
+    if (traj) HIP_TRY(hipMemcpyAsync(traj, ev->w_curves.p + 3 * ng, sizeof(double) * 2 * ng, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&stt, ev->w_status.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (status) *status = stt;
     return MP_OK;
@@ -677,46 +684,45 @@ int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physica
         if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(MP_EINVAL, "mp_model_band: q[%d] = %g is not in [0, 1]", j, q[j]);
     const uint32_t all = MP_BAND_LTOT | MP_BAND_LPROP | MP_BAND_LDIP;
     if (components == 0 || (components & ~all)) return fail(MP_EINVAL, "mp_model_band: components 0x%x is not a non-empty mask of MP_BAND_*", components);
-    if (!h->sub.empty()) return mp_model_band(h->sub[0], pars, n, ndim, physical, q, nq, components, band_out, status_out, n_used);
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    const size_t ng = h->tgrid.size(), rows = (size_t)n * ng;
+    Evaluator *ev = h->first();
+    Held held(h, ev);
+    const size_t ng = ev->tgrid.size(), rows = (size_t)n * ng;
     const int ncomp = __builtin_popcount(components);
     int rc;
-    if ((rc = h->w_pars.ensure((size_t)n * ndim)) || (rc = h->w_lnprob.ensure((size_t)n)) || (rc = h->w_status.ensure((size_t)n)) ||
-        (rc = h->w_band.ensure(rows * (size_t)(ncomp + 1))) || (rc = h->w_band_out.ensure((size_t)ncomp * nq * ng)))
+    if ((rc = ev->w_pars.ensure((size_t)n * ndim)) || (rc = ev->w_lnprob.ensure((size_t)n)) || (rc = ev->w_status.ensure((size_t)n)) ||
+        (rc = ev->w_band.ensure(rows * (size_t)(ncomp + 1))) || (rc = ev->w_band_out.ensure((size_t)ncomp * nq * ng)))
         return rc;
-    hipStream_t st = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->w_pars.p, pars, sizeof(double) * (size_t)n * ndim, hipMemcpyHostToDevice, st));
+    hipStream_t st = ev->stream;
+    HIP_TRY(hipMemcpyAsync(ev->w_pars.p, pars, sizeof(double) * (size_t)n * ndim, hipMemcpyHostToDevice, st));
     mp::LaunchArgs a{};
-    a.pars = h->w_pars.p;
+    a.pars = ev->w_pars.p;
     a.n = n;
     a.ndim = ndim;
     a.physical = physical ? 1 : 0;
     a.want_chi2 = 0;                          // curves only: no dataset needed
-    a.lnprob = h->w_lnprob.p;
-    a.status = h->w_status.p;
+    a.lnprob = ev->w_lnprob.p;
+    a.status = ev->w_status.p;
     double *curve[3] = {nullptr, nullptr, nullptr};
     for (int c = 0, k = 0; c < 3; ++c)
-        if (components & (1u << c)) curve[c] = h->w_band.p + (size_t)k++ * rows;
+        if (components & (1u << c)) curve[c] = ev->w_band.p + (size_t)k++ * rows;
     a.ltot = curve[0];                        // rows of walkers that did not finish are NaN-filled by the kernel
     a.lprop = curve[1];
     a.ldip = curve[2];
-    if ((rc = launch_lnprob_ordered(h, a, st))) return rc;
+    if ((rc = launch_lnprob_ordered(ev, a, st))) return rc;
     mp::BandQ bq{};
     for (int j = 0; j < nq; ++j) bq.q[j] = q[j];
     bq.nq = nq;
-    double *cols = h->w_band.p + (size_t)ncomp * rows;
+    double *cols = ev->w_band.p + (size_t)ncomp * rows;
     for (int c = 0, k = 0; c < 3; ++c) {
         if (!curve[c]) continue;
         int e = mp::launch_band_transpose(curve[c], cols, n, (int)ng, (void *)st);
-        if (!e) e = mp::launch_band_select(cols, n, (int)ng, bq, h->w_band_out.p + (size_t)k * nq * ng, (void *)st);
+        if (!e) e = mp::launch_band_select(cols, n, (int)ng, bq, ev->w_band_out.p + (size_t)k * nq * ng, (void *)st);
         if (e) return fail(MP_EHIP, "band kernel launch failed: %s", hipGetErrorString((hipError_t)e));
         ++k;
     }
     std::vector<int32_t> stt((size_t)n);
-    HIP_TRY(hipMemcpyAsync(band_out, h->w_band_out.p, sizeof(double) * (size_t)ncomp * nq * ng, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(stt.data(), h->w_status.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(band_out, ev->w_band_out.p, sizeof(double) * (size_t)ncomp * nq * ng, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(stt.data(), ev->w_status.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * (size_t)n);
     if (n_used) *n_used = (int32_t)std::count(stt.begin(), stt.end(), (int32_t)MP_STATUS_OK);
@@ -729,15 +735,14 @@ int mp_rhs_batch(mp_handle *h, const double *pars, int ndim, const double *t, co
     if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "mp_rhs_batch: ndim must be 6..9, got %d", ndim);
     if (n < 0) return fail(MP_EINVAL, "mp_rhs_batch: negative n");
     if (n == 0) return MP_OK;
-    if (!h->sub.empty()) return mp_rhs_batch(h->sub[0], pars, ndim, t, y, n, dydt, lam);
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Evaluator *ev = h->first();
+    Held held(h, ev);
     // one device block: [pars n*ndim | t n | y 2n] in, [dydt 2n | lam n] out
     const size_t n_in = (size_t)n * (ndim + 3), n_out = (size_t)n * 3;
     int rc;
-    if ((rc = h->w_curves.ensure(n_in + n_out))) return rc;
-    double *d = h->w_curves.p;
-    hipStream_t st = h->stream;
+    if ((rc = ev->w_curves.ensure(n_in + n_out))) return rc;
+    double *d = ev->w_curves.p;
+    hipStream_t st = ev->stream;
     HIP_TRY(hipMemcpyAsync(d, pars, sizeof(double) * (size_t)n * ndim, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d + (size_t)n * ndim, t, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d + (size_t)n * (ndim + 1), y, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, st));
@@ -749,7 +754,7 @@ int mp_rhs_batch(mp_handle *h, const double *pars, int ndim, const double *t, co
     r.lam = d + n_in + 2 * (size_t)n;
     r.n = n;
     r.ndim = ndim;
-    const int e = mp::launch_rhs(h->sh, r, st);
+    const int e = mp::launch_rhs(ev->sh, r, st);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     HIP_TRY(hipMemcpyAsync(dydt, r.dydt, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
     if (lam) HIP_TRY(hipMemcpyAsync(lam, r.lam, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
@@ -760,18 +765,16 @@ int mp_rhs_batch(mp_handle *h, const double *pars, int ndim, const double *t, co
 int mp_synchronize(mp_handle *h) {
     if (!h) return fail(MP_EINVAL, "mp_synchronize: NULL handle");
     Lock lock(h->mu);
-    if (!h->sub.empty()) {
-        for (mp_handle *s : h->sub) { const int rc = mp_synchronize(s); if (rc) return rc; }
-        return MP_OK;
+    for (Evaluator *ev : h->ev) {
+        DeviceScope scope(ev->device);
+        HIP_TRY(hipStreamSynchronize(ev->stream));
     }
-    DeviceScope scope(h->device);
-    HIP_TRY(hipStreamSynchronize(h->stream));
     return MP_OK;
 }
 
-int mp_device(const mp_handle *h) { return h ? h->device : -1; }
-void *mp_stream(const mp_handle *h) { return h ? (void *)h->stream : nullptr; }   // (a multi-device handle has none: NULL)
-int mp_n_grid(const mp_handle *h) { return h ? (int)h->tgrid.size() : 0; }
+int mp_device(const mp_handle *h) { return h ? h->first()->device : -1; }
+void *mp_stream(const mp_handle *h) { return h && !h->multi ? (void *)h->first()->stream : nullptr; }   // (a multi-device handle has none: NULL)
+int mp_n_grid(const mp_handle *h) { return h ? (int)h->first()->tgrid.size() : 0; }
 double mp_last_mean_sweeps(const mp_handle *h) { return h ? h->last_mean_sweeps : 0.0; }
 double mp_last_mean_tiles(const mp_handle *h) { return h ? h->last_mean_tiles : 0.0; }
 int mp_last_sweeps(const mp_handle *h, int32_t *out, int n) {
@@ -783,21 +786,19 @@ int mp_last_sweeps(const mp_handle *h, int32_t *out, int n) {
 int mp_tile_log(mp_handle *h, int enable) {
     if (!h) return fail(MP_EINVAL, "mp_tile_log: NULL handle");
     Lock lock(h->mu);
-    for (mp_handle *s : h->sub) (void)mp_tile_log(s, enable);
     h->tile_log_on = enable != 0;
     return MP_OK;
 }
 int mp_last_tile_log(const mp_handle *h, int walker, int32_t *out, int n) {
     if (!h || !out || n < 0 || walker < 0) return fail(MP_EINVAL, "mp_last_tile_log: bad argument");
-    if (!h->sub.empty()) {   // the walker's block and its row inside it (contiguous blocks of ceil(n / G) rows)
-        const int G = (int)h->sub.size(), total = (int)h->last_tiles.size(), per = (total + G - 1) / std::max(G, 1);
-        if (per <= 0 || walker >= total) return 0;
-        return mp_last_tile_log(h->sub[(size_t)(walker / per)], walker % per, out, n);
-    }
-    const size_t off = (size_t)walker * MP_TILE_LOG;
-    if (off + MP_TILE_LOG > h->last_tile_log.size()) return 0;
+    // the walker's block and its row inside it (contiguous blocks of ceil(n / G) rows of the last batch)
+    const int G = (int)h->ev.size(), total = (int)h->last_tiles.size(), per = (total + G - 1) / G;
+    if (per <= 0 || walker >= total) return 0;
+    const std::vector<int32_t> &log = h->ev[(size_t)(walker / per)]->last_tile_log;
+    const size_t off = (size_t)(walker % per) * MP_TILE_LOG;
+    if (off + MP_TILE_LOG > log.size()) return 0;
     int m = 0;
-    while (m < n && m < MP_TILE_LOG && h->last_tile_log[off + m] != -1) { out[m] = h->last_tile_log[off + m]; ++m; }
+    while (m < n && m < MP_TILE_LOG && log[off + m] != -1) { out[m] = log[off + m]; ++m; }
     return m;
 }
 int mp_last_tiles(const mp_handle *h, int32_t *out, int n) {
@@ -806,10 +807,10 @@ int mp_last_tiles(const mp_handle *h, int32_t *out, int n) {
     std::copy(h->last_tiles.begin(), h->last_tiles.begin() + m, out);
     return m;
 }
-double mp_sweep_tol(const mp_handle *h) { return h ? h->sh.sweep_tol : 0.0; }
+double mp_sweep_tol(const mp_handle *h) { return h ? h->first()->sh.sweep_tol : 0.0; }
 int mp_get_policy(const mp_handle *h, double *out, int n) {
     if (!h || !out || n < 0) return fail(MP_EINVAL, "mp_get_policy: bad argument");
-    const mp::DevShared &s = h->sh;
+    const mp::DevShared &s = h->first()->sh;
     double v[MP_POLICY_COUNT];
     v[MP_POLICY_MAX_STRIDE] = (double)(s.max_kind <= 1 ? 1 : (1 << (s.max_kind - 1)));
     v[MP_POLICY_STRIDE_TOL] = s.stride_tol;
@@ -836,6 +837,6 @@ int mp_get_policy(const mp_handle *h, double *out, int n) {
     std::copy(v, v + m, out);
     return m;
 }
-int mp_n_simd(const mp_handle *h) { return h ? h->sh.n_simd : 0; }
+int mp_n_simd(const mp_handle *h) { return h ? h->first()->sh.n_simd : 0; }
 
 }  // extern "C"

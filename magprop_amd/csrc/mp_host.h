@@ -1,8 +1,9 @@
 // mp_host.h — what the host sources of the C ABI share (mp_capi.cpp, mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp).
 //
 // Internal: not installed, never seen by a kernel source.  Error reporting, owners of device memory, pinned memory and events,
-// the evaluator handle, and the helpers of mp_capi.cpp that the resident drivers call.  Each driver's own struct stays in its
-// source file.
+// the two types behind the ABI's handle -- Evaluator, everything that lives on ONE device, and mp_handle, the dealer that owns
+// one evaluator per device and the lock -- and the helpers of mp_capi.cpp that the resident drivers call.  Each driver's own
+// struct stays in its source file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,7 +28,7 @@ int fail(int code, const char *fmt, ...);
         if (e_ != hipSuccess) return fail(MP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-struct DeviceScope {  // make the handle's device current for the duration of a call
+struct DeviceScope {  // make an evaluator's device current for the duration of a call
     int prev = -1;
     bool ok = true;
     explicit DeviceScope(int dev) {
@@ -119,7 +120,11 @@ int read_back(T *dst, const T *src, size_t n, Rest... rest) {
     return read_back(rest...);
 }
 
-struct mp_handle {
+// Everything of a handle that lives on one device: stream, constants and tables, the dataset arena, the workspaces of the
+// host-buffer entry points.  Made by evaluator_create and freed by evaluator_destroy (mp_capi.cpp), which deletes it inside a
+// DeviceScope of its device -- not by a destructor body, which would end before the members' destructors free their memory.
+// It has no lock of its own: its handle's lock covers it.
+struct Evaluator {
     int device = 0;
     hipStream_t stream = nullptr;
     std::vector<double> tgrid;
@@ -139,13 +144,9 @@ struct mp_handle {
     DevBuf<double> w_pars, w_lnprob, w_curves;
     DevBuf<double> w_band, w_band_out;   // mp_model_band: [components][n][n_grid] curves | [n_grid][n] transposed; [components][nq][n_grid]
     DevBuf<int32_t> w_dsid, w_status, w_sweeps;
-    double last_mean_tiles = 0.0;
-    bool tile_log_on = false;
     DevBuf<int32_t> w_tile_log;
-    std::vector<int32_t> last_tile_log;
+    std::vector<int32_t> last_tile_log;   // tile words of the rows of its block of the most recent host-buffer batch
     PinnedBuf h_io;               // mp_lnprob_batch: [pars | ds_id] in, [lnprob | status | sweeps | tiles] out, read and written in place by the kernel
-    double last_mean_sweeps = 0.0;
-    std::vector<int32_t> last_sweeps, last_tiles;   // per walker, most recent host-buffer batch (diagnostic)
     // Launch order of mixed-length batches (mp_kernels.hip order_kernel): a ring of index buffers, one per launch in flight.
     // A slot is written by the launch that takes it and read by that launch's workgroups as they start; the launch that
     // takes it kOrderRing launches later waits (stream-level, on the event recorded behind the earlier launch) for that
@@ -154,26 +155,43 @@ struct mp_handle {
     DevBuf<int32_t> order[kOrderRing];
     Event order_done[kOrderRing];
     unsigned order_next = 0;
+    int pend_n = 0;               // rows of its block of the host-buffer batch between batch_begin and batch_end
+    size_t pend_in_bytes = 0;
+    double last_tot_sweeps = 0.0, last_tot_tiles = 0.0;   // over the walkers of its last block that finished (status ok) ...
+    int last_cnt_ok = 0;                                  // ... and how many those were
+};
+
+// The handle of the ABI: a dealer over one evaluator per device (mp_create: one; mp_create_multi: one per listed device) and
+// no device state of its own.  Datasets and the prior go to every evaluator, a host-buffer batch is dealt out in contiguous
+// blocks, whatever serves one walker or one device runs on the first.
+struct mp_handle {
+    std::vector<Evaluator *> ev;  // owned: freed by mp_destroy
+    bool multi = false;           // made by mp_create_multi: the entries that belong to ONE device refuse it, even over one device
     // Threading / stream contract (include/magprop_amd.h): every entry point that takes a handle or a sampler holds
     // `mu` for its duration.  Launches share nothing writable but their own outputs (round 4: no per-walker scratch rows),
     // so launches of one handle on different streams may overlap freely.
     std::recursive_mutex mu;
-    // Multi-device handle (mp_create_multi): one evaluator per listed device; this object then holds no device state of
-    // its own -- datasets and prior are forwarded to every evaluator, a host-buffer batch is dealt out in contiguous blocks.
-    std::vector<mp_handle *> sub;
-    int pend_n = 0;               // rows of the host-buffer batch between batch_begin and batch_end
-    size_t pend_in_bytes = 0;
-    double last_tot_sweeps = 0.0, last_tot_tiles = 0.0;   // over the walkers of the last batch that finished (status ok) ...
-    int last_cnt_ok = 0;                                  // ... and how many those were
+    bool tile_log_on = false;
+    // the most recent host-buffer batch, all blocks (diagnostic): per walker, and the means over the walkers that finished
+    std::vector<int32_t> last_sweeps, last_tiles;
+    double last_mean_sweeps = 0.0, last_mean_tiles = 0.0;
+    Evaluator *first() const { return ev[0]; }   // the scalar settings are the same on every evaluator
 };
 
 using Lock = std::lock_guard<std::recursive_mutex>;
 
+// What an entry point holds for its duration: the handle's lock, then the evaluator's device made current.
+struct Held {
+    Lock lock;
+    DeviceScope scope;
+    Held(mp_handle *h, const Evaluator *e) : lock(h->mu), scope(e->device) {}
+};
+
 // ---------------------------------------------------------------- defined in mp_capi.cpp, used by the drivers
-int launch_lnprob_ordered(mp_handle *h, const mp::LaunchArgs &a_in, hipStream_t st);
+int launch_lnprob_ordered(Evaluator *h, const mp::LaunchArgs &a_in, hipStream_t st);
 int check_box(const char *fn, int ndim, const double *lower, const double *upper);
 int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int rows);
-int groups_running(mp_handle *h, const int32_t *d_flags, int n, int *running);
+int groups_running(Evaluator *h, const int32_t *d_flags, int n, int *running);
 
 // The checks of the drivers' create functions (fn), in the order they fail: a multi-device handle (`multi`: what the message says about
 // it), ndim (the posterior, target 0, needs 6 or more), the driver's own arguments (args(): MP_OK or the code of a failure), the
@@ -182,16 +200,16 @@ int groups_running(mp_handle *h, const int32_t *d_flags, int n, int *running);
 template <class Args>
 int check_create(mp_handle *h, const char *fn, const char *multi, int ndim, int target, const char *group, int n_groups,
                  const int32_t *ds_id, Args &&args) {
-    if (!h->sub.empty()) return fail(MP_ESTATE, "%s: %s", fn, multi);
+    if (h->multi) return fail(MP_ESTATE, "%s: %s", fn, multi);
     if (ndim < 1 || ndim > MP_MAX_NDIM || (target == 0 && ndim < 6)) return fail(MP_EINVAL, "%s: bad ndim %d", fn, ndim);
     const int rc = args();
     if (rc) return rc;
     if (target != 0) return MP_OK;
-    if (h->sh.cfg.dipole_torque != 0)
+    if (h->first()->sh.cfg.dipole_torque != 0)
         return fail(MP_ESTATE, "%s: the alternative dipole torque (cfg.dipole_torque = 1) is served by the curve kernels only", fn);
     for (int g = 0; g < n_groups; ++g) {
         const int d = ds_id ? ds_id[g] : 0;
-        if (d < 0 || d >= MP_MAX_DATASETS || !h->ds[d].set) return fail(MP_ESTATE, "%s: %s %d refers to unset dataset %d", fn, group, g, d);
+        if (d < 0 || d >= MP_MAX_DATASETS || !h->first()->ds[d].set) return fail(MP_ESTATE, "%s: %s %d refers to unset dataset %d", fn, group, g, d);
     }
     return MP_OK;
 }

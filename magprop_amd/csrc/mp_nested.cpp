@@ -2,7 +2,8 @@
 #include "mp_host.h"
 
 struct mp_nested {
-    mp_handle *h = nullptr;
+    mp_handle *h = nullptr;         // the lock
+    Evaluator *ev = nullptr;        // the device state: the handle's one evaluator
     mp::NestArgs a{};
     int n_total = 0;                // n_runs * nlive
     int chunk = 0;                  // iterations per chunk (slots of the dead buffers)
@@ -37,6 +38,7 @@ mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int
     if (rc) return nullptr;
     mp_nested *ns = new mp_nested();
     ns->h = h;
+    ns->ev = h->first();
     ns->n_total = nlive * n_runs;
     // dead buffers of about 16 MB at most, up to 32 iterations per chunk
     const size_t row = (size_t)n_runs * nbatch * (ndim + 2) * sizeof(double);
@@ -48,7 +50,7 @@ mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int
     a.dlogz = dlogz;
     for (int d = 0; d < ndim; ++d) { a.lower[d] = lower[d]; a.upper[d] = upper[d]; }
     ns->dead_pars.resize(n_runs); ns->dead_lnl.resize(n_runs); ns->dead_n.resize(n_runs);
-    DeviceScope scope(h->device);
+    DeviceScope scope(ns->ev->device);
     const size_t nt = (size_t)ns->n_total, nr = (size_t)n_runs, nk = nr * nbatch, nc = (size_t)ns->chunk * nk;
     Binder bind;
     bind(ns->d_live, nt * ndim, a.live); bind(ns->d_lnl, nt, a.lnl); bind(ns->d_st, nt, a.st); bind(ns->d_acc, nt, a.acc);
@@ -67,16 +69,15 @@ mp_nested *mp_nested_create(mp_handle *h, int nlive, int nbatch, int n_runs, int
 
 int mp_nested_destroy(mp_nested *ns) {
     if (!ns) return MP_OK;
-    Lock lock(ns->h->mu);
-    DeviceScope scope(ns->h->device);
-    (void)hipStreamSynchronize(ns->h->stream);
+    Held held(ns->h, ns->ev);
+    (void)hipStreamSynchronize(ns->ev->stream);
     delete ns;
     return MP_OK;
 }
 
 int mp_nested_set_live(mp_nested *ns, const double *live) {
     if (!ns || !live) return fail(MP_EINVAL, "mp_nested_set_live: NULL argument");
-    mp_handle *h = ns->h;
+    Evaluator *ev = ns->ev;
     mp::NestArgs &a = ns->a;
     const size_t nt = (size_t)ns->n_total, nr = (size_t)a.n_runs;
     for (size_t i = 0; i < nt; ++i)
@@ -84,25 +85,24 @@ int mp_nested_set_live(mp_nested *ns, const double *live) {
             const double v = live[i * a.ndim + d];
             if (!(v >= a.lower[d] && v <= a.upper[d])) return fail(MP_EINVAL, "mp_nested_set_live: live point %zu lies outside the box", i);
         }
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Held held(ns->h, ev);
     const std::vector<double> zero(nr, 0.0), ninf(nr, -INFINITY);
-    HIP_TRY(hipMemcpyAsync(a.live, live, nt * a.ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(a.lnx, zero.data(), nr * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(a.lnz, ninf.data(), nr * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(a.stopped, 0, nr * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(a.nit, 0, nr * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(a.ncall, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(a.nacc, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(a.nzero, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(ns->sl.nexpand, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(ns->sl.ncontract, 0, nr * sizeof(int64_t), h->stream));
-    HIP_TRY(hipMemsetAsync(ns->sl.nfail, 0, nr * sizeof(int64_t), h->stream));
+    HIP_TRY(hipMemcpyAsync(a.live, live, nt * a.ndim * sizeof(double), hipMemcpyHostToDevice, ev->stream));
+    HIP_TRY(hipMemcpyAsync(a.lnx, zero.data(), nr * sizeof(double), hipMemcpyHostToDevice, ev->stream));
+    HIP_TRY(hipMemcpyAsync(a.lnz, ninf.data(), nr * sizeof(double), hipMemcpyHostToDevice, ev->stream));
+    HIP_TRY(hipMemsetAsync(a.stopped, 0, nr * sizeof(int32_t), ev->stream));
+    HIP_TRY(hipMemsetAsync(a.nit, 0, nr * sizeof(int32_t), ev->stream));
+    HIP_TRY(hipMemsetAsync(a.ncall, 0, nr * sizeof(int64_t), ev->stream));
+    HIP_TRY(hipMemsetAsync(a.nacc, 0, nr * sizeof(int64_t), ev->stream));
+    HIP_TRY(hipMemsetAsync(a.nzero, 0, nr * sizeof(int64_t), ev->stream));
+    HIP_TRY(hipMemsetAsync(ns->sl.nexpand, 0, nr * sizeof(int64_t), ev->stream));
+    HIP_TRY(hipMemsetAsync(ns->sl.ncontract, 0, nr * sizeof(int64_t), ev->stream));
+    HIP_TRY(hipMemsetAsync(ns->sl.nfail, 0, nr * sizeof(int64_t), ev->stream));
     a.mode = 1;
     a.iter = 0;
-    const int e = mp::launch_nest_walk(h->sh, a, h->stream);
+    const int e = mp::launch_nest_walk(ev->sh, a, ev->stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(ev->stream));
     ns->iter = 0;
     for (size_t r = 0; r < nr; ++r) { ns->dead_pars[r].clear(); ns->dead_lnl[r].clear(); ns->dead_n[r].clear(); }
     ns->have_state = true;
@@ -112,10 +112,9 @@ int mp_nested_set_live(mp_nested *ns, const double *live) {
 int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running) {
     if (!ns || max_iterations < 0) return fail(MP_EINVAL, "mp_nested_run: bad argument");
     if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_run: call mp_nested_set_live first");
-    mp_handle *h = ns->h;
+    Evaluator *ev = ns->ev;
     mp::NestArgs &a = ns->a;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Held held(ns->h, ev);
     // Chunks of iterations enqueued back to back (select, walk, select, walk, ...; no wait inside a chunk), then a stop check on
     // the live set as it stands and one read-back of the counters and the dead rows; the run ends early once every run stopped.
     const int nr = a.n_runs, K = a.nbatch, nd = a.ndim;
@@ -124,29 +123,29 @@ int mp_nested_run(mp_nested *ns, int max_iterations, int *n_running) {
     std::vector<double> hp, hl;
     std::vector<int32_t> hn;
     int running, rc;
-    if ((rc = groups_running(h, a.stopped, nr, &running))) return rc;
+    if ((rc = groups_running(ev, a.stopped, nr, &running))) return rc;
     for (int done = 0; done < max_iterations && running > 0;) {
         const int chunk = std::min(ns->chunk, max_iterations - done);
-        HIP_TRY(hipMemcpyAsync(nit0.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(nit0.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, ev->stream));
         for (int c = 0; c < chunk; ++c) {
             a.slot = c;
             a.iter = ns->iter++;
             a.mode = 0;
-            int e = mp::launch_nest_select(a, h->stream);
-            if (!e) e = ns->sl.slices ? mp::launch_nest_slice(h->sh, a, ns->sl, h->stream) : mp::launch_nest_walk(h->sh, a, h->stream);
+            int e = mp::launch_nest_select(a, ev->stream);
+            if (!e) e = ns->sl.slices ? mp::launch_nest_slice(ev->sh, a, ns->sl, ev->stream) : mp::launch_nest_walk(ev->sh, a, ev->stream);
             if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
         }
         a.mode = 1;
-        int e = mp::launch_nest_select(a, h->stream);
+        int e = mp::launch_nest_select(a, ev->stream);
         if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
         hp.resize((size_t)chunk * per * nd);
         hl.resize((size_t)chunk * per);
         hn.resize((size_t)chunk * per);
-        HIP_TRY(hipMemcpyAsync(hp.data(), a.dead_pars, hp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(hl.data(), a.dead_lnl, hl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(hn.data(), a.dead_n, hn.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(nit1.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        if ((rc = groups_running(h, a.stopped, nr, &running))) return rc;   // (behind the copies above: they have landed)
+        HIP_TRY(hipMemcpyAsync(hp.data(), a.dead_pars, hp.size() * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
+        HIP_TRY(hipMemcpyAsync(hl.data(), a.dead_lnl, hl.size() * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
+        HIP_TRY(hipMemcpyAsync(hn.data(), a.dead_n, hn.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ev->stream));
+        HIP_TRY(hipMemcpyAsync(nit1.data(), a.nit, nr * sizeof(int32_t), hipMemcpyDeviceToHost, ev->stream));
+        if ((rc = groups_running(ev, a.stopped, nr, &running))) return rc;   // (behind the copies above: they have landed)
         // run r ran the first nit1 - nit0 iterations of the chunk (a stopped run stays stopped)
         for (int r = 0; r < nr; ++r)
             for (int c = 0; c < nit1[r] - nit0[r]; ++c) {
@@ -177,12 +176,11 @@ int mp_nested_get_state(mp_nested *ns, double *live, double *lnl, int32_t *statu
                         double *lnx, double *lnz, int64_t *ncall, int64_t *nacc, int64_t *nzero) {
     if (!ns) return fail(MP_EINVAL, "mp_nested_get_state: NULL sampler");
     if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_get_state: call mp_nested_set_live first");
-    mp_handle *h = ns->h;
+    Evaluator *ev = ns->ev;
     const mp::NestArgs &a = ns->a;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Held held(ns->h, ev);
     const size_t nt = (size_t)ns->n_total, nr = (size_t)a.n_runs;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(ev->stream));
     return read_back(live, a.live, nt * a.ndim, lnl, a.lnl, nt, status, a.st, nt, acc, a.acc, nt, nit, a.nit, nr,
                      stopped, a.stopped, nr, lnx, a.lnx, nr, lnz, a.lnz, nr, ncall, a.ncall, nr, nacc, a.nacc, nr, nzero, a.nzero, nr);
 }
@@ -206,11 +204,10 @@ int mp_nested_set_slice(mp_nested *ns, int slices, double mu, int max_steps_out,
 int mp_nested_get_slice_stats(mp_nested *ns, int64_t *nexpand, int64_t *ncontract, int64_t *nfail) {
     if (!ns) return fail(MP_EINVAL, "mp_nested_get_slice_stats: NULL sampler");
     if (!ns->have_state) return fail(MP_ESTATE, "mp_nested_get_slice_stats: call mp_nested_set_live first");
-    mp_handle *h = ns->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Evaluator *ev = ns->ev;
+    Held held(ns->h, ev);
     const size_t nr = (size_t)ns->a.n_runs;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(ev->stream));
     return read_back(nexpand, ns->sl.nexpand, nr, ncontract, ns->sl.ncontract, nr, nfail, ns->sl.nfail, nr);
 }
 

@@ -2,7 +2,8 @@
 #include "mp_host.h"
 
 struct mp_optimizer {
-    mp_handle *h = nullptr;
+    mp_handle *h = nullptr;         // the lock
+    Evaluator *ev = nullptr;        // the device state: the handle's one evaluator
     mp::OptArgs a{};                // pointers: cur / next as of the next launch
     int n_total = 0;
     uint32_t gen = 0;               // generations launched so far (0: only the initial evaluation)
@@ -22,8 +23,8 @@ static void opt_swap(mp_optimizer *o) {
 static int opt_enqueue(mp_optimizer *o, int trial) {
     o->a.trial = trial;
     o->a.gen = o->gen;
-    int e = mp::launch_opt_trial(o->h->sh, o->a, o->h->stream);
-    if (!e) e = mp::launch_opt_reduce(o->a, o->h->stream);
+    int e = mp::launch_opt_trial(o->ev->sh, o->a, o->ev->stream);
+    if (!e) e = mp::launch_opt_reduce(o->a, o->ev->stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     opt_swap(o);
     return MP_OK;
@@ -50,12 +51,13 @@ mp_optimizer *mp_optimizer_create(mp_handle *h, int popsize, int n_pops, int ndi
     if (rc) return nullptr;
     mp_optimizer *o = new mp_optimizer();
     o->h = h;
+    o->ev = h->first();
     o->n_total = popsize * n_pops;
     mp::OptArgs &a = o->a;
     a.popsize = popsize; a.n_pops = n_pops; a.ndim = ndim; a.strategy = strategy; a.target = target; a.seed = seed;
     a.f_lo = f_lo; a.f_hi = f_hi; a.cr = cr; a.tol = tol; a.atol = atol;
     for (int d = 0; d < ndim; ++d) { a.lower[d] = lower[d]; a.upper[d] = upper[d]; }
-    DeviceScope scope(h->device);
+    DeviceScope scope(o->ev->device);
     const size_t nt = (size_t)o->n_total;
     Binder bind;
     bind(o->d_pop[0], nt * ndim, a.pop_cur); bind(o->d_pop[1], nt * ndim, a.pop_next);
@@ -73,29 +75,27 @@ mp_optimizer *mp_optimizer_create(mp_handle *h, int popsize, int n_pops, int ndi
 
 int mp_optimizer_destroy(mp_optimizer *o) {
     if (!o) return MP_OK;
-    Lock lock(o->h->mu);
-    DeviceScope scope(o->h->device);
-    (void)hipStreamSynchronize(o->h->stream);
+    Held held(o->h, o->ev);
+    (void)hipStreamSynchronize(o->ev->stream);
     delete o;
     return MP_OK;
 }
 
 int mp_optimizer_set_population(mp_optimizer *o, const double *pop) {
     if (!o || !pop) return fail(MP_EINVAL, "mp_optimizer_set_population: NULL argument");
-    mp_handle *h = o->h;
+    Evaluator *ev = o->ev;
     const size_t nt = (size_t)o->n_total, n_pops = (size_t)o->a.n_pops;
     for (size_t i = 0; i < nt * o->a.ndim; ++i)
         if (!std::isfinite(pop[i])) return fail(MP_EINVAL, "mp_optimizer_set_population: non-finite coordinate");
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
-    HIP_TRY(hipMemcpyAsync(o->a.pop_cur, pop, nt * o->a.ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(o->a.converged, 0, n_pops * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(o->a.nit, 0, n_pops * sizeof(int32_t), h->stream));
-    HIP_TRY(hipMemsetAsync(o->a.nfev, 0, n_pops * sizeof(int64_t), h->stream));
+    Held held(o->h, ev);
+    HIP_TRY(hipMemcpyAsync(o->a.pop_cur, pop, nt * o->a.ndim * sizeof(double), hipMemcpyHostToDevice, ev->stream));
+    HIP_TRY(hipMemsetAsync(o->a.converged, 0, n_pops * sizeof(int32_t), ev->stream));
+    HIP_TRY(hipMemsetAsync(o->a.nit, 0, n_pops * sizeof(int32_t), ev->stream));
+    HIP_TRY(hipMemsetAsync(o->a.nfev, 0, n_pops * sizeof(int64_t), ev->stream));
     o->gen = 0;
     int rc = opt_enqueue(o, 0);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(ev->stream));
     o->have_state = true;
     return MP_OK;
 }
@@ -103,22 +103,21 @@ int mp_optimizer_set_population(mp_optimizer *o, const double *pop) {
 int mp_optimizer_run(mp_optimizer *o, int max_generations, int *n_running) {
     if (!o || max_generations < 0) return fail(MP_EINVAL, "mp_optimizer_run: bad argument");
     if (!o->have_state) return fail(MP_ESTATE, "mp_optimizer_run: call mp_optimizer_set_population first");
-    mp_handle *h = o->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Evaluator *ev = o->ev;
+    Held held(o->h, ev);
     // Chunks of generations enqueued back to back (no allocation, no wait inside a chunk); the flags are read back behind each
     // chunk, and the run ends early once every population has converged.  A frozen population costs an empty workgroup per
     // member and launch.
     constexpr int kChunk = 16;
     int running, rc;
-    if ((rc = groups_running(h, o->a.converged, o->a.n_pops, &running))) return rc;
+    if ((rc = groups_running(ev, o->a.converged, o->a.n_pops, &running))) return rc;
     for (int done = 0; done < max_generations && running > 0;) {
         const int chunk = std::min(kChunk, max_generations - done);
         for (int g = 0; g < chunk; ++g) {
             ++o->gen;
             if ((rc = opt_enqueue(o, 1))) return rc;
         }
-        if ((rc = groups_running(h, o->a.converged, o->a.n_pops, &running))) return rc;
+        if ((rc = groups_running(ev, o->a.converged, o->a.n_pops, &running))) return rc;
         done += chunk;
     }
     if (n_running) *n_running = running;
@@ -129,11 +128,10 @@ int mp_optimizer_get_state(mp_optimizer *o, double *pop, double *lnprob, int32_t
                            int32_t *converged, int64_t *nfev) {
     if (!o) return fail(MP_EINVAL, "mp_optimizer_get_state: NULL optimizer");
     if (!o->have_state) return fail(MP_ESTATE, "mp_optimizer_get_state: call mp_optimizer_set_population first");
-    mp_handle *h = o->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Evaluator *ev = o->ev;
+    Held held(o->h, ev);
     const size_t nt = (size_t)o->n_total, np = (size_t)o->a.n_pops;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(ev->stream));
     const mp::OptArgs &a = o->a;
     return read_back(pop, a.pop_cur, nt * a.ndim, lnprob, a.lnp_cur, nt, status, a.st_cur, nt,
                      best, a.best, np, nit, a.nit, np, converged, a.converged, np, nfev, a.nfev, np);

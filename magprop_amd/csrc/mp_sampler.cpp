@@ -19,7 +19,8 @@ struct AcfMonitor {
 };
 
 struct mp_sampler {
-    mp_handle *h = nullptr;
+    mp_handle *h = nullptr;         // the lock
+    Evaluator *ev = nullptr;        // the device state: the handle's one evaluator
     int n_walkers = 0, n_ensembles = 0, n_total = 0, ndim = 0, target = 0;
     uint64_t seed = 0;
     double a = 2.0;
@@ -79,7 +80,7 @@ static mp::AcfArgs acf_args(const mp_sampler *s) {
 static int acf_restart(mp_sampler *s) {
     AcfMonitor *m = s->acf.get();
     const size_t ns = (size_t)s->n_total * s->ndim;
-    hipStream_t st = s->h->stream;
+    hipStream_t st = s->ev->stream;
     HIP_TRY(hipMemsetAsync(m->hist.p, 0, (size_t)m->ring_rows * ns * sizeof(double), st));
     HIP_TRY(hipMemsetAsync(m->S.p, 0, (size_t)m->kp * ns * sizeof(double), st));
     HIP_TRY(hipMemsetAsync(m->H.p, 0, (size_t)m->kp * ns * sizeof(double), st));
@@ -100,7 +101,7 @@ static int acf_feed(mp_sampler *s, int chunk) {
     mp::AcfArgs a = acf_args(s);
     a.first = first;
     a.rows = chunk - first;
-    const int e = mp::launch_acf_accumulate(a, s->h->stream);
+    const int e = mp::launch_acf_accumulate(a, s->ev->stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     m->head = (m->head + a.rows) % m->ring_rows;
     m->n += a.rows;
@@ -182,7 +183,7 @@ static mp::StretchArgs stretch_args(const mp_sampler *s, const int32_t *d_perm, 
         int idx[16];
         std::iota(idx, idx + s->n_ensembles, 0);
         std::stable_sort(idx, idx + s->n_ensembles, [&](int x, int y) {
-            return s->h->ds[s->ens_ds[(size_t)x]].g.size() > s->h->ds[s->ens_ds[(size_t)y]].g.size();
+            return s->ev->ds[s->ens_ds[(size_t)x]].g.size() > s->ev->ds[s->ens_ds[(size_t)y]].g.size();
         });
         bool identity = true;
         for (int e = 0; e < s->n_ensembles; ++e) identity = identity && idx[e] == e;
@@ -207,9 +208,9 @@ mp_sampler *mp_sampler_create(mp_handle *h, int n_walkers, int n_ensembles, int 
     });
     if (rc) return nullptr;
     mp_sampler *s = new mp_sampler();
-    s->h = h; s->n_walkers = n_walkers; s->n_ensembles = n_ensembles; s->n_total = n_walkers * n_ensembles;
+    s->h = h; s->ev = h->first(); s->n_walkers = n_walkers; s->n_ensembles = n_ensembles; s->n_total = n_walkers * n_ensembles;
     s->ndim = ndim; s->target = target; s->seed = seed; s->a = a;
-    DeviceScope scope(h->device);
+    DeviceScope scope(s->ev->device);
     const size_t nt = (size_t)s->n_total;
     for (int e = 0; e < n_ensembles; ++e) s->ens_ds.push_back(ens_ds_id ? ens_ds_id[e] : 0);
     constexpr size_t kBadRows = MP_BAD_WINDOW;   // device window of failed proposals between two drains (drain_bad)
@@ -229,8 +230,7 @@ mp_sampler *mp_sampler_create(mp_handle *h, int n_walkers, int n_ensembles, int 
 
 int mp_sampler_destroy(mp_sampler *s) {
     if (!s) return MP_OK;
-    Lock lock(s->h->mu);
-    DeviceScope scope(s->h->device);
+    Held held(s->h, s->ev);
     (void)hipDeviceSynchronize();
     delete s;
     return MP_OK;
@@ -250,7 +250,7 @@ int mp_sampler_set_temperatures(mp_sampler *s, int n_temps, const double *betas)
     for (int e = 0; e < s->n_ensembles; ++e)
         if (s->ens_ds[(size_t)e] != s->ens_ds[(size_t)(e - e % n_temps)])
             return fail(MP_EINVAL, "mp_sampler_set_temperatures: ensembles %d and %d of one group have different datasets", e - e % n_temps, e);
-    DeviceScope scope(s->h->device);
+    DeviceScope scope(s->ev->device);
     std::vector<double> b((size_t)s->n_ensembles);
     for (int e = 0; e < s->n_ensembles; ++e) b[(size_t)e] = betas[e % n_temps];
     const size_t n_pairs = (size_t)(s->n_ensembles / n_temps) * (size_t)(n_temps - 1);
@@ -319,7 +319,7 @@ int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted) {
     if (!s || !n_swaps_accepted) return fail(MP_EINVAL, "mp_sampler_get_swaps: NULL argument");
     Lock lock(s->h->mu);
     if (!s->n_temps) return fail(MP_ESTATE, "mp_sampler_get_swaps: the sampler is not tempered (mp_sampler_set_temperatures)");
-    DeviceScope scope(s->h->device);
+    DeviceScope scope(s->ev->device);
     HIP_TRY(hipDeviceSynchronize());
     const size_t n_pairs = (size_t)(s->n_ensembles / s->n_temps) * (size_t)(s->n_temps - 1);
     HIP_TRY(hipMemcpy(n_swaps_accepted, s->d_swaps.p, n_pairs * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -328,28 +328,27 @@ int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted) {
 
 int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
     if (!s || !pos) return fail(MP_EINVAL, "mp_sampler_set_positions: NULL argument");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Evaluator *ev = s->ev;
+    Held held(s->h, ev);
     const size_t nt = (size_t)s->n_total;
     for (size_t i = 0; i < nt * s->ndim; ++i)
         if (!std::isfinite(pos[i])) return fail(MP_EINVAL, "mp_sampler_set_positions: non-finite coordinate");
     HIP_TRY(hipDeviceSynchronize());   // the sharded entry points may have work in flight on a caller's stream
     s->ext_stream_work = false;
-    HIP_TRY(hipMemcpyAsync(s->d_pos.p, pos, nt * s->ndim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_pos.p, pos, nt * s->ndim * sizeof(double), hipMemcpyHostToDevice, ev->stream));
     if (s->target == 1) {
         std::vector<double> lp(nt, 0.0);
         for (size_t k = 0; k < nt; ++k)
             for (int i = 0; i < s->ndim; ++i) lp[k] -= 0.5 * pos[k * s->ndim + i] * pos[k * s->ndim + i];
-        HIP_TRY(hipMemcpyAsync(s->d_lnprob.p, lp.data(), nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpyAsync(s->d_lnprob.p, lp.data(), nt * sizeof(double), hipMemcpyHostToDevice, ev->stream));
+        HIP_TRY(hipStreamSynchronize(ev->stream));
     } else {
         mp::LaunchArgs a{};
         a.pars = s->d_pos.p; a.ds_id = s->d_dsid.p; a.n = s->n_total; a.ndim = s->ndim; a.want_chi2 = 1;
         a.lnprob = s->d_lnprob.p; a.status = s->d_status.p;
-        const int rc = launch_lnprob_ordered(h, a, h->stream);
+        const int rc = launch_lnprob_ordered(ev, a, ev->stream);
         if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipStreamSynchronize(ev->stream));
     }
     s->have_state = true;
     if (s->acf) return acf_restart(s);   // the series is broken
@@ -360,7 +359,7 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
 // chain is set, move mv (nullptr: the stretch move of mp_sampler_create).  A whole step per launch (stretch_step_kernel and the
 // commit kernel) where `whole` and the move is the stretch move, else two half-step launches; then the swap sweep when tempered.
 static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_sampler::Move *mv, bool chain, bool whole) {
-    mp_handle *h = s->h;
+    Evaluator *ev = s->ev;
     mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done + (uint64_t)row, 0);
     g.chain = chain ? s->d_chain.p : nullptr;
     g.chain_lnp = chain ? s->d_chain_lnp.p : nullptr;
@@ -375,14 +374,14 @@ static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_
     int e;
     if (whole && g.move == MP_MOVE_STRETCH) {
         g.spec = s->d_spec.p;
-        e = mp::launch_stretch_step(h->sh, g, 3 * g.n_half * g.n_ensembles, h->stream);
-        if (!e) e = mp::launch_stretch_step_commit(g, h->stream);
+        e = mp::launch_stretch_step(ev->sh, g, 3 * g.n_half * g.n_ensembles, ev->stream);
+        if (!e) e = mp::launch_stretch_step_commit(g, ev->stream);
     } else {
-        e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
+        e = mp::launch_stretch(ev->sh, g, g.n_half * g.n_ensembles, ev->stream);
         g.half = 1;
-        if (!e) e = mp::launch_stretch(h->sh, g, g.n_half * g.n_ensembles, h->stream);
+        if (!e) e = mp::launch_stretch(ev->sh, g, g.n_half * g.n_ensembles, ev->stream);
     }
-    if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, h->stream);
+    if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, ev->stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return MP_OK;
 }
@@ -391,9 +390,8 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
     if (!s || n_steps < 0) return fail(MP_EINVAL, "mp_sampler_run: bad argument");
     if (!s->have_state) return fail(MP_ESTATE, "mp_sampler_run: call mp_sampler_set_positions first");
     if ((chain == nullptr) != (chain_lnprob == nullptr)) return fail(MP_EINVAL, "mp_sampler_run: chain and chain_lnprob go together");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Evaluator *ev = s->ev;
+    Held held(s->h, ev);
     const size_t nt = (size_t)s->n_total, row = nt * s->ndim;
     // chunks of steps so that the device-resident chain slab stays below ~256 MB, the splits below ~64 MB, and the
     // window of failed proposals (drained after every chunk) overflows only if more than 1 in 32 proposals fails
@@ -407,7 +405,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
     // that beats two half-step launches (mp_device.h stretch_whole_step_fits); larger ensembles fill the device with one half-step
     // at a time.
     const int n_slots = (s->n_walkers / 2) * s->n_ensembles;
-    const bool whole = s->whole_step && mp::stretch_whole_step_fits(h->sh, 3 * (long long)n_slots);
+    const bool whole = s->whole_step && mp::stretch_whole_step_fits(ev->sh, 3 * (long long)n_slots);
     if (whole && (rc = s->d_spec.ensure((size_t)3 * n_slots * (size_t)(s->ndim + mp::kSpecExtra)))) return rc;
     if (s->ext_stream_work) {   // sharded half-steps on a caller's stream may still be updating the state
         HIP_TRY(hipDeviceSynchronize());
@@ -426,7 +424,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
             int step_move[kSub];   // with a move table: the move of every step of the batch, drawn next to its splits
             for (int st = sub; st < sub_end; ++st) step_move[st - sub] = draw_move(s, s->steps_done + (uint64_t)st);
             HIP_TRY(hipMemcpyAsync(s->d_perm.p + (size_t)sub * nt, perm + (size_t)sub * nt,
-                                   (size_t)(sub_end - sub) * nt * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+                                   (size_t)(sub_end - sub) * nt * sizeof(int32_t), hipMemcpyHostToDevice, ev->stream));
             for (int st = sub; st < sub_end; ++st) {
                 const mp_sampler::Move *mv = s->moves.empty() ? nullptr : &s->moves[(size_t)step_move[st - sub]];
                 if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, slab, whole))) return rc;
@@ -434,10 +432,10 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
         }
         if (monitor && (rc = acf_feed(s, chunk))) return rc;
         if (chain) {
-            HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
+            HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
         }
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipStreamSynchronize(ev->stream));
         if ((rc = drain_bad(s))) return rc;
         s->steps_done += (uint64_t)chunk;
         done += chunk;
@@ -450,9 +448,7 @@ int mp_sampler_set_autocorr(mp_sampler *s, int max_lag, int64_t discard) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_set_autocorr: NULL sampler");
     if (max_lag < 0 || max_lag > MP_ACF_MAX_LAG) return fail(MP_EINVAL, "mp_sampler_set_autocorr: max_lag must be in [0, %d] (MP_ACF_MAX_LAG; 0 turns the monitor off), got %d", MP_ACF_MAX_LAG, max_lag);
     if (discard < 0) return fail(MP_EINVAL, "mp_sampler_set_autocorr: discard must be >= 0, got %lld", (long long)discard);
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Held held(s->h, s->ev);
     HIP_TRY(hipDeviceSynchronize());
     s->acf.reset();
     if (max_lag == 0) return MP_OK;
@@ -484,17 +480,16 @@ static int acf_finalise(mp_sampler *s, const char *fn, double c) {
     if (s->acf->n < 2) return fail(MP_ESTATE, "%s: the monitor holds %lld samples, an estimate needs 2 or more", fn, (long long)s->acf->n);
     mp::AcfArgs a = acf_args(s);
     a.c = c;
-    const int e = mp::launch_acf_finalise(a, s->h->stream);
+    const int e = mp::launch_acf_finalise(a, s->ev->stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipStreamSynchronize(s->h->stream));
+    HIP_TRY(hipStreamSynchronize(s->ev->stream));
     return MP_OK;
 }
 
 int mp_sampler_get_autocorr(mp_sampler *s, double c, double *tau, int32_t *window, int64_t *n_samples) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_autocorr: NULL sampler");
     if (!(c > 0.0) || !std::isfinite(c)) return fail(MP_EINVAL, "mp_sampler_get_autocorr: c must be finite and > 0, got %g", c);
-    Lock lock(s->h->mu);
-    DeviceScope scope(s->h->device);
+    Held held(s->h, s->ev);
     if (n_samples) *n_samples = s->acf ? s->acf->n : 0;
     int rc = acf_finalise(s, "mp_sampler_get_autocorr", c);
     if (rc) return rc;
@@ -505,8 +500,7 @@ int mp_sampler_get_autocorr(mp_sampler *s, double c, double *tau, int32_t *windo
 int mp_sampler_get_acf(mp_sampler *s, int ensemble, int max_rows, double *acf) {
     if (!s || !acf || max_rows < 0) return fail(MP_EINVAL, "mp_sampler_get_acf: bad argument");
     if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "mp_sampler_get_acf: ensemble must be in [0, %d), got %d", s->n_ensembles, ensemble);
-    Lock lock(s->h->mu);
-    DeviceScope scope(s->h->device);
+    Held held(s->h, s->ev);
     int rc = acf_finalise(s, "mp_sampler_get_acf", 5.0);
     if (rc) return rc;
     const AcfMonitor *m = s->acf.get();
@@ -522,11 +516,10 @@ int mp_sampler_get_autocorr_sums(mp_sampler *s, int ensemble, double *S, double 
                                  int64_t *n_samples) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_autocorr_sums: NULL sampler");
     if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "mp_sampler_get_autocorr_sums: ensemble must be in [0, %d), got %d", s->n_ensembles, ensemble);
-    Lock lock(s->h->mu);
-    DeviceScope scope(s->h->device);
+    Held held(s->h, s->ev);
     if (!s->acf) return fail(MP_ESTATE, "mp_sampler_get_autocorr_sums: the autocorrelation monitor is off (mp_sampler_set_autocorr)");
     const AcfMonitor *m = s->acf.get();
-    HIP_TRY(hipStreamSynchronize(s->h->stream));
+    HIP_TRY(hipStreamSynchronize(s->ev->stream));
     const size_t ns = (size_t)s->n_total * s->ndim, w = (size_t)s->n_walkers * s->ndim, off = (size_t)ensemble * w;
     const size_t K = (size_t)m->max_lag;
     // rows [r0, r0 + rows) of a [.][n_series] device array, the ensemble's columns -> dst[rows][n_walkers][ndim]
@@ -591,11 +584,10 @@ int mp_sampler_n_slots(const mp_sampler *s) { return s ? (s->n_walkers / 2) * s-
 // a tempered one and one with a move table are refused (those run through mp_sampler_run only); otherwise the handle's lock and
 // device are held for the call, d_perm is the split of the current step and the sampler notes work on a caller's stream.
 struct ShardCall {
-    Lock lock;
-    DeviceScope scope;
+    Held held;
     const int32_t *d_perm = nullptr;
     int rc = MP_OK;
-    ShardCall(mp_sampler *s, const char *fn, void *stream) : lock(s->h->mu), scope(s->h->device) {
+    ShardCall(mp_sampler *s, const char *fn, void *stream) : held(s->h, s->ev) {
         if (!s->have_state) rc = fail(MP_ESTATE, "%s: call mp_sampler_set_positions first", fn);
         else if (s->n_temps) rc = fail(MP_ESTATE, "%s: a tempered sampler runs on one device only (mp_sampler_run)", fn);
         else if (!s->moves.empty())
@@ -617,7 +609,7 @@ int mp_sampler_halfstep_shard(mp_sampler *s, int half, int slot_lo, int slot_hi,
     mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, half);
     g.upd = d_rows;
     g.slot_lo = slot_lo;
-    const int e = mp::launch_stretch(s->h->sh, g, slot_hi - slot_lo, stream);
+    const int e = mp::launch_stretch(s->ev->sh, g, slot_hi - slot_lo, stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return MP_OK;
 }
@@ -655,7 +647,7 @@ int mp_sampler_step_shard(mp_sampler *s, int block_lo, int block_hi, double *d_r
     mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, 0);
     g.spec = d_rows;
     g.slot_lo = block_lo;
-    const int e = mp::launch_stretch_step(s->h->sh, g, block_hi - block_lo, stream);
+    const int e = mp::launch_stretch_step(s->ev->sh, g, block_hi - block_lo, stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return MP_OK;
 }
@@ -685,9 +677,7 @@ int mp_sampler_state_ptrs(mp_sampler *s, double **d_pos, double **d_lnprob) {
 
 int mp_sampler_get_bad(mp_sampler *s, int64_t first_row, double *pars, int max_rows, int64_t *n_bad, int64_t *n_logged) {
     if (!s || max_rows < 0 || first_row < 0 || (max_rows > 0 && !pars)) return fail(MP_EINVAL, "mp_sampler_get_bad: bad argument");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Held held(s->h, s->ev);
     HIP_TRY(hipDeviceSynchronize());
     const int rc = drain_bad(s);
     if (rc) return rc;
@@ -701,9 +691,7 @@ int mp_sampler_get_bad(mp_sampler *s, int64_t first_row, double *pars, int max_r
 
 int mp_sampler_get_state(mp_sampler *s, double *pos, double *lnprob, int64_t *n_accepted, int64_t *steps_done) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_state: NULL sampler");
-    mp_handle *h = s->h;
-    Lock lock(h->mu);
-    DeviceScope scope(h->device);
+    Held held(s->h, s->ev);
     const size_t nt = (size_t)s->n_total;
     HIP_TRY(hipDeviceSynchronize());
     const int rc = read_back(pos, s->d_pos.p, nt * s->ndim, lnprob, s->d_lnprob.p, nt, n_accepted, s->d_acc.p, nt);

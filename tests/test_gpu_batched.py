@@ -509,3 +509,60 @@ def test_multi_device_handle_deals_a_batch_out_inside_the_library(gsynth):
         two.lnprob_device(d)
     # the model light curve of one walker: the first device
     assert np.array_equal(two.handle.model_lc(np.array([1.0, 5.0, 1e-3, 100.0, 0.1, 1.0]))[1], one.handle.model_lc(np.array([1.0, 5.0, 1e-3, 100.0, 0.1, 1.0]))[1])
+
+
+def test_multi_device_handle_small_batches_diagnostics_and_error_path(gsynth, gflag):
+    """What the one dealing path of mp_lnprob_batch carries beside the values, on handles over one, two and three evaluators
+    (the same device listed again): a prior set after creation reaches every evaluator (a row that only the later, narrower
+    prior excludes sits in the LAST block), a flagging row, sweeps and tiles per walker, the tile log of a walker of every
+    block (7 rows over 3 evaluators: blocks of 3, 3, 1), the two means, and a refused batch that leaves the handle as it
+    was.  Every block and the whole batch have at most 256 rows, so all run the same build of the team kernel: results
+    equal the single-device handle's bit for bit.  The means are one division of sums of small integers: exact."""
+    from magprop_amd import LogProb, _capi
+    sets = [(gsynth[t + "_x"], gsynth[t + "_y"], gsynth[t + "_yerr"]) for t in TYPES]
+    handles = [LogProb(*sets[0]), LogProb(*sets[0], device=[0, 0]), LogProb(*sets[0], device=[0, 0, 0])]
+    lo, hi = gsynth["prior_lower"].copy(), gsynth["prior_upper"].copy()
+    hi[0] = 8.0                                                                     # (the default box ends at 10)
+    for lp_ in handles:
+        for s_ in sets[1:]:
+            lp_.add_dataset(*s_)
+        lp_.handle.set_prior(lo, hi, LOG_MASK)
+        lp_.handle.tile_log(True)
+    flag = gflag["pars"][gflag["status"] == 1][0]
+    assert np.all(flag >= lo) and np.all(flag <= hi)
+    rng = np.random.default_rng(12)
+    for n in (7, 130):
+        P = lo + (hi - lo) * rng.random((n, 6))
+        P[: n // 2] = np.array(TRUTHS["Humped"]) + 1.0e-3 * rng.standard_normal((n // 2, 6))
+        ids = rng.integers(0, 4, n).astype(np.int32)
+        P[1], ids[1] = flag, 0
+        P[n - 1] = TRUTHS["Humped"]
+        P[n - 1, 0] = 9.0                                                           # inside the default prior, outside the one set later
+        bad_ids = ids.copy()
+        bad_ids[n - 1] = 9                                                          # a slot that was never set, in the last block
+        ref = None
+        for lp_ in handles:
+            H, G = lp_.handle, lp_.handle.n_devices
+            with pytest.raises(ValueError, match="refers to unset dataset"):
+                H.lnprob_batch(P, ds_id=bad_ids, want_status=True)
+            out, st = H.lnprob_batch(P, ds_id=ids, want_status=True)                # the next valid batch on the same handle
+            sweeps, tiles = H.last_sweeps(n), H.last_tiles(n)
+            per = -(-n // G)
+            walkers = sorted({0, n - 1} | {k * per - 1 for k in range(1, G)} | {k * per for k in range(1, G) if k * per < n})
+            if n == 7:
+                walkers = list(range(n))
+            logs = [H.last_tile_log(w) for w in walkers]
+            ok = st == 0
+            assert len(sweeps) == n and len(tiles) == n and ok.sum() > 0
+            assert H.last_mean_tiles == tiles[ok].sum() / ok.sum()
+            assert H.last_mean_sweeps == sweeps[ok].sum() / tiles[ok].sum()
+            assert H.last_tile_log(n) == []                                         # past the batch
+            if ref is None:
+                ref = (out, st, sweeps, tiles)
+                ref_log = {w: H.last_tile_log(w) for w in range(n)}
+                assert st[1] == _capi.STATUS_FLAG and st[n - 1] == _capi.STATUS_PRIOR and out[n - 1] == -np.inf
+                assert all(len(ref_log[w]) > 0 for w in range(n) if ok[w])
+                continue
+            for got, want in zip((out, st, sweeps, tiles), ref):
+                assert np.array_equal(got, want)
+            assert logs == [ref_log[w] for w in walkers]

@@ -1,6 +1,6 @@
 """Wall time per call of the host-buffer entries (numpy in, numpy out: PCIe both ways + synchronisation), the path
 `emcee.EnsembleSampler(..., vectorize=True)` drives, next to the kernel time of the same rows (device-pointer entry).
-    python tools/host_entry_time.py [--reps 200]"""
+    python tools/host_entry_time.py [--reps 200] [--rows 512,1024]"""
 import argparse
 import os
 import sys
@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--rows", default="24,256,512,1024,4096", help="batch sizes, comma-separated")
     a = ap.parse_args()
     import pandas as pd
     import torch
@@ -33,7 +34,7 @@ def main():
             f()
         return (time.perf_counter() - t0) / a.reps * 1e3
 
-    for n in (24, 256, 512, 1024, 4096):
+    for n in (int(v) for v in a.rows.split(",")):
         P = np.array([1.0, 5.0, -3.0, 2.0, -1.0, 0.0]) + 1.0e-4 * rng.standard_normal((n, 6))
         dP = torch.from_numpy(P).cuda()
         out = torch.empty(n, dtype=torch.float64, device="cuda")
