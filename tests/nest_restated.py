@@ -103,6 +103,28 @@ def walk(s, r, slot, t, surv, lstar, seed, walks, g0, s3, lower, upper, evaluate
     return x, lnl, st, n_acc, n_eval
 
 
+def select(lnl, lnx, lnz, nbatch, dlogz):
+    """The select step of one run on the live lnL `lnl` (a NaN ranks, and is listed, as -inf): None where the stop rule fires on
+    the live set as it stands, else (dead slots in ascending (lnL, slot), survivors in slot order, L*, the dead lnL, the live
+    counts n_k of the dead, the new ln X, the new ln Z)."""
+    key = [_clean(v) for v in lnl]
+    n = len(key)
+    o = order(key)
+    if stops(key[o[-1]], lnx, lnz, dlogz):
+        return None
+    dead, surv = o[:nbatch], sorted(o[nbatch:])
+    lnx, lnz = float(lnx), float(lnz)
+    dead_lnl, dead_n = [], []
+    for k, j in enumerate(dead):
+        dead_lnl.append(key[j])
+        dead_n.append(n - k)
+        inv = 1.0 / float(n - k)
+        lnw = (key[j] + lnx) + math.log(-math.expm1(-inv))
+        lnx = lnx - inv
+        lnz = logaddexp(lnz, lnw)
+    return dead, surv, key[dead[-1]], dead_lnl, dead_n, lnx, lnz
+
+
 def iteration(s, nbatch, seed, walks, g0, sigma, dlogz, lower, upper, evaluate_one):
     """One iteration of every run not stopped (the stop rule first, on the live set as it stands)."""
     n_runs, n, ndim = s.live.shape
@@ -110,22 +132,14 @@ def iteration(s, nbatch, seed, walks, g0, sigma, dlogz, lower, upper, evaluate_o
     for r in range(n_runs):
         if s.stopped[r]:
             continue
-        o = order(s.lnl[r])
-        if stops(s.lnl[r, o[-1]], s.lnx[r], s.lnz[r], dlogz):
+        sel = select(s.lnl[r], s.lnx[r], s.lnz[r], nbatch, dlogz)
+        if sel is None:
             s.stopped[r] = 1
             continue
-        dead, surv = o[:nbatch], sorted(o[nbatch:])
-        lnx, lnz = float(s.lnx[r]), float(s.lnz[r])
-        for k, j in enumerate(dead):
-            s.dead_pars[r].append(s.live[r, j].copy())
-            s.dead_lnl[r].append(float(s.lnl[r, j]))
-            s.dead_n[r].append(n - k)
-            inv = 1.0 / float(n - k)
-            lnw = (float(s.lnl[r, j]) + lnx) + math.log(-math.expm1(-inv))
-            lnx = lnx - inv
-            lnz = logaddexp(lnz, lnw)
-        s.lnx[r], s.lnz[r] = lnx, lnz
-        lstar = float(s.lnl[r, dead[-1]])
+        dead, surv, lstar, dead_lnl, dead_n, s.lnx[r], s.lnz[r] = sel
+        s.dead_pars[r].extend(s.live[r, j].copy() for j in dead)
+        s.dead_lnl[r].extend(dead_lnl)
+        s.dead_n[r].extend(dead_n)
         t = int(s.nit[r])
         out = [walk(s, r, j, t, surv, lstar, seed, walks, g0, s3, lower, upper, evaluate_one) for j in dead]
         for j, (x, lq, sq, na, ne) in zip(dead, out):
