@@ -11,10 +11,9 @@
 // Nothing is launched then.
 #include <hip/hip_runtime.h>
 
-#include <vector>
-
 #include "mp_band.h"
 #include "mp_device.h"
+#include "mp_probe_bufs.h"
 
 namespace mp {
 
@@ -24,45 +23,6 @@ constexpr int kMaxGrid = 1 << 16;     // grid points of a band call (the probe's
 constexpr int kMaxRuns = 64;          // runs / populations of a call (the probe's own cap)
 constexpr int kMaxChunk = 64;         // chunk slots of the dead rows (the probe's own cap)
 constexpr int kOptMinPop = 5, kOptMaxPop = 1024;   // mp_optimizer_create (include/magprop_amd.h)
-
-// the device copies of one call: every buffer uploaded at construction, the writable ones downloaded by finish()
-struct Bufs {
-    struct Out { void *host, *dev; size_t bytes; };
-    std::vector<void *> all;
-    std::vector<Out> outs;
-    hipError_t err = hipSuccess;
-
-    template <class T>
-    const T *in(const T *host, size_t count) {
-        return static_cast<const T *>(put(host, count * sizeof(T)));
-    }
-    template <class T>
-    T *io(T *host, size_t count) {
-        void *d = put(host, count * sizeof(T));
-        if (d) outs.push_back({host, d, count * sizeof(T)});
-        return static_cast<T *>(d);
-    }
-    void *put(const void *host, size_t bytes) {
-        if (err != hipSuccess) return nullptr;
-        void *d = nullptr;
-        err = hipMalloc(&d, bytes ? bytes : 1);
-        if (err != hipSuccess) return nullptr;
-        all.push_back(d);
-        if (bytes) err = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
-        return err == hipSuccess ? d : nullptr;
-    }
-    bool ready() const { return err == hipSuccess; }
-    int finish(int launch_rc) {   // after the launch
-        if (err == hipSuccess) err = (hipError_t)launch_rc;
-        if (err == hipSuccess) err = hipDeviceSynchronize();
-        for (const Out &o : outs)
-            if (err == hipSuccess && o.bytes) err = hipMemcpy(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost);
-        return (int)err;
-    }
-    ~Bufs() {
-        for (void *d : all) (void)hipFree(d);
-    }
-};
 
 bool band_sizes_ok(int n, int n_grid) { return n >= 1 && n <= MP_BAND_MAX_SAMPLES && n_grid >= 1 && n_grid <= kMaxGrid; }
 

@@ -46,8 +46,9 @@ class Monitor:
         H[min(self.n, self.K - 1) + 1:] = self.T
         return {"S": self.S.copy(), "T": self.T.copy(), "H": H, "tail": self.tail, "pivot": self.pivot.copy(), "n": self.n}
 
-    def finalise(self, c=5.0):
-        """(tau[ndim], window[ndim], f[lim, ndim]) over the walkers (axis 0 of a sample) of the ensemble."""
+    def finalise(self, c=5.0, with_rho=False):
+        """(tau[ndim], window[ndim], f[lim, ndim]) over the walkers (axis 0 of a sample) of the ensemble; with_rho: also
+        rho[lim, nwalkers, ndim] of every series."""
         K, n = self.K, self.n
         lim = min(K, n)
         tail = self.tail
@@ -75,7 +76,7 @@ class Monitor:
                 window[d], tau[d] = lim - 1, taus[lim - 1, d]
             else:
                 window[d], tau[d] = -1, np.nan
-        return tau, window, f
+        return (tau, window, f, rho) if with_rho else (tau, window, f)
 
 
 def sums_oneshot(x, max_lag):
