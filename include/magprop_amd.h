@@ -444,6 +444,61 @@ int mp_sampler_get_autocorr_sums(mp_sampler *s, int ensemble, double *S, double 
                                  int64_t *n_samples);
 
 /*
+ * Posterior monitor (ABI 5, additive): histograms, moments and the best sample of the chain, accumulated on the device while
+ * mp_sampler_run runs, so that credible intervals, the marginals of a corner plot and the best fit need no chain on the host.
+ * Off by default; while it is off nothing about the sampler changes.  Everything below is a function of the set or sequence
+ * of samples alone: it does not depend on how mp_sampler_run chunks its steps or on how a run was split into calls, and a numpy
+ * restatement (tests/post_restated.py) reproduces every number bit for bit.
+ * A sample is the position x[0 .. ndim) (sampler coordinates) and the stored, untempered lnprob of one walker w of one ensemble
+ * e at one step.  Only steps from `discard` steps after the monitor was (re)started count; t counts them from 0, n of them so
+ * far.  Sample index inside an ensemble: i = t * n_walkers + w.  Every ensemble is monitored on its own; the temperatures of a
+ * tempered sampler are ensembles like any other.
+ * Settings: bins1 (1 .. MP_POST_MAX_BINS), bins2 (0 .. MP_POST_MAX_BINS2; 0: no 2-D histograms), lower[ndim] < upper[ndim],
+ * all finite with a finite width.  The host forms once, in double, per dimension d
+ *     inv1_d = bins1 / (upper_d - lower_d),   inv2_d = bins2 / (upper_d - lower_d),   pivot_d = lower_d + 0.5 (upper_d - lower_d).
+ * Bin rule, for a coordinate value v, a bin count B and its inverse width inv: NaN or +-inf is "non-finite"; v < lower is
+ * "below"; v >= upper is "above"; otherwise b = (int)floor((v - lower) * inv), and b = B - 1 where that gives B (the difference
+ * and the product are each rounded on their own; with lower = -5, upper = 5, B = 256 the largest double below 5 gives 256.0).
+ * 1-D: per dimension hist1[d][bins1], below[d], above[d], nonfinite[d], int64 counts; every sample lands in exactly one of them
+ * per dimension.
+ * 2-D (bins2 > 0): one histogram per pair a < b in lexicographic order (0,1), (0,2), ..., npairs = ndim (ndim - 1) / 2 of them;
+ * hist2[p][ba][bb] under the bin rule with bins2; a sample with either coordinate not in a bin counts in outside2[p] instead.
+ * Moments: over the samples whose coordinates are all finite (n_finite of them), with y = x - pivot, per walker and in
+ * increasing t from 0.0:  s1[w][d] = sum y_d,  s2[w][a][b] = sum (y_a * y_b) for a <= b, the product rounded before the sum, no
+ * FMA.  Per ensemble the walkers are summed in walker order from 0.0.  The ABI returns those totals, the pivot and n_finite;
+ * mean and covariance are formed above the ABI (magprop_amd.posterior.mean_cov).
+ * Best sample: the largest lnprob over the monitored samples, its position and its sample index.  A sample replaces the holder
+ * iff its lnprob is greater, or equal with a lower index; the holder starts at "none" (index -1, lnprob -inf, position NaN).
+ * So -inf and NaN never win, and ties go to the first occurrence.
+ *
+ * mp_sampler_set_posterior(s, bins1, bins2, lower, upper, discard): bins1 = 0 turns the monitor off and frees it (the other
+ * arguments are ignored); otherwise it (re)starts empty, accumulation beginning `discard` (>= 0) steps from now.  MP_EINVAL:
+ * bins1 or bins2 out of range, NULL, non-finite or empty ranges, discard < 0, more than 65 535 ensembles, or accumulators of
+ *     8 (n_ensembles (ndim (bins1 + 3) + npairs (bins2^2 + 1) + ndim + 2) + n_total (ndim + ndim (ndim + 1) / 2 + 1)) bytes
+ * beyond MP_POST_MAX_BYTES; the monitor is then off.
+ * While the monitor is on, the rules of the autocorrelation monitor hold: mp_sampler_run writes its chain rows and their lnprob
+ * to the device slab also when `chain` is NULL and feeds the monitor once per chunk, on the handle's stream, behind the chunk's
+ * last step (chunks of at most 64 MB of chain rows; next to the autocorrelation monitor, the smaller of the two caps);
+ * mp_sampler_set_positions restarts it (`discard` applies again); the walker-sharded entry points (mp_sampler_halfstep_*,
+ * mp_sampler_step_*) do not feed it and return MP_ESTATE.  It runs with tempering, move tables, whole-step and half-step launches.
+ * Read-outs (one ensemble each; any output pointer may be NULL; MP_ESTATE without a monitor, MP_EINVAL on a bad ensemble; with
+ * no sample yet they succeed with zeros and best = none):
+ * mp_sampler_get_posterior_hist1: hist1[ndim][bins1], below, above, nonfinite[ndim], *n_samples = n * n_walkers.
+ * mp_sampler_get_posterior_hist2: hist2[npairs][bins2][bins2], outside2[npairs]; MP_ESTATE when bins2 = 0.
+ * mp_sampler_get_posterior_moments: sum1[ndim], sum2[ndim][ndim] (both triangles filled), pivot[ndim], *n_finite.
+ * mp_sampler_get_posterior_best: x[ndim], *lnprob, *index.
+ */
+#define MP_POST_MAX_BINS 4096
+#define MP_POST_MAX_BINS2 128
+#define MP_POST_MAX_BYTES 1073741824   /* 1 GiB */
+int mp_sampler_set_posterior(mp_sampler *s, int bins1, int bins2, const double *lower, const double *upper, int64_t discard);
+int mp_sampler_get_posterior_hist1(mp_sampler *s, int ensemble, int64_t *hist1, int64_t *below, int64_t *above,
+                                   int64_t *nonfinite, int64_t *n_samples);
+int mp_sampler_get_posterior_hist2(mp_sampler *s, int ensemble, int64_t *hist2, int64_t *outside2);
+int mp_sampler_get_posterior_moments(mp_sampler *s, int ensemble, double *sum1, double *sum2, double *pivot, int64_t *n_finite);
+int mp_sampler_get_posterior_best(mp_sampler *s, int ensemble, double *x, double *lnprob, int64_t *index);
+
+/*
  * Differential-evolution optimizer (ABI 5, additive): scipy.optimize.differential_evolution with deferred updating, without
  * the polish step, every generation one launch that builds, evaluates and judges every trial (plus one small reduction).
  * n_pops populations of popsize members each (5 <= popsize <= 1024, 1 <= n_pops <= MP_MAX_DATASETS); population p runs on

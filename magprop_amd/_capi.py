@@ -25,6 +25,7 @@ DE_BEST1BIN, DE_RAND1BIN = 0, 1                               # include/magprop_
 NEST_MIN_LIVE, NEST_MAX_LIVE, NEST_MAX_WALKS = 16, 4096, 4096  # include/magprop_amd.h MP_NEST_*
 NEST_MAX_SLICES, NEST_MAX_STEPS_OUT, NEST_MAX_SHRINK = 4096, 4096, 254
 ACF_MAX_LAG, ACF_MAX_BYTES = 4096, 8 << 30                    # include/magprop_amd.h MP_ACF_*
+POST_MAX_BINS, POST_MAX_BINS2, POST_MAX_BYTES = 4096, 128, 1 << 30   # include/magprop_amd.h MP_POST_*
 
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -90,6 +91,11 @@ SIGNATURES = {
     "mp_sampler_get_autocorr": (_i, [_vp, _d, _dp, _ip, _i64p]),
     "mp_sampler_get_acf": (_i, [_vp, _i, _i, _dp]),
     "mp_sampler_get_autocorr_sums": (_i, [_vp, _i, _dp, _dp, _dp, _dp, _dp, _i64p]),
+    "mp_sampler_set_posterior": (_i, [_vp, _i, _i, _dp, _dp, _i64]),
+    "mp_sampler_get_posterior_hist1": (_i, [_vp, _i, _i64p, _i64p, _i64p, _i64p, _i64p]),
+    "mp_sampler_get_posterior_hist2": (_i, [_vp, _i, _i64p, _i64p]),
+    "mp_sampler_get_posterior_moments": (_i, [_vp, _i, _dp, _dp, _dp, _i64p]),
+    "mp_sampler_get_posterior_best": (_i, [_vp, _i, _dp, _dp, _i64p]),
     "mp_optimizer_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _i, _d, _d, _d, _d, _d, _dp, _dp, _i]),
     "mp_optimizer_set_population": (_i, [_vp, _dp]),
     "mp_optimizer_run": (_i, [_vp, _i, _ip]),

@@ -5,6 +5,7 @@
 
 #include "mp_acf.h"
 #include "mp_host.h"
+#include "mp_post.h"
 
 // The autocorrelation monitor (mp_sampler_set_autocorr): accumulators and the history ring of mp_acf.h, fed once per chunk of
 // mp_sampler_run from the device slab of chain rows.
@@ -16,6 +17,18 @@ struct AcfMonitor {
     int64_t discard = 0, skip = 0;  // steps to pass over after a (re)start; how many of them are left
     DevBuf<double> hist, S, T, H, pivot, rho, f, tau;
     DevBuf<int32_t> window;
+};
+
+// The posterior monitor (mp_sampler_set_posterior): the counters, running sums and best-sample holders of mp_post.h, fed once
+// per chunk of mp_sampler_run from the device slab of chain rows and their lnprob.
+struct PostMonitor {
+    int bins1 = 0, bins2 = 0;
+    int chunk_cap = 0;              // most steps per chunk of mp_sampler_run while the monitor is on
+    int64_t n = 0;                  // steps accumulated
+    int64_t discard = 0, skip = 0;  // steps to pass over after a (re)start; how many of them are left
+    std::vector<double> par;        // [5][ndim] lower, upper, inv1, inv2, pivot (mp::post_params)
+    DevBuf<double> d_par, mom, best_x, best_lnp;
+    DevBuf<int64_t> hist1, hist2, outside2, nfin, best_idx;
 };
 
 struct mp_sampler {
@@ -55,6 +68,7 @@ struct mp_sampler {
     std::vector<Move> moves;
     std::vector<double> move_cum;   // cumulative weights, summed in order
     std::unique_ptr<AcfMonitor> acf;   // the autocorrelation monitor; null: off
+    std::unique_ptr<PostMonitor> post; // the posterior monitor; null: off
 };
 
 // Steps per chunk of mp_sampler_run when chain rows go to the device slab: the slab stays below ~256 MB
@@ -104,6 +118,51 @@ static int acf_feed(mp_sampler *s, int chunk) {
     const int e = mp::launch_acf_accumulate(a, s->ev->stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     m->head = (m->head + a.rows) % m->ring_rows;
+    m->n += a.rows;
+    return MP_OK;
+}
+
+static mp::PostArgs post_args(const mp_sampler *s) {
+    const PostMonitor *m = s->post.get();
+    mp::PostArgs a{};
+    a.chain = s->d_chain.p; a.lnp = s->d_chain_lnp.p; a.par = m->d_par.p;
+    a.hist1 = m->hist1.p; a.hist2 = m->hist2.p; a.outside2 = m->outside2.p; a.mom = m->mom.p; a.nfin = m->nfin.p;
+    a.best_x = m->best_x.p; a.best_lnp = m->best_lnp.p; a.best_idx = m->best_idx.p;
+    a.n_walkers = s->n_walkers; a.n_ensembles = s->n_ensembles; a.n_total = s->n_total; a.ndim = s->ndim;
+    a.bins1 = m->bins1; a.bins2 = m->bins2; a.n0 = m->n;
+    return a;
+}
+
+// Empty the monitor (stream-ordered on the handle's stream): no sample, best = none, `discard` steps from now.
+static int post_restart(mp_sampler *s) {
+    PostMonitor *m = s->post.get();
+    const size_t ne = (size_t)s->n_ensembles, nt = (size_t)s->n_total, nd = (size_t)s->ndim, np = (size_t)mp::post_n_pairs(s->ndim);
+    hipStream_t st = s->ev->stream;
+    HIP_TRY(hipMemsetAsync(m->hist1.p, 0, ne * nd * mp::post_stride1(m->bins1) * sizeof(int64_t), st));
+    if (m->bins2 && np) {
+        HIP_TRY(hipMemsetAsync(m->hist2.p, 0, ne * np * (size_t)m->bins2 * m->bins2 * sizeof(int64_t), st));
+        HIP_TRY(hipMemsetAsync(m->outside2.p, 0, ne * np * sizeof(int64_t), st));
+    }
+    HIP_TRY(hipMemsetAsync(m->mom.p, 0, (size_t)mp::post_n_entries(s->ndim) * nt * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(m->nfin.p, 0, nt * sizeof(int64_t), st));
+    const int e = mp::launch_post_reset(post_args(s), st);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    m->n = 0;
+    m->skip = m->discard;
+    return MP_OK;
+}
+
+// The chunk's `chunk` rows of the device slab into the monitor, behind the chunk's last step on the handle's stream.
+static int post_feed(mp_sampler *s, int chunk) {
+    PostMonitor *m = s->post.get();
+    const int first = (int)std::min<int64_t>(m->skip, chunk);
+    m->skip -= first;
+    if (first == chunk) return MP_OK;
+    mp::PostArgs a = post_args(s);
+    a.first = first;
+    a.rows = chunk - first;
+    const int e = mp::launch_post_accumulate(a, s->ev->stream);
+    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     m->n += a.rows;
     return MP_OK;
 }
@@ -351,8 +410,10 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
         HIP_TRY(hipStreamSynchronize(ev->stream));
     }
     s->have_state = true;
-    if (s->acf) return acf_restart(s);   // the series is broken
-    return MP_OK;
+    int rc = MP_OK;
+    if (s->acf) rc = acf_restart(s);     // the series is broken
+    if (!rc && s->post) rc = post_restart(s);
+    return rc;
 }
 
 // Enqueue step steps_done + row of mp_sampler_run on the handle's stream: split d_perm, chain row `row` of the device slab when
@@ -396,9 +457,11 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
     // chunks of steps so that the device-resident chain slab stays below ~256 MB, the splits below ~64 MB, and the
     // window of failed proposals (drained after every chunk) overflows only if more than 1 in 32 proposals fails
     const size_t perm_cap = perm_chunk_cap(s);
-    const bool monitor = s->acf != nullptr, slab = chain || monitor;   // the monitor reads the chain rows from the device slab
+    const bool monitor = s->acf != nullptr, post = s->post != nullptr;
+    const bool slab = chain || monitor || post;   // the monitors read the chain rows from the device slab
     int chunk_max = (int)std::min<size_t>((size_t)std::max(n_steps, 1), slab ? slab_chunk_cap(s, perm_cap) : perm_cap);
     if (monitor) chunk_max = std::min(chunk_max, s->acf->chunk_cap);
+    if (post) chunk_max = std::min(chunk_max, s->post->chunk_cap);
     constexpr int kSub = 8;   // steps per batch of splits: the host draws the next batch while the GPU runs this one
     int rc;
     // A whole step per launch (mp_kernels.hip stretch_step_kernel: 3 n/2 evaluations, a third of them speculative) while
@@ -431,6 +494,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
             }
         }
         if (monitor && (rc = acf_feed(s, chunk))) return rc;
+        if (post && (rc = post_feed(s, chunk))) return rc;
         if (chain) {
             HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
             HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
@@ -547,6 +611,127 @@ int mp_sampler_get_autocorr_sums(mp_sampler *s, int ensemble, double *S, double 
     return MP_OK;
 }
 
+// ---- posterior monitor
+int mp_sampler_set_posterior(mp_sampler *s, int bins1, int bins2, const double *lower, const double *upper, int64_t discard) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_set_posterior: NULL sampler");
+    Held held(s->h, s->ev);
+    HIP_TRY(hipDeviceSynchronize());
+    s->post.reset();
+    if (bins1 == 0) return MP_OK;
+    if (bins1 < 0 || bins1 > MP_POST_MAX_BINS) return fail(MP_EINVAL, "mp_sampler_set_posterior: bins1 must be in [0, %d] (MP_POST_MAX_BINS; 0 turns the monitor off), got %d", MP_POST_MAX_BINS, bins1);
+    if (bins2 < 0 || bins2 > MP_POST_MAX_BINS2) return fail(MP_EINVAL, "mp_sampler_set_posterior: bins2 must be in [0, %d] (MP_POST_MAX_BINS2; 0: no 2-D histograms), got %d", MP_POST_MAX_BINS2, bins2);
+    if (discard < 0) return fail(MP_EINVAL, "mp_sampler_set_posterior: discard must be >= 0, got %lld", (long long)discard);
+    if (!lower || !upper) return fail(MP_EINVAL, "mp_sampler_set_posterior: NULL range");
+    for (int d = 0; d < s->ndim; ++d)
+        if (!std::isfinite(lower[d]) || !std::isfinite(upper[d]) || !(lower[d] < upper[d]) || !std::isfinite(upper[d] - lower[d]))
+            return fail(MP_EINVAL, "mp_sampler_set_posterior: range of dimension %d must be finite with lower < upper, got [%g, %g]", d, lower[d], upper[d]);
+    if (s->n_ensembles > 65535) return fail(MP_EINVAL, "mp_sampler_set_posterior: at most 65535 ensembles, got %d", s->n_ensembles);
+    const size_t ne = (size_t)s->n_ensembles, nt = (size_t)s->n_total, nd = (size_t)s->ndim;
+    const size_t np = (size_t)mp::post_n_pairs(s->ndim), nent = (size_t)mp::post_n_entries(s->ndim);
+    const size_t n_h1 = ne * nd * mp::post_stride1(bins1), n_h2 = ne * np * (size_t)bins2 * bins2;
+    const double bytes = 8.0 * ((double)n_h1 + (double)n_h2 + (double)(ne * np) + (double)(ne * (nd + 2)) + (double)nt * (double)(nent + 1));
+    if (bytes > (double)MP_POST_MAX_BYTES)
+        return fail(MP_EINVAL, "mp_sampler_set_posterior: bins1 = %d, bins2 = %d over %d ensembles of %d dimensions need %.0f bytes of accumulators, more than MP_POST_MAX_BYTES = %lld: lower the bin counts",
+                    bins1, bins2, s->n_ensembles, s->ndim, bytes, (long long)MP_POST_MAX_BYTES);
+    std::unique_ptr<PostMonitor> m(new PostMonitor());
+    m->bins1 = bins1; m->bins2 = bins2; m->discard = discard;
+    // chunks of at most 64 MB of chain rows while the monitor is on, as under the autocorrelation monitor
+    m->chunk_cap = (int)std::max<size_t>(1, std::min<size_t>(slab_chunk_cap(s, perm_chunk_cap(s)), ((size_t)64 << 20) / (nt * nd * sizeof(double))));
+    m->par.resize(5 * nd);
+    mp::post_params(m->par.data(), s->ndim, bins1, bins2, lower, upper);
+    int rc;
+    if ((rc = m->d_par.ensure(5 * nd)) || (rc = m->hist1.ensure(n_h1)) || (rc = m->hist2.ensure(n_h2)) || (rc = m->outside2.ensure(ne * np)) ||
+        (rc = m->mom.ensure(nent * nt)) || (rc = m->nfin.ensure(nt)) || (rc = m->best_x.ensure(ne * nd)) || (rc = m->best_lnp.ensure(ne)) ||
+        (rc = m->best_idx.ensure(ne)))
+        return rc;
+    HIP_TRY(hipMemcpy(m->d_par.p, m->par.data(), 5 * nd * sizeof(double), hipMemcpyHostToDevice));
+    s->post = std::move(m);
+    if ((rc = post_restart(s))) s->post.reset();
+    return rc;
+}
+
+// The prologue of the read-outs: the monitor is on, the ensemble exists, and what was fed has been accumulated
+static int post_ready(mp_sampler *s, const char *fn, int ensemble) {
+    if (!s->post) return fail(MP_ESTATE, "%s: the posterior monitor is off (mp_sampler_set_posterior)", fn);
+    if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "%s: ensemble must be in [0, %d), got %d", fn, s->n_ensembles, ensemble);
+    HIP_TRY(hipStreamSynchronize(s->ev->stream));
+    return MP_OK;
+}
+
+int mp_sampler_get_posterior_hist1(mp_sampler *s, int ensemble, int64_t *hist1, int64_t *below, int64_t *above,
+                                   int64_t *nonfinite, int64_t *n_samples) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_posterior_hist1: NULL sampler");
+    Held held(s->h, s->ev);
+    const int rc = post_ready(s, "mp_sampler_get_posterior_hist1", ensemble);
+    if (rc) return rc;
+    const PostMonitor *m = s->post.get();
+    const size_t nd = (size_t)s->ndim, B = (size_t)m->bins1, stride = (size_t)mp::post_stride1(m->bins1);
+    std::vector<int64_t> h(nd * stride);
+    HIP_TRY(hipMemcpy(h.data(), m->hist1.p + (size_t)ensemble * nd * stride, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (size_t d = 0; d < nd; ++d) {
+        const int64_t *row = h.data() + d * stride;
+        if (hist1) std::memcpy(hist1 + d * B, row, B * sizeof(int64_t));
+        if (below) below[d] = row[B];
+        if (above) above[d] = row[B + 1];
+        if (nonfinite) nonfinite[d] = row[B + 2];
+    }
+    if (n_samples) *n_samples = m->n * s->n_walkers;
+    return MP_OK;
+}
+
+int mp_sampler_get_posterior_hist2(mp_sampler *s, int ensemble, int64_t *hist2, int64_t *outside2) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_posterior_hist2: NULL sampler");
+    Held held(s->h, s->ev);
+    const int rc = post_ready(s, "mp_sampler_get_posterior_hist2", ensemble);
+    if (rc) return rc;
+    const PostMonitor *m = s->post.get();
+    if (!m->bins2) return fail(MP_ESTATE, "mp_sampler_get_posterior_hist2: the monitor keeps no 2-D histograms (bins2 = 0)");
+    const size_t np = (size_t)mp::post_n_pairs(s->ndim), cells = (size_t)m->bins2 * m->bins2;
+    if (!np) return MP_OK;
+    return read_back(hist2, (const int64_t *)m->hist2.p + (size_t)ensemble * np * cells, np * cells,
+                     outside2, (const int64_t *)m->outside2.p + (size_t)ensemble * np, np);
+}
+
+int mp_sampler_get_posterior_moments(mp_sampler *s, int ensemble, double *sum1, double *sum2, double *pivot, int64_t *n_finite) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_posterior_moments: NULL sampler");
+    Held held(s->h, s->ev);
+    const int rc = post_ready(s, "mp_sampler_get_posterior_moments", ensemble);
+    if (rc) return rc;
+    const PostMonitor *m = s->post.get();
+    const size_t nd = (size_t)s->ndim, nw = (size_t)s->n_walkers, nt = (size_t)s->n_total, nent = (size_t)mp::post_n_entries(s->ndim);
+    // the ensemble's walkers of every entry, summed in walker order from 0.0
+    std::vector<double> part(nent * nw), tot(nent);
+    HIP_TRY(hipMemcpy2D(part.data(), nw * sizeof(double), m->mom.p + (size_t)ensemble * nw, nt * sizeof(double), nw * sizeof(double), nent, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nent; ++k) {
+        double t = 0.0;
+        for (size_t w = 0; w < nw; ++w) t += part[k * nw + w];
+        tot[k] = t;
+    }
+    if (sum1) std::memcpy(sum1, tot.data(), nd * sizeof(double));
+    if (sum2) {
+        size_t k = nd;
+        for (size_t a = 0; a < nd; ++a)
+            for (size_t b = a; b < nd; ++b, ++k) sum2[a * nd + b] = sum2[b * nd + a] = tot[k];
+    }
+    if (pivot) std::memcpy(pivot, m->par.data() + 4 * nd, nd * sizeof(double));
+    if (n_finite) {
+        std::vector<int64_t> cnt(nw);
+        HIP_TRY(hipMemcpy(cnt.data(), m->nfin.p + (size_t)ensemble * nw, nw * sizeof(int64_t), hipMemcpyDeviceToHost));
+        *n_finite = std::accumulate(cnt.begin(), cnt.end(), (int64_t)0);
+    }
+    return MP_OK;
+}
+
+int mp_sampler_get_posterior_best(mp_sampler *s, int ensemble, double *x, double *lnprob, int64_t *index) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_posterior_best: NULL sampler");
+    Held held(s->h, s->ev);
+    const int rc = post_ready(s, "mp_sampler_get_posterior_best", ensemble);
+    if (rc) return rc;
+    const PostMonitor *m = s->post.get();
+    return read_back(x, (const double *)m->best_x.p + (size_t)ensemble * s->ndim, (size_t)s->ndim,
+                     lnprob, (const double *)m->best_lnp.p + ensemble, (size_t)1, index, (const int64_t *)m->best_idx.p + ensemble, (size_t)1);
+}
+
 int mp_sampler_set_whole_step(mp_sampler *s, int enable) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_set_whole_step: NULL sampler");
     Lock lock(s->h->mu);
@@ -594,6 +779,8 @@ struct ShardCall {
             rc = fail(MP_ESTATE, "%s: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)", fn);
         else if (s->acf)
             rc = fail(MP_ESTATE, "%s: the autocorrelation monitor (mp_sampler_set_autocorr) is fed by mp_sampler_run only; turn it off first", fn);
+        else if (s->post)
+            rc = fail(MP_ESTATE, "%s: the posterior monitor (mp_sampler_set_posterior) is fed by mp_sampler_run only; turn it off first", fn);
         else if (!(rc = current_split(s, (hipStream_t)stream, &d_perm))) s->ext_stream_work = true;
     }
 };

@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi, engine, tempering
+from . import _capi, engine, posterior, tempering
 from . import moves as _moves
 
 
@@ -85,7 +85,9 @@ class EnsembleSampler:
         self.fbad = fbad
         self._bad_written = 0
         self._warned_bad = False
+        self._have_positions = False
         self._acf = None            # (max_lag, discard) of the device autocorrelation monitor; None: off
+        self._post = None           # (bins, bins2, lower, upper) of the device posterior monitor; None: off
         self.converged = False      # run_mcmc_until
         self.tau_history = []
 
@@ -167,6 +169,7 @@ class EnsembleSampler:
         if p.shape != (self.ntotal, self.ndim):
             raise ValueError(f"pos must have shape {(self.ntotal, self.ndim)}")
         _capi.check(self._L.mp_sampler_set_positions(self._s, _capi.ptr(p)), "mp_sampler_set_positions")
+        self._have_positions = True
 
     def halfstep_shard(self, half, lo, hi, d_rows, stream=0):
         _capi.check(self._L.mp_sampler_halfstep_shard(self._s, int(half), int(lo), int(hi), C.c_void_p(d_rows or None),
@@ -359,12 +362,105 @@ class EnsembleSampler:
         out["n"] = int(out["n"])
         return out
 
+    # ---- the device posterior monitor (include/magprop_amd.h mp_sampler_set_posterior states the definition)
+    def monitor_posterior(self, bins=256, bins2=64, range=None, discard=0):
+        """Turn the posterior monitor on (empty, accumulating from `discard` steps from now on), or off with bins=0: per
+        ensemble, 1-D histograms of `bins` bins per dimension, 2-D histograms of bins2 x bins2 bins per pair (0: none), the
+        moments and the best sample, all kept on the device (get_posterior, get_quantiles).
+        range: None, the handle's prior box in sampler coordinates; "ensemble", per dimension [min - span, max + span] of the
+        current positions of all ensembles, span = max - min, clipped to the prior box (for use after a burn-in; raises before
+        positions are set or where a span is 0); or an array (ndim, 2) of [lower, upper) per dimension.
+        While it is on, set_positions (run_mcmc with pos) restarts it and the walker-sharded entry points refuse."""
+        bins, bins2 = int(bins), int(bins2)
+        if bins == 0:
+            _capi.check(self._L.mp_sampler_set_posterior(self._s, 0, 0, None, None, 0), "mp_sampler_set_posterior")
+            self._post = None
+            return
+        box = tuple(np.asarray(v, dtype=np.float64) for v in self._prior)
+        if range is None or isinstance(range, str):
+            if box[0].shape != (self.ndim,):
+                raise ValueError(f"the prior box has {box[0].size} dimensions, the sampler {self.ndim}: give range=array(ndim, 2)")
+            if range is None:
+                lo, hi = box
+            elif range == "ensemble":
+                if not self._have_positions:
+                    raise ValueError("range='ensemble' needs positions: call it after set_positions or a burn-in")
+                lo, hi = posterior.ensemble_range(self.get_last_sample()[0], *box)
+            else:
+                raise ValueError(f"range must be None, 'ensemble' or an array (ndim, 2), got {range!r}")
+        else:
+            r = np.asarray(range, dtype=np.float64)
+            if r.shape != (self.ndim, 2):
+                raise ValueError(f"range must have shape ({self.ndim}, 2), got {r.shape}")
+            lo, hi = r[:, 0], r[:, 1]
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        self._post = None
+        _capi.check(self._L.mp_sampler_set_posterior(self._s, bins, bins2, _capi.ptr(lo), _capi.ptr(hi), int(discard)),
+                    "mp_sampler_set_posterior")
+        self._post = (bins, bins2, lo, hi)
+
+    def _post_ensemble(self, ensemble, temp):
+        """Index of `ensemble` in the library's order; temp=t: ensemble counts the beta_t ensembles, as get_chain(temp=) does."""
+        if self._post is None:
+            raise _capi.MagpropAmdError("the posterior monitor is off (monitor_posterior)")
+        e = int(ensemble)
+        if temp is None:
+            return e
+        t = int(temp)
+        if not 0 <= t < self.ntemps:
+            raise ValueError(f"temp must be in 0..{self.ntemps - 1}, got {temp}")
+        if not 0 <= e < self.ngroups:
+            raise ValueError(f"ensemble must be in 0..{self.ngroups - 1} with temp=, got {ensemble}")
+        return e * self.ntemps + t
+
+    def get_posterior(self, ensemble=0, temp=None):
+        """The posterior monitor's summary of one ensemble (temp=t: the beta_t ensemble of group `ensemble`): a dict with
+        n (samples), edges1 (ndim, bins + 1), hist1 (ndim, bins), below, above, nonfinite (ndim,), pairs [(a, b), ...],
+        edges2 (ndim, bins2 + 1), hist2 (npairs, bins2, bins2) indexed [pair][bin of a][bin of b], outside2 (npairs,)
+        (edges2, hist2, outside2 None with bins2=0), mean (ndim,), cov (ndim, ndim) over the n_finite samples whose coordinates
+        are all finite, best_x (ndim,), best_lnprob, best_index (t * nwalkers + w; -1 and NaN before the first sample)."""
+        e = self._post_ensemble(ensemble, temp)
+        bins, bins2, lo, hi = self._post
+        nd = self.ndim
+        pairs = [(a, b) for a in range(nd) for b in range(a + 1, nd)]
+        L = self._L
+        h1 = _capi.read_back(L.mp_sampler_get_posterior_hist1, self._s, [
+            ("hist1", (nd, bins), np.int64), ("below", nd, np.int64), ("above", nd, np.int64), ("nonfinite", nd, np.int64),
+            ("n", (), np.int64)], e)
+        out = dict(h1, n=int(h1["n"]), edges1=posterior.edges(lo, hi, bins), pairs=pairs, edges2=None, hist2=None, outside2=None)
+        if bins2:
+            out.update(_capi.read_back(L.mp_sampler_get_posterior_hist2, self._s, [
+                ("hist2", (len(pairs), bins2, bins2), np.int64), ("outside2", len(pairs), np.int64)], e))
+            out["edges2"] = posterior.edges(lo, hi, bins2)
+        m = _capi.read_back(L.mp_sampler_get_posterior_moments, self._s, [
+            ("sum1", nd, np.float64), ("sum2", (nd, nd), np.float64), ("pivot", nd, np.float64), ("n_finite", (), np.int64)], e)
+        out["n_finite"] = int(m["n_finite"])
+        out["mean"], out["cov"] = posterior.mean_cov(m["sum1"], m["sum2"], m["pivot"], out["n_finite"])
+        b = _capi.read_back(L.mp_sampler_get_posterior_best, self._s, [
+            ("x", nd, np.float64), ("lnprob", (), np.float64), ("index", (), np.int64)], e)
+        out["best_x"], out["best_lnprob"], out["best_index"] = b["x"], float(b["lnprob"]), int(b["index"])
+        return out
+
+    def get_quantiles(self, q=(0.16, 0.5, 0.84), ensemble=0, temp=None):
+        """(len(q), ndim): the quantiles q of every dimension from the monitor's 1-D histograms (posterior.hist_quantiles:
+        linear inside the bin that holds the rank, so good to a bin width; NaN and a RuntimeWarning where the histogram's range
+        was too narrow)."""
+        e = self._post_ensemble(ensemble, temp)
+        bins, _, lo, hi = self._post
+        h = _capi.read_back(self._L.mp_sampler_get_posterior_hist1, self._s, [
+            ("hist1", (self.ndim, bins), np.int64), ("below", self.ndim, np.int64), ("above", self.ndim, np.int64),
+            ("nonfinite", None, None), ("n", None, None)], e)
+        return posterior.hist_quantiles(h["hist1"], h["below"], h["above"], lo, hi, q)
+
     def run_mcmc_until(self, pos, max_steps, check_every=100, tol=50, rtol=0.01, c=5.0, store=True):
         """emcee's run-until-converged recipe on the device monitor: after every check_every steps read tau (the beta = 1
         ensembles of a tempered sampler) and stop once autocorr_converged(tau, previous tau, n, tol, rtol) holds, n the
         monitor's samples, or after max_steps.  Turns the monitor on (max_lag 1024, discard 0) if it is off.  Sets
         self.converged and self.tau_history = [(n, tau), ...]; returns the final positions.  store=True appends the steps
-        to the stored chain (preallocated once for max_steps, trimmed); store=False: no chain reaches the host."""
+        to the stored chain (preallocated once for max_steps, trimmed); store=False: no chain reaches the host.
+        The posterior monitor (monitor_posterior) runs next to it: both are fed from the same device rows, so a
+        store=False run ends with tau and with the histograms, moments and best sample of get_posterior.  Both restart at
+        set_positions, so give pos=None to keep what a monitor holds, and turn monitor_posterior on after the burn-in."""
         max_steps, check_every = int(max_steps), int(check_every)
         if check_every < 1 or max_steps < 0:
             raise ValueError(f"check_every must be >= 1 and max_steps >= 0, got {check_every}, {max_steps}")
