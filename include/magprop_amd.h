@@ -252,6 +252,57 @@ int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physica
                   double *band_out, int32_t *status_out, int32_t *n_used);
 
 /*
+ * Energy budgets and light-curve landmarks of the model of n parameter rows, computed on the device (ABI 5, additive): the
+ * physical quantities a fit implies, which are functions of a sample's whole curves and trajectory (how much energy it
+ * radiates and through which channel, when and how high it peaks, by when half of the energy is out, how far accretion spins
+ * the star up).  pars, ndim and physical are mp_model_band's; out[n][MP_DERIVED_N], status_out[n] (optional) and *n_used
+ * (optional: the rows with MP_STATUS_OK) are host buffers, and the call returns when the results are in them.  A row whose
+ * status is not MP_STATUS_OK gets MP_DERIVED_N NaNs; no row finished: all NaN and MP_OK.  No dataset is needed.  A
+ * multi-device handle runs the call on its first device.
+ *
+ * n has no cap: the rows go through the device in chunks of mp_n_simd(h) rows (1 024 on an MI355X), each one launch of the
+ * curve kernels with all five curves (the 4-steps-per-lane build, the one mp_model_lc runs for a single row), one reduction
+ * launch and one copy, all on the handle's stream with one wait at the end.  A row's columns are therefore bit for bit the
+ * definition below applied to what mp_model_lc returns for that row alone, whatever n is and wherever the row sits.
+ * Workspace: 5 * min(n, mp_n_simd) * n_grid doubles (410 MB), owned by the handle, grow-only, freed by mp_destroy.
+ *
+ * Columns.  G = n_grid, t_i the grid, dt_i = t_{i+1} - t_i, luminosities in 1e50 erg/s as mp_model_lc returns them:
+ *   E_TOT, E_PROP, E_DIP   trapezoid of Ltot, Lprop, Ldip over the grid (1e50 erg): the sum of 0.5 * dt_i * (L_i + L_{i+1}),
+ *                          formed as (0.5 * dt_i) * (L_i + L_{i+1}) with every difference, product and sum rounded on its own
+ *   L_PEAK, T_PEAK         the largest Ltot and its grid time (the first one of equal values); LPROP_PEAK, T_LPROP_PEAK: of Lprop
+ *   T10, T50, T90          the first grid time t_{i+1} at which the cumulative trapezoid of Ltot up to t_{i+1} is >= f * E_TOT,
+ *                          f = 0.1, 0.5, 0.9 (the product rounded once); E_TOT == 0: t_1; never reached (a negative total):
+ *                          t_{G-1}
+ *   OMEGA_END              omega at the last grid point (rad/s); OMEGA_MAX, T_OMEGA_MAX its largest value and that value's
+ *                          time, first occurrence (the accretion spin-up)
+ *   MDISC_END, MDISC_MAX, T_MDISC_MAX   the same of the disc mass (g)
+ * Order of the sums (a function of the row's curves and G only): the G - 1 intervals are cut into 256 contiguous segments of
+ * ceil((G - 1) / 256) intervals (the last ones may be short or empty); inside a segment the terms are added in increasing i
+ * from 0.0; the 256 segment totals are added in segment order from 0.0 (an empty segment adds 0.0); the cumulative energy up
+ * to t_{i+1} is the total of the segments before i's plus the running sum of its segment.  No FMA contraction and no
+ * floating-point atomic anywhere.  (tests/derive_restated.py is this definition in numpy.)
+ */
+#define MP_DERIVED_N 16
+#define MP_DERIVED_E_TOT 0
+#define MP_DERIVED_E_PROP 1
+#define MP_DERIVED_E_DIP 2
+#define MP_DERIVED_L_PEAK 3
+#define MP_DERIVED_T_PEAK 4
+#define MP_DERIVED_LPROP_PEAK 5
+#define MP_DERIVED_T_LPROP_PEAK 6
+#define MP_DERIVED_T10 7
+#define MP_DERIVED_T50 8
+#define MP_DERIVED_T90 9
+#define MP_DERIVED_OMEGA_END 10
+#define MP_DERIVED_OMEGA_MAX 11
+#define MP_DERIVED_T_OMEGA_MAX 12
+#define MP_DERIVED_MDISC_END 13
+#define MP_DERIVED_MDISC_MAX 14
+#define MP_DERIVED_T_MDISC_MAX 15
+int mp_model_derived(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, double *out, int32_t *status_out,
+                     int64_t *n_used);
+
+/*
  * Ensemble sampler: emcee's affine-invariant stretch move (Goodman & Weare 2010) with a random red/blue
  * split per step, as driven by code/synthetic_datasets/synth_mcmc.py:175-185
  * (em.EnsembleSampler(Nwalk, Npars, lnprob, ...).run_mcmc(pos, Nstep)).  Positions, log-posteriors,

@@ -21,6 +21,7 @@ MAX_DATASETS = 64
 BAND_MAX_SAMPLES, BAND_MAX_Q = 16384, 16                      # include/magprop_amd.h MP_BAND_*
 BAND_LTOT, BAND_LPROP, BAND_LDIP = 1, 2, 4
 BAND_COMPONENTS = {"Ltot": BAND_LTOT, "Lprop": BAND_LPROP, "Ldip": BAND_LDIP}
+DERIVED_N = 16                                                # include/magprop_amd.h MP_DERIVED_N (columns: magprop_amd/derived.py)
 DE_BEST1BIN, DE_RAND1BIN = 0, 1                               # include/magprop_amd.h MP_DE_*
 NEST_MIN_LIVE, NEST_MAX_LIVE, NEST_MAX_WALKS = 16, 4096, 4096  # include/magprop_amd.h MP_NEST_*
 NEST_MAX_SLICES, NEST_MAX_STEPS_OUT, NEST_MAX_SHRINK = 4096, 4096, 254
@@ -68,6 +69,7 @@ SIGNATURES = {
     "mp_model_lc": (_i, [_vp, _dp, _i, _dp, _dp, _ip]),
     "mp_rhs_batch": (_i, [_vp, _dp, _i, _dp, _dp, _i, _dp, _dp]),
     "mp_model_band": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _u32, _dp, _ip, _ip]),
+    "mp_model_derived": (_i, [_vp, _dp, _i64, _i, _i, _dp, _ip, _i64p]),
     "mp_sampler_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _d, _i]),
     "mp_sampler_destroy": (_i, [_vp]),
     "mp_sampler_set_positions": (_i, [_vp, _dp]),
@@ -454,6 +456,22 @@ class Handle(_Owner):
         check(self._L.mp_model_band(self._h, _dptr(p), n, nd, int(bool(physical)), _dptr(qa), int(qa.size), C.c_uint32(mask),
                                     _dptr(band), _iptr(st), C.byref(used)), "mp_model_band")
         return band, st, int(used.value)
+
+    def model_derived(self, pars, physical=False):
+        """Energy budgets and light-curve landmarks of the models of the rows of pars (mp_model_derived; the columns are
+        magprop_amd.derived.NAMES): returns (values[n, DERIVED_N], status[n], n_used), rows that did not finish all NaN.  Any
+        number of rows: the library works through them in chunks.  physical=False: sampler coordinates under the handle's
+        prior, as lnprob_batch takes them."""
+        p = np.ascontiguousarray(pars, dtype=np.float64)
+        if p.ndim != 2 or p.shape[0] < 1:
+            raise ValueError(f"pars must be 2-D (n >= 1, ndim), got shape {p.shape}")
+        n, nd = p.shape
+        out = np.empty((n, DERIVED_N), dtype=np.float64)
+        st = np.empty(n, dtype=np.int32)
+        used = C.c_int64(0)
+        check(self._L.mp_model_derived(self._h, _dptr(p), n, nd, int(bool(physical)), _dptr(out), _iptr(st), C.byref(used)),
+              "mp_model_derived")
+        return out, st, int(used.value)
 
     def rhs_batch(self, pars, t, y, want_lam=False):
         """(dMdisc/dt, domega/dt) at n states: pars (n, ndim) physical, t (n,), y (n, 2) = (Mdisc, omega)."""

@@ -13,6 +13,7 @@
 #include <string>
 
 #include "mp_band.h"
+#include "mp_derive.h"
 #include "mp_host.h"
 
 static thread_local std::string g_err;
@@ -726,6 +727,65 @@ int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physica
     HIP_TRY(hipStreamSynchronize(st));
     if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * (size_t)n);
     if (n_used) *n_used = (int32_t)std::count(stt.begin(), stt.end(), (int32_t)MP_STATUS_OK);
+    return MP_OK;
+}
+
+// The rows go through the device in chunks of n_simd rows: five curves of a chunk are the workspace, and every chunk runs the
+// curve build kernel_spl_curves names for n <= n_simd, the one mp_model_lc runs for a single row.
+int mp_model_derived(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, double *out, int32_t *status_out,
+                     int64_t *n_used) {
+    // (the sizes first: they can be judged without a handle)
+    if (n < 1) return fail(MP_EINVAL, "mp_model_derived: n must be at least 1, got %lld", (long long)n);
+    if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "mp_model_derived: ndim must be 6..9, got %d", ndim);
+    if (!h || !pars || !out) return fail(MP_EINVAL, "mp_model_derived: NULL argument");
+    Evaluator *ev = h->first();
+    Held held(h, ev);
+    const size_t ng = ev->tgrid.size(), nn = (size_t)n;
+    const size_t chunk = (size_t)std::min<int64_t>(n, std::max(1, ev->sh.n_simd)), rows = chunk * ng;
+    int rc;
+    if ((rc = ev->w_pars.ensure(nn * (size_t)ndim)) || (rc = ev->w_lnprob.ensure(chunk)) || (rc = ev->w_status.ensure(nn)) ||
+        (rc = ev->w_derive.ensure(5 * rows)) || (rc = ev->w_derive_out.ensure(chunk * MP_DERIVED_N)))
+        return rc;
+    hipStream_t st = ev->stream;
+    HIP_TRY(hipMemcpyAsync(ev->w_pars.p, pars, sizeof(double) * nn * (size_t)ndim, hipMemcpyHostToDevice, st));
+    std::vector<int32_t> stt(nn);
+    int first_rc = MP_OK;
+    for (size_t lo = 0; lo < nn && !first_rc; lo += chunk) {
+        const size_t cnt = std::min(chunk, nn - lo);
+        mp::LaunchArgs a{};
+        a.pars = ev->w_pars.p + lo * (size_t)ndim;
+        a.n = (int32_t)cnt;
+        a.ndim = ndim;
+        a.physical = physical ? 1 : 0;
+        a.want_chi2 = 0;                          // curves only: no dataset needed
+        a.lnprob = ev->w_lnprob.p;
+        a.status = ev->w_status.p + lo;
+        a.ltot = ev->w_derive.p;                  // rows of walkers that did not finish are NaN-filled by the kernel
+        a.lprop = ev->w_derive.p + rows;
+        a.ldip = ev->w_derive.p + 2 * rows;
+        a.mdisc = ev->w_derive.p + 3 * rows;
+        a.omega = ev->w_derive.p + 4 * rows;
+        if ((first_rc = launch_lnprob_ordered(ev, a, st))) break;
+        mp::DeriveArgs d{};
+        d.curve[0] = a.ltot; d.curve[1] = a.lprop; d.curve[2] = a.ldip; d.curve[3] = a.mdisc; d.curve[4] = a.omega;
+        d.status = a.status;
+        d.tgrid = ev->d_tgrid.p;
+        d.out = ev->w_derive_out.p;
+        d.n = (int32_t)cnt;
+        d.n_grid = (int32_t)ng;
+        const int e = mp::launch_derive(d, (void *)st);
+        if (e) { first_rc = fail(MP_EHIP, "derive kernel launch failed: %s", hipGetErrorString((hipError_t)e)); break; }
+        hipError_t ce = hipMemcpyAsync(out + lo * MP_DERIVED_N, ev->w_derive_out.p, sizeof(double) * cnt * MP_DERIVED_N, hipMemcpyDeviceToHost, st);
+        if (ce == hipSuccess) ce = hipMemcpyAsync(stt.data() + lo, ev->w_status.p + lo, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st);
+        if (ce != hipSuccess) first_rc = fail(MP_EHIP, "mp_model_derived: copy failed: %s", hipGetErrorString(ce));
+    }
+    if (first_rc) {
+        (void)hipStreamSynchronize(st);           // nothing may still write the caller's buffers
+        return first_rc;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * nn);
+    if (n_used) *n_used = (int64_t)std::count(stt.begin(), stt.end(), (int32_t)MP_STATUS_OK);
     return MP_OK;
 }
 

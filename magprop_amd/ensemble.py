@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi, engine, posterior, tempering
+from . import _capi, derived, engine, posterior, tempering
 from . import moves as _moves
 
 
@@ -292,6 +292,16 @@ class EnsembleSampler:
         rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
                               discard, thin, ensemble)
         return _capi.band_result(self.handle, rows, qa, names)
+
+    def get_derived(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, ensemble=0):
+        """Energy budgets and light-curve landmarks over the stored chain (magprop_amd.derived.NAMES): the model of every row of
+        chain[discard::thin, ensemble's walkers], evaluated and reduced on this sampler's handle (mp_model_derived).  Returns
+        {"values": (rows, 16), "status", "n_used", "summary": derived.summarize(values, q)}."""
+        if self._target != 0:
+            raise ValueError("get_derived needs the posterior target: a target='gaussian' sampler has no light curve")
+        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
+                              discard, thin, ensemble)
+        return derived.result(self.handle, rows, q)
 
     def get_autocorr_time(self, c=5.0, tol=50, quiet=False, device=False):
         """emcee's default (quiet=False) raises when the chain is shorter than tol autocorrelation times; the

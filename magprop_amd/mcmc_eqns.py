@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from . import _capi, engine
+from . import _capi, derived, engine
 
 # Default prior box: the values of the reference's magnetar/mcmc_limits.csv:2-10 (rows B, P, log_MdiscI, log_RdiscI,
 # log_epsilon, log_delta, dipeff, propeff, f_beam), kept in code so that nothing depends on the working directory
@@ -99,3 +99,17 @@ def lnprob(pars, data, GRBtype, custom_lims=None, device=-1, reference_quirk=Fal
     p = np.asarray(pars, dtype=np.float64)
     lo, hi = _bounds(p.shape[-1], custom_lims)
     return _evaluate(p, data, GRBtype, lo, hi, 0 if reference_quirk else LIB_LOG_MASK, device)
+
+
+def model_derived(samples, GRBtype, custom_lims=None, q=(0.16, 0.5, 0.84), weights=None, device=-1):
+    """Energy budgets and light-curve landmarks of the library model of every row of `samples` (n, 6..9) in the sampler
+    coordinates of ``lnprob`` (box prior of ``custom_lims``, parameters 3-6 un-logged before the model), on the grid of
+    ``GRBtype``: what magprop_amd.derived.NAMES lists.  Returns {"values": (n, 16) with rows outside the prior or whose model
+    failed all NaN, "status", "n_used", "summary": derived.summarize(values, q, weights)}."""
+    p = np.ascontiguousarray(samples, dtype=np.float64)
+    if p.ndim != 2 or not 6 <= p.shape[1] <= 9:
+        raise ValueError(f"samples must be 2-D (n, 6..9), got shape {p.shape}")
+    lo, hi = _bounds(p.shape[1], custom_lims)
+    with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
+        eng.set_prior(lo, hi, LIB_LOG_MASK)
+        return derived.result(eng.handle, p, q, weights)

@@ -14,7 +14,7 @@ import warnings
 
 import numpy as np
 
-from . import _capi, engine, tempering
+from . import _capi, derived, engine, tempering
 from .optimize import OptimizeResult
 
 TARGETS = {"posterior": 0, "gaussian": 1}
@@ -308,6 +308,16 @@ class NestedSampler:
         if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
             rows = rows[np.linspace(0, rows.shape[0] - 1, _capi.BAND_MAX_SAMPLES).astype(int)]
         return _capi.band_result(self.handle, rows, qa, names)
+
+    def get_derived(self, q=(0.16, 0.5, 0.84), run=0):
+        """Energy budgets and light-curve landmarks of run `run` (magprop_amd.derived.NAMES): the model of every one of its
+        weighted samples, evaluated and reduced on this sampler's handle (mp_model_derived), and the quantiles q under the
+        samples' weights exp(logwt - max(logwt)) (the posterior weights up to a common factor) -- no resampling.  Returns {"values": (n, 16), "status", "n_used",
+        "summary": derived.summarize(values, q, weights)}."""
+        if self.target != "posterior":
+            raise ValueError("get_derived needs the posterior target: the gaussian target has no light curve")
+        r = self._run(run)
+        return derived.result(self.handle, r.samples, q, np.exp(r.logwt - np.max(r.logwt)))
 
 
 def get_state(L, ns, n_runs, nlive, ndim):

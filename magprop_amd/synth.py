@@ -6,7 +6,7 @@
 """
 import numpy as np
 
-from . import _capi, engine
+from . import _capi, derived, engine
 
 PRIOR_UPPER = np.array([10.0, 10.0, -2.0, np.log10(2000.0), 2.0, 3.0])   # :40
 PRIOR_LOWER = np.array([1.0e-3, 0.69, -6.0, np.log10(50.0), -2.0, -1.0])  # :41
@@ -90,3 +90,21 @@ def model_band(samples, q=(0.025, 0.5, 0.975), components=("Ltot",), device=-1):
     out.update({c: band[k] for k, c in enumerate(names)})
     out["n_used"] = used
     return out
+
+
+def model_derived(samples, q=(0.16, 0.5, 0.84), weights=None, device=-1):
+    """Energy budgets and light-curve landmarks of the synthetic model of every row of `samples` (sampler coordinates, as a
+    chain stores them; any number of rows), on the grid logspace(0, 6, 10001): radiated energy and its dipole / propeller
+    split, peaks, the times by which 10, 50 and 90 % of the energy is out, spin-up and disc mass (magprop_amd.derived.NAMES).
+    Returns {"values": (n, 16) with rows outside the prior or whose model failed all NaN, "status": (n,), "n_used": rows that
+    finished, "summary": derived.summarize(values, q, weights)}."""
+    p = np.ascontiguousarray(samples, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 6:
+        raise ValueError(f"samples must be 2-D (n, 6), got shape {p.shape}")
+    eng = engine.acquire(_cfg(), None, device)
+    try:
+        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
+        res = derived.result(eng.handle, p, q, weights)
+    finally:
+        engine.release(eng)
+    return res
