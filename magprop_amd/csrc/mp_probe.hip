@@ -192,6 +192,18 @@ __global__ void __launch_bounds__(64) lse_merge_kernel(const double *m, const do
     os[base] = ss;
 }
 
+// ---------------------------------------------------------------- index draws of the DE and snooker moves
+// out[e][0 .. 2] = pick(u, m), pick_skip(u, m, c0), pick_skip2(u, m, c0, c1) of element e; -1 where m is below the draw's
+// smallest size (2 for pick_skip, 3 for pick_skip2: what mp_sampler_set_moves enforces)
+__global__ void __launch_bounds__(64) pick_kernel(const double *u, const double *m, const double *c0, const double *c1, double *out, int n) {
+    const long base = lane_base<1>(n);
+    if (base < 0) return;
+    const int mm = (int)m[base], a = (int)c0[base], b = (int)c1[base];
+    out[3 * base] = (double)pick(u[base], mm);
+    out[3 * base + 1] = mm >= 2 ? (double)pick_skip(u[base], mm, a) : -1.0;
+    out[3 * base + 2] = mm >= 3 ? (double)pick_skip2(u[base], mm, a, b) : -1.0;
+}
+
 // ---------------------------------------------------------------- host side
 bool size_ok(int n, int per_lane) { return per_lane >= 1 && n >= 1 && n <= kMaxN && n % (64 * per_lane) == 0; }
 
@@ -439,6 +451,24 @@ int mpp_lse_merge(const double *m, const double *s, const double *mo, const doub
     const double *a = B.in(m, n), *b = B.in(s, n), *c = B.in(mo, n), *d = B.in(so, n);
     double *x = B.out(om, n), *y = B.out(os, n);
     if (B.ready()) lse_merge_kernel<<<dim3(n / 64), dim3(64)>>>(a, b, c, d, x, y, n);
+    return B.finish();
+}
+
+// out[n][3] = pick(u, m), pick_skip(u, m, c0), pick_skip2(u, m, c0, c1) per element, the integers m, c0, c1 and the results as
+// doubles; -1 where m < 2 (pick_skip) or m < 3 (pick_skip2).  Refused: u outside [0, 1), m outside 1 .. 2^20, c0 or c1 outside
+// [0, m), c0 == c1 where m >= 3
+int mpp_pick(const double *u, const double *m, const double *c0, const double *c1, double *out, int n) {
+    if (!size_ok(n, 1) || !u || !m || !c0 || !c1 || !out) return -1;
+    for (int i = 0; i < n; ++i) {
+        if (!(u[i] >= 0.0) || !(u[i] < 1.0) || !(m[i] >= 1.0) || !(m[i] <= (double)kMaxN) || m[i] != (double)(int)m[i]) return -1;
+        if (!(c0[i] >= 0.0) || !(c0[i] < m[i]) || c0[i] != (double)(int)c0[i]) return -1;
+        if (!(c1[i] >= 0.0) || !(c1[i] < m[i]) || c1[i] != (double)(int)c1[i]) return -1;
+        if (m[i] >= 3.0 && c0[i] == c1[i]) return -1;
+    }
+    Bufs B;
+    const double *du = B.in(u, n), *dm = B.in(m, n), *d0 = B.in(c0, n), *d1 = B.in(c1, n);
+    double *d = B.out(out, (size_t)n * 3);
+    if (B.ready()) pick_kernel<<<dim3(n / 64), dim3(64)>>>(du, dm, d0, d1, d, n);
     return B.finish();
 }
 

@@ -26,7 +26,7 @@ def fma(a, b, c):
 # every function libmp_probe.so exports (magprop_amd/csrc/mp_probe.hip); none of them belongs to libmagprop_amd.so
 PROBE_EXPORTS = ("mpp_unary", "mpp_exp10", "mpp_phi", "mpp_phi6", "mpp_node_weights", "mpp_wtab_size", "mpp_wtab_stride",
                  "mpp_scan_affine", "mpp_lane_prev", "mpp_lane_prev_map", "mpp_lane_bcast", "mpp_uniform", "mpp_wave_sum",
-                 "mpp_lane_ext", "mpp_unfused", "mpp_lse", "mpp_lse_merge")
+                 "mpp_lane_ext", "mpp_unfused", "mpp_lse", "mpp_lse_merge", "mpp_pick")
 
 
 # ---------------------------------------------------------------- error measures against a double-double expectation

@@ -110,6 +110,12 @@ class Probe:
         self._ok(self.L.mpp_lse(K, _p(t), _p(m), _p(s), t.size), "mpp_lse")
         return m, s
 
+    def pick(self, u, m, c0, c1):
+        u, m, c0, c1 = _in(u), _in(m), _in(c0), _in(c1)
+        out = np.full((u.size, 3), np.nan)
+        self._ok(self.L.mpp_pick(_p(u), _p(m), _p(c0), _p(c1), _p(out), u.size), "mpp_pick")
+        return out
+
     def lse_merge(self, m, s, mo, so):
         m, s, mo, so = _in(m), _in(s), _in(mo), _in(so)
         om, os_ = np.full(m.size, np.nan), np.full(m.size, np.nan)
@@ -493,3 +499,20 @@ def test_lse_merge(probe, g):
     # symmetric in its operands
     bm, bs = probe.lse_merge(mo, so, m, s)
     assert same_bits(bm, om) and same_bits(bs, os_)
+
+
+# ---------------------------------------------------------------- index draws of the DE and snooker moves
+def test_index_draws_equal_the_restatement(probe):
+    """pick, pick_skip and pick_skip2 (mp_math.hpp) on the cases of tests/commit_cases.py: m = 1 .. 70, u at the double below, at
+    and above every j / m' of the reduced ranges, 0 and 1 - 2^-53, every c0 != c1 for m <= 12 and seeded pairs above; equal to
+    moves_restated.pick* on every element (-1 where m is below the draw's smallest size), which tests/test_commit_cases_cpu.py
+    holds in range and distinct from c0 and c1.  One launch."""
+    import commit_cases as cc
+    u, m, c0, c1 = cc.pick_cases()
+    got = probe.pick(u, m, c0, c1)
+    assert np.array_equal(got, cc.pick_expected())
+    one = np.ones(64)
+    zero, out = np.zeros(64), np.full((64, 3), np.nan)
+    for bad in ((one, one, zero, zero), (-one, one, zero, zero), (zero, zero, zero, zero), (zero, 2 * one, 2 * one, zero),
+                (zero, 3 * one, one, one), (zero, 3 * one, -one, zero), (zero, 2.5 * one, zero, one), (np.full(64, np.nan), one, zero, zero)):
+        assert probe.L.mpp_pick(*(_p(_in(a)) for a in bad), _p(out), 64) == -1 and np.all(np.isnan(out)), bad

@@ -55,6 +55,47 @@ def test_gaussian_chain_bit_for_bit_on_the_one_wave_builds(name):
         assert np.array_equal(a, b), name
 
 
+@pytest.mark.parametrize("name", ["snooker", "de"])
+def test_coinciding_walkers_match_the_restatement_bit_for_bit(name):
+    """12 walkers x 3 dims x 30 steps started as six pairs of coinciding walkers.  Snooker: a walker whose z is its twin in the
+    other half has dd = 0, a NaN factor and a NaN Hastings term; the proposal is rejected, the walker stays and its chain row
+    repeats.  DE: partners x1 == x2 make the proposal the walker itself, to the bit (and accepted: 0 > ln u).  Chain, lnprob
+    and acceptance counts equal the restatement exactly, with one launch per step and with two."""
+    from oracle.stretch_oracle import gaussian_lnprob
+    table, seed = TABLES[name], 20261018
+    half = np.random.default_rng(21).normal(size=(6, 3))
+    pos = np.concatenate([half, half])
+    seen = {"nan": 0, "self": 0}
+    state = pos.copy()
+
+    def lnprob(q):      # (the restated loop advances `state` in place: q is held against the positions of the moment)
+        seen["nan"] += bool(np.any(np.isnan(q)))
+        seen["self"] += any(np.array_equal(q, x) for x in state)
+        return gaussian_lnprob(q)
+    ref = restate(state, 30, seed, table, lnprob_fn=lnprob)
+    assert seen["nan" if name == "snooker" else "self"] > 0, seen
+    assert not np.any(np.isnan(ref.chain)) and not np.any(np.isnan(ref.lnp)) and 0 < ref.acc.sum() < 30 * 12
+    for whole in (True, False):
+        got = gaussian_run(12, 1, 3, seed, table, pos, (30,), whole=whole)
+        for a, b in zip(got, (ref.chain, ref.lnp, ref.acc)):
+            assert np.array_equal(a, b), (name, whole)
+
+
+@pytest.mark.parametrize("whole", [True, False], ids=["whole-step", "half-steps"])
+def test_three_ensembles_match_the_restatement_bit_for_bit(whole):
+    """3 ensembles x 10 walkers x 3 dims x 40 steps of the stretch move, untempered, as one launch per step
+    (stretch_step_kernel and stretch_step_commit_kernel, whose partner lookup carries the ensemble term w_ens * n_half) and as two
+    half-step launches: chain, lnprob and acceptance counts equal the restatement exactly.  (tests/test_gpu_sampler.py
+    test_two_ensembles_match_the_oracle runs two ensembles in the library's default mode only.)"""
+    table, seed = [(STRETCH, 1.0, 2.0, 0.0)], 20261019
+    pos = np.random.default_rng(22).normal(size=(3 * 10, 3)) * 1.5
+    ref = restate(pos.copy(), 40, seed, table, n_ensembles=3)
+    assert 0 < ref.acc.sum() < 40 * 30
+    got = gaussian_run(10, 3, 3, seed, table, pos, (40,), whole=whole)
+    for a, b in zip(got, (ref.chain, ref.lnp, ref.acc)):
+        assert np.array_equal(a, b), whole
+
+
 def test_explicit_stretch_move_is_the_default_chain(gsynth):
     """moves=[StretchMove()] runs the chain of the default sampler on Humped, 64 walkers x 100 steps, bit for bit."""
     from magprop_amd import EnsembleSampler, StretchMove
