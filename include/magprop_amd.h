@@ -303,6 +303,63 @@ int mp_model_derived(mp_handle *h, const double *pars, int64_t n, int ndim, int 
                      int64_t *n_used);
 
 /*
+ * Pointwise predictive scores of a fit, computed on the device (ABI 5, additive): per observation of dataset ds_id, the
+ * reductions over the n samples' pointwise log-likelihoods from which WAIC, importance-sampling and Pareto-smoothed
+ * leave-one-out (PSIS-LOO) scores and their Pareto-k diagnostics follow on the host (magprop_amd/pointwise.py), without the
+ * n x n_obs matrix ever leaving the device.  pars, n, ndim and physical are mp_model_derived's; the dataset has to be set (as in
+ * mp_lnprob_batch: MP_ESTATE otherwise).  Observations are in the order mp_set_dataset keeps them: ascending time (stable).
+ *   obs_out[n_obs][MP_POINTWISE_N]              the columns below
+ *   tail_out[n_obs][mp_pointwise_tail_len(n)]   (optional) the min(T, N_USED) largest r of the observation, ascending, then NaN
+ *   z_out[n_obs][n]                             (optional) the cell matrix itself, for small calls and tests
+ *   status_out[n], *n_used                      (optional) as in mp_model_derived
+ * Limits: 1 <= n <= MP_POINTWISE_MAX_SAMPLES and n * n_obs <= MP_POINTWISE_MAX_CELLS.  The rows go through the device in chunks
+ * of mp_n_simd(h) rows, each one launch of the curve kernels (Ltot only, the build mp_model_lc runs for a single row) and one
+ * launch that turns the chunk's curves into cells; two reduction launches per call follow.  Workspace, owned by the handle,
+ * grow-only, freed by mp_destroy: n * n_obs + min(n, mp_n_simd) * n_grid doubles.  A multi-device handle runs the call on its
+ * first device.
+ *
+ * Cell of sample s (status MP_STATUS_OK) and observation j, with La, Lb the sample's Ltot (1e50 erg/s, as mp_model_lc returns
+ * it) at grid points g_j and g_j + 1, t[g_j] <= x_j < t[g_j + 1] (the last point: the last interval), dx_j = x_j - t[g_j],
+ * idt_j = 1 / (t[g_j + 1] - t[g_j]):
+ *   mod = ((Lb - La) * idt_j) * dx_j + La,   z = (y_j - mod) / yerr_j,   r = 0.5 * (z * z),   ll = -r
+ * every operation rounded on its own (no FMA contraction).  ll is the term of the unnormalised lnlike = -0.5 chi^2 the library
+ * samples; -0.5 ln(2 pi yerr_j^2) per point normalises it.  A sample whose status is not OK has NaN cells; the used cells of an
+ * observation are its non-NaN ones, N_USED of them.  T = mp_pointwise_tail_len(N_USED) = M + 1, M = ceil(min(N_USED / 5,
+ * 3 sqrt(N_USED))) the length of the Pareto tail of PSIS, computed in integers.  Columns, over the used cells:
+ *   N_USED                   their number
+ *   Z_MEAN, R_MEAN           means of z and of r (sum / N_USED; NaN for N_USED = 0)
+ *   LL_VAR                   variance of ll, two passes: the mean -R_MEAN, then the sum of squared deviations / (N_USED - 1); NaN
+ *                            for N_USED < 2
+ *   R_MIN, R_MAX             least and largest r (NaN for N_USED = 0)
+ *   LPPD_M, LPPD_S           running log-sum-exp pair of ll: sum exp(ll) = e^M S, M the largest ll ((-inf, 0): none)
+ *   CUT                      the min(T, N_USED)-th largest r: the first entry of the tail row (NaN for N_USED = 0)
+ *   NONTAIL_COUNT            cells with r <= CUT; the N_USED - NONTAIL_COUNT cells above the cut are the last entries of the tail
+ *   NONTAIL_M, NONTAIL_S     log-sum-exp pair of r (the log importance ratios) over exactly those cells
+ * Order of the sums: thread k of 256 takes the cells of samples k, k + 256, ... in increasing index from the empty sum, a
+ * wavefront's 64 partial results are combined by an xor butterfly (distances 32 .. 1), the four wavefronts in wavefront
+ * order.  Every number is a function of the cells and their sample indices, not of the chunking.  (tests/pointwise_restated.py
+ * is this definition in numpy.)
+ */
+#define MP_POINTWISE_MAX_SAMPLES 262144
+#define MP_POINTWISE_MAX_CELLS 268435456
+#define MP_POINTWISE_N 12
+#define MP_POINTWISE_N_USED 0
+#define MP_POINTWISE_Z_MEAN 1
+#define MP_POINTWISE_R_MEAN 2
+#define MP_POINTWISE_LL_VAR 3
+#define MP_POINTWISE_R_MIN 4
+#define MP_POINTWISE_R_MAX 5
+#define MP_POINTWISE_LPPD_M 6
+#define MP_POINTWISE_LPPD_S 7
+#define MP_POINTWISE_CUT 8
+#define MP_POINTWISE_NONTAIL_COUNT 9
+#define MP_POINTWISE_NONTAIL_M 10
+#define MP_POINTWISE_NONTAIL_S 11
+int mp_pointwise_tail_len(int64_t n_used);              /* T above; 0 for n_used < 1 */
+int mp_model_pointwise(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, int ds_id, double *obs_out,
+                       double *tail_out, double *z_out, int32_t *status_out, int64_t *n_used);
+
+/*
  * Ensemble sampler: emcee's affine-invariant stretch move (Goodman & Weare 2010) with a random red/blue
  * split per step, as driven by code/synthetic_datasets/synth_mcmc.py:175-185
  * (em.EnsembleSampler(Nwalk, Npars, lnprob, ...).run_mcmc(pos, Nstep)).  Positions, log-posteriors,

@@ -15,6 +15,7 @@
 #include "mp_band.h"
 #include "mp_derive.h"
 #include "mp_host.h"
+#include "mp_pointwise.h"
 
 static thread_local std::string g_err;
 
@@ -778,6 +779,93 @@ int mp_model_derived(mp_handle *h, const double *pars, int64_t n, int ndim, int 
         hipError_t ce = hipMemcpyAsync(out + lo * MP_DERIVED_N, ev->w_derive_out.p, sizeof(double) * cnt * MP_DERIVED_N, hipMemcpyDeviceToHost, st);
         if (ce == hipSuccess) ce = hipMemcpyAsync(stt.data() + lo, ev->w_status.p + lo, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st);
         if (ce != hipSuccess) first_rc = fail(MP_EHIP, "mp_model_derived: copy failed: %s", hipGetErrorString(ce));
+    }
+    if (first_rc) {
+        (void)hipStreamSynchronize(st);           // nothing may still write the caller's buffers
+        return first_rc;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * nn);
+    if (n_used) *n_used = (int64_t)std::count(stt.begin(), stt.end(), (int32_t)MP_STATUS_OK);
+    return MP_OK;
+}
+
+int mp_pointwise_tail_len(int64_t n_used) { return mp::pointwise_tail_len(n_used); }
+
+// The rows go through the device in chunks of n_simd rows as in mp_model_derived, with Ltot alone: every chunk's curve launch is
+// followed by the launch that turns its rows into columns [lo, lo + cnt) of the cell matrix.  The select and reduce kernels run
+// once behind the last chunk; nothing but the results reaches the host.
+int mp_model_pointwise(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, int ds_id, double *obs_out,
+                       double *tail_out, double *z_out, int32_t *status_out, int64_t *n_used) {
+    // (the sizes first: they can be judged without a handle)
+    if (n < 1 || n > MP_POINTWISE_MAX_SAMPLES)
+        return fail(MP_EINVAL, "mp_model_pointwise: n must be 1..%d (MP_POINTWISE_MAX_SAMPLES), got %lld", MP_POINTWISE_MAX_SAMPLES, (long long)n);
+    if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "mp_model_pointwise: ndim must be 6..9, got %d", ndim);
+    if (ds_id < 0 || ds_id >= MP_MAX_DATASETS) return fail(MP_EINVAL, "mp_model_pointwise: ds_id %d out of range", ds_id);
+    if (!h || !pars || !obs_out) return fail(MP_EINVAL, "mp_model_pointwise: NULL argument");
+    Evaluator *ev = h->first();
+    Held held(h, ev);
+    if (!ev->ds[ds_id].set) return fail(MP_ESTATE, "mp_model_pointwise: refers to unset dataset %d", ds_id);
+    const mp::DsDesc &dd = ev->desc[(size_t)ds_id];
+    const size_t ng = ev->tgrid.size(), nn = (size_t)n, n_obs = (size_t)dd.n_obs;
+    if ((int64_t)nn * (int64_t)n_obs > (int64_t)MP_POINTWISE_MAX_CELLS)
+        return fail(MP_EINVAL, "mp_model_pointwise: n * n_obs = %lld * %d exceeds MP_POINTWISE_MAX_CELLS = %lld", (long long)n, dd.n_obs,
+                    (long long)MP_POINTWISE_MAX_CELLS);
+    const size_t chunk = (size_t)std::min<int64_t>(n, std::max(1, ev->sh.n_simd));
+    const size_t tlen = (size_t)mp::pointwise_tail_len(n);
+    int rc;
+    if ((rc = ev->w_pars.ensure(nn * (size_t)ndim)) || (rc = ev->w_lnprob.ensure(chunk)) || (rc = ev->w_status.ensure(nn)) ||
+        (rc = ev->w_pw_ltot.ensure(chunk * ng)) || (rc = ev->w_pw_z.ensure(n_obs * nn)) ||
+        (rc = ev->w_pw_obs.ensure(n_obs * MP_POINTWISE_N)) || (rc = ev->w_pw_tail.ensure(n_obs * tlen)))
+        return rc;
+    hipStream_t st = ev->stream;
+    HIP_TRY(hipMemcpyAsync(ev->w_pars.p, pars, sizeof(double) * nn * (size_t)ndim, hipMemcpyHostToDevice, st));
+    const mp::PointwiseData pd{ev->d_obs_g.p + dd.obs_off, ev->d_obs_dx.p + dd.obs_off, ev->d_obs_idt.p + dd.obs_off,
+                               ev->d_obs_y.p + dd.obs_off, ev->d_obs_yerr.p + dd.obs_off, dd.n_obs};
+    int first_rc = MP_OK;
+    for (size_t lo = 0; lo < nn && !first_rc; lo += chunk) {
+        const size_t cnt = std::min(chunk, nn - lo);
+        mp::LaunchArgs a{};
+        a.pars = ev->w_pars.p + lo * (size_t)ndim;
+        a.n = (int32_t)cnt;
+        a.ndim = ndim;
+        a.physical = physical ? 1 : 0;
+        a.want_chi2 = 0;                          // the curve only: the cells are formed from it behind the launch
+        a.lnprob = ev->w_lnprob.p;
+        a.status = ev->w_status.p + lo;
+        a.ltot = ev->w_pw_ltot.p;                 // rows of walkers that did not finish are NaN-filled by the kernel (and not read)
+        if ((first_rc = launch_lnprob_ordered(ev, a, st))) break;
+        mp::PointwiseCellsArgs c{};
+        c.ltot = a.ltot;
+        c.status = a.status;
+        c.d = pd;
+        c.z = ev->w_pw_z.p;
+        c.n = n;
+        c.lo = (int64_t)lo;
+        c.cnt = (int32_t)cnt;
+        c.n_grid = (int32_t)ng;
+        const int e = mp::launch_pointwise_cells(c, (void *)st);
+        if (e) first_rc = fail(MP_EHIP, "pointwise cells kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    std::vector<int32_t> stt(nn);
+    if (!first_rc) {
+        mp::PointwiseColsArgs r{};
+        r.z = ev->w_pw_z.p;
+        r.obs = ev->w_pw_obs.p;
+        r.tail = ev->w_pw_tail.p;
+        r.n = n;
+        r.n_obs = dd.n_obs;
+        r.tail_stride = (int32_t)tlen;
+        int e = mp::launch_pointwise_select(r, (void *)st);
+        if (!e) e = mp::launch_pointwise_reduce(r, (void *)st);
+        if (e) first_rc = fail(MP_EHIP, "pointwise reduction kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    if (!first_rc) {
+        hipError_t ce = hipMemcpyAsync(obs_out, ev->w_pw_obs.p, sizeof(double) * n_obs * MP_POINTWISE_N, hipMemcpyDeviceToHost, st);
+        if (ce == hipSuccess && tail_out) ce = hipMemcpyAsync(tail_out, ev->w_pw_tail.p, sizeof(double) * n_obs * tlen, hipMemcpyDeviceToHost, st);
+        if (ce == hipSuccess && z_out) ce = hipMemcpyAsync(z_out, ev->w_pw_z.p, sizeof(double) * n_obs * nn, hipMemcpyDeviceToHost, st);
+        if (ce == hipSuccess) ce = hipMemcpyAsync(stt.data(), ev->w_status.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, st);
+        if (ce != hipSuccess) first_rc = fail(MP_EHIP, "mp_model_pointwise: copy failed: %s", hipGetErrorString(ce));
     }
     if (first_rc) {
         (void)hipStreamSynchronize(st);           // nothing may still write the caller's buffers

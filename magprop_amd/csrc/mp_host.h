@@ -144,6 +144,7 @@ struct Evaluator {
     DevBuf<double> w_pars, w_lnprob, w_curves;
     DevBuf<double> w_band, w_band_out;   // mp_model_band: [components][n][n_grid] curves | [n_grid][n] transposed; [components][nq][n_grid]
     DevBuf<double> w_derive, w_derive_out;   // mp_model_derived: [5][chunk][n_grid] curves of a chunk of rows; [chunk][MP_DERIVED_N]
+    DevBuf<double> w_pw_ltot, w_pw_z, w_pw_obs, w_pw_tail;   // mp_model_pointwise: [chunk][n_grid] Ltot of a chunk of rows; [n_obs][n] cells; [n_obs][MP_POINTWISE_N]; [n_obs][T(n)]
     DevBuf<int32_t> w_dsid, w_status, w_sweeps;
     DevBuf<int32_t> w_tile_log;
     std::vector<int32_t> last_tile_log;   // tile words of the rows of its block of the most recent host-buffer batch

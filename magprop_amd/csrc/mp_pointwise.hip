@@ -1,0 +1,324 @@
+// mp_pointwise.hip — gfx950 kernels of the pointwise predictive scores (mp_model_pointwise, include/magprop_amd.h; the cell, the
+// tail length and the order of the sums are stated in mp_pointwise.h).
+//
+// pointwise_cells_kernel turns a chunk's Ltot rows (walker-major [cnt][n_grid], what the curve kernels write) into standardised
+// residuals z in the observation-major matrix Z[n_obs][n], through 64 x 64 LDS tiles of stride 65: on the way in a wavefront
+// walks one curve row at the observations' grid points, on the way out it stores 64 consecutive samples of one observation.
+// pointwise_select_kernel takes one observation per workgroup: the min(T, N_USED)-th largest r = z^2 / 2 by an MSB-first radix
+// select over 8-bit digits of band_key(r) (mp_band.h; the column is streamed from memory once per digit: it does not fit LDS at
+// 262 144 samples), then the larger values are compacted into LDS, filled up with copies of the cut and sorted (bitonic, at most
+// 2 048 slots).  pointwise_reduce_kernel takes one observation per workgroup as well: counts, means, the two-pass variance,
+// extrema and the log-sum-exp pairs (lse_add, wave_lse, lse_merge of mp_math.hpp), with the select kernel's cut.
+#include <hip/hip_runtime.h>
+
+#include "mp_band.h"
+#include "mp_math.hpp"
+#include "mp_pointwise.h"
+
+namespace mp {
+
+namespace {
+
+constexpr int kWaves = kPointwiseThreads / 64;
+enum { kMiscCount = 0, kMiscDigit = 1, kMiscRank = 2, kMiscWave = 4 /* .. 4 + kWaves */, kMiscWords = 8 };
+
+__device__ inline double cell_r(double z) {
+#pragma clang fp contract(off)
+    const double zz = z * z;
+    return 0.5 * zz;
+}
+
+__global__ __launch_bounds__(kPointwiseThreads) void pointwise_cells_kernel(const PointwiseCellsArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double tile[kPointwiseTile][kPointwiseTile + 1];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int j0 = blockIdx.x * kPointwiseTile, s0 = blockIdx.y * kPointwiseTile;
+    const int j = j0 + tx;
+    const bool have = j < a.d.n_obs;
+    int g = 0;
+    double dx = 0.0, idt = 0.0, y = 0.0, ye = 1.0;
+    if (have) {
+        g = min(max(a.d.g[j], 0), a.n_grid - 2);   // (mp_set_dataset keeps g inside the grid: the last point sits in the last interval)
+        dx = a.d.dx[j];
+        idt = a.d.idt[j];
+        y = a.d.y[j];
+        ye = a.d.yerr[j];
+    }
+    for (int r = ty; r < kPointwiseTile; r += kWaves) {
+        const int s = s0 + r;
+        double z = __builtin_nan("");
+        if (have && s < a.cnt && a.status[s] == MP_STATUS_OK) {
+            const double *row = a.ltot + (size_t)s * (size_t)a.n_grid;
+            const double La = row[g], Lb = row[g + 1];
+            const double d = Lb - La;
+            const double slope = d * idt;
+            const double rise = slope * dx;
+            const double mod = rise + La;
+            const double res = y - mod;
+            z = res / ye;
+        }
+        tile[r][tx] = z;
+    }
+    __syncthreads();
+    for (int r = ty; r < kPointwiseTile; r += kWaves) {
+        const int jj = j0 + r, s = s0 + tx;
+        if (jj < a.d.n_obs && s < a.cnt) a.z[(size_t)jj * (size_t)a.n + (size_t)a.lo + (size_t)s] = tile[tx][r];
+    }
+}
+
+// ---------------------------------------------------------------- workgroup combinations (every thread gets the result; each ends with a barrier)
+__device__ inline double block_sum(double v, double *sh) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    v = wave_sum(v);
+    if (lane == 0) sh[wave] = v;
+    __syncthreads();
+    double r = sh[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) r = r + sh[w];
+    __syncthreads();
+    return r;
+}
+
+__device__ inline void block_lse(double &m, double &s, double *shm, double *shs) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wave_lse(m, s);
+    if (lane == 0) { shm[wave] = m; shs[wave] = s; }
+    __syncthreads();
+    m = shm[0];
+    s = shs[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) lse_merge(m, s, shm[w], shs[w]);
+    __syncthreads();
+}
+
+template <bool kMax>
+__device__ inline double block_extreme(double v, double *sh) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double o = __shfl_xor(v, d, 64);
+        v = kMax ? fmax(v, o) : fmin(v, o);
+    }
+    if (lane == 0) sh[wave] = v;
+    __syncthreads();
+    double r = sh[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) r = kMax ? fmax(r, sh[w]) : fmin(r, sh[w]);
+    __syncthreads();
+    return r;
+}
+
+__device__ inline uint32_t block_count(uint32_t v, uint32_t *sh) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    if (lane == 0) sh[wave] = v;
+    __syncthreads();
+    uint32_t r = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) r += sh[w];
+    __syncthreads();
+    return r;
+}
+
+// Inclusive sum over the workgroup's 256 threads (one value each); every thread gets its own prefix.  Ends with a barrier.
+__device__ inline uint32_t block_inclusive_scan(uint32_t v, uint32_t *misc) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    if (lane == 63) misc[kMiscWave + wave] = v;
+    __syncthreads();
+    uint32_t before = 0;
+    for (int w = 0; w < wave; ++w) before += misc[kMiscWave + w];
+    __syncthreads();
+    return v + before;
+}
+
+// The key of rank r (0-based, ascending) among band_key(cell_r(z)) of the non-NaN z of col[0 .. n).  Every thread returns it.
+__device__ uint64_t radix_select_col(const double *__restrict__ col, int n, uint32_t r, uint32_t *hist, uint32_t *misc) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t *my_hist = hist + wave * 256;
+    uint64_t prefix = 0, mask = 0;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        for (int i = threadIdx.x; i < kWaves * 256; i += kPointwiseThreads) hist[i] = 0;
+        __syncthreads();
+        for (int base = wave * 64; base < n; base += kPointwiseThreads) {
+            const int i = base + lane;
+            const double z = i < n ? col[i] : __builtin_nan("");
+            const uint64_t k = band_key(cell_r(z));
+            const bool take = !__builtin_isnan(z) && (k & mask) == prefix;
+            const uint32_t bin = (uint32_t)(k >> shift) & 255u;
+            const uint64_t act = __ballot(take);
+            if (act == 0) continue;
+            // the cells of an observation share their leading digits: a wavefront whose candidates all fall into one bin adds once
+            const int first = __builtin_ctzll(act);
+            const uint32_t bin0 = __shfl(bin, first, 64);
+            if (__ballot(take && bin == bin0) == act) {
+                if (lane == first) atomicAdd(&my_hist[bin0], (uint32_t)__popcll(act));
+            } else if (take) {
+                atomicAdd(&my_hist[bin], 1u);
+            }
+        }
+        __syncthreads();
+        uint32_t c = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) c += hist[w * 256 + threadIdx.x];
+        const uint32_t incl = block_inclusive_scan(c, misc);
+        const uint32_t excl = incl - c;
+        if (excl <= r && r < incl) {
+            misc[kMiscDigit] = threadIdx.x;
+            misc[kMiscRank] = r - excl;
+        }
+        __syncthreads();
+        prefix |= (uint64_t)misc[kMiscDigit] << shift;
+        mask |= (uint64_t)255 << shift;
+        r = misc[kMiscRank];
+        __syncthreads();
+    }
+    return prefix;
+}
+
+__global__ __launch_bounds__(kPointwiseThreads) void pointwise_select_kernel(const PointwiseColsArgs a) {
+    __shared__ uint32_t hist[kWaves * 256];
+    __shared__ uint32_t misc[kMiscWords];
+    __shared__ uint64_t keys[kPointwiseSortCap];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int n = (int)a.n;
+    const double *col = a.z + (size_t)j * (size_t)a.n;
+    double *out = a.obs + (size_t)j * MP_POINTWISE_N;
+    double *tail = a.tail ? a.tail + (size_t)j * (size_t)a.tail_stride : nullptr;
+    uint32_t c = 0;
+    for (int i = tid; i < n; i += kPointwiseThreads) c += !__builtin_isnan(col[i]);
+    const int m = (int)block_count(c, misc + kMiscWave);
+    const int tm = min(min(pointwise_tail_len(m), m), kPointwiseMaxTail);   // entries of the tail row (uniform over the workgroup)
+    if (m == 0) {
+        if (tid == 0) out[MP_POINTWISE_CUT] = __builtin_nan("");
+        if (tail)
+            for (int i = tid; i < a.tail_stride; i += kPointwiseThreads) tail[i] = __builtin_nan("");
+        return;
+    }
+    const uint64_t kc = radix_select_col(col, n, (uint32_t)(m - tm), hist, misc);
+    if (tid == 0) {
+        misc[kMiscCount] = 0;
+        out[MP_POINTWISE_CUT] = band_value(kc);
+    }
+    __syncthreads();
+    // the values above the cut, packed (in no particular order: they are sorted below); fewer than tm by the choice of the cut
+    for (int base = wave * 64; base < n; base += kPointwiseThreads) {
+        const int i = base + lane;
+        const double z = i < n ? col[i] : __builtin_nan("");
+        const uint64_t k = band_key(cell_r(z));
+        const bool keep = !__builtin_isnan(z) && k > kc;
+        const uint64_t act = __ballot(keep);
+        uint32_t at = 0;
+        if (lane == 0 && act) at = atomicAdd(&misc[kMiscCount], (uint32_t)__popcll(act));
+        at = __shfl(at, 0, 64);
+        const uint32_t slot = at + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
+        if (keep && slot < (uint32_t)tm) keys[slot] = k;
+    }
+    __syncthreads();
+    const int above = min((int)misc[kMiscCount], tm);
+    int slots = 1;                                          // the power of two that holds the tm entries
+    while (slots < tm) slots <<= 1;
+    for (int i = above + tid; i < slots; i += kPointwiseThreads) keys[i] = i < tm ? kc : ~0ull;   // copies of the cut, then padding that sorts last
+    __syncthreads();
+    for (int k = 2; k <= slots; k <<= 1)
+        for (int d = k >> 1; d > 0; d >>= 1) {
+            for (int i = tid; i < slots; i += kPointwiseThreads) {
+                const int l = i ^ d;
+                if (l > i) {
+                    const uint64_t x = keys[i], y = keys[l];
+                    if (((i & k) == 0) ? x > y : x < y) { keys[i] = y; keys[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    if (tail)
+        for (int i = tid; i < a.tail_stride; i += kPointwiseThreads) tail[i] = i < tm ? band_value(keys[i]) : __builtin_nan("");
+}
+
+__global__ __launch_bounds__(kPointwiseThreads) void pointwise_reduce_kernel(const PointwiseColsArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double shm[kWaves], shs[kWaves];
+    __shared__ uint32_t shc[kWaves];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const int n = (int)a.n;
+    const double *col = a.z + (size_t)j * (size_t)a.n;
+    double *out = a.obs + (size_t)j * MP_POINTWISE_N;
+    const double cut = out[MP_POINTWISE_CUT];               // the select kernel's (NaN: no used cell; nothing here writes it)
+    double sz = 0.0, sr = 0.0, rmin = INFINITY, rmax = -INFINITY, lm = -INFINITY, ls = 0.0, tm = -INFINITY, ts = 0.0;
+    uint32_t cnt = 0, nt = 0;
+    for (int i = tid; i < n; i += kPointwiseThreads) {
+        const double z = col[i];
+        if (__builtin_isnan(z)) continue;
+        const double r = cell_r(z);
+        ++cnt;
+        sz = sz + z;
+        sr = sr + r;
+        rmin = fmin(rmin, r);
+        rmax = fmax(rmax, r);
+        lse_add(lm, ls, -r);
+        if (r <= cut) {
+            ++nt;
+            lse_add(tm, ts, r);
+        }
+    }
+    const uint32_t m = block_count(cnt, shc);
+    const uint32_t nontail = block_count(nt, shc);
+    sz = block_sum(sz, shm);
+    sr = block_sum(sr, shm);
+    rmin = block_extreme<false>(rmin, shm);
+    rmax = block_extreme<true>(rmax, shm);
+    block_lse(lm, ls, shm, shs);
+    block_lse(tm, ts, shm, shs);
+    const double zmean = sz / (double)m, rmean = sr / (double)m;   // (0 / 0 = NaN without a used cell)
+    // second pass: squared deviations of ll = -r from its mean -rmean
+    const double mean_ll = -rmean;
+    double ss = 0.0;
+    for (int i = tid; i < n; i += kPointwiseThreads) {
+        const double z = col[i];
+        if (__builtin_isnan(z)) continue;
+        const double dev = -cell_r(z) - mean_ll;
+        const double sq = dev * dev;
+        ss = ss + sq;
+    }
+    ss = block_sum(ss, shm);
+    if (tid == 0) {
+        out[MP_POINTWISE_N_USED] = (double)m;
+        out[MP_POINTWISE_Z_MEAN] = zmean;
+        out[MP_POINTWISE_R_MEAN] = rmean;
+        out[MP_POINTWISE_LL_VAR] = m >= 2 ? ss / (double)(m - 1) : __builtin_nan("");
+        out[MP_POINTWISE_R_MIN] = m ? rmin : __builtin_nan("");
+        out[MP_POINTWISE_R_MAX] = m ? rmax : __builtin_nan("");
+        out[MP_POINTWISE_LPPD_M] = lm;
+        out[MP_POINTWISE_LPPD_S] = ls;
+        out[MP_POINTWISE_NONTAIL_COUNT] = (double)nontail;
+        out[MP_POINTWISE_NONTAIL_M] = tm;
+        out[MP_POINTWISE_NONTAIL_S] = ts;
+    }
+}
+
+}  // namespace
+
+int launch_pointwise_cells(const PointwiseCellsArgs &a, void *stream) {
+    const dim3 grid((unsigned)((a.d.n_obs + kPointwiseTile - 1) / kPointwiseTile), (unsigned)((a.cnt + kPointwiseTile - 1) / kPointwiseTile));
+    hipLaunchKernelGGL(pointwise_cells_kernel, grid, dim3(kPointwiseThreads), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int launch_pointwise_select(const PointwiseColsArgs &a, void *stream) {
+    hipLaunchKernelGGL(pointwise_select_kernel, dim3((unsigned)a.n_obs), dim3(kPointwiseThreads), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int launch_pointwise_reduce(const PointwiseColsArgs &a, void *stream) {
+    hipLaunchKernelGGL(pointwise_reduce_kernel, dim3((unsigned)a.n_obs), dim3(kPointwiseThreads), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace mp

@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi, derived, engine, posterior, tempering
+from . import _capi, derived, engine, pointwise, posterior, tempering
 from . import moves as _moves
 
 
@@ -61,6 +61,7 @@ class EnsembleSampler:
             raise ValueError("a dataset is required")
         for k, (dx, dy, de) in enumerate(datasets):
             self.handle.set_dataset(k, dx, dy, de)
+        self._times = [np.array(dx, dtype=np.float64) for dx, _, _ in datasets]   # (get_pointwise reports in the caller's order)
         self.betas = None if betas is None else tempering.check_ladder(betas)
         self.ntemps = 1 if self.betas is None else int(self.betas.size)
         self.ngroups = max(1, len(datasets))
@@ -208,10 +209,11 @@ class EnsembleSampler:
         return st["pos"], st["lnp"], st["acc"]
 
     # ---- emcee-shaped views (synth_mcmc.py:188-226 indexes chain[i, j, k], lnprobability[i, j])
-    def get_chain(self, temp=None):
+    def get_chain(self, temp=None, flat=False):
         """(nsteps, nwalkers_total, ndim); temp=t: the walkers at beta_t of every group, in group order
-        (nsteps, ngroups x nwalkers, ndim)."""
-        return self._at_temp(self._chain, temp)
+        (nsteps, ngroups x nwalkers, ndim).  flat=True (emcee's): the steps folded into the rows, (nsteps x walkers, ndim)."""
+        c = self._at_temp(self._chain, temp)
+        return c.reshape(-1, c.shape[-1]) if flat and c is not None else c
 
     def get_log_prob(self, temp=None):
         """(nsteps, nwalkers_total), untempered lnprob; temp=t: as in get_chain."""
@@ -302,6 +304,18 @@ class EnsembleSampler:
         rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
                               discard, thin, ensemble)
         return derived.result(self.handle, rows, q)
+
+    def get_pointwise(self, discard=0, thin=1, ensemble=0):
+        """Pointwise predictive scores over the stored chain: PSIS-LOO with its Pareto-k diagnostic and WAIC per observation
+        of group `ensemble`'s dataset, in the order the dataset was given, over the rows chain[discard::thin, ensemble's
+        walkers], evaluated and reduced on this sampler's handle (mp_model_pointwise).  Returns what synth.model_pointwise
+        returns.  The selection is capped like get_model_band's: thin a longer chain, or hand its rows to
+        synth.model_pointwise / mcmc_eqns.model_pointwise."""
+        if self._target != 0:
+            raise ValueError("get_pointwise needs the posterior target: a target='gaussian' sampler has no light curve")
+        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
+                              discard, thin, ensemble)
+        return pointwise.result(self.handle, rows, int(ensemble), x=self._times[int(ensemble)])
 
     def get_autocorr_time(self, c=5.0, tol=50, quiet=False, device=False):
         """emcee's default (quiet=False) raises when the chain is shorter than tol autocorrelation times; the

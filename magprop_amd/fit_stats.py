@@ -32,6 +32,22 @@ def aicc(ydata, ymod, yerr, Npars):
     return (-chisq + 2.0 * k) + (2.0 * k * (k + 1.0)) / (n - k - 1.0)
 
 
+def ppc_pvalue(lnlike, n_obs):
+    """Posterior-predictive p-value of the chi-square discrepancy, from the lnlike = -0.5 chi^2 of posterior samples (a
+    sampler's lnprobability under the flat prior).  Under the model a replicated dataset's chi^2 is exactly chi^2 with n_obs
+    degrees of freedom whatever the parameters are, so P(chi^2_rep >= chi^2_obs | sample) = chi2.sf(-2 lnlike, n_obs) and the
+    p-value is its mean over the samples (non-finite lnlike left out; none left: NaN).  Near 0: the model cannot reproduce
+    the data's scatter; near 1: the error bars are too generous."""
+    from scipy.stats import chi2
+    ll = np.asarray(lnlike, dtype=float).ravel()
+    ll = ll[np.isfinite(ll)]
+    if int(n_obs) < 1:
+        raise ValueError("n_obs must be at least 1")
+    if ll.size == 0:
+        return float("nan")
+    return float(np.mean(chi2.sf(-2.0 * ll, int(n_obs))))
+
+
 def fit_statistics(pars, x, y, yerr, variant="synth", GRBtype=None, device=-1):
     """{'chisq', 'redchisq', 'aicc', 'lnlike'} of sampler-coordinate `pars` against (x, y, yerr): the chi-square is the
     kernel's (-2 * lnlike); `pars` may be (n, ndim) for n parameter sets at once.  Failed models give inf."""

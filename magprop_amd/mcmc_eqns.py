@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from . import _capi, derived, engine
+from . import _capi, derived, engine, pointwise
 
 # Default prior box: the values of the reference's magnetar/mcmc_limits.csv:2-10 (rows B, P, log_MdiscI, log_RdiscI,
 # log_epsilon, log_delta, dipeff, propeff, f_beam), kept in code so that nothing depends on the working directory
@@ -113,3 +113,20 @@ def model_derived(samples, GRBtype, custom_lims=None, q=(0.16, 0.5, 0.84), weigh
     with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
         eng.set_prior(lo, hi, LIB_LOG_MASK)
         return derived.result(eng.handle, p, q, weights)
+
+
+def model_pointwise(samples, data, GRBtype, custom_lims=None, device=-1, cells=False):
+    """Pointwise predictive scores of the library model on the light curve ``data`` (columns t, Lum50, Lum50err): per
+    observation, in the order of data["t"], PSIS-LOO with its Pareto-k diagnostic and WAIC over the rows of `samples` (n, 6..9)
+    in the sampler coordinates of ``lnprob`` (equally weighted; up to pointwise.MAX_SAMPLES rows).  What
+    ``synth.model_pointwise`` returns; two models fitted to the same ``data`` (6 against 7 parameters, say) are held against
+    each other with pointwise.compare(a["loo"], b["loo"])."""
+    p = np.ascontiguousarray(samples, dtype=np.float64)
+    if p.ndim != 2 or not 6 <= p.shape[1] <= 9:
+        raise ValueError(f"samples must be 2-D (n, 6..9), got shape {p.shape}")
+    lo, hi = _bounds(p.shape[1], custom_lims)
+    x, y, yerr = _columns(data)
+    with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
+        slot = eng.dataset_slot(x, y, yerr)
+        eng.set_prior(lo, hi, LIB_LOG_MASK)
+        return pointwise.result(eng.handle, p, slot, x=x, cells=cells)

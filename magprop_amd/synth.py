@@ -6,7 +6,7 @@
 """
 import numpy as np
 
-from . import _capi, derived, engine
+from . import _capi, derived, engine, pointwise
 
 PRIOR_UPPER = np.array([10.0, 10.0, -2.0, np.log10(2000.0), 2.0, 3.0])   # :40
 PRIOR_LOWER = np.array([1.0e-3, 0.69, -6.0, np.log10(50.0), -2.0, -1.0])  # :41
@@ -105,6 +105,27 @@ def model_derived(samples, q=(0.16, 0.5, 0.84), weights=None, device=-1):
     try:
         eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
         res = derived.result(eng.handle, p, q, weights)
+    finally:
+        engine.release(eng)
+    return res
+
+
+def model_pointwise(samples, x, y, yerr, device=-1, cells=False):
+    """Pointwise predictive scores of the synthetic model on the light curve (x, y, yerr): per observation, in the order of x,
+    PSIS-LOO with its Pareto-k diagnostic and WAIC over the rows of `samples` (sampler coordinates, as a chain stores them;
+    equally weighted: resample a nested run's rows first; up to pointwise.MAX_SAMPLES rows).  The reductions over the samples
+    run on the device (mp_model_pointwise), the scores on the host (magprop_amd.pointwise).  Returns {"obs": (n_obs, 12) the
+    table of pointwise.NAMES, "tail", "status": (n,), "n_used": rows that finished, "loo": pointwise.psis_loo, "waic":
+    pointwise.waic, "summary": pointwise.summarize}; cells=True adds "z": (n_obs, n), the standardised residuals.  The
+    log-likelihood is the unnormalised lnlike term; pointwise.normalisation(yerr) per point normalises it."""
+    p = np.ascontiguousarray(samples, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 6:
+        raise ValueError(f"samples must be 2-D (n, 6), got shape {p.shape}")
+    eng = engine.acquire(_cfg(), None, device)
+    try:
+        slot = eng.dataset_slot(x, y, yerr)
+        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
+        res = pointwise.result(eng.handle, p, slot, x=engine._as_f64(x), cells=cells)
     finally:
         engine.release(eng)
     return res
