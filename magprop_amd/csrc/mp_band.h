@@ -19,7 +19,7 @@
 
 namespace mp {
 
-constexpr int kBandThreads = 256;   // one workgroup of the select kernel per (component, grid point)
+constexpr int kBandThreads = 256;   // one workgroup of the select kernel per (component, grid point) (mp_wg.h kWgThreads)
 constexpr int kBandTile = 64;       // transpose tiles: 64 walkers x 64 grid points
 
 // Order-preserving map of a (non-NaN) double to an unsigned key: negative values have every bit flipped, the others only the

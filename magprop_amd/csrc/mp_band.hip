@@ -9,17 +9,22 @@
 #include <hip/hip_runtime.h>
 
 #include "mp_band.h"
+#include "mp_wg.h"
 
 namespace mp {
 
 namespace {
 
-constexpr int kWaves = kBandThreads / 64;
-// dynamic LDS of the select kernel: [kWaves][256] u32 histograms | 16 u32 of broadcast words | keys[n] u64
-constexpr int kHistBytes = kWaves * 256 * 4;
-constexpr int kMiscWords = 16;
-constexpr int kKeysOffset = kHistBytes + kMiscWords * 4;   // 4 160: a multiple of 16
-enum { kMiscCount = 0, kMiscDigit = 1, kMiscRank = 2, kMiscLe = 3, kMiscWave = 4 /* .. 4 + kWaves */, kMiscMinLo = 8, kMiscMinHi = 9 };
+static_assert(kBandThreads == kWgThreads, "the select kernel is one workgroup of mp_wg.h");
+constexpr int kWaves = kWgWaves;
+// dynamic LDS of the select kernel: the select's words (spare: next_rank's count) | next_rank's minimum | keys[n] u64
+struct BandLds {
+    WgSelectLds sel;
+    unsigned long long above;
+    uint32_t pad[6];
+};
+constexpr int kKeysOffset = sizeof(BandLds);
+static_assert(kKeysOffset == 4160, "a multiple of 16, and what the cap of MP_BAND_MAX_SAMPLES keys was sized with");
 
 __global__ __launch_bounds__(kBandThreads) void band_transpose_kernel(const double *__restrict__ src, double *__restrict__ dst,
                                                                       int n, int n_grid) {
@@ -37,68 +42,8 @@ __global__ __launch_bounds__(kBandThreads) void band_transpose_kernel(const doub
     }
 }
 
-// Inclusive sum over the workgroup's 256 threads (one value each); every thread gets its own prefix.  misc[kMiscWave..] is
-// scratch.  Ends with a barrier.
-__device__ inline uint32_t block_inclusive_scan(uint32_t v, uint32_t *misc) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d, 64);
-        if (lane >= d) v += u;
-    }
-    if (lane == 63) misc[kMiscWave + wave] = v;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int w = 0; w < wave; ++w) before += misc[kMiscWave + w];
-    __syncthreads();
-    return v + before;
-}
-
-// The key of rank r (0-based) among keys[0 .. m).  Every thread returns it.
-__device__ uint64_t radix_select(const uint64_t *keys, int m, uint32_t r, uint32_t *hist, uint32_t *misc) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t *my_hist = hist + wave * 256;
-    uint64_t prefix = 0, mask = 0;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        for (int i = threadIdx.x; i < kWaves * 256; i += kBandThreads) hist[i] = 0;
-        __syncthreads();
-        for (int base = wave * 64; base < m; base += kBandThreads) {
-            const int i = base + lane;
-            const uint64_t k = i < m ? keys[i] : 0;
-            const bool take = i < m && (k & mask) == prefix;
-            const uint32_t bin = (uint32_t)(k >> shift) & 255u;
-            const uint64_t act = __ballot(take);
-            if (act == 0) continue;
-            // most walkers share the leading digits at a grid point: a wavefront whose candidates all fall into one bin adds once
-            const int first = __builtin_ctzll(act);
-            const uint32_t bin0 = __shfl(bin, first, 64);
-            if (__ballot(take && bin == bin0) == act) {
-                if (lane == first) atomicAdd(&my_hist[bin0], (uint32_t)__popcll(act));
-            } else if (take) {
-                atomicAdd(&my_hist[bin], 1u);
-            }
-        }
-        __syncthreads();
-        uint32_t c = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) c += hist[w * 256 + threadIdx.x];
-        const uint32_t incl = block_inclusive_scan(c, misc);
-        const uint32_t excl = incl - c;
-        if (excl <= r && r < incl) {
-            misc[kMiscDigit] = threadIdx.x;
-            misc[kMiscRank] = r - excl;
-        }
-        __syncthreads();
-        prefix |= (uint64_t)misc[kMiscDigit] << shift;
-        mask |= (uint64_t)255 << shift;
-        r = misc[kMiscRank];
-        __syncthreads();
-    }
-    return prefix;
-}
-
 // The key of rank lo + 1, given the key a of rank lo: a itself if more than lo + 1 keys are <= a, else the least key above a.
-__device__ uint64_t next_rank(const uint64_t *keys, int m, int lo, uint64_t a, uint32_t *misc) {
+__device__ uint64_t next_rank(const uint64_t *keys, int m, int lo, uint64_t a, BandLds &s) {
     uint32_t le = 0;
     uint64_t above = ~0ull;
     for (int i = threadIdx.x; i < m; i += kBandThreads) {
@@ -111,16 +56,15 @@ __device__ uint64_t next_rank(const uint64_t *keys, int m, int lo, uint64_t a, u
         const uint64_t o = __shfl_xor(above, d, 64);
         above = o < above ? o : above;
     }
-    if (threadIdx.x == 0) { misc[kMiscLe] = 0; misc[kMiscMinLo] = ~0u; misc[kMiscMinHi] = ~0u; }
+    if (threadIdx.x == 0) { s.sel.spare = 0; s.above = ~0ull; }
     __syncthreads();
-    unsigned long long *mn = reinterpret_cast<unsigned long long *>(misc + kMiscMinLo);
     if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&misc[kMiscLe], le);
-        atomicMin(mn, (unsigned long long)above);
+        atomicAdd(&s.sel.spare, le);
+        atomicMin(&s.above, (unsigned long long)above);
     }
     __syncthreads();
-    const uint32_t cnt = misc[kMiscLe];
-    const uint64_t res = cnt > (uint32_t)(lo + 1) ? a : (uint64_t)*mn;
+    const uint32_t cnt = s.sel.spare;
+    const uint64_t res = cnt > (uint32_t)(lo + 1) ? a : (uint64_t)s.above;
     __syncthreads();
     return res;
 }
@@ -128,27 +72,24 @@ __device__ uint64_t next_rank(const uint64_t *keys, int m, int lo, uint64_t a, u
 __global__ __launch_bounds__(kBandThreads) void band_select_kernel(const double *__restrict__ cols, int n, int n_grid, const BandQ q,
                                                                    double *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t *hist = reinterpret_cast<uint32_t *>(smem);
-    uint32_t *misc = reinterpret_cast<uint32_t *>(smem + kHistBytes);
+    BandLds &s = *reinterpret_cast<BandLds *>(smem);
     uint64_t *keys = reinterpret_cast<uint64_t *>(smem + kKeysOffset);
     const int g = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const double *col = cols + (size_t)g * n;
-    if (threadIdx.x == 0) misc[kMiscCount] = 0;
+    if (threadIdx.x == 0) s.sel.count = 0;
     __syncthreads();
     // keys of the non-NaN values, packed (in no particular order: the order statistics do not depend on it)
     for (int base = wave * 64; base < n; base += kBandThreads) {
         const int i = base + lane;
         const double v = i < n ? col[i] : 0.0;
         const bool keep = i < n && !__builtin_isnan(v);
-        const uint64_t act = __ballot(keep);
-        uint32_t at = 0;
-        if (lane == 0 && act) at = atomicAdd(&misc[kMiscCount], (uint32_t)__popcll(act));
-        at = __shfl(at, 0, 64);
-        if (keep) keys[at + __popcll(act & ((1ull << lane) - 1ull))] = band_key(v);
+        const uint64_t k = band_key(v);                 // (ahead of the packing step: the select loop below keeps its place in the code)
+        const uint32_t slot = wave_pack_slot(keep, &s.sel.count);
+        if (keep) keys[slot] = k;
     }
     __syncthreads();
-    const int m = (int)misc[kMiscCount];
+    const int m = (int)s.sel.count;
     __syncthreads();
     for (int j = 0; j < q.nq; ++j) {
         double res;
@@ -156,8 +97,8 @@ __global__ __launch_bounds__(kBandThreads) void band_select_kernel(const double 
             res = __builtin_nan("");
         } else {
             const BandRank rk = band_rank(m, q.q[j]);
-            const uint64_t ka = radix_select(keys, m, (uint32_t)rk.lo, hist, misc);
-            const uint64_t kb = rk.hi == rk.lo ? ka : next_rank(keys, m, rk.lo, ka, misc);
+            const uint64_t ka = wg_radix_select(m, (uint32_t)rk.lo, s.sel, [keys](int i, uint64_t &k) { k = keys[i]; return true; });
+            const uint64_t kb = rk.hi == rk.lo ? ka : next_rank(keys, m, rk.lo, ka, s);
             res = band_lerp(band_value(ka), band_value(kb), rk.gamma);
         }
         if (threadIdx.x == 0) out[(size_t)j * n_grid + g] = res;

@@ -387,6 +387,75 @@ static Evaluator *evaluator_create(const mp_model_cfg *cfg, const double *tgrid,
     return ev;
 }
 
+// ---------------------------------------------------------------- the curve pass
+// What mp_model_lc, mp_model_band, mp_model_derived and mp_model_pointwise share: the curves of host rows pars[n][ndim], built on
+// the device chunk by chunk and handed to the caller's own kernels and copies.  (The caller holds the evaluator, has validated its
+// arguments and has ensured its own workspaces.)
+// a set of curves: bit i is curve i of Ltot, Lprop, Ldip, Mdisc, omega
+constexpr uint32_t kCurveLtot = 1u, kCurveLprop = 2u, kCurveLdip = 4u, kCurveAll = 31u;
+
+struct CurveChunk {
+    size_t lo, cnt;          // rows [lo, lo + cnt) of the pass
+    double *curve[5];        // [cnt][n_grid] each, in the order of the set's bits; nullptr: not wanted.  The wanted ones lie
+                             // one behind the other, a chunk size of rows apart; rows of walkers that did not finish are
+                             // NaN-filled by the kernel
+    const int32_t *status;   // [cnt] on the device
+    hipStream_t st;
+};
+
+// (everything that enqueues: curve_pass synchronises behind it whatever it returns)
+template <class Consume>
+static int curve_pass_enqueue(Evaluator *ev, const double *pars, size_t n, int ndim, int physical, uint32_t curves, size_t chunk,
+                              std::vector<int32_t> &stt, Consume &consume) {
+    const size_t ng = ev->tgrid.size(), rows = chunk * ng;
+    hipStream_t st = ev->stream;
+    HIP_TRY(hipMemcpyAsync(ev->w_pars.p, pars, sizeof(double) * n * (size_t)ndim, hipMemcpyHostToDevice, st));
+    for (size_t lo = 0; lo < n; lo += chunk) {
+        CurveChunk c{lo, std::min(chunk, n - lo), {}, ev->w_status.p + lo, st};
+        for (int i = 0, k = 0; i < 5; ++i)
+            if (curves & (1u << i)) c.curve[i] = ev->w_curves.p + (size_t)k++ * rows;
+        mp::LaunchArgs a{};
+        a.pars = ev->w_pars.p + lo * (size_t)ndim;
+        a.n = (int32_t)c.cnt;
+        a.ndim = ndim;
+        a.physical = physical ? 1 : 0;
+        a.want_chi2 = 0;                          // curves only: no dataset needed
+        a.lnprob = ev->w_lnprob.p;
+        a.status = ev->w_status.p + lo;
+        a.ltot = c.curve[0];
+        a.lprop = c.curve[1];
+        a.ldip = c.curve[2];
+        a.mdisc = c.curve[3];
+        a.omega = c.curve[4];
+        int rc;
+        if ((rc = launch_lnprob_ordered(ev, a, st)) || (rc = consume(c))) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(stt.data(), ev->w_status.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    return MP_OK;
+}
+
+// Uploads the rows once; per chunk of `chunk` rows, in stream order: the curve launch (curves: which of the five), then whatever
+// consume(chunk) enqueues -- it returns MP_OK or the code of a failure it has reported; at the end the statuses of all rows, one
+// synchronise, status_out (may be NULL) and the number of rows that finished.  Every failure behind the first enqueue
+// synchronises the stream before it returns, so that nothing still writes the caller's buffers.
+template <class Consume>
+static int curve_pass(Evaluator *ev, const double *pars, size_t n, int ndim, int physical, uint32_t curves, size_t chunk,
+                      int32_t *status_out, int64_t *n_used, Consume consume) {
+    int rc;
+    if ((rc = ev->w_pars.ensure(n * (size_t)ndim)) || (rc = ev->w_lnprob.ensure(chunk)) || (rc = ev->w_status.ensure(n)) ||
+        (rc = ev->w_curves.ensure((size_t)__builtin_popcount(curves) * chunk * ev->tgrid.size())))
+        return rc;
+    std::vector<int32_t> stt(n);
+    if ((rc = curve_pass_enqueue(ev, pars, n, ndim, physical, curves, chunk, stt, consume))) {
+        (void)hipStreamSynchronize(ev->stream);
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(ev->stream));
+    if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * n);
+    if (n_used) *n_used = (int64_t)std::count(stt.begin(), stt.end(), (int32_t)MP_STATUS_OK);
+    return MP_OK;
+}
+
 extern "C" {
 
 int mp_abi_version(void) { return MP_ABI_VERSION; }
@@ -646,36 +715,17 @@ int mp_model_lc(mp_handle *h, const double *pars, int ndim, double *out, double 
     Evaluator *ev = h->first();   // one walker, one device: the first
     Held held(h, ev);
     const size_t ng = ev->tgrid.size();
-    int rc;
-    if ((rc = ev->w_pars.ensure(MP_MAX_NDIM)) || (rc = ev->w_lnprob.ensure(1)) || (rc = ev->w_status.ensure(1)) ||
-        (rc = ev->w_curves.ensure(5 * ng)))
-        return rc;
-    hipStream_t st = ev->stream;
-    HIP_TRY(hipMemcpyAsync(ev->w_pars.p, pars, sizeof(double) * (size_t)ndim, hipMemcpyHostToDevice, st));
-    mp::LaunchArgs a{};
-    a.pars = ev->w_pars.p;
-    a.n = 1;
-    a.ndim = ndim;
-    a.physical = 1;
-    a.want_chi2 = 0;
-    a.lnprob = ev->w_lnprob.p;
-    a.status = ev->w_status.p;
-    a.ltot = ev->w_curves.p;
-    a.lprop = ev->w_curves.p + ng;
-    a.ldip = ev->w_curves.p + 2 * ng;
-    a.mdisc = ev->w_curves.p + 3 * ng;
-    a.omega = ev->w_curves.p + 4 * ng;
-    if ((rc = launch_lnprob_ordered(ev, a, st))) return rc;
-    int32_t stt = 0;
-    std::memcpy(out, ev->tgrid.data(), sizeof(double) * ng);
-    HIP_TRY(hipMemcpyAsync(out + ng, ev->w_curves.p, sizeof(double) * 3 * ng, hipMemcpyDeviceToHost, st));
-    if (traj) HIP_TRY(hipMemcpyAsync(traj, ev->w_curves.p + 3 * ng, sizeof(double) * 2 * ng, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&stt, ev->w_status.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (status) *status = stt;
-    return MP_OK;
+    return curve_pass(ev, pars, 1, ndim, 1, kCurveAll, 1, status, nullptr, [&](const CurveChunk &c) {
+        std::memcpy(out, ev->tgrid.data(), sizeof(double) * ng);
+        // (a chunk of one row: its five curves are one block)
+        HIP_TRY(hipMemcpyAsync(out + ng, c.curve[0], sizeof(double) * 3 * ng, hipMemcpyDeviceToHost, c.st));
+        if (traj) HIP_TRY(hipMemcpyAsync(traj, c.curve[3], sizeof(double) * 2 * ng, hipMemcpyDeviceToHost, c.st));
+        return (int)MP_OK;
+    });
 }
 
+// One launch of all n rows (the curve build kernel_spl_curves names depends on the launch size), then per component a transpose
+// into point-major columns and the select.
 int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physical, const double *q, int nq, uint32_t components,
                   double *band_out, int32_t *status_out, int32_t *n_used) {
     if (!h || !pars || !q || !band_out) return fail(MP_EINVAL, "mp_model_band: NULL argument");
@@ -684,51 +734,32 @@ int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physica
     if (nq < 1 || nq > MP_BAND_MAX_Q) return fail(MP_EINVAL, "mp_model_band: nq must be 1..%d (MP_BAND_MAX_Q), got %d", MP_BAND_MAX_Q, nq);
     for (int j = 0; j < nq; ++j)
         if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(MP_EINVAL, "mp_model_band: q[%d] = %g is not in [0, 1]", j, q[j]);
+    static_assert(MP_BAND_LTOT == kCurveLtot && MP_BAND_LPROP == kCurveLprop && MP_BAND_LDIP == kCurveLdip, "a component mask is a curve set");
     const uint32_t all = MP_BAND_LTOT | MP_BAND_LPROP | MP_BAND_LDIP;
     if (components == 0 || (components & ~all)) return fail(MP_EINVAL, "mp_model_band: components 0x%x is not a non-empty mask of MP_BAND_*", components);
     Evaluator *ev = h->first();
     Held held(h, ev);
-    const size_t ng = ev->tgrid.size(), rows = (size_t)n * ng;
+    const size_t ng = ev->tgrid.size();
     const int ncomp = __builtin_popcount(components);
     int rc;
-    if ((rc = ev->w_pars.ensure((size_t)n * ndim)) || (rc = ev->w_lnprob.ensure((size_t)n)) || (rc = ev->w_status.ensure((size_t)n)) ||
-        (rc = ev->w_band.ensure(rows * (size_t)(ncomp + 1))) || (rc = ev->w_band_out.ensure((size_t)ncomp * nq * ng)))
-        return rc;
-    hipStream_t st = ev->stream;
-    HIP_TRY(hipMemcpyAsync(ev->w_pars.p, pars, sizeof(double) * (size_t)n * ndim, hipMemcpyHostToDevice, st));
-    mp::LaunchArgs a{};
-    a.pars = ev->w_pars.p;
-    a.n = n;
-    a.ndim = ndim;
-    a.physical = physical ? 1 : 0;
-    a.want_chi2 = 0;                          // curves only: no dataset needed
-    a.lnprob = ev->w_lnprob.p;
-    a.status = ev->w_status.p;
-    double *curve[3] = {nullptr, nullptr, nullptr};
-    for (int c = 0, k = 0; c < 3; ++c)
-        if (components & (1u << c)) curve[c] = ev->w_band.p + (size_t)k++ * rows;
-    a.ltot = curve[0];                        // rows of walkers that did not finish are NaN-filled by the kernel
-    a.lprop = curve[1];
-    a.ldip = curve[2];
-    if ((rc = launch_lnprob_ordered(ev, a, st))) return rc;
+    if ((rc = ev->w_band.ensure((size_t)n * ng)) || (rc = ev->w_band_out.ensure((size_t)ncomp * nq * ng))) return rc;
     mp::BandQ bq{};
     for (int j = 0; j < nq; ++j) bq.q[j] = q[j];
     bq.nq = nq;
-    double *cols = ev->w_band.p + (size_t)ncomp * rows;
-    for (int c = 0, k = 0; c < 3; ++c) {
-        if (!curve[c]) continue;
-        int e = mp::launch_band_transpose(curve[c], cols, n, (int)ng, (void *)st);
-        if (!e) e = mp::launch_band_select(cols, n, (int)ng, bq, ev->w_band_out.p + (size_t)k * nq * ng, (void *)st);
-        if (e) return fail(MP_EHIP, "band kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        ++k;
-    }
-    std::vector<int32_t> stt((size_t)n);
-    HIP_TRY(hipMemcpyAsync(band_out, ev->w_band_out.p, sizeof(double) * (size_t)ncomp * nq * ng, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(stt.data(), ev->w_status.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * (size_t)n);
-    if (n_used) *n_used = (int32_t)std::count(stt.begin(), stt.end(), (int32_t)MP_STATUS_OK);
-    return MP_OK;
+    int64_t used = 0;
+    rc = curve_pass(ev, pars, (size_t)n, ndim, physical, components, (size_t)n, status_out, &used, [&](const CurveChunk &c) {
+        for (int i = 0, k = 0; i < 3; ++i) {
+            if (!c.curve[i]) continue;
+            int e = mp::launch_band_transpose(c.curve[i], ev->w_band.p, n, (int)ng, (void *)c.st);
+            if (!e) e = mp::launch_band_select(ev->w_band.p, n, (int)ng, bq, ev->w_band_out.p + (size_t)k * nq * ng, (void *)c.st);
+            if (e) return fail(MP_EHIP, "band kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+            ++k;
+        }
+        HIP_TRY(hipMemcpyAsync(band_out, ev->w_band_out.p, sizeof(double) * (size_t)ncomp * nq * ng, hipMemcpyDeviceToHost, c.st));
+        return (int)MP_OK;
+    });
+    if (!rc && n_used) *n_used = (int32_t)used;
+    return rc;
 }
 
 // The rows go through the device in chunks of n_simd rows: five curves of a chunk are the workspace, and every chunk runs the
@@ -741,53 +772,23 @@ int mp_model_derived(mp_handle *h, const double *pars, int64_t n, int ndim, int 
     if (!h || !pars || !out) return fail(MP_EINVAL, "mp_model_derived: NULL argument");
     Evaluator *ev = h->first();
     Held held(h, ev);
-    const size_t ng = ev->tgrid.size(), nn = (size_t)n;
-    const size_t chunk = (size_t)std::min<int64_t>(n, std::max(1, ev->sh.n_simd)), rows = chunk * ng;
+    const size_t chunk = (size_t)std::min<int64_t>(n, std::max(1, ev->sh.n_simd));
     int rc;
-    if ((rc = ev->w_pars.ensure(nn * (size_t)ndim)) || (rc = ev->w_lnprob.ensure(chunk)) || (rc = ev->w_status.ensure(nn)) ||
-        (rc = ev->w_derive.ensure(5 * rows)) || (rc = ev->w_derive_out.ensure(chunk * MP_DERIVED_N)))
-        return rc;
-    hipStream_t st = ev->stream;
-    HIP_TRY(hipMemcpyAsync(ev->w_pars.p, pars, sizeof(double) * nn * (size_t)ndim, hipMemcpyHostToDevice, st));
-    std::vector<int32_t> stt(nn);
-    int first_rc = MP_OK;
-    for (size_t lo = 0; lo < nn && !first_rc; lo += chunk) {
-        const size_t cnt = std::min(chunk, nn - lo);
-        mp::LaunchArgs a{};
-        a.pars = ev->w_pars.p + lo * (size_t)ndim;
-        a.n = (int32_t)cnt;
-        a.ndim = ndim;
-        a.physical = physical ? 1 : 0;
-        a.want_chi2 = 0;                          // curves only: no dataset needed
-        a.lnprob = ev->w_lnprob.p;
-        a.status = ev->w_status.p + lo;
-        a.ltot = ev->w_derive.p;                  // rows of walkers that did not finish are NaN-filled by the kernel
-        a.lprop = ev->w_derive.p + rows;
-        a.ldip = ev->w_derive.p + 2 * rows;
-        a.mdisc = ev->w_derive.p + 3 * rows;
-        a.omega = ev->w_derive.p + 4 * rows;
-        if ((first_rc = launch_lnprob_ordered(ev, a, st))) break;
+    if ((rc = ev->w_derive_out.ensure(chunk * MP_DERIVED_N))) return rc;
+    return curve_pass(ev, pars, (size_t)n, ndim, physical, kCurveAll, chunk, status_out, n_used, [&](const CurveChunk &c) {
         mp::DeriveArgs d{};
-        d.curve[0] = a.ltot; d.curve[1] = a.lprop; d.curve[2] = a.ldip; d.curve[3] = a.mdisc; d.curve[4] = a.omega;
-        d.status = a.status;
+        for (int i = 0; i < 5; ++i) d.curve[i] = c.curve[i];
+        d.status = c.status;
         d.tgrid = ev->d_tgrid.p;
         d.out = ev->w_derive_out.p;
-        d.n = (int32_t)cnt;
-        d.n_grid = (int32_t)ng;
-        const int e = mp::launch_derive(d, (void *)st);
-        if (e) { first_rc = fail(MP_EHIP, "derive kernel launch failed: %s", hipGetErrorString((hipError_t)e)); break; }
-        hipError_t ce = hipMemcpyAsync(out + lo * MP_DERIVED_N, ev->w_derive_out.p, sizeof(double) * cnt * MP_DERIVED_N, hipMemcpyDeviceToHost, st);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(stt.data() + lo, ev->w_status.p + lo, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st);
-        if (ce != hipSuccess) first_rc = fail(MP_EHIP, "mp_model_derived: copy failed: %s", hipGetErrorString(ce));
-    }
-    if (first_rc) {
-        (void)hipStreamSynchronize(st);           // nothing may still write the caller's buffers
-        return first_rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * nn);
-    if (n_used) *n_used = (int64_t)std::count(stt.begin(), stt.end(), (int32_t)MP_STATUS_OK);
-    return MP_OK;
+        d.n = (int32_t)c.cnt;
+        d.n_grid = (int32_t)ev->tgrid.size();
+        const int e = mp::launch_derive(d, (void *)c.st);
+        if (e) return fail(MP_EHIP, "derive kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        const hipError_t ce = hipMemcpyAsync(out + c.lo * MP_DERIVED_N, ev->w_derive_out.p, sizeof(double) * c.cnt * MP_DERIVED_N, hipMemcpyDeviceToHost, c.st);
+        if (ce != hipSuccess) return fail(MP_EHIP, "mp_model_derived: copy failed: %s", hipGetErrorString(ce));
+        return (int)MP_OK;
+    });
 }
 
 int mp_pointwise_tail_len(int64_t n_used) { return mp::pointwise_tail_len(n_used); }
@@ -807,48 +808,31 @@ int mp_model_pointwise(mp_handle *h, const double *pars, int64_t n, int ndim, in
     Held held(h, ev);
     if (!ev->ds[ds_id].set) return fail(MP_ESTATE, "mp_model_pointwise: refers to unset dataset %d", ds_id);
     const mp::DsDesc &dd = ev->desc[(size_t)ds_id];
-    const size_t ng = ev->tgrid.size(), nn = (size_t)n, n_obs = (size_t)dd.n_obs;
+    const size_t nn = (size_t)n, n_obs = (size_t)dd.n_obs;
     if ((int64_t)nn * (int64_t)n_obs > (int64_t)MP_POINTWISE_MAX_CELLS)
         return fail(MP_EINVAL, "mp_model_pointwise: n * n_obs = %lld * %d exceeds MP_POINTWISE_MAX_CELLS = %lld", (long long)n, dd.n_obs,
                     (long long)MP_POINTWISE_MAX_CELLS);
     const size_t chunk = (size_t)std::min<int64_t>(n, std::max(1, ev->sh.n_simd));
     const size_t tlen = (size_t)mp::pointwise_tail_len(n);
     int rc;
-    if ((rc = ev->w_pars.ensure(nn * (size_t)ndim)) || (rc = ev->w_lnprob.ensure(chunk)) || (rc = ev->w_status.ensure(nn)) ||
-        (rc = ev->w_pw_ltot.ensure(chunk * ng)) || (rc = ev->w_pw_z.ensure(n_obs * nn)) ||
-        (rc = ev->w_pw_obs.ensure(n_obs * MP_POINTWISE_N)) || (rc = ev->w_pw_tail.ensure(n_obs * tlen)))
+    if ((rc = ev->w_pw_z.ensure(n_obs * nn)) || (rc = ev->w_pw_obs.ensure(n_obs * MP_POINTWISE_N)) || (rc = ev->w_pw_tail.ensure(n_obs * tlen)))
         return rc;
-    hipStream_t st = ev->stream;
-    HIP_TRY(hipMemcpyAsync(ev->w_pars.p, pars, sizeof(double) * nn * (size_t)ndim, hipMemcpyHostToDevice, st));
     const mp::PointwiseData pd{ev->d_obs_g.p + dd.obs_off, ev->d_obs_dx.p + dd.obs_off, ev->d_obs_idt.p + dd.obs_off,
                                ev->d_obs_y.p + dd.obs_off, ev->d_obs_yerr.p + dd.obs_off, dd.n_obs};
-    int first_rc = MP_OK;
-    for (size_t lo = 0; lo < nn && !first_rc; lo += chunk) {
-        const size_t cnt = std::min(chunk, nn - lo);
-        mp::LaunchArgs a{};
-        a.pars = ev->w_pars.p + lo * (size_t)ndim;
-        a.n = (int32_t)cnt;
-        a.ndim = ndim;
-        a.physical = physical ? 1 : 0;
-        a.want_chi2 = 0;                          // the curve only: the cells are formed from it behind the launch
-        a.lnprob = ev->w_lnprob.p;
-        a.status = ev->w_status.p + lo;
-        a.ltot = ev->w_pw_ltot.p;                 // rows of walkers that did not finish are NaN-filled by the kernel (and not read)
-        if ((first_rc = launch_lnprob_ordered(ev, a, st))) break;
+    return curve_pass(ev, pars, nn, ndim, physical, kCurveLtot, chunk, status_out, n_used, [&](const CurveChunk &k) {
         mp::PointwiseCellsArgs c{};
-        c.ltot = a.ltot;
-        c.status = a.status;
+        c.ltot = k.curve[0];                      // (the rows of walkers that did not finish are not read)
+        c.status = k.status;
         c.d = pd;
         c.z = ev->w_pw_z.p;
         c.n = n;
-        c.lo = (int64_t)lo;
-        c.cnt = (int32_t)cnt;
-        c.n_grid = (int32_t)ng;
-        const int e = mp::launch_pointwise_cells(c, (void *)st);
-        if (e) first_rc = fail(MP_EHIP, "pointwise cells kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    std::vector<int32_t> stt(nn);
-    if (!first_rc) {
+        c.lo = (int64_t)k.lo;
+        c.cnt = (int32_t)k.cnt;
+        c.n_grid = (int32_t)ev->tgrid.size();
+        int e = mp::launch_pointwise_cells(c, (void *)k.st);
+        if (e) return fail(MP_EHIP, "pointwise cells kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        if (k.lo + k.cnt < nn) return (int)MP_OK;
+        // behind the last chunk
         mp::PointwiseColsArgs r{};
         r.z = ev->w_pw_z.p;
         r.obs = ev->w_pw_obs.p;
@@ -856,25 +840,15 @@ int mp_model_pointwise(mp_handle *h, const double *pars, int64_t n, int ndim, in
         r.n = n;
         r.n_obs = dd.n_obs;
         r.tail_stride = (int32_t)tlen;
-        int e = mp::launch_pointwise_select(r, (void *)st);
-        if (!e) e = mp::launch_pointwise_reduce(r, (void *)st);
-        if (e) first_rc = fail(MP_EHIP, "pointwise reduction kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    if (!first_rc) {
-        hipError_t ce = hipMemcpyAsync(obs_out, ev->w_pw_obs.p, sizeof(double) * n_obs * MP_POINTWISE_N, hipMemcpyDeviceToHost, st);
-        if (ce == hipSuccess && tail_out) ce = hipMemcpyAsync(tail_out, ev->w_pw_tail.p, sizeof(double) * n_obs * tlen, hipMemcpyDeviceToHost, st);
-        if (ce == hipSuccess && z_out) ce = hipMemcpyAsync(z_out, ev->w_pw_z.p, sizeof(double) * n_obs * nn, hipMemcpyDeviceToHost, st);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(stt.data(), ev->w_status.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, st);
-        if (ce != hipSuccess) first_rc = fail(MP_EHIP, "mp_model_pointwise: copy failed: %s", hipGetErrorString(ce));
-    }
-    if (first_rc) {
-        (void)hipStreamSynchronize(st);           // nothing may still write the caller's buffers
-        return first_rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * nn);
-    if (n_used) *n_used = (int64_t)std::count(stt.begin(), stt.end(), (int32_t)MP_STATUS_OK);
-    return MP_OK;
+        e = mp::launch_pointwise_select(r, (void *)k.st);
+        if (!e) e = mp::launch_pointwise_reduce(r, (void *)k.st);
+        if (e) return fail(MP_EHIP, "pointwise reduction kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        hipError_t ce = hipMemcpyAsync(obs_out, ev->w_pw_obs.p, sizeof(double) * n_obs * MP_POINTWISE_N, hipMemcpyDeviceToHost, k.st);
+        if (ce == hipSuccess && tail_out) ce = hipMemcpyAsync(tail_out, ev->w_pw_tail.p, sizeof(double) * n_obs * tlen, hipMemcpyDeviceToHost, k.st);
+        if (ce == hipSuccess && z_out) ce = hipMemcpyAsync(z_out, ev->w_pw_z.p, sizeof(double) * n_obs * nn, hipMemcpyDeviceToHost, k.st);
+        if (ce != hipSuccess) return fail(MP_EHIP, "mp_model_pointwise: copy failed: %s", hipGetErrorString(ce));
+        return (int)MP_OK;
+    });
 }
 
 int mp_rhs_batch(mp_handle *h, const double *pars, int ndim, const double *t, const double *y, int n, double *dydt,

@@ -7,7 +7,8 @@
 // G - 1)) (the last ones may be short or empty).  Inside a segment the terms 0.5 * dt_i * (L_i + L_{i+1}) are added in increasing
 // i from 0.0; the 256 segment totals are added in segment order from 0.0 (an empty segment adds 0.0).  The cumulative energy up
 // to t_{i+1} is the total of the segments before i's plus the running sum of its segment.  Every product and sum rounds on its
-// own: no FMA contraction, no floating-point atomic.  tests/derive_restated.py is the same order in numpy.
+// own: no FMA contraction, no floating-point atomic.  A maximum is the first largest value: every segment's in increasing i, then
+// the segments' under wg_best of mp_wg.h (larger value, then lower index).  tests/derive_restated.py is the same order in numpy.
 #pragma once
 #include <stdint.h>
 
@@ -21,7 +22,7 @@
 
 namespace mp {
 
-constexpr int kDeriveThreads = 256;   // one workgroup per row; thread k walks segment k
+constexpr int kDeriveThreads = 256;   // one workgroup per row; thread k walks segment k (mp_wg.h kWgThreads)
 constexpr int kDeriveWindow = 14;     // intervals of every segment staged in LDS at a time (15 points: an odd stride in doubles)
 
 // intervals per segment

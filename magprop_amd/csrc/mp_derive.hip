@@ -15,6 +15,7 @@
 #include <climits>
 
 #include "mp_derive.h"
+#include "mp_wg.h"
 
 namespace mp {
 
@@ -22,47 +23,9 @@ namespace {
 
 constexpr int kStride = kDeriveWindow + 1;              // points of a segment's window, and its LDS stride in doubles
 constexpr int kSlots = kDeriveThreads * kStride;
-constexpr int kWaves = kDeriveThreads / 64;
-
-struct Best {
-    double v;
-    int i;
-};
-
-__device__ inline bool better(double av, int ai, double bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
-// the best of the workgroup's candidates (i = INT_MAX: none), returned to every thread; ends with a barrier
-__device__ Best block_best(Best b, double *rv, int *ri) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double ov = __shfl_xor(b.v, d, 64);
-        const int oi = __shfl_xor(b.i, d, 64);
-        if (better(ov, oi, b.v, b.i)) { b.v = ov; b.i = oi; }
-    }
-    if (lane == 0) { rv[wave] = b.v; ri[wave] = b.i; }
-    __syncthreads();
-    Best r{rv[0], ri[0]};
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w)
-        if (better(rv[w], ri[w], r.v, r.i)) { r.v = rv[w]; r.i = ri[w]; }
-    __syncthreads();
-    return r;
-}
-
-// the least of the workgroup's indices, returned to every thread; ends with a barrier
-__device__ int block_min(int v, int *ri) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    if (lane == 0) ri[wave] = v;
-    __syncthreads();
-    int r = ri[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) r = min(r, ri[w]);
-    __syncthreads();
-    return r;
-}
+static_assert(kDeriveThreads == kWgThreads, "derive_kernel is one workgroup of mp_wg.h");
+constexpr int kWaves = kWgWaves;
+using Best = WgBest;   // every thread's best in increasing index, then wg_best's total order (larger value, then lower index)
 
 // window c of every segment of src[0 .. G) into dst[k * kStride + r]: point k seg + c W + r for r <= the window's intervals
 __device__ inline void stage(const double *__restrict__ src, double *dst, int G, int seg, int c) {
@@ -151,7 +114,7 @@ __global__ __launch_bounds__(kDeriveThreads) void derive_kernel(const DeriveArgs
     // Ltot: segment sums and peak
     walk<true, true, false>(ltot, t, G, seg, lc, lt, s, b, 0.0, nullptr, nullptr);
     tot[tid] = s;
-    b = block_best(b, rv, ri);                 // (its barriers order tot[] too)
+    b = wg_best(b, rv, ri);                 // (its barriers order tot[] too)
     if (tid == 0) {
         double e = 0.0;
         for (int k = 0; k < kDeriveThreads; ++k) { const double v = tot[k]; tot[k] = e; e = e + v; }
@@ -166,7 +129,7 @@ __global__ __launch_bounds__(kDeriveThreads) void derive_kernel(const DeriveArgs
         const double thr[3] = {0.1 * e, 0.5 * e, 0.9 * e};
         walk<false, false, true>(ltot, t, G, seg, lc, lt, s, b, tot[tid], thr, cross);
         for (int f = 0; f < 3; ++f) {
-            int i = block_min(cross[f], ri);
+            int i = wg_least(cross[f], ri);
             if (i == INT_MAX) i = G - 2;       // never reached (a negative total): the last grid time
             if (e == 0.0) i = 0;
             if (tid == 0) res[MP_DERIVED_T10 + f] = t[i + 1];
@@ -175,7 +138,7 @@ __global__ __launch_bounds__(kDeriveThreads) void derive_kernel(const DeriveArgs
     // Lprop: sum and peak
     walk<true, true, false>(lprop, t, G, seg, lc, lt, s, b, 0.0, nullptr, nullptr);
     tot[tid] = s;
-    b = block_best(b, rv, ri);
+    b = wg_best(b, rv, ri);
     if (tid == 0) {
         double e = 0.0;
         for (int k = 0; k < kDeriveThreads; ++k) e = e + tot[k];
@@ -195,14 +158,14 @@ __global__ __launch_bounds__(kDeriveThreads) void derive_kernel(const DeriveArgs
     }
     // omega and Mdisc: end value and peak
     walk<false, true, false>(omega, t, G, seg, lc, lt, s, b, 0.0, nullptr, nullptr);
-    b = block_best(b, rv, ri);
+    b = wg_best(b, rv, ri);
     if (tid == 0) {
         res[MP_DERIVED_OMEGA_END] = omega[G - 1];
         res[MP_DERIVED_OMEGA_MAX] = b.v;
         res[MP_DERIVED_T_OMEGA_MAX] = t[b.i];
     }
     walk<false, true, false>(mdisc, t, G, seg, lc, lt, s, b, 0.0, nullptr, nullptr);
-    b = block_best(b, rv, ri);
+    b = wg_best(b, rv, ri);
     if (tid == 0) {
         res[MP_DERIVED_MDISC_END] = mdisc[G - 1];
         res[MP_DERIVED_MDISC_MAX] = b.v;

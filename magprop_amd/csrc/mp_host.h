@@ -140,11 +140,16 @@ struct Evaluator {
     // tp_used entries are live or stale), a replaced one leaves its old entries behind as garbage until the next rebuild.
     size_t obs_used = 0, tp_used = 0;
     std::vector<mp::DsDesc> desc;   // host mirror of d_ds
-    // workspace of the host-buffer entry points
-    DevBuf<double> w_pars, w_lnprob, w_curves;
-    DevBuf<double> w_band, w_band_out;   // mp_model_band: [components][n][n_grid] curves | [n_grid][n] transposed; [components][nq][n_grid]
-    DevBuf<double> w_derive, w_derive_out;   // mp_model_derived: [5][chunk][n_grid] curves of a chunk of rows; [chunk][MP_DERIVED_N]
-    DevBuf<double> w_pw_ltot, w_pw_z, w_pw_obs, w_pw_tail;   // mp_model_pointwise: [chunk][n_grid] Ltot of a chunk of rows; [n_obs][n] cells; [n_obs][MP_POINTWISE_N]; [n_obs][T(n)]
+    // Workspaces of the host-buffer entry points.  Every user runs under the handle's lock and synchronises the stream before it
+    // returns, so no two calls have a workspace in use at once and the entry points may share them.
+    DevBuf<double> w_pars, w_lnprob;
+    // w_curves: the curve rows of whichever call runs.  The curve pass of mp_model_lc, mp_model_band, mp_model_derived and
+    // mp_model_pointwise (mp_capi.cpp): [wanted curves][chunk][n_grid]; mp_lnprob_batch with ltot_out: [n][n_grid]; mp_rhs_batch:
+    // [pars | t | y] in and [dydt | lam] out.
+    DevBuf<double> w_curves;
+    DevBuf<double> w_band, w_band_out;   // mp_model_band: [n_grid][n] one component's curves transposed; [components][nq][n_grid]
+    DevBuf<double> w_derive_out;         // mp_model_derived: [chunk][MP_DERIVED_N]
+    DevBuf<double> w_pw_z, w_pw_obs, w_pw_tail;   // mp_model_pointwise: [n_obs][n] cells; [n_obs][MP_POINTWISE_N]; [n_obs][T(n)]
     DevBuf<int32_t> w_dsid, w_status, w_sweeps;
     DevBuf<int32_t> w_tile_log;
     std::vector<int32_t> last_tile_log;   // tile words of the rows of its block of the most recent host-buffer batch

@@ -8,9 +8,9 @@
 //
 // Order of every sum over the used cells of an observation (a function of the cells and of their sample indices only): thread k
 // of kPointwiseThreads = 256 takes the cells of samples k, k + 256, ... in increasing index (NaN cells skipped) from the empty
-// sum, the 64 partial results of a wavefront are combined by the xor butterfly of mp_math.hpp (wave_sum / wave_lse: distances
-// 32, 16, .. 1), and the four wavefronts are combined in wavefront order starting from wavefront 0's result.  Minima, maxima
-// and counts do not depend on an order.  tests/pointwise_restated.py is the same order in numpy.
+// sum, and the 256 partial results are combined as mp_wg.h combines a workgroup's (wg_sum, wg_lse: the xor butterfly of
+// mp_math.hpp inside a wavefront, distances 32, 16, .. 1, then the four wavefronts in wavefront order starting from wavefront
+// 0's result).  Minima, maxima and counts do not depend on an order.  tests/pointwise_restated.py is the same order in numpy.
 #pragma once
 #include <stdint.h>
 
@@ -24,7 +24,7 @@
 
 namespace mp {
 
-constexpr int kPointwiseThreads = 256;   // one workgroup of the select and reduce kernels per observation
+constexpr int kPointwiseThreads = 256;   // one workgroup of the select and reduce kernels per observation (mp_wg.h kWgThreads)
 constexpr int kPointwiseTile = 64;       // cells kernel: tiles of 64 samples x 64 observations
 constexpr int kPointwiseMaxTail = 1537;  // pointwise_tail_len(MP_POINTWISE_MAX_SAMPLES)
 constexpr int kPointwiseSortCap = 2048;  // slots of the select kernel's LDS sort: the power of two above kPointwiseMaxTail

@@ -14,13 +14,14 @@
 #include "mp_band.h"
 #include "mp_math.hpp"
 #include "mp_pointwise.h"
+#include "mp_wg.h"
 
 namespace mp {
 
 namespace {
 
-constexpr int kWaves = kPointwiseThreads / 64;
-enum { kMiscCount = 0, kMiscDigit = 1, kMiscRank = 2, kMiscWave = 4 /* .. 4 + kWaves */, kMiscWords = 8 };
+static_assert(kPointwiseThreads == kWgThreads, "the select and reduce kernels are one workgroup of mp_wg.h each");
+constexpr int kWaves = kWgWaves;
 
 __device__ inline double cell_r(double z) {
 #pragma clang fp contract(off)
@@ -66,125 +67,8 @@ __global__ __launch_bounds__(kPointwiseThreads) void pointwise_cells_kernel(cons
     }
 }
 
-// ---------------------------------------------------------------- workgroup combinations (every thread gets the result; each ends with a barrier)
-__device__ inline double block_sum(double v, double *sh) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_sum(v);
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double r = sh[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) r = r + sh[w];
-    __syncthreads();
-    return r;
-}
-
-__device__ inline void block_lse(double &m, double &s, double *shm, double *shs) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    wave_lse(m, s);
-    if (lane == 0) { shm[wave] = m; shs[wave] = s; }
-    __syncthreads();
-    m = shm[0];
-    s = shs[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) lse_merge(m, s, shm[w], shs[w]);
-    __syncthreads();
-}
-
-template <bool kMax>
-__device__ inline double block_extreme(double v, double *sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o = __shfl_xor(v, d, 64);
-        v = kMax ? fmax(v, o) : fmin(v, o);
-    }
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double r = sh[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) r = kMax ? fmax(r, sh[w]) : fmin(r, sh[w]);
-    __syncthreads();
-    return r;
-}
-
-__device__ inline uint32_t block_count(uint32_t v, uint32_t *sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    uint32_t r = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) r += sh[w];
-    __syncthreads();
-    return r;
-}
-
-// Inclusive sum over the workgroup's 256 threads (one value each); every thread gets its own prefix.  Ends with a barrier.
-__device__ inline uint32_t block_inclusive_scan(uint32_t v, uint32_t *misc) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d, 64);
-        if (lane >= d) v += u;
-    }
-    if (lane == 63) misc[kMiscWave + wave] = v;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int w = 0; w < wave; ++w) before += misc[kMiscWave + w];
-    __syncthreads();
-    return v + before;
-}
-
-// The key of rank r (0-based, ascending) among band_key(cell_r(z)) of the non-NaN z of col[0 .. n).  Every thread returns it.
-__device__ uint64_t radix_select_col(const double *__restrict__ col, int n, uint32_t r, uint32_t *hist, uint32_t *misc) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t *my_hist = hist + wave * 256;
-    uint64_t prefix = 0, mask = 0;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        for (int i = threadIdx.x; i < kWaves * 256; i += kPointwiseThreads) hist[i] = 0;
-        __syncthreads();
-        for (int base = wave * 64; base < n; base += kPointwiseThreads) {
-            const int i = base + lane;
-            const double z = i < n ? col[i] : __builtin_nan("");
-            const uint64_t k = band_key(cell_r(z));
-            const bool take = !__builtin_isnan(z) && (k & mask) == prefix;
-            const uint32_t bin = (uint32_t)(k >> shift) & 255u;
-            const uint64_t act = __ballot(take);
-            if (act == 0) continue;
-            // the cells of an observation share their leading digits: a wavefront whose candidates all fall into one bin adds once
-            const int first = __builtin_ctzll(act);
-            const uint32_t bin0 = __shfl(bin, first, 64);
-            if (__ballot(take && bin == bin0) == act) {
-                if (lane == first) atomicAdd(&my_hist[bin0], (uint32_t)__popcll(act));
-            } else if (take) {
-                atomicAdd(&my_hist[bin], 1u);
-            }
-        }
-        __syncthreads();
-        uint32_t c = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) c += hist[w * 256 + threadIdx.x];
-        const uint32_t incl = block_inclusive_scan(c, misc);
-        const uint32_t excl = incl - c;
-        if (excl <= r && r < incl) {
-            misc[kMiscDigit] = threadIdx.x;
-            misc[kMiscRank] = r - excl;
-        }
-        __syncthreads();
-        prefix |= (uint64_t)misc[kMiscDigit] << shift;
-        mask |= (uint64_t)255 << shift;
-        r = misc[kMiscRank];
-        __syncthreads();
-    }
-    return prefix;
-}
-
 __global__ __launch_bounds__(kPointwiseThreads) void pointwise_select_kernel(const PointwiseColsArgs a) {
-    __shared__ uint32_t hist[kWaves * 256];
-    __shared__ uint32_t misc[kMiscWords];
+    __shared__ WgSelectLds sel;
     __shared__ uint64_t keys[kPointwiseSortCap];
     const int j = blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -194,7 +78,7 @@ __global__ __launch_bounds__(kPointwiseThreads) void pointwise_select_kernel(con
     double *tail = a.tail ? a.tail + (size_t)j * (size_t)a.tail_stride : nullptr;
     uint32_t c = 0;
     for (int i = tid; i < n; i += kPointwiseThreads) c += !__builtin_isnan(col[i]);
-    const int m = (int)block_count(c, misc + kMiscWave);
+    const int m = (int)wg_count(c, sel.wave);
     const int tm = min(min(pointwise_tail_len(m), m), kPointwiseMaxTail);   // entries of the tail row (uniform over the workgroup)
     if (m == 0) {
         if (tid == 0) out[MP_POINTWISE_CUT] = __builtin_nan("");
@@ -202,9 +86,14 @@ __global__ __launch_bounds__(kPointwiseThreads) void pointwise_select_kernel(con
             for (int i = tid; i < a.tail_stride; i += kPointwiseThreads) tail[i] = __builtin_nan("");
         return;
     }
-    const uint64_t kc = radix_select_col(col, n, (uint32_t)(m - tm), hist, misc);
+    // the key of rank m - tm among band_key(cell_r(z)) of the non-NaN z (the column is streamed from memory once per digit)
+    const uint64_t kc = wg_radix_select(n, (uint32_t)(m - tm), sel, [col](int i, uint64_t &k) {
+        const double z = col[i];
+        k = band_key(cell_r(z));
+        return !__builtin_isnan(z);
+    });
     if (tid == 0) {
-        misc[kMiscCount] = 0;
+        sel.count = 0;
         out[MP_POINTWISE_CUT] = band_value(kc);
     }
     __syncthreads();
@@ -214,15 +103,11 @@ __global__ __launch_bounds__(kPointwiseThreads) void pointwise_select_kernel(con
         const double z = i < n ? col[i] : __builtin_nan("");
         const uint64_t k = band_key(cell_r(z));
         const bool keep = !__builtin_isnan(z) && k > kc;
-        const uint64_t act = __ballot(keep);
-        uint32_t at = 0;
-        if (lane == 0 && act) at = atomicAdd(&misc[kMiscCount], (uint32_t)__popcll(act));
-        at = __shfl(at, 0, 64);
-        const uint32_t slot = at + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
+        const uint32_t slot = wave_pack_slot(keep, &sel.count);
         if (keep && slot < (uint32_t)tm) keys[slot] = k;
     }
     __syncthreads();
-    const int above = min((int)misc[kMiscCount], tm);
+    const int above = min((int)sel.count, tm);
     int slots = 1;                                          // the power of two that holds the tm entries
     while (slots < tm) slots <<= 1;
     for (int i = above + tid; i < slots; i += kPointwiseThreads) keys[i] = i < tm ? kc : ~0ull;   // copies of the cut, then padding that sorts last
@@ -268,14 +153,14 @@ __global__ __launch_bounds__(kPointwiseThreads) void pointwise_reduce_kernel(con
             lse_add(tm, ts, r);
         }
     }
-    const uint32_t m = block_count(cnt, shc);
-    const uint32_t nontail = block_count(nt, shc);
-    sz = block_sum(sz, shm);
-    sr = block_sum(sr, shm);
-    rmin = block_extreme<false>(rmin, shm);
-    rmax = block_extreme<true>(rmax, shm);
-    block_lse(lm, ls, shm, shs);
-    block_lse(tm, ts, shm, shs);
+    const uint32_t m = wg_count(cnt, shc);
+    const uint32_t nontail = wg_count(nt, shc);
+    sz = wg_sum(sz, shm);
+    sr = wg_sum(sr, shm);
+    rmin = wg_min(rmin, shm);
+    rmax = wg_max(rmax, shm);
+    wg_lse(lm, ls, shm, shs);
+    wg_lse(tm, ts, shm, shs);
     const double zmean = sz / (double)m, rmean = sr / (double)m;   // (0 / 0 = NaN without a used cell)
     // second pass: squared deviations of ll = -r from its mean -rmean
     const double mean_ll = -rmean;
@@ -287,7 +172,7 @@ __global__ __launch_bounds__(kPointwiseThreads) void pointwise_reduce_kernel(con
         const double sq = dev * dev;
         ss = ss + sq;
     }
-    ss = block_sum(ss, shm);
+    ss = wg_sum(ss, shm);
     if (tid == 0) {
         out[MP_POINTWISE_N_USED] = (double)m;
         out[MP_POINTWISE_Z_MEAN] = zmean;

@@ -10,6 +10,7 @@ import pytest
 
 import commit_cases as cc
 import commit_restated as cr
+import probe_lib
 from moves_restated import STRETCH, pick, pick_skip, pick_skip2
 from oracle import stretch_oracle as so
 from sampler_restated import run
@@ -386,7 +387,7 @@ def test_pick_cases_and_the_restated_draws():
 # ---------------------------------------------------------------- the probe's caps and refusals (no launch, no GPU)
 def test_cases_fit_the_caps_of_the_built_probe():
     from magprop_amd import _capi
-    L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "libmp_probe_commit.so"))
+    L = probe_lib.load("commit")
     cap = {n: getattr(L, "mpc_max_" + n)() for n in ("ndim", "walkers", "ensembles", "total", "rows", "bad_cap", "order_n", "datasets")}
     assert cap["ndim"] == cc.MAX_NDIM and L.mpc_spec_extra() == cc.SPEC_EXTRA
     for c in cc.commit_cases() + cc.apply_cases() + cc.swap_cases():

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import acf_cases as ac
+import probe_lib
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +39,7 @@ class Probe:
     def __init__(self):
         from magprop_amd import _capi
         _capi.lib()                                        # first, so that one HIP runtime is shared
-        self.L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "libmp_probe_acf.so"))
+        self.L = probe_lib.load("acf")
         for name in GETTERS:
             getattr(self.L, name).restype = _i
             getattr(self.L, name).argtypes = []

@@ -566,3 +566,50 @@ def test_multi_device_handle_small_batches_diagnostics_and_error_path(gsynth, gf
             for got, want in zip((out, st, sweeps, tiles), ref):
                 assert np.array_equal(got, want)
             assert logs == [ref_log[w] for w in walkers]
+
+
+# ---------------------------------------------------------------- one curve workspace for every host-buffer entry point
+def test_entry_points_share_one_curve_workspace(gsynth, gflag, tarr):
+    """mp_model_lc, mp_model_band, mp_model_derived, mp_model_pointwise, mp_lnprob_batch with ltot_out and mp_rhs_batch keep their
+    curve rows in ONE workspace of the evaluator (mp_host.h w_curves).  A handle that serves them one after the other -- n_simd
+    + 3 rows: two chunks, the second ragged; then sizes that shrink, through a workspace an earlier call sized larger -- gives
+    every result bit for bit as a fresh handle with the same configuration, prior and dataset gives it."""
+    from magprop_amd import _capi, synth
+    rng = np.random.default_rng(808)
+
+    def make():
+        h = _capi.Handle(_capi.cfg_synth(), tarr)
+        h.set_prior(synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK)
+        h.set_dataset(0, gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"])
+        return h
+
+    shared = make()
+    big = shared.n_simd + 3
+    S = np.array(TRUTHS["Humped"]) + 0.02 * rng.standard_normal((big, 6))
+    S[2] = gflag["pars"][gflag["status"] == 1][0]         # a row that flags
+    S[big - 2, 5] = 3.5                                   # outside the prior (delta), in the ragged chunk
+    phys = np.array(CANON["Humped"], dtype=np.float64)
+    P8 = np.tile(phys, (8, 1))
+    t8 = np.geomspace(1.0, 1.0e5, 8)
+    y8 = np.column_stack([np.full(8, 1.0e-3), np.linspace(100.0, 6000.0, 8)])
+    calls = [
+        lambda h: h.model_lc(phys, want_traj=True),
+        lambda h: h.model_band(S[:64], [0.05, 0.5, 0.95], components=("Ltot", "Lprop", "Ldip")),
+        lambda h: h.model_derived(S),
+        lambda h: h.model_pointwise(S, ds_id=0, cells=True),
+        lambda h: h.lnprob_batch(S[:70], ds_id=0, want_status=True, want_ltot=True),
+        lambda h: h.rhs_batch(P8, t8, y8, want_lam=True),
+        lambda h: h.model_band(S[:5], [0.05, 0.5, 0.95], components=("Ltot", "Lprop", "Ldip")),
+        lambda h: h.model_derived(S[:1]),
+    ]
+    for k, call in enumerate(calls):
+        got = call(shared)
+        fresh = make()
+        want = call(fresh)
+        fresh.close()
+        assert len(got) == len(want)
+        for a, b in zip(got, want):
+            assert np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True), k
+    st = calls[2](shared)[1]
+    assert st[2] == _capi.STATUS_FLAG and st[big - 2] == _capi.STATUS_PRIOR and np.sum(st == 0) > 0.9 * big
+    shared.close()

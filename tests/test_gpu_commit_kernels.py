@@ -16,6 +16,7 @@ import pytest
 
 import commit_cases as cc
 import commit_restated as cr
+import probe_lib
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +40,7 @@ class Probe:
     def __init__(self):
         from magprop_amd import _capi
         _capi.lib()                                        # first, so that one HIP runtime is shared
-        self.L = L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "libmp_probe_commit.so"))
+        self.L = L = probe_lib.load("commit")
         for name in CAPS:
             getattr(L, name).restype = _i
             getattr(L, name).argtypes = []

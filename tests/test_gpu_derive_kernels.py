@@ -14,6 +14,7 @@ import pytest
 
 import derive_cases as dc
 import derive_restated as dr
+import probe_lib
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +27,7 @@ class Probe:
     def __init__(self):
         from magprop_amd import _capi
         _capi.lib()                                        # first, so that one HIP runtime is shared
-        self.L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "libmp_probe_derive.so"))
+        self.L = probe_lib.load("derive")
         for name in ("mpd_threads", "mpd_window", "mpd_columns", "mpd_max_rows", "mpd_max_grid"):
             getattr(self.L, name).restype = _i
             getattr(self.L, name).argtypes = []

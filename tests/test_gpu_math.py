@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import math_restated as mr
+import probe_lib
 from math_restated import EPS, err_rel, err_ulps, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +43,7 @@ class Probe:
     def __init__(self):
         from magprop_amd import _capi
         _capi.lib()                                        # first, so that one HIP runtime is shared
-        self.L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "libmp_probe.so"))
+        self.L = probe_lib.load()
         for name in mr.PROBE_EXPORTS:
             getattr(self.L, name).restype = _i
         self.L.mpp_lane_prev.argtypes = [_dp, _d, _dp, _i]

@@ -16,6 +16,7 @@ import pytest
 
 import pointwise_cases as pc
 import pointwise_restated as pr
+import probe_lib
 from test_pointwise_cases_cpu import lse_bound, lse_error, same
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +35,7 @@ class Probe:
     def __init__(self):
         from magprop_amd import _capi
         _capi.lib()                                        # first, so that one HIP runtime is shared
-        self.L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "libmp_probe_pointwise.so"))
+        self.L = probe_lib.load("pointwise")
         for name in ("mpw_threads", "mpw_tile", "mpw_columns", "mpw_max_tail", "mpw_sort_cap", "mpw_max_rows", "mpw_max_obs"):
             getattr(self.L, name).restype = _i
             getattr(self.L, name).argtypes = []

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import post_cases as pc
+import probe_lib
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +34,7 @@ class Probe:
     def __init__(self):
         from magprop_amd import _capi
         _capi.lib()                                        # first, so that one HIP runtime is shared
-        self.L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "libmp_probe_post.so"))
+        self.L = probe_lib.load("post")
         for name in ("mpq_threads", "mpq_max_bins", "mpq_max_bins2", "mpq_max_ndim", "mpq_max_rows", "mpq_max_elements"):
             getattr(self.L, name).restype = _i
             getattr(self.L, name).argtypes = []

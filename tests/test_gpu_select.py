@@ -13,6 +13,7 @@ import warnings
 import numpy as np
 import pytest
 
+import probe_lib
 import select_cases as sc
 
 pytestmark = pytest.mark.gpu
@@ -36,7 +37,7 @@ class Probe:
     def __init__(self):
         from magprop_amd import _capi
         _capi.lib()                                        # first, so that one HIP runtime is shared
-        self.L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "libmp_probe_select.so"))
+        self.L = probe_lib.load("select")
         for name in GETTERS:
             getattr(self.L, name).restype = _i
             getattr(self.L, name).argtypes = []
