@@ -693,7 +693,9 @@ int mp_optimizer_destroy(mp_optimizer *o);
  * Every iteration writes the dead rows (pars, lnL, n_k) of every running run; mp_nested_run reads them back behind every chunk
  * of iterations (one wait per chunk) and keeps them per run in order.  The final estimate (adding the live points, the
  * information H, the error, resampling) is the caller's (magprop_amd.nested).
- * Kernel build: the rule of mp_lnprob_batch for a batch of n_runs * nbatch walkers (the live-set evaluation: n_runs * nlive).
+ * Kernel build: the rule of mp_lnprob_batch for a batch of n_runs * nbatch walkers (the live-set evaluation: n_runs * nlive), so
+ * that (shipped build) every evaluation of a walk, random-walk step or slice point, and every live point's first lnL and status are
+ * bit for bit what mp_lnprob_batch returns for that row on dataset run_ds_id[r] in a batch of the launch's size.
  * mp_nested_create: MP_EINVAL on bad sizes (ndim < 6 for target 0, walks outside 1 .. MP_NEST_MAX_WALKS), g0 > 0 not finite,
  * sigma outside [0, 1/sqrt(3)), dlogz not finite and > 0, an empty or non-finite box, unset datasets; MP_ESTATE on
  * multi-device handles and (target 0) handles with cfg.dipole_torque = 1.  mp_nested_set_live(live[n_runs * nlive][ndim], inside

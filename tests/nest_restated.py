@@ -2,7 +2,10 @@
 constrained DE walks with the unfused arithmetic of the kernels (magprop_amd/csrc/mp_nest.hip), the volume bookkeeping and the
 stop rule.  Test infrastructure: the GPU tests compare the device state with it bit for bit (ln X and ln Z to rounding: the
 device's log1p / exp / expm1 are not numpy's), the CPU tests check with it that the scheme samples the constrained prior.
-Every product and sum is a separately rounded float64 operation in the kernel's order (Python floats)."""
+Every product and sum is a separately rounded float64 operation in the kernel's order (Python floats).
+A walk is a generator with the kernel's round structure (it names a point, is sent the point's lnL and status, decides); the
+walks of an iteration run a point at a time (evaluate_one) or all together, one evaluate(rows, runs) call per round (in_rounds),
+which is how the GPU tests put an mp_lnprob_batch call of the launch's own size behind every likelihood."""
 import math
 
 import numpy as np
@@ -62,11 +65,13 @@ def _clean(v):
     return -math.inf if v != v else float(v)
 
 
-def start(live0, evaluate):
-    """The live set live0 (n_runs, N, ndim) evaluated: evaluate(rows[n, ndim]) -> (lnL, status)."""
+def start(live0, evaluate, with_runs=False):
+    """The live set live0 (n_runs, N, ndim) evaluated: evaluate(rows[n, ndim]) -> (lnL, status); with_runs: evaluate(rows,
+    runs[n]), the run of every row with it."""
     live = np.array(live0, dtype=np.float64)
     n_runs, n, ndim = live.shape
-    lnl, st = evaluate(live.reshape(-1, ndim))
+    rows = live.reshape(-1, ndim)
+    lnl, st = evaluate(rows, np.repeat(np.arange(n_runs), n)) if with_runs else evaluate(rows)
     lnl = np.array([_clean(v) for v in lnl]).reshape(n_runs, n)
     return State(live, lnl, np.asarray(st, dtype=np.int32).reshape(n_runs, n))
 
@@ -76,8 +81,10 @@ def order(lnl):
     return sorted(range(len(lnl)), key=lambda j: (lnl[j], j))
 
 
-def walk(s, r, slot, t, surv, lstar, seed, walks, g0, s3, lower, upper, evaluate_one):
-    """The constrained walk into dead slot `slot` of run r, iteration t: (end point, lnL, status, accepted steps, evaluations)."""
+def walk_rounds(s, r, slot, t, surv, lstar, seed, walks, g0, s3, lower, upper):
+    """The constrained walk into dead slot `slot` of run r, iteration t, as the kernel's rounds: a generator that yields the
+    next point to evaluate (a proposal inside the box), is sent its (lnL, status), and returns (end point, lnL, status,
+    accepted steps, evaluations)."""
     m = len(surv)
     u = draw(seed, t, r, slot, 0)
     fr = surv[pick(u01(u[0], u[1]), m)]
@@ -94,13 +101,59 @@ def walk(s, r, slot, t, surv, lstar, seed, walks, g0, s3, lower, upper, evaluate
         q = [x[d] + gamma * (float(a[d]) - float(b[d])) for d in range(len(x))]
         if not all(lower[d] <= q[d] <= upper[d] for d in range(len(x))):
             continue
-        lq, sq = evaluate_one(np.array(q))
+        lq, sq = yield np.array(q)
         lq = _clean(lq)
         n_eval += 1
         if lq > lstar:
             x, lnl, st = q, lq, int(sq)
             n_acc += 1
     return x, lnl, st, n_acc, n_eval
+
+
+def one_at_a_time(gen, evaluate_one):
+    """Drives one walk to its end, every point it names through evaluate_one(q) -> (lnL, status); returns what the walk returns."""
+    try:
+        q = next(gen)
+        while True:
+            q = gen.send(evaluate_one(q))
+    except StopIteration as e:
+        return e.value
+
+
+def in_rounds(gens, runs, evaluate):
+    """Drives the walks gens (gens[i] a walk of run runs[i]) together, a round at a time as the device launch does: every
+    unfinished walk names its next point, ONE evaluate(rows[k, ndim], runs[k]) -> (lnL[k], status[k]) answers them all (in the
+    order of gens), every walk decides.  As many calls as the longest walk has rounds.  Returns what the walks return."""
+    out, pending = [None] * len(gens), {}
+
+    def advance(i, answer):
+        try:
+            pending[i] = next(gens[i]) if answer is None else gens[i].send(answer)
+        except StopIteration as e:
+            pending.pop(i, None)
+            out[i] = e.value
+
+    for i in range(len(gens)):
+        advance(i, None)
+    while pending:
+        idx = sorted(pending)
+        lnl, st = evaluate(np.array([pending[i] for i in idx]), np.array([runs[i] for i in idx]))
+        assert len(lnl) == len(idx) and len(st) == len(idx)
+        for k, i in enumerate(idx):
+            advance(i, (lnl[k], st[k]))
+    return out
+
+
+def drive(gens, runs, evaluate_one=None, evaluate=None):
+    """The walks of an iteration through evaluate (in_rounds) where one is given, else one after the other through evaluate_one."""
+    if evaluate is not None:
+        return in_rounds(gens, runs, evaluate)
+    return [one_at_a_time(g, evaluate_one) for g in gens]
+
+
+def walk(s, r, slot, t, surv, lstar, seed, walks, g0, s3, lower, upper, evaluate_one):
+    """walk_rounds, one evaluate_one(q) per round: (end point, lnL, status, accepted steps, evaluations)."""
+    return one_at_a_time(walk_rounds(s, r, slot, t, surv, lstar, seed, walks, g0, s3, lower, upper), evaluate_one)
 
 
 def select(lnl, lnx, lnz, nbatch, dlogz):
@@ -125,11 +178,11 @@ def select(lnl, lnx, lnz, nbatch, dlogz):
     return dead, surv, key[dead[-1]], dead_lnl, dead_n, lnx, lnz
 
 
-def iteration(s, nbatch, seed, walks, g0, sigma, dlogz, lower, upper, evaluate_one):
-    """One iteration of every run not stopped (the stop rule first, on the live set as it stands)."""
-    n_runs, n, ndim = s.live.shape
-    g0, s3 = resolve(g0, sigma, ndim)
-    for r in range(n_runs):
+def retire(s, nbatch, dlogz):
+    """The select step of every run not stopped, booked into s (stopped flags, dead lists, ln X, ln Z): the list of
+    (r, dead slots, survivors, L*, t) of the runs that go on to their walks."""
+    jobs = []
+    for r in range(s.lnl.shape[0]):
         if s.stopped[r]:
             continue
         sel = select(s.lnl[r], s.lnx[r], s.lnz[r], nbatch, dlogz)
@@ -140,13 +193,25 @@ def iteration(s, nbatch, seed, walks, g0, sigma, dlogz, lower, upper, evaluate_o
         s.dead_pars[r].extend(s.live[r, j].copy() for j in dead)
         s.dead_lnl[r].extend(dead_lnl)
         s.dead_n[r].extend(dead_n)
-        t = int(s.nit[r])
-        out = [walk(s, r, j, t, surv, lstar, seed, walks, g0, s3, lower, upper, evaluate_one) for j in dead]
-        for j, (x, lq, sq, na, ne) in zip(dead, out):
-            s.live[r, j], s.lnl[r, j], s.status[r, j], s.acc[r, j] = x, lq, sq, na
-            s.ncall[r] += ne
-            s.nacc[r] += na
-            s.nzero[r] += na == 0
+        jobs.append((r, dead, surv, lstar, int(s.nit[r])))
+    return jobs
+
+
+def iteration(s, nbatch, seed, walks, g0, sigma, dlogz, lower, upper, evaluate_one=None, evaluate=None):
+    """One iteration of every run not stopped (the stop rule first, on the live set as it stands).  evaluate(rows, runs): the
+    walks of all runs and slots advance together, one call per round (in_rounds); else evaluate_one(q), a point at a time."""
+    g0, s3 = resolve(g0, sigma, s.live.shape[2])
+    jobs = retire(s, nbatch, dlogz)
+    where = [(r, j) for r, dead, *_ in jobs for j in dead]
+    gens = [walk_rounds(s, r, j, t, surv, lstar, seed, walks, g0, s3, lower, upper)
+            for r, dead, surv, lstar, t in jobs for j in dead]
+    out = drive(gens, [r for r, _ in where], evaluate_one, evaluate)      # (survivors are only read, dead slots written behind)
+    for (r, j), (x, lq, sq, na, ne) in zip(where, out):
+        s.live[r, j], s.lnl[r, j], s.status[r, j], s.acc[r, j] = x, lq, sq, na
+        s.ncall[r] += ne
+        s.nacc[r] += na
+        s.nzero[r] += na == 0
+    for r, *_ in jobs:
         s.nit[r] += 1
 
 
@@ -156,14 +221,16 @@ def check_stops(s, dlogz):
             s.stopped[r] = 1
 
 
-def run(s, iterations, nbatch, seed, walks=25, g0=0.0, sigma=0.1, dlogz=0.01, lower=None, upper=None, evaluate_one=None):
-    """Up to `iterations` iterations and the stop check behind them (mp_nested_run); s is advanced in place."""
+def run(s, iterations, nbatch, seed, walks=25, g0=0.0, sigma=0.1, dlogz=0.01, lower=None, upper=None, evaluate_one=None,
+        evaluate=None):
+    """Up to `iterations` iterations and the stop check behind them (mp_nested_run); s is advanced in place.  evaluate_one /
+    evaluate: as iteration takes them."""
     if iterations <= 0 or np.all(s.stopped):
         return s
     for _ in range(iterations):
         if np.all(s.stopped):
             break
-        iteration(s, nbatch, seed, walks, g0, sigma, dlogz, lower, upper, evaluate_one)
+        iteration(s, nbatch, seed, walks, g0, sigma, dlogz, lower, upper, evaluate_one, evaluate)
     check_stops(s, dlogz)
     return s
 

@@ -21,12 +21,13 @@ def slice_draw(seed, t, r, slot, s, c):
     return philox4x32_10(seed & M32, seed >> 32, int(t) & M32, int(r), int(slot), SLICE_CTR + 0x100 * int(s) + int(c))
 
 
-def slice_walk(x, lnl, st, t, r, slot, surv_pts, lstar, seed, slices, mu, max_steps_out, max_shrink, lower, upper, evaluate_one,
-               broken=None):
-    """`slices` slice updates of x (a list of floats; lnL lnl, status st) at iteration t, run r, dead slot `slot`; surv_pts[m]
-    the survivors in slot order (the directions).  Returns (x, lnl, st, slices moved, evaluations, expansions, contractions,
-    failed slices).  broken="forward" (the negative control of the tests): the interval starts at x and steps out forward
-    only (L = 0, R = mu, J = 0, K = m - 1), so that the walk moves along +d alone and is not reversible."""
+def slice_walk_rounds(x, lnl, st, t, r, slot, surv_pts, lstar, seed, slices, mu, max_steps_out, max_shrink, lower, upper,
+                      broken=None):
+    """`slices` slice updates of x (a list of floats; lnL lnl, status st) at iteration t, run r, dead slot `slot`, as the kernel's
+    rounds: a generator that yields the next point to evaluate (a named point inside the box), is sent its (lnL, status), and
+    returns (x, lnl, st, slices moved, evaluations, expansions, contractions, failed slices).  surv_pts[m]: the survivors in
+    slot order (the directions).  broken="forward" (the negative control of the tests): the interval starts at x and steps out
+    forward only (L = 0, R = mu, J = 0, K = m - 1), so that the walk moves along +d alone and is not reversible."""
     m, nd = len(surv_pts), len(x)
     moved = n_eval = n_exp = n_con = n_fail = 0
 
@@ -36,7 +37,7 @@ def slice_walk(x, lnl, st, t, r, slot, surv_pts, lstar, seed, slices, mu, max_st
         q = [x[k] + tt * d[k] for k in range(nd)]
         if not all(lower[k] <= q[k] <= upper[k] for k in range(nd)):
             return q, False, None, None
-        lq, sq = evaluate_one(np.array(q))
+        lq, sq = yield np.array(q)
         lq = -math.inf if lq != lq else float(lq)
         n_eval += 1
         return q, lq > lstar, lq, int(sq)
@@ -57,18 +58,18 @@ def slice_walk(x, lnl, st, t, r, slot, surv_pts, lstar, seed, slices, mu, max_st
         right = max_steps_out - 1 - left
         if broken == "forward":
             lo, hi, left, right = 0.0, mu, 0, max_steps_out - 1
-        while left > 0 and named(lo, d)[1]:
+        while left > 0 and (yield from named(lo, d))[1]:
             lo = lo - mu
             left -= 1
             n_exp += 1
-        while right > 0 and named(hi, d)[1]:
+        while right > 0 and (yield from named(hi, d))[1]:
             hi = hi + mu
             right -= 1
             n_exp += 1
         for i in range(max_shrink):
             u = slice_draw(seed, t, r, slot, s, 2 + i)
             tt = lo + u01(u[0], u[1]) * (hi - lo)
-            q, inside, lq, sq = named(tt, d)
+            q, inside, lq, sq = yield from named(tt, d)
             if inside:
                 x, lnl, st = q, lq, sq
                 moved += 1
@@ -83,9 +84,16 @@ def slice_walk(x, lnl, st, t, r, slot, surv_pts, lstar, seed, slices, mu, max_st
     return x, lnl, st, moved, n_eval, n_exp, n_con, n_fail
 
 
-def start(live0, evaluate):
+def slice_walk(x, lnl, st, t, r, slot, surv_pts, lstar, seed, slices, mu, max_steps_out, max_shrink, lower, upper, evaluate_one,
+               broken=None):
+    """slice_walk_rounds, one evaluate_one(q) per round."""
+    return nr.one_at_a_time(slice_walk_rounds(x, lnl, st, t, r, slot, surv_pts, lstar, seed, slices, mu, max_steps_out, max_shrink,
+                                              lower, upper, broken), evaluate_one)
+
+
+def start(live0, evaluate, with_runs=False):
     """nest_restated.start with the slice counters (nexpand, ncontract, nfail per run) at 0."""
-    s = nr.start(live0, evaluate)
+    s = nr.start(live0, evaluate, with_runs)
     n_runs = s.lnl.shape[0]
     s.nexpand = np.zeros(n_runs, dtype=np.int64)
     s.ncontract = np.zeros(n_runs, dtype=np.int64)
@@ -93,55 +101,39 @@ def start(live0, evaluate):
     return s
 
 
-def iteration(s, nbatch, seed, slices, mu, max_steps_out, max_shrink, dlogz, lower, upper, evaluate_one):
+def iteration(s, nbatch, seed, slices, mu, max_steps_out, max_shrink, dlogz, lower, upper, evaluate_one=None, evaluate=None):
     """One iteration of every run not stopped, in slice mode (nest_restated.iteration with the slice walk)."""
-    n_runs, n, ndim = s.live.shape
-    for r in range(n_runs):
-        if s.stopped[r]:
-            continue
-        o = nr.order(s.lnl[r])
-        if nr.stops(s.lnl[r, o[-1]], s.lnx[r], s.lnz[r], dlogz):
-            s.stopped[r] = 1
-            continue
-        dead, surv = o[:nbatch], sorted(o[nbatch:])
-        lnx, lnz = float(s.lnx[r]), float(s.lnz[r])
-        for k, j in enumerate(dead):
-            s.dead_pars[r].append(s.live[r, j].copy())
-            s.dead_lnl[r].append(float(s.lnl[r, j]))
-            s.dead_n[r].append(n - k)
-            inv = 1.0 / float(n - k)
-            lnw = (float(s.lnl[r, j]) + lnx) + math.log(-math.expm1(-inv))
-            lnx = lnx - inv
-            lnz = nr.logaddexp(lnz, lnw)
-        s.lnx[r], s.lnz[r] = lnx, lnz
-        lstar = float(s.lnl[r, dead[-1]])
-        t = int(s.nit[r])
+    jobs = nr.retire(s, nbatch, dlogz)
+    where, gens = [], []
+    for r, dead, surv, lstar, t in jobs:
         surv_pts = s.live[r, surv].copy()
-        out = []
         for j in dead:
             u = nr.draw(seed, t, r, j, 0)
             fr = surv[pick(u01(u[0], u[1]), len(surv))]
-            out.append(slice_walk([float(v) for v in s.live[r, fr]], float(s.lnl[r, fr]), int(s.status[r, fr]), t, r, j,
-                                  surv_pts, lstar, seed, slices, mu, max_steps_out, max_shrink, lower, upper, evaluate_one))
-        for j, (x, lq, sq, mv, ne, nx, nc, nf) in zip(dead, out):
-            s.live[r, j], s.lnl[r, j], s.status[r, j], s.acc[r, j] = x, lq, sq, mv
-            s.ncall[r] += ne
-            s.nacc[r] += mv
-            s.nzero[r] += mv == 0
-            s.nexpand[r] += nx
-            s.ncontract[r] += nc
-            s.nfail[r] += nf
+            where.append((r, j))
+            gens.append(slice_walk_rounds([float(v) for v in s.live[r, fr]], float(s.lnl[r, fr]), int(s.status[r, fr]), t, r, j,
+                                          surv_pts, lstar, seed, slices, mu, max_steps_out, max_shrink, lower, upper))
+    out = nr.drive(gens, [r for r, _ in where], evaluate_one, evaluate)
+    for (r, j), (x, lq, sq, mv, ne, nx, nc, nf) in zip(where, out):
+        s.live[r, j], s.lnl[r, j], s.status[r, j], s.acc[r, j] = x, lq, sq, mv
+        s.ncall[r] += ne
+        s.nacc[r] += mv
+        s.nzero[r] += mv == 0
+        s.nexpand[r] += nx
+        s.ncontract[r] += nc
+        s.nfail[r] += nf
+    for r, *_ in jobs:
         s.nit[r] += 1
 
 
 def run(s, iterations, nbatch, seed, slices, mu=1.0, max_steps_out=8, max_shrink=64, dlogz=0.01, lower=None, upper=None,
-        evaluate_one=None):
+        evaluate_one=None, evaluate=None):
     """Up to `iterations` slice-mode iterations and the stop check behind them (mp_nested_run); s is advanced in place."""
     if iterations <= 0 or np.all(s.stopped):
         return s
     for _ in range(iterations):
         if np.all(s.stopped):
             break
-        iteration(s, nbatch, seed, slices, mu, max_steps_out, max_shrink, dlogz, lower, upper, evaluate_one)
+        iteration(s, nbatch, seed, slices, mu, max_steps_out, max_shrink, dlogz, lower, upper, evaluate_one, evaluate)
     nr.check_stops(s, dlogz)
     return s

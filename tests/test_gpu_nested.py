@@ -1,6 +1,7 @@
 """GPU tests of the nested sampler (include/magprop_amd.h mp_nested_*, magprop_amd.nested): the device state against the numpy
 restatement (tests/nest_restated.py) bit for bit, chunk independence, evidence against closed forms and brute force, posterior
-samples against a long ensemble chain, a long Swift light curve, and refused handles."""
+samples against a long ensemble chain, a long Swift light curve, and refused handles.  On the real posterior the restatement's
+evaluations are mp_lnprob_batch calls of the launch's own size, on every kernel build."""
 import ctypes as C
 import math
 
@@ -9,7 +10,8 @@ import pytest
 from scipy.special import erf
 
 import nest_restated as nr
-from conftest import TRUTHS
+import nest_slice_restated as sr
+from conftest import TRUTHS, TYPES
 from raw_abi import dp, ip, synth_handle
 
 pytestmark = pytest.mark.gpu
@@ -98,6 +100,166 @@ def test_gaussian_state_matches_the_restatement_bit_for_bit(n_runs):
     _assert_equal(st, s)
     assert np.all(st["stopped"] == 1) and np.all(st["nit"] > 6)
     print(f"stop iterations {st['nit'].tolist()}, ln Z {st['lnz'].tolist()}")
+
+
+# ---------------------------------------------------------------- the real posterior against mp_lnprob_batch, build by build
+def launch_class(n, ns):
+    """(wavefronts per walker, steps per lane, wavefronts per SIMD) of a walker launch of n workgroups on a device of ns SIMDs
+    (mp_device.h kernel_waves / walker_variant): a team of four up to ns / 2 (a SIMD per wavefront up to ns / 4), one wavefront
+    with four steps per lane up to ns, two beyond."""
+    return (4, 1, 1) if 4 * n <= ns else ((4, 1, 2) if 2 * n <= ns else ((1, 4, 1) if n <= ns else (1, 2, 2)))
+
+
+def posterior_cases(ns):
+    """The smallest shapes whose walk launch (n_runs * nbatch workgroups) runs each build; nlive = 2 nbatch, so that the live-set
+    launch lies a class further on.  run_ds: the dataset of every run (TYPES); chunks: the iterations of every mp_nested_run."""
+    return {"team-1": dict(run_ds=[2, 0, 1], nbatch=8, chunks=(1, 3), walks=10, build=(4, 1, 1)),
+            "team-2": dict(run_ds=[3, 1], nbatch=3 * ns // 16, chunks=(2,), walks=3, build=(4, 1, 2)),
+            "wave-4": dict(run_ds=[1, 2], nbatch=3 * ns // 8, chunks=(2,), walks=3, build=(1, 4, 1)),
+            "wave-2": dict(run_ds=[0, 3], nbatch=5 * ns // 8, chunks=(2,), walks=3, build=(1, 2, 2))}
+
+
+def posterior_live(truths, nlive, seed):
+    """Live points (n_runs, nlive, 6) in the synthetic prior box: the first half uniform in the box (flagged, out-of-range and
+    -inf points among them), the other half truths[r] + 0.05 randn, clipped into the box."""
+    from magprop_amd import synth
+    lo, hi = synth.PRIOR_LOWER, synth.PRIOR_UPPER
+    rng = np.random.default_rng(seed)
+    live = lo + (hi - lo) * rng.random((len(truths), nlive, 6))
+    for r, t in enumerate(truths):
+        live[r, nlive // 2:] = np.clip(np.array(t) + 0.05 * rng.standard_normal((nlive - nlive // 2, 6)), lo, hi)
+    return live
+
+
+class BatchEvaluator:
+    """The restatement's evaluate(rows, runs) as ONE mp_lnprob_batch call of exactly n rows, the size of the device launch (and
+    so its kernel build): the pending rows, padded with copies of the first (on that row's dataset); row i runs on the dataset
+    of its run."""
+
+    def __init__(self, h, run_ds):
+        self.h, self.run_ds, self.calls = h, np.asarray(run_ds, dtype=np.int32), 0
+
+    def at(self, n):
+        def evaluate(rows, runs):
+            k = len(rows)
+            assert 1 <= k <= n and len(runs) == k
+            padded = np.concatenate([rows, np.repeat(rows[:1], n - k, axis=0)])
+            ids = self.run_ds[np.concatenate([runs, np.full(n - k, runs[0])]).astype(int)]
+            assert padded.shape == (n, 6) and ids.shape == (n,)
+            out, st = self.h.lnprob_batch(padded, ds_id=ids, want_status=True)
+            self.calls += 1
+            return out[:k], st[:k]
+        return evaluate
+
+
+def assert_reference_is_not_vacuous(s, status0, walks):
+    """Conditions on the inputs, read off the restatement alone: a live point started flagged; a proposal fell outside the box
+    (a step without an evaluation); evaluated steps were accepted and rejected; every run moved."""
+    steps = walks * int(np.sum(s.nit)) * (s.lnl.shape[1] // 2)
+    assert np.any(status0 != 0)
+    assert s.ncall.sum() < steps
+    assert np.all(s.nacc > 0) and s.nacc.sum() < s.ncall.sum()
+
+
+@pytest.fixture(scope="module")
+def synth_sets(gsynth):
+    """One handle with the synthetic prior and the four synthetic datasets (ds k = TYPES[k])."""
+    from magprop_amd import synth
+    h = synth_handle()
+    h.set_prior(synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK)
+    for k, t in enumerate(TYPES):
+        h.set_dataset(k, gsynth[t + "_x"], gsynth[t + "_y"], gsynth[t + "_yerr"])
+    yield h
+    h.close()
+
+
+@pytest.fixture(scope="module")
+def long_sets(gsynth, glonglc):
+    """One handle with Humped (ds 0) and a Humped-type light curve of 112 points (ds 1: every launch runs the LONG builds)."""
+    from magprop_amd import synth
+    h = synth_handle()
+    h.set_prior(synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK)
+    h.set_dataset(0, gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"])
+    x, y, yerr = glonglc["synth112_ds"]
+    assert len(x) > 64
+    h.set_dataset(1, x, y, yerr)
+    yield h
+    h.close()
+
+
+def drive_posterior(h, run_ds, truths, nbatch, chunks, walks, seed, build=None):
+    """RawNested(target=0, ds=run_ds) on h and the restatement in step, nlive = 2 nbatch: equal after the live-set evaluation
+    and behind every mp_nested_run of `chunks` -- n iterations each, or (n, (slices, mu, max_steps_out, max_shrink)) after an
+    mp_nested_set_slice of those (slices = 0: back to the random walk); the slice counters are compared throughout.  Returns the
+    restatement's state, its first (live, lnL, status), and the evaluator."""
+    from magprop_amd import nested, synth
+    lo, hi = synth.PRIOR_LOWER, synth.PRIOR_UPPER
+    n_runs, nlive, ns_ = len(run_ds), 2 * nbatch, h.n_simd
+    if build is not None:
+        assert launch_class(n_runs * nbatch, ns_) == build, (n_runs * nbatch, ns_)
+    assert len(set(run_ds)) == n_runs
+    live0 = posterior_live(truths, nlive, seed)
+    ev = BatchEvaluator(h, run_ds)
+    kw = dict(dlogz=1e-9, lower=lo, upper=hi, evaluate=ev.at(n_runs * nbatch))
+    s = sr.start(live0, ev.at(n_runs * nlive), with_runs=True)
+    first = live0, s.lnl.copy(), s.status.copy()
+    ns = RawNested(h, nlive, nbatch, n_runs, 6, lo, hi, seed, walks, 0, ds=run_ds, dlogz=1e-9)
+
+    def check():
+        st = ns.state()
+        st.update(nested.get_slice_stats(ns.L, ns.ns, n_runs))
+        _assert_equal(st, s)
+        for k in ("nexpand", "ncontract", "nfail"):
+            assert np.array_equal(st[k], getattr(s, k)), k
+
+    try:
+        ns.set_live(live0.reshape(-1, 6))
+        check()
+        sl = (0, 1.0, 1, 1)
+        for c in chunks:
+            n, new = c if isinstance(c, tuple) else (c, None)
+            if new is not None:
+                sl = new
+                assert ns.L.mp_nested_set_slice(ns.ns, *sl) == 0
+            assert ns.run(n) == n_runs
+            if sl[0]:
+                sr.run(s, n, nbatch, seed, sl[0], mu=sl[1], max_steps_out=sl[2], max_shrink=sl[3], **kw)
+            else:
+                nr.run(s, n, nbatch, seed, walks=walks, g0=0.0, sigma=0.1, **kw)
+            check()
+    finally:
+        ns.close()
+    total = sum(c[0] if isinstance(c, tuple) else c for c in chunks)
+    assert np.all(s.nit == total) and not np.any(s.stopped)
+    print(f"walk launch {n_runs * nbatch} {launch_class(n_runs * nbatch, ns_)}, live-set launch {n_runs * nlive} "
+          f"{launch_class(n_runs * nlive, ns_)}: {ev.calls} batches, flagged at the start {int(np.sum(first[2] != 0))}, ncall "
+          f"{s.ncall.tolist()}, nacc {s.nacc.tolist()}, nzero {s.nzero.tolist()}, nexpand {s.nexpand.tolist()}, ncontract "
+          f"{s.ncontract.tolist()}, nfail {s.nfail.tolist()}")
+    return s, first, ev
+
+
+@pytest.mark.parametrize("case", ["team-1", "team-2", "wave-4", "wave-2"])
+def test_posterior_walks_match_lnprob_batch_on_every_build(synth_sets, case):
+    """The random walk on the real posterior, runs on different datasets, at the smallest shape of each of the four builds:
+    the device state equals the restatement bit for bit where every likelihood of the restatement -- the live set and every
+    round of the walks -- is an mp_lnprob_batch call of the launch's size on the row's dataset (ln X, ln Z to 1e-14)."""
+    h = synth_sets
+    c = posterior_cases(h.n_simd)[case]
+    truths = [TRUTHS[TYPES[d]] for d in c["run_ds"]]
+    s, (live0, lnl0, status0), ev = drive_posterior(h, c["run_ds"], truths, c["nbatch"], c["chunks"], c["walks"], 20261019,
+                                                    c["build"])
+    assert_reference_is_not_vacuous(s, status0, c["walks"])
+    if case == "team-1":   # the runs' datasets matter: the reference with two of them swapped starts from another live lnL
+        swap = BatchEvaluator(h, [c["run_ds"][1], c["run_ds"][0]] + c["run_ds"][2:]).at(lnl0.size)
+        lnl1 = nr.start(live0, swap, with_runs=True).lnl
+        assert not np.array_equal(lnl1[0], lnl0[0]) and not np.array_equal(lnl1[1], lnl0[1]) and np.array_equal(lnl1[2], lnl0[2])
+
+
+def test_posterior_walks_match_lnprob_batch_on_the_long_builds(long_sets):
+    """The LONG builds: a handle that also holds a light curve of 112 points, one run on Humped and one on the long set."""
+    truths = [TRUTHS["Humped"], TRUTHS["Humped"]]
+    s, (_, _, status0), ev = drive_posterior(long_sets, [0, 1], truths, 8, (1, 3), 10, 20261220, (4, 1, 1))
+    assert_reference_is_not_vacuous(s, status0, 10)
 
 
 def test_chunks_of_one_iteration_equal_one_unsplit_run():

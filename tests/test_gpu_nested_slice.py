@@ -11,9 +11,10 @@ import pytest
 
 import nest_restated as nr
 import nest_slice_restated as sr
-from conftest import TRUTHS
+from conftest import TRUTHS, TYPES
 from raw_abi import lp, synth_handle
-from test_gpu_nested import EVIDENCE_INFLATION, RawNested, _assert_equal, _gaussian_lnz
+from test_gpu_nested import (EVIDENCE_INFLATION, RawNested, _assert_equal, _gaussian_lnz, drive_posterior, long_sets,  # noqa: F401
+                             posterior_cases, synth_sets)
 
 pytestmark = pytest.mark.gpu
 
@@ -124,6 +125,47 @@ def test_zero_slices_is_the_random_walk():
         assert np.array_equal(a[k], b[k]), k
     for k in ("nexpand", "ncontract", "nfail"):
         assert np.all(a[k] == 0) and np.all(b[k] == 0), k
+
+
+def _assert_slices_are_not_vacuous(s, status0):
+    """Conditions on the inputs, read off the restatement alone: a live point started flagged, a slice stepped out, a shrink
+    point was rejected, and every run moved a slice."""
+    assert np.any(status0 != 0)
+    assert s.nexpand.sum() > 0 and s.ncontract.sum() > 0 and np.all(s.nacc > 0)
+
+
+@pytest.mark.parametrize("case", ["team-1", "team-2", "wave-4", "wave-2"])
+def test_posterior_slices_match_lnprob_batch_on_every_build(synth_sets, case):
+    """Slice mode on the real posterior at the shapes of test_gpu_nested.py's random-walk cases (runs on different datasets, the
+    smallest shape of each build): the device state and the slice counters equal the restatement bit for bit where every
+    likelihood of the restatement is an mp_lnprob_batch call of the launch's size on the row's dataset.  Small budgets bound
+    the rounds: 2 slices, 4 steps out, 16 shrink points over 1 + 3 iterations on the first case; 1 slice and 1 iteration on the
+    larger ones."""
+    h = synth_sets
+    c = posterior_cases(h.n_simd)[case]
+    truths = [TRUTHS[TYPES[d]] for d in c["run_ds"]]
+    chunks = ((1, (2, 1.0, 4, 16)), 3) if case == "team-1" else ((1, (1, 1.0, 4, 16)),)
+    s, (_, _, status0), ev = drive_posterior(h, c["run_ds"], truths, c["nbatch"], chunks, c["walks"], 20261061, c["build"])
+    _assert_slices_are_not_vacuous(s, status0)
+
+
+def test_posterior_slices_match_lnprob_batch_on_the_long_builds(long_sets):
+    """The LONG builds in slice mode: one run on Humped and one on a light curve of 112 points."""
+    truths = [TRUTHS["Humped"], TRUTHS["Humped"]]
+    s, (_, _, status0), ev = drive_posterior(long_sets, [0, 1], truths, 8, ((1, (2, 1.0, 4, 16)), 3), 10, 20261192, (4, 1, 1))
+    _assert_slices_are_not_vacuous(s, status0)
+
+
+def test_switching_walks_between_iterations_on_the_posterior(synth_sets):
+    """A random-walk iteration, two slice iterations after mp_nested_set_slice, and a random-walk iteration again after
+    mp_nested_set_slice(0, ...), on the real posterior with three runs on different datasets: equal to the restatement behind
+    every call, the slice counters standing still while the random walk runs."""
+    c = posterior_cases(synth_sets.n_simd)["team-1"]
+    truths = [TRUTHS[TYPES[d]] for d in c["run_ds"]]
+    chunks = (1, (2, (2, 1.0, 4, 16)), (1, (0, 1.0, 4, 16)))
+    s, (_, _, status0), ev = drive_posterior(synth_sets, c["run_ds"], truths, c["nbatch"], chunks, c["walks"], 20261073, c["build"])
+    _assert_slices_are_not_vacuous(s, status0)
+    assert np.all(s.ncall > s.nacc)
 
 
 def test_slice_gaussian_evidence_and_scatter_in_an_asymmetric_6d_box():

@@ -9,6 +9,7 @@ import pytest
 import de_restated as de
 from conftest import GOLDEN, TRUTHS, TYPES
 from raw_abi import dp, ip, synth_handle
+from test_gpu_nested import launch_class
 
 pytestmark = pytest.mark.gpu
 
@@ -104,6 +105,63 @@ def test_humped_posterior_matches_the_restatement_with_lnprob_batch():
         h.close()
     _assert_equal(st, ref)
     assert np.all(np.isfinite(ref.lnp.max(axis=1)))
+
+
+def _humped_and_classic(long_set=None):
+    """A handle with the synthetic prior, Humped (ds 0) and Classic (ds 1), or Humped and a light curve of more than 64 points."""
+    from magprop_amd import synth
+    g = np.load(GOLDEN + "/golden_synth.npz")
+    h = synth_handle()
+    h.set_prior(synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK)
+    h.set_dataset(0, g["Humped_x"], g["Humped_y"], g["Humped_yerr"])
+    if long_set is None:
+        h.set_dataset(1, g["Classic_x"], g["Classic_y"], g["Classic_yerr"])
+    else:
+        assert len(long_set[0]) > 64
+        h.set_dataset(1, *long_set)
+    return h
+
+
+@pytest.mark.parametrize("case, strategy", [("team-2", de.BEST1BIN), ("team-2", de.RAND1BIN), ("wave-4", de.BEST1BIN),
+                                            ("wave-2", de.BEST1BIN), ("long", de.BEST1BIN)])
+def test_posterior_matches_the_restatement_with_lnprob_batch_on_the_other_builds(case, strategy, glonglc):
+    """Two populations on different datasets (population 0 on ds 1, population 1 on ds 0) at the smallest launch of each build
+    the 60-member test does not run -- a team with two wavefronts per SIMD (3/8 of the SIMDs), one wavefront per walker with 4
+    steps per lane (3/4) and with 2 (5/4), and the LONG builds on a handle that holds a light curve of 112 points: 5 generations
+    (20 at the two smaller launches) equal the restatement whose evaluations are mp_lnprob_batch calls of the launch's size with
+    every row's dataset."""
+    from magprop_amd import optimize, synth
+    h = _humped_and_classic(tuple(glonglc["synth112_ds"]) if case == "long" else None)
+    try:
+        ns = h.n_simd
+        n, build, gens = {"team-2": (3 * ns // 8, (4, 1, 2), 20), "wave-4": (3 * ns // 4, (1, 4, 1), 5),
+                          "wave-2": (5 * ns // 4, (1, 2, 2), 5), "long": (60, (4, 1, 1), 20)}[case]
+        popsize, ds = n // 2, [1, 0]
+        assert launch_class(2 * popsize, ns) == build and 5 <= popsize <= 1024
+        lo, hi = synth.PRIOR_LOWER, synth.PRIOR_UPPER
+        rng = np.random.default_rng(6)
+        pop0 = np.stack([optimize.latin_hypercube(rng, popsize, lo, hi) for _ in range(2)])
+        ids = np.repeat(np.array(ds, dtype=np.int32), popsize)
+
+        def evaluate(rows):
+            assert rows.shape == (2 * popsize, 6)
+            return h.lnprob_batch(rows, ds_id=ids, want_status=True)
+
+        ref = de.run(pop0, gens, evaluate, 101, strategy, 0.5, 1.0, 0.7, 0.01, 0.0, lo, hi)
+        opt = RawOptimizer(h, popsize, 2, 6, lo, hi, 101, strategy, 0, ds=ds)
+        try:
+            opt.set_population(pop0.reshape(-1, 6))
+            opt.run(gens)
+            st = opt.state()
+        finally:
+            opt.close()
+    finally:
+        h.close()
+    _assert_equal(st, ref)
+    # conditions on the inputs, from the restatement: both populations ran every generation and replaced members
+    assert np.all(ref.nit == gens) and np.all(np.isfinite(ref.lnp.max(axis=1)))
+    assert np.all(np.any(ref.pop != pop0, axis=(1, 2)))
+    print(f"{case}: launch {2 * popsize} {build}, flagged members at the end {int(np.sum(ref.status != 0))}")
 
 
 @pytest.fixture(scope="module")

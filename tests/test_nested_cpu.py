@@ -166,6 +166,77 @@ def test_restatement_dead_points_rise_and_walks_respect_the_constraint():
         assert s.dead_n[r][:8] == list(range(32, 24, -1))
 
 
+def assert_states_equal(a, b, extra=()):
+    """Two restated States field by field: arrays and dead lists with np.array_equal, ln X and ln Z with ==."""
+    for k in ("live", "lnl", "status", "acc", "nit", "stopped", "ncall", "nacc", "nzero") + tuple(extra):
+        assert np.array_equal(getattr(a, k), getattr(b, k)), k
+    for r in range(len(a.nit)):
+        assert np.array_equal(np.array(a.dead_pars[r]), np.array(b.dead_pars[r]))
+        assert np.array_equal(np.array(a.dead_lnl[r]), np.array(b.dead_lnl[r]))
+        assert a.dead_n[r] == b.dead_n[r]
+    assert np.all(a.lnx == b.lnx) and np.all(a.lnz == b.lnz)
+
+
+class RecordingGaussian:
+    """evaluate(rows, runs) of the unit Gaussian that keeps every call's arguments."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __call__(self, rows, runs):
+        self.calls.append((np.array(rows), np.array(runs)))
+        return nr.gaussian(rows)
+
+
+def test_rounds_leave_the_state_of_the_one_at_a_time_path():
+    """3 runs on the unit Gaussian, N = 32, K = 8, 6 iterations as run(2) + run(4): the round-batched driver and the
+    one-at-a-time path leave identical States; the driver hands every row's run through (a row of run r is a point of a walk
+    of run r: the walks of different runs start from different live sets) and the live set's rows carry their run."""
+    lo, hi = np.array([-2.0, -1.0, -4.0]), np.array([3.0, 2.5, 1.5])
+    live0 = lo + (hi - lo) * np.random.default_rng(11).random((3, 32, 3))
+    kw = dict(walks=10, g0=0.0, sigma=0.1, dlogz=1e-6, lower=lo, upper=hi)
+    a = nr.start(live0, nr.gaussian)
+    rec = RecordingGaussian()
+    b = nr.start(live0, rec, with_runs=True)
+    assert len(rec.calls) == 1 and np.array_equal(rec.calls[0][1], np.repeat(np.arange(3), 32))
+    assert np.array_equal(rec.calls[0][0], live0.reshape(-1, 3))
+    for n in (2, 4):
+        nr.run(a, n, 8, 77, evaluate_one=nr.gaussian_one, **kw)
+        nr.run(b, n, 8, 77, evaluate=rec, **kw)
+    assert_states_equal(a, b)
+    assert np.all(a.nit == 6) and np.all(a.nacc > 0) and np.all(a.ncall > a.nacc)
+    rows = sum(len(c[1]) for c in rec.calls[1:])
+    assert rows == a.ncall.sum()                                       # every evaluation went through a round, once
+    for r in range(3):
+        assert sum(int(np.sum(c[1] == r)) for c in rec.calls[1:]) == a.ncall[r]
+    assert all(np.all(np.diff(c[1]) >= 0) and set(c[1]) <= {0, 1, 2} for c in rec.calls[1:])
+    assert 6 < len(rec.calls) - 1 <= 6 * 10                            # at most `walks` rounds an iteration
+
+
+def test_the_round_driver_calls_evaluate_once_per_round_of_the_longest_walk():
+    """The walks of one iteration of 3 runs driven together: as many evaluate calls as the longest walk has evaluations, each
+    with one row per walk still going, and the results of the walks driven one at a time."""
+    lo, hi = np.array([-2.0, -1.0, -4.0]), np.array([3.0, 2.5, 1.5])
+    live0 = lo + (hi - lo) * np.random.default_rng(12).random((3, 32, 3))
+    s = nr.start(live0, nr.gaussian)
+    g0, s3 = nr.resolve(0.0, 0.1, 3)
+    jobs = nr.retire(s, 8, 1e-6)
+
+    def gens():
+        return [nr.walk_rounds(s, r, j, t, surv, lstar, 5, 10, g0, s3, lo, hi) for r, dead, surv, lstar, t in jobs for j in dead]
+
+    runs = [r for r, dead, *_ in jobs for _ in dead]
+    rec = RecordingGaussian()
+    out = nr.in_rounds(gens(), runs, rec)
+    one = [nr.one_at_a_time(g, nr.gaussian_one) for g in gens()]
+    assert len(out) == 24 and out == one
+    evals = np.array([o[4] for o in out])
+    assert len(rec.calls) == evals.max() and evals.min() < evals.max()
+    for k, (rows, rr) in enumerate(rec.calls):
+        assert len(rows) == np.sum(evals > k) and rr.tolist() == [runs[i] for i in np.nonzero(evals > k)[0]]
+    assert nr.in_rounds([], [], rec) == [] and len(rec.calls) == evals.max()
+
+
 def test_stop_rule():
     assert not nr.stops(-1.0, 0.0, -np.inf, 0.01)
     assert not nr.stops(-np.inf, 0.0, -np.inf, 0.01)

@@ -14,6 +14,7 @@ from scipy.special import erf
 import nest_restated as nr
 import nest_slice_restated as sr
 from conftest import ROOT
+from test_nested_cpu import RecordingGaussian, assert_states_equal
 
 LO, HI = np.array([-1.5, -0.7, -2.0]), np.array([2.0, 1.2, 0.8])
 C_LEVEL = 1.5        # the region {0.5 |x|^2 < 1.5} cut by the asymmetric box LO, HI
@@ -96,6 +97,50 @@ def test_restated_slice_run_finds_the_gaussian_evidence():
     assert 0 <= s.nfail[0] <= 0.01 * slices * walks and s.nzero[0] <= s.nfail[0]
     assert s.ncall[0] >= s.nacc[0] and s.ncontract[0] <= s.ncall[0]
     assert s.dead_lnl[0][-1] <= np.min(s.lnl[0])
+
+
+def test_slice_rounds_leave_the_state_of_the_one_at_a_time_path():
+    """3 runs on the unit Gaussian, N = 32, K = 8, 3 slices per walk, 6 iterations as run(2) + run(4): the round-batched driver
+    and the one-at-a-time path leave identical States (the slice counters among them), and every row's run is handed through."""
+    lo, hi = np.array([-2.0, -1.0, -4.0]), np.array([3.0, 2.5, 1.5])
+    live0 = lo + (hi - lo) * np.random.default_rng(11).random((3, 32, 3))
+    kw = dict(mu=1.0, max_steps_out=4, max_shrink=32, dlogz=1e-6, lower=lo, upper=hi)
+    a = sr.start(live0, nr.gaussian)
+    rec = RecordingGaussian()
+    b = sr.start(live0, rec, with_runs=True)
+    assert len(rec.calls) == 1 and np.array_equal(rec.calls[0][1], np.repeat(np.arange(3), 32))
+    for n in (2, 4):
+        sr.run(a, n, 8, 78, 3, evaluate_one=nr.gaussian_one, **kw)
+        sr.run(b, n, 8, 78, 3, evaluate=rec, **kw)
+    assert_states_equal(a, b, extra=("nexpand", "ncontract", "nfail"))
+    assert np.all(a.nit == 6) and np.all(a.nexpand > 0) and np.all(a.ncontract > 0)
+    for r in range(3):
+        assert sum(int(np.sum(c[1] == r)) for c in rec.calls[1:]) == a.ncall[r]
+    assert all(np.all(np.diff(c[1]) >= 0) for c in rec.calls[1:])
+
+
+def test_the_round_driver_calls_evaluate_once_per_round_of_the_longest_slice_walk():
+    """The slice walks of one iteration of 3 runs driven together: as many evaluate calls as the longest walk has evaluations,
+    one row per walk still going, and the results of the walks driven one at a time."""
+    lo, hi = np.array([-2.0, -1.0, -4.0]), np.array([3.0, 2.5, 1.5])
+    live0 = lo + (hi - lo) * np.random.default_rng(12).random((3, 32, 3))
+    s = sr.start(live0, nr.gaussian)
+    jobs = nr.retire(s, 8, 1e-6)
+
+    def gens():
+        return [sr.slice_walk_rounds([float(v) for v in s.live[r, surv[0]]], float(s.lnl[r, surv[0]]), 0, t, r, j, s.live[r, surv],
+                                     lstar, 5, 3, 1.0, 4, 32, lo, hi)
+                for r, dead, surv, lstar, t in jobs for j in dead]             # (every walk from its run's first survivor)
+
+    runs = [r for r, dead, *_ in jobs for _ in dead]
+    rec = RecordingGaussian()
+    out = nr.in_rounds(gens(), runs, rec)
+    one = [nr.one_at_a_time(g, nr.gaussian_one) for g in gens()]
+    assert len(out) == 24 and out == one
+    evals = np.array([o[4] for o in out])
+    assert len(rec.calls) == evals.max() and evals.min() < evals.max()
+    for k, (rows, rr) in enumerate(rec.calls):
+        assert len(rows) == np.sum(evals > k) and rr.tolist() == [runs[i] for i in np.nonzero(evals > k)[0]]
 
 
 @pytest.mark.parametrize("kw, match", [
