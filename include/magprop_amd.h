@@ -252,6 +252,34 @@ int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physica
                   double *band_out, int32_t *status_out, int32_t *n_used);
 
 /*
+ * The band of WEIGHTED samples (ABI 5, additive): per grid point the quantiles q[nq] of the weighted empirical distribution of
+ * the curves of n parameter rows under weights[n] -- the dead and live points of a nested run with exp(logwt), or a chain
+ * reweighted to another prior, error model or temperature -- computed on the device, without resampling.  Every argument but
+ * weights is mp_model_band's, and so are the curve pass (one launch of all n rows, the build kernel_spl_curves(n) names), the
+ * limits, the component order, status_out, *n_used and the workspace (plus n uint32 on the device).
+ *
+ * Definition.  A floating-point sum of weights depends on its order and a band must not, so the weights become integers once
+ * and every sum after that is exact.
+ *   units      wmax = the largest weight; u_i = (uint32) floor((w_i / wmax) * 2147483648.0).  The division rounds once, the
+ *              product with 2^31 and the floor are exact.  The heaviest row has exactly 2^31 units; a row below 2^-31 of it has
+ *              none and drops out.  The weights have to be finite and >= 0 with at least one > 0: MP_EINVAL otherwise, judged
+ *              before a handle is needed.  mp_band_weight_units is this conversion alone (host only, no handle).
+ *   per grid point   the used values are the column's non-NaN ones (a row that did not finish is NaN everywhere).  W = the sum
+ *              of their units (below 2^46 at n <= MP_BAND_MAX_SAMPLES, so exact in a double); W == 0: NaN.  Target
+ *              T = ceil(q * (double)W), the product rounded once, clamped to [1, W].  The answer is the least used value v whose
+ *              cumulative units over the used values <= v reach T.  Values are ordered as mp_model_band orders them, -0.0 below
+ *              +0.0.  No interpolation: this is the weighted empirical distribution function, the rule of numpy's
+ *              method="inverted_cdf" (equal weights give np.nanquantile(curves, q, axis=0, method="inverted_cdf")).  q = 0
+ *              answers the least value that carries weight, q = 1 the largest.
+ * No floating-point atomic and no floating-point sum anywhere: the result is a function of the rows and their weights, bit for
+ * bit, in whatever order they come.  No row finished, or no weight on those that did: all NaN and MP_OK.  (tests/wband_restated.py
+ * is this definition in numpy.)
+ */
+int mp_band_weight_units(const double *weights, int n, uint32_t *units_out);
+int mp_model_band_weighted(mp_handle *h, const double *pars, int n, int ndim, int physical, const double *weights, const double *q,
+                           int nq, uint32_t components, double *band_out, int32_t *status_out, int32_t *n_used);
+
+/*
  * Energy budgets and light-curve landmarks of the model of n parameter rows, computed on the device (ABI 5, additive): the
  * physical quantities a fit implies, which are functions of a sample's whole curves and trajectory (how much energy it
  * radiates and through which channel, when and how high it peaks, by when half of the energy is out, how far accretion spins

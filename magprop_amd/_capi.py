@@ -51,6 +51,7 @@ class ModelCfg(C.Structure):
 
 _i, _u32, _i64, _u64, _d = C.c_int, C.c_uint32, C.c_int64, C.c_uint64, C.c_double
 _vp, _dp, _ip, _i64p, _cfgp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(ModelCfg)
+_u32p = C.POINTER(C.c_uint32)
 # name -> (restype, argtypes) of every function of include/magprop_amd.h, in header order (tests/test_capi_cpu.py holds the two
 # together).  Handles, samplers, optimizers, nested samplers and streams are c_void_p; so are the host pointers of
 # mp_lnprob_batch, passed as integers (the hot entry), and the device pointers.
@@ -70,6 +71,8 @@ SIGNATURES = {
     "mp_model_lc": (_i, [_vp, _dp, _i, _dp, _dp, _ip]),
     "mp_rhs_batch": (_i, [_vp, _dp, _i, _dp, _dp, _i, _dp, _dp]),
     "mp_model_band": (_i, [_vp, _dp, _i, _i, _i, _dp, _i, _u32, _dp, _ip, _ip]),
+    "mp_band_weight_units": (_i, [_dp, _i, _u32p]),
+    "mp_model_band_weighted": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _u32, _dp, _ip, _ip]),
     "mp_model_derived": (_i, [_vp, _dp, _i64, _i, _i, _dp, _ip, _i64p]),
     "mp_pointwise_tail_len": (_i, [_i64]),
     "mp_model_pointwise": (_i, [_vp, _dp, _i64, _i, _i, _i, _dp, _dp, _dp, _ip, _i64p]),
@@ -307,12 +310,43 @@ def read_back(fn, obj, spec, *lead):
     return out
 
 
-def band_result(handle, rows, q, names):
-    """{"t": grid, name: (nq, n_grid) per component, "n_used": rows that entered} of handle.model_band(rows, q, names)."""
-    band, _, used = handle.model_band(rows, q, names)
+def band_weights(weights, n):
+    """weights as contiguous float64 (n,), one per row of a band request: finite, >= 0 and not all zero (mp_band_weight_units'
+    conditions, judged here so that the message names the argument)."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (n,):
+        raise ValueError(f"weights must be of shape ({n},), one per row, got {w.shape}")
+    if not np.all(np.isfinite(w)) or np.any(w < 0.0) or not np.any(w > 0.0):
+        raise ValueError("weights must be finite and >= 0 with at least one > 0")
+    return w
+
+
+def band_weight_units(weights):
+    """The integer units the weighted band gives the rows (mp_band_weight_units): floor(w / max(w) * 2^31) as uint32."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 1 or w.size < 1:
+        raise ValueError(f"weights must be 1-D and not empty, got shape {w.shape}")
+    u = np.empty(w.size, dtype=np.uint32)
+    check(lib().mp_band_weight_units(_dptr(w), int(w.size), u.ctypes.data_as(_u32p)), "mp_band_weight_units")
+    return u
+
+
+def kish_n_eff(weights, status):
+    """Kish's effective sample size (sum w)^2 / sum w^2 over the rows that finished (0.0: none of them carries weight)."""
+    w = np.asarray(weights, dtype=np.float64)[np.asarray(status) == STATUS_OK]
+    s2 = float(np.sum(w * w))
+    return float(np.sum(w)) ** 2 / s2 if s2 > 0.0 else 0.0
+
+
+def band_result(handle, rows, q, names, weights=None):
+    """{"t": grid, name: (nq, n_grid) per component, "n_used": rows that entered} of handle.model_band(rows, q, names); with
+    weights (one per row: the weighted band) also "n_eff", Kish's effective sample size of the rows that finished."""
+    band, st, used = handle.model_band(rows, q, names, weights=weights)
     out = {"t": handle.tgrid.copy()}
     out.update({c: band[k] for k, c in enumerate(names)})
     out["n_used"] = used
+    if weights is not None:
+        out["n_eff"] = kish_n_eff(weights, st)
     return out
 
 
@@ -451,18 +485,25 @@ class Handle(_Owner):
               "mp_model_lc")
         return (st.value, out, traj) if want_traj else (st.value, out)
 
-    def model_band(self, pars, q, components=("Ltot",), physical=False):
+    def model_band(self, pars, q, components=("Ltot",), physical=False, weights=None):
         """Quantiles q of the model light curves of the rows of pars over the handle's grid (mp_model_band): returns
         (band[ncomp, nq, n_grid], status[n], n_used); components in the order Ltot, Lprop, Ldip whatever order they are
-        named in.  physical=False: sampler coordinates under the handle's prior, as lnprob_batch takes them."""
+        named in.  physical=False: sampler coordinates under the handle's prior, as lnprob_batch takes them.  weights (n,),
+        finite and >= 0: the quantiles of the weighted empirical distribution of the curves instead (mp_model_band_weighted:
+        no interpolation, weights in integer units of max(weights) / 2^31)."""
         qa, mask, names = band_args(q, components)
         p = band_rows(pars)
         n, nd = p.shape
+        w = None if weights is None else band_weights(weights, n)
         band = np.empty((len(names), qa.size, self.tgrid.size), dtype=np.float64)
         st = np.empty(n, dtype=np.int32)
         used = C.c_int32(0)
-        check(self._L.mp_model_band(self._h, _dptr(p), n, nd, int(bool(physical)), _dptr(qa), int(qa.size), C.c_uint32(mask),
-                                    _dptr(band), _iptr(st), C.byref(used)), "mp_model_band")
+        if w is None:
+            check(self._L.mp_model_band(self._h, _dptr(p), n, nd, int(bool(physical)), _dptr(qa), int(qa.size), C.c_uint32(mask),
+                                        _dptr(band), _iptr(st), C.byref(used)), "mp_model_band")
+        else:
+            check(self._L.mp_model_band_weighted(self._h, _dptr(p), n, nd, int(bool(physical)), _dptr(w), _dptr(qa), int(qa.size),
+                                                 C.c_uint32(mask), _dptr(band), _iptr(st), C.byref(used)), "mp_model_band_weighted")
         return band, st, int(used.value)
 
     def model_derived(self, pars, physical=False):

@@ -6,6 +6,9 @@
 // dropped; S <= MP_BAND_MAX_SAMPLES = 16 384 keys are 128 KiB), every needed order statistic is found by an MSB-first radix
 // select over 8-bit digits (256-bin histograms, one per wavefront, merged and scanned once per pass), its upper neighbour by
 // one counting pass, and mp_band.h's lerp finishes the quantile.
+// band_wselect_kernel is the select of the weighted band (mp_model_band_weighted): the same walk over sums of the rows' integer
+// units (64-bit histograms; wg_wradix_select of mp_wg.h), one select per quantile and no interpolation.  The keys sit in LDS at
+// their row index, a NaN as the all-ones key; the units stay in global memory, one array shared by every workgroup.
 #include <hip/hip_runtime.h>
 
 #include "mp_band.h"
@@ -105,6 +108,41 @@ __global__ __launch_bounds__(kBandThreads) void band_select_kernel(const double 
     }
 }
 
+// dynamic LDS of the weighted select kernel: the select's words | keys[n] u64, unpacked (row i at keys[i])
+constexpr int kWKeysOffset = sizeof(WgWSelectLds);
+static_assert(kWKeysOffset == 8240 && kWKeysOffset % 16 == 0, "a multiple of 16; with MP_BAND_MAX_SAMPLES keys 139 312 of the CU's 163 840 bytes");
+constexpr uint64_t kNoKey = ~0ull;   // what a NaN is stored as: band_key maps no non-NaN double to it
+
+__global__ __launch_bounds__(kBandThreads) void band_wselect_kernel(const double *__restrict__ cols, const uint32_t *__restrict__ units,
+                                                                    int n, int n_grid, const BandQ q, double *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    WgWSelectLds &s = *reinterpret_cast<WgWSelectLds *>(smem);
+    uint64_t *keys = reinterpret_cast<uint64_t *>(smem + kWKeysOffset);
+    const int g = blockIdx.x;
+    const double *col = cols + (size_t)g * n;
+    // the keys, and W: the units of the rows the column uses
+    unsigned long long w = 0;
+    for (int i = threadIdx.x; i < n; i += kBandThreads) {
+        const double v = col[i];
+        const bool used = !__builtin_isnan(v);
+        keys[i] = used ? band_key(v) : kNoKey;
+        w += used ? units[i] : 0u;
+    }
+    const uint64_t W = wg_across(wave_all(w, WgAdd()), s.wave, WgAdd());   // (its barriers publish the keys)
+    for (int j = 0; j < q.nq; ++j) {
+        double res = __builtin_nan("");
+        if (W != 0) {
+            const uint64_t k = wg_wradix_select(n, band_weight_target(q.q[j], W), s, [keys, units](int i, uint64_t &k, uint32_t &u) {
+                k = keys[i];
+                u = units[i];
+                return k != kNoKey;
+            });
+            res = band_value(k);
+        }
+        if (threadIdx.x == 0) out[(size_t)j * n_grid + g] = res;
+    }
+}
+
 }  // namespace
 
 int launch_band_transpose(const double *src, double *dst, int n, int n_grid, void *stream) {
@@ -120,6 +158,16 @@ int launch_band_select(const double *cols, int n, int n_grid, const BandQ &q, do
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL(band_select_kernel, dim3((unsigned)n_grid), dim3(kBandThreads), lds, (hipStream_t)stream, cols, n, n_grid, q, out);
+    return (int)hipGetLastError();
+}
+
+int launch_band_wselect(const double *cols, const uint32_t *units, int n, int n_grid, const BandQ &q, double *out, void *stream) {
+    const size_t lds = (size_t)kWKeysOffset + sizeof(uint64_t) * (size_t)n;
+    if (lds > 65536) {   // (as above)
+        const hipError_t e = hipFuncSetAttribute((const void *)band_wselect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(band_wselect_kernel, dim3((unsigned)n_grid), dim3(kBandThreads), lds, (hipStream_t)stream, cols, units, n, n_grid, q, out);
     return (int)hipGetLastError();
 }
 

@@ -724,34 +724,39 @@ int mp_model_lc(mp_handle *h, const double *pars, int ndim, double *out, double 
     });
 }
 
-// One launch of all n rows (the curve build kernel_spl_curves names depends on the launch size), then per component a transpose
-// into point-major columns and the select.
-int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physical, const double *q, int nq, uint32_t components,
-                  double *band_out, int32_t *status_out, int32_t *n_used) {
-    if (!h || !pars || !q || !band_out) return fail(MP_EINVAL, "mp_model_band: NULL argument");
-    if (n < 1 || n > MP_BAND_MAX_SAMPLES) return fail(MP_EINVAL, "mp_model_band: n must be 1..%d (MP_BAND_MAX_SAMPLES), got %d", MP_BAND_MAX_SAMPLES, n);
-    if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "mp_model_band: ndim must be 6..9, got %d", ndim);
-    if (nq < 1 || nq > MP_BAND_MAX_Q) return fail(MP_EINVAL, "mp_model_band: nq must be 1..%d (MP_BAND_MAX_Q), got %d", MP_BAND_MAX_Q, nq);
+// mp_model_band and mp_model_band_weighted (who; units[n]: the weighted one, the weights already in integer units): one launch of
+// all n rows (the curve build kernel_spl_curves names depends on the launch size), then per component a transpose into
+// point-major columns and the select -- by rank, or with units by cumulative units, which are uploaded behind the curve launch.
+static int model_band(const char *who, mp_handle *h, const double *pars, int n, int ndim, int physical, const uint32_t *units,
+                      const double *q, int nq, uint32_t components, double *band_out, int32_t *status_out, int32_t *n_used) {
+    if (!h || !pars || !q || !band_out) return fail(MP_EINVAL, "%s: NULL argument", who);
+    if (n < 1 || n > MP_BAND_MAX_SAMPLES) return fail(MP_EINVAL, "%s: n must be 1..%d (MP_BAND_MAX_SAMPLES), got %d", who, MP_BAND_MAX_SAMPLES, n);
+    if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "%s: ndim must be 6..9, got %d", who, ndim);
+    if (nq < 1 || nq > MP_BAND_MAX_Q) return fail(MP_EINVAL, "%s: nq must be 1..%d (MP_BAND_MAX_Q), got %d", who, MP_BAND_MAX_Q, nq);
     for (int j = 0; j < nq; ++j)
-        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(MP_EINVAL, "mp_model_band: q[%d] = %g is not in [0, 1]", j, q[j]);
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(MP_EINVAL, "%s: q[%d] = %g is not in [0, 1]", who, j, q[j]);
     static_assert(MP_BAND_LTOT == kCurveLtot && MP_BAND_LPROP == kCurveLprop && MP_BAND_LDIP == kCurveLdip, "a component mask is a curve set");
     const uint32_t all = MP_BAND_LTOT | MP_BAND_LPROP | MP_BAND_LDIP;
-    if (components == 0 || (components & ~all)) return fail(MP_EINVAL, "mp_model_band: components 0x%x is not a non-empty mask of MP_BAND_*", components);
+    if (components == 0 || (components & ~all)) return fail(MP_EINVAL, "%s: components 0x%x is not a non-empty mask of MP_BAND_*", who, components);
     Evaluator *ev = h->first();
     Held held(h, ev);
     const size_t ng = ev->tgrid.size();
     const int ncomp = __builtin_popcount(components);
     int rc;
     if ((rc = ev->w_band.ensure((size_t)n * ng)) || (rc = ev->w_band_out.ensure((size_t)ncomp * nq * ng))) return rc;
+    if (units && (rc = ev->w_band_units.ensure((size_t)n))) return rc;
     mp::BandQ bq{};
     for (int j = 0; j < nq; ++j) bq.q[j] = q[j];
     bq.nq = nq;
     int64_t used = 0;
     rc = curve_pass(ev, pars, (size_t)n, ndim, physical, components, (size_t)n, status_out, &used, [&](const CurveChunk &c) {
+        if (units) HIP_TRY(hipMemcpyAsync(ev->w_band_units.p, units, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, c.st));
         for (int i = 0, k = 0; i < 3; ++i) {
             if (!c.curve[i]) continue;
+            double *out = ev->w_band_out.p + (size_t)k * nq * ng;
             int e = mp::launch_band_transpose(c.curve[i], ev->w_band.p, n, (int)ng, (void *)c.st);
-            if (!e) e = mp::launch_band_select(ev->w_band.p, n, (int)ng, bq, ev->w_band_out.p + (size_t)k * nq * ng, (void *)c.st);
+            if (!e) e = units ? mp::launch_band_wselect(ev->w_band.p, ev->w_band_units.p, n, (int)ng, bq, out, (void *)c.st)
+                              : mp::launch_band_select(ev->w_band.p, n, (int)ng, bq, out, (void *)c.st);
             if (e) return fail(MP_EHIP, "band kernel launch failed: %s", hipGetErrorString((hipError_t)e));
             ++k;
         }
@@ -760,6 +765,31 @@ int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physica
     });
     if (!rc && n_used) *n_used = (int32_t)used;
     return rc;
+}
+
+int mp_model_band(mp_handle *h, const double *pars, int n, int ndim, int physical, const double *q, int nq, uint32_t components,
+                  double *band_out, int32_t *status_out, int32_t *n_used) {
+    return model_band("mp_model_band", h, pars, n, ndim, physical, nullptr, q, nq, components, band_out, status_out, n_used);
+}
+
+int mp_band_weight_units(const double *weights, int n, uint32_t *units_out) {
+    if (!weights || !units_out) return fail(MP_EINVAL, "mp_band_weight_units: NULL argument");
+    if (n < 1) return fail(MP_EINVAL, "mp_band_weight_units: n must be at least 1, got %d", n);
+    if (!mp::band_weight_units(weights, n, units_out))
+        return fail(MP_EINVAL, "mp_band_weight_units: the weights must be finite and >= 0 with at least one > 0");
+    return MP_OK;
+}
+
+int mp_model_band_weighted(mp_handle *h, const double *pars, int n, int ndim, int physical, const double *weights, const double *q,
+                           int nq, uint32_t components, double *band_out, int32_t *status_out, int32_t *n_used) {
+    // (the weights first: they are judged without a handle)
+    if (!weights) return fail(MP_EINVAL, "mp_model_band_weighted: NULL argument");
+    if (n < 1 || n > MP_BAND_MAX_SAMPLES)
+        return fail(MP_EINVAL, "mp_model_band_weighted: n must be 1..%d (MP_BAND_MAX_SAMPLES), got %d", MP_BAND_MAX_SAMPLES, n);
+    std::vector<uint32_t> units((size_t)n);
+    if (!mp::band_weight_units(weights, n, units.data()))
+        return fail(MP_EINVAL, "mp_model_band_weighted: the weights must be finite and >= 0 with at least one > 0");
+    return model_band("mp_model_band_weighted", h, pars, n, ndim, physical, units.data(), q, nq, components, band_out, status_out, n_used);
 }
 
 // The rows go through the device in chunks of n_simd rows: five curves of a chunk are the workspace, and every chunk runs the

@@ -148,6 +148,7 @@ struct Evaluator {
     // [pars | t | y] in and [dydt | lam] out.
     DevBuf<double> w_curves;
     DevBuf<double> w_band, w_band_out;   // mp_model_band: [n_grid][n] one component's curves transposed; [components][nq][n_grid]
+    DevBuf<uint32_t> w_band_units;       // mp_model_band_weighted: [n] the rows' weights in integer units
     DevBuf<double> w_derive_out;         // mp_model_derived: [chunk][MP_DERIVED_N]
     DevBuf<double> w_pw_z, w_pw_obs, w_pw_tail;   // mp_model_pointwise: [n_obs][n] cells; [n_obs][MP_POINTWISE_N]; [n_obs][T(n)]
     DevBuf<int32_t> w_dsid, w_status, w_sweeps;

@@ -101,17 +101,19 @@ __device__ inline WgBest wg_best(WgBest b, double *shv, int *shi) {
     return r;
 }
 
-// Inclusive sum over the workgroup's 256 threads (one value each); every thread gets its own prefix.  sh[kWgWaves] is scratch.
-__device__ inline uint32_t wg_inclusive_scan(uint32_t v, uint32_t *sh) {
+// Inclusive sum over the workgroup's 256 threads (one value each, a 32- or 64-bit count); every thread gets its own prefix.
+// sh[kWgWaves] is scratch.
+template <class T>
+__device__ inline T wg_inclusive_scan(T v, T *sh) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d, 64);
+        const T u = __shfl_up(v, d, 64);
         if (lane >= d) v += u;
     }
     if (lane == 63) sh[wave] = v;
     __syncthreads();
-    uint32_t before = 0;
+    T before = 0;
     for (int w = 0; w < wave; ++w) before += sh[w];
     __syncthreads();
     return v + before;
@@ -179,6 +181,79 @@ __device__ uint64_t wg_radix_select(int n, uint32_t r, WgSelectLds &s, Key key) 
         prefix |= (uint64_t)s.digit << shift;
         mask |= (uint64_t)255 << shift;
         r = s.rank;
+        __syncthreads();
+    }
+    return prefix;
+}
+
+// LDS of the weighted select: 64-bit sums of units where the select above counts candidates (three rows of 2^31 units already
+// overflow 32 bits)
+struct WgWSelectLds {
+    unsigned long long hist[kWgWaves * 256];   // one histogram of a digit per wavefront: the units of the candidates in each bin
+    unsigned long long target;                 // of a pass: the target inside the digit taken
+    unsigned long long wave[kWgWaves];         // scratch of the scan; the caller's between selects
+    uint32_t digit;                            // of a pass: the digit taken
+    uint32_t pad;
+};
+
+// The least key whose cumulative units, over the candidates of elements 0 .. n) with keys <= it, reach t (1 <= t <= the units of
+// all candidates): key(i, k, u) says whether element i is a candidate and sets k to its 64-bit key and u to its units (0: the
+// element is there and weighs nothing).  The walk of wg_radix_select over sums of units: per digit the bin with excl < t <= incl
+// is taken and t becomes t - excl, so the key returned always belongs to a candidate with units.  Every thread returns the key.
+template <class Key>
+__device__ uint64_t wg_wradix_select(int n, uint64_t t, WgWSelectLds &s, Key key) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long *my_hist = s.hist + wave * 256;
+    uint64_t prefix = 0, mask = 0;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        for (int i = threadIdx.x; i < kWgWaves * 256; i += kWgThreads) s.hist[i] = 0;
+        __syncthreads();
+        // As above, a wavefront whose takers all fall into one bin adds once -- but a sum of units is a butterfly where a count is
+        // a popcount, so the lanes keep their own sums for as long as that bin stays the same (held: the bin, or -1; the same in
+        // every lane) and the butterfly runs when it changes and behind the last element.  Integer sums: the order is free.
+        int held = -1;
+        unsigned long long mine = 0;
+        const auto flush = [&]() {
+            if (held < 0) return;
+            const unsigned long long sum = wave_all(mine, WgAdd());
+            if (lane == 0) atomicAdd(&my_hist[held], sum);
+            mine = 0;
+        };
+        for (int base = wave * 64; base < n; base += kWgThreads) {
+            const int i = base + lane;
+            uint64_t k = 0;
+            uint32_t u = 0;
+            const bool cand = i < n && key(i, k, u);
+            const bool take = cand & ((k & mask) == prefix);
+            const uint32_t bin = (uint32_t)(k >> shift) & 255u;
+            const uint64_t act = __ballot(take);
+            if (act == 0) continue;
+            const uint32_t bin0 = __shfl(bin, __builtin_ctzll(act), 64);
+            if ((act & (act - 1)) != 0 && __ballot(take && bin == bin0) == act) {   // (a single taker adds for itself)
+                if ((int)bin0 != held) {
+                    flush();
+                    held = (int)bin0;
+                }
+                mine += take ? u : 0u;
+            } else if (take) {
+                atomicAdd(&my_hist[bin], (unsigned long long)u);
+            }
+        }
+        flush();
+        __syncthreads();
+        unsigned long long c = 0;
+#pragma unroll
+        for (int w = 0; w < kWgWaves; ++w) c += s.hist[w * 256 + threadIdx.x];
+        const unsigned long long incl = wg_inclusive_scan(c, s.wave);
+        const unsigned long long excl = incl - c;
+        if (excl < t && t <= incl) {
+            s.digit = threadIdx.x;
+            s.target = t - excl;
+        }
+        __syncthreads();
+        prefix |= (uint64_t)s.digit << shift;
+        mask |= (uint64_t)255 << shift;
+        t = s.target;
         __syncthreads();
     }
     return prefix;

@@ -283,17 +283,20 @@ class EnsembleSampler:
     def acceptance_fraction(self):
         return self.get_last_sample()[2] / max(self.iteration, 1)
 
-    def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), discard=0, thin=1, ensemble=0):
+    def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), discard=0, thin=1, ensemble=0, weights=None):
         """Posterior-predictive band over the stored chain: the quantiles q of the model light curves of the rows
         chain[discard::thin, ensemble's walkers], evaluated on this sampler's handle (its prior, grid and configuration).
-        Returns {"t": grid, "Ltot": (nq, n_grid), ..., "n_used": rows that entered}."""
+        Returns {"t": grid, "Ltot": (nq, n_grid), ..., "n_used": rows that entered}.  weights: one per selected row, in the
+        order band_selection gives them (a chain reweighted to another prior, error model or temperature): the weighted band
+        (mp_model_band_weighted), and "n_eff" in the result."""
         if self._target != 0:
             raise ValueError("get_model_band needs the posterior target: a target='gaussian' sampler has no light curve")
         qa, _, names = _capi.band_args(q, components)
         # (tempered: the beta = 1 walkers of group `ensemble`)
         rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
                               discard, thin, ensemble)
-        return _capi.band_result(self.handle, rows, qa, names)
+        w = None if weights is None else _capi.band_weights(weights, rows.shape[0])
+        return _capi.band_result(self.handle, rows, qa, names, w)
 
     def get_derived(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, ensemble=0):
         """Energy budgets and light-curve landmarks over the stored chain (magprop_amd.derived.NAMES): the model of every row of

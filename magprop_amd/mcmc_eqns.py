@@ -101,6 +101,22 @@ def lnprob(pars, data, GRBtype, custom_lims=None, device=-1, reference_quirk=Fal
     return _evaluate(p, data, GRBtype, lo, hi, 0 if reference_quirk else LIB_LOG_MASK, device)
 
 
+def model_band(samples, GRBtype, custom_lims=None, q=(0.025, 0.5, 0.975), components=("Ltot",), weights=None, device=-1):
+    """Posterior-predictive band of the library model: per point of the grid of ``GRBtype``, the quantiles q of the light
+    curves of the rows of `samples` (n, 6..9) in the sampler coordinates of ``lnprob`` (rows outside the prior or whose model
+    failed are left out).  With weights (one per row, finite and >= 0) the quantiles of the weighted empirical distribution of
+    the curves, without interpolation (mp_model_band_weighted).  Returns what ``synth.model_band`` returns."""
+    qa, _, names = _capi.band_args(q, components)
+    p = _capi.band_rows(samples)
+    if not 6 <= p.shape[1] <= 9:
+        raise ValueError(f"samples must be 2-D (n, 6..9), got shape {p.shape}")
+    w = None if weights is None else _capi.band_weights(weights, p.shape[0])
+    lo, hi = _bounds(p.shape[1], custom_lims)
+    with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
+        eng.set_prior(lo, hi, LIB_LOG_MASK)
+        return _capi.band_result(eng.handle, p, qa, names, w)
+
+
 def model_derived(samples, GRBtype, custom_lims=None, q=(0.16, 0.5, 0.84), weights=None, device=-1):
     """Energy budgets and light-curve landmarks of the library model of every row of `samples` (n, 6..9) in the sampler
     coordinates of ``lnprob`` (box prior of ``custom_lims``, parameters 3-6 un-logged before the model), on the grid of

@@ -91,6 +91,28 @@ def resample_equal(samples, logwt, rng=None):
     return samples[rng.permutation(idx)]
 
 
+def band_exact_selection(samples, logwt, cap=None):
+    """(rows, weights, weight_dropped) of a weighted band over a run's samples: weights exp(logwt - max); the rows of zero units
+    go (weights below 2^-31 of the largest, mp_band_weight_units: the band gives them no part, so leaving them out changes
+    nothing), and of more than `cap` (default _capi.BAND_MAX_SAMPLES) remaining rows the heaviest `cap` stay (ties: the earlier
+    row), all in the run's order.  weight_dropped is the share of the run's total weight on the rows the cap cut: 0.0 when it cut
+    none."""
+    samples = np.asarray(samples, dtype=np.float64)
+    lw = np.asarray(logwt, dtype=np.float64)
+    if samples.ndim != 2 or lw.shape != (samples.shape[0],) or lw.size == 0:
+        raise ValueError("one log-weight per sample expected")
+    cap = _capi.BAND_MAX_SAMPLES if cap is None else int(cap)
+    w = np.exp(lw - np.max(lw))
+    units = np.floor(w * 2147483648.0)              # (max(w) == 1.0: the ratio of mp_band_weight_units is w itself)
+    keep = np.nonzero(units > 0)[0]
+    dropped = 0.0
+    if keep.size > cap:
+        order = np.argsort(-w[keep], kind="stable")
+        dropped = float(np.sum(w[np.sort(keep[order[cap:]])])) / float(np.sum(w))
+        keep = np.sort(keep[order[:cap]])
+    return np.ascontiguousarray(samples[keep]), w[keep], dropped
+
+
 def _check_args(x, datasets, nlive, nbatch, walks, variant, ndim, bounds, n_runs, g0, sigma, target):
     """(box lower, box upper, prior lower, prior upper, log mask, nbatch, number of datasets): every check, no device touched."""
     if target not in TARGETS:
@@ -297,13 +319,27 @@ class NestedSampler:
         r = self._run(run)
         return resample_equal(r.samples, r.logwt, self.seed if seed is None else seed)
 
-    def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), run=0):
-        """Posterior-predictive band of run `run`: the quantiles q of the model light curves of its equal-weight samples (at most
-        _capi.BAND_MAX_SAMPLES, evenly thinned), on this sampler's handle (mp_model_band).  Returns {"t": grid, "Ltot": (nq,
-        n_grid), ..., "n_used": rows that entered}."""
+    def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), run=0, weights="resample"):
+        """Posterior-predictive band of run `run` on this sampler's handle.  weights="resample" (the default): the quantiles q
+        of the model light curves of its equal-weight samples (at most _capi.BAND_MAX_SAMPLES, evenly thinned; mp_model_band).
+        Returns {"t": grid, "Ltot": (nq, n_grid), ..., "n_used": rows that entered}.  weights="exact": no resampling -- the
+        run's own samples under their weights (band_exact_selection; mp_model_band_weighted), a function of the run alone; the
+        result also holds "n_eff" (Kish's effective sample size of the rows that entered) and "weight_dropped", the share of
+        the run's weight on rows the cap of _capi.BAND_MAX_SAMPLES cut (a RuntimeWarning above 1e-3)."""
         if self.target != "posterior":
             raise ValueError("get_model_band needs the posterior target: the gaussian target has no light curve")
+        if weights not in ("resample", "exact"):
+            raise ValueError(f"weights must be 'resample' or 'exact', got {weights!r}")
         qa, _, names = _capi.band_args(q, components)
+        if weights == "exact":
+            r = self._run(run)
+            rows, w, dropped = band_exact_selection(r.samples, r.logwt)
+            if dropped > 1.0e-3:
+                warnings.warn(f"run {run}: the {rows.shape[0]} heaviest samples leave {dropped:.2e} of the weight out of the band",
+                              RuntimeWarning, stacklevel=2)
+            out = _capi.band_result(self.handle, rows, qa, names, w)
+            out["weight_dropped"] = dropped
+            return out
         rows = self.resample_equal(run)
         if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
             rows = rows[np.linspace(0, rows.shape[0] - 1, _capi.BAND_MAX_SAMPLES).astype(int)]

@@ -71,25 +71,23 @@ def lnprob(pars, x, y, yerr, fbad=None, device=-1):
     return out
 
 
-def model_band(samples, q=(0.025, 0.5, 0.975), components=("Ltot",), device=-1):
+def model_band(samples, q=(0.025, 0.5, 0.975), components=("Ltot",), device=-1, weights=None):
     """Posterior-predictive band of the synthetic model: per point of the grid logspace(0, 6, 10001), the quantiles q of the
     light curves of `samples` (rows in sampler coordinates, as a chain stores them; rows outside the prior or whose model
     failed are left out, as np.nanquantile leaves out NaN).  The reference's plot_synth.py:143-206 takes percentiles of the
     parameters and draws one curve at their medians instead.  Returns {"t": tarr, "Ltot": (nq, n_grid), ..., "n_used": rows
-    that entered}; a grid point no row reached is NaN."""
+    that entered}; a grid point no row reached is NaN.  weights (one per row, finite and >= 0): the quantiles of the weighted
+    empirical distribution of the curves (mp_model_band_weighted, no interpolation), and "n_eff", Kish's effective sample size
+    of the rows that entered."""
     qa, _, names = _capi.band_args(q, components)
     p = _capi.band_rows(samples, 6)
+    w = None if weights is None else _capi.band_weights(weights, p.shape[0])
     eng = engine.acquire(_cfg(), None, device)
     try:
         eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
-        band, _, used = eng.handle.model_band(p, qa, names)
-        tarr = eng.handle.tgrid.copy()
+        return _capi.band_result(eng.handle, p, qa, names, w)
     finally:
         engine.release(eng)
-    out = {"t": tarr}
-    out.update({c: band[k] for k, c in enumerate(names)})
-    out["n_used"] = used
-    return out
 
 
 def model_derived(samples, q=(0.16, 0.5, 0.84), weights=None, device=-1):
