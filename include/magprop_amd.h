@@ -388,6 +388,105 @@ int mp_model_pointwise(mp_handle *h, const double *pars, int64_t n, int ndim, in
                        double *tail_out, double *z_out, int32_t *status_out, int64_t *n_used);
 
 /*
+ * Radii, mass flows and torques of the model of n parameter rows, computed on the device (ABI 5, additive): the quantities
+ * INSIDE the model, recovered from the integrated (Mdisc, omega) as code/figure_3.py:202-286 recovers them and
+ * code/figure_4.py:139-175 plots them -- the Alfven, corotation and light-cylinder radii, the fastness parameter, the
+ * propelled, accreted and fallback mass-flow rates, the accretion and dipole torques -- and per row their reduction to a mass
+ * budget, an angular-momentum budget and the answer to whether the sample lives as a propeller or as an accretor.  pars, ndim,
+ * physical, status_out and n_used are mp_model_derived's; out[n][MP_FLOW_N] and curves_out are host buffers, and the call
+ * returns when the results are in them.  curve_mask selects the cell curves that are returned: bit c is curve MP_FLOW_CURVE_c,
+ * curves_out[n][popcount(curve_mask)][n_grid] holds them in the order of the bits (NULL with curve_mask == 0 only).  A row whose
+ * status is not MP_STATUS_OK gets NaN columns and NaN cells; no row finished: all NaN and MP_OK.  No dataset is needed; a
+ * multi-device handle runs the call on its first device; cfg.dipole_torque = 1 is served.
+ *
+ * Cell curves, cgs, at every grid point from the row's Mdisc and omega there (what mp_model_lc returns in traj).  They describe
+ * the integrated system: the switch is cfg.n_ode (not the luminosity stage's n_lum), cfg.rm_massflow_factor and
+ * cfg.inertia_factor apply as in the right-hand side, and the arithmetic is the right-hand side's own (the device functions
+ * the solver calls, with the row's constants un-logged once, by the function the curve kernels call):
+ *   RM         Alfven radius mu^(4/7) GM^(-1/7) (f Mdisc / tvisc)^(-2/7) after the cap Rm >= k Rlc -> k Rlc
+ *   RC, RLC    corotation radius (GM / omega^2)^(1/3); light-cylinder radius c / omega
+ *   FASTNESS   w = (Rm / Rc)^1.5
+ *   MDOT_PROP  eta2 Mdisc / tvisc, eta2 = (1 + tanh(n (w - 1))) / 2;  MDOT_ACC: eta1 Mdisc / tvisc, eta1 = (1 - tanh(..)) / 2
+ *              formed from e = exp(-2 n |w - 1|) as e / (1 + e) or 1 / (1 + e), never as 1 - eta2: the small one of the two keeps
+ *              its relative accuracy (and is exactly 0 where a whole wavefront has n |w - 1| > 19.5: it is below 1.2e-17 there)
+ *   MDOT_FB    (M0 / tfb) ((t + tfb) / tfb)^(-5/3)
+ *   N_ACC      sqrt(GM max(Rm, R)) (Mdot_acc - Mdot_prop), 0 where the rotation parameter T/|W| exceeds 0.27 (the ODE's rule)
+ *   N_DIP      -mu^2 omega^3 / (6 c^3); cfg.dipole_torque = 1: -(2/3) (mu^2 omega^3 / c^3) (Rlc / Rm)^3
+ *   BRANCH     0 .. 3 as a double: bit 0 = the cap is active, bit 1 = Rm >= R
+ * dMdisc/dt = MDOT_FB - MDOT_PROP - MDOT_ACC and domega/dt = (N_ACC + N_DIP) / I are what mp_rhs_batch returns there.
+ *
+ * Columns.  G = n_grid, t_i the grid:
+ *   M_FB, M_PROP, M_ACC    trapezoids of MDOT_FB, MDOT_PROP, MDOT_ACC over the grid (g), formed as mp_model_derived forms E_TOT
+ *   J_ACC, J_DIP           trapezoids of N_ACC, N_DIP (g cm^2 / s): angular momentum gained by accretion, lost to the dipole
+ *   W_MAX, T_W_MAX, W_END  the largest fastness, its grid time (first occurrence), the fastness at the last grid point
+ *   N_PROP                 grid points with FASTNESS >= 1 (the propeller side, eta2 >= 1/2)
+ *   T_PROP_FIRST, T_PROP_LAST   grid time of the first and of the last such point; NaN when there is none
+ *   N_SWITCH               intervals i with (w_i >= 1) != (w_{i+1} >= 1)
+ *   N_CAPPED, N_INSIDE     grid points with BRANCH bit 0 set; with bit 1 clear (the Alfven radius inside the star)
+ *   RM_MIN, T_RM_MIN       the smallest RM and its grid time (first occurrence)
+ * Every column is a function of the row's cells and the grid alone.  Order of the sums: mp_model_derived's (256 contiguous
+ * segments of ceil((G - 1) / 256) intervals, terms in increasing i from 0.0, segment totals in segment order from 0.0, no FMA
+ * contraction, no floating-point atomic).  Counts are integers, and extrema and first / last indices are taken under total
+ * orders (larger value then lower index; least index), so they have no order to state.  (tests/flows_restated.py is the cells
+ * and the reduction in numpy.)
+ *
+ * n has no cap: the rows go through the device in chunks of mp_n_simd(h) rows, each one launch of the curve kernels with the
+ * Mdisc and omega curves only (the build mp_model_lc runs for a single row), the cells launch, the reduction launch and the
+ * copies, all on the handle's stream with one wait at the end.  A row's numbers are therefore bit for bit the two kernels
+ * applied to what mp_model_lc returns in traj for that row alone, whatever n is and wherever the row sits.  Workspace:
+ * 12 * min(n, mp_n_simd) * n_grid doubles (the two curves and the ten cell curves of a chunk; 983 MB at 1 024 x 10 001), owned
+ * by the handle's evaluator, grow-only, freed by mp_destroy.
+ */
+#define MP_FLOW_NCURVES 10
+#define MP_FLOW_CURVE_RM 0
+#define MP_FLOW_CURVE_RC 1
+#define MP_FLOW_CURVE_RLC 2
+#define MP_FLOW_CURVE_FASTNESS 3
+#define MP_FLOW_CURVE_MDOT_PROP 4
+#define MP_FLOW_CURVE_MDOT_ACC 5
+#define MP_FLOW_CURVE_MDOT_FB 6
+#define MP_FLOW_CURVE_N_ACC 7
+#define MP_FLOW_CURVE_N_DIP 8
+#define MP_FLOW_CURVE_BRANCH 9
+#define MP_FLOW_N 16
+#define MP_FLOW_M_FB 0
+#define MP_FLOW_M_PROP 1
+#define MP_FLOW_M_ACC 2
+#define MP_FLOW_J_ACC 3
+#define MP_FLOW_J_DIP 4
+#define MP_FLOW_W_MAX 5
+#define MP_FLOW_T_W_MAX 6
+#define MP_FLOW_W_END 7
+#define MP_FLOW_N_PROP 8
+#define MP_FLOW_T_PROP_FIRST 9
+#define MP_FLOW_T_PROP_LAST 10
+#define MP_FLOW_N_SWITCH 11
+#define MP_FLOW_N_CAPPED 12
+#define MP_FLOW_N_INSIDE 13
+#define MP_FLOW_RM_MIN 14
+#define MP_FLOW_T_RM_MIN 15
+int mp_model_flows(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, double *out, uint32_t curve_mask,
+                   double *curves_out, int32_t *status_out, int64_t *n_used);
+
+/*
+ * Bands of the cell curves above over n samples (ABI 5, additive): per grid point and selected curve, the quantiles q[nq] over
+ * the rows that finished, band_out[popcount(curve_mask)][nq][n_grid] in the order of the mask's bits.  weights == NULL: every
+ * row counts once and a quantile is np.nanquantile(..., method="linear") of the column, as in mp_model_band; else weights[n]
+ * under mp_model_band_weighted's rule (mp_band_weight_units).  Limits are mp_model_band's: 1 <= n <= MP_BAND_MAX_SAMPLES,
+ * 1 <= nq <= MP_BAND_MAX_Q, q in [0, 1]; curve_mask is a non-empty mask of MP_FLOW_CURVE_* bits without BRANCH (a flag has no
+ * quantile: MP_EINVAL).  status_out[n] and *n_used are optional.
+ *
+ * The rows go through the chunked pass of mp_model_flows (only the selected curves are written), every chunk's cells landing at
+ * its row offset of an n x n_grid matrix per selected curve; those matrices then go through mp_model_band's transpose and select
+ * kernels.  The band is therefore the band of what mp_model_flows returns in curves_out for the same rows.  Workspace:
+ * (popcount(curve_mask) + 1) * n * n_grid + 2 * min(n, mp_n_simd) * n_grid + popcount(curve_mask) * nq * n_grid doubles, owned
+ * by the handle's evaluator.  It is grow-only as mp_model_band's is, except that the popcount(curve_mask) * n * n_grid matrices
+ * of a band of more than one curve (11.8 GB at 9 curves x 16 384 rows) are freed before the call returns.
+ */
+int mp_model_flow_band(mp_handle *h, const double *pars, int n, int ndim, int physical, const double *weights, const double *q,
+                       int nq, uint32_t curve_mask, double *band_out, int32_t *status_out, int32_t *n_used);
+
+/*
  * Ensemble sampler: emcee's affine-invariant stretch move (Goodman & Weare 2010) with a random red/blue
  * split per step, as driven by code/synthetic_datasets/synth_mcmc.py:175-185
  * (em.EnsembleSampler(Nwalk, Npars, lnprob, ...).run_mcmc(pos, Nstep)).  Positions, log-posteriors,

@@ -23,6 +23,9 @@ BAND_LTOT, BAND_LPROP, BAND_LDIP = 1, 2, 4
 BAND_COMPONENTS = {"Ltot": BAND_LTOT, "Lprop": BAND_LPROP, "Ldip": BAND_LDIP}
 DERIVED_N = 16                                                # include/magprop_amd.h MP_DERIVED_N (columns: magprop_amd/derived.py)
 POINTWISE_N, POINTWISE_MAX_SAMPLES, POINTWISE_MAX_CELLS = 12, 262144, 1 << 28   # include/magprop_amd.h MP_POINTWISE_* (columns: magprop_amd/pointwise.py)
+FLOW_N, FLOW_NCURVES = 16, 10                                 # include/magprop_amd.h MP_FLOW_* (columns and curves: magprop_amd/flows.py)
+# cell curves of mp_model_flows in the order of their mask bits MP_FLOW_CURVE_*
+FLOW_CURVES = ("Rm", "Rc", "Rlc", "fastness", "Mdot_prop", "Mdot_acc", "Mdot_fb", "N_acc", "N_dip", "branch")
 DE_BEST1BIN, DE_RAND1BIN = 0, 1                               # include/magprop_amd.h MP_DE_*
 NEST_MIN_LIVE, NEST_MAX_LIVE, NEST_MAX_WALKS = 16, 4096, 4096  # include/magprop_amd.h MP_NEST_*
 NEST_MAX_SLICES, NEST_MAX_STEPS_OUT, NEST_MAX_SHRINK = 4096, 4096, 254
@@ -76,6 +79,8 @@ SIGNATURES = {
     "mp_model_derived": (_i, [_vp, _dp, _i64, _i, _i, _dp, _ip, _i64p]),
     "mp_pointwise_tail_len": (_i, [_i64]),
     "mp_model_pointwise": (_i, [_vp, _dp, _i64, _i, _i, _i, _dp, _dp, _dp, _ip, _i64p]),
+    "mp_model_flows": (_i, [_vp, _dp, _i64, _i, _i, _dp, _u32, _dp, _ip, _i64p]),
+    "mp_model_flow_band": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _u32, _dp, _ip, _ip]),
     "mp_sampler_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _d, _i]),
     "mp_sampler_destroy": (_i, [_vp]),
     "mp_sampler_set_positions": (_i, [_vp, _dp]),
@@ -277,6 +282,20 @@ def band_args(q, components):
     for c in names:
         mask |= BAND_COMPONENTS[c]
     return qa, mask, tuple(c for c in BAND_COMPONENTS if mask & BAND_COMPONENTS[c])
+
+
+def flow_curve_args(curves, band=False):
+    """(mask, names in output order) of a selection of FLOW_CURVES (a name or a sequence of names, no repeats); band=True: not
+    empty and without "branch" (mp_model_flow_band's conditions)."""
+    names = (curves,) if isinstance(curves, str) else tuple(curves)
+    if any(c not in FLOW_CURVES for c in names) or len(set(names)) != len(names):
+        raise ValueError(f"curves must be a selection of {FLOW_CURVES} without repeats, got {curves!r}")
+    if band and (not names or "branch" in names):
+        raise ValueError(f"a flow band takes a non-empty selection of curves without 'branch' (a flag has no quantile), got {curves!r}")
+    mask = 0
+    for c in names:
+        mask |= 1 << FLOW_CURVES.index(c)
+    return mask, tuple(c for k, c in enumerate(FLOW_CURVES) if mask >> k & 1)
 
 
 def band_rows(pars, ndim=None):
@@ -521,6 +540,42 @@ class Handle(_Owner):
         check(self._L.mp_model_derived(self._h, _dptr(p), n, nd, int(bool(physical)), _dptr(out), _iptr(st), C.byref(used)),
               "mp_model_derived")
         return out, st, int(used.value)
+
+    def model_flows(self, pars, curves=(), physical=False):
+        """Mass budget, angular-momentum budget and propeller / accretor regime of the models of the rows of pars
+        (mp_model_flows; the columns are magprop_amd.flows.NAMES): returns (values[n, FLOW_N], cells[n, ncurves, n_grid],
+        status[n], n_used), rows that did not finish all NaN.  curves: names of FLOW_CURVES whose cell curves (radii, fastness,
+        mass-flow rates, torques, cgs) come back too, in the order of FLOW_CURVES whatever order they are named in; none: cells
+        is None.  Any number of rows: the library works through them in chunks.  physical=False: sampler coordinates under the
+        handle's prior, as lnprob_batch takes them."""
+        mask, names = flow_curve_args(curves)
+        p = np.ascontiguousarray(pars, dtype=np.float64)
+        if p.ndim != 2 or p.shape[0] < 1:
+            raise ValueError(f"pars must be 2-D (n >= 1, ndim), got shape {p.shape}")
+        n, nd = p.shape
+        out = np.empty((n, FLOW_N), dtype=np.float64)
+        cells = np.empty((n, len(names), self.tgrid.size), dtype=np.float64) if names else None
+        st = np.empty(n, dtype=np.int32)
+        used = C.c_int64(0)
+        check(self._L.mp_model_flows(self._h, _dptr(p), n, nd, int(bool(physical)), _dptr(out), C.c_uint32(mask),
+                                     _dptr(cells) if names else None, _iptr(st), C.byref(used)), "mp_model_flows")
+        return out, cells, st, int(used.value)
+
+    def model_flow_band(self, pars, q, curves=("fastness",), physical=False, weights=None):
+        """Quantiles q over the rows of pars of the cell curves of model_flows at every grid point (mp_model_flow_band): returns
+        (band[ncurves, nq, n_grid], status[n], n_used), curves in the order of FLOW_CURVES.  Rows, q and weights as in
+        model_band; "branch" is refused."""
+        qa, _, _ = band_args(q, "Ltot")
+        mask, names = flow_curve_args(curves, band=True)
+        p = band_rows(pars)
+        n, nd = p.shape
+        w = None if weights is None else band_weights(weights, n)
+        band = np.empty((len(names), qa.size, self.tgrid.size), dtype=np.float64)
+        st = np.empty(n, dtype=np.int32)
+        used = C.c_int32(0)
+        check(self._L.mp_model_flow_band(self._h, _dptr(p), n, nd, int(bool(physical)), None if w is None else _dptr(w), _dptr(qa),
+                                         int(qa.size), C.c_uint32(mask), _dptr(band), _iptr(st), C.byref(used)), "mp_model_flow_band")
+        return band, st, int(used.value)
 
     def model_pointwise(self, pars, ds_id=0, physical=False, cells=False):
         """Per-observation reductions of the pointwise log-likelihoods of the rows of pars against dataset ds_id

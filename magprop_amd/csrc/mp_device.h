@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <cmath>
 #include <type_traits>
 
 #include "../../include/magprop_amd.h"
@@ -126,6 +127,24 @@ struct DevShared {
                           // used to spend 16 double-precision exponentials per lane on it at every launch)
     mp_model_cfg cfg;
 };
+
+// The derived star constants of DevShared from the model configuration (host; evaluator_create of mp_capi.cpp, and the probe of
+// the flow kernels, which has no handle)
+inline void star_constants(DevShared &s, const mp_model_cfg &cfg) {
+    // star constants, magnetar/funcs.py:7-13,75-76
+    const double M = 1.4 * kMsol;
+    s.GM = kG * M;
+    s.inertia = cfg.inertia_factor * M * kR * kR;
+    s.inv_inertia = 1.0 / s.inertia;
+    const double beta = s.GM / (kR * kC * kC);
+    const double modW = 0.6 * M * kC * kC * (beta / (1.0 - 0.5 * beta));
+    s.crot = 0.5 * s.inertia / modW;
+    s.sqrtGM = std::sqrt(s.GM);
+    s.inv_sqrtGM = 1.0 / s.sqrtGM;
+    s.sqrtR = std::sqrt(kR);
+    s.crm_unit = std::pow(1.0e15 * kR * kR * kR, 4.0 / 7.0) * std::pow(s.GM, -1.0 / 7.0) *
+                 std::pow(cfg.rm_massflow_factor, -2.0 / 7.0);
+}
 
 // Per-launch arguments.
 struct LaunchArgs {

@@ -57,11 +57,14 @@ struct DevBuf {
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf() { if (p) (void)hipFree(p); }
-    int ensure(size_t n) {
-        if (n <= cap) return MP_OK;
+    void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
+    }
+    int ensure(size_t n) {
+        if (n <= cap) return MP_OK;
+        release();
         size_t want = std::max<size_t>(n, 16);
         HIP_TRY(hipMalloc((void **)&p, want * sizeof(T)));
         cap = want;
@@ -143,13 +146,15 @@ struct Evaluator {
     // Workspaces of the host-buffer entry points.  Every user runs under the handle's lock and synchronises the stream before it
     // returns, so no two calls have a workspace in use at once and the entry points may share them.
     DevBuf<double> w_pars, w_lnprob;
-    // w_curves: the curve rows of whichever call runs.  The curve pass of mp_model_lc, mp_model_band, mp_model_derived and
-    // mp_model_pointwise (mp_capi.cpp): [wanted curves][chunk][n_grid]; mp_lnprob_batch with ltot_out: [n][n_grid]; mp_rhs_batch:
+    // w_curves: the curve rows of whichever call runs.  The curve pass of mp_model_lc, mp_model_band, mp_model_derived,
+    // mp_model_pointwise, mp_model_flows and mp_model_flow_band (mp_capi.cpp): [wanted curves][chunk][n_grid]; mp_lnprob_batch with ltot_out: [n][n_grid]; mp_rhs_batch:
     // [pars | t | y] in and [dydt | lam] out.
     DevBuf<double> w_curves;
     DevBuf<double> w_band, w_band_out;   // mp_model_band: [n_grid][n] one component's curves transposed; [components][nq][n_grid]
     DevBuf<uint32_t> w_band_units;       // mp_model_band_weighted: [n] the rows' weights in integer units
     DevBuf<double> w_derive_out;         // mp_model_derived: [chunk][MP_DERIVED_N]
+    DevBuf<double> w_flow_cells, w_flow_out;      // mp_model_flows: [MP_FLOW_NCURVES][chunk][n_grid] cell curves; [chunk][MP_FLOW_N]
+    DevBuf<double> w_flow_band;                   // mp_model_flow_band: [selected curves][n][n_grid]; kept between calls for one curve only
     DevBuf<double> w_pw_z, w_pw_obs, w_pw_tail;   // mp_model_pointwise: [n_obs][n] cells; [n_obs][MP_POINTWISE_N]; [n_obs][T(n)]
     DevBuf<int32_t> w_dsid, w_status, w_sweeps;
     DevBuf<int32_t> w_tile_log;

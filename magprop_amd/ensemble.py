@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi, derived, engine, pointwise, posterior, tempering
+from . import _capi, derived, engine, flows, pointwise, posterior, tempering
 from . import moves as _moves
 
 
@@ -307,6 +307,29 @@ class EnsembleSampler:
         rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
                               discard, thin, ensemble)
         return derived.result(self.handle, rows, q)
+
+    def get_flows(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, ensemble=0, curves=()):
+        """Mass budget, angular-momentum budget and propeller / accretor regime over the stored chain (magprop_amd.flows.NAMES):
+        the model of every row of chain[discard::thin, ensemble's walkers], evaluated and reduced on this sampler's handle
+        (mp_model_flows).  Returns {"values": (rows, 16), "status", "n_used", "summary": flows.summarize(values, q)} and the
+        cell curves named in `curves`."""
+        if self._target != 0:
+            raise ValueError("get_flows needs the posterior target: a target='gaussian' sampler has no trajectory")
+        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
+                              discard, thin, ensemble)
+        return flows.result(self.handle, rows, q, None, curves)
+
+    def get_flow_band(self, q=(0.025, 0.5, 0.975), curves=("fastness",), discard=0, thin=1, ensemble=0, weights=None):
+        """Bands of the radii, mass-flow rates and torques over the stored chain: the quantiles q, per grid point, of the cell
+        curves named in `curves` (flows.CURVES without "branch") over the rows get_model_band takes (mp_model_flow_band).
+        Returns {"t": grid, name: (nq, n_grid), "n_used"}; weights as in get_model_band."""
+        if self._target != 0:
+            raise ValueError("get_flow_band needs the posterior target: a target='gaussian' sampler has no trajectory")
+        qa, _, _ = _capi.band_args(q, "Ltot")
+        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
+                              discard, thin, ensemble)
+        w = None if weights is None else _capi.band_weights(weights, rows.shape[0])
+        return flows.band_result(self.handle, rows, qa, curves, w)
 
     def get_pointwise(self, discard=0, thin=1, ensemble=0):
         """Pointwise predictive scores over the stored chain: PSIS-LOO with its Pareto-k diagnostic and WAIC per observation

@@ -5,7 +5,8 @@ right-hand sides: the propeller model with ``I = 0.8 M R^2``, the factor 3 in th
 and either the packages' dipole torque ``-mu^2 omega^3 / (6 c^3)`` or the alternative
 ``-(2/3) (mu^2 omega^3 / c^3) (Rlc / Rm)^3`` (``mp_model_cfg.dipole_torque = 1``).  ``trajectory(...)`` integrates a
 model over the script's grid, ``np.logspace(0, 6, 10001)`` (:20): what its two ``odeint`` calls (:194-201) return.
-The script's plotting is out of scope.
+``recover(...)`` returns what the script's "Recover radii, Mdotprop, and Mdotacc" section (:202-286) leaves behind for a
+model.  The script's plotting is out of scope.
 """
 import numpy as np
 
@@ -40,3 +41,29 @@ def trajectory(model, B, P, MdiscI, RdiscI, epsilon, delta, device=-1):
     if status != _capi.STATUS_OK:
         return "flag"
     return out[0], traj[0], traj[1]
+
+
+# what code/figure_3.py:206-245 (po_*) and :248-286 (b_*) recover, by the name behind the prefix -> the cell curve of mp_model_flows
+_RECOVERED = {"Rm": "Rm", "Rc": "Rc", "Rlc": "Rlc", "w": "fastness", "Ndip": "N_dip", "Mdotprop": "Mdot_prop", "Mdotacc": "Mdot_acc",
+              "Nacc": "N_acc"}
+
+
+def recover(model, B, P, MdiscI, RdiscI, epsilon, delta, device=-1):
+    """What the script's recovery section leaves in ``po_*`` (model "piroott", code/figure_3.py:206-245) or ``b_*``
+    ("bucciantini", :248-286), on its grid: {"tarr", "Mdisc", "omega", "Rm", "Rc", "Rlc", "w", "Ndip", "Mdotprop", "Mdotacc",
+    "Nacc"} in cgs, the radii, fastness, torques and mass-flow rates computed on the device from the trajectory next to them
+    (mp_model_flows); the string "flag" where the reference's integrator gives up."""
+    if model not in ("piroott", "bucciantini"):
+        raise ValueError("model must be 'piroott' or 'bucciantini'")
+    pars = np.array([[B, P, MdiscI, RdiscI, epsilon, delta]], dtype=np.float64)
+    with engine.use(_cfg(model == "bucciantini"), None, device) as eng:
+        status, out, traj = eng.handle.model_lc(pars[0], want_traj=True)
+        if status != _capi.STATUS_OK:
+            return "flag"
+        _, cells, st, _ = eng.handle.model_flows(pars, curves=tuple(_RECOVERED.values()), physical=True)
+    if st[0] != _capi.STATUS_OK:
+        return "flag"
+    _, names = _capi.flow_curve_args(tuple(_RECOVERED.values()))
+    res = {"tarr": out[0], "Mdisc": traj[0], "omega": traj[1]}
+    res.update({k: cells[0, names.index(c)] for k, c in _RECOVERED.items()})
+    return res

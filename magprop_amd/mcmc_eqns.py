@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from . import _capi, derived, engine, pointwise
+from . import _capi, derived, engine, flows, pointwise
 
 # Default prior box: the values of the reference's magnetar/mcmc_limits.csv:2-10 (rows B, P, log_MdiscI, log_RdiscI,
 # log_epsilon, log_delta, dipeff, propeff, f_beam), kept in code so that nothing depends on the working directory
@@ -129,6 +129,20 @@ def model_derived(samples, GRBtype, custom_lims=None, q=(0.16, 0.5, 0.84), weigh
     with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
         eng.set_prior(lo, hi, LIB_LOG_MASK)
         return derived.result(eng.handle, p, q, weights)
+
+
+def model_flows(rows, GRBtype, custom_lims=None, curves=(), q=(0.16, 0.5, 0.84), weights=None, device=-1):
+    """Mass budget, angular-momentum budget and propeller / accretor regime of the library model of every row of `rows`
+    (n, 6..9) in the sampler coordinates of ``lnprob``, on the grid of ``GRBtype``: what magprop_amd.flows.NAMES lists (the
+    quantities code/figure_4.py:139-175 plots for every burst type, reduced per sample).  Returns what ``synth.model_flows``
+    returns."""
+    p = np.ascontiguousarray(rows, dtype=np.float64)
+    if p.ndim != 2 or not 6 <= p.shape[1] <= 9:
+        raise ValueError(f"rows must be 2-D (n, 6..9), got shape {p.shape}")
+    lo, hi = _bounds(p.shape[1], custom_lims)
+    with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
+        eng.set_prior(lo, hi, LIB_LOG_MASK)
+        return flows.result(eng.handle, p, q, weights, curves)
 
 
 def model_pointwise(samples, data, GRBtype, custom_lims=None, device=-1, cells=False):

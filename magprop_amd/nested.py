@@ -14,7 +14,7 @@ import warnings
 
 import numpy as np
 
-from . import _capi, derived, engine, tempering
+from . import _capi, derived, engine, flows, tempering
 from .optimize import OptimizeResult
 
 TARGETS = {"posterior": 0, "gaussian": 1}
@@ -354,6 +354,39 @@ class NestedSampler:
             raise ValueError("get_derived needs the posterior target: the gaussian target has no light curve")
         r = self._run(run)
         return derived.result(self.handle, r.samples, q, np.exp(r.logwt - np.max(r.logwt)))
+
+    def get_flows(self, q=(0.16, 0.5, 0.84), run=0, curves=()):
+        """Mass budget, angular-momentum budget and propeller / accretor regime of run `run` (magprop_amd.flows.NAMES): the
+        model of every one of its weighted samples, evaluated and reduced on this sampler's handle (mp_model_flows), and the
+        quantiles q under the samples' weights exp(logwt - max(logwt)) -- no resampling.  Returns {"values": (n, 16), "status",
+        "n_used", "summary": flows.summarize(values, q, weights)} and the cell curves named in `curves`."""
+        if self.target != "posterior":
+            raise ValueError("get_flows needs the posterior target: the gaussian target has no trajectory")
+        r = self._run(run)
+        return flows.result(self.handle, r.samples, q, np.exp(r.logwt - np.max(r.logwt)), curves)
+
+    def get_flow_band(self, q=(0.025, 0.5, 0.975), curves=("fastness",), run=0, weights="exact"):
+        """Bands of the radii, mass-flow rates and torques of run `run` (flows.CURVES without "branch"; mp_model_flow_band), with
+        get_model_band's two choices of rows: weights="exact" (the default here) the run's own samples under their weights
+        (band_exact_selection), with "n_eff" and "weight_dropped" in the result; "resample" its equal-weight samples."""
+        if self.target != "posterior":
+            raise ValueError("get_flow_band needs the posterior target: the gaussian target has no trajectory")
+        if weights not in ("resample", "exact"):
+            raise ValueError(f"weights must be 'resample' or 'exact', got {weights!r}")
+        qa, _, _ = _capi.band_args(q, "Ltot")
+        if weights == "exact":
+            r = self._run(run)
+            rows, w, dropped = band_exact_selection(r.samples, r.logwt)
+            if dropped > 1.0e-3:
+                warnings.warn(f"run {run}: the {rows.shape[0]} heaviest samples leave {dropped:.2e} of the weight out of the band",
+                              RuntimeWarning, stacklevel=2)
+            out = flows.band_result(self.handle, rows, qa, curves, w)
+            out["weight_dropped"] = dropped
+            return out
+        rows = self.resample_equal(run)
+        if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
+            rows = rows[np.linspace(0, rows.shape[0] - 1, _capi.BAND_MAX_SAMPLES).astype(int)]
+        return flows.band_result(self.handle, rows, qa, curves)
 
 
 def get_state(L, ns, n_runs, nlive, ndim):

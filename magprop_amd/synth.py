@@ -6,7 +6,7 @@
 """
 import numpy as np
 
-from . import _capi, derived, engine, pointwise
+from . import _capi, derived, engine, flows, pointwise
 
 PRIOR_UPPER = np.array([10.0, 10.0, -2.0, np.log10(2000.0), 2.0, 3.0])   # :40
 PRIOR_LOWER = np.array([1.0e-3, 0.69, -6.0, np.log10(50.0), -2.0, -1.0])  # :41
@@ -106,6 +106,41 @@ def model_derived(samples, q=(0.16, 0.5, 0.84), weights=None, device=-1):
     finally:
         engine.release(eng)
     return res
+
+
+def model_flows(rows, curves=(), q=(0.16, 0.5, 0.84), weights=None, device=-1):
+    """Mass budget, angular-momentum budget and propeller / accretor regime of the synthetic model of every row of `rows`
+    (sampler coordinates, as a chain stores them; any number of rows), on the grid logspace(0, 6, 10001): what
+    magprop_amd.flows.NAMES lists, from the radii, mass-flow rates and torques of the integrated system (mp_model_flows; the
+    quantities code/figure_3.py:202-286 recovers and code/figure_4.py:139-175 plots).  Returns {"values": (n, 16) with rows
+    outside the prior or whose model failed all NaN, "status": (n,), "n_used", "summary": flows.summarize(values, q, weights)}
+    and, per name of flows.CURVES in `curves`, that cell curve (n, n_grid) in cgs, with "t" the grid."""
+    p = np.ascontiguousarray(rows, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 6:
+        raise ValueError(f"rows must be 2-D (n, 6), got shape {p.shape}")
+    eng = engine.acquire(_cfg(), None, device)
+    try:
+        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
+        res = flows.result(eng.handle, p, q, weights, curves)
+    finally:
+        engine.release(eng)
+    return res
+
+
+def model_flow_band(samples, q=(0.025, 0.5, 0.975), curves=("fastness",), device=-1, weights=None):
+    """Bands of the cell curves of model_flows over `samples` (sampler coordinates; up to _capi.BAND_MAX_SAMPLES rows): per grid
+    point, the quantiles q of every curve named in `curves` (flows.CURVES without "branch") over the rows that finished, as
+    model_band gives them for the luminosities (mp_model_flow_band).  Returns {"t", name: (nq, n_grid), "n_used"}; with
+    weights also "n_eff"."""
+    qa, _, _ = _capi.band_args(q, "Ltot")
+    p = _capi.band_rows(samples, 6)
+    w = None if weights is None else _capi.band_weights(weights, p.shape[0])
+    eng = engine.acquire(_cfg(), None, device)
+    try:
+        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
+        return flows.band_result(eng.handle, p, qa, curves, w)
+    finally:
+        engine.release(eng)
 
 
 def model_pointwise(samples, x, y, yerr, device=-1, cells=False):
