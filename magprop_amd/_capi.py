@@ -357,18 +357,6 @@ def kish_n_eff(weights, status):
     return float(np.sum(w)) ** 2 / s2 if s2 > 0.0 else 0.0
 
 
-def band_result(handle, rows, q, names, weights=None):
-    """{"t": grid, name: (nq, n_grid) per component, "n_used": rows that entered} of handle.model_band(rows, q, names); with
-    weights (one per row: the weighted band) also "n_eff", Kish's effective sample size of the rows that finished."""
-    band, st, used = handle.model_band(rows, q, names, weights=weights)
-    out = {"t": handle.tgrid.copy()}
-    out.update({c: band[k] for k, c in enumerate(names)})
-    out["n_used"] = used
-    if weights is not None:
-        out["n_eff"] = kish_n_eff(weights, st)
-    return out
-
-
 class _Owner:
     """close() on `with`-exit and when garbage-collected."""
 

@@ -1,5 +1,5 @@
 // mp_derive.h — energy budgets and light-curve landmarks of model samples (mp_model_derived; include/magprop_amd.h states the
-// definition and the columns MP_DERIVED_*): what the gfx950 reduction kernel (mp_derive.hip), the host driver (mp_capi.cpp) and a
+// definition and the columns MP_DERIVED_*): what the gfx950 reduction kernel (mp_derive.hip), the host driver (mp_summaries.cpp) and a
 // host test share -- the segment rule of the summation order, the workgroup size and the launcher.
 //
 // Order of every sum (a function of the row's curves and of G = n_grid only): the G - 1 intervals are cut into kDeriveThreads =

@@ -1,5 +1,5 @@
 // mp_flows.h — radii, mass flows and torques of model samples (mp_model_flows, mp_model_flow_band; include/magprop_amd.h states the
-// curves MP_FLOW_CURVE_* and the columns MP_FLOW_*): what the gfx950 kernels (mp_flows.hip), the host driver (mp_capi.cpp) and a
+// curves MP_FLOW_CURVE_* and the columns MP_FLOW_*): what the gfx950 kernels (mp_flows.hip), the host driver (mp_summaries.cpp) and a
 // host test share -- the launch arguments and the launchers.
 //
 // flow_cells_kernel turns the (Mdisc, omega) rows of a chunk, as the curve kernels leave them, into up to MP_FLOW_NCURVES cell

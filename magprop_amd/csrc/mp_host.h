@@ -1,8 +1,8 @@
-// mp_host.h — what the host sources of the C ABI share (mp_capi.cpp, mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp).
+// mp_host.h — what the host sources of the C ABI share (mp_capi.cpp, mp_summaries.cpp, mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp).
 //
 // Internal: not installed, never seen by a kernel source.  Error reporting, owners of device memory, pinned memory and events,
 // the two types behind the ABI's handle -- Evaluator, everything that lives on ONE device, and mp_handle, the dealer that owns
-// one evaluator per device and the lock -- and the helpers of mp_capi.cpp that the resident drivers call.  Each driver's own
+// one evaluator per device and the lock -- and the helpers of mp_capi.cpp that the summaries and the resident drivers call.  Each driver's own
 // struct stays in its source file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -147,7 +147,7 @@ struct Evaluator {
     // returns, so no two calls have a workspace in use at once and the entry points may share them.
     DevBuf<double> w_pars, w_lnprob;
     // w_curves: the curve rows of whichever call runs.  The curve pass of mp_model_lc, mp_model_band, mp_model_derived,
-    // mp_model_pointwise, mp_model_flows and mp_model_flow_band (mp_capi.cpp): [wanted curves][chunk][n_grid]; mp_lnprob_batch with ltot_out: [n][n_grid]; mp_rhs_batch:
+    // mp_model_pointwise, mp_model_flows and mp_model_flow_band (mp_summaries.cpp): [wanted curves][chunk][n_grid]; mp_lnprob_batch with ltot_out: [n][n_grid]; mp_rhs_batch:
     // [pars | t | y] in and [dydt | lam] out.
     DevBuf<double> w_curves;
     DevBuf<double> w_band, w_band_out;   // mp_model_band: [n_grid][n] one component's curves transposed; [components][nq][n_grid]
@@ -200,7 +200,7 @@ struct Held {
     Held(mp_handle *h, const Evaluator *e) : lock(h->mu), scope(e->device) {}
 };
 
-// ---------------------------------------------------------------- defined in mp_capi.cpp, used by the drivers
+// ---------------------------------------------------------------- defined in mp_capi.cpp, used by the summaries and the drivers
 int launch_lnprob_ordered(Evaluator *h, const mp::LaunchArgs &a_in, hipStream_t st);
 int check_box(const char *fn, int ndim, const double *lower, const double *upper);
 int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int rows);

@@ -1,5 +1,5 @@
 // mp_pointwise.h — pointwise predictive scores of model samples (mp_model_pointwise; include/magprop_amd.h states the definition
-// and the columns MP_POINTWISE_*): what the gfx950 kernels (mp_pointwise.hip), the host driver (mp_capi.cpp), the probe and a
+// and the columns MP_POINTWISE_*): what the gfx950 kernels (mp_pointwise.hip), the host driver (mp_summaries.cpp), the probe and a
 // host test share -- the tail-length rule, the tile and workgroup sizes, the arguments and the launchers.
 //
 // Cell (s, j): La, Lb the Ltot row of sample s at grid points g_j, g_j + 1; mod = ((Lb - La) * idt_j) * dx_j + La; z = (y_j -

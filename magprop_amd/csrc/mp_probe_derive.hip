@@ -4,7 +4,7 @@
 // reached here is the product's compiled code, through the product's launcher launch_derive.  Nothing here is part of
 // libmagprop_amd.so, of include/magprop_amd.h or of the product's ABI.
 //
-// mpd_run_derive does what the chunk loop of mp_model_derived (mp_capi.cpp) does behind the curve launch, with the curves in the
+// mpd_run_derive does what the chunk loop of mp_model_derived (mp_summaries.cpp) does behind the curve launch, with the curves in the
 // caller's hands.  It returns 0, a hipError_t, or -1 for arguments it refuses; nothing is launched then.
 #include <hip/hip_runtime.h>
 

@@ -4,7 +4,7 @@
 // (build/all/mp_flows.hip.o): the kernels reached here are the product's compiled code, through the product's launchers.
 // Nothing here is part of libmagprop_amd.so, of include/magprop_amd.h or of the product's ABI.
 //
-// mpf_cells does what the chunk loop of mp_model_flows (mp_capi.cpp) does behind the curve launch, with the states in the
+// mpf_cells does what the chunk loop of mp_model_flows (mp_summaries.cpp) does behind the curve launch, with the states in the
 // caller's hands: every state has its own time, the parameter rows are physical, and the star constants come from the caller's
 // mp_model_cfg by the function evaluator_create uses.  mpf_reduce is the reduction launch on caller-given cell curves.  Both
 // return 0, a hipError_t, or -1 for arguments they refuse; nothing is launched then.

@@ -4,7 +4,7 @@
 // kernels reached here are the product's compiled code, through the product's launchers.  Nothing here is part of
 // libmagprop_amd.so, of include/magprop_amd.h or of the product's ABI.
 //
-// Each function does what mp_model_pointwise (mp_capi.cpp) does with one launch, with the buffers in the caller's hands.  It
+// Each function does what mp_model_pointwise (mp_summaries.cpp) does with one launch, with the buffers in the caller's hands.  It
 // returns 0, a hipError_t, or -1 for arguments it refuses; nothing is launched then.
 #include <hip/hip_runtime.h>
 

@@ -73,9 +73,3 @@ def summarize(values, q=(0.16, 0.5, 0.84), weights=None):
             cols = np.stack([weighted_quantile(v[ok, k], qa, w) for k in range(len(NAMES))], axis=1)
     out.update({name: cols[:, k] for k, name in enumerate(NAMES)})
     return out
-
-
-def result(handle, rows, q=(0.16, 0.5, 0.84), weights=None, physical=False):
-    """{"values", "status", "n_used", "summary"} of handle.model_derived(rows) and summarize(values, q, weights)."""
-    values, status, used = handle.model_derived(rows, physical=physical)
-    return {"values": values, "status": status, "n_used": used, "summary": summarize(values, q, weights)}

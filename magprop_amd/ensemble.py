@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi, derived, engine, flows, pointwise, posterior, tempering
+from . import _capi, engine, posterior, summaries, tempering
 from . import moves as _moves
 
 
@@ -283,53 +283,45 @@ class EnsembleSampler:
     def acceptance_fraction(self):
         return self.get_last_sample()[2] / max(self.iteration, 1)
 
+    def _summary_rows(self, name, discard, thin, ensemble):
+        """The rows chain[discard::thin, ensemble's walkers] the front end `name` summarises (band_selection; tempered: the
+        beta = 1 walkers of group `ensemble`)."""
+        if self._target != 0:
+            raise ValueError(f"{name} needs the posterior target: a target='gaussian' sampler has no "
+                             f"{'trajectory' if 'flow' in name else 'light curve'}")
+        return band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
+                              discard, thin, ensemble)
+
     def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), discard=0, thin=1, ensemble=0, weights=None):
         """Posterior-predictive band over the stored chain: the quantiles q of the model light curves of the rows
         chain[discard::thin, ensemble's walkers], evaluated on this sampler's handle (its prior, grid and configuration).
         Returns {"t": grid, "Ltot": (nq, n_grid), ..., "n_used": rows that entered}.  weights: one per selected row, in the
         order band_selection gives them (a chain reweighted to another prior, error model or temperature): the weighted band
         (mp_model_band_weighted), and "n_eff" in the result."""
-        if self._target != 0:
-            raise ValueError("get_model_band needs the posterior target: a target='gaussian' sampler has no light curve")
-        qa, _, names = _capi.band_args(q, components)
-        # (tempered: the beta = 1 walkers of group `ensemble`)
-        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
-                              discard, thin, ensemble)
-        w = None if weights is None else _capi.band_weights(weights, rows.shape[0])
-        return _capi.band_result(self.handle, rows, qa, names, w)
+        rows = self._summary_rows("get_model_band", discard, thin, ensemble)
+        return summaries.band(summaries.on(self.handle), rows, q, components, weights)
 
     def get_derived(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, ensemble=0):
         """Energy budgets and light-curve landmarks over the stored chain (magprop_amd.derived.NAMES): the model of every row of
         chain[discard::thin, ensemble's walkers], evaluated and reduced on this sampler's handle (mp_model_derived).  Returns
         {"values": (rows, 16), "status", "n_used", "summary": derived.summarize(values, q)}."""
-        if self._target != 0:
-            raise ValueError("get_derived needs the posterior target: a target='gaussian' sampler has no light curve")
-        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
-                              discard, thin, ensemble)
-        return derived.result(self.handle, rows, q)
+        rows = self._summary_rows("get_derived", discard, thin, ensemble)
+        return summaries.derived(summaries.on(self.handle), rows, q)
 
     def get_flows(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, ensemble=0, curves=()):
         """Mass budget, angular-momentum budget and propeller / accretor regime over the stored chain (magprop_amd.flows.NAMES):
         the model of every row of chain[discard::thin, ensemble's walkers], evaluated and reduced on this sampler's handle
         (mp_model_flows).  Returns {"values": (rows, 16), "status", "n_used", "summary": flows.summarize(values, q)} and the
         cell curves named in `curves`."""
-        if self._target != 0:
-            raise ValueError("get_flows needs the posterior target: a target='gaussian' sampler has no trajectory")
-        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
-                              discard, thin, ensemble)
-        return flows.result(self.handle, rows, q, None, curves)
+        rows = self._summary_rows("get_flows", discard, thin, ensemble)
+        return summaries.flows(summaries.on(self.handle), rows, q, None, curves)
 
     def get_flow_band(self, q=(0.025, 0.5, 0.975), curves=("fastness",), discard=0, thin=1, ensemble=0, weights=None):
         """Bands of the radii, mass-flow rates and torques over the stored chain: the quantiles q, per grid point, of the cell
         curves named in `curves` (flows.CURVES without "branch") over the rows get_model_band takes (mp_model_flow_band).
         Returns {"t": grid, name: (nq, n_grid), "n_used"}; weights as in get_model_band."""
-        if self._target != 0:
-            raise ValueError("get_flow_band needs the posterior target: a target='gaussian' sampler has no trajectory")
-        qa, _, _ = _capi.band_args(q, "Ltot")
-        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
-                              discard, thin, ensemble)
-        w = None if weights is None else _capi.band_weights(weights, rows.shape[0])
-        return flows.band_result(self.handle, rows, qa, curves, w)
+        rows = self._summary_rows("get_flow_band", discard, thin, ensemble)
+        return summaries.flow_band(summaries.on(self.handle), rows, q, curves, weights)
 
     def get_pointwise(self, discard=0, thin=1, ensemble=0):
         """Pointwise predictive scores over the stored chain: PSIS-LOO with its Pareto-k diagnostic and WAIC per observation
@@ -337,11 +329,8 @@ class EnsembleSampler:
         walkers], evaluated and reduced on this sampler's handle (mp_model_pointwise).  Returns what synth.model_pointwise
         returns.  The selection is capped like get_model_band's: thin a longer chain, or hand its rows to
         synth.model_pointwise / mcmc_eqns.model_pointwise."""
-        if self._target != 0:
-            raise ValueError("get_pointwise needs the posterior target: a target='gaussian' sampler has no light curve")
-        rows = band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
-                              discard, thin, ensemble)
-        return pointwise.result(self.handle, rows, int(ensemble), x=self._times[int(ensemble)])
+        rows = self._summary_rows("get_pointwise", discard, thin, ensemble)
+        return summaries.pointwise(summaries.on(self.handle, int(ensemble), self._times[int(ensemble)]), rows)
 
     def get_autocorr_time(self, c=5.0, tol=50, quiet=False, device=False):
         """emcee's default (quiet=False) raises when the chain is shorter than tol autocorrelation times; the

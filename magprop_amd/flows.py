@@ -85,27 +85,3 @@ def budgets(table, derived_table, pars, cfg):
     mass = np.abs((d["Mdisc_end"] - mdisc0) - (f["M_fb"] - f["M_prop"] - f["M_acc"])) / (f["M_fb"] + f["M_prop"] + f["M_acc"])
     mom = np.abs(inertia * (d["omega_end"] - omega0) - (f["J_acc"] + f["J_dip"])) / (np.abs(f["J_acc"]) + np.abs(f["J_dip"]))
     return {"mass": mass, "momentum": mom}
-
-
-def result(handle, rows, q=(0.16, 0.5, 0.84), weights=None, curves=(), physical=False):
-    """{"values", "status", "n_used", "summary"} of handle.model_flows(rows) and summarize(values, q, weights); with curves also
-    "t" and {name: (n, n_grid)} per named cell curve."""
-    values, cells, status, used = handle.model_flows(rows, curves=curves, physical=physical)
-    out = {"values": values, "status": status, "n_used": used, "summary": summarize(values, q, weights)}
-    if cells is not None:
-        _, names = _capi.flow_curve_args(curves)
-        out["t"] = handle.tgrid.copy()
-        out.update({c: cells[:, k] for k, c in enumerate(names)})
-    return out
-
-
-def band_result(handle, rows, q, curves, weights=None, physical=False):
-    """{"t": grid, name: (nq, n_grid) per curve, "n_used"} of handle.model_flow_band; with weights also "n_eff" (Kish)."""
-    _, names = _capi.flow_curve_args(curves, band=True)
-    band, st, used = handle.model_flow_band(rows, q, names, physical=physical, weights=weights)
-    out = {"t": handle.tgrid.copy()}
-    out.update({c: band[k] for k, c in enumerate(names)})
-    out["n_used"] = used
-    if weights is not None:
-        out["n_eff"] = _capi.kish_n_eff(weights, st)
-    return out

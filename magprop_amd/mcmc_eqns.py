@@ -9,11 +9,12 @@ Reference quirk Q1: the reference's ``lnprob`` checks a log-spac
 ``lnprob`` implements the documented intent — parameters 3-6 are log10 in sampler coordinates and are
 un-logged before the model — while ``lnlike`` keeps the reference behaviour (physical parameters).
 """
+import contextlib
 import os
 
 import numpy as np
 
-from . import _capi, derived, engine, flows, pointwise
+from . import _capi, engine, summaries
 
 # Default prior box: the values of the reference's magnetar/mcmc_limits.csv:2-10 (rows B, P, log_MdiscI, log_RdiscI,
 # log_epsilon, log_delta, dipeff, propeff, f_beam), kept in code so that nothing depends on the working directory
@@ -101,20 +102,27 @@ def lnprob(pars, data, GRBtype, custom_lims=None, device=-1, reference_quirk=Fal
     return _evaluate(p, data, GRBtype, lo, hi, 0 if reference_quirk else LIB_LOG_MASK, device)
 
 
+def _source(GRBtype, custom_lims, device, data=None):
+    """Source of magprop_amd.summaries: the cached engine of the library variant on the grid of ``GRBtype`` and `device`, under the
+    prior box ``lnprob`` uses for rows of ndim parameters, held for the duration of a summary, with the light curve ``data``
+    registered when one is given."""
+    @contextlib.contextmanager
+    def enter(ndim):
+        lo, hi = _bounds(ndim, custom_lims)
+        x, y, yerr = (None, None, None) if data is None else _columns(data)
+        with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
+            slot = 0 if data is None else eng.dataset_slot(x, y, yerr)
+            eng.set_prior(lo, hi, LIB_LOG_MASK)
+            yield eng.handle, slot, x
+    return enter
+
+
 def model_band(samples, GRBtype, custom_lims=None, q=(0.025, 0.5, 0.975), components=("Ltot",), weights=None, device=-1):
     """Posterior-predictive band of the library model: per point of the grid of ``GRBtype``, the quantiles q of the light
     curves of the rows of `samples` (n, 6..9) in the sampler coordinates of ``lnprob`` (rows outside the prior or whose model
     failed are left out).  With weights (one per row, finite and >= 0) the quantiles of the weighted empirical distribution of
     the curves, without interpolation (mp_model_band_weighted).  Returns what ``synth.model_band`` returns."""
-    qa, _, names = _capi.band_args(q, components)
-    p = _capi.band_rows(samples)
-    if not 6 <= p.shape[1] <= 9:
-        raise ValueError(f"samples must be 2-D (n, 6..9), got shape {p.shape}")
-    w = None if weights is None else _capi.band_weights(weights, p.shape[0])
-    lo, hi = _bounds(p.shape[1], custom_lims)
-    with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
-        eng.set_prior(lo, hi, LIB_LOG_MASK)
-        return _capi.band_result(eng.handle, p, qa, names, w)
+    return summaries.band(_source(GRBtype, custom_lims, device), samples, q, components, weights, width=(6, 9))
 
 
 def model_derived(samples, GRBtype, custom_lims=None, q=(0.16, 0.5, 0.84), weights=None, device=-1):
@@ -122,13 +130,7 @@ def model_derived(samples, GRBtype, custom_lims=None, q=(0.16, 0.5, 0.84), weigh
     coordinates of ``lnprob`` (box prior of ``custom_lims``, parameters 3-6 un-logged before the model), on the grid of
     ``GRBtype``: what magprop_amd.derived.NAMES lists.  Returns {"values": (n, 16) with rows outside the prior or whose model
     failed all NaN, "status", "n_used", "summary": derived.summarize(values, q, weights)}."""
-    p = np.ascontiguousarray(samples, dtype=np.float64)
-    if p.ndim != 2 or not 6 <= p.shape[1] <= 9:
-        raise ValueError(f"samples must be 2-D (n, 6..9), got shape {p.shape}")
-    lo, hi = _bounds(p.shape[1], custom_lims)
-    with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
-        eng.set_prior(lo, hi, LIB_LOG_MASK)
-        return derived.result(eng.handle, p, q, weights)
+    return summaries.derived(_source(GRBtype, custom_lims, device), samples, q, weights, width=(6, 9))
 
 
 def model_flows(rows, GRBtype, custom_lims=None, curves=(), q=(0.16, 0.5, 0.84), weights=None, device=-1):
@@ -136,13 +138,7 @@ def model_flows(rows, GRBtype, custom_lims=None, curves=(), q=(0.16, 0.5, 0.84),
     (n, 6..9) in the sampler coordinates of ``lnprob``, on the grid of ``GRBtype``: what magprop_amd.flows.NAMES lists (the
     quantities code/figure_4.py:139-175 plots for every burst type, reduced per sample).  Returns what ``synth.model_flows``
     returns."""
-    p = np.ascontiguousarray(rows, dtype=np.float64)
-    if p.ndim != 2 or not 6 <= p.shape[1] <= 9:
-        raise ValueError(f"rows must be 2-D (n, 6..9), got shape {p.shape}")
-    lo, hi = _bounds(p.shape[1], custom_lims)
-    with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
-        eng.set_prior(lo, hi, LIB_LOG_MASK)
-        return flows.result(eng.handle, p, q, weights, curves)
+    return summaries.flows(_source(GRBtype, custom_lims, device), rows, q, weights, curves, width=(6, 9))
 
 
 def model_pointwise(samples, data, GRBtype, custom_lims=None, device=-1, cells=False):
@@ -151,12 +147,4 @@ def model_pointwise(samples, data, GRBtype, custom_lims=None, device=-1, cells=F
     in the sampler coordinates of ``lnprob`` (equally weighted; up to pointwise.MAX_SAMPLES rows).  What
     ``synth.model_pointwise`` returns; two models fitted to the same ``data`` (6 against 7 parameters, say) are held against
     each other with pointwise.compare(a["loo"], b["loo"])."""
-    p = np.ascontiguousarray(samples, dtype=np.float64)
-    if p.ndim != 2 or not 6 <= p.shape[1] <= 9:
-        raise ValueError(f"samples must be 2-D (n, 6..9), got shape {p.shape}")
-    lo, hi = _bounds(p.shape[1], custom_lims)
-    x, y, yerr = _columns(data)
-    with engine.use(_capi.cfg_lib(), GRBtype, device) as eng:
-        slot = eng.dataset_slot(x, y, yerr)
-        eng.set_prior(lo, hi, LIB_LOG_MASK)
-        return pointwise.result(eng.handle, p, slot, x=x, cells=cells)
+    return summaries.pointwise(_source(GRBtype, custom_lims, device, data), samples, cells, width=(6, 9))

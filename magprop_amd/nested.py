@@ -14,7 +14,7 @@ import warnings
 
 import numpy as np
 
-from . import _capi, derived, engine, flows, tempering
+from . import _capi, engine, summaries, tempering
 from .optimize import OptimizeResult
 
 TARGETS = {"posterior": 0, "gaussian": 1}
@@ -319,6 +319,31 @@ class NestedSampler:
         r = self._run(run)
         return resample_equal(r.samples, r.logwt, self.seed if seed is None else seed)
 
+    def _summary_rows(self, name, run, weights=None):
+        """(rows, weights, extra entries of the result) of run `run` for the front end `name`.  A band ("..._band") takes weights
+        "exact": band_exact_selection of the run's samples, "weight_dropped" in the result and a RuntimeWarning above 1e-3; or
+        "resample": its equal-weight samples, evenly thinned to _capi.BAND_MAX_SAMPLES, no weights.  Every other summary takes all
+        of the run's samples under exp(logwt - max(logwt))."""
+        if self.target != "posterior":
+            raise ValueError(f"{name} needs the posterior target: the gaussian target has no "
+                             f"{'trajectory' if 'flow' in name else 'light curve'}")
+        if not name.endswith("band"):
+            r = self._run(run)
+            return r.samples, np.exp(r.logwt - np.max(r.logwt)), {}
+        if weights not in ("resample", "exact"):
+            raise ValueError(f"weights must be 'resample' or 'exact', got {weights!r}")
+        if weights == "exact":
+            r = self._run(run)
+            rows, w, dropped = band_exact_selection(r.samples, r.logwt)
+            if dropped > 1.0e-3:
+                warnings.warn(f"run {run}: the {rows.shape[0]} heaviest samples leave {dropped:.2e} of the weight out of the band",
+                              RuntimeWarning, stacklevel=3)
+            return rows, w, {"weight_dropped": dropped}
+        rows = self.resample_equal(run)
+        if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
+            rows = rows[np.linspace(0, rows.shape[0] - 1, _capi.BAND_MAX_SAMPLES).astype(int)]
+        return rows, None, {}
+
     def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), run=0, weights="resample"):
         """Posterior-predictive band of run `run` on this sampler's handle.  weights="resample" (the default): the quantiles q
         of the model light curves of its equal-weight samples (at most _capi.BAND_MAX_SAMPLES, evenly thinned; mp_model_band).
@@ -326,67 +351,31 @@ class NestedSampler:
         run's own samples under their weights (band_exact_selection; mp_model_band_weighted), a function of the run alone; the
         result also holds "n_eff" (Kish's effective sample size of the rows that entered) and "weight_dropped", the share of
         the run's weight on rows the cap of _capi.BAND_MAX_SAMPLES cut (a RuntimeWarning above 1e-3)."""
-        if self.target != "posterior":
-            raise ValueError("get_model_band needs the posterior target: the gaussian target has no light curve")
-        if weights not in ("resample", "exact"):
-            raise ValueError(f"weights must be 'resample' or 'exact', got {weights!r}")
-        qa, _, names = _capi.band_args(q, components)
-        if weights == "exact":
-            r = self._run(run)
-            rows, w, dropped = band_exact_selection(r.samples, r.logwt)
-            if dropped > 1.0e-3:
-                warnings.warn(f"run {run}: the {rows.shape[0]} heaviest samples leave {dropped:.2e} of the weight out of the band",
-                              RuntimeWarning, stacklevel=2)
-            out = _capi.band_result(self.handle, rows, qa, names, w)
-            out["weight_dropped"] = dropped
-            return out
-        rows = self.resample_equal(run)
-        if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
-            rows = rows[np.linspace(0, rows.shape[0] - 1, _capi.BAND_MAX_SAMPLES).astype(int)]
-        return _capi.band_result(self.handle, rows, qa, names)
+        rows, w, extra = self._summary_rows("get_model_band", run, weights)
+        return summaries.band(summaries.on(self.handle), rows, q, components, w, extra=extra)
 
     def get_derived(self, q=(0.16, 0.5, 0.84), run=0):
         """Energy budgets and light-curve landmarks of run `run` (magprop_amd.derived.NAMES): the model of every one of its
         weighted samples, evaluated and reduced on this sampler's handle (mp_model_derived), and the quantiles q under the
         samples' weights exp(logwt - max(logwt)) (the posterior weights up to a common factor) -- no resampling.  Returns {"values": (n, 16), "status", "n_used",
         "summary": derived.summarize(values, q, weights)}."""
-        if self.target != "posterior":
-            raise ValueError("get_derived needs the posterior target: the gaussian target has no light curve")
-        r = self._run(run)
-        return derived.result(self.handle, r.samples, q, np.exp(r.logwt - np.max(r.logwt)))
+        rows, w, _ = self._summary_rows("get_derived", run)
+        return summaries.derived(summaries.on(self.handle), rows, q, w)
 
     def get_flows(self, q=(0.16, 0.5, 0.84), run=0, curves=()):
         """Mass budget, angular-momentum budget and propeller / accretor regime of run `run` (magprop_amd.flows.NAMES): the
         model of every one of its weighted samples, evaluated and reduced on this sampler's handle (mp_model_flows), and the
         quantiles q under the samples' weights exp(logwt - max(logwt)) -- no resampling.  Returns {"values": (n, 16), "status",
         "n_used", "summary": flows.summarize(values, q, weights)} and the cell curves named in `curves`."""
-        if self.target != "posterior":
-            raise ValueError("get_flows needs the posterior target: the gaussian target has no trajectory")
-        r = self._run(run)
-        return flows.result(self.handle, r.samples, q, np.exp(r.logwt - np.max(r.logwt)), curves)
+        rows, w, _ = self._summary_rows("get_flows", run)
+        return summaries.flows(summaries.on(self.handle), rows, q, w, curves)
 
     def get_flow_band(self, q=(0.025, 0.5, 0.975), curves=("fastness",), run=0, weights="exact"):
         """Bands of the radii, mass-flow rates and torques of run `run` (flows.CURVES without "branch"; mp_model_flow_band), with
         get_model_band's two choices of rows: weights="exact" (the default here) the run's own samples under their weights
         (band_exact_selection), with "n_eff" and "weight_dropped" in the result; "resample" its equal-weight samples."""
-        if self.target != "posterior":
-            raise ValueError("get_flow_band needs the posterior target: the gaussian target has no trajectory")
-        if weights not in ("resample", "exact"):
-            raise ValueError(f"weights must be 'resample' or 'exact', got {weights!r}")
-        qa, _, _ = _capi.band_args(q, "Ltot")
-        if weights == "exact":
-            r = self._run(run)
-            rows, w, dropped = band_exact_selection(r.samples, r.logwt)
-            if dropped > 1.0e-3:
-                warnings.warn(f"run {run}: the {rows.shape[0]} heaviest samples leave {dropped:.2e} of the weight out of the band",
-                              RuntimeWarning, stacklevel=2)
-            out = flows.band_result(self.handle, rows, qa, curves, w)
-            out["weight_dropped"] = dropped
-            return out
-        rows = self.resample_equal(run)
-        if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
-            rows = rows[np.linspace(0, rows.shape[0] - 1, _capi.BAND_MAX_SAMPLES).astype(int)]
-        return flows.band_result(self.handle, rows, qa, curves)
+        rows, w, extra = self._summary_rows("get_flow_band", run, weights)
+        return summaries.flow_band(summaries.on(self.handle), rows, q, curves, w, extra=extra)
 
 
 def get_state(L, ns, n_runs, nlive, ndim):

@@ -209,25 +209,3 @@ def compare(a, b):
     if x.shape != y.shape or x.ndim != 1:
         raise ValueError(f"two per-point arrays of one length expected, got shapes {x.shape} and {y.shape}")
     return _total(x - y)
-
-
-def result(handle, rows, ds_id=0, x=None, physical=False, cells=False):
-    """{"obs", "tail", "status", "n_used", "loo", "waic", "summary"} (and "z" with cells=True) of handle.model_pointwise(rows,
-    ds_id) and the scores above.  The library keeps a dataset's observations in ascending time (stable); with the times x the
-    dataset was registered with, every per-point array is returned in the caller's order of x."""
-    res = handle.model_pointwise(rows, ds_id=ds_id, physical=physical, cells=cells)
-    obs, tail, status, used = res[:4]
-    z = res[4] if cells else None
-    if x is not None:
-        order = np.argsort(np.asarray(x, dtype=np.float64), kind="stable")
-        if order.size != obs.shape[0]:
-            raise ValueError(f"x has {order.size} points, the dataset {obs.shape[0]}")
-        back = np.empty_like(order)
-        back[order] = np.arange(order.size)
-        obs, tail = obs[back], tail[back]
-        z = None if z is None else z[back]
-    loo, w = psis_loo(obs, tail), waic(obs)
-    out = {"obs": obs, "tail": tail, "status": status, "n_used": used, "loo": loo, "waic": w, "summary": summarize({**w, **loo})}
-    if cells:
-        out["z"] = z
-    return out

@@ -4,9 +4,11 @@
 (:52-81) — the callable ``synth_mcmc.py:180-185`` hands to ``emcee.EnsembleSampler``.  ``pars`` may be
 2-D ``(n_walkers, 6)`` (emcee ``vectorize=True``): one kernel launch for the whole batch.
 """
+import contextlib
+
 import numpy as np
 
-from . import _capi, derived, engine, flows, pointwise
+from . import _capi, engine, summaries
 
 PRIOR_UPPER = np.array([10.0, 10.0, -2.0, np.log10(2000.0), 2.0, 3.0])   # :40
 PRIOR_LOWER = np.array([1.0e-3, 0.69, -6.0, np.log10(50.0), -2.0, -1.0])  # :41
@@ -71,6 +73,18 @@ def lnprob(pars, x, y, yerr, fbad=None, device=-1):
     return out
 
 
+def _source(device, x=None, y=None, yerr=None):
+    """Source of magprop_amd.summaries: the cached engine of the synthetic variant on `device` under the synthetic prior, held for
+    the duration of a summary, with the light curve (x, y, yerr) registered when one is given."""
+    @contextlib.contextmanager
+    def enter(ndim):
+        with engine.use(_cfg(), None, device) as eng:
+            slot = 0 if x is None else eng.dataset_slot(x, y, yerr)
+            eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
+            yield eng.handle, slot, None if x is None else engine._as_f64(x)
+    return enter
+
+
 def model_band(samples, q=(0.025, 0.5, 0.975), components=("Ltot",), device=-1, weights=None):
     """Posterior-predictive band of the synthetic model: per point of the grid logspace(0, 6, 10001), the quantiles q of the
     light curves of `samples` (rows in sampler coordinates, as a chain stores them; rows outside the prior or whose model
@@ -79,15 +93,7 @@ def model_band(samples, q=(0.025, 0.5, 0.975), components=("Ltot",), device=-1, 
     that entered}; a grid point no row reached is NaN.  weights (one per row, finite and >= 0): the quantiles of the weighted
     empirical distribution of the curves (mp_model_band_weighted, no interpolation), and "n_eff", Kish's effective sample size
     of the rows that entered."""
-    qa, _, names = _capi.band_args(q, components)
-    p = _capi.band_rows(samples, 6)
-    w = None if weights is None else _capi.band_weights(weights, p.shape[0])
-    eng = engine.acquire(_cfg(), None, device)
-    try:
-        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
-        return _capi.band_result(eng.handle, p, qa, names, w)
-    finally:
-        engine.release(eng)
+    return summaries.band(_source(device), samples, q, components, weights, width=6)
 
 
 def model_derived(samples, q=(0.16, 0.5, 0.84), weights=None, device=-1):
@@ -96,16 +102,7 @@ def model_derived(samples, q=(0.16, 0.5, 0.84), weights=None, device=-1):
     split, peaks, the times by which 10, 50 and 90 % of the energy is out, spin-up and disc mass (magprop_amd.derived.NAMES).
     Returns {"values": (n, 16) with rows outside the prior or whose model failed all NaN, "status": (n,), "n_used": rows that
     finished, "summary": derived.summarize(values, q, weights)}."""
-    p = np.ascontiguousarray(samples, dtype=np.float64)
-    if p.ndim != 2 or p.shape[1] != 6:
-        raise ValueError(f"samples must be 2-D (n, 6), got shape {p.shape}")
-    eng = engine.acquire(_cfg(), None, device)
-    try:
-        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
-        res = derived.result(eng.handle, p, q, weights)
-    finally:
-        engine.release(eng)
-    return res
+    return summaries.derived(_source(device), samples, q, weights, width=6)
 
 
 def model_flows(rows, curves=(), q=(0.16, 0.5, 0.84), weights=None, device=-1):
@@ -115,16 +112,7 @@ def model_flows(rows, curves=(), q=(0.16, 0.5, 0.84), weights=None, device=-1):
     quantities code/figure_3.py:202-286 recovers and code/figure_4.py:139-175 plots).  Returns {"values": (n, 16) with rows
     outside the prior or whose model failed all NaN, "status": (n,), "n_used", "summary": flows.summarize(values, q, weights)}
     and, per name of flows.CURVES in `curves`, that cell curve (n, n_grid) in cgs, with "t" the grid."""
-    p = np.ascontiguousarray(rows, dtype=np.float64)
-    if p.ndim != 2 or p.shape[1] != 6:
-        raise ValueError(f"rows must be 2-D (n, 6), got shape {p.shape}")
-    eng = engine.acquire(_cfg(), None, device)
-    try:
-        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
-        res = flows.result(eng.handle, p, q, weights, curves)
-    finally:
-        engine.release(eng)
-    return res
+    return summaries.flows(_source(device), rows, q, weights, curves, width=6)
 
 
 def model_flow_band(samples, q=(0.025, 0.5, 0.975), curves=("fastness",), device=-1, weights=None):
@@ -132,15 +120,7 @@ def model_flow_band(samples, q=(0.025, 0.5, 0.975), curves=("fastness",), device
     point, the quantiles q of every curve named in `curves` (flows.CURVES without "branch") over the rows that finished, as
     model_band gives them for the luminosities (mp_model_flow_band).  Returns {"t", name: (nq, n_grid), "n_used"}; with
     weights also "n_eff"."""
-    qa, _, _ = _capi.band_args(q, "Ltot")
-    p = _capi.band_rows(samples, 6)
-    w = None if weights is None else _capi.band_weights(weights, p.shape[0])
-    eng = engine.acquire(_cfg(), None, device)
-    try:
-        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
-        return flows.band_result(eng.handle, p, qa, curves, w)
-    finally:
-        engine.release(eng)
+    return summaries.flow_band(_source(device), samples, q, curves, weights, width=6)
 
 
 def model_pointwise(samples, x, y, yerr, device=-1, cells=False):
@@ -151,14 +131,4 @@ def model_pointwise(samples, x, y, yerr, device=-1, cells=False):
     table of pointwise.NAMES, "tail", "status": (n,), "n_used": rows that finished, "loo": pointwise.psis_loo, "waic":
     pointwise.waic, "summary": pointwise.summarize}; cells=True adds "z": (n_obs, n), the standardised residuals.  The
     log-likelihood is the unnormalised lnlike term; pointwise.normalisation(yerr) per point normalises it."""
-    p = np.ascontiguousarray(samples, dtype=np.float64)
-    if p.ndim != 2 or p.shape[1] != 6:
-        raise ValueError(f"samples must be 2-D (n, 6), got shape {p.shape}")
-    eng = engine.acquire(_cfg(), None, device)
-    try:
-        slot = eng.dataset_slot(x, y, yerr)
-        eng.set_prior(PRIOR_LOWER, PRIOR_UPPER, LOG_MASK)
-        res = pointwise.result(eng.handle, p, slot, x=engine._as_f64(x), cells=cells)
-    finally:
-        engine.release(eng)
-    return res
+    return summaries.pointwise(_source(device, x, y, yerr), samples, cells, width=6)

@@ -124,7 +124,7 @@ def test_repeat_is_bitwise(humped, gflag):
 
 
 def test_sampler_and_module_wiring(gsynth):
-    from magprop_amd import EnsembleSampler, _capi, synth
+    from magprop_amd import EnsembleSampler, _capi, summaries, synth
     x, y, yerr = gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"]
     rng = np.random.default_rng(4)
     p0 = np.array(TRUTHS["Humped"]) + 1e-3 * rng.standard_normal((32, 6))
@@ -139,7 +139,7 @@ def test_sampler_and_module_wiring(gsynth):
     assert "n_eff" not in s.get_model_band(discard=2, thin=2)
     with pytest.raises(ValueError, match="shape"):
         s.get_model_band(discard=2, thin=2, weights=w[:-1])
-    direct = _capi.band_result(s.handle, rows, Q3, ("Ltot",), w)
+    direct = summaries.band(summaries.on(s.handle), rows, Q3, ("Ltot",), w)
     assert _same(direct["Ltot"], got["Ltot"])
     s.close()
     # the library variant: mcmc_eqns.model_band is the handle's band under the variant's prior box
@@ -150,15 +150,15 @@ def test_sampler_and_module_wiring(gsynth):
     lo, hi = mcmc_eqns._bounds(6)
     with engine.use(_capi.cfg_lib(), "L", -1) as eng:
         eng.set_prior(lo, hi, mcmc_eqns.LIB_LOG_MASK)
-        b = _capi.band_result(eng.handle, S, Q3, ("Ltot", "Ldip"), wl)
+        b = summaries.band(summaries.on(eng.handle), S, Q3, ("Ltot", "Ldip"), wl)
     assert a["n_used"] == b["n_used"] >= 1 and a["n_eff"] == b["n_eff"] and _same(a["Ltot"], b["Ltot"]) and _same(a["Ldip"], b["Ldip"])
     assert set(mcmc_eqns.model_band(S, "L", q=Q3)) == {"t", "Ltot", "n_used"}
 
 
 def test_nested_sampler_exact_band(gsynth):
-    """A short nested run (the smallest live set the nested tests use): weights="exact" is _capi.band_result on the documented row
+    """A short nested run (the smallest live set the nested tests use): weights="exact" is summaries.band on the documented row
     selection, a function of the run alone; the default call is what it was."""
-    from magprop_amd import NestedSampler, _capi, nested
+    from magprop_amd import NestedSampler, _capi, nested, summaries
     x, y, yerr = gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"]
     s = NestedSampler(x, y, yerr, nlive=64, nbatch=16, seed=3)
     res = s.run_nested(dlogz=0.5, maxiter=30)
@@ -168,14 +168,14 @@ def test_nested_sampler_exact_band(gsynth):
     assert 1 <= keep.sum() <= len(w) <= _capi.BAND_MAX_SAMPLES
     rows, wsel, dropped = nested.band_exact_selection(res.samples, res.logwt)
     assert np.array_equal(rows, res.samples[keep]) and np.array_equal(wsel, w[keep]) and dropped == 0.0
-    want = _capi.band_result(s.handle, res.samples[keep], Q3, ("Ltot",), w[keep])
+    want = summaries.band(summaries.on(s.handle), res.samples[keep], Q3, ("Ltot",), w[keep])
     assert _same(got["Ltot"], want["Ltot"]) and got["n_used"] == want["n_used"] > 0 and got["n_eff"] == want["n_eff"] > 0.0
     assert got["weight_dropped"] == 0.0 and got["Ltot"].shape == (3, 10001)
     assert _same(s.get_model_band(weights="exact")["Ltot"], got["Ltot"])
     # the default: the equal-weight resample, as before
     default = s.get_model_band()
     eq = s.resample_equal()
-    old = _capi.band_result(s.handle, eq, Q3, ("Ltot",))
+    old = summaries.band(summaries.on(s.handle), eq, Q3, ("Ltot",))
     assert set(default) == {"t", "Ltot", "n_used"} and _same(default["Ltot"], old["Ltot"]) and default["n_used"] == old["n_used"]
     assert _same(s.get_model_band(weights="resample")["Ltot"], default["Ltot"])
     s.close()
