@@ -856,6 +856,59 @@ int mp_nested_set_slice(mp_nested *ns, int slices, double mu, int max_steps_out,
 int mp_nested_get_slice_stats(mp_nested *ns, int64_t *nexpand, int64_t *ncontract, int64_t *nfail);
 int mp_nested_destroy(mp_nested *ns);
 
+/*
+ * Nelder-Mead simplex search (ABI 5, additive): scipy.optimize.minimize(method="Nelder-Mead", bounds=...), its iterate sequence
+ * exactly, for n_simplex simplexes at once (1 <= n_simplex <= 1024); simplex s runs on dataset simplex_ds_id[s] (NULL: dataset 0
+ * for all; several simplexes may share a dataset: multiple starts).  N = ndim; a simplex is N + 1 vertices v_0 .. v_N sorted by
+ * f = -lnprob ascending (v_0 the best).  The bounds box lower[ndim] < upper[ndim] (finite) is in sampler coordinates.  target: 0
+ * the log-posterior of the handle, 1 the isotropic unit Gaussian G(x) = -0.5 sum x^2 (lnp = lnp - (0.5 x_d) x_d in index order),
+ * 2 the terraced Gaussian G(x) - 1e-3 floor(37 x_0), whose plateaus and ties make every branch below occur (1 and 2: tests).
+ * A NaN lnprob counts (and is stored) as -inf.
+ * An iteration of the serial algorithm asks for 1 or 2 points, or N + 2 on a shrink, each after the last; all N + 4 it may ask
+ * for depend on the sorted simplex alone, so one launch evaluates them all (one workgroup per simplex and candidate) and a small
+ * launch behind it takes scipy's decisions.  Candidate c of a simplex, with xbar = ((v_0 + v_1) + ... + v_{N-1}) / N in vertex
+ * order and clip(x) = min(max(x, lower), upper) per coordinate:
+ *   c = 0  reflection           clip((1 + rho) xbar - rho v_N)
+ *   c = 1  expansion            clip((1 + rho chi) xbar - rho chi v_N)
+ *   c = 2  outside contraction  clip((1 + psi rho) xbar - psi rho v_N)
+ *   c = 3  inside contraction   clip((1 - psi) xbar + psi v_N)
+ *   c = 4 + (j - 1)             the shrink of vertex j = 1 .. N: clip(v_0 + sigma (v_j - v_0))
+ * All of it unfused (separately rounded products, sums and the division); the coefficients 1 + rho, rho chi, 1 + rho chi, psi rho,
+ * 1 + psi rho and 1 - psi are formed once, each operation rounded on its own.  The decision, fr, fe, fo, fi the values of c = 0 .. 3:
+ *   fr < f_0:           v_N = the expansion if fe < fr, else the reflection;
+ *   else fr < f_{N-1}:  v_N = the reflection;
+ *   else fr < f_N:      v_N = the outside contraction if fo <= fr, else shrink;
+ *   else:               v_N = the inside contraction if fi < f_N, else shrink;
+ *   shrink: v_j = candidate 4 + (j - 1) for j = 1 .. N.
+ * Then the vertices are sorted by f, stably (equal values keep their order, the replaced vertex having sat last), nit += 1, one
+ * of the outcome counters (reflect, expand, outside, inside, shrink) += 1, and nfev grows by what the serial algorithm would have
+ * evaluated: 1 for a reflection taken without trying the expansion (the second line), 2 for every other outcome but a shrink,
+ * N + 2 for a shrink.  A simplex stops -- scipy's test at the top of its loop, made here on the sorted simplex for the next
+ * iteration -- when |v_j[d] - v_0[d]| <= xatol for every j, d and |f_0 - f_j| <= fatol for every j: every term has to pass, so a
+ * NaN difference (inf - inf) means go on.  A stopped simplex is frozen: its vertices, lnprob, status and counters stay as they
+ * are, and its later iterations evaluate nothing.  There is no maxfev: the budget is the iteration count alone.
+ * Kernel build: the rule of mp_lnprob_batch for a batch of n_simplex * (N + 4) walkers, the initial evaluation included, so that
+ * (shipped build) every stored lnprob is bit for bit what mp_lnprob_batch returns for the same row in a batch of that size.
+ * mp_simplex_create: MP_EINVAL on bad sizes (ndim outside 1 .. MP_MAX_NDIM, < 6 for target 0), rho, chi, psi or sigma not finite
+ * and > 0, psi or sigma >= 1, xatol / fatol not finite and >= 0, an empty or non-finite box, unset datasets; MP_ESTATE on
+ * multi-device handles and (target 0) handles with cfg.dipole_torque = 1.  mp_simplex_set_vertices(sim[n_simplex][N + 1][N])
+ * refuses non-finite coordinates (MP_EINVAL), applies scipy's rule to vertices outside the box (a coordinate above upper becomes
+ * 2 upper - it, then everything is clipped), evaluates the vertices and sorts them (nit = 1 as scipy counts, nfev = N + 1) and
+ * clears the flags and counters.  mp_simplex_run runs up to max_iterations more iterations of every simplex that has not
+ * stopped, in chunks of launches with one read-back of the flags per chunk; the state does not depend on how a run is split
+ * into calls; *n_running (optional) = simplexes still running.  mp_simplex_get_state: any output may be NULL;
+ * sim[n_simplex][N + 1][N], lnprob[n_simplex][N + 1], status[n_simplex][N + 1], nit, stopped, nfev [n_simplex],
+ * outcomes[n_simplex][5] in the order above.  The object behind the void pointers is an mp_simplex.
+ */
+typedef struct mp_simplex mp_simplex;
+void *mp_simplex_create(mp_handle *h, int n_simplex, int ndim, const int32_t *simplex_ds_id, double rho, double chi, double psi,
+                        double sigma, double xatol, double fatol, const double *lower, const double *upper, int target);
+int mp_simplex_set_vertices(void *s, const double *sim);
+int mp_simplex_run(void *s, int max_iterations, int *n_running);
+int mp_simplex_get_state(void *s, double *sim, double *lnprob, int32_t *status, int32_t *nit, int32_t *stopped, int64_t *nfev,
+                         int64_t *outcomes);
+int mp_simplex_destroy(void *s);
+
 /* wait for everything enqueued on the handle's own stream */
 int mp_synchronize(mp_handle *h);
 

@@ -122,6 +122,11 @@ SIGNATURES = {
     "mp_nested_set_slice": (_i, [_vp, _i, _d, _i, _i]),
     "mp_nested_get_slice_stats": (_i, [_vp, _i64p, _i64p, _i64p]),
     "mp_nested_destroy": (_i, [_vp]),
+    "mp_simplex_create": (_vp, [_vp, _i, _i, _ip, _d, _d, _d, _d, _d, _d, _dp, _dp, _i]),
+    "mp_simplex_set_vertices": (_i, [_vp, _dp]),
+    "mp_simplex_run": (_i, [_vp, _i, _ip]),
+    "mp_simplex_get_state": (_i, [_vp, _dp, _dp, _ip, _ip, _ip, _i64p, _i64p]),
+    "mp_simplex_destroy": (_i, [_vp]),
     "mp_synchronize": (_i, [_vp]),
     "mp_device": (_i, [_vp]),
     "mp_stream": (_vp, [_vp]),
@@ -376,7 +381,7 @@ class _Owner:
 
 
 class Driver(_Owner):
-    """Owns one device-resident driver object (mp_sampler, mp_optimizer, mp_nested) of `handle`: `name`_create(handle,
+    """Owns one device-resident driver object (mp_sampler, mp_optimizer, mp_nested, mp_simplex) of `handle`: `name`_create(handle,
     *args), freed once by `name`_destroy.  Passed to the ABI as its pointer (NULL once closed); holds the handle, so the
     handle outlives it."""
 
