@@ -8,6 +8,7 @@
 #include "../../include/magprop_amd.h"
 
 #if defined(__HIP__) || defined(__HIPCC__)
+#include <hip/hip_runtime_api.h>   // (launch_point_kernel)
 #define MP_HD __host__ __device__
 #else
 #define MP_HD
@@ -322,6 +323,17 @@ void dispatch(F &&f, bool b, B... rest) {
     if (b) dispatch([&](auto... c) { f(std::true_type(), c...); }, rest...);
     else dispatch([&](auto... c) { f(std::false_type(), c...); }, rest...);
 }
+#if defined(__HIP__) || defined(__HIPCC__)
+// The launch of a resident driver's kernel (mp_point.h) on n workgroups, one evaluated point each: launch(Build<...>(), lng) is
+// called with the build of launch_lnprob for a batch of n walkers -- walker_variant with a team where kernel_waves says so; lng:
+// the LONG builds, for handles with light curves of more than 64 points -- and launches the kernel.  Returns hipError_t as int.
+template <class F>
+int launch_point_kernel(const DevShared &sh, int n, F &&launch) {
+    const Variant v = walker_variant(sh, n, kernel_waves(sh, n) == 4);
+    dispatch([&](auto team, auto roomy, auto lng) { launch(Build<team, roomy>(), lng); }, v.team, v.roomy, sh.has_long != 0);
+    return (int)hipGetLastError();
+}
+#endif
 
 // Arguments of the batched right-hand-side evaluation (mp_kernels.hip: rhs_kernel), device pointers.
 struct RhsArgs {

@@ -38,7 +38,7 @@
 // formulas and the tests compare the two.
 #include <hip/hip_runtime.h>
 
-#include "mp_eval.hpp"
+#include "mp_point.h"
 
 namespace mp {
 
@@ -423,8 +423,7 @@ MP_DEV void kde_proposal(const StretchArgs &g, int k, int base, const int32_t *p
 // KDE: the builds of the KDE move (kde_proposal, DIFF false): the workgroup's proposal stage over the other half, counters
 // c3 = 0x4B00 + j; a NaN proposal (S not positive definite) is not evaluated and is rejected.
 template <int SPL, bool LONG, int W = 1, int OCC = 0, bool TEMPERED = false, bool DIFF = false, bool KDE = false>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
-void stretch_kernel(const DevShared sh, const StretchArgs g) {
+MP_POINT_KERNEL(SPL, W, OCC) void stretch_kernel(const DevShared sh, const StretchArgs g) {
     __shared__ TileImage<SPL * W> im;
     __shared__ TimeTable<SPL * W> tt;
     __shared__ double lds[1];
@@ -599,8 +598,7 @@ MP_DEV void stretch_draw(const StretchArgs &g, int half, int k, int n_comp, int 
 }
 
 template <int SPL, bool LONG, int W = 1, int OCC = 0>   // (W, OCC: as in stretch_kernel)
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
-void stretch_step_kernel(const DevShared sh, const StretchArgs g) {
+MP_POINT_KERNEL(SPL, W, OCC) void stretch_step_kernel(const DevShared sh, const StretchArgs g) {
     __shared__ TileImage<SPL * W> im;
     __shared__ TimeTable<SPL * W> tt;
     __shared__ double lds[1];

@@ -4,16 +4,16 @@
 // nest_select_kernel: one workgroup per run.  It ranks the live lnL (by lnL, then slot; N <= 4096 keys in LDS), applies the stop
 // rule to the live set as it stands, and otherwise writes the iteration's dead list (ascending lnL), the survivors in slot order,
 // L*, the dead rows of the chunk and the new ln X and ln Z (one thread, in the order of the header).
-// nest_walk_kernel: one workgroup per dead slot (the builds of lnprob_kernel / lnprob_team_kernel).  Lane 0 picks a survivor as
-// the start and builds every DE step in LDS, the workgroup evaluates the step with walker_eval, lane 0 decides (inside the box and
-// lnL > L*).  Survivors are only read and dead slots only written, so the workgroups need no hand-off among themselves.  Mode 1
-// evaluates the live set as the caller set it.
+// nest_walk_kernel: one workgroup per dead slot, on the shell of mp_point.h.  Lane 0 picks a survivor as the start and builds
+// every DE step in LDS, the workgroup evaluates the step, lane 0 decides (inside the box and lnL > L*).  Survivors are only read
+// and dead slots only written, so the workgroups need no hand-off among themselves.  Mode 1 evaluates the live set as the caller
+// set it.  (The one kernel of the four that states point_eval's block itself: with the call its walks ran 3 % slower.)
 // nest_slice_kernel: the walk of slice mode (mp_nested_set_slice), the same workgroups and builds.  Lane 0 runs the slice updates
 // as a state machine in LDS (start a slice, step out left, step out right, shrink) that names one point per round or ends the
-// walk; the workgroup evaluates the named point through the one walker_eval call site of the kernel.
+// walk; the workgroup evaluates the named point through the one point_eval call of the kernel.
 #include <hip/hip_runtime.h>
 
-#include "mp_eval.hpp"
+#include "mp_point.h"
 
 namespace mp {
 
@@ -32,22 +32,16 @@ MP_DEV double logaddexp(double x, double y) {
     return add_rn(m, log1p(exp(-fabs(sub_rn(x, y)))));
 }
 
-// W, OCC, SPL, LONG: the builds of launch_lnprob (W = 4: lnprob_team_kernel<1, 4, OCC>; W = 1: lnprob_kernel<false, SPL>), chosen
-// by the same rule for the launch's workgroup count (launch_nest_walk).
+// The builds of mp_point.h for the launch's workgroup count (launch_nest_walk); a run's points are evaluated as walker r.
 template <int SPL, bool LONG, int W = 1, int OCC = 0>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
-void nest_walk_kernel(const DevShared sh, const NestArgs a) {
+MP_POINT_KERNEL(SPL, W, OCC) void nest_walk_kernel(const DevShared sh, const NestArgs a) {
     const int b = (int)blockIdx.x, per = a.mode ? a.nlive : a.nbatch, r = b / per, k = b - r * per;
     if (a.mode == 0 && a.stopped[r]) return;   // frozen run (uniform for the workgroup): nothing to do
-    __shared__ TileImage<SPL * W> im;
-    __shared__ TimeTable<SPL * W> tt;
-    __shared__ double lds[1];
+    __shared__ PointLds<SPL, W> ws;
     __shared__ double cur[MP_MAX_NDIM];      // the walk's current point
-    __shared__ double prop[MP_MAX_NDIM];     // the step's proposal across walker_eval
+    __shared__ double prop[MP_MAX_NDIM];     // the step's proposal across the evaluation
     __shared__ int go;                       // 1: the proposal lies in the box (evaluate it)
-    __shared__ TeamLds<SPL * W, (W > 1)> tl;
-    TeamX<SPL * W> *const tx = tl.ptr();
-    tables_init<SPL * W, 64 * W>(sh, tt);
+    tables_init<SPL * W, 64 * W>(sh, ws.tt);
     const int nd = a.ndim, m = a.nlive - a.nbatch, base = r * a.nlive;
     const int slot = a.mode ? k : a.dead_slot[r * a.nbatch + k];
     const int steps = a.mode ? 1 : a.walks;
@@ -90,6 +84,8 @@ void nest_walk_kernel(const DevShared sh, const NestArgs a) {
         }
         __syncthreads();
         if (!go) continue;                     // (uniform: LDS behind the barrier)
+        // point_eval(sh, ws, a.ds_id, nd, a.target, r, prop, lnp, status), stated here: through the call the team build of up to
+        // n_simd / 4 walks spills less and yet takes 1.611 ms per iteration where this takes 1.56
         double par[MP_MAX_NDIM];
 #pragma unroll
         for (int d = 0; d < MP_MAX_NDIM; ++d) par[d] = d < nd ? prop[d] : 0.0;
@@ -104,8 +100,8 @@ void nest_walk_kernel(const DevShared sh, const NestArgs a) {
             la.ndim = nd;
             la.physical = 0;
             la.want_chi2 = 1;
-            if constexpr (W > 1) walker_eval<false, SPL, LONG, false, W, OCC >= 2>(sh, la, r, par, im, tt, lds, lnp, status, sweeps, tiles, tx);
-            else walker_eval<false, SPL, LONG>(sh, la, r, par, im, tt, lds, lnp, status, sweeps, tiles);
+            if constexpr (W > 1) walker_eval<false, SPL, LONG, false, W, OCC >= 2>(sh, la, r, par, ws.im, ws.tt, ws.lds, lnp, status, sweeps, tiles, ws.tl.ptr());
+            else walker_eval<false, SPL, LONG>(sh, la, r, par, ws.im, ws.tt, ws.lds, lnp, status, sweeps, tiles);
         }
         if (threadIdx.x == 0) {
             if (lnp != lnp) lnp = -INFINITY;   // NaN counts (and is kept) as -inf
@@ -232,21 +228,16 @@ MP_DEV int slice_round(const NestArgs &a, const NestSlice &sl, int r, int slot, 
 
 // One workgroup per dead slot of a running run; builds and template arguments as nest_walk_kernel.
 template <int SPL, bool LONG, int W = 1, int OCC = 0>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
-void nest_slice_kernel(const DevShared sh, const NestArgs a, const NestSlice sl) {
+MP_POINT_KERNEL(SPL, W, OCC) void nest_slice_kernel(const DevShared sh, const NestArgs a, const NestSlice sl) {
     const int b = (int)blockIdx.x, r = b / a.nbatch, k = b - r * a.nbatch;
     if (a.stopped[r]) return;   // frozen run (uniform for the workgroup): nothing to do
-    __shared__ TileImage<SPL * W> im;
-    __shared__ TimeTable<SPL * W> tt;
-    __shared__ double lds[1];
+    __shared__ PointLds<SPL, W> ws;
     __shared__ double cur[MP_MAX_NDIM];      // the walk's current point
     __shared__ double dir[MP_MAX_NDIM];      // the slice's direction
-    __shared__ double prop[MP_MAX_NDIM];     // the named point across walker_eval
+    __shared__ double prop[MP_MAX_NDIM];     // the named point across the evaluation
     __shared__ SliceState z;
     __shared__ int go;                       // 1: evaluate prop; 0: the walk has ended
-    __shared__ TeamLds<SPL * W, (W > 1)> tl;
-    TeamX<SPL * W> *const tx = tl.ptr();
-    tables_init<SPL * W, 64 * W>(sh, tt);
+    tables_init<SPL * W, 64 * W>(sh, ws.tt);
     const int nd = a.ndim, m = a.nlive - a.nbatch, base = r * a.nlive;
     const int slot = a.dead_slot[r * a.nbatch + k];
     if (threadIdx.x == 0) {
@@ -266,28 +257,8 @@ void nest_slice_kernel(const DevShared sh, const NestArgs a, const NestSlice sl)
         if (threadIdx.x == 0) go = slice_round(a, sl, r, slot, z, cur, dir, prop, have, lnp, status);
         __syncthreads();
         if (!go) break;                        // (uniform: LDS behind the barrier)
-        double par[MP_MAX_NDIM];
-#pragma unroll
-        for (int d = 0; d < MP_MAX_NDIM; ++d) par[d] = d < nd ? prop[d] : 0.0;
-        lnp = 0.0;
-        status = MP_STATUS_OK;
-        int sweeps, tiles;
-        if (a.target == 1) {   // isotropic unit Gaussian: exercises the algorithm itself (tests)
-#pragma unroll
-            for (int d = 0; d < MP_MAX_NDIM; ++d) lnp = d < nd ? sub_rn(lnp, mul_rn(mul_rn(0.5, par[d]), par[d])) : lnp;
-        } else {
-            LaunchArgs la{};
-            la.ds_id = a.ds_id;
-            la.ndim = nd;
-            la.physical = 0;
-            la.want_chi2 = 1;
-            if constexpr (W > 1) walker_eval<false, SPL, LONG, false, W, OCC >= 2>(sh, la, r, par, im, tt, lds, lnp, status, sweeps, tiles, tx);
-            else walker_eval<false, SPL, LONG>(sh, la, r, par, im, tt, lds, lnp, status, sweeps, tiles);
-        }
-        if (threadIdx.x == 0) {
-            if (lnp != lnp) lnp = -INFINITY;   // NaN counts (and is kept) as -inf
-            ++z.n_eval;
-        }
+        point_eval<SPL, LONG, W, OCC>(sh, ws, a.ds_id, nd, a.target, r, prop, lnp, status);
+        if (threadIdx.x == 0) ++z.n_eval;
     }
     if (threadIdx.x == 0) {
         const size_t row = (size_t)(base + slot);
@@ -379,29 +350,24 @@ __global__ __launch_bounds__(kSelThreads) void nest_select_kernel(const NestArgs
 
 }  // namespace
 
-// The build of launch_lnprob for a batch of n = n_runs * nbatch walkers (mode 1: n_runs * nlive): walker_variant with a team where
-// kernel_waves says so; LONG builds for handles with light curves of more than 64 points.
+// One workgroup per dead slot: n = n_runs * nbatch (mode 1: one per live point, n_runs * nlive).
 int launch_nest_walk(const DevShared &sh, const NestArgs &a, void *stream) {
     const int n = a.n_runs * (a.mode ? a.nlive : a.nbatch);
     if (n <= 0) return 0;
-    const Variant v = walker_variant(sh, n, kernel_waves(sh, n) == 4);
-    dispatch([&](auto team, auto roomy, auto lng) {
-        using B = Build<team, roomy>;
+    return launch_point_kernel(sh, n, [&](auto build, auto lng) {
+        using B = decltype(build);
         hipLaunchKernelGGL((nest_walk_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n), dim3(64 * B::W), 0, (hipStream_t)stream, sh, a);
-    }, v.team, v.roomy, sh.has_long != 0);
-    return (int)hipGetLastError();
+    });
 }
 
 // slice mode: the builds of launch_nest_walk for its n_runs * nbatch workgroups
 int launch_nest_slice(const DevShared &sh, const NestArgs &a, const NestSlice &sl, void *stream) {
     const int n = a.n_runs * a.nbatch;
     if (n <= 0 || a.mode) return 0;
-    const Variant v = walker_variant(sh, n, kernel_waves(sh, n) == 4);
-    dispatch([&](auto team, auto roomy, auto lng) {
-        using B = Build<team, roomy>;
+    return launch_point_kernel(sh, n, [&](auto build, auto lng) {
+        using B = decltype(build);
         hipLaunchKernelGGL((nest_slice_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n), dim3(64 * B::W), 0, (hipStream_t)stream, sh, a, sl);
-    }, v.team, v.roomy, sh.has_long != 0);
-    return (int)hipGetLastError();
+    });
 }
 
 int launch_nest_select(const NestArgs &a, void *stream) {

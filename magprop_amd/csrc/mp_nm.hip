@@ -1,17 +1,17 @@
 // mp_nm.hip — gfx950 kernels of the Nelder-Mead simplex search (include/magprop_amd.h mp_simplex_*): scipy's
 // minimize(method="Nelder-Mead") with bounds, every iteration of every simplex one speculative launch and one small decision.
 //
-// nm_eval_kernel: one workgroup per (simplex, candidate) (the builds of opt_trial_kernel).  All ndim + 4 points an iteration of the
+// nm_eval_kernel: one workgroup per (simplex, candidate), on the shell of mp_point.h.  All ndim + 4 points an iteration of the
 // serial algorithm may ask for -- reflection, expansion, outside and inside contraction, the ndim shrunk vertices -- depend on the
-// sorted simplex alone, so lane 0 builds its candidate from it in LDS, the workgroup evaluates it with walker_eval and lane 0 writes
+// sorted simplex alone, so lane 0 builds its candidate from it in LDS, the workgroup evaluates it (point_eval) and lane 0 writes
 // the candidate's row.  Nothing is written that another workgroup of the launch reads.  The initial evaluation runs the same grid
 // on the vertices as they are.
 // nm_decide_kernel: one workgroup per simplex behind every eval launch: scipy's decision tree on the candidates' values, the stable
 // sort of the vertices, the counters and the stop rule for the next iteration.
 #include <hip/hip_runtime.h>
 
-#include "mp_eval.hpp"
 #include "mp_nm.h"
+#include "mp_point.h"
 
 namespace mp {
 
@@ -44,44 +44,23 @@ MP_DEV void nm_build(const NmArgs &a, int s, int c, double *t) {
     }
 }
 
-// W, OCC, SPL, LONG: the builds of opt_trial_kernel, chosen by the same rule for the launch's n_simplex * (ndim + 4) candidates
-// (launch_nm_eval).
+// The builds of mp_point.h for the launch's n_simplex * (ndim + 4) candidates (launch_nm_eval).  Target 2, the terraces of
+// point_eval, is this driver's: mp_simplex_create alone accepts it.
 template <int SPL, bool LONG, int W = 1, int OCC = 0>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
-void nm_eval_kernel(const DevShared sh, const NmArgs a) {
+MP_POINT_KERNEL(SPL, W, OCC) void nm_eval_kernel(const DevShared sh, const NmArgs a) {
     const int nc = a.ndim + 4;
     const int k = (int)blockIdx.x, s = k / nc, c = k - s * nc;
     if (a.stopped[s]) return;                // frozen simplex (uniform for the workgroup): nothing to do
     if (a.initial && c > a.ndim) return;     // the initial evaluation has ndim + 1 points
-    __shared__ TileImage<SPL * W> im;
-    __shared__ TimeTable<SPL * W> tt;
-    __shared__ double lds[1];
-    __shared__ double park[MP_MAX_NDIM];     // the candidate across walker_eval
-    __shared__ TeamLds<SPL * W, (W > 1)> tl;
-    TeamX<SPL * W> *const tx = tl.ptr();
-    tables_init<SPL * W, 64 * W>(sh, tt);
+    __shared__ PointLds<SPL, W> ws;
+    __shared__ double park[MP_MAX_NDIM];     // the candidate across the evaluation
+    tables_init<SPL * W, 64 * W>(sh, ws.tt);
     if (threadIdx.x == 0) nm_build(a, s, c, park);
     __syncthreads();
-    double par[MP_MAX_NDIM];
-#pragma unroll
-    for (int d = 0; d < MP_MAX_NDIM; ++d) par[d] = d < a.ndim ? park[d] : 0.0;
-    double lnp = 0.0;
-    int status = MP_STATUS_OK, sweeps, tiles;
-    if (a.target != 0) {   // 1: isotropic unit Gaussian (opt_trial_kernel's); 2: the same on terraces along x_0, for ties and shrinks (tests)
-#pragma unroll
-        for (int d = 0; d < MP_MAX_NDIM; ++d) lnp = d < a.ndim ? sub_rn(lnp, mul_rn(mul_rn(0.5, par[d]), par[d])) : lnp;
-        if (a.target == 2) lnp = sub_rn(lnp, mul_rn(1.0e-3, floor(mul_rn(37.0, par[0]))));
-    } else {
-        LaunchArgs la{};
-        la.ds_id = a.ds_id;
-        la.ndim = a.ndim;
-        la.physical = 0;
-        la.want_chi2 = 1;
-        if constexpr (W > 1) walker_eval<false, SPL, LONG, false, W, OCC >= 2>(sh, la, k, par, im, tt, lds, lnp, status, sweeps, tiles, tx);
-        else walker_eval<false, SPL, LONG>(sh, la, k, par, im, tt, lds, lnp, status, sweeps, tiles);
-    }
+    double lnp;
+    int status;
+    point_eval<SPL, LONG, W, OCC>(sh, ws, a.ds_id, a.ndim, a.target, k, park, lnp, status);
     if (threadIdx.x == 0) {
-        if (lnp != lnp) lnp = -INFINITY;   // NaN counts (and is kept) as -inf
         for (int d = 0; d < a.ndim; ++d) a.cand[(size_t)k * a.ndim + d] = park[d];
         a.cand_lnp[k] = lnp;
         a.cand_st[k] = status;
@@ -177,17 +156,15 @@ __global__ __launch_bounds__(64) void nm_decide_kernel(const NmArgs a) {
 
 }  // namespace
 
-// The build of launch_opt_trial for a batch of n = n_simplex * (ndim + 4) walkers (fixed for the whole run, the initial evaluation
-// included, stopped simplexes or not).
+// One workgroup per (simplex, candidate): n = n_simplex * (ndim + 4), fixed for the whole run, the initial evaluation included,
+// stopped simplexes or not.
 int launch_nm_eval(const DevShared &sh, const NmArgs &a, void *stream) {
     const int n = a.n_simplex * (a.ndim + 4);
     if (n <= 0) return 0;
-    const Variant v = walker_variant(sh, n, kernel_waves(sh, n) == 4);
-    dispatch([&](auto team, auto roomy, auto lng) {
-        using B = Build<team, roomy>;
+    return launch_point_kernel(sh, n, [&](auto build, auto lng) {
+        using B = decltype(build);
         hipLaunchKernelGGL((nm_eval_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n), dim3(64 * B::W), 0, (hipStream_t)stream, sh, a);
-    }, v.team, v.roomy, sh.has_long != 0);
-    return (int)hipGetLastError();
+    });
 }
 
 int launch_nm_decide(const NmArgs &a, void *stream) {

@@ -1,15 +1,14 @@
 // mp_opt.hip — gfx950 kernels of the differential-evolution optimizer (include/magprop_amd.h mp_optimizer_*): scipy's
 // differential_evolution with deferred updating, one launch per generation.
 //
-// opt_trial_kernel: one workgroup per member (the builds of lnprob_kernel / lnprob_team_kernel: one wavefront with SPL steps
-// per lane, or a team of W = 4 wavefronts).  Lane 0 builds the member's trial vector from the population of the previous
-// generation (OptArgs::pop_cur) in LDS, the workgroup evaluates it with walker_eval, lane 0 decides (greedy) and writes the
-// member's row of the next generation (pop_next).  Nothing is written that another workgroup of the launch reads, so the
-// workgroups need no hand-off among themselves.  Generation 0 runs the same builds on the population as it is.
+// opt_trial_kernel: one workgroup per member, on the shell of mp_point.h.  Lane 0 builds the member's trial vector from the
+// population of the previous generation (OptArgs::pop_cur) in LDS, the workgroup evaluates it (point_eval), lane 0 decides (greedy)
+// and writes the member's row of the next generation (pop_next).  Nothing is written that another workgroup of the launch reads, so
+// the workgroups need no hand-off among themselves.  Generation 0 runs the same builds on the population as it is.
 // opt_reduce_kernel: one workgroup per population behind every generation: the best member, scipy's stop rule, the counters.
 #include <hip/hip_runtime.h>
 
-#include "mp_eval.hpp"
+#include "mp_point.h"
 
 namespace mp {
 
@@ -45,44 +44,23 @@ MP_DEV void opt_build_trial(const OptArgs &o, int p, int i, double *t) {
     }
 }
 
-// W, OCC, SPL, LONG: the builds of launch_lnprob (W = 4: lnprob_team_kernel<1, 4, OCC>; W = 1: lnprob_kernel<false, SPL>), chosen
-// by the same rule for the launch's n_pops * popsize members (launch_opt_trial).
+// The builds of mp_point.h for the launch's n_pops * popsize members (launch_opt_trial).
 template <int SPL, bool LONG, int W = 1, int OCC = 0>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 1 ? OCC : (SPL >= 4 ? 1 : 2), W > 1 ? OCC : (SPL >= 4 ? 1 : 2))))
-void opt_trial_kernel(const DevShared sh, const OptArgs o) {
+MP_POINT_KERNEL(SPL, W, OCC) void opt_trial_kernel(const DevShared sh, const OptArgs o) {
     const int k = (int)blockIdx.x, p = k / o.popsize, i = k - p * o.popsize;
     if (o.trial && o.converged[p]) return;   // frozen population (uniform for the workgroup): nothing to do
-    __shared__ TileImage<SPL * W> im;
-    __shared__ TimeTable<SPL * W> tt;
-    __shared__ double lds[1];
-    __shared__ double park[MP_MAX_NDIM];     // the member's trial (generation 0: the member itself) across walker_eval
-    __shared__ TeamLds<SPL * W, (W > 1)> tl;
-    TeamX<SPL * W> *const tx = tl.ptr();
-    tables_init<SPL * W, 64 * W>(sh, tt);
+    __shared__ PointLds<SPL, W> ws;
+    __shared__ double park[MP_MAX_NDIM];     // the member's trial (generation 0: the member itself) across the evaluation
+    tables_init<SPL * W, 64 * W>(sh, ws.tt);
     if (threadIdx.x == 0) {
         if (o.trial) opt_build_trial(o, p, i, park);
         else for (int d = 0; d < o.ndim; ++d) park[d] = o.pop_cur[(size_t)k * o.ndim + d];
     }
     __syncthreads();
-    double par[MP_MAX_NDIM];
-#pragma unroll
-    for (int d = 0; d < MP_MAX_NDIM; ++d) par[d] = d < o.ndim ? park[d] : 0.0;
-    double lnp = 0.0;
-    int status = MP_STATUS_OK, sweeps, tiles;
-    if (o.target == 1) {   // isotropic unit Gaussian: exercises the algorithm itself (tests)
-#pragma unroll
-        for (int d = 0; d < MP_MAX_NDIM; ++d) lnp = d < o.ndim ? sub_rn(lnp, mul_rn(mul_rn(0.5, par[d]), par[d])) : lnp;
-    } else {
-        LaunchArgs a{};
-        a.ds_id = o.ds_id;
-        a.ndim = o.ndim;
-        a.physical = 0;
-        a.want_chi2 = 1;
-        if constexpr (W > 1) walker_eval<false, SPL, LONG, false, W, OCC >= 2>(sh, a, k, par, im, tt, lds, lnp, status, sweeps, tiles, tx);
-        else walker_eval<false, SPL, LONG>(sh, a, k, par, im, tt, lds, lnp, status, sweeps, tiles);
-    }
+    double lnp;
+    int status;
+    point_eval<SPL, LONG, W, OCC>(sh, ws, o.ds_id, o.ndim, o.target, k, park, lnp, status);
     if (threadIdx.x == 0) {
-        if (lnp != lnp) lnp = -INFINITY;   // NaN counts (and is kept) as -inf
         const bool take = !o.trial || lnp >= o.lnp_cur[k];
         const double *src = take ? park : o.pop_cur + (size_t)k * o.ndim;
         for (int d = 0; d < o.ndim; ++d) o.pop_next[(size_t)k * o.ndim + d] = src[d];
@@ -138,18 +116,15 @@ __global__ __launch_bounds__(64) void opt_reduce_kernel(const OptArgs o) {
 
 }  // namespace
 
-// The build of launch_lnprob for a batch of n = n_pops * popsize walkers (fixed for the whole run, converged populations or not):
-// walker_variant with a team where kernel_waves says so; LONG builds for handles with light curves of more than 64 points.  (The
-// experiments build's two-wavefront team, force_waves = 2, has no optimizer build: one wavefront there.)
+// One workgroup per member: n = n_pops * popsize, fixed for the whole run, converged populations or not.  (The experiments
+// build's two-wavefront team, force_waves = 2, has no build here: one wavefront there.)
 int launch_opt_trial(const DevShared &sh, const OptArgs &o, void *stream) {
     const int n = o.popsize * o.n_pops;
     if (n <= 0) return 0;
-    const Variant v = walker_variant(sh, n, kernel_waves(sh, n) == 4);
-    dispatch([&](auto team, auto roomy, auto lng) {
-        using B = Build<team, roomy>;
+    return launch_point_kernel(sh, n, [&](auto build, auto lng) {
+        using B = decltype(build);
         hipLaunchKernelGGL((opt_trial_kernel<B::SPL, lng, B::W, B::OCC>), dim3((unsigned)n), dim3(64 * B::W), 0, (hipStream_t)stream, sh, o);
-    }, v.team, v.roomy, sh.has_long != 0);
-    return (int)hipGetLastError();
+    });
 }
 
 int launch_opt_reduce(const OptArgs &o, void *stream) {
