@@ -1,9 +1,11 @@
-// mp_host.h — what the host sources of the C ABI share (mp_capi.cpp, mp_summaries.cpp, mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp, mp_simplex.cpp).
+// mp_host.h — what the host sources of the C ABI share (mp_capi.cpp, mp_summaries.cpp, mp_sampler.cpp, mp_monitor.cpp, mp_optimizer.cpp,
+// mp_nested.cpp, mp_simplex.cpp).
 //
 // Internal: not installed, never seen by a kernel source.  Error reporting, owners of device memory, pinned memory and events,
 // the two types behind the ABI's handle -- Evaluator, everything that lives on ONE device, and mp_handle, the dealer that owns
 // one evaluator per device and the lock -- and the helpers of mp_capi.cpp that the summaries and the resident drivers call.  Each driver's own
-// struct stays in its source file.
+// struct stays in its source file; the sampler's two chain monitors are a unit of their own (mp_monitor.h), which the probe
+// libraries of their kernels link as well.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,95 @@
+// mp_monitor.h — the two chain monitors of the ensemble sampler as a host unit of their own (mp_monitor.cpp): the autocorrelation
+// monitor (mp_sampler_set_autocorr; kernels mp_acf.hip) and the posterior monitor (mp_sampler_set_posterior; kernels mp_post.hip).
+//
+// Internal, like mp_host.h.  A monitor knows the shape of the chain, the device rows it is fed and a stream, and nothing of the
+// sampler: mp_sampler.cpp holds one of each behind its entry points, and the probe libraries mp_probe_acf.hip and
+// mp_probe_post.hip drive the same functions over crafted chains.  A function that reports an error names the entry point `fn`.
+#pragma once
+#include <memory>
+
+#include "mp_acf.h"
+#include "mp_host.h"
+#include "mp_post.h"
+
+#pragma GCC visibility push(hidden)
+
+// What both monitors keep: the shape of the chain and the count of the steps that went in.
+struct ChainMonitor {
+    int n_walkers = 0, n_ensembles = 0, n_total = 0, ndim = 0;
+    int chunk_cap = 0;              // most steps per chunk of mp_sampler_run while the monitor is on
+    int64_t n = 0;                  // steps accumulated
+    int64_t discard = 0, skip = 0;  // steps to pass over after a (re)start; how many of them are left
+    ChainMonitor(int n_walkers, int n_ensembles, int ndim, int64_t discard)
+        : n_walkers(n_walkers), n_ensembles(n_ensembles), n_total(n_walkers * n_ensembles), ndim(ndim), discard(discard) {}
+    // chunks of at most 64 MB of chain rows while a monitor is on, and no longer than the sampler's own chunks (sampler_cap)
+    size_t capped(size_t sampler_cap) const {
+        return std::max<size_t>(1, std::min<size_t>(sampler_cap, ((size_t)64 << 20) / ((size_t)n_total * ndim * sizeof(double))));
+    }
+    void start_over() { n = 0; skip = discard; }
+    // Of a chunk of `chunk` steps, the rows that go in: rows [first, first + rows), behind the steps still to be passed over
+    int take(int chunk, int *first) {
+        *first = (int)std::min<int64_t>(skip, chunk);
+        skip -= *first;
+        return chunk - *first;
+    }
+};
+
+// Accumulators and the history ring of mp_acf.h, fed once per chunk of mp_sampler_run from the device slab of chain rows.
+struct AcfMonitor : ChainMonitor {
+    int max_lag = 0, kp = 0;        // lags asked for; rounded up to the kernels' lag block
+    int ring_rows = 0, head = 0;    // the ring: kp + chunk_cap rows; row of the next sample
+    DevBuf<double> hist, S, T, H, pivot, rho, f, tau;
+    DevBuf<int32_t> window;
+    using ChainMonitor::ChainMonitor;
+
+    static int off(const char *fn);
+    static int check(const char *fn, int max_lag, int64_t discard);   // max_lag = 0, which turns the monitor off, passes
+    // A monitor of max_lag >= 1 checked lags with its buffers, within MP_ACF_MAX_BYTES; restart() comes next
+    static int make(const char *fn, int n_walkers, int n_ensembles, int ndim, int max_lag, int64_t discard, size_t sampler_cap,
+                    std::unique_ptr<AcfMonitor> *out);
+    // Empty the monitor (stream-ordered): the series starts again, `discard` steps from now.
+    int restart(hipStream_t st);
+    // The `chunk` rows chain[chunk][n_series] of a chunk into the monitor (stream-ordered)
+    int feed(const double *chain, int chunk, hipStream_t st);
+    // rho, the walker means, windows and taus of the samples so far into the monitor's buffers; waits for them
+    int finalise(const char *fn, double c, hipStream_t st);
+    // read-outs behind mp_sampler_get_autocorr, _get_acf (after finalise) and _get_autocorr_sums (after a wait for the stream)
+    int read_tau(double *tau_out, int32_t *window_out) const;
+    int read_acf(int ensemble, int max_rows, double *acf) const;   // the rows written
+    int read_sums(int ensemble, double *S_out, double *T_out, double *H_out, double *tail, double *pivot_out, int64_t *n_samples) const;
+
+private:
+    mp::AcfArgs args(const double *chain) const;
+};
+
+// The counters, running sums and best-sample holders of mp_post.h, fed once per chunk of mp_sampler_run from the device slab of
+// chain rows and their lnprob.
+struct PostMonitor : ChainMonitor {
+    int bins1 = 0, bins2 = 0;
+    std::vector<double> par;        // [5][ndim] lower, upper, inv1, inv2, pivot (mp::post_params)
+    DevBuf<double> d_par, mom, best_x, best_lnp;
+    DevBuf<int64_t> hist1, hist2, outside2, nfin, best_idx;
+    using ChainMonitor::ChainMonitor;
+
+    static int off(const char *fn);
+    // A monitor of bins1 != 0 bins with its buffers, after the checks of bins1, bins2, discard, the range, the ensemble count and
+    // MP_POST_MAX_BYTES in this order; restart() comes next
+    static int make(const char *fn, int n_walkers, int n_ensembles, int ndim, int bins1, int bins2, const double *lower,
+                    const double *upper, int64_t discard, size_t sampler_cap, std::unique_ptr<PostMonitor> *out);
+    // Empty the monitor (stream-ordered): no sample, best = none, `discard` steps from now.
+    int restart(hipStream_t st);
+    // The `chunk` rows chain[chunk][n_total][ndim] and lnp[chunk][n_total] of a chunk into the monitor (stream-ordered)
+    int feed(const double *chain, const double *lnp, int chunk, hipStream_t st);
+    // The prologue of the read-outs: the ensemble exists, and what was fed has been accumulated
+    int ready(const char *fn, int ensemble, hipStream_t st) const;
+    // read-outs behind mp_sampler_get_posterior_hist1, _hist2, _moments and _best (after ready)
+    int read_hist1(int ensemble, int64_t *hist1_out, int64_t *below, int64_t *above, int64_t *nonfinite, int64_t *n_samples) const;
+    int read_hist2(const char *fn, int ensemble, int64_t *hist2_out, int64_t *outside2_out) const;
+    int read_moments(int ensemble, double *sum1, double *sum2, double *pivot, int64_t *n_finite) const;
+    int read_best(int ensemble, double *x, double *lnprob, int64_t *index) const;
+
+private:
+    mp::PostArgs args(const double *chain, const double *lnp) const;
+};
+
+#pragma GCC visibility pop

@@ -13,6 +13,7 @@
 
 #include "mp_device.h"
 #include "mp_math.hpp"
+#include "mp_probe_bufs.h"
 
 namespace mp {
 
@@ -207,44 +208,6 @@ __global__ void __launch_bounds__(64) pick_kernel(const double *u, const double 
 // ---------------------------------------------------------------- host side
 bool size_ok(int n, int per_lane) { return per_lane >= 1 && n >= 1 && n <= kMaxN && n % (64 * per_lane) == 0; }
 
-// the device copies of one call: inputs uploaded at construction, outputs downloaded by finish()
-struct Bufs {
-    struct Out { double *host, *dev; size_t count; };
-    std::vector<double *> all;
-    std::vector<Out> outs;
-    hipError_t err = hipSuccess;
-
-    const double *in(const double *host, size_t count) {
-        double *d = alloc(count);
-        if (d && err == hipSuccess) err = hipMemcpy(d, host, count * sizeof(double), hipMemcpyHostToDevice);
-        return d;
-    }
-    double *out(double *host, size_t count) {
-        double *d = alloc(count);
-        if (d) outs.push_back({host, d, count});
-        return d;
-    }
-    double *alloc(size_t count) {
-        if (err != hipSuccess) return nullptr;
-        double *d = nullptr;
-        err = hipMalloc(&d, count * sizeof(double));
-        if (err != hipSuccess) return nullptr;
-        all.push_back(d);
-        return d;
-    }
-    bool ready() const { return err == hipSuccess; }
-    int finish() {   // after the launch
-        if (err == hipSuccess) err = hipGetLastError();
-        if (err == hipSuccess) err = hipDeviceSynchronize();
-        for (const Out &o : outs)
-            if (err == hipSuccess) err = hipMemcpy(o.host, o.dev, o.count * sizeof(double), hipMemcpyDeviceToHost);
-        return (int)err;
-    }
-    ~Bufs() {
-        for (double *d : all) (void)hipFree(d);
-    }
-};
-
 // f(std::integral_constant<int, N>) for N in 1 .. 5; false for any other N
 template <class F>
 bool with_n(int N, F &&f) {
@@ -284,7 +247,7 @@ int mpp_unary(int func, int N, const double *x, double *y, int n) {
     if (func < 0 || func >= kUnaryCount || !n124(N) || !size_ok(n, N) || !x || !y) return -1;
     Bufs B;
     const double *dx = B.in(x, n);
-    double *dy = B.out(y, n);
+    double *dy = B.io(y, n);
     if (B.ready()) {
         switch (func) {
             case kRcp: launch_unary<kRcp>(N, dx, dy, n); break;
@@ -294,16 +257,16 @@ int mpp_unary(int func, int N, const double *x, double *y, int n) {
             default: launch_unary<kPow17>(N, dx, dy, n); break;
         }
     }
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 
 int mpp_exp10(const double *x, double *y, int n) {
     if (!size_ok(n, 1) || !x || !y) return -1;
     Bufs B;
     const double *dx = B.in(x, n);
-    double *dy = B.out(y, n);
+    double *dy = B.io(y, n);
     if (B.ready()) exp10_kernel<<<dim3(n / 64), dim3(64)>>>(dx, dy, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 
 // out[n][7] = e^z, phi_1 .. phi_6
@@ -311,14 +274,14 @@ int mpp_phi(int N, const double *z, double *out, int n) {
     if (!n124(N) || !size_ok(n, N) || !z || !out) return -1;
     Bufs B;
     const double *dz = B.in(z, n);
-    double *d = B.out(out, (size_t)n * 7);
+    double *d = B.io(out, (size_t)n * 7);
     if (B.ready()) {
         const dim3 g(n / (64 * N)), b(64);
         if (N == 1) phi_kernel<1><<<g, b>>>(dz, d, n);
         else if (N == 2) phi_kernel<2><<<g, b>>>(dz, d, n);
         else phi_kernel<4><<<g, b>>>(dz, d, n);
     }
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 
 // out[n] = phi6(z, Phi5 with phi_5 = p5)
@@ -326,14 +289,14 @@ int mpp_phi6(int N, const double *z, const double *p5, double *out, int n) {
     if (!n124(N) || !size_ok(n, N) || !z || !p5 || !out) return -1;
     Bufs B;
     const double *dz = B.in(z, n), *dp = B.in(p5, n);
-    double *d = B.out(out, n);
+    double *d = B.io(out, n);
     if (B.ready()) {
         const dim3 g(n / (64 * N)), b(64);
         if (N == 1) phi6_kernel<1><<<g, b>>>(dz, dp, d, n);
         else if (N == 2) phi6_kernel<2><<<g, b>>>(dz, dp, d, n);
         else phi6_kernel<4><<<g, b>>>(dz, dp, d, n);
     }
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 
 // out[n][5] = c_0 .. c_4 from rows of tile kind `kind` of wtab[wtab_len] (wtab_len must be mp::kWtabSize)
@@ -341,7 +304,7 @@ int mpp_node_weights(int N, int pipelined, int kind, const double *wtab, int wta
     if (!n124(N) || !size_ok(n, N) || kind < 0 || kind >= kKinds || wtab_len != kWtabSize || !wtab || !z || !out) return -1;
     Bufs B;
     const double *dw = B.in(wtab, kWtabSize), *dz = B.in(z, n);
-    double *d = B.out(out, (size_t)n * 5);
+    double *d = B.io(out, (size_t)n * 5);
     if (B.ready()) {
         const dim3 g(n / (64 * N)), b(64);
         if (pipelined) {
@@ -354,7 +317,7 @@ int mpp_node_weights(int N, int pipelined, int kind, const double *wtab, int wta
             else weights_kernel<4, false><<<g, b>>>(dw, kind, dz, d, n);
         }
     }
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 int mpp_wtab_size(void) { return kWtabSize; }
 int mpp_wtab_stride(void) { return kWtabStride; }
@@ -363,49 +326,49 @@ int mpp_scan_affine(const double *a, const double *b, double *oa, double *ob, in
     if (!size_ok(n, 1) || !a || !b || !oa || !ob) return -1;
     Bufs B;
     const double *da = B.in(a, n), *db = B.in(b, n);
-    double *xa = B.out(oa, n), *xb = B.out(ob, n);
+    double *xa = B.io(oa, n), *xb = B.io(ob, n);
     if (B.ready()) scan_kernel<<<dim3(n / 64), dim3(64)>>>(da, db, xa, xb, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 int mpp_lane_prev(const double *v, double first, double *out, int n) {
     if (!size_ok(n, 1) || !v || !out) return -1;
     Bufs B;
     const double *dv = B.in(v, n);
-    double *d = B.out(out, n);
+    double *d = B.io(out, n);
     if (B.ready()) lane_prev_kernel<<<dim3(n / 64), dim3(64)>>>(dv, first, d, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 int mpp_lane_prev_map(const double *a, const double *b, double *pa, double *pb, int n) {
     if (!size_ok(n, 1) || !a || !b || !pa || !pb) return -1;
     Bufs B;
     const double *da = B.in(a, n), *db = B.in(b, n);
-    double *xa = B.out(pa, n), *xb = B.out(pb, n);
+    double *xa = B.io(pa, n), *xb = B.io(pb, n);
     if (B.ready()) lane_prev_map_kernel<<<dim3(n / 64), dim3(64)>>>(da, db, xa, xb, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 int mpp_lane_bcast(const double *v, int src, double *out, int n) {
     if (!size_ok(n, 1) || src < 0 || src > 63 || !v || !out) return -1;
     Bufs B;
     const double *dv = B.in(v, n);
-    double *d = B.out(out, n);
+    double *d = B.io(out, n);
     if (B.ready()) lane_bcast_kernel<<<dim3(n / 64), dim3(64)>>>(dv, src, d, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 int mpp_uniform(const double *v, double *out, int n) {
     if (!size_ok(n, 1) || !v || !out) return -1;
     Bufs B;
     const double *dv = B.in(v, n);
-    double *d = B.out(out, n);
+    double *d = B.io(out, n);
     if (B.ready()) uniform_kernel<<<dim3(n / 64), dim3(64)>>>(dv, d, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 int mpp_wave_sum(const double *v, double *out, int n) {
     if (!size_ok(n, 1) || !v || !out) return -1;
     Bufs B;
     const double *dv = B.in(v, n);
-    double *d = B.out(out, n);
+    double *d = B.io(out, n);
     if (B.ready()) wave_sum_kernel<<<dim3(n / 64), dim3(64)>>>(dv, d, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 
 // func: 0 lane_maxabs, 1 lane_minabs, 2 lane_max, 3 lane_min; N = 1 .. 5 values per lane; out[n / N]
@@ -413,7 +376,7 @@ int mpp_lane_ext(int func, int N, const double *v, double *out, int n) {
     if (func < 0 || func >= kExtCount || N < 1 || N > 5 || !size_ok(n, N) || !v || !out) return -1;
     Bufs B;
     const double *dv = B.in(v, n);
-    double *d = B.out(out, n / N);
+    double *d = B.io(out, n / N);
     if (B.ready()) {
         switch (func) {
             case kMaxAbs: launch_ext<kMaxAbs>(N, dv, d, n); break;
@@ -422,7 +385,7 @@ int mpp_lane_ext(int func, int N, const double *v, double *out, int n) {
             default: launch_ext<kMin>(N, dv, d, n); break;
         }
     }
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 
 // addmul = add_rn(mul_rn(a, b), c), submul = sub_rn(a, mul_rn(b, c))
@@ -430,9 +393,9 @@ int mpp_unfused(const double *a, const double *b, const double *c, double *addmu
     if (!size_ok(n, 1) || !a || !b || !c || !addmul || !submul) return -1;
     Bufs B;
     const double *da = B.in(a, n), *db = B.in(b, n), *dc = B.in(c, n);
-    double *x = B.out(addmul, n), *y = B.out(submul, n);
+    double *x = B.io(addmul, n), *y = B.io(submul, n);
     if (B.ready()) unfused_kernel<<<dim3(n / 64), dim3(64)>>>(da, db, dc, x, y, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 
 // terms[n], K per lane (1 .. 64); m[n / K], s[n / K]: the pair of every lane after lse_add over its terms and wave_lse
@@ -440,18 +403,18 @@ int mpp_lse(int K, const double *terms, double *m, double *s, int n) {
     if (K < 1 || K > 64 || !size_ok(n, K) || !terms || !m || !s) return -1;
     Bufs B;
     const double *dt = B.in(terms, n);
-    double *dm = B.out(m, n / K), *ds = B.out(s, n / K);
+    double *dm = B.io(m, n / K), *ds = B.io(s, n / K);
     if (B.ready()) lse_kernel<<<dim3(n / (64 * K)), dim3(64)>>>(dt, K, dm, ds, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 // (om, os) = lse_merge((m, s), (mo, so)) element by element
 int mpp_lse_merge(const double *m, const double *s, const double *mo, const double *so, double *om, double *os, int n) {
     if (!size_ok(n, 1) || !m || !s || !mo || !so || !om || !os) return -1;
     Bufs B;
     const double *a = B.in(m, n), *b = B.in(s, n), *c = B.in(mo, n), *d = B.in(so, n);
-    double *x = B.out(om, n), *y = B.out(os, n);
+    double *x = B.io(om, n), *y = B.io(os, n);
     if (B.ready()) lse_merge_kernel<<<dim3(n / 64), dim3(64)>>>(a, b, c, d, x, y, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 
 // out[n][3] = pick(u, m), pick_skip(u, m, c0), pick_skip2(u, m, c0, c1) per element, the integers m, c0, c1 and the results as
@@ -467,9 +430,9 @@ int mpp_pick(const double *u, const double *m, const double *c0, const double *c
     }
     Bufs B;
     const double *du = B.in(u, n), *dm = B.in(m, n), *d0 = B.in(c0, n), *d1 = B.in(c1, n);
-    double *d = B.out(out, (size_t)n * 3);
+    double *d = B.io(out, (size_t)n * 3);
     if (B.ready()) pick_kernel<<<dim3(n / 64), dim3(64)>>>(du, dm, d0, d1, d, n);
-    return B.finish();
+    return B.finish((int)hipGetLastError());
 }
 
 }  // extern "C"

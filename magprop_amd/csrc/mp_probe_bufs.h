@@ -1,4 +1,4 @@
-// mp_probe_bufs.h — test infrastructure only: the device copies of one call of a probe library (mp_probe_select.hip,
+// mp_probe_bufs.h — test infrastructure only: the device copies of one call of a probe library (mp_probe.hip, mp_probe_select.hip,
 // mp_probe_acf.hip, mp_probe_post.hip, mp_probe_derive.hip, mp_probe_pointwise.hip, mp_probe_commit.hip, mp_probe_flows.hip).  Nothing here is part of libmagprop_amd.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +25,13 @@ struct Bufs {
         void *d = put(host, count * sizeof(T));
         if (d) outs.push_back({host, d, count * sizeof(T)});
         return static_cast<T *>(d);
+    }
+    // a device buffer that somebody else owns: the caller's bytes go into it now and come back with finish()
+    template <class T>
+    void adopt(T *host, T *dev, size_t count) {
+        if (err != hipSuccess || !count) return;
+        err = hipMemcpy(dev, host, count * sizeof(T), hipMemcpyHostToDevice);
+        if (err == hipSuccess) outs.push_back({host, dev, count * sizeof(T)});
     }
     void *put(const void *host, size_t bytes) {
         if (err != hipSuccess) return nullptr;

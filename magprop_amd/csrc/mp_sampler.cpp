@@ -3,33 +3,7 @@
 #include <memory>
 #include <thread>
 
-#include "mp_acf.h"
-#include "mp_host.h"
-#include "mp_post.h"
-
-// The autocorrelation monitor (mp_sampler_set_autocorr): accumulators and the history ring of mp_acf.h, fed once per chunk of
-// mp_sampler_run from the device slab of chain rows.
-struct AcfMonitor {
-    int max_lag = 0, kp = 0;        // lags asked for; rounded up to the kernels' lag block
-    int chunk_cap = 0;              // most steps per chunk of mp_sampler_run while the monitor is on
-    int ring_rows = 0, head = 0;    // the ring: kp + chunk_cap rows; row of the next sample
-    int64_t n = 0;                  // samples accumulated
-    int64_t discard = 0, skip = 0;  // steps to pass over after a (re)start; how many of them are left
-    DevBuf<double> hist, S, T, H, pivot, rho, f, tau;
-    DevBuf<int32_t> window;
-};
-
-// The posterior monitor (mp_sampler_set_posterior): the counters, running sums and best-sample holders of mp_post.h, fed once
-// per chunk of mp_sampler_run from the device slab of chain rows and their lnprob.
-struct PostMonitor {
-    int bins1 = 0, bins2 = 0;
-    int chunk_cap = 0;              // most steps per chunk of mp_sampler_run while the monitor is on
-    int64_t n = 0;                  // steps accumulated
-    int64_t discard = 0, skip = 0;  // steps to pass over after a (re)start; how many of them are left
-    std::vector<double> par;        // [5][ndim] lower, upper, inv1, inv2, pivot (mp::post_params)
-    DevBuf<double> d_par, mom, best_x, best_lnp;
-    DevBuf<int64_t> hist1, hist2, outside2, nfin, best_idx;
-};
+#include "mp_monitor.h"
 
 struct mp_sampler {
     mp_handle *h = nullptr;         // the lock
@@ -78,93 +52,6 @@ static size_t slab_chunk_cap(const mp_sampler *s, size_t perm_cap) {
 }
 static size_t perm_chunk_cap(const mp_sampler *s) {
     return std::max<size_t>(1, std::min<size_t>((size_t)16 << 20, (size_t)32 * MP_BAD_WINDOW) / (size_t)s->n_total);
-}
-
-static mp::AcfArgs acf_args(const mp_sampler *s) {
-    const AcfMonitor *m = s->acf.get();
-    mp::AcfArgs a{};
-    a.chain = s->d_chain.p; a.hist = m->hist.p; a.S = m->S.p; a.T = m->T.p; a.H = m->H.p; a.pivot = m->pivot.p;
-    a.rho = m->rho.p; a.f = m->f.p; a.tau = m->tau.p; a.window = m->window.p;
-    a.n_series = s->n_total * s->ndim; a.n_walkers = s->n_walkers; a.n_ensembles = s->n_ensembles; a.ndim = s->ndim;
-    a.kp = m->kp; a.max_lag = m->max_lag; a.ring_rows = m->ring_rows; a.head = m->head; a.n0 = m->n;
-    return a;
-}
-
-// Empty the monitor (stream-ordered on the handle's stream): the series starts again, `discard` steps from now.
-static int acf_restart(mp_sampler *s) {
-    AcfMonitor *m = s->acf.get();
-    const size_t ns = (size_t)s->n_total * s->ndim;
-    hipStream_t st = s->ev->stream;
-    HIP_TRY(hipMemsetAsync(m->hist.p, 0, (size_t)m->ring_rows * ns * sizeof(double), st));
-    HIP_TRY(hipMemsetAsync(m->S.p, 0, (size_t)m->kp * ns * sizeof(double), st));
-    HIP_TRY(hipMemsetAsync(m->H.p, 0, (size_t)m->kp * ns * sizeof(double), st));
-    HIP_TRY(hipMemsetAsync(m->T.p, 0, ns * sizeof(double), st));
-    HIP_TRY(hipMemsetAsync(m->pivot.p, 0, ns * sizeof(double), st));
-    m->n = 0;
-    m->head = 0;
-    m->skip = m->discard;
-    return MP_OK;
-}
-
-// The chunk's `chunk` rows of the device slab into the monitor, behind the chunk's last step on the handle's stream.
-static int acf_feed(mp_sampler *s, int chunk) {
-    AcfMonitor *m = s->acf.get();
-    const int first = (int)std::min<int64_t>(m->skip, chunk);
-    m->skip -= first;
-    if (first == chunk) return MP_OK;
-    mp::AcfArgs a = acf_args(s);
-    a.first = first;
-    a.rows = chunk - first;
-    const int e = mp::launch_acf_accumulate(a, s->ev->stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    m->head = (m->head + a.rows) % m->ring_rows;
-    m->n += a.rows;
-    return MP_OK;
-}
-
-static mp::PostArgs post_args(const mp_sampler *s) {
-    const PostMonitor *m = s->post.get();
-    mp::PostArgs a{};
-    a.chain = s->d_chain.p; a.lnp = s->d_chain_lnp.p; a.par = m->d_par.p;
-    a.hist1 = m->hist1.p; a.hist2 = m->hist2.p; a.outside2 = m->outside2.p; a.mom = m->mom.p; a.nfin = m->nfin.p;
-    a.best_x = m->best_x.p; a.best_lnp = m->best_lnp.p; a.best_idx = m->best_idx.p;
-    a.n_walkers = s->n_walkers; a.n_ensembles = s->n_ensembles; a.n_total = s->n_total; a.ndim = s->ndim;
-    a.bins1 = m->bins1; a.bins2 = m->bins2; a.n0 = m->n;
-    return a;
-}
-
-// Empty the monitor (stream-ordered on the handle's stream): no sample, best = none, `discard` steps from now.
-static int post_restart(mp_sampler *s) {
-    PostMonitor *m = s->post.get();
-    const size_t ne = (size_t)s->n_ensembles, nt = (size_t)s->n_total, nd = (size_t)s->ndim, np = (size_t)mp::post_n_pairs(s->ndim);
-    hipStream_t st = s->ev->stream;
-    HIP_TRY(hipMemsetAsync(m->hist1.p, 0, ne * nd * mp::post_stride1(m->bins1) * sizeof(int64_t), st));
-    if (m->bins2 && np) {
-        HIP_TRY(hipMemsetAsync(m->hist2.p, 0, ne * np * (size_t)m->bins2 * m->bins2 * sizeof(int64_t), st));
-        HIP_TRY(hipMemsetAsync(m->outside2.p, 0, ne * np * sizeof(int64_t), st));
-    }
-    HIP_TRY(hipMemsetAsync(m->mom.p, 0, (size_t)mp::post_n_entries(s->ndim) * nt * sizeof(double), st));
-    HIP_TRY(hipMemsetAsync(m->nfin.p, 0, nt * sizeof(int64_t), st));
-    const int e = mp::launch_post_reset(post_args(s), st);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    m->n = 0;
-    m->skip = m->discard;
-    return MP_OK;
-}
-
-// The chunk's `chunk` rows of the device slab into the monitor, behind the chunk's last step on the handle's stream.
-static int post_feed(mp_sampler *s, int chunk) {
-    PostMonitor *m = s->post.get();
-    const int first = (int)std::min<int64_t>(m->skip, chunk);
-    m->skip -= first;
-    if (first == chunk) return MP_OK;
-    mp::PostArgs a = post_args(s);
-    a.first = first;
-    a.rows = chunk - first;
-    const int e = mp::launch_post_accumulate(a, s->ev->stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    m->n += a.rows;
-    return MP_OK;
 }
 
 // Move the device window of failed proposals into the host log and reset it.  The caller has made sure that no kernel
@@ -411,8 +298,8 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
     }
     s->have_state = true;
     int rc = MP_OK;
-    if (s->acf) rc = acf_restart(s);     // the series is broken
-    if (!rc && s->post) rc = post_restart(s);
+    if (s->acf) rc = s->acf->restart(ev->stream);     // the series is broken
+    if (!rc && s->post) rc = s->post->restart(ev->stream);
     return rc;
 }
 
@@ -493,8 +380,8 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
                 if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, slab, whole))) return rc;
             }
         }
-        if (monitor && (rc = acf_feed(s, chunk))) return rc;
-        if (post && (rc = post_feed(s, chunk))) return rc;
+        if (monitor && (rc = s->acf->feed(s->d_chain.p, chunk, ev->stream))) return rc;
+        if (post && (rc = s->post->feed(s->d_chain.p, s->d_chain_lnp.p, chunk, ev->stream))) return rc;
         if (chain) {
             HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
             HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
@@ -507,47 +394,20 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
     return MP_OK;
 }
 
-// ---- autocorrelation monitor
+// ---- autocorrelation monitor (mp_monitor.h AcfMonitor)
 int mp_sampler_set_autocorr(mp_sampler *s, int max_lag, int64_t discard) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_set_autocorr: NULL sampler");
-    if (max_lag < 0 || max_lag > MP_ACF_MAX_LAG) return fail(MP_EINVAL, "mp_sampler_set_autocorr: max_lag must be in [0, %d] (MP_ACF_MAX_LAG; 0 turns the monitor off), got %d", MP_ACF_MAX_LAG, max_lag);
-    if (discard < 0) return fail(MP_EINVAL, "mp_sampler_set_autocorr: discard must be >= 0, got %lld", (long long)discard);
+    int rc = AcfMonitor::check("mp_sampler_set_autocorr", max_lag, discard);
+    if (rc) return rc;
     Held held(s->h, s->ev);
     HIP_TRY(hipDeviceSynchronize());
     s->acf.reset();
     if (max_lag == 0) return MP_OK;
-    const size_t ns = (size_t)s->n_total * s->ndim;
-    const int kp = (max_lag + mp::kAcfLagBlock - 1) / mp::kAcfLagBlock * mp::kAcfLagBlock;
-    // chunks of at most 64 MB of chain rows while the monitor is on: the ring holds one chunk behind the kp rows it keeps
-    const size_t cap = std::max<size_t>(1, std::min<size_t>(slab_chunk_cap(s, perm_chunk_cap(s)), ((size_t)64 << 20) / (ns * sizeof(double))));
-    const size_t ring = (size_t)kp + cap;
-    const double bytes = ((double)ring + 3.0 * kp + 2.0) * (double)ns * sizeof(double);   // ring, S, H, rho, T, pivot
-    if (bytes > (double)MP_ACF_MAX_BYTES)
-        return fail(MP_EINVAL, "mp_sampler_set_autocorr: max_lag = %d over %zu series needs %.0f bytes of accumulators, more than MP_ACF_MAX_BYTES = %lld: lower max_lag",
-                    max_lag, ns, bytes, (long long)MP_ACF_MAX_BYTES);
-    std::unique_ptr<AcfMonitor> m(new AcfMonitor());
-    m->max_lag = max_lag; m->kp = kp; m->chunk_cap = (int)cap; m->ring_rows = (int)ring; m->discard = discard;
-    const size_t ned = (size_t)s->n_ensembles * s->ndim;
-    int rc;
-    if ((rc = m->hist.ensure(ring * ns)) || (rc = m->S.ensure((size_t)kp * ns)) || (rc = m->H.ensure((size_t)kp * ns)) ||
-        (rc = m->rho.ensure((size_t)kp * ns)) || (rc = m->T.ensure(ns)) || (rc = m->pivot.ensure(ns)) ||
-        (rc = m->f.ensure(ned * kp)) || (rc = m->tau.ensure(ned)) || (rc = m->window.ensure(ned)))
+    if ((rc = AcfMonitor::make("mp_sampler_set_autocorr", s->n_walkers, s->n_ensembles, s->ndim, max_lag, discard,
+                               slab_chunk_cap(s, perm_chunk_cap(s)), &s->acf)))
         return rc;
-    s->acf = std::move(m);
-    if ((rc = acf_restart(s))) s->acf.reset();
+    if ((rc = s->acf->restart(s->ev->stream))) s->acf.reset();
     return rc;
-}
-
-// rho, the walker means, windows and taus of the samples so far into the monitor's buffers; waits for them
-static int acf_finalise(mp_sampler *s, const char *fn, double c) {
-    if (!s->acf) return fail(MP_ESTATE, "%s: the autocorrelation monitor is off (mp_sampler_set_autocorr)", fn);
-    if (s->acf->n < 2) return fail(MP_ESTATE, "%s: the monitor holds %lld samples, an estimate needs 2 or more", fn, (long long)s->acf->n);
-    mp::AcfArgs a = acf_args(s);
-    a.c = c;
-    const int e = mp::launch_acf_finalise(a, s->ev->stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipStreamSynchronize(s->ev->stream));
-    return MP_OK;
 }
 
 int mp_sampler_get_autocorr(mp_sampler *s, double c, double *tau, int32_t *window, int64_t *n_samples) {
@@ -555,25 +415,18 @@ int mp_sampler_get_autocorr(mp_sampler *s, double c, double *tau, int32_t *windo
     if (!(c > 0.0) || !std::isfinite(c)) return fail(MP_EINVAL, "mp_sampler_get_autocorr: c must be finite and > 0, got %g", c);
     Held held(s->h, s->ev);
     if (n_samples) *n_samples = s->acf ? s->acf->n : 0;
-    int rc = acf_finalise(s, "mp_sampler_get_autocorr", c);
-    if (rc) return rc;
-    const size_t ned = (size_t)s->n_ensembles * s->ndim;
-    return read_back(tau, (const double *)s->acf->tau.p, ned, window, (const int32_t *)s->acf->window.p, ned);
+    if (!s->acf) return AcfMonitor::off("mp_sampler_get_autocorr");
+    const int rc = s->acf->finalise("mp_sampler_get_autocorr", c, s->ev->stream);
+    return rc ? rc : s->acf->read_tau(tau, window);
 }
 
 int mp_sampler_get_acf(mp_sampler *s, int ensemble, int max_rows, double *acf) {
     if (!s || !acf || max_rows < 0) return fail(MP_EINVAL, "mp_sampler_get_acf: bad argument");
     if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "mp_sampler_get_acf: ensemble must be in [0, %d), got %d", s->n_ensembles, ensemble);
     Held held(s->h, s->ev);
-    int rc = acf_finalise(s, "mp_sampler_get_acf", 5.0);
-    if (rc) return rc;
-    const AcfMonitor *m = s->acf.get();
-    const int rows = (int)std::min<int64_t>({(int64_t)max_rows, (int64_t)m->max_lag, m->n});
-    std::vector<double> f((size_t)s->ndim * m->kp);
-    HIP_TRY(hipMemcpy(f.data(), m->f.p + (size_t)ensemble * s->ndim * m->kp, f.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int k = 0; k < rows; ++k)
-        for (int d = 0; d < s->ndim; ++d) acf[(size_t)k * s->ndim + d] = f[(size_t)d * m->kp + k];
-    return rows;
+    if (!s->acf) return AcfMonitor::off("mp_sampler_get_acf");
+    const int rc = s->acf->finalise("mp_sampler_get_acf", 5.0, s->ev->stream);
+    return rc ? rc : s->acf->read_acf(ensemble, max_rows, acf);
 }
 
 int mp_sampler_get_autocorr_sums(mp_sampler *s, int ensemble, double *S, double *T, double *H, double *tail, double *pivot,
@@ -581,81 +434,28 @@ int mp_sampler_get_autocorr_sums(mp_sampler *s, int ensemble, double *S, double 
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_autocorr_sums: NULL sampler");
     if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "mp_sampler_get_autocorr_sums: ensemble must be in [0, %d), got %d", s->n_ensembles, ensemble);
     Held held(s->h, s->ev);
-    if (!s->acf) return fail(MP_ESTATE, "mp_sampler_get_autocorr_sums: the autocorrelation monitor is off (mp_sampler_set_autocorr)");
-    const AcfMonitor *m = s->acf.get();
+    if (!s->acf) return AcfMonitor::off("mp_sampler_get_autocorr_sums");
     HIP_TRY(hipStreamSynchronize(s->ev->stream));
-    const size_t ns = (size_t)s->n_total * s->ndim, w = (size_t)s->n_walkers * s->ndim, off = (size_t)ensemble * w;
-    const size_t K = (size_t)m->max_lag;
-    // rows [r0, r0 + rows) of a [.][n_series] device array, the ensemble's columns -> dst[rows][n_walkers][ndim]
-    auto cols = [&](double *dst, const double *src, size_t r0, size_t rows) {
-        return rows == 0 ? hipSuccess
-                         : hipMemcpy2D(dst, w * sizeof(double), src + r0 * ns + off, ns * sizeof(double), w * sizeof(double), rows, hipMemcpyDeviceToHost);
-    };
-    if (S) HIP_TRY(cols(S, m->S.p, 0, K));
-    if (T) HIP_TRY(cols(T, m->T.p, 0, 1));
-    if (pivot) HIP_TRY(cols(pivot, m->pivot.p, 0, 1));
-    if (H) {
-        HIP_TRY(cols(H, m->H.p, 0, K));
-        std::vector<double> t(w);
-        HIP_TRY(cols(t.data(), m->T.p, 0, 1));
-        for (size_t k = (size_t)std::min<int64_t>(m->n, (int64_t)K - 1) + 1; k < K; ++k)   // H_k = T once k >= n
-            std::memcpy(H + k * w, t.data(), w * sizeof(double));
-    }
-    if (tail) {   // samples n - K .. n - 1: the K ring rows behind the head, zeros before sample 0
-        const size_t start = ((size_t)m->head + (size_t)m->ring_rows - K) % (size_t)m->ring_rows;
-        const size_t a_rows = std::min(K, (size_t)m->ring_rows - start);
-        HIP_TRY(cols(tail, m->hist.p, start, a_rows));
-        HIP_TRY(cols(tail + a_rows * w, m->hist.p, 0, K - a_rows));
-    }
-    if (n_samples) *n_samples = m->n;
-    return MP_OK;
+    return s->acf->read_sums(ensemble, S, T, H, tail, pivot, n_samples);
 }
 
-// ---- posterior monitor
+// ---- posterior monitor (mp_monitor.h PostMonitor)
 int mp_sampler_set_posterior(mp_sampler *s, int bins1, int bins2, const double *lower, const double *upper, int64_t discard) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_set_posterior: NULL sampler");
     Held held(s->h, s->ev);
     HIP_TRY(hipDeviceSynchronize());
     s->post.reset();
     if (bins1 == 0) return MP_OK;
-    if (bins1 < 0 || bins1 > MP_POST_MAX_BINS) return fail(MP_EINVAL, "mp_sampler_set_posterior: bins1 must be in [0, %d] (MP_POST_MAX_BINS; 0 turns the monitor off), got %d", MP_POST_MAX_BINS, bins1);
-    if (bins2 < 0 || bins2 > MP_POST_MAX_BINS2) return fail(MP_EINVAL, "mp_sampler_set_posterior: bins2 must be in [0, %d] (MP_POST_MAX_BINS2; 0: no 2-D histograms), got %d", MP_POST_MAX_BINS2, bins2);
-    if (discard < 0) return fail(MP_EINVAL, "mp_sampler_set_posterior: discard must be >= 0, got %lld", (long long)discard);
-    if (!lower || !upper) return fail(MP_EINVAL, "mp_sampler_set_posterior: NULL range");
-    for (int d = 0; d < s->ndim; ++d)
-        if (!std::isfinite(lower[d]) || !std::isfinite(upper[d]) || !(lower[d] < upper[d]) || !std::isfinite(upper[d] - lower[d]))
-            return fail(MP_EINVAL, "mp_sampler_set_posterior: range of dimension %d must be finite with lower < upper, got [%g, %g]", d, lower[d], upper[d]);
-    if (s->n_ensembles > 65535) return fail(MP_EINVAL, "mp_sampler_set_posterior: at most 65535 ensembles, got %d", s->n_ensembles);
-    const size_t ne = (size_t)s->n_ensembles, nt = (size_t)s->n_total, nd = (size_t)s->ndim;
-    const size_t np = (size_t)mp::post_n_pairs(s->ndim), nent = (size_t)mp::post_n_entries(s->ndim);
-    const size_t n_h1 = ne * nd * mp::post_stride1(bins1), n_h2 = ne * np * (size_t)bins2 * bins2;
-    const double bytes = 8.0 * ((double)n_h1 + (double)n_h2 + (double)(ne * np) + (double)(ne * (nd + 2)) + (double)nt * (double)(nent + 1));
-    if (bytes > (double)MP_POST_MAX_BYTES)
-        return fail(MP_EINVAL, "mp_sampler_set_posterior: bins1 = %d, bins2 = %d over %d ensembles of %d dimensions need %.0f bytes of accumulators, more than MP_POST_MAX_BYTES = %lld: lower the bin counts",
-                    bins1, bins2, s->n_ensembles, s->ndim, bytes, (long long)MP_POST_MAX_BYTES);
-    std::unique_ptr<PostMonitor> m(new PostMonitor());
-    m->bins1 = bins1; m->bins2 = bins2; m->discard = discard;
-    // chunks of at most 64 MB of chain rows while the monitor is on, as under the autocorrelation monitor
-    m->chunk_cap = (int)std::max<size_t>(1, std::min<size_t>(slab_chunk_cap(s, perm_chunk_cap(s)), ((size_t)64 << 20) / (nt * nd * sizeof(double))));
-    m->par.resize(5 * nd);
-    mp::post_params(m->par.data(), s->ndim, bins1, bins2, lower, upper);
-    int rc;
-    if ((rc = m->d_par.ensure(5 * nd)) || (rc = m->hist1.ensure(n_h1)) || (rc = m->hist2.ensure(n_h2)) || (rc = m->outside2.ensure(ne * np)) ||
-        (rc = m->mom.ensure(nent * nt)) || (rc = m->nfin.ensure(nt)) || (rc = m->best_x.ensure(ne * nd)) || (rc = m->best_lnp.ensure(ne)) ||
-        (rc = m->best_idx.ensure(ne)))
-        return rc;
-    HIP_TRY(hipMemcpy(m->d_par.p, m->par.data(), 5 * nd * sizeof(double), hipMemcpyHostToDevice));
-    s->post = std::move(m);
-    if ((rc = post_restart(s))) s->post.reset();
+    int rc = PostMonitor::make("mp_sampler_set_posterior", s->n_walkers, s->n_ensembles, s->ndim, bins1, bins2, lower, upper, discard,
+                               slab_chunk_cap(s, perm_chunk_cap(s)), &s->post);
+    if (rc) return rc;
+    if ((rc = s->post->restart(s->ev->stream))) s->post.reset();
     return rc;
 }
 
-// The prologue of the read-outs: the monitor is on, the ensemble exists, and what was fed has been accumulated
+// The prologue of the posterior read-outs: the monitor is on, the ensemble exists, and what was fed has been accumulated
 static int post_ready(mp_sampler *s, const char *fn, int ensemble) {
-    if (!s->post) return fail(MP_ESTATE, "%s: the posterior monitor is off (mp_sampler_set_posterior)", fn);
-    if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "%s: ensemble must be in [0, %d), got %d", fn, s->n_ensembles, ensemble);
-    HIP_TRY(hipStreamSynchronize(s->ev->stream));
-    return MP_OK;
+    return s->post ? s->post->ready(fn, ensemble, s->ev->stream) : PostMonitor::off(fn);
 }
 
 int mp_sampler_get_posterior_hist1(mp_sampler *s, int ensemble, int64_t *hist1, int64_t *below, int64_t *above,
@@ -663,73 +463,28 @@ int mp_sampler_get_posterior_hist1(mp_sampler *s, int ensemble, int64_t *hist1, 
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_posterior_hist1: NULL sampler");
     Held held(s->h, s->ev);
     const int rc = post_ready(s, "mp_sampler_get_posterior_hist1", ensemble);
-    if (rc) return rc;
-    const PostMonitor *m = s->post.get();
-    const size_t nd = (size_t)s->ndim, B = (size_t)m->bins1, stride = (size_t)mp::post_stride1(m->bins1);
-    std::vector<int64_t> h(nd * stride);
-    HIP_TRY(hipMemcpy(h.data(), m->hist1.p + (size_t)ensemble * nd * stride, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-    for (size_t d = 0; d < nd; ++d) {
-        const int64_t *row = h.data() + d * stride;
-        if (hist1) std::memcpy(hist1 + d * B, row, B * sizeof(int64_t));
-        if (below) below[d] = row[B];
-        if (above) above[d] = row[B + 1];
-        if (nonfinite) nonfinite[d] = row[B + 2];
-    }
-    if (n_samples) *n_samples = m->n * s->n_walkers;
-    return MP_OK;
+    return rc ? rc : s->post->read_hist1(ensemble, hist1, below, above, nonfinite, n_samples);
 }
 
 int mp_sampler_get_posterior_hist2(mp_sampler *s, int ensemble, int64_t *hist2, int64_t *outside2) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_posterior_hist2: NULL sampler");
     Held held(s->h, s->ev);
     const int rc = post_ready(s, "mp_sampler_get_posterior_hist2", ensemble);
-    if (rc) return rc;
-    const PostMonitor *m = s->post.get();
-    if (!m->bins2) return fail(MP_ESTATE, "mp_sampler_get_posterior_hist2: the monitor keeps no 2-D histograms (bins2 = 0)");
-    const size_t np = (size_t)mp::post_n_pairs(s->ndim), cells = (size_t)m->bins2 * m->bins2;
-    if (!np) return MP_OK;
-    return read_back(hist2, (const int64_t *)m->hist2.p + (size_t)ensemble * np * cells, np * cells,
-                     outside2, (const int64_t *)m->outside2.p + (size_t)ensemble * np, np);
+    return rc ? rc : s->post->read_hist2("mp_sampler_get_posterior_hist2", ensemble, hist2, outside2);
 }
 
 int mp_sampler_get_posterior_moments(mp_sampler *s, int ensemble, double *sum1, double *sum2, double *pivot, int64_t *n_finite) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_posterior_moments: NULL sampler");
     Held held(s->h, s->ev);
     const int rc = post_ready(s, "mp_sampler_get_posterior_moments", ensemble);
-    if (rc) return rc;
-    const PostMonitor *m = s->post.get();
-    const size_t nd = (size_t)s->ndim, nw = (size_t)s->n_walkers, nt = (size_t)s->n_total, nent = (size_t)mp::post_n_entries(s->ndim);
-    // the ensemble's walkers of every entry, summed in walker order from 0.0
-    std::vector<double> part(nent * nw), tot(nent);
-    HIP_TRY(hipMemcpy2D(part.data(), nw * sizeof(double), m->mom.p + (size_t)ensemble * nw, nt * sizeof(double), nw * sizeof(double), nent, hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < nent; ++k) {
-        double t = 0.0;
-        for (size_t w = 0; w < nw; ++w) t += part[k * nw + w];
-        tot[k] = t;
-    }
-    if (sum1) std::memcpy(sum1, tot.data(), nd * sizeof(double));
-    if (sum2) {
-        size_t k = nd;
-        for (size_t a = 0; a < nd; ++a)
-            for (size_t b = a; b < nd; ++b, ++k) sum2[a * nd + b] = sum2[b * nd + a] = tot[k];
-    }
-    if (pivot) std::memcpy(pivot, m->par.data() + 4 * nd, nd * sizeof(double));
-    if (n_finite) {
-        std::vector<int64_t> cnt(nw);
-        HIP_TRY(hipMemcpy(cnt.data(), m->nfin.p + (size_t)ensemble * nw, nw * sizeof(int64_t), hipMemcpyDeviceToHost));
-        *n_finite = std::accumulate(cnt.begin(), cnt.end(), (int64_t)0);
-    }
-    return MP_OK;
+    return rc ? rc : s->post->read_moments(ensemble, sum1, sum2, pivot, n_finite);
 }
 
 int mp_sampler_get_posterior_best(mp_sampler *s, int ensemble, double *x, double *lnprob, int64_t *index) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_posterior_best: NULL sampler");
     Held held(s->h, s->ev);
     const int rc = post_ready(s, "mp_sampler_get_posterior_best", ensemble);
-    if (rc) return rc;
-    const PostMonitor *m = s->post.get();
-    return read_back(x, (const double *)m->best_x.p + (size_t)ensemble * s->ndim, (size_t)s->ndim,
-                     lnprob, (const double *)m->best_lnp.p + ensemble, (size_t)1, index, (const int64_t *)m->best_idx.p + ensemble, (size_t)1);
+    return rc ? rc : s->post->read_best(ensemble, x, lnprob, index);
 }
 
 int mp_sampler_set_whole_step(mp_sampler *s, int enable) {
