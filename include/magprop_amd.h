@@ -561,27 +561,66 @@ int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted);
  *                    proposal of that ensemble in that half-step is NaN, is rejected and is never stored.  Sums and the
  *                    log-sum-exp run in a fixed order of their own (workgroup reductions), so a restatement agrees to rounding
  *                    and to the accuracy of log, exp, sqrt, cos, sin; n_comp >= ndim + 1 is required.
- * ln u = ln u01(r2_2, r2_3) for DE and snooker.  Decision (every move): h + beta lnprob(q) - beta lnprob(x_k) > ln u, beta of the
- * walker's ensemble (1 untempered); the stretch move's h is (ndim - 1) ln z.
+ * ln u = ln u01(r2_2, r2_3) for DE and snooker.  Decision (every move but the slice move): h + beta lnprob(q) - beta lnprob(x_k) >
+ * ln u, beta of the walker's ensemble (1 untempered); the stretch move's h is (ndim - 1) ln z.
+ *   MP_MOVE_SLICE    (ensemble slice sampling: Karamanis & Beutler 2021 over Neal 2003's stepping out and shrinkage) params[0] =
+ *                    mu0 (finite, > 0), params[1] = tune_steps (a whole number in [0, 2^31 - 1]); at most one entry per table,
+ *                    n_half >= 2.  Not a propose-then-reject move: every update that does not fail moves the walker.  A slice step
+ *                    is two half-step launches over the step's split, a tune launch, then the swap sweep when tempered.  Walker
+ *                    k at x with stored lnprob lnp_x, its ensemble e at inverse temperature beta_e (1 untempered) and scale mu_e;
+ *                    r = Philox(...; c3 = 0x51C00000 + c):
+ *                      c = 0      partners c1 = pick(u01(r0, r1), n_comp), c2 distinct from c1 by u01(r2, r3) (the DE rule), from the
+ *                                 other half as it stands; direction d = x_c1 - x_c2.
+ *                      c = 1      L = -(mu_e u01(r0, r1)), R = L + mu_e; of the stepping-out budget m = max_steps_out, J = floor(m
+ *                                 u01(r2, r3)) steps go left and K = m - 1 - J right.
+ *                      c = 2      level lny = beta_e lnp_x + ln u01(r0, r1) (product and sum rounded separately; ln 0 = -inf).
+ *                      c = 3 + i  shrink point i = 0 .. max_shrink - 1: t = L + u01(r0, r1) (R - L).
+ *                    Points on the line: q(t)_i = x_i + t d_i (unfused).  q is inside if it lies in the handle's prior box (target 0
+ *                    only, sampler coordinates; a point outside the box is not evaluated) and beta_e lnprob(q) > lny, a NaN lnprob
+ *                    counting as -inf.  Stepping out: while J > 0 and q(L) is inside, L -= mu_e, J -= 1; then while K > 0 and q(R)
+ *                    is inside, R += mu_e, K -= 1.  Shrinkage: if q(t) is inside the walker moves there (n_accepted[k] += 1, its
+ *                    stored lnprob the untempered value of q), else L = t if t < 0, else R = t.  The slice fails, and the walker
+ *                    stays, after max_shrink rejected points, and at once when d = 0 in every coordinate.  A walker whose own
+ *                    lnprob is -inf has lny = -inf: any point with a finite lnprob is inside, and it escapes.  Every evaluated
+ *                    point whose model failed goes to the fbad window (mp_sampler_get_bad): a slice step evaluates several
+ *                    points per walker, so the window fills sooner than with the other moves.
+ *                    Tuning (zeus's rule, a function of the chain alone): behind the second half-step, for every ensemble, with
+ *                    that step's stepping-out steps nexpand_s and rejected shrink points ncontract_s: while fewer than tune_steps
+ *                    slice steps have been taken since mp_sampler_set_moves, mu_e <- mu_e (2 a / (a + ncontract_s)), a = max(1,
+ *                    nexpand_s) (IEEE quotient in double, the product rounded separately).  mu_e, the count of slice steps and
+ *                    the totals live on the device and survive mp_sampler_run calls and mp_sampler_set_positions; only
+ *                    mp_sampler_set_moves resets them, so a run does not depend on how it is split into calls.  Steps of a
+ *                    mixture that draw another move change nothing of it.  Behind the tuning steps, which the user discards, the
+ *                    chain is a plain Markov chain.
  * Philox counters c3 in use: 0, 1 (stretch), 2, 3 (DE, snooker), 0x4B00 .. 0x4B05 (KDE), 0x5117 (splits), 0x30FE (move of a
- * step), 0 with half = 2 (swaps); the optimizer 0xDE00 .. and 0xDEFF, the nested sampler 0x4E000000 + j (random walk) and
- * 0x4E400000 + 0x100 s + c (slice mode).
+ * step), 0 with half = 2 (swaps), 0x51C00000 + c, c = 0 .. 2 + max_shrink (slice move); the optimizer 0xDE00 .. and 0xDEFF, the
+ * nested sampler 0x4E000000 + j (random walk) and 0x4E400000 + 0x100 s + c (slice mode).
  * Mixtures: one move per step for the whole sampler.  With n_moves > 1, step s draws r = Philox(seed; s, 3, 0, 0x30FE) and takes
  * the first move m with u01(r0, r1) C_last < C_m, C the cumulative weights (summed in order, double): the move of a step depends
- * on (seed, s, table) only, so split runs give the chain of one run.  DE, snooker and KDE steps run two half-step launches (plus the
+ * on (seed, s, table) only, so split runs give the chain of one run.  DE, snooker, KDE and slice steps run two half-step launches (plus the
  * swap sweep when tempered); stretch steps run as mp_sampler_set_whole_step decides.
  * n_moves == 0 restores the default (the stretch move with the a of mp_sampler_create); may be called between runs.
  * MP_EINVAL: NULL sampler or arrays, n_moves outside [0, MP_MAX_MOVES], an unknown kind, a weight that is not finite and > 0,
- * bad params (NaN and inf included), DE with n_half < 2, snooker with n_half < 3, KDE with n_comp < ndim + 1.  With a table
+ * bad params (NaN and inf included), DE with n_half < 2, snooker with n_half < 3, KDE with n_comp < ndim + 1, slice with n_half < 2 or a second slice entry.  With a table
  * set (n_moves > 0), the walker-sharded entry points (mp_sampler_halfstep_*, mp_sampler_step_*) return MP_ESTATE.
  */
 #define MP_MOVE_STRETCH 0   /* params: a (> 1)                                              */
 #define MP_MOVE_DE      1   /* params: g0 (0: 2.38/sqrt(2 ndim)), sigma in [0, 1/sqrt(3))    */
 #define MP_MOVE_SNOOKER 2   /* params: gamma_s (> 0)                                         */
 #define MP_MOVE_KDE     3   /* params: bandwidth (0 Scott, -1 Silverman, > 0 factor), 0      */
+#define MP_MOVE_SLICE   4   /* params: mu0 (> 0), tune_steps (whole, 0 .. 2^31 - 1)            */
 #define MP_MAX_MOVES    8
 int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const double *weights,
                          const double *params /* [n_moves][2] */);
+/* The limits of a slice of MP_MOVE_SLICE: the stepping-out budget (1 .. MP_NEST_MAX_STEPS_OUT, default 32) and the shrink points
+ * before a slice counts as failed (1 .. MP_SLICE_MAX_SHRINK, default 64).  May be called between runs; MP_EINVAL outside the ranges. */
+#define MP_SLICE_MAX_SHRINK 252
+int mp_sampler_set_slice_limits(mp_sampler *s, int max_steps_out, int max_shrink);
+/* The state of MP_MOVE_SLICE, each output [n_ensembles] and optional (NULL): the scale mu now and, since mp_sampler_set_moves,
+ * the stepping-out steps taken, the shrink points rejected, the slices that failed, the points evaluated and the slice steps taken
+ * (mu is tuned while that is below tune_steps).  MP_ESTATE when the move table has no slice move. */
+int mp_sampler_get_slice(mp_sampler *s, double *mu, int64_t *nexpand, int64_t *ncontract, int64_t *nfail, int64_t *neval,
+                         int64_t *n_tuned);
 /*
  * Proposals inside the prior whose model evaluation failed ('flag' / non-finite): what the reference's lnprob appends
  * to its `fbad` file (code/synthetic_datasets/mcmc_eqns.py:72-79).  The kernels collect them in a device-side window of

@@ -29,7 +29,8 @@ FLOW_CURVES = ("Rm", "Rc", "Rlc", "fastness", "Mdot_prop", "Mdot_acc", "Mdot_fb"
 DE_BEST1BIN, DE_RAND1BIN = 0, 1                               # include/magprop_amd.h MP_DE_*
 NEST_MIN_LIVE, NEST_MAX_LIVE, NEST_MAX_WALKS = 16, 4096, 4096  # include/magprop_amd.h MP_NEST_*
 NEST_MAX_SLICES, NEST_MAX_STEPS_OUT, NEST_MAX_SHRINK = 4096, 4096, 254
-ACF_MAX_LAG, ACF_MAX_BYTES = 4096, 8 << 30                    # include/magprop_amd.h MP_ACF_*
+MOVE_SLICE, SLICE_MAX_SHRINK = 4, 252                          # include/magprop_amd.h MP_MOVE_SLICE, MP_SLICE_MAX_SHRINK
+ACF_MAX_LAG, ACF_MAX_BYTES = 4096, 8 << 30                   # include/magprop_amd.h MP_ACF_*
 POST_MAX_BINS, POST_MAX_BINS2, POST_MAX_BYTES = 4096, 128, 1 << 30   # include/magprop_amd.h MP_POST_*
 
 ABI_VERSION = 5
@@ -90,6 +91,8 @@ SIGNATURES = {
     "mp_sampler_set_temperatures": (_i, [_vp, _i, _dp]),
     "mp_sampler_get_swaps": (_i, [_vp, _i64p]),
     "mp_sampler_set_moves": (_i, [_vp, _i, _ip, _dp, _dp]),
+    "mp_sampler_set_slice_limits": (_i, [_vp, _i, _i]),
+    "mp_sampler_get_slice": (_i, [_vp, _dp, _i64p, _i64p, _i64p, _i64p, _i64p]),
     "mp_sampler_get_bad": (_i, [_vp, _i64, _dp, _i, _i64p, _i64p]),
     "mp_sampler_n_slots": (_i, [_vp]),
     "mp_sampler_row_doubles": (_i, [_vp]),

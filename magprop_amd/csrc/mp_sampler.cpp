@@ -1,9 +1,10 @@
-// mp_sampler.cpp — the device-resident ensemble sampler (mp_sampler_*): stretch, DE, snooker and KDE moves, tempering, whole-step
-// and walker-sharded driving.  Kernels: mp_kernels.hip.
+// mp_sampler.cpp — the device-resident ensemble sampler (mp_sampler_*): stretch, DE, snooker, KDE and slice moves, tempering,
+// whole-step and walker-sharded driving.  Kernels: mp_kernels.hip, and mp_slice.hip for the slice move.
 #include <memory>
 #include <thread>
 
 #include "mp_monitor.h"
+#include "mp_slice.h"
 
 struct mp_sampler {
     mp_handle *h = nullptr;         // the lock
@@ -37,10 +38,18 @@ struct mp_sampler {
     // proposal moves (mp_sampler_set_moves); empty: the stretch move with scale a
     struct Move {
         int32_t kind;
-        double p0, p1;              // stretch: a; DE: g0 (resolved), s = sigma sqrt(3); snooker: gamma_s; KDE: f (resolved)
+        double p0, p1;              // stretch: a; DE: g0 (resolved), s = sigma sqrt(3); snooker: gamma_s; KDE: f (resolved);
+                                    // slice: mu0, tune_steps
     };
     std::vector<Move> moves;
     std::vector<double> move_cum;   // cumulative weights, summed in order
+    // the slice move (MP_MOVE_SLICE): its per-ensemble state on the device, set up by mp_sampler_set_moves when the table has one
+    bool has_slice = false;
+    int64_t slice_tune = 0;         // params[1]
+    int slice_steps_out = 32, slice_shrink = 64;   // mp_sampler_set_slice_limits
+    DevBuf<double> d_slice_mu;      // [n_ensembles]
+    DevBuf<int64_t> d_slice_cnt;    // [kSliceCnt][n_ensembles]: nexpand_s, ncontract_s, nexpand, ncontract, nfail, neval, n_tuned
+    static constexpr int kSliceCnt = 7;
     std::unique_ptr<AcfMonitor> acf;   // the autocorrelation monitor; null: off
     std::unique_ptr<PostMonitor> post; // the posterior monitor; null: off
 };
@@ -139,6 +148,19 @@ static mp::StretchArgs stretch_args(const mp_sampler *s, const int32_t *d_perm, 
     return g;
 }
 
+// the slice move's launch arguments over the sampler's buffers
+static mp::SliceArgs slice_args(const mp_sampler *s) {
+    const size_t ne = (size_t)s->n_ensembles;
+    int64_t *c = s->d_slice_cnt.p;
+    mp::SliceArgs sl{};
+    sl.mu = s->d_slice_mu.p;
+    sl.nexpand_s = c; sl.ncontract_s = c + ne; sl.nexpand = c + 2 * ne; sl.ncontract = c + 3 * ne;
+    sl.nfail = c + 4 * ne; sl.neval = c + 5 * ne; sl.n_tuned = c + 6 * ne;
+    sl.tune_steps = s->slice_tune;
+    sl.max_steps_out = s->slice_steps_out; sl.max_shrink = s->slice_shrink;
+    return sl;
+}
+
 extern "C" {
 
 mp_sampler *mp_sampler_create(mp_handle *h, int n_walkers, int n_ensembles, int ndim, const int32_t *ens_ds_id,
@@ -216,6 +238,7 @@ int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const
     std::vector<mp_sampler::Move> mv;
     std::vector<double> cum;
     double c = 0.0;
+    int slice_at = -1;   // the table's slice entry
     for (int m = 0; m < n_moves; ++m) {
         const double w = weights[m], p0 = params[2 * m], p1 = params[2 * m + 1];
         if (!std::isfinite(w) || !(w > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: weight %d must be finite and > 0, got %g", m, w);
@@ -248,6 +271,16 @@ int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const
             x.p0 = p0 > 0.0 ? p0 : std::pow(p0 == 0.0 ? (double)n_comp : n_comp * (d + 2.0) / 4.0, -1.0 / (d + 4));
             break;
         }
+        case MP_MOVE_SLICE:
+            if (!std::isfinite(p0) || !(p0 > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: slice mu0 must be finite and > 0, got %g", p0);
+            if (!(p1 >= 0.0) || !(p1 <= 2147483647.0) || p1 != std::floor(p1))
+                return fail(MP_EINVAL, "mp_sampler_set_moves: slice tune_steps must be a whole number in [0, 2^31 - 1], got %g", p1);
+            if (n_half < 2) return fail(MP_EINVAL, "mp_sampler_set_moves: the slice move needs n_walkers >= 4 (two partners in the other half)");
+            if (slice_at >= 0) return fail(MP_EINVAL, "mp_sampler_set_moves: at most one slice move per table (entries %d and %d)", slice_at, m);
+            slice_at = m;
+            x.p0 = p0;
+            x.p1 = p1;
+            break;
         default:
             return fail(MP_EINVAL, "mp_sampler_set_moves: unknown move kind %d", (int)kinds[m]);
         }
@@ -255,10 +288,45 @@ int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const
         c += w;
         cum.push_back(c);
     }
-    Lock lock(s->h->mu);
+    Held held(s->h, s->ev);
+    if (slice_at >= 0) {   // the move's state starts over: mu = mu0, no step taken, the counters at zero
+        const size_t ne = (size_t)s->n_ensembles;
+        int rc;
+        if ((rc = s->d_slice_mu.ensure(ne)) || (rc = s->d_slice_cnt.ensure(mp_sampler::kSliceCnt * ne))) return rc;
+        HIP_TRY(hipDeviceSynchronize());
+        const std::vector<double> mu0(ne, mv[(size_t)slice_at].p0);
+        HIP_TRY(hipMemcpy(s->d_slice_mu.p, mu0.data(), ne * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(s->d_slice_cnt.p, 0, mp_sampler::kSliceCnt * ne * sizeof(int64_t)));
+        s->slice_tune = (int64_t)mv[(size_t)slice_at].p1;
+    }
+    s->has_slice = slice_at >= 0;
     s->moves = std::move(mv);
     s->move_cum = std::move(cum);
     return MP_OK;
+}
+
+int mp_sampler_set_slice_limits(mp_sampler *s, int max_steps_out, int max_shrink) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_set_slice_limits: NULL sampler");
+    if (max_steps_out < 1 || max_steps_out > MP_NEST_MAX_STEPS_OUT)
+        return fail(MP_EINVAL, "mp_sampler_set_slice_limits: max_steps_out must be 1 .. %d, got %d", MP_NEST_MAX_STEPS_OUT, max_steps_out);
+    if (max_shrink < 1 || max_shrink > MP_SLICE_MAX_SHRINK)
+        return fail(MP_EINVAL, "mp_sampler_set_slice_limits: max_shrink must be 1 .. %d, got %d", MP_SLICE_MAX_SHRINK, max_shrink);
+    Lock lock(s->h->mu);
+    s->slice_steps_out = max_steps_out;
+    s->slice_shrink = max_shrink;
+    return MP_OK;
+}
+
+int mp_sampler_get_slice(mp_sampler *s, double *mu, int64_t *nexpand, int64_t *ncontract, int64_t *nfail, int64_t *neval,
+                         int64_t *n_tuned) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_slice: NULL sampler");
+    Held held(s->h, s->ev);
+    if (!s->has_slice) return fail(MP_ESTATE, "mp_sampler_get_slice: the move table has no slice move (mp_sampler_set_moves)");
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t ne = (size_t)s->n_ensembles;
+    const mp::SliceArgs sl = slice_args(s);
+    return read_back(mu, (const double *)sl.mu, ne, nexpand, (const int64_t *)sl.nexpand, ne, ncontract, (const int64_t *)sl.ncontract, ne,
+                     nfail, (const int64_t *)sl.nfail, ne, neval, (const int64_t *)sl.neval, ne, n_tuned, (const int64_t *)sl.n_tuned, ne);
 }
 
 int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted) {
@@ -305,7 +373,8 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
 
 // Enqueue step steps_done + row of mp_sampler_run on the handle's stream: split d_perm, chain row `row` of the device slab when
 // chain is set, move mv (nullptr: the stretch move of mp_sampler_create).  A whole step per launch (stretch_step_kernel and the
-// commit kernel) where `whole` and the move is the stretch move, else two half-step launches; then the swap sweep when tempered.
+// commit kernel) where `whole` and the move is the stretch move, else two half-step launches (the slice move: of slice_half_kernel,
+// with the tune launch behind them); then the swap sweep when tempered.
 static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_sampler::Move *mv, bool chain, bool whole) {
     Evaluator *ev = s->ev;
     mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done + (uint64_t)row, 0);
@@ -317,10 +386,16 @@ static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_
         if (mv->kind == MP_MOVE_STRETCH) g.a = mv->p0;
         else if (mv->kind == MP_MOVE_DE) { g.de_g0 = mv->p0; g.de_s = mv->p1; }
         else if (mv->kind == MP_MOVE_SNOOKER) g.gamma_s = mv->p0;
-        else g.kde_f = mv->p0;
+        else if (mv->kind == MP_MOVE_KDE) g.kde_f = mv->p0;
     }
     int e;
-    if (whole && g.move == MP_MOVE_STRETCH) {
+    if (g.move == MP_MOVE_SLICE) {
+        const mp::SliceArgs sl = slice_args(s);
+        e = mp::launch_slice_half(ev->sh, g, sl, ev->stream);
+        g.half = 1;
+        if (!e) e = mp::launch_slice_half(ev->sh, g, sl, ev->stream);
+        if (!e) e = mp::launch_slice_tune(sl, s->n_ensembles, ev->stream);
+    } else if (whole && g.move == MP_MOVE_STRETCH) {
         g.spec = s->d_spec.p;
         e = mp::launch_stretch_step(ev->sh, g, 3 * g.n_half * g.n_ensembles, ev->stream);
         if (!e) e = mp::launch_stretch_step_commit(g, ev->stream);

@@ -35,7 +35,7 @@ class EnsembleSampler:
         parallel tempering with one ensemble per (dataset, temperature), nensembles = len(datasets) x T (T for
         target="gaussian"), positions in ensemble order (group g, temperature t: walkers [(g T + t) nwalkers, + nwalkers)).
         moves: None (the stretch move with scale a, as emcee), or emcee's moves= forms over magprop_amd.moves (StretchMove,
-        DEMove, DESnookerMove, KDEMove): a move, a list of moves, or a list of (move, weight); one move is drawn per step
+        DEMove, DESnookerMove, KDEMove, SliceMove): a move, a list of moves, or a list of (move, weight); one move is drawn per step
         (include/magprop_amd.h mp_sampler_set_moves).  Give the stretch scale as StretchMove(a) then: moves together with a
         non-default a is refused."""
         if nwalkers % 2 or nwalkers < 2:
@@ -79,6 +79,9 @@ class EnsembleSampler:
             params = np.ascontiguousarray(move_tab[2], dtype=np.float64)
             _capi.check(self._L.mp_sampler_set_moves(self._s, int(kinds.size), _capi.ptr(kinds), _capi.ptr(weights), _capi.ptr(params)),
                         "mp_sampler_set_moves")
+            sl = _moves.slice_move(self.moves)
+            if sl is not None:
+                _capi.check(self._L.mp_sampler_set_slice_limits(self._s, *sl.limits()), "mp_sampler_set_slice_limits")
         self.seed = int(seed)
         self._chain = None
         self._lnp = None
@@ -240,6 +243,16 @@ class EnsembleSampler:
         done = _capi.read_back(self._L.mp_sampler_get_state, self._s, [("pos", None, None), ("lnp", None, None),
                                                                        ("acc", None, None), ("done", (), np.int64)])["done"]
         return acc / max(int(done) * self.nwalkers, 1)
+
+    def get_slice_stats(self):
+        """The state of the slice move (moves=SliceMove(...); mp_sampler_get_slice), one entry per ensemble: the scale "mu" now
+        and, since the sampler was made, "nexpand" stepping-out steps, "ncontract" rejected shrink points, "nfail" failed
+        slices, "neval" evaluated points and "n_tuned" slice steps taken (mu is tuned over the first SliceMove.tune of them)."""
+        if self.moves is None or _moves.slice_move(self.moves) is None:
+            raise ValueError("get_slice_stats needs a sampler with a SliceMove in moves=")
+        n = self.nensembles
+        return _capi.read_back(self._L.mp_sampler_get_slice, self._s, [("mu", n, np.float64)] + [
+            (k, n, np.int64) for k in ("nexpand", "ncontract", "nfail", "neval", "n_tuned")])
 
     def log_evidence(self, discard=0, group=0, prior_draws=2 ** 20):
         """(lnZ, dlnZ) of group `group`'s dataset, the prior normalised over its box, from the stored chain of a tempered run:

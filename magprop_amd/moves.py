@@ -3,6 +3,7 @@
     EnsembleSampler(..., moves=DEMove())
     EnsembleSampler(..., moves=[(DEMove(), 0.8), (DESnookerMove(), 0.2)])
     EnsembleSampler(..., moves=KDEMove())
+    EnsembleSampler(..., moves=SliceMove())
 
 Every move runs inside the fused half-step kernels; these classes only carry the parameters.  One move is drawn per step for
 the whole sampler, with probability proportional to its weight, as in emcee.  Two deviations from emcee 3.1:
@@ -11,8 +12,9 @@ partners from the other half of a two-way split, not from a four-way split.
 """
 import math
 
-MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_KDE = 0, 1, 2, 3   # include/magprop_amd.h MP_MOVE_*
+MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_KDE, MOVE_SLICE = 0, 1, 2, 3, 4   # include/magprop_amd.h MP_MOVE_*
 MAX_MOVES = 8                                       # MP_MAX_MOVES
+SLICE_MAX_STEPS_OUT, SLICE_MAX_SHRINK = 4096, 252   # MP_NEST_MAX_STEPS_OUT, MP_SLICE_MAX_SHRINK
 
 
 class Move:
@@ -116,6 +118,50 @@ class KDEMove(Move):
         return f"KDEMove(bw_method={self.bw_method!r})"
 
 
+class SliceMove(Move):
+    """Ensemble slice sampling (Karamanis & Beutler 2021, the sampler known as zeus): a slice update by Neal's stepping out and
+    shrinkage along the difference of two walkers of the other half.  Every update moves the walker unless the slice fails
+    (max_shrink rejected points); a failed model evaluation is a point outside the slice.  mu: the initial scale of the
+    interval, in units of the direction; it tunes itself over the first `tune` slice steps, which the user discards.
+    max_steps_out, max_shrink: the stepping-out budget and the shrink points of a slice (mp_sampler_set_slice_limits)."""
+    kind = MOVE_SLICE
+
+    def __init__(self, mu=1.0, tune=100, max_steps_out=32, max_shrink=64):
+        mu = float(mu)
+        if not (math.isfinite(mu) and mu > 0.0):
+            raise ValueError(f"SliceMove: mu must be finite and > 0, got {mu}")
+        if isinstance(tune, bool) or int(tune) != tune or not 0 <= int(tune) <= 2 ** 31 - 1:
+            raise ValueError(f"SliceMove: tune must be a whole number in [0, 2^31 - 1], got {tune!r}")
+        for name, v, hi in (("max_steps_out", max_steps_out, SLICE_MAX_STEPS_OUT), ("max_shrink", max_shrink, SLICE_MAX_SHRINK)):
+            if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= hi:
+                raise ValueError(f"SliceMove: {name} must be a whole number in [1, {hi}], got {v!r}")
+        self.mu, self.tune, self.max_steps_out, self.max_shrink = mu, int(tune), int(max_steps_out), int(max_shrink)
+
+    def params(self, ndim):
+        return (self.mu, float(self.tune))
+
+    def limits(self):
+        """(max_steps_out, max_shrink) as mp_sampler_set_slice_limits takes them."""
+        return (self.max_steps_out, self.max_shrink)
+
+    def __eq__(self, other):
+        return Move.__eq__(self, other) and self.limits() == other.limits()
+
+    def __hash__(self):
+        return hash((type(self).__name__, self.params(0), self.limits()))
+
+    def __repr__(self):
+        return f"SliceMove(mu={self.mu}, tune={self.tune}, max_steps_out={self.max_steps_out}, max_shrink={self.max_shrink})"
+
+
+def slice_move(table):
+    """The SliceMove of a parsed table, or None."""
+    for mv, _ in table:
+        if isinstance(mv, SliceMove):
+            return mv
+    return None
+
+
 def parse_moves(moves):
     """emcee's forms of moves=: a move, a list of moves (equal weights) or a list of (move, weight).  Returns a list of
     (move, weight).  Weights are kept as given (emcee normalises them; the draw is the same up to rounding)."""
@@ -139,13 +185,15 @@ def parse_moves(moves):
         except (TypeError, ValueError):
             raise ValueError(f"moves entries must be moves or (move, weight) pairs, got {it!r}") from None
         if not isinstance(mv, Move):
-            raise ValueError(f"not a move: {mv!r} (StretchMove, DEMove, DESnookerMove, KDEMove)")
+            raise ValueError(f"not a move: {mv!r} (StretchMove, DEMove, DESnookerMove, KDEMove, SliceMove)")
         w = float(w)
         if not (math.isfinite(w) and w > 0.0):
             raise ValueError(f"move weights must be finite and > 0, got {w}")
         out.append((mv, w))
     if any(isinstance(it, Move) for it in items) and not all(isinstance(it, Move) for it in items):
         raise ValueError("moves mixes bare moves and (move, weight) pairs")
+    if sum(isinstance(mv, SliceMove) for mv, _ in out) > 1:
+        raise ValueError("at most one SliceMove in a table (its scale mu is the sampler's)")
     return out
 
 
@@ -160,12 +208,12 @@ def move_table(moves, ndim):
 
 def parse_spec(spec):
     """'de:0.8,snooker:0.2' (the command-line form of tools/run_synth_mcmc.py) -> [(DEMove(), 0.8), (DESnookerMove(), 0.2)].
-    Names: stretch, de, snooker, kde; a missing weight is 1."""
-    names = {"stretch": StretchMove, "de": DEMove, "snooker": DESnookerMove, "kde": KDEMove}
+    Names: stretch, de, snooker, kde, slice; a missing weight is 1."""
+    names = {"stretch": StretchMove, "de": DEMove, "snooker": DESnookerMove, "kde": KDEMove, "slice": SliceMove}
     out = []
     for part in str(spec).split(","):
         name, _, w = part.strip().partition(":")
         if name not in names:
-            raise ValueError(f"unknown move {name!r} in {spec!r} (stretch, de, snooker, kde)")
+            raise ValueError(f"unknown move {name!r} in {spec!r} (stretch, de, snooker, kde, slice)")
         out.append((names[name](), float(w) if w else 1.0))
     return out

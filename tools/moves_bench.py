@@ -2,11 +2,12 @@
 
     python tools/moves_bench.py rate [--sizes 64,512,1024,4096]   walker-steps/s and acceptance of every configuration
     python tools/moves_bench.py tau                               integrated autocorrelation time per move, 512 walkers x 6 000 steps
-    python tools/moves_bench.py profile --walkers 1024 [--move kde]  a short DE (KDE) run to profile (rocprofv3 --kernel-trace --stats -- ...)
+    python tools/moves_bench.py profile --walkers 1024 [--move kde|slice]  a short DE (KDE, slice) run to profile (rocprofv3 --kernel-trace --stats -- ...)
 
 Configurations: stretch with its default launch (a whole step per launch where it fits), stretch with whole_step=False (the
-launches DE and snooker run: two half-step launches per step), DE, snooker, the mixture 0.8 DE + 0.2 snooker, KDE and the
-mixture 0.8 KDE + 0.2 DE.
+launches DE and snooker run: two half-step launches per step), DE, snooker, the mixture 0.8 DE + 0.2 snooker, KDE, the
+mixture 0.8 KDE + 0.2 DE, and the slice move (its rows also carry the evaluations per walker and step, the failed slices and
+mu; its warm-up covers its tuning steps where --warm is at least 100).
 Rate: every sampler starts at the Humped truth (1e-4 ball), runs --warm steps unstored, then --steps timed steps unstored
 (mp_sampler_run returns when its steps are done).  Tau: --tau-steps stored steps, the first quarter discarded; effective samples
 per second = walker-steps/s of the rate run at the same size / mean tau over the six parameters.
@@ -23,7 +24,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from magprop_amd import DEMove, DESnookerMove, EnsembleSampler, KDEMove  # noqa: E402
+from magprop_amd import DEMove, DESnookerMove, EnsembleSampler, KDEMove, SliceMove  # noqa: E402
 
 TRUTH = [1.0, 5.0, -3.0, 2.0, -1.0, 0.0]     # Humped, sampler coordinates
 CONFIGS = {
@@ -34,7 +35,17 @@ CONFIGS = {
     "de0.8_snooker0.2": dict(moves=[(DEMove(), 0.8), (DESnookerMove(), 0.2)]),
     "kde": dict(moves=KDEMove()),
     "kde0.8_de0.2": dict(moves=[(KDEMove(), 0.8), (DEMove(), 0.2)]),
+    "slice": dict(moves=SliceMove()),
 }
+
+
+def slice_row(s, walker_steps):
+    """What the slice move adds to a row: evaluations per walker and step, failed slices per update, mu."""
+    st = s.get_slice_stats()
+    return {"evaluations_per_walker_step": float(st["neval"].sum()) / walker_steps,
+            "expansions_per_walker_step": float(st["nexpand"].sum()) / walker_steps,
+            "contractions_per_walker_step": float(st["ncontract"].sum()) / walker_steps,
+            "failed_slice_fraction": float(st["nfail"].sum()) / walker_steps, "mu": [float(v) for v in st["mu"]]}
 
 
 def data():
@@ -60,6 +71,8 @@ def rate_at(nwalk, warm, steps):
         nbad, _ = s.get_bad()
         rows[name] = {"ms_per_step": dt / steps * 1e3, "walker_steps_per_s": nwalk * steps / dt,
                       "acceptance": float(acc.mean()), "failed_proposal_fraction": nbad / (nwalk * (warm + steps))}
+        if name == "slice":
+            rows[name].update(slice_row(s, nwalk * (warm + steps)))
         s.close()
     base, half = rows["stretch"]["walker_steps_per_s"], rows["stretch_half_steps"]["walker_steps_per_s"]
     for r in rows.values():
@@ -102,6 +115,8 @@ def tau(args):
                               "effective_samples_per_s": r["walker_steps_per_s"] / float(np.mean(t)),
                               "median": [float(v) for v in np.median(chain.reshape(-1, 6), axis=0)],
                               "std": [float(v) for v in chain.reshape(-1, 6).std(axis=0)]}
+        if name == "slice":
+            out["moves"][name].update(slice_row(s, nwalk * n_steps))
         s.close()
     ref = out["moves"]["stretch"]["effective_samples_per_s"]
     for r in out["moves"].values():
@@ -111,7 +126,7 @@ def tau(args):
 
 def profile(args):
     x, y, yerr = data()
-    s = EnsembleSampler(args.walkers, 6, x, y, yerr, seed=1, moves=KDEMove() if args.move == "kde" else DEMove())
+    s = EnsembleSampler(args.walkers, 6, x, y, yerr, seed=1, moves={"kde": KDEMove(), "slice": SliceMove(), "de": DEMove()}[args.move])
     s.run_mcmc(_start(args.walkers, 0), args.steps, store=False)
     s.close()
     return {"what": f"profiling run ({args.move})", "walkers": args.walkers, "steps": args.steps}
@@ -125,7 +140,7 @@ def main():
     ap.add_argument("--warm", type=int, default=200)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--tau-steps", type=int, default=6000)
-    ap.add_argument("--move", choices=("de", "kde"), default="de", help="profile: the move of the run")
+    ap.add_argument("--move", choices=("de", "kde", "slice"), default="de", help="profile: the move of the run")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     res = {"rate": rate, "tau": tau, "profile": profile}[args.mode](args)
