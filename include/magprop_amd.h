@@ -512,7 +512,10 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
 /* mp_sampler_run evaluates a whole step in one launch while 3/2 x the walkers (all ensembles) are at most 19/8 x the SIMDs of
  * the device (2 432 evaluations on an MI355X: they fit two wavefronts per SIMD, or nearly): the proposals of the first half and, for every walker of the second half, both proposals it can end up making
  * (its partner of the first half moved or not); a small kernel then takes the decisions in emcee's order.  Same chain, bit
- * for bit, as one launch per half-step (enable = 0; what larger ensembles get anyway).  Default: enabled. */
+ * for bit, as one launch per half-step (enable = 0; what larger ensembles get anyway): the half-step launches of the stretch
+ * move of a sampler whose whole step fits run the kernel build of the whole-step launch (chosen by its 3/2 x walkers blocks),
+ * not the one their own size would choose, so enable = 0 is the check of the default and may be slower than it needs to be.
+ * Default: enabled. */
 int mp_sampler_set_whole_step(mp_sampler *s, int enable);
 /* any of the outputs may be NULL */
 int mp_sampler_get_state(mp_sampler *s, double *pos, double *lnprob, int64_t *n_accepted, int64_t *steps_done);
@@ -664,7 +667,9 @@ int mp_sampler_halfstep_apply(mp_sampler *s, int half, const double *d_rows, dou
  *     mp_sampler_step_apply(s, d_rows, d_chain_row, d_chain_lnp_row, stream)
  * (d_rows[3 * n_slots][R'], row index = block index).  Two launches and one collective per step instead of four and two;
  * a third of the evaluations is discarded, so this pays while a rank's share of the blocks fits its device two wavefronts
- * per SIMD (magprop_amd/distributed.py decides).  Same chain as the half-step protocol and as mp_sampler_run.
+ * per SIMD (magprop_amd/distributed.py decides).  Same chain as the half-step protocol and as mp_sampler_run (bit for bit
+ * while both run the same kernel variant, see DESIGN.md section 7: a launch of the sharded entry points chooses its build by
+ * its own block count).
  */
 int mp_sampler_step_blocks(const mp_sampler *s);
 int mp_sampler_step_row_doubles(const mp_sampler *s);

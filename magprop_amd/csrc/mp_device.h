@@ -277,6 +277,13 @@ inline int kernel_waves(const DevShared &sh, int n) {
 // The same for the kernels of the device-resident sampler, by the size of a WHOLE step of the ensembles (3 x slots of a half:
 // what mp_sampler_run evaluates per launch when that fits) -- for one launch per step and one per half-step alike, so that the
 // two forms run the same arithmetic and their chains stay equal bit for bit; likewise every rank of a walker-sharded run.
+// Team or not is all this decides.  The rest of the build (walker_variant: a team one or two wavefronts per SIMD, a single
+// wavefront 4 or 2 steps per lane) goes by a block count, and the two forms launch different ones, 3 x slots and slots: for
+// n_simd / 12 < slots <= n_simd / 6 and for n_simd / 3 < slots <= 19 n_simd / 24 those choose different builds, whose values
+// differ (at 3 n_simd / 8 slots 557 of 768 stored lnprob differed after one step).  So mp_sampler_run hands launch_stretch the
+// whole step's block count for the stretch move's half-step launches of a sampler whose whole step fits; the walker-sharded
+// entry points choose by the blocks of the call (a rank's share), which is why their promise carries "while both run the same
+// kernel variant".
 // Ensembles of up to n_simd / 6 walkers in all (170 on an MI355X: what emcee is usually run with; the reference's own example
 // has 24, code/synthetic_datasets/synth_mcmc.py): a step 0.091 -> 0.075 ms.
 inline int stretch_waves(const DevShared &sh, int whole_step_blocks) {
@@ -350,7 +357,7 @@ struct RhsArgs {
 int launch_rhs(const DevShared &sh, const RhsArgs &r, void *stream);
 int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream);
 int launch_order(const DevShared &sh, const int32_t *ds_id, int n, int32_t *order, void *stream);   // fills order[n] (see order_kernel)
-int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream);
+int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, int variant_blocks, void *stream);   // variant_blocks: the launch size the build is chosen by
 int launch_stretch_apply(const StretchArgs &g, void *stream);
 int launch_stretch_step(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream);   // blocks [g.slot_lo, + n_blocks) of 3 * n_half * n_ensembles
 int launch_stretch_step_commit(const StretchArgs &g, void *stream);

@@ -837,10 +837,11 @@ int launch_lnprob(const DevShared &sh, const LaunchArgs &a, void *stream) {
 // The build of a stretch launch of n_blocks blocks, one rule for stretch_kernel and stretch_step_kernel (walker_variant): small
 // samplers, by the size of a WHOLE step (stretch_waves), evaluate every proposal on a team of four wavefronts.
 // n_blocks slots of the active half starting at g.slot_lo; the DIFF builds (DE / snooker) and the KDE builds are chosen by the
-// same rule
-int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, void *stream) {
+// same rule.  variant_blocks: the launch size that chooses the build -- n_blocks itself, or the 3 x slots of the whole-step launch
+// whose chain this half-step launch has to reproduce bit for bit (mp_sampler_run with mp_sampler_set_whole_step(0))
+int launch_stretch(const DevShared &sh, const StretchArgs &g, int n_blocks, int variant_blocks, void *stream) {
     if (n_blocks <= 0) return 0;
-    const Variant v = walker_variant(sh, n_blocks, stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4);
+    const Variant v = walker_variant(sh, variant_blocks, stretch_waves(sh, 3 * g.n_half * g.n_ensembles) == 4);
     if (g.move == MP_MOVE_KDE) {
         dispatch([&](auto team, auto roomy, auto lng, auto tempered) {
             using B = Build<team, roomy>;

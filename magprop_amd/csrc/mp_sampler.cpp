@@ -374,8 +374,9 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
 // Enqueue step steps_done + row of mp_sampler_run on the handle's stream: split d_perm, chain row `row` of the device slab when
 // chain is set, move mv (nullptr: the stretch move of mp_sampler_create).  A whole step per launch (stretch_step_kernel and the
 // commit kernel) where `whole` and the move is the stretch move, else two half-step launches (the slice move: of slice_half_kernel,
-// with the tune launch behind them); then the swap sweep when tempered.
-static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_sampler::Move *mv, bool chain, bool whole) {
+// with the tune launch behind them); then the swap sweep when tempered.  fits: a whole step of this sampler fits one launch
+// (`whole` is that and mp_sampler_set_whole_step).
+static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_sampler::Move *mv, bool chain, bool whole, bool fits) {
     Evaluator *ev = s->ev;
     mp::StretchArgs g = stretch_args(s, d_perm, s->steps_done + (uint64_t)row, 0);
     g.chain = chain ? s->d_chain.p : nullptr;
@@ -400,9 +401,14 @@ static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_
         e = mp::launch_stretch_step(ev->sh, g, 3 * g.n_half * g.n_ensembles, ev->stream);
         if (!e) e = mp::launch_stretch_step_commit(g, ev->stream);
     } else {
-        e = mp::launch_stretch(ev->sh, g, g.n_half * g.n_ensembles, ev->stream);
+        // The stretch move by half-step launches of a sampler whose whole step fits (mp_sampler_set_whole_step(0)) is the check of
+        // the whole-step launch: it runs the build that launch runs, chosen by 3 x slots, so that the two chains are one bit for
+        // bit at every size.  Every other half-step launch is judged by its own size.
+        const int n_slots = g.n_half * g.n_ensembles;
+        const int variant_blocks = fits && g.move == MP_MOVE_STRETCH ? 3 * n_slots : n_slots;
+        e = mp::launch_stretch(ev->sh, g, n_slots, variant_blocks, ev->stream);
         g.half = 1;
-        if (!e) e = mp::launch_stretch(ev->sh, g, g.n_half * g.n_ensembles, ev->stream);
+        if (!e) e = mp::launch_stretch(ev->sh, g, n_slots, variant_blocks, ev->stream);
     }
     if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, ev->stream);
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -430,7 +436,8 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
     // that beats two half-step launches (mp_device.h stretch_whole_step_fits); larger ensembles fill the device with one half-step
     // at a time.
     const int n_slots = (s->n_walkers / 2) * s->n_ensembles;
-    const bool whole = s->whole_step && mp::stretch_whole_step_fits(ev->sh, 3 * (long long)n_slots);
+    const bool fits = mp::stretch_whole_step_fits(ev->sh, 3 * (long long)n_slots);
+    const bool whole = s->whole_step && fits;
     if (whole && (rc = s->d_spec.ensure((size_t)3 * n_slots * (size_t)(s->ndim + mp::kSpecExtra)))) return rc;
     if (s->ext_stream_work) {   // sharded half-steps on a caller's stream may still be updating the state
         HIP_TRY(hipDeviceSynchronize());
@@ -452,7 +459,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
                                    (size_t)(sub_end - sub) * nt * sizeof(int32_t), hipMemcpyHostToDevice, ev->stream));
             for (int st = sub; st < sub_end; ++st) {
                 const mp_sampler::Move *mv = s->moves.empty() ? nullptr : &s->moves[(size_t)step_move[st - sub]];
-                if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, slab, whole))) return rc;
+                if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, slab, whole, fits))) return rc;
             }
         }
         if (monitor && (rc = s->acf->feed(s->d_chain.p, chunk, ev->stream))) return rc;
@@ -626,7 +633,7 @@ int mp_sampler_halfstep_shard(mp_sampler *s, int half, int slot_lo, int slot_hi,
     mp::StretchArgs g = stretch_args(s, c.d_perm, s->steps_done, half);
     g.upd = d_rows;
     g.slot_lo = slot_lo;
-    const int e = mp::launch_stretch(s->ev->sh, g, slot_hi - slot_lo, stream);
+    const int e = mp::launch_stretch(s->ev->sh, g, slot_hi - slot_lo, slot_hi - slot_lo, stream);   // (a rank's share chooses its own build)
     if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     return MP_OK;
 }

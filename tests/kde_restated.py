@@ -3,7 +3,10 @@ sums and the proposal.  Test infrastructure: the step loop of tests/sampler_rest
 mixture with the moves of tests/moves_restated.py; the GPU tests compare the device chains with that loop on the
 unit-Gaussian target, the CPU tests check it against scipy.stats.gaussian_kde and that it samples a correlated Gaussian.
 The proposal arithmetic is unfused float64 in the kernel's order; the kernel's sums over the other half run in an order of
-their own, and log / exp / sqrt / cos / sin are not numpy's, so the device agrees with this to rounding, not bit for bit."""
+their own, and log / exp / sqrt / cos / sin are not numpy's, so the device agrees with this to rounding, not bit for bit --
+unless the sums are taken in the kernel's order (kernel_sum, fit(waves=)) and the normals through the device's functions
+(normals_batch), which tests/test_gpu_sampler_posterior.py does: the proposal is then the kernel's bit for bit (the Hastings
+term, which only decides, stays restated to rounding)."""
 import math
 
 import numpy as np
@@ -25,13 +28,39 @@ def bandwidth(p0, n_comp, ndim):
     return float(np.power(n, -1.0 / (ndim + 4)))
 
 
-def fit(x, f):
+def kernel_sum(terms, waves):
+    """The sum of terms[n, ...] over n in the order of kde_proposal on a workgroup of `waves` wavefronts: thread t adds the
+    terms t, t + 64 waves, ... in order, a butterfly over the 64 lanes of a wavefront (wave_sum: xor 32, 16, .. 1), then the
+    wavefronts' sums in order."""
+    nt, shape = 64 * waves, terms.shape[1:]
+    acc = np.zeros((nt,) + shape)
+    for r in range(0, len(terms), nt):
+        chunk = terms[r:r + nt]
+        acc[:len(chunk)] = acc[:len(chunk)] + chunk
+    acc = acc.reshape((waves, 64) + shape)
+    lanes = np.arange(64)
+    for dist in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, lanes ^ dist]
+    s = np.zeros(shape)
+    for w in range(waves):
+        s = s + acc[w, 0]
+    return s
+
+
+def fit(x, f, waves=0, sqrt=np.sqrt):
     """(Sigma = f^2 S, its Cholesky factor L or None where S is not positive definite) of the points x[n_comp, ndim]: the
-    mean and the centred products summed in slot order, S = sums / (n_comp - 1), L by rows."""
+    mean and the centred products summed in slot order, S = sums / (n_comp - 1), L by rows.  waves > 0: the sums in the
+    kernel's own order on a workgroup of that many wavefronts (kernel_sum) and the pivots through `sqrt` (the device's), which
+    makes L the kernel's bit for bit."""
     n, d = x.shape
-    mu = np.add.accumulate(x, axis=0)[-1] / n
-    e = x - mu
-    prods = np.add.accumulate(e[:, :, None] * e[:, None, :], axis=0)[-1]
+    if waves:
+        mu = kernel_sum(x, waves) / n
+        e = x - mu
+        prods = kernel_sum(e[:, :, None] * e[:, None, :], waves)
+    else:
+        mu = np.add.accumulate(x, axis=0)[-1] / n
+        e = x - mu
+        prods = np.add.accumulate(e[:, :, None] * e[:, None, :], axis=0)[-1]
     sigma = (f * f) * (prods / (n - 1.0))
     L = np.zeros((d, d))
     ok = True
@@ -43,7 +72,7 @@ def fit(x, f):
             if a == b:
                 ok = ok and 0.0 < s < math.inf
                 with np.errstate(invalid="ignore"):
-                    L[a, a] = np.sqrt(s)
+                    L[a, a] = sqrt(s)
             else:
                 with np.errstate(invalid="ignore", divide="ignore"):
                     L[a, b] = s / L[b, b]
@@ -79,9 +108,25 @@ def normals(seed, step, half, k, d):
     return n[:d]
 
 
-def propose_kde(pos, k, comp, seed, step, half, L, zero_hastings=False):
+def normals_batch(seed, step, half, ks, d, libm):
+    """normals() of the walkers ks, [len(ks), d], with log, sqrt, cos and sin taken from libm (the device's: bit for bit the
+    kernel's normals), one call of each for the whole batch."""
+    pairs = (d + 1) // 2
+    ua, ub = np.empty((len(ks), pairs)), np.empty((len(ks), pairs))
+    for i, k in enumerate(ks):
+        for p in range(pairs):
+            s = philox4x32_10(seed & M32, seed >> 32, step, half, int(k), KDE_CTR + 1 + p)
+            ua[i, p], ub[i, p] = u01(s[0], s[1]), u01(s[2], s[3])
+    rad = libm.sqrt(-2.0 * libm.log(1.0 - ua))
+    ang = TWO_PI * ub
+    n = np.empty((len(ks), 2 * pairs))
+    n[:, 0::2], n[:, 1::2] = rad * libm.cos(ang), rad * libm.sin(ang)
+    return n[:, :d]
+
+
+def propose_kde(pos, k, comp, seed, step, half, L, zero_hastings=False, nrm=None):
     """(proposal, Hastings term, ln u) of walker k; comp = global indices of the other half in split order, L = the factor
-    of fit() over them (None: NaN proposal)."""
+    of fit() over them (None: NaN proposal); nrm: the walker's normals where they come from normals_batch."""
     d = pos.shape[1]
     r = philox4x32_10(seed & M32, seed >> 32, step, half, k, KDE_CTR)
     with np.errstate(divide="ignore"):
@@ -89,7 +134,7 @@ def propose_kde(pos, k, comp, seed, step, half, L, zero_hastings=False):
     if L is None:
         return np.full(d, np.nan), np.nan, logu
     xc = pos[comp[pick(u01(r[0], r[1]), len(comp))]]
-    n = normals(seed, step, half, k, d)
+    n = normals(seed, step, half, k, d) if nrm is None else nrm
     q = np.empty(d)
     for a in range(d):
         s = 0.0

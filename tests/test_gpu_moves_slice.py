@@ -3,8 +3,6 @@ chains against the numpy restatement (tests/slice_move_restated.py) bit for bit 
 n_accepted, the mu of every chunk end and the four counters -- split runs, the real posterior on every kernel build against
 mp_lnprob_batch calls of the launch's size, tempering, a mixture, the monitors, Humped from the reference's starting ball, and
 the refusals."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -24,18 +22,10 @@ FAILS = np.array([1.8171068, 3.68147895, -2.61786801, 1.99840102, -0.33083576, 2
 
 
 class RawSlice(RawSampler):
-    """RawSampler with the dataset of every ensemble (ds; None: dataset 0) and the entry points of the slice move."""
+    """RawSampler with the entry points of the slice move."""
 
     def __init__(self, n_walkers, n_ens, ndim, seed, target=1, handle=None, ds=None):
-        if ds is None:
-            super().__init__(n_walkers, n_ens, ndim, seed, target=target, handle=handle)
-            return
-        from magprop_amd import _capi
-        self.cap, self.L, self.h, self.own_handle = _capi, _capi.lib(), handle, False
-        self.nw, self.ne, self.ndim, self.nt = n_walkers, n_ens, ndim, n_walkers * n_ens
-        ids = np.asarray(ds, dtype=np.int32)
-        self.sp = self.L.mp_sampler_create(handle._h, n_walkers, n_ens, ndim, ip(ids), C.c_uint64(seed), C.c_double(2.0), target)
-        assert self.sp, _capi.last_error()
+        super().__init__(n_walkers, n_ens, ndim, seed, target=target, handle=handle, ds=ds)
 
     def set_limits(self, limits, check=True):
         rc = self.L.mp_sampler_set_slice_limits(self.sp, int(limits[0]), int(limits[1]))
@@ -48,19 +38,6 @@ class RawSlice(RawSampler):
         out.update({k: np.empty(self.ne, dtype=np.int64) for k in COUNTERS})
         self._ok(self.L.mp_sampler_get_slice(self.sp, dp(out["mu"]), *(lp(out[k]) for k in COUNTERS)))
         return out
-
-    def state(self):
-        pos, lnp, acc = np.empty((self.nt, self.ndim)), np.empty(self.nt), np.empty(self.nt, dtype=np.int64)
-        self._ok(self.L.mp_sampler_get_state(self.sp, dp(pos), dp(lnp), lp(acc), None))
-        return pos, lnp, acc
-
-    def bad(self):
-        n_bad, n_logged = C.c_int64(0), C.c_int64(0)
-        assert self.L.mp_sampler_get_bad(self.sp, 0, None, 0, C.byref(n_bad), C.byref(n_logged)) >= 0
-        rows = np.empty((n_logged.value, self.ndim))
-        if n_logged.value:
-            assert self.L.mp_sampler_get_bad(self.sp, 0, dp(rows), n_logged.value, None, None) == n_logged.value
-        return n_bad.value, rows
 
 
 def device_run(n_walkers, n_ens, ndim, seed, table, limits, pos, runs, betas=None, autocorr=0):
