@@ -597,7 +597,8 @@ int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted);
  *                    chain is a plain Markov chain.
  * Philox counters c3 in use: 0, 1 (stretch), 2, 3 (DE, snooker), 0x4B00 .. 0x4B05 (KDE), 0x5117 (splits), 0x30FE (move of a
  * step), 0 with half = 2 (swaps), 0x51C00000 + c, c = 0 .. 2 + max_shrink (slice move); the optimizer 0xDE00 .. and 0xDEFF, the
- * nested sampler 0x4E000000 + j (random walk) and 0x4E400000 + 0x100 s + c (slice mode).
+ * nested sampler 0x4E000000 + j (random walk) and 0x4E400000 + 0x100 s + c (slice mode), the SMC sampler 0x534D0000 + c, c = 0
+ * (a stage's resampling offset) .. 2 walks (its moves).
  * Mixtures: one move per step for the whole sampler.  With n_moves > 1, step s draws r = Philox(seed; s, 3, 0, 0x30FE) and takes
  * the first move m with u01(r0, r1) C_last < C_m, C the cumulative weights (summed in order, double): the move of a step depends
  * on (seed, s, table) only, so split runs give the chain of one run.  DE, snooker, KDE and slice steps run two half-step launches (plus the
@@ -952,6 +953,82 @@ int mp_simplex_run(void *s, int max_iterations, int *n_running);
 int mp_simplex_get_state(void *s, double *sim, double *lnprob, int32_t *status, int32_t *nit, int32_t *stopped, int64_t *nfev,
                          int64_t *outcomes);
 int mp_simplex_destroy(void *s);
+
+/*
+ * Tempered sequential Monte Carlo (ABI 5, additive): SMC over the path prior x L^beta, beta from 0 to 1 (Del Moral, Doucet &
+ * Jasra 2006), every next beta chosen from the particles' own weights, so that no temperature ladder is given; one stage and one
+ * move launch per stage.  The run ends with ln Z and N equally weighted posterior samples.  n_runs independent runs (1 <= n_runs
+ * <= MP_MAX_DATASETS) of N = n_particles each (MP_SMC_MIN_PARTICLES <= N <= MP_SMC_MAX_PARTICLES); run r runs on dataset
+ * run_ds_id[r] (NULL: dataset 0 for all; several runs may share a dataset) and differs from the others by r in the Philox key
+ * alone.  Particle j of run r is row r * N + j.  The prior is uniform over the box lower[ndim] < upper[ndim] (finite; sampler
+ * coordinates).  target: 0 the log-posterior of the handle (lnl), 1 the isotropic unit Gaussian -0.5 sum x^2, 2 the same on
+ * terraces along x_0 (1 and 2: tests).  A NaN lnl counts (and is stored) as -inf.  A run keeps x[N][ndim], the untempered lnl[N],
+ * beta, ln Z, its stage count and a status (MP_SMC_RUNNING, _DONE, _FAILED, _STAGE_LIMIT); two particle buffers alternate from
+ * stage to stage: a stage reads one and its moves write the other.
+ * Start (mp_smc_set_particles): the caller's particles (inside the box) are evaluated as they are; beta = 0, ln Z = 0.
+ * Stage t (t = the run's own stage count, from 0) of run r, one workgroup:
+ *   M = the largest finite lnl, n_fin = the number of finite lnl; n_fin = 0: the run ends with status MP_SMC_FAILED;
+ *   w_i(d) = exp(d (lnl_i - M)) (the product rounded on its own), 0 where lnl_i is not finite;
+ *   ESS(d) = (sum w)^2 / sum w^2, the square and the quotient rounded on their own; the sums: thread k of 256 adds its particles
+ *   k, k + 256, ... in that order, the threads' sums combine in the order of mp_wg.h (xor butterfly over 32, 16, .. 1 inside a
+ *   wavefront, then the four wavefronts in order);
+ *   the target is ess * n_fin; if ESS(1 - beta) >= target then d = 1 - beta and the new beta is exactly 1.0; otherwise bisect
+ *   with lo = 0, hi = 1 - beta, mid = 0.5 (lo + hi): ESS(mid) >= target moves lo to mid, else hi; stop when mid equals lo or hi,
+ *   or after 128 halvings; d = lo if lo > 0, else hi; the new beta is beta + d;
+ *   ln Z += d M + log(sum w / N): N counts every particle, failed ones included, so that the first stage carries ln f_valid;
+ *   integer weights u_i = rint((2^31 w_i) / max w) (mp_band_weight_units' idea: their sums are exact and order-free),
+ *   U = sum u_i, C_i = u_0 + ... + u_i;
+ *   systematic resampling in integers: s = floor(u01(r0, r1) * U), one separately rounded product, from Philox4x32-10 keyed
+ *   (seed; t, r, 0, 0x534D0000); P_j = floor((j U + s) / N) in 64 bits (j U < 2^59); the ancestor anc[j] of slot j is the least
+ *   i with C_i > P_j.  A particle of zero units, every failed one among them, is nobody's ancestor.
+ *   The stage's row of the log is (beta, d, ESS(d), ln Z); a run keeps MP_SMC_MAX_STAGES rows, and one that would need another
+ *   ends with status MP_SMC_STAGE_LIMIT.
+ * Moves of stage t, one workgroup per slot j: the slot starts at x = particle anc[j] of the stage's buffer (its lnl and status
+ * come with it) and takes `walks` Metropolis steps against prior x L^beta, beta the stage's new one.  Step s = 0 .. walks-1
+ * draws u from Philox4x32-10 keyed (seed; t, r, j, 0x534D0000 + 2 s + 1) and v from (..., 0x534D0000 + 2 s + 2):
+ *   partners c1 = pick(u01(u0, u1), N), c2 = distinct from c1 by u01(u2, u3) (mp_sampler_set_moves' rule);
+ *   gamma = g0 (1 + s3 (2 u01(v0, v1) - 1)), s3 = sigma sqrt(3), g0 = 2.38 / sqrt(2 ndim) when given as <= 0;
+ *   q_d = x_d + gamma (y_d - z_d), y = particle anc[c1], z = particle anc[c2] of the stage's buffer (unfused): the differences
+ *   are drawn over the resampled population;
+ *   a q outside the box is rejected without an evaluation; otherwise q is accepted iff
+ *   beta lnl(q) - beta lnl(x) > log(u01(v2, v3)), the two products rounded on their own.
+ *   The end point, its lnl, status and accepted-step count go to slot j of the other buffer.  The resampled population is fixed
+ *   during the launch, so the proposal is symmetric and does not depend on the moving particle's path: this is Metropolis for
+ *   prior x L^beta.  A run whose beta reached 1 makes the moves of that stage and has status MP_SMC_DONE; a stopped run's
+ *   workgroups return at once.
+ * Kernel build: the rule of mp_lnprob_batch for a batch of n_runs * N walkers, so that (shipped build) every evaluation is bit for
+ * bit what mp_lnprob_batch returns for that row on dataset run_ds_id[r] in a batch of the launch's size.
+ * mp_smc_create: MP_EINVAL on bad sizes (N, n_runs, ndim < 6 for target 0, walks outside 1 .. MP_SMC_MAX_WALKS), ess outside
+ * (0, 1), g0 not finite, sigma outside [0, 1/sqrt(3)), an empty or non-finite box, unset datasets; MP_ESTATE on multi-device
+ * handles and (target 0) handles with cfg.dipole_torque = 1.  mp_smc_run runs up to max_stages more stages of every run still
+ * running, enqueued without a wait in between but for one look at the status per chunk; the state does not depend on how a run is
+ * split into calls; *n_running (optional) = runs still running.  mp_smc_get_state: any output may be NULL; x[n_runs * N][ndim],
+ * lnl, status, acc (accepted steps of the slot's last move) [n_runs * N]; per run beta, lnz, nstage, run_status, ncall
+ * (evaluations, those of mp_smc_set_particles included), nacc (accepted steps), nfail (evaluations whose model failed).
+ * mp_smc_get_stages(run): *n_rows = the run's stages so far; the first min(max_rows, *n_rows) rows of the log go to beta[], d[],
+ * ess[], lnz[], accept[] (accepted steps of the stage's moves / (N walks)) and ncall[] (their evaluations), each may be NULL.
+ * mp_smc_get_ancestors: anc[n_runs * N] of every run's last stage (a diagnostic of the genealogy).  The getters return MP_ESTATE
+ * before mp_smc_set_particles.  The object behind the void pointers is an mp_smc.
+ */
+#define MP_SMC_MIN_PARTICLES 4
+#define MP_SMC_MAX_PARTICLES 16384
+#define MP_SMC_MAX_WALKS 4096
+#define MP_SMC_MAX_STAGES 1024
+#define MP_SMC_RUNNING 0
+#define MP_SMC_DONE 1
+#define MP_SMC_FAILED 2
+#define MP_SMC_STAGE_LIMIT 3
+typedef struct mp_smc mp_smc;
+void *mp_smc_create(mp_handle *h, int n_particles, int n_runs, int ndim, const int32_t *run_ds_id, uint64_t seed,
+                    const double *lower, const double *upper, double ess, int walks, double g0, double sigma, int target);
+int mp_smc_set_particles(void *s, const double *particles);
+int mp_smc_run(void *s, int max_stages, int *n_running);
+int mp_smc_get_state(void *s, double *x, double *lnl, int32_t *status, int32_t *acc, double *beta, double *lnz, int32_t *nstage,
+                     int32_t *run_status, int64_t *ncall, int64_t *nacc, int64_t *nfail);
+int mp_smc_get_stages(void *s, int run, int max_rows, double *beta, double *d, double *ess, double *lnz, double *accept,
+                      int64_t *ncall, int *n_rows);
+int mp_smc_get_ancestors(void *s, int32_t *anc);
+int mp_smc_destroy(void *s);
 
 /* wait for everything enqueued on the handle's own stream */
 int mp_synchronize(mp_handle *h);

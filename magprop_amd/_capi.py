@@ -29,7 +29,9 @@ FLOW_CURVES = ("Rm", "Rc", "Rlc", "fastness", "Mdot_prop", "Mdot_acc", "Mdot_fb"
 DE_BEST1BIN, DE_RAND1BIN = 0, 1                               # include/magprop_amd.h MP_DE_*
 NEST_MIN_LIVE, NEST_MAX_LIVE, NEST_MAX_WALKS = 16, 4096, 4096  # include/magprop_amd.h MP_NEST_*
 NEST_MAX_SLICES, NEST_MAX_STEPS_OUT, NEST_MAX_SHRINK = 4096, 4096, 254
-MOVE_SLICE, SLICE_MAX_SHRINK = 4, 252                          # include/magprop_amd.h MP_MOVE_SLICE, MP_SLICE_MAX_SHRINK
+SMC_MIN_PARTICLES, SMC_MAX_PARTICLES, SMC_MAX_WALKS, SMC_MAX_STAGES = 4, 16384, 4096, 1024   # include/magprop_amd.h MP_SMC_*
+SMC_RUNNING, SMC_DONE, SMC_FAILED, SMC_STAGE_LIMIT = 0, 1, 2, 3
+MOVE_SLICE, SLICE_MAX_SHRINK = 4, 252                         # include/magprop_amd.h MP_MOVE_SLICE, MP_SLICE_MAX_SHRINK
 ACF_MAX_LAG, ACF_MAX_BYTES = 4096, 8 << 30                   # include/magprop_amd.h MP_ACF_*
 POST_MAX_BINS, POST_MAX_BINS2, POST_MAX_BYTES = 4096, 128, 1 << 30   # include/magprop_amd.h MP_POST_*
 
@@ -130,6 +132,13 @@ SIGNATURES = {
     "mp_simplex_run": (_i, [_vp, _i, _ip]),
     "mp_simplex_get_state": (_i, [_vp, _dp, _dp, _ip, _ip, _ip, _i64p, _i64p]),
     "mp_simplex_destroy": (_i, [_vp]),
+    "mp_smc_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _dp, _dp, _d, _i, _d, _d, _i]),
+    "mp_smc_set_particles": (_i, [_vp, _dp]),
+    "mp_smc_run": (_i, [_vp, _i, _ip]),
+    "mp_smc_get_state": (_i, [_vp, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _ip, _i64p, _i64p, _i64p]),
+    "mp_smc_get_stages": (_i, [_vp, _i, _i, _dp, _dp, _dp, _dp, _dp, _i64p, _ip]),
+    "mp_smc_get_ancestors": (_i, [_vp, _ip]),
+    "mp_smc_destroy": (_i, [_vp]),
     "mp_synchronize": (_i, [_vp]),
     "mp_device": (_i, [_vp]),
     "mp_stream": (_vp, [_vp]),

@@ -1,5 +1,5 @@
 // mp_host.h — what the host sources of the C ABI share (mp_capi.cpp, mp_summaries.cpp, mp_sampler.cpp, mp_monitor.cpp, mp_optimizer.cpp,
-// mp_nested.cpp, mp_simplex.cpp).
+// mp_nested.cpp, mp_simplex.cpp, mp_smc.cpp).
 //
 // Internal: not installed, never seen by a kernel source.  Error reporting, owners of device memory, pinned memory and events,
 // the two types behind the ABI's handle -- Evaluator, everything that lives on ONE device, and mp_handle, the dealer that owns
