@@ -31,8 +31,18 @@ def digest(t, x):
     """(g, dx, idt) of observation times x (ascending) on the grid t, as mp_set_dataset brackets them: t[g] <= x < t[g + 1],
     the last grid point in the last interval."""
     t, x = np.asarray(t, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    if not np.all((x >= t[0]) & (x <= t[-1])):              # (NaN too) interp1d(bounds_error=True): mp_set_dataset refuses these
+        raise ValueError("A value in x_new is outside the interpolation range.")
     g = np.clip(np.searchsorted(t, x, side="right") - 1, 0, t.size - 2).astype(np.int32)
     return g, x - t[g], 1.0 / (t[g + 1] - t[g])
+
+
+def tile_ptr(g, n_tiles, bucket=64):
+    """tile_ptr[n_tiles + 1] of mp_set_dataset: the observations of the buckets of `bucket` grid intervals before bucket k"""
+    counts = np.zeros(int(n_tiles) + 1, dtype=np.int32)
+    for gj in np.asarray(g):
+        counts[int(gj) // bucket + 1] += 1
+    return np.cumsum(counts, dtype=np.int32)
 
 
 def cells(ltot, status, g, dx, idt, y, yerr):
