@@ -802,8 +802,9 @@ int mp_sampler_get_posterior_best(mp_sampler *s, int ensemble, double *x, double
  * Kernel build: the rule of mp_lnprob_batch for a batch of n_pops * popsize walkers, so that (shipped build) a member's lnprob is
  * bit for bit what mp_lnprob_batch returns for the same row in a batch of that size.
  * mp_optimizer_create: MP_EINVAL on bad sizes, strategy, f_lo > f_hi (or outside [0, 2)), cr outside [0, 1], tol / atol not
- * finite and >= 0, an empty or non-finite box, unset datasets; MP_ESTATE on multi-device handles and (target 0) handles with
- * cfg.dipole_torque = 1.  mp_optimizer_set_population(pop[n_pops * popsize][ndim]) evaluates it (generation 0: nit = 0, nfev =
+ * finite and >= 0, an empty or non-finite box; MP_ESTATE on multi-device handles and (target 0) handles with
+ * cfg.dipole_torque = 1 or a population on an unset dataset.
+ * mp_optimizer_set_population(pop[n_pops * popsize][ndim]) evaluates it (generation 0: nit = 0, nfev =
  * popsize) and clears the converged flags.  mp_optimizer_run runs up to max_generations more generations of every population
  * that has not converged, in chunks of launches with one read-back of the flags per chunk; *n_running (optional) = populations
  * still running.  mp_optimizer_get_state: any output may be NULL; pop[n_total][ndim], lnprob[n_total], status[n_total],
@@ -869,8 +870,8 @@ int mp_optimizer_destroy(mp_optimizer *o);
  * that (shipped build) every evaluation of a walk, random-walk step or slice point, and every live point's first lnL and status are
  * bit for bit what mp_lnprob_batch returns for that row on dataset run_ds_id[r] in a batch of the launch's size.
  * mp_nested_create: MP_EINVAL on bad sizes (ndim < 6 for target 0, walks outside 1 .. MP_NEST_MAX_WALKS), g0 > 0 not finite,
- * sigma outside [0, 1/sqrt(3)), dlogz not finite and > 0, an empty or non-finite box, unset datasets; MP_ESTATE on
- * multi-device handles and (target 0) handles with cfg.dipole_torque = 1.  mp_nested_set_live(live[n_runs * nlive][ndim], inside
+ * sigma outside [0, 1/sqrt(3)), dlogz not finite and > 0, an empty or non-finite box; MP_ESTATE on multi-device handles and
+ * (target 0) handles with cfg.dipole_torque = 1 or a run on an unset dataset.  mp_nested_set_live(live[n_runs * nlive][ndim], inside
  * the box) evaluates the live set and resets every run (no dead rows, ln X = 0, ln Z = -inf, counters 0).  mp_nested_run runs up
  * to max_iterations more iterations of every run not yet stopped; *n_running (optional) = runs still running.
  * mp_nested_get_dead(run): *n_rows = the run's dead rows so far; the first min(max_rows, *n_rows) are copied into pars[][ndim],
@@ -935,8 +936,8 @@ int mp_nested_destroy(mp_nested *ns);
  * Kernel build: the rule of mp_lnprob_batch for a batch of n_simplex * (N + 4) walkers, the initial evaluation included, so that
  * (shipped build) every stored lnprob is bit for bit what mp_lnprob_batch returns for the same row in a batch of that size.
  * mp_simplex_create: MP_EINVAL on bad sizes (ndim outside 1 .. MP_MAX_NDIM, < 6 for target 0), rho, chi, psi or sigma not finite
- * and > 0, psi or sigma >= 1, xatol / fatol not finite and >= 0, an empty or non-finite box, unset datasets; MP_ESTATE on
- * multi-device handles and (target 0) handles with cfg.dipole_torque = 1.  mp_simplex_set_vertices(sim[n_simplex][N + 1][N])
+ * and > 0, psi or sigma >= 1, xatol / fatol not finite and >= 0, an empty or non-finite box; MP_ESTATE on multi-device handles
+ * and (target 0) handles with cfg.dipole_torque = 1 or a simplex on an unset dataset.  mp_simplex_set_vertices(sim[n_simplex][N + 1][N])
  * refuses non-finite coordinates (MP_EINVAL), applies scipy's rule to vertices outside the box (a coordinate above upper becomes
  * 2 upper - it, then everything is clipped), evaluates the vertices and sorts them (nit = 1 as scipy counts, nfev = N + 1) and
  * clears the flags and counters.  mp_simplex_run runs up to max_iterations more iterations of every simplex that has not
@@ -999,8 +1000,8 @@ int mp_simplex_destroy(void *s);
  * Kernel build: the rule of mp_lnprob_batch for a batch of n_runs * N walkers, so that (shipped build) every evaluation is bit for
  * bit what mp_lnprob_batch returns for that row on dataset run_ds_id[r] in a batch of the launch's size.
  * mp_smc_create: MP_EINVAL on bad sizes (N, n_runs, ndim < 6 for target 0, walks outside 1 .. MP_SMC_MAX_WALKS), ess outside
- * (0, 1), g0 not finite, sigma outside [0, 1/sqrt(3)), an empty or non-finite box, unset datasets; MP_ESTATE on multi-device
- * handles and (target 0) handles with cfg.dipole_torque = 1.  mp_smc_run runs up to max_stages more stages of every run still
+ * (0, 1), g0 not finite, sigma outside [0, 1/sqrt(3)), an empty or non-finite box; MP_ESTATE on multi-device handles and (target
+ * 0) handles with cfg.dipole_torque = 1 or a run on an unset dataset.  mp_smc_run runs up to max_stages more stages of every run still
  * running, enqueued without a wait in between but for one look at the status per chunk; the state does not depend on how a run is
  * split into calls; *n_running (optional) = runs still running.  mp_smc_get_state: any output may be NULL; x[n_runs * N][ndim],
  * lnl, status, acc (accepted steps of the slot's last move) [n_runs * N]; per run beta, lnz, nstage, run_status, ncall

@@ -393,8 +393,8 @@ class _Owner:
 
 
 class Driver(_Owner):
-    """Owns one device-resident driver object (mp_sampler, mp_optimizer, mp_nested, mp_simplex) of `handle`: `name`_create(handle,
-    *args), freed once by `name`_destroy.  Passed to the ABI as its pointer (NULL once closed); holds the handle, so the
+    """Owns one device-resident driver object (mp_sampler, mp_optimizer, mp_nested, mp_simplex, mp_smc) of `handle`:
+    `name`_create(handle, *args), freed once by `name`_destroy.  Passed to the ABI as its pointer (NULL once closed); holds the handle, so the
     handle outlives it."""
 
     def __init__(self, name, handle, *args):

@@ -2,11 +2,11 @@
 //
 // Plain HIP runtime only (no torch, no hipBLAS).  First the per-device evaluator (mp_host.h Evaluator): device buffers,
 // one stream, the dataset arena, thin launch wrappers, its constants and tables, evaluator_create / evaluator_destroy, and
-// the helpers that the resident drivers share (the drivers themselves: mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp; the
-// summaries of model curves: mp_summaries.cpp).  Then the mp_* entry points on the handle, a dealer over one evaluator per
-// device -- datasets and prior, the batch entries, mp_rhs_batch and the introspection getters: each has ONE code path, which
-// loops over the evaluators, deals a batch out among them, or runs on the first; mp_create's handle is the case of one
-// evaluator.  The host-side digestion of observed light curves into the tile-bucketed layout the kernel reads happens
+// the helpers that the resident drivers share (the drivers themselves: mp_sampler.cpp, mp_optimizer.cpp, mp_nested.cpp,
+// mp_simplex.cpp, mp_smc.cpp; the summaries of model curves: mp_summaries.cpp).  Then the mp_* entry points on the handle, a
+// dealer over one evaluator per device -- datasets and prior, the batch entries, mp_rhs_batch and the introspection getters:
+// each has ONE code path, which loops over the evaluators, deals a batch out among them, or runs on the first; mp_create's
+// handle is the case of one evaluator.  The host-side digestion of observed light curves into the tile-bucketed layout the kernel reads happens
 // once per mp_set_dataset.  There is NO CPU fallback: without a HIP device mp_create() fails.
 #include <cstdarg>
 #include <cstdio>
@@ -43,11 +43,11 @@ int launch_lnprob_ordered(Evaluator *ev, const mp::LaunchArgs &a_in, hipStream_t
         if (!ev->order_done[slot].e) HIP_TRY(hipEventCreateWithFlags(&ev->order_done[slot].e, hipEventDisableTiming));
         else HIP_TRY(hipStreamWaitEvent(st, ev->order_done[slot].e, 0));
         const int eo = mp::launch_order(ev->sh, a.ds_id, a.n, ev->order[slot].p, (void *)st);
-        if (eo) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)eo));
+        if (eo) return launched(eo);
         a.order = ev->order[slot].p;
     }
     const int e = mp::launch_lnprob(ev->sh, a, (void *)st);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e) return launched(e);
     if (slot >= 0) HIP_TRY(hipEventRecord(ev->order_done[slot].e, st));
     return MP_OK;
 }
@@ -121,14 +121,25 @@ static int upload_dataset(Evaluator *ev, int d, bool replaced) {
 }
 
 // ---------------------------------------------------------------- what the resident drivers share
-// (the ensemble sampler, the differential-evolution optimizer and the nested sampler: mp_sampler_*, mp_optimizer_*, mp_nested_*)
+// (the ensemble sampler, the differential-evolution optimizer, the nested sampler, the simplex search and the SMC sampler:
+// mp_sampler_*, mp_optimizer_*, mp_nested_*, mp_simplex_*, mp_smc_*)
 // (declared in mp_host.h, next to the template check_create)
 
-// the bounds box of the optimizer and the nested sampler: finite, lower < upper in every coordinate
+// the bounds box of a driver: finite, lower < upper in every coordinate
 int check_box(const char *fn, int ndim, const double *lower, const double *upper) {
     for (int d = 0; d < ndim; ++d)
         if (!(std::isfinite(lower[d]) && std::isfinite(upper[d]) && lower[d] < upper[d]))
             return fail(MP_EINVAL, "%s: bounds of coordinate %d are empty or not finite", fn, d);
+    return MP_OK;
+}
+
+// every one of the n rows of ndim coordinates lies inside the box (a NaN does not); `what` names the function and the rows
+int check_inside(const char *what, const double *rows, size_t n, int ndim, const double *lower, const double *upper) {
+    for (size_t i = 0; i < n; ++i)
+        for (int d = 0; d < ndim; ++d) {
+            const double v = rows[i * ndim + d];
+            if (!(v >= lower[d] && v <= upper[d])) return fail(MP_EINVAL, "%s %zu lies outside the box", what, i);
+        }
     return MP_OK;
 }
 
@@ -140,12 +151,14 @@ int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int rows) {
     return MP_OK;
 }
 
-// *running = the groups whose flag (d_flags[n], read back behind the work on the handle's stream) is not 1 (converged, stopped)
+// *running = the groups whose flag (d_flags[n], read back behind the work on the handle's stream) is 0.  Every driver's flag is
+// 0 while its group runs and non-zero once it has ended: converged and stopped become 1, an SMC run's status MP_SMC_DONE,
+// MP_SMC_FAILED or MP_SMC_STAGE_LIMIT (1 to 3).
 int groups_running(Evaluator *ev, const int32_t *d_flags, int n, int *running) {
     std::vector<int32_t> f((size_t)n);
     HIP_TRY(hipMemcpyAsync(f.data(), d_flags, f.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ev->stream));
     HIP_TRY(hipStreamSynchronize(ev->stream));
-    *running = n - (int)std::count(f.begin(), f.end(), 1);
+    *running = (int)std::count(f.begin(), f.end(), 0);
     return MP_OK;
 }
 
@@ -648,7 +661,7 @@ int mp_rhs_batch(mp_handle *h, const double *pars, int ndim, const double *t, co
     r.n = n;
     r.ndim = ndim;
     const int e = mp::launch_rhs(ev->sh, r, st);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e) return launched(e);
     HIP_TRY(hipMemcpyAsync(dydt, r.dydt, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
     if (lam) HIP_TRY(hipMemcpyAsync(lam, r.lam, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));

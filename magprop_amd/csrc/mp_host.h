@@ -3,9 +3,10 @@
 //
 // Internal: not installed, never seen by a kernel source.  Error reporting, owners of device memory, pinned memory and events,
 // the two types behind the ABI's handle -- Evaluator, everything that lives on ONE device, and mp_handle, the dealer that owns
-// one evaluator per device and the lock -- and the helpers of mp_capi.cpp that the summaries and the resident drivers call.  Each driver's own
-// struct stays in its source file; the sampler's two chain monitors are a unit of their own (mp_monitor.h), which the probe
-// libraries of their kernels link as well.
+// one evaluator per device and the lock -- the helpers of mp_capi.cpp that the summaries and the resident drivers call, and the
+// skeleton that the optimizer, the nested sampler, the simplex search and the SMC sampler stand on (Resident and what follows it).
+// Each driver's own struct stays in its source file; the sampler's two chain monitors are a unit of their own (mp_monitor.h),
+// which the probe libraries of their kernels link as well.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,11 @@ int fail(int code, const char *fmt, ...);
         hipError_t e_ = (expr);                                                                    \
         if (e_ != hipSuccess) return fail(MP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// what a launcher returned (a hipError_t as int), as the entry point's return code
+inline int launched(int e) {
+    return e ? fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e)) : MP_OK;
+}
 
 struct DeviceScope {  // make an evaluator's device current for the duration of a call
     int prev = -1;
@@ -125,6 +131,14 @@ int read_back(T *dst, const T *src, size_t n, Rest... rest) {
     return read_back(rest...);
 }
 
+// The resets of a driver's set function, enqueued on st: zero_async(st, p, n, p2, n2, ...) clears n elements of p for every pair.
+inline int zero_async(hipStream_t) { return MP_OK; }
+template <typename T, typename... Rest>
+int zero_async(hipStream_t st, T *p, size_t n, Rest... rest) {
+    HIP_TRY(hipMemsetAsync(p, 0, n * sizeof(T), st));
+    return zero_async(st, rest...);
+}
+
 // Everything of a handle that lives on one device: stream, constants and tables, the dataset arena, the workspaces of the
 // host-buffer entry points.  Made by evaluator_create and freed by evaluator_destroy (mp_capi.cpp), which deletes it inside a
 // DeviceScope of its device -- not by a destructor body, which would end before the members' destructors free their memory.
@@ -205,6 +219,7 @@ struct Held {
 // ---------------------------------------------------------------- defined in mp_capi.cpp, used by the summaries and the drivers
 int launch_lnprob_ordered(Evaluator *h, const mp::LaunchArgs &a_in, hipStream_t st);
 int check_box(const char *fn, int ndim, const double *lower, const double *upper);
+int check_inside(const char *what, const double *rows, size_t n, int ndim, const double *lower, const double *upper);
 int upload_ds_rows(int32_t *dst, const int32_t *ds_id, int n_groups, int rows);
 int groups_running(Evaluator *h, const int32_t *d_flags, int n, int *running);
 
@@ -226,6 +241,79 @@ int check_create(mp_handle *h, const char *fn, const char *multi, int ndim, int 
         const int d = ds_id ? ds_id[g] : 0;
         if (d < 0 || d >= MP_MAX_DATASETS || !h->first()->ds[d].set) return fail(MP_ESTATE, "%s: %s %d refers to unset dataset %d", fn, group, g, d);
     }
+    return MP_OK;
+}
+
+// ---------------------------------------------------------------- the skeleton of the resident drivers besides the ensemble sampler
+// (the optimizer, the nested sampler, the simplex search and the SMC sampler; mp_nested_run keeps a loop of its own, run_chunked's
+// with the dead rows read back around every chunk)
+// What each of the four structs (mp_optimizer, mp_nested, mp_simplex, mp_smc) derives from.  Each adds its launch arguments `a`
+// (with the box a.lower / a.upper) and its buffers, d_dsid among them.
+struct Resident {
+    mp_handle *h = nullptr;         // the lock
+    Evaluator *ev = nullptr;        // the device state: the handle's one evaluator
+    bool have_state = false;        // the driver's set function has run
+};
+
+template <class D>
+int resident_destroy(D *d) {
+    if (!d) return MP_OK;
+    Held held(d->h, d->ev);
+    (void)hipStreamSynchronize(d->ev->stream);
+    delete d;
+    return MP_OK;
+}
+
+// A create function `fn` from end to end: the NULL check, the handle's lock, check_create (multi, group and args() as there), the
+// new driver with the box copied in, then fill(d, bind) -- the driver's own arguments and its bind(...) list -- inside a
+// DeviceScope, and the datasets of the groups' rows (ds_rows rows each) uploaded to d_dsid.  NULL and the message on any failure.
+template <class D, class Args, class Fill>
+D *resident_create(mp_handle *h, const char *fn, const char *multi, int ndim, int target, const char *group, int n_groups,
+                   const int32_t *ds_id, int ds_rows, const double *lower, const double *upper, Args &&args, Fill &&fill) {
+    if (!h || !lower || !upper) { fail(MP_EINVAL, "%s: NULL argument", fn); return nullptr; }
+    Lock lock(h->mu);
+    if (check_create(h, fn, multi, ndim, target, group, n_groups, ds_id, args)) return nullptr;
+    D *d = new D();
+    d->h = h;
+    d->ev = h->first();
+    for (int k = 0; k < ndim; ++k) { d->a.lower[k] = lower[k]; d->a.upper[k] = upper[k]; }
+    DeviceScope scope(d->ev->device);
+    Binder bind;
+    fill(d, bind);
+    if (bind.rc || upload_ds_rows(d->d_dsid.p, ds_id, n_groups, ds_rows)) {
+        fail(MP_EHIP, "%s: device allocation failed", fn);
+        resident_destroy(d);
+        return nullptr;
+    }
+    return d;
+}
+
+// The entry of a run function `fn` of driver d: the arguments (`ok`; `bad` says what is wrong with them or with a NULL d), the
+// state that the function `set` makes, then the handle's lock and the evaluator's device for the rest of the body (`held`).
+#define RESIDENT_ENTER(d, ok, fn, bad, set)                                              \
+    if (!(d) || !(ok)) return fail(MP_EINVAL, fn ": " bad);                              \
+    if (!(d)->have_state) return fail(MP_ESTATE, fn ": call " set " first");             \
+    Held held((d)->h, (d)->ev)
+// The entry of a getter: the same, and the work on the evaluator's stream has finished.
+#define RESIDENT_READ(d, ok, fn, bad, set) \
+    RESIDENT_ENTER(d, ok, fn, bad, set);   \
+    HIP_TRY(hipStreamSynchronize((d)->ev->stream))
+
+// The run loop: up to `limit` units in chunks of at most chunk_max, enqueue() once per unit with no wait inside a chunk.  The
+// groups' flags are read back once before the first chunk and once behind every chunk, and the loop ends early once no group is
+// running; *n_running (unless NULL) is the last count.
+template <class Enqueue>
+int run_chunked(Evaluator *ev, const int32_t *d_flags, int n_groups, int chunk_max, int limit, int *n_running, Enqueue &&enqueue) {
+    int running, rc;
+    if ((rc = groups_running(ev, d_flags, n_groups, &running))) return rc;
+    for (int done = 0; done < limit && running > 0;) {
+        const int chunk = std::min(chunk_max, limit - done);
+        for (int c = 0; c < chunk; ++c)
+            if ((rc = enqueue())) return rc;
+        if ((rc = groups_running(ev, d_flags, n_groups, &running))) return rc;
+        done += chunk;
+    }
+    if (n_running) *n_running = running;
     return MP_OK;
 }
 

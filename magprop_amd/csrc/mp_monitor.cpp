@@ -2,10 +2,6 @@
 // mp_post.hip.
 #include "mp_monitor.h"
 
-static int launched(int e) {
-    return e ? fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e)) : MP_OK;
-}
-
 // ---- autocorrelation monitor
 int AcfMonitor::off(const char *fn) { return fail(MP_ESTATE, "%s: the autocorrelation monitor is off (mp_sampler_set_autocorr)", fn); }
 

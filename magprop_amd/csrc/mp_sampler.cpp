@@ -411,7 +411,7 @@ static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_
         if (!e) e = mp::launch_stretch(ev->sh, g, n_slots, variant_blocks, ev->stream);
     }
     if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, ev->stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e) return launched(e);
     return MP_OK;
 }
 
@@ -634,7 +634,7 @@ int mp_sampler_halfstep_shard(mp_sampler *s, int half, int slot_lo, int slot_hi,
     g.upd = d_rows;
     g.slot_lo = slot_lo;
     const int e = mp::launch_stretch(s->ev->sh, g, slot_hi - slot_lo, slot_hi - slot_lo, stream);   // (a rank's share chooses its own build)
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e) return launched(e);
     return MP_OK;
 }
 
@@ -650,7 +650,7 @@ int mp_sampler_halfstep_apply(mp_sampler *s, int half, const double *d_rows, dou
     g.chain_lnp = d_chain_lnp_row;
     g.chain_row = 0;
     const int e = mp::launch_stretch_apply(g, stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e) return launched(e);
     if (half == 1) s->steps_done += 1;
     return MP_OK;
 }
@@ -672,7 +672,7 @@ int mp_sampler_step_shard(mp_sampler *s, int block_lo, int block_hi, double *d_r
     g.spec = d_rows;
     g.slot_lo = block_lo;
     const int e = mp::launch_stretch_step(s->ev->sh, g, block_hi - block_lo, stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e) return launched(e);
     return MP_OK;
 }
 
@@ -687,7 +687,7 @@ int mp_sampler_step_apply(mp_sampler *s, const double *d_rows, double *d_chain_r
     g.chain_lnp = d_chain_lnp_row;
     g.chain_row = 0;
     const int e = mp::launch_stretch_step_commit(g, stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e) return launched(e);
     s->steps_done += 1;
     return MP_OK;
 }

@@ -2,13 +2,10 @@
 #include "mp_host.h"
 #include "mp_smc.h"
 
-struct mp_smc {
-    mp_handle *h = nullptr;         // the lock
-    Evaluator *ev = nullptr;        // the device state: the handle's one evaluator
+struct mp_smc : Resident {
     mp::SmcArgs a{};
     int n_total = 0;                // n_runs * n
     uint32_t stage = 0;             // stages launched since mp_smc_set_particles: stage t reads buffer t & 1 and writes the other
-    bool have_state = false;
     DevBuf<double> d_x[2], d_lnl[2], d_beta, d_lnz, d_log;
     DevBuf<int32_t> d_st[2], d_acc, d_dsid, d_anc, d_status, d_nstage;
     DevBuf<uint32_t> d_units;
@@ -21,6 +18,7 @@ struct mp_smc {
 namespace {
 
 constexpr int kSmcChunk = 8;   // stages enqueued between two looks at the runs' status
+static_assert(MP_SMC_RUNNING == 0, "groups_running counts the flags that are 0");
 
 // the buffers of stage t (mode 1: of the evaluation of buffer 0 as it is)
 void point_at(mp_smc *s, uint32_t t) {
@@ -30,70 +28,43 @@ void point_at(mp_smc *s, uint32_t t) {
     s->a.st_cur = s->st[c]; s->a.st_next = s->st[c ^ 1];
 }
 
-// *running = the runs whose status (read back behind the work on the handle's stream) is MP_SMC_RUNNING
-int runs_running(mp_smc *s, int *running) {
-    std::vector<int32_t> f((size_t)s->a.n_runs);
-    HIP_TRY(hipMemcpyAsync(f.data(), s->a.status, f.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s->ev->stream));
-    HIP_TRY(hipStreamSynchronize(s->ev->stream));
-    *running = (int)std::count(f.begin(), f.end(), MP_SMC_RUNNING);
-    return MP_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 void *mp_smc_create(mp_handle *h, int n_particles, int n_runs, int ndim, const int32_t *run_ds_id, uint64_t seed,
                     const double *lower, const double *upper, double ess, int walks, double g0, double sigma, int target) {
-    if (!h || !lower || !upper) { fail(MP_EINVAL, "mp_smc_create: NULL argument"); return nullptr; }
-    Lock lock(h->mu);
-    const int rc = check_create(h, "mp_smc_create", "the SMC sampler lives on ONE device (a multi-device handle serves host-buffer batches only)",
-                                ndim, target, "run", n_runs, run_ds_id, [&] {
-        if (n_particles < MP_SMC_MIN_PARTICLES || n_particles > MP_SMC_MAX_PARTICLES)
-            return fail(MP_EINVAL, "mp_smc_create: n_particles must be %d .. %d, got %d", MP_SMC_MIN_PARTICLES, MP_SMC_MAX_PARTICLES, n_particles);
-        if (n_runs < 1 || n_runs > MP_MAX_DATASETS) return fail(MP_EINVAL, "mp_smc_create: n_runs must be 1 .. %d", MP_MAX_DATASETS);
-        if (target < 0 || target > 2) return fail(MP_EINVAL, "mp_smc_create: target must be 0 (posterior), 1 (unit Gaussian) or 2 (terraced Gaussian)");
-        if (!(ess > 0.0 && ess < 1.0)) return fail(MP_EINVAL, "mp_smc_create: ess must lie in (0, 1)");
-        if (walks < 1 || walks > MP_SMC_MAX_WALKS) return fail(MP_EINVAL, "mp_smc_create: walks must be 1 .. %d", MP_SMC_MAX_WALKS);
-        if (!std::isfinite(g0)) return fail(MP_EINVAL, "mp_smc_create: g0 must be finite (<= 0: the default)");
-        if (!(sigma >= 0.0 && sigma < 1.0 / std::sqrt(3.0))) return fail(MP_EINVAL, "mp_smc_create: sigma must lie in [0, 1/sqrt(3))");
-        return check_box("mp_smc_create", ndim, lower, upper);
-    });
-    if (rc) return nullptr;
-    mp_smc *s = new mp_smc();
-    s->h = h;
-    s->ev = h->first();
-    s->n_total = n_particles * n_runs;
-    mp::SmcArgs &a = s->a;
-    a.n = n_particles; a.n_runs = n_runs; a.ndim = ndim; a.walks = walks; a.target = target; a.seed = seed;
-    a.g0 = g0 > 0.0 ? g0 : 2.38 / std::sqrt(2.0 * ndim);
-    a.sig3 = sigma * std::sqrt(3.0);
-    a.ess = ess;
-    for (int d = 0; d < ndim; ++d) { a.lower[d] = lower[d]; a.upper[d] = upper[d]; }
-    DeviceScope scope(s->ev->device);
-    const size_t nt = (size_t)s->n_total, nr = (size_t)n_runs, nl = nr * MP_SMC_MAX_STAGES;
-    Binder bind;
-    for (int c = 0; c < 2; ++c) { bind(s->d_x[c], nt * ndim, s->x[c]); bind(s->d_lnl[c], nt, s->lnl[c]); bind(s->d_st[c], nt, s->st[c]); }
-    bind(s->d_acc, nt, a.acc); bind(s->d_dsid, nr, a.ds_id); bind(s->d_anc, nt, a.anc); bind(s->d_units, nt, a.units); bind(s->d_cum, nt, a.cum);
-    bind(s->d_beta, nr, a.beta); bind(s->d_lnz, nr, a.lnz); bind(s->d_status, nr, a.status); bind(s->d_nstage, nr, a.nstage);
-    bind(s->d_ncall, nr, a.ncall); bind(s->d_nacc, nr, a.nacc); bind(s->d_nfail, nr, a.nfail);
-    bind(s->d_log, nl * mp::kSmcLogCols, a.log); bind(s->d_logcnt, nl * 2, a.log_cnt);
-    if (bind.rc || upload_ds_rows(s->d_dsid.p, run_ds_id, n_runs, 1)) {
-        fail(MP_EHIP, "mp_smc_create: device allocation failed");
-        mp_smc_destroy(s);
-        return nullptr;
-    }
-    return s;
+    return resident_create<mp_smc>(
+        h, "mp_smc_create", "the SMC sampler lives on ONE device (a multi-device handle serves host-buffer batches only)",
+        ndim, target, "run", n_runs, run_ds_id, 1, lower, upper,
+        [&] {
+            if (n_particles < MP_SMC_MIN_PARTICLES || n_particles > MP_SMC_MAX_PARTICLES)
+                return fail(MP_EINVAL, "mp_smc_create: n_particles must be %d .. %d, got %d", MP_SMC_MIN_PARTICLES, MP_SMC_MAX_PARTICLES, n_particles);
+            if (n_runs < 1 || n_runs > MP_MAX_DATASETS) return fail(MP_EINVAL, "mp_smc_create: n_runs must be 1 .. %d", MP_MAX_DATASETS);
+            if (target < 0 || target > 2) return fail(MP_EINVAL, "mp_smc_create: target must be 0 (posterior), 1 (unit Gaussian) or 2 (terraced Gaussian)");
+            if (!(ess > 0.0 && ess < 1.0)) return fail(MP_EINVAL, "mp_smc_create: ess must lie in (0, 1)");
+            if (walks < 1 || walks > MP_SMC_MAX_WALKS) return fail(MP_EINVAL, "mp_smc_create: walks must be 1 .. %d", MP_SMC_MAX_WALKS);
+            if (!std::isfinite(g0)) return fail(MP_EINVAL, "mp_smc_create: g0 must be finite (<= 0: the default)");
+            if (!(sigma >= 0.0 && sigma < 1.0 / std::sqrt(3.0))) return fail(MP_EINVAL, "mp_smc_create: sigma must lie in [0, 1/sqrt(3))");
+            return check_box("mp_smc_create", ndim, lower, upper);
+        },
+        [&](mp_smc *s, Binder &bind) {
+            s->n_total = n_particles * n_runs;
+            mp::SmcArgs &a = s->a;
+            a.n = n_particles; a.n_runs = n_runs; a.ndim = ndim; a.walks = walks; a.target = target; a.seed = seed;
+            a.g0 = g0 > 0.0 ? g0 : 2.38 / std::sqrt(2.0 * ndim);
+            a.sig3 = sigma * std::sqrt(3.0);
+            a.ess = ess;
+            const size_t nt = (size_t)s->n_total, nr = (size_t)n_runs, nl = nr * MP_SMC_MAX_STAGES;
+            for (int c = 0; c < 2; ++c) { bind(s->d_x[c], nt * ndim, s->x[c]); bind(s->d_lnl[c], nt, s->lnl[c]); bind(s->d_st[c], nt, s->st[c]); }
+            bind(s->d_acc, nt, a.acc); bind(s->d_dsid, nr, a.ds_id); bind(s->d_anc, nt, a.anc); bind(s->d_units, nt, a.units); bind(s->d_cum, nt, a.cum);
+            bind(s->d_beta, nr, a.beta); bind(s->d_lnz, nr, a.lnz); bind(s->d_status, nr, a.status); bind(s->d_nstage, nr, a.nstage);
+            bind(s->d_ncall, nr, a.ncall); bind(s->d_nacc, nr, a.nacc); bind(s->d_nfail, nr, a.nfail);
+            bind(s->d_log, nl * mp::kSmcLogCols, a.log); bind(s->d_logcnt, nl * 2, a.log_cnt);
+        });
 }
 
-int mp_smc_destroy(void *sv) {
-    mp_smc *s = (mp_smc *)sv;
-    if (!s) return MP_OK;
-    Held held(s->h, s->ev);
-    (void)hipStreamSynchronize(s->ev->stream);
-    delete s;
-    return MP_OK;
-}
+int mp_smc_destroy(void *sv) { return resident_destroy((mp_smc *)sv); }
 
 int mp_smc_set_particles(void *sv, const double *particles) {
     mp_smc *s = (mp_smc *)sv;
@@ -101,26 +72,17 @@ int mp_smc_set_particles(void *sv, const double *particles) {
     Evaluator *ev = s->ev;
     mp::SmcArgs &a = s->a;
     const size_t nt = (size_t)s->n_total, nr = (size_t)a.n_runs;
-    for (size_t i = 0; i < nt; ++i)
-        for (int d = 0; d < a.ndim; ++d) {
-            const double v = particles[i * a.ndim + d];
-            if (!(v >= a.lower[d] && v <= a.upper[d])) return fail(MP_EINVAL, "mp_smc_set_particles: particle %zu lies outside the box", i);
-        }
+    int rc = check_inside("mp_smc_set_particles: particle", particles, nt, a.ndim, a.lower, a.upper);
+    if (rc) return rc;
     Held held(s->h, ev);
     HIP_TRY(hipMemcpyAsync(s->x[0], particles, nt * a.ndim * sizeof(double), hipMemcpyHostToDevice, ev->stream));
-    HIP_TRY(hipMemsetAsync(a.beta, 0, nr * sizeof(double), ev->stream));   // (all bits zero: 0.0)
-    HIP_TRY(hipMemsetAsync(a.lnz, 0, nr * sizeof(double), ev->stream));
-    HIP_TRY(hipMemsetAsync(a.status, 0, nr * sizeof(int32_t), ev->stream));
-    HIP_TRY(hipMemsetAsync(a.nstage, 0, nr * sizeof(int32_t), ev->stream));
-    HIP_TRY(hipMemsetAsync(a.ncall, 0, nr * sizeof(int64_t), ev->stream));
-    HIP_TRY(hipMemsetAsync(a.nacc, 0, nr * sizeof(int64_t), ev->stream));
-    HIP_TRY(hipMemsetAsync(a.nfail, 0, nr * sizeof(int64_t), ev->stream));
-    HIP_TRY(hipMemsetAsync(a.anc, 0, nt * sizeof(int32_t), ev->stream));
+    // (beta and lnz: all bits zero is 0.0)
+    if ((rc = zero_async(ev->stream, a.beta, nr, a.lnz, nr, a.status, nr, a.nstage, nr, a.ncall, nr, a.nacc, nr, a.nfail, nr, a.anc, nt)))
+        return rc;
     point_at(s, 0);
     a.mode = 1;
     a.stage = 0;
-    const int e = mp::launch_smc_move(ev->sh, a, ev->stream);
-    if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if ((rc = launched(mp::launch_smc_move(ev->sh, a, ev->stream)))) return rc;
     HIP_TRY(hipStreamSynchronize(ev->stream));
     s->stage = 0;
     s->have_state = true;
@@ -129,42 +91,25 @@ int mp_smc_set_particles(void *sv, const double *particles) {
 
 int mp_smc_run(void *sv, int max_stages, int *n_running) {
     mp_smc *s = (mp_smc *)sv;
-    if (!s || max_stages < 0) return fail(MP_EINVAL, "mp_smc_run: bad argument");
-    if (!s->have_state) return fail(MP_ESTATE, "mp_smc_run: call mp_smc_set_particles first");
-    Evaluator *ev = s->ev;
-    mp::SmcArgs &a = s->a;
-    Held held(s->h, ev);
-    // Chunks of stages enqueued back to back (stage, move, stage, move, ...; no wait inside a chunk), then one read-back of the
-    // runs' status; a run that stopped inside a chunk ignores the chunk's later launches.
-    int running, rc;
-    if ((rc = runs_running(s, &running))) return rc;
-    for (int done = 0; done < max_stages && running > 0;) {
-        const int chunk = std::min(kSmcChunk, max_stages - done);
-        for (int c = 0; c < chunk; ++c) {
-            a.stage = s->stage++;
-            a.mode = 0;
-            point_at(s, a.stage);
-            int e = mp::launch_smc_stage(a, ev->stream);
-            if (!e) e = mp::launch_smc_move(ev->sh, a, ev->stream);
-            if (e) return fail(MP_EHIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        }
-        if ((rc = runs_running(s, &running))) return rc;
-        done += chunk;
-    }
-    if (n_running) *n_running = running;
-    return MP_OK;
+    RESIDENT_ENTER(s, max_stages >= 0, "mp_smc_run", "bad argument", "mp_smc_set_particles");
+    // Chunks of stages (stage, move, stage, move, ...); a run that stopped inside a chunk ignores the chunk's later launches.
+    return run_chunked(s->ev, s->a.status, s->a.n_runs, kSmcChunk, max_stages, n_running, [&] {
+        mp::SmcArgs &a = s->a;
+        a.stage = s->stage++;
+        a.mode = 0;
+        point_at(s, a.stage);
+        int e = mp::launch_smc_stage(a, s->ev->stream);
+        if (!e) e = mp::launch_smc_move(s->ev->sh, a, s->ev->stream);
+        return launched(e);
+    });
 }
 
 int mp_smc_get_state(void *sv, double *x, double *lnl, int32_t *status, int32_t *acc, double *beta, double *lnz, int32_t *nstage,
                      int32_t *run_status, int64_t *ncall, int64_t *nacc, int64_t *nfail) {
     mp_smc *s = (mp_smc *)sv;
-    if (!s) return fail(MP_EINVAL, "mp_smc_get_state: NULL sampler");
-    if (!s->have_state) return fail(MP_ESTATE, "mp_smc_get_state: call mp_smc_set_particles first");
-    Evaluator *ev = s->ev;
+    RESIDENT_READ(s, true, "mp_smc_get_state", "NULL sampler", "mp_smc_set_particles");
     const mp::SmcArgs &a = s->a;
-    Held held(s->h, ev);
     const size_t nt = (size_t)s->n_total, nr = (size_t)a.n_runs, n = (size_t)a.n;
-    HIP_TRY(hipStreamSynchronize(ev->stream));
     // a run's particles lie in the buffer its last stage's moves wrote: stage t writes buffer (t + 1) & 1
     std::vector<int32_t> made(nr);
     HIP_TRY(hipMemcpy(made.data(), a.nstage, nr * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -184,12 +129,8 @@ int mp_smc_get_state(void *sv, double *x, double *lnl, int32_t *status, int32_t 
 int mp_smc_get_stages(void *sv, int run, int max_rows, double *beta, double *d, double *ess, double *lnz, double *accept,
                       int64_t *ncall, int *n_rows) {
     mp_smc *s = (mp_smc *)sv;
-    if (!s || run < 0 || run >= s->a.n_runs || max_rows < 0) return fail(MP_EINVAL, "mp_smc_get_stages: bad argument");
-    if (!s->have_state) return fail(MP_ESTATE, "mp_smc_get_stages: call mp_smc_set_particles first");
-    Evaluator *ev = s->ev;
+    RESIDENT_READ(s, run >= 0 && run < s->a.n_runs && max_rows >= 0, "mp_smc_get_stages", "bad argument", "mp_smc_set_particles");
     const mp::SmcArgs &a = s->a;
-    Held held(s->h, ev);
-    HIP_TRY(hipStreamSynchronize(ev->stream));
     int32_t made = 0;
     int64_t tot[2];
     HIP_TRY(hipMemcpy(&made, a.nstage + run, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -219,10 +160,7 @@ int mp_smc_get_stages(void *sv, int run, int max_rows, double *beta, double *d, 
 
 int mp_smc_get_ancestors(void *sv, int32_t *anc) {
     mp_smc *s = (mp_smc *)sv;
-    if (!s || !anc) return fail(MP_EINVAL, "mp_smc_get_ancestors: NULL argument");
-    if (!s->have_state) return fail(MP_ESTATE, "mp_smc_get_ancestors: call mp_smc_set_particles first");
-    Held held(s->h, s->ev);
-    HIP_TRY(hipStreamSynchronize(s->ev->stream));
+    RESIDENT_READ(s, anc, "mp_smc_get_ancestors", "NULL argument", "mp_smc_set_particles");
     return read_back(anc, (const int32_t *)s->a.anc, (size_t)s->n_total);
 }
 

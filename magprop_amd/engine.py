@@ -1,5 +1,5 @@
 """Handle / dataset caches shared by the reference-shaped front ends (funcs, mcmc_eqns, synth), and the model setup of the
-front ends that own a handle (LogProb, EnsembleSampler, differential_evolution, NestedSampler)."""
+front ends that own a handle (LogProb, EnsembleSampler, differential_evolution, nelder_mead, NestedSampler, SMCSampler)."""
 import contextlib
 import hashlib
 import threading

@@ -14,15 +14,14 @@ import warnings
 
 import numpy as np
 
-from . import _capi, engine, summaries, tempering
-from .optimize import OptimizeResult
+from . import _capi, resident, summaries, tempering
 
 TARGETS = {"posterior": 0, "gaussian": 1}
 SAMPLES = ("rwalk", "slice")
 MAX_DRAW_ROUNDS = 4096
 
 
-class Results(OptimizeResult):
+class Results(resident.OptimizeResult):
     """dynesty's result names as a dict whose keys are also attributes (one run)."""
 
 
@@ -130,30 +129,8 @@ def _check_args(x, datasets, nlive, nbatch, walks, variant, ndim, bounds, n_runs
         raise ValueError("sigma must lie in [0, 1/sqrt(3))")
     if int(n_runs) != n_runs or n_runs < 1:
         raise ValueError("n_runs must be a positive integer")
-    if target == "gaussian":
-        if bounds is None:
-            raise ValueError("the gaussian target needs bounds")
-        b = np.asarray(bounds, dtype=np.float64)
-        if b.ndim != 2 or b.shape[1] != 2 or not 1 <= b.shape[0] <= 9:
-            raise ValueError("bounds must be 1 to 9 (lower, upper) pairs")
-        plo = phi = mask = None
-        n_ds = 1
-    else:
-        plo, phi, mask = engine.prior_box(variant, ndim, strict=True)
-        if bounds is None:
-            b = np.stack([plo, phi], axis=1)
-        else:
-            b = np.asarray(bounds, dtype=np.float64)
-            if b.shape != (ndim, 2):
-                raise ValueError(f"bounds must be {ndim} (lower, upper) pairs")
-        n_ds = len(datasets) if datasets is not None else (1 if x is not None else 0)
-        if n_ds == 0:
-            raise ValueError("a dataset is required: (x, y, yerr) or datasets=[...]")
-    lo, hi = b[:, 0].copy(), b[:, 1].copy()
-    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
-        raise ValueError("every bound must be finite with lower < upper")
-    if n_ds * int(n_runs) > _capi.MAX_DATASETS:
-        raise ValueError(f"len(datasets) x n_runs runs must be at most {_capi.MAX_DATASETS}")
+    lo, hi, plo, phi, mask, n_ds = resident.check_box_and_runs(x, datasets, variant, ndim, bounds, n_runs, target == "posterior",
+                                                               "the gaussian target needs bounds")
     return lo, hi, plo, phi, mask, int(nbatch), n_ds
 
 
@@ -177,7 +154,7 @@ def _check_slice(sample, slices, slice_mu, max_steps_out, max_shrink, ndim):
     return int(slices)
 
 
-class NestedSampler:
+class NestedSampler(resident.BoxSampler):
     """Nested sampling of the log-posterior of light curve (x, y, yerr), or of every light curve of datasets=[(x, y, yerr), ...],
     under a uniform prior over a box, on the GPU.
 
@@ -193,6 +170,8 @@ class NestedSampler:
     slice_mu differences at a random offset, steps out with Neal's budget max_steps_out and shrinks at most max_shrink times (a
     slice that reaches the cap, or draws two coinciding survivors, stays where it started and counts as failed).  It needs no
     step size and moves on every slice that does not fail; walks, g0 and sigma are then unused."""
+
+    POSTERIOR, NOT_RUN, NO_MODEL = "posterior", "run_nested first", "the gaussian target has no"
 
     def __init__(self, x=None, y=None, yerr=None, nlive=500, nbatch=None, walks=25, variant="synth", ndim=6, GRBtype=None,
                  datasets=None, n_runs=1, seed=0, bounds=None, log_mask=None, g0=0.0, sigma=0.1, target="posterior", device=-1,
@@ -213,17 +192,6 @@ class NestedSampler:
         self._prior = (plo, phi, mask if log_mask is None else log_mask)
         self.handle = None
         self.results = None
-
-    def _open(self):
-        if self.handle is not None:
-            return
-        self.handle = engine.open_handle(self.variant, self.GRBtype, self.device,
-                                         self._prior if self.target == "posterior" else None, self.datasets)
-
-    def close(self):
-        if self.handle is not None:
-            self.handle.close()
-            self.handle = None
 
     def initial_live(self):
         """(live[n_runs, nlive, ndim], prior draws per run): uniform box draws from np.random.default_rng(seed), run after run;
@@ -306,14 +274,6 @@ class NestedSampler:
         self.results = out[0] if self.n_runs == 1 else out
         return self.results
 
-    def _run(self, run):
-        res = self.results if isinstance(self.results, list) else [self.results]
-        if self.results is None:
-            raise ValueError("run_nested first")
-        if int(run) != run or not 0 <= run < len(res):
-            raise ValueError(f"run must be 0 .. {len(res) - 1}")
-        return res[int(run)]
-
     def resample_equal(self, run=0, seed=None):
         """Equal-weight posterior samples of run `run` (systematic resampling of its weighted sequence)."""
         r = self._run(run)
@@ -324,9 +284,7 @@ class NestedSampler:
         "exact": band_exact_selection of the run's samples, "weight_dropped" in the result and a RuntimeWarning above 1e-3; or
         "resample": its equal-weight samples, evenly thinned to _capi.BAND_MAX_SAMPLES, no weights.  Every other summary takes all
         of the run's samples under exp(logwt - max(logwt))."""
-        if self.target != "posterior":
-            raise ValueError(f"{name} needs the posterior target: the gaussian target has no "
-                             f"{'trajectory' if 'flow' in name else 'light curve'}")
+        self._need_posterior(name)
         if not name.endswith("band"):
             r = self._run(run)
             return r.samples, np.exp(r.logwt - np.max(r.logwt)), {}

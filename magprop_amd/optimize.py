@@ -11,23 +11,12 @@ reference's ``p0 + 1e-4 randn`` (code/synthetic_datasets/synth_mcmc.py).
 import numpy as np
 
 from . import _capi, engine
+from .resident import OptimizeResult, count_datasets, finite_box
 
 STRATEGIES = {"best1bin": _capi.DE_BEST1BIN, "rand1bin": _capi.DE_RAND1BIN}
 NM_STANDARD = (1.0, 2.0, 0.5, 0.5)                                   # rho, chi, psi, sigma of scipy's Nelder-Mead
 NM_OUTCOMES = ("reflect", "expand", "outside", "inside", "shrink")   # the columns of mp_simplex_get_state's outcomes
 NM_MAX_SIMPLEXES = 1024                                              # include/magprop_amd.h mp_simplex_create
-
-
-class OptimizeResult(dict):
-    """scipy.optimize.OptimizeResult's shape: a dict whose keys are also attributes."""
-
-    def __getattr__(self, name):
-        try:
-            return self[name]
-        except KeyError as exc:
-            raise AttributeError(name) from exc
-
-    __setattr__ = dict.__setitem__
 
 
 def latin_hypercube(rng, n, lower, upper):
@@ -54,9 +43,7 @@ def _check_args(variant, bounds, strategy, maxiter, popsize, tol, atol, mutation
             raise ValueError("bounds must be a sequence of (lower, upper) pairs")
         ndim = b.shape[0]
     plo, phi, mask = engine.prior_box(variant, ndim, strict=True)
-    lo, hi = (plo.copy(), phi.copy()) if bounds is None else (b[:, 0].copy(), b[:, 1].copy())
-    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
-        raise ValueError("every bound must be finite with lower < upper")
+    lo, hi = finite_box(np.stack([plo, phi], axis=1) if bounds is None else b)
     if int(maxiter) != maxiter or maxiter < 0:
         raise ValueError("maxiter must be an integer >= 0")
     if int(popsize) != popsize or popsize < 1:
@@ -75,9 +62,7 @@ def _check_args(variant, bounds, strategy, maxiter, popsize, tol, atol, mutation
         raise ValueError("recombination must lie in [0, 1]")
     if int(n_starts) != n_starts or n_starts < 1:
         raise ValueError("n_starts must be a positive integer")
-    n_ds = len(datasets) if datasets is not None else (1 if x is not None else 0)
-    if n_ds == 0:
-        raise ValueError("a dataset is required: (x, y, yerr) or datasets=[...]")
+    n_ds = count_datasets(x, datasets)
     if n_ds * int(n_starts) > _capi.MAX_DATASETS:
         raise ValueError(f"len(datasets) x n_starts populations must be at most {_capi.MAX_DATASETS}")
     return lo, hi, plo, phi, mask, members, f_lo, f_hi
@@ -232,9 +217,7 @@ def _check_simplex_args(x0, variant, bounds, initial_simplex, xatol, fatol, maxi
         if b.shape[0] != ndim:
             raise ValueError(f"bounds must have one (lower, upper) pair per coordinate of x0 ({ndim}), got {b.shape[0]}")
     plo, phi, mask = engine.prior_box(variant, ndim, strict=True)
-    lo, hi = (plo.copy(), phi.copy()) if bounds is None else (b[:, 0].copy(), b[:, 1].copy())
-    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
-        raise ValueError("every bound must be finite with lower < upper")
+    lo, hi = finite_box(np.stack([plo, phi], axis=1) if bounds is None else b)
     if not (np.isfinite(xatol) and xatol >= 0.0 and np.isfinite(fatol) and fatol >= 0.0):
         raise ValueError("xatol and fatol must be finite and >= 0")
     if maxiter is None:
@@ -243,9 +226,7 @@ def _check_simplex_args(x0, variant, bounds, initial_simplex, xatol, fatol, maxi
         raise ValueError("maxiter must be an integer >= 1 (scipy's count, which starts at 1)")
     if int(n_starts) != n_starts or n_starts < 1:
         raise ValueError("n_starts must be a positive integer")
-    n_ds = len(datasets) if datasets is not None else (1 if x is not None else 0)
-    if n_ds == 0:
-        raise ValueError("a dataset is required: (x, y, yerr) or datasets=[...]")
+    n_ds = count_datasets(x, datasets)
     n = n_ds * int(n_starts)
     if n > NM_MAX_SIMPLEXES:
         raise ValueError(f"len(datasets) x n_starts simplexes must be at most {NM_MAX_SIMPLEXES}")

@@ -15,14 +15,13 @@ import math
 
 import numpy as np
 
-from . import _capi, engine, summaries
-from .optimize import OptimizeResult
+from . import _capi, resident, summaries
 
 TARGETS = {"posterior": 0, "gaussian": 1, "terraced": 2}
 STATUS = ("running", "done", "failed", "stage_limit")
 
 
-class Results(OptimizeResult):
+class Results(resident.OptimizeResult):
     """The outcome of one run as a dict whose keys are also attributes."""
 
 
@@ -45,34 +44,12 @@ def _check_args(x, datasets, nparticles, walks, ess, variant, ndim, bounds, n_ru
         raise ValueError("sigma must lie in [0, 1/sqrt(3))")
     if int(n_runs) != n_runs or n_runs < 1:
         raise ValueError("n_runs must be a positive integer")
-    if target != 0:
-        if bounds is None:
-            raise ValueError("the gaussian targets need bounds")
-        b = np.asarray(bounds, dtype=np.float64)
-        if b.ndim != 2 or b.shape[1] != 2 or not 1 <= b.shape[0] <= _capi.MAX_NDIM:
-            raise ValueError(f"bounds must be 1 to {_capi.MAX_NDIM} (lower, upper) pairs")
-        plo = phi = mask = None
-        n_ds = 1
-    else:
-        plo, phi, mask = engine.prior_box(variant, ndim, strict=True)
-        if bounds is None:
-            b = np.stack([plo, phi], axis=1)
-        else:
-            b = np.asarray(bounds, dtype=np.float64)
-            if b.shape != (ndim, 2):
-                raise ValueError(f"bounds must be {ndim} (lower, upper) pairs")
-        n_ds = len(datasets) if datasets is not None else (1 if x is not None else 0)
-        if n_ds == 0:
-            raise ValueError("a dataset is required: (x, y, yerr) or datasets=[...]")
-    lo, hi = b[:, 0].copy(), b[:, 1].copy()
-    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
-        raise ValueError("every bound must be finite with lower < upper")
-    if n_ds * int(n_runs) > _capi.MAX_DATASETS:
-        raise ValueError(f"len(datasets) x n_runs runs must be at most {_capi.MAX_DATASETS}")
+    lo, hi, plo, phi, mask, n_ds = resident.check_box_and_runs(x, datasets, variant, ndim, bounds, n_runs, target == 0,
+                                                               "the gaussian targets need bounds")
     return lo, hi, plo, phi, mask, n_ds, int(target)
 
 
-class SMCSampler:
+class SMCSampler(resident.BoxSampler):
     """Tempered SMC of the log-posterior of light curve (x, y, yerr), or of every light curve of datasets=[(x, y, yerr), ...],
     under a uniform prior over a box, on the GPU.
 
@@ -84,6 +61,8 @@ class SMCSampler:
     their index in the Philox key and by their prior draws.  seed keys both the prior draws (numpy) and the device (Philox).
     target 1 / "gaussian" samples the isotropic unit Gaussian -0.5 sum x^2 in `bounds`, 2 / "terraced" the same on terraces
     (tests, measurements)."""
+
+    POSTERIOR, NOT_RUN, NO_MODEL = 0, "run first", "the gaussian targets have no"
 
     def __init__(self, x=None, y=None, yerr=None, nparticles=1024, walks=10, ess=0.5, variant="synth", ndim=6, GRBtype=None,
                  bounds=None, seed=0, n_runs=1, datasets=None, g0=0.0, sigma=0.1, target=0, device=-1, log_mask=None):
@@ -101,17 +80,6 @@ class SMCSampler:
         self._prior = (plo, phi, mask if log_mask is None else log_mask)
         self.handle = None
         self.results = None
-
-    def _open(self):
-        if self.handle is not None:
-            return
-        self.handle = engine.open_handle(self.variant, self.GRBtype, self.device, self._prior if self.target == 0 else None,
-                                         self.datasets)
-
-    def close(self):
-        if self.handle is not None:
-            self.handle.close()
-            self.handle = None
 
     def initial_particles(self):
         """particles[n_runs, nparticles, ndim]: uniform box draws from np.random.default_rng(seed), run after run.  Every draw is
@@ -154,19 +122,9 @@ class SMCSampler:
         self.results = out[0] if self.n_runs == 1 else out
         return self.results
 
-    def _run(self, run):
-        res = self.results if isinstance(self.results, list) else [self.results]
-        if self.results is None:
-            raise ValueError("run first")
-        if int(run) != run or not 0 <= run < len(res):
-            raise ValueError(f"run must be 0 .. {len(res) - 1}")
-        return res[int(run)]
-
     def _rows(self, name, run):
         """The samples of run `run` for the front end `name`: equally weighted, so every summary takes them without weights."""
-        if self.target != 0:
-            raise ValueError(f"{name} needs the posterior target: the gaussian targets have no "
-                             f"{'trajectory' if 'flow' in name else 'light curve'}")
+        self._need_posterior(name)
         return self._run(run).samples
 
     def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), run=0):
