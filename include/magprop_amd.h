@@ -1010,6 +1010,38 @@ int mp_simplex_destroy(void *s);
  * ess[], lnz[], accept[] (accepted steps of the stage's moves / (N walks)) and ncall[] (their evaluations), each may be NULL.
  * mp_smc_get_ancestors: anc[n_runs * N] of every run's last stage (a diagnostic of the genealogy).  The getters return MP_ESTATE
  * before mp_smc_set_particles.  The object behind the void pointers is an mp_smc.
+ * Adaptive moves (mp_smc_set_adaptive, additive; off after mp_smc_create, and then every result, counter and log row above is
+ * what it is without this paragraph): every run chooses the length of its moves and its scale g on the device.  The moves of
+ * a stage are rounds of `walks` steps each.  Round 0 is the move launch above.  In round k >= 1 slot j continues in place from
+ * its own row of the other buffer (x, lnl, status); the partners y, z are still particles anc[c1], anc[c2] of the stage's
+ * buffer, which nobody writes until the next stage, so the snapshot argument above holds for every round.  Step s of the
+ * stage, counted across its rounds (round k: s = k walks .. (k + 1) walks - 1), draws from 0x534D0000 + 2 s + 1 and + 2 s + 2;
+ * walks * max_rounds <= MP_SMC_MAX_WALKS.  gamma takes the run's g in place of g0; g = g0 at mp_smc_set_particles.  acc[] of
+ * a slot is its accepted steps over all rounds of the stage.
+ *   Tune, behind every round, one workgroup of 256 threads per run: for every dimension d, with a_j = x_d of particle anc[j]
+ *   of the stage's buffer (where slot j started) and b_j = x_d of slot j now: the sums of a and of b (thread k adds its slots
+ *   k, k + 256, ... in that order, then the order of mp_wg.h, as every sum here), the means ma = sum a / N, mb = sum b / N;
+ *   if min b = max b then rho_d = 1 (Sbb = 0: nothing has spread), else if min a = max a then rho_d = 0 (Saa = 0: all slots
+ *   started from one point); else ha = max |a_j - ma|, hb = max |b_j - mb|, the centred values u_j = (a_j - ma) 2^-ilogb(ha),
+ *   v_j = (b_j - mb) 2^-ilogb(hb) (the difference rounded, the scaling exact: it changes no correlation and keeps the squares
+ *   of coordinates of any size in range), Saa = sum u^2, Sbb = sum v^2, Sab = sum u v, every product rounded on its own,
+ *   rho_d = Sab / sqrt(Saa * Sbb).  rho = the largest rho_d; a NaN rho_d makes rho NaN.
+ *   With r = the rounds the stage has made, this one included, the run makes another round iff r < min_rounds, or
+ *   !(rho <= corr) and r < max_rounds (a NaN rho goes on up to the cap).
+ *   At the round that stops: the stage's row of the tuning log is (r, the g its moves used, rho);
+ *   share = A / (N * (r walks)), A = the sum of the slots' acc (an integer), product and quotient rounded on their own;
+ *   g = min(max(g * exp(gain * (share - accept_target)), g_min), g_max), every product rounded on its own, the device's exp
+ *   (PyMC's rule).  gain = 0 leaves g at g0 exactly.
+ *   Control is on the device: per run the rounds made in the current stage and a flag "still moving", both reset by the
+ *   stage; the launches of round k (move, tune) act on the runs that are still moving and have made k rounds, the workgroups
+ *   of every other run return at once.  The host enqueues, per stage, the stage and then max_rounds times (move, tune)
+ *   without a look.  A run that is MP_SMC_DONE still makes and tunes the rounds of its last stage.
+ * mp_smc_set_adaptive: between mp_smc_create and mp_smc_set_particles (MP_ESTATE after it).  max_rounds = 0 turns adaptation
+ * off and reads no other argument.  MP_EINVAL: min_rounds outside 1 .. max_rounds, walks * max_rounds > MP_SMC_MAX_WALKS,
+ * corr outside [0, 1), gain negative or not finite, accept_target outside (0, 1), g_min or g_max (<= 0: g0 / 16 and 4 g0) not
+ * finite or not g_min <= g0 <= g_max.  mp_smc_get_stages: accept[] divides by N times the steps the stage made, r walks.
+ * mp_smc_get_tuning(run): like mp_smc_get_stages, one row per stage made, to rounds[], g[] and rho[], each may be NULL;
+ * without adaptation the rows are (1, g0, NaN).
  */
 #define MP_SMC_MIN_PARTICLES 4
 #define MP_SMC_MAX_PARTICLES 16384
@@ -1029,6 +1061,9 @@ int mp_smc_get_state(void *s, double *x, double *lnl, int32_t *status, int32_t *
 int mp_smc_get_stages(void *s, int run, int max_rows, double *beta, double *d, double *ess, double *lnz, double *accept,
                       int64_t *ncall, int *n_rows);
 int mp_smc_get_ancestors(void *s, int32_t *anc);
+int mp_smc_set_adaptive(void *s, int min_rounds, int max_rounds, double corr, double gain, double accept_target,
+                        double g_min, double g_max);
+int mp_smc_get_tuning(void *s, int run, int max_rows, int32_t *rounds, double *g, double *rho, int *n_rows);
 int mp_smc_destroy(void *s);
 
 /* wait for everything enqueued on the handle's own stream */

@@ -138,6 +138,8 @@ SIGNATURES = {
     "mp_smc_get_state": (_i, [_vp, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _ip, _i64p, _i64p, _i64p]),
     "mp_smc_get_stages": (_i, [_vp, _i, _i, _dp, _dp, _dp, _dp, _dp, _i64p, _ip]),
     "mp_smc_get_ancestors": (_i, [_vp, _ip]),
+    "mp_smc_set_adaptive": (_i, [_vp, _i, _i, _d, _d, _d, _d, _d]),
+    "mp_smc_get_tuning": (_i, [_vp, _i, _i, _ip, _dp, _dp, _ip]),
     "mp_smc_destroy": (_i, [_vp]),
     "mp_synchronize": (_i, [_vp]),
     "mp_device": (_i, [_vp]),

@@ -11,6 +11,9 @@ struct mp_smc : Resident {
     DevBuf<uint32_t> d_units;
     DevBuf<unsigned long long> d_cum;
     DevBuf<int64_t> d_ncall, d_nacc, d_nfail, d_logcnt;
+    DevBuf<double> d_g, d_tlog;     // adaptation: the runs' scale, the tuning log ...
+    DevBuf<int32_t> d_rounds, d_moving, d_trounds;   // ... the flags of the current stage and the rounds of every stage
+    std::vector<double> g_start;    // g0 per run: what mp_smc_set_particles uploads to g
     double *x[2] = {nullptr, nullptr}, *lnl[2] = {nullptr, nullptr};
     int32_t *st[2] = {nullptr, nullptr};
 };
@@ -61,7 +64,37 @@ void *mp_smc_create(mp_handle *h, int n_particles, int n_runs, int ndim, const i
             bind(s->d_beta, nr, a.beta); bind(s->d_lnz, nr, a.lnz); bind(s->d_status, nr, a.status); bind(s->d_nstage, nr, a.nstage);
             bind(s->d_ncall, nr, a.ncall); bind(s->d_nacc, nr, a.nacc); bind(s->d_nfail, nr, a.nfail);
             bind(s->d_log, nl * mp::kSmcLogCols, a.log); bind(s->d_logcnt, nl * 2, a.log_cnt);
+            bind(s->d_g, nr, a.g); bind(s->d_rounds, nr, a.rounds); bind(s->d_moving, nr, a.moving);
+            bind(s->d_trounds, nl, a.tune_rounds); bind(s->d_tlog, nl * mp::kSmcTuneCols, a.tune_log);
+            s->g_start.assign(nr, a.g0);
         });
+}
+
+int mp_smc_set_adaptive(void *sv, int min_rounds, int max_rounds, double corr, double gain, double accept_target, double g_min,
+                        double g_max) {
+    mp_smc *s = (mp_smc *)sv;
+    if (!s) return fail(MP_EINVAL, "mp_smc_set_adaptive: NULL sampler");
+    Held held(s->h, s->ev);
+    if (s->have_state) return fail(MP_ESTATE, "mp_smc_set_adaptive: call it before mp_smc_set_particles");
+    mp::SmcArgs &a = s->a;
+    if (max_rounds == 0) {
+        a.adapt_min = a.adapt_max = 0;
+        return MP_OK;
+    }
+    if (max_rounds < 0 || min_rounds < 1 || min_rounds > max_rounds)
+        return fail(MP_EINVAL, "mp_smc_set_adaptive: min_rounds must be 1 .. max_rounds (max_rounds = 0: off)");
+    if ((long long)a.walks * max_rounds > MP_SMC_MAX_WALKS)
+        return fail(MP_EINVAL, "mp_smc_set_adaptive: walks * max_rounds must be <= %d", MP_SMC_MAX_WALKS);
+    if (!(corr >= 0.0 && corr < 1.0)) return fail(MP_EINVAL, "mp_smc_set_adaptive: corr must lie in [0, 1)");
+    if (!(gain >= 0.0) || !std::isfinite(gain)) return fail(MP_EINVAL, "mp_smc_set_adaptive: gain must be finite and >= 0");
+    if (!(accept_target > 0.0 && accept_target < 1.0)) return fail(MP_EINVAL, "mp_smc_set_adaptive: accept_target must lie in (0, 1)");
+    if (std::isnan(g_min) || std::isnan(g_max)) return fail(MP_EINVAL, "mp_smc_set_adaptive: g_min and g_max must be finite");
+    const double lo = g_min > 0.0 ? g_min : a.g0 / 16.0, hi = g_max > 0.0 ? g_max : 4.0 * a.g0;
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo <= a.g0 && a.g0 <= hi))
+        return fail(MP_EINVAL, "mp_smc_set_adaptive: need 0 < g_min <= g0 <= g_max, finite (<= 0: g0 / 16 and 4 g0)");
+    a.adapt_min = min_rounds; a.adapt_max = max_rounds;
+    a.corr = corr; a.gain = gain; a.accept_target = accept_target; a.g_min = lo; a.g_max = hi;
+    return MP_OK;
 }
 
 int mp_smc_destroy(void *sv) { return resident_destroy((mp_smc *)sv); }
@@ -79,7 +112,10 @@ int mp_smc_set_particles(void *sv, const double *particles) {
     // (beta and lnz: all bits zero is 0.0)
     if ((rc = zero_async(ev->stream, a.beta, nr, a.lnz, nr, a.status, nr, a.nstage, nr, a.ncall, nr, a.nacc, nr, a.nfail, nr, a.anc, nt)))
         return rc;
+    if ((rc = zero_async(ev->stream, a.rounds, nr, a.moving, nr))) return rc;
+    HIP_TRY(hipMemcpyAsync(a.g, s->g_start.data(), nr * sizeof(double), hipMemcpyHostToDevice, ev->stream));
     point_at(s, 0);
+    a.round = 0;
     a.mode = 1;
     a.stage = 0;
     if ((rc = launched(mp::launch_smc_move(ev->sh, a, ev->stream)))) return rc;
@@ -93,13 +129,21 @@ int mp_smc_run(void *sv, int max_stages, int *n_running) {
     mp_smc *s = (mp_smc *)sv;
     RESIDENT_ENTER(s, max_stages >= 0, "mp_smc_run", "bad argument", "mp_smc_set_particles");
     // Chunks of stages (stage, move, stage, move, ...); a run that stopped inside a chunk ignores the chunk's later launches.
+    // Adaptive: a stage is stage, then adapt_max times (move, tune), enqueued without a look: the runs' flags on the device say
+    // which of the rounds are theirs.
     return run_chunked(s->ev, s->a.status, s->a.n_runs, kSmcChunk, max_stages, n_running, [&] {
         mp::SmcArgs &a = s->a;
         a.stage = s->stage++;
         a.mode = 0;
+        a.round = 0;
         point_at(s, a.stage);
         int e = mp::launch_smc_stage(a, s->ev->stream);
         if (!e) e = mp::launch_smc_move(s->ev->sh, a, s->ev->stream);
+        for (int k = 0; !e && k < a.adapt_max; ++k) {
+            a.round = k;
+            if (k) e = mp::launch_smc_move(s->ev->sh, a, s->ev->stream);
+            if (!e) e = mp::launch_smc_tune(a, s->ev->stream);
+        }
         return launched(e);
     });
 }
@@ -144,6 +188,9 @@ int mp_smc_get_stages(void *sv, int run, int max_rows, double *beta, double *d, 
     }
     cnt[(size_t)made * 2] = tot[0];        // behind the last stage: the totals as they stand
     cnt[(size_t)made * 2 + 1] = tot[1];
+    std::vector<int32_t> rounds((size_t)made, 1);   // the rounds of `walks` steps every stage made
+    if (made && a.adapt_max)
+        HIP_TRY(hipMemcpy(rounds.data(), a.tune_rounds + (size_t)run * MP_SMC_MAX_STAGES, (size_t)made * sizeof(int32_t), hipMemcpyDeviceToHost));
     const int k_end = std::min((int)made, max_rows);
     for (int k = 0; k < k_end; ++k) {
         const double *row = rows.data() + (size_t)k * mp::kSmcLogCols;
@@ -151,8 +198,32 @@ int mp_smc_get_stages(void *sv, int run, int max_rows, double *beta, double *d, 
         if (d) d[k] = row[1];
         if (ess) ess[k] = row[2];
         if (lnz) lnz[k] = row[3];
-        if (accept) accept[k] = (double)(cnt[2 * k + 3] - cnt[2 * k + 1]) / ((double)a.n * (double)a.walks);
+        if (accept) accept[k] = (double)(cnt[2 * k + 3] - cnt[2 * k + 1]) / ((double)a.n * (double)(a.walks * rounds[k]));
         if (ncall) ncall[k] = cnt[2 * k + 2] - cnt[2 * k];
+    }
+    if (n_rows) *n_rows = made;
+    return MP_OK;
+}
+
+int mp_smc_get_tuning(void *sv, int run, int max_rows, int32_t *rounds, double *g, double *rho, int *n_rows) {
+    mp_smc *s = (mp_smc *)sv;
+    RESIDENT_READ(s, run >= 0 && run < s->a.n_runs && max_rows >= 0, "mp_smc_get_tuning", "bad argument", "mp_smc_set_particles");
+    const mp::SmcArgs &a = s->a;
+    int32_t made = 0;
+    HIP_TRY(hipMemcpy(&made, a.nstage + run, sizeof(int32_t), hipMemcpyDeviceToHost));
+    // without adaptation: one round at g0, no rho
+    std::vector<int32_t> nr((size_t)made, 1);
+    std::vector<double> rows((size_t)made * mp::kSmcTuneCols);
+    for (int k = 0; k < made; ++k) { rows[(size_t)k * mp::kSmcTuneCols] = a.g0; rows[(size_t)k * mp::kSmcTuneCols + 1] = NAN; }
+    if (made && a.adapt_max) {
+        HIP_TRY(hipMemcpy(nr.data(), a.tune_rounds + (size_t)run * MP_SMC_MAX_STAGES, nr.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rows.data(), a.tune_log + (size_t)run * MP_SMC_MAX_STAGES * mp::kSmcTuneCols, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    const int k_end = std::min((int)made, max_rows);
+    for (int k = 0; k < k_end; ++k) {
+        if (rounds) rounds[k] = nr[k];
+        if (g) g[k] = rows[(size_t)k * mp::kSmcTuneCols];
+        if (rho) rho[k] = rows[(size_t)k * mp::kSmcTuneCols + 1];
     }
     if (n_rows) *n_rows = made;
     return MP_OK;

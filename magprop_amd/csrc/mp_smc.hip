@@ -10,6 +10,12 @@
 // DE step in LDS from two other slots' ancestors, the workgroup evaluates the step through the one point_eval call, lane 0 takes
 // the tempered Metropolis decision.  The stage's buffer is only read and the other one only written, so the workgroups need no
 // hand-off among themselves.  Mode 1 evaluates the particles as the caller set them.
+// Adaptation (mp_smc_set_adaptive): a stage's moves are rounds of `walks` steps.  Round 0 is the launch above; in round k >= 1
+// slot j continues in place from its own row of the other buffer, its partners still drawn over the stage's buffer, which stays
+// unwritten until the next stage.  smc_tune_kernel: one workgroup of kWgThreads per run behind every round; from the correlation
+// between where the slots started and where they are it decides whether the run makes another round, and at the round that stops
+// it writes the stage's row of the tuning log and the run's scale g for the next stage.  The launches of a round act on the runs
+// whose flags (rounds, moving) say the round is theirs; the workgroups of the others return at once.
 #include <hip/hip_runtime.h>
 
 #include "mp_point.h"
@@ -130,6 +136,10 @@ __global__ __launch_bounds__(kWgThreads) void smc_stage_kernel(const SmcArgs a) 
         a.beta[r] = nb;
         a.lnz[r] = lnz;
         a.nstage[r] = made + 1;
+        if (a.adapt_max) {                          // the stage's rounds start over
+            a.rounds[r] = 0;
+            a.moving[r] = 1;
+        }
         if (nb >= 1.0) a.status[r] = MP_SMC_DONE;   // (its moves of this stage still run: they go by nstage)
     }
 }
@@ -139,6 +149,9 @@ template <int SPL, bool LONG, int W = 1, int OCC = 0>
 MP_POINT_KERNEL(SPL, W, OCC) void smc_move_kernel(const DevShared sh, const SmcArgs a) {
     const int b = (int)blockIdx.x, r = b / a.n, j = b - r * a.n;
     if (a.mode == 0 && a.nstage[r] != (int)a.stage + 1) return;   // no stage made (uniform for the workgroup): nothing to do
+    // adaptive: round a.round is this run's only while its moves go on and it has made that many rounds (uniform as well)
+    if (a.mode == 0 && a.adapt_max && (!a.moving[r] || a.rounds[r] != a.round)) return;
+    const int round = a.mode ? 0 : a.round;  // 0 without adaptation; k >= 1: the slot continues in place from its row of next
     __shared__ PointLds<SPL, W> ws;
     __shared__ double cur[MP_MAX_NDIM];      // the walk's current point
     __shared__ double prop[MP_MAX_NDIM];     // the step's proposal across the evaluation
@@ -147,19 +160,21 @@ MP_POINT_KERNEL(SPL, W, OCC) void smc_move_kernel(const DevShared sh, const SmcA
     tables_init<SPL * W, 64 * W>(sh, ws.tt);
     const int nd = a.ndim, n = a.n, base = r * n;
     const int steps = a.mode ? 1 : a.walks;
-    double lnl_cur = -INFINITY, beta = 0.0;
+    double lnl_cur = -INFINITY, beta = 0.0, g = a.g0;
     int st_cur = MP_STATUS_OK, n_acc = 0, n_eval = 0, n_bad = 0;
     if (threadIdx.x == 0) {
         int from = base + j;
         if (!a.mode) {
-            from = base + a.anc[base + j];
-            lnl_cur = a.lnl_cur[from];
-            st_cur = a.st_cur[from];
+            if (round == 0) from = base + a.anc[base + j];
+            lnl_cur = (round ? a.lnl_next : a.lnl_cur)[from];
+            st_cur = (round ? a.st_next : a.st_cur)[from];
             beta = a.beta[r];
+            if (a.adapt_max) g = a.g[r];
         }
-        for (int d = 0; d < nd; ++d) cur[d] = a.x_cur[(size_t)from * nd + d];
+        const double *x0 = round ? a.x_next : a.x_cur;
+        for (int d = 0; d < nd; ++d) cur[d] = x0[(size_t)from * nd + d];
     }
-    for (int s = 0; s < steps; ++s) {
+    for (int s = round * steps; s < (round + 1) * steps; ++s) {   // the stage's steps, counted across its rounds
         __syncthreads();
         if (threadIdx.x == 0) {
             if (a.mode) {
@@ -172,7 +187,7 @@ MP_POINT_KERNEL(SPL, W, OCC) void smc_move_kernel(const DevShared sh, const SmcA
                 const int c1 = pick(u01(u[0], u[1]), n), c2 = pick_skip(u01(u[2], u[3]), n, c1);
                 const double *x1 = a.x_cur + (size_t)(base + a.anc[base + c1]) * nd;
                 const double *x2 = a.x_cur + (size_t)(base + a.anc[base + c2]) * nd;
-                const double gamma = mul_rn(a.g0, add_rn(1.0, mul_rn(a.sig3, sub_rn(mul_rn(2.0, u01(v[0], v[1])), 1.0))));
+                const double gamma = mul_rn(g, add_rn(1.0, mul_rn(a.sig3, sub_rn(mul_rn(2.0, u01(v[0], v[1])), 1.0))));
                 int in = 1;
                 for (int d = 0; d < nd; ++d) {
                     const double q = add_rn(cur[d], mul_rn(gamma, sub_rn(x1[d], x2[d])));
@@ -206,10 +221,83 @@ MP_POINT_KERNEL(SPL, W, OCC) void smc_move_kernel(const DevShared sh, const SmcA
         for (int d = 0; d < nd; ++d) xo[row * nd + d] = cur[d];
         (a.mode ? a.lnl_cur : a.lnl_next)[row] = lnl_cur;
         (a.mode ? a.st_cur : a.st_next)[row] = st_cur;
-        a.acc[row] = n_acc;
+        a.acc[row] = round ? a.acc[row] + n_acc : n_acc;
         atomicAdd((unsigned long long *)&a.ncall[r], (unsigned long long)n_eval);
         if (n_acc) atomicAdd((unsigned long long *)&a.nacc[r], (unsigned long long)n_acc);
         if (n_bad) atomicAdd((unsigned long long *)&a.nfail[r], (unsigned long long)n_bad);
+    }
+}
+
+// Behind round a.round of an adaptive stage, run blockIdx.x (include/magprop_amd.h states the arithmetic): per dimension the
+// correlation over the slots between where a slot started, cur[anc[j]], and where it is, next[j]; the decision; at the round
+// that stops, the stage's row of the tuning log and the run's g for the next stage.
+__global__ __launch_bounds__(kWgThreads) void smc_tune_kernel(const SmcArgs a) {
+    const int r = (int)blockIdx.x, n = a.n, nd = a.ndim, base = r * n, tid = (int)threadIdx.x;
+    if (a.nstage[r] != (int)a.stage + 1 || !a.moving[r] || a.rounds[r] != a.round) return;   // (uniform, before the first barrier)
+    __shared__ double shd[kWgWaves];
+    __shared__ uint32_t shc[kWgWaves];
+    const double *xa = a.x_cur, *xb = a.x_next + (size_t)base * nd;
+    const int32_t *anc = a.anc + base;
+    double rho = -INFINITY;
+    for (int d = 0; d < nd; ++d) {
+        double sa = 0.0, sb = 0.0, la = INFINITY, ua = -INFINITY, lb = INFINITY, ub = -INFINITY;
+        for (int i = tid; i < n; i += kWgThreads) {
+            const double va = xa[(size_t)(base + anc[i]) * nd + d], vb = xb[(size_t)i * nd + d];
+            sa = add_rn(sa, va);
+            sb = add_rn(sb, vb);
+            la = fmin(la, va);
+            ua = fmax(ua, va);
+            lb = fmin(lb, vb);
+            ub = fmax(ub, vb);
+        }
+        const double ma = wg_sum(sa, shd) / (double)n, mb = wg_sum(sb, shd) / (double)n;
+        la = wg_min(la, shd);
+        ua = wg_max(ua, shd);
+        lb = wg_min(lb, shd);
+        ub = wg_max(ub, shd);
+        double rho_d;
+        if (lb == ub) rho_d = 1.0;               // every slot at one value, Sbb = 0: nothing has spread
+        else if (la == ua) rho_d = 0.0;          // Saa = 0: every slot started from one point
+        else {
+            double ha = 0.0, hb = 0.0;           // the largest centred sizes: 2^-ilogb of them scales the squares into range
+            for (int i = tid; i < n; i += kWgThreads) {
+                ha = fmax(ha, fabs(sub_rn(xa[(size_t)(base + anc[i]) * nd + d], ma)));
+                hb = fmax(hb, fabs(sub_rn(xb[(size_t)i * nd + d], mb)));
+            }
+            ha = wg_max(ha, shd);
+            hb = wg_max(hb, shd);
+            const int ea = -ilogb(ha), eb = -ilogb(hb);
+            double saa = 0.0, sbb = 0.0, sab = 0.0;
+            for (int i = tid; i < n; i += kWgThreads) {
+                const double u = ldexp(sub_rn(xa[(size_t)(base + anc[i]) * nd + d], ma), ea);
+                const double v = ldexp(sub_rn(xb[(size_t)i * nd + d], mb), eb);
+                saa = add_rn(saa, mul_rn(u, u));
+                sbb = add_rn(sbb, mul_rn(v, v));
+                sab = add_rn(sab, mul_rn(u, v));
+            }
+            saa = wg_sum(saa, shd);
+            sbb = wg_sum(sbb, shd);
+            sab = wg_sum(sab, shd);
+            rho_d = sab / sqrt(mul_rn(saa, sbb));
+        }
+        if (a.rho_d && tid == 0) a.rho_d[(size_t)r * nd + d] = rho_d;
+        if (rho_d > rho || rho_d != rho_d) rho = rho_d;   // the largest; a NaN stays
+    }
+    uint32_t mine = 0;
+    for (int i = tid; i < n; i += kWgThreads) mine += (uint32_t)a.acc[base + i];
+    const uint32_t accepted = wg_count(mine, shc);
+    if (tid == 0) {
+        const int made = a.round + 1;
+        a.rounds[r] = made;
+        if (made < a.adapt_min || (!(rho <= a.corr) && made < a.adapt_max)) return;   // another round
+        a.moving[r] = 0;
+        const size_t row = (size_t)r * MP_SMC_MAX_STAGES + (size_t)a.stage;
+        const double g = a.g[r];
+        a.tune_rounds[row] = made;
+        a.tune_log[row * kSmcTuneCols] = g;
+        a.tune_log[row * kSmcTuneCols + 1] = rho;
+        const double share = (double)accepted / mul_rn((double)n, (double)(made * a.walks));
+        a.g[r] = fmin(fmax(mul_rn(g, exp(mul_rn(a.gain, sub_rn(share, a.accept_target)))), a.g_min), a.g_max);
     }
 }
 
@@ -218,6 +306,12 @@ MP_POINT_KERNEL(SPL, W, OCC) void smc_move_kernel(const DevShared sh, const SmcA
 int launch_smc_stage(const SmcArgs &a, void *stream) {
     if (a.n_runs <= 0) return 0;
     hipLaunchKernelGGL(smc_stage_kernel, dim3((unsigned)a.n_runs), dim3(kWgThreads), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int launch_smc_tune(const SmcArgs &a, void *stream) {
+    if (a.n_runs <= 0) return 0;
+    hipLaunchKernelGGL(smc_tune_kernel, dim3((unsigned)a.n_runs), dim3(kWgThreads), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

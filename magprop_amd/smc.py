@@ -25,9 +25,46 @@ class Results(resident.OptimizeResult):
     """The outcome of one run as a dict whose keys are also attributes."""
 
 
-def _check_args(x, datasets, nparticles, walks, ess, variant, ndim, bounds, n_runs, g0, sigma, target):
-    """(box lower, box upper, prior lower, prior upper, log mask, number of datasets, target code): every check, no device
-    touched."""
+# The adaptive moves' defaults, chosen from the sweep of tools/smc_bench.py (DESIGN.md section 8): rounds of WALKS_ADAPTIVE steps
+# until every dimension's correlation with the start of the stage is at most corr, at most max_rounds rounds.
+ADAPT_DEFAULTS = dict(min_rounds=1, max_rounds=80, corr=0.5, gain=1.0, accept_target=0.234, g_min=0.0, g_max=0.0)
+WALKS_FIXED, WALKS_ADAPTIVE = 10, 2
+
+
+def _check_adapt(adapt, walks, g0):
+    """The settings of mp_smc_set_adaptive as a dict (None: adaptation off) from adapt = False, True or a dict of overrides;
+    g0 is the scale the library will keep."""
+    if adapt is None or adapt is False:
+        return None
+    if adapt is True:
+        adapt = {}
+    if not isinstance(adapt, dict) or set(adapt) - set(ADAPT_DEFAULTS):
+        raise ValueError(f"adapt must be False, True or a dict with keys among {tuple(ADAPT_DEFAULTS)}, got {adapt!r}")
+    a = {**ADAPT_DEFAULTS, **adapt}
+    for k in ("min_rounds", "max_rounds"):
+        if isinstance(a[k], bool) or int(a[k]) != a[k]:
+            raise ValueError(f"adapt: {k} must be an integer")
+        a[k] = int(a[k])
+    if not 1 <= a["min_rounds"] <= a["max_rounds"]:
+        raise ValueError("adapt: min_rounds must lie in 1 .. max_rounds")
+    if walks * a["max_rounds"] > _capi.SMC_MAX_WALKS:
+        raise ValueError(f"adapt: walks * max_rounds must be <= {_capi.SMC_MAX_WALKS}")
+    if not 0.0 <= a["corr"] < 1.0:
+        raise ValueError("adapt: corr must lie in [0, 1)")
+    if not (np.isfinite(a["gain"]) and a["gain"] >= 0.0):
+        raise ValueError("adapt: gain must be finite and >= 0")
+    if not 0.0 < a["accept_target"] < 1.0:
+        raise ValueError("adapt: accept_target must lie in (0, 1)")
+    lo = a["g_min"] if a["g_min"] > 0.0 else g0 / 16.0
+    hi = a["g_max"] if a["g_max"] > 0.0 else 4.0 * g0
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= g0 <= hi):
+        raise ValueError("adapt: need 0 < g_min <= g0 <= g_max, finite (<= 0: g0 / 16 and 4 g0)")
+    return {k: (a[k] if k.endswith("rounds") else float(a[k])) for k in ADAPT_DEFAULTS}
+
+
+def _check_args(x, datasets, nparticles, walks, ess, variant, ndim, bounds, n_runs, g0, sigma, target, adapt=False):
+    """(box lower, box upper, prior lower, prior upper, log mask, number of datasets, target code, adaptation settings or
+    None): every check, no device touched."""
     if target in TARGETS:
         target = TARGETS[target]
     if target not in TARGETS.values() or isinstance(target, bool):
@@ -46,7 +83,8 @@ def _check_args(x, datasets, nparticles, walks, ess, variant, ndim, bounds, n_ru
         raise ValueError("n_runs must be a positive integer")
     lo, hi, plo, phi, mask, n_ds = resident.check_box_and_runs(x, datasets, variant, ndim, bounds, n_runs, target == 0,
                                                                "the gaussian targets need bounds")
-    return lo, hi, plo, phi, mask, n_ds, int(target)
+    adapt = _check_adapt(adapt, int(walks), g0 if g0 > 0.0 else 2.38 / math.sqrt(2.0 * lo.size))
+    return lo, hi, plo, phi, mask, n_ds, int(target), adapt
 
 
 class SMCSampler(resident.BoxSampler):
@@ -60,14 +98,23 @@ class SMCSampler(resident.BoxSampler):
     n_runs: independent runs per dataset, all in one launch per stage (run index = dataset index x n_runs + run); they differ by
     their index in the Philox key and by their prior draws.  seed keys both the prior draws (numpy) and the device (Philox).
     target 1 / "gaussian" samples the isotropic unit Gaussian -0.5 sum x^2 in `bounds`, 2 / "terraced" the same on terraces
-    (tests, measurements)."""
+    (tests, measurements).
+    adapt=True (or a dict overriding ADAPT_DEFAULTS: min_rounds, max_rounds, corr, gain, accept_target, g_min, g_max) lets every
+    run choose its move length and scale on the device (mp_smc_set_adaptive): `walks` is then the length of a round (default 2
+    where the fixed-length move's is 10), a stage's
+    moves go on round after round until the correlation between where the slots started and where they are has fallen to corr
+    in every dimension (at most max_rounds rounds), and the run's g follows the stage's acceptance towards accept_target.  The
+    results gain rounds, scale and rho per stage.  adapt=False (the default) is the fixed-length run, unchanged."""
 
     POSTERIOR, NOT_RUN, NO_MODEL = 0, "run first", "the gaussian targets have no"
 
-    def __init__(self, x=None, y=None, yerr=None, nparticles=1024, walks=10, ess=0.5, variant="synth", ndim=6, GRBtype=None,
-                 bounds=None, seed=0, n_runs=1, datasets=None, g0=0.0, sigma=0.1, target=0, device=-1, log_mask=None):
-        lo, hi, plo, phi, mask, n_ds, target = _check_args(x, datasets, nparticles, walks, ess, variant, ndim, bounds, n_runs, g0,
-                                                           sigma, target)
+    def __init__(self, x=None, y=None, yerr=None, nparticles=1024, walks=None, ess=0.5, variant="synth", ndim=6, GRBtype=None,
+                 bounds=None, seed=0, n_runs=1, datasets=None, g0=0.0, sigma=0.1, target=0, device=-1, log_mask=None, adapt=False):
+        if walks is None:                   # 10 steps per move; with adaptation rounds of 2
+            walks = WALKS_FIXED if adapt is None or adapt is False else WALKS_ADAPTIVE
+        lo, hi, plo, phi, mask, n_ds, target, adapt = _check_args(x, datasets, nparticles, walks, ess, variant, ndim, bounds,
+                                                                  n_runs, g0, sigma, target, adapt)
+        self.adapt = adapt
         self.lower, self.upper = lo, hi
         self.ndim = lo.size
         self.nparticles, self.walks, self.ess = int(nparticles), int(walks), float(ess)
@@ -94,7 +141,9 @@ class SMCSampler(resident.BoxSampler):
         of the mean over the runs that share the run's dataset; NaN for a single run: no single-run error is made up), beta,
         betas / ess / accept / ncall_stage (per stage: the new beta, the effective sample size at it, the accepted share of the
         stage's N walks proposals, its evaluations), ncall (all evaluations, the first N included), nacc, nfail (evaluations
-        whose model failed), nstages and status ("done", "running" when max_stages ended it, "failed": no particle had a finite
+        whose model failed), rounds / scale / rho (per stage: the rounds of `walks` steps its moves made, the DE scale they used
+        and the correlation at which they stopped; without adaptation 1, g0 and NaN, and with it accept counts the proposals
+        of all rounds), nstages and status ("done", "running" when max_stages ended it, "failed": no particle had a finite
         lnprob, "stage_limit")."""
         if max_stages is not None and (int(max_stages) != max_stages or max_stages < 0):
             raise ValueError("max_stages must be an integer >= 0")
@@ -104,10 +153,13 @@ class SMCSampler(resident.BoxSampler):
         with _capi.Driver("mp_smc", self.handle, self.nparticles, self.n_runs, self.ndim, _capi.ptr(self.run_ds), self.seed,
                           _capi.ptr(self.lower), _capi.ptr(self.upper), self.ess, self.walks, self.g0, self.sigma,
                           self.target) as s:
+            if self.adapt is not None:
+                _capi.check(L.mp_smc_set_adaptive(s, *(self.adapt[k] for k in ADAPT_DEFAULTS)), "mp_smc_set_adaptive")
             _capi.check(L.mp_smc_set_particles(s, _capi.ptr(np.ascontiguousarray(x0))), "mp_smc_set_particles")
             _capi.check(L.mp_smc_run(s, 2 ** 31 - 1 if max_stages is None else int(max_stages), None), "mp_smc_run")
             st = get_state(L, s, self.n_runs, self.nparticles, self.ndim)
             logs = [get_stages(L, s, r) for r in range(self.n_runs)]
+            tunes = [get_tuning(L, s, r) for r in range(self.n_runs)]
         k = self.runs_per_dataset
         out = []
         for r in range(self.n_runs):
@@ -118,7 +170,8 @@ class SMCSampler(resident.BoxSampler):
                 samples=st["x"][r], logl=st["lnl"][r], logz=float(st["lnz"][r]), logzerr=err, beta=float(st["beta"][r]),
                 betas=log["beta"], ess=log["ess"], accept=log["accept"], ncall_stage=log["ncall"], ncall=int(st["ncall"][r]),
                 nacc=int(st["nacc"][r]), nfail=int(st["nfail"][r]), nstages=int(st["nstage"][r]),
-                status=STATUS[int(st["run_status"][r])], particle_status=st["status"][r]))
+                status=STATUS[int(st["run_status"][r])], particle_status=st["status"][r],
+                rounds=tunes[r]["rounds"], scale=tunes[r]["g"], rho=tunes[r]["rho"]))
         self.results = out[0] if self.n_runs == 1 else out
         return self.results
 
@@ -171,6 +224,16 @@ def get_stages(L, s, run):
     n = int(_capi.read_back(L.mp_smc_get_stages, s, none + [("n", (), np.int32)], int(run), 0)["n"])
     d = _capi.read_back(L.mp_smc_get_stages, s, [("beta", n, f8), ("d", n, f8), ("ess", n, f8), ("lnz", n, f8), ("accept", n, f8),
                                                  ("ncall", n, np.int64), ("n", (), np.int32)], int(run), n)
+    d.pop("n")
+    return d
+
+
+def get_tuning(L, s, run):
+    """mp_smc_get_tuning of one run: {"rounds", "g", "rho"}, one entry per stage (without adaptation 1, g0 and NaN)."""
+    none = [(k, None, None) for k in ("rounds", "g", "rho")]
+    n = int(_capi.read_back(L.mp_smc_get_tuning, s, none + [("n", (), np.int32)], int(run), 0)["n"])
+    d = _capi.read_back(L.mp_smc_get_tuning, s, [("rounds", n, np.int32), ("g", n, np.float64), ("rho", n, np.float64),
+                                                 ("n", (), np.int32)], int(run), n)
     d.pop("n")
     return d
 
