@@ -211,6 +211,11 @@ struct StretchArgs {
     double kde_f;           // KDE: bandwidth factor f (resolved by mp_sampler_set_moves), kernel covariance f^2 S
 };
 
+// The ensemble at position e_pos of a half-step launch (StretchArgs::ens_order: longest light curve first).
+MP_HD inline int ens_of_slot(const StretchArgs &g, int e_pos) {
+    return g.ens_order ? (int)((g.ens_order >> (4 * e_pos)) & 15u) : e_pos;
+}
+
 // ---------------------------------------------------------------- compile-time constants of the stride policy
 // (used by mp_eval.hpp; reported by mp_get_policy so that an A/B build made with -D overrides cannot pass for the shipped one)
 // Tile kinds from this one on start their sweeps from the log-space extrapolation (5: none).  Tiles of 256 steps (4 steps

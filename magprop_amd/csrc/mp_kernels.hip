@@ -158,10 +158,8 @@ int launch_order(const DevShared &sh, const int32_t *ds_id, int n, int32_t *orde
 // ranks after the all-gather.  The random numbers (Philox, mp_device.h) are keyed by (seed; step, half, walker), so every rank
 // draws what the single-GPU launch would have drawn for the same walker.
 // Half-step launches run the ensembles in the order of StretchArgs::ens_order (mp_sampler.cpp: longest light curve first, four
-// bits per position; 0 = the ensembles as they are numbered): the waves that take longest start first, as in order_kernel.
-__device__ __forceinline__ int ens_of_slot(const StretchArgs &g, int e_pos) {
-    return g.ens_order ? (int)((g.ens_order >> (4 * e_pos)) & 15u) : e_pos;
-}
+// bits per position; 0 = the ensembles as they are numbered; ens_of_slot, mp_device.h): the waves that take longest start first,
+// as in order_kernel.
 
 // ---- differential-evolution and snooker proposals (the DIFF builds of stretch_kernel; include/magprop_amd.h MP_MOVE_*)
 // (index draws over the m slots of the complementary half: pick / pick_skip / pick_skip2, mp_math.hpp)
@@ -556,11 +554,7 @@ MP_DEV void commit_outcome(const StretchArgs &g, int k, bool accept, const doubl
         for (int i = 0; i < g.ndim; ++i) c[i] = g.pos[(size_t)k * g.ndim + i];
         g.chain_lnp[(size_t)g.chain_row * g.n_total + k] = accept ? lnp : lnp_old;
     }
-    if (g.bad_log && (status == MP_STATUS_FLAG || status == MP_STATUS_NONFINITE)) {
-        const unsigned slot_b = atomicAdd(g.bad_count, 1u);
-        if (slot_b < g.bad_cap)
-            for (int i = 0; i < g.ndim; ++i) g.bad_log[(size_t)slot_b * g.ndim + i] = u[i];
-    }
+    fbad_append(g, status, u);
 }
 
 // Commit one half-step from the gathered outcome rows (see stretch_kernel): one thread per slot of the active half.

@@ -630,6 +630,18 @@ MP_DEV int pick_skip2(double u, int m, int c0, int c1) {
     return t >= max(c0, c1) ? t + 1 : t;
 }
 
+// ---------------------------------------------------------------- the fbad log of the sampler's kernels
+// A point q[0 .. ndim) inside the prior whose model failed (status FLAG or NONFINITE) takes the next row of g.bad_log while rows
+// are left; g.bad_count counts on.  The reference appends such parameter sets to its `fbad` file
+// (code/synthetic_datasets/mcmc_eqns.py:72-79).  (stretch_kernel commits from LDS and states this itself.)
+MP_DEV void fbad_append(const StretchArgs &g, int status, const double *q) {
+    if (g.bad_log && (status == MP_STATUS_FLAG || status == MP_STATUS_NONFINITE)) {
+        const unsigned slot_b = atomicAdd(g.bad_count, 1u);
+        if (slot_b < g.bad_cap)
+            for (int i = 0; i < g.ndim; ++i) g.bad_log[(size_t)slot_b * g.ndim + i] = q[i];
+    }
+}
+
 // ---------------------------------------------------------------- log-sum-exp (the KDE move's Hastings term, mp_kernels.hip)
 // A running log-sum-exp is a pair (m, s): the sum is e^m s, m the largest term so far; (-inf, 0) is the empty sum.
 // lse_add takes one more term v, lse_merge another pair.  Unfused and symmetric in its two operands (no contraction into

@@ -5,15 +5,24 @@
 // rule to the live set as it stands, and otherwise writes the iteration's dead list (ascending lnL), the survivors in slot order,
 // L*, the dead rows of the chunk and the new ln X and ln Z (one thread, in the order of the header).
 // nest_walk_kernel: one workgroup per dead slot, on the shell of mp_point.h.  Lane 0 picks a survivor as the start and builds
-// every DE step in LDS, the workgroup evaluates the step, lane 0 decides (inside the box and lnL > L*).  Survivors are only read
-// and dead slots only written, so the workgroups need no hand-off among themselves.  Mode 1 evaluates the live set as the caller
-// set it.  (The one kernel of the four that states point_eval's block itself: with the call its walks ran 3 % slower.)
+// every DE step in LDS (de_walk_step of mp_walk.h), the workgroup evaluates the step, lane 0 decides (inside the box and lnL >
+// L*).  Survivors are only read and dead slots only written, so the workgroups need no hand-off among themselves.  Mode 1
+// evaluates the live set as the caller set it.  (The one kernel of the four that states point_eval's block itself: with the call
+// its walks ran 3 % slower.)
 // nest_slice_kernel: the walk of slice mode (mp_nested_set_slice), the same workgroups and builds.  Lane 0 runs the slice updates
 // as a state machine in LDS (start a slice, step out left, step out right, shrink) that names one point per round or ends the
 // walk; the workgroup evaluates the named point through the one point_eval call of the kernel.
+//
+// The phases of a slice are stated here a second time: slice_step of mp_walk.h, which the ensemble slice move runs
+// (mp_slice.hip), is the same machine line for line.  On it this kernel spilled less on every build (scratch 92 .. 152 -> 72 ..
+// 124 B/lane) and yet ran slice mode 2.2 % slower on one MI355X, on the posterior and on the Gaussian target alike: 2.786 ..
+// 2.796 ms per iteration against 2.719 .. 2.733 on Humped, 0.304 .. 0.307 against 0.297 .. 0.300 on the 6-d Gaussian, five
+// alternated runs against six (tools/nest_bench.py rate --sample both; profiles/r25_walk_shared_ab.json; DESIGN.md "What the walk
+// kernels share").  A fix to the phase logic goes into both, and into tests/walk_restated.py, which restates them once.
 #include <hip/hip_runtime.h>
 
 #include "mp_point.h"
+#include "mp_walk.h"
 
 namespace mp {
 
@@ -72,14 +81,7 @@ MP_POINT_KERNEL(SPL, W, OCC) void nest_walk_kernel(const DevShared sh, const Nes
                 const int c1 = pick(u01(u[0], u[1]), m), c2 = pick_skip(u01(u[2], u[3]), m, c1);
                 const double *x1 = a.live + (size_t)(base + a.surv[r * m + c1]) * nd;
                 const double *x2 = a.live + (size_t)(base + a.surv[r * m + c2]) * nd;
-                const double gamma = mul_rn(a.g0, add_rn(1.0, mul_rn(a.sig3, sub_rn(mul_rn(2.0, u01(v[0], v[1])), 1.0))));
-                int in = 1;
-                for (int d = 0; d < nd; ++d) {
-                    const double q = add_rn(cur[d], mul_rn(gamma, sub_rn(x1[d], x2[d])));
-                    in &= (q >= a.lower[d] && q <= a.upper[d]) ? 1 : 0;
-                    prop[d] = q;
-                }
-                go = in;
+                go = de_walk_step(cur, x1, x2, a.g0, a.sig3, u01(v[0], v[1]), a.lower, a.upper, nd, prop);
             }
         }
         __syncthreads();

@@ -3,19 +3,16 @@
 //
 // slice_half_kernel: one workgroup per slot of the active half, on the shell of mp_point.h; the block-to-ensemble mapping through
 // slot_lo and ens_order is stretch_kernel's.  Lane 0 draws the direction (a difference of two walkers of the other half) and runs
-// the slice update of its walker as a state machine in LDS (step out left, step out right, shrink) that names one point per round
-// or ends the update; the workgroup evaluates the named point through the one point_eval call of the kernel.  The other half is
-// only read and the active walker only written by its own workgroup, so the workgroups need no hand-off among themselves.
+// the slice update of its walker as a state machine in LDS (slice_step of mp_walk.h, the machine the nested sampler's slice mode
+// states in mp_nest.hip: step out left, step out right, shrink) that names one point per round or ends the update; the workgroup
+// evaluates the named point through the one point_eval call of the kernel.  The other half is only read and the active walker only written by its
+// own workgroup, so the workgroups need no hand-off among themselves.
 // slice_tune_kernel: one thread per ensemble, behind the second half-step: folds the step's counts into the totals and tunes mu.
-//
-// The state machine is a copy of slice_round's of mp_nest.hip, not shared with it: the two differ in the "inside" test (a level
-// under the walker's own tempered lnprob here, L* there), in where the partners and the scale come from, in the number of slices
-// per launch (one here) and in the Philox key, and a shared template would have to leave the nested sampler's builds with the
-// resource figures they have.
 #include <hip/hip_runtime.h>
 
 #include "mp_point.h"
 #include "mp_slice.h"
+#include "mp_walk.h"
 
 namespace mp {
 
@@ -23,22 +20,16 @@ namespace {
 
 constexpr uint32_t kSliceMoveCtr = 0x51C00000u;   // fourth counter word: 0x51C00000 + c, c = 0 partners, 1 interval, 2 level, 3 + i shrink point i
 
-// (stretch_kernel's rule, mp_kernels.hip: the ensemble at position e_pos of a half-step launch, longest light curve first)
-MP_DEV int slice_ens_of_slot(const StretchArgs &g, int e_pos) {
-    return g.ens_order ? (int)((g.ens_order >> (4 * e_pos)) & 15u) : e_pos;
-}
-
 MP_DEV void slice_draw(const StretchArgs &g, int k, uint32_t c, uint32_t (&out)[4]) {
     philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, kSliceMoveCtr + c, out);
 }
 
-// The update's state between rounds, in LDS (only lane 0 reads or writes it).  phase: kLeft / kRight step out (budgets left /
-// right), kShrink draws shrink point i of [lo, hi], kDone ends the update.
-enum { kLeft = 0, kRight = 1, kShrink = 2, kDone = 3 };
+// The update's state between rounds, in LDS (only lane 0 reads or writes it): the walker's one slice is open in c (mp_walk.h)
+// until the update ends.
 struct SliceWalk {
-    double lnp, lny, lo, hi, t, mu, beta;   // the walker's (untempered) lnprob; the level; the interval along dir; the parameter
-                                            // of the named point; the ensemble's scale and inverse temperature
-    int st, phase, left, right, i, moved, n_eval, n_exp, n_con, n_fail;
+    double lnp, lny, mu, beta;   // the walker's (untempered) lnprob; the level; the ensemble's scale and inverse temperature
+    SliceCore c;
+    int st, moved, n_eval;
 };
 
 // Lane 0, before the first round: the walker's position, its direction x_c1 - x_c2, the interval, the budgets and the level.
@@ -61,78 +52,37 @@ MP_DEV void slice_begin(const StretchArgs &g, const SliceArgs &sl, int k, int w_
         dir[d] = sub_rn(x1[d], x2[d]);
         nz |= dir[d] != 0.0 ? 1 : 0;
     }
-    if (!nz) {   // coinciding partners: the slice fails where it starts
-        z.n_fail = 1;
-        z.phase = kDone;
+    if (!nz) {   // coinciding partners: the slice fails where it starts (none is opened)
+        z.c.n_fail = 1;
         return;
     }
     slice_draw(g, k, 1u, u);
-    z.lo = -mul_rn(z.mu, u01(u[0], u[1]));
-    z.hi = add_rn(z.lo, z.mu);
-    z.left = (int)(u01(u[2], u[3]) * (double)sl.max_steps_out);
-    z.right = sl.max_steps_out - 1 - z.left;
+    slice_open(z.c, z.mu, u01(u[0], u[1]), u01(u[2], u[3]), sl.max_steps_out);
     slice_draw(g, k, 2u, u);
     z.lny = add_rn(mul_rn(z.beta, z.lnp), log(u01(u[0], u[1])));   // (ln 0 = -inf: everything finite is inside)
-    z.phase = kLeft;
 }
 
 // Lane 0, once per round: takes the outcome of the point named last round (have: one was evaluated, lnprob lnp, status), then
-// advances until it names the next point to evaluate (prop = cur + t dir, unfused; returns 1) or the update ends (returns 0; a
-// walker that moved has its new position in cur).  Inside = in the prior box (target 0) and beta lnprob > the level; a point
-// outside the box is outside without an evaluation.
+// advances until it names the next point to evaluate (in prop; returns 1) or the update ends (returns 0; a walker that moved has
+// its new position in cur).  Inside = in the prior box (target 0) and beta lnprob > the level.
 MP_DEV int slice_move_round(const DevShared &sh, const StretchArgs &g, const SliceArgs &sl, int k, SliceWalk &z, double *cur,
                             const double *dir, double *prop, bool have, double lnp, int status) {
-    const int nd = g.ndim;
-    bool in = have && mul_rn(z.beta, lnp) > z.lny;
-    for (;;) {
-        if (have) {   // the named point's outcome (evaluated, or outside the box)
-            have = false;
-            if (z.phase == kLeft) {
-                if (in) { z.lo = sub_rn(z.lo, z.mu); --z.left; ++z.n_exp; } else z.phase = kRight;
-            } else if (z.phase == kRight) {
-                if (in) { z.hi = add_rn(z.hi, z.mu); --z.right; ++z.n_exp; } else z.phase = kShrink;
-            } else if (in) {
-                for (int d = 0; d < nd; ++d) cur[d] = prop[d];
-                z.lnp = lnp;
-                z.st = status;
-                z.moved = 1;
-                z.phase = kDone;
-            } else {
-                ++z.n_con;
-                if (z.t < 0.0) z.lo = z.t;
-                else z.hi = z.t;
-            }
-        }
-        double t;
-        if (z.phase == kDone) return 0;
-        if (z.phase == kLeft) {
-            if (z.left == 0) { z.phase = kRight; continue; }
-            t = z.lo;
-        } else if (z.phase == kRight) {
-            if (z.right == 0) { z.phase = kShrink; continue; }
-            t = z.hi;
-        } else {
-            if (z.i == sl.max_shrink) {   // the cap: the slice fails where it starts
-                ++z.n_fail;
-                z.phase = kDone;
-                return 0;
-            }
-            uint32_t u[4];
-            slice_draw(g, k, 3u + (uint32_t)z.i, u);
-            ++z.i;
-            t = add_rn(z.lo, mul_rn(u01(u[0], u[1]), sub_rn(z.hi, z.lo)));
-        }
-        z.t = t;
-        int box = 1;
-        for (int d = 0; d < nd; ++d) {
-            const double q = add_rn(cur[d], mul_rn(t, dir[d]));
-            if (g.target == 0 && d < sh.n_prior && (!(q >= sh.lower[d]) || !(q <= sh.upper[d]))) box = 0;
-            prop[d] = q;
-        }
-        if (box) return 1;
-        have = true;   // outside the box: outside, not evaluated
-        in = false;
+    if (z.c.phase == kSliceEnded) return 0;
+    const int end = slice_step(z.c, z.mu, sl.max_shrink, have, have && mul_rn(z.beta, lnp) > z.lny, cur, dir, prop, g.ndim,
+                               [&](int i) {
+                                   uint32_t u[4];
+                                   slice_draw(g, k, 3u + (uint32_t)i, u);
+                                   return u01(u[0], u[1]);
+                               },
+                               [&](int d, double q) { return g.target != 0 || d >= sh.n_prior || (q >= sh.lower[d] && q <= sh.upper[d]); });
+    if (end == kSliceNamed) return 1;
+    if (end == kSliceMoved) {
+        for (int d = 0; d < g.ndim; ++d) cur[d] = prop[d];
+        z.lnp = lnp;
+        z.st = status;
+        z.moved = 1;
     }
+    return 0;
 }
 
 // One workgroup per slot of the active half; builds and template arguments as the kernels of mp_point.h.
@@ -146,7 +96,7 @@ MP_POINT_KERNEL(SPL, W, OCC) void slice_half_kernel(const DevShared sh, const St
     __shared__ int go;                       // 1: evaluate prop; 0: the update has ended
     tables_init<SPL * W, 64 * W>(sh, ws.tt);
     const int gs = g.slot_lo + (int)blockIdx.x;                    // slot of the active half, all ensembles flattened
-    const int w_ens = slice_ens_of_slot(g, gs / g.n_half);         // which ensemble (longest light curve first)
+    const int w_ens = ens_of_slot(g, gs / g.n_half);               // which ensemble (longest light curve first)
     const int slot = gs % g.n_half;                                // which walker of the active half
     const int32_t *perm = g.perm + (size_t)w_ens * g.n_walkers;    // this step's random split of the ensemble
     const int base = w_ens * g.n_walkers;
@@ -163,12 +113,7 @@ MP_POINT_KERNEL(SPL, W, OCC) void slice_half_kernel(const DevShared sh, const St
         point_eval<SPL, LONG, W, OCC>(sh, ws, g.ds_id, nd, g.target, k, prop, lnp, status);
         if (threadIdx.x == 0) {
             ++z.n_eval;
-            if (g.bad_log && (status == MP_STATUS_FLAG || status == MP_STATUS_NONFINITE)) {
-                // the reference appends such parameter sets to its `fbad` file (code/synthetic_datasets/mcmc_eqns.py:72-79)
-                const unsigned slot_b = atomicAdd(g.bad_count, 1u);
-                if (slot_b < g.bad_cap)
-                    for (int d = 0; d < nd; ++d) g.bad_log[(size_t)slot_b * nd + d] = prop[d];
-            }
+            fbad_append(g, status, prop);
         }
     }
     if (threadIdx.x == 0) {
@@ -182,9 +127,9 @@ MP_POINT_KERNEL(SPL, W, OCC) void slice_half_kernel(const DevShared sh, const St
             for (int d = 0; d < nd; ++d) c[d] = cur[d];
             g.chain_lnp[(size_t)g.chain_row * g.n_total + k] = z.lnp;
         }
-        if (z.n_exp) atomicAdd((unsigned long long *)&sl.nexpand_s[w_ens], (unsigned long long)z.n_exp);
-        if (z.n_con) atomicAdd((unsigned long long *)&sl.ncontract_s[w_ens], (unsigned long long)z.n_con);
-        if (z.n_fail) atomicAdd((unsigned long long *)&sl.nfail[w_ens], (unsigned long long)z.n_fail);
+        if (z.c.n_exp) atomicAdd((unsigned long long *)&sl.nexpand_s[w_ens], (unsigned long long)z.c.n_exp);
+        if (z.c.n_con) atomicAdd((unsigned long long *)&sl.ncontract_s[w_ens], (unsigned long long)z.c.n_con);
+        if (z.c.n_fail) atomicAdd((unsigned long long *)&sl.nfail[w_ens], (unsigned long long)z.c.n_fail);
         if (z.n_eval) atomicAdd((unsigned long long *)&sl.neval[w_ens], (unsigned long long)z.n_eval);
     }
 }

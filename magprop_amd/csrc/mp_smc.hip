@@ -7,8 +7,8 @@
 // run's lnl, read from global memory: a run of 16 384 does not fit LDS), advances ln Z, turns the weights into integer units,
 // scans them and resamples systematically in integers: anc[j], the particle slot j continues from.
 // smc_move_kernel: one workgroup per slot, on the shell of mp_point.h.  Lane 0 starts from the slot's ancestor and builds every
-// DE step in LDS from two other slots' ancestors, the workgroup evaluates the step through the one point_eval call, lane 0 takes
-// the tempered Metropolis decision.  The stage's buffer is only read and the other one only written, so the workgroups need no
+// DE step in LDS from two other slots' ancestors (de_walk_step of mp_walk.h, the nested sampler's), the workgroup evaluates the
+// step through the one point_eval call, lane 0 takes the tempered Metropolis decision.  The stage's buffer is only read and the other one only written, so the workgroups need no
 // hand-off among themselves.  Mode 1 evaluates the particles as the caller set them.
 // Adaptation (mp_smc_set_adaptive): a stage's moves are rounds of `walks` steps.  Round 0 is the launch above; in round k >= 1
 // slot j continues in place from its own row of the other buffer, its partners still drawn over the stage's buffer, which stays
@@ -20,6 +20,7 @@
 
 #include "mp_point.h"
 #include "mp_smc.h"
+#include "mp_walk.h"
 #include "mp_wg.h"
 
 namespace mp {
@@ -187,15 +188,8 @@ MP_POINT_KERNEL(SPL, W, OCC) void smc_move_kernel(const DevShared sh, const SmcA
                 const int c1 = pick(u01(u[0], u[1]), n), c2 = pick_skip(u01(u[2], u[3]), n, c1);
                 const double *x1 = a.x_cur + (size_t)(base + a.anc[base + c1]) * nd;
                 const double *x2 = a.x_cur + (size_t)(base + a.anc[base + c2]) * nd;
-                const double gamma = mul_rn(g, add_rn(1.0, mul_rn(a.sig3, sub_rn(mul_rn(2.0, u01(v[0], v[1])), 1.0))));
-                int in = 1;
-                for (int d = 0; d < nd; ++d) {
-                    const double q = add_rn(cur[d], mul_rn(gamma, sub_rn(x1[d], x2[d])));
-                    in &= (q >= a.lower[d] && q <= a.upper[d]) ? 1 : 0;
-                    prop[d] = q;
-                }
+                go = de_walk_step(cur, x1, x2, g, a.sig3, u01(v[0], v[1]), a.lower, a.upper, nd, prop);
                 lnu = log(u01(v[2], v[3]));
-                go = in;
             }
         }
         __syncthreads();

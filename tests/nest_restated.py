@@ -12,6 +12,7 @@ import numpy as np
 
 from moves_restated import pick, pick_skip
 from oracle.stretch_oracle import philox4x32_10, u01
+from walk_restated import de_step
 
 M32 = 0xFFFFFFFF
 CTR = 0x4E000000
@@ -96,11 +97,10 @@ def walk_rounds(s, r, slot, t, surv, lstar, seed, walks, g0, s3, lower, upper):
         v = draw(seed, t, r, slot, 2 * k + 2)
         c1 = pick(u01(u[0], u[1]), m)
         c2 = pick_skip(u01(u[2], u[3]), m, c1)
-        a, b = s.live[r, surv[c1]], s.live[r, surv[c2]]
-        gamma = g0 * (1.0 + s3 * (2.0 * u01(v[0], v[1]) - 1.0))
-        q = [x[d] + gamma * (float(a[d]) - float(b[d])) for d in range(len(x))]
-        if not all(lower[d] <= q[d] <= upper[d] for d in range(len(x))):
+        q, inside = de_step(x, s.live[r, surv[c1]], s.live[r, surv[c2]], g0, s3, u01(v[0], v[1]), lower, upper)
+        if not inside:
             continue
+        q = [float(c) for c in q]
         lq, sq = yield np.array(q)
         lq = _clean(lq)
         n_eval += 1

@@ -1,15 +1,15 @@
 """numpy restatement of the nested sampler's slice mode (include/magprop_amd.h mp_nested_set_slice): the walk into a dead slot as
 `slices` slice updates along survivor differences, with the Philox layout and the unfused arithmetic of the kernel
-(magprop_amd/csrc/mp_nest.hip nest_slice_kernel).  The ranking, the volume bookkeeping and the stop rule are nest_restated's.
+(magprop_amd/csrc/mp_nest.hip nest_slice_kernel).  The slice update itself is walk_restated.slice_rounds, which the ensemble slice
+move shares; the ranking, the volume bookkeeping and the stop rule are nest_restated's.
 Test infrastructure: the GPU tests compare the device state with it bit for bit, the CPU tests check with it that a slice walk
 leaves the constrained prior invariant.  Every product and sum is a separately rounded float64 operation in the kernel's order."""
-import math
-
 import numpy as np
 
 import nest_restated as nr
 from moves_restated import pick, pick_skip
 from oracle.stretch_oracle import philox4x32_10, u01
+from walk_restated import slice_rounds
 
 M32 = 0xFFFFFFFF
 SLICE_CTR = 0x4E400000
@@ -26,22 +26,9 @@ def slice_walk_rounds(x, lnl, st, t, r, slot, surv_pts, lstar, seed, slices, mu,
     """`slices` slice updates of x (a list of floats; lnL lnl, status st) at iteration t, run r, dead slot `slot`, as the kernel's
     rounds: a generator that yields the next point to evaluate (a named point inside the box), is sent its (lnL, status), and
     returns (x, lnl, st, slices moved, evaluations, expansions, contractions, failed slices).  surv_pts[m]: the survivors in
-    slot order (the directions).  broken="forward" (the negative control of the tests): the interval starts at x and steps out
-    forward only (L = 0, R = mu, J = 0, K = m - 1), so that the walk moves along +d alone and is not reversible."""
+    slot order (the directions).  broken="forward": the negative control of walk_restated.slice_rounds."""
     m, nd = len(surv_pts), len(x)
     moved = n_eval = n_exp = n_con = n_fail = 0
-
-    def named(tt, d):
-        """(q, inside, lnL, status) of the point x + tt d; outside the box: not evaluated."""
-        nonlocal n_eval
-        q = [x[k] + tt * d[k] for k in range(nd)]
-        if not all(lower[k] <= q[k] <= upper[k] for k in range(nd)):
-            return q, False, None, None
-        lq, sq = yield np.array(q)
-        lq = -math.inf if lq != lq else float(lq)
-        n_eval += 1
-        return q, lq > lstar, lq, int(sq)
-
     for s in range(slices):
         u = slice_draw(seed, t, r, slot, s, 0)
         c1 = pick(u01(u[0], u[1]), m)
@@ -51,36 +38,14 @@ def slice_walk_rounds(x, lnl, st, t, r, slot, surv_pts, lstar, seed, slices, mu,
         if not any(v != 0.0 for v in d):
             n_fail += 1
             continue
-        u = slice_draw(seed, t, r, slot, s, 1)
-        lo = -(mu * u01(u[0], u[1]))
-        hi = lo + mu
-        left = int(u01(u[2], u[3]) * float(max_steps_out))
-        right = max_steps_out - 1 - left
-        if broken == "forward":
-            lo, hi, left, right = 0.0, mu, 0, max_steps_out - 1
-        while left > 0 and (yield from named(lo, d))[1]:
-            lo = lo - mu
-            left -= 1
-            n_exp += 1
-        while right > 0 and (yield from named(hi, d))[1]:
-            hi = hi + mu
-            right -= 1
-            n_exp += 1
-        for i in range(max_shrink):
-            u = slice_draw(seed, t, r, slot, s, 2 + i)
-            tt = lo + u01(u[0], u[1]) * (hi - lo)
-            q, inside, lq, sq = yield from named(tt, d)
-            if inside:
-                x, lnl, st = q, lq, sq
-                moved += 1
-                break
-            n_con += 1
-            if tt < 0.0:
-                lo = tt
-            else:
-                hi = tt
-        else:
+        o = yield from slice_rounds(x, d, mu, max_steps_out, max_shrink, lambda c: slice_draw(seed, t, r, slot, s, c), 2,
+                                    lambda lq: lq > lstar, (lower, upper), broken)
+        n_eval, n_exp, n_con = n_eval + o.n_eval, n_exp + o.n_exp, n_con + o.n_con
+        if o.q is None:
             n_fail += 1
+        else:
+            x, lnl, st = o.q, o.lnp, o.status
+            moved += 1
     return x, lnl, st, moved, n_eval, n_exp, n_con, n_fail
 
 

@@ -1,5 +1,6 @@
 """numpy restatement of the sampler's ensemble slice-sampling move (include/magprop_amd.h MP_MOVE_SLICE): one slice update of a
-walker as the kernel's rounds (magprop_amd/csrc/mp_slice.hip slice_half_kernel), the tune rule, and a step loop that runs slice
+walker as the kernel's rounds (magprop_amd/csrc/mp_slice.hip slice_half_kernel; the slice itself is walk_restated.slice_rounds,
+which the nested sampler's slice mode shares), the tune rule, and a step loop that runs slice
 steps here and hands every other move of a mixture, one step at a time, to tests/sampler_restated.py.  Test infrastructure: the
 GPU tests compare the device chains with the loop bit for bit, the CPU tests draw their statistics from it.  Every product and
 sum is a separately rounded float64 operation in the kernel's order."""
@@ -11,6 +12,7 @@ import nest_restated as nr
 import sampler_restated
 from moves_restated import draw_move, pick, pick_skip, resolve
 from oracle.stretch_oracle import gaussian_lnprob, philox4x32_10, split, u01
+from walk_restated import slice_rounds
 
 M32 = 0xFFFFFFFF
 SLICE = 4                   # MP_MOVE_SLICE
@@ -42,54 +44,20 @@ def slice_update_rounds(x, lnp_x, k, comp_pts, seed, step, half, mu, beta, max_s
     order.  box = (lower, upper): points outside it are outside without an evaluation (target 0); None: no box.  drop_lnu (the
     negative control of the tests): the level is beta lnp_x itself, without ln u."""
     m, nd = len(comp_pts), len(x)
-    n_eval = n_exp = n_con = 0
     u = slice_draw(seed, step, half, k, 0)
     c1 = pick(u01(u[0], u[1]), m)
     c2 = pick_skip(u01(u[2], u[3]), m, c1)
     d = [float(comp_pts[c1][i]) - float(comp_pts[c2][i]) for i in range(nd)]
     if not any(v != 0.0 for v in d):
         return Update(x, lnp_x, 0, 0, 0, 0, 0, 1, None)
-    u = slice_draw(seed, step, half, k, 1)
-    lo = -(mu * u01(u[0], u[1]))
-    hi = lo + mu
-    left = int(u01(u[2], u[3]) * float(max_steps_out))
-    right = max_steps_out - 1 - left
-    budgets = (left, right)
     u = slice_draw(seed, step, half, k, 2)
     with np.errstate(divide="ignore"):
         lny = float(beta * lnp_x) if drop_lnu else float(beta * lnp_x + np.log(u01(u[0], u[1])))
-
-    def named(t):
-        """(q, inside, lnprob, status) of the point x + t d; outside the box: not evaluated."""
-        nonlocal n_eval
-        q = [x[i] + t * d[i] for i in range(nd)]
-        if box is not None and not all(box[0][i] <= q[i] <= box[1][i] for i in range(nd)):
-            return q, False, None, None
-        lq, sq = yield np.array(q)
-        lq = -np.inf if lq != lq else float(lq)
-        n_eval += 1
-        return q, beta * lq > lny, lq, int(sq)
-
-    while left > 0 and (yield from named(lo))[1]:
-        lo = lo - mu
-        left -= 1
-        n_exp += 1
-    while right > 0 and (yield from named(hi))[1]:
-        hi = hi + mu
-        right -= 1
-        n_exp += 1
-    for i in range(max_shrink):
-        u = slice_draw(seed, step, half, k, 3 + i)
-        t = lo + u01(u[0], u[1]) * (hi - lo)
-        q, inside, lq, sq = yield from named(t)
-        if inside:
-            return Update(q, lq, sq, 1, n_eval, n_exp, n_con, 0, budgets)
-        n_con += 1
-        if t < 0.0:
-            lo = t
-        else:
-            hi = t
-    return Update(x, lnp_x, 0, 0, n_eval, n_exp, n_con, 1, budgets)
+    o = yield from slice_rounds(x, d, mu, max_steps_out, max_shrink, lambda c: slice_draw(seed, step, half, k, c), 3,
+                                lambda lq: beta * lq > lny, box)
+    if o.q is None:
+        return Update(x, lnp_x, 0, 0, o.n_eval, o.n_exp, o.n_con, 1, o.budgets)
+    return Update(o.q, o.lnp, o.status, 1, o.n_eval, o.n_exp, o.n_con, 0, o.budgets)
 
 
 def tune(mu, nexpand_s, ncontract_s):

@@ -66,11 +66,9 @@ def round_of(s, jobs, pop, first, walks, g, s3, seed, lower, upper, evaluate, lo
             u, v = sm.draws(seed, t, r, slots, 2 * k + 1), sm.draws(seed, t, r, slots, 2 * k + 2)
             c1 = sm.pick(sm.u01(u[0], u[1]), n)
             c2 = sm.pick_skip(sm.u01(u[2], u[3]), n, c1)
-            gamma = g[r] * (1.0 + s3 * (2.0 * sm.u01(v[0], v[1]) - 1.0))
-            q = s.x[r] + gamma[:, None] * (pop[r][c1] - pop[r][c2])
+            props[r], inside[r] = sm.de_step(s.x[r], pop[r][c1], pop[r][c2], g[r], s3, sm.u01(v[0], v[1]), lower, upper)
             with np.errstate(divide="ignore"):
                 lnus[r] = log(sm.u01(v[2], v[3]))
-            props[r], inside[r] = q, np.all((q >= lower) & (q <= upper), axis=1)
         rows = np.concatenate([props[r][inside[r]] for r, _ in jobs])
         runs = np.concatenate([np.full(int(np.sum(inside[r])), r) for r, _ in jobs])
         if rows.shape[0] == 0:

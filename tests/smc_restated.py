@@ -14,6 +14,7 @@ import math
 import numpy as np
 
 from oracle.stretch_oracle import philox4x32_10
+from walk_restated import de_step
 
 M32 = 0xFFFFFFFF
 CTR = 0x534D0000
@@ -202,11 +203,9 @@ def moves(s, jobs, seed, walks, g0, s3, lower, upper, evaluate, log=np.log):
             u, v = draws(seed, t, r, slots, 2 * k + 1), draws(seed, t, r, slots, 2 * k + 2)
             c1 = pick(u01(u[0], u[1]), n)
             c2 = pick_skip(u01(u[2], u[3]), n, c1)
-            gamma = g0 * (1.0 + s3 * (2.0 * u01(v[0], v[1]) - 1.0))
-            q = cur[r] + gamma[:, None] * (pop[r][c1] - pop[r][c2])
+            props[r], inside[r] = de_step(cur[r], pop[r][c1], pop[r][c2], g0, s3, u01(v[0], v[1]), lower, upper)
             with np.errstate(divide="ignore"):
                 lnus[r] = log(u01(v[2], v[3]))
-            props[r], inside[r] = q, np.all((q >= lower) & (q <= upper), axis=1)
         rows = np.concatenate([props[r][inside[r]] for r, _ in jobs])
         runs = np.concatenate([np.full(int(np.sum(inside[r])), r) for r, _ in jobs])
         if rows.shape[0] == 0:

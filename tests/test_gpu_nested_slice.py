@@ -1,5 +1,6 @@
 """GPU tests of the nested sampler's slice mode (include/magprop_amd.h mp_nested_set_slice, NestedSampler(sample="slice")): the
-device state against the numpy restatement (tests/nest_slice_restated.py) bit for bit, chunk independence, slices = 0 as the
+device state against the numpy restatement (tests/nest_slice_restated.py) bit for bit, also under tight limits (zero budgets, the
+shrink cap) and with coinciding survivors, chunk independence, slices = 0 as the
 random walk, evidence against closed forms and brute force, posterior samples on Humped as it is (the case the random walk
 mixes poorly), a long Swift light curve through the LONG builds, and refused arguments."""
 import ctypes as C
@@ -11,6 +12,7 @@ import pytest
 
 import nest_restated as nr
 import nest_slice_restated as sr
+import test_nested_slice_cpu as edge
 from conftest import TRUTHS, TYPES
 from raw_abi import lp, synth_handle
 from test_gpu_nested import (EVIDENCE_INFLATION, RawNested, _assert_equal, _gaussian_lnz, drive_posterior, long_sets,  # noqa: F401
@@ -63,6 +65,41 @@ def test_slice_state_matches_the_restatement_bit_for_bit(n_runs):
     _assert_slice_equal(st, s)
     assert np.all(st["stopped"] == 1) and np.all(st["nit"] > 6) and np.all(st["nexpand"] > 0) and np.all(st["ncontract"] > 0)
     print(f"stop iterations {st['nit'].tolist()}, ln Z {st['lnz'].tolist()}, nfail {st['nfail'].tolist()}")
+
+
+def _device_edge_run(live0, nlive, iterations, slices, mu, steps_out, shrink, dlogz):
+    """One run on the unit Gaussian in the box of the edge cases of tests/test_nested_slice_cpu.py: the device state behind
+    `iterations` iterations of slice mode."""
+    h = synth_handle()
+    ns = RawNested(h, nlive, 8, 1, 3, edge.EDGE_LO, edge.EDGE_HI, edge.EDGE_SEED, 25, 1, dlogz=dlogz)
+    try:
+        assert _set_slice(ns, slices, mu, steps_out, shrink) == 0
+        ns.set_live(live0.reshape(-1, 3))
+        ns.run(iterations)
+        return _state(ns)
+    finally:
+        ns.close()
+        h.close()
+
+
+@pytest.mark.parametrize("limits", sorted(edge.TIGHT))
+def test_tight_limits_match_the_restatement_bit_for_bit(limits):
+    """N = 32, K = 8, 3 slices, 6 iterations under max_steps_out = 1 (both budgets 0) and a shrink cap of 2 (mu = 0.05) or 1
+    (mu = 5): slices that fail at the cap and shrink points outside the box, the paths the CPU twin
+    (test_nested_slice_cpu.py::test_tight_limits_take_the_slices_to_zero_budgets_and_the_shrink_cap) asserts on the restated run."""
+    live0, s = edge.tight_run(limits)
+    st = _device_edge_run(live0, 32, 6, 3, limits[2], limits[0], limits[1], 0.05)
+    _assert_slice_equal(st, s)
+    assert (int(st["nexpand"][0]), int(st["ncontract"][0]), int(st["nfail"][0])) == edge.TIGHT[limits]
+
+
+def test_coinciding_survivors_match_the_restatement_bit_for_bit():
+    """N = 16 (MP_NEST_MIN_LIVE), K = 8, 3 slices, limits 4 / 8, 2 iterations, the eight highest-lnL points of the start set at
+    one position: every direction is zero, no point is evaluated and all 48 slices fail where they start."""
+    live0, s = edge.coinciding_run()
+    st = _device_edge_run(live0, 16, 2, 3, 1.0, 4, 8, 1e-9)
+    _assert_slice_equal(st, s)
+    assert st["nfail"][0] == 48 and st["ncall"][0] == 0 and st["nzero"][0] == 16 and st["stopped"][0] == 0
 
 
 def test_slice_chunks_of_one_iteration_equal_one_unsplit_run():

@@ -2,6 +2,7 @@
 walk (tests/nest_slice_restated.py) leaves the constrained prior invariant and a broken rule does not, a restated run finds
 the Gaussian evidence, ties and coinciding survivors behave as the header states, and the front end checks its arguments
 before any device is touched."""
+import functools
 import math
 import os
 import re
@@ -141,6 +142,65 @@ def test_the_round_driver_calls_evaluate_once_per_round_of_the_longest_slice_wal
     assert len(rec.calls) == evals.max() and evals.min() < evals.max()
     for k, (rows, rr) in enumerate(rec.calls):
         assert len(rows) == np.sum(evals > k) and rr.tolist() == [runs[i] for i in np.nonzero(evals > k)[0]]
+
+
+# ---------------------------------------------------------------- the edge paths of the slice state machine in slice mode
+# One run on the unit Gaussian in the box EDGE_LO, EDGE_HI, seed EDGE_SEED, the live set from default_rng(18); the GPU tests
+# (tests/test_gpu_nested_slice.py) hold the device to the same restated runs bit for bit.
+EDGE_LO, EDGE_HI, EDGE_SEED = np.array([-2.0, -1.0, -4.0]), np.array([3.0, 2.5, 1.5]), 20261201
+# (max_steps_out, max_shrink, mu) -> (nexpand, ncontract, nfail) over 6 iterations of N = 32, K = 8, 3 slices
+TIGHT = {(1, 2, 0.05): (0, 7, 3), (1, 1, 5.0): (0, 103, 103)}
+
+
+def edge_live(nlive):
+    return EDGE_LO + (EDGE_HI - EDGE_LO) * np.random.default_rng(18).random((1, nlive, 3))
+
+
+@functools.lru_cache(maxsize=None)
+def tight_run(limits):
+    """(live0, the restated state behind 6 iterations) under the tight limits `limits`; computed once, not to be changed."""
+    live0 = edge_live(32)
+    s = sr.start(live0, nr.gaussian)
+    sr.run(s, 6, 8, EDGE_SEED, 3, mu=limits[2], max_steps_out=limits[0], max_shrink=limits[1], dlogz=0.05, lower=EDGE_LO,
+           upper=EDGE_HI, evaluate_one=nr.gaussian_one)
+    return live0, s
+
+
+@functools.lru_cache(maxsize=None)
+def coinciding_run():
+    """(live0, the restated state behind 2 iterations) of N = 16, K = 8, 3 slices, limits 4 / 8, dlogz = 1e-9, where the eight
+    highest-lnL points of the start set (the survivors of the first iteration) lie at one position."""
+    live0 = edge_live(16)
+    top = np.argsort(nr.gaussian(live0[0])[0])[8:]
+    live0[0, top] = live0[0, top[-1]]
+    s = sr.start(live0, nr.gaussian)
+    sr.run(s, 2, 8, EDGE_SEED, 3, mu=1.0, max_steps_out=4, max_shrink=8, dlogz=1e-9, lower=EDGE_LO, upper=EDGE_HI,
+           evaluate_one=nr.gaussian_one)
+    return live0, s
+
+
+@pytest.mark.parametrize("limits", sorted(TIGHT))
+def test_tight_limits_take_the_slices_to_zero_budgets_and_the_shrink_cap(limits):
+    """max_steps_out = 1 leaves both budgets 0: no slice steps out, every evaluation is a shrink point.  mu = 0.05 with 2 shrink
+    points: a few slices fail at the cap.  mu = 5 with one shrink point: a slice moves at its first shrink point or fails at the
+    cap behind exactly one contraction, most of them on points outside the box, which are not evaluated."""
+    _, s = tight_run(limits)
+    assert (int(s.nexpand[0]), int(s.ncontract[0]), int(s.nfail[0])) == TIGHT[limits]
+    assert s.nit[0] == 6 and not s.stopped[0] and s.nacc[0] + s.nfail[0] == 3 * 8 * 6 and s.nfail[0] > 0
+    assert s.ncall[0] <= s.nacc[0] + s.ncontract[0]            # nothing but shrink points was evaluated
+    if limits[1] == 1:
+        assert s.ncontract[0] == s.nfail[0] and s.ncall[0] < s.nacc[0] + s.ncontract[0]
+    else:
+        assert s.nfail[0] * limits[1] <= s.ncontract[0]
+
+
+def test_coinciding_survivors_fail_every_slice_without_an_evaluation():
+    """Every direction is zero: no point is evaluated, every slice fails where it starts, every walk ends at the survivor it
+    started from, and the run is not stopped."""
+    live0, s = coinciding_run()
+    assert s.nfail[0] == 48 and s.ncall[0] == 0 and s.nzero[0] == 16 and s.nacc[0] == 0
+    assert s.nexpand[0] == 0 and s.ncontract[0] == 0 and s.nit[0] == 2 and not s.stopped[0]
+    assert np.all(s.live[0] == live0[0, np.argmax(nr.gaussian(live0[0])[0])])
 
 
 @pytest.mark.parametrize("kw, match", [
