@@ -538,6 +538,43 @@ int mp_sampler_set_temperatures(mp_sampler *s, int n_temps, const double *betas)
  * each pair is proposed n_walkers times per step.  MP_ESTATE on an untempered sampler. */
 int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted);
 /*
+ * Ladder adaptation (ABI 5, additive; the dynamics of Vousden, Farr & Mandel 2016, ptemcee's, carried from differences of T to
+ * the gaps of ln beta).  While it adapts, every group spaces its own ladder on the device until each neighbouring pair swaps
+ * equally often.  Both ends stay as set: beta_0 = 1, and the hot end beta_{T-1}, which the evidence estimate relies on, are never
+ * written.  A sampler without this call, and an untempered one, launch what they launched before.
+ * State per group of T = n_temps >= 3 ensembles: the gaps g_i = ln beta_i - ln beta_{i+1} > 0 (i = 0 .. T - 2) and their sum
+ * L = -ln beta_{T-1}.  This call forms them once on the device: lb_i = log(beta_i) with lb_0 = 0, g_i = lb_i - lb_{i+1},
+ * L = -lb_{T-1}, and prev_i = the pair's accepted swaps so far.
+ * Update t = 0, 1, .. n_adapt - 1: one launch behind the swap sweep of each of the first n_adapt steps of mp_sampler_run (t is the
+ * sampler's: it counts on across calls, whatever their lengths).  With kappa_t = lag / (time * (t + lag)), formed on the host in
+ * double by these three operations, per group and in double, every operation rounded on its own (no FMA):
+ *     A_i   = (double)(swaps_i - prev_i) / (double)n_walkers;  prev_i = swaps_i       the step's acceptance of pair (i, i + 1)
+ *     Abar  = (A_0 + A_1 + ... in index order from 0.0) / (double)(T - 1)
+ *     h_i   = g_i * exp(kappa_t * (A_i - Abar))
+ *     G     = h_0 + h_1 + ... in index order from 0.0;  c = L / G;  g'_i = c * h_i
+ *     cum_i = g'_0 + ... + g'_i in index order from 0.0;  beta_{i+1} = exp(-cum_i), i = 0 .. T - 3
+ * exp and log are the device runtime's.  A pair that swapped more often than the mean gets a wider gap; the fixed points are the
+ * ladders on which every pair is accepted equally often.  The update is taken only if every g'_i is finite and > 0 and the new
+ * ladder, both ends included, is strictly decreasing; otherwise g and the ladder stay as they were and the group's count of
+ * dropped updates goes up (prev advances either way).  mp_sampler_get_swaps keeps its meaning.
+ * Order: a step's moves and its swap sweep read the ladder of the previous update; the new one holds from the next step on.
+ * Validity: kappa_t -> 0 (diminishing adaptation), and after update n_adapt - 1 the ladder is frozen for good: steps >= n_adapt
+ * are the steps of a fixed-ladder sampler and enqueue no ladder launch.  Use only those steps for estimates (mp_sampler_get_thermo
+ * passes over the others by itself).  ptemcee's defaults: lag = 10000, time = 100.
+ * mp_sampler_set_ladder_adaptation: after mp_sampler_set_temperatures and before the first mp_sampler_set_positions, else
+ * MP_ESTATE.  MP_EINVAL: n_temps < 3, n_adapt < 1, lag or time not finite and > 0, or keep_history with n_adapt x n_ensembles
+ * doubles beyond MP_LADDER_MAX_HISTORY_BYTES.  keep_history != 0: row t of a device buffer receives the ladders after update t.
+ * mp_sampler_get_temperatures: betas[n_ensembles], the ladders now, one per group (groups adapt independently); *n_updates, the
+ * updates made so far; n_dropped[n_ensembles / n_temps].  On a fixed ladder: the ladder as set, 0 and zeros.  Any output may be
+ * NULL.  MP_ESTATE on an untempered sampler.
+ * mp_sampler_get_ladder_history: rows [first_row, first_row + max_rows) of group `group`, as far as they exist, into
+ * betas[rows][n_temps]; *n_rows: the rows written.  MP_ESTATE without a history, MP_EINVAL on a bad group or range.
+ */
+#define MP_LADDER_MAX_HISTORY_BYTES 268435456   /* 256 MB */
+int mp_sampler_set_ladder_adaptation(mp_sampler *s, int64_t n_adapt, double lag, double time, int keep_history);
+int mp_sampler_get_temperatures(mp_sampler *s, double *betas, int64_t *n_updates, int64_t *n_dropped);
+int mp_sampler_get_ladder_history(mp_sampler *s, int group, int64_t first_row, int64_t max_rows, double *betas, int64_t *n_rows);
+/*
  * Proposal moves (ABI 5, additive; emcee 3's moves=).  Every move is a red-blue move over the step's two-way split: walker k
  * of the active half draws its partners from the n_comp = n_walkers - n_half slots of the other half.  Random numbers are
  * Philox4x32-10 keyed (seed; step, half, k, c3): the stretch move uses c3 = 0, 1, DE and snooker c3 = 2 (r) and 3 (r2).
@@ -777,6 +814,25 @@ int mp_sampler_get_posterior_hist1(mp_sampler *s, int ensemble, int64_t *hist1, 
 int mp_sampler_get_posterior_hist2(mp_sampler *s, int ensemble, int64_t *hist2, int64_t *outside2);
 int mp_sampler_get_posterior_moments(mp_sampler *s, int ensemble, double *sum1, double *sum2, double *pivot, int64_t *n_finite);
 int mp_sampler_get_posterior_best(mp_sampler *s, int ensemble, double *x, double *lnprob, int64_t *index);
+
+/*
+ * Thermodynamic monitor (ABI 5, additive): per ensemble the sum of the stored, untempered lnprob over the monitored steps, which
+ * is all that thermodynamic integration over a ladder needs of a run, so that the evidence needs no chain on the host.  Off by
+ * default; fed like the two monitors above (once per chunk from the device slab's lnprob rows; mp_sampler_set_positions restarts
+ * it; the walker-sharded entry points return MP_ESTATE while it is on).
+ * A step is monitored if it lies `discard` or more steps behind the (re)start AND, on a sampler with ladder adaptation, is a step
+ * >= n_adapt: the steps on a ladder that still moved are passed over.  Per ensemble e and monitored step, in step order:
+ *     rowsum = the sum of the walkers' finite lnprob: thread k of 256 adds walkers k, k + 256, ... in increasing index from 0.0,
+ *              then the xor butterfly over distances 32 .. 1 inside each wavefront and the four wavefronts in order;
+ *     sum[e] = sum[e] + rowsum, one add per step;  n_finite[e], n_nonfinite[e]: the counts of the cells (-inf, +inf and NaN are
+ *              non-finite and enter no sum).
+ * So the numbers are a function of the samples alone, not of chunks or of how a run was split into calls.
+ * mp_sampler_set_thermo(s, discard): discard >= 0 (re)starts the monitor empty, discard = -1 turns it off; else MP_EINVAL.
+ * mp_sampler_get_thermo: sum_lnl, n_finite, n_nonfinite [n_ensembles], *n_steps the monitored steps; any output may be NULL;
+ * MP_ESTATE while the monitor is off.
+ */
+int mp_sampler_set_thermo(mp_sampler *s, int64_t discard);
+int mp_sampler_get_thermo(mp_sampler *s, double *sum_lnl, int64_t *n_finite, int64_t *n_nonfinite, int64_t *n_steps);
 
 /*
  * Differential-evolution optimizer (ABI 5, additive): scipy.optimize.differential_evolution with deferred updating, without

@@ -34,6 +34,7 @@ SMC_RUNNING, SMC_DONE, SMC_FAILED, SMC_STAGE_LIMIT = 0, 1, 2, 3
 MOVE_SLICE, SLICE_MAX_SHRINK = 4, 252                         # include/magprop_amd.h MP_MOVE_SLICE, MP_SLICE_MAX_SHRINK
 ACF_MAX_LAG, ACF_MAX_BYTES = 4096, 8 << 30                   # include/magprop_amd.h MP_ACF_*
 POST_MAX_BINS, POST_MAX_BINS2, POST_MAX_BYTES = 4096, 128, 1 << 30   # include/magprop_amd.h MP_POST_*
+LADDER_MAX_HISTORY_BYTES = 1 << 28                           # include/magprop_amd.h MP_LADDER_MAX_HISTORY_BYTES
 
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -92,6 +93,9 @@ SIGNATURES = {
     "mp_sampler_get_state": (_i, [_vp, _dp, _dp, _i64p, _i64p]),
     "mp_sampler_set_temperatures": (_i, [_vp, _i, _dp]),
     "mp_sampler_get_swaps": (_i, [_vp, _i64p]),
+    "mp_sampler_set_ladder_adaptation": (_i, [_vp, _i64, _d, _d, _i]),
+    "mp_sampler_get_temperatures": (_i, [_vp, _dp, _i64p, _i64p]),
+    "mp_sampler_get_ladder_history": (_i, [_vp, _i, _i64, _i64, _dp, _i64p]),
     "mp_sampler_set_moves": (_i, [_vp, _i, _ip, _dp, _dp]),
     "mp_sampler_set_slice_limits": (_i, [_vp, _i, _i]),
     "mp_sampler_get_slice": (_i, [_vp, _dp, _i64p, _i64p, _i64p, _i64p, _i64p]),
@@ -114,6 +118,8 @@ SIGNATURES = {
     "mp_sampler_get_posterior_hist2": (_i, [_vp, _i, _i64p, _i64p]),
     "mp_sampler_get_posterior_moments": (_i, [_vp, _i, _dp, _dp, _dp, _i64p]),
     "mp_sampler_get_posterior_best": (_i, [_vp, _i, _dp, _dp, _i64p]),
+    "mp_sampler_set_thermo": (_i, [_vp, _i64]),
+    "mp_sampler_get_thermo": (_i, [_vp, _dp, _i64p, _i64p, _i64p]),
     "mp_optimizer_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _i, _d, _d, _d, _d, _d, _dp, _dp, _i]),
     "mp_optimizer_set_population": (_i, [_vp, _dp]),
     "mp_optimizer_run": (_i, [_vp, _i, _ip]),

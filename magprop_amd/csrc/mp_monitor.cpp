@@ -1,5 +1,5 @@
-// mp_monitor.cpp — the host side of the sampler's autocorrelation and posterior monitors (mp_monitor.h).  Kernels: mp_acf.hip,
-// mp_post.hip.
+// mp_monitor.cpp — the host side of the sampler's autocorrelation, posterior and thermodynamic monitors (mp_monitor.h).  Kernels:
+// mp_acf.hip, mp_post.hip, thermo_kernel of mp_ladder.hip.
 #include "mp_monitor.h"
 
 // ---- autocorrelation monitor
@@ -245,4 +245,50 @@ int PostMonitor::read_moments(int ensemble, double *sum1, double *sum2, double *
 int PostMonitor::read_best(int ensemble, double *x, double *lnprob, int64_t *index) const {
     return read_back(x, (const double *)best_x.p + (size_t)ensemble * ndim, (size_t)ndim,
                      lnprob, (const double *)best_lnp.p + ensemble, (size_t)1, index, (const int64_t *)best_idx.p + ensemble, (size_t)1);
+}
+
+// ---- thermodynamic monitor
+int ThermoMonitor::off(const char *fn) { return fail(MP_ESTATE, "%s: the thermodynamic monitor is off (mp_sampler_set_thermo)", fn); }
+
+int ThermoMonitor::make(const char *fn, int n_walkers, int n_ensembles, int ndim, int64_t discard, size_t sampler_cap,
+                        std::unique_ptr<ThermoMonitor> *out) {
+    if (discard < 0) return fail(MP_EINVAL, "%s: discard must be >= 0 (-1 turns the monitor off), got %lld", fn, (long long)discard);
+    std::unique_ptr<ThermoMonitor> m(new ThermoMonitor(n_walkers, n_ensembles, ndim, discard));
+    m->chunk_cap = (int)m->capped(sampler_cap);
+    const size_t ne = (size_t)n_ensembles;
+    int rc;
+    if ((rc = m->sum.ensure(ne)) || (rc = m->n_finite.ensure(ne)) || (rc = m->n_nonfinite.ensure(ne))) return rc;
+    *out = std::move(m);
+    return MP_OK;
+}
+
+int ThermoMonitor::restart(hipStream_t st) {
+    const size_t ne = (size_t)n_ensembles;
+    const int rc = zero_async(st, sum.p, ne, n_finite.p, ne, n_nonfinite.p, ne);
+    if (rc) return rc;
+    start_over();
+    return MP_OK;
+}
+
+int ThermoMonitor::feed(const double *lnp, int chunk, int64_t step0, int64_t frozen_from, hipStream_t st) {
+    mp::ThermoArgs a{};
+    a.lnp = lnp; a.sum = sum.p; a.n_finite = n_finite.p; a.n_nonfinite = n_nonfinite.p;
+    a.n_walkers = n_walkers; a.n_ensembles = n_ensembles;
+    int first;
+    take(chunk, &first);
+    // (the steps before the freeze that lie behind the discard are passed over as well)
+    a.first = (int)std::min<int64_t>(chunk, std::max<int64_t>(first, frozen_from - step0));
+    a.rows = chunk - a.first;
+    if (a.rows == 0) return MP_OK;
+    const int rc = launched(mp::launch_thermo(a, st));
+    if (rc) return rc;
+    n += a.rows;
+    return MP_OK;
+}
+
+int ThermoMonitor::read(double *sum_out, int64_t *n_finite_out, int64_t *n_nonfinite_out, int64_t *n_steps) const {
+    const size_t ne = (size_t)n_ensembles;
+    if (n_steps) *n_steps = n;
+    return read_back(sum_out, (const double *)sum.p, ne, n_finite_out, (const int64_t *)n_finite.p, ne,
+                     n_nonfinite_out, (const int64_t *)n_nonfinite.p, ne);
 }

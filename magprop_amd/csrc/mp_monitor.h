@@ -1,5 +1,6 @@
-// mp_monitor.h — the two chain monitors of the ensemble sampler as a host unit of their own (mp_monitor.cpp): the autocorrelation
-// monitor (mp_sampler_set_autocorr; kernels mp_acf.hip) and the posterior monitor (mp_sampler_set_posterior; kernels mp_post.hip).
+// mp_monitor.h — the three chain monitors of the ensemble sampler as a host unit of their own (mp_monitor.cpp): the autocorrelation
+// monitor (mp_sampler_set_autocorr; kernels mp_acf.hip), the posterior monitor (mp_sampler_set_posterior; kernels mp_post.hip) and
+// the thermodynamic monitor (mp_sampler_set_thermo; thermo_kernel of mp_ladder.hip).
 //
 // Internal, like mp_host.h.  A monitor knows the shape of the chain, the device rows it is fed and a stream, and nothing of the
 // sampler: mp_sampler.cpp holds one of each behind its entry points, and the probe libraries mp_probe_acf.hip and
@@ -9,11 +10,12 @@
 
 #include "mp_acf.h"
 #include "mp_host.h"
+#include "mp_ladder.h"
 #include "mp_post.h"
 
 #pragma GCC visibility push(hidden)
 
-// What both monitors keep: the shape of the chain and the count of the steps that went in.
+// What every monitor keeps: the shape of the chain and the count of the steps that went in.
 struct ChainMonitor {
     int n_walkers = 0, n_ensembles = 0, n_total = 0, ndim = 0;
     int chunk_cap = 0;              // most steps per chunk of mp_sampler_run while the monitor is on
@@ -90,6 +92,26 @@ struct PostMonitor : ChainMonitor {
 
 private:
     mp::PostArgs args(const double *chain, const double *lnp) const;
+};
+
+// Per ensemble the sum of the finite stored lnprob and the counts of finite and non-finite cells (mp_ladder.h ThermoArgs), fed once
+// per chunk of mp_sampler_run from the device slab's lnprob rows: what thermodynamic integration needs of a run.
+struct ThermoMonitor : ChainMonitor {
+    DevBuf<double> sum;
+    DevBuf<int64_t> n_finite, n_nonfinite;
+    using ChainMonitor::ChainMonitor;
+
+    static int off(const char *fn);
+    // A monitor with its buffers, after the check of discard; restart() comes next
+    static int make(const char *fn, int n_walkers, int n_ensembles, int ndim, int64_t discard, size_t sampler_cap,
+                    std::unique_ptr<ThermoMonitor> *out);
+    // Empty the monitor (stream-ordered): no sample, `discard` steps from now.
+    int restart(hipStream_t st);
+    // The rows lnp[chunk][n_total] of a chunk whose first row is step `step0` into the monitor (stream-ordered): those behind the
+    // steps still to be passed over, and of them the steps >= frozen_from (the first step on the ladder's final state)
+    int feed(const double *lnp, int chunk, int64_t step0, int64_t frozen_from, hipStream_t st);
+    // read-out behind mp_sampler_get_thermo (after a wait for the stream)
+    int read(double *sum_out, int64_t *n_finite_out, int64_t *n_nonfinite_out, int64_t *n_steps) const;
 };
 
 #pragma GCC visibility pop

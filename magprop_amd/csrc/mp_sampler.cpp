@@ -1,5 +1,6 @@
-// mp_sampler.cpp — the device-resident ensemble sampler (mp_sampler_*): stretch, DE, snooker, KDE and slice moves, tempering,
-// whole-step and walker-sharded driving.  Kernels: mp_kernels.hip, and mp_slice.hip for the slice move.
+// mp_sampler.cpp — the device-resident ensemble sampler (mp_sampler_*): stretch, DE, snooker, KDE and slice moves, tempering with
+// a fixed or an adapting ladder, whole-step and walker-sharded driving.  Kernels: mp_kernels.hip, mp_slice.hip for the slice move
+// and mp_ladder.hip for the ladder's updates.
 #include <memory>
 #include <thread>
 
@@ -52,7 +53,26 @@ struct mp_sampler {
     static constexpr int kSliceCnt = 7;
     std::unique_ptr<AcfMonitor> acf;   // the autocorrelation monitor; null: off
     std::unique_ptr<PostMonitor> post; // the posterior monitor; null: off
+    std::unique_ptr<ThermoMonitor> thermo;   // the thermodynamic monitor; null: off
+    // ladder adaptation (mp_sampler_set_ladder_adaptation; kernels mp_ladder.hip); n_adapt = 0: off, a fixed ladder.  Every step of
+    // mp_sampler_run makes one update while ladder_t < n_adapt: update t lies behind step t, so steps >= n_adapt run on the frozen
+    // ladder
+    int64_t n_adapt = 0, ladder_t = 0;
+    double ladder_lag = 0.0, ladder_time = 0.0;
+    bool ladder_history = false;
+    DevBuf<double> d_gap, d_span, d_ladder_work, d_ladder_hist;
+    DevBuf<int64_t> d_swaps_prev, d_ladder_dropped;
 };
+
+// the launch arguments of the ladder kernels over the sampler's buffers
+static mp::LadderArgs ladder_args(const mp_sampler *s) {
+    mp::LadderArgs a{};
+    a.beta = s->d_beta.p; a.gap = s->d_gap.p; a.span = s->d_span.p; a.prev = s->d_swaps_prev.p; a.swaps = s->d_swaps.p;
+    a.dropped = s->d_ladder_dropped.p; a.work = s->d_ladder_work.p;
+    a.history = s->ladder_history ? s->d_ladder_hist.p : nullptr;
+    a.n_temps = s->n_temps; a.n_groups = s->n_ensembles / s->n_temps; a.n_walkers = s->n_walkers;
+    return a;
+}
 
 // Steps per chunk of mp_sampler_run when chain rows go to the device slab: the slab stays below ~256 MB
 static size_t slab_chunk_cap(const mp_sampler *s, size_t perm_cap) {
@@ -227,6 +247,65 @@ int mp_sampler_set_temperatures(mp_sampler *s, int n_temps, const double *betas)
     HIP_TRY(hipMemcpy(s->d_beta.p, b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(s->d_swaps.p, 0, n_pairs * sizeof(int64_t)));
     s->n_temps = n_temps;
+    s->n_adapt = 0;   // a new ladder is a fixed one until mp_sampler_set_ladder_adaptation says otherwise
+    s->ladder_t = 0;
+    return MP_OK;
+}
+
+int mp_sampler_set_ladder_adaptation(mp_sampler *s, int64_t n_adapt, double lag, double time, int keep_history) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_set_ladder_adaptation: NULL sampler");
+    Held held(s->h, s->ev);
+    if (!s->n_temps) return fail(MP_ESTATE, "mp_sampler_set_ladder_adaptation: call mp_sampler_set_temperatures first");
+    if (s->have_state) return fail(MP_ESTATE, "mp_sampler_set_ladder_adaptation: call it before the first mp_sampler_set_positions");
+    if (s->n_temps < 3) return fail(MP_EINVAL, "mp_sampler_set_ladder_adaptation: both ends of the ladder stay fixed, so it needs at least 3 temperatures, got %d", s->n_temps);
+    if (n_adapt < 1) return fail(MP_EINVAL, "mp_sampler_set_ladder_adaptation: n_adapt must be >= 1, got %lld", (long long)n_adapt);
+    if (!std::isfinite(lag) || !(lag > 0.0) || !std::isfinite(time) || !(time > 0.0))
+        return fail(MP_EINVAL, "mp_sampler_set_ladder_adaptation: lag and time must be finite and > 0, got %g and %g", lag, time);
+    if (keep_history && (double)n_adapt * (double)s->n_ensembles * sizeof(double) > (double)MP_LADDER_MAX_HISTORY_BYTES)
+        return fail(MP_EINVAL, "mp_sampler_set_ladder_adaptation: the history of %lld updates of %d ensembles is larger than MP_LADDER_MAX_HISTORY_BYTES = %lld",
+                    (long long)n_adapt, s->n_ensembles, (long long)MP_LADDER_MAX_HISTORY_BYTES);
+    const size_t n_groups = (size_t)(s->n_ensembles / s->n_temps), n_pairs = n_groups * (size_t)(s->n_temps - 1);
+    int rc;
+    if ((rc = s->d_gap.ensure(n_pairs)) || (rc = s->d_span.ensure(n_groups)) || (rc = s->d_ladder_work.ensure(2 * n_pairs)) ||
+        (rc = s->d_swaps_prev.ensure(n_pairs)) || (rc = s->d_ladder_dropped.ensure(n_groups)) ||
+        (keep_history && (rc = s->d_ladder_hist.ensure((size_t)n_adapt * (size_t)s->n_ensembles))))
+        return rc;
+    s->ladder_history = keep_history != 0;
+    HIP_TRY(hipMemsetAsync(s->d_ladder_dropped.p, 0, n_groups * sizeof(int64_t), s->ev->stream));
+    if ((rc = launched(mp::launch_ladder_init(ladder_args(s), s->ev->stream)))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->ev->stream));
+    s->n_adapt = n_adapt; s->ladder_t = 0; s->ladder_lag = lag; s->ladder_time = time;
+    return MP_OK;
+}
+
+int mp_sampler_get_temperatures(mp_sampler *s, double *betas, int64_t *n_updates, int64_t *n_dropped) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_temperatures: NULL sampler");
+    Held held(s->h, s->ev);
+    if (!s->n_temps) return fail(MP_ESTATE, "mp_sampler_get_temperatures: the sampler is not tempered (mp_sampler_set_temperatures)");
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t n_groups = (size_t)(s->n_ensembles / s->n_temps);
+    if (n_updates) *n_updates = s->ladder_t;
+    if (!s->n_adapt) {
+        if (n_dropped) std::fill(n_dropped, n_dropped + n_groups, (int64_t)0);
+        return read_back(betas, (const double *)s->d_beta.p, (size_t)s->n_ensembles);
+    }
+    return read_back(betas, (const double *)s->d_beta.p, (size_t)s->n_ensembles, n_dropped, (const int64_t *)s->d_ladder_dropped.p, n_groups);
+}
+
+int mp_sampler_get_ladder_history(mp_sampler *s, int group, int64_t first_row, int64_t max_rows, double *betas, int64_t *n_rows) {
+    if (!s || first_row < 0 || max_rows < 0 || (max_rows > 0 && !betas)) return fail(MP_EINVAL, "mp_sampler_get_ladder_history: bad argument");
+    Held held(s->h, s->ev);
+    if (!s->n_adapt || !s->ladder_history)
+        return fail(MP_ESTATE, "mp_sampler_get_ladder_history: the sampler keeps no ladder history (mp_sampler_set_ladder_adaptation)");
+    const int n_groups = s->n_ensembles / s->n_temps;
+    if (group < 0 || group >= n_groups) return fail(MP_EINVAL, "mp_sampler_get_ladder_history: group must be in [0, %d), got %d", n_groups, group);
+    HIP_TRY(hipDeviceSynchronize());
+    const int64_t rows = std::max<int64_t>(0, std::min<int64_t>(s->ladder_t - first_row, max_rows));
+    const size_t w = (size_t)s->n_temps * sizeof(double), pitch = (size_t)s->n_ensembles * sizeof(double);
+    if (rows)
+        HIP_TRY(hipMemcpy2D(betas, w, s->d_ladder_hist.p + (size_t)first_row * s->n_ensembles + (size_t)group * s->n_temps, pitch, w,
+                            (size_t)rows, hipMemcpyDeviceToHost));
+    if (n_rows) *n_rows = rows;
     return MP_OK;
 }
 
@@ -368,13 +447,14 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
     int rc = MP_OK;
     if (s->acf) rc = s->acf->restart(ev->stream);     // the series is broken
     if (!rc && s->post) rc = s->post->restart(ev->stream);
+    if (!rc && s->thermo) rc = s->thermo->restart(ev->stream);
     return rc;
 }
 
 // Enqueue step steps_done + row of mp_sampler_run on the handle's stream: split d_perm, chain row `row` of the device slab when
 // chain is set, move mv (nullptr: the stretch move of mp_sampler_create).  A whole step per launch (stretch_step_kernel and the
 // commit kernel) where `whole` and the move is the stretch move, else two half-step launches (the slice move: of slice_half_kernel,
-// with the tune launch behind them); then the swap sweep when tempered.  fits: a whole step of this sampler fits one launch
+// with the tune launch behind them); then the swap sweep when tempered, and behind it the ladder's update while it adapts.  fits: a whole step of this sampler fits one launch
 // (`whole` is that and mp_sampler_set_whole_step).
 static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_sampler::Move *mv, bool chain, bool whole, bool fits) {
     Evaluator *ev = s->ev;
@@ -411,6 +491,13 @@ static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_
         if (!e) e = mp::launch_stretch(ev->sh, g, n_slots, variant_blocks, ev->stream);
     }
     if (!e && s->n_temps) e = mp::launch_stretch_swap(g, s->n_temps, s->d_swaps.p, ev->stream);
+    if (!e && s->ladder_t < s->n_adapt) {   // the ladder's update t behind the sweep: the next step reads the new ladder
+        mp::LadderArgs la = ladder_args(s);
+        la.t = s->ladder_t;
+        la.kappa = s->ladder_lag / (s->ladder_time * ((double)s->ladder_t + s->ladder_lag));
+        e = mp::launch_ladder_adapt(la, ev->stream);
+        if (!e) s->ladder_t += 1;
+    }
     if (e) return launched(e);
     return MP_OK;
 }
@@ -425,11 +512,12 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
     // chunks of steps so that the device-resident chain slab stays below ~256 MB, the splits below ~64 MB, and the
     // window of failed proposals (drained after every chunk) overflows only if more than 1 in 32 proposals fails
     const size_t perm_cap = perm_chunk_cap(s);
-    const bool monitor = s->acf != nullptr, post = s->post != nullptr;
-    const bool slab = chain || monitor || post;   // the monitors read the chain rows from the device slab
+    const bool monitor = s->acf != nullptr, post = s->post != nullptr, thermo = s->thermo != nullptr;
+    const bool slab = chain || monitor || post || thermo;   // the monitors read the chain rows from the device slab
     int chunk_max = (int)std::min<size_t>((size_t)std::max(n_steps, 1), slab ? slab_chunk_cap(s, perm_cap) : perm_cap);
     if (monitor) chunk_max = std::min(chunk_max, s->acf->chunk_cap);
     if (post) chunk_max = std::min(chunk_max, s->post->chunk_cap);
+    if (thermo) chunk_max = std::min(chunk_max, s->thermo->chunk_cap);
     constexpr int kSub = 8;   // steps per batch of splits: the host draws the next batch while the GPU runs this one
     int rc;
     // A whole step per launch (mp_kernels.hip stretch_step_kernel: 3 n/2 evaluations, a third of them speculative) while
@@ -464,6 +552,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
         }
         if (monitor && (rc = s->acf->feed(s->d_chain.p, chunk, ev->stream))) return rc;
         if (post && (rc = s->post->feed(s->d_chain.p, s->d_chain_lnp.p, chunk, ev->stream))) return rc;
+        if (thermo && (rc = s->thermo->feed(s->d_chain_lnp.p, chunk, (int64_t)s->steps_done, s->n_adapt, ev->stream))) return rc;
         if (chain) {
             HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
             HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
@@ -569,6 +658,28 @@ int mp_sampler_get_posterior_best(mp_sampler *s, int ensemble, double *x, double
     return rc ? rc : s->post->read_best(ensemble, x, lnprob, index);
 }
 
+// ---- thermodynamic monitor (mp_monitor.h ThermoMonitor)
+int mp_sampler_set_thermo(mp_sampler *s, int64_t discard) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_set_thermo: NULL sampler");
+    Held held(s->h, s->ev);
+    HIP_TRY(hipDeviceSynchronize());
+    s->thermo.reset();
+    if (discard == -1) return MP_OK;
+    int rc = ThermoMonitor::make("mp_sampler_set_thermo", s->n_walkers, s->n_ensembles, s->ndim, discard,
+                                 slab_chunk_cap(s, perm_chunk_cap(s)), &s->thermo);
+    if (rc) return rc;
+    if ((rc = s->thermo->restart(s->ev->stream))) s->thermo.reset();
+    return rc;
+}
+
+int mp_sampler_get_thermo(mp_sampler *s, double *sum_lnl, int64_t *n_finite, int64_t *n_nonfinite, int64_t *n_steps) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_thermo: NULL sampler");
+    Held held(s->h, s->ev);
+    if (!s->thermo) return ThermoMonitor::off("mp_sampler_get_thermo");
+    HIP_TRY(hipStreamSynchronize(s->ev->stream));
+    return s->thermo->read(sum_lnl, n_finite, n_nonfinite, n_steps);
+}
+
 int mp_sampler_set_whole_step(mp_sampler *s, int enable) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_set_whole_step: NULL sampler");
     Lock lock(s->h->mu);
@@ -618,6 +729,8 @@ struct ShardCall {
             rc = fail(MP_ESTATE, "%s: the autocorrelation monitor (mp_sampler_set_autocorr) is fed by mp_sampler_run only; turn it off first", fn);
         else if (s->post)
             rc = fail(MP_ESTATE, "%s: the posterior monitor (mp_sampler_set_posterior) is fed by mp_sampler_run only; turn it off first", fn);
+        else if (s->thermo)
+            rc = fail(MP_ESTATE, "%s: the thermodynamic monitor (mp_sampler_set_thermo) is fed by mp_sampler_run only; turn it off first", fn);
         else if (!(rc = current_split(s, (hipStream_t)stream, &d_perm))) s->ext_stream_work = true;
     }
 };

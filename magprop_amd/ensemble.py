@@ -25,7 +25,7 @@ from . import moves as _moves
 class EnsembleSampler:
     def __init__(self, nwalkers, ndim=6, x=None, y=None, yerr=None, variant="synth", GRBtype=None, seed=0, a=2.0,
                  datasets=None, lower="default", upper="default", log_mask=None, device=-1, target="posterior",
-                 fbad=None, sweep_tol=None, max_stride=None, whole_step=True, betas=None, moves=None):
+                 fbad=None, sweep_tol=None, max_stride=None, whole_step=True, betas=None, moves=None, adapt_ladder=None):
         """One ensemble on dataset (x, y, yerr), or one ensemble per entry of `datasets` = [(x, y, yerr), ...].
         whole_step: small ensembles run a whole step per launch (include/magprop_amd.h mp_sampler_set_whole_step; same
         chain bit for bit as one launch per half-step, which False selects).
@@ -37,7 +37,12 @@ class EnsembleSampler:
         moves: None (the stretch move with scale a, as emcee), or emcee's moves= forms over magprop_amd.moves (StretchMove,
         DEMove, DESnookerMove, KDEMove, SliceMove): a move, a list of moves, or a list of (move, weight); one move is drawn per step
         (include/magprop_amd.h mp_sampler_set_moves).  Give the stretch scale as StretchMove(a) then: moves together with a
-        non-default a is refused."""
+        non-default a is refused.
+        adapt_ladder: None (the ladder stays as given), or the number of steps over which every group spaces its own ladder on
+        the device until its neighbouring pairs swap equally often, both ends fixed (include/magprop_amd.h
+        mp_sampler_set_ladder_adaptation), or a dict {"steps", "lag", "time", "history"} (ptemcee's lag = 10000, time = 100;
+        history=True keeps the ladder after every update for ladder_history()).  Needs betas= with 3 or more temperatures.  The
+        ladder is frozen from step ladder_frozen_at on; estimates belong to those steps (log_evidence refuses earlier ones)."""
         if nwalkers % 2 or nwalkers < 2:
             raise ValueError("nwalkers must be even")            # emcee requires an even number too
         move_tab = None
@@ -71,6 +76,14 @@ class EnsembleSampler:
                                float(a), self._target)
         if self.betas is not None:
             _capi.check(self._L.mp_sampler_set_temperatures(self._s, self.ntemps, _capi.ptr(self.betas)), "mp_sampler_set_temperatures")
+        self._adapt = None              # (steps, lag, time, history) of the ladder adaptation; None: a fixed ladder
+        if adapt_ladder is not None:
+            if self.betas is None:
+                raise ValueError("adapt_ladder needs a tempered sampler (betas=...)")
+            self._adapt = tempering.adaptation_settings(adapt_ladder)
+            steps, lag, time, history = self._adapt
+            _capi.check(self._L.mp_sampler_set_ladder_adaptation(self._s, steps, lag, time, int(history)),
+                        "mp_sampler_set_ladder_adaptation")
         _capi.check(self._L.mp_sampler_set_whole_step(self._s, int(bool(whole_step))), "mp_sampler_set_whole_step")
         self.moves = None if moves is None else _moves.parse_moves(moves)
         if move_tab is not None:
@@ -85,6 +98,8 @@ class EnsembleSampler:
         self.seed = int(seed)
         self._chain = None
         self._lnp = None
+        self._steps = np.empty(0, dtype=np.int64)   # the step index of every stored row
+        self._thermo = False        # the device thermodynamic monitor is on
         self.iteration = 0
         self.fbad = fbad
         self._bad_written = 0
@@ -120,6 +135,7 @@ class EnsembleSampler:
         if store and nsteps > 0:
             self._chain = chain if self._chain is None else np.concatenate([self._chain, chain])
             self._lnp = lnp if self._lnp is None else np.concatenate([self._lnp, lnp])
+            self._steps = np.concatenate([self._steps, self.iteration + np.arange(int(nsteps), dtype=np.int64)])
         self.iteration += int(nsteps)
         self._flush_fbad()
         return self.get_last_sample()[0]
@@ -254,24 +270,95 @@ class EnsembleSampler:
         return _capi.read_back(self._L.mp_sampler_get_slice, self._s, [("mu", n, np.float64)] + [
             (k, n, np.int64) for k in ("nexpand", "ncontract", "nfail", "neval", "n_tuned")])
 
-    def log_evidence(self, discard=0, group=0, prior_draws=2 ** 20):
+    # ---- the ladder as the device holds it (include/magprop_amd.h mp_sampler_set_ladder_adaptation)
+    @property
+    def ladder_frozen_at(self):
+        """The index of the first step that runs on the frozen ladder (the adaptive steps); None on a fixed ladder."""
+        return None if self._adapt is None else self._adapt[0]
+
+    def _temperatures(self):
+        if self.betas is None:
+            raise ValueError("the sampler is not tempered (betas=...)")
+        return _capi.read_back(self._L.mp_sampler_get_temperatures, self._s, [
+            ("betas", (self.ngroups, self.ntemps), np.float64), ("n_updates", (), np.int64), ("n_dropped", self.ngroups, np.int64)])
+
+    def get_betas(self):
+        """(ngroups, T): every group's ladder as the device holds it now.  On a fixed ladder: the ladder as given, per group."""
+        return self._temperatures()["betas"]
+
+    @property
+    def ladder_updates(self):
+        """(updates made so far, (ngroups,) updates that were not taken because they would have left no valid ladder)."""
+        t = self._temperatures()
+        return int(t["n_updates"]), t["n_dropped"]
+
+    def ladder_history(self, group=0):
+        """(updates so far, T): row t is group `group`'s ladder after update t (adapt_ladder={..., "history": True})."""
+        if self._adapt is None or not self._adapt[3]:
+            raise ValueError("ladder_history needs adapt_ladder={..., 'history': True}")
+        rows = max(min(self.iteration, self._adapt[0]), 1)
+        buf, n = np.empty((rows, self.ntemps)), C.c_int64(0)
+        _capi.check(self._L.mp_sampler_get_ladder_history(self._s, int(group), 0, rows, _capi.ptr(buf), C.byref(n)),
+                    "mp_sampler_get_ladder_history")
+        return buf[:n.value]
+
+    # ---- the device thermodynamic monitor (include/magprop_amd.h mp_sampler_set_thermo states the definition)
+    def monitor_thermo(self, discard=0):
+        """Turn the thermodynamic monitor on (empty, accumulating from `discard` steps from now on, and on an adaptive sampler
+        only over the steps on the frozen ladder), or off with discard=None: per ensemble the sum of lnL, which is what
+        log_evidence(device=True) needs of a run, so that no chain has to reach the host.  While it is on, set_positions
+        (run_mcmc with pos) restarts it."""
+        _capi.check(self._L.mp_sampler_set_thermo(self._s, -1 if discard is None else int(discard)), "mp_sampler_set_thermo")
+        self._thermo = discard is not None
+
+    def get_thermo(self):
+        """The monitor's sums: {"sum_lnl", "n_finite", "n_nonfinite": (ngroups, T), "n_steps": monitored steps}."""
+        if not self._thermo:
+            raise _capi.MagpropAmdError("the thermodynamic monitor is off (monitor_thermo)")
+        shape = (self.ngroups, self.ntemps)
+        out = _capi.read_back(self._L.mp_sampler_get_thermo, self._s, [
+            ("sum_lnl", shape, np.float64), ("n_finite", shape, np.int64), ("n_nonfinite", shape, np.int64), ("n_steps", (), np.int64)])
+        out["n_steps"] = int(out["n_steps"])
+        return out
+
+    def log_evidence(self, discard=0, group=0, prior_draws=2 ** 20, device=False):
         """(lnZ, dlnZ) of group `group`'s dataset, the prior normalised over its box, from the stored chain of a tempered run:
         thermodynamic integration of the per-temperature mean lnL over steps[discard:] (magprop_amd.tempering) plus
         ln f_valid, the fraction of `prior_draws` uniform box draws (numpy generator seeded by the sampler seed, evaluated on
         this sampler's handle) whose lnprob is finite.  dlnZ = |TI - TI over every other temperature| in quadrature with the
-        binomial error of ln f_valid.  target="gaussian" has no prior box: lnZ is the integral alone."""
+        binomial error of ln f_valid.  target="gaussian" has no prior box: lnZ is the integral alone.
+        With adapt_ladder= the integral runs over the group's frozen ladder (get_betas), and steps[discard:] must all lie on it:
+        a step before ladder_frozen_at raises ValueError.
+        device=True takes the per-temperature means from the thermodynamic monitor (monitor_thermo) instead of the stored
+        chain, so a store=False run has an evidence; discard is the monitor's then.  It raises while the monitor is off or
+        empty and where a mean is not finite."""
         if self.betas is None:
             raise ValueError("log_evidence needs a tempered sampler (betas=...)")
-        if self._lnp is None or len(self._lnp) == 0:
-            raise ValueError("the chain is empty: run_mcmc(..., store=True) first")
-        discard, group = int(discard), int(group)
-        if not 0 <= discard < len(self._lnp):
-            raise ValueError(f"discard={discard} leaves no step of the {len(self._lnp)} stored")
+        group = int(group)
         if not 0 <= group < self.ngroups:
             raise ValueError(f"group must be in 0..{self.ngroups - 1}, got {group}")
-        lnl = self._lnp[discard:].reshape(-1, self.ngroups, self.ntemps, self.nwalkers)[:, group]
-        means = lnl.transpose(1, 0, 2).reshape(self.ntemps, -1).mean(axis=1)
-        ti, dti = tempering.ti_log_evidence(self.betas, means)
+        if device:
+            th = self.get_thermo()
+            if th["n_steps"] < 1:
+                raise ValueError("the thermodynamic monitor holds no step yet" +
+                                 ("" if self._adapt is None else f" (the ladder is frozen from step {self._adapt[0]} on)"))
+            with np.errstate(invalid="ignore", divide="ignore"):
+                means = th["sum_lnl"][group] / th["n_finite"][group]
+            if np.any(th["n_nonfinite"][group] > 0) or not np.all(np.isfinite(means)):
+                raise ValueError("a per-temperature mean of lnL is not finite (walkers without a valid model: discard more steps)")
+        else:
+            if self._lnp is None or len(self._lnp) == 0:
+                raise ValueError("the chain is empty: run_mcmc(..., store=True) first")
+            discard = int(discard)
+            if not 0 <= discard < len(self._lnp):
+                raise ValueError(f"discard={discard} leaves no step of the {len(self._lnp)} stored")
+            if self._adapt is not None and np.any(self._steps[discard:] < self._adapt[0]):
+                raise ValueError(f"steps[{discard}:] of the stored chain hold steps before {self._adapt[0]}, where the ladder "
+                                 "was frozen: discard them")
+            lnl = self._lnp[discard:].reshape(-1, self.ngroups, self.ntemps, self.nwalkers)[:, group]
+            means = lnl.transpose(1, 0, 2).reshape(self.ntemps, -1).mean(axis=1)
+        betas = self.betas if self._adapt is None else self.get_betas()[group]
+        ti, dti = tempering.ti_log_evidence(betas, means)
         if self._target != 0:
             return ti, dti
         lo, hi = np.asarray(self._prior[0], dtype=np.float64), np.asarray(self._prior[1], dtype=np.float64)
@@ -523,6 +610,7 @@ class EnsembleSampler:
         chain = np.empty((max_steps, self.ntotal, self.ndim)) if store else None
         lnp = np.empty((max_steps, self.ntotal)) if store else None
         done, prev = 0, None
+        first_step = self.iteration
         self.converged, self.tau_history = False, []
         while done < max_steps and not self.converged:
             k = min(check_every, max_steps - done)
@@ -545,6 +633,7 @@ class EnsembleSampler:
                 lnp.resize((done,) + lnp.shape[1:], refcheck=False)
             self._chain = chain if self._chain is None else np.concatenate([self._chain, chain])
             self._lnp = lnp if self._lnp is None else np.concatenate([self._lnp, lnp])
+            self._steps = np.concatenate([self._steps, first_step + np.arange(done, dtype=np.int64)])
         return self.get_last_sample()[0]
 
 

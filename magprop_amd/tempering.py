@@ -39,6 +39,42 @@ def geometric_ladder(n_temps, beta_min):
     return check_ladder(b)
 
 
+def adaptation_rate(t, lag, time):
+    """kappa_t = lag / (time * (t + lag)) of ladder update t (0 for the first), in double with exactly these three operations,
+    as mp_sampler_run forms it (include/magprop_amd.h mp_sampler_set_ladder_adaptation; ptemcee: lag = 10000, time = 100)."""
+    t, lag, time = float(int(t)), float(lag), float(time)
+    return lag / (time * (t + lag))
+
+
+def ladder_gaps(betas):
+    """g_i = ln beta_i - ln beta_{i+1}, the gaps of ln beta that the ladder adaptation moves: (..., T - 1) of a ladder or of an
+    array of ladders (..., T).  A geometric ladder has equal gaps."""
+    lb = np.log(np.asarray(betas, dtype=np.float64))
+    return lb[..., :-1] - lb[..., 1:]
+
+
+def swap_spread(acc):
+    """max - min over the pairs of the swap acceptance fractions acc (..., T - 1): 0 on the ladder the adaptation aims at."""
+    a = np.asarray(acc, dtype=np.float64)
+    return a.max(axis=-1) - a.min(axis=-1)
+
+
+def adaptation_settings(adapt_ladder):
+    """(steps, lag, time, history) of EnsembleSampler's adapt_ladder=: an int (steps; ptemcee's lag and time, no history) or a
+    dict with "steps" and optionally "lag", "time", "history"."""
+    if isinstance(adapt_ladder, dict):
+        extra = set(adapt_ladder) - {"steps", "lag", "time", "history"}
+        if extra or "steps" not in adapt_ladder:
+            raise ValueError(f"adapt_ladder takes 'steps' and optionally 'lag', 'time', 'history', got {sorted(adapt_ladder)}")
+        d = adapt_ladder
+    else:
+        d = {"steps": adapt_ladder}
+    steps = int(d["steps"])
+    if steps != d["steps"] or isinstance(d["steps"], bool):
+        raise ValueError(f"adapt_ladder: steps must be a whole number, got {d['steps']!r}")
+    return steps, float(d.get("lag", 10000.0)), float(d.get("time", 100.0)), bool(d.get("history", False))
+
+
 def thermodynamic_integral(betas, mean_lnl):
     """Trapezoid rule in beta over the ladder and a beta = 0 point carrying the hottest mean:
     sum_t (beta_t - beta_{t+1}) (m_t + m_{t+1}) / 2, t = 0 .. T-1, with beta_T = 0 and m_T = m_{T-1}."""
