@@ -835,6 +835,36 @@ int mp_sampler_set_thermo(mp_sampler *s, int64_t discard);
 int mp_sampler_get_thermo(mp_sampler *s, double *sum_lnl, int64_t *n_finite, int64_t *n_nonfinite, int64_t *n_steps);
 
 /*
+ * Sample reservoir (ABI 5, additive): per ensemble a uniform random subset of fixed size of the run's samples, kept on the device
+ * with their lnprob and where they came from, so that the light-curve band, the derived quantities, the flows and the pointwise
+ * scores of a fit (mp_model_band, mp_model_derived, mp_model_flows, mp_model_pointwise) need no chain on the host.  Off by
+ * default; fed like the three monitors above (once per chunk from the device slab's rows and their lnprob, behind them on the
+ * handle's stream; mp_sampler_set_positions restarts it; the walker-sharded entry points return MP_ESTATE while it is on).
+ * The reservoir is a function of the samples alone: it does not depend on how mp_sampler_run chunks its steps or on how a run was
+ * split into calls, and a numpy restatement (tests/reservoir_restated.py) reproduces the held set bit for bit.
+ * A sample is the position x[0 .. ndim), and the stored, untempered lnprob, of walker w of ensemble e at step t, t the sampler's
+ * absolute step index (steps_done of mp_sampler_get_state before the step).  Eligible are the samples of the steps from `discard`
+ * steps after the monitor was (re)started.  Every sample has the key
+ *     key = (r[0] << 32) | r[1],   r = Philox4x32-10(key words seed_lo, seed_hi; counter t_lo32, t_hi32, e * n_walkers + w, 0x52455300),
+ * `seed` the monitor's own.  The reservoir of size K of ensemble e holds the K eligible samples that are least in the total
+ * order (key, t, w), and all of them while fewer than K were seen.  The keys are independent and identically distributed and do
+ * not depend on the state, so the held set is a uniform random K-subset, without replacement, of the eligible samples.  The
+ * bottom K of a union is the bottom K of the union of the parts' bottom K: reservoirs of runs with other seeds or in other
+ * processes merge on the host by their keys (magprop_amd.reservoir.merge).
+ *
+ * mp_sampler_set_reservoir(s, size, seed, discard): size = 0 turns the monitor off and frees it (the other arguments are
+ * ignored); otherwise it (re)starts empty.  MP_EINVAL: size outside 0 .. MP_RESERVOIR_MAX_ROWS, discard < 0; the monitor is then
+ * off.
+ * mp_sampler_get_reservoir: the held rows of one ensemble sorted by (step, walker) ascending, the first max_rows of them:
+ * x[rows][ndim], lnprob, step, walker, key [rows], *n_rows the rows written, *n_seen the eligible samples so far; any output may
+ * be NULL.  MP_ESTATE while the monitor is off, MP_EINVAL on max_rows < 0 or a bad ensemble.
+ */
+#define MP_RESERVOIR_MAX_ROWS 65536
+int mp_sampler_set_reservoir(mp_sampler *s, int size, uint64_t seed, int64_t discard);   /* size 0: off */
+int mp_sampler_get_reservoir(mp_sampler *s, int ensemble, int max_rows, double *x, double *lnprob, int64_t *step,
+                             int32_t *walker, uint64_t *key, int *n_rows, int64_t *n_seen);
+
+/*
  * Differential-evolution optimizer (ABI 5, additive): scipy.optimize.differential_evolution with deferred updating, without
  * the polish step, every generation one launch that builds, evaluates and judges every trial (plus one small reduction).
  * n_pops populations of popsize members each (5 <= popsize <= 1024, 1 <= n_pops <= MP_MAX_DATASETS); population p runs on

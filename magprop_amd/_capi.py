@@ -35,6 +35,7 @@ MOVE_SLICE, SLICE_MAX_SHRINK = 4, 252                         # include/magprop_
 ACF_MAX_LAG, ACF_MAX_BYTES = 4096, 8 << 30                   # include/magprop_amd.h MP_ACF_*
 POST_MAX_BINS, POST_MAX_BINS2, POST_MAX_BYTES = 4096, 128, 1 << 30   # include/magprop_amd.h MP_POST_*
 LADDER_MAX_HISTORY_BYTES = 1 << 28                           # include/magprop_amd.h MP_LADDER_MAX_HISTORY_BYTES
+RESERVOIR_MAX_ROWS = 65536                                   # include/magprop_amd.h MP_RESERVOIR_MAX_ROWS
 
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -58,7 +59,7 @@ class ModelCfg(C.Structure):
 
 _i, _u32, _i64, _u64, _d = C.c_int, C.c_uint32, C.c_int64, C.c_uint64, C.c_double
 _vp, _dp, _ip, _i64p, _cfgp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(ModelCfg)
-_u32p = C.POINTER(C.c_uint32)
+_u32p, _u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 # name -> (restype, argtypes) of every function of include/magprop_amd.h, in header order (tests/test_capi_cpu.py holds the two
 # together).  Handles, samplers, optimizers, nested samplers and streams are c_void_p; so are the host pointers of
 # mp_lnprob_batch, passed as integers (the hot entry), and the device pointers.
@@ -120,6 +121,8 @@ SIGNATURES = {
     "mp_sampler_get_posterior_best": (_i, [_vp, _i, _dp, _dp, _i64p]),
     "mp_sampler_set_thermo": (_i, [_vp, _i64]),
     "mp_sampler_get_thermo": (_i, [_vp, _dp, _i64p, _i64p, _i64p]),
+    "mp_sampler_set_reservoir": (_i, [_vp, _i, _u64, _i64]),
+    "mp_sampler_get_reservoir": (_i, [_vp, _i, _i, _dp, _dp, _i64p, _ip, _u64p, C.POINTER(C.c_int), _i64p]),
     "mp_optimizer_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _i, _d, _d, _d, _d, _d, _dp, _dp, _i]),
     "mp_optimizer_set_population": (_i, [_vp, _dp]),
     "mp_optimizer_run": (_i, [_vp, _i, _ip]),

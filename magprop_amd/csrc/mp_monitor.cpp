@@ -1,5 +1,5 @@
-// mp_monitor.cpp — the host side of the sampler's autocorrelation, posterior and thermodynamic monitors (mp_monitor.h).  Kernels:
-// mp_acf.hip, mp_post.hip, thermo_kernel of mp_ladder.hip.
+// mp_monitor.cpp — the host side of the sampler's autocorrelation, posterior and thermodynamic monitors and of its sample reservoir
+// (mp_monitor.h).  Kernels: mp_acf.hip, mp_post.hip, thermo_kernel of mp_ladder.hip, mp_reservoir.hip.
 #include "mp_monitor.h"
 
 // ---- autocorrelation monitor
@@ -291,4 +291,99 @@ int ThermoMonitor::read(double *sum_out, int64_t *n_finite_out, int64_t *n_nonfi
     if (n_steps) *n_steps = n;
     return read_back(sum_out, (const double *)sum.p, ne, n_finite_out, (const int64_t *)n_finite.p, ne,
                      n_nonfinite_out, (const int64_t *)n_nonfinite.p, ne);
+}
+
+// ---- sample reservoir
+int ResMonitor::off(const char *fn) { return fail(MP_ESTATE, "%s: the sample reservoir is off (mp_sampler_set_reservoir)", fn); }
+
+int ResMonitor::make(const char *fn, int n_walkers, int n_ensembles, int ndim, int size, uint64_t seed, int64_t discard,
+                     size_t sampler_cap, std::unique_ptr<ResMonitor> *out) {
+    if (size < 0 || size > MP_RESERVOIR_MAX_ROWS) return fail(MP_EINVAL, "%s: size must be in [0, %d] (MP_RESERVOIR_MAX_ROWS; 0 turns the monitor off), got %d", fn, MP_RESERVOIR_MAX_ROWS, size);
+    if (discard < 0) return fail(MP_EINVAL, "%s: discard must be >= 0, got %lld", fn, (long long)discard);
+    std::unique_ptr<ResMonitor> m(new ResMonitor(n_walkers, n_ensembles, ndim, discard));
+    m->size = size; m->seed = seed;
+    m->cand_cap = std::max(n_walkers, mp::kResCandCap);   // a slice is one step at least
+    m->chunk_cap = (int)m->capped(sampler_cap);
+    const size_t ne = (size_t)n_ensembles, held = ne * (size_t)size, cand = ne * (size_t)m->cand_cap;
+    int rc;
+    if ((rc = m->key.ensure(held)) || (rc = m->step.ensure(held)) || (rc = m->walker.ensure(held)) || (rc = m->lnp.ensure(held)) ||
+        (rc = m->x.ensure(held * ndim)) || (rc = m->meta.ensure(ne * mp::kResMeta)) || (rc = m->cand_key.ensure(cand)) ||
+        (rc = m->cand_step.ensure(cand)) || (rc = m->cand_walker.ensure(cand)) || (rc = m->evicted.ensure(cand)) ||
+        (rc = m->n_cand.ensure(ne)))
+        return rc;
+    *out = std::move(m);
+    return MP_OK;
+}
+
+mp::ResArgs ResMonitor::args(const double *chain, const double *lnp_rows) const {
+    mp::ResArgs a{};
+    a.chain = chain; a.lnp = lnp_rows;
+    a.key = key.p; a.step = step.p; a.walker = walker.p; a.x = x.p; a.held_lnp = lnp.p; a.meta = meta.p;
+    a.cand_key = cand_key.p; a.cand_step = cand_step.p; a.cand_walker = cand_walker.p; a.n_cand = n_cand.p; a.evicted = evicted.p;
+    a.seed = seed;
+    a.n_walkers = n_walkers; a.n_ensembles = n_ensembles; a.n_total = n_total; a.ndim = ndim;
+    a.size = size; a.cand_cap = cand_cap;
+    return a;
+}
+
+int ResMonitor::restart(hipStream_t st) {
+    const size_t ne = (size_t)n_ensembles;
+    const int rc = zero_async(st, meta.p, ne * mp::kResMeta, n_cand.p, ne);
+    if (rc) return rc;
+    start_over();
+    return MP_OK;
+}
+
+int ResMonitor::feed(const double *chain, const double *lnp_rows, int chunk, int64_t step0, hipStream_t st) {
+    mp::ResArgs a = args(chain, lnp_rows);
+    int first;
+    const int rows = take(chunk, &first);
+    if (rows == 0) return MP_OK;
+    const int slice = std::max(1, cand_cap / n_walkers);
+    for (int r = first; r < chunk; r += slice) {
+        a.row0 = r;
+        a.rows = std::min(slice, chunk - r);
+        a.t0 = step0 + r;
+        int rc = launched(mp::launch_res_filter(a, st));
+        if (!rc) rc = launched(mp::launch_res_merge(a, st));
+        if (rc) return rc;
+    }
+    n += rows;
+    return MP_OK;
+}
+
+int ResMonitor::ready(const char *fn, int ensemble, hipStream_t st) const {
+    if (ensemble < 0 || ensemble >= n_ensembles) return fail(MP_EINVAL, "%s: ensemble must be in [0, %d), got %d", fn, n_ensembles, ensemble);
+    HIP_TRY(hipStreamSynchronize(st));
+    return MP_OK;
+}
+
+int ResMonitor::read(int ensemble, int max_rows, double *x_out, double *lnprob, int64_t *step_out, int32_t *walker_out,
+                     uint64_t *key_out, int *n_rows, int64_t *n_seen) const {
+    int64_t m[mp::kResMeta];
+    HIP_TRY(hipMemcpy(m, meta.p + (size_t)ensemble * mp::kResMeta, sizeof m, hipMemcpyDeviceToHost));
+    const size_t held = (size_t)std::min<int64_t>(m[mp::kResHeld], size), nd = (size_t)ndim, at = (size_t)ensemble * size;
+    std::vector<uint64_t> k(held);
+    std::vector<int64_t> t(held);
+    std::vector<int32_t> w(held);
+    std::vector<double> l(held), xs(held * nd);
+    int rc = read_back(k.data(), (const uint64_t *)key.p + at, held, t.data(), (const int64_t *)step.p + at, held,
+                       w.data(), (const int32_t *)walker.p + at, held, l.data(), (const double *)lnp.p + at, held,
+                       xs.data(), (const double *)x.p + at * nd, held * nd);
+    if (rc) return rc;
+    std::vector<size_t> order(held);
+    std::iota(order.begin(), order.end(), (size_t)0);
+    std::sort(order.begin(), order.end(), [&](size_t p, size_t q) { return t[p] < t[q] || (t[p] == t[q] && w[p] < w[q]); });
+    const size_t rows = std::min(held, (size_t)std::max(max_rows, 0));
+    for (size_t i = 0; i < rows; ++i) {
+        const size_t j = order[i];
+        if (x_out) std::memcpy(x_out + i * nd, xs.data() + j * nd, nd * sizeof(double));
+        if (lnprob) lnprob[i] = l[j];
+        if (step_out) step_out[i] = t[j];
+        if (walker_out) walker_out[i] = w[j];
+        if (key_out) key_out[i] = k[j];
+    }
+    if (n_rows) *n_rows = (int)rows;
+    if (n_seen) *n_seen = m[mp::kResSeen];
+    return MP_OK;
 }

@@ -1,10 +1,11 @@
-// mp_monitor.h — the three chain monitors of the ensemble sampler as a host unit of their own (mp_monitor.cpp): the autocorrelation
-// monitor (mp_sampler_set_autocorr; kernels mp_acf.hip), the posterior monitor (mp_sampler_set_posterior; kernels mp_post.hip) and
-// the thermodynamic monitor (mp_sampler_set_thermo; thermo_kernel of mp_ladder.hip).
+// mp_monitor.h — the four chain monitors of the ensemble sampler as a host unit of their own (mp_monitor.cpp): the autocorrelation
+// monitor (mp_sampler_set_autocorr; kernels mp_acf.hip), the posterior monitor (mp_sampler_set_posterior; kernels mp_post.hip),
+// the thermodynamic monitor (mp_sampler_set_thermo; thermo_kernel of mp_ladder.hip) and the sample reservoir
+// (mp_sampler_set_reservoir; kernels mp_reservoir.hip).
 //
 // Internal, like mp_host.h.  A monitor knows the shape of the chain, the device rows it is fed and a stream, and nothing of the
-// sampler: mp_sampler.cpp holds one of each behind its entry points, and the probe libraries mp_probe_acf.hip and
-// mp_probe_post.hip drive the same functions over crafted chains.  A function that reports an error names the entry point `fn`.
+// sampler: mp_sampler.cpp holds one of each behind its entry points, and the probe libraries mp_probe_acf.hip,
+// mp_probe_post.hip and mp_probe_reservoir.hip drive the same functions over crafted chains.  A function that reports an error names the entry point `fn`.
 #pragma once
 #include <memory>
 
@@ -12,6 +13,7 @@
 #include "mp_host.h"
 #include "mp_ladder.h"
 #include "mp_post.h"
+#include "mp_reservoir.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -112,6 +114,37 @@ struct ThermoMonitor : ChainMonitor {
     int feed(const double *lnp, int chunk, int64_t step0, int64_t frozen_from, hipStream_t st);
     // read-out behind mp_sampler_get_thermo (after a wait for the stream)
     int read(double *sum_out, int64_t *n_finite_out, int64_t *n_nonfinite_out, int64_t *n_steps) const;
+};
+
+// A uniform random subset of `size` of the monitored samples per ensemble with their lnprob, step, walker and key (mp_reservoir.h
+// states the rule), fed once per chunk of mp_sampler_run from the device slab of chain rows and their lnprob.
+struct ResMonitor : ChainMonitor {
+    int size = 0, cand_cap = 0;     // K; candidates per ensemble and slice of a chunk
+    uint64_t seed = 0;
+    DevBuf<uint64_t> key, cand_key;
+    DevBuf<int64_t> step, cand_step, meta;
+    DevBuf<int32_t> walker, cand_walker, evicted;
+    DevBuf<uint32_t> n_cand;
+    DevBuf<double> x, lnp;
+    using ChainMonitor::ChainMonitor;
+
+    static int off(const char *fn);
+    // A monitor of size != 0 rows per ensemble with its buffers, after the checks of size and discard in this order; restart()
+    // comes next
+    static int make(const char *fn, int n_walkers, int n_ensembles, int ndim, int size, uint64_t seed, int64_t discard,
+                    size_t sampler_cap, std::unique_ptr<ResMonitor> *out);
+    // Empty the monitor (stream-ordered): nothing held, nothing seen, everything passes, `discard` steps from now.
+    int restart(hipStream_t st);
+    // The `chunk` rows chain[chunk][n_total][ndim] and lnp[chunk][n_total] of a chunk whose first row is step `step0` into the
+    // monitor (stream-ordered), in slices of whole steps of at most cand_cap samples per ensemble
+    int feed(const double *chain, const double *lnp, int chunk, int64_t step0, hipStream_t st);
+    // The prologue of the read-out: the ensemble exists, and what was fed has been merged
+    int ready(const char *fn, int ensemble, hipStream_t st) const;
+    // read-out behind mp_sampler_get_reservoir (after ready): the first max_rows held rows in the order (step, walker)
+    int read(int ensemble, int max_rows, double *x_out, double *lnprob, int64_t *step_out, int32_t *walker_out, uint64_t *key_out,
+             int *n_rows, int64_t *n_seen) const;
+    // the launch arguments over the monitor's buffers (the probe's merge entry fills the slice in itself)
+    mp::ResArgs args(const double *chain, const double *lnp) const;
 };
 
 #pragma GCC visibility pop

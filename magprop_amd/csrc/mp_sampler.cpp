@@ -54,6 +54,7 @@ struct mp_sampler {
     std::unique_ptr<AcfMonitor> acf;   // the autocorrelation monitor; null: off
     std::unique_ptr<PostMonitor> post; // the posterior monitor; null: off
     std::unique_ptr<ThermoMonitor> thermo;   // the thermodynamic monitor; null: off
+    std::unique_ptr<ResMonitor> res;   // the sample reservoir; null: off
     // ladder adaptation (mp_sampler_set_ladder_adaptation; kernels mp_ladder.hip); n_adapt = 0: off, a fixed ladder.  Every step of
     // mp_sampler_run makes one update while ladder_t < n_adapt: update t lies behind step t, so steps >= n_adapt run on the frozen
     // ladder
@@ -448,6 +449,7 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
     if (s->acf) rc = s->acf->restart(ev->stream);     // the series is broken
     if (!rc && s->post) rc = s->post->restart(ev->stream);
     if (!rc && s->thermo) rc = s->thermo->restart(ev->stream);
+    if (!rc && s->res) rc = s->res->restart(ev->stream);
     return rc;
 }
 
@@ -512,12 +514,13 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
     // chunks of steps so that the device-resident chain slab stays below ~256 MB, the splits below ~64 MB, and the
     // window of failed proposals (drained after every chunk) overflows only if more than 1 in 32 proposals fails
     const size_t perm_cap = perm_chunk_cap(s);
-    const bool monitor = s->acf != nullptr, post = s->post != nullptr, thermo = s->thermo != nullptr;
-    const bool slab = chain || monitor || post || thermo;   // the monitors read the chain rows from the device slab
+    const bool monitor = s->acf != nullptr, post = s->post != nullptr, thermo = s->thermo != nullptr, res = s->res != nullptr;
+    const bool slab = chain || monitor || post || thermo || res;   // the monitors read the chain rows from the device slab
     int chunk_max = (int)std::min<size_t>((size_t)std::max(n_steps, 1), slab ? slab_chunk_cap(s, perm_cap) : perm_cap);
     if (monitor) chunk_max = std::min(chunk_max, s->acf->chunk_cap);
     if (post) chunk_max = std::min(chunk_max, s->post->chunk_cap);
     if (thermo) chunk_max = std::min(chunk_max, s->thermo->chunk_cap);
+    if (res) chunk_max = std::min(chunk_max, s->res->chunk_cap);
     constexpr int kSub = 8;   // steps per batch of splits: the host draws the next batch while the GPU runs this one
     int rc;
     // A whole step per launch (mp_kernels.hip stretch_step_kernel: 3 n/2 evaluations, a third of them speculative) while
@@ -553,6 +556,7 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
         if (monitor && (rc = s->acf->feed(s->d_chain.p, chunk, ev->stream))) return rc;
         if (post && (rc = s->post->feed(s->d_chain.p, s->d_chain_lnp.p, chunk, ev->stream))) return rc;
         if (thermo && (rc = s->thermo->feed(s->d_chain_lnp.p, chunk, (int64_t)s->steps_done, s->n_adapt, ev->stream))) return rc;
+        if (res && (rc = s->res->feed(s->d_chain.p, s->d_chain_lnp.p, chunk, (int64_t)s->steps_done, ev->stream))) return rc;
         if (chain) {
             HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
             HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
@@ -680,6 +684,30 @@ int mp_sampler_get_thermo(mp_sampler *s, double *sum_lnl, int64_t *n_finite, int
     return s->thermo->read(sum_lnl, n_finite, n_nonfinite, n_steps);
 }
 
+// ---- sample reservoir (mp_monitor.h ResMonitor)
+int mp_sampler_set_reservoir(mp_sampler *s, int size, uint64_t seed, int64_t discard) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_set_reservoir: NULL sampler");
+    Held held(s->h, s->ev);
+    HIP_TRY(hipDeviceSynchronize());
+    s->res.reset();
+    if (size == 0) return MP_OK;
+    int rc = ResMonitor::make("mp_sampler_set_reservoir", s->n_walkers, s->n_ensembles, s->ndim, size, seed, discard,
+                              slab_chunk_cap(s, perm_chunk_cap(s)), &s->res);
+    if (rc) return rc;
+    if ((rc = s->res->restart(s->ev->stream))) s->res.reset();
+    return rc;
+}
+
+int mp_sampler_get_reservoir(mp_sampler *s, int ensemble, int max_rows, double *x, double *lnprob, int64_t *step, int32_t *walker,
+                             uint64_t *key, int *n_rows, int64_t *n_seen) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_reservoir: NULL sampler");
+    if (max_rows < 0) return fail(MP_EINVAL, "mp_sampler_get_reservoir: max_rows must be >= 0, got %d", max_rows);
+    Held held(s->h, s->ev);
+    if (!s->res) return ResMonitor::off("mp_sampler_get_reservoir");
+    const int rc = s->res->ready("mp_sampler_get_reservoir", ensemble, s->ev->stream);
+    return rc ? rc : s->res->read(ensemble, max_rows, x, lnprob, step, walker, key, n_rows, n_seen);
+}
+
 int mp_sampler_set_whole_step(mp_sampler *s, int enable) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_set_whole_step: NULL sampler");
     Lock lock(s->h->mu);
@@ -731,6 +759,8 @@ struct ShardCall {
             rc = fail(MP_ESTATE, "%s: the posterior monitor (mp_sampler_set_posterior) is fed by mp_sampler_run only; turn it off first", fn);
         else if (s->thermo)
             rc = fail(MP_ESTATE, "%s: the thermodynamic monitor (mp_sampler_set_thermo) is fed by mp_sampler_run only; turn it off first", fn);
+        else if (s->res)
+            rc = fail(MP_ESTATE, "%s: the sample reservoir (mp_sampler_set_reservoir) is fed by mp_sampler_run only; turn it off first", fn);
         else if (!(rc = current_split(s, (hipStream_t)stream, &d_perm))) s->ext_stream_work = true;
     }
 };

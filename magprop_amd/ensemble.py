@@ -100,6 +100,7 @@ class EnsembleSampler:
         self._lnp = None
         self._steps = np.empty(0, dtype=np.int64)   # the step index of every stored row
         self._thermo = False        # the device thermodynamic monitor is on
+        self._res = None            # (size, seed, discard) of the device sample reservoir; None: off
         self.iteration = 0
         self.fbad = fbad
         self._bad_written = 0
@@ -383,53 +384,103 @@ class EnsembleSampler:
     def acceptance_fraction(self):
         return self.get_last_sample()[2] / max(self.iteration, 1)
 
-    def _summary_rows(self, name, discard, thin, ensemble):
+    # ---- the device sample reservoir (include/magprop_amd.h mp_sampler_set_reservoir states the rule)
+    def monitor_samples(self, size=4096, seed=None, discard=0):
+        """Turn the sample reservoir on (empty, taking samples from `discard` steps from now on), or off with size=None: per
+        ensemble a uniform random subset of `size` of the run's samples (all of them while fewer were seen), kept on the device
+        with their lnprob, step and walker, so that a store=False run ends with posterior samples (get_samples, and source=
+        "reservoir" of get_model_band, get_derived, get_flows, get_flow_band and get_pointwise).  seed=None derives the
+        monitor's seed from the sampler's; give two runs different seeds to merge their reservoirs (magprop_amd.reservoir.merge).
+        While it is on, set_positions (run_mcmc with pos) restarts it and the walker-sharded entry points refuse."""
+        if size is None:
+            _capi.check(self._L.mp_sampler_set_reservoir(self._s, 0, 0, 0), "mp_sampler_set_reservoir")
+            self._res = None
+            return
+        size = int(size)
+        if size < 1:
+            raise ValueError(f"size must be >= 1 (None turns the monitor off), got {size}")
+        seed = (self.seed ^ 0x5265735F6B657973) & 0xFFFFFFFFFFFFFFFF if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._res = None
+        _capi.check(self._L.mp_sampler_set_reservoir(self._s, size, seed, int(discard)), "mp_sampler_set_reservoir")
+        self._res = (size, seed, int(discard))
+
+    def get_samples(self, ensemble=0, temp=None):
+        """The reservoir of one ensemble: {"x": (rows, ndim), "log_prob", "step", "walker", "key": (rows,), "n_seen"}, the rows
+        sorted by (step, walker); step is the sampler's step index (self.iteration before the step), log_prob the untempered
+        lnprob, n_seen the samples the monitor drew from.  A tempered sampler: the beta = 1 ensemble of group `ensemble`, or with
+        temp=t its beta_t ensemble."""
+        if self._res is None:
+            raise _capi.MagpropAmdError("the sample reservoir is off (monitor_samples)")
+        e = int(ensemble)
+        if self.betas is not None or temp is not None:
+            t = 0 if temp is None else int(temp)
+            if not 0 <= t < self.ntemps:
+                raise ValueError(f"temp must be in 0..{self.ntemps - 1}, got {temp}")
+            if not 0 <= e < self.ngroups:
+                raise ValueError(f"ensemble must be in 0..{self.ngroups - 1}, got {ensemble}")
+            e = e * self.ntemps + t
+        k = self._res[0]
+        out = _capi.read_back(self._L.mp_sampler_get_reservoir, self._s, [
+            ("x", (k, self.ndim), np.float64), ("log_prob", k, np.float64), ("step", k, np.int64), ("walker", k, np.int32),
+            ("key", k, np.uint64), ("n_rows", (), np.int32), ("n_seen", (), np.int64)], e, k)
+        rows = int(out.pop("n_rows"))
+        out = {name: (v[:rows].copy() if name != "n_seen" else int(v)) for name, v in out.items()}
+        return out
+
+    def _summary_rows(self, name, discard, thin, ensemble, source="chain"):
         """The rows chain[discard::thin, ensemble's walkers] the front end `name` summarises (band_selection; tempered: the
-        beta = 1 walkers of group `ensemble`)."""
+        beta = 1 walkers of group `ensemble`); source="reservoir": the rows of get_samples(ensemble) in its order."""
         if self._target != 0:
             raise ValueError(f"{name} needs the posterior target: a target='gaussian' sampler has no "
                              f"{'trajectory' if 'flow' in name else 'light curve'}")
+        if source == "reservoir":
+            return reservoir_selection(self.get_samples, discard, thin, ensemble, self.ngroups)
+        if source != "chain":
+            raise ValueError(f"source must be 'chain' or 'reservoir', got {source!r}")
         return band_selection(self.get_chain(temp=0 if self.betas is not None else None), self.nwalkers, self.ngroups,
                               discard, thin, ensemble)
 
-    def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), discard=0, thin=1, ensemble=0, weights=None):
+    def get_model_band(self, q=(0.025, 0.5, 0.975), components=("Ltot",), discard=0, thin=1, ensemble=0, weights=None, source="chain"):
         """Posterior-predictive band over the stored chain: the quantiles q of the model light curves of the rows
         chain[discard::thin, ensemble's walkers], evaluated on this sampler's handle (its prior, grid and configuration).
         Returns {"t": grid, "Ltot": (nq, n_grid), ..., "n_used": rows that entered}.  weights: one per selected row, in the
         order band_selection gives them (a chain reweighted to another prior, error model or temperature): the weighted band
-        (mp_model_band_weighted), and "n_eff" in the result."""
-        rows = self._summary_rows("get_model_band", discard, thin, ensemble)
+        (mp_model_band_weighted), and "n_eff" in the result.  source="reservoir": over the rows of get_samples(ensemble), in
+        its order, instead of the stored chain (monitor_samples; discard and thin must stay at their defaults)."""
+        rows = self._summary_rows("get_model_band", discard, thin, ensemble, source)
         return summaries.band(summaries.on(self.handle), rows, q, components, weights)
 
-    def get_derived(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, ensemble=0):
+    def get_derived(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, ensemble=0, source="chain"):
         """Energy budgets and light-curve landmarks over the stored chain (magprop_amd.derived.NAMES): the model of every row of
         chain[discard::thin, ensemble's walkers], evaluated and reduced on this sampler's handle (mp_model_derived).  Returns
-        {"values": (rows, 16), "status", "n_used", "summary": derived.summarize(values, q)}."""
-        rows = self._summary_rows("get_derived", discard, thin, ensemble)
+        {"values": (rows, 16), "status", "n_used", "summary": derived.summarize(values, q)}.  source="reservoir": as in
+        get_model_band."""
+        rows = self._summary_rows("get_derived", discard, thin, ensemble, source)
         return summaries.derived(summaries.on(self.handle), rows, q)
 
-    def get_flows(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, ensemble=0, curves=()):
+    def get_flows(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, ensemble=0, curves=(), source="chain"):
         """Mass budget, angular-momentum budget and propeller / accretor regime over the stored chain (magprop_amd.flows.NAMES):
         the model of every row of chain[discard::thin, ensemble's walkers], evaluated and reduced on this sampler's handle
         (mp_model_flows).  Returns {"values": (rows, 16), "status", "n_used", "summary": flows.summarize(values, q)} and the
-        cell curves named in `curves`."""
-        rows = self._summary_rows("get_flows", discard, thin, ensemble)
+        cell curves named in `curves`.  source="reservoir": as in get_model_band."""
+        rows = self._summary_rows("get_flows", discard, thin, ensemble, source)
         return summaries.flows(summaries.on(self.handle), rows, q, None, curves)
 
-    def get_flow_band(self, q=(0.025, 0.5, 0.975), curves=("fastness",), discard=0, thin=1, ensemble=0, weights=None):
+    def get_flow_band(self, q=(0.025, 0.5, 0.975), curves=("fastness",), discard=0, thin=1, ensemble=0, weights=None,
+                      source="chain"):
         """Bands of the radii, mass-flow rates and torques over the stored chain: the quantiles q, per grid point, of the cell
         curves named in `curves` (flows.CURVES without "branch") over the rows get_model_band takes (mp_model_flow_band).
-        Returns {"t": grid, name: (nq, n_grid), "n_used"}; weights as in get_model_band."""
-        rows = self._summary_rows("get_flow_band", discard, thin, ensemble)
+        Returns {"t": grid, name: (nq, n_grid), "n_used"}; weights and source as in get_model_band."""
+        rows = self._summary_rows("get_flow_band", discard, thin, ensemble, source)
         return summaries.flow_band(summaries.on(self.handle), rows, q, curves, weights)
 
-    def get_pointwise(self, discard=0, thin=1, ensemble=0):
+    def get_pointwise(self, discard=0, thin=1, ensemble=0, source="chain"):
         """Pointwise predictive scores over the stored chain: PSIS-LOO with its Pareto-k diagnostic and WAIC per observation
         of group `ensemble`'s dataset, in the order the dataset was given, over the rows chain[discard::thin, ensemble's
         walkers], evaluated and reduced on this sampler's handle (mp_model_pointwise).  Returns what synth.model_pointwise
         returns.  The selection is capped like get_model_band's: thin a longer chain, or hand its rows to
-        synth.model_pointwise / mcmc_eqns.model_pointwise."""
-        rows = self._summary_rows("get_pointwise", discard, thin, ensemble)
+        synth.model_pointwise / mcmc_eqns.model_pointwise.  source="reservoir": as in get_model_band."""
+        rows = self._summary_rows("get_pointwise", discard, thin, ensemble, source)
         return summaries.pointwise(summaries.on(self.handle, int(ensemble), self._times[int(ensemble)]), rows)
 
     def get_autocorr_time(self, c=5.0, tol=50, quiet=False, device=False):
@@ -599,7 +650,9 @@ class EnsembleSampler:
         to the stored chain (preallocated once for max_steps, trimmed); store=False: no chain reaches the host.
         The posterior monitor (monitor_posterior) runs next to it: both are fed from the same device rows, so a
         store=False run ends with tau and with the histograms, moments and best sample of get_posterior.  Both restart at
-        set_positions, so give pos=None to keep what a monitor holds, and turn monitor_posterior on after the burn-in."""
+        set_positions, so give pos=None to keep what a monitor holds, and turn monitor_posterior on after the burn-in.
+        The sample reservoir (monitor_samples) is fed from the same rows: with it a store=False run also ends with posterior
+        samples (get_samples), and the band, derived quantities, flows and pointwise scores take them with source="reservoir"."""
         max_steps, check_every = int(max_steps), int(check_every)
         if check_every < 1 or max_steps < 0:
             raise ValueError(f"check_every must be >= 1 and max_steps >= 0, got {check_every}, {max_steps}")
@@ -645,6 +698,26 @@ def autocorr_converged(tau, tau_prev, n, tol=50, rtol=0.01):
     tau, tau_prev = np.asarray(tau, dtype=float), np.asarray(tau_prev, dtype=float)
     with np.errstate(invalid="ignore", divide="ignore"):
         return bool(np.all(tol * tau < n) and np.all(np.abs(tau - tau_prev) / tau < rtol))
+
+
+def reservoir_selection(get_samples, discard=0, thin=1, ensemble=0, nensembles=1):
+    """The rows of the reservoir of `ensemble` (get_samples(ensemble)["x"], in its order) that the summaries evaluate with
+    source="reservoir".  The reservoir is drawn from the whole monitored run, so discard and thin must be at their defaults
+    (give discard to monitor_samples).  Raises ValueError for those, a bad ensemble, an empty reservoir and one of more than
+    _capi.BAND_MAX_SAMPLES rows."""
+    if int(discard) != 0 or int(thin) != 1:
+        raise ValueError(f"source='reservoir' takes every row of the reservoir: discard and thin must be 0 and 1, got "
+                         f"discard={discard}, thin={thin} (give discard to monitor_samples)")
+    ensemble = int(ensemble)
+    if not 0 <= ensemble < nensembles:
+        raise ValueError(f"ensemble must be in 0..{nensembles - 1}, got {ensemble}")
+    rows = np.ascontiguousarray(get_samples(ensemble)["x"])
+    if rows.shape[0] == 0:
+        raise ValueError("the reservoir is empty: run_mcmc with monitor_samples on first")
+    if rows.shape[0] > _capi.BAND_MAX_SAMPLES:
+        raise ValueError(f"the selection holds {rows.shape[0]} rows, more than {_capi.BAND_MAX_SAMPLES} (MP_BAND_MAX_SAMPLES): "
+                         "raise thin or discard")
+    return rows
 
 
 def band_selection(chain, nwalkers, nensembles=1, discard=0, thin=1, ensemble=0):
