@@ -5,7 +5,7 @@
 // the two types behind the ABI's handle -- Evaluator, everything that lives on ONE device, and mp_handle, the dealer that owns
 // one evaluator per device and the lock -- the helpers of mp_capi.cpp that the summaries and the resident drivers call, and the
 // skeleton that the optimizer, the nested sampler, the simplex search and the SMC sampler stand on (Resident and what follows it).
-// Each driver's own struct stays in its source file; the sampler's two chain monitors are a unit of their own (mp_monitor.h),
+// Each driver's own struct stays in its source file; the sampler's four chain monitors are a unit of their own (mp_monitor.h),
 // which the probe libraries of their kernels link as well.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2,26 +2,40 @@
 // (mp_monitor.h).  Kernels: mp_acf.hip, mp_post.hip, thermo_kernel of mp_ladder.hip, mp_reservoir.hip.
 #include "mp_monitor.h"
 
+// ---- what the four share
+int MonitorNames::off(const char *fn) const { return fail(MP_ESTATE, "%s: %s is off (%s)", fn, what, setter); }
+
+int ChainMonitor::run_only(const char *fn) const { return fail(MP_ESTATE, "%s: %s (%s) is fed by mp_sampler_run only; turn it off first", fn, names.what, names.setter); }
+
+int ChainMonitor::check_discard(const char *fn, int64_t discard, const char *clause) {
+    return discard < 0 ? fail(MP_EINVAL, "%s: discard must be >= 0%s, got %lld", fn, clause, (long long)discard) : MP_OK;
+}
+
+int ChainMonitor::ready(const char *fn, int ensemble, hipStream_t st) const {
+    if (ensemble < 0 || ensemble >= n_ensembles) return fail(MP_EINVAL, "%s: ensemble must be in [0, %d), got %d", fn, n_ensembles, ensemble);
+    HIP_TRY(hipStreamSynchronize(st));
+    return MP_OK;
+}
+
 // ---- autocorrelation monitor
-int AcfMonitor::off(const char *fn) { return fail(MP_ESTATE, "%s: the autocorrelation monitor is off (mp_sampler_set_autocorr)", fn); }
+const MonitorNames AcfMonitor::kNames = {"the autocorrelation monitor", "mp_sampler_set_autocorr"};
 
 int AcfMonitor::check(const char *fn, int max_lag, int64_t discard) {
     if (max_lag < 0 || max_lag > MP_ACF_MAX_LAG) return fail(MP_EINVAL, "%s: max_lag must be in [0, %d] (MP_ACF_MAX_LAG; 0 turns the monitor off), got %d", fn, MP_ACF_MAX_LAG, max_lag);
-    if (discard < 0) return fail(MP_EINVAL, "%s: discard must be >= 0, got %lld", fn, (long long)discard);
-    return MP_OK;
+    return check_discard(fn, discard);
 }
 
 int AcfMonitor::make(const char *fn, int n_walkers, int n_ensembles, int ndim, int max_lag, int64_t discard, size_t sampler_cap,
                      std::unique_ptr<AcfMonitor> *out) {
-    std::unique_ptr<AcfMonitor> m(new AcfMonitor(n_walkers, n_ensembles, ndim, discard));
+    std::unique_ptr<AcfMonitor> m(new AcfMonitor(kNames, n_walkers, n_ensembles, ndim, discard, sampler_cap));
     const size_t ns = (size_t)m->n_total * ndim;
     const int kp = (max_lag + mp::kAcfLagBlock - 1) / mp::kAcfLagBlock * mp::kAcfLagBlock;
-    const size_t cap = m->capped(sampler_cap), ring = (size_t)kp + cap;   // the ring holds one chunk behind the kp rows it keeps
+    const size_t ring = (size_t)kp + (size_t)m->chunk_cap;   // the ring holds one chunk behind the kp rows it keeps
     const double bytes = ((double)ring + 3.0 * kp + 2.0) * (double)ns * sizeof(double);   // ring, S, H, rho, T, pivot
     if (bytes > (double)MP_ACF_MAX_BYTES)
         return fail(MP_EINVAL, "%s: max_lag = %d over %zu series needs %.0f bytes of accumulators, more than MP_ACF_MAX_BYTES = %lld: lower max_lag",
                     fn, max_lag, ns, bytes, (long long)MP_ACF_MAX_BYTES);
-    m->max_lag = max_lag; m->kp = kp; m->chunk_cap = (int)cap; m->ring_rows = (int)ring;
+    m->max_lag = max_lag; m->kp = kp; m->ring_rows = (int)ring;
     const size_t ned = (size_t)n_ensembles * ndim;
     int rc;
     if ((rc = m->hist.ensure(ring * ns)) || (rc = m->S.ensure((size_t)kp * ns)) || (rc = m->H.ensure((size_t)kp * ns)) ||
@@ -53,9 +67,9 @@ int AcfMonitor::restart(hipStream_t st) {
     return MP_OK;
 }
 
-int AcfMonitor::feed(const double *chain, int chunk, hipStream_t st) {
-    mp::AcfArgs a = args(chain);
-    a.rows = take(chunk, &a.first);
+int AcfMonitor::feed(const ChainRows &c, hipStream_t st) {
+    mp::AcfArgs a = args(c.chain);
+    a.rows = take(c.rows, &a.first);
     if (a.rows == 0) return MP_OK;
     const int rc = launched(mp::launch_acf_accumulate(a, st));
     if (rc) return rc;
@@ -118,19 +132,19 @@ int AcfMonitor::read_sums(int ensemble, double *S_out, double *T_out, double *H_
 }
 
 // ---- posterior monitor
-int PostMonitor::off(const char *fn) { return fail(MP_ESTATE, "%s: the posterior monitor is off (mp_sampler_set_posterior)", fn); }
+const MonitorNames PostMonitor::kNames = {"the posterior monitor", "mp_sampler_set_posterior"};
 
 int PostMonitor::make(const char *fn, int n_walkers, int n_ensembles, int ndim, int bins1, int bins2, const double *lower,
                       const double *upper, int64_t discard, size_t sampler_cap, std::unique_ptr<PostMonitor> *out) {
     if (bins1 < 0 || bins1 > MP_POST_MAX_BINS) return fail(MP_EINVAL, "%s: bins1 must be in [0, %d] (MP_POST_MAX_BINS; 0 turns the monitor off), got %d", fn, MP_POST_MAX_BINS, bins1);
     if (bins2 < 0 || bins2 > MP_POST_MAX_BINS2) return fail(MP_EINVAL, "%s: bins2 must be in [0, %d] (MP_POST_MAX_BINS2; 0: no 2-D histograms), got %d", fn, MP_POST_MAX_BINS2, bins2);
-    if (discard < 0) return fail(MP_EINVAL, "%s: discard must be >= 0, got %lld", fn, (long long)discard);
+    if (int rc = check_discard(fn, discard)) return rc;
     if (!lower || !upper) return fail(MP_EINVAL, "%s: NULL range", fn);
     for (int d = 0; d < ndim; ++d)
         if (!std::isfinite(lower[d]) || !std::isfinite(upper[d]) || !(lower[d] < upper[d]) || !std::isfinite(upper[d] - lower[d]))
             return fail(MP_EINVAL, "%s: range of dimension %d must be finite with lower < upper, got [%g, %g]", fn, d, lower[d], upper[d]);
     if (n_ensembles > 65535) return fail(MP_EINVAL, "%s: at most 65535 ensembles, got %d", fn, n_ensembles);
-    std::unique_ptr<PostMonitor> m(new PostMonitor(n_walkers, n_ensembles, ndim, discard));
+    std::unique_ptr<PostMonitor> m(new PostMonitor(kNames, n_walkers, n_ensembles, ndim, discard, sampler_cap));
     const size_t ne = (size_t)n_ensembles, nt = (size_t)m->n_total, nd = (size_t)ndim;
     const size_t np = (size_t)mp::post_n_pairs(ndim), nent = (size_t)mp::post_n_entries(ndim);
     const size_t n_h1 = ne * nd * mp::post_stride1(bins1), n_h2 = ne * np * (size_t)bins2 * bins2;
@@ -139,7 +153,6 @@ int PostMonitor::make(const char *fn, int n_walkers, int n_ensembles, int ndim, 
         return fail(MP_EINVAL, "%s: bins1 = %d, bins2 = %d over %d ensembles of %d dimensions need %.0f bytes of accumulators, more than MP_POST_MAX_BYTES = %lld: lower the bin counts",
                     fn, bins1, bins2, n_ensembles, ndim, bytes, (long long)MP_POST_MAX_BYTES);
     m->bins1 = bins1; m->bins2 = bins2;
-    m->chunk_cap = (int)m->capped(sampler_cap);
     m->par.resize(5 * nd);
     mp::post_params(m->par.data(), ndim, bins1, bins2, lower, upper);
     int rc;
@@ -177,19 +190,13 @@ int PostMonitor::restart(hipStream_t st) {
     return MP_OK;
 }
 
-int PostMonitor::feed(const double *chain, const double *lnp, int chunk, hipStream_t st) {
-    mp::PostArgs a = args(chain, lnp);
-    a.rows = take(chunk, &a.first);
+int PostMonitor::feed(const ChainRows &c, hipStream_t st) {
+    mp::PostArgs a = args(c.chain, c.lnp);
+    a.rows = take(c.rows, &a.first);
     if (a.rows == 0) return MP_OK;
     const int rc = launched(mp::launch_post_accumulate(a, st));
     if (rc) return rc;
     n += a.rows;
-    return MP_OK;
-}
-
-int PostMonitor::ready(const char *fn, int ensemble, hipStream_t st) const {
-    if (ensemble < 0 || ensemble >= n_ensembles) return fail(MP_EINVAL, "%s: ensemble must be in [0, %d), got %d", fn, n_ensembles, ensemble);
-    HIP_TRY(hipStreamSynchronize(st));
     return MP_OK;
 }
 
@@ -248,13 +255,12 @@ int PostMonitor::read_best(int ensemble, double *x, double *lnprob, int64_t *ind
 }
 
 // ---- thermodynamic monitor
-int ThermoMonitor::off(const char *fn) { return fail(MP_ESTATE, "%s: the thermodynamic monitor is off (mp_sampler_set_thermo)", fn); }
+const MonitorNames ThermoMonitor::kNames = {"the thermodynamic monitor", "mp_sampler_set_thermo"};
 
 int ThermoMonitor::make(const char *fn, int n_walkers, int n_ensembles, int ndim, int64_t discard, size_t sampler_cap,
                         std::unique_ptr<ThermoMonitor> *out) {
-    if (discard < 0) return fail(MP_EINVAL, "%s: discard must be >= 0 (-1 turns the monitor off), got %lld", fn, (long long)discard);
-    std::unique_ptr<ThermoMonitor> m(new ThermoMonitor(n_walkers, n_ensembles, ndim, discard));
-    m->chunk_cap = (int)m->capped(sampler_cap);
+    if (int rc = check_discard(fn, discard, " (-1 turns the monitor off)")) return rc;
+    std::unique_ptr<ThermoMonitor> m(new ThermoMonitor(kNames, n_walkers, n_ensembles, ndim, discard, sampler_cap));
     const size_t ne = (size_t)n_ensembles;
     int rc;
     if ((rc = m->sum.ensure(ne)) || (rc = m->n_finite.ensure(ne)) || (rc = m->n_nonfinite.ensure(ne))) return rc;
@@ -270,14 +276,15 @@ int ThermoMonitor::restart(hipStream_t st) {
     return MP_OK;
 }
 
-int ThermoMonitor::feed(const double *lnp, int chunk, int64_t step0, int64_t frozen_from, hipStream_t st) {
+int ThermoMonitor::feed(const ChainRows &c, hipStream_t st) {
     mp::ThermoArgs a{};
-    a.lnp = lnp; a.sum = sum.p; a.n_finite = n_finite.p; a.n_nonfinite = n_nonfinite.p;
+    const int chunk = c.rows;
+    a.lnp = c.lnp; a.sum = sum.p; a.n_finite = n_finite.p; a.n_nonfinite = n_nonfinite.p;
     a.n_walkers = n_walkers; a.n_ensembles = n_ensembles;
     int first;
     take(chunk, &first);
     // (the steps before the freeze that lie behind the discard are passed over as well)
-    a.first = (int)std::min<int64_t>(chunk, std::max<int64_t>(first, frozen_from - step0));
+    a.first = (int)std::min<int64_t>(chunk, std::max<int64_t>(first, c.frozen_from - c.step0));
     a.rows = chunk - a.first;
     if (a.rows == 0) return MP_OK;
     const int rc = launched(mp::launch_thermo(a, st));
@@ -294,16 +301,15 @@ int ThermoMonitor::read(double *sum_out, int64_t *n_finite_out, int64_t *n_nonfi
 }
 
 // ---- sample reservoir
-int ResMonitor::off(const char *fn) { return fail(MP_ESTATE, "%s: the sample reservoir is off (mp_sampler_set_reservoir)", fn); }
+const MonitorNames ResMonitor::kNames = {"the sample reservoir", "mp_sampler_set_reservoir"};
 
 int ResMonitor::make(const char *fn, int n_walkers, int n_ensembles, int ndim, int size, uint64_t seed, int64_t discard,
                      size_t sampler_cap, std::unique_ptr<ResMonitor> *out) {
     if (size < 0 || size > MP_RESERVOIR_MAX_ROWS) return fail(MP_EINVAL, "%s: size must be in [0, %d] (MP_RESERVOIR_MAX_ROWS; 0 turns the monitor off), got %d", fn, MP_RESERVOIR_MAX_ROWS, size);
-    if (discard < 0) return fail(MP_EINVAL, "%s: discard must be >= 0, got %lld", fn, (long long)discard);
-    std::unique_ptr<ResMonitor> m(new ResMonitor(n_walkers, n_ensembles, ndim, discard));
+    if (int rc = check_discard(fn, discard)) return rc;
+    std::unique_ptr<ResMonitor> m(new ResMonitor(kNames, n_walkers, n_ensembles, ndim, discard, sampler_cap));
     m->size = size; m->seed = seed;
     m->cand_cap = std::max(n_walkers, mp::kResCandCap);   // a slice is one step at least
-    m->chunk_cap = (int)m->capped(sampler_cap);
     const size_t ne = (size_t)n_ensembles, held = ne * (size_t)size, cand = ne * (size_t)m->cand_cap;
     int rc;
     if ((rc = m->key.ensure(held)) || (rc = m->step.ensure(held)) || (rc = m->walker.ensure(held)) || (rc = m->lnp.ensure(held)) ||
@@ -334,8 +340,9 @@ int ResMonitor::restart(hipStream_t st) {
     return MP_OK;
 }
 
-int ResMonitor::feed(const double *chain, const double *lnp_rows, int chunk, int64_t step0, hipStream_t st) {
-    mp::ResArgs a = args(chain, lnp_rows);
+int ResMonitor::feed(const ChainRows &c, hipStream_t st) {
+    mp::ResArgs a = args(c.chain, c.lnp);
+    const int chunk = c.rows;
     int first;
     const int rows = take(chunk, &first);
     if (rows == 0) return MP_OK;
@@ -343,18 +350,12 @@ int ResMonitor::feed(const double *chain, const double *lnp_rows, int chunk, int
     for (int r = first; r < chunk; r += slice) {
         a.row0 = r;
         a.rows = std::min(slice, chunk - r);
-        a.t0 = step0 + r;
+        a.t0 = c.step0 + r;
         int rc = launched(mp::launch_res_filter(a, st));
         if (!rc) rc = launched(mp::launch_res_merge(a, st));
         if (rc) return rc;
     }
     n += rows;
-    return MP_OK;
-}
-
-int ResMonitor::ready(const char *fn, int ensemble, hipStream_t st) const {
-    if (ensemble < 0 || ensemble >= n_ensembles) return fail(MP_EINVAL, "%s: ensemble must be in [0, %d), got %d", fn, n_ensembles, ensemble);
-    HIP_TRY(hipStreamSynchronize(st));
     return MP_OK;
 }
 

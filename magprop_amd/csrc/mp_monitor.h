@@ -4,8 +4,9 @@
 // (mp_sampler_set_reservoir; kernels mp_reservoir.hip).
 //
 // Internal, like mp_host.h.  A monitor knows the shape of the chain, the device rows it is fed and a stream, and nothing of the
-// sampler: mp_sampler.cpp holds one of each behind its entry points, and the probe libraries mp_probe_acf.hip,
-// mp_probe_post.hip and mp_probe_reservoir.hip drive the same functions over crafted chains.  A function that reports an error names the entry point `fn`.
+// sampler: mp_sampler.cpp holds one of each behind its entry points and restarts, feeds and refuses through ChainMonitor, and
+// the probe libraries mp_probe_acf.hip, mp_probe_post.hip and mp_probe_reservoir.hip drive the same functions over crafted
+// chains.  A function that reports an error names the entry point `fn`.
 #pragma once
 #include <memory>
 
@@ -17,14 +18,26 @@
 
 #pragma GCC visibility push(hidden)
 
-// What every monitor keeps: the shape of the chain and the count of the steps that went in.
+// What a monitor type is called in messages and the entry point that turns it on and off (every type states its own as kNames);
+// off(): MP_ESTATE "<fn>: <what> is off (<setter>)", the answer of a read-out while the sampler holds no such monitor
+struct MonitorNames { const char *what, *setter; int off(const char *fn) const; };
+
+// What a chunk of mp_sampler_run offers the monitors: `rows` steps chain[rows][n_total][ndim] with their lnp[rows][n_total] on
+// the device, the first of them step `step0`; frozen_from is the first step on the ladder's final state (0: a fixed ladder)
+struct ChainRows { const double *chain, *lnp; int rows; int64_t step0, frozen_from; };
+
+// What every monitor keeps, the shape of the chain and the count of the steps that went in, and what the sampler does to a
+// monitor without knowing which one it is: restart, feed, run_only.
 struct ChainMonitor {
+    const MonitorNames &names;
     int n_walkers = 0, n_ensembles = 0, n_total = 0, ndim = 0;
     int chunk_cap = 0;              // most steps per chunk of mp_sampler_run while the monitor is on
     int64_t n = 0;                  // steps accumulated
     int64_t discard = 0, skip = 0;  // steps to pass over after a (re)start; how many of them are left
-    ChainMonitor(int n_walkers, int n_ensembles, int ndim, int64_t discard)
-        : n_walkers(n_walkers), n_ensembles(n_ensembles), n_total(n_walkers * n_ensembles), ndim(ndim), discard(discard) {}
+    ChainMonitor(const MonitorNames &names, int n_walkers, int n_ensembles, int ndim, int64_t discard, size_t sampler_cap)
+        : names(names), n_walkers(n_walkers), n_ensembles(n_ensembles), n_total(n_walkers * n_ensembles), ndim(ndim),
+          chunk_cap((int)capped(sampler_cap)), discard(discard) {}
+    virtual ~ChainMonitor() = default;
     // chunks of at most 64 MB of chain rows while a monitor is on, and no longer than the sampler's own chunks (sampler_cap)
     size_t capped(size_t sampler_cap) const {
         return std::max<size_t>(1, std::min<size_t>(sampler_cap, ((size_t)64 << 20) / ((size_t)n_total * ndim * sizeof(double))));
@@ -36,6 +49,15 @@ struct ChainMonitor {
         skip -= *first;
         return chunk - *first;
     }
+    // Empty the monitor: nothing accumulated, `discard` steps from now.  A chunk into the monitor: every monitor reads the fields
+    // of ChainRows that it needs.  Both stream-ordered.
+    virtual int restart(hipStream_t st) = 0;
+    virtual int feed(const ChainRows &c, hipStream_t st) = 0;
+    int run_only(const char *fn) const;   // MP_ESTATE: the walker-sharded entry point `fn` does not feed the monitor
+    // The prologue of a read-out by ensemble: the ensemble exists, and what was fed has been accumulated
+    int ready(const char *fn, int ensemble, hipStream_t st) const;
+    // the check of a `discard` argument; `clause` goes behind "must be >= 0"
+    static int check_discard(const char *fn, int64_t discard, const char *clause = "");
 };
 
 // Accumulators and the history ring of mp_acf.h, fed once per chunk of mp_sampler_run from the device slab of chain rows.
@@ -45,16 +67,15 @@ struct AcfMonitor : ChainMonitor {
     DevBuf<double> hist, S, T, H, pivot, rho, f, tau;
     DevBuf<int32_t> window;
     using ChainMonitor::ChainMonitor;
+    static const MonitorNames kNames;
 
-    static int off(const char *fn);
     static int check(const char *fn, int max_lag, int64_t discard);   // max_lag = 0, which turns the monitor off, passes
     // A monitor of max_lag >= 1 checked lags with its buffers, within MP_ACF_MAX_BYTES; restart() comes next
     static int make(const char *fn, int n_walkers, int n_ensembles, int ndim, int max_lag, int64_t discard, size_t sampler_cap,
                     std::unique_ptr<AcfMonitor> *out);
-    // Empty the monitor (stream-ordered): the series starts again, `discard` steps from now.
-    int restart(hipStream_t st);
-    // The `chunk` rows chain[chunk][n_series] of a chunk into the monitor (stream-ordered)
-    int feed(const double *chain, int chunk, hipStream_t st);
+    int restart(hipStream_t st) override;
+    // The rows c.chain[rows][n_series] of a chunk into the monitor (stream-ordered)
+    int feed(const ChainRows &c, hipStream_t st) override;
     // rho, the walker means, windows and taus of the samples so far into the monitor's buffers; waits for them
     int finalise(const char *fn, double c, hipStream_t st);
     // read-outs behind mp_sampler_get_autocorr, _get_acf (after finalise) and _get_autocorr_sums (after a wait for the stream)
@@ -74,18 +95,16 @@ struct PostMonitor : ChainMonitor {
     DevBuf<double> d_par, mom, best_x, best_lnp;
     DevBuf<int64_t> hist1, hist2, outside2, nfin, best_idx;
     using ChainMonitor::ChainMonitor;
+    static const MonitorNames kNames;
 
-    static int off(const char *fn);
     // A monitor of bins1 != 0 bins with its buffers, after the checks of bins1, bins2, discard, the range, the ensemble count and
     // MP_POST_MAX_BYTES in this order; restart() comes next
     static int make(const char *fn, int n_walkers, int n_ensembles, int ndim, int bins1, int bins2, const double *lower,
                     const double *upper, int64_t discard, size_t sampler_cap, std::unique_ptr<PostMonitor> *out);
     // Empty the monitor (stream-ordered): no sample, best = none, `discard` steps from now.
-    int restart(hipStream_t st);
-    // The `chunk` rows chain[chunk][n_total][ndim] and lnp[chunk][n_total] of a chunk into the monitor (stream-ordered)
-    int feed(const double *chain, const double *lnp, int chunk, hipStream_t st);
-    // The prologue of the read-outs: the ensemble exists, and what was fed has been accumulated
-    int ready(const char *fn, int ensemble, hipStream_t st) const;
+    int restart(hipStream_t st) override;
+    // The rows c.chain[rows][n_total][ndim] and c.lnp[rows][n_total] of a chunk into the monitor (stream-ordered)
+    int feed(const ChainRows &c, hipStream_t st) override;
     // read-outs behind mp_sampler_get_posterior_hist1, _hist2, _moments and _best (after ready)
     int read_hist1(int ensemble, int64_t *hist1_out, int64_t *below, int64_t *above, int64_t *nonfinite, int64_t *n_samples) const;
     int read_hist2(const char *fn, int ensemble, int64_t *hist2_out, int64_t *outside2_out) const;
@@ -102,16 +121,15 @@ struct ThermoMonitor : ChainMonitor {
     DevBuf<double> sum;
     DevBuf<int64_t> n_finite, n_nonfinite;
     using ChainMonitor::ChainMonitor;
+    static const MonitorNames kNames;
 
-    static int off(const char *fn);
     // A monitor with its buffers, after the check of discard; restart() comes next
     static int make(const char *fn, int n_walkers, int n_ensembles, int ndim, int64_t discard, size_t sampler_cap,
                     std::unique_ptr<ThermoMonitor> *out);
-    // Empty the monitor (stream-ordered): no sample, `discard` steps from now.
-    int restart(hipStream_t st);
-    // The rows lnp[chunk][n_total] of a chunk whose first row is step `step0` into the monitor (stream-ordered): those behind the
-    // steps still to be passed over, and of them the steps >= frozen_from (the first step on the ladder's final state)
-    int feed(const double *lnp, int chunk, int64_t step0, int64_t frozen_from, hipStream_t st);
+    int restart(hipStream_t st) override;
+    // The rows c.lnp[rows][n_total] of a chunk whose first row is step c.step0 into the monitor (stream-ordered): those behind the
+    // steps still to be passed over, and of them the steps >= c.frozen_from
+    int feed(const ChainRows &c, hipStream_t st) override;
     // read-out behind mp_sampler_get_thermo (after a wait for the stream)
     int read(double *sum_out, int64_t *n_finite_out, int64_t *n_nonfinite_out, int64_t *n_steps) const;
 };
@@ -127,19 +145,17 @@ struct ResMonitor : ChainMonitor {
     DevBuf<uint32_t> n_cand;
     DevBuf<double> x, lnp;
     using ChainMonitor::ChainMonitor;
+    static const MonitorNames kNames;
 
-    static int off(const char *fn);
     // A monitor of size != 0 rows per ensemble with its buffers, after the checks of size and discard in this order; restart()
     // comes next
     static int make(const char *fn, int n_walkers, int n_ensembles, int ndim, int size, uint64_t seed, int64_t discard,
                     size_t sampler_cap, std::unique_ptr<ResMonitor> *out);
     // Empty the monitor (stream-ordered): nothing held, nothing seen, everything passes, `discard` steps from now.
-    int restart(hipStream_t st);
-    // The `chunk` rows chain[chunk][n_total][ndim] and lnp[chunk][n_total] of a chunk whose first row is step `step0` into the
-    // monitor (stream-ordered), in slices of whole steps of at most cand_cap samples per ensemble
-    int feed(const double *chain, const double *lnp, int chunk, int64_t step0, hipStream_t st);
-    // The prologue of the read-out: the ensemble exists, and what was fed has been merged
-    int ready(const char *fn, int ensemble, hipStream_t st) const;
+    int restart(hipStream_t st) override;
+    // The rows c.chain[rows][n_total][ndim] and c.lnp[rows][n_total] of a chunk whose first row is step c.step0 into the monitor
+    // (stream-ordered), in slices of whole steps of at most cand_cap samples per ensemble
+    int feed(const ChainRows &c, hipStream_t st) override;
     // read-out behind mp_sampler_get_reservoir (after ready): the first max_rows held rows in the order (step, walker)
     int read(int ensemble, int max_rows, double *x_out, double *lnprob, int64_t *step_out, int32_t *walker_out, uint64_t *key_out,
              int *n_rows, int64_t *n_seen) const;

@@ -133,7 +133,7 @@ int mpa_run_monitor(const double *x, int n, int n_walkers, int n_ensembles, int 
             break;
         }
         m->skip = first;
-        rc = m->feed(d_slab, first + rows, nullptr);
+        rc = m->feed(ChainRows{d_slab, nullptr, first + rows, 0, 0}, nullptr);
         if (rc == 0 && finalise_after[i] && m->n >= 2) rc = m->finalise(kFn, c_mid, nullptr);   // run_mcmc_until's check between two chunks
     }
     if (rc == 0) rc = m->finalise(kFn, c, nullptr);

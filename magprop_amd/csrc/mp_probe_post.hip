@@ -122,7 +122,7 @@ int mpq_run_posterior(const double *chain, const double *lnp, int n, int n_walke
             break;
         }
         m->skip = 1;
-        rc = m->feed(d_slab, d_lnp, rows + 1, nullptr);
+        rc = m->feed(ChainRows{d_slab, d_lnp, rows + 1, 0, 0}, nullptr);
     }
     return B.finish(probe_rc(rc));
 }

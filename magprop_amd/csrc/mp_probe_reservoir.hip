@@ -105,7 +105,7 @@ int mpr_run_reservoir(const double *chain, const double *lnp, int n, int n_walke
             break;
         }
         m->skip += 1;   // the junk row in front, whose step would be t - 1
-        rc = m->feed(d_slab, d_lnp, rows + 1, t - 1, nullptr);
+        rc = m->feed(ChainRows{d_slab, d_lnp, rows + 1, t - 1, 0}, nullptr);
         t += rows;
     }
     for (int e = 0; e < n_ensembles && rc == 0; ++e) {

@@ -55,6 +55,13 @@ struct mp_sampler {
     std::unique_ptr<PostMonitor> post; // the posterior monitor; null: off
     std::unique_ptr<ThermoMonitor> thermo;   // the thermodynamic monitor; null: off
     std::unique_ptr<ResMonitor> res;   // the sample reservoir; null: off
+    // f(monitor) for every monitor that is on, in the order they are fed, up to the first that fails: its code, else MP_OK
+    template <class F>
+    int each_monitor(F &&f) const {
+        for (ChainMonitor *m : {(ChainMonitor *)acf.get(), (ChainMonitor *)post.get(), (ChainMonitor *)thermo.get(), (ChainMonitor *)res.get()})
+            if (int rc = m ? f(*m) : MP_OK) return rc;
+        return MP_OK;
+    }
     // ladder adaptation (mp_sampler_set_ladder_adaptation; kernels mp_ladder.hip); n_adapt = 0: off, a fixed ladder.  Every step of
     // mp_sampler_run makes one update while ladder_t < n_adapt: update t lies behind step t, so steps >= n_adapt run on the frozen
     // ladder
@@ -82,6 +89,20 @@ static size_t slab_chunk_cap(const mp_sampler *s, size_t perm_cap) {
 }
 static size_t perm_chunk_cap(const mp_sampler *s) {
     return std::max<size_t>(1, std::min<size_t>((size_t)16 << 20, (size_t)32 * MP_BAD_WINDOW) / (size_t)s->n_total);
+}
+
+// The body of the four set functions: with the lock held and the device idle the old monitor goes; if one is asked for (`on`),
+// make(the sampler's own chunk cap) puts the new one into `slot` and it is restarted, and whatever fails leaves the monitor off.
+template <class M, class Make>
+static int set_monitor(mp_sampler *s, std::unique_ptr<M> &slot, bool on, Make &&make) {
+    Held held(s->h, s->ev);
+    HIP_TRY(hipDeviceSynchronize());
+    slot.reset();
+    if (!on) return MP_OK;
+    int rc = make(slab_chunk_cap(s, perm_chunk_cap(s)));
+    if (rc) return rc;
+    if ((rc = slot->restart(s->ev->stream))) slot.reset();
+    return rc;
 }
 
 // Move the device window of failed proposals into the host log and reset it.  The caller has made sure that no kernel
@@ -445,12 +466,7 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
         HIP_TRY(hipStreamSynchronize(ev->stream));
     }
     s->have_state = true;
-    int rc = MP_OK;
-    if (s->acf) rc = s->acf->restart(ev->stream);     // the series is broken
-    if (!rc && s->post) rc = s->post->restart(ev->stream);
-    if (!rc && s->thermo) rc = s->thermo->restart(ev->stream);
-    if (!rc && s->res) rc = s->res->restart(ev->stream);
-    return rc;
+    return s->each_monitor([&](ChainMonitor &m) { return m.restart(ev->stream); });   // the series is broken
 }
 
 // Enqueue step steps_done + row of mp_sampler_run on the handle's stream: split d_perm, chain row `row` of the device slab when
@@ -514,13 +530,10 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
     // chunks of steps so that the device-resident chain slab stays below ~256 MB, the splits below ~64 MB, and the
     // window of failed proposals (drained after every chunk) overflows only if more than 1 in 32 proposals fails
     const size_t perm_cap = perm_chunk_cap(s);
-    const bool monitor = s->acf != nullptr, post = s->post != nullptr, thermo = s->thermo != nullptr, res = s->res != nullptr;
-    const bool slab = chain || monitor || post || thermo || res;   // the monitors read the chain rows from the device slab
-    int chunk_max = (int)std::min<size_t>((size_t)std::max(n_steps, 1), slab ? slab_chunk_cap(s, perm_cap) : perm_cap);
-    if (monitor) chunk_max = std::min(chunk_max, s->acf->chunk_cap);
-    if (post) chunk_max = std::min(chunk_max, s->post->chunk_cap);
-    if (thermo) chunk_max = std::min(chunk_max, s->thermo->chunk_cap);
-    if (res) chunk_max = std::min(chunk_max, s->res->chunk_cap);
+    bool slab = chain != nullptr;   // the monitors read the chain rows from the device slab
+    int monitor_cap = std::max(n_steps, 1);
+    s->each_monitor([&](ChainMonitor &m) { slab = true; monitor_cap = std::min(monitor_cap, m.chunk_cap); return MP_OK; });
+    const int chunk_max = (int)std::min<size_t>((size_t)monitor_cap, slab ? slab_chunk_cap(s, perm_cap) : perm_cap);
     constexpr int kSub = 8;   // steps per batch of splits: the host draws the next batch while the GPU runs this one
     int rc;
     // A whole step per launch (mp_kernels.hip stretch_step_kernel: 3 n/2 evaluations, a third of them speculative) while
@@ -553,10 +566,8 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
                 if ((rc = enqueue_step(s, s->d_perm.p + (size_t)st * nt, st, mv, slab, whole, fits))) return rc;
             }
         }
-        if (monitor && (rc = s->acf->feed(s->d_chain.p, chunk, ev->stream))) return rc;
-        if (post && (rc = s->post->feed(s->d_chain.p, s->d_chain_lnp.p, chunk, ev->stream))) return rc;
-        if (thermo && (rc = s->thermo->feed(s->d_chain_lnp.p, chunk, (int64_t)s->steps_done, s->n_adapt, ev->stream))) return rc;
-        if (res && (rc = s->res->feed(s->d_chain.p, s->d_chain_lnp.p, chunk, (int64_t)s->steps_done, ev->stream))) return rc;
+        const ChainRows rows{s->d_chain.p, s->d_chain_lnp.p, chunk, (int64_t)s->steps_done, s->n_adapt};
+        if ((rc = s->each_monitor([&](ChainMonitor &m) { return m.feed(rows, ev->stream); }))) return rc;
         if (chain) {
             HIP_TRY(hipMemcpyAsync(chain + (size_t)done * row, s->d_chain.p, (size_t)chunk * row * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
             HIP_TRY(hipMemcpyAsync(chain_lnprob + (size_t)done * nt, s->d_chain_lnp.p, (size_t)chunk * nt * sizeof(double), hipMemcpyDeviceToHost, ev->stream));
@@ -571,18 +582,13 @@ int mp_sampler_run(mp_sampler *s, int n_steps, double *chain, double *chain_lnpr
 
 // ---- autocorrelation monitor (mp_monitor.h AcfMonitor)
 int mp_sampler_set_autocorr(mp_sampler *s, int max_lag, int64_t discard) {
-    if (!s) return fail(MP_EINVAL, "mp_sampler_set_autocorr: NULL sampler");
-    int rc = AcfMonitor::check("mp_sampler_set_autocorr", max_lag, discard);
+    const char *fn = "mp_sampler_set_autocorr";
+    if (!s) return fail(MP_EINVAL, "%s: NULL sampler", fn);
+    const int rc = AcfMonitor::check(fn, max_lag, discard);   // (a bad call leaves the old monitor on)
     if (rc) return rc;
-    Held held(s->h, s->ev);
-    HIP_TRY(hipDeviceSynchronize());
-    s->acf.reset();
-    if (max_lag == 0) return MP_OK;
-    if ((rc = AcfMonitor::make("mp_sampler_set_autocorr", s->n_walkers, s->n_ensembles, s->ndim, max_lag, discard,
-                               slab_chunk_cap(s, perm_chunk_cap(s)), &s->acf)))
-        return rc;
-    if ((rc = s->acf->restart(s->ev->stream))) s->acf.reset();
-    return rc;
+    return set_monitor(s, s->acf, max_lag != 0, [&](size_t cap) {
+        return AcfMonitor::make(fn, s->n_walkers, s->n_ensembles, s->ndim, max_lag, discard, cap, &s->acf);
+    });
 }
 
 int mp_sampler_get_autocorr(mp_sampler *s, double c, double *tau, int32_t *window, int64_t *n_samples) {
@@ -590,7 +596,7 @@ int mp_sampler_get_autocorr(mp_sampler *s, double c, double *tau, int32_t *windo
     if (!(c > 0.0) || !std::isfinite(c)) return fail(MP_EINVAL, "mp_sampler_get_autocorr: c must be finite and > 0, got %g", c);
     Held held(s->h, s->ev);
     if (n_samples) *n_samples = s->acf ? s->acf->n : 0;
-    if (!s->acf) return AcfMonitor::off("mp_sampler_get_autocorr");
+    if (!s->acf) return AcfMonitor::kNames.off("mp_sampler_get_autocorr");
     const int rc = s->acf->finalise("mp_sampler_get_autocorr", c, s->ev->stream);
     return rc ? rc : s->acf->read_tau(tau, window);
 }
@@ -599,7 +605,7 @@ int mp_sampler_get_acf(mp_sampler *s, int ensemble, int max_rows, double *acf) {
     if (!s || !acf || max_rows < 0) return fail(MP_EINVAL, "mp_sampler_get_acf: bad argument");
     if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "mp_sampler_get_acf: ensemble must be in [0, %d), got %d", s->n_ensembles, ensemble);
     Held held(s->h, s->ev);
-    if (!s->acf) return AcfMonitor::off("mp_sampler_get_acf");
+    if (!s->acf) return AcfMonitor::kNames.off("mp_sampler_get_acf");
     const int rc = s->acf->finalise("mp_sampler_get_acf", 5.0, s->ev->stream);
     return rc ? rc : s->acf->read_acf(ensemble, max_rows, acf);
 }
@@ -609,7 +615,7 @@ int mp_sampler_get_autocorr_sums(mp_sampler *s, int ensemble, double *S, double 
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_autocorr_sums: NULL sampler");
     if (ensemble < 0 || ensemble >= s->n_ensembles) return fail(MP_EINVAL, "mp_sampler_get_autocorr_sums: ensemble must be in [0, %d), got %d", s->n_ensembles, ensemble);
     Held held(s->h, s->ev);
-    if (!s->acf) return AcfMonitor::off("mp_sampler_get_autocorr_sums");
+    if (!s->acf) return AcfMonitor::kNames.off("mp_sampler_get_autocorr_sums");
     HIP_TRY(hipStreamSynchronize(s->ev->stream));
     return s->acf->read_sums(ensemble, S, T, H, tail, pivot, n_samples);
 }
@@ -617,20 +623,14 @@ int mp_sampler_get_autocorr_sums(mp_sampler *s, int ensemble, double *S, double 
 // ---- posterior monitor (mp_monitor.h PostMonitor)
 int mp_sampler_set_posterior(mp_sampler *s, int bins1, int bins2, const double *lower, const double *upper, int64_t discard) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_set_posterior: NULL sampler");
-    Held held(s->h, s->ev);
-    HIP_TRY(hipDeviceSynchronize());
-    s->post.reset();
-    if (bins1 == 0) return MP_OK;
-    int rc = PostMonitor::make("mp_sampler_set_posterior", s->n_walkers, s->n_ensembles, s->ndim, bins1, bins2, lower, upper, discard,
-                               slab_chunk_cap(s, perm_chunk_cap(s)), &s->post);
-    if (rc) return rc;
-    if ((rc = s->post->restart(s->ev->stream))) s->post.reset();
-    return rc;
+    return set_monitor(s, s->post, bins1 != 0, [&](size_t cap) {
+        return PostMonitor::make("mp_sampler_set_posterior", s->n_walkers, s->n_ensembles, s->ndim, bins1, bins2, lower, upper, discard, cap, &s->post);
+    });
 }
 
 // The prologue of the posterior read-outs: the monitor is on, the ensemble exists, and what was fed has been accumulated
 static int post_ready(mp_sampler *s, const char *fn, int ensemble) {
-    return s->post ? s->post->ready(fn, ensemble, s->ev->stream) : PostMonitor::off(fn);
+    return s->post ? s->post->ready(fn, ensemble, s->ev->stream) : PostMonitor::kNames.off(fn);
 }
 
 int mp_sampler_get_posterior_hist1(mp_sampler *s, int ensemble, int64_t *hist1, int64_t *below, int64_t *above,
@@ -665,21 +665,15 @@ int mp_sampler_get_posterior_best(mp_sampler *s, int ensemble, double *x, double
 // ---- thermodynamic monitor (mp_monitor.h ThermoMonitor)
 int mp_sampler_set_thermo(mp_sampler *s, int64_t discard) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_set_thermo: NULL sampler");
-    Held held(s->h, s->ev);
-    HIP_TRY(hipDeviceSynchronize());
-    s->thermo.reset();
-    if (discard == -1) return MP_OK;
-    int rc = ThermoMonitor::make("mp_sampler_set_thermo", s->n_walkers, s->n_ensembles, s->ndim, discard,
-                                 slab_chunk_cap(s, perm_chunk_cap(s)), &s->thermo);
-    if (rc) return rc;
-    if ((rc = s->thermo->restart(s->ev->stream))) s->thermo.reset();
-    return rc;
+    return set_monitor(s, s->thermo, discard != -1, [&](size_t cap) {
+        return ThermoMonitor::make("mp_sampler_set_thermo", s->n_walkers, s->n_ensembles, s->ndim, discard, cap, &s->thermo);
+    });
 }
 
 int mp_sampler_get_thermo(mp_sampler *s, double *sum_lnl, int64_t *n_finite, int64_t *n_nonfinite, int64_t *n_steps) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_thermo: NULL sampler");
     Held held(s->h, s->ev);
-    if (!s->thermo) return ThermoMonitor::off("mp_sampler_get_thermo");
+    if (!s->thermo) return ThermoMonitor::kNames.off("mp_sampler_get_thermo");
     HIP_TRY(hipStreamSynchronize(s->ev->stream));
     return s->thermo->read(sum_lnl, n_finite, n_nonfinite, n_steps);
 }
@@ -687,15 +681,9 @@ int mp_sampler_get_thermo(mp_sampler *s, double *sum_lnl, int64_t *n_finite, int
 // ---- sample reservoir (mp_monitor.h ResMonitor)
 int mp_sampler_set_reservoir(mp_sampler *s, int size, uint64_t seed, int64_t discard) {
     if (!s) return fail(MP_EINVAL, "mp_sampler_set_reservoir: NULL sampler");
-    Held held(s->h, s->ev);
-    HIP_TRY(hipDeviceSynchronize());
-    s->res.reset();
-    if (size == 0) return MP_OK;
-    int rc = ResMonitor::make("mp_sampler_set_reservoir", s->n_walkers, s->n_ensembles, s->ndim, size, seed, discard,
-                              slab_chunk_cap(s, perm_chunk_cap(s)), &s->res);
-    if (rc) return rc;
-    if ((rc = s->res->restart(s->ev->stream))) s->res.reset();
-    return rc;
+    return set_monitor(s, s->res, size != 0, [&](size_t cap) {
+        return ResMonitor::make("mp_sampler_set_reservoir", s->n_walkers, s->n_ensembles, s->ndim, size, seed, discard, cap, &s->res);
+    });
 }
 
 int mp_sampler_get_reservoir(mp_sampler *s, int ensemble, int max_rows, double *x, double *lnprob, int64_t *step, int32_t *walker,
@@ -703,7 +691,7 @@ int mp_sampler_get_reservoir(mp_sampler *s, int ensemble, int max_rows, double *
     if (!s) return fail(MP_EINVAL, "mp_sampler_get_reservoir: NULL sampler");
     if (max_rows < 0) return fail(MP_EINVAL, "mp_sampler_get_reservoir: max_rows must be >= 0, got %d", max_rows);
     Held held(s->h, s->ev);
-    if (!s->res) return ResMonitor::off("mp_sampler_get_reservoir");
+    if (!s->res) return ResMonitor::kNames.off("mp_sampler_get_reservoir");
     const int rc = s->res->ready("mp_sampler_get_reservoir", ensemble, s->ev->stream);
     return rc ? rc : s->res->read(ensemble, max_rows, x, lnprob, step, walker, key, n_rows, n_seen);
 }
@@ -742,8 +730,9 @@ int mp_sampler_row_doubles(const mp_sampler *s) { return s ? s->ndim + 3 : 0; }
 int mp_sampler_n_slots(const mp_sampler *s) { return s ? (s->n_walkers / 2) * s->n_ensembles : 0; }
 
 // The prologue of the four sharded entry points (fn: the entry point, which every message starts with): a sampler without state,
-// a tempered one and one with a move table are refused (those run through mp_sampler_run only); otherwise the handle's lock and
-// device are held for the call, d_perm is the split of the current step and the sampler notes work on a caller's stream.
+// a tempered one, one with a move table and one with a monitor on are refused (those run through mp_sampler_run only); otherwise
+// the handle's lock and device are held for the call, d_perm is the split of the current step and the sampler notes work on a
+// caller's stream.
 struct ShardCall {
     Held held;
     const int32_t *d_perm = nullptr;
@@ -753,15 +742,8 @@ struct ShardCall {
         else if (s->n_temps) rc = fail(MP_ESTATE, "%s: a tempered sampler runs on one device only (mp_sampler_run)", fn);
         else if (!s->moves.empty())
             rc = fail(MP_ESTATE, "%s: a sampler with a move table (mp_sampler_set_moves) runs on one device only (mp_sampler_run)", fn);
-        else if (s->acf)
-            rc = fail(MP_ESTATE, "%s: the autocorrelation monitor (mp_sampler_set_autocorr) is fed by mp_sampler_run only; turn it off first", fn);
-        else if (s->post)
-            rc = fail(MP_ESTATE, "%s: the posterior monitor (mp_sampler_set_posterior) is fed by mp_sampler_run only; turn it off first", fn);
-        else if (s->thermo)
-            rc = fail(MP_ESTATE, "%s: the thermodynamic monitor (mp_sampler_set_thermo) is fed by mp_sampler_run only; turn it off first", fn);
-        else if (s->res)
-            rc = fail(MP_ESTATE, "%s: the sample reservoir (mp_sampler_set_reservoir) is fed by mp_sampler_run only; turn it off first", fn);
-        else if (!(rc = current_split(s, (hipStream_t)stream, &d_perm))) s->ext_stream_work = true;
+        else rc = s->each_monitor([&](ChainMonitor &m) { return m.run_only(fn); });   // the first monitor that is on refuses
+        if (!rc && !(rc = current_split(s, (hipStream_t)stream, &d_perm))) s->ext_stream_work = true;
     }
 };
 

@@ -134,12 +134,16 @@ class EnsembleSampler:
             cp, lp = _capi.ptr(chain), _capi.ptr(lnp)
         _capi.check(self._L.mp_sampler_run(self._s, int(nsteps), cp, lp), "mp_sampler_run")
         if store and nsteps > 0:
-            self._chain = chain if self._chain is None else np.concatenate([self._chain, chain])
-            self._lnp = lnp if self._lnp is None else np.concatenate([self._lnp, lnp])
-            self._steps = np.concatenate([self._steps, self.iteration + np.arange(int(nsteps), dtype=np.int64)])
+            self._append(chain, lnp, self.iteration)
         self.iteration += int(nsteps)
         self._flush_fbad()
         return self.get_last_sample()[0]
+
+    def _append(self, chain, lnp, first_step):
+        """The rows of a finished run, whose first step has the index first_step, behind the stored chain."""
+        self._chain = chain if self._chain is None else np.concatenate([self._chain, chain])
+        self._lnp = lnp if self._lnp is None else np.concatenate([self._lnp, lnp])
+        self._steps = np.concatenate([self._steps, first_step + np.arange(len(chain), dtype=np.int64)])
 
     # ---- failed proposals (the reference's fbad file)
     def get_bad(self, first_row=0, max_rows=None):
@@ -242,9 +246,7 @@ class EnsembleSampler:
     def _at_temp(self, a, temp):
         if temp is None:
             return a
-        t = int(temp)
-        if not 0 <= t < self.ntemps:
-            raise ValueError(f"temp must be in 0..{self.ntemps - 1}, got {temp}")
+        t = self._ensemble_index(0, temp)      # (group 0's beta_t ensemble has the index t)
         if a is None:
             return None
         v = a.reshape((a.shape[0], self.ngroups, self.ntemps, self.nwalkers) + a.shape[2:])[:, :, t]
@@ -411,14 +413,7 @@ class EnsembleSampler:
         temp=t its beta_t ensemble."""
         if self._res is None:
             raise _capi.MagpropAmdError("the sample reservoir is off (monitor_samples)")
-        e = int(ensemble)
-        if self.betas is not None or temp is not None:
-            t = 0 if temp is None else int(temp)
-            if not 0 <= t < self.ntemps:
-                raise ValueError(f"temp must be in 0..{self.ntemps - 1}, got {temp}")
-            if not 0 <= e < self.ngroups:
-                raise ValueError(f"ensemble must be in 0..{self.ngroups - 1}, got {ensemble}")
-            e = e * self.ntemps + t
+        e = self._ensemble_index(ensemble, temp, grouped=self.betas is not None)
         k = self._res[0]
         out = _capi.read_back(self._L.mp_sampler_get_reservoir, self._s, [
             ("x", (k, self.ndim), np.float64), ("log_prob", k, np.float64), ("step", k, np.int64), ("walker", k, np.int32),
@@ -589,19 +584,24 @@ class EnsembleSampler:
                     "mp_sampler_set_posterior")
         self._post = (bins, bins2, lo, hi)
 
-    def _post_ensemble(self, ensemble, temp):
-        """Index of `ensemble` in the library's order; temp=t: ensemble counts the beta_t ensembles, as get_chain(temp=) does."""
-        if self._post is None:
-            raise _capi.MagpropAmdError("the posterior monitor is off (monitor_posterior)")
+    def _ensemble_index(self, ensemble, temp, grouped=False, note=""):
+        """Index of `ensemble` in the library's order.  temp=t: `ensemble` counts the groups, as get_chain(temp=) does, and the
+        index is that of the group's beta_t ensemble; temp=None: `ensemble` is that index already, or with grouped=True the
+        group whose beta = 1 ensemble is meant.  note: what the message about a bad group says behind the range."""
         e = int(ensemble)
-        if temp is None:
+        if temp is None and not grouped:
             return e
-        t = int(temp)
+        t = 0 if temp is None else int(temp)
         if not 0 <= t < self.ntemps:
             raise ValueError(f"temp must be in 0..{self.ntemps - 1}, got {temp}")
         if not 0 <= e < self.ngroups:
-            raise ValueError(f"ensemble must be in 0..{self.ngroups - 1} with temp=, got {ensemble}")
+            raise ValueError(f"ensemble must be in 0..{self.ngroups - 1}{note}, got {ensemble}")
         return e * self.ntemps + t
+
+    def _post_ensemble(self, ensemble, temp):
+        if self._post is None:
+            raise _capi.MagpropAmdError("the posterior monitor is off (monitor_posterior)")
+        return self._ensemble_index(ensemble, temp, note=" with temp=")
 
     def get_posterior(self, ensemble=0, temp=None):
         """The posterior monitor's summary of one ensemble (temp=t: the beta_t ensemble of group `ensemble`): a dict with
@@ -684,9 +684,7 @@ class EnsembleSampler:
             if done < max_steps:                       # an early stop gives the unused rows back (refcheck: no other owner here)
                 chain.resize((done,) + chain.shape[1:], refcheck=False)
                 lnp.resize((done,) + lnp.shape[1:], refcheck=False)
-            self._chain = chain if self._chain is None else np.concatenate([self._chain, chain])
-            self._lnp = lnp if self._lnp is None else np.concatenate([self._lnp, lnp])
-            self._steps = np.concatenate([self._steps, first_step + np.arange(done, dtype=np.int64)])
+            self._append(chain, lnp, first_step)
         return self.get_last_sample()[0]
 
 
