@@ -12,7 +12,8 @@ from conftest import TRUTHS, TYPES
 from moves_restated import DE
 from raw_abi import RawSampler, dp, ip, lp, table_args
 from test_autocorr_cpu import MEASURED_DISCREPANCY
-from test_gpu_nested import launch_class, long_sets, posterior_cases, synth_sets  # noqa: F401  (the two handles are fixtures)
+from test_gpu_nested import (LONG_MIXED_LENGTHS, assert_long_reference_is_not_vacuous, launch_class, long_cases,  # noqa: F401
+                             long_mixed_sets, long_sets, posterior_cases, synth_sets)  # (the three handles are fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -190,6 +191,7 @@ def drive_posterior(h, ens_ds, truths, n_half, steps, seed, build, wide=False):
         assert n_bad > 0 and np.any(~np.isfinite(lnp0) & np.isfinite(ref.lnp[-1]))
     print(f"launch {n} {build}: {calls[0]} batches, start lnprob -inf {int(np.sum(~np.isfinite(lnp0)))}, bad {n_bad}, "
           + ", ".join(f"{k} {want[k].tolist()}" for k in COUNTERS) + f", mu {ref.state.mu.tolist()}")
+    return ref, pos, lnp0
 
 
 @pytest.mark.parametrize("case", ["team-1", "team-2", "wave-4", "wave-2"])
@@ -211,6 +213,27 @@ def test_failed_evaluations_reach_the_fbad_window_and_lost_walkers_escape(synth_
 
 def test_posterior_slices_match_lnprob_batch_on_the_long_builds(long_sets):  # noqa: F811
     drive_posterior(long_sets, [0, 1], [TRUTHS["Humped"], TRUTHS["Humped"]], 8, 1, 20261108, (4, 1, 1))
+
+
+@pytest.mark.parametrize("case", ["team-2", "wave-4", "wave-2"])
+def test_posterior_slices_match_lnprob_batch_on_the_long_builds_of_every_class(long_mixed_sets, case):  # noqa: F811
+    """slice_half_kernel's LONG builds beyond (4, 1, 1): one ensemble on Humped next to one on a light curve of 410 or 1 944
+    points (long_cases); the 50-point set comes first, so the launches start the ensembles in another order than they are
+    numbered.  Conditions on the inputs, from the restatement: the ensemble on the long set moved a walker and turned a shrink
+    point down, and its best lnprob is finite."""
+    h = long_mixed_sets
+    c = long_cases(h.n_simd)[case]
+    ds, n_half = c["ds"], c["nbatch"]
+    lens = [LONG_MIXED_LENGTHS[d] for d in ds]
+    assert sorted(range(len(ds)), key=lambda e: -lens[e]) != list(range(len(ds)))
+    ref, pos, lnp0 = drive_posterior(h, ds, [TRUTHS["Humped"]] * len(ds), n_half, c["iters"], 20261304, c["build"])
+    acc = ref.acc.reshape(len(ds), -1).sum(axis=1)
+    assert_long_reference_is_not_vacuous(ds, acc, acc + ref.state.ncontract, ref.lnp[-1].reshape(len(ds), -1).max(axis=1))
+    if case == "wave-4":   # a kernel that read the other ensemble's light curve would start from these values instead
+        ens = np.arange(len(pos)) // (2 * n_half)
+        first, other = (h.lnprob_batch(pos, ds_id=np.asarray(d, dtype=np.int32)[ens]) for d in (ds, ds[::-1]))
+        assert np.array_equal(first, lnp0)
+        assert np.all(np.any((first != other).reshape(len(ds), -1), axis=1))
 
 
 # ---------------------------------------------------------------- tempering, mixtures, monitors

@@ -187,6 +187,56 @@ def long_sets(gsynth, glonglc):
     h.close()
 
 
+LONG_MIXED_LENGTHS = (50, 112, 410, 1944)      # ds k of long_mixed_sets
+
+
+@pytest.fixture(scope="module")
+def long_mixed_sets(gsynth, glonglc):
+    """One handle with Humped (ds 0, 50 points) and the Humped-type light curves of 112, 410 and 1 944 points (ds 1, 2, 3):
+    every launch runs the LONG builds, a short light curve next to ones of one and of many chunks behind the 64 captured
+    observations."""
+    from magprop_amd import synth
+    h = synth_handle()
+    h.set_prior(synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK)
+    sets = [(gsynth["Humped_x"], gsynth["Humped_y"], gsynth["Humped_yerr"])]
+    sets += [tuple(glonglc[f"synth{n}_ds"]) for n in LONG_MIXED_LENGTHS[1:]]
+    assert tuple(len(s[0]) for s in sets) == LONG_MIXED_LENGTHS
+    for k, s in enumerate(sets):
+        h.set_dataset(k, *s)
+    yield h
+    h.close()
+
+
+def long_cases(ns):
+    """The LONG cases of every resident driver on long_mixed_sets, one per build, at the smallest shapes that reach it (the
+    formulas of posterior_cases here, of smc_cases, of the optimizer's and the simplex search's tables and of family_cases):
+    ds: the datasets of the runs, ensembles or populations, the 50-point set first, so that every case scores a short light
+    curve on a LONG build and the lengths are not in descending order as numbered (the sampler's ens_order is then not the
+    identity); over the four cases every long set appears.  nbatch: workgroups per run of a nested walk launch and slots per
+    ensemble of a slice-move launch; n: particles per SMC run; pop: members of a launch of the optimizer, over all populations;
+    n_simplex: simplexes (10 workgroups each at ndim 6), cycling through ds; whole / half: walkers per ensemble of a sampler by
+    whole steps and by half-step launches (half has no two-per-SIMD team).  iters: iterations, stages, generations or steps."""
+    return {"team-1": dict(ds=[0, 3, 1], build=(4, 1, 1), nbatch=8, n=ns // 16, pop=60, n_simplex=ns // 50, whole=16, half=16,
+                           iters=4),
+            "team-2": dict(ds=[0, 2], build=(4, 1, 2), nbatch=3 * ns // 16, n=3 * ns // 16, pop=3 * ns // 8, n_simplex=ns // 25,
+                           whole=3 * ns // 32, half=None, iters=3),
+            "wave-4": dict(ds=[0, 3], build=(1, 4, 1), nbatch=3 * ns // 8, n=3 * ns // 8, pop=3 * ns // 4,
+                           n_simplex=5 * ns // 64, whole=ns // 4, half=ns // 4, iters=2),
+            "wave-2": dict(ds=[0, 3], build=(1, 2, 2), nbatch=5 * ns // 8, n=5 * ns // 8, pop=5 * ns // 4, n_simplex=ns // 8,
+                           whole=3 * ns // 8, half=5 * ns // 4, iters=1)}
+
+
+def assert_long_reference_is_not_vacuous(ds, accepted, evaluated, best):
+    """Conditions on the inputs of a long_cases run, read off the restatement alone: every run (ensemble, population) on a
+    light curve of more than 64 points accepted and rejected at least one evaluated point, and its best lnprob is finite."""
+    accepted, evaluated, best = np.asarray(accepted), np.asarray(evaluated), np.asarray(best)
+    long_runs = [r for r, d in enumerate(ds) if LONG_MIXED_LENGTHS[d] > 64]
+    assert long_runs and len(long_runs) < len(ds)
+    for r in long_runs:
+        assert 0 < accepted[r] < evaluated[r], (r, accepted[r], evaluated[r])
+        assert np.isfinite(best[r]), (r, best[r])
+
+
 def drive_posterior(h, run_ds, truths, nbatch, chunks, walks, seed, build=None):
     """RawNested(target=0, ds=run_ds) on h and the restatement in step, nlive = 2 nbatch: equal after the live-set evaluation
     and behind every mp_nested_run of `chunks` -- n iterations each, or (n, (slices, mu, max_steps_out, max_shrink)) after an
@@ -260,6 +310,25 @@ def test_posterior_walks_match_lnprob_batch_on_the_long_builds(long_sets):
     truths = [TRUTHS["Humped"], TRUTHS["Humped"]]
     s, (_, _, status0), ev = drive_posterior(long_sets, [0, 1], truths, 8, (1, 3), 10, 20261220, (4, 1, 1))
     assert_reference_is_not_vacuous(s, status0, 10)
+
+
+@pytest.mark.parametrize("case", ["team-2", "wave-4", "wave-2"])
+def test_posterior_walks_match_lnprob_batch_on_the_long_builds_of_every_class(long_mixed_sets, case):
+    """nest_walk_kernel's LONG builds beyond (4, 1, 1): one run on Humped next to one on a light curve of 410 or 1 944 points
+    (long_cases).  At wave-2 the live-set evaluation of the restatement is a batch of more than 2 n_simd rows on light curves
+    of different lengths, which mp_lnprob_batch evaluates longest first (launch_lnprob_ordered) without changing a row's
+    bits (test_gpu_batched.py::test_longest_light_curves_first_launch_order)."""
+    h = long_mixed_sets
+    c = long_cases(h.n_simd)[case]
+    truths = [TRUTHS["Humped"]] * len(c["ds"])
+    s, (live0, lnl0, status0), ev = drive_posterior(h, c["ds"], truths, c["nbatch"], (c["iters"],), 3, 20261301, c["build"])
+    assert_reference_is_not_vacuous(s, status0, 3)
+    assert_long_reference_is_not_vacuous(c["ds"], s.nacc, s.ncall, s.lnl.max(axis=1))
+    assert (lnl0.size > 2 * h.n_simd) == (case == "wave-2")
+    if case == "team-2":   # a kernel that read the other run's light curve would start from these values instead
+        swap = BatchEvaluator(h, c["ds"][::-1]).at(lnl0.size)
+        lnl1 = nr.start(live0, swap, with_runs=True).lnl
+        assert not np.array_equal(lnl1[0], lnl0[0]) and not np.array_equal(lnl1[1], lnl0[1])
 
 
 def test_chunks_of_one_iteration_equal_one_unsplit_run():

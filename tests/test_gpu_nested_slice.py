@@ -15,7 +15,8 @@ import nest_slice_restated as sr
 import test_nested_slice_cpu as edge
 from conftest import TRUTHS, TYPES
 from raw_abi import lp, synth_handle
-from test_gpu_nested import (EVIDENCE_INFLATION, RawNested, _assert_equal, _gaussian_lnz, drive_posterior, long_sets,  # noqa: F401
+from test_gpu_nested import (EVIDENCE_INFLATION, BatchEvaluator, RawNested, _assert_equal, _gaussian_lnz,  # noqa: F401
+                             assert_long_reference_is_not_vacuous, drive_posterior, long_cases, long_mixed_sets, long_sets,
                              posterior_cases, synth_sets)
 
 pytestmark = pytest.mark.gpu
@@ -191,6 +192,25 @@ def test_posterior_slices_match_lnprob_batch_on_the_long_builds(long_sets):
     truths = [TRUTHS["Humped"], TRUTHS["Humped"]]
     s, (_, _, status0), ev = drive_posterior(long_sets, [0, 1], truths, 8, ((1, (2, 1.0, 4, 16)), 3), 10, 20261192, (4, 1, 1))
     _assert_slices_are_not_vacuous(s, status0)
+
+
+@pytest.mark.parametrize("case", ["team-2", "wave-4", "wave-2"])
+def test_posterior_slices_match_lnprob_batch_on_the_long_builds_of_every_class(long_mixed_sets, case):
+    """nest_slice_kernel's LONG builds beyond (4, 1, 1): one run on Humped next to one on a light curve of 410 or 1 944
+    points (long_cases), 1 slice per walk with 4 steps out and 16 shrink points (2 slices on the team)."""
+    h = long_mixed_sets
+    c = long_cases(h.n_simd)[case]
+    truths = [TRUTHS["Humped"]] * len(c["ds"])
+    chunks = ((c["iters"], (2 if case == "team-2" else 1, 1.0, 4, 16)),)
+    s, (live0, lnl0, status0), ev = drive_posterior(h, c["ds"], truths, c["nbatch"], chunks, 3, 20261302, c["build"])
+    _assert_slices_are_not_vacuous(s, status0)
+    # a slice that moved accepted its last point; a shrink point that was rejected was evaluated
+    assert_long_reference_is_not_vacuous(c["ds"], s.nacc, s.nacc + s.ncontract, s.lnl.max(axis=1))
+    assert np.all(s.ncall >= s.nacc + s.ncontract)
+    if case == "team-2":   # a kernel that read the other run's light curve would start from these values instead
+        swap = BatchEvaluator(h, c["ds"][::-1]).at(lnl0.size)
+        lnl1 = nr.start(live0, swap, with_runs=True).lnl
+        assert not np.array_equal(lnl1[0], lnl0[0]) and not np.array_equal(lnl1[1], lnl0[1])
 
 
 def test_switching_walks_between_iterations_on_the_posterior(synth_sets):

@@ -10,7 +10,7 @@ import pytest
 import nm_restated as nm
 from conftest import GOLDEN, TRUTHS, TYPES
 from raw_abi import dp, ip, synth_handle
-from test_gpu_nested import launch_class
+from test_gpu_nested import assert_long_reference_is_not_vacuous, launch_class, long_cases, long_mixed_sets  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -193,6 +193,36 @@ def test_posterior_matches_the_restatement_on_a_long_light_curve(glonglc):
         h.close()
     _assert_equal(st, ref)
     assert np.all(ref.nit == 13) and np.all(np.isfinite(ref.lnp[:, 0]))
+
+
+@pytest.mark.parametrize("case", ["team-1", "team-2", "wave-4", "wave-2"])
+def test_posterior_matches_the_restatement_on_the_long_builds_of_every_class(long_mixed_sets, case):
+    """nm_eval_kernel's LONG builds on every class: the four launch shapes of the test on every build on a handle that holds
+    light curves of 50, 112, 410 and 1 944 points, the simplexes alternating between Humped and the long sets of the case
+    (long_cases), 12 iterations as there.  Conditions on the inputs, from the restatement: every simplex on a long set took a
+    candidate and turned one down (an iteration of two or more evaluations), and its best vertex is finite.  (With 3 iterations
+    on the one-wavefront launches some simplexes only ever reflected, at 1 evaluation each -- of the 40 and the 64
+    simplexes on 1 944 points number 3 and number 9 were the first --, which a seed does not cure at that many simplexes; 12
+    iterations take 0.01 s.)"""
+    h = long_mixed_sets
+    c = long_cases(h.n_simd)[case]
+    n_simplex, iterations = c["n_simplex"], 12
+    assert launch_class(10 * n_simplex, h.n_simd) == c["build"] and 1 <= n_simplex <= 1024
+    ds = [c["ds"][k % len(c["ds"])] for k in range(n_simplex)]
+    seed = 60 + n_simplex
+    sim0 = np.stack([nm.default_simplex(np.array(TRUTHS["Humped"]) + 0.05 * r)
+                     for r in np.random.default_rng(seed).standard_normal((n_simplex, 6))])
+    st, ref = _posterior_run(h, sim0, ds, iterations)
+    _assert_equal(st, ref)
+    assert np.all(ref.nit == iterations + 1) and np.all(ref.outcomes.sum(axis=1) == iterations)
+    taken = ref.outcomes[:, :nm.SHRINK].sum(axis=1)
+    assert_long_reference_is_not_vacuous(ds, taken, ref.nfev - 7, ref.lnp[:, 0])
+    if case == "team-1":   # a kernel that read another simplex's light curve would start from these values instead
+        swapped = [ds[1], ds[0]] + ds[2:]
+        first, other = (_posterior_run(h, sim0, d, 0)[1] for d in (ds, swapped))
+        differ = np.any(np.sort(first.lnp, axis=1) != np.sort(other.lnp, axis=1), axis=1)
+        assert differ.tolist() == [True, True] + [False] * (n_simplex - 2)
+    print(f"long launch {10 * n_simplex} {c['build']}: outcomes {ref.outcomes.sum(axis=0).tolist()}")
 
 
 def test_break_up_corners_keep_their_status_and_store_no_nan(gcorners):

@@ -9,7 +9,7 @@ import pytest
 import de_restated as de
 from conftest import GOLDEN, TRUTHS, TYPES
 from raw_abi import dp, ip, synth_handle
-from test_gpu_nested import launch_class
+from test_gpu_nested import assert_long_reference_is_not_vacuous, launch_class, long_cases, long_mixed_sets  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -107,35 +107,30 @@ def test_humped_posterior_matches_the_restatement_with_lnprob_batch():
     assert np.all(np.isfinite(ref.lnp.max(axis=1)))
 
 
-def _humped_and_classic(long_set=None):
-    """A handle with the synthetic prior, Humped (ds 0) and Classic (ds 1), or Humped and a light curve of more than 64 points."""
+def _humped_and_classic():
+    """A handle with the synthetic prior, Humped (ds 0) and Classic (ds 1)."""
     from magprop_amd import synth
     g = np.load(GOLDEN + "/golden_synth.npz")
     h = synth_handle()
     h.set_prior(synth.PRIOR_LOWER, synth.PRIOR_UPPER, synth.LOG_MASK)
     h.set_dataset(0, g["Humped_x"], g["Humped_y"], g["Humped_yerr"])
-    if long_set is None:
-        h.set_dataset(1, g["Classic_x"], g["Classic_y"], g["Classic_yerr"])
-    else:
-        assert len(long_set[0]) > 64
-        h.set_dataset(1, *long_set)
+    h.set_dataset(1, g["Classic_x"], g["Classic_y"], g["Classic_yerr"])
     return h
 
 
 @pytest.mark.parametrize("case, strategy", [("team-2", de.BEST1BIN), ("team-2", de.RAND1BIN), ("wave-4", de.BEST1BIN),
-                                            ("wave-2", de.BEST1BIN), ("long", de.BEST1BIN)])
-def test_posterior_matches_the_restatement_with_lnprob_batch_on_the_other_builds(case, strategy, glonglc):
+                                            ("wave-2", de.BEST1BIN)])
+def test_posterior_matches_the_restatement_with_lnprob_batch_on_the_other_builds(case, strategy):
     """Two populations on different datasets (population 0 on ds 1, population 1 on ds 0) at the smallest launch of each build
     the 60-member test does not run -- a team with two wavefronts per SIMD (3/8 of the SIMDs), one wavefront per walker with 4
-    steps per lane (3/4) and with 2 (5/4), and the LONG builds on a handle that holds a light curve of 112 points: 5 generations
-    (20 at the two smaller launches) equal the restatement whose evaluations are mp_lnprob_batch calls of the launch's size with
-    every row's dataset."""
+    steps per lane (3/4) and with 2 (5/4): 5 generations (20 at the smaller launch) equal the restatement whose evaluations are
+    mp_lnprob_batch calls of the launch's size with every row's dataset.  (The LONG builds: below.)"""
     from magprop_amd import optimize, synth
-    h = _humped_and_classic(tuple(glonglc["synth112_ds"]) if case == "long" else None)
+    h = _humped_and_classic()
     try:
         ns = h.n_simd
         n, build, gens = {"team-2": (3 * ns // 8, (4, 1, 2), 20), "wave-4": (3 * ns // 4, (1, 4, 1), 5),
-                          "wave-2": (5 * ns // 4, (1, 2, 2), 5), "long": (60, (4, 1, 1), 20)}[case]
+                          "wave-2": (5 * ns // 4, (1, 2, 2), 5)}[case]
         popsize, ds = n // 2, [1, 0]
         assert launch_class(2 * popsize, ns) == build and 5 <= popsize <= 1024
         lo, hi = synth.PRIOR_LOWER, synth.PRIOR_UPPER
@@ -162,6 +157,54 @@ def test_posterior_matches_the_restatement_with_lnprob_batch_on_the_other_builds
     assert np.all(ref.nit == gens) and np.all(np.isfinite(ref.lnp.max(axis=1)))
     assert np.all(np.any(ref.pop != pop0, axis=(1, 2)))
     print(f"{case}: launch {2 * popsize} {build}, flagged members at the end {int(np.sum(ref.status != 0))}")
+
+
+@pytest.mark.parametrize("case", ["team-1", "team-2", "wave-4", "wave-2"])
+def test_posterior_matches_the_restatement_with_lnprob_batch_on_the_long_builds(long_mixed_sets, case):
+    """opt_trial_kernel's LONG builds on every class: a handle that holds light curves of 50, 112, 410 and 1 944 points, one
+    population on Humped and the others on long sets (long_cases), 20 generations on the 60-member team, 10 on the larger
+    team, 3 and 2 on the one-wavefront launches.  The restatement goes generation by generation, so that the members every
+    population replaced and kept are counted."""
+    from magprop_amd import optimize, synth
+    h = long_mixed_sets
+    c = long_cases(h.n_simd)[case]
+    ds, gens = c["ds"], {"team-1": 20, "team-2": 10, "wave-4": 3, "wave-2": 2}[case]
+    n_pops, popsize = len(ds), c["pop"] // len(ds)
+    assert launch_class(n_pops * popsize, h.n_simd) == c["build"] and 5 <= popsize <= 1024
+    lo, hi = synth.PRIOR_LOWER, synth.PRIOR_UPPER
+    rng = np.random.default_rng(7)
+    pop0 = np.stack([optimize.latin_hypercube(rng, popsize, lo, hi) for _ in range(n_pops)])
+
+    def evaluator(pop_ds):
+        ids = np.repeat(np.array(pop_ds, dtype=np.int32), popsize)
+
+        def evaluate(rows):
+            assert rows.shape == (n_pops * popsize, 6)
+            return h.lnprob_batch(rows, ds_id=ids, want_status=True)
+        return evaluate
+
+    ref = de.start(pop0, evaluator(ds))
+    lnp0 = ref.lnp.copy()
+    replaced = np.zeros(n_pops, dtype=np.int64)
+    for g in range(1, gens + 1):
+        before = ref.pop.copy()
+        de.generation(ref, g, evaluator(ds), 102, de.BEST1BIN, 0.5, 1.0, 0.7, 0.01, 0.0, lo, hi)
+        replaced += np.any(ref.pop != before, axis=2).sum(axis=1)
+    opt = RawOptimizer(h, popsize, n_pops, 6, lo, hi, 102, de.BEST1BIN, 0, ds=ds)
+    try:
+        opt.set_population(pop0.reshape(-1, 6))
+        opt.run(gens)
+        st = opt.state()
+    finally:
+        opt.close()
+    _assert_equal(st, ref)
+    assert np.all(ref.nit == gens)
+    assert_long_reference_is_not_vacuous(ds, replaced, gens * np.full(n_pops, popsize), ref.lnp.max(axis=1))
+    if case == "team-1":   # a kernel that read another population's light curve would start from these values instead
+        lnp1 = de.start(pop0, evaluator([ds[1], ds[0]] + ds[2:])).lnp
+        assert not np.array_equal(lnp1[0], lnp0[0]) and not np.array_equal(lnp1[1], lnp0[1]) and np.array_equal(lnp1[2], lnp0[2])
+    print(f"long {case}: launch {n_pops * popsize} {c['build']}, replaced {replaced.tolist()} of {gens * popsize}, flagged members "
+          f"at the end {int(np.sum(ref.status != 0))}")
 
 
 @pytest.fixture(scope="module")

@@ -19,7 +19,8 @@ from moves_restated import DE, SNOOKER
 from oracle.stretch_oracle import M32, _draw, philox4x32_10, split, step_rows, u01
 from raw_abi import RawSampler, dp
 from test_gpu_moves_slice import FAILS
-from test_gpu_nested import BatchEvaluator, launch_class, long_sets, synth_sets  # noqa: F401  (the two handles are fixtures)
+from test_gpu_nested import (LONG_MIXED_LENGTHS, BatchEvaluator, launch_class, long_cases, long_mixed_sets, long_sets,  # noqa: F401
+                             synth_sets)  # (the three handles are fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -60,12 +61,13 @@ def eval_rows(cls, k, ns):
     return n
 
 
-def start_near_truths(ens_ds, nw, seed, fails=False):
-    """truths + 1e-2 randn per ensemble; fails: the first half of every ensemble in a ball of 0.05 around a point whose model
-    fails, clipped into the prior box."""
+def start_near_truths(ens_ds, nw, seed, fails=False, truths=None):
+    """truths + 1e-2 randn per ensemble (truths: of TYPES[d] unless given); fails: the first half of every ensemble in a ball
+    of 0.05 around a point whose model fails, clipped into the prior box."""
     from magprop_amd import synth
     rng = np.random.default_rng(seed)
-    pos = np.concatenate([np.array(TRUTHS[TYPES[d]]) + 1.0e-2 * rng.standard_normal((nw, 6)) for d in ens_ds])
+    truths = [TRUTHS[TYPES[d]] for d in ens_ds] if truths is None else truths
+    pos = np.concatenate([np.array(t) + 1.0e-2 * rng.standard_normal((nw, 6)) for t in truths])
     if fails:
         for e in range(len(ens_ds)):
             pos[e * nw:e * nw + nw // 2] = np.clip(FAILS + 0.05 * rng.standard_normal((nw // 2, 6)), synth.PRIOR_LOWER,
@@ -135,14 +137,14 @@ def assert_device_equals(dev, ref, start):
 
 
 def drive_posterior(h, ens_ds, nw, steps, seed=SEED, table=None, whole=True, betas=None, build=None, fails=False, runs=None,
-                    autocorr=0, outside=False, compare=True):
+                    autocorr=0, outside=False, compare=True, truths=None):
     """A sampler of len(ens_ds) ensembles of nw walkers on h (target 0) and the restatement in step.  Equal afterwards: the
     start's lnprob, chain, chain lnprob, final pos / lnprob / n_accepted, n_bad, the logged rows as multisets and, tempered, the
     swap counts (compare=False: left to the caller).  Returns the restatement's Run, the batch's start lnprob, the device's
     results and an evaluator of the step's class: rows, ensembles -> lnprob."""
     ns, n_ens = h.n_simd, len(ens_ds)
     n_slots = (nw // 2) * n_ens
-    pos = start_near_truths(ens_ds, nw, seed, fails)
+    pos = start_near_truths(ens_ds, nw, seed, fails, truths)
     dev = device_run(h, ens_ds, nw, pos, runs or (steps,), seed, table, whole, betas, autocorr)
     ev = BatchEvaluator(h, ens_ds)
     # the decisions start from the device's own start values, which are compared with the batch in assert_device_equals
@@ -159,6 +161,19 @@ def drive_posterior(h, ens_ds, nw, steps, seed=SEED, table=None, whole=True, bet
         assert_device_equals(dev, ref, start)
     assert_not_vacuous(ref, n_ens, tempered=betas is not None, outside=outside)
     return ref, start, dev, ev.at(n_eval)
+
+
+def drive_long(h, ens_ds, nw, steps, **kw):
+    """drive_posterior on long_mixed_sets (every set is Humped-type: starts around Humped's truths).  The ensembles mix a light
+    curve of at most 64 points with longer ones and their lengths do not descend as numbered, so the launches start them in
+    another order (ens_order; stable: mp_sampler.cpp stretch_args); every ensemble's best lnprob is finite (that each accepted
+    and rejected an evaluated proposal: assert_not_vacuous)."""
+    lens = [LONG_MIXED_LENGTHS[d] for d in ens_ds]
+    assert sorted(range(len(ens_ds)), key=lambda e: -lens[e]) != list(range(len(ens_ds)))
+    assert min(lens) <= 64 < max(lens)
+    out = drive_posterior(h, ens_ds, nw, steps, truths=[TRUTHS["Humped"]] * len(ens_ds), **kw)
+    assert np.all(np.isfinite(out[0].lnp[-1].reshape(len(ens_ds), nw).max(axis=1)))
+    return out
 
 
 # ---------------------------------------------------------------- rows first: the stage that localises a failure
@@ -329,7 +344,9 @@ KDE_CASES = {"team-1": dict(handle="synth_sets", family="team-1", steps=3),
              "wave-4": dict(handle="synth_sets", family="wave-4", steps=1),
              "wave-2": dict(handle="synth_sets", family="wave-2", steps=1),
              "long": dict(handle="long_sets", ens_ds=[0, 1], nw=16, steps=2, seed=SEED + 2),
-             "tempered": dict(handle="synth_sets", ens_ds=[2, 2, 0, 0], nw=16, steps=3, seed=SEED + 3, betas=LADDER)}
+             "tempered": dict(handle="synth_sets", ens_ds=[2, 2, 0, 0], nw=16, steps=3, seed=SEED + 3, betas=LADDER),
+             "long-wave-4": dict(handle="long_mixed_sets", long="wave-4", steps=1, seed=SEED + 24),
+             "long-wave-2": dict(handle="long_mixed_sets", long="wave-2", steps=1, seed=SEED + 25)}
 _KDE_RUNS = {}
 
 
@@ -338,11 +355,16 @@ def kde_run(request, case):
     if case not in _KDE_RUNS:
         c = dict(KDE_CASES[case])
         h = request.getfixturevalue(c.pop("handle"))
+        drive = drive_posterior
         if "family" in c:
             ens_ds, nw, build = family_cases(h.n_simd)["kde"][c.pop("family")]
+        elif "long" in c:
+            lc = long_cases(h.n_simd)[c.pop("long")]
+            ens_ds, nw, build, drive = lc["ds"], lc["half"], lc["build"], drive_long
+            assert nw - nw // 2 > 6                                           # (n_comp > ndim: a full-rank covariance)
         else:
             ens_ds, nw, build = c.pop("ens_ds"), c.pop("nw"), (4, 1, 1)
-        ref, start, dev, evaluate = drive_posterior(h, ens_ds, nw, c.pop("steps"), table=KDE_TABLE, build=build, compare=False, **c)
+        ref, start, dev, evaluate = drive(h, ens_ds, nw, c.pop("steps"), table=KDE_TABLE, build=build, compare=False, **c)
         _KDE_RUNS[case] = ref, start, dev, evaluate, nw
     return _KDE_RUNS[case]
 
@@ -395,6 +417,65 @@ def test_posterior_chains_match_lnprob_batch_on_the_long_builds(long_sets, what)
     drive_posterior(long_sets, ens_ds, nw, 2, seed=SEED + 2, whole=what != "tempered", betas=LADDER if what == "tempered" else None, build=(4, 1, 1))
 
 
+LONG_IDS = ([("step", c) for c in ("team-2", "wave-4", "wave-2")] + [("half", c) for c in ("team-1", "team-2", "wave-4", "wave-2")]
+            + [("diff", c) for c in ("team-1", "wave-4", "wave-2")])
+
+
+@pytest.mark.parametrize("form,case", LONG_IDS)
+def test_posterior_chains_match_lnprob_batch_on_the_long_builds_of_every_class(long_mixed_sets, form, case):
+    """The LONG builds beyond (4, 1, 1) on a handle that holds light curves of 50, 112, 410 and 1 944 points, the ensembles of
+    long_cases: stretch_step_kernel by whole steps (step), the plain untempered stretch_kernel by half-step launches, which
+    take the whole step's class (half: mp_sampler_set_whole_step(0)), and the DIFF builds under the DE + snooker table (diff;
+    their two-per-SIMD team is unreachable through the launchers).  KDE: above; TEMPERED: below."""
+    h = long_mixed_sets
+    c = long_cases(h.n_simd)[case]
+    ens_ds, nw = c["ds"], c["half" if form == "diff" else "whole"]
+    seed = SEED + 10 + LONG_IDS.index((form, case))
+    ref, start, _, _ = drive_long(h, ens_ds, nw, c["iters"], seed=seed, table=DIFF_TABLE if form == "diff" else None,
+                                  whole=form == "step", build=c["build"])
+    if (form, case) == ("half", "team-1"):   # a kernel that read another ensemble's light curve would start from these values
+        pos = start_near_truths(ens_ds, nw, seed, truths=[TRUTHS["Humped"]] * len(ens_ds))
+        n = len(pos)
+        other = BatchEvaluator(h, [ens_ds[1], ens_ds[0]] + ens_ds[2:]).at(n)(pos, np.arange(n) // nw)[0]
+        differ = np.any((other != start).reshape(len(ens_ds), nw), axis=1)
+        assert differ.tolist() == [True, True] + [False] * (len(ens_ds) - 2)
+
+
+def tempered_cases(ns):
+    """The smallest shapes of the TEMPERED builds beyond the roomy team, two groups x ladder (1, 0.3): (walkers of each of the
+    four ensembles, class).  The stretch move by half-step launches, which take the whole step's class; DE + snooker and KDE
+    by their own size (no two-per-SIMD team; their roomy team is here for its LONG build)."""
+    half = {"team-1": (16, (4, 1, 1)), "wave-4": (ns // 8, (1, 4, 1)), "wave-2": (5 * ns // 8, (1, 2, 2))}
+    return {"stretch": {"team-2": (3 * ns // 64, (4, 1, 2)), "wave-4": (ns // 8, (1, 4, 1)), "wave-2": (3 * ns // 16, (1, 2, 2))},
+            "diff": half, "kde": half}
+
+
+TEMPERED_IDS = [(f, c) for f in ("stretch", "diff", "kde") for c in ("team-1", "team-2", "wave-4", "wave-2")
+                if c in tempered_cases(1024)[f]]
+
+
+@pytest.mark.parametrize("handle", ["synth_sets", "long_mixed_sets"])
+@pytest.mark.parametrize("family,case", TEMPERED_IDS)
+def test_tempered_posterior_chains_match_lnprob_batch_beyond_the_roomy_team(request, family, case, handle):
+    """TEMPERED on the classes beyond (4, 1, 1), for the stretch move by half-step launches, DE + snooker and KDE (those two
+    on (4, 1, 1) as well, which no other tempered DE case and no other tempered LONG KDE case runs), on the four 50-point sets
+    and on the handle with the long ones (both ensembles of the second group on the case's long set: TEMPERED LONG); two
+    steps with their swap sweeps, one on the largest launches; a swap was accepted and one refused."""
+    h = request.getfixturevalue(handle)
+    nw, build = tempered_cases(h.n_simd)[family][case]
+    long = handle == "long_mixed_sets"
+    ds = long_cases(h.n_simd)[case]["ds"]
+    seed = SEED + 30 + 2 * TEMPERED_IDS.index((family, case)) + long
+    (drive_long if long else drive_posterior)(h, [ds[0], ds[0], ds[1], ds[1]] if long else [2, 2, 0, 0], nw, 1 if case == "wave-2" else 2,
+                                              seed=seed, table=FAMILY_TABLE[family], whole=False, betas=LADDER, build=build)
+
+
+def test_whole_step_launch_equals_half_step_launches_on_the_long_builds(long_mixed_sets):
+    """The contract of the test at the class boundaries below on the LONG builds: 3 n_simd / 8 slots, one ensemble on Humped
+    and one on 1 944 points, one step by one launch and by two half-step launches gives one chain."""
+    _whole_step_equals_half_steps(long_mixed_sets, [0, 3], (3, 8), False, [TRUTHS["Humped"]] * 2)
+
+
 @pytest.mark.parametrize("whole", [True, False])
 def test_tempered_posterior_chains_match_lnprob_batch(synth_sets, whole):
     """Two groups x ladder (1, 0.3), 16 walkers each, both ensembles of a group on one light curve: the TEMPERED builds and the
@@ -434,13 +515,16 @@ def test_whole_step_launch_equals_half_step_launches_at_the_class_boundaries(syn
     size, 557 of the 768 stored lnprob differed after the step at 3 ns / 8 from the starts near the truths; at 3 ns / 32 the
     two team builds gave the same bits.)  ns / 4, where both sizes choose 4 steps per lane, is the control; fails: half of
     every ensemble starts at the edge of the prior box around a point whose model fails, so that the log has rows."""
-    h = synth_sets
+    _whole_step_equals_half_steps(synth_sets, [1, 2], frac, fails)
+
+
+def _whole_step_equals_half_steps(h, ens_ds, frac, fails, truths=None):
     ns = h.n_simd
     n_slots = frac[0] * ns // frac[1]
-    ens_ds, nw = [1, 2], n_slots
+    nw = n_slots
     assert whole_step_fits(n_slots, ns)
     assert (stretch_class(3 * n_slots, n_slots, ns) != stretch_class(n_slots, n_slots, ns)) == (frac != (1, 4))
-    pos = start_near_truths(ens_ds, nw, SEED + 6, fails)
+    pos = start_near_truths(ens_ds, nw, SEED + 6, fails, truths)
     a = device_run(h, ens_ds, nw, pos, (1,), SEED + 6, whole=True)
     b = device_run(h, ens_ds, nw, pos, (1,), SEED + 6, whole=False)
     differ = np.flatnonzero(a[2][0] != b[2][0])

@@ -13,7 +13,8 @@ import pytest
 import smc_restated as sm
 from conftest import TRUTHS, TYPES
 from raw_abi import dp, ip, synth_handle
-from test_gpu_nested import BatchEvaluator, launch_class, long_sets, posterior_live, synth_sets  # noqa: F401  (two are fixtures)
+from test_gpu_nested import (BatchEvaluator, assert_long_reference_is_not_vacuous, launch_class, long_cases,  # noqa: F401
+                             long_mixed_sets, long_sets, posterior_live, synth_sets)  # (three are fixtures)
 from test_gpu_smc_kernels import device_exp, device_log
 
 pytestmark = pytest.mark.gpu
@@ -148,6 +149,23 @@ def test_posterior_stages_match_lnprob_batch_on_every_build(synth_sets, case):
 def test_posterior_stages_match_lnprob_batch_on_the_long_builds(long_sets):
     """The LONG builds: a handle that also holds a light curve of 112 points, one run on Humped and one on the long set."""
     drive_posterior(long_sets, [0, 1], [TRUTHS["Humped"], TRUTHS["Humped"]], 64, 2, 3, 20261221, (4, 1, 1))
+
+
+@pytest.mark.parametrize("case", ["team-2", "wave-4", "wave-2"])
+def test_posterior_stages_match_lnprob_batch_on_the_long_builds_of_every_class(long_mixed_sets, case):
+    """smc_move_kernel's LONG builds beyond (4, 1, 1): one run on Humped next to one on a light curve of 410 or 1 944 points
+    (long_cases), stages of 3 steps."""
+    h = long_mixed_sets
+    c = long_cases(h.n_simd)[case]
+    ds, n, seed = c["ds"], c["n"], 20261303
+    truths = [TRUTHS["Humped"]] * len(ds)
+    s = drive_posterior(h, ds, truths, n, c["iters"], 3, seed, c["build"])
+    assert_long_reference_is_not_vacuous(ds, s.nacc, s.ncall - n, s.lnl.max(axis=1))
+    if case == "team-2":   # a kernel that read the other run's light curve would start from these values instead
+        x0 = posterior_live(truths, n, seed)
+        lnl0 = sm.start(x0, BatchEvaluator(h, ds).at(len(ds) * n)).lnl
+        lnl1 = sm.start(x0, BatchEvaluator(h, ds[::-1]).at(len(ds) * n)).lnl
+        assert not np.array_equal(lnl1[0], lnl0[0]) and not np.array_equal(lnl1[1], lnl0[1])
 
 
 def _gaussian_runs(n, n_runs, ndim, seed, x0, calls, lo=None, hi=None, walks=4):
