@@ -546,6 +546,9 @@ MP_DEV void walker_eval(const DevShared &sh, const LaunchArgs &a, int walker, do
                         int &sweeps_out, int &tiles_out, TeamX<SPL * W> *tx = nullptr) {
     static_assert(W == 1 || (SPL * W == 4 && !CURVES), "team kernels: 256-step tiles, mode A");
     constexpr int kSPL = SPL, kG = SPL * W, kTile = 64 * kG, kMaxSweeps = kTile + kMaxSweepsMargin;
+    // mode A, one wavefront per walker, four steps per lane (one wavefront per SIMD, nothing to hide an LDS round trip behind):
+    // a kept tile hands its end state to the next one through lanes, and its image holds only what is read back
+    constexpr bool kLaneCarry = !CURVES && W == 1 && kG >= 4;
     const int lane = threadIdx.x & 63;
     const int wave = W > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;   // which wavefront of the walker's team
     const int j0 = wave * kSPL;              // its first step inside a lane's group of kG steps
@@ -1474,16 +1477,48 @@ MP_DEV void walker_eval(const DevShared &sh, const LaunchArgs &a, int walker, do
             for (int s = 0; s < kSPL; ++s) {
                 const int e = e0 + s + 1;
                 const double dM = fma(-M1[s], w.inv_tau, S1[s]);               // dM/dt = Mdotfb - M/tvisc, and its derivative
-                im.W[e] = wg[s]; im.F[e] = Ef[4 + s]; im.M[e] = M1[s]; im.D[e] = dM;
-                im.D2[e] = (CURVES && all_qs) ? ratio[s] : fma(-dM, w.inv_tau, dS1[s]);
-                im.R[e] = d1.rmu[s];
-                if (e == keep) { im.C[0] = S1[s]; im.C[1] = dS1[s]; im.C[2] = iu1[s]; }
+                im.W[e] = wg[s]; im.F[e] = Ef[4 + s]; im.M[e] = M1[s];
+                if constexpr (kLaneCarry) {
+                    // (the hand-over goes through lanes, below: no R, no C.  A tile over single intervals or sub-steps is read at
+                    // its nodes only -- image_state returns them, the history reads W and F -- so its Mdisc derivatives stay out)
+                    if (kind >= 2) { im.D[e] = dM; im.D2[e] = fma(-dM, w.inv_tau, dS1[s]); }
+                } else {
+                    im.D[e] = dM;
+                    im.D2[e] = (CURVES && all_qs) ? ratio[s] : fma(-dM, w.inv_tau, dS1[s]);
+                    im.R[e] = d1.rmu[s];
+                    if (e == keep) { im.C[0] = S1[s]; im.C[1] = dS1[s]; im.C[2] = iu1[s]; }
+                }
             }
             if (lead) {
                 const double dM = fma(-M_s, w.inv_tau, cS0);
-                im.W[0] = om_s; im.F[0] = cf0; im.M[0] = M_s; im.D[0] = dM;
-                if (CURVES && all_qs) { const Vd<1> s0{{cS0}}; im.D2[0] = M_s * rcp_fast(s0)[0]; }
-                else im.D2[0] = fma(-dM, w.inv_tau, cdS0);
+                im.W[0] = om_s; im.F[0] = cf0; im.M[0] = M_s;
+                if constexpr (kLaneCarry) {
+                    if (kind >= 2) { im.D[0] = dM; im.D2[0] = fma(-dM, w.inv_tau, cdS0); }
+                } else {
+                    im.D[0] = dM;
+                    if (CURVES && all_qs) { const Vd<1> s0{{cS0}}; im.D2[0] = M_s * rcp_fast(s0)[0]; }
+                    else im.D2[0] = fma(-dM, w.inv_tau, cdS0);
+                }
+            }
+            if constexpr (kLaneCarry) {
+                // Hand-over through lanes, while the stores drain: the state at the last kept node sits in the registers of the
+                // lane that owns step keep - 1, in its slot (keep - 1) mod 4 -- both wave-uniform -- and goes to every lane from
+                // there instead of through the image (a write, a wait and a read back in LDS).  Nothing below reads the old
+                // values: the observations take the tile's start from the image and its time from t_s, which moves behind them.
+                // (one scalar branch on the slot around seven broadcasts: selecting each value lane by lane first costs three
+                // times as many vector instructions)
+                const int slot = (keep - 1) & 3, owner = (keep - 1) >> 2;
+                double Rk;
+                auto from_slot = [&](int s) {
+                    M_s = lane_bcast(M1[s], owner); om_s = lane_bcast(wg[s], owner); cf0 = lane_bcast(Ef[4 + s], owner);
+                    cS0 = lane_bcast(S1[s], owner); cdS0 = lane_bcast(dS1[s], owner); ciu0 = lane_bcast(iu1[s], owner);
+                    Rk = lane_bcast(d1.rmu[s], owner);
+                };
+                if (slot == 0) from_slot(0);
+                else if (slot == 1) from_slot(1);
+                else if (slot == 2) from_slot(2);
+                else from_slot(3);
+                flags_s = branch_flags(w, Rk, om_s);
             }
             __syncthreads();
 
@@ -1705,7 +1740,11 @@ MP_DEV void walker_eval(const DevShared &sh, const LaunchArgs &a, int walker, do
 
             MP_PHASE(7)
             // ---------------- carry the end of the kept steps to the next tile
-            if constexpr (kG >= 4) {
+            if constexpr (kLaneCarry) {
+                // (the state went through lanes at the commit; the time is the one thing the observations still needed)
+                const double tf_tab = tt.E[max(kind, 1) - 1][keep];
+                t_s = t_s * (kind == 0 ? time_factor(sh, tt, 0, keep) : tf_tab);
+            } else if constexpr (kG >= 4) {
                 // (all the reads of the hand-over issued together, the table value among them: one LDS round trip)
                 const double tf_tab = tt.E[max(kind, 1) - 1][keep], Rk = im.R[keep];
                 M_s = im.M[keep];
