@@ -632,8 +632,39 @@ int mp_sampler_get_ladder_history(mp_sampler *s, int group, int64_t first_row, i
  *                    mp_sampler_set_moves resets them, so a run does not depend on how it is split into calls.  Steps of a
  *                    mixture that draw another move change nothing of it.  Behind the tuning steps, which the user discards, the
  *                    chain is a plain Markov chain.
+ *   MP_MOVE_GAUSSIAN (emcee's GaussianMove: plain Metropolis with a given covariance; the one move that reads nothing of the
+ *                    other walkers, so it runs with 2 walkers) params[0] = scale0 (finite, > 0), params[1] = tune_steps (a whole
+ *                    number in [0, 2^31 - 1]); at most one entry per table; mp_sampler_set_gaussian must have been called, else
+ *                    MP_ESTATE (the params are checked first).  L = the Cholesky factor of the covariance and the mode of
+ *                    mp_sampler_set_gaussian, sigma_e = the scale of the walker's ensemble e (it starts at scale0).  r =
+ *                    Philox(...; c3 = 0x47410000), ln u = ln u01(r2, r3); normals n_2p, n_2p+1 by the KDE move's Box-Muller
+ *                    formula from Philox(...; c3 = 0x47410001 + p).  MP_GAUSS_VECTOR: q_a = x_a + sigma_e (sum_{b <= a} L_ab n_b),
+ *                    the sum in index order from 0.  MP_GAUSS_RANDOM: axis a = pick(u01(r0, r1), ndim), MP_GAUSS_SEQUENTIAL: a =
+ *                    step mod ndim; q_a = x_a + sigma_e (L_aa n_0), the other coordinates unchanged.  Hastings term 0.
+ *                    Tuning (a function of the chain alone, every operation a separately rounded double operation): behind the
+ *                    second half-step of a Gaussian step, for every ensemble, with a = that step's accepted walkers of the
+ *                    ensemble, r = a / n_walkers and t = target_accept: while n_tuned_e < tune_steps, f = (r + t) / (2 t), g = 8 /
+ *                    (8 + n_tuned_e), sigma_e <- sigma_e (1 + g (f - 1)), n_tuned_e += 1.  f is 1 at the target and 1/2 at r = 0,
+ *                    the gain decays like 1/n; the constants are the move's definition.  sigma_e, n_tuned_e and the totals live
+ *                    on the device and survive mp_sampler_run calls and mp_sampler_set_positions; only mp_sampler_set_moves
+ *                    resets them, so split runs give one run's chain.  Steps of a mixture that draw another move change nothing
+ *                    of it.  Behind the tuning steps, which the user discards, the chain is a plain Markov chain.
+ *   MP_MOVE_WALK     (Goodman & Weare 2010's walk move, emcee's WalkMove) params[0] = s: 0 = all n_comp slots of the other half,
+ *                    else a whole number in 2 .. min(n_comp, MP_WALK_MAX_S) (or n_comp itself, which is s = 0); params[1] = 0;
+ *                    n_half >= 2.  r = Philox(...; c3 = 0x57410000), ln u = ln u01(r2, r3).  Members: with s = n_comp, member_i =
+ *                    i; otherwise s distinct slots by Floyd's algorithm, for i = 0 .. s - 1: j = n_comp - s + i, t = pick(u_i, j +
+ *                    1), u_i = u01 of the words (0, 1) for even i, (2, 3) for odd i, of Philox(...; c3 = 0x57410100 + i / 2);
+ *                    member_i = t unless t is a member already, then j.  z_i standard normals by the KDE move's Box-Muller
+ *                    formula, pair p from Philox(...; c3 = 0x57800000 + p).  m = (sum_i x_member_i) / s, q = x_k + (sum_i z_i
+ *                    (x_member_i - m)) / sqrt(s - 1): the covariance of q - x_k is the sample covariance (ddof 1) of the members,
+ *                    without a factorisation, so s < ndim + 1 is allowed.  Both sums run in the KDE move's order over i (thread
+ *                    t of the workgroup takes i = t, t + 64 W, ..., a butterfly over the wavefront, the wavefronts in order).
+ *                    Hastings term 0.
+ * The Gaussian and walk moves run two half-step launches of a kernel of their own (normal_half_kernel; the Gaussian move a tune
+ * launch behind them) and decide beta lnprob(q) - beta lnprob(x_k) > ln u; failed models go to the fbad window.
  * Philox counters c3 in use: 0, 1 (stretch), 2, 3 (DE, snooker), 0x4B00 .. 0x4B05 (KDE), 0x5117 (splits), 0x30FE (move of a
- * step), 0 with half = 2 (swaps), 0x51C00000 + c, c = 0 .. 2 + max_shrink (slice move); the optimizer 0xDE00 .. and 0xDEFF, the
+ * step), 0 with half = 2 (swaps), 0x51C00000 + c, c = 0 .. 2 + max_shrink (slice move), 0x47410000 .. 0x47410000 + (ndim + 1) / 2
+ * (Gaussian move), 0x57410000, 0x57410100 .. 0x5741011F and 0x57800000 + p, p < 2^22 (walk move); the optimizer 0xDE00 .. and 0xDEFF, the
  * nested sampler 0x4E000000 + j (random walk) and 0x4E400000 + 0x100 s + c (slice mode), the SMC sampler 0x534D0000 + c, c = 0
  * (a stage's resampling offset) .. 2 walks (its moves).
  * Mixtures: one move per step for the whole sampler.  With n_moves > 1, step s draws r = Philox(seed; s, 3, 0, 0x30FE) and takes
@@ -642,7 +673,9 @@ int mp_sampler_get_ladder_history(mp_sampler *s, int group, int64_t first_row, i
  * swap sweep when tempered); stretch steps run as mp_sampler_set_whole_step decides.
  * n_moves == 0 restores the default (the stretch move with the a of mp_sampler_create); may be called between runs.
  * MP_EINVAL: NULL sampler or arrays, n_moves outside [0, MP_MAX_MOVES], an unknown kind, a weight that is not finite and > 0,
- * bad params (NaN and inf included), DE with n_half < 2, snooker with n_half < 3, KDE with n_comp < ndim + 1, slice with n_half < 2 or a second slice entry.  With a table
+ * bad params (NaN and inf included), DE with n_half < 2, snooker with n_half < 3, KDE with n_comp < ndim + 1, slice with n_half < 2 or a second slice entry,
+ * a second Gaussian entry, walk with a non-whole s, s = 1, s > n_comp, s > MP_WALK_MAX_S (unless s = n_comp), params[1] != 0 or
+ * n_half < 2.  MP_ESTATE: a Gaussian entry before mp_sampler_set_gaussian.  With a table
  * set (n_moves > 0), the walker-sharded entry points (mp_sampler_halfstep_*, mp_sampler_step_*) return MP_ESTATE.
  */
 #define MP_MOVE_STRETCH 0   /* params: a (> 1)                                              */
@@ -650,6 +683,9 @@ int mp_sampler_get_ladder_history(mp_sampler *s, int group, int64_t first_row, i
 #define MP_MOVE_SNOOKER 2   /* params: gamma_s (> 0)                                         */
 #define MP_MOVE_KDE     3   /* params: bandwidth (0 Scott, -1 Silverman, > 0 factor), 0      */
 #define MP_MOVE_SLICE   4   /* params: mu0 (> 0), tune_steps (whole, 0 .. 2^31 - 1)            */
+#define MP_MOVE_GAUSSIAN 5  /* params: scale0 (finite, > 0), tune_steps (whole, 0 .. 2^31 - 1) */
+#define MP_MOVE_WALK    6   /* params: s (0: all of the other half; else whole, 2 .. min(n_comp, MP_WALK_MAX_S)), 0 */
+#define MP_WALK_MAX_S   64
 #define MP_MAX_MOVES    8
 int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const double *weights,
                          const double *params /* [n_moves][2] */);
@@ -662,6 +698,20 @@ int mp_sampler_set_slice_limits(mp_sampler *s, int max_steps_out, int max_shrink
  * (mu is tuned while that is below tune_steps).  MP_ESTATE when the move table has no slice move. */
 int mp_sampler_get_slice(mp_sampler *s, double *mu, int64_t *nexpand, int64_t *ncontract, int64_t *nfail, int64_t *neval,
                          int64_t *n_tuned);
+/* The covariance and mode of MP_MOVE_GAUSSIAN, to be set before a table with that move.  L[ndim (ndim + 1) / 2]: the Cholesky
+ * factor of the covariance in sampler coordinates, lower triangle by rows (entry (a, b <= a) at a (a + 1) / 2 + b).  mode:
+ * MP_GAUSS_VECTOR (all coordinates at once), MP_GAUSS_RANDOM (one axis drawn per proposal) or MP_GAUSS_SEQUENTIAL (axis step mod
+ * ndim); target_accept: the acceptance fraction the tuning aims at.  May be called between runs; the scales and counters stay.
+ * MP_EINVAL: NULL argument, an unknown mode, a non-finite entry, a diagonal entry that is not > 0, an off-diagonal entry other
+ * than 0 with a single-axis mode (emcee's rule), target_accept outside (0, 1). */
+#define MP_GAUSS_VECTOR     0
+#define MP_GAUSS_RANDOM     1
+#define MP_GAUSS_SEQUENTIAL 2
+int mp_sampler_set_gaussian(mp_sampler *s, const double *L, int mode, double target_accept);
+/* The state of MP_MOVE_GAUSSIAN, each output [n_ensembles] and optional (NULL): the scale sigma now and, since
+ * mp_sampler_set_moves, the proposals made, the proposals accepted and the tuning updates made (at most tune_steps).  MP_ESTATE
+ * when the move table has no Gaussian move. */
+int mp_sampler_get_gaussian(mp_sampler *s, double *sigma, int64_t *n_proposed, int64_t *n_accepted, int64_t *n_tuned);
 /*
  * Proposals inside the prior whose model evaluation failed ('flag' / non-finite): what the reference's lnprob appends
  * to its `fbad` file (code/synthetic_datasets/mcmc_eqns.py:72-79).  The kernels collect them in a device-side window of

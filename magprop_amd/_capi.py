@@ -32,6 +32,8 @@ NEST_MAX_SLICES, NEST_MAX_STEPS_OUT, NEST_MAX_SHRINK = 4096, 4096, 254
 SMC_MIN_PARTICLES, SMC_MAX_PARTICLES, SMC_MAX_WALKS, SMC_MAX_STAGES = 4, 16384, 4096, 1024   # include/magprop_amd.h MP_SMC_*
 SMC_RUNNING, SMC_DONE, SMC_FAILED, SMC_STAGE_LIMIT = 0, 1, 2, 3
 MOVE_SLICE, SLICE_MAX_SHRINK = 4, 252                         # include/magprop_amd.h MP_MOVE_SLICE, MP_SLICE_MAX_SHRINK
+MOVE_GAUSSIAN, MOVE_WALK, WALK_MAX_S = 5, 6, 64               # include/magprop_amd.h MP_MOVE_GAUSSIAN, MP_MOVE_WALK, MP_WALK_MAX_S
+GAUSS_MODES = {"vector": 0, "random": 1, "sequential": 2}    # include/magprop_amd.h MP_GAUSS_*
 ACF_MAX_LAG, ACF_MAX_BYTES = 4096, 8 << 30                   # include/magprop_amd.h MP_ACF_*
 POST_MAX_BINS, POST_MAX_BINS2, POST_MAX_BYTES = 4096, 128, 1 << 30   # include/magprop_amd.h MP_POST_*
 LADDER_MAX_HISTORY_BYTES = 1 << 28                           # include/magprop_amd.h MP_LADDER_MAX_HISTORY_BYTES
@@ -100,6 +102,8 @@ SIGNATURES = {
     "mp_sampler_set_moves": (_i, [_vp, _i, _ip, _dp, _dp]),
     "mp_sampler_set_slice_limits": (_i, [_vp, _i, _i]),
     "mp_sampler_get_slice": (_i, [_vp, _dp, _i64p, _i64p, _i64p, _i64p, _i64p]),
+    "mp_sampler_set_gaussian": (_i, [_vp, _dp, _i, _d]),
+    "mp_sampler_get_gaussian": (_i, [_vp, _dp, _i64p, _i64p, _i64p]),
     "mp_sampler_get_bad": (_i, [_vp, _i64, _dp, _i, _i64p, _i64p]),
     "mp_sampler_n_slots": (_i, [_vp]),
     "mp_sampler_row_doubles": (_i, [_vp]),

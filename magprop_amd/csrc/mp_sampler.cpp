@@ -1,10 +1,11 @@
-// mp_sampler.cpp — the device-resident ensemble sampler (mp_sampler_*): stretch, DE, snooker, KDE and slice moves, tempering with
-// a fixed or an adapting ladder, whole-step and walker-sharded driving.  Kernels: mp_kernels.hip, mp_slice.hip for the slice move
-// and mp_ladder.hip for the ladder's updates.
+// mp_sampler.cpp — the device-resident ensemble sampler (mp_sampler_*): stretch, DE, snooker, KDE, slice, Gaussian and walk moves,
+// tempering with a fixed or an adapting ladder, whole-step and walker-sharded driving.  Kernels: mp_kernels.hip, mp_slice.hip for
+// the slice move, mp_normal.hip for the Gaussian and walk moves and mp_ladder.hip for the ladder's updates.
 #include <memory>
 #include <thread>
 
 #include "mp_monitor.h"
+#include "mp_normal.h"
 #include "mp_slice.h"
 
 struct mp_sampler {
@@ -40,7 +41,7 @@ struct mp_sampler {
     struct Move {
         int32_t kind;
         double p0, p1;              // stretch: a; DE: g0 (resolved), s = sigma sqrt(3); snooker: gamma_s; KDE: f (resolved);
-                                    // slice: mu0, tune_steps
+                                    // slice: mu0, tune_steps; Gaussian: scale0, tune_steps; walk: s (resolved: 2 .. n_comp)
     };
     std::vector<Move> moves;
     std::vector<double> move_cum;   // cumulative weights, summed in order
@@ -51,6 +52,16 @@ struct mp_sampler {
     DevBuf<double> d_slice_mu;      // [n_ensembles]
     DevBuf<int64_t> d_slice_cnt;    // [kSliceCnt][n_ensembles]: nexpand_s, ncontract_s, nexpand, ncontract, nfail, neval, n_tuned
     static constexpr int kSliceCnt = 7;
+    // the Gaussian move (MP_MOVE_GAUSSIAN): covariance factor, mode and target of mp_sampler_set_gaussian; its per-ensemble state
+    // on the device, set up by mp_sampler_set_moves when the table has one
+    bool gauss_set = false, has_gauss = false;
+    int gauss_mode = MP_GAUSS_VECTOR;
+    double gauss_target = 0.25;
+    int64_t gauss_tune = 0;         // params[1]
+    DevBuf<double> d_gauss_L;       // [ndim (ndim + 1) / 2]
+    DevBuf<double> d_gauss_sigma;   // [n_ensembles]
+    DevBuf<int64_t> d_gauss_cnt;    // [kGaussCnt][n_ensembles]: acc_s, n_proposed, n_accepted, n_tuned
+    static constexpr int kGaussCnt = 4;
     std::unique_ptr<AcfMonitor> acf;   // the autocorrelation monitor; null: off
     std::unique_ptr<PostMonitor> post; // the posterior monitor; null: off
     std::unique_ptr<ThermoMonitor> thermo;   // the thermodynamic monitor; null: off
@@ -203,6 +214,23 @@ static mp::SliceArgs slice_args(const mp_sampler *s) {
     return sl;
 }
 
+// the launch arguments of the Gaussian and walk moves over the sampler's buffers (walk_s: the walk move's resolved s, else 0)
+static mp::NormalArgs normal_args(const mp_sampler *s, int walk_s) {
+    const size_t ne = (size_t)s->n_ensembles;
+    int64_t *c = s->d_gauss_cnt.p;
+    mp::NormalArgs na{};
+    if (s->has_gauss) {
+        na.L = s->d_gauss_L.p;
+        na.sigma = s->d_gauss_sigma.p;
+        na.acc_s = c; na.n_proposed = c + ne; na.n_accepted = c + 2 * ne; na.n_tuned = c + 3 * ne;
+    }
+    na.tune_steps = s->gauss_tune;
+    na.target_accept = s->gauss_target;
+    na.mode = s->gauss_mode;
+    na.walk_s = walk_s;
+    return na;
+}
+
 extern "C" {
 
 mp_sampler *mp_sampler_create(mp_handle *h, int n_walkers, int n_ensembles, int ndim, const int32_t *ens_ds_id,
@@ -340,6 +368,7 @@ int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const
     std::vector<double> cum;
     double c = 0.0;
     int slice_at = -1;   // the table's slice entry
+    int gauss_at = -1;   // the table's Gaussian entry
     for (int m = 0; m < n_moves; ++m) {
         const double w = weights[m], p0 = params[2 * m], p1 = params[2 * m + 1];
         if (!std::isfinite(w) || !(w > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: weight %d must be finite and > 0, got %g", m, w);
@@ -382,6 +411,29 @@ int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const
             x.p0 = p0;
             x.p1 = p1;
             break;
+        case MP_MOVE_GAUSSIAN:   // (the params first: a bad pair is MP_EINVAL whatever else is wrong)
+            if (!std::isfinite(p0) || !(p0 > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_moves: Gaussian scale0 must be finite and > 0, got %g", p0);
+            if (!(p1 >= 0.0) || !(p1 <= 2147483647.0) || p1 != std::floor(p1))
+                return fail(MP_EINVAL, "mp_sampler_set_moves: Gaussian tune_steps must be a whole number in [0, 2^31 - 1], got %g", p1);
+            if (gauss_at >= 0) return fail(MP_EINVAL, "mp_sampler_set_moves: at most one Gaussian move per table (entries %d and %d)", gauss_at, m);
+            if (!s->gauss_set) return fail(MP_ESTATE, "mp_sampler_set_moves: the Gaussian move needs a covariance: call mp_sampler_set_gaussian first");
+            gauss_at = m;
+            x.p0 = p0;
+            x.p1 = p1;
+            break;
+        case MP_MOVE_WALK: {
+            const int n_comp = s->n_walkers - n_half;
+            if (!(p0 >= 0.0) || !std::isfinite(p0) || p0 != std::floor(p0))
+                return fail(MP_EINVAL, "mp_sampler_set_moves: walk s must be 0 (all of the other half) or a whole number >= 2, got %g", p0);
+            if (p0 == 1.0) return fail(MP_EINVAL, "mp_sampler_set_moves: walk s must be 0 or >= 2 (one member has no covariance), got 1");
+            if (p1 != 0.0) return fail(MP_EINVAL, "mp_sampler_set_moves: walk params[1] must be 0, got %g", p1);
+            if (n_half < 2) return fail(MP_EINVAL, "mp_sampler_set_moves: the walk move needs n_walkers >= 4 (two members in the other half)");
+            if (p0 > (double)n_comp) return fail(MP_EINVAL, "mp_sampler_set_moves: walk s = %g exceeds the %d walkers of the other half", p0, n_comp);
+            if (p0 != 0.0 && p0 != (double)n_comp && p0 > (double)MP_WALK_MAX_S)
+                return fail(MP_EINVAL, "mp_sampler_set_moves: walk s must be at most MP_WALK_MAX_S = %d (or 0: all %d of the other half), got %g", MP_WALK_MAX_S, n_comp, p0);
+            x.p0 = p0 == 0.0 ? (double)n_comp : p0;
+            break;
+        }
         default:
             return fail(MP_EINVAL, "mp_sampler_set_moves: unknown move kind %d", (int)kinds[m]);
         }
@@ -400,7 +452,18 @@ int mp_sampler_set_moves(mp_sampler *s, int n_moves, const int32_t *kinds, const
         HIP_TRY(hipMemset(s->d_slice_cnt.p, 0, mp_sampler::kSliceCnt * ne * sizeof(int64_t)));
         s->slice_tune = (int64_t)mv[(size_t)slice_at].p1;
     }
+    if (gauss_at >= 0) {   // likewise: sigma = scale0, no update made, the counters at zero
+        const size_t ne = (size_t)s->n_ensembles;
+        int rc;
+        if ((rc = s->d_gauss_sigma.ensure(ne)) || (rc = s->d_gauss_cnt.ensure(mp_sampler::kGaussCnt * ne))) return rc;
+        HIP_TRY(hipDeviceSynchronize());
+        const std::vector<double> s0(ne, mv[(size_t)gauss_at].p0);
+        HIP_TRY(hipMemcpy(s->d_gauss_sigma.p, s0.data(), ne * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(s->d_gauss_cnt.p, 0, mp_sampler::kGaussCnt * ne * sizeof(int64_t)));
+        s->gauss_tune = (int64_t)mv[(size_t)gauss_at].p1;
+    }
     s->has_slice = slice_at >= 0;
+    s->has_gauss = gauss_at >= 0;
     s->moves = std::move(mv);
     s->move_cum = std::move(cum);
     return MP_OK;
@@ -428,6 +491,43 @@ int mp_sampler_get_slice(mp_sampler *s, double *mu, int64_t *nexpand, int64_t *n
     const mp::SliceArgs sl = slice_args(s);
     return read_back(mu, (const double *)sl.mu, ne, nexpand, (const int64_t *)sl.nexpand, ne, ncontract, (const int64_t *)sl.ncontract, ne,
                      nfail, (const int64_t *)sl.nfail, ne, neval, (const int64_t *)sl.neval, ne, n_tuned, (const int64_t *)sl.n_tuned, ne);
+}
+
+int mp_sampler_set_gaussian(mp_sampler *s, const double *L, int mode, double target_accept) {
+    if (!s || !L) return fail(MP_EINVAL, "mp_sampler_set_gaussian: NULL argument");
+    if (mode != MP_GAUSS_VECTOR && mode != MP_GAUSS_RANDOM && mode != MP_GAUSS_SEQUENTIAL)
+        return fail(MP_EINVAL, "mp_sampler_set_gaussian: mode must be MP_GAUSS_VECTOR, MP_GAUSS_RANDOM or MP_GAUSS_SEQUENTIAL, got %d", mode);
+    if (!(target_accept > 0.0) || !(target_accept < 1.0))
+        return fail(MP_EINVAL, "mp_sampler_set_gaussian: target_accept must lie in (0, 1), got %g", target_accept);
+    const size_t tri = (size_t)s->ndim * (size_t)(s->ndim + 1) / 2;
+    for (int a = 0; a < s->ndim; ++a)
+        for (int b = 0; b <= a; ++b) {
+            const double v = L[(size_t)a * (a + 1) / 2 + b];
+            if (!std::isfinite(v)) return fail(MP_EINVAL, "mp_sampler_set_gaussian: L[%d][%d] is not finite", a, b);
+            if (a == b && !(v > 0.0)) return fail(MP_EINVAL, "mp_sampler_set_gaussian: the diagonal of L must be > 0, got L[%d][%d] = %g", a, a, v);
+            if (a != b && mode != MP_GAUSS_VECTOR && v != 0.0)
+                return fail(MP_EINVAL, "mp_sampler_set_gaussian: a single-axis mode needs a diagonal covariance, got L[%d][%d] = %g", a, b, v);
+        }
+    Held held(s->h, s->ev);
+    int rc;
+    if ((rc = s->d_gauss_L.ensure(tri))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(s->d_gauss_L.p, L, tri * sizeof(double), hipMemcpyHostToDevice));
+    s->gauss_set = true;
+    s->gauss_mode = mode;
+    s->gauss_target = target_accept;
+    return MP_OK;
+}
+
+int mp_sampler_get_gaussian(mp_sampler *s, double *sigma, int64_t *n_proposed, int64_t *n_accepted, int64_t *n_tuned) {
+    if (!s) return fail(MP_EINVAL, "mp_sampler_get_gaussian: NULL sampler");
+    Held held(s->h, s->ev);
+    if (!s->has_gauss) return fail(MP_ESTATE, "mp_sampler_get_gaussian: the move table has no Gaussian move (mp_sampler_set_moves)");
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t ne = (size_t)s->n_ensembles;
+    const mp::NormalArgs na = normal_args(s, 0);
+    return read_back(sigma, (const double *)na.sigma, ne, n_proposed, (const int64_t *)na.n_proposed, ne, n_accepted,
+                     (const int64_t *)na.n_accepted, ne, n_tuned, (const int64_t *)na.n_tuned, ne);
 }
 
 int mp_sampler_get_swaps(mp_sampler *s, int64_t *n_swaps_accepted) {
@@ -472,7 +572,7 @@ int mp_sampler_set_positions(mp_sampler *s, const double *pos) {
 // Enqueue step steps_done + row of mp_sampler_run on the handle's stream: split d_perm, chain row `row` of the device slab when
 // chain is set, move mv (nullptr: the stretch move of mp_sampler_create).  A whole step per launch (stretch_step_kernel and the
 // commit kernel) where `whole` and the move is the stretch move, else two half-step launches (the slice move: of slice_half_kernel,
-// with the tune launch behind them); then the swap sweep when tempered, and behind it the ladder's update while it adapts.  fits: a whole step of this sampler fits one launch
+// with the tune launch behind them; the Gaussian and walk moves: of normal_half_kernel, the Gaussian move with its tune launch); then the swap sweep when tempered, and behind it the ladder's update while it adapts.  fits: a whole step of this sampler fits one launch
 // (`whole` is that and mp_sampler_set_whole_step).
 static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_sampler::Move *mv, bool chain, bool whole, bool fits) {
     Evaluator *ev = s->ev;
@@ -494,6 +594,12 @@ static int enqueue_step(mp_sampler *s, const int32_t *d_perm, int row, const mp_
         g.half = 1;
         if (!e) e = mp::launch_slice_half(ev->sh, g, sl, ev->stream);
         if (!e) e = mp::launch_slice_tune(sl, s->n_ensembles, ev->stream);
+    } else if (g.move == MP_MOVE_GAUSSIAN || g.move == MP_MOVE_WALK) {
+        const mp::NormalArgs na = normal_args(s, g.move == MP_MOVE_WALK ? (int)mv->p0 : 0);
+        e = mp::launch_normal_half(ev->sh, g, na, ev->stream);
+        g.half = 1;
+        if (!e) e = mp::launch_normal_half(ev->sh, g, na, ev->stream);
+        if (!e && g.move == MP_MOVE_GAUSSIAN) e = mp::launch_gauss_tune(na, s->n_ensembles, s->n_walkers, ev->stream);
     } else if (whole && g.move == MP_MOVE_STRETCH) {
         g.spec = s->d_spec.p;
         e = mp::launch_stretch_step(ev->sh, g, 3 * g.n_half * g.n_ensembles, ev->stream);

@@ -35,7 +35,7 @@ class EnsembleSampler:
         parallel tempering with one ensemble per (dataset, temperature), nensembles = len(datasets) x T (T for
         target="gaussian"), positions in ensemble order (group g, temperature t: walkers [(g T + t) nwalkers, + nwalkers)).
         moves: None (the stretch move with scale a, as emcee), or emcee's moves= forms over magprop_amd.moves (StretchMove,
-        DEMove, DESnookerMove, KDEMove, SliceMove): a move, a list of moves, or a list of (move, weight); one move is drawn per step
+        DEMove, DESnookerMove, KDEMove, SliceMove, GaussianMove, WalkMove): a move, a list of moves, or a list of (move, weight); one move is drawn per step
         (include/magprop_amd.h mp_sampler_set_moves).  Give the stretch scale as StretchMove(a) then: moves together with a
         non-default a is refused.
         adapt_ladder: None (the ladder stays as given), or the number of steps over which every group spaces its own ladder on
@@ -50,6 +50,8 @@ class EnsembleSampler:
             if float(a) != 2.0:
                 raise ValueError("give the stretch scale as moves=StretchMove(a=...) when moves= is set, not as a=")
             move_tab = _moves.move_table(moves, int(ndim))
+            gm = _moves.gaussian_move(_moves.parse_moves(moves))
+            gauss_L = None if gm is None else gm.packed_factor(int(ndim))   # (refuses a covariance of another size)
         self.nwalkers, self.ndim = int(nwalkers), int(ndim)
         self._L = _capi.lib()
         lo, hi, mask = engine.prior_box(variant, ndim)   # (no range check of ndim: target="gaussian" takes any)
@@ -90,6 +92,9 @@ class EnsembleSampler:
             kinds = np.asarray(move_tab[0], dtype=np.int32)
             weights = np.asarray(move_tab[1], dtype=np.float64)
             params = np.ascontiguousarray(move_tab[2], dtype=np.float64)
+            if gm is not None:   # the covariance goes before the table that names the move
+                _capi.check(self._L.mp_sampler_set_gaussian(self._s, _capi.ptr(gauss_L), _moves.GAUSS_MODES[gm.mode],
+                                                            gm.target_accept), "mp_sampler_set_gaussian")
             _capi.check(self._L.mp_sampler_set_moves(self._s, int(kinds.size), _capi.ptr(kinds), _capi.ptr(weights), _capi.ptr(params)),
                         "mp_sampler_set_moves")
             sl = _moves.slice_move(self.moves)
@@ -272,6 +277,16 @@ class EnsembleSampler:
         n = self.nensembles
         return _capi.read_back(self._L.mp_sampler_get_slice, self._s, [("mu", n, np.float64)] + [
             (k, n, np.int64) for k in ("nexpand", "ncontract", "nfail", "neval", "n_tuned")])
+
+    def get_gaussian_stats(self):
+        """The state of the Gaussian move (moves=GaussianMove(...); mp_sampler_get_gaussian), one entry per ensemble: the scale
+        "sigma" now and, since the sampler was made, "n_proposed" proposals, "n_accepted" of them accepted and "n_tuned" tuning
+        updates made (at most GaussianMove.tune)."""
+        if self.moves is None or _moves.gaussian_move(self.moves) is None:
+            raise ValueError("get_gaussian_stats needs a sampler with a GaussianMove in moves=")
+        n = self.nensembles
+        return _capi.read_back(self._L.mp_sampler_get_gaussian, self._s, [("sigma", n, np.float64)] + [
+            (k, n, np.int64) for k in ("n_proposed", "n_accepted", "n_tuned")])
 
     # ---- the ladder as the device holds it (include/magprop_amd.h mp_sampler_set_ladder_adaptation)
     @property

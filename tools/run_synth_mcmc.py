@@ -32,7 +32,7 @@ def main(argv=None):
     ap.add_argument("--data", default=None, help="x,y,yerr CSV (default: the seeded golden dataset)")
     ap.add_argument("--out", default="synth_out")
     ap.add_argument("-r", "--re-run", action="store_true", help="repeat the run recorded in <out>/<grb>_info.json")
-    ap.add_argument("--moves", default=None, help="proposal moves out of stretch, de, snooker, kde, slice, e.g. de:0.8,snooker:0.2 or slice (default: the stretch move)")
+    ap.add_argument("--moves", default=None, help="proposal moves out of stretch, de, snooker, kde, slice, awalk, e.g. de:0.8,snooker:0.2 or slice (default: the stretch move)")
     a = ap.parse_args(argv)
     if a.re_run:
         rec = mcmc_io.read_info(os.path.join(a.out, a.grb + "_info.json"))
