@@ -1202,6 +1202,81 @@ int mp_smc_set_adaptive(void *s, int min_rounds, int max_rounds, double corr, do
 int mp_smc_get_tuning(void *s, int run, int max_rows, int32_t *rounds, double *g, double *rho, int *n_rows);
 int mp_smc_destroy(void *s);
 
+/*
+ * Bridge-sampling evidence (ABI 5, additive): ln Z from the samples of an ordinary, untempered run and their lnprob (Meng & Wong
+ * 1996 with the optimal bridge; Gronau et al. 2017).  One call with no state.  A Gaussian N(m, L L^T) is fitted to the rows
+ * x_fit[n_fit][ndim], N2 = n_draws points are drawn from it per repetition and evaluated, and a one-dimensional fixed point is
+ * iterated over the log-ratios of the N1 = n_est rows x_est (with their lnprob lnp_est) and of the draws.  n_rep repetitions
+ * (1 .. MP_BRIDGE_MAX_REP) share the proposal and the estimator rows and differ by their draws.  All rows are sampler
+ * coordinates.  target as in mp_smc_create: 0 the log-posterior of the handle on dataset ds_id, 1 the isotropic unit Gaussian
+ * -0.5 sum x^2, 2 the same on terraces along x_0 (1 and 2: tests; ds_id is not read).  The box lower[ndim] < upper[ndim] is the
+ * support of the prior, uniform over it; NULL (both; targets 1 and 2 only): no box.  Every product, sum and difference below is
+ * rounded on its own (nothing is fused); exp, log, cos, sin, sqrt are the device's unless "the host's" is said.
+ * Moments (device): pivot = row 0 of x_fit.  s_a = sum_i (x_ia - pivot_a) and P_ab = sum_i (x_ia - pivot_a)(x_ib - pivot_b), b <= a,
+ *   over the n_fit rows: the rows are cut into blocks of MP_BRIDGE_BLOCK consecutive rows from row 0, one workgroup per block;
+ *   inside a block thread k of 256 adds its rows k, k + 256, ... in that order from 0.0, the threads' sums combine in the order
+ *   of mp_wg.h (xor butterfly over 32, 16, .. 1 inside a wavefront, then the four wavefronts in order); the blocks' sums are
+ *   added in block order starting from block 0's.  The sums are a function of the rows alone, not of how the call moves them
+ *   to the device.  moments (optional) [ndim + ndim (ndim + 1) / 2]: s, then P with entry (a, b <= a) at ndim + a (a + 1) / 2 + b.
+ * Factor (host, doubles): m_a = pivot_a + s_a / n_fit; S_ab = P_ab - (s_a s_b) / n_fit; C_ab = S_ab / (n_fit - 1); the lower
+ *   Cholesky factor L by rows: for a = 0 .., for b = 0 .. a: t = C_ab - L_a0 L_b0 - ... - L_a,b-1 L_b,b-1 (subtracted in that
+ *   order); L_ab = t / L_bb for b < a, L_aa = sqrt(t).  A pivot sqrt(t) that is not finite and > 0 returns MP_ERANGE and names
+ *   the dimension (a constant or linearly dependent column).  c = (ln L_00 + ln L_11 + ..., added in order from 0.0) +
+ *   (0.5 ndim) * 1.8378770664093453, the host's log.
+ * Draws (device, one thread per draw j of repetition r, row r * n_draws + j of draws / draw_lnp / draw_lnq): pair p = 0, 1, ..
+ *   of normals z_2p, z_2p+1 from the words w of Philox4x32-10 keyed (seed; j, r, p, 0x42524700) by Box-Muller (the KDE move's
+ *   formula): rad = sqrt(-2 log(1 - u01(w0, w1))), ang = 6.283185307179586 u01(w2, w3), z_2p = rad cos(ang), z_2p+1 = rad sin(ang).
+ *   x_a = m_a + (L_a0 z_0 + ... + L_aa z_a), the sum from 0.0 in that order; lnq = -0.5 (z_0^2 + ... , from 0.0 in order) - c.
+ * Evaluation: target 0: one launch of mp_lnprob_batch_dev over the n_rep * n_draws rows, all on ds_id: every draw_lnp is bit for
+ *   bit what mp_lnprob_batch returns for that row in a batch of that size.  Targets 1 and 2: point_eval's arithmetic,
+ *   lnp = 0 - (0.5 x_0) x_0 - (0.5 x_1) x_1 - ... (target 2: - 1e-3 floor(37 x_0)).  b_j = lnp_j - lnq_j where the draw lies in
+ *   [lower, upper] in every coordinate (no box: everywhere) and lnp_j is finite; otherwise b_j = -inf: a draw outside the
+ *   support, a NaN, a failed model or a prior miss has posterior density zero.
+ * Proposal density at the estimator rows (device, one thread per row): forward substitution z_a = (x_a - m_a - L_a0 z_0 - ... -
+ *   L_a,a-1 z_a-1) / L_aa, subtracted in that order, then lnq by the formula above (est_lnq, optional) and a_i = lnp_est_i - lnq_i.
+ * Fixed point (device, one workgroup of 256 threads per repetition).  From the host: ln s1 = log(neff / (neff + N2)), ln s2 =
+ *   log(N2 / (neff + N2)), ln N1, ln N2, tau = N1 / neff, ln_volume = log(upper_0 - lower_0) + ... in order from 0.0 (no box:
+ *   0), the host's log.  lse2(u, v) = max(u, v) + log(1 + exp(min(u, v) - max(u, v))).  LSE of values v: a pair (M, s) per thread
+ *   from (-inf, 0), thread k takes elements k, k + 256, ... in order: a v > M makes s = s exp(M - v) + 1, M = v; any other
+ *   v > -inf makes s = s + exp(v - M); -inf is skipped; the pairs merge in the order of mp_wg.h, two pairs as s = s exp(M - max)
+ *   + s' exp(M' - max) (a zero s contributes 0), M = max; LSE = M + log(s).
+ *   lambda_0 = LSE_j b_j - ln N2, the plain importance-sampling estimate; n_finite = the draws with b_j > -inf.  n_finite = 0:
+ *   status MP_BRIDGE_NO_OVERLAP, lnz, lambda, dlnz and the four moments NaN, lambda_0 = -inf, nothing is iterated.
+ *   Update t: c2 = ln s2 + lambda_t;
+ *   lambda_t+1 = [LSE_j (b_j - lse2(ln s1 + b_j, c2)) - ln N2] - [LSE_i (-lse2(ln s1 + a_i, c2)) - ln N1].
+ *   The loop stops with MP_BRIDGE_OK once |lambda_t+1 - lambda_t| <= tol, with MP_BRIDGE_ITER_LIMIT after max_iter updates;
+ *   lambda = the last lambda_t+1.  Nothing is subtracted for stability: every term stays a logarithm, so a common offset of
+ *   the lnprob of any size moves lambda by that offset and nothing else.
+ *   Behind the loop f1_i = exp(-lse2((ln s1 + a_i) - lambda, ln s2)), f2_j = exp((b_j - lambda) - lse2((ln s1 + b_j) - lambda,
+ *   ln s2)) (0 for b_j = -inf); mean = (sum f) / N and var = (sum (f - mean)^2) / N in a second pass, sums in the order of the
+ *   moments above (thread k its elements in order, then mp_wg.h).
+ *   dlnz = sqrt(var2 / (N2 (mean2 mean2)) + tau (var1 / (N1 (mean1 mean1)))): Fruehwirth-Schnatter's (2004) approximate relative
+ *   mean-squared error of the bridge estimate, with the normalised spectral density of f1 at frequency zero replaced by
+ *   tau = N1 / neff, the caller's integrated autocorrelation time of the estimator rows.  It leaves out the error of the
+ *   proposal's fit (x_fit is taken as given) and any bias of a chain that has not converged.
+ * out[n_rep][MP_BRIDGE_NOUT]: lnz = lambda - ln_volume, lambda, ln_volume, dlnz, the updates made, the status, n_finite,
+ * lambda_0, mean1, var1, mean2, var2 (MP_BRIDGE_LNZ .. MP_BRIDGE_VAR2).
+ * MP_EINVAL: a NULL handle, row or out pointer; target outside 0 .. 2; ndim outside 1 .. MP_MAX_NDIM or < 6 for target 0;
+ * n_fit < ndim + 2, n_est < 1, n_draws < 1; n_rep outside 1 .. MP_BRIDGE_MAX_REP; n_fit, n_est or n_rep * n_draws above
+ * MP_BRIDGE_MAX_ROWS; neff outside (0, n_est]; tol not finite or < 0; max_iter < 1; a NULL box for target 0 or one bound NULL;
+ * an empty or non-finite box; a non-finite row of x_fit or x_est; a non-finite lnp_est; (target 0) ds_id out of range.
+ * MP_ESTATE: a multi-device handle; (target 0) cfg.dipole_torque = 1 or an unset dataset.  The rows of x_fit and x_est go through
+ * the device in chunks of whole blocks; the draws, a and b stay there.
+ */
+#define MP_BRIDGE_BLOCK 4096
+#define MP_BRIDGE_MAX_REP 64
+#define MP_BRIDGE_MAX_ROWS 4194304
+#define MP_BRIDGE_NOUT 12
+#define MP_BRIDGE_OK 0
+#define MP_BRIDGE_ITER_LIMIT 1
+#define MP_BRIDGE_NO_OVERLAP 2
+enum { MP_BRIDGE_LNZ = 0, MP_BRIDGE_LAMBDA, MP_BRIDGE_LN_VOLUME, MP_BRIDGE_DLNZ, MP_BRIDGE_NITER, MP_BRIDGE_STATUS,
+       MP_BRIDGE_NFINITE, MP_BRIDGE_LAMBDA0, MP_BRIDGE_MEAN1, MP_BRIDGE_VAR1, MP_BRIDGE_MEAN2, MP_BRIDGE_VAR2 };
+int mp_bridge_logz(mp_handle *h, const double *x_fit, int64_t n_fit, const double *x_est, const double *lnp_est, int64_t n_est,
+                   int ndim, int ds_id, const double *lower, const double *upper, int64_t n_draws, int n_rep, uint64_t seed,
+                   double neff, int max_iter, double tol, int target, double *out, double *moments, double *draws,
+                   double *draw_lnp, double *draw_lnq, double *est_lnq);
+
 /* wait for everything enqueued on the handle's own stream */
 int mp_synchronize(mp_handle *h);
 

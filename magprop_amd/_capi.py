@@ -38,6 +38,10 @@ ACF_MAX_LAG, ACF_MAX_BYTES = 4096, 8 << 30                   # include/magprop_a
 POST_MAX_BINS, POST_MAX_BINS2, POST_MAX_BYTES = 4096, 128, 1 << 30   # include/magprop_amd.h MP_POST_*
 LADDER_MAX_HISTORY_BYTES = 1 << 28                           # include/magprop_amd.h MP_LADDER_MAX_HISTORY_BYTES
 RESERVOIR_MAX_ROWS = 65536                                   # include/magprop_amd.h MP_RESERVOIR_MAX_ROWS
+BRIDGE_BLOCK, BRIDGE_MAX_REP, BRIDGE_MAX_ROWS, BRIDGE_NOUT = 4096, 64, 1 << 22, 12   # include/magprop_amd.h MP_BRIDGE_*
+BRIDGE_OK, BRIDGE_ITER_LIMIT, BRIDGE_NO_OVERLAP = 0, 1, 2
+# columns of mp_bridge_logz's out rows, in the order of MP_BRIDGE_LNZ .. MP_BRIDGE_VAR2
+BRIDGE_COLUMNS = ("lnz", "lambda", "ln_volume", "dlnz", "niter", "status", "n_finite", "lambda0", "mean1", "var1", "mean2", "var2")
 
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -154,6 +158,7 @@ SIGNATURES = {
     "mp_smc_set_adaptive": (_i, [_vp, _i, _i, _d, _d, _d, _d, _d]),
     "mp_smc_get_tuning": (_i, [_vp, _i, _i, _ip, _dp, _dp, _ip]),
     "mp_smc_destroy": (_i, [_vp]),
+    "mp_bridge_logz": (_i, [_vp, _dp, _i64, _dp, _dp, _i64, _i, _i, _dp, _dp, _i64, _i, _u64, _d, _i, _d, _i, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mp_synchronize": (_i, [_vp]),
     "mp_device": (_i, [_vp]),
     "mp_stream": (_vp, [_vp]),
@@ -618,6 +623,47 @@ class Handle(_Owner):
                                          _dptr(z) if cells else None, _iptr(st), C.byref(used)), "mp_model_pointwise")
         res = (obs, tail[:, :tlen], st, int(used.value))
         return res + (z,) if cells else res
+
+    def bridge_logz(self, x_fit, x_est, lnp_est, lower=None, upper=None, ds_id=0, n_draws=None, n_rep=1, seed=0, neff=None,
+                    max_iter=1000, tol=1.0e-10, target=0, details=False):
+        """The bridge-sampling evidence of mp_bridge_logz: a Gaussian fitted to the rows x_fit, n_draws draws from it per
+        repetition, and the fixed point over the rows x_est with their lnprob lnp_est (sampler coordinates; the box lower,
+        upper is the prior's support, None for the test targets 1 and 2).  n_draws=None: as many as x_est has rows; neff=None:
+        that number too (independent rows).  Returns {"out": (n_rep, BRIDGE_NOUT), columns BRIDGE_COLUMNS}; details=True adds
+        "moments", "draws" (n_rep, n_draws, ndim), "draw_lnp", "draw_lnq" (n_rep, n_draws) and "est_lnq" (n_est,)."""
+        xf = np.ascontiguousarray(x_fit, dtype=np.float64)
+        xe = np.ascontiguousarray(x_est, dtype=np.float64)
+        le = np.ascontiguousarray(lnp_est, dtype=np.float64)
+        if xf.ndim != 2 or xe.ndim != 2 or xf.shape[1] != xe.shape[1] or le.shape != (xe.shape[0],):
+            raise ValueError(f"x_fit (n_fit, ndim), x_est (n_est, ndim) and lnp_est (n_est,) expected, got {xf.shape}, {xe.shape}, {le.shape}")
+        nd, n_est = xf.shape[1], xe.shape[0]
+        n_draws = n_est if n_draws is None else int(n_draws)
+        n_rep = int(n_rep)
+        if (lower is None) != (upper is None):
+            raise ValueError("lower and upper go together")
+        lo = hi = None
+        if lower is not None:
+            lo = np.ascontiguousarray(lower, dtype=np.float64)
+            hi = np.ascontiguousarray(upper, dtype=np.float64)
+            if lo.shape != (nd,) or hi.shape != (nd,):
+                raise ValueError(f"lower and upper must have shape ({nd},), got {lo.shape}, {hi.shape}")
+        out = np.full((max(n_rep, 1), BRIDGE_NOUT), np.nan)
+        nm, tot = nd + nd * (nd + 1) // 2, max(n_rep, 1) * max(n_draws, 1)
+        det = {}
+        if details:
+            det = {"moments": np.full(nm, np.nan), "draws": np.full((tot, nd), np.nan), "draw_lnp": np.full(tot, np.nan),
+                   "draw_lnq": np.full(tot, np.nan), "est_lnq": np.full(max(n_est, 1), np.nan)}
+        opt = [(_dptr(det[k]) if details else None) for k in ("moments", "draws", "draw_lnp", "draw_lnq", "est_lnq")]
+        check(self._L.mp_bridge_logz(self._h, _dptr(xf), xf.shape[0], _dptr(xe), _dptr(le), n_est, nd, int(ds_id),
+                                     None if lo is None else _dptr(lo), None if hi is None else _dptr(hi), n_draws, n_rep,
+                                     C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(n_est if neff is None else neff), int(max_iter),
+                                     float(tol), int(target), _dptr(out), *opt), "mp_bridge_logz")
+        res = {"out": out}
+        if details:
+            res.update(moments=det["moments"], draws=det["draws"].reshape(n_rep, n_draws, nd),
+                       draw_lnp=det["draw_lnp"].reshape(n_rep, n_draws), draw_lnq=det["draw_lnq"].reshape(n_rep, n_draws),
+                       est_lnq=det["est_lnq"][:n_est])
+        return res
 
     def rhs_batch(self, pars, t, y, want_lam=False):
         """(dMdisc/dt, domega/dt) at n states: pars (n, ndim) physical, t (n,), y (n, 2) = (Mdisc, omega)."""

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mp_normal.h"
+#include "mp_normal_pair.h"
 #include "mp_point.h"
 
 namespace mp {
@@ -24,14 +25,6 @@ constexpr uint32_t kWalkNormalCtr = 0x57800000u;   // + p: normals 2p, 2p + 1
 
 MP_DEV void normal_draw(const StretchArgs &g, int k, uint32_t c3, uint32_t (&out)[4]) {
     philox4x32_10((uint32_t)g.seed, (uint32_t)(g.seed >> 32), (uint32_t)g.step, (uint32_t)g.half, (uint32_t)k, c3, out);
-}
-
-// Box-Muller on the four words of one draw (the KDE move's formula): sqrt(-2 ln(1 - u_a)) cos, sin (2 pi u_b)
-MP_DEV void normal_pair(const uint32_t (&s4)[4], double &n0, double &n1) {
-    const double rad = sqrt(mul_rn(-2.0, log(sub_rn(1.0, u01(s4[0], s4[1])))));
-    const double ang = mul_rn(6.283185307179586, u01(s4[2], s4[3]));
-    n0 = mul_rn(rad, cos(ang));
-    n1 = mul_rn(rad, sin(ang));
 }
 
 // The LDS of a proposal beside the parked proposal itself (an array of its own, as in slice_half_kernel): what outlives the

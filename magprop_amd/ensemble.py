@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi, engine, posterior, summaries, tempering
+from . import _capi, bridge, engine, posterior, summaries, tempering
 from . import moves as _moves
 
 
@@ -339,8 +339,9 @@ class EnsembleSampler:
         out["n_steps"] = int(out["n_steps"])
         return out
 
-    def log_evidence(self, discard=0, group=0, prior_draws=2 ** 20, device=False):
-        """(lnZ, dlnZ) of group `group`'s dataset, the prior normalised over its box, from the stored chain of a tempered run:
+    def log_evidence(self, discard=0, group=0, prior_draws=2 ** 20, device=False, method="ti", thin=1, ensemble=None, temp=None,
+                     n_draws=None, repetitions=1, seed=None, neff=None, source="chain", max_iter=1000, tol=None):
+        """method="ti" (the default; thin and the arguments behind it are not read): (lnZ, dlnZ) of group `group`'s dataset, the prior normalised over its box, from the stored chain of a tempered run:
         thermodynamic integration of the per-temperature mean lnL over steps[discard:] (magprop_amd.tempering) plus
         ln f_valid, the fraction of `prior_draws` uniform box draws (numpy generator seeded by the sampler seed, evaluated on
         this sampler's handle) whose lnprob is finite.  dlnZ = |TI - TI over every other temperature| in quadrature with the
@@ -349,7 +350,23 @@ class EnsembleSampler:
         a step before ladder_frozen_at raises ValueError.
         device=True takes the per-temperature means from the thermodynamic monitor (monitor_thermo) instead of the stored
         chain, so a store=False run has an evidence; discard is the monitor's then.  It raises while the monitor is off or
-        empty and where a mean is not finite."""
+        empty and where a mean is not finite.
+        method="bridge": the evidence of an ordinary, untempered run by bridge sampling (magprop_amd.bridge, mp_bridge_logz), a
+        bridge.BridgeResult (it unpacks as (lnZ, dlnZ)): a Gaussian fitted to the first half of the steps
+        chain[discard::thin] of `ensemble` (default: `group`; a tempered sampler: the group's cold chain, or with temp=t its
+        beta_t ensemble, whose lnprob is still the untempered one) proposes n_draws points (default N1, the rows of the second
+        half) per repetition, and the second half with its stored lnprob is the estimator's: n_draws model evaluations on top
+        of the run.  seed: of the draws (default: derived from the sampler's).  neff=None: N1 / max tau over the estimator
+        half, tau from the autocorrelation monitor where it is on and else from get_autocorr_time's estimator on that half,
+        clamped to (0, N1]; without a tau neff = N1, and a RuntimeWarning says so.  source="reservoir": the rows of
+        get_samples(ensemble) split at their median step instead (monitor_samples; discard and thin stay at their defaults), so
+        that run_mcmc_until(..., store=False) ends with an evidence.  repetitions > 1: lnz is the median over the repetitions'
+        draws, dlnz their mean, dlnz_reps the spread of lnz over them.  max_iter, tol: of the fixed point."""
+        if method == "bridge":
+            return self._bridge_evidence(discard, thin, group if ensemble is None else ensemble, temp, n_draws, repetitions, seed, neff,
+                                         source, max_iter, tol)
+        if method != "ti":
+            raise ValueError(f"method must be 'ti' or 'bridge', got {method!r}")
         if self.betas is None:
             raise ValueError("log_evidence needs a tempered sampler (betas=...)")
         group = int(group)
@@ -388,6 +405,50 @@ class EnsembleSampler:
             n_finite += int(np.count_nonzero(np.isfinite(lp)))
         lnf, dlnf = tempering.validity_term(n_finite, n_draws)
         return ti + lnf, float(np.hypot(dti, dlnf))
+
+    def _bridge_evidence(self, discard, thin, ensemble, temp, n_draws, repetitions, seed, neff, source, max_iter, tol):
+        """log_evidence(method="bridge")"""
+        e = self._ensemble_index(ensemble, temp, grouped=self.betas is not None)
+        grp = e // self.ntemps
+        tau, n_seen, why = None, None, "the estimator half is too short"
+        if source == "reservoir":
+            if int(discard) != 0 or int(thin) != 1:
+                raise ValueError(f"source='reservoir' takes every row of the reservoir: discard and thin must be 0 and 1, got "
+                                 f"discard={discard}, thin={thin} (give discard to monitor_samples)")
+            if self._res is None:
+                raise _capi.MagpropAmdError("the sample reservoir is off (monitor_samples)")
+            res = _capi.read_back(self._L.mp_sampler_get_reservoir, self._s, [
+                ("x", (self._res[0], self.ndim), np.float64), ("log_prob", self._res[0], np.float64), ("step", self._res[0], np.int64),
+                ("walker", None, None), ("key", None, None), ("n_rows", (), np.int32), ("n_seen", (), np.int64)], e, self._res[0])
+            rows = int(res["n_rows"])
+            fit, est, lnp = bridge.reservoir_split({k: res[k][:rows] for k in ("x", "log_prob", "step")})
+            n_seen = float(res["n_seen"]) * est.shape[0] / max(rows, 1)     # the samples the estimator rows stand for
+            if neff is None:
+                why = "the autocorrelation monitor is off or holds no estimate"
+                if self._acf is not None:
+                    t, _, _ = self.get_autocorr_device(wait=True)
+                    tau = None if t is None else np.atleast_2d(t)[grp if np.ndim(t) > 1 else 0]
+        elif source == "chain":
+            if self._chain is None or len(self._chain) == 0:
+                raise ValueError("the chain is empty: run_mcmc(..., store=True) first")
+            discard, thin = int(discard), int(thin)
+            if discard < 0 or thin < 1:
+                raise ValueError(f"discard must be >= 0 and thin >= 1, got discard={discard}, thin={thin}")
+            w = slice(e * self.nwalkers, (e + 1) * self.nwalkers)
+            fit, est, lnp, est_chain = bridge.split(self._chain[discard::thin, w], self._lnp[discard::thin, w])
+            if neff is None and est_chain.shape[0] >= 4:
+                from .mcmc_io import integrated_time
+                tau = integrated_time(est_chain, quiet=True)
+        else:
+            raise ValueError(f"source must be 'chain' or 'reservoir', got {source!r}")
+        if neff is None:
+            neff, known = bridge.neff_from_tau(int(np.count_nonzero(np.isfinite(lnp))), tau, n_seen)
+            if not known:
+                bridge.warn_no_tau(why)
+        seed = (self.seed ^ 0x4272696467655F7A) & 0xFFFFFFFFFFFFFFFF if seed is None else int(seed)
+        lo, hi = (None, None) if self._target != 0 else self._prior
+        return bridge.bridge_evidence(fit, est, lnp, summaries.on(self.handle, grp), lo, hi, n_draws=n_draws, repetitions=repetitions,
+                                      seed=seed, neff=neff, max_iter=max_iter, tol=tol, target=self._target)
 
     @property
     def chain(self):
