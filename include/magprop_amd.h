@@ -75,6 +75,7 @@ extern "C" {
 #define MP_STATUS_BADDATASET 4 /* ds_id names no registered light curve (out of range or never set): lnprob = -inf.  The   */
                               /* host-buffer entry rejects such a batch with MP_EINVAL; the device-pointer entries cannot */
                               /* read the ids and report it per walker instead                                            */
+#define MP_STATUS_ZEROERR 5   /* mp_simulate only: a simulated observation of the row has error 0 (a model value of 0)   */
 
 /* limits */
 #define MP_MAX_NDIM 9        /* 6 physics parameters + up to dipeff, propeff, f_beam */
@@ -386,6 +387,59 @@ int mp_model_derived(mp_handle *h, const double *pars, int64_t n, int ndim, int 
 int mp_pointwise_tail_len(int64_t n_used);              /* T above; 0 for n_used < 1 */
 int mp_model_pointwise(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, int ds_id, double *obs_out,
                        double *tail_out, double *z_out, int32_t *status_out, int64_t *n_used);
+
+/*
+ * Simulated light curves of n parameter rows, computed on the device (ABI 5, additive): the model of every row at observed
+ * times, an error per observation and Gaussian noise -- the synthetic datasets of the reference's
+ * code/synthetic_datasets/generate_data.py:61-67 (the model at grid points, yerr = 0.25 y, normal noise), for any times inside
+ * the grid, and the first step of an injection-recovery study (magprop_amd/calibration.py).  pars, n, ndim and physical are
+ * mp_model_derived's.  Host buffers; the call returns when the results are in them:
+ *   x[x_rows][n_obs]      observed times; x_rows = 1: every row is observed at the same times, x_rows = n: row i at x[i]
+ *   yerr[x_rows][n_obs]   absolute errors, or NULL: the error is frac_err * |model|
+ *   y_out, yerr_out, model_out, z_out   [n][n_obs] the data, the errors, the noiseless model (1e50 erg/s, as mp_model_lc returns
+ *                         Ltot) and the standard normals; y_out is required, the others may be NULL
+ *   status_out[n], *n_ok  (optional) the rows' statuses and the number of rows with MP_STATUS_OK
+ * Limits: 1 <= n <= MP_SIM_MAX_ROWS, n_obs >= 1, n * n_obs <= MP_SIM_MAX_CELLS.  The rows go through the device in chunks of
+ * mp_n_simd(h) rows, each one launch of the curve kernels (Ltot only, the build mp_model_lc runs for a single row), one launch
+ * that turns the chunk's curves into cells, and the copies of the chunk's cells.  Workspace, owned by the handle, grow-only,
+ * freed by mp_destroy: min(n, mp_n_simd) * (n_grid + 4 n_obs) doubles of curves and cells, and 3 n_obs doubles and n_obs
+ * integers per table row on the device (one row with x_rows = 1, a chunk's rows otherwise).
+ * A multi-device handle runs the call on its first device and cfg.dipole_torque = 1 is served, as in mp_model_derived: no
+ * state of the handle makes the call return MP_ESTATE.  No dataset is needed.
+ *
+ * Rows.  A row whose status is not MP_STATUS_OK gets NaN in every output.  Every output number of a row is a function of the
+ * row's parameters, its times, its errors, its index i in the call (0 .. n - 1) and the seed; it is NOT a function of the
+ * chunking, of n or of the other rows.
+ *
+ * Model value.  The bracket of a time x on the grid t[0 .. G - 1] is formed on the host, by the code mp_set_dataset digests a
+ * light curve with: g the largest index with t[g] <= x, dx = x - t[g], and for g < G - 1 idt = 1 / (t[g + 1] - t[g]) (the
+ * last grid point: g = G - 1, dx = 0).  Times need not be sorted and may repeat; outputs are in the caller's order.  A time
+ * outside [t[0], t[G - 1]] or not finite: MP_ERANGE.  On the device, with L the row's Ltot:
+ *   dx == 0 (x is the knot t[g], the last one included):   mod = L[g]
+ *   otherwise:                                             mod = ((L[g + 1] - L[g]) * idt) * dx + L[g]
+ * every operation rounded on its own (no FMA contraction).  At grid times model_out therefore equals mp_model_lc's Ltot bit for
+ * bit: the reference's recipe.
+ *
+ * Error.  yerr given: used as is; every value has to be finite and > 0 (MP_EINVAL).  yerr NULL: yerr_out = frac_err * fabs(mod),
+ * frac_err finite and > 0 (MP_EINVAL).  A row with a resulting error of 0 (a model value of 0, or a product that underflows)
+ * cannot be a dataset: its status is MP_STATUS_ZEROERR and all its outputs are NaN.
+ *
+ * Noise.  Observation j of row i takes a standard normal z from Philox4x32-10 with key (seed & 0xFFFFFFFF, seed >> 32) and
+ * counter ((uint32) i, (uint32) (j / 2), 0, 0x53494D00): with w the four words of the draw, ua = u01(w0, w1), ub = u01(w2, w3),
+ * u01(hi, lo) = ((hi << 32 | lo) >> 11) * 2^-53,
+ *   rad = sqrt(-2 * log(1 - ua)),   ang = 6.283185307179586 * ub,   z = rad * cos(ang) for even j, rad * sin(ang) for odd j
+ * (the one Box-Muller step of the device code, with the device runtime's log, cos, sin and sqrt), and
+ *   y = mod + yerr * z
+ * product and sum rounded separately.  z_out returns z.  An odd n_obs leaves the second normal of its last pair unused.
+ *
+ * Returns MP_EINVAL for n, ndim, n_obs, n * n_obs or x_rows out of range, a NULL h, pars, x or y_out, a bad yerr or (yerr NULL) a
+ * bad frac_err, in this order; then MP_ERANGE for a bad time.  (tests/simulate_restated.py is this definition in numpy.)
+ */
+#define MP_SIM_MAX_ROWS 262144
+#define MP_SIM_MAX_CELLS 268435456 /* n * n_obs */
+int mp_simulate(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, const double *x, int n_obs, int64_t x_rows,
+                const double *yerr, double frac_err, uint64_t seed, double *y_out, double *yerr_out, double *model_out,
+                double *z_out, int32_t *status_out, int64_t *n_ok);
 
 /*
  * Radii, mass flows and torques of the model of n parameter rows, computed on the device (ABI 5, additive): the quantities

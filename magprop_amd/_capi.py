@@ -15,7 +15,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MAGPROP_AMD_LIB") or os.path.join(_PKG, "libmagprop_amd.so")  # override: A/B builds
 
 MP_OK, MP_EINVAL, MP_EHIP, MP_ERANGE, MP_ENODEV, MP_ESTATE = 0, -1, -2, -3, -4, -5
-STATUS_OK, STATUS_FLAG, STATUS_NONFINITE, STATUS_PRIOR, STATUS_BADDATASET = 0, 1, 2, 3, 4
+STATUS_OK, STATUS_FLAG, STATUS_NONFINITE, STATUS_PRIOR, STATUS_BADDATASET, STATUS_ZEROERR = 0, 1, 2, 3, 4, 5
 MAX_NDIM = 9
 MAX_DATASETS = 64
 BAND_MAX_SAMPLES, BAND_MAX_Q = 16384, 16                      # include/magprop_amd.h MP_BAND_*
@@ -23,6 +23,7 @@ BAND_LTOT, BAND_LPROP, BAND_LDIP = 1, 2, 4
 BAND_COMPONENTS = {"Ltot": BAND_LTOT, "Lprop": BAND_LPROP, "Ldip": BAND_LDIP}
 DERIVED_N = 16                                                # include/magprop_amd.h MP_DERIVED_N (columns: magprop_amd/derived.py)
 POINTWISE_N, POINTWISE_MAX_SAMPLES, POINTWISE_MAX_CELLS = 12, 262144, 1 << 28   # include/magprop_amd.h MP_POINTWISE_* (columns: magprop_amd/pointwise.py)
+SIM_MAX_ROWS, SIM_MAX_CELLS = 262144, 1 << 28                 # include/magprop_amd.h MP_SIM_*
 FLOW_N, FLOW_NCURVES = 16, 10                                 # include/magprop_amd.h MP_FLOW_* (columns and curves: magprop_amd/flows.py)
 # cell curves of mp_model_flows in the order of their mask bits MP_FLOW_CURVE_*
 FLOW_CURVES = ("Rm", "Rc", "Rlc", "fastness", "Mdot_prop", "Mdot_acc", "Mdot_fb", "N_acc", "N_dip", "branch")
@@ -90,6 +91,7 @@ SIGNATURES = {
     "mp_model_derived": (_i, [_vp, _dp, _i64, _i, _i, _dp, _ip, _i64p]),
     "mp_pointwise_tail_len": (_i, [_i64]),
     "mp_model_pointwise": (_i, [_vp, _dp, _i64, _i, _i, _i, _dp, _dp, _dp, _ip, _i64p]),
+    "mp_simulate": (_i, [_vp, _dp, _i64, _i, _i, _dp, _i, _i64, _dp, _d, _u64, _dp, _dp, _dp, _dp, _ip, _i64p]),
     "mp_model_flows": (_i, [_vp, _dp, _i64, _i, _i, _dp, _u32, _dp, _ip, _i64p]),
     "mp_model_flow_band": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _u32, _dp, _ip, _ip]),
     "mp_sampler_create": (_vp, [_vp, _i, _i, _i, _ip, _u64, _d, _i]),
@@ -623,6 +625,33 @@ class Handle(_Owner):
                                          _dptr(z) if cells else None, _iptr(st), C.byref(used)), "mp_model_pointwise")
         res = (obs, tail[:, :tlen], st, int(used.value))
         return res + (z,) if cells else res
+
+    def simulate(self, pars, x, yerr=None, frac_err=0.25, seed=0, physical=False):
+        """Simulated light curves of the rows of pars (mp_simulate): the model at the times x, an error per observation and
+        Gaussian noise.  x: (n_obs,) times shared by the rows, or (n, n_obs) a row of times each; yerr: absolute errors of x's
+        shape, or None for frac_err * |model|.  Returns {"y", "yerr", "model", "z": (n, n_obs), "status": (n,), "n_ok"}; a row
+        that did not finish, or whose error came out 0 (STATUS_ZEROERR), is all NaN.  Row i's noise depends on seed, i and the
+        observation alone.  physical=False: sampler coordinates under the handle's prior, as lnprob_batch takes them."""
+        p = np.ascontiguousarray(pars, dtype=np.float64)
+        if p.ndim != 2 or p.shape[0] < 1:
+            raise ValueError(f"pars must be 2-D (n >= 1, ndim), got shape {p.shape}")
+        n, nd = p.shape
+        xa = np.ascontiguousarray(x, dtype=np.float64)
+        if xa.ndim not in (1, 2) or xa.shape[-1] < 1 or (xa.ndim == 2 and xa.shape[0] != n):
+            raise ValueError(f"x must be (n_obs,) or (n = {n}, n_obs), got shape {xa.shape}")
+        ye = None if yerr is None else np.ascontiguousarray(yerr, dtype=np.float64)
+        if ye is not None and ye.shape != xa.shape:
+            raise ValueError(f"yerr must have x's shape {xa.shape}, got {ye.shape}")
+        n_obs, x_rows = xa.shape[-1], (1 if xa.ndim == 1 else n)
+        out = {k: np.empty((n, n_obs), dtype=np.float64) for k in ("y", "yerr", "model", "z")}
+        st = np.empty(n, dtype=np.int32)
+        ok = C.c_int64(0)
+        check(self._L.mp_simulate(self._h, _dptr(p), n, nd, int(bool(physical)), _dptr(xa), int(n_obs), x_rows,
+                                  None if ye is None else _dptr(ye), float(frac_err), C.c_uint64(int(seed) & (2**64 - 1)),
+                                  _dptr(out["y"]), _dptr(out["yerr"]), _dptr(out["model"]), _dptr(out["z"]), _iptr(st), C.byref(ok)),
+              "mp_simulate")
+        out.update(status=st, n_ok=int(ok.value))
+        return out
 
     def bridge_logz(self, x_fit, x_est, lnp_est, lower=None, upper=None, ds_id=0, n_draws=None, n_rep=1, seed=0, neff=None,
                     max_iter=1000, tol=1.0e-10, target=0, details=False):

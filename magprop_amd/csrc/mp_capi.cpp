@@ -14,6 +14,7 @@
 #include <string>
 
 #include "mp_host.h"
+#include "mp_simulate.h"
 
 static thread_local std::string g_err;
 
@@ -440,7 +441,6 @@ int mp_set_dataset(mp_handle *h, int ds_id, const double *x, const double *y, co
     if (n_obs <= 0) return fail(MP_EINVAL, "mp_set_dataset: n_obs must be positive");
     Lock lock(h->mu);
     const std::vector<double> &t = h->first()->tgrid;   // (every evaluator has the same grid: the light curve is digested once)
-    const int n = (int)t.size();
     for (int j = 0; j < n_obs; ++j) {
         if (!(x[j] >= t.front()) || !(x[j] <= t.back()))  // interp1d(bounds_error=True), magnetar/funcs.py:214-215
             return fail(MP_ERANGE, "A value in x_new is %s the interpolation range.",
@@ -454,11 +454,12 @@ int mp_set_dataset(mp_handle *h, int ds_id, const double *x, const double *y, co
     d.tile_ptr.assign((size_t)h->first()->n_tiles + 1, 0);
     for (int k = 0; k < n_obs; ++k) {
         const int j = order[k];
-        int g = (int)(std::upper_bound(t.begin(), t.end(), x[j]) - t.begin()) - 1;  // t[g] <= x < t[g+1]
-        g = std::min(std::max(g, 0), n - 2);
+        int32_t g;
+        double dx, idt;
+        mp::obs_bracket(t, x[j], g, dx, idt);   // t[g] <= x < t[g+1]; the last point: the last interval
         d.g.push_back(g);
-        d.dx.push_back(x[j] - t[g]);
-        d.idt.push_back(1.0 / (t[g + 1] - t[g]));
+        d.dx.push_back(dx);
+        d.idt.push_back(idt);
         d.y.push_back(y[j]);
         d.yerr.push_back(yerr[j]);
         d.tile_ptr[(size_t)(g / mp::kTile) + 1] += 1;

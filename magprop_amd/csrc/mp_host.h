@@ -172,6 +172,8 @@ struct Evaluator {
     DevBuf<double> w_flow_cells, w_flow_out;      // mp_model_flows: [MP_FLOW_NCURVES][chunk][n_grid] cell curves; [chunk][MP_FLOW_N]
     DevBuf<double> w_flow_band;                   // mp_model_flow_band: [selected curves][n][n_grid]; kept between calls for one curve only
     DevBuf<double> w_pw_z, w_pw_obs, w_pw_tail;   // mp_model_pointwise: [n_obs][n] cells; [n_obs][MP_POINTWISE_N]; [n_obs][T(n)]
+    DevBuf<double> w_sim;                         // mp_simulate: [dx | idt | yerr][table rows][n_obs], then [y | yerr | model | z][chunk][n_obs]
+    DevBuf<int32_t> w_sim_g;                      // mp_simulate: [table rows][n_obs] the brackets' g, then [n] the rows' zero-error marks
     DevBuf<int32_t> w_dsid, w_status, w_sweeps;
     DevBuf<int32_t> w_tile_log;
     std::vector<int32_t> last_tile_log;   // tile words of the rows of its block of the most recent host-buffer batch

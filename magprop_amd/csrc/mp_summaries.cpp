@@ -1,5 +1,6 @@
 // mp_summaries.cpp — the summaries of model curves over host rows of parameters (mp_model_lc, mp_model_band*, mp_model_derived,
-// mp_model_flows, mp_model_flow_band, mp_model_pointwise).  Kernels: mp_band.hip, mp_derive.hip, mp_flows.hip, mp_pointwise.hip.
+// mp_model_flows, mp_model_flow_band, mp_model_pointwise, mp_simulate).  Kernels: mp_band.hip, mp_derive.hip, mp_flows.hip,
+// mp_pointwise.hip, mp_simulate.hip.
 //
 // First what the entries share: the curve pass, which builds the curves of the rows on the device chunk by chunk and hands every
 // chunk to the entry's own kernels and copies, and the band of curve matrices.  Then the entries, each on the handle's first
@@ -9,9 +10,10 @@
 #include "mp_flows.h"
 #include "mp_host.h"
 #include "mp_pointwise.h"
+#include "mp_simulate.h"
 
 // ---------------------------------------------------------------- the curve pass
-// What mp_model_lc, mp_model_band, mp_model_derived, mp_model_pointwise, mp_model_flows and mp_model_flow_band share: the curves of host rows pars[n][ndim], built on
+// What mp_model_lc, mp_model_band, mp_model_derived, mp_model_pointwise, mp_simulate, mp_model_flows and mp_model_flow_band share: the curves of host rows pars[n][ndim], built on
 // the device chunk by chunk and handed to the caller's own kernels and copies.  (The caller holds the evaluator, has validated its
 // arguments and has ensured its own workspaces.)
 // a set of curves: bit i is curve i of Ltot, Lprop, Ldip, Mdisc, omega
@@ -382,6 +384,113 @@ int mp_model_pointwise(mp_handle *h, const double *pars, int64_t n, int ndim, in
         if (ce != hipSuccess) return fail(MP_EHIP, "mp_model_pointwise: copy failed: %s", hipGetErrorString(ce));
         return (int)MP_OK;
     });
+}
+
+// The rows go through the device in chunks of n_simd rows as in mp_model_pointwise, with Ltot alone: every chunk's curve launch is
+// followed by the launch that turns its rows into cells, and the copies of the chunk's cells to the caller's rows [lo, lo + cnt).
+// The brackets are formed here, on the host, by the rule mp_set_dataset keeps (mp_simulate.h); shared tables go up once, per-row
+// tables chunk by chunk.  A row's noise is drawn under its index in the call (lo + its place in the chunk), so nothing depends
+// on the chunking.  Behind the pass the rows the kernel marked (a cell with error 0) get MP_STATUS_ZEROERR and NaN cells.
+int mp_simulate(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, const double *x, int n_obs, int64_t x_rows,
+                const double *yerr, double frac_err, uint64_t seed, double *y_out, double *yerr_out, double *model_out,
+                double *z_out, int32_t *status_out, int64_t *n_ok) {
+    // (the sizes first: they can be judged without a handle)
+    if (n < 1 || n > MP_SIM_MAX_ROWS) return fail(MP_EINVAL, "mp_simulate: n must be 1..%d (MP_SIM_MAX_ROWS), got %lld", MP_SIM_MAX_ROWS, (long long)n);
+    if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "mp_simulate: ndim must be 6..9, got %d", ndim);
+    if (n_obs < 1) return fail(MP_EINVAL, "mp_simulate: n_obs must be at least 1, got %d", n_obs);
+    if (n * (int64_t)n_obs > (int64_t)MP_SIM_MAX_CELLS)
+        return fail(MP_EINVAL, "mp_simulate: n * n_obs = %lld * %d exceeds MP_SIM_MAX_CELLS = %lld", (long long)n, n_obs, (long long)MP_SIM_MAX_CELLS);
+    if (x_rows != 1 && x_rows != n) return fail(MP_EINVAL, "mp_simulate: x_rows must be 1 or n = %lld, got %lld", (long long)n, (long long)x_rows);
+    if (!h || !pars || !x || !y_out) return fail(MP_EINVAL, "mp_simulate: NULL argument");
+    const size_t nn = (size_t)n, no = (size_t)n_obs, tab = (size_t)x_rows * no;
+    if (yerr) {
+        for (size_t j = 0; j < tab; ++j)
+            if (!(yerr[j] > 0.0) || !std::isfinite(yerr[j])) return fail(MP_EINVAL, "mp_simulate: yerr[%zu] = %g is not finite and > 0", j, yerr[j]);
+    } else if (!(frac_err > 0.0) || !std::isfinite(frac_err)) {
+        return fail(MP_EINVAL, "mp_simulate: frac_err = %g is not finite and > 0", frac_err);
+    }
+    Evaluator *ev = h->first();
+    Held held(h, ev);
+    const std::vector<double> &t = ev->tgrid;
+    std::vector<int32_t> g(tab);
+    std::vector<double> dx(tab), idt(tab);
+    for (size_t j = 0; j < tab; ++j) {
+        if (!(x[j] >= t.front()) || !(x[j] <= t.back()))
+            return fail(MP_ERANGE, "mp_simulate: x[%zu] = %g is outside the model grid [%g, %g]", j, x[j], t.front(), t.back());
+        mp::sim_bracket(t, x[j], g[j], dx[j], idt[j]);
+    }
+    const size_t chunk = (size_t)std::min<int64_t>(n, std::max(1, ev->sh.n_simd));
+    const size_t trows = x_rows == 1 ? 1 : chunk;             // table rows on the device at a time
+    const size_t tcells = trows * no, ccells = chunk * no;
+    int rc;
+    if ((rc = ev->w_sim.ensure(3 * tcells + 4 * ccells)) || (rc = ev->w_sim_g.ensure(tcells + nn))) return rc;
+    double *d_dx = ev->w_sim.p, *d_idt = d_dx + tcells, *d_ye_in = d_idt + tcells, *d_out = d_ye_in + tcells;
+    int32_t *d_g = ev->w_sim_g.p, *d_zero = d_g + tcells;
+    hipStream_t st = ev->stream;
+    auto upload = [&](size_t row_lo, size_t rows) {           // table rows [row_lo, row_lo + rows) to the front of the device tables
+        const size_t o = row_lo * no, c = rows * no;
+        hipError_t e = hipMemcpyAsync(d_g, g.data() + o, sizeof(int32_t) * c, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_dx, dx.data() + o, sizeof(double) * c, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_idt, idt.data() + o, sizeof(double) * c, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && yerr) e = hipMemcpyAsync(d_ye_in, yerr + o, sizeof(double) * c, hipMemcpyHostToDevice, st);
+        return e;
+    };
+    HIP_TRY(hipMemsetAsync(d_zero, 0, sizeof(int32_t) * nn, st));
+    if (x_rows == 1) {
+        const hipError_t e = upload(0, 1);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            return fail(MP_EHIP, "mp_simulate: copy failed: %s", hipGetErrorString(e));
+        }
+    }
+    std::vector<int32_t> stt(nn);
+    rc = curve_pass(ev, pars, nn, ndim, physical, kCurveLtot, chunk, stt.data(), nullptr, [&](const CurveChunk &k) {
+        hipError_t ce = x_rows == 1 ? hipSuccess : upload(k.lo, k.cnt);
+        if (ce != hipSuccess) return fail(MP_EHIP, "mp_simulate: copy failed: %s", hipGetErrorString(ce));
+        mp::SimCellsArgs c{};
+        c.ltot = k.curve[0];                      // (the rows of walkers that did not finish are not read)
+        c.status = k.status;
+        c.g = d_g;
+        c.dx = d_dx;
+        c.idt = d_idt;
+        c.yerr = yerr ? d_ye_in : nullptr;
+        c.frac_err = frac_err;
+        c.seed = seed;
+        c.row0 = (int64_t)k.lo;
+        c.y = d_out;
+        c.ye = yerr_out ? d_out + ccells : nullptr;
+        c.mod = model_out ? d_out + 2 * ccells : nullptr;
+        c.z = z_out ? d_out + 3 * ccells : nullptr;
+        c.zero_err = d_zero + k.lo;
+        c.cnt = (int32_t)k.cnt;
+        c.n_obs = n_obs;
+        c.n_grid = (int32_t)t.size();
+        c.tab_rows = x_rows == 1 ? 1 : (int32_t)k.cnt;
+        const int e = mp::launch_simulate_cells(c, (void *)k.st);
+        if (e) return fail(MP_EHIP, "simulate cells kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        double *const host[4] = {y_out, yerr_out, model_out, z_out};
+        for (int i = 0; i < 4 && ce == hipSuccess; ++i)
+            if (host[i]) ce = hipMemcpyAsync(host[i] + k.lo * no, d_out + (size_t)i * ccells, sizeof(double) * k.cnt * no, hipMemcpyDeviceToHost, k.st);
+        if (ce != hipSuccess) return fail(MP_EHIP, "mp_simulate: copy failed: %s", hipGetErrorString(ce));
+        return (int)MP_OK;
+    });
+    if (rc) return rc;
+    // (curve_pass has synchronised the stream)
+    std::vector<int32_t> zero(nn);
+    HIP_TRY(hipMemcpy(zero.data(), d_zero, sizeof(int32_t) * nn, hipMemcpyDeviceToHost));
+    int64_t ok = 0;
+    for (size_t i = 0; i < nn; ++i) {
+        if (stt[i] == MP_STATUS_OK && zero[i]) {
+            stt[i] = MP_STATUS_ZEROERR;
+            double *const host[4] = {y_out, yerr_out, model_out, z_out};
+            for (double *o : host)
+                if (o) std::fill(o + i * no, o + (i + 1) * no, std::nan(""));
+        }
+        ok += stt[i] == MP_STATUS_OK;
+    }
+    if (status_out) std::memcpy(status_out, stt.data(), sizeof(int32_t) * nn);
+    if (n_ok) *n_ok = ok;
+    return MP_OK;
 }
 
 }  // extern "C"

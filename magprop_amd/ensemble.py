@@ -114,6 +114,7 @@ class EnsembleSampler:
         self._acf = None            # (max_lag, discard) of the device autocorrelation monitor; None: off
         self._post = None           # (bins, bins2, lower, upper) of the device posterior monitor; None: off
         self.converged = False      # run_mcmc_until
+        self.converged_ensembles = None
         self.tau_history = []
 
     def close(self):
@@ -718,7 +719,7 @@ class EnsembleSampler:
             ("nonfinite", None, None), ("n", None, None)], e)
         return posterior.hist_quantiles(h["hist1"], h["below"], h["above"], lo, hi, q)
 
-    def run_mcmc_until(self, pos, max_steps, check_every=100, tol=50, rtol=0.01, c=5.0, store=True):
+    def run_mcmc_until(self, pos, max_steps, check_every=100, tol=50, rtol=0.01, c=5.0, store=True, per_ensemble=False):
         """emcee's run-until-converged recipe on the device monitor: after every check_every steps read tau (the beta = 1
         ensembles of a tempered sampler) and stop once autocorr_converged(tau, previous tau, n, tol, rtol) holds, n the
         monitor's samples, or after max_steps.  Turns the monitor on (max_lag 1024, discard 0) if it is off.  Sets
@@ -728,7 +729,11 @@ class EnsembleSampler:
         store=False run ends with tau and with the histograms, moments and best sample of get_posterior.  Both restart at
         set_positions, so give pos=None to keep what a monitor holds, and turn monitor_posterior on after the burn-in.
         The sample reservoir (monitor_samples) is fed from the same rows: with it a store=False run also ends with posterior
-        samples (get_samples), and the band, derived quantities, flows and pointwise scores take them with source="reservoir"."""
+        samples (get_samples), and the band, derived quantities, flows and pointwise scores take them with source="reservoir".
+        per_ensemble=True (ensembles that are fits of their own, one per dataset): the rule is applied to every reported ensemble
+        on its own and remembered once met -- an ensemble's chain that was long enough at one check stays long enough -- and the
+        run stops when every ensemble has met it; self.converged_ensembles holds the flags.  The default asks all ensembles to
+        meet the rule at the same check, which many independent fits do far later than any one of them."""
         max_steps, check_every = int(max_steps), int(check_every)
         if check_every < 1 or max_steps < 0:
             raise ValueError(f"check_every must be >= 1 and max_steps >= 0, got {check_every}, {max_steps}")
@@ -741,6 +746,7 @@ class EnsembleSampler:
         done, prev = 0, None
         first_step = self.iteration
         self.converged, self.tau_history = False, []
+        self.converged_ensembles = np.zeros(self.nensembles // self.ntemps, dtype=bool)   # one flag per reported ensemble
         while done < max_steps and not self.converged:
             k = min(check_every, max_steps - done)
             cp, lp = (_capi.ptr(chain[done:done + k]), _capi.ptr(lnp[done:done + k])) if store else (None, None)
@@ -754,7 +760,14 @@ class EnsembleSampler:
             if tau is None:                            # still inside the monitor's discard: fewer than 2 samples
                 continue
             self.tau_history.append((n, tau))
-            self.converged = autocorr_converged(tau, prev, n, tol, rtol)
+            if per_ensemble:
+                rows = np.atleast_2d(tau)
+                for e in range(len(rows)):
+                    self.converged_ensembles[e] |= autocorr_converged(rows[e], None if prev is None else np.atleast_2d(prev)[e], n, tol, rtol)
+                self.converged = bool(np.all(self.converged_ensembles))
+            else:
+                self.converged = autocorr_converged(tau, prev, n, tol, rtol)
+                self.converged_ensembles[:] = self.converged
             prev = tau
         if store and done > 0:
             if done < max_steps:                       # an early stop gives the unused rows back (refcheck: no other owner here)

@@ -117,6 +117,14 @@ def _source(GRBtype, custom_lims, device, data=None):
     return enter
 
 
+def generate_data(pars, GRBtype, times=None, n_obs=50, frac_err=0.25, seed=0, yerr=None, custom_lims=None, physical=False, device=-1):
+    """Synthetic light curves of the library model from known parameters on the grid of ``GRBtype`` ("L" or "S"): pars (ndim,) or
+    (n, ndim), 6..9 parameters in the sampler coordinates of ``lnprob`` (physical=True: physical ones, as ``lnlike`` takes
+    them), observed at ``times`` ((n_obs,) or (n, n_obs); None: n_obs grid points drawn as ``synth.generate_data`` draws them)
+    with errors yerr or frac_err * |model| and Gaussian noise (mp_simulate).  Returns what ``synth.generate_data`` returns."""
+    return summaries.simulate(_source(GRBtype, custom_lims, device), pars, times, n_obs, frac_err, seed, yerr, physical, width=(6, 9))
+
+
 def model_band(samples, GRBtype, custom_lims=None, q=(0.025, 0.5, 0.975), components=("Ltot",), weights=None, device=-1):
     """Posterior-predictive band of the library model: per point of the grid of ``GRBtype``, the quantiles q of the light
     curves of the rows of `samples` (n, 6..9) in the sampler coordinates of ``lnprob`` (rows outside the prior or whose model

@@ -1,5 +1,5 @@
 """The summaries of model curves over a set of parameter rows, each one path from the rows to the result: the light-curve band,
-the derived quantities, the flows, the flow band and the pointwise scores.
+the derived quantities, the flows, the flow band, the pointwise scores and the simulated light curves.
 
 Every front end (synth, mcmc_eqns, EnsembleSampler, NestedSampler) hands its rows and the request to one function here, together
 with its *source*: a function of the rows' width that returns a context manager yielding (handle, dataset slot, times) -- the
@@ -81,6 +81,28 @@ def flows(source, samples, q, weights=None, curves=(), width=None):
     if cells is not None:
         out["t"] = t
         out.update({c: cells[:, k] for k, c in enumerate(names)})
+    return out
+
+
+def simulate(source, pars, x=None, n_obs=50, frac_err=0.25, seed=0, yerr=None, physical=False, width=None):
+    """{"x", "y", "yerr", "model", "z", "status", "n_ok"} of Handle.simulate(rows, x): noisy light curves of the rows.  pars (ndim,)
+    gives 1-D arrays, pars (n, ndim) arrays (n, n_obs) with "x" (n_obs,) when the rows share their times.  x=None is the
+    reference's recipe (code/synthetic_datasets/generate_data.py:61-67): n_obs indices of the handle's grid drawn with
+    replacement from numpy.random.default_rng(seed) and sorted, shared by the rows; the noise comes from the device's own
+    generator under the same seed."""
+    single = np.ndim(pars) == 1
+    p = _rows(np.atleast_2d(np.asarray(pars, dtype=np.float64)), width)
+    if x is None and int(n_obs) < 1:
+        raise ValueError(f"n_obs must be at least 1, got {n_obs}")
+    with source(p.shape[1]) as (handle, _, _):
+        if x is None:
+            t = handle.tgrid
+            x = t[np.sort(np.random.default_rng(seed).integers(0, t.size, size=int(n_obs)))]
+        xa = np.asarray(x, dtype=np.float64)
+        out = handle.simulate(p, xa, yerr=yerr, frac_err=frac_err, seed=seed, physical=physical)
+    out["x"] = xa.copy()
+    if single:
+        out.update({k: out[k][0] for k in ("y", "yerr", "model", "z")}, x=xa.reshape(-1), status=int(out["status"][0]))
     return out
 
 

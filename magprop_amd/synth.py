@@ -85,6 +85,28 @@ def _source(device, x=None, y=None, yerr=None):
     return enter
 
 
+# the four canonical parameter sets of code/synthetic_datasets/generate_data.py:10-15, physical as the reference writes them
+GRBS = {"Humped": (1.0, 5.0, 1.0e-3, 100.0, 0.1, 1.0), "Classic": (1.0, 5.0, 1.0e-3, 1000.0, 0.1, 1.0),
+        "Sloped": (1.0, 1.0, 1.0e-3, 100.0, 10.0, 10.0), "Stuttering": (1.0, 5.0, 1.0e-5, 100.0, 0.1, 100.0)}
+
+
+def generate_data(pars=None, grb=None, n_obs=50, frac_err=0.25, seed=0, x=None, yerr=None, physical=False, device=-1):
+    """A synthetic light curve from known parameters, the recipe of code/synthetic_datasets/generate_data.py:61-67 on the device
+    (mp_simulate): the model at n_obs grid points drawn with replacement and sorted (numpy.random.default_rng(seed)), yerr =
+    frac_err * |model|, Gaussian noise.  grb: one of GRBS by name (its physical parameters, as the reference takes them); or
+    pars (6,) / (n, 6) for n datasets at once, in sampler coordinates (physical=True: physical ones).  x: observed times
+    instead of the draw, anywhere inside the grid, (n_obs,) or (n, n_obs); yerr: absolute errors of x's shape instead of
+    frac_err.  Returns {"x", "y", "yerr", "model", "z", "status", "n_ok"}; dataset i's noise depends on seed and i alone.  A row
+    whose model failed, or with a zero error (_capi.STATUS_ZEROERR), is all NaN."""
+    if (pars is None) == (grb is None):
+        raise ValueError("give either pars or grb")
+    if grb is not None:
+        if grb not in GRBS:
+            raise ValueError(f"grb must be one of {', '.join(GRBS)}, got {grb!r}")
+        pars, physical = np.array(GRBS[grb]), True
+    return summaries.simulate(_source(device), pars, x, n_obs, frac_err, seed, yerr, physical, width=6)
+
+
 def model_band(samples, q=(0.025, 0.5, 0.975), components=("Ltot",), device=-1, weights=None):
     """Posterior-predictive band of the synthetic model: per point of the grid logspace(0, 6, 10001), the quantiles q of the
     light curves of `samples` (rows in sampler coordinates, as a chain stores them; rows outside the prior or whose model
