@@ -1331,6 +1331,63 @@ int mp_bridge_logz(mp_handle *h, const double *x_fit, int64_t n_fit, const doubl
                    double neff, int max_iter, double tol, int target, double *out, double *moments, double *draws,
                    double *draw_lnp, double *draw_lnq, double *est_lnq);
 
+/*
+ * Bridge sampling with a Student-t proposal and with Warp-III (ABI 5, additive; Meng & Schilling 2002; "warp3" of Gronau et al.'s
+ * bridgesampling).  Everything mp_bridge_logz takes means here what it means there: the moments, the factor (m, L, c), the
+ * counters of z, the fixed point, dlnz and the status codes are those of mp_bridge_logz, and with proposal = MP_BRIDGE_NORMAL and
+ * warp = 0 every output both entries have is bit for bit mp_bridge_logz's (formed by kernels of this entry's own).  As there,
+ * every product, sum and difference is rounded on its own, sums run in the order written, and exp, log, sqrt are the device's
+ * unless "the host's" is said.
+ * target: 0 .. 2 as in mp_bridge_logz; 3 and 4 are test targets of this entry alone.  3, the split normal: u_d = x_d for
+ *   x_d < 0, else 0.25 x_d; lnp = 0 - (0.5 u_0) u_0 - (0.5 u_1) u_1 - ... (ln of its integral: ndim (ln 2.5 + 0.5 ln 2 pi)).
+ *   4, the product of t_3 densities: lnp = 0 - 2 log(1 + (x_0 x_0) / 3) - 2 log(1 + (x_1 x_1) / 3) - ... (ndim ln(sqrt(3) pi / 2)).
+ * proposal = MP_BRIDGE_STUDENT: the multivariate t with nu (3 .. MP_BRIDGE_MAX_NU, read for this proposal only) degrees of
+ *   freedom and the covariance L L^T.  Host (doubles; the host's sqrt, log, lgamma): k = sqrt((nu - 2) / nu); L_t,ab = k L_ab;
+ *   c_t = ((ln L_t,00 + ln L_t,11 + ..., in order from 0.0) + (0.5 ndim) log(nu 3.141592653589793)) + lgamma(nu / 2) -
+ *   lgamma((nu + ndim) / 2); h = 0.5 (nu + ndim).
+ *   Draw (device, one thread per draw): z as in mp_bridge_logz.  Pairs p = 0 .. ceil(nu / 2) - 1 of normals g_2p, g_2p+1 by the
+ *   same Box-Muller formula from Philox4x32-10 keyed (seed; j, r, p, 0x42524701); w = g_0 g_0 + g_1 g_1 + ... + g_nu-1 g_nu-1 in
+ *   order from 0.0 (an odd nu leaves the second normal of its last pair unused); scale = sqrt(nu / w);
+ *   s_a = L_t,a0 z_0 + ... + L_t,aa z_a from 0.0 in order; x_a = m_a + scale s_a; xi_a = scale z_a; Q = xi_0 xi_0 + ... from 0.0
+ *   in order; lnq = (-h) log(1 + Q / nu) - c_t.  Estimator rows: xi by mp_bridge_logz's forward substitution with L_t for L,
+ *   then Q and lnq by the same formula.  (MP_BRIDGE_NORMAL: x_a = m_a + s_a with L, lnq as in mp_bridge_logz.)
+ * warp = 1: the posterior is replaced by its symmetrisation about m, q~(x) = (q(x) + q(2 m - x)) / 2, which either proposal,
+ *   symmetric about m, covers with the lnq of the point itself.  The mirror of a draw is x'_a = m_a - scale s_a (m_a - s_a for
+ *   the Gaussian), formed beside the draw from the same rounded product; the mirror of an estimator row is
+ *   x'_a = m_a - (x_a - m_a).  v, v' the lnprob of a point and of its mirror: a point counts where it lies in [lower, upper] in
+ *   every coordinate (no box: everywhere) and its lnprob is finite; an estimator row itself always counts (its lnp_est is
+ *   finite by the checks and it is taken as the caller's sample).  t = lse2(v, v') where both count, the one that counts where
+ *   one does; a_i = (t - 0.6931471805599453) - lnq_i, b_j likewise, b_j = -inf where neither the draw nor its mirror counts; no
+ *   lse2 of an infinite value is formed.  warp = 0: a_i = lnp_est_i - lnq_i, b_j = lnp_j - lnq_j or -inf, as in mp_bridge_logz.
+ *   n_finite counts the b_j > -inf.
+ * Evaluation.  Targets 1 .. 4: the arithmetic above (1, 2: mp_bridge_logz's) at every draw and at every mirror.  Target 0,
+ *   warp = 0: one launch of mp_lnprob_batch_dev over the n_rep n_draws draws.  Target 0, warp = 1: one launch over
+ *   2 n_rep n_draws rows, all draws first, then all mirrors in the same order: draw_lnp and draw_mirror_lnp are bit for bit what
+ *   mp_lnprob_batch returns for those rows in one batch of that size and order; the estimator rows go through the device in
+ *   chunks of 64 MP_BRIDGE_BLOCK consecutive rows from row 0 (the last one shorter), and the mirrors of each chunk are one
+ *   launch of mp_lnprob_batch_dev of the chunk's size: est_mirror_lnp is bit for bit mp_lnprob_batch of those rows in batches
+ *   of those sizes.  The mirror arrays hold the lnprob as evaluated, whether or not the point counts.
+ * Optional outputs beside mp_bridge_logz's (NULL: not wanted): a_out[n_est], b_out[n_rep n_draws], the log-ratios the fixed
+ *   point reads; with warp = 1 draw_mirrors[n_rep n_draws][ndim], est_mirror_lnp[n_est], draw_mirror_lnp[n_rep n_draws] (not
+ *   written with warp = 0).
+ * out[n_rep][MP_BRIDGE_WARP_NOUT]: the MP_BRIDGE_NOUT columns of mp_bridge_logz in their places, then MP_BRIDGE_EST_MIRRORS, the
+ *   estimator rows whose mirror counts (the same in every row), and MP_BRIDGE_DRAW_MIRRORS, the draws of the repetition whose
+ *   mirror counts (both 0 with warp = 0).
+ * MP_EINVAL: whatever mp_bridge_logz refuses, with target outside 0 .. 4 in place of 0 .. 2 and a NULL box allowed for targets
+ * 1 .. 4; proposal outside 0 .. 1; nu outside 3 .. MP_BRIDGE_MAX_NU for MP_BRIDGE_STUDENT; warp outside 0 .. 1; with warp = 1,
+ * 2 n_rep n_draws above MP_BRIDGE_MAX_ROWS.  MP_ERANGE and MP_ESTATE as in mp_bridge_logz.
+ */
+#define MP_BRIDGE_NORMAL 0
+#define MP_BRIDGE_STUDENT 1
+#define MP_BRIDGE_MAX_NU 32
+#define MP_BRIDGE_WARP_NOUT 14
+enum { MP_BRIDGE_EST_MIRRORS = 12, MP_BRIDGE_DRAW_MIRRORS };
+int mp_bridge_logz_warp(mp_handle *h, const double *x_fit, int64_t n_fit, const double *x_est, const double *lnp_est, int64_t n_est,
+                        int ndim, int ds_id, const double *lower, const double *upper, int64_t n_draws, int n_rep, uint64_t seed,
+                        double neff, int max_iter, double tol, int target, int proposal, int nu, int warp, double *out,
+                        double *moments, double *draws, double *draw_lnp, double *draw_lnq, double *est_lnq, double *a_out,
+                        double *b_out, double *draw_mirrors, double *est_mirror_lnp, double *draw_mirror_lnp);
+
 /* wait for everything enqueued on the handle's own stream */
 int mp_synchronize(mp_handle *h);
 

@@ -43,6 +43,10 @@ BRIDGE_BLOCK, BRIDGE_MAX_REP, BRIDGE_MAX_ROWS, BRIDGE_NOUT = 4096, 64, 1 << 22, 
 BRIDGE_OK, BRIDGE_ITER_LIMIT, BRIDGE_NO_OVERLAP = 0, 1, 2
 # columns of mp_bridge_logz's out rows, in the order of MP_BRIDGE_LNZ .. MP_BRIDGE_VAR2
 BRIDGE_COLUMNS = ("lnz", "lambda", "ln_volume", "dlnz", "niter", "status", "n_finite", "lambda0", "mean1", "var1", "mean2", "var2")
+BRIDGE_NORMAL, BRIDGE_STUDENT, BRIDGE_MAX_NU, BRIDGE_WARP_NOUT = 0, 1, 32, 14   # include/magprop_amd.h mp_bridge_logz_warp
+BRIDGE_PROPOSALS = {"normal": BRIDGE_NORMAL, "t": BRIDGE_STUDENT}
+# columns of mp_bridge_logz_warp's out rows: mp_bridge_logz's, then MP_BRIDGE_EST_MIRRORS and MP_BRIDGE_DRAW_MIRRORS
+BRIDGE_WARP_COLUMNS = BRIDGE_COLUMNS + ("est_mirrors", "draw_mirrors")
 
 ABI_VERSION = 5
 # order of mp_get_policy()'s vector (include/magprop_amd.h MP_POLICY_*)
@@ -161,6 +165,8 @@ SIGNATURES = {
     "mp_smc_get_tuning": (_i, [_vp, _i, _i, _ip, _dp, _dp, _ip]),
     "mp_smc_destroy": (_i, [_vp]),
     "mp_bridge_logz": (_i, [_vp, _dp, _i64, _dp, _dp, _i64, _i, _i, _dp, _dp, _i64, _i, _u64, _d, _i, _d, _i, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mp_bridge_logz_warp": (_i, [_vp, _dp, _i64, _dp, _dp, _i64, _i, _i, _dp, _dp, _i64, _i, _u64, _d, _i, _d, _i, _i, _i, _i, _dp, _dp, _dp,
+                                 _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mp_synchronize": (_i, [_vp]),
     "mp_device": (_i, [_vp]),
     "mp_stream": (_vp, [_vp]),
@@ -394,6 +400,19 @@ def kish_n_eff(weights, status):
     w = np.asarray(weights, dtype=np.float64)[np.asarray(status) == STATUS_OK]
     s2 = float(np.sum(w * w))
     return float(np.sum(w)) ** 2 / s2 if s2 > 0.0 else 0.0
+
+
+def bridge_proposal(proposal, nu=5, warp=False):
+    """(proposal, nu, warp) as mp_bridge_logz_warp takes them, of proposal "normal" | "t" (or MP_BRIDGE_NORMAL | MP_BRIDGE_STUDENT),
+    nu and warp, judged by the entry's own rules; nu is 0 where it is not read."""
+    prop = BRIDGE_PROPOSALS.get(proposal, proposal) if isinstance(proposal, str) else proposal
+    if isinstance(prop, bool) or prop not in (BRIDGE_NORMAL, BRIDGE_STUDENT):
+        raise ValueError(f"proposal must be one of {tuple(BRIDGE_PROPOSALS)}, got {proposal!r}")
+    if prop == BRIDGE_STUDENT and not (isinstance(nu, (int, np.integer)) and not isinstance(nu, bool) and 3 <= nu <= BRIDGE_MAX_NU):
+        raise ValueError(f"nu must be an integer in 3..{BRIDGE_MAX_NU} (MP_BRIDGE_MAX_NU), got {nu!r}")
+    if not isinstance(warp, (bool, np.bool_)) and warp not in (0, 1):
+        raise ValueError(f"warp must be True or False, got {warp!r}")
+    return int(prop), int(nu) if prop == BRIDGE_STUDENT else 0, int(bool(warp))
 
 
 class _Owner:
@@ -654,12 +673,18 @@ class Handle(_Owner):
         return out
 
     def bridge_logz(self, x_fit, x_est, lnp_est, lower=None, upper=None, ds_id=0, n_draws=None, n_rep=1, seed=0, neff=None,
-                    max_iter=1000, tol=1.0e-10, target=0, details=False):
+                    max_iter=1000, tol=1.0e-10, target=0, details=False, proposal="normal", nu=5, warp=False):
         """The bridge-sampling evidence of mp_bridge_logz: a Gaussian fitted to the rows x_fit, n_draws draws from it per
         repetition, and the fixed point over the rows x_est with their lnprob lnp_est (sampler coordinates; the box lower,
-        upper is the prior's support, None for the test targets 1 and 2).  n_draws=None: as many as x_est has rows; neff=None:
+        upper is the prior's support, None for the test targets).  n_draws=None: as many as x_est has rows; neff=None:
         that number too (independent rows).  Returns {"out": (n_rep, BRIDGE_NOUT), columns BRIDGE_COLUMNS}; details=True adds
-        "moments", "draws" (n_rep, n_draws, ndim), "draw_lnp", "draw_lnq" (n_rep, n_draws) and "est_lnq" (n_est,)."""
+        "moments", "draws" (n_rep, n_draws, ndim), "draw_lnp", "draw_lnq" (n_rep, n_draws) and "est_lnq" (n_est,).
+        proposal="t" (a Student-t with nu degrees of freedom and the rows' covariance), warp=True (Warp-III: the posterior
+        symmetrised about the rows' mean) or a target above 2 go to mp_bridge_logz_warp: "out" is (n_rep, BRIDGE_WARP_NOUT),
+        columns BRIDGE_WARP_COLUMNS, and details=True adds "a" (n_est,) and "b" (n_rep, n_draws) too, with warp also
+        "draw_mirrors", "draw_mirror_lnp" and "est_mirror_lnp".  With the defaults the call is mp_bridge_logz's as before."""
+        prop = bridge_proposal(proposal, nu, warp)
+        new = prop != (BRIDGE_NORMAL, 0, 0) or int(target) > 2
         xf = np.ascontiguousarray(x_fit, dtype=np.float64)
         xe = np.ascontiguousarray(x_est, dtype=np.float64)
         le = np.ascontiguousarray(lnp_est, dtype=np.float64)
@@ -676,22 +701,25 @@ class Handle(_Owner):
             hi = np.ascontiguousarray(upper, dtype=np.float64)
             if lo.shape != (nd,) or hi.shape != (nd,):
                 raise ValueError(f"lower and upper must have shape ({nd},), got {lo.shape}, {hi.shape}")
-        out = np.full((max(n_rep, 1), BRIDGE_NOUT), np.nan)
-        nm, tot = nd + nd * (nd + 1) // 2, max(n_rep, 1) * max(n_draws, 1)
-        det = {}
-        if details:
-            det = {"moments": np.full(nm, np.nan), "draws": np.full((tot, nd), np.nan), "draw_lnp": np.full(tot, np.nan),
-                   "draw_lnq": np.full(tot, np.nan), "est_lnq": np.full(max(n_est, 1), np.nan)}
-        opt = [(_dptr(det[k]) if details else None) for k in ("moments", "draws", "draw_lnp", "draw_lnq", "est_lnq")]
-        check(self._L.mp_bridge_logz(self._h, _dptr(xf), xf.shape[0], _dptr(xe), _dptr(le), n_est, nd, int(ds_id),
-                                     None if lo is None else _dptr(lo), None if hi is None else _dptr(hi), n_draws, n_rep,
-                                     C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(n_est if neff is None else neff), int(max_iter),
-                                     float(tol), int(target), _dptr(out), *opt), "mp_bridge_logz")
+        out = np.full((max(n_rep, 1), BRIDGE_WARP_NOUT if new else BRIDGE_NOUT), np.nan)
+        nm, tot, ne = nd + nd * (nd + 1) // 2, max(n_rep, 1) * max(n_draws, 1), max(n_est, 1)
+        # the optional outputs in the entries' order: mp_bridge_logz's five, then mp_bridge_logz_warp's
+        shapes = {"moments": nm, "draws": (tot, nd), "draw_lnp": tot, "draw_lnq": tot, "est_lnq": ne}
+        if new:
+            shapes.update(a=ne, b=tot, draw_mirrors=(tot, nd), est_mirror_lnp=ne, draw_mirror_lnp=tot)
+        mirrors = ("draw_mirrors", "est_mirror_lnp", "draw_mirror_lnp")
+        det = {k: np.full(shape, np.nan) for k, shape in shapes.items() if details and (prop[2] or k not in mirrors)}
+        opt = [(_dptr(det[k]) if k in det else None) for k in shapes]
+        lead = (self._h, _dptr(xf), xf.shape[0], _dptr(xe), _dptr(le), n_est, nd, int(ds_id), None if lo is None else _dptr(lo),
+                None if hi is None else _dptr(hi), n_draws, n_rep, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                float(n_est if neff is None else neff), int(max_iter), float(tol), int(target))
+        if new:
+            check(self._L.mp_bridge_logz_warp(*lead, *prop, _dptr(out), *opt), "mp_bridge_logz_warp")
+        else:
+            check(self._L.mp_bridge_logz(*lead, _dptr(out), *opt), "mp_bridge_logz")
         res = {"out": out}
-        if details:
-            res.update(moments=det["moments"], draws=det["draws"].reshape(n_rep, n_draws, nd),
-                       draw_lnp=det["draw_lnp"].reshape(n_rep, n_draws), draw_lnq=det["draw_lnq"].reshape(n_rep, n_draws),
-                       est_lnq=det["est_lnq"][:n_est])
+        for k, v in det.items():      # per call, per estimator row, or per draw of a repetition
+            res[k] = v if k == "moments" else v[:n_est] if k in ("est_lnq", "a", "est_mirror_lnp") else v.reshape((n_rep, n_draws) + v.shape[1:])
         return res
 
     def rhs_batch(self, pars, t, y, want_lam=False):

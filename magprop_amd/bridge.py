@@ -1,7 +1,9 @@
 """Bridge-sampling evidence from the samples of an ordinary run (include/magprop_amd.h mp_bridge_logz; Meng & Wong 1996, Gronau et
 al. 2017): a Gaussian is fitted to one half of the posterior samples, drawn from and evaluated on the device, and a fixed point
 over the other half's lnprob and the draws' gives ln Z.  The samples carry their lnprob already, so the evidence costs n_draws
-model evaluations on top of the fit.
+model evaluations on top of the fit.  Where the Gaussian covers the posterior badly, proposal="t" draws from a Student-t
+with the same covariance (heavy tails) and warp=True symmetrises the posterior about the fitted mean (Warp-III: skew, a wall of
+the box), both through mp_bridge_logz_warp; without them the call and its bits are mp_bridge_logz's.
 
 ``bridge_evidence`` is the one path from rows to the result, on a *source* as magprop_amd.summaries takes it.
 EnsembleSampler.log_evidence(method="bridge") hands it the two halves of its chain or of its reservoir.  The equally weighted
@@ -21,12 +23,18 @@ class BridgeResult:
     mean over the repetitions; dlnz_reps: the standard deviation of lnz over the repetitions (0.0 for one); reps: the
     repetitions' rows as dicts keyed by _capi.BRIDGE_COLUMNS; niter, status, n_finite: per repetition; lnz_is: the plain
     importance-sampling estimate lambda_0 - ln_volume per repetition; neff, n_est, n_draws: what the call ran with.
+    proposal ("normal" or "t"), nu (None for the Gaussian), warp: the proposal the call ran with; est_mirrors: the estimator rows
+    whose mirror counted, draw_mirrors: per repetition the draws whose mirror did (0 without warp).
     Unpacks as (lnz, dlnz), the pair log_evidence returns for the other methods."""
 
-    def __init__(self, out, neff, n_est, n_draws):
+    def __init__(self, out, neff, n_est, n_draws, proposal="normal", nu=None, warp=False):
         self.out = np.asarray(out, dtype=np.float64)
-        col = {c: self.out[:, k] for k, c in enumerate(_capi.BRIDGE_COLUMNS)}
-        self.reps = [dict(zip(_capi.BRIDGE_COLUMNS, row)) for row in self.out]
+        names = _capi.BRIDGE_WARP_COLUMNS[:self.out.shape[1]]          # (mp_bridge_logz's rows end before the mirror counts)
+        col = {c: self.out[:, k] for k, c in enumerate(names)}
+        self.reps = [dict(zip(names, row)) for row in self.out]
+        self.proposal, self.nu, self.warp = proposal, (int(nu) if proposal == "t" else None), bool(warp)
+        self.est_mirrors = int(col["est_mirrors"][0]) if "est_mirrors" in col else 0
+        self.draw_mirrors = col["draw_mirrors"].astype(np.int64) if "draw_mirrors" in col else np.zeros(len(self.out), dtype=np.int64)
         self.lnz_reps = col["lnz"].copy()
         self.lnz = float(np.median(col["lnz"]))
         self.dlnz = float(np.mean(col["dlnz"]))
@@ -45,8 +53,10 @@ class BridgeResult:
         return iter((self.lnz, self.dlnz))
 
     def __repr__(self):
+        extra = (f", proposal=t({self.nu})" if self.proposal == "t" else "") + (
+            f", warp=True, est_mirrors={self.est_mirrors}, draw_mirrors={self.draw_mirrors.tolist()}" if self.warp else "")
         return (f"BridgeResult(lnz={self.lnz:.6g}, dlnz={self.dlnz:.3g}, status={[STATUS_NAMES.get(int(s), int(s)) for s in self.status]}, "
-                f"niter={self.niter.tolist()}, neff={self.neff:.6g})")
+                f"niter={self.niter.tolist()}, neff={self.neff:.6g}{extra})")
 
 
 def split(chain, lnp):
@@ -74,7 +84,7 @@ def neff_from_tau(n_est, tau, n_seen=None):
 
 
 def bridge_evidence(rows_fit, rows_est, lnp_est, source, lower=None, upper=None, n_draws=None, repetitions=1, seed=0, neff=None,
-                    max_iter=1000, tol=None, target=0, details=False):
+                    max_iter=1000, tol=None, target=0, details=False, proposal="normal", nu=5, warp=False):
     """ln Z by bridge sampling (Handle.bridge_logz) on the handle of `source` (magprop_amd.summaries: a function of the rows' width
     that yields (handle, dataset slot, times); summaries.on(handle, ds_id) for an open one).  rows_fit (n_fit, ndim) shape the
     Gaussian proposal, rows_est (n_est, ndim) with their lnprob lnp_est are the estimator's rows; rows of rows_est whose lnprob
@@ -83,7 +93,13 @@ def bridge_evidence(rows_fit, rows_est, lnp_est, source, lower=None, upper=None,
     (default n_est); repetitions: independent sets of draws; neff: the effective number of estimator rows (default n_est,
     independent rows); max_iter, tol: of the fixed point, which stops at a step of tol or less (default: 1e-10, or 8 ulp of
     the largest |lnprob| where that is more -- a step below the ulp of the result cannot be seen).  Returns a BridgeResult;
-    with details=True (result, the dict of Handle.bridge_logz)."""
+    with details=True (result, the dict of Handle.bridge_logz).
+    proposal="t": a multivariate Student-t with nu (3 .. 32) degrees of freedom and the fit rows' covariance in place of the
+    Gaussian: its tails dominate a heavy-tailed posterior's, so the ratios p / q stay bounded (reach for it where lnz_is lies far
+    from lnz).  warp=True: Warp-III, the posterior symmetrised about the fit rows' mean -- for a skewed posterior or one piled
+    against a wall of the box; it costs one more model evaluation per estimator row and per draw.  The two compose.  With the
+    defaults the call and its bits are mp_bridge_logz's."""
+    prop = _capi.bridge_proposal(proposal, nu, warp)
     xf = np.ascontiguousarray(rows_fit, dtype=np.float64)
     xe = np.ascontiguousarray(rows_est, dtype=np.float64)
     le = np.ascontiguousarray(lnp_est, dtype=np.float64)
@@ -100,8 +116,8 @@ def bridge_evidence(rows_fit, rows_est, lnp_est, source, lower=None, upper=None,
     neff = float(n_est) if neff is None else float(min(max(float(neff), np.finfo(float).tiny), float(n_est)))
     with source(xf.shape[1]) as (handle, ds_id, _):
         res = handle.bridge_logz(xf, xe, le, lower, upper, ds_id=ds_id, n_draws=n_draws, n_rep=int(repetitions), seed=seed, neff=neff,
-                                 max_iter=max_iter, tol=tol, target=target, details=details)
-    out = BridgeResult(res["out"], neff, n_est, n_draws)
+                                 max_iter=max_iter, tol=tol, target=target, details=details, proposal=proposal, nu=nu, warp=warp)
+    out = BridgeResult(res["out"], neff, n_est, n_draws, "t" if prop[0] == _capi.BRIDGE_STUDENT else "normal", nu, warp)
     return (out, res) if details else out
 
 

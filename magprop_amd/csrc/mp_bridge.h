@@ -1,6 +1,7 @@
-// mp_bridge.h — the bridge-sampling evidence estimate (include/magprop_amd.h mp_bridge_logz): what mp_bridge.cpp passes to the
-// kernels of mp_bridge.hip, and the host-only rules of the call (the Cholesky factor of the proposal and the constants formed
-// from it), which the kernels take as arguments.  The header states every operation; this file names where each one lives.
+// mp_bridge.h — the bridge-sampling evidence estimate (include/magprop_amd.h mp_bridge_logz, mp_bridge_logz_warp): what
+// mp_bridge.cpp passes to the kernels of mp_bridge.hip, and the host-only rules of the call (the Cholesky factor of the proposal,
+// the constants formed from it and those of the Student-t proposal), which the kernels take as arguments.  The header states
+// every operation; this file names where each one lives.
 #pragma once
 #include <cmath>
 
@@ -9,6 +10,7 @@
 namespace mp {
 
 constexpr uint32_t kBridgeCtr = 0x42524700u;                                   // fourth counter word of every normal draw
+constexpr uint32_t kBridgeCtrChi = 0x42524701u;                                // ... and of the normals behind a t draw's chi-square
 constexpr int kBridgeMaxMoments = MP_MAX_NDIM + MP_MAX_NDIM * (MP_MAX_NDIM + 1) / 2;   // sums of ndim 9: 9 + 45
 
 // the sums of one call over ndim coordinates: [ndim] of (x - pivot), then [ndim (ndim + 1) / 2] of their products, entry
@@ -65,6 +67,51 @@ inline int bridge_factor(const double *mom, const double *pivot, int64_t n, int 
     return -1;
 }
 
+// The Student-t proposal of mp_bridge_logz_warp as the kernels take it beside a BridgeGauss that holds L_t and c_t.
+struct BridgeStudent {
+    double h, nu;                                    // 0.5 (nu + ndim), nu as a double
+    int32_t n_nu, on;                                // nu; 0: the proposal is the Gaussian, nothing else here is read
+};
+
+// Host: the constants of the t proposal with nu degrees of freedom and the covariance L L^T of g: k = sqrt((nu - 2) / nu),
+// L_t,ab = k L_ab, c_t = ((sum_a ln L_t,aa, in order from 0.0) + (0.5 ndim) ln(nu 3.141592653589793)) + lgamma(nu / 2) -
+// lgamma((nu + ndim) / 2), h = 0.5 (nu + ndim); the host's sqrt, log and lgamma.  gt: g with L_t for L and c_t for c.
+inline void bridge_student(const BridgeGauss &g, int nu, BridgeGauss &gt, BridgeStudent &t) {
+#pragma clang fp contract(off)
+    const double dn = (double)nu, dd = (double)g.ndim;
+    const double k = std::sqrt((dn - 2.0) / dn);
+    gt = g;
+    double sum_ln = 0.0;
+    for (int a = 0; a < g.ndim; ++a) {
+        for (int b = 0; b <= a; ++b) gt.L[a * (a + 1) / 2 + b] = k * g.L[a * (a + 1) / 2 + b];
+        sum_ln = sum_ln + std::log(gt.L[a * (a + 1) / 2 + a]);
+    }
+    const double half_d = 0.5 * dd;
+    const double ln_nu_pi = std::log(dn * 3.141592653589793);
+    const double with_pi = sum_ln + half_d * ln_nu_pi;
+    const double with_lg = with_pi + std::lgamma(dn / 2.0);
+    gt.c = with_lg - std::lgamma((dn + dd) / 2.0);
+    t.h = 0.5 * (dn + dd);
+    t.nu = dn;
+    t.n_nu = nu;
+    t.on = 1;
+}
+
+// What the pair kernel takes: the rows and (warp) their mirrors, and what it reads and writes about them.
+struct BridgePairArgs {
+    const double *x;         // [n][ndim] the rows
+    const double *xm;        // [n][ndim] their mirrors; NULL: no warp, ab = lnp - lnq where the row counts
+    double *lnp;             // [n] read where `given`, else written (the test targets 1 .. 4)
+    double *lnp_m;           // [n] (warp) the mirrors' lnprob: read for target 0, else written
+    const double *lnq;       // [n]
+    double *ab;              // [n] the log-ratio
+    uint8_t *counted_m;      // [n] (warp) 1 where the mirror counts, else 0
+    int64_t n;
+    int32_t target, ndim;
+    int32_t given;           // 1: lnp holds the rows' lnprob (target 0, and the estimator rows of every target)
+    int32_t test_row;        // 1: a row outside the box or with a non-finite lnprob does not count (the draws)
+};
+
 // What the fixed-point kernel takes beside its arrays; the logs are the host's.
 struct BridgeFixedArgs {
     const double *a;         // [n1] a_i = lnp_est_i - lnq_i, all finite; shared by the repetitions
@@ -93,5 +140,15 @@ int launch_bridge_est(const BridgeGauss &g, const double *x, const double *lnp, 
 int launch_bridge_b(const BridgeBox &box, int target, int ndim, const double *x, double *lnp, const double *lnq, int64_t n, double *b,
                     void *stream);
 int launch_bridge_fixed(const BridgeFixedArgs &f, void *stream);
+// mp_bridge_logz_warp's.  One thread per draw: x, lnq and (xm not NULL) the mirror rows xm[r * n_draws + j][ndim], from the Gaussian
+// g (t.on = 0) or the t proposal (g holds L_t and c_t)
+int launch_bridge_draws_warp(const BridgeGauss &g, const BridgeStudent &t, uint64_t seed, int64_t n_draws, int n_rep, double *x, double *xm,
+                             double *lnq, void *stream);
+// one thread per estimator row: lnq[i] of x[i] under either proposal and (xm not NULL) the mirror row xm[i][ndim]
+int launch_bridge_est_warp(const BridgeGauss &g, const BridgeStudent &t, const double *x, int64_t n, double *lnq, double *xm, void *stream);
+// one thread per row: the test targets' lnp of the row and of its mirror, the box, and ab (a of estimator rows, b of draws)
+int launch_bridge_pair(const BridgeBox &box, const BridgePairArgs &p, void *stream);
+// one workgroup per repetition r: out[r] = the non-zero flags among flag[r * n .. r * n + n), as a double
+int launch_bridge_count(const uint8_t *flag, int64_t n, int n_rep, double *out, void *stream);
 
 }  // namespace mp

@@ -9,6 +9,11 @@
 // bridge_b_kernel: one thread per draw: the test targets' lnp, the box, and b = lnp - lnq or -inf.
 // bridge_fixed_kernel: one workgroup of 256 threads per repetition: the fixed point over a and b, which it only reads (they are
 // formed once, by the two kernels above), and the moments of f1 and f2 behind it.
+// mp_bridge_logz_warp's: bridge_draws_warp_kernel: one thread per draw from the Gaussian or the Student-t proposal (the chi-square
+// loop over Philox pairs has a uniform trip count), with the mirror row beside it; bridge_est_warp_kernel: one thread per
+// estimator row: lnq under either proposal and the mirror row; bridge_pair_kernel: one thread per row: the test targets' lnp of
+// the row and of its mirror, the box on both, and a or b; bridge_count_kernel: one workgroup per repetition counts the mirrors
+// that counted.  mp_bridge_logz keeps the three kernels above; the fixed-point kernel serves both entries as it is.
 // Every read of a row-major array by consecutive threads is of consecutive elements (a, b, lnp, lnq) or of consecutive rows of
 // ndim doubles; every per-thread array is indexed by unrolled constants, so nothing goes to scratch memory.
 #include <hip/hip_runtime.h>
@@ -139,6 +144,40 @@ __global__ __launch_bounds__(kWgThreads) void bridge_est_kernel(const BridgeGaus
     if (lnp) a_out[i] = sub_rn(lnp[i], q);
 }
 
+// The test targets of mp_bridge_logz_warp at a point.  1 and 2: point_eval's arithmetic, as bridge_b_kernel below forms it (that
+// kernel, mp_bridge_logz's, stays as compiled); 3 (the split normal) and 4 (the product of t_3 densities) live here alone.
+MP_DEV double bridge_test_lnp(int target, const double (&par)[MP_MAX_NDIM], int ndim) {
+    double v = 0.0;
+    if (target == 3) {
+#pragma unroll
+        for (int d = 0; d < MP_MAX_NDIM; ++d) {
+            const double u = par[d] < 0.0 ? par[d] : mul_rn(0.25, par[d]);
+            v = d < ndim ? sub_rn(v, mul_rn(mul_rn(0.5, u), u)) : v;
+        }
+        return v;
+    }
+    if (target == 4) {
+#pragma unroll
+        for (int d = 0; d < MP_MAX_NDIM; ++d)
+            v = d < ndim ? sub_rn(v, mul_rn(2.0, log(add_rn(1.0, mul_rn(par[d], par[d]) / 3.0)))) : v;
+        return v;
+    }
+#pragma unroll
+    for (int d = 0; d < MP_MAX_NDIM; ++d) v = d < ndim ? sub_rn(v, mul_rn(mul_rn(0.5, par[d]), par[d])) : v;
+    if (target == 2) v = sub_rn(v, mul_rn(1.0e-3, floor(mul_rn(37.0, par[0]))));
+    return v;
+}
+
+MP_DEV bool bridge_inside(const BridgeBox &box, const double (&par)[MP_MAX_NDIM], int ndim) {
+    bool inside = true;
+    if (box.on) {
+#pragma unroll
+        for (int d = 0; d < MP_MAX_NDIM; ++d)
+            if (d < ndim) inside = inside && par[d] >= box.lower[d] && par[d] <= box.upper[d];
+    }
+    return inside;
+}
+
 __global__ __launch_bounds__(kWgThreads) void bridge_b_kernel(const BridgeBox box, int target, int ndim, const double *x, double *lnp,
                                                               const double *lnq, int64_t n, double *b) {
     const int64_t i = (int64_t)blockIdx.x * kWgThreads + threadIdx.x;
@@ -263,6 +302,141 @@ __global__ __launch_bounds__(kWgThreads) void bridge_fixed_kernel(const BridgeFi
     }
 }
 
+// ---------------------------------------------------------------- mp_bridge_logz_warp: both proposals, mirror rows, pairs
+// the t density of the scaled residuals xi: lnq = -h log(1 + Q / nu) - c_t, Q = sum xi^2 added in order from dimension 0
+MP_DEV double bridge_lnq_t(const double (&xi)[MP_MAX_NDIM + 1], int ndim, const BridgeStudent &t, double c) {
+    double q = 0.0;
+#pragma unroll
+    for (int a = 0; a < MP_MAX_NDIM; ++a) q = a < ndim ? add_rn(q, mul_rn(xi[a], xi[a])) : q;
+    return sub_rn(mul_rn(-t.h, log(add_rn(1.0, q / t.nu))), c);
+}
+
+__global__ __launch_bounds__(kWgThreads) void bridge_draws_warp_kernel(const BridgeGauss g, const BridgeStudent t, uint64_t seed,
+                                                                       int64_t n_draws, int n_rep, double *x, double *xm, double *lnq) {
+    const int64_t i = (int64_t)blockIdx.x * kWgThreads + threadIdx.x;
+    if (i >= n_draws * n_rep) return;
+    const int nd = g.ndim;
+    const uint32_t r = (uint32_t)(i / n_draws), j = (uint32_t)(i % n_draws);
+    double z[MP_MAX_NDIM + 1];
+#pragma unroll
+    for (int p = 0; p < (MP_MAX_NDIM + 1) / 2; ++p) {
+        z[2 * p] = z[2 * p + 1] = 0.0;
+        if (2 * p < nd) {
+            uint32_t s4[4];
+            philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), j, r, (uint32_t)p, kBridgeCtr, s4);
+            normal_pair(s4, z[2 * p], z[2 * p + 1]);
+        }
+    }
+    double scale = 1.0;
+    if (t.on) {                                                      // (uniform: launch arguments, the trip count too)
+        double w = 0.0;
+        const int pairs = (t.n_nu + 1) / 2;
+        for (int p = 0; p < pairs; ++p) {
+            uint32_t s4[4];
+            double g0, g1;
+            philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), j, r, (uint32_t)p, kBridgeCtrChi, s4);
+            normal_pair(s4, g0, g1);
+            w = add_rn(w, mul_rn(g0, g0));
+            if (2 * p + 1 < t.n_nu) w = add_rn(w, mul_rn(g1, g1));   // an odd nu leaves the last pair's second normal
+        }
+        scale = sqrt(t.nu / w);
+    }
+    double *row = x + i * nd;
+    double *rowm = xm ? xm + i * nd : nullptr;
+#pragma unroll
+    for (int a = 0; a < MP_MAX_NDIM; ++a) {
+        if (a < nd) {
+            double s = 0.0;
+#pragma unroll
+            for (int b = 0; b <= a; ++b) s = add_rn(s, mul_rn(g.L[a * (a + 1) / 2 + b], z[b]));
+            const double d = t.on ? mul_rn(scale, s) : s;
+            row[a] = add_rn(g.m[a], d);
+            if (rowm) rowm[a] = sub_rn(g.m[a], d);
+        }
+    }
+    if (t.on) {
+#pragma unroll
+        for (int a = 0; a < MP_MAX_NDIM + 1; ++a) z[a] = mul_rn(scale, z[a]);
+        lnq[i] = bridge_lnq_t(z, nd, t, g.c);
+    } else {
+        lnq[i] = bridge_lnq(z, nd, g.c);
+    }
+}
+
+__global__ __launch_bounds__(kWgThreads) void bridge_est_warp_kernel(const BridgeGauss g, const BridgeStudent t, const double *x,
+                                                                     int64_t n, double *lnq, double *xm) {
+    const int64_t i = (int64_t)blockIdx.x * kWgThreads + threadIdx.x;
+    if (i >= n) return;
+    const int nd = g.ndim;
+    const double *row = x + i * nd;
+    double *rowm = xm ? xm + i * nd : nullptr;
+    double z[MP_MAX_NDIM + 1];
+#pragma unroll
+    for (int a = 0; a < MP_MAX_NDIM + 1; ++a) z[a] = 0.0;
+#pragma unroll
+    for (int a = 0; a < MP_MAX_NDIM; ++a) {
+        if (a < nd) {
+            const double d = sub_rn(row[a], g.m[a]);
+            if (rowm) rowm[a] = sub_rn(g.m[a], d);
+            double s = d;
+#pragma unroll
+            for (int b = 0; b < a; ++b) s = sub_rn(s, mul_rn(g.L[a * (a + 1) / 2 + b], z[b]));
+            z[a] = s / g.L[a * (a + 1) / 2 + a];
+        }
+    }
+    lnq[i] = t.on ? bridge_lnq_t(z, nd, t, g.c) : bridge_lnq(z, nd, g.c);
+}
+
+__global__ __launch_bounds__(kWgThreads) void bridge_pair_kernel(const BridgeBox box, const BridgePairArgs p) {
+    const int64_t i = (int64_t)blockIdx.x * kWgThreads + threadIdx.x;
+    if (i >= p.n) return;
+    const int nd = p.ndim;
+    const double *row = p.x + i * nd;
+    double par[MP_MAX_NDIM];
+#pragma unroll
+    for (int d = 0; d < MP_MAX_NDIM; ++d) par[d] = d < nd ? row[d] : 0.0;
+    double v;
+    if (p.given) {
+        v = p.lnp[i];
+    } else {
+        v = bridge_test_lnp(p.target, par, nd);
+        p.lnp[i] = v;
+    }
+    const bool ok = isfinite(v) && (!p.test_row || bridge_inside(box, par, nd));
+    const double q = p.lnq[i];
+    if (!p.xm) {                                                     // (uniform)
+        p.ab[i] = ok ? sub_rn(v, q) : -INFINITY;
+        return;
+    }
+    const double *rowm = p.xm + i * nd;
+#pragma unroll
+    for (int d = 0; d < MP_MAX_NDIM; ++d) par[d] = d < nd ? rowm[d] : 0.0;
+    double vm;
+    if (p.target == 0) {
+        vm = p.lnp_m[i];
+    } else {
+        vm = bridge_test_lnp(p.target, par, nd);
+        p.lnp_m[i] = vm;
+    }
+    const bool okm = isfinite(vm) && bridge_inside(box, par, nd);
+    p.counted_m[i] = okm ? 1 : 0;
+    // the symmetrised density in logs; a point that does not count contributes nothing, and lse2 is formed of two finite values only
+    double both = -INFINITY;
+    if (ok && okm) both = lse2(v, vm);
+    else if (ok) both = v;
+    else if (okm) both = vm;
+    p.ab[i] = ok || okm ? sub_rn(sub_rn(both, 0.6931471805599453), q) : -INFINITY;
+}
+
+__global__ __launch_bounds__(kWgThreads) void bridge_count_kernel(const uint8_t *flag, int64_t n, double *out) {
+    __shared__ uint32_t shc[kWgWaves];
+    const uint8_t *f = flag + (int64_t)blockIdx.x * n;
+    uint32_t cnt = 0;
+    for (int64_t j = threadIdx.x; j < n; j += kWgThreads) cnt += f[j] ? 1u : 0u;
+    const uint32_t total = wg_count(cnt, shc);
+    if (threadIdx.x == 0) out[blockIdx.x] = (double)total;
+}
+
 unsigned grid_of(int64_t n) { return (unsigned)((n + kWgThreads - 1) / kWgThreads); }
 
 }  // namespace
@@ -300,6 +474,28 @@ int launch_bridge_b(const BridgeBox &box, int target, int ndim, const double *x,
 
 int launch_bridge_fixed(const BridgeFixedArgs &f, void *stream) {
     hipLaunchKernelGGL(bridge_fixed_kernel, dim3((unsigned)f.n_rep), dim3(kWgThreads), 0, (hipStream_t)stream, f);
+    return (int)hipGetLastError();
+}
+
+int launch_bridge_draws_warp(const BridgeGauss &g, const BridgeStudent &t, uint64_t seed, int64_t n_draws, int n_rep, double *x, double *xm,
+                             double *lnq, void *stream) {
+    hipLaunchKernelGGL(bridge_draws_warp_kernel, dim3(grid_of(n_draws * n_rep)), dim3(kWgThreads), 0, (hipStream_t)stream, g, t, seed,
+                       n_draws, n_rep, x, xm, lnq);
+    return (int)hipGetLastError();
+}
+
+int launch_bridge_est_warp(const BridgeGauss &g, const BridgeStudent &t, const double *x, int64_t n, double *lnq, double *xm, void *stream) {
+    hipLaunchKernelGGL(bridge_est_warp_kernel, dim3(grid_of(n)), dim3(kWgThreads), 0, (hipStream_t)stream, g, t, x, n, lnq, xm);
+    return (int)hipGetLastError();
+}
+
+int launch_bridge_pair(const BridgeBox &box, const BridgePairArgs &p, void *stream) {
+    hipLaunchKernelGGL(bridge_pair_kernel, dim3(grid_of(p.n)), dim3(kWgThreads), 0, (hipStream_t)stream, box, p);
+    return (int)hipGetLastError();
+}
+
+int launch_bridge_count(const uint8_t *flag, int64_t n, int n_rep, double *out, void *stream) {
+    hipLaunchKernelGGL(bridge_count_kernel, dim3((unsigned)n_rep), dim3(kWgThreads), 0, (hipStream_t)stream, flag, n, out);
     return (int)hipGetLastError();
 }
 

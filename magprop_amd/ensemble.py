@@ -341,7 +341,8 @@ class EnsembleSampler:
         return out
 
     def log_evidence(self, discard=0, group=0, prior_draws=2 ** 20, device=False, method="ti", thin=1, ensemble=None, temp=None,
-                     n_draws=None, repetitions=1, seed=None, neff=None, source="chain", max_iter=1000, tol=None):
+                     n_draws=None, repetitions=1, seed=None, neff=None, source="chain", max_iter=1000, tol=None,
+                     proposal="normal", nu=5, warp=False):
         """method="ti" (the default; thin and the arguments behind it are not read): (lnZ, dlnZ) of group `group`'s dataset, the prior normalised over its box, from the stored chain of a tempered run:
         thermodynamic integration of the per-temperature mean lnL over steps[discard:] (magprop_amd.tempering) plus
         ln f_valid, the fraction of `prior_draws` uniform box draws (numpy generator seeded by the sampler seed, evaluated on
@@ -362,10 +363,13 @@ class EnsembleSampler:
         clamped to (0, N1]; without a tau neff = N1, and a RuntimeWarning says so.  source="reservoir": the rows of
         get_samples(ensemble) split at their median step instead (monitor_samples; discard and thin stay at their defaults), so
         that run_mcmc_until(..., store=False) ends with an evidence.  repetitions > 1: lnz is the median over the repetitions'
-        draws, dlnz their mean, dlnz_reps the spread of lnz over them.  max_iter, tol: of the fixed point."""
+        draws, dlnz their mean, dlnz_reps the spread of lnz over them.  max_iter, tol: of the fixed point.  proposal="t" with nu
+        degrees of freedom (heavy tails: lnz_is far from lnz) and warp=True (Warp-III: a skewed posterior, or one against a wall
+        of the box; one more evaluation per estimator row and per draw) are bridge.bridge_evidence's (mp_bridge_logz_warp);
+        without them the call and its bits are mp_bridge_logz's."""
         if method == "bridge":
             return self._bridge_evidence(discard, thin, group if ensemble is None else ensemble, temp, n_draws, repetitions, seed, neff,
-                                         source, max_iter, tol)
+                                         source, max_iter, tol, proposal, nu, warp)
         if method != "ti":
             raise ValueError(f"method must be 'ti' or 'bridge', got {method!r}")
         if self.betas is None:
@@ -407,8 +411,9 @@ class EnsembleSampler:
         lnf, dlnf = tempering.validity_term(n_finite, n_draws)
         return ti + lnf, float(np.hypot(dti, dlnf))
 
-    def _bridge_evidence(self, discard, thin, ensemble, temp, n_draws, repetitions, seed, neff, source, max_iter, tol):
+    def _bridge_evidence(self, discard, thin, ensemble, temp, n_draws, repetitions, seed, neff, source, max_iter, tol, proposal, nu, warp):
         """log_evidence(method="bridge")"""
+        _capi.bridge_proposal(proposal, nu, warp)
         e = self._ensemble_index(ensemble, temp, grouped=self.betas is not None)
         grp = e // self.ntemps
         tau, n_seen, why = None, None, "the estimator half is too short"
@@ -449,7 +454,8 @@ class EnsembleSampler:
         seed = (self.seed ^ 0x4272696467655F7A) & 0xFFFFFFFFFFFFFFFF if seed is None else int(seed)
         lo, hi = (None, None) if self._target != 0 else self._prior
         return bridge.bridge_evidence(fit, est, lnp, summaries.on(self.handle, grp), lo, hi, n_draws=n_draws, repetitions=repetitions,
-                                      seed=seed, neff=neff, max_iter=max_iter, tol=tol, target=self._target)
+                                      seed=seed, neff=neff, max_iter=max_iter, tol=tol, target=self._target, proposal=proposal, nu=nu,
+                                      warp=warp)
 
     @property
     def chain(self):
