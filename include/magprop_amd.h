@@ -389,6 +389,80 @@ int mp_model_pointwise(mp_handle *h, const double *pars, int64_t n, int ndim, in
                        double *tail_out, double *z_out, int32_t *status_out, int64_t *n_used);
 
 /*
+ * Importance reweighting of a fit to other error models and data subsets, computed on the device (ABI 5, additive): per sample
+ * the log weight that carries a chain sampled under lnlike = -0.5 chi^2 (the light curve's own yerr, every observation counted
+ * once) to each of n_alt alternative likelihoods, and per alternative the reductions from which the Bayes factor between the
+ * error models, Kish's effective sample size and the Pareto-k diagnostic follow on the host (magprop_amd/reweight.py).  The
+ * weights are what mp_model_band_weighted and the weights= arguments of the summaries take.  pars, n, ndim, physical,
+ * status_out and n_used are mp_model_pointwise's; the dataset has to be set (MP_ESTATE otherwise).
+ *   kind[n_alt]                       MP_REWEIGHT_GAUSS or MP_REWEIGHT_STUDENT
+ *   alt[n_alt][3]                     scale (finite, > 0), jitter (finite, >= 0), nu (Student-t: finite, > 0; Gaussian: ignored)
+ *   obs_w[n_alt][n_obs]               (optional) a weight per alternative and observation, finite and >= 0, in the order
+ *                                     mp_set_dataset keeps the observations: ascending time (stable).  NULL: every weight 1
+ *   lw_out[n_alt][n]                  (optional) the log weights, alternative-major
+ *   alt_out[n_alt][MP_REWEIGHT_N]     the columns below
+ *   tail_out[n_alt][mp_pointwise_tail_len(n)]   (optional) the min(T, N_USED) largest lw of the alternative, ascending, then NaN
+ * Limits: 1 <= n <= MP_POINTWISE_MAX_SAMPLES (the tail row relies on it), 1 <= n_alt <= MP_REWEIGHT_MAX_ALT; there is no cell
+ * matrix, so n * n_obs has no cap.  The rows go through the device in chunks of mp_n_simd(h) rows, each one launch of the curve
+ * kernels (Ltot only) and one launch that turns the chunk's curves into log weights; two reduction launches per call follow.
+ * The alternatives and obs_w are uploaded once per call.  Workspace, owned by the handle, grow-only, freed by mp_destroy:
+ * n_alt * (n + n_obs + T(n) + MP_REWEIGHT_N + 3) + min(n, mp_n_simd) * n_grid doubles.  A multi-device handle runs the call on
+ * its first device and cfg.dipole_torque = 1 is served.
+ *
+ * Term of sample s (status MP_STATUS_OK), observation j and alternative k, with mod mp_model_pointwise's and every operation
+ * rounded on its own (no FMA contraction), log and log1p the device runtime's:
+ *   res = y_j - mod,   se = scale_k * yerr_j,   a = se * se,   jm = jitter_k * mod,   b = jm * jm,   var = a + b
+ *   q = (res * res) / var,   g = 0.5 * log(var)
+ *   MP_REWEIGHT_GAUSS:     t_k = -(0.5 * q + g)
+ *   MP_REWEIGHT_STUDENT:   u = q / nu_k,   p = (0.5 * (nu_k + 1)) * log1p(u),   t_k = -(p + g)
+ * The base term t_0 is the Gaussian one with scale 1 and jitter 0, formed by the same arithmetic (var = yerr_j * yerr_j).  The
+ * difference is d = t_k - t_0 without obs_w, d = w_kj * t_k - t_0 for w_kj != 0 and d = -t_0 for w_kj == 0 (whatever t_k is,
+ * NaN or infinite included).  The constants of the densities (-0.5 ln 2 pi per Gaussian point, the Student-t's ratio of gamma functions) are left
+ * to the host: magprop_amd.reweight.shape_constant.
+ *
+ * Row sum: one wavefront owns a sample; lane l adds d of observations l, l + 64, ... in increasing order from 0.0, and the 64
+ * partial sums are combined by the xor butterfly (distances 32 .. 1).  lw[k][s] is that sum: a sum of differences, so that an
+ * alternative equal to the base gives exactly +0.0, leaving one observation out gives exactly -t_0 of that observation and no
+ * cancellation error grows with n_obs.  A sample whose status is not OK has NaN in every alternative (its curve is not read).
+ * A row's numbers are a function of the row, the dataset and the alternative, NOT of the chunking, of n or of the row's place.
+ *
+ * Columns, per alternative over the used samples (the non-NaN lw, N_USED of them; -inf is a used value), T =
+ * mp_pointwise_tail_len(N_USED); values order as their sign-magnitude keys do: -0.0 below +0.0:
+ *   N_USED                   their number
+ *   LW_MEAN                  sum / N_USED (NaN for N_USED = 0)
+ *   LW_MIN, LW_MAX           least and largest lw (NaN for N_USED = 0)
+ *   LSE1_M, LSE1_S           running log-sum-exp pair of lw: sum exp(lw) = e^M S ((-inf, 0): none)
+ *   LSE2_M, LSE2_S           the pair of 2 * lw
+ *   CUT                      the min(T, N_USED)-th largest lw: the first entry of the tail row (NaN for N_USED = 0)
+ *   NONTAIL_COUNT            samples with lw <= CUT
+ *   NONTAIL_M, NONTAIL_S     log-sum-exp pair of lw over exactly those samples
+ * in the order of mp_model_pointwise's sums (thread k of 256 takes samples k, k + 256, ...; butterfly; wavefront order).
+ *
+ * Returns MP_EINVAL for n, ndim, ds_id or n_alt out of range; for a NULL h, pars, kind, alt or alt_out; for a bad alternative
+ * (all of this is judged without a handle), in this order; then MP_ESTATE for an unset dataset; then MP_EINVAL for a bad obs_w
+ * value.  (tests/reweight_restated.py is this definition in numpy.)
+ */
+#define MP_REWEIGHT_MAX_ALT 64
+#define MP_REWEIGHT_GAUSS 0
+#define MP_REWEIGHT_STUDENT 1
+#define MP_REWEIGHT_N 12
+#define MP_REWEIGHT_N_USED 0
+#define MP_REWEIGHT_LW_MEAN 1
+#define MP_REWEIGHT_LW_MIN 2
+#define MP_REWEIGHT_LW_MAX 3
+#define MP_REWEIGHT_LSE1_M 4
+#define MP_REWEIGHT_LSE1_S 5
+#define MP_REWEIGHT_LSE2_M 6
+#define MP_REWEIGHT_LSE2_S 7
+#define MP_REWEIGHT_CUT 8
+#define MP_REWEIGHT_NONTAIL_COUNT 9
+#define MP_REWEIGHT_NONTAIL_M 10
+#define MP_REWEIGHT_NONTAIL_S 11
+int mp_model_reweight(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, int ds_id, int n_alt,
+                      const int32_t *kind, const double *alt, const double *obs_w, double *lw_out, double *alt_out,
+                      double *tail_out, int32_t *status_out, int64_t *n_used);
+
+/*
  * Simulated light curves of n parameter rows, computed on the device (ABI 5, additive): the model of every row at observed
  * times, an error per observation and Gaussian noise -- the synthetic datasets of the reference's
  * code/synthetic_datasets/generate_data.py:61-67 (the model at grid points, yerr = 0.25 y, normal noise), for any times inside

@@ -23,6 +23,7 @@ BAND_LTOT, BAND_LPROP, BAND_LDIP = 1, 2, 4
 BAND_COMPONENTS = {"Ltot": BAND_LTOT, "Lprop": BAND_LPROP, "Ldip": BAND_LDIP}
 DERIVED_N = 16                                                # include/magprop_amd.h MP_DERIVED_N (columns: magprop_amd/derived.py)
 POINTWISE_N, POINTWISE_MAX_SAMPLES, POINTWISE_MAX_CELLS = 12, 262144, 1 << 28   # include/magprop_amd.h MP_POINTWISE_* (columns: magprop_amd/pointwise.py)
+REWEIGHT_N, REWEIGHT_MAX_ALT = 12, 64                         # include/magprop_amd.h MP_REWEIGHT_* (columns: magprop_amd/reweight.py)
 SIM_MAX_ROWS, SIM_MAX_CELLS = 262144, 1 << 28                 # include/magprop_amd.h MP_SIM_*
 FLOW_N, FLOW_NCURVES = 16, 10                                 # include/magprop_amd.h MP_FLOW_* (columns and curves: magprop_amd/flows.py)
 # cell curves of mp_model_flows in the order of their mask bits MP_FLOW_CURVE_*
@@ -95,6 +96,7 @@ SIGNATURES = {
     "mp_model_derived": (_i, [_vp, _dp, _i64, _i, _i, _dp, _ip, _i64p]),
     "mp_pointwise_tail_len": (_i, [_i64]),
     "mp_model_pointwise": (_i, [_vp, _dp, _i64, _i, _i, _i, _dp, _dp, _dp, _ip, _i64p]),
+    "mp_model_reweight": (_i, [_vp, _dp, _i64, _i, _i, _i, _i, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _i64p]),
     "mp_simulate": (_i, [_vp, _dp, _i64, _i, _i, _dp, _i, _i64, _dp, _d, _u64, _dp, _dp, _dp, _dp, _ip, _i64p]),
     "mp_model_flows": (_i, [_vp, _dp, _i64, _i, _i, _dp, _u32, _dp, _ip, _i64p]),
     "mp_model_flow_band": (_i, [_vp, _dp, _i, _i, _i, _dp, _dp, _i, _u32, _dp, _ip, _ip]),
@@ -644,6 +646,36 @@ class Handle(_Owner):
                                          _dptr(z) if cells else None, _iptr(st), C.byref(used)), "mp_model_pointwise")
         res = (obs, tail[:, :tlen], st, int(used.value))
         return res + (z,) if cells else res
+
+    def model_reweight(self, pars, kind, alt, obs_w=None, ds_id=0, physical=False):
+        """Log importance weights of the rows of pars against dataset ds_id under the alternatives kind[n_alt], alt[n_alt, 3]
+        (scale, jitter, nu) and the observation weights obs_w[n_alt, n_obs] (None: 1 each; observations in ascending time, as
+        the library keeps them) (mp_model_reweight; the columns are magprop_amd.reweight.NAMES): returns (lw[n_alt, n],
+        table[n_alt, REWEIGHT_N], tail[n_alt, T(n)], status[n], n_used), the rows that did not finish NaN in lw.
+        physical=False: sampler coordinates under the handle's prior, as lnprob_batch takes them."""
+        p = np.ascontiguousarray(pars, dtype=np.float64)
+        if p.ndim != 2 or p.shape[0] < 1:
+            raise ValueError(f"pars must be 2-D (n >= 1, ndim), got shape {p.shape}")
+        n, nd = p.shape
+        kd = np.ascontiguousarray(kind, dtype=np.int32)
+        al = np.ascontiguousarray(alt, dtype=np.float64)
+        if kd.ndim != 1 or kd.size < 1 or al.shape != (kd.size, 3):
+            raise ValueError(f"kind (n_alt,) and alt (n_alt, 3) expected, got {kd.shape} and {al.shape}")
+        n_alt = int(kd.size)
+        n_obs = self.dataset_size(ds_id)                     # (0: never set here; the library refuses the call then)
+        ow = None if obs_w is None else np.ascontiguousarray(obs_w, dtype=np.float64)
+        if ow is not None and ow.shape != (n_alt, n_obs):
+            raise ValueError(f"obs_w must be of shape ({n_alt}, {n_obs}), one weight per alternative and observation, got {ow.shape}")
+        tlen = int(self._L.mp_pointwise_tail_len(n))
+        lw = np.empty((n_alt, n), dtype=np.float64)
+        table = np.empty((n_alt, REWEIGHT_N), dtype=np.float64)
+        tail = np.empty((n_alt, max(tlen, 1)), dtype=np.float64)
+        st = np.empty(n, dtype=np.int32)
+        used = C.c_int64(0)
+        check(self._L.mp_model_reweight(self._h, _dptr(p), n, nd, int(bool(physical)), int(ds_id), n_alt, _iptr(kd), _dptr(al),
+                                        None if ow is None else _dptr(ow), _dptr(lw), _dptr(table), _dptr(tail), _iptr(st),
+                                        C.byref(used)), "mp_model_reweight")
+        return lw, table, tail[:, :tlen], st, int(used.value)
 
     def simulate(self, pars, x, yerr=None, frac_err=0.25, seed=0, physical=False):
         """Simulated light curves of the rows of pars (mp_simulate): the model at the times x, an error per observation and

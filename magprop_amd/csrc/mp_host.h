@@ -172,6 +172,9 @@ struct Evaluator {
     DevBuf<double> w_flow_cells, w_flow_out;      // mp_model_flows: [MP_FLOW_NCURVES][chunk][n_grid] cell curves; [chunk][MP_FLOW_N]
     DevBuf<double> w_flow_band;                   // mp_model_flow_band: [selected curves][n][n_grid]; kept between calls for one curve only
     DevBuf<double> w_pw_z, w_pw_obs, w_pw_tail;   // mp_model_pointwise: [n_obs][n] cells; [n_obs][MP_POINTWISE_N]; [n_obs][T(n)]
+    DevBuf<double> w_rw_lw, w_rw_out, w_rw_tail;  // mp_model_reweight: [n_alt][n] log weights; [n_alt][MP_REWEIGHT_N]; [n_alt][T(n)]
+    DevBuf<double> w_rw_alt;                      // mp_model_reweight: [n_alt][3] the alternatives, then [n_alt][n_obs] the observation weights
+    DevBuf<int32_t> w_rw_kind;                    // mp_model_reweight: [n_alt]
     DevBuf<double> w_sim;                         // mp_simulate: [dx | idt | yerr][table rows][n_obs], then [y | yerr | model | z][chunk][n_obs]
     DevBuf<int32_t> w_sim_g;                      // mp_simulate: [table rows][n_obs] the brackets' g, then [n] the rows' zero-error marks
     DevBuf<int32_t> w_dsid, w_status, w_sweeps;

@@ -7,13 +7,14 @@
 // pointwise_select_kernel takes one observation per workgroup: the min(T, N_USED)-th largest r = z^2 / 2 by an MSB-first radix
 // select over 8-bit digits of band_key(r) (mp_band.h; the column is streamed from memory once per digit: it does not fit LDS at
 // 262 144 samples), then the larger values are compacted into LDS, filled up with copies of the cut and sorted (bitonic, at most
-// 2 048 slots).  pointwise_reduce_kernel takes one observation per workgroup as well: counts, means, the two-pass variance,
+// 2 048 slots): wg_tail_select of mp_tail.h, which mp_reweight.hip shares.  pointwise_reduce_kernel takes one observation per workgroup as well: counts, means, the two-pass variance,
 // extrema and the log-sum-exp pairs (lse_add, wave_lse, lse_merge of mp_math.hpp), with the select kernel's cut.
 #include <hip/hip_runtime.h>
 
 #include "mp_band.h"
 #include "mp_math.hpp"
 #include "mp_pointwise.h"
+#include "mp_tail.h"
 #include "mp_wg.h"
 
 namespace mp {
@@ -70,61 +71,15 @@ __global__ __launch_bounds__(kPointwiseThreads) void pointwise_cells_kernel(cons
 __global__ __launch_bounds__(kPointwiseThreads) void pointwise_select_kernel(const PointwiseColsArgs a) {
     __shared__ WgSelectLds sel;
     __shared__ uint64_t keys[kPointwiseSortCap];
-    const int j = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int n = (int)a.n;
+    const int j = blockIdx.x;
     const double *col = a.z + (size_t)j * (size_t)a.n;
-    double *out = a.obs + (size_t)j * MP_POINTWISE_N;
-    double *tail = a.tail ? a.tail + (size_t)j * (size_t)a.tail_stride : nullptr;
-    uint32_t c = 0;
-    for (int i = tid; i < n; i += kPointwiseThreads) c += !__builtin_isnan(col[i]);
-    const int m = (int)wg_count(c, sel.wave);
-    const int tm = min(min(pointwise_tail_len(m), m), kPointwiseMaxTail);   // entries of the tail row (uniform over the workgroup)
-    if (m == 0) {
-        if (tid == 0) out[MP_POINTWISE_CUT] = __builtin_nan("");
-        if (tail)
-            for (int i = tid; i < a.tail_stride; i += kPointwiseThreads) tail[i] = __builtin_nan("");
-        return;
-    }
-    // the key of rank m - tm among band_key(cell_r(z)) of the non-NaN z (the column is streamed from memory once per digit)
-    const uint64_t kc = wg_radix_select(n, (uint32_t)(m - tm), sel, [col](int i, uint64_t &k) {
-        const double z = col[i];
-        k = band_key(cell_r(z));
-        return !__builtin_isnan(z);
-    });
-    if (tid == 0) {
-        sel.count = 0;
-        out[MP_POINTWISE_CUT] = band_value(kc);
-    }
-    __syncthreads();
-    // the values above the cut, packed (in no particular order: they are sorted below); fewer than tm by the choice of the cut
-    for (int base = wave * 64; base < n; base += kPointwiseThreads) {
-        const int i = base + lane;
-        const double z = i < n ? col[i] : __builtin_nan("");
-        const uint64_t k = band_key(cell_r(z));
-        const bool keep = !__builtin_isnan(z) && k > kc;
-        const uint32_t slot = wave_pack_slot(keep, &sel.count);
-        if (keep && slot < (uint32_t)tm) keys[slot] = k;
-    }
-    __syncthreads();
-    const int above = min((int)sel.count, tm);
-    int slots = 1;                                          // the power of two that holds the tm entries
-    while (slots < tm) slots <<= 1;
-    for (int i = above + tid; i < slots; i += kPointwiseThreads) keys[i] = i < tm ? kc : ~0ull;   // copies of the cut, then padding that sorts last
-    __syncthreads();
-    for (int k = 2; k <= slots; k <<= 1)
-        for (int d = k >> 1; d > 0; d >>= 1) {
-            for (int i = tid; i < slots; i += kPointwiseThreads) {
-                const int l = i ^ d;
-                if (l > i) {
-                    const uint64_t x = keys[i], y = keys[l];
-                    if (((i & k) == 0) ? x > y : x < y) { keys[i] = y; keys[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    if (tail)
-        for (int i = tid; i < a.tail_stride; i += kPointwiseThreads) tail[i] = i < tm ? band_value(keys[i]) : __builtin_nan("");
+    // the candidates are the non-NaN z, their keys band_key(cell_r(z))
+    wg_tail_select((int)a.n, sel, keys, a.obs + (size_t)j * MP_POINTWISE_N + MP_POINTWISE_CUT,
+                   a.tail ? a.tail + (size_t)j * (size_t)a.tail_stride : nullptr, a.tail_stride, [col](int i, uint64_t &k) {
+                       const double z = col[i];
+                       k = band_key(cell_r(z));
+                       return !__builtin_isnan(z);
+                   });
 }
 
 __global__ __launch_bounds__(kPointwiseThreads) void pointwise_reduce_kernel(const PointwiseColsArgs a) {

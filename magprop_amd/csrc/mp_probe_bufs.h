@@ -1,6 +1,6 @@
 // mp_probe_bufs.h — test infrastructure only: the device copies of one call of a probe library (mp_probe.hip, mp_probe_select.hip,
 // mp_probe_acf.hip, mp_probe_post.hip, mp_probe_derive.hip, mp_probe_pointwise.hip, mp_probe_commit.hip, mp_probe_flows.hip,
-// mp_probe_dense.hip, mp_probe_libm.hip, mp_probe_smc.hip, mp_probe_ladder.hip, mp_probe_reservoir.hip, mp_probe_bridge.hip, mp_probe_simulate.hip).  Nothing here is part of libmagprop_amd.so.
+// mp_probe_dense.hip, mp_probe_libm.hip, mp_probe_smc.hip, mp_probe_ladder.hip, mp_probe_reservoir.hip, mp_probe_bridge.hip, mp_probe_simulate.hip, mp_probe_reweight.hip).  Nothing here is part of libmagprop_amd.so.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // mp_summaries.cpp — the summaries of model curves over host rows of parameters (mp_model_lc, mp_model_band*, mp_model_derived,
-// mp_model_flows, mp_model_flow_band, mp_model_pointwise, mp_simulate).  Kernels: mp_band.hip, mp_derive.hip, mp_flows.hip,
-// mp_pointwise.hip, mp_simulate.hip.
+// mp_model_flows, mp_model_flow_band, mp_model_pointwise, mp_model_reweight, mp_simulate).  Kernels: mp_band.hip, mp_derive.hip,
+// mp_flows.hip, mp_pointwise.hip, mp_reweight.hip, mp_simulate.hip.
 //
 // First what the entries share: the curve pass, which builds the curves of the rows on the device chunk by chunk and hands every
 // chunk to the entry's own kernels and copies, and the band of curve matrices.  Then the entries, each on the handle's first
@@ -10,10 +10,11 @@
 #include "mp_flows.h"
 #include "mp_host.h"
 #include "mp_pointwise.h"
+#include "mp_reweight.h"
 #include "mp_simulate.h"
 
 // ---------------------------------------------------------------- the curve pass
-// What mp_model_lc, mp_model_band, mp_model_derived, mp_model_pointwise, mp_simulate, mp_model_flows and mp_model_flow_band share: the curves of host rows pars[n][ndim], built on
+// What mp_model_lc, mp_model_band, mp_model_derived, mp_model_pointwise, mp_model_reweight, mp_simulate, mp_model_flows and mp_model_flow_band share: the curves of host rows pars[n][ndim], built on
 // the device chunk by chunk and handed to the caller's own kernels and copies.  (The caller holds the evaluator, has validated its
 // arguments and has ensured its own workspaces.)
 // a set of curves: bit i is curve i of Ltot, Lprop, Ldip, Mdisc, omega
@@ -382,6 +383,87 @@ int mp_model_pointwise(mp_handle *h, const double *pars, int64_t n, int ndim, in
         if (ce == hipSuccess && tail_out) ce = hipMemcpyAsync(tail_out, ev->w_pw_tail.p, sizeof(double) * n_obs * tlen, hipMemcpyDeviceToHost, k.st);
         if (ce == hipSuccess && z_out) ce = hipMemcpyAsync(z_out, ev->w_pw_z.p, sizeof(double) * n_obs * nn, hipMemcpyDeviceToHost, k.st);
         if (ce != hipSuccess) return fail(MP_EHIP, "mp_model_pointwise: copy failed: %s", hipGetErrorString(ce));
+        return (int)MP_OK;
+    });
+}
+
+// The rows go through the device in chunks of n_simd rows as in mp_model_pointwise, with Ltot alone: every chunk's curve launch is
+// followed by the launch that sums its rows' differences into columns [lo, lo + cnt) of lw[n_alt][n].  The alternatives and the
+// observation weights go up once, inside the pass (so that every failure behind their enqueue synchronises the stream, as
+// curve_pass promises); the select and reduce kernels run once behind the last chunk.
+int mp_model_reweight(mp_handle *h, const double *pars, int64_t n, int ndim, int physical, int ds_id, int n_alt,
+                      const int32_t *kind, const double *alt, const double *obs_w, double *lw_out, double *alt_out,
+                      double *tail_out, int32_t *status_out, int64_t *n_used) {
+    // (the sizes and the alternatives first: they can be judged without a handle)
+    if (n < 1 || n > MP_POINTWISE_MAX_SAMPLES)
+        return fail(MP_EINVAL, "mp_model_reweight: n must be 1..%d (MP_POINTWISE_MAX_SAMPLES), got %lld", MP_POINTWISE_MAX_SAMPLES, (long long)n);
+    if (ndim < 6 || ndim > MP_MAX_NDIM) return fail(MP_EINVAL, "mp_model_reweight: ndim must be 6..9, got %d", ndim);
+    if (ds_id < 0 || ds_id >= MP_MAX_DATASETS) return fail(MP_EINVAL, "mp_model_reweight: ds_id %d out of range", ds_id);
+    if (n_alt < 1 || n_alt > MP_REWEIGHT_MAX_ALT)
+        return fail(MP_EINVAL, "mp_model_reweight: n_alt must be 1..%d (MP_REWEIGHT_MAX_ALT), got %d", MP_REWEIGHT_MAX_ALT, n_alt);
+    if (!h || !pars || !kind || !alt || !alt_out) return fail(MP_EINVAL, "mp_model_reweight: NULL argument");
+    const int bad = mp::reweight_bad_alternative(n_alt, kind, alt);
+    if (bad >= 0)
+        return fail(MP_EINVAL, "mp_model_reweight: alternative %d (kind %d, scale %g, jitter %g, nu %g) is not a Gaussian or Student-t with "
+                    "finite scale > 0, jitter >= 0 and (Student-t) nu > 0", bad, (int)kind[bad], alt[3 * bad], alt[3 * bad + 1], alt[3 * bad + 2]);
+    Evaluator *ev = h->first();
+    Held held(h, ev);
+    if (!ev->ds[ds_id].set) return fail(MP_ESTATE, "mp_model_reweight: refers to unset dataset %d", ds_id);
+    const mp::DsDesc &dd = ev->desc[(size_t)ds_id];
+    const size_t nn = (size_t)n, n_obs = (size_t)dd.n_obs, na = (size_t)n_alt;
+    if (obs_w) {
+        const int64_t bw = mp::reweight_bad_weight(obs_w, (int64_t)(na * n_obs));
+        if (bw >= 0)
+            return fail(MP_EINVAL, "mp_model_reweight: obs_w[%lld][%lld] = %g is not finite and >= 0", (long long)(bw / (int64_t)n_obs),
+                        (long long)(bw % (int64_t)n_obs), obs_w[bw]);
+    }
+    const size_t chunk = (size_t)std::min<int64_t>(n, std::max(1, ev->sh.n_simd));
+    const size_t tlen = (size_t)mp::pointwise_tail_len(n);
+    int rc;
+    if ((rc = ev->w_rw_lw.ensure(na * nn)) || (rc = ev->w_rw_out.ensure(na * MP_REWEIGHT_N)) || (rc = ev->w_rw_tail.ensure(na * tlen)) ||
+        (rc = ev->w_rw_alt.ensure(na * (3 + n_obs))) || (rc = ev->w_rw_kind.ensure(na)))
+        return rc;
+    double *d_w = obs_w ? ev->w_rw_alt.p + 3 * na : nullptr;
+    const mp::PointwiseData pd{ev->d_obs_g.p + dd.obs_off, ev->d_obs_dx.p + dd.obs_off, ev->d_obs_idt.p + dd.obs_off,
+                               ev->d_obs_y.p + dd.obs_off, ev->d_obs_yerr.p + dd.obs_off, dd.n_obs};
+    return curve_pass(ev, pars, nn, ndim, physical, kCurveLtot, chunk, status_out, n_used, [&](const CurveChunk &k) {
+        if (k.lo == 0) {                          // the tables go up once, behind the first curve launch and before the first row launch
+            hipError_t ue = hipMemcpyAsync(ev->w_rw_kind.p, kind, sizeof(int32_t) * na, hipMemcpyHostToDevice, k.st);
+            if (ue == hipSuccess) ue = hipMemcpyAsync(ev->w_rw_alt.p, alt, sizeof(double) * 3 * na, hipMemcpyHostToDevice, k.st);
+            if (ue == hipSuccess && obs_w) ue = hipMemcpyAsync(d_w, obs_w, sizeof(double) * na * n_obs, hipMemcpyHostToDevice, k.st);
+            if (ue != hipSuccess) return fail(MP_EHIP, "mp_model_reweight: copy failed: %s", hipGetErrorString(ue));
+        }
+        mp::ReweightRowsArgs c{};
+        c.ltot = k.curve[0];                      // (the rows of walkers that did not finish are not read)
+        c.status = k.status;
+        c.d = pd;
+        c.kind = ev->w_rw_kind.p;
+        c.alt = ev->w_rw_alt.p;
+        c.obs_w = d_w;
+        c.lw = ev->w_rw_lw.p;
+        c.n = n;
+        c.lo = (int64_t)k.lo;
+        c.cnt = (int32_t)k.cnt;
+        c.n_grid = (int32_t)ev->tgrid.size();
+        c.n_alt = n_alt;
+        int e = mp::launch_reweight_rows(c, (void *)k.st);
+        if (e) return fail(MP_EHIP, "reweight rows kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        if (k.lo + k.cnt < nn) return (int)MP_OK;
+        // behind the last chunk
+        mp::ReweightColsArgs r{};
+        r.lw = ev->w_rw_lw.p;
+        r.out = ev->w_rw_out.p;
+        r.tail = ev->w_rw_tail.p;
+        r.n = n;
+        r.n_alt = n_alt;
+        r.tail_stride = (int32_t)tlen;
+        e = mp::launch_reweight_select(r, (void *)k.st);
+        if (!e) e = mp::launch_reweight_reduce(r, (void *)k.st);
+        if (e) return fail(MP_EHIP, "reweight reduction kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        hipError_t ce = hipMemcpyAsync(alt_out, ev->w_rw_out.p, sizeof(double) * na * MP_REWEIGHT_N, hipMemcpyDeviceToHost, k.st);
+        if (ce == hipSuccess && tail_out) ce = hipMemcpyAsync(tail_out, ev->w_rw_tail.p, sizeof(double) * na * tlen, hipMemcpyDeviceToHost, k.st);
+        if (ce == hipSuccess && lw_out) ce = hipMemcpyAsync(lw_out, ev->w_rw_lw.p, sizeof(double) * na * nn, hipMemcpyDeviceToHost, k.st);
+        if (ce != hipSuccess) return fail(MP_EHIP, "mp_model_reweight: copy failed: %s", hipGetErrorString(ce));
         return (int)MP_OK;
     });
 }

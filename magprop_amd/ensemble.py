@@ -474,7 +474,7 @@ class EnsembleSampler:
         """Turn the sample reservoir on (empty, taking samples from `discard` steps from now on), or off with size=None: per
         ensemble a uniform random subset of `size` of the run's samples (all of them while fewer were seen), kept on the device
         with their lnprob, step and walker, so that a store=False run ends with posterior samples (get_samples, and source=
-        "reservoir" of get_model_band, get_derived, get_flows, get_flow_band and get_pointwise).  seed=None derives the
+        "reservoir" of get_model_band, get_derived, get_flows, get_flow_band, get_pointwise and get_reweight).  seed=None derives the
         monitor's seed from the sampler's; give two runs different seeds to merge their reservoirs (magprop_amd.reservoir.merge).
         While it is on, set_positions (run_mcmc with pos) restarts it and the walker-sharded entry points refuse."""
         if size is None:
@@ -560,6 +560,16 @@ class EnsembleSampler:
         synth.model_pointwise / mcmc_eqns.model_pointwise.  source="reservoir": as in get_model_band."""
         rows = self._summary_rows("get_pointwise", discard, thin, ensemble, source)
         return summaries.pointwise(summaries.on(self.handle, int(ensemble), self._times[int(ensemble)]), rows)
+
+    def get_reweight(self, alternatives, discard=0, thin=1, ensemble=0, source="chain"):
+        """Importance reweighting of the stored chain to other error models and data subsets: the log importance weights of the
+        rows chain[discard::thin, ensemble's walkers] under every alternative (magprop_amd.reweight.gaussian / student_t)
+        against group `ensemble`'s dataset, per-observation weights in the order the dataset was given, summed on this
+        sampler's handle (mp_model_reweight).  Returns what synth.model_reweight returns; reweight.weights(lw, k) are the
+        weights= of get_model_band and get_flow_band for the same selection.  The selection is capped like get_model_band's.
+        source="reservoir": as in get_model_band."""
+        rows = self._summary_rows("get_reweight", discard, thin, ensemble, source)
+        return summaries.reweight(summaries.on(self.handle, int(ensemble), self._times[int(ensemble)]), rows, alternatives)
 
     def get_autocorr_time(self, c=5.0, tol=50, quiet=False, device=False):
         """emcee's default (quiet=False) raises when the chain is shorter than tol autocorrelation times; the

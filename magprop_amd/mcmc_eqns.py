@@ -156,3 +156,10 @@ def model_pointwise(samples, data, GRBtype, custom_lims=None, device=-1, cells=F
     ``synth.model_pointwise`` returns; two models fitted to the same ``data`` (6 against 7 parameters, say) are held against
     each other with pointwise.compare(a["loo"], b["loo"])."""
     return summaries.pointwise(_source(GRBtype, custom_lims, device, data), samples, cells, width=(6, 9))
+
+
+def model_reweight(samples, data, GRBtype, alternatives, custom_lims=None, device=-1):
+    """Importance reweighting of a fit of the library model on the light curve ``data`` (columns t, Lum50, Lum50err) to other
+    error models and data subsets, over the rows of `samples` (n, 6..9) in the sampler coordinates of ``lnprob``; per-observation
+    weights and leave_out masks are in the order of data["t"].  What ``synth.model_reweight`` returns."""
+    return summaries.reweight(_source(GRBtype, custom_lims, device, data), samples, alternatives, width=(6, 9))

@@ -1,5 +1,6 @@
 """The summaries of model curves over a set of parameter rows, each one path from the rows to the result: the light-curve band,
-the derived quantities, the flows, the flow band, the pointwise scores and the simulated light curves.
+the derived quantities, the flows, the flow band, the pointwise scores, the importance reweighting and the simulated light
+curves.
 
 Every front end (synth, mcmc_eqns, EnsembleSampler, NestedSampler) hands its rows and the request to one function here, together
 with its *source*: a function of the rows' width that returns a context manager yielding (handle, dataset slot, times) -- the
@@ -16,6 +17,7 @@ from . import _capi
 from . import derived as _derived
 from . import flows as _flows
 from . import pointwise as _pointwise
+from . import reweight as _reweight
 
 
 def on(handle, ds_id=0, x=None):
@@ -128,3 +130,21 @@ def pointwise(source, samples, cells=False, width=None):
     if cells:
         out["z"] = z
     return out
+
+
+def reweight(source, samples, alternatives, width=None):
+    """{"lw", "table", "tail", "status", "n_used", "n_eff", "khat", "log_evidence_ratio", "log_evidence_ratio_err"} of
+    Handle.model_reweight(rows, ...) under the alternatives (magprop_amd.reweight.gaussian / student_t, one or a sequence) and
+    the host functions of magprop_amd.reweight: lw (n_alt, n) the log importance weights, one row of the table and of the tail
+    per alternative.  Per-observation weights and leave_out masks are in the caller's order of the source's times x; the
+    library keeps a dataset's observations in ascending time (stable) and gets them in that order."""
+    p = _rows(samples, width)
+    alts = _reweight._list(alternatives)
+    with source(p.shape[1]) as (handle, ds_id, x):
+        n_obs = handle.dataset_size(ds_id) if x is None else int(np.size(x))
+        order = None if x is None else np.argsort(np.asarray(x, dtype=np.float64), kind="stable")
+        kind, alt, obs_w = _reweight.pack(alts, n_obs, order)
+        lw, table, tail, status, used = handle.model_reweight(p, kind, alt, obs_w, ds_id=ds_id)
+    ratio, err = _reweight.log_evidence_ratio(table, alts, n_obs)
+    return {"lw": lw, "table": table, "tail": tail, "status": status, "n_used": used, "n_eff": _reweight.n_eff(table),
+            "khat": _reweight.psis(table, tail)["khat"], "log_evidence_ratio": ratio, "log_evidence_ratio_err": err}

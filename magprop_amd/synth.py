@@ -154,3 +154,14 @@ def model_pointwise(samples, x, y, yerr, device=-1, cells=False):
     pointwise.waic, "summary": pointwise.summarize}; cells=True adds "z": (n_obs, n), the standardised residuals.  The
     log-likelihood is the unnormalised lnlike term; pointwise.normalisation(yerr) per point normalises it."""
     return summaries.pointwise(_source(device, x, y, yerr), samples, cells, width=6)
+
+
+def model_reweight(samples, x, y, yerr, alternatives, device=-1):
+    """Importance reweighting of a fit of the synthetic model on the light curve (x, y, yerr) to other error models and data
+    subsets: per row of `samples` (sampler coordinates, as a chain stores them; up to pointwise.MAX_SAMPLES rows) and per
+    alternative (magprop_amd.reweight.gaussian / student_t, one or up to 64), the log importance weight that carries the chain
+    from lnlike = -0.5 chi^2 to the alternative likelihood, summed on the device (mp_model_reweight); per-observation weights
+    and leave_out masks are in the order of x.  Returns {"lw": (n_alt, n), "table": (n_alt, 12) of reweight.NAMES, "tail",
+    "status": (n,), "n_used", "n_eff", "khat", "log_evidence_ratio", "log_evidence_ratio_err": (n_alt,)};
+    reweight.weights(lw, k) are the weights the weights= arguments of model_band, model_derived and model_flows take."""
+    return summaries.reweight(_source(device, x, y, yerr), samples, alternatives, width=6)
